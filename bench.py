@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the PointPillars hot path (voxelise -> NMS) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of `--batch` independent frames per GPU through pp_infer_batch (each frame keeps the
@@ -9,18 +9,21 @@ reference's batch=1 semantics, train.py:219-242: no statistic is shared between 
 kernel launches) plus the async D2H of their detection records.  Workload: configs/<config>.json, synthetic
 LiDAR-shaped clouds, random-init weights of the reference architecture.
 
-Two timed regions of K steps each, both bracketed by barrier + synchronize, max over ranks:
-  * `value`            -- clouds already resident in HBM when the region starts (the contract's definition of `value`);
+A plain run times ONE region of W warm-up + K steps, bracketed by barrier + synchronize, max over ranks:
+  * `value` / `ms_per_step` -- clouds already resident in HBM when the region starts (the contract's definition of `value`).
+`--full` adds, after it, everything else the bench measures:
   * `value_host_start` -- SURVEY 8(d)'s timer, the one train.py:223-237 uses: clouds start in pinned HOST memory, their
                           H2D copies run inside the region (copy stream, double-buffered, overlapping the previous pass),
-                          the region ends when the last detection record is on the host.
+                          the region ends when the last detection record is on the host (a second region of K steps);
+  * `roofline` -- dominant conv kernel timed with HIP events on its launch stream inside the resident region; `frac` =
+                  EXECUTED MFMA flops / fp32-MFMA peak; per-stage HBM rooflines under `stages`;
+  * at N=1, `cpu_baseline` (the CPU oracle on the host cores) and `extras` (batch-1 latency, trained-like head bias).
 Frames are sharded by index across ranks with no data-path collective; RCCL only gathers the detection records, one
 all_gather per step inside the timed loop (stream-ordered behind the step's kernels).  Default: weak scaling, `--batch`
 frames per rank per step.
 `--global-batch G` (BASELINE config 5: G = 64) fixes the TOTAL frames per step and shards them, strong scaling.
-Rank 0 prints ONE JSON line with `roofline` (dominant conv kernel timed with HIP events on its launch stream inside
-the resident region; `frac` = EXECUTED MFMA flops / fp32-MFMA peak; per-stage HBM rooflines under `stages`) and, at
-N=1, `cpu_baseline` (the CPU oracle on the host cores) and `extras` (batch-1 latency, trained-like head bias).
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` writes, after the timed steps, the detection records of the last timed
+step (what pp_infer_batch hands its caller) as DIR/*.npy; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import glob
@@ -218,10 +221,16 @@ def main():
                     help="TOTAL frames per step, sharded by frame index over the ranks (strong scaling; BASELINE config 5: 64)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16", "fp16", "fp16s"],
                     help="MFMA operand type of convolutions, upsamplers and head (pp_set_precision); anything but fp32 prints a TAGGED line, never the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the host-start region, the roofline figures, the CPU baseline and the extras (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detection records of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-frames", type=int, default=20)
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed side measurements (stage rooflines, batch-1 latency, trained-like bias)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed side measurements (stage rooflines, batch-1 latency, trained-like bias)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -361,9 +370,14 @@ def main():
 
     for ev in pass_done:
         D.record(ev, compute)
-    elapsed, prof = timed_region(step_resident, True)
+    # the HIP events of the roofline kernel are only recorded under --full
+    elapsed, prof = timed_region(step_resident, args.full)
     mean_det = float(cnt_h[:, :, 0].float().mean())
-    elapsed_h, _ = timed_region(step_host, False)
+    # the records of the last timed step, as this rank's caller receives them (copied before a later region reuses the slots)
+    last_det, last_cnt = det_h[K - 1, :NB].clone(), cnt_h[K - 1, :NB].clone()
+    if args.full:
+        elapsed_h, _ = timed_region(step_host, False)
+    g_det = g_cnt = None
     if gatherer:
         # after the timed regions: the last step's gathered records, trimmed per rank from host-known frame counts, must hold this
         # rank's own detections at its slot (the collective really moved them)
@@ -372,10 +386,14 @@ def main():
         g_det, g_cnt = gatherer.unpack(counts, gathered[0])
         assert sum(x.shape[0] for x in g_det) == n_all
         assert torch.equal(g_cnt[rank].cpu(), cnt[(K - 1) % K, :NB].cpu()) if NB else True
+    if args.dump_outputs and rank == 0:
+        if gatherer:
+            frames = [f for r in range(world) for f in (shard.frames_for_rank(r, world, n_all) if args.global_batch > 0 else range(r * NB, (r + 1) * NB))]
+            dump_outputs(args.dump_outputs, torch.cat([x.cpu() for x in g_det]), torch.cat([x.cpu() for x in g_cnt]), frames)
+        else:
+            dump_outputs(args.dump_outputs, last_det, last_cnt, mine)
 
     if rank == 0:
-        k_ms, k_n, k_flops = prof
-        ratio = eng.executed_ratio()
         out = {
             "metric": f"point-cloud frames/sec end-to-end (voxelise→NMS), {args.config}, {world}x MI355X",  # BASELINE.json's metric (default config eight_20cm)
             "value": round(K * frames_per_step / elapsed, 3),
@@ -389,50 +407,54 @@ def main():
             "vs_baseline": None,
             "dtype": "f32" if args.precision == "fp32" else args.precision,
             "data": "synthetic",
-            "value_host_start": round(K * frames_per_step / elapsed_h, 3),
-            "ms_per_step_host_start": round(elapsed_h / K * 1e3, 4),
+            **({"value_host_start": round(K * frames_per_step / elapsed_h, 3),
+                "ms_per_step_host_start": round(elapsed_h / K * 1e3, 4)} if args.full else {}),
             "config": {"workload": f"configs/{args.config}.json, synthetic {CLOUD_DESC.get(args.config, 'LiDAR-shaped')} clouds "
                                    f"(mean {int(np.mean([c.shape[0] for c in clouds])) if clouds else 0} points, one distinct cloud per frame of a step), "
                                    "independent frames (batch=1 semantics), random-init weights (InstanceNorm backbone), AABB NMS; "
-                                   "`value`: clouds resident in HBM; `value_host_start`: clouds in pinned host memory, H2D inside the timed region (SURVEY 8(d) timer)",
+                                   "`value`: clouds resident in HBM" +
+                                   ("; `value_host_start`: clouds in pinned host memory, H2D inside the timed region (SURVEY 8(d) timer)" if args.full else ""),
                        "frames_per_step": frames_per_step, "frames_per_pass_per_gpu": min(NB, MAXB), "engine_max_batch": ENG_B,
                        "parallelism": f"frame-sharded x{world}" + (", one all_gather of detection records per step" if world > 1 else ""),
                        "global_batch": args.global_batch or None, "cls_bias": args.cls_bias, "mean_detections": mean_det},
         }
-        ach = (k_flops / (k_ms * 1e-3) / 1e12) if k_ms > 0 else 0.0
-        traffic, traffic_src = hbm_traffic(eng.dominant_kernel(), min(NB, MAXB), eng.H, eng.W)
-        kname = f"conv 3x3 s1 64->64 @ {eng.H}x{eng.W} x{min(NB, MAXB)} frames, tiling '{eng.dominant_kernel()}'"
-        if args.precision == "fp32":
-            out["roofline"] = {"bound": "mfma", "kernel": kname,
-                               "achieved": round(ach * ratio, 3), "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                               "frac": round(ach * ratio / F32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                               "avg_launch_ms": round(k_ms, 5), "launches": k_n,
-                               "algorithmic_flops_per_launch": k_flops, "executed_flops_per_launch": k_flops * ratio,
-                               "algorithmic_tflops": round(ach, 3), "algorithmic_frac": round(ach / F32_MFMA_PEAK_TFLOPS, 4),
-                               "note": "achieved / frac price the MFMA flops the kernel EXECUTES (hardware utilisation, <= 1): Winograd F(2x2,3x3) executes 4/9 of the "
-                                       "direct-convolution count, F(4x4,3x3) 1/4 -- a FASTER kernel with fewer executed flops shows a LOWER frac; "
-                                       "`algorithmic_tflops` / `algorithmic_frac` price SURVEY 8(d)'s direct-convolution flops against the same peak (> 1 for Winograd)" if ratio < 1.0 else "direct convolution: executed = algorithmic flops"}
-        else:
-            # 16-bit operands: the same layer is no longer bound by the matrix pipe.  Both floors are stated, the binding one
-            # (the larger time) is the roofline: HBM with SURVEY 8(d)'s algorithmic bytes (input read once + output written
-            # once: 2 * 4 * 64 * H * W per frame with fp32 activations, half that under fp16s), MFMA with the executed flops at the 16-bit dense peak.
-            nfr = min(NB, MAXB)
-            elem = 2 if args.precision == "fp16s" else 4  # fp16s stores its activation tensors in fp16
-            alg_bytes = 2.0 * elem * 64 * eng.H * eng.W * nfr
-            t_hbm = alg_bytes / (HBM_PEAK_GBS * 1e9) * 1e3
-            t_mfma = k_flops * ratio / (LP_MFMA_PEAK_TFLOPS * 1e12) * 1e3
-            hbm_bound = t_hbm >= t_mfma
-            gbs = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-            out["roofline"] = {"bound": "hbm" if hbm_bound else "mfma", "kernel": kname,
-                               "achieved": round(gbs, 1) if hbm_bound else round(ach * ratio, 2),
-                               "peak": HBM_PEAK_GBS if hbm_bound else LP_MFMA_PEAK_TFLOPS, "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                               "frac": round((gbs / HBM_PEAK_GBS) if hbm_bound else (ach * ratio / LP_MFMA_PEAK_TFLOPS), 4),
-                               "traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": round(k_ms, 5), "launches": k_n,
-                               "algorithmic_bytes_per_launch": alg_bytes, "executed_flops_per_launch": k_flops * ratio,
-                               "floors_ms": {"hbm_8TBps": round(t_hbm, 5), "mfma_16bit_2500TF": round(t_mfma, 5)},
-                               "mfma_frac": round(ach * ratio / LP_MFMA_PEAK_TFLOPS, 4), "hbm_frac": round(gbs / HBM_PEAK_GBS, 4),
-                               "algorithmic_tflops": round(ach, 2),  # useful (direct-convolution) flops: bf16x3 EXECUTES three MFMAs per product
-                               "note": "16-bit operand mode: floors of this layer per launch in `floors_ms`; the larger one is the bound"}
+        if args.full:
+            k_ms, k_n, k_flops = prof
+            ratio = eng.executed_ratio()
+            ach = (k_flops / (k_ms * 1e-3) / 1e12) if k_ms > 0 else 0.0
+            traffic, traffic_src = hbm_traffic(eng.dominant_kernel(), min(NB, MAXB), eng.H, eng.W)
+            kname = f"conv 3x3 s1 64->64 @ {eng.H}x{eng.W} x{min(NB, MAXB)} frames, tiling '{eng.dominant_kernel()}'"
+            if args.precision == "fp32":
+                out["roofline"] = {"bound": "mfma", "kernel": kname,
+                                   "achieved": round(ach * ratio, 3), "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                   "frac": round(ach * ratio / F32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                                   "avg_launch_ms": round(k_ms, 5), "launches": k_n,
+                                   "algorithmic_flops_per_launch": k_flops, "executed_flops_per_launch": k_flops * ratio,
+                                   "algorithmic_tflops": round(ach, 3), "algorithmic_frac": round(ach / F32_MFMA_PEAK_TFLOPS, 4),
+                                   "note": "achieved / frac price the MFMA flops the kernel EXECUTES (hardware utilisation, <= 1): Winograd F(2x2,3x3) executes 4/9 of the "
+                                           "direct-convolution count, F(4x4,3x3) 1/4 -- a FASTER kernel with fewer executed flops shows a LOWER frac; "
+                                           "`algorithmic_tflops` / `algorithmic_frac` price SURVEY 8(d)'s direct-convolution flops against the same peak (> 1 for Winograd)" if ratio < 1.0 else "direct convolution: executed = algorithmic flops"}
+            else:
+                # 16-bit operands: the same layer is no longer bound by the matrix pipe.  Both floors are stated, the binding one
+                # (the larger time) is the roofline: HBM with SURVEY 8(d)'s algorithmic bytes (input read once + output written
+                # once: 2 * 4 * 64 * H * W per frame with fp32 activations, half that under fp16s), MFMA with the executed flops at the 16-bit dense peak.
+                nfr = min(NB, MAXB)
+                elem = 2 if args.precision == "fp16s" else 4  # fp16s stores its activation tensors in fp16
+                alg_bytes = 2.0 * elem * 64 * eng.H * eng.W * nfr
+                t_hbm = alg_bytes / (HBM_PEAK_GBS * 1e9) * 1e3
+                t_mfma = k_flops * ratio / (LP_MFMA_PEAK_TFLOPS * 1e12) * 1e3
+                hbm_bound = t_hbm >= t_mfma
+                gbs = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+                out["roofline"] = {"bound": "hbm" if hbm_bound else "mfma", "kernel": kname,
+                                   "achieved": round(gbs, 1) if hbm_bound else round(ach * ratio, 2),
+                                   "peak": HBM_PEAK_GBS if hbm_bound else LP_MFMA_PEAK_TFLOPS, "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                                   "frac": round((gbs / HBM_PEAK_GBS) if hbm_bound else (ach * ratio / LP_MFMA_PEAK_TFLOPS), 4),
+                                   "traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": round(k_ms, 5), "launches": k_n,
+                                   "algorithmic_bytes_per_launch": alg_bytes, "executed_flops_per_launch": k_flops * ratio,
+                                   "floors_ms": {"hbm_8TBps": round(t_hbm, 5), "mfma_16bit_2500TF": round(t_mfma, 5)},
+                                   "mfma_frac": round(ach * ratio / LP_MFMA_PEAK_TFLOPS, 4), "hbm_frac": round(gbs / HBM_PEAK_GBS, 4),
+                                   "algorithmic_tflops": round(ach, 2),  # useful (direct-convolution) flops: bf16x3 EXECUTES three MFMAs per product
+                                   "note": "16-bit operand mode: floors of this layer per launch in `floors_ms`; the larger one is the bound"}
         if args.precision != "fp32":
             out["tagged"] = (f"reduced-precision deploy mode '{args.precision}': convolutions, upsamplers and head on 16-bit MFMA operands, fp32 accumulation, "
                              + ("fp16 activation tensors in HBM" if args.precision == "fp16s" else "fp32 activations in HBM") +
@@ -440,18 +462,38 @@ def main():
                              "the headline is the fp32 line (dtype f32); tolerance table in DESIGN.md")
         if stub or (world > 1 and os.environ.get("PP_BENCH_BACKEND", "nccl") != "nccl"):
             out["rehearsal"] = "stub engine / ranks share devices, gather over gloo: not a measurement"
-        if world == 1 and not args.no_extras and not stub:
+        if args.full and world == 1 and not args.no_extras and not stub:
             stages, whole, til = stage_rooflines(eng, clouds, min(NB, MAXB), cfg, mfma_peak=F32_MFMA_PEAK_TFLOPS if args.precision == "fp32" else LP_MFMA_PEAK_TFLOPS)
             out["roofline"]["stages"] = stages
             out["roofline"]["whole_frame"] = whole
             out["extras"] = extras(eng, eng_mod, synth, args, cfg, local, clouds, host, dev, D)
             out["extras"]["tilings"] = [L["tiling"] for L in til]
             out["roofline"]["batch1"] = out["extras"].pop("batch1_roofline")
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = cpu_baseline(synth, args.config, args.cpu_frames)
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, det, cnt, frames):
+    """--dump-outputs: the last timed step's records in global frame order -- detections.npy f32[F, rows, 9] (rows past a frame's
+    count zeroed: the caller reads only the first det_count[f, 0]), det_count.npy f64[F, 1 + PP_MAX_CLASSES] (total, then per
+    class), frame_index.npy f64[F].  Above 64 MB in all, a fixed seeded sample of the frames."""
+    det, cnt = det.cpu().numpy().astype(np.float32), cnt.cpu().numpy().astype(np.float64)
+    frames = np.asarray(frames, dtype=np.float64)
+    order = np.argsort(frames, kind="stable")
+    det, cnt, frames = det[order], cnt[order], frames[order]
+    per_frame = det[0].nbytes + cnt[0].nbytes + 8 if len(frames) else 1
+    cap = (64 << 20) // per_frame
+    if len(frames) > cap:
+        keep = np.sort(np.random.default_rng(0).choice(len(frames), cap, replace=False))
+        det, cnt, frames = det[keep], cnt[keep], frames[keep]
+    for f in range(det.shape[0]):
+        det[f, int(cnt[f, 0]):] = 0.0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("detections", det), ("det_count", cnt), ("frame_index", frames)):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def extras(eng, eng_mod, synth, args, cfg, local, clouds, host, dev, D):

@@ -8,11 +8,11 @@ O=$R/gpurun_out/r04
 mkdir -p $O
 export PP_TUNE_CACHE=$O/tune.cache
 rm -f $PP_TUNE_CACHE
-python bench.py --no-cpu-baseline --no-extras --steps 4 --warmup 2 > $O/warm.json 2> $O/warm.err
+python bench.py --full --no-cpu-baseline --no-extras --steps 4 --warmup 2 > $O/warm.json 2> $O/warm.err
 T=$(python -c "import json;print(json.load(open('$O/warm.json'))['roofline']['kernel'].split(\"'\")[1])")
 echo "roofline tiling: $T"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --no-cpu-baseline --no-extras > $O/prof.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $O/prof.json 2> $O/prof.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d $O/pmcs -- python3 $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /dev/null 2> $O/pmcs.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d $O/pmci -- python3 $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /dev/null 2> $O/pmci.err
 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmcg -- python3 $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > /dev/null 2> $O/pmcg.err
@@ -40,6 +40,6 @@ python tools/hbm_traffic.py $O/hbm_traffic.json 32 $((32 * 2 * 64 * 400 * 400 * 
 # bench.py reports the PMC traffic figure only for the source tree it was taken on: publish it before the final line
 cp $O/hbm_traffic.json $R/profiles/r04_hbm_traffic.json
 # the final line runs the launch plan the kernel trace above was taken on
-PP_TUNE_CACHE=$O/tune.cache python bench.py > $O/bench_default.json 2> $O/bench_default.err
+PP_TUNE_CACHE=$O/tune.cache python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp $(ls -t $O/prof/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
 cat $O/kernel_summary.txt | head -40; cat $O/bench_default.json
