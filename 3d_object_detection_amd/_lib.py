@@ -6,6 +6,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpp_hip.so")
 PP_MAX_CLASSES = 12
+PP_LOSS_TERMS = 21
+PP_ASSIGN_MAX_GT = 4096
 
 c_f = ctypes.c_float
 c_i32 = ctypes.c_int32
@@ -57,6 +59,10 @@ PROTOTYPES = {
     "pp_infer_frame": (ctypes.c_int, [c_p, c_p, ctypes.c_int, c_p, c_p, ctypes.c_int, c_p]),
     "pp_infer_batch": (ctypes.c_int, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, ctypes.c_int, c_p]),
     "pp_fetch_frame_tensor": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p]),
+    "pp_set_assign_thresholds": (ctypes.c_int, [c_p, c_p, c_p]),
+    "pp_assign_targets": (ctypes.c_int, [c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
+    "pp_target_loss": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p]),
+    "pp_batch_loss": (ctypes.c_int, [c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p]),
     "pp_box_decode": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p]),
     "pp_corners2d": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_p]),
     "pp_standup2d": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),

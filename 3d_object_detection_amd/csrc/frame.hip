@@ -15,6 +15,7 @@ extern "C" int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int3
     if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, "pp_infer_batch: call pp_set_anchors first");
     if (!det || !det_count || !pts_h || !n_h) return pp_fail(ctx, PP_E_ARG, "pp_infer_batch: null pointer");
     if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_infer_batch: nb exceeds cfg.max_batch");
+    ctx->last_nb = 0; // frames whose masks / head outputs the context holds (pp_batch_loss); set once the pass is enqueued
     int rc;
     // The integer stages are latency-bound at one frame per launch (a few workgroups each); with blockIdx.z =
     // frame every stage is ONE launch per group of <= PP_GROUP (32) frames: 21 launches per group instead of 21 per frame.
@@ -41,6 +42,7 @@ extern "C" int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int3
         if (b0 && (rc = pp_stage_mark(ctx, stream, PP_ST_POST))) return rc;
         if ((rc = pp_postprocess_group(ctx, b0, g, det, det_count, nms_mode, stream))) return rc;
     }
+    ctx->last_nb = nb;
     return pp_stage_mark(ctx, stream, -1);
 }
 

@@ -116,6 +116,12 @@ struct pp_ctx {
     std::vector<int> stage_id; // stage that FOLLOWS event i (-1: end of the pass)
     std::vector<hipStream_t> stage_stream; // stream event i was recorded on (an interval needs both ends on one stream)
     size_t stage_used = 0;
+    int last_nb = 0;                  // frames of the last completed pp_infer_batch / pp_infer_frame pass (pp_batch_loss reads them)
+    // ---- target assignment / loss (assign.hip): per-class IoU thresholds (pp_set_assign_thresholds; host side) and the device
+    //      workspace, allocated on the first assignment or loss call ----
+    bool asg_thr_set = false;
+    float asg_thr_m[PP_MAX_CLASSES] = {}, asg_thr_u[PP_MAX_CLASSES] = {};
+    void* asg = nullptr;
 };
 // stage ids of pp_stage_mark / pp_stage_profile_end
 enum { PP_ST_VOXELIZE = 0, PP_ST_MASK = 1, PP_ST_PFN = 2, PP_ST_CONV = 3, PP_ST_NORM = 4, PP_ST_HEAD = 5, PP_ST_POST = 6 /* filter + threshold + gather */,
@@ -148,5 +154,6 @@ int pp_pfn_pmap_group(pp_ctx* ctx, int b0, int g, hipStream_t stream);
 int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream);
 int pp_run_head_fused(pp_ctx* ctx, float* cls, float* box, float* dir, int nb, hipStream_t stream); // norm+ReLU fused in the prologue
 void pp_post_destroy(pp_ctx* ctx);
+void pp_assign_destroy(pp_ctx* ctx);
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -6,6 +6,7 @@ here computes on the CPU except the one-off geometry / anchor tables that the re
 also builds in __init__ (voxel_generator.py:6-26, anchor_assigner.py:221-298).
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -103,6 +104,7 @@ def build_anchor_tables(offset, range_diff, grid_size, voxel_size, names=None, t
 
 
 _DUMMY = {}
+_ENGINES = weakref.WeakSet()  # live engines, for callers that hold tensors but no config dict (framework.metrics.Metric())
 
 
 def _ptr(t):
@@ -193,12 +195,16 @@ class Engine:
                 raise RuntimeError("pp_create failed: " + self.lib.pp_last_error(None).decode())
             _lib.check(self.lib.pp_set_anchors(self.ctx, self.anchors_np.ctypes.data_as(ctypes.c_void_p),
                                                self.rects_np.ctypes.data_as(ctypes.c_void_p), self.A), self.ctx, "pp_set_anchors")
+        # per-class IoU thresholds of the target assignment (AnchorAssigner.__init__ reads the same entries)
+        self.set_assign_thresholds([self.class_table[n].get("matched_threshold", 0.6) for n in self.class_masks],
+                                   [self.class_table[n].get("unmatched_threshold", 0.45) for n in self.class_masks])
         self.weights_loaded = False
         self._sd = None
         self.precision = "fp32"
         if precision != "fp32":
             self.set_precision(precision)
         self._P1 = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _ENGINES.add(self)
 
     def __del__(self):
         try:
@@ -383,6 +389,83 @@ class Engine:
             _lib.check(self.lib.pp_fetch_frame_tensor(self.ctx, int(frame), kind, _ptr(out), _stream()), self.ctx, "pp_fetch_frame_tensor")
         return out
 
+    # ------------------------------------------------------------------ training targets / loss (assign.hip)
+    def _gt_args(self, gt_boxes, gt_classes, gt_offsets, nb, what):
+        """Host checks of one batch of ground truth before anything is launched: f32[G,7] / i32[G] device tensors, offsets a
+        host sequence of nb+1 non-decreasing ints from 0 to G, class ids 1 .. num_classes, G within the library's capacity."""
+        G = int(gt_boxes.shape[0]) if gt_boxes.dim() == 2 else -1
+        gt_boxes = _chk(gt_boxes, torch.float32, (G, 7), what + ": gt_boxes")
+        gt_classes = _chk(gt_classes, torch.int32, (G,), what + ": gt_classes")
+        off = [int(v) for v in gt_offsets]
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"{what}: {nb} frames, max_batch is {self.max_batch}")
+        if len(off) != nb + 1 or off[0] != 0 or off[-1] != G or any(b < a for a, b in zip(off, off[1:])):
+            raise ValueError(f"{what}: gt offsets must be {nb + 1} non-decreasing values from 0 to {G}")
+        if G > _lib.PP_ASSIGN_MAX_GT:
+            raise ValueError(f"{what}: {G} ground-truth boxes exceed the capacity {_lib.PP_ASSIGN_MAX_GT}")
+        if G and (int(gt_classes.min()) < 1 or int(gt_classes.max()) > self.cfg.num_classes):
+            raise ValueError(f"{what}: class ids must lie in 1 .. {self.cfg.num_classes}")
+        return gt_boxes, gt_classes, (ctypes.c_int32 * (nb + 1))(*off)
+
+    def set_assign_thresholds(self, matched, unmatched):
+        m = np.ascontiguousarray(matched, dtype=F32)
+        u = np.ascontiguousarray(unmatched, dtype=F32)
+        if m.shape != (self.cfg.num_classes,) or u.shape != m.shape:
+            raise ValueError("set_assign_thresholds: one matched and one unmatched threshold per class")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_set_assign_thresholds(self.ctx, m.ctypes.data_as(ctypes.c_void_p), u.ctypes.data_as(ctypes.c_void_p)),
+                       self.ctx, "pp_set_assign_thresholds")
+
+    def assign_targets(self, masks, gt_boxes, gt_classes, gt_offsets):
+        """pp_assign_targets: masks u8/bool[nb,A], ground truth of nb frames (gt_boxes f32[G,7], gt_classes i32[G] 1-based,
+        gt_offsets host ints [nb+1]) -> labels i32[nb,A], bbox_targets f32[nb,A,7], outside_w f32[nb,A], dir_targets i32[nb,A]."""
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        nb = int(m.shape[0]) if m.dim() == 2 else 0
+        m = _chk(m, torch.uint8, (nb, self.A), "assign_targets: masks")
+        gt_boxes, gt_classes, off = self._gt_args(gt_boxes, gt_classes, gt_offsets, nb, "assign_targets")
+        labels = self._t((nb, self.A), torch.int32)
+        tgt = self._t((nb, self.A, 7), torch.float32)
+        ow = self._t((nb, self.A), torch.float32)
+        dirt = self._t((nb, self.A), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_assign_targets(self.ctx, _ptr(m), _ptr(gt_boxes), _ptr(gt_classes), off, nb, _ptr(labels), _ptr(tgt),
+                                                  _ptr(ow), _ptr(dirt), _stream()), self.ctx, "pp_assign_targets")
+        return labels, tgt, ow, dirt
+
+    def target_loss(self, cls, box, dr, labels, bbox_targets, dir_targets):
+        """pp_target_loss: head outputs and targets of nb frames -> terms f64[nb, PP_LOSS_TERMS] (include/pp_hip.h).
+        box, dr, bbox_targets and dir_targets all None: the metric counts (and npos, cls_pos, cls_neg) only."""
+        nb = int(labels.shape[0]) if labels.dim() == 2 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"target_loss: {nb} frames, max_batch is {self.max_batch}")
+        cls = _chk(cls.reshape(nb, -1), torch.float32, (nb, self.A), "target_loss: cls_preds")
+        if box is None and dr is None and bbox_targets is None and dir_targets is None:
+            labels = _chk(labels, torch.int32, (nb, self.A), "target_loss: labels")
+            terms = self._t((nb, _lib.PP_LOSS_TERMS), torch.float64)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.pp_target_loss(self.ctx, _ptr(cls), None, None, _ptr(labels), None, None, nb, _ptr(terms), _stream()),
+                           self.ctx, "pp_target_loss")
+            return terms
+        box = _chk(box.reshape(nb, -1), torch.float32, (nb, self.A * 7), "target_loss: box_preds")
+        dr = _chk(dr.reshape(nb, -1), torch.float32, (nb, self.A * 2), "target_loss: dir_preds")
+        labels = _chk(labels, torch.int32, (nb, self.A), "target_loss: labels")
+        bbox_targets = _chk(bbox_targets.reshape(nb, -1), torch.float32, (nb, self.A * 7), "target_loss: bbox_targets")
+        dir_targets = _chk(dir_targets, torch.int32, (nb, self.A), "target_loss: dir_targets")
+        terms = self._t((nb, _lib.PP_LOSS_TERMS), torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_target_loss(self.ctx, _ptr(cls), _ptr(box), _ptr(dr), _ptr(labels), _ptr(bbox_targets), _ptr(dir_targets),
+                                               nb, _ptr(terms), _stream()), self.ctx, "pp_target_loss")
+        return terms
+
+    def batch_loss(self, gt_boxes, gt_classes, gt_offsets, nb):
+        """pp_batch_loss: assignment + loss for frames 0 .. nb-1 of the last infer_batch / infer_frame pass -> terms f64[nb, PP_LOSS_TERMS]."""
+        gt_boxes, gt_classes, off = self._gt_args(gt_boxes, gt_classes, gt_offsets, nb, "batch_loss")
+        terms = self._t((nb, _lib.PP_LOSS_TERMS), torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_batch_loss(self.ctx, _ptr(gt_boxes), _ptr(gt_classes), off, nb, _ptr(terms), _stream()),
+                       self.ctx, "pp_batch_loss")
+        return terms
+
     def dominant_kernel(self):
         return self.lib.pp_dominant_kernel(self.ctx).decode()
 
@@ -420,6 +503,15 @@ class Engine:
         ms, n, fl = ctypes.c_double(), ctypes.c_int32(), ctypes.c_double()
         _lib.check(self.lib.pp_profile_end(self.ctx, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)), self.ctx, "pp_profile_end")
         return ms.value, n.value, fl.value
+
+
+def engine_for_anchors(num_anchors, device):
+    """The live engine on `device` whose anchor table has `num_anchors` rows (the most recently created if several)."""
+    dev = torch.device(device)
+    found = [e for e in list(_ENGINES) if getattr(e, "ctx", None) and e.A == num_anchors and e.device.index == (dev.index or 0)]
+    if not found:
+        raise RuntimeError(f"no engine with {num_anchors} anchors on {dev}: build the network / AnchorAssigner from the config first")
+    return found[-1]
 
 
 def tuning_lib():

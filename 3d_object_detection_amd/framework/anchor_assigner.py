@@ -1,5 +1,5 @@
-"""framework.anchor_assigner.AnchorAssigner, inference half (reference anchor_assigner.py:220-335).
-Target assignment (`assign`, :337-425) is training-only and out of scope."""
+"""framework.anchor_assigner.AnchorAssigner (reference anchor_assigner.py:220-457): anchor tables, the occupied-anchor mask and
+the training targets (`assign`), all on the device (anchor_mask.hip, assign.hip)."""
 import numpy as np
 import torch
 
@@ -49,3 +49,27 @@ class AnchorAssigner:
             raise ValueError("more pillars than max_voxels")
         mask = eng.anchor_mask(co, eng.num_tensor(co.shape[0])).view(torch.bool)
         return mask if isinstance(coors, torch.Tensor) else mask.cpu().numpy()
+
+    def assign(self, gt_classes_all, gt_boxes_all, anchors_mask_all):
+        """The reference's assign (anchor_assigner.py:337-457) through pp_assign_targets: gt classes (1-based, detect_class order)
+        [G], boxes [G,7], anchor mask [A] -> labels int32[A], bbox_targets float32[A,7], bbox_outside_weights float32[A],
+        dir_cls_targets int32[A].  numpy in gives numpy out; torch tensors in give device tensors out."""
+        as_np = not isinstance(gt_boxes_all, torch.Tensor)
+        out = self.assign_batch([(gt_classes_all, gt_boxes_all)], self._dev(anchors_mask_all, torch.uint8).reshape(1, -1))
+        out = tuple(t[0] for t in out)
+        return tuple(t.cpu().numpy() for t in out) if as_np else out
+
+    def assign_batch(self, gt_list, masks):
+        """nb frames in one pp_assign_targets call: gt_list [(gt_classes [G_i], gt_boxes [G_i,7])] (numpy or torch), masks [nb,A]
+        -> device tensors labels i32[nb,A], bbox_targets f32[nb,A,7], outside weights f32[nb,A], dir targets i32[nb,A]."""
+        eng = engine_for(self._config)
+        cls = [self._dev(c, torch.int32).reshape(-1) for c, _ in gt_list]
+        box = [self._dev(b, torch.float32).reshape(-1, 7) for _, b in gt_list]
+        off = np.concatenate([[0], np.cumsum([int(c.shape[0]) for c in cls])]).tolist()
+        return eng.assign_targets(self._dev(masks, torch.uint8), torch.cat(box).contiguous(), torch.cat(cls).contiguous(), off)
+
+    def _dev(self, x, dtype):
+        eng = engine_for(self._config)
+        if isinstance(x, torch.Tensor):
+            return x.to(eng.device).to(dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).astype(torch.empty(0, dtype=dtype).numpy().dtype))).to(eng.device)

@@ -8,6 +8,8 @@
   annos_from_records(...)        device detection records -> KITTI-style annos    (inference.py:124-138,724-737)
   run_sequence(...)              clouds -> annos through pp_infer_batch, B frames per pass, one D2H per pass
   save_detections / load_detections   the `dt_info` pickle                        (train.py:264-265)
+  gt_from_annos(annos, ...)      annos -> (gt_classes, gt_boxes) as GenericDataset builds them (dataset.py:108-140, no augmentation)
+  sequence_loss(...)             validation loss and Metric over a labelled sequence: pp_infer_batch + pp_batch_loss per pass
   pointcloud2_to_points(msg)     sensor_msgs/PointCloud2 payload -> f32[N,4] on the device   (ros_node.py:55-59)
 
 Host-side glue only: the compute stays in libpp_hip.so (engine.Engine).
@@ -166,3 +168,70 @@ def pointcloud2_to_points(msg, device=None):
         _lib.check(_lib.load().pp_unpack_points(buf.data_ptr(), n, int(msg.width), int(msg.row_step), int(msg.point_step), offs, dts,
                                                 int(bool(msg.is_bigendian)), out.data_ptr(), s), None, "pp_unpack_points")
     return out
+
+
+def _box_corners_bev(boxes):
+    """center_to_corner_box2d(xy, lw, r) (box_np_ops.py:81-119): f32[N,4,2] in the reference's corner order."""
+    dims = boxes[:, [3, 4]]
+    norm = np.array([[-0.5, -0.5], [-0.5, 0.5], [0.5, 0.5], [0.5, -0.5]], dtype=dims.dtype)
+    corners = dims.reshape(-1, 1, 2) * norm.reshape(1, 4, 2)
+    s, c = np.sin(boxes[:, 6]), np.cos(boxes[:, 6])
+    corners = np.einsum('aij,jka->aik', corners, np.stack([[c, s], [-s, c]]))
+    return corners + boxes[:, [0, 1]].reshape(-1, 1, 2)
+
+
+def gt_in_range(boxes, bv_range):
+    """filter_gt_box_outside_range (box_np_ops.py:6-16): keep a box when any of its four BEV corners lies strictly inside
+    the range rectangle (points_in_convex_polygon_jit, clockwise)."""
+    x0, y0, x1, y1 = [np.asarray(v, dtype=boxes.dtype) for v in bv_range]
+    poly = np.array([[x0, y0], [x0, y1], [x1, y1], [x1, y0]], dtype=boxes.dtype)
+    vec = poly - poly[[3, 0, 1, 2]]
+    pts = _box_corners_bev(boxes).reshape(-1, 2)
+    inside = np.ones(pts.shape[0], bool)
+    for k in range(4):
+        cross = vec[k, 1] * (poly[k, 0] - pts[:, 0]) - vec[k, 0] * (poly[k, 1] - pts[:, 1])
+        inside &= cross < 0
+    return inside.reshape(-1, 4).any(1)
+
+
+def gt_from_annos(annos, detect_class, detection_range):
+    """GenericDataset.__getitem__'s ground truth without augmentation (dataset.py:108-140): class filter, 1-based ids in
+    detect_class order, float32 (x,y,z,l,w,h,r) boxes, boxes whose four BEV corners all lie outside the range dropped, then
+    limit_period(r, 0.5, 2 pi).  Returns (gt_classes i32[G], gt_boxes f32[G,7])."""
+    names = np.asarray(annos["name"])
+    keep = np.array([n in detect_class for n in names], dtype=np.bool_)
+    cls = np.array([detect_class.index(n) + 1 for n in names[keep]], dtype=np.int32)
+    boxes = np.concatenate([np.asarray(annos["location"])[keep].reshape(-1, 3), np.asarray(annos["dimensions"])[keep].reshape(-1, 3),
+                            np.asarray(annos["rotation_y"])[keep].reshape(-1, 1)], axis=1).astype(np.float32)
+    rng = np.asarray(detection_range, dtype=np.float32)[[0, 1, 3, 4]]
+    m = gt_in_range(boxes, rng)
+    boxes, cls = boxes[m], cls[m]
+    boxes[:, 6] = boxes[:, 6] - np.floor(boxes[:, 6] / (2 * np.pi) + 0.5) * (2 * np.pi)
+    return cls, boxes
+
+
+def sequence_loss(config, clouds, gts, batch=16, nms_mode=0):
+    """Validation loss over a labelled sequence: clouds (numpy f32[N,4] or .bin paths) and gts [(gt_classes, gt_boxes)] per frame
+    go through pp_infer_batch and pp_batch_loss `batch` frames at a time, one D2H of the loss terms per pass.  Returns
+    (per-frame dicts of the reference's six loss keys as floats, framework.metrics.Metric over the whole sequence)."""
+    from .framework.loss_generator import combine_terms
+    from .framework.metrics import Metric
+    eng = engine_for(config)
+    batch = max(1, min(int(batch), eng.max_batch))
+    metric = Metric(config)
+    losses = []
+    for i0 in range(0, len(clouds), batch):
+        group = []
+        for c in clouds[i0:i0 + batch]:
+            pts = read_velodyne(c) if isinstance(c, (str, os.PathLike)) else np.ascontiguousarray(c, dtype=np.float32)
+            group.append(torch.from_numpy(pts).to(eng.device, non_blocking=True))
+        nb = len(group)
+        eng.infer_batch(group, nms_mode=nms_mode)
+        g = gts[i0:i0 + nb]
+        off = np.concatenate([[0], np.cumsum([len(np.asarray(c)) for c, _ in g])]).tolist()
+        cls = torch.from_numpy(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in g])).to(eng.device)
+        box = torch.from_numpy(np.concatenate([np.asarray(b, np.float32).reshape(-1, 7) for _, b in g])).to(eng.device)
+        terms = eng.batch_loss(box, cls, off, nb).cpu().numpy()
+        losses += [combine_terms(terms[f:f + 1]) for f in range(nb)]
+        metric.update_counts(terms)
+    return losses, metric

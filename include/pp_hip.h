@@ -149,6 +149,38 @@ int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int32_t* n_h, i
  * 5 PFN rows f32[max_voxels,64] | 6 coors i32[max_voxels,3] | 7 pillar count i32[1]. */
 int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream);
 
+/* ---- training targets and loss (anchor_assigner.py:337-457, loss_generator.py:26-253, metrics.py:14-69) ----
+ * Ground truth of nb frames: gt f32[G][7] (x,y,z,l,w,h,r), gt_cls i32[G] 1-based class id in detect_class order,
+ * gt_off_h HOST i32[nb+1] (frame f owns rows gt_off_h[f] .. gt_off_h[f+1]-1; non-decreasing, gt_off_h[nb] <= PP_ASSIGN_MAX_GT).
+ * 1 <= nb <= cfg.max_batch.  Class ids outside 1 .. num_classes are the caller's error (the Python layer refuses them before any
+ * launch; the kernels treat such rows as belonging to no class).  Labels follow the reference bit for bit: per class, IoU of the
+ * near BEV boxes in float32, forced anchors (IoU == a box's maximum over inside anchors, every tie), matched / unmatched
+ * thresholds of pp_set_assign_thresholds, -1 outside the mask, 0 for every inside anchor of a class without boxes. */
+#define PP_ASSIGN_MAX_GT 4096 /* ground-truth rows per call, all frames together */
+/* per-frame terms of pp_target_loss / pp_batch_loss: [0] npos = #(label > 0); [1] loc, [2] cls_pos, [3] cls_neg, [4] dir: the
+ * reference's per-frame sums, each divided by max(npos, 1) (NormByNumPositives; not yet scaled by the loss weights or 1/B);
+ * [5 + 4*i + j]: metric count j (0 tp, 1 tn, 2 fp, 3 fn) at threshold i (0.1, 0.3, 0.5, 0.7) of sigmoid(cls), label != -1 */
+#define PP_LOSS_TERMS 21
+/* per-class matched / unmatched IoU thresholds (HOST f32[num_classes]; AnchorAssigner reads them from the class table);
+ * defaults 0.6 / 0.45.  Host-side only (no device work, no allocation).  Labels follow the reference's order: forced -> 1, else
+ * max < unmatched -> 0, else max >= matched -> 1, else -1 (so a matched threshold below the unmatched one behaves as there). */
+int pp_set_assign_thresholds(pp_ctx* ctx, const float* matched_h, const float* unmatched_h);
+/* replaces AnchorAssigner.assign (anchor_assigner.py:337-457) for nb frames at once.  mask u8[nb][A].  Outputs labels i32[nb][A],
+ * bbox_targets f32[nb][A][7], outside_w f32[nb][A], dir_targets i32[nb][A], all fully written. */
+int pp_assign_targets(pp_ctx* ctx, const uint8_t* mask, const float* gt, const int32_t* gt_cls, const int32_t* gt_off_h, int nb,
+                      int32_t* labels, float* bbox_targets, float* outside_w, int32_t* dir_targets, void* stream);
+/* replaces LossGenerator.generate + Metric.update's counts, per frame: cls f32[nb][A], box f32[nb][A][7], dir f32[nb][A][2] and the
+ * targets of pp_assign_targets -> terms f64[nb][PP_LOSS_TERMS].  Deterministic (no float atomics): two runs are bit-identical.
+ * Counts only (Metric.update): box, dir, bbox_targets and dir_targets all NULL -> npos, cls_pos, cls_neg and the 16 counts as
+ * above, loc and dir 0.  The assignment / loss workspace is allocated on the first call of the three functions below. */
+int pp_target_loss(pp_ctx* ctx, const float* cls, const float* box, const float* dir, const int32_t* labels,
+                   const float* bbox_targets, const int32_t* dir_targets, int nb, double* terms, void* stream);
+/* fused: assignment + loss for frames 0 .. nb-1 of the LAST pp_infer_batch / pp_infer_frame pass, read from the context's own
+ * anchor masks and head outputs; no [A,7] target tensor is materialised.  Same terms, bit for bit, as pp_assign_targets on the
+ * fetched masks followed by pp_target_loss on the fetched logits.  nb must not exceed the frames of that pass (PP_E_ARG);
+ * PP_E_STATE before the first pass. */
+int pp_batch_loss(pp_ctx* ctx, const float* gt, const int32_t* gt_cls, const int32_t* gt_off_h, int nb, double* terms, void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);
