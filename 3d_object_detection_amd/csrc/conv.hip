@@ -176,7 +176,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_mfma(const ConvP p)
         for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     const size_t in_plane = (size_t)p.Hin * p.Win;
-    int nchunk = (p.dbg & 16) ? 0 : p.Cin / KC;
+    int nchunk = p.Cin / KC;
     // Sparse BEV input (first conv): each staged position carries the pillar id of its cell; channels come from
     // the [P][64] PFN rows.  A workgroup whose whole halo patch is empty has an all-zero output: skip its MFMA loop.
     const bool sparse = p.pmap != nullptr;
@@ -246,13 +246,13 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_mfma(const ConvP p)
     if (nchunk > 0) PP_LOAD_CHUNK(0)
     __syncthreads(); // scl/shl visible
     if (nchunk > 0) PP_STORE_CHUNK(0, 0)
-    if (nchunk > 1 && !(p.dbg & 1)) PP_LOAD_CHUNK(1)
+    if (nchunk > 1) PP_LOAD_CHUNK(1)
     __syncthreads();
 
     for (int ch = 0; ch < nchunk; ++ch) {
         const int buf = ch & 1;
         __builtin_amdgcn_s_setprio(1);
-        if (ch + 1 < nchunk && !(p.dbg & 1)) {
+        if (ch + 1 < nchunk) {
             PP_STORE_CHUNK(ch + 1, buf ^ 1)
             if (ch + 2 < nchunk) PP_LOAD_CHUNK(ch + 2)
         }
@@ -286,12 +286,11 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_mfma(const ConvP p)
             __builtin_amdgcn_sched_barrier(0);
         });
 #undef PP_LOAD_OPS
-        if (!(p.dbg & 8)) __syncthreads();
+        __syncthreads();
     }
     __builtin_amdgcn_s_setprio(1); // epilogue
 
     // ---- epilogue ----
-    if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) gout[0] = 1.f; return; }
     const size_t out_plane = (size_t)p.Hout * p.Wout;
     float ssum[MT][4], ssq[MT][4];
 #pragma unroll
@@ -401,27 +400,9 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_mfma(const ConvP p)
 //   LDS pass, no extra barrier
 // * the OUTPUT transform is per lane too (the 16 positions of a tile are 16 accumulators of one lane)
 // ------------------------------------------------------------------------------------------
-#ifndef PP_WINO_STAMP
-#define PP_WINO_STAMP 0 // diagnostic build: s_memtime stamps around the segments of the Winograd chunk loop (tools/wino_stamp.sh)
-#endif
-#if PP_WINO_STAMP
-// stamp sums go to a caller-provided device buffer of 8 x u64 (pp_debug_set_stamp_buffer); cycles: [0] pre-steps, [1] steps, [2] barrier, [3] epilogue+tile setup, [4] chunks, [5] tiles
-#define WN_STAMP(VAR) { __builtin_amdgcn_sched_barrier(0); VAR = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); }
-#else
-#define WN_STAMP(VAR)
-#endif
-#ifndef PP_WINO_PER
-#define PP_WINO_PER 2 // minimum LDS write pieces per MFMA step of the staging pipeline (2: +0.3 % over 1, 4: -1.5 %)
-#endif
-#ifndef PP_WINO_AD
-#define PP_WINO_AD 6 // steps the A-operand LDS reads run ahead of their MFMA pair
-#endif
-#ifndef PP_WINO_PRIO
-#define PP_WINO_PRIO 1 // s_setprio level of the NON-MFMA segments (chunk opening, epilogue, tile prologue) of the Winograd loop (0: off)
-#endif
-#ifndef PP_WINO_DIAG
-#define PP_WINO_DIAG 0 // timing-only ablations of the Winograd loop (wrong results): 1 no transform, 2 no raw reads, 4 no A reads, 8 no MFMA
-#endif
+constexpr int WINO_PER = 2;  // minimum LDS write pieces per MFMA step of the staging pipeline (2: +0.3 % over 1, 4: -1.5 %)
+constexpr int WINO_AD = 6;   // steps the A-operand LDS reads run ahead of their MFMA pair
+constexpr int WINO_PRIO = 1; // s_setprio level of the NON-MFMA segments (chunk opening, epilogue, tile prologue) of the Winograd loop
 template <int TWT, int WM, int WN, int BTX, int KC>
 struct WinoCfg {
     static constexpr int THT = 16 / TWT;
@@ -548,26 +529,15 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfm
         _Pragma("unroll") for (int r = 0; r < C::PR; ++r) WN_LOAD_X(CH, r)                       \
         WN_LOAD_W(CH)                                                                            \
     }
-    // timing experiment (PP_CONV_DBG bits 8..14): delay the second workgroup of every CU by n x 512 cycles so the two
-    // resident workgroups run out of phase (staging of one under the MFMA phase of the other)
-    if ((p.dbg >> 8) && blockIdx.x >= (gridDim.x >> 1))
-        for (int i = 0; i < ((p.dbg >> 8) & 0x7F); ++i) __builtin_amdgcn_s_sleep(8);
-#if PP_WINO_STAMP
-    unsigned long long sum_pre_ = 0, sum_steps_ = 0, sum_bar_ = 0, sum_epi_ = 0, n_chunks_ = 0, n_tiles_ = 0, sum_e1_ = 0, sum_pro_ = 0;
-#endif
     int cur_frame = -1;
     {
         const int lin0 = xk * per + xj;
         if (lin0 < lin_end) {
             set_load_tile(lin0);
-            if (!(p.dbg & 1)) WN_LOAD_CHUNK(0)
+            WN_LOAD_CHUNK(0)
         }
     }
     for (int lin = xk * per + xj; lin < lin_end; lin += nloc) {
-#if PP_WINO_STAMP
-    unsigned long long sp0_ = 0;
-    WN_STAMP(sp0_)
-#endif
     BlockId bid;
     bid.y = lin % ncb;
     bid.x = (lin / ncb) % ntile;
@@ -672,34 +642,27 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfm
     constexpr int NPIECE = C::PR * KC + C::WR;                       // LDS write pieces of one chunk
     constexpr int LOAD_STEPS = C::PR + 1;                            // re-issue: one x row or the weights per step
     constexpr int PER_MIN = (NPIECE + (NSTEP - LOAD_STEPS - 1) - 1) / (NSTEP - LOAD_STEPS - 1);
-    constexpr int PER = PER_MIN > PP_WINO_PER ? PER_MIN : PP_WINO_PER; // write pieces per step (more per step = the next loads go out earlier)
+    constexpr int PER = PER_MIN > WINO_PER ? PER_MIN : WINO_PER; // write pieces per step (more per step = the next loads go out earlier)
     constexpr int WSTEPS = (NPIECE + PER - 1) / PER;
     static_assert(WSTEPS + LOAD_STEPS <= NSTEP, "staging does not fit the chunk's MFMA steps");
     // A operands run AD steps ahead of their MFMAs (a step is only 2 MFMAs = 64 cycles; LDS latency is 2-3x that)
-    constexpr int AD = PP_WINO_AD;
+    constexpr int AD = WINO_AD;
 
     // chunk 0 of this tile was requested before the previous tile's epilogue (or ahead of the loop)
     __syncthreads(); // scl / shl visible
     WN_NORM_CHUNK(0)
     pp_steps<0, NPIECE>([&](auto E) { WN_WRITE_PIECE(decltype(E)::value, 0) });
-    if (nchunk > 1 && !(p.dbg & 1)) WN_LOAD_CHUNK(1)
+    if (nchunk > 1) WN_LOAD_CHUNK(1)
     __syncthreads();
 
-#if PP_WINO_STAMP
-    { unsigned long long sx_ = 0; WN_STAMP(sx_) sum_pro_ += sx_ - sp0_; }
-#endif
     for (int ch = 0; ch < nchunk; ++ch) {
-#if PP_WINO_STAMP
-        unsigned long long st0_ = 0, st1_ = 0, st2_ = 0, st3_ = 0;
-        WN_STAMP(st0_)
-#endif
         const int buf = ch & 1;
         const float* ib = il + buf * C::LDS_IN;
         const float* wb = wl + buf * C::LDS_W;
         float draw[16], tq[2][16];
         float2 a[AD];
         float vcur, vnext;
-        if (PP_WINO_PRIO) __builtin_amdgcn_s_setprio(PP_WINO_PRIO); // the short non-MFMA segments first: back to the matrix pipe sooner
+        __builtin_amdgcn_s_setprio(WINO_PRIO); // the short non-MFMA segments first: back to the matrix pipe sooner
         WN_READ_RAW(draw, 0)
 #define WN_LOAD_A(S)                                                                             \
     {                                                                                            \
@@ -713,59 +676,39 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfm
             const int chn = ch + 1 < nchunk ? ch + 1 : ch;
             WN_NORM_CHUNK(chn)
         }
-        if constexpr (PP_WINO_DIAG & 1) {
-#pragma unroll
-            for (int q_ = 0; q_ < 16; ++q_) tq[0][q_] = draw[q_];
-        } else {
-            pp_steps<0, 16>([&](auto K) { WN_COLPASS(tq[0], draw, decltype(K)::value) });
-        }
+        pp_steps<0, 16>([&](auto K) { WN_COLPASS(tq[0], draw, decltype(K)::value) });
         vnext = WN_ROWPASS(tq[0], 0);
-        if (PP_WINO_PRIO) __builtin_amdgcn_s_setprio(0);
-        WN_STAMP(st1_)
+        __builtin_amdgcn_s_setprio(0);
         pp_steps<0, NSTEP>([&](auto S) {
             constexpr int s_ = decltype(S)::value;
             constexpr int c4 = s_ / 16, xi = s_ % 16;
             vcur = vnext;
             // next quad: raw reads at its predecessor's first step, column pass over steps 6..13
-            if constexpr (xi == 0 && c4 + 1 < NQ && !(PP_WINO_DIAG & 2)) WN_READ_RAW(draw, c4 + 1)
+            if constexpr (xi == 0 && c4 + 1 < NQ) WN_READ_RAW(draw, c4 + 1)
             if constexpr (c4 + 1 < NQ && xi >= 6 && xi < 14) {
-                if constexpr (PP_WINO_DIAG & 1) {
-                    tq[(c4 + 1) & 1][(xi - 6) * 2] = draw[(xi - 6) * 2];
-                    tq[(c4 + 1) & 1][(xi - 6) * 2 + 1] = draw[(xi - 6) * 2 + 1];
-                } else {
-                    WN_COLPASS(tq[(c4 + 1) & 1], draw, (xi - 6) * 2)
-                    WN_COLPASS(tq[(c4 + 1) & 1], draw, (xi - 6) * 2 + 1)
-                }
+                WN_COLPASS(tq[(c4 + 1) & 1], draw, (xi - 6) * 2)
+                WN_COLPASS(tq[(c4 + 1) & 1], draw, (xi - 6) * 2 + 1)
             }
             if constexpr (s_ + 1 < NSTEP) {
                 constexpr int c4n = (s_ + 1) / 16, xin = (s_ + 1) % 16;
-                vnext = (PP_WINO_DIAG & 1) ? tq[c4n & 1][xin] : WN_ROWPASS(tq[c4n & 1], xin);
+                vnext = WN_ROWPASS(tq[c4n & 1], xin);
             }
-            if constexpr (s_ + AD - 1 < NSTEP && !(PP_WINO_DIAG & 4)) WN_LOAD_A(s_ + AD - 1)
+            if constexpr (s_ + AD - 1 < NSTEP) WN_LOAD_A(s_ + AD - 1)
             // staging of chunk ch+1: LDS writes first, then the loads of chunk ch+2 into the freed registers
             if constexpr (s_ < WSTEPS) {
                 pp_steps<0, PER>([&](auto Q) { WN_WRITE_PIECE(s_ * PER + decltype(Q)::value, buf ^ 1) });
             } else if constexpr (s_ - WSTEPS < C::PR) {
-                if (ch + 2 < nchunk && !(p.dbg & 1)) WN_LOAD_X(ch + 2, s_ - WSTEPS)
+                if (ch + 2 < nchunk) WN_LOAD_X(ch + 2, s_ - WSTEPS)
             } else if constexpr (s_ - WSTEPS == C::PR) {
-                if (ch + 2 < nchunk && !(p.dbg & 1)) WN_LOAD_W(ch + 2)
+                if (ch + 2 < nchunk) WN_LOAD_W(ch + 2)
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PP_WINO_DIAG & 8) {
-                asm volatile("" ::"v"(a[s_ % AD].x), "v"(a[s_ % AD].y), "v"(vcur));
-            } else {
-                acc[0][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s_ % AD].x, vcur, acc[0][xi], 0, 0, 0);
-                acc[1][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s_ % AD].y, vcur, acc[1][xi], 0, 0, 0);
-            }
+            acc[0][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s_ % AD].x, vcur, acc[0][xi], 0, 0, 0);
+            acc[1][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s_ % AD].y, vcur, acc[1][xi], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         });
 #undef WN_LOAD_A
-        WN_STAMP(st2_)
         __syncthreads();
-#if PP_WINO_STAMP
-        WN_STAMP(st3_)
-        sum_pre_ += st1_ - st0_; sum_steps_ += st2_ - st1_; sum_bar_ += st3_ - st2_; n_chunks_ += 1; // flushed once per workgroup
-#endif
     }
 #undef WN_NORM_CHUNK
 #undef WN_WRITE_PIECE
@@ -773,17 +716,12 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfm
 #undef WN_COLPASS
 #undef WN_ROWPASS
 
-    if (PP_WINO_PRIO) __builtin_amdgcn_s_setprio(PP_WINO_PRIO);
-#if PP_WINO_STAMP
-    unsigned long long se0_ = 0;
-    WN_STAMP(se0_)
-#endif
+    __builtin_amdgcn_s_setprio(WINO_PRIO);
     if (lin + nloc < lin_end) { // next tile's first chunk: in flight during the epilogue below
         set_load_tile(lin + nloc);
-        if (!(p.dbg & 1)) WN_LOAD_CHUNK(0)
+        WN_LOAD_CHUNK(0)
     }
     // ---- epilogue: Y = A^T M A per lane, residual, store (float2 rows), statistics ----
-    if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) gout[0] = 1.f; continue; }
     const size_t out_plane = (size_t)p.Hout * p.Wout;
     float ssum[MT][4], ssq[MT][4];
     const bool pix_ok = (opx < p.Wout) && (opy < p.Hout);
@@ -882,9 +820,6 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfm
         }
     }
     }
-#if PP_WINO_STAMP
-    { unsigned long long sx_ = 0; WN_STAMP(sx_) sum_e1_ += sx_ - se0_; }
-#endif
     if (gstat) {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -914,21 +849,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfm
             atomicAdd(dst + 1, q);
         }
     }
-#if PP_WINO_STAMP
-    {
-        unsigned long long se1_ = 0;
-        WN_STAMP(se1_)
-        sum_epi_ += se1_ - se0_; n_tiles_ += 1;
-    }
-#endif
     } // tile loop
-#if PP_WINO_STAMP
-    if (tid == 0 && p.dbg_buf) {
-        atomicAdd(&p.dbg_buf[0], sum_pre_); atomicAdd(&p.dbg_buf[1], sum_steps_); atomicAdd(&p.dbg_buf[2], sum_bar_);
-        atomicAdd(&p.dbg_buf[3], sum_epi_); atomicAdd(&p.dbg_buf[4], n_chunks_); atomicAdd(&p.dbg_buf[5], n_tiles_);
-        atomicAdd(&p.dbg_buf[6], sum_e1_); atomicAdd(&p.dbg_buf[7], sum_pro_);
-    }
-#endif
 #undef WN_LOAD_X
 #undef WN_LOAD_W
 #undef WN_LOAD_CHUNK
@@ -1038,23 +959,6 @@ __device__ __forceinline__ f32x4 w4_pair_rows(float y0, float y1, float y2, floa
     return (f32x4){v0, v1, v2, v3};
 }
 
-#if defined(PP_W4_DIAG) && (PP_W4_DIAG & 32)
-#define W4_PAD ""
-#else
-#define W4_PAD "s_nop 1\n\t"
-#endif
-#ifndef PP_W4_STORE_AUX
-#define PP_W4_STORE_AUX 0 // cache-policy bits of the epilogue's output stores (experiment: 2 = nt)
-#endif
-#ifndef PP_W4_ONEGAP
-#define PP_W4_ONEGAP 0 // 1: all LDS / VMEM instructions of a step in ONE gap behind its last MFMA (tried: 872 against 890 frames/s); 0: A fragment behind the first MFMA, raw patch row behind the second, staging behind the last
-#endif
-#ifndef PP_W4_RES_EARLY
-#define PP_W4_RES_EARLY 0 // 1: the first M-tile's residual rows are requested at the top of the tile's last chunk (tried: the 16 registers held across that chunk cost spills in the epilogue, 888 vs 890 frames/s; 32 registers -- the whole first half -- spilled in the chunk loop, 750)
-#endif
-#ifndef PP_W4_DIAG
-#define PP_W4_DIAG 0 // timing-only ablations of wino4_mfma's step loop (wrong results): 1 no transform VALU, 2 no raw LDS reads, 4 no A LDS reads, 8 no MFMA, 16 no LDS writes, 32 no s_nop pad, 64 no global loads, 128 load side frozen (no advance() at the chunk top), 256 no chunk barrier
-#endif
 template <int TWT, int BTX, int KC>
 struct Wino4Cfg {
     static constexpr int WN = 4, MT = 4;
@@ -1281,10 +1185,6 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
     const int rbase = (2 * tty) * C::IWP + ttx + kq * C::CS;
     const int aoff = kq * C::BM + m * 4;
 
-    // timing experiment (PP_CONV_DBG bits 8..): stagger the workgroups of an XCD by (dbg >> 8) x 512 cycles per phase, 8 phases:
-    // all CUs run tiles of equal length in lockstep, so their epilogues' stores hit the memory system as one burst
-    if (p.dbg >> 8)
-        for (int i = 0; i < (p.dbg >> 8) * (xj & 7); ++i) __builtin_amdgcn_s_sleep(8);
     // ---------------- pipeline prologue: chunks 0 and 1 into ring slots 0 and 1, chunk 2 into the registers ----------------
     set_load_tile(lin0);
     load_aff(s_frame);
@@ -1325,9 +1225,6 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
     p12[1] = (f32x2){0.f, 0.f};
     W4_ROW_ALL(tq[0], 0)
 
-#if PP_WINO_STAMP
-    unsigned long long sum_pre_ = 0, sum_steps_ = 0, sum_bar_ = 0, sum_epi_ = 0, n_chunks_ = 0, n_tiles_ = 0, sum_p1_ = 0, sum_p2_ = 0;
-#endif
     int buf = 0;                 // ring slot of the chunk being multiplied
     bool pending = false;        // statistics of the previous tile wait in `red` for their cross-wave reduction
     double* pend_dst = nullptr;
@@ -1380,23 +1277,13 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
             float* wbw = wl + wbuf * C::LDS_W;
             // the registers hold chunk g+2 (each piece requested a whole chunk ago): its (scale, shift) and in-image mask;
             // then the load side moves on to chunk g+3, whose pieces are requested as the registers are freed
-#if PP_WINO_STAMP
-            unsigned long long st0_ = 0, st1_ = 0, st2_ = 0, st3_ = 0;
-            WN_STAMP(st0_)
-#endif
             float sc_[KC], sh_[KC];
             W4_READ_AFF(sc_, sh_, r_tab, r_c0)
             float q_mask[C::PR]; // upper clamp of the normalised value: +inf inside the image, 0 on the zero padding (v_med3_f32 does ReLU and padding in one)
 #pragma unroll
             for (int r = 0; r < C::PR; ++r) q_mask[r] = ((r_vmask >> r) & 1u) ? __builtin_inff() : 0.f;
-            if constexpr (!(PP_W4_DIAG & 128)) {
             advance();
             r_tab = s_tab; r_c0 = s_ch * KC; r_vmask = vmask;
-            }
-            // the tile's last chunk: the first half's residual rows are requested a whole chunk before the epilogue adds them
-            // (from HBM under load they took 3-6 k cycles, which the epilogue had to wait out: stamps)
-            if constexpr (PP_W4_RES_EARLY) { if (ch == nchunk - 1 && x4_map) request_res(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}); }
-            WN_STAMP(st1_)
             // One wave per SIMD issues IN ORDER and nothing of its own hides behind an fp32 MFMA (tools/issue_probe.hip): a VALU
             // instruction costs its 4 issue cycles wherever it stands and every MFMA -> VALU -> MFMA turn ~12 more; SALU 0.5 cycle;
             // the first LDS / VMEM instruction of a gap ~6.  The step = 4 MFMAs of one Winograd position and channel quad:
@@ -1406,21 +1293,19 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
             //   MFMA 3 | gap D (steps 0..23): LDS write of staging piece s + the request that refills its register
             // MFMAs with an empty gap between them share one asm statement.  A B operand is written >= 1 step before its first
             // use and the A fragments come from LDS behind hipcc's own lgkmcnt wait, so the asm MFMAs need no s_nop pad.
-            // (All memory instructions in ONE gap behind MFMA 3 -- PP_W4_ONEGAP -- measured slower, 872 against 890 frames/s.)
+            // (All memory instructions in ONE gap behind MFMA 3 measured slower, 872 against 890 frames/s.)
 // N MFMAs of one step (M-tiles I .. I+N-1) in ONE asm statement: hipcc pads every boundary between two asm statements
 // with an s_nop, so MFMAs with nothing to put between them are issued from one statement
 #define W4_ACC(I) "i"((xi * 4 + (I)) * 4), "i"((xi * 4 + (I)) * 4 + 3)
 #define W4_MFMA_1(I)                                                                             \
-            if constexpr (PP_W4_DIAG & 8) { asm volatile("" ::"v"(a[s_ % AD][I]), "v"(vcur)); }   \
-            else if constexpr (first_ && s_ < 16) {                                              \
+            if constexpr (first_ && s_ < 16) {                                                   \
                 asm volatile("v_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, 0" :: "v"(a[s_ % AD][I]), "v"(vcur), W4_ACC(I) : W4_AGPRS); \
             } else {                                                                             \
                 asm volatile("v_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" :: "v"(a[s_ % AD][I]), "v"(vcur), W4_ACC(I) : W4_AGPRS); \
             }                                                                                    \
             __builtin_amdgcn_sched_barrier(0);
 #define W4_MFMA_2(I)                                                                             \
-            if constexpr (PP_W4_DIAG & 8) { asm volatile("" ::"v"(a[s_ % AD][I]), "v"(vcur)); }   \
-            else if constexpr (first_ && s_ < 16) {                                              \
+            if constexpr (first_ && s_ < 16) {                                                   \
                 asm volatile("v_mfma_f32_16x16x4_f32 a[%c3:%c4], %0, %2, 0\n\tv_mfma_f32_16x16x4_f32 a[%c5:%c6], %1, %2, 0"                  \
                              :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(vcur), W4_ACC(I), W4_ACC((I) + 1) : W4_AGPRS); \
             } else {                                                                             \
@@ -1429,8 +1314,7 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
             }                                                                                    \
             __builtin_amdgcn_sched_barrier(0);
 #define W4_MFMA_3(I)                                                                             \
-            if constexpr (PP_W4_DIAG & 8) { asm volatile("" ::"v"(a[s_ % AD][I]), "v"(vcur)); }   \
-            else if constexpr (first_ && s_ < 16) {                                              \
+            if constexpr (first_ && s_ < 16) {                                                   \
                 asm volatile("v_mfma_f32_16x16x4_f32 a[%c4:%c5], %0, %3, 0\n\tv_mfma_f32_16x16x4_f32 a[%c6:%c7], %1, %3, 0\n\t"            \
                              "v_mfma_f32_16x16x4_f32 a[%c8:%c9], %2, %3, 0"                                                                 \
                              :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(a[s_ % AD][(I) + 2]), "v"(vcur), W4_ACC(I), W4_ACC((I) + 1), W4_ACC((I) + 2) : W4_AGPRS); \
@@ -1441,8 +1325,7 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
             }                                                                                    \
             __builtin_amdgcn_sched_barrier(0);
 #define W4_MFMA_4(I)                                                                             \
-            if constexpr (PP_W4_DIAG & 8) { asm volatile("" ::"v"(a[s_ % AD][I]), "v"(vcur)); }   \
-            else if constexpr (first_ && s_ < 16) {                                              \
+            if constexpr (first_ && s_ < 16) {                                                   \
                 asm volatile("v_mfma_f32_16x16x4_f32 a[%c5:%c6], %0, %4, 0\n\tv_mfma_f32_16x16x4_f32 a[%c7:%c8], %1, %4, 0\n\t"            \
                              "v_mfma_f32_16x16x4_f32 a[%c9:%c10], %2, %4, 0\n\tv_mfma_f32_16x16x4_f32 a[%c11:%c12], %3, %4, 0"             \
                              :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(a[s_ % AD][(I) + 2]), "v"(a[s_ % AD][(I) + 3]), "v"(vcur), \
@@ -1454,18 +1337,14 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                                 W4_ACC(I), W4_ACC((I) + 1), W4_ACC((I) + 2), W4_ACC((I) + 3) : W4_AGPRS);                                    \
             }                                                                                    \
             __builtin_amdgcn_sched_barrier(0);
-#ifdef PP_W4_ALIGN
-            asm volatile(".p2align " PP_W4_ALIGN);
-#endif
             pp_steps<0, NSTEP>([&](auto S) {
                 constexpr int s_ = decltype(S)::value;
                 constexpr int c4 = s_ / 16, xi = s_ % 16, row = s_ / 4;
-                constexpr bool gap_b = xi < 4 && !(PP_W4_DIAG & 2); // raw patch rows of the next quad
+                constexpr bool gap_b = xi < 4;                      // raw patch rows of the next quad
                 constexpr bool gap_c = (xi & 3) == 0;               // the VALU work of four steps
                 vcur = (xi & 3) == 0 ? o0[row & 1] : (xi & 3) == 3 ? o3[row & 1] : p12[row & 1][(xi & 3) - 1];
                 __builtin_amdgcn_sched_barrier(0);
                 auto gap_a_body = [&]() {   // the A fragment of step s_+AD-1 (this chunk, or the next chunk's first steps from ring slot nbuf)
-                  if constexpr (!(PP_W4_DIAG & 4)) {
                     constexpr int sa = s_ + AD - 1;
                     if constexpr (sa < NSTEP) {
                         constexpr int n4_ = sa / 16, nx_ = sa % 16;
@@ -1474,7 +1353,6 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                         constexpr int sb = sa - NSTEP, n4_ = sb / 16, nx_ = sb % 16;
                         a[sa % AD] = *reinterpret_cast<const f32x4*>(wbn + (nx_ * KC + n4_ * 4) * C::BM + aoff);
                     }
-                  }
                 };
                 // gap B (steps 0..3 of a quad): one raw patch row of the next quad (the next CHUNK's first quad from ring slot nbuf
                 // when this is the chunk's last quad)
@@ -1492,7 +1370,7 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                 auto gap_c_body = [&]() {
                     constexpr int rn = row + 1; // next patch row; & 3 inside its quad, whose column pass sits in tq[(rn / 4) & 1]
                     W4_ROW_ALL(tq[(rn / 4) & 1], rn)
-                    if constexpr (!(PP_W4_DIAG & 16)) { W4_NORM_PAIR(s_, sc_, sh_, q_mask) W4_NORM_PAIR(s_ + 2, sc_, sh_, q_mask) }
+                    W4_NORM_PAIR(s_, sc_, sh_, q_mask) W4_NORM_PAIR(s_ + 2, sc_, sh_, q_mask)
                     if constexpr (xi == 4 || xi == 8) {
                         W4_COLPASS2(tq[(c4 + 1) & 1], draw, xi - 4)
                         W4_COLPASS2(tq[(c4 + 1) & 1], draw, xi - 4 + 1)
@@ -1501,25 +1379,17 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 };
-                if constexpr (PP_W4_ONEGAP) {
-                    // ONE memory gap per step, behind its last MFMA: the first LDS / VMEM instruction after an MFMA costs a lone wave
-                    // ~6 cycles, further ones 0.5 (tools/issue_probe.hip); the four MFMAs come from one asm statement
-                    if constexpr (gap_c) { W4_MFMA_3(0) gap_c_body(); W4_MFMA_1(3) } else { W4_MFMA_4(0) }
-                    gap_a_body();
-                    if constexpr (gap_b) gap_b_body();
-                } else {
-                    W4_MFMA_1(0)
-                    gap_a_body();
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (gap_b && gap_c) { W4_MFMA_1(1) gap_b_body(); __builtin_amdgcn_sched_barrier(0); W4_MFMA_1(2) gap_c_body(); W4_MFMA_1(3) }
-                    else if constexpr (gap_b) { W4_MFMA_1(1) gap_b_body(); __builtin_amdgcn_sched_barrier(0); W4_MFMA_2(2) }
-                    else if constexpr (gap_c) { W4_MFMA_2(1) gap_c_body(); W4_MFMA_1(3) }
-                    else { W4_MFMA_3(1) }
-                }
+                W4_MFMA_1(0)
+                gap_a_body();
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (gap_b && gap_c) { W4_MFMA_1(1) gap_b_body(); __builtin_amdgcn_sched_barrier(0); W4_MFMA_1(2) gap_c_body(); W4_MFMA_1(3) }
+                else if constexpr (gap_b) { W4_MFMA_1(1) gap_b_body(); __builtin_amdgcn_sched_barrier(0); W4_MFMA_2(2) }
+                else if constexpr (gap_c) { W4_MFMA_2(1) gap_c_body(); W4_MFMA_1(3) }
+                else { W4_MFMA_3(1) }
                 // gap D: staging of chunk g+2 into ring slot wbuf, and the request that refills the register with chunk g+3's piece
                 if constexpr (s_ < NPIECE) {
-                    if constexpr (!(PP_W4_DIAG & 16)) { W4_WRITE_PIECE(s_, ibw, wbw) }
-                    if constexpr (!(PP_W4_DIAG & 64)) { W4_LOAD_PIECE(s_) }
+                    W4_WRITE_PIECE(s_, ibw, wbw)
+                    W4_LOAD_PIECE(s_)
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -1528,12 +1398,7 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
 #undef W4_MFMA_3
 #undef W4_MFMA_4
 #undef W4_ACC
-            WN_STAMP(st2_)
-            if constexpr (!(PP_W4_DIAG & 256)) __syncthreads();
-#if PP_WINO_STAMP
-            WN_STAMP(st3_)
-            sum_pre_ += st1_ - st0_; sum_steps_ += st2_ - st1_; sum_bar_ += st3_ - st2_; n_chunks_ += 1;
-#endif
+            __syncthreads();
             buf = nbuf;
             if (ch == 0 && pending) { // previous tile's statistics: every wave's partial sums are in `red` since before this barrier
                 if (tid < C::BM) {
@@ -1554,11 +1419,6 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
         for (int ch = 1; ch < nchunk; ++ch) chunk_body(std::false_type{}, ch);
 
         // ---------------- epilogue: Y = A^T M A per lane, residual, float2 row stores, statistics ----------------
-#if PP_WINO_STAMP
-        unsigned long long se0_ = 0;
-        WN_STAMP(se0_)
-#endif
-        if (!(p.dbg & 4)) {
         // an 8-pass MFMA's D needs 12 wait states before anything but the next accumulating MFMA touches it (hipcc pads nothing
         // behind an asm statement)
         asm volatile("s_nop 11" ::: W4_AGPRS);
@@ -1577,12 +1437,8 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
         // swap half their 2x2 outputs (w4_pair_rows: four v_cndmask_b32_dpp) so that the even lane owns row y and the odd lane
         // row y+1 of the pair's 4 pixels: one dwordx4 store (and one dwordx4 residual load) per lane and row instead of two dwordx2.
         f32x2 y2[2][2][4]; // [M-tile of the half][row pair][output pixel of the 2x2 tile], .x = row 2 rp, .y = row 2 rp + 1
-#if PP_WINO_STAMP
-        unsigned long long sh0_ = 0, sh1_ = 0;
-#endif
         auto transform_half = [&](auto HALF) {
             constexpr int h = decltype(HALF)::value;
-            WN_STAMP(sh0_)
             pp_steps<0, 2>([&](auto II) {
                 constexpr int ii = decltype(II)::value, i = h * 2 + ii;
                 pp_steps<0, 2>([&](auto RP) {
@@ -1598,15 +1454,10 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                     y2[ii][rp][2] = t0[1] - t0[2] - t0[3]; y2[ii][rp][3] = t1[1] - t1[2] - t1[3];
                 });
             });
-            WN_STAMP(sh1_)
-#if PP_WINO_STAMP
-            sum_p1_ += sh1_ - sh0_;
-#endif
         };
         auto finish_mt = [&](auto HALF, auto II0, auto II1, auto X4) { // M-tiles 2h+II0 .. 2h+II1-1
             constexpr int h = decltype(HALF)::value, ii0 = decltype(II0)::value, ii1 = decltype(II1)::value;
             constexpr bool x4 = decltype(X4)::value;
-            WN_STAMP(sh0_)
             f32x2 r0[2][4], r1[2][4];
             if constexpr (!x4) { // maps whose width is not a multiple of 4: two dwordx2 rows per lane, requested here
                 const __amdgpu_buffer_rsrc_t rres_ = res_desc();
@@ -1629,7 +1480,7 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                     if constexpr (x4) {
                         f32x4 v = w4_pair_rows(y_0, y_1, y_2, y_3);
                         v += rq[h][ii][r];
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b128(rout, 0u, 0, 0)), v), rout, lb0, so, PP_W4_STORE_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b128(rout, 0u, 0, 0)), v), rout, lb0, so, 0);
                         const f32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
                         const f32x2 s2 = lo + hi, q2 = __builtin_elementwise_fma(hi, hi, lo * lo);
                         ssum[r] = ok0 ? s2[0] + s2[1] : 0.f;
@@ -1656,10 +1507,6 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
                     }
                 }
             }
-            WN_STAMP(sh1_)
-#if PP_WINO_STAMP
-            sum_p2_ += sh1_ - sh0_;
-#endif
         };
         {
             using I0 = std::integral_constant<int, 0>;
@@ -1667,8 +1514,8 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
             using I2 = std::integral_constant<int, 2>;
             if (x4_map) {
                 // every residual request is >= one transform + one M-tile's finish (~3.5 k cycles) ahead of its add; 32 registers
-                // rotate through the four M-tiles' rows (PP_W4_RES_EARLY: M-tile 0's were requested at the top of the last chunk)
-                if constexpr (!PP_W4_RES_EARLY) request_res(I0{}, I0{});
+                // rotate through the four M-tiles' rows
+                request_res(I0{}, I0{});
                 request_res(I0{}, I1{});
                 transform_half(I0{});
                 finish_mt(I0{}, I0{}, I1{}, std::true_type{});
@@ -1688,18 +1535,7 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
             pending = true;
             pend_dst = p.stat_acc + fz * p.stat_fs + ((size_t)(blockIdx.x % NREP) * p.stat_C + co0) * 2;
         }
-        } // dbg & 4 (timing ablation: no epilogue)
-#if PP_WINO_STAMP
-        { unsigned long long se1_ = 0; WN_STAMP(se1_) sum_epi_ += se1_ - se0_; n_tiles_ += 1; }
-#endif
     }
-#if PP_WINO_STAMP
-    if (tid == 0 && p.dbg_buf) {
-        atomicAdd(&p.dbg_buf[0], sum_pre_); atomicAdd(&p.dbg_buf[1], sum_steps_); atomicAdd(&p.dbg_buf[2], sum_bar_);
-        atomicAdd(&p.dbg_buf[3], sum_epi_); atomicAdd(&p.dbg_buf[4], n_chunks_); atomicAdd(&p.dbg_buf[5], n_tiles_);
-        atomicAdd(&p.dbg_buf[6], sum_p1_); atomicAdd(&p.dbg_buf[7], sum_p2_);
-    }
-#endif
     if (pending) {
         __syncthreads();
         if (tid < C::BM && blockIdx.x >= 0) {
@@ -1720,310 +1556,6 @@ __global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
 #undef W4_WRITE_PIECE
 #undef W4_COLPASS2
 #undef W4_ROW_ALL
-}
-
-// ------------------------------------------------------------------------------------------
-// Winograd with the WHOLE transformed weight slab resident in LDS (160 KB per CU on gfx950):
-//   16 positions x CIN x BM floats = 128 KB for CIN*BM = 2048 (CIN 64 x 32 rows, CIN 128 x 16 rows).
-// * persistent workgroups (one per CU, 8 waves): the slab is loaded once per launch, never re-staged
-// * every wavefront is autonomous: it walks (frame, N-tile) items on its own, stages the 6 x 18 raw
-//   patch of its N-tile (16 x 4 output pixels) into a wave-private LDS slot, transforms it in registers
-//   and issues its MFMAs -- no workgroup barrier after the slab load
-// * per chunk of 4 input channels: read raw(c) -> registers, overwrite the slot with raw(c+1) (already
-//   in registers from global), issue the global loads of raw(c+2), then 16*MT*NT MFMAs
-// * InstanceNorm statistics accumulate in registers across a wave's items and are flushed per frame
-// ------------------------------------------------------------------------------------------
-template <int CIN, int MT, int NT>
-struct WresCfg {
-    static constexpr int NW = 8;             // waves per workgroup
-    static constexpr int BM = MT * 16;       // rows shared by all waves
-    static constexpr int KC = 4;
-    static constexpr int NCH = CIN / KC;
-    static constexpr int PWT = 16, PHT = 4;  // output pixels of one N-tile (8 x 2 Winograd tiles)
-    static constexpr int IW = PWT + 2, IH = PHT + 2, HALF = IW / 2;
-    static constexpr int IWP = 20;           // (2*IWP) % 32 == 8: the two tile rows use disjoint banks
-    static constexpr int CS = 144;           // >= IH*IWP, == 16 mod 32
-    static constexpr int NPOS = KC * IH * IW; // 432 raw values per chunk
-    static constexpr int PR = (NPOS + 63) / 64;
-    static constexpr int RAW_FLOATS = KC * CS;             // per N-tile slot
-    static constexpr int U_FLOATS = 16 * CIN * BM;
-    static constexpr int LDS_FLOATS = U_FLOATS + NW * NT * RAW_FLOATS + 2 * NW * CIN; // + per-wave (scale, shift)
-    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "must fit the 160 KB LDS");
-};
-
-template <int CIN, int MT, int NT>
-__global__ void __launch_bounds__(512, 2) wino_res(const ConvP p)
-{
-    using C = WresCfg<CIN, MT, NT>;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* ul = smem;                                   // [16][CIN][BM] (swizzled when BM == 32)
-    float* rawl = ul + C::U_FLOATS;                     // [NW][NT][KC][CS]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m = lane & 15, kq = lane >> 4;
-    float* scl = rawl + C::NW * NT * C::RAW_FLOATS + wave * 2 * CIN; // wave-private: waves may be on different frames
-    float* shl = scl + CIN;
-
-    const int ncb = p.Cout / C::BM;                     // row blocks
-    // XCD-aware: workgroups are dealt round-robin over the 8 XCDs, so the ncb channel blocks that stream the
-    // SAME pixels are given ids 8 apart -- they share one L2 instead of fetching the input once per XCD
-    const bool xcd_ok = gridDim.x % (8 * ncb) == 0;
-    const int xj = blockIdx.x >> 3, xk = blockIdx.x & 7;
-    const int cb = xcd_ok ? xj % ncb : blockIdx.x % ncb;
-    const int wi = xcd_ok ? xk + 8 * (xj / ncb) : blockIdx.x / ncb, nworkers = gridDim.x / ncb;
-    if (wi >= nworkers) return;
-    const int co0 = cb * C::BM;
-
-    // ---- one-off: resident slab + per-channel (scale, shift) ----
-    {
-        const f32x4* g = reinterpret_cast<const f32x4*>(p.w) + (size_t)cb * (C::U_FLOATS / 4);
-        f32x4* d = reinterpret_cast<f32x4*>(ul);
-        for (int e = tid; e < C::U_FLOATS / 4; e += 512) d[e] = g[e];
-    }
-    const int ntx = (p.Wout + C::PWT - 1) / C::PWT, nty = (p.Hout + C::PHT - 1) / C::PHT;
-    const int tiles_per_frame = ntx * nty;
-    const int total = tiles_per_frame * p.nb;
-    const size_t plane = (size_t)p.Hin * p.Win;
-    const size_t out_plane = (size_t)p.Hout * p.Wout;
-
-    float ssum[MT][4], ssq[MT][4];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { ssum[i][r] = 0.f; ssq[i][r] = 0.f; }
-    int stat_frame = -1;
-    __syncthreads(); // the resident slab is visible to every wave; no workgroup barrier after this point
-
-    auto flush_stats = [&](int frame) {
-        if (!p.stat_acc || frame < 0) return;
-        double* base = p.stat_acc + (size_t)frame * p.stat_fs + ((size_t)((blockIdx.x * 8 + wave) % NREP) * p.stat_C) * 2;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s = ssum[i][r], q = ssq[i][r];
-                s = row16_sum(s);
-                q = row16_sum(q);
-                if (m == 0) {
-                    const int row = co0 + i * 16 + kq * 4 + r;
-                    atomicAdd(base + (size_t)row * 2, (double)s);
-                    atomicAdd(base + (size_t)row * 2 + 1, (double)q);
-                }
-                ssum[i][r] = 0.f;
-                ssq[i][r] = 0.f;
-            }
-    };
-
-    int cur_pre_frame = -1;
-    const int gw = wi * C::NW + wave, gstride = nworkers * C::NW;
-    // lane constants
-    const int ttx = m & 7, tty = m >> 3;                          // tile inside the N-tile (8 x 2)
-    const int rbase = (2 * tty) * C::IWP + ttx + kq * C::CS;       // raw patch base of this lane's tile/channel
-    int aoffs[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int col = i * 16 + m;
-        aoffs[i] = kq * C::BM + ((C::BM == 32) ? (col ^ ((kq & 1) << 4)) : col);
-    }
-    float* myraw = rawl + wave * NT * C::RAW_FLOATS;
-
-    for (int it0 = gw * NT; it0 < total; it0 += gstride * NT) {
-        // ---- items of this round: NT consecutive N-tiles (same frame whenever possible) ----
-        int fr[NT], oy[NT], ox[NT];
-        bool live[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int item = it0 + j;
-            live[j] = item < total;
-            const int it = live[j] ? item : total - 1;
-            fr[j] = it / tiles_per_frame;
-            const int t = it - fr[j] * tiles_per_frame;
-            oy[j] = (t / ntx) * C::PHT;
-            ox[j] = (t % ntx) * C::PWT;
-        }
-        if (fr[0] != stat_frame) { flush_stats(stat_frame); stat_frame = fr[0]; }
-        // scale/shift of the producer's normalisation for this frame (workgroup-shared; frames change rarely)
-        if (p.pre != PRE_RAW && fr[0] != cur_pre_frame) {
-            for (int c = lane; c < CIN; c += 64) {
-                if (p.pre == PRE_STATS) {
-                    const double* pa = p.pre_acc + (size_t)fr[0] * p.pre_fs;
-                    double s = 0.0, q = 0.0;
-#pragma unroll
-                    for (int r = 0; r < NREP; ++r) { s += pa[((size_t)r * CIN + c) * 2]; q += pa[((size_t)r * CIN + c) * 2 + 1]; }
-                    const double mean = s * p.pre_inv_n;
-                    double var = q * p.pre_inv_n - mean * mean;
-                    var = var > 0.0 ? var : 0.0;
-                    const double rstd = 1.0 / sqrt(var + (double)p.eps);
-                    scl[c] = (float)rstd;
-                    shl[c] = (float)(-mean * rstd);
-                } else {
-                    scl[c] = p.pre_scale[(size_t)fr[0] * p.aff_fs + c];
-                    shl[c] = p.pre_shift[(size_t)fr[0] * p.aff_fs + c];
-                }
-            }
-            cur_pre_frame = fr[0];
-        }
-        // staging map of this round
-        int goff[NT][C::PR], loff[NT][C::PR];
-        unsigned vmask[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            vmask[j] = 0u;
-#pragma unroll
-            for (int r = 0; r < C::PR; ++r) {
-                const int pos = lane + 64 * r;
-                const int c = pos / (C::IH * C::IW);
-                const int q = pos - c * (C::IH * C::IW);
-                const int iy = q / C::IW, ix = q - iy * C::IW;
-                const int gy = oy[j] - 1 + iy, gx = ox[j] - 1 + ix;
-                const bool inb = pos < C::NPOS && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
-                goff[j][r] = inb ? (int)((size_t)c * plane) + gy * p.Win + gx : 0;
-                vmask[j] |= (inb ? 1u : 0u) << r;
-                loff[j][r] = pos < C::NPOS ? c * C::CS + iy * C::IWP + (ix & 1) * C::HALF + (ix >> 1) : -1;
-            }
-        }
-        f32x4 acc[MT][NT][16];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int x = 0; x < 16; ++x) acc[i][j][x] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-        float xv[NT][C::PR];
-#define WR_GLOAD(CH)                                                                             \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                             \
-        const float* b_ = p.in + (size_t)fr[j] * p.in_fs + (size_t)((CH) * C::KC) * plane;       \
-        _Pragma("unroll") for (int r = 0; r < C::PR; ++r) xv[j][r] = b_[goff[j][r]];             \
-    }
-#define WR_LSTORE(CH)                                                                            \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j)                                               \
-        _Pragma("unroll") for (int r = 0; r < C::PR; ++r) {                                      \
-            if (loff[j][r] >= 0) {                                                               \
-                float v_ = xv[j][r];                                                             \
-                if (p.pre != PRE_RAW) {                                                          \
-                    const int c_ = (CH) * C::KC + (lane + 64 * r) / (C::IH * C::IW);             \
-                    v_ = fmaxf(fmaf(v_, scl[c_], shl[c_]), 0.f);                                 \
-                }                                                                                \
-                myraw[j * C::RAW_FLOATS + loff[j][r]] = ((vmask[j] >> r) & 1u) ? v_ : 0.f;       \
-            }                                                                                    \
-        }
-        WR_GLOAD(0)
-        WR_LSTORE(0)
-        if (C::NCH > 1) WR_GLOAD(1)
-
-        for (int ch = 0; ch < C::NCH; ++ch) {
-            // raw(ch) -> registers, then the slot is free for raw(ch+1)
-            float d[NT][16];
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int i_ = 0; i_ < 4; ++i_)
-#pragma unroll
-                    for (int j_ = 0; j_ < 4; ++j_)
-                        d[j][i_ * 4 + j_] = myraw[j * C::RAW_FLOATS + rbase + i_ * C::IWP + (j_ & 1) * C::HALF + (j_ >> 1)];
-            if (ch + 1 < C::NCH) {
-                WR_LSTORE(ch + 1)
-                if (ch + 2 < C::NCH) WR_GLOAD(ch + 2)
-            }
-            float V[NT][16];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                float t_[16];
-#pragma unroll
-                for (int j_ = 0; j_ < 4; ++j_) {
-                    t_[0 + j_] = d[j][0 + j_] - d[j][8 + j_];
-                    t_[4 + j_] = d[j][4 + j_] + d[j][8 + j_];
-                    t_[8 + j_] = d[j][8 + j_] - d[j][4 + j_];
-                    t_[12 + j_] = d[j][4 + j_] - d[j][12 + j_];
-                }
-#pragma unroll
-                for (int a_ = 0; a_ < 4; ++a_) {
-                    V[j][a_ * 4 + 0] = t_[a_ * 4 + 0] - t_[a_ * 4 + 2];
-                    V[j][a_ * 4 + 1] = t_[a_ * 4 + 1] + t_[a_ * 4 + 2];
-                    V[j][a_ * 4 + 2] = t_[a_ * 4 + 2] - t_[a_ * 4 + 1];
-                    V[j][a_ * 4 + 3] = t_[a_ * 4 + 1] - t_[a_ * 4 + 3];
-                }
-            }
-            // 16 positions x MT x NT MFMAs, A operands AD steps ahead
-            constexpr int AD = PP_WINO_AD;
-            float a[AD][MT];
-            const float* ub = ul + (size_t)(ch * C::KC) * C::BM;
-#define WR_LOAD_A(XI)                                                                            \
-    _Pragma("unroll") for (int i = 0; i < MT; ++i) a[(XI) % AD][i] = ub[(XI) * CIN * C::BM + aoffs[i]];
-            pp_steps<0, AD - 1>([&](auto S) { WR_LOAD_A(decltype(S)::value) });
-            pp_steps<0, 16>([&](auto S) {
-                constexpr int xi = decltype(S)::value;
-                if constexpr (xi + AD - 1 < 16) WR_LOAD_A(xi + AD - 1)
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[xi % AD][i], V[j][xi], acc[i][j][xi], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-#undef WR_LOAD_A
-        }
-#undef WR_GLOAD
-#undef WR_LSTORE
-
-        // ---- epilogue of this round: Y = A^T M A, residual, store, statistics ----
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            if (!live[j]) continue;
-            if (fr[j] != stat_frame) { flush_stats(stat_frame); stat_frame = fr[j]; }
-            const int opx = ox[j] + 2 * ttx, opy = oy[j] + 2 * tty;
-            const bool pix_ok = (opx < p.Wout) && (opy < p.Hout);
-            float* gout = p.out + (size_t)fr[j] * p.out_fs;
-            const float* gres = p.res ? p.res + (size_t)fr[j] * p.res_fs : nullptr;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int row0 = co0 + i * 16 + kq * 4;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float t0[4], t1[4];
-#pragma unroll
-                    for (int a_ = 0; a_ < 4; ++a_) {
-                        const float m0 = acc[i][j][a_ * 4 + 0][r], m1 = acc[i][j][a_ * 4 + 1][r], m2 = acc[i][j][a_ * 4 + 2][r],
-                                    m3 = acc[i][j][a_ * 4 + 3][r];
-                        t0[a_] = m0 + m1 + m2;
-                        t1[a_] = m1 - m2 - m3;
-                    }
-                    float y00 = t0[0] + t0[1] + t0[2], y01 = t1[0] + t1[1] + t1[2];
-                    float y10 = t0[1] - t0[2] - t0[3], y11 = t1[1] - t1[2] - t1[3];
-                    if (pix_ok) {
-                        const size_t o = (size_t)(row0 + r) * out_plane + (size_t)opy * p.Wout + opx;
-                        const bool two_x = opx + 1 < p.Wout, two_y = opy + 1 < p.Hout;
-                        if (gres) {
-                            if (two_x) {
-                                const float2 r0 = *reinterpret_cast<const float2*>(gres + o);
-                                y00 += r0.x; y01 += r0.y;
-                                if (two_y) { const float2 r1 = *reinterpret_cast<const float2*>(gres + o + p.Wout); y10 += r1.x; y11 += r1.y; }
-                            } else {
-                                y00 += gres[o];
-                                if (two_y) y10 += gres[o + p.Wout];
-                            }
-                        }
-                        if (two_x) {
-                            *reinterpret_cast<float2*>(gout + o) = make_float2(y00, y01);
-                            if (two_y) *reinterpret_cast<float2*>(gout + o + p.Wout) = make_float2(y10, y11);
-                        } else {
-                            gout[o] = y00;
-                            if (two_y) gout[o + p.Wout] = y10;
-                        }
-                        float s_ = y00, q_ = y00 * y00;
-                        if (two_x) { s_ += y01; q_ += y01 * y01; }
-                        if (two_y) { s_ += y10; q_ += y10 * y10; if (two_x) { s_ += y11; q_ += y11 * y11; } }
-                        ssum[i][r] += s_;
-                        ssq[i][r] += q_;
-                    }
-                }
-            }
-        }
-    }
-    flush_stats(stat_frame);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2599,7 +2131,7 @@ Variant make_wino(bool roofline_layer)
     v.bm = C::BM; v.bmp = C::BMP; v.pw = C::PW; v.ph = C::PH; v.kc = KC; v.threads = C::THREADS;
     v.waves = WM * WN; v.pairs = 2 * 16;
     v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    v.wino = 1;
+    v.family = Family::Wino;
     snprintf(v.name, sizeof(v.name), "wino tw%d w%dx%d bx%d kc%d", TWT, WM, WN, BTX, KC);
     return v;
 }
@@ -2613,23 +2145,8 @@ Variant make_wino4(bool roofline_layer)
     v.bm = C::BM; v.bmp = C::BM; v.pw = C::PW; v.ph = C::PH; v.kc = KC; v.threads = C::THREADS;
     v.waves = 4; v.pairs = 4 * 16;
     v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    v.wino = 4;
+    v.family = Family::Wino4;
     snprintf(v.name, sizeof(v.name), "wino4 tw%d bx%d kc%d", TWT, BTX, KC);
-    return v;
-}
-
-template <int CIN, int MT, int NT>
-Variant make_wres()
-{
-    using C = WresCfg<CIN, MT, NT>;
-    Variant v;
-    v.kern = wino_res<CIN, MT, NT>;
-    v.bm = C::BM; v.bmp = C::BM; v.pw = C::PWT; v.ph = C::PHT; v.kc = C::KC; v.threads = 512;
-    v.waves = 8; v.pairs = MT * NT * 16;
-    v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    v.wino = 2;
-    v.cin = CIN;
-    snprintf(v.name, sizeof(v.name), "wres c%d m%d n%d", CIN, MT, NT);
     return v;
 }
 
@@ -2643,7 +2160,7 @@ Variant make_g1()
     v.bm = MT * 16; v.bmp = v.bm + ((v.bm % 32 == 0) ? 16 : 0); v.pw = NT * 16; v.ph = 1; v.kc = 4; v.threads = 512;
     v.waves = 8; v.pairs = MT * NT;
     v.lds = 0; // depends on K: set per layer
-    v.wino = 3;
+    v.family = Family::Gemm1x1;
     if (IO16) snprintf(v.name, sizeof(v.name), "g1x1 m%d n%d e%d h%d p%d", MT, NT, EPI, IO16, PREC);
     else if (PREC) snprintf(v.name, sizeof(v.name), "g1x1 m%d n%d e%d p%d", MT, NT, EPI, PREC);
     else snprintf(v.name, sizeof(v.name), "g1x1 m%d n%d e%d", MT, NT, EPI);
@@ -2784,17 +2301,22 @@ void layer_menu(int kind, int stride, int up, std::vector<Variant>& menu, int ci
         menu.push_back(make_wino4<8, 1, 8>(roofline_layer));       // 16x16 px, 8x2-tile N-tiles
         menu.push_back(make_wino4<8, 2, 8>(roofline_layer));       // 32x8 px
         if (cin % 32 == 0) wino6_menu(menu, roofline_layer);       // Winograd F(4x4,3x3), 16x16 px (wino6.hip)
-        if (cin == 64) menu.push_back(make_wres<64, 2, 1>());   // 128 KB slab: 64 ch x 32 rows
-        if (cin == 128) menu.push_back(make_wres<128, 1, 1>()); // 128 KB slab: 128 ch x 16 rows
     }
 }
 
-// wino4 strip tilings: a map that is not a multiple of the main tile (16x16 px) is covered by whole main tiles plus a right
-// strip of 4 x 64 px tiles and a bottom strip of 64 x 4 px tiles -- 100 x 100: 36 + 2 + 2 tiles instead of 49 mostly-empty ones
-static Variant& wino4_strip_v() { static Variant v = make_wino4<2, 1, 8>(false); return v; }  // 4 px wide, 64 px tall
-static Variant& wino4_strip_h() { static Variant v = make_wino4<16, 2, 8>(false); return v; } // 64 px wide, 4 px tall
-static Variant& wino6_strip_v_() { static Variant v = wino6_strip_v(); return v; }
-static Variant& wino6_strip_h_() { static Variant v = wino6_strip_h(); return v; }
+// strip tilings of wino4 / wino6 (launch_conv): a map that is not a multiple of the main tile (16x16 px) is covered by whole main
+// tiles plus a right strip of 4 x 64 px tiles and a bottom strip of 64 x 4 px tiles -- 100 x 100: 36 + 2 + 2 tiles instead of
+// 49 mostly-empty ones
+static const Variant& strip_v(Family f) // 4 px wide, 64 px tall
+{
+    static const Variant w4 = make_wino4<2, 1, 8>(false), w6 = wino6_strip_v();
+    return f == Family::Wino6 ? w6 : w4;
+}
+static const Variant& strip_h(Family f) // 64 px wide, 4 px tall
+{
+    static const Variant w4 = make_wino4<16, 2, 8>(false), w6 = wino6_strip_h();
+    return f == Family::Wino6 ? w6 : w4;
+}
 
 // cost model: wavefronts are dealt to 1024 SIMDs; a SIMD's time ~ (its wave count) x (tile pairs per wave).
 double model_cost(const Variant& v, int rows, int Hout, int Wout)
@@ -2807,15 +2329,60 @@ double model_cost(const Variant& v, int rows, int Hout, int Wout)
     return cost;
 }
 
-bool variant_ok(const Variant& v, int rows) { return (v.wino == 2 || v.wino == 4 || v.wino == 5 || v.wino == 6) ? (rows % v.bm == 0) : v.bm <= ((rows + 63) / 64) * 64; }
-// shape limits of a tiling family: wino4_mfma stores float2 rows (even output width); gemm1x1 feeds four N-tiles from one
-// dwordx4 of 4 consecutive pixels of the input plane (pixel count a multiple of 4 -- a 9 x 11 map has 99)
-// conv16 fetches its patches as aligned pixel quads and stores pixel quads (input and output width multiples of 4)
-// (gemm1x1 with a 16-bit tensor has no path for maps that are not a multiple of 4 wide)
-// wino6 works on whole 4x4 output tiles and dwordx4 rows (maps a multiple of 4 in both directions; stride 1: Hin = Hout)
-bool shape_ok(const Variant& v, int Hin, int Win, int Wout) { return !(v.wino == 6 && ((Wout & 3) || (Hin & 3))) && !(v.wino == 4 && (Wout & 1)) && !(v.wino == 3 && ((Hin * Win) & 3)) && !(v.wino == 3 && v.io16 && (Wout & 3)) && !(v.wino == 5 && ((Win & 3) || (Wout & 3))); }
+// ---- the per-family rules of the tuner and the launcher ----
+// rows: wino4, conv16 and wino6 tile whole row blocks; the others clip their last block
+bool variant_ok(const Variant& v, int rows)
+{
+    switch (v.family) {
+    case Family::Wino4:
+    case Family::Conv16:
+    case Family::Wino6: return rows % v.bm == 0;
+    default: return v.bm <= ((rows + 63) / 64) * 64;
+    }
+}
+// shape limits of a tiling family
+bool shape_ok(const Variant& v, int Hin, int Win, int Wout)
+{
+    switch (v.family) {
+    case Family::Wino4: return !(Wout & 1); // float2 row stores (even output width)
+    // gemm1x1 feeds four N-tiles from one dwordx4 of 4 consecutive pixels of the input plane (pixel count a multiple of 4 -- a
+    // 9 x 11 map has 99); with a 16-bit tensor it has no path for maps that are not a multiple of 4 wide
+    case Family::Gemm1x1: return !((Hin * Win) & 3) && !(v.io16 && (Wout & 3));
+    // conv16 fetches its patches as aligned pixel quads and stores pixel quads (input and output width multiples of 4)
+    case Family::Conv16: return !((Win & 3) || (Wout & 3));
+    // wino6 works on whole 4x4 output tiles and dwordx4 rows (maps a multiple of 4 in both directions; stride 1: Hin = Hout)
+    case Family::Wino6: return !((Wout & 3) || (Hin & 3));
+    default: return true;
+    }
+}
 // LDS bytes of a persistent 1x1 GEMM for a given K
 size_t g1_lds(const Variant& v, int K) { return ((size_t)K * v.bmp + (size_t)8 * 2 * K) * sizeof(float); }
+// LDS bytes of a launch of v on a layer with cin input channels (gemm1x1 keeps the whole [K][BM] weight slab)
+size_t layer_lds(const Variant& v, int cin) { return v.family == Family::Gemm1x1 ? g1_lds(v, cin) : v.lds; }
+// One frame per launch: the families that finalise the producer's statistics in their own prologue, instead of a norm_finalize
+// launch in front of the layer -- 14 launches of 4.7 us + a boundary each per frame at batch 1.  (Batched launches keep
+// norm_finalize: a persistent workgroup would redo the fp64 finalisation at every frame change.)
+bool finalises_in_prologue(Family f)
+{
+    switch (f) {
+    case Family::Direct:
+    case Family::Gemm1x1:
+    case Family::Wino4:
+    case Family::Wino6: return true;
+    default: return false;
+    }
+}
+// MFMA flops a tiling executes per algorithmic flop of the direct convolution
+double executed_ratio(const Variant& v)
+{
+    switch (v.family) {
+    case Family::Wino6: return 0.25;
+    case Family::Wino:
+    case Family::Wino4: return 4.0 / 9.0;
+    case Family::Conv16: return v.prec == 1 ? 3.0 : 1.0; // bf16x3: three MFMAs per product
+    default: return 1.0;
+    }
+}
 
 Variant pick_variant(int kind, int stride, int up, int rows, int Hout, int Wout, bool head9 = true)
 {
@@ -2824,7 +2391,7 @@ Variant pick_variant(int kind, int stride, int up, int rows, int Hout, int Wout,
     double best = 1e30;
     Variant bv = menu[0];
     for (const Variant& v : menu) {
-        if (!variant_ok(v, rows) || v.wino >= 2) continue; // persistent kernels are only chosen by measurement
+        if (!variant_ok(v, rows) || (v.family != Family::Direct && v.family != Family::Wino)) continue; // persistent kernels are only chosen by measurement
         const double c = model_cost(v, rows, Hout, Wout);
         if (c < best) { best = c; bv = v; }
     }
@@ -2905,7 +2472,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         }
     }
     L.rows = rows;
-    if (v.wino == 6) { // F(4x4,3x3): U = G g G^T in the order the four waves fetch their positions (wino6.hip)
+    if (v.family == Family::Wino6) { // F(4x4,3x3): U = G g G^T in the order the four waves fetch their positions (wino6.hip)
         std::vector<float> pk6;
         wino6_pack(rowsW.data(), rows, L.cin, pk6);
         if (L.w) (void)hipFree(L.w);
@@ -2914,7 +2481,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         return 0;
     }
     int taps_eff = taps;
-    if (v.wino == 1 || v.wino == 2 || v.wino == 4) { // U = G g G^T per (cout, cin), fp64 on the host; position xi = 4*a + b
+    if (v.family == Family::Wino || v.family == Family::Wino4) { // U = G g G^T per (cout, cin), fp64 on the host; position xi = 4*a + b
         static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
         std::vector<float> u((size_t)rows * L.cin * 16);
         for (size_t rc = 0; rc < (size_t)rows * L.cin; ++rc) {
@@ -2928,7 +2495,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         rowsW.swap(u);
         taps_eff = 16;
     }
-    if (v.wino == 3 && L.kind == 2) { // head under gemm1x1: rows in head_tile_row order
+    if (v.family == Family::Gemm1x1 && L.kind == 2) { // head under gemm1x1: rows in head_tile_row order
         std::vector<float> perm((size_t)96 * L.cin, 0.f);
         for (int t = 0; t < 96; ++t) {
             const int src = head_tile_row(t);
@@ -2936,7 +2503,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         }
         rowsW.swap(perm);
     }
-    if (v.wino == 5) { // conv16: [row block][cin/16][image: hi (| lo for bf16x3)][tap][k-half][BM rows][8 x 16 bit] = the LDS image of a step
+    if (v.family == Family::Conv16) { // conv16: [row block][cin/16][image: hi (| lo for bf16x3)][tap][k-half][BM rows][8 x 16 bit] = the LDS image of a step
         auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
         auto bf16f = [](uint16_t h) -> float { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };
         auto f16 = [](float f) -> uint16_t { const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }; // round to nearest even
@@ -2963,7 +2530,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         PP_HIP(hipMemcpy(L.w, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         return 0;
     }
-    if (v.wino == 3 && v.prec) { // [row block][K/16][hi|lo][k-group][BMP][4 bf16]: the byte count of the fp32 slab
+    if (v.family == Family::Gemm1x1 && v.prec) { // [row block][K/16][hi|lo][k-group][BMP][4 bf16]: the byte count of the fp32 slab
         auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
         auto bf16f = [](uint16_t h) -> float { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };
         const int nb_ = pp_div_up(rows, v.bm), nkb = L.cin / 16;
@@ -2988,7 +2555,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         PP_HIP(hipMemcpy(L.w, pk4.data(), pk4.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         return 0;
     }
-    if (v.wino == 3) { // [row block][K][BMP]
+    if (v.family == Family::Gemm1x1) { // [row block][K][BMP]
         const int nb_ = pp_div_up(rows, v.bm);
         std::vector<float> pk3((size_t)nb_ * L.cin * v.bmp, 0.f);
         for (int b = 0; b < nb_; ++b)
@@ -3002,21 +2569,6 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         PP_HIP(hipMemcpy(L.w, pk3.data(), pk3.size() * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     }
-    if (v.wino == 2) { // [row block][position][cin][BM], 16-float halves swapped on odd channels when BM == 32
-        const int nb_ = rows / v.bm;
-        std::vector<float> pk2((size_t)nb_ * 16 * L.cin * v.bm, 0.f);
-        for (int b = 0; b < nb_; ++b)
-            for (int x = 0; x < 16; ++x)
-                for (int c = 0; c < L.cin; ++c)
-                    for (int mm = 0; mm < v.bm; ++mm) {
-                        const int col = (v.bm == 32) ? (mm ^ ((c & 1) << 4)) : mm;
-                        pk2[(((size_t)b * 16 + x) * L.cin + c) * v.bm + col] = rowsW[((size_t)(b * v.bm + mm) * L.cin + c) * 16 + x];
-                    }
-        if (L.w) (void)hipFree(L.w);
-        PP_HIP(hipMalloc((void**)&L.w, pk2.size() * sizeof(float)));
-        PP_HIP(hipMemcpy(L.w, pk2.data(), pk2.size() * sizeof(float), hipMemcpyHostToDevice));
-        return 0;
-    }
     const int nblk = pp_div_up(rows, v.bm), nchunk = L.cin / v.kc;
     std::vector<float> pk((size_t)nblk * nchunk * taps_eff * v.kc * v.bmp, 0.f); // LDS image incl. row padding
     for (int b = 0; b < nblk; ++b)
@@ -3028,7 +2580,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
                         if (row >= rows) continue;
                         // Winograd image: row = [wm][m][M-tile] so a lane's two A operands are adjacent (ds_read_b64)
                         // wino4 image: row = [m][M-tile 0..3] so a lane's four A operands are one ds_read_b128
-                        const int col = (v.wino == 1) ? ((mm >> 5) * 32 + (mm & 15) * 2 + ((mm >> 4) & 1)) : (v.wino == 4) ? ((mm & 15) * 4 + (mm >> 4)) : mm;
+                        const int col = (v.family == Family::Wino) ? ((mm >> 5) * 32 + (mm & 15) * 2 + ((mm >> 4) & 1)) : (v.family == Family::Wino4) ? ((mm & 15) * 4 + (mm >> 4)) : mm;
                         pk[((((size_t)b * nchunk + ch) * taps_eff + t) * v.kc + k) * v.bmp + col] =
                             rowsW[((size_t)row * L.cin + ch * v.kc + k) * taps_eff + t];
                     }
@@ -3059,10 +2611,6 @@ __global__ void __launch_bounds__(320) norm_finalize(const double* __restrict__ 
 
 constexpr size_t STAT_FS = (size_t)24 * NREP * 320 * 2; // doubles of statistics per frame
 
-static unsigned long long* g_stamp_buf = nullptr; // diagnostic builds only
-
-static bool getenv_flag_off(const char* name) { const char* e = getenv(name); return e && e[0] == '0'; }
-
 int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, float* out, const float* res,
                 const NormRef& pre, double* stat_acc, int stat_C, int Hout, int Wout, hipStream_t stream,
                 float* out_box = nullptr, float* out_dir = nullptr, int B = 1, size_t out_fs = 0, size_t in_fs = 0,
@@ -3077,15 +2625,8 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
     p.pre = pre.mode; p.pre_acc = pre.acc; p.pre_scale = pre.scale; p.pre_shift = pre.shift;
     p.pre_inv_n = pre.inv_n; p.eps = 1e-3f;
     p.stat_acc = stat_acc; p.stat_C = stat_C;
-    p.dbg_buf = g_stamp_buf;
-    {   // diagnostic builds: PP_STAMP_CIN / PP_STAMP_RES narrow the stamped layers (input channels; 0 / 1 = without / with residual)
-        static const char* sc = getenv("PP_STAMP_CIN");
-        static const char* sr = getenv("PP_STAMP_RES");
-        if ((sc && atoi(sc) != L.cin) || (sr && (atoi(sr) != 0) != (res != nullptr))) p.dbg_buf = nullptr;
-    }
-    p.bias = (L.kind == 2 && L.var.wino == 3) ? net->head_bias_perm : net->head_bias; p.out_box = out_box; p.out_dir = out_dir;
+    p.bias = (L.kind == 2 && L.var.family == Family::Gemm1x1) ? net->head_bias_perm : net->head_bias; p.out_box = out_box; p.out_dir = out_dir;
     { const int na = ctx->cfg.num_anchor_per_loc; p.n_cls = na; p.n_box = 7 * na; p.n_rows = 10 * na; }
-    { static const char* d = getenv("PP_CONV_DBG"); p.dbg = d ? atoi(d) : 0; }
     {   // frame strides of a batched launch (every per-frame tensor is stored [B][...])
         const size_t hw = (size_t)Hout * Wout;
         p.in_fs = in_fs ? in_fs : (size_t)L.cin * Hin * Win;
@@ -3099,10 +2640,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         p.pmap_fs = (size_t)Hin * Win;
         p.feat_fs = (size_t)ctx->cfg.max_voxels * 64;
     }
-    // one frame per launch: the kernels that can finalise the producer's statistics in their prologue (conv_mfma, wino_res, gemm1x1, wino4_mfma, wino6_mfma)
-    // do so, instead of a norm_finalize launch in front of the layer -- 14 launches of 4.7 us + a boundary each per frame at batch 1.
-    // (Batched launches keep norm_finalize: a persistent workgroup would redo the fp64 finalisation at every frame change.)
-    const bool fin_in_kernel = B == 1 && (L.var.wino == 0 || L.var.wino == 2 || L.var.wino == 3 || L.var.wino == 4 || L.var.wino == 6) && !getenv_flag_off("PP_FIN_IN_KERNEL");
+    const bool fin_in_kernel = B == 1 && finalises_in_prologue(L.var.family);
     if (pre.mode == PRE_STATS && net->aff && L.cin <= 320 && !fin_in_kernel) {
         hipLaunchKernelGGL(norm_finalize, dim3(B), dim3(320), 0, stream, pre.acc, pre.fs, L.cin, pre.inv_n, p.eps, net->aff, (size_t)640);
         p.pre = PRE_AFFINE; p.pre_scale = net->aff; p.pre_shift = net->aff + 320; p.aff_fs = 640;
@@ -3110,16 +2648,15 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
     const Variant& v = L.var;
     dim3 grid(pp_div_up(Wout, v.pw) * pp_div_up(Hout, v.ph), pp_div_up(L.rows, v.bm), B);
     p.nb = B;
-    size_t lds_bytes = v.lds;
-    if (v.wino == 3 && ((Hin * Win) & 3)) return PP_E_ARG; // gemm1x1 reads pixel quads (choose_variant never offers it for such a plane)
-    if (v.wino == 3) lds_bytes = g1_lds(v, L.cin);
-    if (v.wino == 2 || v.wino == 3) { // persistent: one workgroup per CU, a multiple of the row-block count
+    const size_t lds_bytes = layer_lds(v, L.cin);
+    if (v.family == Family::Gemm1x1 && ((Hin * Win) & 3)) return PP_E_ARG; // gemm1x1 reads pixel quads (choose_variant never offers it for such a plane)
+    if (v.family == Family::Gemm1x1) { // persistent: one workgroup per CU, a multiple of the row-block count
         const int ncb = pp_div_up(L.rows, v.bm);
         int g = (net->num_cu / ncb) * ncb;
         if (g < ncb) g = ncb;
         grid = dim3(g, 1, 1);
     }
-    if (v.wino == 5) { // conv16: persistent, one 4-wave workgroup per CU, XCD-contiguous item ranges (grid a multiple of 8)
+    if (v.family == Family::Conv16) { // conv16: persistent, one 4-wave workgroup per CU, XCD-contiguous item ranges (grid a multiple of 8)
         if ((size_t)L.rows * Hout * Wout * 4 >= 0x80000000ull || (size_t)L.cin * Hin * Win * 4 >= 0x80000000ull) return PP_E_ARG; // buffer offsets are 32-bit, idle lanes park 2 GB out
         if (p.pre == PRE_STATS) return pp_fail(ctx, PP_E_STATE, "conv16: the producer's statistics must be finalised to (scale, shift)");
         if ((Win & 3) || (Wout & 3) || (L.cin & 15) || (L.rows % v.bm)) return PP_E_ARG;
@@ -3130,7 +2667,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         g = (g + 7) & ~7;
         grid = dim3(g, 1, 1);
     }
-    if (v.wino == 4 || v.wino == 6) {
+    if (v.family == Family::Wino4 || v.family == Family::Wino6) {
         // persistent, ONE 4-wave workgroup per CU (512 registers per lane, 3-deep LDS ring), a multiple of the 8 XCDs.
         // Whole main tiles first; what they leave uncovered goes to strip launches of thin tiles when that needs fewer tiles
         // than rounding the main grid up (same weight image: it depends on the 64-row block and the chunk only).
@@ -3159,7 +2696,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
             hipLaunchKernelGGL(rv.kern, dim3(g), dim3(rv.threads), rv.lds, stream, q);
         };
         const int mw = (Wout / v.pw) * v.pw, mh = (Hout / v.ph) * v.ph;
-        const Variant &sv = v.wino == 6 ? wino6_strip_v_() : wino4_strip_v(), &sh = v.wino == 6 ? wino6_strip_h_() : wino4_strip_h();
+        const Variant &sv = strip_v(v.family), &sh = strip_h(v.family);
         // cost of the slowest workgroup: items are dealt evenly over min(CUs, items) persistent workgroups, a tile takes about
         // 2.4 us per 8-channel chunk + 5 us of epilogue, and a strip launch adds its own rounds plus ~30 us of launch gap and
         // pipeline prologue (at batch 1 the 20 extra launches of a frame cost more than the empty tile area they save: 3.4 ms
@@ -3172,7 +2709,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         const int t_main = (mw / v.pw) * (mh / v.ph);
         const int t_right = Wout > mw ? pp_div_up(Wout - mw, sv.pw) * pp_div_up(Hout, sv.ph) : 0;
         const int t_bottom = Hout > mh ? pp_div_up(mw, sh.pw) * pp_div_up(Hout - mh, sh.ph) : 0;
-        const double tile_us = v.wino == 6 ? 1.9 * (L.cin / 8) + 3.5 : 2.4 * (L.cin / 8) + 5.0;
+        const double tile_us = v.family == Family::Wino6 ? 1.9 * (L.cin / 8) + 3.5 : 2.4 * (L.cin / 8) + 5.0;
         const double full = rounds(pp_div_up(Wout, v.pw) * pp_div_up(Hout, v.ph)) * tile_us;
         const double split = (rounds(t_main) + rounds(t_right) + rounds(t_bottom)) * tile_us + 30.0 * ((t_right > 0) + (t_bottom > 0));
         const bool no_strips = net->w4_strips == 0, all_strips = net->w4_strips == 2;
@@ -3190,10 +2727,9 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         PP_HIP(hipGetLastError());
         return 0;
     }
-    if (v.wino == 1) { // persistent Winograd: two workgroups per CU (LDS and registers allow exactly two), a multiple of the 8 XCDs
+    if (v.family == Family::Wino) { // persistent Winograd: two workgroups per CU (LDS and registers allow exactly two), a multiple of the 8 XCDs
         const int total = (int)grid.x * (int)grid.y * B;
         int g = (v.threads >= 512 ? 1 : 2) * net->num_cu; // 8-wave workgroups fill a CU's registers alone
-        if (p.dbg & 32) { g = net->num_cu; lds_bytes = 100 * 1024; } // timing experiment: ONE workgroup per CU (one wave per SIMD)
         if (g > total) g = total;
         g = (g + 7) & ~7;
         grid = dim3(g, 1, 1);
@@ -3302,7 +2838,7 @@ int autotune_layer(pp_ctx* ctx, Layer& L, int Hin, int Win, int Hout, int Wout, 
     std::vector<Variant> menu;
     const int rows_ = (L.kind == 2) ? head_rows(ctx->cfg.num_anchor_per_loc) : (L.kind == 1 ? L.cout * L.up * L.up : L.cout);
     auto legal = [&](const Variant& v) {
-        return variant_ok(v, rows_) && shape_ok(v, Hin, Win, Wout) && ((v.wino == 3) ? g1_lds(v, L.cin) : v.lds) <= (size_t)160 * 1024;
+        return variant_ok(v, rows_) && shape_ok(v, Hin, Win, Wout) && layer_lds(v, L.cin) <= (size_t)160 * 1024;
     };
     const bool first_conv = L.kind == 0 && L.stride == 2 && L.level == 0;
     layer_menu(L.kind, L.stride, L.up, menu, L.cin, L.kind == 0 && L.stride == 1 && L.level == 0, ctx->cfg.num_anchor_per_loc == 9, eprec, first_conv);
@@ -3328,11 +2864,6 @@ int autotune_layer(pp_ctx* ctx, Layer& L, int Hin, int Win, int Hout, int Wout, 
     snprintf(sig, sizeof(sig), "v%d m%d k%d s%d u%d c%d r%d %dx%d n%d b%d p%d", pp_version(), (int)menu.size(), L.kind, L.stride, L.up, L.cin, L.cout, Hout, Wout,
              ctx->cfg.norm_kind, ctx->max_batch < TUNE_FRAMES ? ctx->max_batch : TUNE_FRAMES, eprec);
     const int rows = (L.kind == 2) ? head_rows(ctx->cfg.num_anchor_per_loc) : (L.kind == 1 ? L.cout * L.up * L.up : L.cout);
-    if (const char* ff = getenv("PP_FORCE_FIRST")) { // experiments: pin the tiling of the first (sparse, stride-2) convolution alone
-        if (first_conv)
-            for (const Variant& v : menu)
-                if (variant_ok(v, rows) && shape_ok(v, Hin, Win, Wout) && strstr(v.name, ff)) { L.var = v; return 0; }
-    }
     if (const char* force = getenv("PP_FORCE_VARIANT")) { // tests: pin a tiling family by name substring
         for (const Variant& v : menu)
             if (variant_ok(v, rows) && shape_ok(v, Hin, Win, Wout) && strstr(v.name, force)) { L.var = v; return 0; }
@@ -3353,7 +2884,7 @@ int autotune_layer(pp_ctx* ctx, Layer& L, int Hin, int Win, int Hout, int Wout, 
     // Infinity Cache holds, as in production (aliased frames would hide a tiling's HBM re-reads)
     const int tb = ctx->max_batch < TUNE_FRAMES ? ctx->max_batch : TUNE_FRAMES;
     auto time_variant = [&](const Variant& v, int reps, double& out_ms) -> int {
-        const size_t need = (v.wino == 3) ? g1_lds(v, L.cin) : v.lds;
+        const size_t need = layer_lds(v, L.cin);
         L.var = v;
         PP_HIP(hipFuncSetAttribute((const void*)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
         if (v.kern2) PP_HIP(hipFuncSetAttribute((const void*)v.kern2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
@@ -3376,7 +2907,7 @@ int autotune_layer(pp_ctx* ctx, Layer& L, int Hin, int Win, int Hout, int Wout, 
     for (const Variant& v : menu) {
         if (!variant_ok(v, rows)) continue;
         if (!shape_ok(v, Hin, Win, Wout)) continue;
-        const size_t need = (v.wino == 3) ? g1_lds(v, L.cin) : v.lds;
+        const size_t need = layer_lds(v, L.cin);
         if (need > 160 * 1024) continue;
         double ms;
         int rc = time_variant(v, 3, ms);
@@ -3477,10 +3008,9 @@ int pp_net_create(pp_ctx* ctx)
                                 pick_variant(2, 1, 1, head_rows(ctx->cfg.num_anchor_per_loc), H, W, ctx->cfg.num_anchor_per_loc == 9)});
     for (Layer& L : net->layers)
         PP_HIP(hipFuncSetAttribute((const void*)L.var.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.var.lds));
-    PP_HIP(hipFuncSetAttribute((const void*)wino4_strip_v().kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wino4_strip_v().lds));
-    PP_HIP(hipFuncSetAttribute((const void*)wino4_strip_h().kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wino4_strip_h().lds));
-    PP_HIP(hipFuncSetAttribute((const void*)wino6_strip_v_().kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wino6_strip_v_().lds));
-    PP_HIP(hipFuncSetAttribute((const void*)wino6_strip_h_().kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wino6_strip_h_().lds));
+    for (Family f : {Family::Wino4, Family::Wino6})
+        for (const Variant* sv : {&strip_v(f), &strip_h(f)})
+            PP_HIP(hipFuncSetAttribute((const void*)sv->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sv->lds));
     return 0;
 }
 
@@ -3579,7 +3109,7 @@ int pp_net_commit(pp_ctx* ctx)
                 if (rc) { if (tin) { (void)hipFree(tin - W6_FRONT_PAD); (void)hipFree(tout); } return rc; }
             }
             PP_HIP(hipFuncSetAttribute((const void*)L.var.kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(L.var.wino == 3 ? g1_lds(L.var, L.cin) : L.var.lds)));
+                                       (int)layer_lds(L.var, L.cin)));
             if (L.var.kern2) PP_HIP(hipFuncSetAttribute((const void*)L.var.kern2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.var.lds));
             rc = pack_layer(ctx, L);
             if (rc) { if (tin) { (void)hipFree(tin - W6_FRONT_PAD); (void)hipFree(tout); } return rc; }
@@ -3875,12 +3405,12 @@ extern "C" double pp_dominant_executed_ratio(pp_ctx* ctx)
     pp_net* net = (pp_net*)ctx->net;
     for (const Layer& L : net->layers)
         if (L.kind == 0 && L.level == 0 && L.stride == 1)
-            return L.var.wino == 6 ? 0.25 : (L.var.wino == 1 || L.var.wino == 2 || L.var.wino == 4) ? 4.0 / 9.0 : (L.var.wino == 5 && L.var.prec == 1) ? 3.0 : 1.0; // bf16x3: three MFMAs per product
+            return executed_ratio(L.var);
     return 1.0;
 }
 
 // The network's launch plan as text, one line per conv / deconv / head layer in execution order:
-//   "<index> kind=<0 conv3x3|1 deconv|2 head> cin=<> cout=<> stride=<> up=<> level=<> wino=<0|1|2|3> tiling=<name>"
+//   "<index> kind=<0 conv3x3|1 deconv|2 head> cin=<> cout=<> stride=<> up=<> level=<> wino=<family number> tiling=<name>"
 // (bench.py derives the executed MFMA flops of a frame from it and records it in its JSON line).
 extern "C" int pp_layer_tilings(pp_ctx* ctx, char* buf, int cap)
 {
@@ -3891,7 +3421,7 @@ extern "C" int pp_layer_tilings(pp_ctx* ctx, char* buf, int cap)
     int i = 0;
     for (const Layer& L : net->layers) {
         snprintf(line, sizeof(line), "%d kind=%d cin=%d cout=%d stride=%d up=%d level=%d wino=%d tiling=%s\n", i++, L.kind, L.cin, L.cout, L.stride, L.up, L.level,
-                 L.var.wino, L.var.name);
+                 (int)L.var.family, L.var.name);
         t += line;
     }
     if (buf && cap > 0) {
@@ -3932,7 +3462,3 @@ extern "C" int pp_tune_import(const char* text)
     }
     return n;
 }
-
-#if PP_WINO_STAMP
-extern "C" int pp_debug_set_stamp_buffer(unsigned long long* dev8) { g_stamp_buf = dev8; return 0; }
-#endif

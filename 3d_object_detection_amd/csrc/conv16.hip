@@ -53,18 +53,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 enum { P16_BF16X3 = 1, P16_BF16 = 2, P16_FP16 = 3 };
 
-// diagnostic build (make stamp16; tools/c16_stamp.py): s_memtime sums of the phases of an item, lane 0 of wave 0 of every
-// workgroup, into ConvP::dbg_buf[0..7] = prologue | loads issued | tap loop | barrier after the taps | commit + rest of staging |
-// second barrier | epilogue | items
-#ifndef C16_STAMP
-#define C16_STAMP 0
-#endif
-#if C16_STAMP
-#define C16_T(x) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_[x] += t_ - tl_; tl_ = t_; }
-#else
-#define C16_T(x)
-#endif
-
 template <int PREC>
 __device__ __forceinline__ unsigned pack2(float a, float b)
 {
@@ -175,9 +163,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
     // tile (same patch) meet in one L2.  Placement is a speed matter only.
     const int nslots = gridDim.x >> 3, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int per_xcd = (total + 7) >> 3;
-    // diagnostics (PP_CONV_DBG, timing only -- results are wrong): 1 stage only step 0 of an item, 4 skip the epilogue,
-    // 16 skip the step loop, 128 skip the commit (loads stay).  (No hook inside the tap loop: a branch there moves the accumulators out of the AGPRs.)
-    const int nsteps = (p.dbg & 16) ? 0 : (p.Cin / 16) * PASSES;
+    const int nsteps = (p.Cin / 16) * PASSES;
     constexpr bool sparse = SPARSE;
     static_assert(!SPARSE || S == 2, "the sparse BEV input feeds the stride-2 first conv");
     const size_t in_plane = (size_t)p.Hin * p.Win, out_plane = (size_t)p.Hout * p.Wout;
@@ -195,10 +181,6 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
     }
     const int aoff = kh * C::BM + wm * MT * 32 + n32;
 
-#if C16_STAMP
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tl_ = __builtin_amdgcn_s_memtime();
-#endif
     for (int it = slot; it < per_xcd; it += nslots) {
         const int item = xcd * per_xcd + it;
         if (item >= total) break;
@@ -381,15 +363,13 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
         };
 
         if (any) {
-            C16_T(6)
             issue_all(0);
             commit_all(0);
             if constexpr (!C::DB) stage_rest(0);
-            else if (nsteps > 1 && !(p.dbg & 1)) issue_all(1);
+            else if (nsteps > 1) issue_all(1);
             __syncthreads();
-            C16_T(0)
             for (int step = 0; step < nsteps; ++step) {
-                const bool stage = step + 1 < nsteps && !(p.dbg & 1);
+                const bool stage = step + 1 < nsteps;
                 if (stage) {
                     if constexpr (C::DB) {
                         // ONE register set, written AFTER the barrier and re-requested at once: the data of step s+1 (requested a
@@ -397,8 +377,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
                         // requests of step s+2 leave right behind it, so loads are in flight during every phase of the step
                         // (the first version requested at the top of a step and wrote at its end: one burst per step, and the
                         // memory pipe idle while the wave multiplied and converted)
-                        if (!(p.dbg & 128)) commit_all(step + 1);
-                        C16_T(4)
+                        commit_all(step + 1);
                         if (step + 2 < nsteps) issue_all(step + 2);
                     } else {
                         issue_x(step + 1, I0{}, I0{});
@@ -406,7 +385,6 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
                         if constexpr (C::WDB) issue_w(step + 1);
                     }
                 }
-                C16_T(1)
                 const u32x4* xb = xl + xbuf_of(step) * C::X_UNITS;
                 const u32x4* wb = wl + wbuf_of(step) * C::W_UNITS;
                 // operand reads run ONE TAP AHEAD of the MFMAs that consume them (two register sets, order pinned with
@@ -434,20 +412,16 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
                         for (int j = 0; j < NT; ++j) acc[i][j] = mfma16<PREC>(a[cur][i], b[cur][j], acc[i][j]);
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                C16_T(2)
                 if constexpr (C::DB) {
                     __syncthreads();
-                    C16_T(5)
                 } else {
                     if constexpr (C::WDB)
-                        if (stage && !(p.dbg & 128)) commit_w(wbuf_of(step + 1)); // the other image: nobody reads it in this step
+                        if (stage) commit_w(wbuf_of(step + 1)); // the other image: nobody reads it in this step
                     __syncthreads(); // every wave is done reading the operands of this step
-                    C16_T(3)
                     if (stage) {
-                        if (!(p.dbg & 128)) { commit_x(step + 1, 0, I0{}, I0{}); stage_rest(step + 1); }
-                        C16_T(4)
+                        commit_x(step + 1, 0, I0{}, I0{});
+                        stage_rest(step + 1);
                         __syncthreads();
-                        C16_T(5)
                     }
                 }
             }
@@ -460,7 +434,6 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
         // ds_write_b32, 4 ds_read_b128) and comes back as 4 consecutive pixels of one channel per lane: 4 dwordx4 per block, a
         // wave instruction = 8 channels x 128 contiguous bytes.  The residual quads of block b + 2 are requested while block b
         // is transposed (the compiler must assume residual and output alias, so nothing is left for it to hoist).
-        if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) p.out[0] = 1.f; if (!C::DB) __syncthreads(); continue; }
         float* gout = OUT16 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(p.out) + (size_t)fr * p.out_fs) : p.out + (size_t)fr * p.out_fs;
         const float* gres = !p.res ? nullptr
                             : OUT16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(p.res) + (size_t)fr * p.res_fs) : p.res + (size_t)fr * p.res_fs;
@@ -565,15 +538,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv16(const ConvP p)
             }
         }
         if (p.stat_acc || !C::DB) __syncthreads(); // red (and, single-buffered, the transpose tiles inside the operand buffers) are rewritten by the next item
-#if C16_STAMP
-        st_[7] += 1;
-#endif
     }
-#if C16_STAMP
-    { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_[6] += t_ - tl_; }
-    if (p.dbg_buf && tid == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(p.dbg_buf + k, st_[k]);
-#endif
 }
 
 template <int STRIDE, int PREC, int WM, int WN, int MT, int NT, int PW, int PH, int OCC, int IO16 = 0>
@@ -587,7 +552,7 @@ Variant make_c16()
     v.bm = C::BM; v.bmp = C::BM; v.pw = PW; v.ph = PH; v.kc = 16; v.threads = C::T;
     v.waves = 4 * OCC; v.pairs = MT * NT; // waves: per CU (the launcher sizes the persistent grid: waves * 64 / threads workgroups per CU)
     v.lds = C::LDS_BYTES;
-    v.wino = 5;
+    v.family = Family::Conv16;
     v.prec = PREC;
     if (IO16) snprintf(v.name, sizeof(v.name), "c16 s%d p%d h%d w%dx%d t%dx%d %dx%d o%d", STRIDE, PREC, IO16, WM, WN, MT, NT, PW, PH, OCC);
     else snprintf(v.name, sizeof(v.name), "c16 s%d p%d w%dx%d t%dx%d %dx%d o%d", STRIDE, PREC, WM, WN, MT, NT, PW, PH, OCC);

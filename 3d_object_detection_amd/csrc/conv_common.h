@@ -86,12 +86,10 @@ struct ConvP {
     float* out_dir;
     int n_cls, n_box; // na, 7 na (dir = rest up to n_rows) for na anchors per location (reference: 9, 63)
     int n_rows;       // 10 na (reference: 90)
-    int dbg;          // diagnostics only (PP_CONV_DBG): 1 = skip staging after chunk 0, 4 = skip epilogue
     // batch: blockIdx.z = frame; strides in elements between consecutive frames
     size_t in_fs, out_fs, res_fs, box_fs, dir_fs; // floats
     size_t pre_fs, stat_fs;                        // doubles
     size_t aff_fs;                                 // floats between frames of pre_scale / pre_shift (0: shared)
-    unsigned long long* dbg_buf;                   // diagnostic builds only (PP_WINO_STAMP): stamp sums
     int nb;                                        // frames (persistent kernels loop over them; others use grid.z)
     // sparse BEV input of the first conv: pillar-index map [Hin*Win] (-1 = empty) + PFN rows [P][64]
     const int32_t* pmap;
@@ -102,17 +100,25 @@ struct ConvP {
     int rx0, ry0, rx1, ry1, rnbx, rnby;
 };
 
-struct Variant { // one compiled tiling of conv_mfma
+// Kernel family of a tiling.  The numbers are part of pp_layer_tilings' text ("wino=<n>").
+enum class Family : int {
+    Direct = 0,  // conv_mfma: direct convolution
+    Wino = 1,    // wino_mfma: Winograd F(2x2,3x3) image
+    Gemm1x1 = 3, // gemm1x1: persistent 1x1 GEMM (weights resident)
+    Wino4 = 4,   // wino4_mfma: Winograd F(2x2,3x3), one wave per SIMD
+    Conv16 = 5,  // conv16.hip: 16-bit operand 3x3 convolutions
+    Wino6 = 6,   // wino6.hip: Winograd F(4x4,3x3), positions split over the waves
+};
+
+struct Variant { // one compiled tiling
     void (*kern)(const ConvP);
     void (*kern2)(const ConvP) = nullptr; // conv16, stride 2: twin for the sparse BEV input of the first conv (ConvP::pmap)
     int bm, bmp, pw, ph, kc, threads, waves, pairs; // pairs = MT*NT tile pairs per wave
     size_t lds;
     char name[48];
-    int wino = 0; // 1: Winograd F(2x2,3x3) image; 2: slab-resident persistent Winograd; 3: persistent 1x1 GEMM (weights resident); 4: wino4_mfma;
-                  // 5: conv16; 6: Winograd F(4x4,3x3), positions split over the waves (wino6.hip)
-    int cin = 0;  // wino == 2: compiled for exactly this Cin
-    int prec = 0; // wino == 3 / 5: 0 fp32 MFMA, 1 split-bf16 (bf16x3), 2 plain bf16, 3 fp16 operands
-    int io16 = 0; // wino == 3 / 5: bit 0 = the input tensor is fp16, bit 1 = the output tensor (and residual) is (pp_set_precision 4)
+    Family family = Family::Direct;
+    int prec = 0; // Gemm1x1 / Conv16: 0 fp32 MFMA, 1 split-bf16 (bf16x3), 2 plain bf16, 3 fp16 operands
+    int io16 = 0; // Gemm1x1 / Conv16: bit 0 = the input tensor is fp16, bit 1 = the output tensor (and residual) is (pp_set_precision 4)
 };
 
 

@@ -36,10 +36,6 @@ namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef PP_W6_DIAG
-#define PP_W6_DIAG 0 // timing-only ablations (wrong results): 1 no input transform, 2 no raw LDS reads, 4 no A loads, 8 no MFMA, 16 no staging, 32 no epilogue exchange, 64 load side frozen (patch loads hit L2), 128 A loads always the same 72 KB, 2048 every A load lands in the VGPR buffer (is the AGPR destination what costs?), 4096 A loads of 4 bytes per lane (requests or bytes?), 16384 no epilogue
-#endif
-
 template <int TWT>
 struct Wino6Cfg {
     static constexpr int THT = 16 / TWT;             // the 16 tiles of a workgroup: TWT x THT tiles of 4x4 pixels
@@ -112,11 +108,6 @@ struct Wino6Cfg {
     static_assert(N_A <= 63, "vmcnt is a 6-bit counter");
 };
 
-#if PP_W6_DIAG & 256
-#define W6_SYNC "\n\ts_waitcnt vmcnt(0)" // debugging: every request completes before the next instruction (tests the logic without anything in flight)
-#else
-#define W6_SYNC ""
-#endif
 // hipcc pads no hazard inside an asm statement: an SGPR operand it has just reloaded from a spill lane (v_readlane_b32, a VALU write
 // of an SGPR) needs 5 wait states before a VMEM instruction reads it as descriptor or offset
 #define W6_SGPR_PAD "s_nop 4\n\t"
@@ -191,7 +182,6 @@ template <int J, int KB, bool ZERO>
 __device__ __forceinline__ void w6_mfma4(const float b, const f32x4& a3)
 {
     constexpr int c0 = J * 16, a0 = 144 + (KB * 9 + J) * 4;
-    if constexpr (PP_W6_DIAG & 8) { asm volatile("" ::"v"(b)); return; }
     if constexpr (KB < 3) {
         if constexpr (ZERO)
             asm volatile("v_mfma_f32_16x16x4_f32 a[%c1:%c2], a[%c9], %0, 0\n\tv_mfma_f32_16x16x4_f32 a[%c3:%c4], a[%c10], %0, 0\n\t"
@@ -223,13 +213,13 @@ __device__ __forceinline__ void w6_mfma4_load(const float b, const i32x4 rw, con
     if constexpr (ZERO)
         asm volatile("v_mfma_f32_16x16x4_f32 a[%c1:%c2], a[%c9], %0, 0\n\tv_mfma_f32_16x16x4_f32 a[%c3:%c4], a[%c10], %0, 0\n\t"
                      "v_mfma_f32_16x16x4_f32 a[%c5:%c6], a[%c11], %0, 0\n\tv_mfma_f32_16x16x4_f32 a[%c7:%c8], a[%c12], %0, 0\n\t"
-                     "s_nop 1\n\tbuffer_load_dwordx4 a[%c9:%c12], %13, %14, %15 offen" W6_SYNC
+                     "s_nop 1\n\tbuffer_load_dwordx4 a[%c9:%c12], %13, %14, %15 offen"
                      :: "v"(b), "i"(c0), "i"(c0 + 3), "i"(c0 + 4), "i"(c0 + 7), "i"(c0 + 8), "i"(c0 + 11), "i"(c0 + 12), "i"(c0 + 15),
                         "i"(a0), "i"(a0 + 1), "i"(a0 + 2), "i"(a0 + 3), "v"(voff), "s"(rw), "s"(soff) : W6_AGPRS);
     else
         asm volatile("v_mfma_f32_16x16x4_f32 a[%c1:%c2], a[%c9], %0, a[%c1:%c2]\n\tv_mfma_f32_16x16x4_f32 a[%c3:%c4], a[%c10], %0, a[%c3:%c4]\n\t"
                      "v_mfma_f32_16x16x4_f32 a[%c5:%c6], a[%c11], %0, a[%c5:%c6]\n\tv_mfma_f32_16x16x4_f32 a[%c7:%c8], a[%c12], %0, a[%c7:%c8]\n\t"
-                     "s_nop 1\n\tbuffer_load_dwordx4 a[%c9:%c12], %13, %14, %15 offen" W6_SYNC
+                     "s_nop 1\n\tbuffer_load_dwordx4 a[%c9:%c12], %13, %14, %15 offen"
                      :: "v"(b), "i"(c0), "i"(c0 + 3), "i"(c0 + 4), "i"(c0 + 7), "i"(c0 + 8), "i"(c0 + 11), "i"(c0 + 12), "i"(c0 + 15),
                         "i"(a0), "i"(a0 + 1), "i"(a0 + 2), "i"(a0 + 3), "v"(voff), "s"(rw), "s"(soff) : W6_AGPRS);
 }
@@ -237,27 +227,17 @@ __device__ __forceinline__ void w6_mfma4_load(const float b, const i32x4 rw, con
 template <int J, int KB>
 __device__ __forceinline__ void w6_load_A(const i32x4 rw, const unsigned voff, const unsigned soff, f32x4& a3)
 {
-    if constexpr (PP_W6_DIAG & 4) return;
-    if constexpr (PP_W6_DIAG & 4096) { // 4 bytes per lane instead of 16: the same requests with a quarter of the data
-        constexpr int a0 = 144 + ((KB < 3 ? KB : 0) * 9 + J) * 4;
-        asm volatile(W6_SGPR_PAD "buffer_load_dword a[%c3], %0, %1, %2 offen" :: "v"(voff), "s"(rw), "s"(soff), "i"(a0) : W6_AGPRS);
-    } else if constexpr (KB < 3 && !(PP_W6_DIAG & 2048)) {
+    if constexpr (KB < 3) {
         constexpr int a0 = 144 + (KB * 9 + J) * 4;
-        asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 a[%c3:%c4], %0, %1, %2 offen" W6_SYNC :: "v"(voff), "s"(rw), "s"(soff), "i"(a0), "i"(a0 + 3) : W6_AGPRS);
+        asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 a[%c3:%c4], %0, %1, %2 offen" :: "v"(voff), "s"(rw), "s"(soff), "i"(a0), "i"(a0 + 3) : W6_AGPRS);
     } else {
-        asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 %0, %1, %2, %3 offen" W6_SYNC : "=v"(a3) : "v"(voff), "s"(rw), "s"(soff));
+        asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(a3) : "v"(voff), "s"(rw), "s"(soff));
     }
 }
 __device__ __forceinline__ void w6_load_x4(f32x4& dst, const i32x4 rs, const unsigned voff, const unsigned soff)
 {
-    if constexpr (PP_W6_DIAG & 16) { asm volatile("" : "=v"(dst)); return; }
-    asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 %0, %1, %2, %3 offen" W6_SYNC : "=v"(dst) : "v"(voff), "s"(rs), "s"(soff));
+    asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rs), "s"(soff));
 }
-#if PP_W6_DIAG & 512
-#define W6_STAMP(V) { __builtin_amdgcn_sched_barrier(0); V = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#else
-#define W6_STAMP(V)
-#endif
 template <int N> __device__ __forceinline__ void w6_wait() { asm volatile("s_waitcnt vmcnt(%c0)" :: "i"(N)); }
 template <int N> __device__ __forceinline__ void w6_wait(f32x4& x) { asm volatile("s_waitcnt vmcnt(%c1)" : "+v"(x) : "i"(N)); }
 // the 9 positions' accumulator rows (2 RP, 2 RP + 1) of M-tile MT as pairs, for v_pk_* arithmetic
@@ -356,7 +336,6 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
             dst[c] = (f32x2){p.pre_scale[(size_t)f_ * p.aff_fs + c], p.pre_shift[(size_t)f_ * p.aff_fs + c]};
     };
     auto advance = [&]() {
-        if constexpr (PP_W6_DIAG & 64) return;
         if (s_ch + 1 < nchunk) ++s_ch;
         else if (s_lin + nloc < lin_end) {
             const int f_old = s_frame;
@@ -375,14 +354,14 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
 #define W6_LOAD_PIECE(X, RD)                                                                     \
     { if constexpr ((RD) < PRND) w6_load_x4(xv[X][RD], rin, goff[RD], (unsigned)(s_ch * KC) * plane_b); }
 #define W6_NORM_PIECE(X, RD, N)                                                                  \
-    { if constexpr ((RD) < PRND && !(PP_W6_DIAG & 16)) {                                        \
+    { if constexpr ((RD) < PRND) {                                                              \
         w6_wait<N>(xv[X][RD]);                                                                   \
         const f32x2 a_ = __builtin_elementwise_fma(lo2(xv[X][RD]), (f32x2){ss[0], ss[0]}, (f32x2){ss[1], ss[1]}); \
         const f32x2 b_ = __builtin_elementwise_fma(hi2(xv[X][RD]), (f32x2){ss[0], ss[0]}, (f32x2){ss[1], ss[1]}); \
         xv[X][RD] = (f32x4){__builtin_amdgcn_fmed3f(a_[0], 0.f, mk[RD][0]), __builtin_amdgcn_fmed3f(a_[1], 0.f, mk[RD][1]), \
                             __builtin_amdgcn_fmed3f(b_[0], 0.f, mk[RD][2]), __builtin_amdgcn_fmed3f(b_[1], 0.f, mk[RD][3])}; } }
 #define W6_WRITE_PIECE(X, RD, IB)                                                                \
-    { if constexpr ((RD) < PRND && !(PP_W6_DIAG & 16)) *reinterpret_cast<f32x4*>((IB) + loff[RD]) = xv[X][RD]; }
+    { if constexpr ((RD) < PRND) *reinterpret_cast<f32x4*>((IB) + loff[RD]) = xv[X][RD]; }
 
     // ---------------- compute side ----------------
     const int tx = m % TWT, ty = m / TWT;
@@ -396,47 +375,38 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
     f32x2 d[6][3];   // raw 6x6 window of one (channel, tile) as column pairs
 
     auto read_raw = [&](const float* base, auto R0, auto R1) {
-        if constexpr (!(PP_W6_DIAG & 2)) {
-            pp_steps<decltype(R0)::value, decltype(R1)::value>([&](auto AA) {
-                constexpr int a = decltype(AA)::value;
-                if constexpr (a >= A0 && a <= A1) {
-                    constexpr int ro = a * C::RS + (a >= 4 ? C::SK : 0); // window row a of tile ty = patch row 4 ty + a
-                    const f32x4 q = *reinterpret_cast<const f32x4*>(base + ro);
-                    d[a][0] = lo2(q); d[a][1] = hi2(q);
-                    d[a][2] = *reinterpret_cast<const f32x2*>(base + ro + 4);
-                }
-            });
-        }
+        pp_steps<decltype(R0)::value, decltype(R1)::value>([&](auto AA) {
+            constexpr int a = decltype(AA)::value;
+            if constexpr (a >= A0 && a <= A1) {
+                constexpr int ro = a * C::RS + (a >= 4 ? C::SK : 0); // window row a of tile ty = patch row 4 ty + a
+                const f32x4 q = *reinterpret_cast<const f32x4*>(base + ro);
+                d[a][0] = lo2(q); d[a][1] = hi2(q);
+                d[a][2] = *reinterpret_cast<const f32x2*>(base + ro + 4);
+            }
+        });
     };
     f32x2 F[3], H[3]; // the wave's full row and the source row of its half row of B^T d (over the window's columns, as pairs)
     auto row_pass = [&]() {
-        if constexpr (!(PP_W6_DIAG & 1)) {
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                if constexpr (WV == 0) {
-                    F[q] = pkfma(d[2][q], -5.f, pkfma(d[0][q], 4.f, d[4][q]));
-                    H[q] = pkfma(d[2][q], -4.f, d[4][q]) + pkfma(d[1][q], -4.f, d[3][q]);
-                } else if constexpr (WV == 1) {
-                    const f32x2 u = pkfma(d[2][q], -4.f, d[4][q]), v = pkfma(d[1][q], -4.f, d[3][q]);
-                    H[q] = u + v; F[q] = u - v;
-                } else if constexpr (WV == 2) {
-                    const f32x2 u = d[4][q] - d[2][q], v = d[3][q] - d[1][q];
-                    F[q] = pkfma(v, 2.f, u); H[q] = pkfma(v, -2.f, u);
-                } else {
-                    H[q] = pkfma(d[3][q] - d[1][q], -2.f, d[4][q] - d[2][q]);
-                    F[q] = pkfma(d[3][q], -5.f, pkfma(d[1][q], 4.f, d[5][q]));
-                }
+        for (int q = 0; q < 3; ++q) {
+            if constexpr (WV == 0) {
+                F[q] = pkfma(d[2][q], -5.f, pkfma(d[0][q], 4.f, d[4][q]));
+                H[q] = pkfma(d[2][q], -4.f, d[4][q]) + pkfma(d[1][q], -4.f, d[3][q]);
+            } else if constexpr (WV == 1) {
+                const f32x2 u = pkfma(d[2][q], -4.f, d[4][q]), v = pkfma(d[1][q], -4.f, d[3][q]);
+                H[q] = u + v; F[q] = u - v;
+            } else if constexpr (WV == 2) {
+                const f32x2 u = d[4][q] - d[2][q], v = d[3][q] - d[1][q];
+                F[q] = pkfma(v, 2.f, u); H[q] = pkfma(v, -2.f, u);
+            } else {
+                H[q] = pkfma(d[3][q] - d[1][q], -2.f, d[4][q] - d[2][q]);
+                F[q] = pkfma(d[3][q], -5.f, pkfma(d[1][q], 4.f, d[5][q]));
             }
         }
     };
     auto col_pass = [&](float* bn) {
-        if constexpr (!(PP_W6_DIAG & 1)) {
-            w6_bt_pairs<0>(F[0], F[1], F[2], two, bn);
-            w6_bt_pairs<(WV & 1) ? 2 : 1>(H[0], H[1], H[2], two, bn + 6);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) bn[j] = d[A0 + (j % 4)][j % 3][j & 1];
-        }
+        w6_bt_pairs<0>(F[0], F[1], F[2], two, bn);
+        w6_bt_pairs<(WV & 1) ? 2 : 1>(H[0], H[1], H[2], two, bn + 6);
     };
     // weights of (block, chunk, k-step, position): byte offset inside the image (wave WV's slice)
     auto w_off = [&](unsigned chunk_base, int ks, int j) { return chunk_base + (unsigned)(ks * 36864 + WV * 9216 + j * 1024); };
@@ -495,9 +465,6 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
 
     int buf = 0;
     const size_t out_plane = (size_t)p.Hout * p.Wout;
-#if PP_W6_DIAG & 512
-    unsigned long long st_top = 0, st_k0 = 0, st_k1 = 0, st_bar = 0, st_epi1 = 0, st_epi2 = 0, st_epi3 = 0, st_epi4 = 0, st_adv_t = 0, st_adv_n = 0, st_adv_s = 0, st_n = 0, st_tiles = 0, st_g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
 
     for (int lin = lin0; lin < lin_end; lin += nloc) {
         const int cb = lin % ncb, tile = (lin / ncb) % ntile;
@@ -533,24 +500,15 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
             constexpr bool LAST = decltype(LAST_)::value;
             static_assert(POS == 2 || POS == X, "a tile starts on an even chunk");
             static_assert(!LAST || X == 1, "a tile ends on an odd chunk");
-#if PP_W6_DIAG & 512
-            unsigned long long t0_ = 0, t1_ = 0, t2_ = 0, t3_ = 0, t4_ = 0, tg_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            W6_STAMP(t0_)
-#endif
             const int nbuf = buf == 2 ? 0 : buf + 1, wbuf = buf == 0 ? 2 : buf - 1;
             float* ibw = il + wbuf * C::LDS_IN;
             // register set X holds chunk g+2: its (scale, shift) and in-image clamps; then the load side moves on to chunk g+4
             ss = aff[r_tab[X] * 320 + r_c0[X] + chl];
             if (r_lin[X] != mk_lin) { expand_mask(r_vmask[X]); mk_lin = r_lin[X]; }
-#if PP_W6_DIAG & 512
-            { unsigned long long a0_ = 0, a1_ = 0; const int lin_before_ = s_lin; W6_STAMP(a0_) advance(); W6_STAMP(a1_)
-              if (s_lin != lin_before_) { st_adv_t += a1_ - a0_; st_adv_n += 1; } else st_adv_s += a1_ - a0_; }
-#else
             advance();
-#endif
             r_tab[X] = s_tab; r_c0[X] = s_ch * KC; r_vmask[X] = vmask; r_lin[X] = s_lin;
             // A operands requested during this chunk: those of chunk g+2 (this item's, or the next item's first two)
-            const unsigned wnext = (PP_W6_DIAG & 128) ? 0u : ((ch + 2 < nchunk) ? wb_item + (unsigned)(ch + 2) * chunk_wb : wb_next_item + (unsigned)(ch + 2 - nchunk) * chunk_wb);
+            const unsigned wnext = (ch + 2 < nchunk) ? wb_item + (unsigned)(ch + 2) * chunk_wb : wb_next_item + (unsigned)(ch + 2 - nchunk) * chunk_wb;
             const unsigned soff_x = (unsigned)(s_ch * KC) * plane_b;
             const float* raw1 = il + buf * C::LDS_IN + 4 * C::CS + rbase;  // this chunk's second channel quad
             const float* raw0n = il + nbuf * C::LDS_IN + rbase;            // the next chunk's first channel quad
@@ -563,18 +521,11 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
                     for (int y = 0; y < 4; ++y) w6_load_x4(rq[r][y], rres, lb, (unsigned)r * plane_ob + (unsigned)y * row_ob);
             }
             __builtin_amdgcn_sched_barrier(0);
-            W6_STAMP(t1_)
             pp_steps<0, 2>([&](auto KS_) {
                 constexpr int ks = decltype(KS_)::value, kb = 2 * X + ks;
-#if PP_W6_DIAG & 512
-                if constexpr (ks == 1) { W6_STAMP(t2_) }
-#endif
                 const float* rawn = ks == 0 ? raw1 : raw0n;
                 pp_steps<0, 9>([&](auto J) {
                     constexpr int j = decltype(J)::value;
-#if PP_W6_DIAG & 512
-                    if constexpr (ks == 0) { W6_STAMP(tg_[j]) }
-#endif
                     // the A operands of (kb, j), requested two chunks ago: N_A younger operations (a lower bound around the epilogue,
                     // whose stores are not counted: waiting for a few more of the oldest costs nothing, they are two chunks old)
                     // Buffer 3 (VGPRs) is NOT re-requested in a tile's last chunk: its 36 registers are free for the epilogue, and its
@@ -583,14 +534,13 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
                     // fewer younger operations.  Every wait of an odd chunk's second k-step allows for the (up to) nine missing requests.
                     constexpr int NW = (kb == 3) ? (POS == 1 ? (8 - j) + C::T + C::idx_A(1, j) : C::N_A - 9) : C::N_A;
                     if constexpr (kb == 3) w6_wait<NW>(A3[j]); else w6_wait<NW>();
-                    if constexpr (kb < 3 && !(PP_W6_DIAG & (4 | 8 | 2048 | 4096))) {
+                    if constexpr (kb < 3) {
                         w6_mfma4_load<j, kb, first_ && ks == 0>(B[ks][j], rw, wlane, w_off(wnext, ks, j)); // the MFMAs and the buffer's next request
                         __builtin_amdgcn_sched_barrier(0);
                     } else {
                         w6_mfma4<j, kb, first_ && ks == 0>(B[ks][j], A3[j]);
                         __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (kb == 3) { if constexpr (!LAST) w6_load_A<j, kb>(rw, wlane, w_off(wnext, ks, j), A3[j]); }
-                        else w6_load_A<j, kb>(rw, wlane, w_off(wnext, ks, j), A3[j]);
+                        if constexpr (!LAST) w6_load_A<j, kb>(rw, wlane, w_off(wnext, ks, j), A3[j]);
                     }
                     // gaps: raw window rows of the next k-step behind positions 0..2, the two VALU clusters behind 4 and 6
                     if constexpr (j == 0) read_raw(rawn, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
@@ -614,15 +564,7 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
                     __builtin_amdgcn_sched_barrier(0);
                 });
             });
-            W6_STAMP(t3_)
             __syncthreads();
-            W6_STAMP(t4_)
-#if PP_W6_DIAG & 512
-            st_top += t1_ - t0_; st_k0 += t2_ - t1_; st_k1 += t3_ - t2_; st_bar += t4_ - t3_; st_n += 1;
-#pragma unroll
-            for (int g_ = 0; g_ < 8; ++g_) st_g[g_] += tg_[g_ + 1] - tg_[g_];
-            st_g[8] += t2_ - tg_[8];
-#endif
             buf = nbuf;
         };
         using X0 = std::integral_constant<int, 0>;
@@ -644,161 +586,131 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
         chunk_body(P2{}, X1{}, LY{}, nchunk - 1);
 
         // ---------------- epilogue ----------------
-#if PP_W6_DIAG & 512
-        unsigned long long e0_ = 0, e1_ = 0, e2_ = 0, e3_ = 0;
-        W6_STAMP(e0_)
-#endif
-        if constexpr (!(PP_W6_DIAG & 16384)) {
-            // an 8-pass MFMA's D needs 12 wait states before anything but the next accumulating MFMA touches it (hipcc pads nothing
-            // behind an asm statement)
-            asm volatile("s_nop 11" ::: W6_AGPRS);
-            float* __restrict__ gout = p.out + fz * p.out_fs;
-            const i32x4 rout = w6_rsrc(gout, frame_bytes);
-            {
-                const float* gres = p.res ? p.res + fz * p.res_fs : p.out;
-                const i32x4 rres = w6_rsrc(gres, p.res ? frame_bytes : 0u);
+        // an 8-pass MFMA's D needs 12 wait states before anything but the next accumulating MFMA touches it (hipcc pads nothing
+        // behind an asm statement)
+        asm volatile("s_nop 11" ::: W6_AGPRS);
+        float* __restrict__ gout = p.out + fz * p.out_fs;
+        const i32x4 rout = w6_rsrc(gout, frame_bytes);
+        {
+            const float* gres = p.res ? p.res + fz * p.res_fs : p.out;
+            const i32x4 rres = w6_rsrc(gres, p.res ? frame_bytes : 0u);
 #pragma unroll
-                for (int r = 2; r < 4; ++r)
+            for (int r = 2; r < 4; ++r)
 #pragma unroll
-                    for (int y = 0; y < 4; ++y) w6_load_x4(rq[r][y], rres, lb, (unsigned)r * plane_ob + (unsigned)y * row_ob);
-            }
+                for (int y = 0; y < 4; ++y) w6_load_x4(rq[r][y], rres, lb, (unsigned)r * plane_ob + (unsigned)y * row_ob);
+        }
 
-            // column half of the output transform on this wave's positions, per M-tile and accumulator row pair:
-            //   full row (m0..m5)  ->  T = (m0 + s12 + s34, d12 + 2 d34, s12 + 4 s34, d12 + 8 d34 + m5)
-            //   left half (m0, m1, m2) -> (m0 + s12, d12, s12, d12)        right half (m3, m4, m5) -> (s34, 2 d34, 4 s34, 8 d34 + m5)
-            f32x2 ownF[4][2], ownH[4][2]; // this wave's own M-tile: [x][row pair]
-            pp_steps<0, 4>([&](auto MT_) {
-                constexpr int mt = decltype(MT_)::value;
-                constexpr int src = WV - (WV > mt ? 1 : 0); // slot of this wave among the three sources of M-tile mt
-                pp_steps<0, 2>([&](auto RP_) {
-                    constexpr int rp = decltype(RP_)::value;
-                    f32x2 mm[9];
-                    w6_acc_read<mt, rp>(mm);
-                    const f32x2 s12 = mm[1] + mm[2], d12 = mm[1] - mm[2], s34 = mm[3] + mm[4], d34 = mm[3] - mm[4];
-                    f32x2 tf[4], th[4];
-                    tf[0] = mm[0] + s12 + s34;
-                    tf[1] = pkfma(d34, 2.f, d12);
-                    tf[2] = pkfma(s34, 4.f, s12);
-                    tf[3] = pkfma(d34, 8.f, d12) + mm[5];
-                    if constexpr ((WV & 1) == 0) {
-                        const f32x2 hs = mm[7] + mm[8], hd = mm[7] - mm[8];
-                        th[0] = mm[6] + hs; th[1] = hd; th[2] = hs; th[3] = hd;
-                    } else {
-                        const f32x2 hs = mm[6] + mm[7], hd = mm[6] - mm[7];
-                        th[0] = hs; th[1] = hd + hd; th[2] = hs * (f32x2){4.f, 4.f}; th[3] = pkfma(hd, 8.f, mm[8]);
-                    }
-                    if constexpr (mt == WV) {
+        // column half of the output transform on this wave's positions, per M-tile and accumulator row pair:
+        //   full row (m0..m5)  ->  T = (m0 + s12 + s34, d12 + 2 d34, s12 + 4 s34, d12 + 8 d34 + m5)
+        //   left half (m0, m1, m2) -> (m0 + s12, d12, s12, d12)        right half (m3, m4, m5) -> (s34, 2 d34, 4 s34, 8 d34 + m5)
+        f32x2 ownF[4][2], ownH[4][2]; // this wave's own M-tile: [x][row pair]
+        pp_steps<0, 4>([&](auto MT_) {
+            constexpr int mt = decltype(MT_)::value;
+            constexpr int src = WV - (WV > mt ? 1 : 0); // slot of this wave among the three sources of M-tile mt
+            pp_steps<0, 2>([&](auto RP_) {
+                constexpr int rp = decltype(RP_)::value;
+                f32x2 mm[9];
+                w6_acc_read<mt, rp>(mm);
+                const f32x2 s12 = mm[1] + mm[2], d12 = mm[1] - mm[2], s34 = mm[3] + mm[4], d34 = mm[3] - mm[4];
+                f32x2 tf[4], th[4];
+                tf[0] = mm[0] + s12 + s34;
+                tf[1] = pkfma(d34, 2.f, d12);
+                tf[2] = pkfma(s34, 4.f, s12);
+                tf[3] = pkfma(d34, 8.f, d12) + mm[5];
+                if constexpr ((WV & 1) == 0) {
+                    const f32x2 hs = mm[7] + mm[8], hd = mm[7] - mm[8];
+                    th[0] = mm[6] + hs; th[1] = hd; th[2] = hs; th[3] = hd;
+                } else {
+                    const f32x2 hs = mm[6] + mm[7], hd = mm[6] - mm[7];
+                    th[0] = hs; th[1] = hd + hd; th[2] = hs * (f32x2){4.f, 4.f}; th[3] = pkfma(hd, 8.f, mm[8]);
+                }
+                if constexpr (mt == WV) {
 #pragma unroll
-                        for (int x = 0; x < 4; ++x) { ownF[x][rp] = tf[x]; ownH[x][rp] = th[x]; }
-                    } else if constexpr (!(PP_W6_DIAG & 32)) {
-                        float* wf = xb + ((((mt * 3 + src) * 2 + 0) * 4 + 2 * rp) * 64 + lane) * 4;
-                        float* wh = xb + ((((mt * 3 + src) * 2 + 1) * 4 + 2 * rp) * 64 + lane) * 4;
-                        *reinterpret_cast<f32x4*>(wf) = (f32x4){tf[0][0], tf[1][0], tf[2][0], tf[3][0]};
-                        *reinterpret_cast<f32x4*>(wf + 256) = (f32x4){tf[0][1], tf[1][1], tf[2][1], tf[3][1]};
-                        *reinterpret_cast<f32x4*>(wh) = (f32x4){th[0][0], th[1][0], th[2][0], th[3][0]};
-                        *reinterpret_cast<f32x4*>(wh + 256) = (f32x4){th[0][1], th[1][1], th[2][1], th[3][1]};
-                    }
-                });
+                    for (int x = 0; x < 4; ++x) { ownF[x][rp] = tf[x]; ownH[x][rp] = th[x]; }
+                } else {
+                    float* wf = xb + ((((mt * 3 + src) * 2 + 0) * 4 + 2 * rp) * 64 + lane) * 4;
+                    float* wh = xb + ((((mt * 3 + src) * 2 + 1) * 4 + 2 * rp) * 64 + lane) * 4;
+                    *reinterpret_cast<f32x4*>(wf) = (f32x4){tf[0][0], tf[1][0], tf[2][0], tf[3][0]};
+                    *reinterpret_cast<f32x4*>(wf + 256) = (f32x4){tf[0][1], tf[1][1], tf[2][1], tf[3][1]};
+                    *reinterpret_cast<f32x4*>(wh) = (f32x4){th[0][0], th[1][0], th[2][0], th[3][0]};
+                    *reinterpret_cast<f32x4*>(wh + 256) = (f32x4){th[0][1], th[1][1], th[2][1], th[3][1]};
+                }
             });
-            // the residual rows were requested a whole chunk ago (T operations younger than the last of them)
-            W6_STAMP(e1_)
-            __syncthreads();
-            W6_STAMP(e2_)
-            // row half for M-tile WV: T[i] (float4 over x) from the four waves, Y[y] = sum_i A^T[y][i] T[i]
-            float ssum[4], ssq[4];
-            pp_steps<0, 4>([&](auto R_) {
-                constexpr int r = decltype(R_)::value;
-                f32x4 T[6], TH[2][2]; // TH[row 1 | row 4][left | right]
-                auto own4 = [&](const f32x2 (&o)[4][2]) { return (f32x4){o[0][r >> 1][r & 1], o[1][r >> 1][r & 1], o[2][r >> 1][r & 1], o[3][r >> 1][r & 1]}; };
-                pp_steps<0, 4>([&](auto W_) {
-                    constexpr int w = decltype(W_)::value;
-                    constexpr int irow = w == 0 ? 0 : w == 1 ? 2 : w == 2 ? 3 : 5;
-                    if constexpr (w == WV) { T[irow] = own4(ownF); TH[w >> 1][w & 1] = own4(ownH); }
-                    else {
-                        constexpr int src = w - (w > WV ? 1 : 0);
-                        if constexpr (!(PP_W6_DIAG & 32)) {
-                            T[irow] = *reinterpret_cast<const f32x4*>(xb + ((((WV * 3 + src) * 2 + 0) * 4 + r) * 64 + lane) * 4);
-                            TH[w >> 1][w & 1] = *reinterpret_cast<const f32x4*>(xb + ((((WV * 3 + src) * 2 + 1) * 4 + r) * 64 + lane) * 4);
-                        } else { T[irow] = own4(ownF); TH[w >> 1][w & 1] = own4(ownH); }
-                    }
-                });
-                T[1] = TH[0][0] + TH[0][1];
-                T[4] = TH[1][0] + TH[1][1];
-                const f32x4 s12 = T[1] + T[2], d12 = T[1] - T[2], s34 = T[3] + T[4], d34 = T[3] - T[4];
-                f32x4 Y[4];
-                Y[0] = T[0] + s12 + s34;
-                Y[1] = __builtin_elementwise_fma(d34, (f32x4){2.f, 2.f, 2.f, 2.f}, d12);
-                Y[2] = __builtin_elementwise_fma(s34, (f32x4){4.f, 4.f, 4.f, 4.f}, s12);
-                Y[3] = __builtin_elementwise_fma(d34, (f32x4){8.f, 8.f, 8.f, 8.f}, d12) + T[5];
-                f32x4 sv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f};
-                // residual rows of r.  vmcnt orders loads among loads and stores among stores, NOT one against the other: a younger store that
-                // completes first lowers the counter, so a count that allows for pending stores proves nothing about an older load (the first
-                // version waited for rows 2, 3 with "the 4 r stores issued so far" and, once in ~1000 frames, added a residual row that had
-                // not landed: tools/perm_probe.py).  Hence NO store is issued before the last residual wait -- the finished rows stay in the
-                // residual's registers and go out together below -- and the counts are the younger LOADS alone: rows 0, 1 -- the last chunk's
-                // T - 9 requests and the 8 requests of rows 2, 3 (a lower bound for all but the youngest quad); rows 2, 3 -- the quads behind
-                pp_steps<0, 4>([&](auto Y_) {
-                    constexpr int y = decltype(Y_)::value;
-                    w6_wait<(r < 2 ? C::T - 9 + 8 : 7 - (4 * (r - 2) + y))>(rq[r][y]);
-                });
-#pragma unroll
-                for (int y = 0; y < 4; ++y) {
-                    const f32x4 v = Y[y] + rq[r][y];
-                    rq[r][y] = v;
-                    sv += v;
-                    qv = __builtin_elementwise_fma(v, v, qv);
+        });
+        // the residual rows were requested a whole chunk ago (T operations younger than the last of them)
+        __syncthreads();
+        // row half for M-tile WV: T[i] (float4 over x) from the four waves, Y[y] = sum_i A^T[y][i] T[i]
+        float ssum[4], ssq[4];
+        pp_steps<0, 4>([&](auto R_) {
+            constexpr int r = decltype(R_)::value;
+            f32x4 T[6], TH[2][2]; // TH[row 1 | row 4][left | right]
+            auto own4 = [&](const f32x2 (&o)[4][2]) { return (f32x4){o[0][r >> 1][r & 1], o[1][r >> 1][r & 1], o[2][r >> 1][r & 1], o[3][r >> 1][r & 1]}; };
+            pp_steps<0, 4>([&](auto W_) {
+                constexpr int w = decltype(W_)::value;
+                constexpr int irow = w == 0 ? 0 : w == 1 ? 2 : w == 2 ? 3 : 5;
+                if constexpr (w == WV) { T[irow] = own4(ownF); TH[w >> 1][w & 1] = own4(ownH); }
+                else {
+                    constexpr int src = w - (w > WV ? 1 : 0);
+                    T[irow] = *reinterpret_cast<const f32x4*>(xb + ((((WV * 3 + src) * 2 + 0) * 4 + r) * 64 + lane) * 4);
+                    TH[w >> 1][w & 1] = *reinterpret_cast<const f32x4*>(xb + ((((WV * 3 + src) * 2 + 1) * 4 + r) * 64 + lane) * 4);
                 }
-                ssum[r] = pix_ok ? (sv[0] + sv[1]) + (sv[2] + sv[3]) : 0.f;
-                ssq[r] = pix_ok ? (qv[0] + qv[1]) + (qv[2] + qv[3]) : 0.f;
             });
-            if constexpr (!(PP_W6_DIAG & 1024)) {
+            T[1] = TH[0][0] + TH[0][1];
+            T[4] = TH[1][0] + TH[1][1];
+            const f32x4 s12 = T[1] + T[2], d12 = T[1] - T[2], s34 = T[3] + T[4], d34 = T[3] - T[4];
+            f32x4 Y[4];
+            Y[0] = T[0] + s12 + s34;
+            Y[1] = __builtin_elementwise_fma(d34, (f32x4){2.f, 2.f, 2.f, 2.f}, d12);
+            Y[2] = __builtin_elementwise_fma(s34, (f32x4){4.f, 4.f, 4.f, 4.f}, s12);
+            Y[3] = __builtin_elementwise_fma(d34, (f32x4){8.f, 8.f, 8.f, 8.f}, d12) + T[5];
+            f32x4 sv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f};
+            // residual rows of r.  vmcnt orders loads among loads and stores among stores, NOT one against the other: a younger store that
+            // completes first lowers the counter, so a count that allows for pending stores proves nothing about an older load (the first
+            // version waited for rows 2, 3 with "the 4 r stores issued so far" and, once in ~1000 frames, added a residual row that had
+            // not landed: tools/perm_probe.py).  Hence NO store is issued before the last residual wait -- the finished rows stay in the
+            // residual's registers and go out together below -- and the counts are the younger LOADS alone: rows 0, 1 -- the last chunk's
+            // T - 9 requests and the 8 requests of rows 2, 3 (a lower bound for all but the youngest quad); rows 2, 3 -- the quads behind
+            pp_steps<0, 4>([&](auto Y_) {
+                constexpr int y = decltype(Y_)::value;
+                w6_wait<(r < 2 ? C::T - 9 + 8 : 7 - (4 * (r - 2) + y))>(rq[r][y]);
+            });
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int y = 0; y < 4; ++y)
-                        asm volatile(W6_SGPR_PAD "buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" :: "v"(rq[r][y]), "v"(lb), "s"(rout), "s"((unsigned)r * plane_ob + (unsigned)y * row_ob) : "memory");
+            for (int y = 0; y < 4; ++y) {
+                const f32x4 v = Y[y] + rq[r][y];
+                rq[r][y] = v;
+                sv += v;
+                qv = __builtin_elementwise_fma(v, v, qv);
             }
-#if PP_W6_DIAG & 512
-            { unsigned long long e2b_ = 0; W6_STAMP(e2b_) st_epi4 += e2b_ - e2_; }
-#endif
-            if (p.stat_acc) {
-                // ONE atomic instruction per wave and tile: after the row reductions every lane of a 16-lane row holds the row's four (sum, sum of
-                // squares) pairs; lane m < 8 of each row adds component m & 1 of accumulator row m >> 1, so the 32 values of the wave's 16
-                // channels go out as 32 lanes of one global_atomic_add_f64 (eight instructions of 4 lanes each cost 0.2 ms of a 2 ms launch:
-                // a CU retires about one atomic wave-instruction per 50 ns whatever its lane count)
-                float sel[4];
+            ssum[r] = pix_ok ? (sv[0] + sv[1]) + (sv[2] + sv[3]) : 0.f;
+            ssq[r] = pix_ok ? (qv[0] + qv[1]) + (qv[2] + qv[3]) : 0.f;
+        });
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float s = row16_sum(ssum[r]), q = row16_sum(ssq[r]);
-                    sel[r] = (m & 1) ? q : s;
-                }
-                const int rr = (m >> 1) & 3;
-                const float v = rr == 0 ? sel[0] : rr == 1 ? sel[1] : rr == 2 ? sel[2] : sel[3];
-                if (m < 8) {
-                    double* dst = p.stat_acc + fz * p.stat_fs + ((size_t)(blockIdx.x % NREP) * p.stat_C + co0 + WV * 16 + kq * 4 + rr) * 2 + (m & 1);
-                    const double dv = (double)v;
-                    asm volatile("global_atomic_add_f64 %0, %1, off\n\ts_nop 1" :: "v"(dst), "v"(dv) : "memory");
-                }
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int y = 0; y < 4; ++y)
+                asm volatile(W6_SGPR_PAD "buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" :: "v"(rq[r][y]), "v"(lb), "s"(rout), "s"((unsigned)r * plane_ob + (unsigned)y * row_ob) : "memory");
+        if (p.stat_acc) {
+            // ONE atomic instruction per wave and tile: after the row reductions every lane of a 16-lane row holds the row's four (sum, sum of
+            // squares) pairs; lane m < 8 of each row adds component m & 1 of accumulator row m >> 1, so the 32 values of the wave's 16
+            // channels go out as 32 lanes of one global_atomic_add_f64 (eight instructions of 4 lanes each cost 0.2 ms of a 2 ms launch:
+            // a CU retires about one atomic wave-instruction per 50 ns whatever its lane count)
+            float sel[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float s = row16_sum(ssum[r]), q = row16_sum(ssq[r]);
+                sel[r] = (m & 1) ? q : s;
             }
-        } else {
-            pp_steps<0, 2>([&](auto R_) { pp_steps<0, 4>([&](auto Y_) { w6_wait<C::T - 9>(rq[decltype(R_)::value][decltype(Y_)::value]); }); });
+            const int rr = (m >> 1) & 3;
+            const float v = rr == 0 ? sel[0] : rr == 1 ? sel[1] : rr == 2 ? sel[2] : sel[3];
+            if (m < 8) {
+                double* dst = p.stat_acc + fz * p.stat_fs + ((size_t)(blockIdx.x % NREP) * p.stat_C + co0 + WV * 16 + kq * 4 + rr) * 2 + (m & 1);
+                const double dv = (double)v;
+                asm volatile("global_atomic_add_f64 %0, %1, off\n\ts_nop 1" :: "v"(dst), "v"(dv) : "memory");
+            }
         }
         // buffer 3 for the next tile's second chunk (see the chunk body)
         pp_steps<0, 9>([&](auto J) { w6_load_A<decltype(J)::value, 3>(rw, wlane, w_off(wb_next_item + chunk_wb, 1, decltype(J)::value), A3[decltype(J)::value]); });
-#if PP_W6_DIAG & 512
-        W6_STAMP(e3_)
-        st_epi1 += e1_ - e0_; st_epi2 += e2_ - e1_; st_epi3 += e3_ - e2_; st_tiles += 1;
-#endif
     }
-#if PP_W6_DIAG & 512
-    if (lane == 0 && p.dbg_buf) {
-        unsigned long long* q = p.dbg_buf + WV * 24;
-        atomicAdd(q + 0, st_top); atomicAdd(q + 1, st_k0); atomicAdd(q + 2, st_k1); atomicAdd(q + 3, st_bar); atomicAdd(q + 4, st_epi1); atomicAdd(q + 5, st_epi2);
-        atomicAdd(q + 6, st_epi3); atomicAdd(q + 7, st_n); atomicAdd(q + 8, st_tiles);
-        for (int g_ = 0; g_ < 9; ++g_) atomicAdd(q + 9 + g_, st_g[g_]);
-        atomicAdd(q + 18, st_epi4); atomicAdd(q + 19, st_adv_t); atomicAdd(q + 20, st_adv_n); atomicAdd(q + 21, st_adv_s);
-    }
-#endif
     w6_wait<0>(); // nothing of this wave's requests may land in registers a successor workgroup owns
 #undef W6_LOAD_PIECE
 #undef W6_NORM_PIECE
@@ -825,7 +737,7 @@ Variant make_wino6(bool roofline_layer)
     v.bm = C::BM; v.bmp = C::BM; v.pw = C::PW; v.ph = C::PH; v.kc = C::KC; v.threads = C::THREADS;
     v.waves = 4; v.pairs = 4 * 9;
     v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    v.wino = 6;
+    v.family = Family::Wino6;
     snprintf(v.name, sizeof(v.name), "wino6 tw%d", TWT);
     return v;
 }

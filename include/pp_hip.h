@@ -245,7 +245,7 @@ double pp_dominant_executed_ratio(pp_ctx* ctx);
 int pp_stage_profile_begin(pp_ctx* ctx);
 int pp_stage_profile_end(pp_ctx* ctx, double* ms_h);
 /* The network's launch plan as text, one line per conv / deconv / head layer in execution order:
- * "<index> kind=<0 conv3x3|1 deconv|2 head> cin= cout= stride= up= level= wino=<0 direct|1,2,4 Winograd|3 1x1 GEMM> tiling=<name>".
+ * "<index> kind=<0 conv3x3|1 deconv|2 head> cin= cout= stride= up= level= wino=<kernel family: 0 direct|1,4,6 Winograd|3 1x1 GEMM|5 16-bit conv> tiling=<name>".
  * Returns the text length (buf may be NULL to query). */
 int pp_layer_tilings(pp_ctx* ctx, char* buf_h, int cap);
 /* The autotuner's table (process-wide) as text, "layer signature<TAB>tiling" per line.  Rank 0 of a multi-GPU job

@@ -1,6 +1,6 @@
 // Stand-alone check + timing of wino6_mfma (csrc/wino6.hip) on ONE layer against a CPU direct convolution.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -munsafe-fp-atomics tools/w6_test.hip -o tools/_build/w6_test
-//   tools/_build/w6_test [C] [H] [W] [B] [twt] [check 0/1] [reps]
+//   tools/_build/w6_test [C] [H] [W] [B] [twt] [check 0/1] [reps] [nostat 0/1] [nores 0/1]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -26,7 +26,7 @@ __global__ void soak_cmp(const unsigned* __restrict__ a, const unsigned* __restr
 int main(int argc, char** argv)
 {
     const int C = argc > 1 ? atoi(argv[1]) : 64, H = argc > 2 ? atoi(argv[2]) : 32, W = argc > 3 ? atoi(argv[3]) : 32, B = argc > 4 ? atoi(argv[4]) : 2;
-    const int twt = argc > 5 ? atoi(argv[5]) : 4, check = argc > 6 ? atoi(argv[6]) : 1, reps = argc > 7 ? atoi(argv[7]) : 3, dbg = argc > 8 ? atoi(argv[8]) : 0, nostat = argc > 9 ? atoi(argv[9]) : 0, nores = argc > 10 ? atoi(argv[10]) : 0;
+    const int twt = argc > 5 ? atoi(argv[5]) : 4, check = argc > 6 ? atoi(argv[6]) : 1, reps = argc > 7 ? atoi(argv[7]) : 3, nostat = argc > 8 ? atoi(argv[8]) : 0, nores = argc > 9 ? atoi(argv[9]) : 0;
     const int Cout = C;
     std::mt19937 rng(1);
     std::normal_distribution<float> nd(0.f, 1.f);
@@ -52,12 +52,10 @@ int main(int argc, char** argv)
     CK(hipMemcpy(dres, res.data(), B * fs * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(dsc, sc.data(), C * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(dsh, sh.data(), C * 4, hipMemcpyHostToDevice));
     CK(hipMemset(dst, 0, B * stat_fs * 8)); CK(hipMemset(dy, 0xff, B * fs * 4));
-    unsigned long long* dbgb; CK(hipMalloc(&dbgb, 96 * 8)); CK(hipMemset(dbgb, 0, 96 * 8));
     ConvP p; memset(&p, 0, sizeof(p));
-    p.dbg_buf = dbgb;
     p.in = dx; p.w = dw; p.out = dy; p.res = dres; p.Cin = C; p.Hin = H; p.Win = W; p.Cout = Cout; p.Hout = H; p.Wout = W;
     p.pre = PRE_AFFINE; p.pre_scale = dsc; p.pre_shift = dsh; p.aff_fs = 0; p.stat_acc = dst; p.stat_C = C; p.stat_fs = stat_fs;
-    p.dbg = dbg; if (nostat) p.stat_acc = nullptr; if (nores) p.res = nullptr; p.in_fs = fs; p.out_fs = fs; p.res_fs = fs; p.nb = B;
+    if (nostat) p.stat_acc = nullptr; if (nores) p.res = nullptr; p.in_fs = fs; p.out_fs = fs; p.res_fs = fs; p.nb = B;
     Variant v = twt == 4 ? make_wino6<4>(false) : twt == 1 ? make_wino6<1>(false) : make_wino6<16>(false);
     p.rx0 = 0; p.ry0 = 0; p.rx1 = W; p.ry1 = H; p.rnbx = (W + v.pw - 1) / v.pw; p.rnby = (H + v.ph - 1) / v.ph;
     const int total = p.rnbx * p.rnby * (Cout / 64) * B;
@@ -73,21 +71,8 @@ int main(int argc, char** argv)
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= reps;
     const double exec = 2.0 * plane * C * Cout * 2.25 * B;
-    printf("nostat %d nores %d diag %d dbg %d %s C=%d %dx%d B=%d grid=%d: %.3f ms/launch, executed %.1f TFLOP/s (%.3f of 157.3), algorithmic %.1f\n", nostat, nores, PP_W6_DIAG, dbg, v.name, C, H, W, B, g, ms, exec / ms * 1e-9,
+    printf("nostat %d nores %d %s C=%d %dx%d B=%d grid=%d: %.3f ms/launch, executed %.1f TFLOP/s (%.3f of 157.3), algorithmic %.1f\n", nostat, nores, v.name, C, H, W, B, g, ms, exec / ms * 1e-9,
            exec / ms * 1e-9 / 157.3, exec * 4 / ms * 1e-9);
-#if PP_W6_DIAG & 512
-    {
-        unsigned long long h[96]; CK(hipMemcpy(h, dbgb, sizeof(h), hipMemcpyDeviceToHost));
-        for (int wv = 0; wv < 4; ++wv) {
-            const unsigned long long* q = h + wv * 24; const double n = (double)q[7], t = (double)q[8];
-            printf("  wave %d: per chunk: top %.0f  k-step0 %.0f  k-step1 %.0f  barrier %.0f | per tile: epi sender %.0f  wait+barrier %.0f  receiver %.0f | k-step0 groups:", wv,
-                   q[0] / n, q[1] / n, q[2] / n, q[3] / n, q[4] / t, q[5] / t, q[6] / t);
-            for (int g = 0; g < 9; ++g) printf(" %.0f", q[9 + g] / n);
-            printf(" | receiver up to the stores %.0f | advance: tile change %.0f (x%.0f), else %.0f per chunk", q[18] / t, q[19] / (double)(q[20] ? q[20] : 1), (double)q[20], q[21] / n);
-            printf("\n");
-        }
-    }
-#endif
     if (const char* sk = getenv("W6_SOAK")) { // W6_SOAK=<launches>: repeat the launch and compare output + statistics with the first one's
         const int n_soak = atoi(sk);
         float* dref; double* sref; unsigned long long* dres;
