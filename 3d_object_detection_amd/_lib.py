@@ -8,6 +8,9 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libpp_hip.so")
 PP_MAX_CLASSES = 12
 PP_LOSS_TERMS = 21
 PP_ASSIGN_MAX_GT = 4096
+PP_AUG_MAX_BOXES = 256
+PP_AUG_MAX_TRIES = 128
+PP_AUG_PARAMS = 16
 
 c_f = ctypes.c_float
 c_i32 = ctypes.c_int32
@@ -63,6 +66,12 @@ PROTOTYPES = {
     "pp_assign_targets": (ctypes.c_int, [c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_target_loss": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p]),
     "pp_batch_loss": (ctypes.c_int, [c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p]),
+    "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
+    "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),
+    "pp_augment_boxes": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
+    "pp_augment_points": (ctypes.c_int, [c_p, c_p, c_p, ctypes.POINTER(c_i32), c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int,
+                                         c_p, c_p]),
     "pp_box_decode": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p]),
     "pp_corners2d": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_p]),
     "pp_standup2d": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),

@@ -466,6 +466,114 @@ class Engine:
                        self.ctx, "pp_batch_loss")
         return terms
 
+    # ------------------------------------------------------------------ training-input augmentation (augment.hip)
+    @staticmethod
+    def _csr(off, n_rows, what, per_frame=None):
+        """Host CSR offsets [nb+1]: non-decreasing ints from 0 to n_rows, at most per_frame rows per frame."""
+        off = [int(v) for v in off]
+        nb = len(off) - 1
+        if nb < 1 or off[0] != 0 or off[-1] != n_rows or any(b < a for a, b in zip(off, off[1:])):
+            raise ValueError(f"{what}: offsets must be {max(nb, 1) + 1} non-decreasing values from 0 to {n_rows}")
+        if per_frame is not None and any(b - a > per_frame for a, b in zip(off, off[1:])):
+            raise ValueError(f"{what}: more than {per_frame} boxes in one frame (PP_AUG_MAX_BOXES)")
+        return (ctypes.c_int32 * (nb + 1))(*off), nb
+
+    def _aug_boxes(self, boxes, valid, box_off, what):
+        G = int(boxes.shape[0]) if boxes.dim() == 2 else -1
+        boxes = _chk(boxes, torch.float32, (G, 7), what + ": boxes")
+        valid = _chk(valid.view(torch.uint8) if valid.dtype == torch.bool else valid, torch.uint8, (G,), what + ": valid")
+        if G > _lib.PP_ASSIGN_MAX_GT:
+            raise ValueError(f"{what}: {G} boxes exceed the capacity {_lib.PP_ASSIGN_MAX_GT}")
+        off, nb = self._csr(box_off, G, what + ": box offsets", _lib.PP_AUG_MAX_BOXES)
+        return boxes, valid, off, nb, G
+
+    def augment_noise(self, boxes, valid, loc, rot, grot, box_off):
+        """pp_augment_noise: boxes f32[G,7], valid u8/bool[G], loc f64[G,T,3], rot / grot f64[G,T], box_off host ints [nb+1] ->
+        sel i32[G] (chosen try or -1), sel_loc f64[G,3], sel_rot f64[G]."""
+        boxes, valid, off, nb, G = self._aug_boxes(boxes, valid, box_off, "augment_noise")
+        T = int(loc.shape[1]) if loc.dim() == 3 else -1
+        if not 1 <= T <= _lib.PP_AUG_MAX_TRIES:
+            raise ValueError(f"augment_noise: tries per box must be 1 .. {_lib.PP_AUG_MAX_TRIES}")
+        loc = _chk(loc, torch.float64, (G, T, 3), "augment_noise: loc")
+        rot = _chk(rot, torch.float64, (G, T), "augment_noise: rot")
+        grot = _chk(grot, torch.float64, (G, T), "augment_noise: grot")
+        sel = self._t((G,), torch.int32)
+        sel_loc = self._t((G, 3), torch.float64)
+        sel_rot = self._t((G,), torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_augment_noise(self.ctx, _ptr(boxes), _ptr(valid), _ptr(loc), _ptr(rot), _ptr(grot), T, off, nb, _ptr(sel),
+                                                 _ptr(sel_loc), _ptr(sel_rot), _stream()), self.ctx, "pp_augment_noise")
+        return sel, sel_loc, sel_rot
+
+    def augment_draw(self, seed, epoch, samples, steps, box_off, num_try=100):
+        """pp_augment_draw (device random mode): the draws of nb frames keyed by (seed, epoch, samples[f]) -> loc f64[G,T,3], rot and
+        grot f64[G,T], prm f64[nb, PP_AUG_PARAMS] (steps in prm[0], the permutation key in prm[11:13])."""
+        samples = [int(s) for s in samples]
+        nb = len(samples)
+        G = int(box_off[-1]) if len(box_off) else 0
+        off, nbo = self._csr(box_off, G, "augment_draw: box offsets", _lib.PP_AUG_MAX_BOXES)
+        if nbo != nb:
+            raise ValueError("augment_draw: one sample index per frame")
+        if G > _lib.PP_ASSIGN_MAX_GT:
+            raise ValueError(f"augment_draw: {G} boxes exceed the capacity {_lib.PP_ASSIGN_MAX_GT}")
+        if not 0 <= int(epoch) < (1 << 24) or not 0 <= int(seed) < (1 << 64) or any(s < 0 for s in samples):
+            raise ValueError("augment_draw: seed must fit 64 bits, epoch 24 bits, sample indices must be >= 0")
+        if not 1 <= int(num_try) <= _lib.PP_AUG_MAX_TRIES:
+            raise ValueError(f"augment_draw: tries per box must be 1 .. {_lib.PP_AUG_MAX_TRIES}")
+        T = int(num_try)
+        loc = self._t((G, T, 3), torch.float64)
+        rot = self._t((G, T), torch.float64)
+        grot = self._t((G, T), torch.float64)
+        prm = self._t((nb, _lib.PP_AUG_PARAMS), torch.float64)
+        sh = (ctypes.c_int64 * nb)(*samples)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_augment_draw(self.ctx, int(seed), int(epoch), sh, int(steps), T, off, nb, _ptr(loc), _ptr(rot), _ptr(grot),
+                                                _ptr(prm), _stream()), self.ctx, "pp_augment_draw")
+        return loc, rot, grot, prm
+
+    def _aug_sel(self, sel_loc, sel_rot, G, what):
+        return (_chk(sel_loc, torch.float64, (G, 3), what + ": sel_loc"), _chk(sel_rot, torch.float64, (G,), what + ": sel_rot"))
+
+    def augment_boxes(self, boxes, classes, valid, sel_loc, sel_rot, prm, box_off, bv_range):
+        """pp_augment_boxes: the box side of the chain on nb frames; prm f64[nb, PP_AUG_PARAMS], bv_range (x0, y0, x1, y1) ->
+        boxes f32[G,7] and classes i32[G] kept in order at the start of each frame's slot, keep u8[G], kept i32[nb]."""
+        boxes, valid, off, nb, G = self._aug_boxes(boxes, valid, box_off, "augment_boxes")
+        classes = _chk(classes, torch.int32, (G,), "augment_boxes: classes")
+        sel_loc, sel_rot = self._aug_sel(sel_loc, sel_rot, G, "augment_boxes")
+        prm = _chk(prm, torch.float64, (nb, _lib.PP_AUG_PARAMS), "augment_boxes: prm")
+        rg = np.ascontiguousarray(bv_range, dtype=F32)
+        if rg.shape != (4,):
+            raise ValueError("augment_boxes: bv_range must be (x0, y0, x1, y1)")
+        out = self._t((G, 7), torch.float32)
+        out_cls = self._t((G,), torch.int32)
+        keep = self._t((G,), torch.uint8)
+        kept = self._t((nb,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_augment_boxes(self.ctx, _ptr(boxes), _ptr(classes), _ptr(valid), _ptr(sel_loc), _ptr(sel_rot), _ptr(prm),
+                                                 rg.ctypes.data_as(ctypes.c_void_p), off, nb, _ptr(out), _ptr(out_cls), _ptr(keep), _ptr(kept),
+                                                 _stream()), self.ctx, "pp_augment_boxes")
+        return out, out_cls, keep, kept
+
+    def augment_points(self, points, perm, pt_off, boxes, valid, sel_loc, sel_rot, prm, box_off):
+        """pp_augment_points: points f32[P,4] of nb frames (pt_off host ints [nb+1]), perm i32[P] frame-local (None: identity; not
+        validated -- checking a device permutation would cost a sync; an entry outside the frame reads row k, never another frame) ->
+        f32[P,4], row k of a frame = its input row perm[k] after the box move and the global chain."""
+        boxes, valid, boff, nb, G = self._aug_boxes(boxes, valid, box_off, "augment_points")
+        P = int(points.shape[0]) if points.dim() == 2 else -1
+        points = _chk(points, torch.float32, (P, 4), "augment_points: points")
+        poff, nbp = self._csr(pt_off, P, "augment_points: point offsets")
+        if nbp != nb:
+            raise ValueError("augment_points: point and box offsets describe different frame counts")
+        if perm is not None:
+            perm = _chk(perm, torch.int32, (P,), "augment_points: perm")
+        sel_loc, sel_rot = self._aug_sel(sel_loc, sel_rot, G, "augment_points")
+        prm = _chk(prm, torch.float64, (nb, _lib.PP_AUG_PARAMS), "augment_points: prm")
+        out = self._t((P, 4), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_augment_points(self.ctx, _ptr(points), _ptr(perm), poff, _ptr(boxes), _ptr(valid), _ptr(sel_loc), _ptr(sel_rot),
+                                                  _ptr(prm), boff, nb, _ptr(out), _stream()), self.ctx, "pp_augment_points")
+        return out
+
     def dominant_kernel(self):
         return self.lib.pp_dominant_kernel(self.ctx).decode()
 

@@ -201,6 +201,46 @@ int pp_rotated_iou(const float* boxes_a /*[n,5]*/, const float* boxes_b /*[m,5]*
 int pp_unpack_points(const void* data, int64_t n, int64_t width, int64_t row_step, int point_step, const int32_t* offs /*[4]*/,
                      const int32_t* dtypes /*[4]*/, int big_endian, float* out /*[n,4]*/, void* stream);
 
+/* ---- training-input augmentation (framework/dataset.py:121-146, augmentation.py, box_np_ops.py:6-16,102-104,460-467) ----
+ * All three run nb frames on `stream` with no host synchronisation.  box_off_h / pt_off_h: HOST i32[nb+1] CSR offsets (frame f owns
+ * box rows box_off_h[f] .. box_off_h[f+1]-1; at most PP_AUG_MAX_BOXES per frame and PP_ASSIGN_MAX_GT in all).  boxes f32[G][7]
+ * (x, y, z, l, w, h, r) as the reference's gt_boxes, valid u8[G] its valid_mask (GenericDataset passes the class mask of ALL
+ * annotations, so box i reads entry i of the unfiltered list).  prm f64[nb][PP_AUG_PARAMS] per frame: PP_AUG_ON holds step bits
+ * (1 box noise move, 2 flip, 4 rotations, 8 scaling, 16 translation, 32 range filter + limit_period, 64 permutation from the
+ * keyed Feistel bijection of prm[PP_AUG_KEY_LO / _HI] instead of perm; 0: points only permuted by perm), then flip, pitch / roll /
+ * yaw in radians (the reference's `deg / 180 * np.pi`), the three scales and the three translations, as the reference draws them. */
+#define PP_AUG_MAX_BOXES 256 /* boxes per frame (LDS of the noise and points kernels) */
+#define PP_AUG_MAX_TRIES 128 /* noise tries per box (one lane each; the reference uses 100) */
+#define PP_AUG_PARAMS 16
+enum { PP_AUG_ON = 0, PP_AUG_FLIP = 1, PP_AUG_PITCH = 2, PP_AUG_ROLL = 3, PP_AUG_YAW = 4, PP_AUG_SX = 5, PP_AUG_SY = 6, PP_AUG_SZ = 7,
+       PP_AUG_TX = 8, PP_AUG_TY = 9, PP_AUG_TZ = 10, PP_AUG_KEY_LO = 11, PP_AUG_KEY_HI = 12 };
+/* device random mode: fills loc f64[G][num_try][3], rot / grot f64[G][num_try] and prm f64[nb][PP_AUG_PARAMS] (steps -> PP_AUG_ON;
+ * the permutation key in PP_AUG_KEY_LO / _HI) from Philox4x32-10 keyed by seed, counter (element, stream | epoch << 8, sample_h[f]):
+ * HOST i64[nb] sample indices, epoch < 2^24.  53-bit uniforms, float64 Box-Muller normals, the reference's ranges.  A frame's draws
+ * depend only on (seed, epoch, sample index).  Replaces the host draws and the permutation upload of the numpy mode. */
+int pp_augment_draw(pp_ctx* ctx, uint64_t seed, uint32_t epoch, const int64_t* sample_h, int steps, int num_try, const int32_t* box_off_h,
+                    int nb, double* loc, double* rot, double* grot, double* prm, void* stream);
+/* replaces noise_per_box_v2_ + box_collision_test (augmentation.py:122-175,617-697) as noise_per_object (:177-212) calls them:
+ * loc f64[G][num_try][3], rot and grot f64[G][num_try] (the reference's loc_noises, rot_noises, global_rot_noises) -> sel i32[G]
+ * (chosen try, -1 if none or not valid), sel_loc f64[G][3], sel_rot f64[G] (_select_transform's loc / rot rows with the
+ * dst_pos / dst_grot corrections; 0 when sel is -1).  Containment without an edge crossing is a collision (numba semantics). */
+int pp_augment_noise(pp_ctx* ctx, const float* boxes, const uint8_t* valid, const double* loc, const double* rot, const double* grot,
+                     int num_try, const int32_t* box_off_h, int nb, int32_t* sel, double* sel_loc, double* sel_rot, void* stream);
+/* replaces box3d_transform_ (:419-425), random_flip, global_rotation_v2, global_scaling_v2, global_translate on the boxes, then
+ * filter_gt_box_outside_range against range_h (HOST f32[4]: x0, y0, x1, y1) and limit_period(r, 0.5, 2 pi) (dataset.py:136-143).
+ * Outputs: keep u8[G]; the kept boxes f32[G][7] and their classes i32[G] (from cls i32[G]) compacted in order at the start of each
+ * frame's slot, zero behind; kept i32[nb] per frame. */
+int pp_augment_boxes(pp_ctx* ctx, const float* boxes, const int32_t* cls, const uint8_t* valid, const double* sel_loc,
+                     const double* sel_rot, const double* prm, const float* range_h, const int32_t* box_off_h, int nb, float* out,
+                     int32_t* out_cls, uint8_t* keep, int32_t* kept, void* stream);
+/* replaces points_in_rbbox + points_transform_ (box_np_ops.py:460-467, augmentation.py:400-416), the global functions on the points
+ * and np.random.shuffle (dataset.py:146): out row k (f32[P][4], P = pt_off_h[nb]) of frame f is frame f's input row perm[k]
+ * (i32[P], frame-local, not validated: an entry outside [0, n) reads row k; NULL: identity) moved by the first VALID box (original boxes, before the noise) containing it, then by the
+ * global chain.  Feature 3 passes through. */
+int pp_augment_points(pp_ctx* ctx, const float* pts, const int32_t* perm, const int32_t* pt_off_h, const float* boxes,
+                      const uint8_t* valid, const double* sel_loc, const double* sel_rot, const double* prm, const int32_t* box_off_h,
+                      int nb, float* out, void* stream);
+
 /* ---- evaluation ----
  * pp_rotated_iou_eval replaces rotate_iou_gpu_eval (eval/iou.py:540-638): out[i,j] for box i and query j with
  * criterion -1: IoU, 0: inter / area(query), 1: inter / area(box), 2: intersection area -- the reference's kernel
