@@ -66,6 +66,9 @@ PROTOTYPES = {
     "pp_assign_targets": (ctypes.c_int, [c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_target_loss": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p]),
     "pp_batch_loss": (ctypes.c_int, [c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p]),
+    "pp_target_loss_grad": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.c_int, c_f, c_p, c_p, c_p, c_p]),
+    "pp_head_backward": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_update_head_weights": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),

@@ -3318,6 +3318,55 @@ extern "C" int pp_head(pp_ctx* ctx, const float* rpn_out, float* cls, float* box
     return pp_head_impl(ctx, rpn_out, raw, cls, box, dir, 1, stream);
 }
 
+// The head's packed weight image as an index map (pp_common.h): pack_layer itself packs an index-valued weight (element i of the
+// natural [cls | box | dir][320] order holds the float i + 1; exact below 2^24) into a scratch image with the committed tiling, so
+// whatever row order (head_tile_row), row padding and K blocking that tiling uses is read back, not restated.  fp32 images only:
+// the 16-bit images round their elements, the indices would not survive.  Synchronous; called once per commit by train.hip.
+int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    Layer& head = net->layers.back();
+    if (net->eff_prec != 0 || head.var.prec != 0 || head.var.io16 != 0)
+        return pp_fail(ctx, PP_E_ARG, "head weights can be rewritten in place in the fp32 mode only (the committed plan packs the head in a 16-bit format)");
+    const int na = ctx->cfg.num_anchor_per_loc;
+    const char* names[3] = {"heads.conv_cls.weight", "heads.conv_box.weight", "heads.conv_dir.weight"};
+    const int cnt[3] = {na, 7 * na, 2 * na};
+    std::vector<float> saved[3];
+    float idx = 1.f;
+    for (int h = 0; h < 3; ++h) {
+        auto w = ctx->host_w.find(names[h]);
+        if (w == ctx->host_w.end() || (int64_t)w->second.data.size() != (int64_t)cnt[h] * head.cin)
+            return pp_fail(ctx, PP_E_NAME, (std::string("missing/mis-shaped weight ") + names[h]).c_str());
+        saved[h] = w->second.data;
+        for (float& v : w->second.data) v = idx++;
+    }
+    Layer scratch = head;
+    scratch.w = nullptr;
+    int rc = pack_layer(ctx, scratch);
+    for (int h = 0; h < 3; ++h) ctx->host_w[names[h]].data.swap(saved[h]);
+    if (rc) { if (scratch.w) (void)hipFree(scratch.w); return rc; }
+    size_t bytes = 0;
+    hipError_t e = hipMemPtrGetInfo(scratch.w, &bytes);
+    std::vector<float> image(bytes / sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(image.data(), scratch.w, image.size() * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(scratch.w);
+    PP_HIP(e);
+    img->wmap.resize(image.size());
+    for (size_t i = 0; i < image.size(); ++i) img->wmap[i] = (int32_t)image[i] - 1;
+    img->w = head.w;
+    img->bias = net->head_bias;
+    img->bmap.assign((size_t)head_rows(na), -1);
+    for (int r = 0; r < 10 * na; ++r) img->bmap[r] = r;
+    img->bias_perm = nullptr;
+    img->bpmap.clear();
+    if (na == 9) {
+        img->bias_perm = net->head_bias_perm;
+        img->bpmap.resize(96);
+        for (int t = 0; t < 96; ++t) img->bpmap[t] = head_tile_row(t);
+    }
+    return 0;
+}
+
 // Test / inspection hook: copy one tensor of frame `frame` of the LAST pp_infer_batch / pp_infer_frame pass out of the
 // context's internal frame buffers (device -> device, on `stream`).  kind: 0 cls f32[A], 1 box f32[A,7], 2 dir f32[A,2],
 // 3 anchor mask u8[A], 4 rpn output f32[320,H,W] = relu(norm(concat)) as RPN.forward returns it

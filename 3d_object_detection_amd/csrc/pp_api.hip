@@ -196,6 +196,7 @@ extern "C" void pp_destroy(pp_ctx* ctx)
     pp_net_destroy(ctx);
     pp_post_destroy(ctx);
     pp_assign_destroy(ctx);
+    pp_train_destroy(ctx);
     for (pp_slot& S : ctx->slot) {
         void* sp[] = {S.cell_first, S.pt_cell, S.pt_rank, S.wave_cnt, S.occ};
         for (void* q : sp)
@@ -264,6 +265,7 @@ extern "C" int pp_commit_weights(pp_ctx* ctx)
     int rc = pp_net_commit(ctx);
     if (rc) return rc;
     ctx->weights_ready = true;
+    ++ctx->commit_gen;
     return 0;
 }
 

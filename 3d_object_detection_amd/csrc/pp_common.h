@@ -122,6 +122,10 @@ struct pp_ctx {
     bool asg_thr_set = false;
     float asg_thr_m[PP_MAX_CLASSES] = {}, asg_thr_u[PP_MAX_CLASSES] = {};
     void* asg = nullptr;
+    // ---- loss gradient / head backward (train.hip): workspace allocated on first use; commit_gen counts pp_commit_weights calls so
+    //      the natural-order copy of the head weights and the index map of the head's packed image are rebuilt after a commit ----
+    uint64_t commit_gen = 0;
+    void* trn = nullptr;
 };
 // stage ids of pp_stage_mark / pp_stage_profile_end
 enum { PP_ST_VOXELIZE = 0, PP_ST_MASK = 1, PP_ST_PFN = 2, PP_ST_CONV = 3, PP_ST_NORM = 4, PP_ST_HEAD = 5, PP_ST_POST = 6 /* filter + threshold + gather */,
@@ -155,5 +159,15 @@ int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_co
 int pp_run_head_fused(pp_ctx* ctx, float* cls, float* box, float* dir, int nb, hipStream_t stream); // norm+ReLU fused in the prologue
 void pp_post_destroy(pp_ctx* ctx);
 void pp_assign_destroy(pp_ctx* ctx);
+void pp_train_destroy(pp_ctx* ctx);
+// The head's packed weight image and biases of the committed plan (conv.hip), described for pp_update_head_weights (train.hip):
+// wmap[i] is the element of the natural [cls | box | dir][320] weight (state_dict order, rows concatenated) that image element i
+// holds, -1 for padding; bmap / bpmap likewise for the bias in natural order and in gemm1x1's head_tile_row order (bias_perm is
+// null when the plan has no such copy).  PP_E_ARG when the committed plan packs the head in a 16-bit format.
+struct pp_head_image {
+    float *w = nullptr, *bias = nullptr, *bias_perm = nullptr;
+    std::vector<int32_t> wmap, bmap, bpmap;
+};
+int pp_net_head_image(pp_ctx* ctx, pp_head_image* img);
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

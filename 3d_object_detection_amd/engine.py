@@ -311,13 +311,73 @@ class Engine:
         return out
 
     def head(self, rpn_out):
-        _chk(rpn_out.reshape(-1), torch.float32, (320 * self.H * self.W,), "head: rpn_out [1,320,H,W]")
-        cls = self._t((1, self.A, 1), torch.float32)
-        box = self._t((1, self.A, 7), torch.float32)
-        dr = self._t((1, self.A, 2), torch.float32)
+        """pp_head on rpn_out [B,320,H,W] (1 <= B <= max_batch; a [320,H,W] tensor is one frame), one launch per frame."""
+        hw = 320 * self.H * self.W
+        nb = rpn_out.numel() // hw if isinstance(rpn_out, torch.Tensor) else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"head: rpn_out holds {nb} frames of [320,{self.H},{self.W}], max_batch is {self.max_batch}")
+        x = _chk(rpn_out.reshape(-1), torch.float32, (nb * hw,), "head: rpn_out [B,320,H,W]")
+        cls = self._t((nb, self.A, 1), torch.float32)
+        box = self._t((nb, self.A, 7), torch.float32)
+        dr = self._t((nb, self.A, 2), torch.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_head(self.ctx, _ptr(rpn_out), _ptr(cls), _ptr(box), _ptr(dr), _stream()), self.ctx, "pp_head")
+            for f in range(nb):
+                _lib.check(self.lib.pp_head(self.ctx, _ptr(x[f * hw:]), _ptr(cls[f]), _ptr(box[f]), _ptr(dr[f]), _stream()), self.ctx, "pp_head")
         return cls, box, dr
+
+    # ------------------------------------------------------------------ head-only training (train.hip)
+    def head_backward(self, rpn_out, dcls, dbox, ddir, need_dx=True):
+        """pp_head_backward: rpn_out [nb,320,H,W] and the gradients of the head outputs (dcls [nb,A(,1)], dbox [nb,A,7], ddir [nb,A,2],
+        the head's output layout) -> ({state_dict name: gradient} for the six head tensors, summed over the frames, and
+        dL/d(rpn_out) [nb,320,H,W] or None when need_dx is False).  fp32, deterministic."""
+        nb = int(rpn_out.shape[0]) if isinstance(rpn_out, torch.Tensor) and rpn_out.dim() == 4 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"head_backward: rpn_out must be [nb,320,H,W] with 1 <= nb <= max_batch ({self.max_batch})")
+        x = _chk(rpn_out, torch.float32, (nb, 320, self.H, self.W), "head_backward: rpn_out")
+        dcls = _chk(dcls.reshape(nb, -1) if isinstance(dcls, torch.Tensor) else dcls, torch.float32, (nb, self.A), "head_backward: dcls")
+        dbox = _chk(dbox.reshape(nb, -1) if isinstance(dbox, torch.Tensor) else dbox, torch.float32, (nb, self.A * 7), "head_backward: dbox")
+        ddir = _chk(ddir.reshape(nb, -1) if isinstance(ddir, torch.Tensor) else ddir, torch.float32, (nb, self.A * 2), "head_backward: ddir")
+        for t, what in ((x, "rpn_out"), (dcls, "dcls"), (dbox, "dbox"), (ddir, "ddir")):
+            if t.device != self.device:
+                raise ValueError(f"head_backward: {what} is on {t.device}, the engine on {self.device}")
+        na = self.num_anchor_per_loc
+        g = {"heads.conv_cls.weight": self._t((na, 320, 1, 1), torch.float32), "heads.conv_cls.bias": self._t((na,), torch.float32),
+             "heads.conv_box.weight": self._t((7 * na, 320, 1, 1), torch.float32), "heads.conv_box.bias": self._t((7 * na,), torch.float32),
+             "heads.conv_dir.weight": self._t((2 * na, 320, 1, 1), torch.float32), "heads.conv_dir.bias": self._t((2 * na,), torch.float32)}
+        dx = self._t((nb, 320, self.H, self.W), torch.float32) if need_dx else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_head_backward(self.ctx, _ptr(x), _ptr(dcls), _ptr(dbox), _ptr(ddir), nb, _ptr(g["heads.conv_cls.weight"]),
+                                                 _ptr(g["heads.conv_box.weight"]), _ptr(g["heads.conv_dir.weight"]), _ptr(g["heads.conv_cls.bias"]),
+                                                 _ptr(g["heads.conv_box.bias"]), _ptr(g["heads.conv_dir.bias"]), _ptr(dx), _stream()),
+                       self.ctx, "pp_head_backward")
+        return g, dx
+
+    HEAD_KEYS = ("heads.conv_cls.weight", "heads.conv_cls.bias", "heads.conv_box.weight", "heads.conv_box.bias",
+                 "heads.conv_dir.weight", "heads.conv_dir.bias")
+
+    def update_head_weights(self, sd):
+        """pp_update_head_weights: {state_dict name: device tensor} of the six head tensors -> the committed head image, in place on the
+        current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
+        na = self.num_anchor_per_loc
+        rows_of = {"cls": na, "box": 7 * na, "dir": 2 * na}
+        args = {}
+        for k in self.HEAD_KEYS:
+            if k not in sd:
+                raise KeyError(f"update_head_weights: {k} is missing")
+            rows = rows_of[k.split(".")[1][5:]]
+            t = sd[k].detach() if isinstance(sd[k], torch.Tensor) else sd[k]
+            if k.endswith("weight"):
+                if isinstance(t, torch.Tensor) and t.dim() == 4 and t.shape[2:] == (1, 1) and t.is_contiguous():
+                    t = t.reshape(t.shape[0], t.shape[1])
+                t = _chk(t, torch.float32, (rows, 320), "update_head_weights: " + k + " as [rows,320,1,1]")
+            else:
+                t = _chk(t, torch.float32, (rows,), "update_head_weights: " + k)
+            if t.device != self.device:
+                raise ValueError(f"update_head_weights: {k} is on {t.device}, the engine on {self.device}")
+            args[k] = t
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_head_weights(self.ctx, *[_ptr(args[k]) for k in self.HEAD_KEYS], _stream()), self.ctx,
+                       "pp_update_head_weights")
 
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
@@ -456,6 +516,37 @@ class Engine:
             _lib.check(self.lib.pp_target_loss(self.ctx, _ptr(cls), _ptr(box), _ptr(dr), _ptr(labels), _ptr(bbox_targets), _ptr(dir_targets),
                                                nb, _ptr(terms), _stream()), self.ctx, "pp_target_loss")
         return terms
+
+    def target_loss_grad(self, cls, box, dr, labels, bbox_targets, dir_targets, grad_scale=1.0, batch_size=None):
+        """pp_target_loss_grad: gradient of LossGenerator's `loss` with respect to cls [nb,A(,1)], box [nb,A,7], dr [nb,A,2], times
+        grad_scale / batch_size (batch_size: the whole batch when these nb frames are a chunk of it; default nb).  Returns (dcls [nb,A,1],
+        dbox [nb,A,7], ddir [nb,A,2])."""
+        nb = int(labels.shape[0]) if isinstance(labels, torch.Tensor) and labels.dim() == 2 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"target_loss_grad: {nb} frames, max_batch is {self.max_batch}")
+        batch_size = nb if batch_size is None else int(batch_size)
+        if batch_size < nb:
+            raise ValueError(f"target_loss_grad: batch_size {batch_size} is smaller than the {nb} frames passed")
+
+        def flat(t, n, dtype, what):
+            t = _chk(t.reshape(nb, -1) if isinstance(t, torch.Tensor) else t, dtype, (nb, n), "target_loss_grad: " + what)
+            if t.device != self.device:
+                raise ValueError(f"target_loss_grad: {what} is on {t.device}, the engine on {self.device}")
+            return t
+        cls = flat(cls, self.A, torch.float32, "cls_preds")
+        box = flat(box, self.A * 7, torch.float32, "box_preds")
+        dr = flat(dr, self.A * 2, torch.float32, "dir_preds")
+        labels = flat(labels, self.A, torch.int32, "labels")
+        bbox_targets = flat(bbox_targets, self.A * 7, torch.float32, "bbox_targets")
+        dir_targets = flat(dir_targets, self.A, torch.int32, "dir_targets")
+        dcls = self._t((nb, self.A, 1), torch.float32)
+        dbox = self._t((nb, self.A, 7), torch.float32)
+        ddir = self._t((nb, self.A, 2), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_target_loss_grad(self.ctx, _ptr(cls), _ptr(box), _ptr(dr), _ptr(labels), _ptr(bbox_targets),
+                                                    _ptr(dir_targets), nb, batch_size, float(grad_scale), _ptr(dcls), _ptr(dbox), _ptr(ddir),
+                                                    _stream()), self.ctx, "pp_target_loss_grad")
+        return dcls, dbox, ddir
 
     def batch_loss(self, gt_boxes, gt_classes, gt_offsets, nb):
         """pp_batch_loss: assignment + loss for frames 0 .. nb-1 of the last infer_batch / infer_frame pass -> terms f64[nb, PP_LOSS_TERMS]."""

@@ -1,6 +1,8 @@
 """framework.loss_generator.LossGenerator (reference loss_generator.py:26-253): the NormByNumPositives detection loss -- sigmoid focal
 classification (gamma 2, alpha 0.25), smooth-L1 regression (sigma 3, sin difference on the angle code), 2-way softmax direction
-loss -- computed by pp_target_loss (assign.hip) with a deterministic fp64 reduction.  Forward only: the values serve validation."""
+loss -- computed by pp_target_loss (assign.hip) with a deterministic fp64 reduction.  When a prediction requires grad, the `loss` key
+carries a grad_fn whose backward is pp_target_loss_grad (train.hip): the gradient with respect to the three head outputs.  The
+other five keys are values only."""
 import numpy as np
 import torch
 
@@ -28,6 +30,27 @@ def _dev(x, dtype, device):
     return torch.from_numpy(np.ascontiguousarray(x)).to(device=device, dtype=dtype)
 
 
+class _LossFunction(torch.autograd.Function):
+    """`loss` of LossGenerator.generate: forward = the value of the pp_target_loss path, backward = pp_target_loss_grad per chunk of
+    at most max_batch frames, each scaled by the upstream gradient over the WHOLE batch size."""
+
+    @staticmethod
+    def forward(ctx, eng, value, cls, box, dr, labels, tgt, dirt):
+        ctx.eng = eng
+        ctx.save_for_backward(cls, box, dr, labels, tgt, dirt)
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        cls, box, dr, labels, tgt, dirt = ctx.saved_tensors
+        eng, B = ctx.eng, int(labels.shape[0])
+        scale = float(grad)
+        parts = [eng.target_loss_grad(cls[i:i + k], box[i:i + k], dr[i:i + k], labels[i:i + k], tgt[i:i + k], dirt[i:i + k], scale, B)
+                 for i in range(0, B, eng.max_batch) for k in [min(eng.max_batch, B - i)]]
+        dcls, dbox, ddir = (torch.cat([p[j] for p in parts]) for j in range(3))
+        return None, None, dcls.reshape(cls.shape), dbox.reshape(box.shape), ddir.reshape(dr.shape), None, None, None
+
+
 class LossGenerator:
     def __init__(self, config):
         self._box_code_size = config['box_code_size']
@@ -38,7 +61,7 @@ class LossGenerator:
     def generate(self, preds_dict, example):
         """preds_dict: cls_preds [B,A(,1)], box_preds [B,A,7], dir_preds [B,A,2]; example: labels [B,A], bbox_targets [B,A,7],
         dir_targets [B,A] (numpy as the reference's DataLoader yields them, or torch).  Returns the reference's six keys as 0-d
-        float32 tensors on the device."""
+        float32 tensors on the device.  With a prediction that requires grad, `loss` is differentiable (same value, bit for bit)."""
         eng = engine_for(self._config)
         dev = eng.device
         labels = _dev(example['labels'], torch.int32, dev)
@@ -53,4 +76,8 @@ class LossGenerator:
                            for i in range(0, B, eng.max_batch) for k in [min(eng.max_batch, B - i)]])
         self.last_terms = terms
         vals = combine_terms(terms.cpu().numpy())
-        return {k: torch.tensor(vals[k], dtype=torch.float32, device=dev) for k in KEYS}
+        out = {k: torch.tensor(vals[k], dtype=torch.float32, device=dev) for k in KEYS}
+        if torch.is_grad_enabled() and any(isinstance(preds_dict[k], torch.Tensor) and preds_dict[k].requires_grad
+                                           for k in ('cls_preds', 'box_preds', 'dir_preds')):
+            out["loss"] = _LossFunction.apply(eng, out["loss"], cls, box, dr, labels, tgt, dirt)
+        return out

@@ -181,6 +181,39 @@ int pp_target_loss(pp_ctx* ctx, const float* cls, const float* box, const float*
  * PP_E_STATE before the first pass. */
 int pp_batch_loss(pp_ctx* ctx, const float* gt, const int32_t* gt_cls, const int32_t* gt_off_h, int nb, double* terms, void* stream);
 
+/* ---- loss gradient and head backward (train.hip): head-only fine-tuning, the backbone is frozen ----
+ * Gradients are fp32 whatever pp_set_precision says.  Deterministic: no float atomics, two runs on the same inputs are bit-identical.
+ *
+ * pp_target_loss_grad: gradient of the `loss` value of LossGenerator.generate (loss_generator.py:26-72; loc 0.25, cls 1.0, dir 0.2,
+ * NormByNumPositives) with respect to the head outputs.  Inputs as pp_target_loss (all required); dcls f32[nb][A], dbox f32[nb][A][7],
+ * ddir f32[nb][A][2], fully written.  The result is scaled by grad_scale / batch_div: grad_scale is the upstream dL/dloss (1 for
+ * loss.backward()), batch_div the batch size of the loss's 1/B mean -- nb, or the whole batch when the caller passes it in chunks of
+ * at most max_batch frames (batch_div >= nb).  Per anchor, npos = max(#(label > 0) of the frame, 1), counted on the device:
+ * sigmoid focal derivative (gamma 2, alpha 0.25; target label > 0) / npos where label >= 0; smooth-L1 (sigma 3) derivative with the
+ * sin-difference angle code / npos and softmax - onehot / npos where label > 0.  Rows with label == -1 are exact zeros in all three,
+ * rows with label <= 0 in dbox and ddir.  dir and ddir must be 8-byte aligned; 16-byte aligned box tensors and A % 4 == 0 take the
+ * 16-byte path. */
+int pp_target_loss_grad(pp_ctx* ctx, const float* cls, const float* box, const float* dir, const int32_t* labels,
+                        const float* bbox_targets, const int32_t* dir_targets, int nb, int batch_div, float grad_scale, float* dcls,
+                        float* dbox, float* ddir, void* stream);
+/* backward of SharedHead.forward (pointpillars8_shared.py:323-343) for nb frames: rpn_out f32[nb][320][H][W] (what pp_head consumed),
+ * dcls / dbox / ddir in the head's OUTPUT layout (anchor type, x, y; codes innermost) -> dw_cls f32[na][320], dw_box f32[7 na][320],
+ * dw_dir f32[2 na][320], db_cls f32[na], db_box f32[7 na], db_dir f32[2 na] in state_dict order (channel a * 7 + k of conv_box,
+ * a * 2 + k of conv_dir), summed over the nb frames, and dx f32[nb][320][H][W] = dL/d(rpn_out) (NULL: skipped).  fp32-input MFMA, fp32
+ * accumulation.  Each workgroup owns a pixel range of one frame; its [10 na][320] partial is summed with the others in a fixed order,
+ * so the result depends on nb (the ranges do) only within fp32 summation error.  dx uses the committed head weights, or those of the
+ * last pp_update_head_weights.  At most 9 anchors per location.  PP_E_STATE before pp_commit_weights. */
+int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* dcls, const float* dbox, const float* ddir, int nb, float* dw_cls,
+                     float* dw_box, float* dw_dir, float* db_cls, float* db_box, float* db_dir, float* dx, void* stream);
+/* After an optimizer step: six DEVICE tensors in state_dict layout (heads.conv_{cls,box,dir}.{weight,bias}: [na][320], [na], [7 na][320],
+ * [7 na], [2 na][320], [2 na]) -> the head's packed weight image and biases of the committed launch plan, rewritten in place on
+ * `stream` (no host copy, no re-tuning).  pp_head, pp_infer_frame and pp_infer_batch read that image, so all three see the new weights.
+ * The first call after a commit reads the image's layout back once (synchronous).  The host copies of pp_load_weights are NOT changed:
+ * a later pp_commit_weights packs those again.  fp32 mode only: in the 16-bit modes (pp_effective_precision != 0) the packed image
+ * holds rounded / split operands and this returns PP_E_ARG.  PP_E_ARG before the first commit. */
+int pp_update_head_weights(pp_ctx* ctx, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box, const float* w_dir,
+                           const float* b_dir, void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Kernel time of head-only training (csrc/train.hip) on eight_20cm at nb = 1, 8, 32: HIP events around back-to-back C calls whose
+arguments are built beforehand, next to each call's floor -- the larger of its algorithmic HBM bytes / 8 TB/s and, for the head
+backward, its executed MFMA flops / 157.3 TF (the constants bench.py uses).
+
+    python tools/headtrain_probe.py [--frames 1,8,32] [--reps 10]
+    rocprofv3 --kernel-trace --stats -d OUT -o headtrain -- python tools/headtrain_probe.py --frames 8     (per-kernel split: k_count_pos,
+                                                             k_loss_grad, k_head_dw, k_head_dw_reduce, k_head_dx, k_gather3)
+Also timed in the same run: the same head backward in stock PyTorch (conv2d with 90 output channels on [nb,320,H,W], .backward()),
+and one whole fine-tuning step at nb = 8 (frozen forward, loss, backward, SGD step, weight upload).  Prints one JSON line."""
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(ROOT)
+sys.path.insert(0, ROOT)
+HBM_BS, MFMA_FS = 8.0e12, 157.3e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", default="1,8,32")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--no-torch", action="store_true", help="skip the stock PyTorch yardstick and the whole-step line")
+    a = ap.parse_args()
+    frames = [int(v) for v in a.frames.split(",")]
+    pkg = importlib.import_module("3d_object_detection_amd")
+    pkg.install()
+    synth = importlib.import_module("3d_object_detection_amd.synth")
+    shared = importlib.import_module("3d_object_detection_amd.networks.pointpillars8_shared")
+    vgm = importlib.import_module("3d_object_detection_amd.framework.voxel_generator")
+    lgm = importlib.import_module("3d_object_detection_amd.framework.loss_generator")
+    cfg = synth.load_config("eight_20cm")
+    cfg["device"] = torch.device("cuda:0")
+    cfg["max_batch"] = max(frames + [8])
+    vgm.VoxelGenerator(cfg)
+    net = shared.PointPillars(cfg)
+    net.load_state_dict(synth.seeded_state_dict(0, cls_bias=-3.0))
+    eng = net._eng
+    d, A, H, W, na = eng.device, eng.A, eng.H, eng.W, eng.num_anchor_per_loc
+    P = H * W
+    lib, ctx, st = eng.lib, eng.ctx, torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    gen = torch.Generator(device=d).manual_seed(0)
+
+    def timed(fn, reps=a.reps):
+        rc = fn()
+        assert rc in (0, None), rc
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(reps):
+            fn()
+        e.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(e) / reps
+
+    out = {"anchors": A, "map": [H, W], "rows": []}
+    for nb in frames:
+        x = torch.relu(torch.randn((nb, 320, H, W), device=d, generator=gen))
+        cls = torch.randn((nb, A), device=d, generator=gen) * 2 - 3
+        box = torch.randn((nb, A, 7), device=d, generator=gen) * 0.3
+        dr = torch.randn((nb, A, 2), device=d, generator=gen)
+        u = torch.rand((nb, A), device=d, generator=gen)
+        lab = torch.where(u < 0.002, 1, torch.where(u < 0.3, 0, -1)).to(torch.int32)
+        tgt = torch.randn((nb, A, 7), device=d, generator=gen) * 0.3
+        dirt = (torch.rand((nb, A), device=d, generator=gen) < 0.5).to(torch.int32)
+        dcls, dbox, ddir, dx = torch.empty_like(cls), torch.empty_like(box), torch.empty_like(dr), torch.empty_like(x)
+        g = [torch.empty(n, device=d) for n in (na * 320, 7 * na * 320, 2 * na * 320, na, 7 * na, 2 * na)]
+        w = [p.detach().clone() for p in net.parameters()]
+        row = {"frames": nb}
+        row["loss_grad_ms"] = timed(lambda: lib.pp_target_loss_grad(ctx, ptr(cls), ptr(box), ptr(dr), ptr(lab), ptr(tgt), ptr(dirt), nb, nb, 1.0,
+                                                                    ptr(dcls), ptr(dbox), ptr(ddir), st))
+        bw = lambda need_dx: lib.pp_head_backward(ctx, ptr(x), ptr(dcls), ptr(dbox), ptr(ddir), nb, *[ptr(t) for t in g],  # noqa: E731
+                                                  ptr(dx) if need_dx else None, st)
+        row["head_backward_ms"] = timed(lambda: bw(True))
+        row["head_backward_dw_only_ms"] = timed(lambda: bw(False))
+        row["update_head_weights_ms"] = timed(lambda: lib.pp_update_head_weights(ctx, *[ptr(t) for t in w], st))
+        # floors: 29 floats in and out + the label re-read of the count pass per anchor; X read once per product, dY twice, dX written
+        n = nb * A
+        row["loss_grad_floor_ms"] = (29 * 4 + 4) * n / HBM_BS * 1e3
+        by = nb * P * 4 * (320 * 2 + 10 * na * 2 + 320)
+        fl = 2 * 2.0 * 96 * 320 * nb * P  # executed: 96 padded rows, two products
+        row["head_backward_floor_ms"] = max(by / HBM_BS, fl / MFMA_FS) * 1e3
+        row["head_backward_floor_bound"] = "bytes" if by / HBM_BS > fl / MFMA_FS else "flops"
+        if not a.no_torch:
+            conv_w = torch.randn((10 * na, 320, 1, 1), device=d, generator=gen).requires_grad_(True)
+            conv_b = torch.zeros(10 * na, device=d, requires_grad=True)
+            xg = x.clone().requires_grad_(True)
+            gy = torch.randn((nb, 10 * na, H, W), device=d, generator=gen)
+
+            def stock():
+                xg.grad = conv_w.grad = conv_b.grad = None
+                torch.nn.functional.conv2d(xg, conv_w, conv_b).backward(gy)
+            row["torch_conv2d_fwd_bwd_ms"] = timed(stock, max(2, a.reps // 2))
+
+            def stock_fwd():
+                torch.nn.functional.conv2d(x, conv_w.detach(), conv_b.detach())
+            row["torch_conv2d_fwd_ms"] = timed(stock_fwd, max(2, a.reps // 2))
+        out["rows"].append(row)
+        del x, dx
+        torch.cuda.empty_cache()
+    if not a.no_torch:
+        # one whole fine-tuning step at nb = 8: frozen forward of 8 clouds (pp_infer_batch keeps the rpn outputs), head, loss, backward,
+        # SGD step, weight upload at the next forward
+        nb = 8
+        pts = [torch.from_numpy(synth.lidar_cloud("eight_20cm", seed=300 + i)).to(d) for i in range(nb)]
+        u = torch.rand((nb, A), device=d, generator=gen)
+        ex = {"labels": torch.where(u < 0.002, 1, torch.where(u < 0.3, 0, -1)).to(torch.int32),
+              "bbox_targets": torch.randn((nb, A, 7), device=d, generator=gen) * 0.3,
+              "dir_targets": (torch.rand((nb, A), device=d, generator=gen) < 0.5).to(torch.int32)}
+        lg = lgm.LossGenerator(cfg)
+        net.train()
+        opt = torch.optim.SGD(net.parameters(), lr=1e-3)
+        parts = {}
+
+        def step():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            eng.infer_batch(pts)
+            rpn = torch.stack([eng.fetch(f, "rpn") for f in range(nb)])
+            ev[1].record()
+            loss = lg.generate(net.heads(rpn), ex)["loss"]
+            ev[2].record()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            net._sync_head()
+            ev[3].record()
+            torch.cuda.synchronize()
+            for k, i in (("frozen_forward_ms", 0), ("head_and_loss_ms", 1), ("backward_step_upload_ms", 2)):
+                parts[k] = ev[i].elapsed_time(ev[i + 1])
+        step()
+        step()
+        out["step_nb8"] = dict(parts, total_ms=sum(parts.values()))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
