@@ -451,6 +451,7 @@ extern "C" int pp_batch_loss(pp_ctx* ctx, const float* gt, const int32_t* gt_cls
     asg_ws* w = workspace(ctx);
     if (!w) return pp_fail(ctx, -(int)hipErrorOutOfMemory, "pp_batch_loss: workspace allocation failed");
     hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = pp_head_materialise(ctx, stream)) return rc; // a deferred pass left f_box / f_dir stale
     if (int rc = launch_gmax(ctx, w, ctx->f_mask, gt, gt_cls, gt_off_h, nb, stream)) return rc;
     asg_args p = make_args(ctx);
     for (int f0 = 0; f0 < nb; f0 += ASG_GROUP) {

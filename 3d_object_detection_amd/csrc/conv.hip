@@ -1598,15 +1598,21 @@ __device__ __forceinline__ f32x4 mfma_lp(const s16x4 a, const s16x4 b, const f32
 
 // IO16 (pp_set_precision 4, "fp16s": fp16 operands AND fp16 storage of the [320,H,W] concat buffer the upsamplers write and the head
 // reads -- the largest tensor of the network, 205 MB per frame in fp32): bit 0 = the input tensor is fp16, bit 1 = the output is.
-template <int MT, int NT, int EPI, int PREC = 0, int IO16 = 0>
-__global__ void __launch_bounds__(512, 2) gemm1x1(const ConvP p)
+// EPI_HEAD_CLS (deferred head, MT = 1): the head's `na` cls rows alone -- the slab is gathered out of the committed full head image
+// (cls row of anchor a = tile row 4 (9 + a) + 3 of head_tile_row), so there is one weight image and the cls logits are bit-identical to
+// the full head's: same A and B values, same channel-quad order, same bias add.  One MFMA per 256 B loaded: the kernel is bound by the
+// bytes in flight per CU: it runs two workgroups per CU (a 128-register budget; at the 64 registers of four per CU the ring spills)
+// and PDX varies the ring depth.
+template <int MT, int NT, int EPI, int PREC = 0, int IO16 = 0, int PDX = 0>
+__global__ void __launch_bounds__(512, EPI == EPI_HEAD_CLS ? 4 : 2) gemm1x1(const ConvP p)
 {
     constexpr bool IN16 = (IO16 & 1) != 0, OUT16 = (IO16 & 2) != 0;
     static_assert(IO16 == 0 || PREC != 0, "16-bit storage comes with the 16-bit operand path");
     static_assert(!OUT16 || EPI != EPI_HEAD, "the head's logits stay fp32");
     constexpr int BM = MT * 16;
     constexpr int BMP = BM + ((BM % 32 == 0) ? 16 : 0);
-    constexpr int PD = (MT >= 8) ? 4 : 8; // B-operand ring depth (steps in flight); even, K % (4 * PD) == 0; 128 accumulator registers leave room for 4
+    static_assert(EPI != EPI_HEAD_CLS || (MT == 1 && PREC == 0 && IO16 == 0), "the cls-only head pass is one fp32 M-tile");
+    constexpr int PD = PDX ? PDX : (MT >= 8) ? 4 : 8; // B-operand ring depth (steps in flight); even, K % (4 * PD) == 0; 128 accumulator registers leave room for 4
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wl = smem;                         // [K][BMP]
     const int K = p.Cin;
@@ -1625,7 +1631,12 @@ __global__ void __launch_bounds__(512, 2) gemm1x1(const ConvP p)
     const int wi = xcd_ok ? xk + 8 * (xj / ncb) : blockIdx.x / ncb, nworkers = gridDim.x / ncb;
     if (wi >= nworkers) return;
     const int co0 = cb * BM;
-    {
+    if constexpr (EPI == EPI_HEAD_CLS) { // column a of the slab = the cls row of anchor a in the full image [row block][K][w_bmp]; columns na .. 15 are zero
+        for (int e = tid; e < K * BMP; e += 512) {
+            const int k = e / BMP, a = e - k * BMP, t = 4 * (9 + a) + 3;
+            wl[e] = a < p.n_cls ? p.w[((size_t)(t / p.w_bm) * K + k) * p.w_bmp + t % p.w_bm] : 0.f;
+        }
+    } else {
         const f32x4* g = reinterpret_cast<const f32x4*>(p.w) + (size_t)cb * ((size_t)K * BMP / 4);
         f32x4* d = reinterpret_cast<f32x4*>(wl);
         for (int e = tid; e < K * BMP / 4; e += 512) d[e] = g[e];
@@ -1649,7 +1660,7 @@ __global__ void __launch_bounds__(512, 2) gemm1x1(const ConvP p)
         for (int r = 0; r < SR; ++r) { ssum[i][r] = 0.f; ssq[i][r] = 0.f; }
     int stat_frame = -1, pre_frame = -1;
     auto flush_stats = [&](int frame) {
-        if (EPI == EPI_HEAD || !p.stat_acc || frame < 0) return;
+        if (EPI == EPI_HEAD || EPI == EPI_HEAD_CLS || !p.stat_acc || frame < 0) return;
         double* base = p.stat_acc + (size_t)frame * p.stat_fs + ((size_t)((blockIdx.x * 8 + wave) % NREP) * p.stat_C) * 2;
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -1981,6 +1992,16 @@ __global__ void __launch_bounds__(512, 2) gemm1x1(const ConvP p)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { ssum[i][0] += v[r]; ssq[i][0] += v[r] * v[r]; }
                     }
+                } else if (EPI == EPI_HEAD_CLS) { // row = anchor: cls(a) over the lane's 4 pixels, as the full head stores it
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int a_ = row0 + r;
+                        if (a_ < p.n_cls) {
+                            const float bs = p.bias[4 * (9 + a_) + 3];
+                            *reinterpret_cast<f32x4*>(gout + (size_t)a_ * plane + pxb) =
+                                (f32x4){acc[i][0][r] + bs, acc[i][1][r] + bs, acc[i][2][r] + bs, acc[i][3][r] + bs};
+                        }
+                    }
                 } else {
                     // head rows in head_tile_row order: this lane's 4 rows are one output run (see the host helper)
                     const int g = row0 >> 2;
@@ -2167,6 +2188,21 @@ Variant make_g1()
     return v;
 }
 
+// cls-only head pass (EPI_HEAD_CLS): ring depth PD, two workgroups per CU
+template <int PD>
+Variant make_g1_cls()
+{
+    Variant v;
+    v.kern = gemm1x1<1, 4, EPI_HEAD_CLS, 0, 0, PD>;
+    v.bm = 16; v.bmp = 16; v.pw = 64; v.ph = 1; v.kc = 4; v.threads = 512;
+    v.waves = 8; v.pairs = 4;
+    v.lds = 0; // depends on K (g1_lds)
+    v.family = Family::Gemm1x1;
+    v.wpc = 2;
+    snprintf(v.name, sizeof(v.name), "g1x1 cls pd%d wg%d", PD, v.wpc);
+    return v;
+}
+
 struct Layer {
     std::string wkey;
     int kind;   // 0 conv3x3, 1 deconv(up), 2 head
@@ -2203,6 +2239,8 @@ struct pp_net {
     int num_cu = 256;
     int eff_prec = 0;   // the precision the launch plan is built for: ctx->precision, except 4 -> 3 when the concat buffer cannot be fp16
     bool up16 = false;  // pp_set_precision 4 with every layer on a 16-bit-tensor tiling: the level buffers and the concat buffer `up` hold fp16
+    bool defer_ok = false; // the committed plan can run the deferred head: fp32 mode, 9-anchor head on a gemm1x1 tiling
+    Variant cls_var;       // tiling of the cls-only head pass (chosen at pp_commit_weights when defer_ok)
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };
 
@@ -2627,6 +2665,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
     p.stat_acc = stat_acc; p.stat_C = stat_C;
     p.bias = (L.kind == 2 && L.var.family == Family::Gemm1x1) ? net->head_bias_perm : net->head_bias; p.out_box = out_box; p.out_dir = out_dir;
     { const int na = ctx->cfg.num_anchor_per_loc; p.n_cls = na; p.n_box = 7 * na; p.n_rows = 10 * na; }
+    p.w_bm = net->layers.back().var.bm; p.w_bmp = net->layers.back().var.bmp;
     {   // frame strides of a batched launch (every per-frame tensor is stored [B][...])
         const size_t hw = (size_t)Hout * Wout;
         p.in_fs = in_fs ? in_fs : (size_t)L.cin * Hin * Win;
@@ -2652,7 +2691,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
     if (v.family == Family::Gemm1x1 && ((Hin * Win) & 3)) return PP_E_ARG; // gemm1x1 reads pixel quads (choose_variant never offers it for such a plane)
     if (v.family == Family::Gemm1x1) { // persistent: one workgroup per CU, a multiple of the row-block count
         const int ncb = pp_div_up(L.rows, v.bm);
-        int g = (net->num_cu / ncb) * ncb;
+        int g = (net->num_cu * v.wpc / ncb) * ncb;
         if (g < ncb) g = ncb;
         grid = dim3(g, 1, 1);
     }
@@ -2949,6 +2988,57 @@ int autotune_layer(pp_ctx* ctx, Layer& L, int Hin, int Win, int Hout, int Wout, 
     return 0;
 }
 
+// The cls-only head pass as a launch: the head layer with the cls tiling and one 16-row block; the weights stay the head's image.
+int launch_head_cls(pp_ctx* ctx, const Variant& v, const float* in, const NormRef& pre, float* cls, int nb, hipStream_t stream)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    Layer L = net->layers.back(); // shares the device image (no ownership: Layer has no destructor)
+    L.var = v;
+    L.rows = 16;
+    return launch_conv(ctx, L, in, ctx->H, ctx->W, cls, nullptr, pre, nullptr, 0, ctx->H, ctx->W, stream, nullptr, nullptr, nb);
+}
+
+// Shapes of the cls-only pass, timed like a layer's tilings (3 launches after a warm-up, the fastest is kept and cached).
+int autotune_head_cls(pp_ctx* ctx, float* tin, bool verbose, bool measure)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    const std::vector<Variant> menu = {make_g1_cls<8>(), make_g1_cls<10>(), make_g1_cls<4>()}; // every shape without scratch: a 16-deep ring spills
+    for (const Variant& v : menu)
+        PP_HIP(hipFuncSetAttribute((const void*)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g1_lds(v, 320)));
+    net->cls_var = menu[0];
+    if (!measure) return 0;
+    const int tb = ctx->max_batch < TUNE_FRAMES ? ctx->max_batch : TUNE_FRAMES;
+    char sig[160];
+    snprintf(sig, sizeof(sig), "v%d m%d headcls %s %dx%d n%d b%d", pp_version(), (int)menu.size(), net->layers.back().var.name, ctx->H, ctx->W, ctx->cfg.norm_kind, tb);
+    auto hit = tune_cache().find(sig);
+    if (hit != tune_cache().end())
+        for (const Variant& v : menu)
+            if (hit->second == v.name) { net->cls_var = v; return 0; }
+    hipEvent_t e0, e1;
+    PP_HIP(hipEventCreate(&e0));
+    PP_HIP(hipEventCreate(&e1));
+    NormRef pre;
+    pre.mode = PRE_AFFINE; pre.scale = net->ones; pre.shift = net->zeros;
+    double best = 1e30;
+    for (const Variant& v : menu) {
+        float ms = 0.f;
+        for (int it = 0; it <= 3; ++it) {
+            if (it == 1) PP_HIP(hipEventRecord(e0, 0));
+            int rc = launch_head_cls(ctx, v, tin, pre, ctx->f_cls, tb, 0);
+            if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
+        }
+        PP_HIP(hipEventRecord(e1, 0));
+        PP_HIP(hipEventSynchronize(e1));
+        PP_HIP(hipEventElapsedTime(&ms, e0, e1));
+        if (verbose) fprintf(stderr, "[pp autotune] %-28s %-34s %8.1f us\n", sig, v.name, ms / 3 * 1e3);
+        if (ms < best) { best = ms; net->cls_var = v; }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    tune_cache()[sig] = net->cls_var.name;
+    return 0;
+}
+
 } // namespace
 
 int pp_net_create(pp_ctx* ctx)
@@ -3113,6 +3203,14 @@ int pp_net_commit(pp_ctx* ctx)
             if (L.var.kern2) PP_HIP(hipFuncSetAttribute((const void*)L.var.kern2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.var.lds));
             rc = pack_layer(ctx, L);
             if (rc) { if (tin) { (void)hipFree(tin - W6_FRONT_PAD); (void)hipFree(tout); } return rc; }
+        }
+        {   // deferred head: fp32 plan with the 9-anchor head on a gemm1x1 tiling (its image is what the cls pass and the candidate head read)
+            const Layer& head = net->layers.back();
+            net->defer_ok = net->eff_prec == 0 && na == 9 && head.var.family == Family::Gemm1x1 && head.var.prec == 0 && head.var.io16 == 0;
+            if (net->defer_ok) {
+                const int rc = autotune_head_cls(ctx, tin, verbose, can_tune);
+                if (rc) { if (tin) { (void)hipFree(tin - W6_FRONT_PAD); (void)hipFree(tout); } return rc; }
+            }
         }
         if (tin) { PP_HIP(hipDeviceSynchronize()); (void)hipFree(tin - W6_FRONT_PAD); (void)hipFree(tout); tune_cache_save(); }
         if (net->up16)
@@ -3288,12 +3386,70 @@ int pp_run_head_fused(pp_ctx* ctx, float* cls, float* box, float* dir, int nb, h
     return pp_head_impl(ctx, net->up, pre, cls, box, dir, nb, stream);
 }
 
+// ---- deferred head (pp_infer_batch): cls rows for every pixel, box / dir logits for the selected candidates only ----
+bool pp_head_defer_on(pp_ctx* ctx)
+{
+    const pp_net* net = (const pp_net*)ctx->net;
+    return ctx->head_defer && net && ctx->weights_ready && net->defer_ok;
+}
+
+int pp_run_head_cls(pp_ctx* ctx, float* cls, int nb, hipStream_t stream)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    NormRef pre = norm_ref(ctx, 7, 320, 0, (size_t)ctx->H * ctx->W);
+    int rc = launch_head_cls(ctx, net->cls_var, net->up, pre, cls, nb, stream);
+    if (rc) return rc;
+    ctx->head_stale = true;
+    ctx->stale_nb = nb;
+    ctx->stale_stream = stream;
+    return 0;
+}
+
+// What the candidate head (postprocess.hip) reads: the head image and the concat buffer with the normalisation the cls pass of
+// `nb` frames just used (a batched launch finalised the statistics into net->aff, a single frame finalises them in the kernel).
+int pp_net_head_gather(pp_ctx* ctx, int nb, pp_head_gather* g)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    const Layer& head = net->layers.back();
+    if (!net->defer_ok) return pp_fail(ctx, PP_E_STATE, "candidate head: the committed plan has no fp32 gemm1x1 head image");
+    const NormRef pre = norm_ref(ctx, 7, 320, 0, (size_t)ctx->H * ctx->W);
+    g->w = head.w; g->bm = head.var.bm; g->bmp = head.var.bmp; g->K = head.cin;
+    g->bias_perm = net->head_bias_perm;
+    g->in = net->up; g->in_fs = (size_t)head.cin * ctx->H * ctx->W; g->HW = ctx->H * ctx->W;
+    g->pre = pre.mode; g->pre_acc = pre.acc; g->pre_fs = pre.fs; g->pre_inv_n = pre.inv_n;
+    g->pre_scale = pre.scale; g->pre_shift = pre.shift; g->aff_fs = 0; g->eps = 1e-3f;
+    if (pre.mode == PRE_STATS && nb > 1) { g->pre = PRE_AFFINE; g->pre_scale = net->aff; g->pre_shift = net->aff + 320; g->aff_fs = 640; }
+    return 0;
+}
+
+// Full box / dir (and cls) tensors of the last deferred pass: today's head over the retained concat buffer and statistics.
+int pp_head_materialise(pp_ctx* ctx, hipStream_t stream)
+{
+    if (!ctx->head_stale) return 0;
+    ctx->head_stale = false;
+    return pp_run_head_fused(ctx, ctx->f_cls, ctx->f_box, ctx->f_dir, ctx->stale_nb, stream);
+}
+
+extern "C" int pp_set_head_defer(pp_ctx* ctx, int on)
+{
+    if (!ctx) return PP_E_ARG;
+    ctx->head_defer = on && !ctx->head_defer_env_off;
+    return 0;
+}
+
+extern "C" int pp_head_defer_active(pp_ctx* ctx)
+{
+    if (!ctx) return 0;
+    return pp_head_defer_on(ctx) ? 1 : 0;
+}
+
 extern "C" int pp_backbone(pp_ctx* ctx, const float* canvas, float* rpn_out, void* stream_)
 {
     if (!ctx) return PP_E_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone: weights not committed");
     if (!canvas || !rpn_out) return pp_fail(ctx, PP_E_ARG, "pp_backbone: null pointer");
+    if (int rc0 = pp_head_materialise(ctx, stream)) return rc0; // the concat buffer and its statistics are about to be overwritten
     int rc = pp_run_backbone(ctx, canvas, 1, stream, nullptr, nullptr);
     if (rc) return rc;
     pp_net* net = (pp_net*)ctx->net;
@@ -3381,6 +3537,8 @@ extern "C" int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst
     const size_t A = (size_t)ctx->A, mv = (size_t)ctx->cfg.max_voxels, HW = (size_t)ctx->H * ctx->W;
     const void* src = nullptr;
     size_t bytes = 0;
+    if (kind == 1 || kind == 2)
+        if (int rc0 = pp_head_materialise(ctx, stream)) return rc0;
     switch (kind) {
     case 0: src = ctx->f_cls + frame * A; bytes = A * 4; break;
     case 1: src = ctx->f_box + frame * A * 7; bytes = A * 28; break;

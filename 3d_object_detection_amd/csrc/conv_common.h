@@ -61,7 +61,7 @@ static __device__ __forceinline__ void pp_steps(F&& f)
     }
 }
 
-enum { EPI_PLAIN = 0, EPI_UP2 = 1, EPI_UP4 = 2, EPI_HEAD = 3 };
+enum { EPI_PLAIN = 0, EPI_UP2 = 1, EPI_UP4 = 2, EPI_HEAD = 3, EPI_HEAD_CLS = 4 /* the head's cls rows alone (deferred head) */ };
 enum { PRE_RAW = 0, PRE_STATS = 1, PRE_AFFINE = 2 };
 
 struct ConvP {
@@ -86,6 +86,7 @@ struct ConvP {
     float* out_dir;
     int n_cls, n_box; // na, 7 na (dir = rest up to n_rows) for na anchors per location (reference: 9, 63)
     int n_rows;       // 10 na (reference: 90)
+    int w_bm, w_bmp;  // EPI_HEAD_CLS: row-block height and padded width of the committed full head image `w` points to
     // batch: blockIdx.z = frame; strides in elements between consecutive frames
     size_t in_fs, out_fs, res_fs, box_fs, dir_fs; // floats
     size_t pre_fs, stat_fs;                        // doubles
@@ -119,6 +120,7 @@ struct Variant { // one compiled tiling
     Family family = Family::Direct;
     int prec = 0; // Gemm1x1 / Conv16: 0 fp32 MFMA, 1 split-bf16 (bf16x3), 2 plain bf16, 3 fp16 operands
     int io16 = 0; // Gemm1x1 / Conv16: bit 0 = the input tensor is fp16, bit 1 = the output tensor (and residual) is (pp_set_precision 4)
+    int wpc = 1;  // Gemm1x1: persistent workgroups per CU
 };
 
 

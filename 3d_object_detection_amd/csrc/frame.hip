@@ -15,6 +15,7 @@ extern "C" int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int3
     if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, "pp_infer_batch: call pp_set_anchors first");
     if (!det || !det_count || !pts_h || !n_h) return pp_fail(ctx, PP_E_ARG, "pp_infer_batch: null pointer");
     if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_infer_batch: nb exceeds cfg.max_batch");
+    ctx->head_stale = false; // this pass overwrites whatever a deferred one left (set again once its cls pass is enqueued)
     ctx->last_nb = 0; // frames whose masks / head outputs the context holds (pp_batch_loss); set once the pass is enqueued
     int rc;
     // The integer stages are latency-bound at one frame per launch (a few workgroups each); with blockIdx.z =
@@ -35,12 +36,15 @@ extern "C" int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int3
     if ((rc = pp_stage_mark(ctx, stream, PP_ST_CONV))) return rc;
     if ((rc = pp_run_backbone(ctx, nullptr, nb, stream, ctx->f_pmap, ctx->f_feat))) return rc;
     if ((rc = pp_stage_mark(ctx, stream, PP_ST_HEAD))) return rc;
-    if ((rc = pp_run_head_fused(ctx, ctx->f_cls, ctx->f_box, ctx->f_dir, nb, stream))) return rc;
+    // deferred head: the cls rows for every pixel here, the box / dir logits of the selected candidates after the top-k
+    const bool defer = pp_head_defer_on(ctx);
+    if (defer) { if ((rc = pp_run_head_cls(ctx, ctx->f_cls, nb, stream))) return rc; }
+    else if ((rc = pp_run_head_fused(ctx, ctx->f_cls, ctx->f_box, ctx->f_dir, nb, stream))) return rc;
     if ((rc = pp_stage_mark(ctx, stream, PP_ST_POST))) return rc;
     for (int b0 = 0; b0 < nb; b0 += PP_GROUP) {
         const int g = nb - b0 < PP_GROUP ? nb - b0 : PP_GROUP;
         if (b0 && (rc = pp_stage_mark(ctx, stream, PP_ST_POST))) return rc;
-        if ((rc = pp_postprocess_group(ctx, b0, g, det, det_count, nms_mode, stream))) return rc;
+        if ((rc = pp_postprocess_group(ctx, b0, g, det, det_count, nms_mode, stream, defer ? nb : 0))) return rc;
     }
     ctx->last_nb = nb;
     return pp_stage_mark(ctx, stream, -1);

@@ -8,6 +8,8 @@
 //   Q3 post_gather   candidates in bins >= that bin -> short list (K .. K + one bin)
 //   Q4 post_topk     per class (one workgroup): exact top-K by bitonic sort of the short list in LDS
 //                    (radix-select fallback when a bin is huge), box decode, NMS boxes
+//   Q4b post_cand_b  deferred head (pp_infer_batch): post_topk only selects; this kernel computes the box / dir logits of the
+//                    selected anchors from the concat buffer (the head's own MFMA arithmetic, 16 candidates per N-tile) and decodes them
 //   Q5 nms_mask      64x64 suppression bit tiles, one WAVEFRONT per tile row-block: the 64-bit
 //                    ballot of a wave64 IS a mask word (nms.py:119-150 needs a 64-iteration loop)
 //   Q6 nms_reduce    greedy sweep, tile-serial (wave-uniform bit tricks inside a tile, vector OR
@@ -236,7 +238,8 @@ __device__ __forceinline__ void post_topk_body(pp_config cfg, const uint64_t* __
                                                   const uint64_t* __restrict__ shortl, int32_t* __restrict__ counters, int K,
                                                   const float* __restrict__ box, const float* __restrict__ dir,
                                                   const float* __restrict__ anchors, int rotate, uint64_t* __restrict__ sel,
-                                                  float* __restrict__ boxes, float* __restrict__ nbox, int32_t* __restrict__ dirl)
+                                                  float* __restrict__ boxes, float* __restrict__ nbox, int32_t* __restrict__ dirl,
+                                                  bool decode = true)
 {
     __shared__ uint64_t keys[SHORT_CAP];
     __shared__ int s_hist[2048];
@@ -300,6 +303,7 @@ __device__ __forceinline__ void post_topk_body(pp_config cfg, const uint64_t* __
         const uint64_t k = keys[i];
         const uint32_t a = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);
         sel[(size_t)c * K + i] = k;
+        if (!decode) continue; // deferred head: post_cand_b computes and decodes the candidates' logits
         float b[7];
         decode_box(box + (size_t)a * 7, anchors + (size_t)a * 7, b);
         float* bo = boxes + ((size_t)c * K + i) * 7;
@@ -307,6 +311,110 @@ __device__ __forceinline__ void post_topk_body(pp_config cfg, const uint64_t* __
         for (int q = 0; q < 7; ++q) bo[q] = b[q];
         dirl[(size_t)c * K + i] = dir[(size_t)a * 2 + 1] > dir[(size_t)a * 2] ? 1 : 0;
         float* nb = nbox + ((size_t)c * K + i) * 6;
+        if (rotate) { nb[0] = b[0]; nb[1] = b[1]; nb[2] = b[3]; nb[3] = b[4]; nb[4] = b[6]; }
+        else standup_box(b[0], b[1], b[3], b[4], b[6], nb);
+    }
+}
+
+// ---------------------------------------------------------------- Q4b
+// Candidate head.  One wave = one N-tile of 16 selected anchors of (frame, class): lane (m, kq) gathers channel 4 S + kq of candidate
+// m's pixel from the pre-norm concat buffer, normalises it with the frame's (scale, shift) and feeds v_mfma_f32_16x16x4_f32 over the
+// channel quads S = 0 .. K/4 - 1 in ascending order from a zero accumulator, against the SAME A values the full head reads from the
+// SAME image -- an MFMA output element depends on its own row and column only, so every logit is bit-identical to the full head's.
+// All 96 rows are computed (the flops are free; the cost is the gather), each candidate then picks the 7 + 2 rows of its anchor.
+// Padding lanes of a partly filled tile gather the class's last candidate (in bounds) and store nothing.
+typedef float pc_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int CAND_WAVES = 4;   // N-tiles per workgroup
+constexpr int CAND_MAXK = 320;  // input channels of the head
+__global__ void __launch_bounds__(64 * CAND_WAVES) post_cand_b(const pp_post_frame* __restrict__ tab, int f0, int K, int HW, const float* __restrict__ anchors,
+                                                                  int rotate, pp_head_gather h)
+{
+    __shared__ float s_aff[2][CAND_MAXK];
+    __shared__ float s_out[CAND_WAVES][16][12];
+    const int c = blockIdx.y, fz = blockIdx.z;
+    const pp_post_frame F = tab[fz];
+    const int frame = f0 + fz; // index into the pass's concat buffer / statistics
+    const int nsel = F.counters[c * 8 + 3];
+    if ((int)blockIdx.x * (16 * CAND_WAVES) >= nsel) return; // workgroup-uniform (covers nsel == 0)
+    for (int ch = threadIdx.x; ch < h.K; ch += blockDim.x) { // the frame's (scale, shift): gemm1x1's own prologue
+        float sc, sh; // the concat buffer is always pre-norm: statistics (InstanceNorm) or a folded affine (BatchNorm)
+        if (h.pre == 1) { // PRE_STATS
+            const double* pa = h.pre_acc + (size_t)frame * h.pre_fs;
+            double s = 0.0, q = 0.0;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { s += pa[((size_t)r * h.K + ch) * 2]; q += pa[((size_t)r * h.K + ch) * 2 + 1]; }
+            const double mean = s * h.pre_inv_n;
+            double var = q * h.pre_inv_n - mean * mean;
+            var = var > 0.0 ? var : 0.0;
+            const double rstd = 1.0 / sqrt(var + (double)h.eps);
+            sc = (float)rstd;
+            sh = (float)(-mean * rstd);
+        } else { // PRE_AFFINE
+            sc = h.pre_scale[(size_t)frame * h.aff_fs + ch];
+            sh = h.pre_shift[(size_t)frame * h.aff_fs + ch];
+        }
+        s_aff[0][ch] = sc;
+        s_aff[1][ch] = sh;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, kq = lane >> 4;
+    const int base = ((int)blockIdx.x * CAND_WAVES + wave) * 16;
+    const int i = base + m;
+    const bool valid = i < nsel;
+    const uint64_t key = F.sel[(size_t)c * K + (valid ? i : nsel - 1)];
+    const uint32_t a = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+    const int aloc = (int)(a / (uint32_t)HW), pix = (int)(a - (uint32_t)aloc * (uint32_t)HW);
+    if (base < nsel) { // wave-uniform
+        const float* bp = h.in + (size_t)frame * h.in_fs + (size_t)kq * HW + pix; // + 4 S HW per step
+        int aoff[6];
+#pragma unroll
+        for (int t = 0; t < 6; ++t) aoff[t] = ((t * 16) / h.bm) * h.K * h.bmp + kq * h.bmp + (t * 16) % h.bm + m; // + 4 S bmp per step
+        pc_f32x4 acc[6];
+#pragma unroll
+        for (int t = 0; t < 6; ++t) acc[t] = (pc_f32x4){0.f, 0.f, 0.f, 0.f};
+        const int nsteps = h.K / 4;
+        constexpr int U = 8; // K % 32 == 0 (gemm1x1's own condition)
+        for (int s0 = 0; s0 < nsteps; s0 += U) {
+            float x[U], wv[U][6];
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = bp[(size_t)(s0 + u) * 4 * HW];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int t = 0; t < 6; ++t) wv[u][t] = h.w[aoff[t] + (s0 + u) * 4 * h.bmp];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float bb = fmaxf(fmaf(x[u], s_aff[0][(s0 + u) * 4 + kq], s_aff[1][(s0 + u) * 4 + kq]), 0.f);
+#pragma unroll
+                for (int t = 0; t < 6; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[u][t], bb, acc[t], 0, 0, 0);
+            }
+        }
+        // lane (m, kq) holds tile rows 16 t + 4 kq + r of candidate m: group g = 4 t + kq of head_tile_row
+        if (valid) {
+#pragma unroll
+            for (int t = 0; t < 6; ++t) {
+                const int g = 4 * t + kq;
+                const float b0 = h.bias_perm[4 * g], b1 = h.bias_perm[4 * g + 1], b2 = h.bias_perm[4 * g + 2], b3 = h.bias_perm[4 * g + 3];
+                const float v0 = acc[t][0] + b0, v1 = acc[t][1] + b1, v2 = acc[t][2] + b2, v3 = acc[t][3] + b3;
+                float* o = s_out[wave][m];
+                if (g == aloc) { o[0] = v0; o[1] = v1; o[2] = v2; o[3] = v3; }            // box k = 0..3
+                if (g == 9 + aloc) { o[4] = v0; o[5] = v1; o[6] = v2; }                   // box k = 4..6
+                if (g == 18 + (aloc >> 1)) { o[7] = (aloc & 1) ? v2 : v0; o[8] = (aloc & 1) ? v3 : v1; } // dir 0, 1
+            }
+        }
+    }
+    __syncthreads();
+    if (valid && kq == 0) {
+        float t7[7], b[7];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) t7[q] = s_out[wave][m][q];
+        const float d0 = s_out[wave][m][7], d1 = s_out[wave][m][8];
+        decode_box(t7, anchors + (size_t)a * 7, b);
+        float* bo = F.boxes + ((size_t)c * K + i) * 7;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) bo[q] = b[q];
+        F.dirl[(size_t)c * K + i] = d1 > d0 ? 1 : 0;
+        float* nb = F.nbox + ((size_t)c * K + i) * 6;
         if (rotate) { nb[0] = b[0]; nb[1] = b[1]; nb[2] = b[3]; nb[3] = b[4]; nb[4] = b[6]; }
         else standup_box(b[0], b[1], b[3], b[4], b[6], nb);
     }
@@ -651,10 +759,10 @@ __global__ void __launch_bounds__(256) post_gather_b(const pp_post_frame* __rest
     post_gather_body(F.cand, cand_cap, F.counters, thr_bits, bin_shift, F.shortl);
 }
 __global__ void __launch_bounds__(1024) post_topk_b(const pp_post_frame* __restrict__ tab, pp_config cfg, int64_t cand_cap, int K,
-                                                    const float* __restrict__ anchors, int nms_mode)
+                                                    const float* __restrict__ anchors, int nms_mode, int decode)
 {
     const pp_post_frame F = tab[blockIdx.z];
-    post_topk_body(cfg, F.cand, cand_cap, F.shortl, F.counters, K, F.box, F.dir, anchors, nms_mode, F.sel, F.boxes, F.nbox, F.dirl);
+    post_topk_body(cfg, F.cand, cand_cap, F.shortl, F.counters, K, F.box, F.dir, anchors, nms_mode, F.sel, F.boxes, F.nbox, F.dirl, decode != 0);
 }
 __global__ void __launch_bounds__(64) nms_mask_b(const pp_post_frame* __restrict__ tab, int ncls, int K, int cb, float thr, int rotate)
 {
@@ -813,7 +921,7 @@ void pp_post_fill_table(pp_ctx* ctx, int slot, pp_post_frame* f)
 }
 
 // post-processing of frames b0 .. b0+g-1 as one launch per stage (blockIdx.z = frame)
-int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream)
+int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream, int defer_nb)
 {
     const pp_post* P = (const pp_post*)ctx->slot[0].post; // sizes are the same for every slot
     const pp_config& c = ctx->cfg;
@@ -829,7 +937,14 @@ int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_co
     hipLaunchKernelGGL(post_gather_b, dim3(pp_div_up(P->cand_cap, 256 * GATHER_ITEMS), n, g), dim3(256), 0, stream, tab, P->cand_cap, P->thr_bits, P->bin_shift);
     int rc_;
     if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_TOPK))) return rc_;
-    hipLaunchKernelGGL(post_topk_b, dim3(n, 1, g), dim3(1024), 0, stream, tab, c, P->cand_cap, P->K, ctx->anchors, nms_mode);
+    hipLaunchKernelGGL(post_topk_b, dim3(n, 1, g), dim3(1024), 0, stream, tab, c, P->cand_cap, P->K, ctx->anchors, nms_mode, defer_nb > 0 ? 0 : 1);
+    if (defer_nb > 0) { // deferred head: the selected anchors' box / dir logits, decoded (same stage mark)
+        pp_head_gather hg;
+        if ((rc_ = pp_net_head_gather(ctx, defer_nb, &hg))) return rc_;
+        if (hg.K > CAND_MAXK || (hg.K & 31)) return pp_fail(ctx, PP_E_STATE, "candidate head: unexpected channel count");
+        hipLaunchKernelGGL(post_cand_b, dim3(pp_div_up(P->K, 16 * CAND_WAVES), n, g), dim3(64 * CAND_WAVES), 0, stream, tab, b0, P->K,
+                           ctx->H * ctx->W, ctx->anchors, nms_mode, hg);
+    }
     if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_NMS))) return rc_;
     hipLaunchKernelGGL(nms_mask_b, dim3(P->cb, P->cb, n * g), dim3(64), 0, stream, tab, n, P->K, P->cb, c.nms_iou_threshold, nms_mode);
     hipLaunchKernelGGL(nms_reduce_b, dim3(1, 1, g), dim3(64 * PP_MAX_CLASSES), 0, stream, tab, c, P->K, P->cb, det + (size_t)b0 * det_fs, det_fs,

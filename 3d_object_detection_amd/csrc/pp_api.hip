@@ -1,6 +1,7 @@
 // Context lifetime, weight intake, anchor tables and error reporting of libpp_hip.so.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include "pp_common.h"
 
@@ -22,7 +23,7 @@ int pp_fail(pp_ctx* ctx, int code, const char* msg)
 }
 
 extern "C" const char* pp_last_error(pp_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
-extern "C" int pp_version(void) { return 3; } // round 3: launch plan keyed on max_batch, 16-bit conv kernels, pp_select_candidates
+extern "C" int pp_version(void) { return 4; } // 4: deferred head (cls-only pass + candidate head), pp_set_head_defer
 
 int pp_stage_mark(pp_ctx* ctx, hipStream_t stream, int id)
 {
@@ -146,6 +147,8 @@ extern "C" pp_ctx* pp_create(int device, const pp_config* cfg)
     ctx->gy = cfg->grid_size[1];
     ctx->H = ctx->gx / 2;
     ctx->W = ctx->gy / 2;
+    if (const char* e = getenv("PP_HEAD_DEFER")) ctx->head_defer_env_off = e[0] == '0';
+    ctx->head_defer = !ctx->head_defer_env_off;
     int rc = create_impl(ctx);
     if (rc) {
         g_create_err = ctx->err;
@@ -246,6 +249,10 @@ extern "C" int pp_commit_weights(pp_ctx* ctx)
 {
     if (!ctx) return PP_E_ARG;
     PP_HIP(hipSetDevice(ctx->device));
+    if (ctx->head_stale && ctx->net) { // the head image is about to be repacked: the last deferred pass gets its full tensors first
+        if (int rc0 = pp_head_materialise(ctx, ctx->stale_stream)) return rc0;
+        PP_HIP(hipStreamSynchronize(ctx->stale_stream));
+    }
     // PFN: Conv1d weight [64,9,1] -> [9][64]; BatchNorm1d(eval, eps 1e-5) -> scale/shift
     const std::string p = "pillar_point_net.pfn_layers.";
     const pp_tensor_h *w = find_w(ctx, p + "0.weight", 64 * 9), *g = find_w(ctx, p + "1.weight", 64),

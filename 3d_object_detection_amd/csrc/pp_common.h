@@ -126,6 +126,14 @@ struct pp_ctx {
     //      the natural-order copy of the head weights and the index map of the head's packed image are rebuilt after a commit ----
     uint64_t commit_gen = 0;
     void* trn = nullptr;
+    // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
+    //      the selected candidates only; f_box / f_dir are then stale until pp_head_materialise runs the full head over the retained
+    //      concat buffer and statistics of that pass ----
+    bool head_defer = true;          // the switch (default on; PP_HEAD_DEFER=0 forces it off)
+    bool head_defer_env_off = false;
+    bool head_stale = false;         // f_box / f_dir do not hold the last pass
+    int stale_nb = 0;                // frames of that pass
+    hipStream_t stale_stream = nullptr;
 };
 // stage ids of pp_stage_mark / pp_stage_profile_end
 enum { PP_ST_VOXELIZE = 0, PP_ST_MASK = 1, PP_ST_PFN = 2, PP_ST_CONV = 3, PP_ST_NORM = 4, PP_ST_HEAD = 5, PP_ST_POST = 6 /* filter + threshold + gather */,
@@ -155,8 +163,21 @@ void pp_post_fill_table(pp_ctx* ctx, int slot, pp_post_frame* f);
 int pp_voxelize_group(pp_ctx* ctx, int b0, int g, const pp_in_group& in, hipStream_t stream);
 int pp_anchor_mask_group(pp_ctx* ctx, int b0, int g, hipStream_t stream);
 int pp_pfn_pmap_group(pp_ctx* ctx, int b0, int g, hipStream_t stream);
-int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream);
+int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream,
+                         int defer_nb = 0); // defer_nb > 0: box / dir logits come from the candidate head (a deferred pass of defer_nb frames)
 int pp_run_head_fused(pp_ctx* ctx, float* cls, float* box, float* dir, int nb, hipStream_t stream); // norm+ReLU fused in the prologue
+// deferred head (conv.hip): is it what pp_infer_batch runs; the cls-only pass (marks f_box / f_dir stale); the full tensors on demand
+// (no-op unless stale) -- to be called by whatever reads f_box / f_dir or overwrites the concat buffer, its statistics or the head weights
+bool pp_head_defer_on(pp_ctx* ctx);
+int pp_run_head_cls(pp_ctx* ctx, float* cls, int nb, hipStream_t stream);
+int pp_head_materialise(pp_ctx* ctx, hipStream_t stream);
+struct pp_head_gather { // inputs of the candidate head (postprocess.hip)
+    const float* w; int bm, bmp, K;  // the head image [row block][K][bmp] in head_tile_row order
+    const float* bias_perm;
+    const float* in; size_t in_fs; int HW; // concat buffer [nb][K][HW], pre-norm
+    int pre; const double* pre_acc; size_t pre_fs; double pre_inv_n; const float *pre_scale, *pre_shift; size_t aff_fs; float eps;
+};
+int pp_net_head_gather(pp_ctx* ctx, int nb, pp_head_gather* g);
 void pp_post_destroy(pp_ctx* ctx);
 void pp_assign_destroy(pp_ctx* ctx);
 void pp_train_destroy(pp_ctx* ctx);

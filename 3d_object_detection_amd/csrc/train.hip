@@ -484,6 +484,7 @@ extern "C" int pp_update_head_weights(pp_ctx* ctx, const float* w_cls, const flo
     PP_HIP(hipSetDevice(ctx->device));
     trn_ws* w = workspace(ctx);
     if (!w) return pp_fail(ctx, PP_E_STATE, "pp_update_head_weights: workspace allocation failed");
+    if (int rc0 = pp_head_materialise(ctx, stream)) return rc0; // the last deferred pass gets its full tensors from the weights it ran with
     if (w->img_gen != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
         int rc = pp_net_head_image(ctx, &w->img);
         if (rc) return rc;

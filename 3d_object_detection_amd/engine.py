@@ -6,6 +6,7 @@ here computes on the CPU except the one-off geometry / anchor tables that the re
 also builds in __init__ (voxel_generator.py:6-26, anchor_assigner.py:221-298).
 """
 import ctypes
+import os
 import weakref
 
 import numpy as np
@@ -201,6 +202,8 @@ class Engine:
         self.weights_loaded = False
         self._sd = None
         self.precision = "fp32"
+        self._defer_env_off = os.environ.get("PP_HEAD_DEFER", "")[:1] == "0"  # read by pp_create: forces the switch off
+        self.head_defer = not self._defer_env_off  # the switch as it stands (set_head_defer); head_defer_active() says what the passes run
         if precision != "fp32":
             self.set_precision(precision)
         self._P1 = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -235,6 +238,17 @@ class Engine:
         tensors are not possible; None before the weights are committed."""
         v = self.lib.pp_effective_precision(self.ctx)
         return None if v < 0 else {n: k for k, n in self.PRECISIONS.items()}[v]
+
+    def set_head_defer(self, on):
+        """pp_set_head_defer: passes compute the head's box / dir logits for the selected candidates only (default) or for every
+        pixel.  Results are the same either way; switch it off where the full tensors are read after every pass (batch_loss)."""
+        _lib.check(self.lib.pp_set_head_defer(self.ctx, 1 if on else 0), self.ctx, "pp_set_head_defer")
+        self.head_defer = bool(on) and not self._defer_env_off
+
+    def head_defer_active(self):
+        """Whether the passes of the committed plan run the deferred head (pp_head_defer_active): switched on, fp32 mode, 9-anchor
+        head on a gemm1x1 tiling."""
+        return bool(self.lib.pp_head_defer_active(self.ctx))
 
     def load_state_dict(self, sd):
         for k, v in sd.items():

@@ -220,18 +220,23 @@ def sequence_loss(config, clouds, gts, batch=16, nms_mode=0):
     batch = max(1, min(int(batch), eng.max_batch))
     metric = Metric(config)
     losses = []
-    for i0 in range(0, len(clouds), batch):
-        group = []
-        for c in clouds[i0:i0 + batch]:
-            pts = read_velodyne(c) if isinstance(c, (str, os.PathLike)) else np.ascontiguousarray(c, dtype=np.float32)
-            group.append(torch.from_numpy(pts).to(eng.device, non_blocking=True))
-        nb = len(group)
-        eng.infer_batch(group, nms_mode=nms_mode)
-        g = gts[i0:i0 + nb]
-        off = np.concatenate([[0], np.cumsum([len(np.asarray(c)) for c, _ in g])]).tolist()
-        cls = torch.from_numpy(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in g])).to(eng.device)
-        box = torch.from_numpy(np.concatenate([np.asarray(b, np.float32).reshape(-1, 7) for _, b in g])).to(eng.device)
-        terms = eng.batch_loss(box, cls, off, nb).cpu().numpy()
-        losses += [combine_terms(terms[f:f + 1]) for f in range(nb)]
-        metric.update_counts(terms)
+    was = eng.head_defer
+    eng.set_head_defer(False)  # batch_loss reads the full box / dir tensors after every pass: do not pay for both heads
+    try:
+        for i0 in range(0, len(clouds), batch):
+            group = []
+            for c in clouds[i0:i0 + batch]:
+                pts = read_velodyne(c) if isinstance(c, (str, os.PathLike)) else np.ascontiguousarray(c, dtype=np.float32)
+                group.append(torch.from_numpy(pts).to(eng.device, non_blocking=True))
+            nb = len(group)
+            eng.infer_batch(group, nms_mode=nms_mode)
+            g = gts[i0:i0 + nb]
+            off = np.concatenate([[0], np.cumsum([len(np.asarray(c)) for c, _ in g])]).tolist()
+            cls = torch.from_numpy(np.concatenate([np.asarray(c, np.int32).reshape(-1) for c, _ in g])).to(eng.device)
+            box = torch.from_numpy(np.concatenate([np.asarray(b, np.float32).reshape(-1, 7) for _, b in g])).to(eng.device)
+            terms = eng.batch_loss(box, cls, off, nb).cpu().numpy()
+            losses += [combine_terms(terms[f:f + 1]) for f in range(nb)]
+            metric.update_counts(terms)
+    finally:
+        eng.set_head_defer(was)
     return losses, metric

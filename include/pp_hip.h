@@ -149,6 +149,18 @@ int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int32_t* n_h, i
  * 5 PFN rows f32[max_voxels,64] | 6 coors i32[max_voxels,3] | 7 pillar count i32[1]. */
 int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream);
 
+/* Deferred head (default on).  Post-processing reads the box / dir logits of at most nms_pre_max anchors per class, so a pass of
+ * pp_infer_batch / pp_infer_frame computes the cls rows of the head for every pixel and the box / dir logits for the selected
+ * candidates only (bit-identical to the full head: same MFMA arithmetic on the same weight image).  The context's full box / dir
+ * tensors are then stale; whatever reads them (pp_batch_loss, pp_fetch_frame_tensor kinds 1 and 2) or would overwrite their inputs
+ * (pp_backbone, pp_update_head_weights, pp_commit_weights) first runs the full head over the retained concat buffer of that pass, so
+ * results never differ -- but a caller that needs the full tensors after EVERY pass (a loss per pass) should switch the mode off and
+ * not pay for both heads.  on = 0 / 1; the environment variable PP_HEAD_DEFER=0 (read at pp_create) forces it off.
+ * Active means: switched on AND the committed plan is the fp32 mode with the 9-anchor head on a gemm1x1 tiling; every other plan
+ * (16-bit modes, other anchor counts, a head on a direct tiling) runs the full head as before.  pp_head_defer_active: 1 / 0. */
+int pp_set_head_defer(pp_ctx* ctx, int on);
+int pp_head_defer_active(pp_ctx* ctx);
+
 /* ---- training targets and loss (anchor_assigner.py:337-457, loss_generator.py:26-253, metrics.py:14-69) ----
  * Ground truth of nb frames: gt f32[G][7] (x,y,z,l,w,h,r), gt_cls i32[G] 1-based class id in detect_class order,
  * gt_off_h HOST i32[nb+1] (frame f owns rows gt_off_h[f] .. gt_off_h[f+1]-1; non-decreasing, gt_off_h[nb] <= PP_ASSIGN_MAX_GT).

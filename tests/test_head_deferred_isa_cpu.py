@@ -1,0 +1,50 @@
+"""Resource audit of the deferred head's kernels (no GPU needed: hipcc cross-compiles for gfx950): every shape of the cls-only
+gemm1x1 pass and the candidate head must fit their register budgets without scratch -- a spilled B ring or accumulator would put
+private-memory traffic into kernels whose whole point is fewer bytes."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "3d_object_detection_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize", "-munsafe-fp-atomics",
+         "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull]
+
+
+def kernel_usage(src):
+    """{mangled kernel name: {remark field: value}} of one translation unit, built with the library's own flags."""
+    r = subprocess.run([HIPCC] + FLAGS + [src], cwd=CSRC, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z /\[\]]+): (\S+) \[-Rpass", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = m.group(2)
+    return out
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_candidate_head_uses_no_scratch():
+    k = {n: u for n, u in kernel_usage("postprocess.hip").items() if "post_cand_b" in n}
+    print(k)
+    assert len(k) == 1
+    u = next(iter(k.values()))
+    assert u["ScratchSize [bytes/lane]"] == "0" and u["VGPRs Spill"] == "0" and u["SGPRs Spill"] == "0"
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_cls_only_pass_uses_no_scratch():
+    # gemm1x1<MT = 1, NT = 4, EPI_HEAD_CLS = 4, ...>: every ring depth / register budget on the menu
+    k = {n: u for n, u in kernel_usage("conv.hip").items() if "gemm1x1ILi1ELi4ELi4E" in n}
+    print(k)
+    assert len(k) == 3
+    for n, u in k.items():
+        assert u["ScratchSize [bytes/lane]"] == "0" and u["VGPRs Spill"] == "0" and u["SGPRs Spill"] == "0", (n, u)
+        assert int(u["Occupancy [waves/SIMD]"]) >= 4, (n, u)  # two 8-wave workgroups per CU
