@@ -3204,6 +3204,7 @@ int pp_net_commit(pp_ctx* ctx)
             rc = pack_layer(ctx, L);
             if (rc) { if (tin) { (void)hipFree(tin - W6_FRONT_PAD); (void)hipFree(tout); } return rc; }
         }
+        ctx->sc1_kc = (net->layers[0].var.family == Family::Direct && net->layers[0].var.kc == 8) ? 8 : 4;
         {   // deferred head: fp32 plan with the 9-anchor head on a gemm1x1 tiling (its image is what the cls pass and the candidate head read)
             const Layer& head = net->layers.back();
             net->defer_ok = net->eff_prec == 0 && na == 9 && head.var.family == Family::Gemm1x1 && head.var.prec == 0 && head.var.io16 == 0;
@@ -3311,6 +3312,7 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
     const int H = ctx->H, W = ctx->W;
     if ((H % 4) || (W % 4)) return pp_fail(ctx, PP_E_ARG, "backbone: BEV grid must be a multiple of 8 in x and y");
     if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "backbone: batch exceeds cfg.max_batch");
+    ctx->sc1_last_nb = 0;
     if (ctx->cfg.norm_kind == 0) PP_HIP(hipMemsetAsync(net->stats, 0, STAT_FS * sizeof(double) * nb, stream));
     NormRef raw;
     const float* x = canvas;
@@ -3324,8 +3326,11 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
         const size_t cnt = (size_t)h * w;
         float** Bf = net->buf[b];
         int rc;
-        // strided conv (raw input) -> Bf[0] + stats(site 0)
-        if ((rc = launch_conv(ctx, net->layers[li++], x, Hin, Win, Bf[0], nullptr, raw, stat_slot(ctx, site_block(b, 0)), c, h, w, stream,
+        // strided conv (raw input) -> Bf[0] + stats(site 0); the fused fp32 path runs the first one over the active pixels only
+        if (b == 0 && pmap && net->eff_prec == 0 && pp_sc1_usable(ctx)) {
+            ++li;
+            if ((rc = pp_sc1_run(ctx, pmap, feat, Bf[0], stat_slot(ctx, site_block(0, 0)), STAT_FS, nb, stream))) return rc;
+        } else if ((rc = launch_conv(ctx, net->layers[li++], x, Hin, Win, Bf[0], nullptr, raw, stat_slot(ctx, site_block(b, 0)), c, h, w, stream,
                               nullptr, nullptr, nb, 0, 0, b == 0 ? pmap : nullptr, b == 0 ? feat : nullptr))) return rc;
         // y = relu(norm(Bf[0])) -> Bf[1] + stats(site 1) (the first Resnet2 unit's leading norm)
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_NORM))) return rc;
@@ -3527,7 +3532,8 @@ int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
 // context's internal frame buffers (device -> device, on `stream`).  kind: 0 cls f32[A], 1 box f32[A,7], 2 dir f32[A,2],
 // 3 anchor mask u8[A], 4 rpn output f32[320,H,W] = relu(norm(concat)) as RPN.forward returns it
 // (pointpillars8_shared.py:173-181; materialised here, the fused path never stores it), 5 PFN rows f32[max_voxels,64],
-// 6 coors i32[max_voxels,3], 7 pillar count i32[1].
+// 6 coors i32[max_voxels,3], 7 pillar count i32[1], 8 active list of the sparse first conv i32[1 + min(4 max_voxels, H W)]
+// (count, then the active output pixels in ascending order; PP_E_STATE when the pass ran the dense first conv).
 extern "C" int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream_)
 {
     if (!ctx || !dst) return pp_fail(ctx, PP_E_ARG, "pp_fetch_frame_tensor: null pointer");
@@ -3554,6 +3560,7 @@ extern "C" int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst
     case 5: src = ctx->f_feat + frame * mv * 64; bytes = mv * 64 * 4; break;
     case 6: src = ctx->f_coors + frame * mv * 3; bytes = mv * 12; break;
     case 7: src = ctx->f_num + frame * 4; bytes = 4; break;
+    case 8: return pp_sc1_fetch_list(ctx, frame, dst, stream);
     default: return pp_fail(ctx, PP_E_ARG, "pp_fetch_frame_tensor: unknown kind");
     }
     PP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));

@@ -119,6 +119,8 @@ static int create_impl(pp_ctx* ctx)
     PP_HIP(dalloc(&ctx->f_dir, Amax * 2));
     int rc = pp_net_create(ctx);
     if (rc) return rc;
+    rc = pp_sc1_create(ctx);
+    if (rc) return rc;
     rc = pp_post_create(ctx);
     return rc;
 }
@@ -149,6 +151,8 @@ extern "C" pp_ctx* pp_create(int device, const pp_config* cfg)
     ctx->W = ctx->gy / 2;
     if (const char* e = getenv("PP_HEAD_DEFER")) ctx->head_defer_env_off = e[0] == '0';
     ctx->head_defer = !ctx->head_defer_env_off;
+    if (const char* e = getenv("PP_SPARSE_CONV1")) ctx->sparse_conv1_env_off = e[0] == '0';
+    ctx->sparse_conv1 = !ctx->sparse_conv1_env_off;
     int rc = create_impl(ctx);
     if (rc) {
         g_create_err = ctx->err;
@@ -197,6 +201,7 @@ extern "C" void pp_destroy(pp_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     pp_net_destroy(ctx);
+    pp_sc1_destroy(ctx);
     pp_post_destroy(ctx);
     pp_assign_destroy(ctx);
     pp_train_destroy(ctx);
@@ -271,6 +276,7 @@ extern "C" int pp_commit_weights(pp_ctx* ctx)
     PP_HIP(hipMemcpy(ctx->pfn_shift, sh, sizeof(sh), hipMemcpyHostToDevice));
     int rc = pp_net_commit(ctx);
     if (rc) return rc;
+    if ((rc = pp_sc1_commit(ctx))) return rc;
     ctx->weights_ready = true;
     ++ctx->commit_gen;
     return 0;

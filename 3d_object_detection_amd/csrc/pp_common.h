@@ -134,6 +134,13 @@ struct pp_ctx {
     bool head_stale = false;         // f_box / f_dir do not hold the last pass
     int stale_nb = 0;                // frames of that pass
     hipStream_t stale_stream = nullptr;
+    // ---- sparse first convolution (sparse_conv1.hip; pp_set_sparse_conv1): the fused fp32 path computes the first conv for the output
+    //      pixels that see a pillar only ----
+    bool sparse_conv1 = true;        // the switch (default on; PP_SPARSE_CONV1=0 forces it off)
+    bool sparse_conv1_env_off = false;
+    void* sc1 = nullptr;             // weight image, active lists and their workspace
+    int sc1_kc = 4;                  // channels per chunk of the committed dense first-conv tiling: the sparse kernel walks K in its order
+    int sc1_last_nb = 0;             // frames of the last pass whose active lists the context holds (0: that pass ran the dense first conv)
 };
 // stage ids of pp_stage_mark / pp_stage_profile_end
 enum { PP_ST_VOXELIZE = 0, PP_ST_MASK = 1, PP_ST_PFN = 2, PP_ST_CONV = 3, PP_ST_NORM = 4, PP_ST_HEAD = 5, PP_ST_POST = 6 /* filter + threshold + gather */,
@@ -178,6 +185,14 @@ struct pp_head_gather { // inputs of the candidate head (postprocess.hip)
     int pre; const double* pre_acc; size_t pre_fs; double pre_inv_n; const float *pre_scale, *pre_shift; size_t aff_fs; float eps;
 };
 int pp_net_head_gather(pp_ctx* ctx, int nb, pp_head_gather* g);
+// sparse first convolution (sparse_conv1.hip): workspace at pp_create, weight image at pp_commit_weights; usable = switched on, image
+// committed, offsets fit 32 bits.  pp_sc1_run: nb pillar maps + PFN rows -> dense pre-norm [nb][64,H,W] (+ statistics; stat nullable)
+int pp_sc1_create(pp_ctx* ctx);
+void pp_sc1_destroy(pp_ctx* ctx);
+int pp_sc1_commit(pp_ctx* ctx);
+bool pp_sc1_usable(pp_ctx* ctx);
+int pp_sc1_run(pp_ctx* ctx, const int32_t* pmap, const float* feat, float* out, double* stat, size_t stat_fs, int nb, hipStream_t stream);
+int pp_sc1_fetch_list(pp_ctx* ctx, int frame, void* dst, hipStream_t stream);
 void pp_post_destroy(pp_ctx* ctx);
 void pp_assign_destroy(pp_ctx* ctx);
 void pp_train_destroy(pp_ctx* ctx);

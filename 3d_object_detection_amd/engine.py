@@ -250,6 +250,11 @@ class Engine:
         head on a gemm1x1 tiling."""
         return bool(self.lib.pp_head_defer_active(self.ctx))
 
+    def set_sparse_conv1(self, on):
+        """pp_set_sparse_conv1: fp32 passes of the fused path compute the first convolution for the output pixels that see a pillar only
+        (default) or with the dense tiling.  PP_SPARSE_CONV1=0 in the environment (read by pp_create) forces it off."""
+        _lib.check(self.lib.pp_set_sparse_conv1(self.ctx, 1 if on else 0), self.ctx, "pp_set_sparse_conv1")
+
     def load_state_dict(self, sd):
         for k, v in sd.items():
             if k.endswith("num_batches_tracked"):
@@ -452,11 +457,12 @@ class Engine:
 
     def fetch(self, frame, what):
         """Inspection hook (pp_fetch_frame_tensor): one tensor of frame `frame` of the last infer_batch / infer_frame
-        pass, copied out of the context's internal buffers.  what: cls | box | dir | mask | rpn | feat | coors | num."""
+        pass, copied out of the context's internal buffers.  what: cls | box | dir | mask | rpn | feat | coors | num | active (the
+        sparse first convolution's list: i32[1 + min(4 max_voxels, H W)] = count, then the active output pixels in ascending order)."""
         kinds = {"cls": (0, (self.A,), torch.float32), "box": (1, (self.A, 7), torch.float32), "dir": (2, (self.A, 2), torch.float32),
                  "mask": (3, (self.A,), torch.uint8), "rpn": (4, (320, self.H, self.W), torch.float32),
                  "feat": (5, (self.max_voxels, 64), torch.float32), "coors": (6, (self.max_voxels, 3), torch.int32),
-                 "num": (7, (1,), torch.int32)}
+                 "num": (7, (1,), torch.int32), "active": (8, (1 + min(4 * self.max_voxels, self.H * self.W),), torch.int32)}
         kind, shape, dtype = kinds[what]
         out = torch.empty(shape, dtype=dtype, device=self.device)
         with torch.cuda.device(self.device):

@@ -146,7 +146,10 @@ int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int32_t* n_h, i
  * pass out of the context's internal buffers into caller memory (device pointer, enqueued on stream).
  * kind 0 cls f32[A] | 1 box f32[A,7] | 2 dir f32[A,2] | 3 anchor mask u8[A] | 4 rpn output f32[320,H,W] as RPN.forward
  * returns it (pointpillars8_shared.py:173-181; the fused path never stores it, it is materialised for the copy) |
- * 5 PFN rows f32[max_voxels,64] | 6 coors i32[max_voxels,3] | 7 pillar count i32[1]. */
+ * 5 PFN rows f32[max_voxels,64] | 6 coors i32[max_voxels,3] | 7 pillar count i32[1] |
+ * 8 active list of the sparse first convolution i32[1 + min(4 max_voxels, H W)]: the count, then the active output pixels
+ * (index = x * W + y on the level-0 map) in ascending order, entries past the count unspecified; PP_E_STATE when the last pass
+ * ran the dense first convolution. */
 int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream);
 
 /* Deferred head (default on).  Post-processing reads the box / dir logits of at most nms_pre_max anchors per class, so a pass of
@@ -160,6 +163,14 @@ int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* str
  * (16-bit modes, other anchor counts, a head on a direct tiling) runs the full head as before.  pp_head_defer_active: 1 / 0. */
 int pp_set_head_defer(pp_ctx* ctx, int on);
 int pp_head_defer_active(pp_ctx* ctx);
+
+/* Sparse first convolution (default on).  In the fp32 mode a pass of pp_infer_batch / pp_infer_frame computes the first convolution
+ * (3x3, stride 2, on the pillar map) only for the output pixels with a pillar among their 3x3 input cells: a per-frame list of these
+ * pixels in ascending order, a gather-GEMM over the list, and a scatter into the zero-filled dense map the rest of the network reads.
+ * Same values up to the fp32 summation order inside the convolution and its InstanceNorm statistics (~3e-5 on the logits).  A
+ * frame's result does not depend on the batch it rides in.  on = 0 / 1; the environment variable PP_SPARSE_CONV1=0 (read at
+ * pp_create) forces it off.  The 16-bit modes and the dense-canvas entry points (pp_scatter + pp_backbone) are not affected. */
+int pp_set_sparse_conv1(pp_ctx* ctx, int on);
 
 /* ---- training targets and loss (anchor_assigner.py:337-457, loss_generator.py:26-253, metrics.py:14-69) ----
  * Ground truth of nb frames: gt f32[G][7] (x,y,z,l,w,h,r), gt_cls i32[G] 1-based class id in detect_class order,
