@@ -2241,6 +2241,7 @@ struct pp_net {
     bool up16 = false;  // pp_set_precision 4 with every layer on a 16-bit-tensor tiling: the level buffers and the concat buffer `up` hold fp16
     bool defer_ok = false; // the committed plan can run the deferred head: fp32 mode, 9-anchor head on a gemm1x1 tiling
     Variant cls_var;       // tiling of the cls-only head pass (chosen at pp_commit_weights when defer_ok)
+    const float* tap[3] = {}; // block outputs of the last pp_run_backbone pass (what the three upsamplers read): pp_backbone_taps
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };
 
@@ -3361,6 +3362,7 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
                 cur = t1;
             }
         }
+        net->tap[b] = cur;
         // deconv on the raw block output -> channel slice of up[320,H,W] + stats (site 7, channel offset)
         {
             const Layer& L = net->layers[li++];
@@ -3479,10 +3481,39 @@ extern "C" int pp_head(pp_ctx* ctx, const float* rpn_out, float* cls, float* box
     return pp_head_impl(ctx, rpn_out, raw, cls, box, dir, 1, stream);
 }
 
-// The head's packed weight image as an index map (pp_common.h): pack_layer itself packs an index-valued weight (element i of the
-// natural [cls | box | dir][320] order holds the float i + 1; exact below 2^24) into a scratch image with the committed tiling, so
-// whatever row order (head_tile_row), row padding and K blocking that tiling uses is read back, not restated.  fp32 images only:
-// the 16-bit images round their elements, the indices would not survive.  Synchronous; called once per commit by train.hip.
+// A packed weight image as an index map (pp_common.h): pack_layer itself packs an index-valued weight (element i of the
+// concatenation of the named host tensors holds the float i + 1; exact below 2^24) into a scratch image with the layer's committed
+// tiling, so whatever row order (head_tile_row), row padding and K blocking that tiling uses is read back, not restated.  fp32 images
+// only: the 16-bit images round their elements, the indices would not survive.  Synchronous; called once per commit by train.hip.
+static int layer_index_map(pp_ctx* ctx, const Layer& L, const std::vector<std::string>& names, std::vector<int32_t>& wmap)
+{
+    std::vector<std::vector<float>> saved(names.size());
+    float idx = 1.f;
+    for (size_t h = 0; h < names.size(); ++h) {
+        auto w = ctx->host_w.find(names[h]);
+        if (w == ctx->host_w.end()) {
+            for (size_t g = 0; g < h; ++g) ctx->host_w[names[g]].data.swap(saved[g]);
+            return pp_fail(ctx, PP_E_NAME, ("missing weight " + names[h]).c_str());
+        }
+        saved[h] = w->second.data;
+        for (float& v : w->second.data) v = idx++;
+    }
+    Layer scratch = L;
+    scratch.w = nullptr;
+    int rc = idx > 16777216.f ? pp_fail(ctx, PP_E_ARG, "weight too large for an index map") : pack_layer(ctx, scratch);
+    for (size_t h = 0; h < names.size(); ++h) ctx->host_w[names[h]].data.swap(saved[h]);
+    if (rc) { if (scratch.w) (void)hipFree(scratch.w); return rc; }
+    size_t bytes = 0;
+    hipError_t e = hipMemPtrGetInfo(scratch.w, &bytes);
+    std::vector<float> image(bytes / sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(image.data(), scratch.w, image.size() * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(scratch.w);
+    PP_HIP(e);
+    wmap.resize(image.size());
+    for (size_t i = 0; i < image.size(); ++i) wmap[i] = (int32_t)image[i] - 1;
+    return 0;
+}
+
 int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
 {
     pp_net* net = (pp_net*)ctx->net;
@@ -3492,28 +3523,13 @@ int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
     const int na = ctx->cfg.num_anchor_per_loc;
     const char* names[3] = {"heads.conv_cls.weight", "heads.conv_box.weight", "heads.conv_dir.weight"};
     const int cnt[3] = {na, 7 * na, 2 * na};
-    std::vector<float> saved[3];
-    float idx = 1.f;
     for (int h = 0; h < 3; ++h) {
         auto w = ctx->host_w.find(names[h]);
         if (w == ctx->host_w.end() || (int64_t)w->second.data.size() != (int64_t)cnt[h] * head.cin)
             return pp_fail(ctx, PP_E_NAME, (std::string("missing/mis-shaped weight ") + names[h]).c_str());
-        saved[h] = w->second.data;
-        for (float& v : w->second.data) v = idx++;
     }
-    Layer scratch = head;
-    scratch.w = nullptr;
-    int rc = pack_layer(ctx, scratch);
-    for (int h = 0; h < 3; ++h) ctx->host_w[names[h]].data.swap(saved[h]);
-    if (rc) { if (scratch.w) (void)hipFree(scratch.w); return rc; }
-    size_t bytes = 0;
-    hipError_t e = hipMemPtrGetInfo(scratch.w, &bytes);
-    std::vector<float> image(bytes / sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(image.data(), scratch.w, image.size() * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(scratch.w);
-    PP_HIP(e);
-    img->wmap.resize(image.size());
-    for (size_t i = 0; i < image.size(); ++i) img->wmap[i] = (int32_t)image[i] - 1;
+    int rc = layer_index_map(ctx, head, {names[0], names[1], names[2]}, img->wmap);
+    if (rc) return rc;
     img->w = head.w;
     img->bias = net->head_bias;
     img->bmap.assign((size_t)head_rows(na), -1);
@@ -3525,6 +3541,42 @@ int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
         img->bpmap.resize(96);
         for (int t = 0; t < 96; ++t) img->bpmap[t] = head_tile_row(t);
     }
+    return 0;
+}
+
+// The packed image of upsampler `branch` (0..2) of the committed plan, described the same way: wmap[i] is the element of the
+// state_dict tensor rpn.deconv<branch+1>.0.weight [Cin][Cup][s][s] that image element i holds, -1 for padding.
+int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    int seen = 0;
+    for (Layer& L : net->layers) {
+        if (L.kind != 1 || seen++ != branch) continue;
+        if (net->eff_prec != 0 || L.var.prec != 0 || L.var.io16 != 0)
+            return pp_fail(ctx, PP_E_ARG, "upsampler weights can be rewritten in place in the fp32 mode only (the committed plan packs them in a 16-bit format)");
+        int rc = layer_index_map(ctx, L, {L.wkey}, img->wmap);
+        if (rc) return rc;
+        img->w = L.w;
+        img->elems = (size_t)L.cin * L.cout * L.up * L.up;
+        return 0;
+    }
+    return pp_fail(ctx, PP_E_ARG, "pp_net_deconv_image: no such upsampler");
+}
+
+extern "C" int pp_backbone_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_taps: weights not committed");
+    if (!canvas || !rpn_out || !x1 || !x2 || !x3) return pp_fail(ctx, PP_E_ARG, "pp_backbone_taps: null pointer");
+    pp_net* net = (pp_net*)ctx->net;
+    if (net->eff_prec != 0 || net->up16)
+        return pp_fail(ctx, PP_E_ARG, "pp_backbone_taps: fp32 mode only (in the 16-bit modes the level buffers may hold fp16)");
+    int rc = pp_backbone(ctx, canvas, rpn_out, stream_);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    float* dst[3] = {x1, x2, x3};
+    for (int b = 0; b < 3; ++b)
+        PP_HIP(hipMemcpyAsync(dst[b], net->tap[b], (size_t)kC[b] * (ctx->H >> b) * (ctx->W >> b) * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return 0;
 }
 

@@ -1,0 +1,423 @@
+// Training side of the neck (gfx950): the backward of one RPN upsampling branch, ConvTranspose2d(k = s) -> InstanceNorm2d(eps 1e-3,
+// no affine) -> ReLU (pointpillars8_shared.py:139-171), and the in-place rewrite of the three upsamplers' packed weights after an
+// optimizer step.  fp32 throughout, InstanceNorm backbone only.
+//
+// A ConvTranspose with kernel = stride is a GEMM on the INPUT grid: with R = Cup s s rows r = co s s + ky s + kx and p = h w input
+// pixels, Z[r][q] = sum_ci w[ci][r] x[ci][q] is output element (co, s qy + ky, s qx + kx), and w [Cin][Cup][s][s] IS [Cin][R].
+// pp_neck_backward keeps Z -- and then dZ, in place -- in that row layout in a workspace ([frame][R][pld], pld = p rounded up to 4,
+// padding columns zero), so both gradient products are plain GEMMs with contiguous operands:
+//   k_neck_fwd    Z = w^T x                                     M = R,   N = p, K = Cin
+//   k_neck_stats  per (frame, co): sum z, sum z^2, sum Gr, sum Gr z in fp64 over S segments of the channel's N = H W elements
+//   k_neck_dz     mean / rstd / the two backward means from the S partials, dZ = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) over Z
+//   k_neck_dw     dw[ci][r] = sum_{frame, q} x[ci][q] dZ[r][q]  M = Cin, N = R, K = frames x p, split into pixel / frame ranges
+//   k_neck_dw_reduce  partials summed in index order (double, rounded once)
+//   k_neck_dx     dx[ci][q] = sum_r w[ci][r] dZ[r][q]           M = Cin, N = p, K = R, summed in blocks of DX_BLOCK rows
+// The three products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory (every operand row is contiguous along
+// the lane's load direction; the sum over K is order-free, so where K is the contiguous direction a lane's four k-steps are one
+// 16-byte load, as in k_head_dw).
+//
+// Determinism: no atomics at all.  Segment and range counts depend on the shapes only; a frame's Z, statistics, dZ and dx do not depend
+// on the batch it rides in, dw depends on nb within fp32 summation error (the K ranges do).
+#include <cmath>
+#include "pp_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr size_t Z_BUDGET = (size_t)256 << 20; // bytes of Z / dZ workspace: larger batches run in frame chunks
+constexpr int DW_WGS = 512;                    // workgroups a dw launch aims at (output tiles x K ranges)
+constexpr int DW_MAX_SPLIT = 256;
+constexpr int ST_MAX_SEG = 64;
+constexpr int DX_BLOCK = 64;                   // rows of R that k_neck_dx sums in one accumulator before adding the block to the total
+
+struct neck_ws {
+    float* z = nullptr;     size_t z_elems = 0;
+    double* st = nullptr;   size_t st_elems = 0;
+    float* part = nullptr;  size_t part_elems = 0;
+    uint64_t img_gen = 0;   // ctx->commit_gen the index maps belong to (0: none)
+    pp_layer_image img[3];
+    int32_t* wmap[3] = {nullptr, nullptr, nullptr};
+};
+
+struct geom {
+    int Cin, Cup, s, ls, h, w, p, pld, R, coff, H, W;
+};
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <typename T>
+int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need, hipStream_t stream)
+{
+    if (need <= *have) return 0;
+    PP_HIP(hipStreamSynchronize(stream)); // a running kernel may still read the old buffer
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    PP_HIP(hipMalloc((void**)buf, need * sizeof(T)));
+    *have = need;
+    return 0;
+}
+
+// ---- Z = w^T x: workgroup tile 64 rows x 64 pixels, four waves 2 x 2, each 32 x 32 (2 x 2 MFMA tiles) -------------------------
+__global__ void __launch_bounds__(256) k_neck_fwd(const float* __restrict__ x, const float* __restrict__ wt, float* __restrict__ Z, int Cin, int R,
+                                                  int p, int pld)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int r0 = blockIdx.y * 64 + 32 * (wave >> 1), p0 = blockIdx.x * 64 + 32 * (wave & 1);
+    const float* xf = x + (size_t)blockIdx.z * Cin * p;
+    float* Zf = Z + (size_t)blockIdx.z * R * pld;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int px0 = p0 + l16, px1 = p0 + 16 + l16;
+    for (int k0 = 0; k0 < Cin; k0 += 4) {
+        const float* wr = wt + (size_t)(k0 + q) * R + r0 + l16;
+        const float* xr = xf + (size_t)(k0 + q) * p;
+        const float a0 = wr[0], a1 = wr[16];
+        const float b0 = px0 < p ? xr[px0] : 0.f, b1 = px1 < p ? xr[px1] : 0.f;
+        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int px = p0 + 16 * b + l16;
+            if (px < pld) // columns p .. pld-1 get exact zeros (their x was masked): the padding the dw product reads
+#pragma unroll
+                for (int i = 0; i < 4; ++i) Zf[(size_t)(r0 + 16 * a + 4 * q + i) * pld + px] = acc[a][b][i];
+        }
+}
+
+// element i of channel co's [H][W] output plane -> its place in the row layout
+__device__ __forceinline__ size_t z_index(int i, int co, int W, int ls, int w, int pld)
+{
+    const int s = 1 << ls, oy = i / W, ox = i - oy * W;
+    const int row = (co << (2 * ls)) + ((oy & (s - 1)) << ls) + (ox & (s - 1));
+    return (size_t)row * pld + (size_t)(oy >> ls) * w + (ox >> ls);
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ---- statistics: grid (S, Cup, frames); st[((frame Cup + co) S + seg) 4 + {z, z^2, Gr, Gr z}] ------------------------------------
+__global__ void __launch_bounds__(256) k_neck_stats(const float* __restrict__ Z, const float* __restrict__ y, const float* __restrict__ dy,
+                                                    double* __restrict__ st, int Cup, int coff, int H, int W, int ls, int w, int pld, int R,
+                                                    int seg_len)
+{
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x, co = blockIdx.y, f = blockIdx.z, N = H * W;
+    const float* Zf = Z + (size_t)f * R * pld;
+    const size_t plane = ((size_t)f * 320 + coff + co) * N;
+    const int i0 = blockIdx.x * seg_len, i1 = i0 + seg_len < N ? i0 + seg_len : N;
+    double sz = 0.0, szz = 0.0, sg = 0.0, sgz = 0.0;
+    for (int i = i0 + tid; i < i1; i += 256) {
+        const double z = (double)Zf[z_index(i, co, W, ls, w, pld)];
+        const double g = y[plane + i] > 0.f ? (double)dy[plane + i] : 0.0; // the mask is the caller's y, never a recomputed sign
+        sz += z; szz += z * z; sg += g; sgz += g * z;
+    }
+    sz = wave_sum(sz); szz = wave_sum(szz); sg = wave_sum(sg); sgz = wave_sum(sgz);
+    if ((tid & 63) == 0) { red[tid >> 6][0] = sz; red[tid >> 6][1] = szz; red[tid >> 6][2] = sg; red[tid >> 6][3] = sgz; }
+    __syncthreads();
+    if (tid < 4) st[(((size_t)f * Cup + co) * gridDim.x + blockIdx.x) * 4 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
+// ---- dZ over Z, same grid.  sum(Gr xhat) = rstd (sum(Gr z) - mean sum(Gr)): formed in double from the fp64 sums ------------------
+__global__ void __launch_bounds__(256) k_neck_dz(float* __restrict__ Z, const float* __restrict__ y, const float* __restrict__ dy,
+                                                 const double* __restrict__ st, int Cup, int coff, int H, int W, int ls, int w, int pld, int R,
+                                                 int seg_len)
+{
+    const int tid = threadIdx.x, co = blockIdx.y, f = blockIdx.z, N = H * W, S = gridDim.x;
+    const double* sp = st + ((size_t)f * Cup + co) * S * 4;
+    double sz = 0.0, szz = 0.0, sg = 0.0, sgz = 0.0;
+    for (int k = 0; k < S; ++k) { sz += sp[4 * k]; szz += sp[4 * k + 1]; sg += sp[4 * k + 2]; sgz += sp[4 * k + 3]; }
+    const double inv_n = 1.0 / (double)N, mean = sz * inv_n;
+    double var = szz * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const double rstd = 1.0 / sqrt(var + 1e-3);
+    const float meanf = (float)mean, rstdf = (float)rstd;
+    const float c1 = (float)(sg * inv_n), c2 = (float)(rstd * (sgz - mean * sg) * inv_n);
+    float* Zf = Z + (size_t)f * R * pld;
+    const size_t plane = ((size_t)f * 320 + coff + co) * N;
+    const int i0 = blockIdx.x * seg_len, i1 = i0 + seg_len < N ? i0 + seg_len : N;
+    for (int i = i0 + tid; i < i1; i += 256) {
+        const size_t zi = z_index(i, co, W, ls, w, pld);
+        const float xhat = (Zf[zi] - meanf) * rstdf;
+        const float g = y[plane + i] > 0.f ? dy[plane + i] : 0.f;
+        Zf[zi] = rstdf * ((g - c1) - xhat * c2);
+    }
+}
+
+// ---- dw: workgroup tile 64 ci x 32 NB rows, four waves 2 x 2, each 32 ci x 16 NB rows.  K runs over 16-pixel chunks of the launch's
+// frames (chunk c: frame c / cpf, pixels 16 (c % cpf) ..); a lane takes pixels 4 q .. 4 q + 3 of the chunk as its four k-steps, one
+// 16-byte load per operand row.  blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z.
+template <int NB>
+__global__ void __launch_bounds__(256) k_neck_dw(const float* __restrict__ x, const float* __restrict__ dZ, float* __restrict__ part, int Cin, int R,
+                                                 int p, int pld, int cpf, int nchunks, int cps, int gbase, int xvec)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int ci0 = blockIdx.y * 64 + 32 * (wave >> 1), r0 = blockIdx.x * (32 * NB) + 16 * NB * (wave & 1);
+    f32x4 acc[2][NB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
+    for (int c = c0; c < c1; ++c) {
+        const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
+        const float* xf = x + (size_t)f * Cin * p + pb;
+        const float* zf = dZ + (size_t)f * R * pld + pb;
+        float xa[2][4], zb[NB][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const float* s_ = xf + (size_t)(ci0 + 16 * a + l16) * p;
+            if (xvec) {
+                const float4 v = pb < p ? *reinterpret_cast<const float4*>(s_) : make_float4(0.f, 0.f, 0.f, 0.f);
+                xa[a][0] = v.x; xa[a][1] = v.y; xa[a][2] = v.z; xa[a][3] = v.w;
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) xa[a][s] = pb + s < p ? s_[s] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const float4 v = pb < pld ? *reinterpret_cast<const float4*>(zf + (size_t)(r0 + 16 * b + l16) * pld) : make_float4(0.f, 0.f, 0.f, 0.f);
+            zb[b][0] = v.x; zb[b][1] = v.y; zb[b][2] = v.z; zb[b][3] = v.w;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[a][s], zb[b][s], acc[a][b], 0, 0, 0);
+    }
+    float* pw = part + (size_t)(gbase + blockIdx.z) * Cin * R;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pw[(size_t)(ci0 + 16 * a + 4 * q + i) * R + r0 + 16 * b + l16] = acc[a][b][i];
+}
+
+__global__ void __launch_bounds__(256) k_neck_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += (double)part[(size_t)g * n + i];
+    dw[i] = (float)s;
+}
+
+// ---- dx: a workgroup covers ALL Cin channels (WM = Cin / 64 waves down, 4 / WM across), each wave 64 ci x 32 pixels, so dZ is read
+// once.  K = R in steps of 16 rows: a lane's four k-steps are rows 4 q .. 4 q + 3, one 16-byte load of w per ci row.  The sum over R
+// (up to 2048 terms) is blocked: each DX_BLOCK rows accumulate from zero and the block sums are then added in row order, so the
+// rounding error grows with the block length and the block count, not with R (one running accumulator over R = 2048 deviates from
+// float64 about eight times as much).
+template <int WM>
+__global__ void __launch_bounds__(256) k_neck_dx(const float* __restrict__ wt, const float* __restrict__ dZ, float* __restrict__ dx, int Cin, int R,
+                                                 int p, int pld)
+{
+    constexpr int WN = 4 / WM;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int ci0 = 64 * (wave / WN), p0 = blockIdx.x * (32 * WN) + 32 * (wave % WN);
+    const float* zf = dZ + (size_t)blockIdx.z * R * pld;
+    float* dxf = dx + (size_t)blockIdx.z * Cin * p;
+    f32x4 tot[4][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) tot[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int px0 = p0 + l16, px1 = p0 + 16 + l16;
+    for (int rb0 = 0; rb0 < R; rb0 += DX_BLOCK) { // R = Cup s s is a multiple of DX_BLOCK
+        f32x4 acc[4][2];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int rb = rb0; rb < rb0 + DX_BLOCK; rb += 16) {
+            float wa[4][4], zb[2][4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const float4 v = *reinterpret_cast<const float4*>(wt + (size_t)(ci0 + 16 * a + l16) * R + rb + 4 * q);
+                wa[a][0] = v.x; wa[a][1] = v.y; wa[a][2] = v.z; wa[a][3] = v.w;
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const float* zr = zf + (size_t)(rb + 4 * q + s) * pld;
+                zb[0][s] = px0 < p ? zr[px0] : 0.f;
+                zb[1][s] = px1 < p ? zr[px1] : 0.f;
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a][s], zb[b][s], acc[a][b], 0, 0, 0);
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) tot[a][b] += acc[a][b];
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int px = p0 + 16 * b + l16;
+            if (px < p)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dxf[(size_t)(ci0 + 16 * a + 4 * q + i) * p + px] = tot[a][b][i];
+        }
+}
+
+// dst[i] = src[map[i]], 0 where map[i] < 0 (padding of the packed image)
+__global__ void __launch_bounds__(256) k_gather1(float* __restrict__ dst, const int32_t* __restrict__ map, int n, const float* __restrict__ src, int nsrc)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int m = map[i];
+    dst[i] = m < 0 || m >= nsrc ? 0.f : src[m];
+}
+
+neck_ws* workspace(pp_ctx* ctx)
+{
+    if (!ctx->neck) ctx->neck = new neck_ws();
+    return (neck_ws*)ctx->neck;
+}
+
+// K ranges of one dw launch over `nchunks` 16-pixel chunks
+void dw_ranges(int tiles, int nchunks, int* splits, int* cps)
+{
+    int sp = DW_WGS / tiles;
+    sp = sp < 1 ? 1 : sp > DW_MAX_SPLIT ? DW_MAX_SPLIT : sp;
+    if (sp > nchunks) sp = nchunks;
+    *cps = (nchunks + sp - 1) / sp;
+    *splits = (nchunks + *cps - 1) / *cps;
+}
+
+} // namespace
+
+void pp_neck_destroy(pp_ctx* ctx)
+{
+    neck_ws* w = (neck_ws*)ctx->neck;
+    if (!w) return;
+    void* q[] = {w->z, w->st, w->part, w->wmap[0], w->wmap[1], w->wmap[2]};
+    for (void* x : q)
+        if (x) (void)hipFree(x);
+    delete w;
+    ctx->neck = nullptr;
+}
+
+extern "C" int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const float* wt, const float* y, const float* dy, int nb, float* dw,
+                                float* dx, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
+    if (branch < 0 || branch > 2) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: branch must be 0, 1 or 2");
+    if (!x || !wt || !y || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: null pointer");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: nb must be 1 .. max_batch");
+    if ((ctx->H % 4) || (ctx->W % 4)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: BEV grid must be a multiple of 8 in x and y");
+    if (!aligned16(wt)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: w must be 16-byte aligned");
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: tensors must be 4-byte aligned");
+    geom g;
+    g.H = ctx->H; g.W = ctx->W; g.ls = branch; g.s = 1 << branch;
+    g.Cin = 64 << branch; g.Cup = branch ? 128 : 64; g.coff = branch == 0 ? 0 : branch == 1 ? 64 : 192;
+    g.h = g.H >> branch; g.w = g.W >> branch; g.p = g.h * g.w; g.pld = (g.p + 3) & ~3; g.R = g.Cup * g.s * g.s;
+    const int N = g.H * g.W;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    neck_ws* ws = workspace(ctx);
+    // frames per chunk, statistics segments, K ranges: functions of the shapes alone
+    const size_t zf_elems = (size_t)g.R * g.pld;
+    int fc = (int)(Z_BUDGET / (zf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
+    S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
+    const int seg_len = (N + S - 1) / S;
+    S = (N + seg_len - 1) / seg_len;
+    const int NBt = g.R >= 128 ? 4 : 2;
+    const int tiles = (g.R / (32 * NBt)) * (g.Cin / 64), cpf = (g.p + 15) / 16;
+    int G = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        G += sp;
+    }
+    const int nw = g.Cin * g.R;
+    int rc;
+    if ((rc = grow(ctx, &ws->z, &ws->z_elems, (size_t)fc * zf_elems, stream)) ||
+        (rc = grow(ctx, &ws->st, &ws->st_elems, (size_t)fc * g.Cup * S * 4, stream)) ||
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)G * nw, stream)))
+        return rc;
+    const int xvec = g.p % 4 == 0 && aligned16(x);
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const float* xc = x + (size_t)f0 * g.Cin * g.p;
+        const float* yc = y + (size_t)f0 * 320 * N;
+        const float* dyc = dy + (size_t)f0 * 320 * N;
+        hipLaunchKernelGGL(k_neck_fwd, dim3(pp_div_up(g.pld, 64), g.R / 64, fn), dim3(256), 0, stream, xc, wt, ws->z, g.Cin, g.R, g.p, g.pld);
+        hipLaunchKernelGGL(k_neck_stats, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, ws->st, g.Cup, g.coff, g.H, g.W, g.ls, g.w,
+                           g.pld, g.R, seg_len);
+        hipLaunchKernelGGL(k_neck_dz, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, ws->st, g.Cup, g.coff, g.H, g.W, g.ls, g.w, g.pld,
+                           g.R, seg_len);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(g.R / (32 * NBt), g.Cin / 64, sp);
+        if (NBt == 4)
+            hipLaunchKernelGGL(k_neck_dw<4>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
+        else
+            hipLaunchKernelGGL(k_neck_dw<2>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
+        gbase += sp;
+        if (dx) {
+            float* dxc = dx + (size_t)f0 * g.Cin * g.p;
+            if (g.Cin == 64)
+                hipLaunchKernelGGL(k_neck_dx<1>, dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
+            else if (g.Cin == 128)
+                hipLaunchKernelGGL(k_neck_dx<2>, dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
+            else
+                hipLaunchKernelGGL(k_neck_dx<4>, dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
+        }
+    }
+    hipLaunchKernelGGL(k_neck_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, G, nw, dw);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const float* w3, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_neck_weights: no committed weights to update (pp_commit_weights first)");
+    if (!w1 || !w2 || !w3) return pp_fail(ctx, PP_E_ARG, "pp_update_neck_weights: null pointer");
+    if (pp_effective_precision(ctx) != 0)
+        return pp_fail(ctx, PP_E_ARG, "pp_update_neck_weights: fp32 mode only (the committed plan packs the upsamplers in a 16-bit format)");
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    neck_ws* ws = workspace(ctx);
+    if (ws->img_gen != ctx->commit_gen) { // first update after a commit: read the committed images' layout back (synchronous)
+        for (int b = 0; b < 3; ++b) {
+            int rc = pp_net_deconv_image(ctx, b, &ws->img[b]);
+            if (rc) return rc;
+            if (ws->wmap[b]) { (void)hipFree(ws->wmap[b]); ws->wmap[b] = nullptr; }
+            PP_HIP(hipMalloc((void**)&ws->wmap[b], ws->img[b].wmap.size() * sizeof(int32_t)));
+            PP_HIP(hipMemcpy(ws->wmap[b], ws->img[b].wmap.data(), ws->img[b].wmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        ws->img_gen = ctx->commit_gen;
+    }
+    const float* src[3] = {w1, w2, w3};
+    for (int b = 0; b < 3; ++b) {
+        const int n = (int)ws->img[b].wmap.size();
+        hipLaunchKernelGGL(k_gather1, dim3(pp_div_up(n, 256)), dim3(256), 0, stream, ws->img[b].w, ws->wmap[b], n, src[b], (int)ws->img[b].elems);
+    }
+    PP_HIP(hipGetLastError());
+    return 0;
+}

@@ -126,6 +126,7 @@ struct pp_ctx {
     //      the natural-order copy of the head weights and the index map of the head's packed image are rebuilt after a commit ----
     uint64_t commit_gen = 0;
     void* trn = nullptr;
+    void* neck = nullptr;            // neck backward (neck_train.hip): dZ workspace, dW partials, index maps of the upsampler images
     // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
     //      the selected candidates only; f_box / f_dir are then stale until pp_head_materialise runs the full head over the retained
     //      concat buffer and statistics of that pass ----
@@ -205,5 +206,14 @@ struct pp_head_image {
     std::vector<int32_t> wmap, bmap, bpmap;
 };
 int pp_net_head_image(pp_ctx* ctx, pp_head_image* img);
+// The same for upsampler `branch` (0..2), for pp_update_neck_weights (neck_train.hip): wmap[i] is the element of the state_dict tensor
+// rpn.deconv<branch+1>.0.weight [Cin][Cup][s][s] (elems in all) that image element i holds, -1 for padding.
+struct pp_layer_image {
+    float* w = nullptr;
+    size_t elems = 0;
+    std::vector<int32_t> wmap;
+};
+int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img);
+void pp_neck_destroy(pp_ctx* ctx);
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

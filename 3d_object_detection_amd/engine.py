@@ -398,6 +398,69 @@ class Engine:
             _lib.check(self.lib.pp_update_head_weights(self.ctx, *[_ptr(args[k]) for k in self.HEAD_KEYS], _stream()), self.ctx,
                        "pp_update_head_weights")
 
+    # ------------------------------------------------------------------ neck training (neck_train.hip)
+    NECK_KEYS = ("rpn.deconv1.0.weight", "rpn.deconv2.0.weight", "rpn.deconv3.0.weight")
+
+    def neck_shapes(self, branch):
+        """(x shape [Cin,h,w], w shape [Cin,Cup,s,s]) of upsampling branch 0..2."""
+        cin, cup, s = 64 << branch, 128 if branch else 64, 1 << branch
+        return (cin, self.H >> branch, self.W >> branch), (cin, cup, s, s)
+
+    def backbone_taps(self, canvas):
+        """pp_backbone_taps: backbone(canvas) and the three block outputs the upsamplers read -> (rpn_out [1,320,H,W], x1 [1,64,H,W],
+        x2 [1,128,H/2,W/2], x3 [1,256,H/4,W/4]).  fp32 mode only."""
+        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
+            raise ValueError("backbone_taps: expected a contiguous canvas")
+        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
+             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_taps: canvas [1,64,gx,gy]")
+        out = self._t((1, 320, self.H, self.W), torch.float32)
+        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_backbone_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]), _stream()),
+                       self.ctx, "pp_backbone_taps")
+        return (out, *taps)
+
+    def neck_backward(self, branch, x, w, y, dy, need_dx=True):
+        """pp_neck_backward: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
+        dL/d(rpn_out) dy [nb,320,H,W] -> (dw [Cin,Cup,s,s] summed over the frames, dx [nb,Cin,h,w] or None when need_dx is False).
+        fp32, deterministic, stateless."""
+        if branch not in (0, 1, 2):
+            raise ValueError(f"neck_backward: branch must be 0, 1 or 2, got {branch!r}")
+        xs, wsh = self.neck_shapes(branch)
+        nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"neck_backward: x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
+        x = _chk(x, torch.float32, (nb,) + xs, "neck_backward: x")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, "neck_backward: w")
+        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), "neck_backward: y")
+        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), "neck_backward: dy")
+        for t, what in ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")):
+            if t.device != self.device:
+                raise ValueError(f"neck_backward: {what} is on {t.device}, the engine on {self.device}")
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
+        dw = self._t(wsh, torch.float32)
+        dx = self._t((nb,) + xs, torch.float32) if need_dx else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_neck_backward(self.ctx, branch, _ptr(x), _ptr(w), _ptr(y), _ptr(dy), nb, _ptr(dw), _ptr(dx), _stream()),
+                       self.ctx, "pp_neck_backward")
+        return dw, dx
+
+    def update_neck_weights(self, params):
+        """pp_update_neck_weights: {state_dict name: device tensor} of rpn.deconv{1,2,3}.0.weight -> the committed upsampler images, in
+        place on the current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
+        args = []
+        for b, k in enumerate(self.NECK_KEYS):
+            if k not in params:
+                raise KeyError(f"update_neck_weights: {k} is missing")
+            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
+            t = _chk(t, torch.float32, self.neck_shapes(b)[1], "update_neck_weights: " + k)
+            if t.device != self.device:
+                raise ValueError(f"update_neck_weights: {k} is on {t.device}, the engine on {self.device}")
+            args.append(t)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_neck_weights(self.ctx, *[_ptr(t) for t in args], _stream()), self.ctx, "pp_update_neck_weights")
+
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1 + _lib.PP_MAX_CLASSES,), dtype=torch.int32, device=self.device)

@@ -1,9 +1,11 @@
 """networks.pointpillars8_shared.PointPillars (reference pointpillars8_shared.py:346-382): the eager
 network with the InstanceNorm backbone, running PFN / scatter / RPN / head as HIP kernels.
 
-Training surface: head-only fine-tuning.  The backbone (PFN, scatter, RPN) is FROZEN: it has no backward pass, and
-parameters() yields the six tensors of the anchor head only.  train() makes them require grad; heads(x) then records a
-torch.autograd.Function whose backward is pp_head_backward (csrc/train.hip)."""
+Training surface: head fine-tuning, optionally with the neck.  train() makes the six tensors of the anchor head require grad;
+heads(x) then records a torch.autograd.Function whose backward is pp_head_backward (csrc/train.hip).  train(scope="neck") adds the
+three upsampler weights rpn.deconv{1,2,3}.0.weight: the training forward then runs the backbone through pp_backbone_taps and records
+a second Function whose backward is pp_neck_backward (csrc/neck_train.hip).  Everything in front of the upsamplers (PFN, scatter, the
+three Resnet blocks) is FROZEN: it has no backward pass."""
 import time
 
 import numpy as np
@@ -14,6 +16,7 @@ from .init import init_state_dict
 
 HEAD_KEYS = ("heads.conv_cls.weight", "heads.conv_cls.bias", "heads.conv_box.weight", "heads.conv_box.bias",
              "heads.conv_dir.weight", "heads.conv_dir.bias")
+NECK_KEYS = ("rpn.deconv1.0.weight", "rpn.deconv2.0.weight", "rpn.deconv3.0.weight")
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -36,6 +39,29 @@ class _HeadFunction(torch.autograd.Function):
         return (None, dx) + tuple(g[k] if ctx.needs_input_grad[2 + i] else None for i, k in enumerate(HEAD_KEYS))
 
 
+class _NeckFunction(torch.autograd.Function):
+    """RPN.forward on a list of canvases as pp_backbone_taps per frame, stacked; its backward is pp_neck_backward for the three
+    upsampling branches.  The three weights are inputs only so that autograd routes their gradients; the forward reads the engine's
+    packed copy of them (PointPillars uploads it beforehand).  The block outputs get no gradient: nothing in front of them trains."""
+
+    @staticmethod
+    def forward(ctx, eng, canvases, *weights):
+        ctx.eng = eng
+        outs = [eng.backbone_taps(c) for c in canvases]
+        y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
+        ctx.save_for_backward(y, x1, x2, x3, *weights)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, *rest = ctx.saved_tensors
+        taps, weights = rest[:3], rest[3:]
+        gy = gy.contiguous()
+        dws = tuple(ctx.eng.neck_backward(b, taps[b], weights[b], y, gy, need_dx=False)[0] if ctx.needs_input_grad[2 + b] else None
+                    for b in range(3))
+        return (None, None) + dws
+
+
 class PointPillars:
     _norm = "instance"
 
@@ -49,6 +75,10 @@ class PointPillars:
         self._uploaded = None        # their _version numbers at the last upload into the engine
         self.training = False
         self._trained = False        # the head has been stepped since load_state_dict
+        self._scope = "head"         # train(scope=...): "head" or "neck" (the head and the three upsamplers)
+        self._neck = {}              # the three upsampler weights as device Parameters
+        self._neck_uploaded = None
+        self._neck_trained = False
         self.profile_stages = True  # the reference synchronises after every stage (:365-374)
         self.pfn_time, self.rpn_time, self.scatter_time, self.heads_time = 0.0, 0.0, 0.0, 0.0
         # like nn.Module construction, start from random initial weights
@@ -61,23 +91,35 @@ class PointPillars:
     def eval(self):
         return self.train(False)
 
-    def train(self, mode=True):
-        """Head-only training mode: the six head parameters require grad (the backbone stays frozen: it has no backward), and
-        forward() accepts a batch of several frames.  eval() / train(False) restores the inference behaviour."""
+    def train(self, mode=True, scope="head"):
+        """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
+        trains rpn.deconv{1,2,3}.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays frozen: it has no
+        backward.  eval() / train(False) restores the inference behaviour."""
+        if scope not in ("head", "neck"):
+            raise ValueError(f"train: scope must be 'head' or 'neck', got {scope!r}")
+        if mode and scope == "neck" and (self._norm != "instance" or len(self._neck) != 3):
+            raise RuntimeError("train(scope='neck'): the neck backward exists for the InstanceNorm backbone only")
         self.training = bool(mode)
+        self._scope = scope if self.training else "head"
         for p in self._params.values():
             p.requires_grad_(self.training)
+        for p in self._neck.values():
+            p.requires_grad_(self.training and self._scope == "neck")
         return self
 
+    def _trainable(self):
+        return {**self._neck, **self._params} if self._scope == "neck" else self._params
+
     def named_parameters(self):
-        """The trainable tensors: heads.conv_{cls,box,dir}.{weight,bias} on the device.  Everything before the head is frozen."""
-        return iter(self._params.items())
+        """The trainable tensors on the device: heads.conv_{cls,box,dir}.{weight,bias}, behind rpn.deconv{1,2,3}.0.weight under
+        train(scope="neck") (state_dict order).  Everything before them is frozen."""
+        return iter(self._trainable().items())
 
     def parameters(self):
-        return iter(self._params.values())
+        return iter(self._trainable().values())
 
     def zero_grad(self, set_to_none=True):
-        for p in self._params.values():
+        for p in list(self._neck.values()) + list(self._params.values()):
             if set_to_none:
                 p.grad = None
             elif p.grad is not None:
@@ -89,6 +131,16 @@ class PointPillars:
         if ver != self._uploaded:
             self._eng.update_head_weights(self._params)
             self._uploaded = ver
+
+    def _neck_moved(self):
+        return self._neck_uploaded is not None and tuple(p._version for p in self._neck.values()) != self._neck_uploaded
+
+    def _sync_neck(self):
+        """The same for the three upsampler weights, ahead of whatever runs the backbone."""
+        if self._neck_moved():
+            self._neck_trained = True
+            self._eng.update_neck_weights(self._neck)
+            self._neck_uploaded = tuple(p._version for p in self._neck.values())
 
     def half(self):
         """The reference deploys FP16 TensorRT engines (framework/trt_utils.py:30, networks/pointpillars8_trt.py:208-223,295-314).
@@ -105,14 +157,19 @@ class PointPillars:
         self._eng.set_precision(mode)
         if self._trained or self._head_moved():
             self._uploaded = ()  # a change of mode packs the loaded weights again: the trained head is uploaded at the next heads()
+        if self._neck_trained or self._neck_moved():
+            self._neck_uploaded = ()  # and the trained upsamplers at the next backbone pass
         return self
 
     def _head_moved(self):
         return self._uploaded is not None and tuple(p._version for p in self._params.values()) != self._uploaded
 
     def state_dict(self):
-        """The loaded tensors, the head's six with their CURRENT values (after optimizer steps)."""
+        """The loaded tensors, the head's six and the three upsampler weights with their CURRENT values (after optimizer steps)."""
         sd = dict(self._sd)
+        if self._neck_moved() or self._neck_trained:
+            for k, p in self._neck.items():
+                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
         if self._head_moved() or self._trained:
             for k, p in self._params.items():
                 sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
@@ -125,6 +182,11 @@ class PointPillars:
                                               requires_grad=self.training) for k in HEAD_KEYS if k in self._sd}
         self._uploaded = tuple(p._version for p in self._params.values())
         self._trained = False
+        neck = self.training and self._scope == "neck"
+        self._neck = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
+                                            requires_grad=neck) for k in NECK_KEYS if k in self._sd}
+        self._neck_uploaded = tuple(p._version for p in self._neck.values())
+        self._neck_trained = False
         return self
 
     def _sync(self):
@@ -141,6 +203,8 @@ class PointPillars:
         nb = int(frame.max().item()) + 1 if coors.shape[0] else 1
         if not 1 <= nb <= eng.max_batch:
             raise ValueError(f"forward: {nb} frames in the batch, max_batch is {eng.max_batch}")
+        neck = self._neck_grad()
+        self._sync_neck()
         rpn = []
         with torch.no_grad():
             for f in range(nb):
@@ -148,8 +212,9 @@ class PointPillars:
                 c = coors[sel][:, :-1].contiguous()
                 num = eng.num_tensor(c.shape[0])
                 feat = eng.pfn(example["voxels"][sel].contiguous(), c, example["num_points_per_voxel"][sel].contiguous(), num)
-                rpn.append(eng.backbone(eng.scatter(feat, c, num)))
-        return self.heads(torch.cat(rpn))
+                canvas = eng.scatter(feat, c, num)
+                rpn.append(canvas if neck else eng.backbone(canvas))
+        return self.heads(self.rpn_train(torch.cat(rpn)) if neck else torch.cat(rpn))
 
     def forward(self, example):
         eng = self._eng
@@ -164,7 +229,7 @@ class PointPillars:
         pfn_time = self._sync()
         canvas = eng.scatter(feat, coors, num)
         scatter_time = self._sync()
-        rpn = eng.backbone(canvas)
+        rpn = self.rpn_train(canvas) if self._neck_grad() else self.rpn(canvas)
         rpn_time = self._sync()
         p = self.heads(rpn)
         cls, box, dr = p["cls_preds"], p["box_preds"], p["dir_preds"]
@@ -186,7 +251,30 @@ class PointPillars:
         return self._eng.scatter(voxel_features.contiguous(), coords.contiguous(), self._eng.num_tensor(coords.shape[0]))
 
     def rpn(self, x):
+        self._sync_neck()
         return self._eng.backbone(x.contiguous())
+
+    def _neck_grad(self):
+        return self.training and self._scope == "neck" and torch.is_grad_enabled() and any(p.requires_grad for p in self._neck.values())
+
+    def rpn_train(self, x):
+        """RPN.forward on canvases x [B,64,gx,gy], 1 <= B <= max_batch, one backbone pass per frame; same values as rpn() bit for
+        bit.  Differentiable with respect to the three upsampler weights when they require grad (train(scope="neck")); gradients are
+        fp32 and need the fp32 precision mode."""
+        eng = self._eng
+        gx, gy = int(eng.grid_size[0]), int(eng.grid_size[1])
+        if not isinstance(x, torch.Tensor) or x.numel() == 0 or x.numel() % (64 * gx * gy):
+            raise ValueError(f"rpn_train: expected canvases [B,64,{gx},{gy}]")
+        x = x.contiguous().reshape(-1, 64, gx, gy)
+        if not 1 <= x.shape[0] <= eng.max_batch:
+            raise ValueError(f"rpn_train: {x.shape[0]} frames in the batch, max_batch is {eng.max_batch}")
+        self._sync_neck()
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in self._neck.values())):
+            return torch.cat([eng.backbone(c) for c in x])
+        if eng.effective_precision() != "fp32":
+            raise RuntimeError(f"neck training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
+                               "(gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place); call float()")
+        return _NeckFunction.apply(eng, list(x), *[self._neck[k] for k in NECK_KEYS])
 
     def heads(self, x):
         """SharedHead.forward on x [B,320,H,W], 1 <= B <= max_batch.  Differentiable with respect to x and the head parameters when

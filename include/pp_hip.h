@@ -237,6 +237,37 @@ int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* dcls, const
 int pp_update_head_weights(pp_ctx* ctx, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box, const float* w_dir,
                            const float* b_dir, void* stream);
 
+/* ---- neck backward (neck_train.hip): the three upsampling branches of RPN train with the head ----
+ * Each branch is ConvTranspose2d(k = s, no bias) -> InstanceNorm2d(eps 1e-3, no affine) -> ReLU (pointpillars8_shared.py:139-171) on a
+ * block output; branch b (0..2) has Cin = 64 << b, Cup = 64 | 128 | 128, s = 1 << b, reads x f32[Cin][H >> b][W >> b] and fills channels
+ * [0,64) | [64,192) | [192,320) of rpn_out.  fp32, InstanceNorm backbone only.  Deterministic: no atomics, two runs are bit-identical.
+ *
+ * pp_backbone_taps: exactly pp_backbone (same rpn_out, bit for bit), and also copies the three block outputs -- the tensors the
+ * upsamplers consume, raw residual sums -- to caller memory: x1 f32[64][H][W], x2 f32[128][H/2][W/2], x3 f32[256][H/4][W/4].  fp32 mode
+ * only: in the 16-bit modes the level buffers may hold fp16 and this returns PP_E_ARG. */
+int pp_backbone_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, void* stream);
+/* Backward of branch `branch` for nb <= max_batch frames.  Stateless: the result depends on the arguments only, not on the context's
+ * last pass or committed weights.  x f32[nb][Cin][h][w] (the block output), w DEVICE f32[Cin][Cup][s][s] (state_dict layout, 16-byte
+ * aligned), y / dy f32[nb][320][H][W] = the full rpn_out and dL/d(rpn_out), of which the branch's channel slice is read ->
+ * dw f32[Cin][Cup][s][s] summed over the frames, fully written, and dx f32[nb][Cin][h][w] (NULL: skipped).  Per frame and output
+ * channel, N = H W: Z = ConvT(x, w) is recomputed, mean and rstd = 1 / sqrt(biased var + 1e-3) come from fp64 sums over Z,
+ * Gr = dy [y > 0] (the mask is the given y, never a recomputed sign), dZ = rstd (Gr - sum(Gr) / N - xhat sum(Gr xhat) / N),
+ * dw[ci][co][ky][kx] = sum_{frames, q} x[ci, q] dZ[co, s q + (ky, kx)], dx[ci, q] = sum_{co, ky, kx} w[ci][co][ky][kx] dZ[co, s q + (ky, kx)].
+ * The three products are fp32-input MFMA GEMMs; dZ is materialised once in a workspace (allocated on first use, at most 256 MB: larger
+ * batches run in frame chunks).  dw is tiled over workgroups and its K range (frames x pixels) split into a fixed number of ranges
+ * whose partials are summed in index order, so dw depends on nb within fp32 summation error; a frame's dx does not depend on nb at all.
+ * PP_E_ARG for a null pointer, branch outside 0..2, nb outside 1..max_batch, a misaligned w and the BatchNorm backbone. */
+int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const float* w, const float* y, const float* dy, int nb, float* dw, float* dx,
+                     void* stream);
+/* After an optimizer step: three DEVICE tensors in state_dict layout (rpn.deconv{1,2,3}.0.weight: [64][64][1][1], [128][128][2][2],
+ * [256][128][4][4]) -> the packed weight images of the three upsamplers of the committed launch plan, rewritten in place on `stream` (no
+ * host copy, no re-tuning).  pp_backbone, pp_backbone_taps, pp_infer_frame and pp_infer_batch read those images, so all see the new
+ * weights.  The first call after a commit reads the images' layout back once (synchronous).  The host copies of pp_load_weights are
+ * NOT changed: a later pp_commit_weights packs those again.  The call touches neither the concat buffer nor the head image, so a
+ * deferred head pass that is still pending keeps its inputs and needs nothing here.  fp32 mode only: PP_E_ARG when
+ * pp_effective_precision != 0, and before the first commit. */
+int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const float* w3, void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);
