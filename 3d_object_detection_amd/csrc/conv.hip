@@ -2221,6 +2221,7 @@ struct NormRef { // where a consumer finds the producer's normalisation
     int C = 0;
     double inv_n = 0.0;
     size_t fs = 0; // doubles between frames of `acc`
+    size_t aff_fs = 0; // floats between frames of `scale` / `shift` (0: shared by all frames)
 };
 
 struct pp_net {
@@ -2242,6 +2243,7 @@ struct pp_net {
     bool defer_ok = false; // the committed plan can run the deferred head: fp32 mode, 9-anchor head on a gemm1x1 tiling
     Variant cls_var;       // tiling of the cls-only head pass (chosen at pp_commit_weights when defer_ok)
     const float* tap[3] = {}; // block outputs of the last pp_run_backbone pass (what the three upsamplers read): pp_backbone_taps
+    double* dbg_stats = nullptr; // statistics accumulators of pp_debug_layer (allocated on its first call that asks for statistics)
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };
 
@@ -2662,7 +2664,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
     p.Cin = L.cin; p.Hin = Hin; p.Win = Win;
     p.Cout = L.rows; p.Hout = Hout; p.Wout = Wout;
     p.pre = pre.mode; p.pre_acc = pre.acc; p.pre_scale = pre.scale; p.pre_shift = pre.shift;
-    p.pre_inv_n = pre.inv_n; p.eps = 1e-3f;
+    p.pre_inv_n = pre.inv_n; p.eps = 1e-3f; p.aff_fs = pre.aff_fs;
     p.stat_acc = stat_acc; p.stat_C = stat_C;
     p.bias = (L.kind == 2 && L.var.family == Family::Gemm1x1) ? net->head_bias_perm : net->head_bias; p.out_box = out_box; p.out_dir = out_dir;
     { const int na = ctx->cfg.num_anchor_per_loc; p.n_cls = na; p.n_box = 7 * na; p.n_rows = 10 * na; }
@@ -2712,6 +2714,8 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         // Whole main tiles first; what they leave uncovered goes to strip launches of thin tiles when that needs fewer tiles
         // than rounding the main grid up (same weight image: it depends on the 64-row block and the chunk only).
         if ((size_t)L.rows * Hout * Wout * 4 >= 0x80000000ull) return PP_E_ARG; // the epilogue parks idle lanes' offsets 2 GB out (W4_FAR)
+        // these two kernels always normalise (every stride-1 convolution of the network follows a norm): with PRE_RAW they would read a null table
+        if (p.pre == PRE_RAW) return pp_fail(ctx, PP_E_ARG, "wino4 / wino6 tilings have no raw prologue: give the layer a (scale, shift)");
         const bool tag4 = ctx->prof_on && L.kind == 0 && L.level == 0 && L.stride == 1;
         if (tag4) {
             if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
@@ -3114,7 +3118,7 @@ void pp_net_destroy(pp_ctx* ctx)
             if (net->buf[l][b]) (void)hipFree(net->buf[l][b] - W6_FRONT_PAD);
     for (Layer& L : net->layers)
         if (L.w) (void)hipFree(L.w);
-    void* ptrs[] = {net->up, net->stats, net->aff, net->bn_scale, net->bn_shift, net->head_bias, net->head_bias_perm, net->ones, net->zeros};
+    void* ptrs[] = {net->dbg_stats, net->up, net->stats, net->aff, net->bn_scale, net->bn_shift, net->head_bias, net->head_bias_perm, net->ones, net->zeros};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     delete net;
@@ -3616,6 +3620,69 @@ extern "C" int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst
     default: return pp_fail(ctx, PP_E_ARG, "pp_fetch_frame_tensor: unknown kind");
     }
     PP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+    return 0;
+}
+
+namespace {
+// out[f][c][k] = sum over the NREP replicated accumulators (k = 0 sum, 1 sum of squares)
+__global__ void __launch_bounds__(256) dbg_reduce_stats(const double* __restrict__ acc, size_t acc_fs, int C, double* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * C) return;
+    const double* a = acc + (size_t)blockIdx.y * acc_fs;
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < NREP; ++r) s += a[(size_t)r * C * 2 + i];
+    out[(size_t)blockIdx.y * 2 * C + i] = s;
+}
+} // namespace
+
+// Test hook: ONE layer of the committed plan (kernel, tiling and weight image as pp_layer_tilings reports them) through launch_conv on
+// caller tensors -- see include/pp_hip.h.  Reads the plan and the weight images, writes only caller memory and its own statistics
+// scratch: nothing a later pass reads changes.
+extern "C" int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,
+                              const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->net || !ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_debug_layer: weights not committed");
+    pp_net* net = (pp_net*)ctx->net;
+    if (layer < 0 || layer >= (int)net->layers.size()) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: layer index out of range");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: nb must be 1 .. cfg.max_batch");
+    const Layer& L = net->layers[layer];
+    const bool sparse = pmap || feat;
+    if (sparse && layer != 0) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the sparse input form belongs to layer 0");
+    if (sparse && (!pmap || !feat || in)) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: layer 0 takes either `in` or pmap + feat");
+    if (!sparse && !in) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: null input");
+    if (!out) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: null output");
+    if (res && L.kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: only a convolution takes a residual");
+    if (pre_mode < 0 || pre_mode > 2) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: pre_mode must be 0 (raw), 1 (shared affine) or 2 (per-frame affine)");
+    if ((pre_mode != 0) != (scale != nullptr) || (pre_mode != 0) != (shift != nullptr))
+        return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: scale and shift go with pre_mode 1 / 2 and with nothing else");
+    if (L.kind == 2 && (!out_box || !out_dir)) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the head needs out_box and out_dir");
+    if (L.kind != 2 && (out_box || out_dir)) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: out_box / out_dir belong to the head");
+    if (L.kind == 2 && stats) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the head accumulates no statistics");
+    if (pre_mode == 0 && (L.var.family == Family::Wino4 || L.var.family == Family::Wino6))
+        return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the committed tiling (wino4 / wino6) has no raw prologue, give it a (scale, shift)");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int h = ctx->H >> L.level, w = ctx->W >> L.level;
+    const bool s2 = L.kind == 0 && L.stride == 2;
+    const int hin = s2 ? 2 * h : h, win = s2 ? 2 * w : w;
+    NormRef pre;
+    if (pre_mode) { pre.mode = PRE_AFFINE; pre.scale = const_cast<float*>(scale); pre.shift = const_cast<float*>(shift); pre.C = L.cin; pre.aff_fs = pre_mode == 2 ? (size_t)L.cin : 0; }
+    double* st = nullptr;
+    if (stats) {
+        if (!net->dbg_stats) PP_HIP(hipMalloc((void**)&net->dbg_stats, (size_t)ctx->max_batch * STAT_FS * sizeof(double)));
+        st = net->dbg_stats;
+        PP_HIP(hipMemsetAsync(st, 0, (size_t)nb * STAT_FS * sizeof(double), stream));
+    }
+    const int rc = launch_conv(ctx, L, (const float*)in, hin, win, (float*)out, (const float*)res, pre, st, L.cout, h, w, stream, out_box, out_dir, nb, 0, 0,
+                               pmap, feat);
+    if (rc == PP_E_ARG) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the committed tiling does not take this layer's shape");
+    if (rc) return rc;
+    if (stats) {
+        hipLaunchKernelGGL(dbg_reduce_stats, dim3(pp_div_up(2 * L.cout, 256), nb), dim3(256), 0, stream, st, STAT_FS, L.cout, stats);
+        PP_HIP(hipGetLastError());
+    }
     return 0;
 }
 

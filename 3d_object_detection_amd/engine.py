@@ -7,6 +7,7 @@ also builds in __init__ (voxel_generator.py:6-26, anchor_assigner.py:221-298).
 """
 import ctypes
 import os
+import re
 import weakref
 
 import numpy as np
@@ -531,6 +532,84 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_fetch_frame_tensor(self.ctx, int(frame), kind, _ptr(out), _stream()), self.ctx, "pp_fetch_frame_tensor")
         return out
+
+    def debug_layer(self, layer, x=None, res=None, scale=None, shift=None, pmap=None, feat=None, stats=False):
+        """Test hook (pp_debug_layer): ONE layer of the committed plan -- index 0 .. 19 of layer_tilings(), with the kernel, tiling and
+        weight image reported there -- on caller tensors.  x [nb,cin,hin,win] (or, layer 0 only, pmap i32[nb,gx,gy] + feat
+        f32[nb,max_voxels,64]); res [nb,cout,h,w] for a conv; scale / shift f32[cin] (shared) or f32[nb,cin] (per frame) select the
+        relu(x * scale + shift) prologue, None reads x raw.  x and res must have the element type of the committed tiling
+        (layer_io_dtypes).  Returns the output tensor -- conv [nb,cout,h,w], upsampler [nb,cout,h*up,w*up], head (cls [nb,A,1],
+        box [nb,A,7], dir [nb,A,2]) -- and, with stats=True, also f64[nb,cout,2] = per-channel (sum, sum of squares)."""
+        til = self.layer_tilings()
+        if not self.weights_loaded or not til:
+            raise RuntimeError("debug_layer: load_state_dict first")
+        if not isinstance(layer, int) or not 0 <= layer < len(til):
+            raise ValueError(f"debug_layer: layer must be 0 .. {len(til) - 1}")
+        t = til[layer]
+        in_dt, out_dt = self.layer_io_dtypes(layer)
+        kind, cin, cout, up = t["kind"], t["cin"], t["cout"], t["up"]
+        h, w = self.H >> t["level"], self.W >> t["level"]
+        s = 2 if kind == 0 and t["stride"] == 2 else 1
+        hin, win = h * s, w * s
+        sparse = pmap is not None or feat is not None
+        if sparse:
+            if layer != 0 or x is not None or pmap is None or feat is None:
+                raise ValueError("debug_layer: the sparse form is pmap + feat, without x, on layer 0")
+            nb = int(pmap.shape[0]) if isinstance(pmap, torch.Tensor) and pmap.dim() == 3 else 0
+        else:
+            nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"debug_layer: the input must hold 1 .. max_batch ({self.max_batch}) frames")
+        if sparse:
+            pmap = _chk(pmap, torch.int32, (nb, hin, win), "debug_layer: pmap")
+            feat = _chk(feat, torch.float32, (nb, self.max_voxels, 64), "debug_layer: feat")
+            xin = None
+        else:
+            x = _chk(x, in_dt, (nb, cin, hin, win), "debug_layer: x")
+            # the Winograd tilings fetch aligned pieces that start in front of a row and end behind it: stage the input with the
+            # padding the context's own buffers have
+            front, per = 128, cin * hin * win
+            stage = torch.zeros(front + nb * per + nb * cin * (hin + win + 1) + 64, dtype=in_dt, device=self.device)
+            xin = stage[front:front + nb * per]
+            xin.copy_(x.reshape(-1))
+        if res is not None:
+            if kind != 0:
+                raise ValueError("debug_layer: only a convolution takes a residual")
+            res = _chk(res, out_dt, (nb, cout, h, w), "debug_layer: res")
+        if (scale is None) != (shift is None):
+            raise ValueError("debug_layer: scale and shift come together")
+        pre_mode = 0
+        if scale is not None:
+            pre_mode = 2 if isinstance(scale, torch.Tensor) and scale.dim() == 2 else 1
+            shp = (nb, cin) if pre_mode == 2 else (cin,)
+            scale = _chk(scale, torch.float32, shp, "debug_layer: scale")
+            shift = _chk(shift, torch.float32, shp, "debug_layer: shift")
+        for tns, what in ((x, "x"), (res, "res"), (scale, "scale"), (shift, "shift"), (pmap, "pmap"), (feat, "feat")):
+            if tns is not None and tns.device != self.device:
+                raise ValueError(f"debug_layer: {what} is on {tns.device}, the engine on {self.device}")
+        if kind == 2:
+            if stats:
+                raise ValueError("debug_layer: the head accumulates no statistics")
+            out = self._t((nb, self.A, 1), torch.float32)
+            box = self._t((nb, self.A, 7), torch.float32)
+            dr = self._t((nb, self.A, 2), torch.float32)
+        else:
+            out = self._t((nb, cout, h * up, w * up), out_dt)
+            box = dr = None
+        st = self._t((nb, cout, 2), torch.float64) if stats else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_debug_layer(self.ctx, layer, nb, _ptr(xin), _ptr(res), pre_mode, _ptr(scale), _ptr(shift), _ptr(pmap), _ptr(feat),
+                                               _ptr(out), _ptr(box), _ptr(dr), _ptr(st), _stream()), self.ctx, "pp_debug_layer")
+        ret = (out, box, dr) if kind == 2 else out
+        return (ret, st) if stats else ret
+
+    def layer_io_dtypes(self, layer):
+        """(input dtype, output / residual dtype) of layer `layer` of the committed plan: the `h<n>` tag of its tiling name (bit 0 of n:
+        fp16 input, bit 1: fp16 output); the head's outputs are fp32 whatever the tag says."""
+        t = self.layer_tilings()[layer]
+        m = re.search(r"(?:^| )h([123])(?: |$)", t["tiling"])
+        io16 = int(m.group(1)) if m else 0
+        return (torch.float16 if io16 & 1 else torch.float32, torch.float16 if (io16 & 2) and t["kind"] != 2 else torch.float32)
 
     # ------------------------------------------------------------------ training targets / loss (assign.hip)
     def _gt_args(self, gt_boxes, gt_classes, gt_offsets, nb, what):

@@ -152,6 +152,30 @@ int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int32_t* n_h, i
  * ran the dense first convolution. */
 int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream);
 
+/* Single-layer hook for the layer tests: runs ONE layer of the committed launch plan -- the kernel, tiling and packed weight image
+ * pp_layer_tilings reports for it, whatever PP_FORCE_VARIANT and pp_set_precision selected -- on caller tensors, nb frames
+ * (1 <= nb <= cfg.max_batch) in one launch.  layer: 0 .. 19 in plan order (16 convs, 3 upsamplers, the head).  Map sizes are the
+ * context's own for the layer's level (h, w = H >> level, W >> level; a stride-2 conv reads 2h x 2w); H, W multiples of 4.
+ *   in    [nb][cin][hin][win]; res (NULL or, for a conv, [nb][cout][h][w]) is added before the store and the statistics;
+ *   out   conv [nb][cout][h][w] | upsampler [nb][cout][h up][w up], dense (not a slice of the 320-channel buffer) |
+ *         head: cls f32[nb][A], with out_box f32[nb][A][7] and out_dir f32[nb][A][2] as pp_head returns them (NULL for other layers);
+ *   element types follow the committed tiling's `h<n>` tag in pp_layer_tilings: bit 0 of n = `in` is fp16, bit 1 = `out` and `res`
+ *         are fp16; fp32 without the tag.  The head's outputs are always fp32.
+ *   pre_mode 0: the kernel reads `in` as it is (scale = shift = NULL); 1: relu(in * scale[c] + shift[c]) with scale / shift f32[cin]
+ *         shared by the frames (folded BatchNorm); 2: scale / shift f32[nb][cin], one row per frame (finalised InstanceNorm).
+ *         The wino4 / wino6 tilings of the stride-1 convolutions always normalise (in the network such a layer always follows a norm):
+ *         pre_mode 0 on a layer that runs one of them is PP_E_ARG.
+ *   layer 0 alternatively takes the sparse form of the fused path: in = NULL, pmap i32[nb][gx gy] (pillar index per BEV cell, -1 =
+ *         empty) and feat f32[nb][max_voxels][64] (PFN rows), which runs the tiling's sparse twin.
+ *   stats (NULL or f64[nb][cout][2]): per frame and output channel the sum and the sum of squares the epilogue accumulates for the
+ *         consumer's InstanceNorm (of the fp32 values, before a 16-bit store), summed over the replicated accumulators; not the head.
+ * `in` must be readable 256 bytes in front of its first and (hin + win + 1) * 4 * cin * nb bytes behind its last element (the
+ * Winograd tilings fetch whole aligned pieces; the context's own buffers are padded the same way).  Every argument is checked
+ * before anything is launched (PP_E_ARG; PP_E_STATE before pp_commit_weights).  The call changes nothing a later pass reads; the
+ * first call that asks for statistics allocates their scratch accumulators (synchronous), later calls only enqueue. */
+int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,
+                   const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats, void* stream);
+
 /* Deferred head (default on).  Post-processing reads the box / dir logits of at most nms_pre_max anchors per class, so a pass of
  * pp_infer_batch / pp_infer_frame computes the cls rows of the head for every pixel and the box / dir logits for the selected
  * candidates only (bit-identical to the full head: same MFMA arithmetic on the same weight image).  The context's full box / dir
