@@ -63,9 +63,12 @@ PROTOTYPES = {
     "pp_infer_batch": (ctypes.c_int, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, ctypes.c_int, c_p]),
     "pp_fetch_frame_tensor": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p]),
     "pp_debug_layer": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_debug_layer_skip": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p]),
     "pp_set_head_defer": (ctypes.c_int, [c_p, ctypes.c_int]),
     "pp_head_defer_active": (ctypes.c_int, [c_p]),
     "pp_set_sparse_conv1": (ctypes.c_int, [c_p, ctypes.c_int]),
+    "pp_set_tile_skip": (ctypes.c_int, [c_p, ctypes.c_int]),
+    "pp_tile_skip_active": (ctypes.c_int, [c_p]),
     "pp_set_assign_thresholds": (ctypes.c_int, [c_p, c_p, c_p]),
     "pp_assign_targets": (ctypes.c_int, [c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_target_loss": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p]),

@@ -2655,7 +2655,7 @@ constexpr size_t STAT_FS = (size_t)24 * NREP * 320 * 2; // doubles of statistics
 int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, float* out, const float* res,
                 const NormRef& pre, double* stat_acc, int stat_C, int Hout, int Wout, hipStream_t stream,
                 float* out_box = nullptr, float* out_dir = nullptr, int B = 1, size_t out_fs = 0, size_t in_fs = 0,
-                const int32_t* pmap = nullptr, const float* feat = nullptr)
+                const int32_t* pmap = nullptr, const float* feat = nullptr, int ts_k = 0)
 {
     pp_net* net = (pp_net*)ctx->net;
     ConvP p;
@@ -2717,7 +2717,19 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         // these two kernels always normalise (every stride-1 convolution of the network follows a norm): with PRE_RAW they would read a null table
         if (p.pre == PRE_RAW) return pp_fail(ctx, PP_E_ARG, "wino4 / wino6 tilings have no raw prologue: give the layer a (scale, shift)");
         const bool tag4 = ctx->prof_on && L.kind == 0 && L.level == 0 && L.stride == 1;
+        const int ncb = pp_div_up(L.rows, v.bm);
+        // Tile skipping (tile_skip.hip): ts_k = the layer's ordinal among level 0's stride-1 layers, handed over by a pass whose first conv
+        // ran sparse (or by the single-layer hook).  Listed launch + fill only for the fp32 wino6 main tile on a map of whole main tiles
+        // (no strip launches) with lists for exactly these B frames in place; today's launch in every other case.
+        const int2* ts_items = nullptr;
+        const int32_t* ts_count = nullptr;
+        const bool listed = ts_k > 0 && v.family == Family::Wino6 && v.kern2 && v.pw == 16 && v.ph == 16 && net->eff_prec == 0 && !net->up16 &&
+                            L.kind == 0 && L.level == 0 && L.stride == 1 && Wout % v.pw == 0 && Hout % v.ph == 0 && Hout == ctx->H && Wout == ctx->W &&
+                            pp_ts_list(ctx, ts_k, B, &ts_items, &ts_count);
         if (tag4) {
+            const double dense = (double)(Wout / v.pw) * (Hout / v.ph) * ncb * B;
+            ctx->prof_items_dense += dense;
+            if (listed) ctx->prof_ts_layer.push_back(ts_k | (ncb << 8)); else ctx->prof_items += dense;
             if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
                 hipEvent_t a, b;
                 PP_HIP(hipEventCreate(&a));
@@ -2728,7 +2740,6 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
             ctx->prof_flops = 2.0 * Hout * Wout * (double)L.cin * L.cout * 9.0 * B;
             PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used], stream));
         }
-        const int ncb = pp_div_up(L.rows, v.bm);
         auto launch_region = [&](const Variant& rv, int x0, int y0, int x1, int y1) {
             ConvP q = p;
             q.rx0 = x0; q.ry0 = y0; q.rx1 = x1; q.ry1 = y1;
@@ -2737,7 +2748,8 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
             int g = net->num_cu;
             if (g > total) g = total;
             g = (g + 7) & ~7;
-            hipLaunchKernelGGL(rv.kern, dim3(g), dim3(rv.threads), rv.lds, stream, q);
+            if (listed) { q.items = ts_items; q.item_count = ts_count; } // same grid as the dense total: the kernel reads its own
+            hipLaunchKernelGGL(listed ? rv.kern2 : rv.kern, dim3(g), dim3(rv.threads), rv.lds, stream, q);
         };
         const int mw = (Wout / v.pw) * v.pw, mh = (Hout / v.ph) * v.ph;
         const Variant &sv = strip_v(v.family), &sh = strip_h(v.family);
@@ -2763,6 +2775,8 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
             if (Hout > mh) launch_region(sh, 0, mh, mw, Hout);
         } else {
             launch_region(v, 0, 0, Wout, Hout);
+            if (listed)
+                if (int rc = pp_ts_fill(ctx, ts_k, B, out, p.out_fs, L.rows, stream)) return rc;
         }
         if (tag4) {
             PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used + 1], stream));
@@ -3309,6 +3323,18 @@ int launch_norm_relu(pp_ctx* ctx, const float* x, float* y, int C, int HW, const
 
 } // namespace
 
+// do all stride-1 layers of level 0 (at most three: tile_skip.hip's rule) run the fp32 wino6 main tile on a map of whole main tiles?
+static bool level0_main_wino6(const pp_net* net, int h, int w)
+{
+    int n = 0;
+    for (const Layer& L : net->layers)
+        if (L.kind == 0 && L.level == 0 && L.stride == 1) {
+            ++n;
+            if (L.var.family != Family::Wino6 || !L.var.kern2 || L.var.pw != 16 || L.var.ph != 16 || (w % 16) || (h % 16)) return false;
+        }
+    return n >= 1 && n <= 3 && net->eff_prec == 0;
+}
+
 // canvas [64,gx,gy] -> up [320,H,W] PRE-norm (+ statistics); the head (or pp_backbone's final pass)
 // applies the last norm + ReLU.
 int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream, const int32_t* pmap, const float* feat)
@@ -3318,6 +3344,7 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
     if ((H % 4) || (W % 4)) return pp_fail(ctx, PP_E_ARG, "backbone: BEV grid must be a multiple of 8 in x and y");
     if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "backbone: batch exceeds cfg.max_batch");
     ctx->sc1_last_nb = 0;
+    pp_ts_begin_pass(ctx);
     if (ctx->cfg.norm_kind == 0) PP_HIP(hipMemsetAsync(net->stats, 0, STAT_FS * sizeof(double) * nb, stream));
     NormRef raw;
     const float* x = canvas;
@@ -3335,6 +3362,11 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
         if (b == 0 && pmap && net->eff_prec == 0 && pp_sc1_usable(ctx)) {
             ++li;
             if ((rc = pp_sc1_run(ctx, pmap, feat, Bf[0], stat_slot(ctx, site_block(0, 0)), STAT_FS, nb, stream))) return rc;
+            // the map is exactly zero outside the active set now: lists of the tiles level 0's stride-1 layers need not recompute
+            if (ctx->sc1_last_nb == nb && !net->up16 && pp_ts_usable(ctx, 3) && level0_main_wino6(net, h, w)) {
+                if ((rc = pp_ts_build(ctx, nb, nullptr, stream))) return rc;
+                pp_ts_mark_pass(ctx, nb);
+            }
         } else if ((rc = launch_conv(ctx, net->layers[li++], x, Hin, Win, Bf[0], nullptr, raw, stat_slot(ctx, site_block(b, 0)), c, h, w, stream,
                               nullptr, nullptr, nb, 0, 0, b == 0 ? pmap : nullptr, b == 0 ? feat : nullptr))) return rc;
         // y = relu(norm(Bf[0])) -> Bf[1] + stats(site 1) (the first Resnet2 unit's leading norm)
@@ -3345,6 +3377,7 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
         float* cur = Bf[1];
         float* spare[3] = {Bf[0], Bf[2], Bf[3]};
         const int nunits = (b == 0) ? 2 : 3;
+        int ts_k = 0; // level 0: ordinal of the next stride-1 layer (launch_conv ignores it unless this pass built tile lists)
         for (int u = 0; u < nunits; ++u) {
             const int nl = (u == nunits - 1) ? 0 : 1;
             const bool last = (u == nunits - 1);
@@ -3354,14 +3387,15 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
             double* out_stat = last ? nullptr : stat_slot(ctx, site_block(b, 1 + 2 * (u + 1)));
             if (nl == 1) {
                 if ((rc = launch_conv(ctx, net->layers[li++], cur, h, w, t1, nullptr, norm_ref(ctx, site_block(b, 1 + 2 * u), c, 0, cnt),
-                                      stat_slot(ctx, site_block(b, 2 + 2 * u)), c, h, w, stream, nullptr, nullptr, nb))) return rc;
+                                      stat_slot(ctx, site_block(b, 2 + 2 * u)), c, h, w, stream, nullptr, nullptr, nb, 0, 0, nullptr, nullptr,
+                                      b == 0 ? ++ts_k : 0))) return rc;
                 if ((rc = launch_conv(ctx, net->layers[li++], t1, h, w, t2, cur, norm_ref(ctx, site_block(b, 2 + 2 * u), c, 0, cnt),
-                                      out_stat, c, h, w, stream, nullptr, nullptr, nb))) return rc;
+                                      out_stat, c, h, w, stream, nullptr, nullptr, nb, 0, 0, nullptr, nullptr, b == 0 ? ++ts_k : 0))) return rc;
                 spare[1] = cur; // t2 becomes current; old current and t1 are free
                 cur = t2;
             } else {
                 if ((rc = launch_conv(ctx, net->layers[li++], cur, h, w, t1, cur, norm_ref(ctx, site_block(b, 1 + 2 * u), c, 0, cnt),
-                                      out_stat, c, h, w, stream, nullptr, nullptr, nb))) return rc;
+                                      out_stat, c, h, w, stream, nullptr, nullptr, nb, 0, 0, nullptr, nullptr, b == 0 ? ++ts_k : 0))) return rc;
                 spare[0] = cur;
                 cur = t1;
             }
@@ -3589,7 +3623,8 @@ extern "C" int pp_backbone_taps(pp_ctx* ctx, const float* canvas, float* rpn_out
 // 3 anchor mask u8[A], 4 rpn output f32[320,H,W] = relu(norm(concat)) as RPN.forward returns it
 // (pointpillars8_shared.py:173-181; materialised here, the fused path never stores it), 5 PFN rows f32[max_voxels,64],
 // 6 coors i32[max_voxels,3], 7 pillar count i32[1], 8 active list of the sparse first conv i32[1 + min(4 max_voxels, H W)]
-// (count, then the active output pixels in ascending order; PP_E_STATE when the pass ran the dense first conv).
+// (count, then the active output pixels in ascending order; PP_E_STATE when the pass ran the dense first conv), 9 tile flags of the
+// tile-skipping path u8[3][(H / 16) (W / 16)] (1 = skippable at layer 1, 2, 3; PP_E_STATE when the pass built none).
 extern "C" int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream_)
 {
     if (!ctx || !dst) return pp_fail(ctx, PP_E_ARG, "pp_fetch_frame_tensor: null pointer");
@@ -3617,6 +3652,7 @@ extern "C" int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst
     case 6: src = ctx->f_coors + frame * mv * 3; bytes = mv * 12; break;
     case 7: src = ctx->f_num + frame * 4; bytes = 4; break;
     case 8: return pp_sc1_fetch_list(ctx, frame, dst, stream);
+    case 9: return pp_ts_fetch_flags(ctx, frame, dst, stream);
     default: return pp_fail(ctx, PP_E_ARG, "pp_fetch_frame_tensor: unknown kind");
     }
     PP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
@@ -3643,6 +3679,15 @@ __global__ void __launch_bounds__(256) dbg_reduce_stats(const double* __restrict
 extern "C" int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,
                               const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats, void* stream_)
 {
+    return pp_debug_layer_skip(ctx, layer, nb, in, res, pre_mode, scale, shift, pmap, feat, out, out_box, out_dir, stats, nullptr, 0, stream_);
+}
+
+// pp_debug_layer with the tile-skipping form: active u8[nb][H][W] (the pixels the sparse first conv would have computed) and the layer's
+// ordinal skip_k (1..3) build the lists with the pass's own builder; the layer then runs as the listed launch plus the fill.
+extern "C" int pp_debug_layer_skip(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,
+                                   const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats,
+                                   const uint8_t* active, int skip_k, void* stream_)
+{
     if (!ctx) return PP_E_ARG;
     if (!ctx->net || !ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_debug_layer: weights not committed");
     pp_net* net = (pp_net*)ctx->net;
@@ -3663,6 +3708,9 @@ extern "C" int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, co
     if (L.kind == 2 && stats) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the head accumulates no statistics");
     if (pre_mode == 0 && (L.var.family == Family::Wino4 || L.var.family == Family::Wino6))
         return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the committed tiling (wino4 / wino6) has no raw prologue, give it a (scale, shift)");
+    if ((active != nullptr) != (skip_k != 0)) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer_skip: the activity bitmap and the layer ordinal come together");
+    if (active && (skip_k < 1 || skip_k > 3 || L.kind != 0 || L.level != 0 || L.stride != 1 || !pp_ts_usable(ctx, 3) || !level0_main_wino6(net, ctx->H, ctx->W)))
+        return pp_fail(ctx, PP_E_ARG, "pp_debug_layer_skip: tile skipping serves the stride-1 layers of level 0 (ordinal 1..3) on the fp32 wino6 main tile, whole tiles, switch on");
     hipStream_t stream = (hipStream_t)stream_;
     const int h = ctx->H >> L.level, w = ctx->W >> L.level;
     const bool s2 = L.kind == 0 && L.stride == 2;
@@ -3675,8 +3723,12 @@ extern "C" int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, co
         st = net->dbg_stats;
         PP_HIP(hipMemsetAsync(st, 0, (size_t)nb * STAT_FS * sizeof(double), stream));
     }
+    pp_ts_begin_hook(ctx, active != nullptr);
+    if (active)
+        if (int rc0 = pp_ts_build_from_bitmap(ctx, nb, active, stream)) return rc0;
     const int rc = launch_conv(ctx, L, (const float*)in, hin, win, (float*)out, (const float*)res, pre, st, L.cout, h, w, stream, out_box, out_dir, nb, 0, 0,
-                               pmap, feat);
+                               pmap, feat, active ? skip_k : 0);
+    if (active) pp_ts_end_hook(ctx);
     if (rc == PP_E_ARG) return pp_fail(ctx, PP_E_ARG, "pp_debug_layer: the committed tiling does not take this layer's shape");
     if (rc) return rc;
     if (stats) {
@@ -3691,6 +3743,8 @@ extern "C" int pp_profile_begin(pp_ctx* ctx)
     if (!ctx) return PP_E_ARG;
     ctx->prof_on = true;
     ctx->prof_used = 0;
+    ctx->prof_ts_layer.clear();
+    ctx->prof_items = ctx->prof_items_dense = 0.0;
     return 0;
 }
 
@@ -3706,6 +3760,14 @@ extern "C" int pp_profile_end(pp_ctx* ctx, double* avg_ms, int32_t* launches, do
         PP_HIP(hipEventElapsedTime(&ms, ctx->prof_ev[2 * i], ctx->prof_ev[2 * i + 1]));
         tot += ms;
     }
+    // items the listed launches really ran (their counts live on the device; the loop above has synchronised).  Every pass rebuilds the
+    // lists, so the counts are those of the last profiled pass: exact when the profiled passes see the same frames.
+    for (int e : ctx->prof_ts_layer) {
+        int32_t cnt = 0;
+        if (int rc = pp_ts_read_count(ctx, e & 0xFF, &cnt)) return rc;
+        ctx->prof_items += (double)cnt * (e >> 8);
+    }
+    ctx->prof_ts_layer.clear();
     *avg_ms = n ? tot / (double)n : 0.0;
     *launches = (int32_t)n;
     *flops = ctx->prof_flops;
@@ -3737,8 +3799,8 @@ extern "C" double pp_dominant_executed_ratio(pp_ctx* ctx)
     if (!ctx || !ctx->net) return 1.0;
     pp_net* net = (pp_net*)ctx->net;
     for (const Layer& L : net->layers)
-        if (L.kind == 0 && L.level == 0 && L.stride == 1)
-            return executed_ratio(L.var);
+        if (L.kind == 0 && L.level == 0 && L.stride == 1) // x the share of the dense work items the profiled launches ran (tile skipping)
+            return executed_ratio(L.var) * (ctx->prof_items_dense > 0.0 ? ctx->prof_items / ctx->prof_items_dense : 1.0);
     return 1.0;
 }
 

@@ -99,6 +99,10 @@ struct ConvP {
     // wino4_mfma: the rectangle of output pixels this launch tiles (a layer whose map is not a multiple of the tile is
     // covered by a main launch of whole tiles plus strip launches of thin tiles): origin, exclusive end, tiles in x / y
     int rx0, ry0, rx1, ry1, rnbx, rnby;
+    // wino6_mfma's list twin (tile skipping, tile_skip.hip): work item l / ncb is entry {frame * ntile + tile, mult} of `items` instead of
+    // (frame, tile) = l / ncb itself, the item count comes from the device, and the tile's statistics are added `mult` times
+    const int2* items;
+    const int32_t* item_count;
 };
 
 // Kernel family of a tiling.  The numbers are part of pp_layer_tilings' text ("wino=<n>").
@@ -113,7 +117,7 @@ enum class Family : int {
 
 struct Variant { // one compiled tiling
     void (*kern)(const ConvP);
-    void (*kern2)(const ConvP) = nullptr; // conv16, stride 2: twin for the sparse BEV input of the first conv (ConvP::pmap)
+    void (*kern2)(const ConvP) = nullptr; // conv16, stride 2: twin for the sparse BEV input of the first conv (ConvP::pmap); wino6 main tile: the list twin (ConvP::items)
     int bm, bmp, pw, ph, kc, threads, waves, pairs; // pairs = MT*NT tile pairs per wave
     size_t lds;
     char name[48];

@@ -121,6 +121,8 @@ static int create_impl(pp_ctx* ctx)
     if (rc) return rc;
     rc = pp_sc1_create(ctx);
     if (rc) return rc;
+    rc = pp_ts_create(ctx);
+    if (rc) return rc;
     rc = pp_post_create(ctx);
     return rc;
 }
@@ -153,6 +155,8 @@ extern "C" pp_ctx* pp_create(int device, const pp_config* cfg)
     ctx->head_defer = !ctx->head_defer_env_off;
     if (const char* e = getenv("PP_SPARSE_CONV1")) ctx->sparse_conv1_env_off = e[0] == '0';
     ctx->sparse_conv1 = !ctx->sparse_conv1_env_off;
+    if (const char* e = getenv("PP_TILE_SKIP")) ctx->tile_skip_env_off = e[0] == '0';
+    ctx->tile_skip = !ctx->tile_skip_env_off;
     int rc = create_impl(ctx);
     if (rc) {
         g_create_err = ctx->err;
@@ -202,6 +206,7 @@ extern "C" void pp_destroy(pp_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     pp_net_destroy(ctx);
     pp_sc1_destroy(ctx);
+    pp_ts_destroy(ctx);
     pp_post_destroy(ctx);
     pp_assign_destroy(ctx);
     pp_train_destroy(ctx);

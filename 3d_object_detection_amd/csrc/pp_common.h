@@ -142,6 +142,13 @@ struct pp_ctx {
     void* sc1 = nullptr;             // weight image, active lists and their workspace
     int sc1_kc = 4;                  // channels per chunk of the committed dense first-conv tiling: the sparse kernel walks K in its order
     int sc1_last_nb = 0;             // frames of the last pass whose active lists the context holds (0: that pass ran the dense first conv)
+    // ---- tile skipping (tile_skip.hip; pp_set_tile_skip): behind the sparse first conv, the fp32 wino6 launches of level 0's stride-1
+    //      layers compute one tile per (frame, layer, border class) of those whose input is constant and copy it to the others ----
+    bool tile_skip = true;           // the switch (default on; PP_TILE_SKIP=0 forces it off)
+    bool tile_skip_env_off = false;
+    void* ts = nullptr;              // flags, item and fill lists
+    std::vector<int> prof_ts_layer;  // per profiled launch: the layer ordinal (1..3) of a listed launch, 0 for a dense one
+    double prof_items = 0.0, prof_items_dense = 0.0; // items launched / dense items over the profiled launches (pp_profile_end)
 };
 // stage ids of pp_stage_mark / pp_stage_profile_end
 enum { PP_ST_VOXELIZE = 0, PP_ST_MASK = 1, PP_ST_PFN = 2, PP_ST_CONV = 3, PP_ST_NORM = 4, PP_ST_HEAD = 5, PP_ST_POST = 6 /* filter + threshold + gather */,
@@ -194,6 +201,26 @@ int pp_sc1_commit(pp_ctx* ctx);
 bool pp_sc1_usable(pp_ctx* ctx);
 int pp_sc1_run(pp_ctx* ctx, const int32_t* pmap, const float* feat, float* out, double* stat, size_t stat_fs, int nb, hipStream_t stream);
 int pp_sc1_fetch_list(pp_ctx* ctx, int frame, void* dst, hipStream_t stream);
+const uint64_t* pp_sc1_words(pp_ctx* ctx, int* nblk); // ballot words [max_batch][nblk * 4] of the last pp_sc1_run (complete even when the list is capped)
+// tile skipping (tile_skip.hip): workspace at pp_create (sized for max_batch).  usable = switched on, the map is a whole number of
+// 16 x 16 tiles and level 0 has at most three stride-1 layers.  pp_ts_build: flags, item lists and fill lists of the three layers for
+// nb frames, from the sparse first conv's ballot words of this pass (words == nullptr) or from given ones.  pp_ts_list: the item list
+// and device count of layer ordinal k (1..3) if lists for nb frames are in place.  pp_ts_fill: copy the representatives' tiles of
+// layer k in `out` [nb][C][H][W] to the skipped tiles.
+int pp_ts_create(pp_ctx* ctx);
+void pp_ts_destroy(pp_ctx* ctx);
+bool pp_ts_usable(pp_ctx* ctx, int level0_layers);
+void pp_ts_begin_pass(pp_ctx* ctx);
+int pp_ts_build(pp_ctx* ctx, int nb, const uint64_t* words, hipStream_t stream);
+int pp_ts_build_from_bitmap(pp_ctx* ctx, int nb, const uint8_t* bitmap, hipStream_t stream);
+void pp_ts_mark_pass(pp_ctx* ctx, int nb);
+void pp_ts_begin_hook(pp_ctx* ctx, bool builds);
+void pp_ts_end_hook(pp_ctx* ctx);
+bool pp_ts_list(pp_ctx* ctx, int k, int nb, const int2** items, const int32_t** count);
+int pp_ts_fill(pp_ctx* ctx, int k, int nb, float* out, size_t out_fs, int C, hipStream_t stream);
+int pp_ts_dense_items(pp_ctx* ctx, int nb);
+int pp_ts_read_count(pp_ctx* ctx, int k, int32_t* n);
+int pp_ts_fetch_flags(pp_ctx* ctx, int frame, void* dst, hipStream_t stream);
 void pp_post_destroy(pp_ctx* ctx);
 void pp_assign_destroy(pp_ctx* ctx);
 void pp_train_destroy(pp_ctx* ctx);

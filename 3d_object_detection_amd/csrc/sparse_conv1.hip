@@ -348,6 +348,14 @@ int pp_sc1_fetch_list(pp_ctx* ctx, int frame, void* dst, hipStream_t stream)
     return 0;
 }
 
+const uint64_t* pp_sc1_words(pp_ctx* ctx, int* nblk)
+{
+    const Sc1* S = (const Sc1*)ctx->sc1;
+    if (!S || ctx->sc1_last_nb < 1) return nullptr;
+    *nblk = S->nblk;
+    return S->words;
+}
+
 extern "C" int pp_set_sparse_conv1(pp_ctx* ctx, int on)
 {
     if (!ctx) return PP_E_ARG;

@@ -238,6 +238,16 @@ __device__ __forceinline__ void w6_load_x4(f32x4& dst, const i32x4 rs, const uns
 {
     asm volatile(W6_SGPR_PAD "buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rs), "s"(soff));
 }
+// Entry i of the item list (LIST) through the scalar cache.  A plain load would do no worse than this in a kernel that stores nothing; here
+// hipcc cannot rule out that the list aliases the output, makes it a global_load -- one more user of vmcnt -- and waits for it with
+// vmcnt(0): the whole prefetch queue of the wave (patch pieces from HBM, two chunks of A operands) drained twice per tile.
+__device__ __forceinline__ int2 w6_item(const int2* items, int i)
+{
+    const int2* q = items + i;
+    int2 r;
+    asm volatile(W6_SGPR_PAD "s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(q) : "memory");
+    return r;
+}
 template <int N> __device__ __forceinline__ void w6_wait() { asm volatile("s_waitcnt vmcnt(%c0)" :: "i"(N)); }
 template <int N> __device__ __forceinline__ void w6_wait(f32x4& x) { asm volatile("s_waitcnt vmcnt(%c1)" : "+v"(x) : "i"(N)); }
 // the 9 positions' accumulator rows (2 RP, 2 RP + 1) of M-tile MT as pairs, for v_pk_* arithmetic
@@ -262,7 +272,10 @@ __device__ __forceinline__ void w6_acc_read(f32x2 (&mm)[9])
     for (int j = 0; j < 9; ++j) { mm[j][0] = l[j]; mm[j][1] = u[j]; }
 }
 
-template <int TWT, int WV, int ROOF>
+// LIST (tile skipping, tile_skip.hip): work item l / ncb is entry {frame * ntile + tile, mult} of p.items -- ascending in (frame, tile), so
+// the frame-parity table flip works as it does for the dense order -- the item count comes from the device, and a tile's statistics are added
+// mult times (its output stands for mult bit-identical tiles; the product is exact in fp64).  Everything else is the dense kernel.
+template <int TWT, int WV, int ROOF, bool LIST>
 __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
 {
     using C = Wino6Cfg<TWT>;
@@ -277,7 +290,8 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
 
     const int nbx = p.rnbx, nby = p.rnby;
     const int ntile = nbx * nby, ncb = p.Cout / C::BM;
-    const int total = ntile * ncb * p.nb;
+    int total = ntile * ncb * p.nb;
+    if constexpr (LIST) total = min(p.item_count[0], ntile * p.nb) * ncb;
     const int per = (total + 7) >> 3;
     const int xk = blockIdx.x & 7, xj = blockIdx.x >> 3, nloc = gridDim.x >> 3;
     const int lin_end = min(total, (xk + 1) * per);
@@ -311,8 +325,11 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
     int s_lin = lin0, s_ch = 0, s_frame = 0, s_tab = 0;
     int r_c0[2] = {0, 0}, r_tab[2] = {0, 0}, r_lin[2] = {lin0, lin0}, mk_lin = -1; // the chunk held by register set 0 / 1
     unsigned r_vmask[2] = {0u, 0u};
+    const int2* items = p.items;
     auto set_load_tile = [&](int l) {
-        const int t_ = (l / ncb) % ntile, f_ = l / (ncb * ntile);
+        int t_, f_;
+        if constexpr (LIST) { const int ft_ = w6_item(items, l / ncb).x; t_ = ft_ % ntile; f_ = ft_ / ntile; }
+        else { t_ = (l / ncb) % ntile; f_ = l / (ncb * ntile); }
         const int iy0_ = ry0 + (t_ / nbx) * C::PH - 1, ix0_ = rx0 + (t_ % nbx) * C::PW - 1;
         vmask = 0u;
 #pragma unroll
@@ -467,8 +484,11 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
     const size_t out_plane = (size_t)p.Hout * p.Wout;
 
     for (int lin = lin0; lin < lin_end; lin += nloc) {
-        const int cb = lin % ncb, tile = (lin / ncb) % ntile;
-        const size_t fz = lin / (ncb * ntile);
+        const int cb = lin % ncb;
+        int tile, mult = 1;
+        size_t fz;
+        if constexpr (LIST) { const int2 it = w6_item(items, lin / ncb); tile = it.x % ntile; fz = it.x / ntile; mult = it.y; }
+        else { tile = (lin / ncb) % ntile; fz = lin / (ncb * ntile); }
         const int co0 = cb * C::BM;
         const int ox0 = p.rx0 + (tile % nbx) * C::PW, oy0 = p.ry0 + (tile / nbx) * C::PH;
         const unsigned wb_item = (unsigned)cb * block_wb;
@@ -704,7 +724,8 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
             const float v = rr == 0 ? sel[0] : rr == 1 ? sel[1] : rr == 2 ? sel[2] : sel[3];
             if (m < 8) {
                 double* dst = p.stat_acc + fz * p.stat_fs + ((size_t)(blockIdx.x % NREP) * p.stat_C + co0 + WV * 16 + kq * 4 + rr) * 2 + (m & 1);
-                const double dv = (double)v;
+                double dv = (double)v;
+                if constexpr (LIST) dv *= (double)mult;
                 asm volatile("global_atomic_add_f64 %0, %1, off\n\ts_nop 1" :: "v"(dst), "v"(dv) : "memory");
             }
         }
@@ -717,23 +738,29 @@ __device__ __forceinline__ void wino6_body(const ConvP& p, float* smem)
 #undef W6_WRITE_PIECE
 }
 
-template <int TWT, int ROOF>
+template <int TWT, int ROOF, bool LIST = false>
 __global__ void __launch_bounds__(256, 1) wino6_mfma(const ConvP p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (wv == 0) wino6_body<TWT, 0, ROOF>(p, smem);
-    else if (wv == 1) wino6_body<TWT, 1, ROOF>(p, smem);
-    else if (wv == 2) wino6_body<TWT, 2, ROOF>(p, smem);
-    else wino6_body<TWT, 3, ROOF>(p, smem);
+    if (wv == 0) wino6_body<TWT, 0, ROOF, LIST>(p, smem);
+    else if (wv == 1) wino6_body<TWT, 1, ROOF, LIST>(p, smem);
+    else if (wv == 2) wino6_body<TWT, 2, ROOF, LIST>(p, smem);
+    else wino6_body<TWT, 3, ROOF, LIST>(p, smem);
 }
 
-template <int TWT>
+// MAIN: the 16 x 16 main tile -- the two name tags (ROOF: the level-0 layers bench.py prices) and, for each, the list twin as kern2; the strip
+// tilings exist as <TWT, 0> alone
+template <int TWT, bool MAIN>
 Variant make_wino6(bool roofline_layer)
 {
     using C = Wino6Cfg<TWT>;
     Variant v;
-    v.kern = roofline_layer ? wino6_mfma<TWT, 1> : wino6_mfma<TWT, 0>;
+    if constexpr (MAIN) {
+        v.kern = roofline_layer ? wino6_mfma<TWT, 1> : wino6_mfma<TWT, 0>;
+        v.kern2 = roofline_layer ? wino6_mfma<TWT, 1, true> : wino6_mfma<TWT, 0, true>;
+    } else
+        v.kern = wino6_mfma<TWT, 0>;
     v.bm = C::BM; v.bmp = C::BM; v.pw = C::PW; v.ph = C::PH; v.kc = C::KC; v.threads = C::THREADS;
     v.waves = 4; v.pairs = 4 * 9;
     v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
@@ -751,11 +778,11 @@ Variant make_wino6(bool roofline_layer)
 void wino6_menu(std::vector<Variant>& menu, bool roofline_layer)
 {
     const char* e = getenv("PP_WINO6"); // read per call (commit time only)
-    if (!(e && e[0] == '0')) menu.push_back(make_wino6<4>(roofline_layer)); // 16 x 16 px
+    if (!(e && e[0] == '0')) menu.push_back(make_wino6<4, true>(roofline_layer)); // 16 x 16 px
 }
 // strip tilings of the region launches (launch_conv): a map that is no multiple of 16 x 16 is covered by whole main tiles plus thin tiles
-Variant wino6_strip_v() { return make_wino6<1>(false); }  // 4 px wide, 64 px tall
-Variant wino6_strip_h() { return make_wino6<16>(false); } // 64 px wide, 4 px tall
+Variant wino6_strip_v() { return make_wino6<1, false>(false); }  // 4 px wide, 64 px tall
+Variant wino6_strip_h() { return make_wino6<16, false>(false); } // 64 px wide, 4 px tall
 
 // Transformed weights U = G g G^T (fp64 on the host, rounded once) in the order the waves fetch them:
 //   [cout block][k-step][wave][local position][lane = (cin quad lane kq) * 16 + m][M-tile]  =  U[block*64 + mt*16 + m][4 s + kq][i][jj]

@@ -256,6 +256,16 @@ class Engine:
         (default) or with the dense tiling.  PP_SPARSE_CONV1=0 in the environment (read by pp_create) forces it off."""
         _lib.check(self.lib.pp_set_sparse_conv1(self.ctx, 1 if on else 0), self.ctx, "pp_set_sparse_conv1")
 
+    def set_tile_skip(self, on):
+        """pp_set_tile_skip: behind the sparse first convolution, the fp32 wino6 launches of level 0's stride-1 layers compute one tile
+        per (frame, layer, border class) of those whose input is constant and copy it to the others (default), or every tile.
+        PP_TILE_SKIP=0 in the environment (read by pp_create) forces it off."""
+        _lib.check(self.lib.pp_set_tile_skip(self.ctx, 1 if on else 0), self.ctx, "pp_set_tile_skip")
+
+    def tile_skip_active(self):
+        """pp_tile_skip_active: did the last pass (or debug_layer call) run a listed launch."""
+        return bool(self.lib.pp_tile_skip_active(self.ctx))
+
     def load_state_dict(self, sd):
         for k, v in sd.items():
             if k.endswith("num_batches_tracked"):
@@ -522,24 +532,28 @@ class Engine:
     def fetch(self, frame, what):
         """Inspection hook (pp_fetch_frame_tensor): one tensor of frame `frame` of the last infer_batch / infer_frame
         pass, copied out of the context's internal buffers.  what: cls | box | dir | mask | rpn | feat | coors | num | active (the
-        sparse first convolution's list: i32[1 + min(4 max_voxels, H W)] = count, then the active output pixels in ascending order)."""
+        sparse first convolution's list: i32[1 + min(4 max_voxels, H W)] = count, then the active output pixels in ascending order) |
+        tile_flags (tile skipping: u8[3, H // 16, W // 16], 1 = skippable at level 0's first, second, third stride-1 layer)."""
         kinds = {"cls": (0, (self.A,), torch.float32), "box": (1, (self.A, 7), torch.float32), "dir": (2, (self.A, 2), torch.float32),
                  "mask": (3, (self.A,), torch.uint8), "rpn": (4, (320, self.H, self.W), torch.float32),
                  "feat": (5, (self.max_voxels, 64), torch.float32), "coors": (6, (self.max_voxels, 3), torch.int32),
-                 "num": (7, (1,), torch.int32), "active": (8, (1 + min(4 * self.max_voxels, self.H * self.W),), torch.int32)}
+                 "num": (7, (1,), torch.int32), "active": (8, (1 + min(4 * self.max_voxels, self.H * self.W),), torch.int32),
+                 "tile_flags": (9, (3, self.H // 16, self.W // 16), torch.uint8)}
         kind, shape, dtype = kinds[what]
         out = torch.empty(shape, dtype=dtype, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_fetch_frame_tensor(self.ctx, int(frame), kind, _ptr(out), _stream()), self.ctx, "pp_fetch_frame_tensor")
         return out
 
-    def debug_layer(self, layer, x=None, res=None, scale=None, shift=None, pmap=None, feat=None, stats=False):
+    def debug_layer(self, layer, x=None, res=None, scale=None, shift=None, pmap=None, feat=None, stats=False, active=None, skip_k=0):
         """Test hook (pp_debug_layer): ONE layer of the committed plan -- index 0 .. 19 of layer_tilings(), with the kernel, tiling and
         weight image reported there -- on caller tensors.  x [nb,cin,hin,win] (or, layer 0 only, pmap i32[nb,gx,gy] + feat
         f32[nb,max_voxels,64]); res [nb,cout,h,w] for a conv; scale / shift f32[cin] (shared) or f32[nb,cin] (per frame) select the
         relu(x * scale + shift) prologue, None reads x raw.  x and res must have the element type of the committed tiling
         (layer_io_dtypes).  Returns the output tensor -- conv [nb,cout,h,w], upsampler [nb,cout,h*up,w*up], head (cls [nb,A,1],
-        box [nb,A,7], dir [nb,A,2]) -- and, with stats=True, also f64[nb,cout,2] = per-channel (sum, sum of squares)."""
+        box [nb,A,7], dir [nb,A,2]) -- and, with stats=True, also f64[nb,cout,2] = per-channel (sum, sum of squares).
+        active u8[nb,H,W] with skip_k = 1..3 (pp_debug_layer_skip): the tile-skipping form of a stride-1 layer of level 0 -- the pixels
+        the sparse first convolution would have computed and the layer's ordinal; x and res must then be what the previous layers give."""
         til = self.layer_tilings()
         if not self.weights_loaded or not til:
             raise RuntimeError("debug_layer: load_state_dict first")
@@ -584,7 +598,11 @@ class Engine:
             shp = (nb, cin) if pre_mode == 2 else (cin,)
             scale = _chk(scale, torch.float32, shp, "debug_layer: scale")
             shift = _chk(shift, torch.float32, shp, "debug_layer: shift")
-        for tns, what in ((x, "x"), (res, "res"), (scale, "scale"), (shift, "shift"), (pmap, "pmap"), (feat, "feat")):
+        if (active is None) != (skip_k == 0):
+            raise ValueError("debug_layer: active and skip_k come together")
+        if active is not None:
+            active = _chk(active, torch.uint8, (nb, self.H, self.W), "debug_layer: active")
+        for tns, what in ((x, "x"), (res, "res"), (scale, "scale"), (shift, "shift"), (pmap, "pmap"), (feat, "feat"), (active, "active")):
             if tns is not None and tns.device != self.device:
                 raise ValueError(f"debug_layer: {what} is on {tns.device}, the engine on {self.device}")
         if kind == 2:
@@ -598,8 +616,13 @@ class Engine:
             box = dr = None
         st = self._t((nb, cout, 2), torch.float64) if stats else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_debug_layer(self.ctx, layer, nb, _ptr(xin), _ptr(res), pre_mode, _ptr(scale), _ptr(shift), _ptr(pmap), _ptr(feat),
-                                               _ptr(out), _ptr(box), _ptr(dr), _ptr(st), _stream()), self.ctx, "pp_debug_layer")
+            if active is not None:
+                _lib.check(self.lib.pp_debug_layer_skip(self.ctx, layer, nb, _ptr(xin), _ptr(res), pre_mode, _ptr(scale), _ptr(shift), _ptr(pmap),
+                                                        _ptr(feat), _ptr(out), _ptr(box), _ptr(dr), _ptr(st), _ptr(active), int(skip_k), _stream()),
+                           self.ctx, "pp_debug_layer_skip")
+            else:
+                _lib.check(self.lib.pp_debug_layer(self.ctx, layer, nb, _ptr(xin), _ptr(res), pre_mode, _ptr(scale), _ptr(shift), _ptr(pmap), _ptr(feat),
+                                                   _ptr(out), _ptr(box), _ptr(dr), _ptr(st), _stream()), self.ctx, "pp_debug_layer")
         ret = (out, box, dr) if kind == 2 else out
         return (ret, st) if stats else ret
 

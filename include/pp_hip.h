@@ -149,7 +149,9 @@ int pp_infer_batch(pp_ctx* ctx, const float* const* pts_h, const int32_t* n_h, i
  * 5 PFN rows f32[max_voxels,64] | 6 coors i32[max_voxels,3] | 7 pillar count i32[1] |
  * 8 active list of the sparse first convolution i32[1 + min(4 max_voxels, H W)]: the count, then the active output pixels
  * (index = x * W + y on the level-0 map) in ascending order, entries past the count unspecified; PP_E_STATE when the last pass
- * ran the dense first convolution. */
+ * ran the dense first convolution |
+ * 9 tile flags of the tile-skipping path u8[3][(H / 16) (W / 16)]: 1 = the 16 x 16 tile (index = (x / 16) * (W / 16) + y / 16) is
+ * skippable at the first, second, third stride-1 layer of level 0; PP_E_STATE when the last pass built none (see pp_set_tile_skip). */
 int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* stream);
 
 /* Single-layer hook for the layer tests: runs ONE layer of the committed launch plan -- the kernel, tiling and packed weight image
@@ -176,6 +178,16 @@ int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* str
 int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,
                    const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats, void* stream);
 
+/* pp_debug_layer with the tile-skipping form of a stride-1 layer of level 0 (see pp_set_tile_skip): active u8[nb][H][W] marks the
+ * pixels the sparse first convolution would have computed, skip_k = 1..3 is the layer's ordinal among those layers.  The lists are
+ * built by the pass's own builder and the layer runs as the listed launch plus the fill.  `in` and `res` must satisfy the rule's
+ * precondition (constant per channel outside the layer's non-constant blocks): produce them by running the previous layers.
+ * active = NULL and skip_k = 0 is pp_debug_layer.  PP_E_ARG when the path does not serve the layer (tiling, precision, map not a
+ * whole number of 16 x 16 tiles, switch off). */
+int pp_debug_layer_skip(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,
+                        const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats,
+                        const uint8_t* active, int skip_k, void* stream);
+
 /* Deferred head (default on).  Post-processing reads the box / dir logits of at most nms_pre_max anchors per class, so a pass of
  * pp_infer_batch / pp_infer_frame computes the cls rows of the head for every pixel and the box / dir logits for the selected
  * candidates only (bit-identical to the full head: same MFMA arithmetic on the same weight image).  The context's full box / dir
@@ -195,6 +207,16 @@ int pp_head_defer_active(pp_ctx* ctx);
  * frame's result does not depend on the batch it rides in.  on = 0 / 1; the environment variable PP_SPARSE_CONV1=0 (read at
  * pp_create) forces it off.  The 16-bit modes and the dense-canvas entry points (pp_scatter + pp_backbone) are not affected. */
 int pp_set_sparse_conv1(pp_ctx* ctx, int on);
+
+/* Tile skipping (default on).  Behind the sparse first convolution the level-0 map is exactly zero outside the active pixels, so
+ * relu(norm(.)) is one constant per channel there and the three stride-1 3x3 layers of level 0 would compute the same 16 x 16 tile
+ * hundreds of times per frame.  fp32 passes whose first convolution ran sparse, on the wino6 main tile and a map of whole 16 x 16
+ * tiles, compute one such tile per (frame, layer, border class), weight its statistics by the class's count (exact in fp64) and copy
+ * it to the others: outputs are bit-identical to the dense launches', the fp64 statistics differ in addition order only (as they do
+ * from run to run).  Every other case runs the dense launches.  on = 0 / 1; PP_TILE_SKIP=0 in the environment (read at pp_create)
+ * forces it off.  pp_tile_skip_active: did the last pass (or single-layer call) run a listed launch. */
+int pp_set_tile_skip(pp_ctx* ctx, int on);
+int pp_tile_skip_active(pp_ctx* ctx);
 
 /* ---- training targets and loss (anchor_assigner.py:337-457, loss_generator.py:26-253, metrics.py:14-69) ----
  * Ground truth of nb frames: gt f32[G][7] (x,y,z,l,w,h,r), gt_cls i32[G] 1-based class id in detect_class order,
