@@ -79,6 +79,9 @@ PROTOTYPES = {
     "pp_backbone_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_neck_backward": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
     "pp_update_neck_weights": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
+    "pp_unit_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
+    "pp_backbone_block_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_update_block_weights": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_int, c_p]),
     "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),

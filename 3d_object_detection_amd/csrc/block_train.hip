@@ -1,0 +1,440 @@
+// Training side of the backbone (gfx950): the backward of one pre-activation Resnet unit, InstanceNorm2d(eps 1e-3, no affine) -> ReLU
+// -> Conv2d(C -> C, 3 x 3, pad 1, no bias), the unit every Resnet2 module of RPN is made of (pointpillars8_shared.py:418-431).  fp32
+// throughout, InstanceNorm backbone only, generic in C = 64 | 128 | 256 and in the map size.
+//
+// pp_unit_backward materialises a = relu(xhat) and dz once per call, both in the same padded plane layout: a plane is the
+// (h + 2) x (w + 2) zero-haloed image (PP = (h + 2) wp elements, wp = w + 2) between two guard bands of G >= wp + 17 zeros, PS elements
+// in all (G and PS multiples of 4).  In that layout a 3 x 3 tap is a shift of the flat index by off_t = (ky - 1) wp + (kx - 1), every
+// shifted read stays inside the plane, and halo x anything = 0, so both gradient products are plain GEMMs over flat positions P with
+// no branch per tap:
+//   k_unit_wt      wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows
+//   k_unit_pack    per (frame, c): sum u, sum u^2 in fp64, mean / rstd, a and dz into the padded planes (halo and guards rewritten)
+//   k_unit_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      M = C, N = 9 C, K = frames x PP, split into ranges
+//   k_unit_dw_reduce  partials summed in index order (double, rounded once)
+//   k_unit_dgrad   da[ci][P] = sum_{t, co} wT[t][co][ci] dz[co][P - off_t]           M = C, N = PP, K = 9 C, summed in blocks of DA_BLOCK
+//   k_unit_norm    per (frame, c): sum Gr, sum Gr xhat in fp64 over da, then du = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) (+ dskip)
+// The two products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory, as in neck_train.hip.
+//
+// Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
+// order; K ranges of the wgrad depend on the shapes only.  A frame's a, dz, da and du do not
+// depend on the batch it rides in; dw depends on nb within fp32 summation error (the K ranges do).
+#include <cmath>
+#include "pp_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr size_t WS_BUDGET = (size_t)256 << 20; // bytes of the a + dz planes: larger batches run in frame chunks
+constexpr int DW_WGS = 512;                     // workgroups a wgrad launch aims at (output tiles x K ranges)
+constexpr int DW_MAX_SPLIT = 256;
+constexpr int DA_BLOCK = 64;                    // k-terms that k_unit_dgrad sums in one accumulator before adding the block to the total
+
+struct block_ws {
+    float* planes = nullptr; size_t planes_elems = 0; // a [fc][C][PS], then dz [fc][C][PS]
+    float* stm = nullptr;    size_t stm_elems = 0;    // [fc][C][2]: mean, rstd as the forward rounds them
+    float* wT = nullptr;     size_t wT_elems = 0;
+    float* part = nullptr;   size_t part_elems = 0;
+    uint64_t img_gen = 0;    // ctx->commit_gen the position maps belong to (0: none)
+    pp_block_image img[5];
+    int32_t* pmap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
+// the Winograd weight transforms' G of pack_layer (F(2x2,3x3)) and wino6_pack (F(4x4,3x3)), the same constant expressions
+__constant__ double kG4[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+__constant__ double kG6[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                 {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <typename T>
+int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need)
+{
+    if (need <= *have) return 0;
+    PP_HIP(hipDeviceSynchronize()); // a kernel of an earlier call, on this stream or another, may still read the old buffer
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    PP_HIP(hipMalloc((void**)buf, need * sizeof(T)));
+    *have = need;
+    return 0;
+}
+
+// both sums over the 256 threads' partials (segment t: elements t, t + 256, ...), added in index order 0 .. 255 by every thread: the
+// same bits in every thread
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[2])
+{
+    __syncthreads(); // red may still be read from an earlier call
+    red[threadIdx.x][0] = a; red[threadIdx.x][1] = b;
+    __syncthreads();
+    double sa = 0.0, sb = 0.0;
+    for (int t = 0; t < 256; ++t) { sa += red[t][0]; sb += red[t][1]; }
+    a = sa; b = sb;
+}
+
+__global__ void __launch_bounds__(256) k_unit_wt(const float* __restrict__ w, float* __restrict__ wT, int C)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][C][C]
+    if (i >= 9 * C * C) return;
+    const int ci = i % C, co = (i / C) % C, t = i / (C * C);
+    wT[i] = w[((size_t)co * C + ci) * 9 + t];
+}
+
+// ---- statistics + a + dz: grid (C, frames), one workgroup per plane ------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_unit_pack(const float* __restrict__ u, const float* __restrict__ dy, float* __restrict__ ap,
+                                                   float* __restrict__ dzp, float* __restrict__ stm, int C, int h, int w, int wp, int G, int PP,
+                                                   int PS)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x, N = h * w;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* dp = dy + pl * N;
+    double s = 0.0, ss = 0.0;
+    for (int i = tid; i < N; i += 256) {
+        const double v = (double)up[i];
+        s += v; ss += v * v;
+    }
+    block_sum2(s, ss, red);
+    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
+    double var = ss * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
+    if (tid == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    float* ao = ap + pl * PS;
+    float* zo = dzp + pl * PS;
+    for (int j = tid; j < PS; j += 256) {
+        const int P = j - G;
+        float av = 0.f, dv = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, x = P - y * wp;
+            if (y >= 1 && y <= h && x >= 1 && x <= w) {
+                const int i = (y - 1) * w + x - 1;
+                const float xhat = (up[i] - meanf) * rstdf;
+                av = xhat > 0.f ? xhat : 0.f;
+                dv = dp[i];
+            }
+        }
+        ao[j] = av; zo[j] = dv;
+    }
+}
+
+// ---- wgrad: workgroup tile 64 co x 32 NB columns n = ci 9 + t, four waves 2 x 2, each 32 co x 16 NB columns.  K runs over 16-position
+// chunks of the launch's frames (chunk c: frame c / cpf, positions 16 (c % cpf) ..; positions past PP read guard zeros of dz); a lane
+// takes positions 4 q .. 4 q + 3 of the chunk as its four k-steps: one 16-byte load per dz row, four shifted loads per a column.
+// blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z, already in the state_dict layout [co][ci][3][3].
+template <int NB>
+__global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dzp, const float* __restrict__ ap, float* __restrict__ part, int C,
+                                                    int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int co0 = blockIdx.y * 64 + 32 * (wave >> 1), n0 = blockIdx.x * (32 * NB) + 16 * NB * (wave & 1);
+    const int NC = 9 * C;
+    int boff[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int n = n0 + 16 * b + l16, ci = n / 9, t = n - 9 * ci;
+        boff[b] = ci * PS + G + (t / 3 - 1) * wp + (t % 3 - 1);
+    }
+    f32x4 acc[2][NB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
+    for (int c = c0; c < c1; ++c) {
+        const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
+        const float* zf = dzp + (size_t)f * C * PS + G + pb;
+        const float* af = ap + (size_t)f * C * PS + pb;
+        float za[2][4], ab[NB][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const float4 v = *reinterpret_cast<const float4*>(zf + (size_t)(co0 + 16 * a + l16) * PS);
+            za[a][0] = v.x; za[a][1] = v.y; za[a][2] = v.z; za[a][3] = v.w;
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) ab[b][s] = af[boff[b] + s];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a][s], ab[b][s], acc[a][b], 0, 0, 0);
+    }
+    float* pw = part + (size_t)(gbase + blockIdx.z) * C * NC;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
+}
+
+__global__ void __launch_bounds__(256) k_unit_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += (double)part[(size_t)g * n + i];
+    dw[i] = (float)s;
+}
+
+// ---- dgrad: a workgroup covers ALL C channels (WM = C / 64 waves down, 4 / WM across), each wave 64 ci x 32 positions, so dz is read
+// once per tap.  K = (t, co) in steps of 4 output channels (lane group q takes co + q).  The sum over K (2304 terms at C = 256) is
+// blocked: each DA_BLOCK terms accumulate from zero and the block sums are then added in (t, co) order, so the rounding error grows
+// with the block length and the block count, not with K.  Positions past PP read a clamped index and are never stored; only interior
+// positions are stored, into the tight [C][h][w] plane of du.
+template <int WM>
+__global__ void __launch_bounds__(256) k_unit_dgrad(const float* __restrict__ wT, const float* __restrict__ dzp, float* __restrict__ da, int C, int h,
+                                                    int w, int wp, int G, int PP, int PS)
+{
+    constexpr int WN = 4 / WM;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int ci0 = 64 * (wave / WN), p0 = blockIdx.x * (32 * WN) + 32 * (wave % WN);
+    const float* zf = dzp + (size_t)blockIdx.z * C * PS + G;
+    float* daf = da + (size_t)blockIdx.z * C * h * w;
+    f32x4 tot[4][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) tot[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int P0 = p0 + l16, P1 = p0 + 16 + l16;
+    const int i0 = P0 < PP ? P0 : 0, i1 = P1 < PP ? P1 : 0;
+    for (int t = 0; t < 9; ++t) {
+        const int off = (t / 3 - 1) * wp + (t % 3 - 1);
+        const float* wt_t = wT + (size_t)t * C * C + ci0 + l16;
+        for (int cb0 = 0; cb0 < C; cb0 += DA_BLOCK) { // C is a multiple of DA_BLOCK
+            f32x4 acc[4][2];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int cb = cb0; cb < cb0 + DA_BLOCK; cb += 4) {
+                const int co = cb + q;
+                const float* wr = wt_t + (size_t)co * C;
+                const float* zr = zf + (size_t)co * PS - off;
+                const float z0 = zr[i0], z1 = zr[i1];
+                float wa[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) wa[a] = wr[16 * a];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z0, acc[a][0], 0, 0, 0);
+                    acc[a][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z1, acc[a][1], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) tot[a][b] += acc[a][b];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int P = p0 + 16 * b + l16;
+        if (P >= PP) continue;
+        const int y = P / wp, x = P - y * wp;
+        if (y < 1 || y > h || x < 1 || x > w) continue;
+        float* o = daf + (size_t)(y - 1) * w + x - 1;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[(size_t)(ci0 + 16 * a + 4 * q + i) * h * w] = tot[a][b][i];
+    }
+}
+
+// ---- norm backward, in place over da (= du): grid (C, frames).  Gr = da [a > 0] with the a of this call; xhat is re-evaluated by the
+// expression k_unit_pack used, so it is the xhat whose sign made the mask ------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, const float* __restrict__ ap, const float* __restrict__ stm,
+                                                   const float* __restrict__ dskip, float* __restrict__ du, int C, int h, int w, int wp, int G, int PS)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x, N = h * w;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* ai = ap + pl * PS + G + wp + 1; // interior origin
+    float* dp = du + pl * N;
+    const float meanf = stm[pl * 2], rstdf = stm[pl * 2 + 1];
+    double sg = 0.0, sgx = 0.0;
+    for (int i = tid; i < N; i += 256) {
+        const int y = i / w, x = i - y * w;
+        const float av = ai[y * wp + x];
+        if (av > 0.f) {
+            const double g = (double)dp[i];
+            sg += g; sgx += g * (double)av;
+        }
+    }
+    block_sum2(sg, sgx, red);
+    const double inv_n = 1.0 / (double)N;
+    const float c1 = (float)(sg * inv_n), c2 = (float)(sgx * inv_n);
+    for (int i = tid; i < N; i += 256) {
+        const int y = i / w, x = i - y * w;
+        const float g = ai[y * wp + x] > 0.f ? dp[i] : 0.f;
+        const float xhat = (up[i] - meanf) * rstdf;
+        float v = rstdf * ((g - c1) - xhat * c2);
+        if (dskip) v = v + dskip[pl * N + i];
+        dp[i] = v;
+    }
+}
+
+// ---- weight update: image element i holds position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T.  U = G g G^T is
+// evaluated in fp64 in the host packers' own expression order and rounded once; the library is built with -ffp-contract=off on both
+// sides, so the image is the one a fresh commit of the same values packs, bit for bit -------------------------------------------------
+__global__ void __launch_bounds__(256) k_unit_image(float* __restrict__ dst, const int32_t* __restrict__ pmap, int n, const float* __restrict__ w,
+                                                    int T, int nrc)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int m = pmap[i];
+    const int rc = m < 0 ? -1 : m / T;
+    if (rc < 0 || rc >= nrc) { dst[i] = 0.f; return; }
+    const int pos = m - rc * T;
+    const float* g = w + (size_t)rc * 9;
+    if (T == 9) { dst[i] = g[pos]; return; }
+    const int nn = T == 16 ? 4 : 6, a = pos / nn, b = pos - a * nn;
+    const double* Ga = T == 16 ? kG4[a] : kG6[a];
+    const double* Gb = T == 16 ? kG4[b] : kG6[b];
+    const double ga0 = Ga[0], ga1 = Ga[1], ga2 = Ga[2];
+    const double t0 = ga0 * g[0] + ga1 * g[3] + ga2 * g[6];
+    const double t1 = ga0 * g[1] + ga1 * g[4] + ga2 * g[7];
+    const double t2 = ga0 * g[2] + ga1 * g[5] + ga2 * g[8];
+    dst[i] = (float)(t0 * Gb[0] + t1 * Gb[1] + t2 * Gb[2]);
+}
+
+block_ws* workspace(pp_ctx* ctx)
+{
+    if (!ctx->blk) ctx->blk = new block_ws();
+    return (block_ws*)ctx->blk;
+}
+
+// K ranges of one wgrad launch over `nchunks` 16-position chunks
+void dw_ranges(int tiles, int nchunks, int* splits, int* cps)
+{
+    int sp = DW_WGS / tiles;
+    sp = sp < 1 ? 1 : sp > DW_MAX_SPLIT ? DW_MAX_SPLIT : sp;
+    if (sp > nchunks) sp = nchunks;
+    *cps = (nchunks + sp - 1) / sp;
+    *splits = (nchunks + *cps - 1) / *cps;
+}
+
+} // namespace
+
+void pp_block_destroy(pp_ctx* ctx)
+{
+    block_ws* w = (block_ws*)ctx->blk;
+    if (!w) return;
+    void* q[] = {w->planes, w->stm, w->wT, w->part, w->pmap[0], w->pmap[1], w->pmap[2], w->pmap[3], w->pmap[4]};
+    for (void* x : q)
+        if (x) (void)hipFree(x);
+    delete w;
+    ctx->blk = nullptr;
+}
+
+extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip, int nb,
+                                float* dw, float* du, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
+    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: C must be 64, 128 or 256");
+    if (!u || !wgt || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: null pointer");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: nb must be 1 .. max_batch");
+    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: h, w >= 1 and h w >= 2");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: w must be 16-byte aligned");
+    if (((uintptr_t)u | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw | (uintptr_t)du) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: tensors must be 4-byte aligned");
+    // padded plane: guards of G zeros around the (h + 2) x wp image
+    const int64_t wp64 = (int64_t)w + 2, PP64 = ((int64_t)h + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
+    if (2 * (uint64_t)C * (uint64_t)PS64 * sizeof(float) > WS_BUDGET)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: map too large (one frame's planes exceed the 256 MB workspace)");
+    const int wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64, N = h * w;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: functions of the shapes alone
+    const size_t pf_elems = (size_t)C * PS;
+    int fc = (int)(WS_BUDGET / (2 * pf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int NBt = C >= 128 ? 4 : 2;
+    const int NC = 9 * C, tiles = (NC / (32 * NBt)) * (C / 64), cpf = (PP + 15) / 16;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = C * NC;
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)fc * C * 2)) ||
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
+        return rc;
+    float* ap = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * pf_elems;
+    if (du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, C);
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t o = (size_t)f0 * C * N;
+        hipLaunchKernelGGL(k_unit_pack, dim3(C, fn), dim3(256), 0, stream, u + o, dy + o, ap, dzp, ws->stm, C, h, w, wp, G, PP, PS);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / (32 * NBt), C / 64, sp);
+        if (NBt == 4)
+            hipLaunchKernelGGL(k_unit_wgrad<4>, gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        else
+            hipLaunchKernelGGL(k_unit_wgrad<2>, gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        gbase += sp;
+        if (du) {
+            float* duc = du + o;
+            if (C == 64)
+                hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            else if (C == 128)
+                hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            else
+                hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            hipLaunchKernelGGL(k_unit_norm, dim3(C, fn), dim3(256), 0, stream, u + o, ap, ws->stm, dskip ? dskip + o : nullptr, duc, C, h, w, wp,
+                               G, PS);
+        }
+    }
+    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, Gp, nw, dw);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pp_update_block_weights(pp_ctx* ctx, int block, const float* const* w, int n, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_block_weights: no committed weights to update (pp_commit_weights first)");
+    if (block != 2 || n != 5)
+        return pp_fail(ctx, PP_E_ARG, "pp_update_block_weights: block 3 only (block = 2, n = 5): blocks 1 and 2 have no backward yet, and level 0 "
+                                      "carries the tile-skipping path");
+    if (!w) return pp_fail(ctx, PP_E_ARG, "pp_update_block_weights: null pointer");
+    for (int k = 0; k < n; ++k)
+        if (!w[k] || ((uintptr_t)w[k] & 3)) return pp_fail(ctx, PP_E_ARG, "pp_update_block_weights: null or misaligned weight pointer");
+    if (pp_effective_precision(ctx) != 0)
+        return pp_fail(ctx, PP_E_ARG, "pp_update_block_weights: fp32 mode only (the committed plan packs the convolutions in a 16-bit format)");
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    if (ws->img_gen != ctx->commit_gen) { // first update after a commit: read the committed images' layout back (synchronous)
+        ws->img_gen = 0;
+        for (int k = 0; k < 5; ++k) {
+            int rc = pp_net_block_image(ctx, block, k, &ws->img[k]);
+            if (rc) return rc;
+            if (ws->pmap[k]) { (void)hipFree(ws->pmap[k]); ws->pmap[k] = nullptr; }
+            PP_HIP(hipMalloc((void**)&ws->pmap[k], ws->img[k].pmap.size() * sizeof(int32_t)));
+            PP_HIP(hipMemcpy(ws->pmap[k], ws->img[k].pmap.data(), ws->img[k].pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        ws->img_gen = ctx->commit_gen;
+    }
+    for (int k = 0; k < 5; ++k) {
+        const pp_block_image& im = ws->img[k];
+        const int cnt = (int)im.pmap.size();
+        hipLaunchKernelGGL(k_unit_image, dim3(pp_div_up(cnt, 256)), dim3(256), 0, stream, im.w, ws->pmap[k], cnt, w[k], im.T, im.C * im.C);
+    }
+    PP_HIP(hipGetLastError());
+    return 0;
+}

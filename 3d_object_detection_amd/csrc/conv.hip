@@ -2210,6 +2210,7 @@ struct Layer {
     int level;  // pixel grid of the GEMM: 0 = H,W ; 1 = H/2 ; 2 = H/4 (input grid for deconv)
     Variant var;
     float* w = nullptr; // packed device weights
+    size_t w_bytes = 0; // size of that image (pack_layer)
     int rows = 0;       // GEMM rows (virtual channels)
 };
 
@@ -2243,6 +2244,7 @@ struct pp_net {
     bool defer_ok = false; // the committed plan can run the deferred head: fp32 mode, 9-anchor head on a gemm1x1 tiling
     Variant cls_var;       // tiling of the cls-only head pass (chosen at pp_commit_weights when defer_ok)
     const float* tap[3] = {}; // block outputs of the last pp_run_backbone pass (what the three upsamplers read): pp_backbone_taps
+    float* unit_tap = nullptr; // copy hook of pp_backbone_block_taps: caller memory f32[5][256][H/4][W/4] for block 3's unit inputs (null: inert)
     double* dbg_stats = nullptr; // statistics accumulators of pp_debug_layer (allocated on its first call that asks for statistics)
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };
@@ -2474,7 +2476,10 @@ static inline int head_tile_row(int t)
     return -1;
 }
 
-int pack_layer(pp_ctx* ctx, Layer& L)
+// index_positions: the transform (U = G g G^T of the Winograd families, the identity elsewhere) is replaced by position indices --
+// element k of the transformed [rows][cin][taps_eff] array holds the float k + 1 -- so the image that comes out is the layout alone
+// (layer_position_map); conv3x3 layers on fp32 tilings only
+int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
 {
     const Variant& v = L.var;
     const int ks = (L.kind == 0) ? 3 : 1;
@@ -2515,9 +2520,10 @@ int pack_layer(pp_ctx* ctx, Layer& L)
     L.rows = rows;
     if (v.family == Family::Wino6) { // F(4x4,3x3): U = G g G^T in the order the four waves fetch their positions (wino6.hip)
         std::vector<float> pk6;
-        wino6_pack(rowsW.data(), rows, L.cin, pk6);
+        wino6_pack(rowsW.data(), rows, L.cin, pk6, index_positions);
         if (L.w) (void)hipFree(L.w);
         PP_HIP(hipMalloc((void**)&L.w, pk6.size() * sizeof(float)));
+        L.w_bytes = pk6.size() * sizeof(float);
         PP_HIP(hipMemcpy(L.w, pk6.data(), pk6.size() * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     }
@@ -2536,6 +2542,8 @@ int pack_layer(pp_ctx* ctx, Layer& L)
         rowsW.swap(u);
         taps_eff = 16;
     }
+    if (index_positions)
+        for (size_t k = 0; k < rowsW.size(); ++k) rowsW[k] = (float)(k + 1);
     if (v.family == Family::Gemm1x1 && L.kind == 2) { // head under gemm1x1: rows in head_tile_row order
         std::vector<float> perm((size_t)96 * L.cin, 0.f);
         for (int t = 0; t < 96; ++t) {
@@ -2568,6 +2576,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
                             }
         if (L.w) (void)hipFree(L.w);
         PP_HIP(hipMalloc((void**)&L.w, pk.size() * sizeof(uint16_t)));
+        L.w_bytes = pk.size() * sizeof(uint16_t);
         PP_HIP(hipMemcpy(L.w, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         return 0;
     }
@@ -2593,6 +2602,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
                     }
         if (L.w) (void)hipFree(L.w);
         PP_HIP(hipMalloc((void**)&L.w, pk4.size() * sizeof(uint16_t)));
+        L.w_bytes = pk4.size() * sizeof(uint16_t);
         PP_HIP(hipMemcpy(L.w, pk4.data(), pk4.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         return 0;
     }
@@ -2607,6 +2617,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
                 }
         if (L.w) (void)hipFree(L.w);
         PP_HIP(hipMalloc((void**)&L.w, pk3.size() * sizeof(float)));
+        L.w_bytes = pk3.size() * sizeof(float);
         PP_HIP(hipMemcpy(L.w, pk3.data(), pk3.size() * sizeof(float), hipMemcpyHostToDevice));
         return 0;
     }
@@ -2627,6 +2638,7 @@ int pack_layer(pp_ctx* ctx, Layer& L)
                     }
     if (L.w) (void)hipFree(L.w);
     PP_HIP(hipMalloc((void**)&L.w, pk.size() * sizeof(float)));
+    L.w_bytes = pk.size() * sizeof(float);
     PP_HIP(hipMemcpy(L.w, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
@@ -3376,6 +3388,12 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_CONV))) return rc;
         float* cur = Bf[1];
         float* spare[3] = {Bf[0], Bf[2], Bf[3]};
+        // block 3's unit inputs h, m3, r3, m4, r4 leave through the copy hook behind the launch that produces each: the level
+        // buffers are reused before the pass ends
+        float* utap = (b == 2 && nb == 1) ? net->unit_tap : nullptr;
+        const size_t ubytes = (size_t)c * cnt * sizeof(float);
+        int ucount = 0;
+        if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, cur, ubytes, hipMemcpyDeviceToDevice, stream));
         const int nunits = (b == 0) ? 2 : 3;
         int ts_k = 0; // level 0: ordinal of the next stride-1 layer (launch_conv ignores it unless this pass built tile lists)
         for (int u = 0; u < nunits; ++u) {
@@ -3389,8 +3407,10 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
                 if ((rc = launch_conv(ctx, net->layers[li++], cur, h, w, t1, nullptr, norm_ref(ctx, site_block(b, 1 + 2 * u), c, 0, cnt),
                                       stat_slot(ctx, site_block(b, 2 + 2 * u)), c, h, w, stream, nullptr, nullptr, nb, 0, 0, nullptr, nullptr,
                                       b == 0 ? ++ts_k : 0))) return rc;
+                if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, t1, ubytes, hipMemcpyDeviceToDevice, stream));
                 if ((rc = launch_conv(ctx, net->layers[li++], t1, h, w, t2, cur, norm_ref(ctx, site_block(b, 2 + 2 * u), c, 0, cnt),
                                       out_stat, c, h, w, stream, nullptr, nullptr, nb, 0, 0, nullptr, nullptr, b == 0 ? ++ts_k : 0))) return rc;
+                if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, t2, ubytes, hipMemcpyDeviceToDevice, stream));
                 spare[1] = cur; // t2 becomes current; old current and t1 are free
                 cur = t2;
             } else {
@@ -3541,15 +3561,52 @@ static int layer_index_map(pp_ctx* ctx, const Layer& L, const std::vector<std::s
     int rc = idx > 16777216.f ? pp_fail(ctx, PP_E_ARG, "weight too large for an index map") : pack_layer(ctx, scratch);
     for (size_t h = 0; h < names.size(); ++h) ctx->host_w[names[h]].data.swap(saved[h]);
     if (rc) { if (scratch.w) (void)hipFree(scratch.w); return rc; }
-    size_t bytes = 0;
-    hipError_t e = hipMemPtrGetInfo(scratch.w, &bytes);
-    std::vector<float> image(bytes / sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(image.data(), scratch.w, image.size() * sizeof(float), hipMemcpyDeviceToHost);
+    std::vector<float> image(scratch.w_bytes / sizeof(float));
+    const hipError_t e = hipMemcpy(image.data(), scratch.w, scratch.w_bytes, hipMemcpyDeviceToHost);
     (void)hipFree(scratch.w);
     PP_HIP(e);
     wmap.resize(image.size());
     for (size_t i = 0; i < image.size(); ++i) wmap[i] = (int32_t)image[i] - 1;
     return 0;
+}
+
+// The layout of a conv3x3 layer's fp32 image as a map onto the TRANSFORMED weights: pmap[i] = (row cin + c) T + position of the element
+// of [rows][cin][T] that image element i holds (T = 36 wino6, 16 wino / wino4: position a n + b of U = G g G^T; 9 direct: the tap),
+// -1 for padding.  The Winograd images hold U, not permuted copies of g, so layer_index_map cannot describe them.
+static int layer_position_map(pp_ctx* ctx, const Layer& L, std::vector<int32_t>& pmap, int* T)
+{
+    const Family f = L.var.family;
+    *T = f == Family::Wino6 ? 36 : (f == Family::Wino || f == Family::Wino4) ? 16 : 9;
+    if ((size_t)L.cout * L.cin * *T >= 16777216) return pp_fail(ctx, PP_E_ARG, "weight too large for a position map");
+    Layer scratch = L;
+    scratch.w = nullptr;
+    int rc = pack_layer(ctx, scratch, true);
+    if (rc) { if (scratch.w) (void)hipFree(scratch.w); return rc; }
+    std::vector<float> image(scratch.w_bytes / sizeof(float));
+    const hipError_t e = hipMemcpy(image.data(), scratch.w, scratch.w_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(scratch.w);
+    PP_HIP(e);
+    pmap.resize(image.size());
+    for (size_t i = 0; i < image.size(); ++i) pmap[i] = (int32_t)image[i] - 1;
+    return 0;
+}
+
+// Unit `unit` (0..4) of Resnet block `block` of the committed plan, for pp_update_block_weights (block_train.hip)
+int pp_net_block_image(pp_ctx* ctx, int block, int unit, pp_block_image* img)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    int seen = 0;
+    for (Layer& L : net->layers) {
+        if (L.kind != 0 || L.level != block || L.stride != 1 || seen++ != unit) continue;
+        if (net->eff_prec != 0 || L.var.prec != 0 || L.var.io16 != 0 || L.var.family == Family::Conv16)
+            return pp_fail(ctx, PP_E_ARG, "block weights can be rewritten in place in the fp32 mode only (the committed plan packs them in a 16-bit format)");
+        int rc = layer_position_map(ctx, L, img->pmap, &img->T);
+        if (rc) return rc;
+        img->w = L.w;
+        img->C = L.cin;
+        return L.cin == L.cout ? 0 : pp_fail(ctx, PP_E_ARG, "pp_net_block_image: not a C -> C unit");
+    }
+    return pp_fail(ctx, PP_E_ARG, "pp_net_block_image: no such unit");
 }
 
 int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
@@ -3616,6 +3673,18 @@ extern "C" int pp_backbone_taps(pp_ctx* ctx, const float* canvas, float* rpn_out
     for (int b = 0; b < 3; ++b)
         PP_HIP(hipMemcpyAsync(dst[b], net->tap[b], (size_t)kC[b] * (ctx->H >> b) * (ctx->W >> b) * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return 0;
+}
+
+extern "C" int pp_backbone_block_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* units, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_block_taps: weights not committed");
+    if (!units) return pp_fail(ctx, PP_E_ARG, "pp_backbone_block_taps: null pointer");
+    pp_net* net = (pp_net*)ctx->net;
+    net->unit_tap = units; // pp_backbone_taps checks the rest; the hook is armed for this one pass only
+    int rc = pp_backbone_taps(ctx, canvas, rpn_out, x1, x2, x3, stream_);
+    net->unit_tap = nullptr;
+    return rc;
 }
 
 // Test / inspection hook: copy one tensor of frame `frame` of the LAST pp_infer_batch / pp_infer_frame pass out of the

@@ -135,7 +135,8 @@ void conv16_menu(int stride, int prec, std::vector<Variant>& menu, int io16 = 0)
 void wino6_menu(std::vector<Variant>& menu, bool roofline_layer);
 Variant wino6_strip_v(); // 4 px wide, 64 px tall
 Variant wino6_strip_h(); // 64 px wide, 4 px tall
-void wino6_pack(const float* w /*[rows][cin][3][3]*/, int rows, int cin, std::vector<float>& out);
+// index_positions: instead of U, element k of (row, cin)'s 6 x 6 block holds the float (row cin + c) 36 + k + 1 (the layout read back as a map)
+void wino6_pack(const float* w /*[rows][cin][3][3]*/, int rows, int cin, std::vector<float>& out, bool index_positions = false);
 constexpr int W6_FRONT_PAD = 64; // floats in front of every tensor a wino6 launch reads: its dwordx4 patch pieces start one float before a row
 
 } // namespace ppc

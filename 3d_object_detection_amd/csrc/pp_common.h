@@ -127,6 +127,7 @@ struct pp_ctx {
     uint64_t commit_gen = 0;
     void* trn = nullptr;
     void* neck = nullptr;            // neck backward (neck_train.hip): dZ workspace, dW partials, index maps of the upsampler images
+    void* blk = nullptr;             // Resnet unit backward (block_train.hip): padded a / dz planes, transposed weights, dW partials
     // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
     //      the selected candidates only; f_box / f_dir are then stale until pp_head_materialise runs the full head over the retained
     //      concat buffer and statistics of that pass ----
@@ -242,5 +243,15 @@ struct pp_layer_image {
 };
 int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img);
 void pp_neck_destroy(pp_ctx* ctx);
+// Unit `unit` (0..4 = a..e) of Resnet block `block` (0..2) for pp_update_block_weights (block_train.hip): pmap[i] = (row C + c) T + pos
+// names the element of the TRANSFORMED weight [C][C][T] that image element i holds (T = 36 | 16: position of U = G g G^T of the
+// Winograd families; 9: the tap of the direct tilings), -1 for padding.  fp32 images only (PP_E_ARG otherwise).
+struct pp_block_image {
+    float* w = nullptr;
+    int C = 0, T = 0;
+    std::vector<int32_t> pmap;
+};
+int pp_net_block_image(pp_ctx* ctx, int block, int unit, pp_block_image* img);
+void pp_block_destroy(pp_ctx* ctx);
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -786,7 +786,7 @@ Variant wino6_strip_h() { return make_wino6<16, false>(false); } // 64 px wide, 
 
 // Transformed weights U = G g G^T (fp64 on the host, rounded once) in the order the waves fetch them:
 //   [cout block][k-step][wave][local position][lane = (cin quad lane kq) * 16 + m][M-tile]  =  U[block*64 + mt*16 + m][4 s + kq][i][jj]
-void wino6_pack(const float* w /*[rows][cin][3][3]*/, int rows, int cin, std::vector<float>& out)
+void wino6_pack(const float* w /*[rows][cin][3][3]*/, int rows, int cin, std::vector<float>& out, bool index_positions)
 {
     static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
@@ -801,6 +801,8 @@ void wino6_pack(const float* w /*[rows][cin][3][3]*/, int rows, int cin, std::ve
                 for (int j = 0; j < 3; ++j) t[a][j] = G[a][0] * g[0 * 3 + j] + G[a][1] * g[1 * 3 + j] + G[a][2] * g[2 * 3 + j];
             for (int a = 0; a < 6; ++a)
                 for (int b = 0; b < 6; ++b) u[a * 6 + b] = (float)(t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2]);
+            if (index_positions)
+                for (int k = 0; k < 36; ++k) u[k] = (float)(((size_t)row * cin + c) * 36 + k + 1);
             const int blk = row / 64, mt = (row % 64) / 16, mm = row % 16, s = c / 4, kq = c % 4;
             for (int wv = 0; wv < 4; ++wv)
                 for (int j = 0; j < 9; ++j) {

@@ -472,6 +472,71 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_neck_weights(self.ctx, *[_ptr(t) for t in args], _stream()), self.ctx, "pp_update_neck_weights")
 
+    # ------------------------------------------------------------------ Resnet unit backward (block_train.hip)
+    BLOCK3_KEYS = ("rpn.block3.3.conv_block.2.weight", "rpn.block3.3.conv_block.5.weight", "rpn.block3.4.conv_block.2.weight",
+                   "rpn.block3.4.conv_block.5.weight", "rpn.block3.5.conv_block.2.weight")
+
+    def unit_backward(self, u, w, dy, dskip=None, need_du=True):
+        """pp_unit_backward: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
+        dy (dL/d(conv output)) and the optional dskip (added to du: the residual path around the unit) are [nb,C,h,w], w [C,C,3,3] ->
+        (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  fp32, deterministic, stateless."""
+        if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
+            raise ValueError(f"unit_backward: u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb, C, h, wd = (int(v) for v in u.shape)
+        if C not in (64, 128, 256):
+            raise ValueError(f"unit_backward: C must be 64, 128 or 256, got {C}")
+        if h < 1 or wd < 1 or h * wd < 2:
+            raise ValueError(f"unit_backward: the map needs at least two elements, got {h} x {wd}")
+        u = _chk(u, torch.float32, (nb, C, h, wd), "unit_backward: u")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), "unit_backward: w")
+        dy = _chk(dy, torch.float32, (nb, C, h, wd), "unit_backward: dy")
+        ts = [(u, "u"), (w, "w"), (dy, "dy")]
+        if dskip is not None:
+            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), "unit_backward: dskip")
+            ts.append((dskip, "dskip"))
+        for t, what in ts:
+            if t.device != self.device:
+                raise ValueError(f"unit_backward: {what} is on {t.device}, the engine on {self.device}")
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
+        dw = self._t((C, C, 3, 3), torch.float32)
+        du = self._t((nb, C, h, wd), torch.float32) if need_du else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_unit_backward(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(dy), _ptr(dskip), nb, _ptr(dw), _ptr(du), _stream()),
+                       self.ctx, "pp_unit_backward")
+        return dw, du
+
+    def backbone_block_taps(self, canvas):
+        """pp_backbone_block_taps: backbone_taps(canvas) plus the inputs of block 3's five units -> (rpn_out, x1, x2, x3,
+        units [5,256,H/4,W/4] = h, m3, r3, m4, r4 in the order of BLOCK3_KEYS).  fp32 mode only."""
+        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
+            raise ValueError("backbone_block_taps: expected a contiguous canvas")
+        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
+             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_block_taps: canvas [1,64,gx,gy]")
+        out = self._t((1, 320, self.H, self.W), torch.float32)
+        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        units = self._t((5,) + self.neck_shapes(2)[0], torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_backbone_block_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]),
+                                                       _ptr(units), _stream()), self.ctx, "pp_backbone_block_taps")
+        return (out, *taps, units)
+
+    def update_block_weights(self, params):
+        """pp_update_block_weights: {state_dict name: device tensor} of BLOCK3_KEYS -> the committed images of block 3's five
+        convolutions, in place on the current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
+        args = []
+        for k in self.BLOCK3_KEYS:
+            if k not in params:
+                raise KeyError(f"update_block_weights: {k} is missing")
+            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
+            t = _chk(t, torch.float32, (256, 256, 3, 3), "update_block_weights: " + k)
+            if t.device != self.device:
+                raise ValueError(f"update_block_weights: {k} is on {t.device}, the engine on {self.device}")
+            args.append(t)
+        ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in args])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_block_weights(self.ctx, 2, ptrs, 5, _stream()), self.ctx, "pp_update_block_weights")
+
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1 + _lib.PP_MAX_CLASSES,), dtype=torch.int32, device=self.device)

@@ -314,6 +314,46 @@ int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const float* w, co
  * pp_effective_precision != 0, and before the first commit. */
 int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const float* w3, void* stream);
 
+/* ---- Resnet unit backward (block_train.hip): the primitive of every Resnet2 module's backward ----
+ * The backbone's stride-1 layers are all one unit, InstanceNorm2d(eps 1e-3, no affine) -> ReLU -> Conv2d(C -> C, 3 x 3, pad 1, no bias)
+ * (pointpillars8_shared.py:418-431).  Per frame and input channel, N = h w: mean and rstd = 1 / sqrt(biased var + 1e-3) come from fp64
+ * sums over u, xhat = (u - mean) rstd, a = max(xhat, 0), z = conv(a, w).  fp32 whatever pp_set_precision says, InstanceNorm backbone
+ * only.  Deterministic: no atomics, two runs are bit-identical.
+ *
+ * pp_unit_backward: backward of one unit for nb <= max_batch frames.  Stateless: the result depends on the arguments only, not on the
+ * context's last pass or committed weights.  C is 64, 128 or 256; h, w >= 1 with h w >= 2.  u (the unit's input), dy (= dL/dz), dskip
+ * and du are f32[nb][C][h][w], w DEVICE f32[C][C][3][3] (state_dict layout, 16-byte aligned) ->
+ * dw[co][ci][ky][kx] = sum_{frames, p} dy[co, p] a[ci, py + ky - 1, px + kx - 1], f32[C][C][3][3] summed over the frames, fully written,
+ * and du = rstd (Gr - sum(Gr) / N - xhat sum(Gr xhat) / N) + dskip with da[ci, q] = sum_{co, ky, kx} w[co][ci][ky][kx] dy[co, qy - ky + 1,
+ * qx - kx + 1] and Gr = da [a > 0]; the mask is that of the a this call materialises, so dw and du see the same activation.  dskip may
+ * be NULL (nothing is added; otherwise it is one fp32 add behind the rounded norm backward: the gradient of a residual connection
+ * around the unit).  du NULL: the dgrad product and the norm backward are not run.  Both products are fp32-input MFMA GEMMs over
+ * zero-haloed copies of a and dy in a workspace (allocated on first use, at most 256 MB: larger batches run in frame chunks; a map
+ * whose single frame exceeds it is PP_E_ARG).  dw is tiled over workgroups and its K range (frames x positions) split into a fixed
+ * number of ranges whose partials are summed in index order in double, so dw depends on nb within fp32 summation error; a frame's du
+ * does not depend on nb at all.  The dgrad sums its K = 9 C terms in blocks of 64 from zero and adds the block sums in a fixed order.
+ * The workspace belongs to the context, so "stateless" is about values, not about concurrency: calls on one context must be issued in
+ * order on one stream (or ordered by events), like every other call that takes a pp_ctx.  A call that has to enlarge the workspace
+ * waits for the whole device before it frees the old one.
+ * PP_E_ARG for a null pointer, C outside the three, sizes out of range, nb outside 1..max_batch, a misaligned w and the BatchNorm
+ * backbone. */
+int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip /* may be NULL */,
+                     int nb, float* dw, float* du /* NULL: skipped */, void* stream);
+/* pp_backbone_taps plus the inputs of the five units of block 3 (the deepest block: h -> r3 = h + U_b(U_a(h)), r4 = r3 + U_d(U_c(r3)),
+ * x3 = r4 + U_e(r4), weights rpn.block3.{3,3,4,4,5}.conv_block.{2,5,2,5,2}.weight): units f32[5][256][H/4][W/4] = h, m3 = U_a(h), r3,
+ * m4 = U_c(r3), r4, each copied out behind the launch that produces it (the level buffers are reused inside a block).  rpn_out, x1, x2
+ * and x3 match pp_backbone bit for bit.  fp32 mode only, as pp_backbone_taps. */
+int pp_backbone_block_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* units, void* stream);
+/* After an optimizer step: the five DEVICE tensors f32[256][256][3][3] of block 3 in unit order a..e (state_dict layout) -> the packed
+ * weight images of those five layers of the committed launch plan, rewritten in place on `stream` (no host copy, no re-tuning).  block
+ * must be 2 (block 3) and n 5: PP_E_ARG for the other blocks (they have no backward yet, and level 0 carries the tile-skipping path).
+ * The Winograd tilings' images hold U = G g G^T, which a device kernel evaluates from g in fp64 in the host packer's own expression
+ * order and rounds once, so the images equal those of a fresh commit of the same values bit for bit; the direct tilings' images are
+ * permuted copies.  The strip tilings share the main image.  pp_backbone*, pp_infer_frame and pp_infer_batch all see the new weights.
+ * The first call after a commit reads the images' layout back once (synchronous).  The host copies of pp_load_weights are NOT changed.
+ * fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and before the first commit. */
+int pp_update_block_weights(pp_ctx* ctx, int block, const float* const* w, int n, void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);
