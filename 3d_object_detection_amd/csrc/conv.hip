@@ -1,29 +1,10 @@
-// 2D backbone (RPN) + shared head as fp32 MFMA implicit GEMMs for gfx950.
-// Reference: networks/pointpillars8_shared.py:114-181 (RPN), :299-343 (SharedHead),
-// :418-431 (Resnet2); BatchNorm variant networks/pointpillars8_export.py:54-119.
-//
-// One kernel template covers conv3x3 (stride 1/2), ConvTranspose(k == stride) and the 1x1 head:
-//
-//   D[cout, pixel] = sum_k  Wt[cout, k] * X[k, pixel]        k = (tap, cin)
-//
-// * MFMA: v_mfma_f32_16x16x4_f32 (exact fp32, k-ordered fma chain).  M = 16 output channels,
-//   N = 16 output pixels, K = 4 input channels of one filter tap.  Pixels sit on the LANE axis of
-//   the C/D layout (col = lane&15), channels in the 4 accumulator registers, so one store
-//   instruction writes 16 consecutive pixels of a channel (NCHW, coalesced) and the per-channel
-//   InstanceNorm statistics reduce with 4 xor-shuffles.
-// * Tensors stay NCHW (the reference layout): for a fixed (cin, tap) the 16 pixels of an N-tile are
-//   contiguous in the LDS patch, so the B-operand read is one conflict-free ds_read_b32.
-// * No im2col: each workgroup stages a [KC][IH][IW] input patch with halo ONCE per channel chunk
-//   and walks the 9 taps as shifted windows of it.  Zero padding, the producer's normalisation
-//   (InstanceNorm / folded BatchNorm as x*scale+shift) and ReLU are applied while staging, so
-//   normalised activations are never materialised in HBM.
-// * InstanceNorm2d(eps=1e-3, affine=False) needs full-plane statistics of every conv output: the
-//   epilogue reduces sum / sum-of-squares per channel (fp32 over <= 64 pixels, then fp64) and adds
-//   them to 8 replicated fp64 accumulators; the CONSUMER kernel turns them into (scale, shift) in
-//   its prologue.  No separate statistics pass, no finalize launch.
-// * ConvTranspose(k = s, stride = s) is a 1x1 conv onto Cout*s*s virtual channels whose epilogue
-//   pixel-shuffles (float2 / float4 stores); the three upsampled maps land in one [320,H,W]
-//   buffer, so the concat is free and the head normalises + ReLUs them in its prologue.
+// 2D backbone (RPN) + shared head: the host side.  The MFMA kernels live one family per file -- conv_direct.hip (conv_mfma),
+// wino2.hip (wino_mfma), wino4.hip (wino4_mfma), gemm1x1.hip (gemm1x1), conv16.hip and wino6.hip -- and export their tilings as
+// menu functions through conv_common.h.  This file holds everything that is per network and not per kernel: the layer table
+// (Layer, NormRef, pp_net), layer_menu (the families' menus composed per layer shape and precision), the per-family rules of the
+// tuner and the launcher, the weight packer (pack_layer: every family's image, read back as a map by the training code), launch_conv,
+// the tuner and its cache, create / commit / run, the C ABI and the debug and profile hooks.  Its own kernels are the five small
+// ones around the layers: norm_relu_stats, norm_finalize, f32_to_f16, fill_pattern and dbg_reduce_stats.
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
@@ -37,2009 +18,6 @@
 namespace {
 
 using namespace ppc;
-
-template <int KS, int STRIDE, int TW, int WM, int WN, int MT, int NT, int BTX, int KC, int EPI>
-struct ConvCfg {
-    static constexpr int TH = 16 / TW;
-    static constexpr int TILES = WN * NT;
-    static constexpr int BTY = TILES / BTX;
-    static constexpr int PW = BTX * TW, PH = BTY * TH;
-    static constexpr int IW = (PW - 1) * STRIDE + KS, IH = (PH - 1) * STRIDE + KS;
-    static constexpr int HALF = (IW + 1) / 2; // stride 2: even columns first, odd columns after (de-interleaved)
-    static constexpr int iwp()
-    {
-        int v = IW;
-        if (TW == 16) return v;
-        while ((STRIDE * v) % 32 != TW) ++v; // the TH rows of an N-tile land on disjoint bank groups
-        return v;
-    }
-    static constexpr int IWP = iwp();
-    static constexpr int cs()
-    {
-        int v = IH * IWP;
-        while (v % 32 != 16) ++v; // channel c+1 (lanes 16-31 / 48-63) is 16 banks away from channel c
-        return v;
-    }
-    static constexpr int CS = cs();
-    static constexpr int BM = WM * MT * 16;
-    static constexpr int BMP = BM + ((BM % 32 == 0) ? 16 : 0);
-    static constexpr int THREADS = 64 * WM * WN;
-    static constexpr int NPOS = IH * IW;                          // patch positions per channel
-    static constexpr int PR = (NPOS + THREADS - 1) / THREADS;     // positions per thread
-    static constexpr int W4 = KS * KS * KC * BMP / 4;             // float4 per weight chunk image
-    static constexpr int WR = (W4 + THREADS - 1) / THREADS;
-    static constexpr int LDS_IN = KC * CS;
-    static constexpr int LDS_W = KS * KS * KC * BMP;
-    static constexpr int LDS_FLOATS = 2 * (LDS_IN + LDS_W) + 2 * 320 + 2 * WN * BM;
-    static_assert(TILES % BTX == 0, "tiles must form a rectangle");
-    static_assert(KC % 4 == 0, "KC multiple of the MFMA K");
-    static_assert((KS * KS * KC * BMP) % 4 == 0 && LDS_IN % 4 == 0, "float4 staging");
-};
-
-// Software pipeline per channel chunk (one barrier per chunk):
-//   global loads of chunk c+1 -> registers   (in flight during the MFMAs)
-//   MFMAs of chunk c from LDS buffer c&1
-//   registers -> LDS buffer (c+1)&1 (normalise + ReLU + zero padding applied here)
-//   barrier
-template <int KS, int STRIDE, int TW, int WM, int WN, int MT, int NT, int BTX, int KC, int EPI>
-__global__ void __launch_bounds__(64 * WM * WN) conv_mfma(const ConvP p)
-{
-    using C = ConvCfg<KS, STRIDE, TW, WM, WN, MT, NT, BTX, KC, EPI>;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* il = smem;                          // [2][KC][CS]
-    float* wl = il + 2 * C::LDS_IN;            // [2][KS*KS][KC][BMP]
-    float* scl = wl + 2 * C::LDS_W;            // [320] scale
-    float* shl = scl + 320;                    // [320] shift
-    float* red = shl + 320;                    // [WN][BM][2]
-    // frame of this workgroup (batched launch)
-    const BlockId bid = xcd_block_id();
-    const size_t fz = bid.z;
-    const float* __restrict__ gin = p.in + fz * p.in_fs;
-    float* __restrict__ gout = p.out + fz * p.out_fs;
-    const float* __restrict__ gres = p.res ? p.res + fz * p.res_fs : nullptr;
-    const double* __restrict__ gpre = p.pre_acc ? p.pre_acc + fz * p.pre_fs : nullptr;
-    double* __restrict__ gstat = p.stat_acc ? p.stat_acc + fz * p.stat_fs : nullptr;
-    float* __restrict__ gbox = p.out_box ? p.out_box + fz * p.box_fs : nullptr;
-    float* __restrict__ gdir = p.out_dir ? p.out_dir + fz * p.dir_fs : nullptr;
-    (void)gbox; (void)gdir;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int m = lane & 15, kq = lane >> 4;
-
-    const int nbx = (p.Wout + C::PW - 1) / C::PW;
-    const int bx = bid.x % nbx, by = bid.x / nbx;
-    const int co0 = bid.y * C::BM;
-    const int ox0 = bx * C::PW, oy0 = by * C::PH;
-    const int ix0 = ox0 * STRIDE - KS / 2, iy0 = oy0 * STRIDE - KS / 2;
-
-    // ---- prologue: per-input-channel (scale, shift) of the producer's normalisation ----
-    if (p.pre == PRE_STATS) {
-        for (int c = tid; c < p.Cin; c += C::THREADS) {
-            double s = 0.0, q = 0.0;
-#pragma unroll
-            for (int r = 0; r < NREP; ++r) {
-                s += gpre[((size_t)r * p.Cin + c) * 2];
-                q += gpre[((size_t)r * p.Cin + c) * 2 + 1];
-            }
-            double mean = s * p.pre_inv_n;
-            double var = q * p.pre_inv_n - mean * mean;
-            var = var > 0.0 ? var : 0.0;
-            double rstd = 1.0 / sqrt(var + (double)p.eps);
-            scl[c] = (float)rstd;
-            shl[c] = (float)(-mean * rstd);
-        }
-    } else if (p.pre == PRE_AFFINE) {
-        for (int c = tid; c < p.Cin; c += C::THREADS) {
-            scl[c] = p.pre_scale[fz * p.aff_fs + c];
-            shl[c] = p.pre_shift[fz * p.aff_fs + c];
-        }
-    }
-
-    // ---- per-thread staging map: position -> (global offset in a channel plane, LDS offset) ----
-    // Loads are UNCONDITIONAL (out-of-image positions read offset 0 of the plane and are zeroed when
-    // written to LDS): a per-element "load or 0" select makes hipcc branch around every load.
-    int goff[C::PR], loff[C::PR];
-    unsigned vmask = 0u;
-#pragma unroll
-    for (int r = 0; r < C::PR; ++r) {
-        const int pos = tid + r * C::THREADS;
-        const int iy = pos / C::IW, ix = pos - iy * C::IW;
-        const int gy = iy0 + iy, gx = ix0 + ix;
-        const bool inb = pos < C::NPOS && gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
-        goff[r] = inb ? gy * p.Win + gx : 0;
-        vmask |= (inb ? 1u : 0u) << r;
-        const int col = (STRIDE == 2) ? ((ix & 1) * C::HALF + (ix >> 1)) : ix;
-        loff[r] = pos < C::NPOS ? iy * C::IWP + col : -1;
-    }
-
-    // lane's pixel base inside the LDS patch for each of its N-tiles
-    int toff[NT];
-    int opx[NT], opy[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int t = wn * NT + nt;
-        const int tx = t % BTX, ty = t / BTX;
-        const int px = tx * TW + (m % TW), py = ty * C::TH + (m / TW);
-        opx[nt] = ox0 + px;
-        opy[nt] = oy0 + py;
-        toff[nt] = (py * STRIDE) * C::IWP + px + kq * C::CS; // stride 2: px indexes the even-column plane
-    }
-    const int aoff = kq * C::BMP + wm * MT * 16 + m;
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    const size_t in_plane = (size_t)p.Hin * p.Win;
-    int nchunk = p.Cin / KC;
-    // Sparse BEV input (first conv): each staged position carries the pillar id of its cell; channels come from
-    // the [P][64] PFN rows.  A workgroup whose whole halo patch is empty has an all-zero output: skip its MFMA loop.
-    const bool sparse = p.pmap != nullptr;
-    int pid[C::PR];
-    const float* gfeat = nullptr;
-    if (sparse) {
-        const int32_t* gmap = p.pmap + fz * p.pmap_fs;
-        gfeat = p.feat + fz * p.feat_fs;
-        int any = 0;
-#pragma unroll
-        for (int r = 0; r < C::PR; ++r) {
-            pid[r] = ((vmask >> r) & 1u) ? gmap[goff[r]] : -1;
-            any |= (pid[r] >= 0);
-            if (pid[r] < 0) vmask &= ~(1u << r);
-            goff[r] = pid[r] >= 0 ? pid[r] * 64 : 0; // reuse goff as the row offset into feat
-        }
-        if (!__syncthreads_or(any)) nchunk = 0;
-    }
-    const float4* wsrc = reinterpret_cast<const float4*>(p.w) + (size_t)bid.y * (p.Cin / KC) * C::W4;
-
-    float xv[C::PR][KC];
-    f32x4 wv[C::WR];
-    const f32x4* wsrc4 = reinterpret_cast<const f32x4*>(wsrc);
-
-#define PP_LOAD_CHUNK(CH)                                                                        \
-    {                                                                                            \
-        if (sparse) {                                                                            \
-            const float* fb_ = gfeat + (CH) * KC;                                                \
-            _Pragma("unroll") for (int r = 0; r < C::PR; ++r)                                    \
-                _Pragma("unroll") for (int c = 0; c < KC; ++c) xv[r][c] = fb_[goff[r] + c];      \
-        } else {                                                                                 \
-            const float* base_ = gin + (size_t)((CH) * KC) * in_plane;                           \
-            _Pragma("unroll") for (int r = 0; r < C::PR; ++r)                                    \
-                _Pragma("unroll") for (int c = 0; c < KC; ++c) xv[r][c] = base_[(size_t)c * in_plane + goff[r]]; \
-        }                                                                                        \
-        const f32x4* g_ = wsrc4 + (size_t)(CH) * C::W4;                                          \
-        _Pragma("unroll") for (int r = 0; r < C::WR; ++r) {                                      \
-            const int e_ = tid + r * C::THREADS;                                                 \
-            wv[r] = g_[e_ < C::W4 ? e_ : C::W4 - 1];                                             \
-        }                                                                                        \
-    }
-#define PP_STORE_CHUNK(CH, BUF)                                                                  \
-    {                                                                                            \
-        float* ib_ = il + (BUF) * C::LDS_IN;                                                     \
-        const int c0_ = (CH) * KC;                                                               \
-        _Pragma("unroll") for (int r = 0; r < C::PR; ++r) {                                      \
-            if (loff[r] >= 0) {                                                                  \
-                const bool inb_ = (vmask >> r) & 1u;                                             \
-                _Pragma("unroll") for (int c = 0; c < KC; ++c) {                                 \
-                    float v_ = xv[r][c];                                                         \
-                    if (p.pre != PRE_RAW) v_ = fmaxf(fmaf(v_, scl[c0_ + c], shl[c0_ + c]), 0.f); \
-                    ib_[c * C::CS + loff[r]] = inb_ ? v_ : 0.f;                                  \
-                }                                                                                \
-            }                                                                                    \
-        }                                                                                        \
-        f32x4* wb_ = reinterpret_cast<f32x4*>(wl + (BUF) * C::LDS_W);                            \
-        _Pragma("unroll") for (int r = 0; r < C::WR; ++r) {                                      \
-            const int e_ = tid + r * C::THREADS;                                                 \
-            if (e_ < C::W4) wb_[e_] = wv[r];                                                     \
-        }                                                                                        \
-    }
-
-    // One register set holds the NEXT chunk: it is written to the other LDS buffer right AFTER the barrier that opens a
-    // chunk (its loads were issued a whole chunk earlier, so the wait is free), and the loads of chunk ch+2 are
-    // re-issued at once -- they have the MFMA steps of this chunk plus the barrier to land.  (Writing at the END of
-    // the chunk, as the first version did, gave the loads only the chunk's own MFMA time and exposed the rest.)
-    if (nchunk > 0) PP_LOAD_CHUNK(0)
-    __syncthreads(); // scl/shl visible
-    if (nchunk > 0) PP_STORE_CHUNK(0, 0)
-    if (nchunk > 1) PP_LOAD_CHUNK(1)
-    __syncthreads();
-
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int buf = ch & 1;
-        __builtin_amdgcn_s_setprio(1);
-        if (ch + 1 < nchunk) {
-            PP_STORE_CHUNK(ch + 1, buf ^ 1)
-            if (ch + 2 < nchunk) PP_LOAD_CHUNK(ch + 2)
-        }
-        const float* ib = il + buf * C::LDS_IN;
-        const float* wb = wl + buf * C::LDS_W;
-        // Operand reads run ONE STEP AHEAD of the MFMAs that consume them (two register sets, order
-        // pinned with sched_barrier): left alone, hipcc issues each step's ds_reads right before its
-        // MFMAs and every step eats the LDS latency.
-        constexpr int NS = KS * KS * (KC / 4);
-        float a[2][MT], b[2][NT];
-#define PP_LOAD_OPS(S, SET)                                                                          \
-    {                                                                                                \
-        constexpr int tap_ = (S) / (KC / 4), c4_ = (S) % (KC / 4);                                   \
-        constexpr int ky_ = tap_ / KS, kx_ = tap_ % KS;                                              \
-        constexpr int tapoff_ = ky_ * C::IWP + ((STRIDE == 2) ? ((kx_ & 1) * C::HALF + (kx_ >> 1)) : kx_); \
-        _Pragma("unroll") for (int i = 0; i < MT; ++i) a[SET][i] = wb[(tap_ * KC + c4_ * 4) * C::BMP + aoff + i * 16]; \
-        _Pragma("unroll") for (int j = 0; j < NT; ++j) b[SET][j] = ib[toff[j] + c4_ * 4 * C::CS + tapoff_]; \
-    }
-        PP_LOAD_OPS(0, 0)
-        __builtin_amdgcn_s_setprio(0);
-        pp_steps<0, NS>([&](auto S) {
-            constexpr int s_ = decltype(S)::value;
-            constexpr int cur = s_ & 1;
-            if constexpr (s_ + 1 < NS) PP_LOAD_OPS(s_ + 1, cur ^ 1)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-#undef PP_LOAD_OPS
-        __syncthreads();
-    }
-    __builtin_amdgcn_s_setprio(1); // epilogue
-
-    // ---- epilogue ----
-    const size_t out_plane = (size_t)p.Hout * p.Wout;
-    float ssum[MT][4], ssq[MT][4];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { ssum[i][r] = 0.f; ssq[i][r] = 0.f; }
-
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int row0 = co0 + wm * MT * 16 + i * 16 + kq * 4; // first of this lane's 4 rows
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const bool ok = (opx[j] < p.Wout) && (opy[j] < p.Hout) && (row0 < p.Cout);
-            if (!ok) continue;
-            const size_t pix = (size_t)opy[j] * p.Wout + opx[j];
-            f32x4 v = acc[i][j];
-            if (EPI == EPI_PLAIN) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const size_t o = (size_t)(row0 + r) * out_plane + pix;
-                    float x = v[r];
-                    if (gres) x += gres[o];
-                    gout[o] = x;
-                    ssum[i][r] += x;
-                    ssq[i][r] += x * x;
-                }
-            } else if (EPI == EPI_UP2) { // rows (co*4 + dy*2 + dx) -> out[co][2y+dy][2x+dx]
-                const int co = row0 >> 2;
-                const size_t W2 = (size_t)p.Wout * 2;
-                float* o = gout + (size_t)co * out_plane * 4 + (size_t)(2 * opy[j]) * W2 + 2 * opx[j];
-                *reinterpret_cast<float2*>(o) = make_float2(v[0], v[1]);
-                *reinterpret_cast<float2*>(o + W2) = make_float2(v[2], v[3]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { ssum[i][0] += v[r]; ssq[i][0] += v[r] * v[r]; }
-            } else if (EPI == EPI_UP4) { // rows (co*16 + dy*4 + dx) -> out[co][4y+dy][4x+dx]
-                const int co = row0 >> 4, dy = (row0 >> 2) & 3;
-                const size_t W4o = (size_t)p.Wout * 4;
-                float* o = gout + (size_t)co * out_plane * 16 + (size_t)(4 * opy[j] + dy) * W4o + 4 * opx[j];
-                *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { ssum[i][0] += v[r]; ssq[i][0] += v[r] * v[r]; }
-            } else { // EPI_HEAD: rows = [cls 9 | box 63 | dir 18], outputs ordered (anchor, x, y[, code])
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = row0 + r;
-                    if (row >= p.n_rows) continue;
-                    const float x = v[r] + p.bias[row];
-                    if (row < p.n_cls) {
-                        gout[(size_t)row * out_plane + pix] = x;
-                    } else if (row < p.n_cls + p.n_box) {
-                        const int q = row - p.n_cls, a = q / 7, k = q - a * 7;
-                        gbox[((size_t)a * out_plane + pix) * 7 + k] = x;
-                    } else {
-                        const int q = row - p.n_cls - p.n_box, a = q >> 1, k = q & 1;
-                        gdir[((size_t)a * out_plane + pix) * 2 + k] = x;
-                    }
-                }
-            }
-        }
-    }
-
-    if (EPI != EPI_HEAD && gstat) {
-        // reduce over the 16 pixel lanes, then over the WN waves through LDS, then fp64 atomics
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s = ssum[i][r], q = ssq[i][r];
-                s = row16_sum(s);
-                q = row16_sum(q);
-                if (m == 0) {
-                    const int lr = wm * MT * 16 + i * 16 + kq * 4 + r; // local row
-                    red[(wn * C::BM + lr) * 2] = s;
-                    red[(wn * C::BM + lr) * 2 + 1] = q;
-                }
-            }
-        __syncthreads();
-        for (int lr = tid; lr < C::BM; lr += C::THREADS) {
-            const int row = co0 + lr;
-            if (row >= p.Cout) continue;
-            double s = 0.0, q = 0.0;
-#pragma unroll
-            for (int w = 0; w < WN; ++w) {
-                s += (double)red[(w * C::BM + lr) * 2];
-                q += (double)red[(w * C::BM + lr) * 2 + 1];
-            }
-            int ch;
-            if (EPI == EPI_UP2) { if (lr & 3) continue; ch = row >> 2; }
-            else if (EPI == EPI_UP4) { if (lr & 3) continue; ch = row >> 4; }
-            else ch = row;
-            double* dst = gstat + ((size_t)(blockIdx.x % NREP) * p.stat_C + ch) * 2;
-            atomicAdd(dst, s);
-            atomicAdd(dst + 1, q);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Winograd F(2x2, 3x3) for the stride-1 3x3 convs (13 of the 16 convs, 141 of the 203 GFLOP):
-//   Y = A^T [ sum_cin (G g G^T) (.) (B^T d B) ] A      -> 16 MFMA "positions" instead of 9 taps per
-// 2x2 output tile, i.e. 2.25x fewer MFMAs, still exact-fp32 MFMA accumulation.
-// * one lane = one 2x2 output tile (N-tile = 16 tiles, TWT x 16/TWT), M = 16 output channels
-// * the weights are transformed on the host (fp64) and staged as a [16][KC][rows] LDS image
-// * the INPUT transform runs in registers: each lane reads the 4x4 raw patch of its tile from the
-//   same normalised/ReLU'd/zero-padded LDS patch the direct kernel uses (columns de-interleaved so the
-//   stride-2 tile walk is bank-conflict free) and forms its 16 B-operands with 32 adds -- no second
-//   LDS pass, no extra barrier
-// * the OUTPUT transform is per lane too (the 16 positions of a tile are 16 accumulators of one lane)
-// ------------------------------------------------------------------------------------------
-constexpr int WINO_PER = 2;  // minimum LDS write pieces per MFMA step of the staging pipeline (2: +0.3 % over 1, 4: -1.5 %)
-constexpr int WINO_AD = 6;   // steps the A-operand LDS reads run ahead of their MFMA pair
-constexpr int WINO_PRIO = 1; // s_setprio level of the NON-MFMA segments (chunk opening, epilogue, tile prologue) of the Winograd loop
-template <int TWT, int WM, int WN, int BTX, int KC>
-struct WinoCfg {
-    static constexpr int THT = 16 / TWT;
-    static constexpr int MT = 2;
-    static constexpr int BTY = WN / BTX;
-    static constexpr int PW = BTX * TWT * 2, PH = BTY * THT * 2;
-    static constexpr int IW = PW + 2, IH = PH + 2;
-    static constexpr int HALF = (IW + 1) / 2;
-    static constexpr int iwp()
-    {
-        int v = IW;
-        if (TWT == 16) return v;
-        while ((2 * v) % 32 != TWT) ++v;
-        return v;
-    }
-    static constexpr int IWP = iwp();
-    static constexpr int cs()
-    {
-        int v = IH * IWP;
-        while (v % 32 != 16) ++v;
-        return v;
-    }
-    static constexpr int CS = cs();
-    static constexpr int BM = WM * MT * 16;
-    // A image row = [wm][m 0..15][M-tile 0/1]: one ds_read_b64 fetches a lane's two A operands; a 32-float row needs no
-    // padding (kq and kq+1 fall on opposite 32-bank halves of the 64-bank b64 access), a 64-float row is padded by 32
-    static constexpr int BMP = (BM == 32) ? 32 : BM + 32;
-    static constexpr int THREADS = 64 * WM * WN;
-    static constexpr int NPOS = IH * IW;
-    static constexpr int PR = (NPOS + THREADS - 1) / THREADS;
-    static constexpr int W4 = 16 * KC * BMP / 4;
-    static constexpr int WR = (W4 + THREADS - 1) / THREADS;
-    static constexpr int LDS_IN = KC * CS;
-    static constexpr int LDS_W = 16 * KC * BMP;
-    static constexpr int LDS_FLOATS = 2 * (LDS_IN + LDS_W) + 2 * 320 + 2 * WN * BM;
-    static_assert(WN % BTX == 0, "tiles must form a rectangle");
-};
-
-// ROOFLINE: 1 instantiates a second, identical copy of the kernel for the roofline layer (3x3 s1 64->64 on the level-0
-// map) only, so that a kernel trace / --stats summary has that layer's launches under their own symbol instead of
-// averaged with the other layers the tuner gives the same tiling.
-template <int TWT, int WM, int WN, int BTX, int KC, int ROOFLINE = 0>
-__global__ void __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) wino_mfma(const ConvP p)
-{
-    using C = WinoCfg<TWT, WM, WN, BTX, KC>;
-    constexpr int MT = 2;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* il = smem;
-    float* wl = il + 2 * C::LDS_IN;
-    float* scl = wl + 2 * C::LDS_W;
-    float* shl = scl + 320;
-    float* red = shl + 320;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int m = lane & 15, kq = lane >> 4;
-
-    // PERSISTENT: two workgroups per CU walk the (cout block, tile, frame) list.  Workgroups are dealt round-robin
-    // over the 8 XCDs, so XCD k takes the k-th contiguous eighth of the list (cout blocks of a tile and
-    // neighbouring tiles meet in one L2) and its workgroups stride through that eighth.  Per tile this saves the
-    // launch slot + scale/shift prologue of a fresh workgroup, and the next tile's first loads are in flight while
-    // the stores of this tile's epilogue drain.
-    const int nbx = (p.Wout + C::PW - 1) / C::PW, nby = (p.Hout + C::PH - 1) / C::PH;
-    const int ntile = nbx * nby, ncb = (p.Cout + C::BM - 1) / C::BM;
-    const int total = ntile * ncb * p.nb;
-    const int per = (total + 7) >> 3;
-    const int xk = blockIdx.x & 7, xj = blockIdx.x >> 3, nloc = gridDim.x >> 3;
-    const int lin_end = min(total, (xk + 1) * per);
-    // ---- load-side state: the tile whose global loads are being issued.  It runs one tile AHEAD of the compute
-    //      side at a tile boundary: the next tile's first chunk is requested before this tile's epilogue, so its
-    //      latency hides under the output transform and stores.
-    int goff[C::PR], loff[C::PR];
-    unsigned vmask = 0u;
-    bool all_in = false;
-    __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, 0x7FFFFFFF, 0x00020000);
-    const unsigned plane_b = (unsigned)(p.Hin * p.Win) * 4u;
-    unsigned wbase_b = 0u;
-    float xv[C::PR][KC];
-    f32x4 wv[C::WR];
-#pragma unroll
-    for (int r = 0; r < C::PR; ++r) {
-        // threads past the patch's last position duplicate it (same load, same value to the same LDS word):
-        // every staging instruction is unconditional, the MFMA stream stays one basic block
-        const int pos = min(tid + r * C::THREADS, C::NPOS - 1);
-        const int iy = pos / C::IW, ix = pos - iy * C::IW;
-        loff[r] = iy * C::IWP + (ix & 1) * C::HALF + (ix >> 1);
-    }
-    auto set_load_tile = [&](int l) {
-        const int cb_ = l % ncb, t_ = (l / ncb) % ntile, f_ = l / (ncb * ntile);
-        const int iy0_ = (t_ / nbx) * C::PH - 1, ix0_ = (t_ % nbx) * C::PW - 1;
-        vmask = 0u;
-#pragma unroll
-        for (int r = 0; r < C::PR; ++r) {
-            const int pos = min(tid + r * C::THREADS, C::NPOS - 1);
-            const int iy = pos / C::IW, ix = pos - iy * C::IW;
-            const int gy = iy0_ + iy, gx = ix0_ + ix;
-            const bool inb = gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
-            goff[r] = inb ? (gy * p.Win + gx) * 4 : 0; // byte offset inside a channel plane (SGPR base + 32-bit VGPR offset)
-            vmask |= (inb ? 1u : 0u) << r;
-        }
-        // interior patches (the vast majority) need no zero-padding select at all: workgroup-uniform fast path
-        all_in = (iy0_ >= 0) && (ix0_ >= 0) && (iy0_ + C::IH <= p.Hin) && (ix0_ + C::IW <= p.Win);
-        rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in + (size_t)f_ * p.in_fs), 0, 0x7FFFFFFF, 0x00020000);
-        wbase_b = (unsigned)((size_t)cb_ * (p.Cin / KC) * C::W4 * 16);
-    };
-#define WN_LOAD_X(CH, R)                                                                         \
-    {                                                                                            \
-        const unsigned cb_ = (unsigned)((CH) * KC) * plane_b;                                    \
-        _Pragma("unroll") for (int c = 0; c < KC; ++c)                                           \
-            xv[R][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, goff[R], cb_ + (unsigned)c * plane_b, 0)); \
-    }
-#define WN_LOAD_W(CH)                                                                            \
-    {                                                                                            \
-        const unsigned wb_ = wbase_b + (unsigned)(CH) * (C::W4 * 16);                            \
-        _Pragma("unroll") for (int r = 0; r < C::WR; ++r) {                                      \
-            const int e_ = tid + r * C::THREADS;                                                 \
-            wv[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (e_ < C::W4 ? e_ : C::W4 - 1) * 16, wb_, 0)); \
-        }                                                                                        \
-    }
-#define WN_LOAD_CHUNK(CH)                                                                        \
-    {                                                                                            \
-        _Pragma("unroll") for (int r = 0; r < C::PR; ++r) WN_LOAD_X(CH, r)                       \
-        WN_LOAD_W(CH)                                                                            \
-    }
-    int cur_frame = -1;
-    {
-        const int lin0 = xk * per + xj;
-        if (lin0 < lin_end) {
-            set_load_tile(lin0);
-            WN_LOAD_CHUNK(0)
-        }
-    }
-    for (int lin = xk * per + xj; lin < lin_end; lin += nloc) {
-    BlockId bid;
-    bid.y = lin % ncb;
-    bid.x = (lin / ncb) % ntile;
-    bid.z = lin / (ncb * ntile);
-    const size_t fz = bid.z;
-    float* __restrict__ gout = p.out + fz * p.out_fs;
-    const float* __restrict__ gres = p.res ? p.res + fz * p.res_fs : nullptr;
-    double* __restrict__ gstat = p.stat_acc ? p.stat_acc + fz * p.stat_fs : nullptr;
-
-    const int bx = bid.x % nbx, by = bid.x / nbx;
-    const int co0 = bid.y * C::BM;
-    const int ox0 = bx * C::PW, oy0 = by * C::PH;
-
-    // (scale, shift) of the producer's normalisation: per frame, written by norm_finalize (PRE_AFFINE) -- reloaded
-    // only when this workgroup moves to another frame.  Every wave is past the previous tile's last chunk barrier
-    // here, so nobody still reads the arrays; the prologue's first barrier publishes them.
-    if (p.pre != PRE_RAW && bid.z != cur_frame) {
-        for (int c = tid; c < p.Cin; c += C::THREADS) {
-            scl[c] = p.pre_scale[fz * p.aff_fs + c];
-            shl[c] = p.pre_shift[fz * p.aff_fs + c];
-        }
-        cur_frame = bid.z;
-    }
-
-    // this lane's tile: block-local tile coords -> top-left output pixel and raw-patch base
-    const int btx = wn % BTX, bty = wn / BTX;
-    const int ttx = btx * TWT + (m % TWT), tty = bty * C::THT + (m / TWT);
-    const int opx = ox0 + 2 * ttx, opy = oy0 + 2 * tty;
-    const int rbase = (2 * tty) * C::IWP + ttx + kq * C::CS;
-    const int aoff = kq * C::BMP + wm * 32 + m * 2; // float2 {M-tile 0, M-tile 1}
-
-    f32x4 acc[MT][16];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int x = 0; x < 16; ++x) acc[i][x] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    const int nchunk = p.Cin / KC;
-
-    // ---- software-pipelined chunk loop ------------------------------------------------------------
-    // One register set holds the NEXT chunk's raw loads.  Per chunk (after its opening barrier):
-    //   * LDS reads of this chunk's first channel quad are issued first, and the staged registers are
-    //     normalised (VALU that needs no LDS) while those reads are in flight
-    //   * the normalised registers are written to the OTHER LDS buffer one piece per MFMA step, then the
-    //     loads of chunk ch+2 are re-issued -- they have until the next barrier (> half a chunk) to land
-    //   * the input transform is cut in two: the column pass of quad q+1 is spread over the steps of
-    //     quad q, the row pass is one add per step right before its MFMA pair
-    // so a wave keeps issuing MFMAs by itself instead of relying on another wave being out of phase.
-// normalise + ReLU + zero padding of the staged registers (chunk CH), in place
-#define WN_NORM_CHUNK(CH)                                                                        \
-    {                                                                                            \
-        const int c0_ = (CH) * KC;                                                               \
-        if (p.pre != PRE_RAW) {                                                                  \
-            float sc_[KC], sh_[KC];                                                              \
-            _Pragma("unroll") for (int c = 0; c < KC; c += 4) {                                  \
-                const f32x4 a_ = *reinterpret_cast<const f32x4*>(scl + c0_ + c);                 \
-                const f32x4 b_ = *reinterpret_cast<const f32x4*>(shl + c0_ + c);                 \
-                _Pragma("unroll") for (int q = 0; q < 4; ++q) { sc_[c + q] = a_[q]; sh_[c + q] = b_[q]; } \
-            }                                                                                    \
-            _Pragma("unroll") for (int r = 0; r < C::PR; ++r)                                    \
-                _Pragma("unroll") for (int c = 0; c < KC; ++c) xv[r][c] = fmaxf(fmaf(xv[r][c], sc_[c], sh_[c]), 0.f); \
-        }                                                                                        \
-        if (!all_in) { /* border patch: positions outside the image are zero AFTER the normalisation */ \
-            _Pragma("unroll") for (int r = 0; r < C::PR; ++r) {                                  \
-                const bool inb_ = (vmask >> r) & 1u;                                             \
-                _Pragma("unroll") for (int c = 0; c < KC; ++c) xv[r][c] = inb_ ? xv[r][c] : 0.f; \
-            }                                                                                    \
-        }                                                                                        \
-    }
-// piece E of the LDS write of the staged chunk into buffer BUF: E < PR*KC one input element, then the weight quads
-#define WN_WRITE_PIECE(E, BUF)                                                                   \
-    {                                                                                            \
-        if constexpr ((E) < C::PR * KC) {                                                        \
-            constexpr int r_ = (E) / KC, c_ = (E) % KC;                                          \
-            (il + (BUF) * C::LDS_IN)[c_ * C::CS + loff[r_]] = xv[r_][c_];                        \
-        } else if constexpr ((E) < C::PR * KC + C::WR) {                                         \
-            constexpr int r_ = (E) - C::PR * KC;                                                 \
-            const int e_ = tid + r_ * C::THREADS;                                                \
-            reinterpret_cast<f32x4*>(wl + (BUF) * C::LDS_W)[e_ < C::W4 ? e_ : C::W4 - 1] = wv[r_]; /* clamped lanes repeat the last quad */ \
-        }                                                                                        \
-    }
-// raw 4x4 patch of this lane's tile for channel quad C4 (this lane: channel C4*4 + kq)
-#define WN_READ_RAW(DST, C4)                                                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                             \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                         \
-            DST[i_ * 4 + j_] = ib[rbase + (C4) * 4 * C::CS + i_ * C::IWP + (j_ & 1) * C::HALF + (j_ >> 1)];
-// V = B^T d B in two passes.  Column pass, piece K (0..15): T = B^T d
-#define WN_COLPASS(T, D, K)                                                                      \
-    {                                                                                            \
-        constexpr int a_ = (K) / 4, j_ = (K) % 4;                                                \
-        if constexpr (a_ == 0) T[0 + j_] = D[0 + j_] - D[8 + j_];                                \
-        else if constexpr (a_ == 1) T[4 + j_] = D[4 + j_] + D[8 + j_];                           \
-        else if constexpr (a_ == 2) T[8 + j_] = D[8 + j_] - D[4 + j_];                           \
-        else T[12 + j_] = D[4 + j_] - D[12 + j_];                                                \
-    }
-// row pass for Winograd point XI
-#define WN_ROWPASS(T, XI)                                                                        \
-    (((XI) & 3) == 0 ? T[(XI)] - T[((XI) + 2) & 15] : ((XI) & 3) == 1 ? T[(XI)] + T[((XI) + 1) & 15] : ((XI) & 3) == 2 ? T[(XI)] - T[((XI) - 1) & 15] : T[((XI) - 2) & 15] - T[(XI)]) /* & 15: keeps the untaken arms in range */
-
-    constexpr int NQ = KC / 4;
-    constexpr int NSTEP = NQ * 16;
-    constexpr int NPIECE = C::PR * KC + C::WR;                       // LDS write pieces of one chunk
-    constexpr int LOAD_STEPS = C::PR + 1;                            // re-issue: one x row or the weights per step
-    constexpr int PER_MIN = (NPIECE + (NSTEP - LOAD_STEPS - 1) - 1) / (NSTEP - LOAD_STEPS - 1);
-    constexpr int PER = PER_MIN > WINO_PER ? PER_MIN : WINO_PER; // write pieces per step (more per step = the next loads go out earlier)
-    constexpr int WSTEPS = (NPIECE + PER - 1) / PER;
-    static_assert(WSTEPS + LOAD_STEPS <= NSTEP, "staging does not fit the chunk's MFMA steps");
-    // A operands run AD steps ahead of their MFMAs (a step is only 2 MFMAs = 64 cycles; LDS latency is 2-3x that)
-    constexpr int AD = WINO_AD;
-
-    // chunk 0 of this tile was requested before the previous tile's epilogue (or ahead of the loop)
-    __syncthreads(); // scl / shl visible
-    WN_NORM_CHUNK(0)
-    pp_steps<0, NPIECE>([&](auto E) { WN_WRITE_PIECE(decltype(E)::value, 0) });
-    if (nchunk > 1) WN_LOAD_CHUNK(1)
-    __syncthreads();
-
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int buf = ch & 1;
-        const float* ib = il + buf * C::LDS_IN;
-        const float* wb = wl + buf * C::LDS_W;
-        float draw[16], tq[2][16];
-        float2 a[AD];
-        float vcur, vnext;
-        __builtin_amdgcn_s_setprio(WINO_PRIO); // the short non-MFMA segments first: back to the matrix pipe sooner
-        WN_READ_RAW(draw, 0)
-#define WN_LOAD_A(S)                                                                             \
-    {                                                                                            \
-        constexpr int n4_ = (S) / 16, nx_ = (S) % 16;                                            \
-        a[(S) % AD] = *reinterpret_cast<const float2*>(wb + (nx_ * KC + n4_ * 4) * C::BMP + aoff); \
-    }
-        pp_steps<0, (AD - 1 < NSTEP ? AD - 1 : NSTEP)>([&](auto S) { WN_LOAD_A(decltype(S)::value) });
-        // registers of chunk ch+1: normalise while the LDS reads above are in flight (at the last chunk this
-        // re-normalises stale registers whose LDS copy nobody reads)
-        {
-            const int chn = ch + 1 < nchunk ? ch + 1 : ch;
-            WN_NORM_CHUNK(chn)
-        }
-        pp_steps<0, 16>([&](auto K) { WN_COLPASS(tq[0], draw, decltype(K)::value) });
-        vnext = WN_ROWPASS(tq[0], 0);
-        __builtin_amdgcn_s_setprio(0);
-        pp_steps<0, NSTEP>([&](auto S) {
-            constexpr int s_ = decltype(S)::value;
-            constexpr int c4 = s_ / 16, xi = s_ % 16;
-            vcur = vnext;
-            // next quad: raw reads at its predecessor's first step, column pass over steps 6..13
-            if constexpr (xi == 0 && c4 + 1 < NQ) WN_READ_RAW(draw, c4 + 1)
-            if constexpr (c4 + 1 < NQ && xi >= 6 && xi < 14) {
-                WN_COLPASS(tq[(c4 + 1) & 1], draw, (xi - 6) * 2)
-                WN_COLPASS(tq[(c4 + 1) & 1], draw, (xi - 6) * 2 + 1)
-            }
-            if constexpr (s_ + 1 < NSTEP) {
-                constexpr int c4n = (s_ + 1) / 16, xin = (s_ + 1) % 16;
-                vnext = WN_ROWPASS(tq[c4n & 1], xin);
-            }
-            if constexpr (s_ + AD - 1 < NSTEP) WN_LOAD_A(s_ + AD - 1)
-            // staging of chunk ch+1: LDS writes first, then the loads of chunk ch+2 into the freed registers
-            if constexpr (s_ < WSTEPS) {
-                pp_steps<0, PER>([&](auto Q) { WN_WRITE_PIECE(s_ * PER + decltype(Q)::value, buf ^ 1) });
-            } else if constexpr (s_ - WSTEPS < C::PR) {
-                if (ch + 2 < nchunk) WN_LOAD_X(ch + 2, s_ - WSTEPS)
-            } else if constexpr (s_ - WSTEPS == C::PR) {
-                if (ch + 2 < nchunk) WN_LOAD_W(ch + 2)
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s_ % AD].x, vcur, acc[0][xi], 0, 0, 0);
-            acc[1][xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s_ % AD].y, vcur, acc[1][xi], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-#undef WN_LOAD_A
-        __syncthreads();
-    }
-#undef WN_NORM_CHUNK
-#undef WN_WRITE_PIECE
-#undef WN_READ_RAW
-#undef WN_COLPASS
-#undef WN_ROWPASS
-
-    __builtin_amdgcn_s_setprio(WINO_PRIO);
-    if (lin + nloc < lin_end) { // next tile's first chunk: in flight during the epilogue below
-        set_load_tile(lin + nloc);
-        WN_LOAD_CHUNK(0)
-    }
-    // ---- epilogue: Y = A^T M A per lane, residual, store (float2 rows), statistics ----
-    const size_t out_plane = (size_t)p.Hout * p.Wout;
-    float ssum[MT][4], ssq[MT][4];
-    const bool pix_ok = (opx < p.Wout) && (opy < p.Hout);
-    if (!(p.Wout & 1)) {
-        // Even width (every map of this network): a lane's two output columns are one aligned float2.  Branch-free: the
-        // residual rows are requested up front and everything goes through buffer descriptors whose bounds check drops
-        // the lanes that have no pixel / row (offset 0xFFFFFFFF).  The per-row `load -> s_waitcnt vmcnt(0) -> add ->
-        // store` chains of the branchy form made every row wait for the previous row's STORES and for the next tile's
-        // prefetch as well (vmcnt is in order): 5.5 k of a tile's 113 k cycles by the stamps.
-        const unsigned frame_bytes = (unsigned)((size_t)p.Cout * out_plane * 4);
-        const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(gout, 0, frame_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rres_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gres ? gres : gout), 0, gres ? frame_bytes : 0u, 0x00020000);
-        const bool two_y = opy + 1 < p.Hout;
-        unsigned off0[MT][4], off1[MT][4];
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        f32x2 r0[MT][4], r1[MT][4];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = co0 + wm * MT * 16 + i * 16 + kq * 4 + r;
-                const bool ok = pix_ok && row < p.Cout;
-                const unsigned o = (unsigned)(((size_t)row * out_plane + (size_t)opy * p.Wout + opx) * 4);
-                off0[i][r] = ok ? o : 0xFFFFFFFFu;
-                off1[i][r] = (ok && two_y) ? o + (unsigned)p.Wout * 4u : 0xFFFFFFFFu;
-                r0[i][r] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rres_, off0[i][r], 0, 0)); // zero records when the layer has no residual
-                r1[i][r] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rres_, off1[i][r], 0, 0));
-            }
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float t0[4], t1[4];
-#pragma unroll
-                for (int a_ = 0; a_ < 4; ++a_) {
-                    const float m0 = acc[i][a_ * 4 + 0][r], m1 = acc[i][a_ * 4 + 1][r], m2 = acc[i][a_ * 4 + 2][r], m3 = acc[i][a_ * 4 + 3][r];
-                    t0[a_] = m0 + m1 + m2;
-                    t1[a_] = m1 - m2 - m3;
-                }
-                float y00 = t0[0] + t0[1] + t0[2], y01 = t1[0] + t1[1] + t1[2];
-                float y10 = t0[1] - t0[2] - t0[3], y11 = t1[1] - t1[2] - t1[3];
-                y00 += r0[i][r][0]; y01 += r0[i][r][1];
-                y10 += r1[i][r][0]; y11 += r1[i][r][1];
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b64(rout, 0u, 0, 0)), (f32x2){y00, y01}), rout, off0[i][r], 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b64(rout, 0u, 0, 0)), (f32x2){y10, y11}), rout, off1[i][r], 0, 0);
-                const bool ok0 = off0[i][r] != 0xFFFFFFFFu, ok1 = off1[i][r] != 0xFFFFFFFFu;
-                // same summation order as the reference form below: row y, then row y+1
-                float s_ = y00 + y01, q_ = y00 * y00 + y01 * y01;
-                if (ok1) { s_ += y10; q_ += y10 * y10; s_ += y11; q_ += y11 * y11; }
-                ssum[i][r] = ok0 ? s_ : 0.f;
-                ssq[i][r] = ok0 ? q_ : 0.f;
-            }
-    } else {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int row0 = co0 + wm * MT * 16 + i * 16 + kq * 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float t0[4], t1[4];
-#pragma unroll
-            for (int a_ = 0; a_ < 4; ++a_) {
-                const float m0 = acc[i][a_ * 4 + 0][r], m1 = acc[i][a_ * 4 + 1][r], m2 = acc[i][a_ * 4 + 2][r], m3 = acc[i][a_ * 4 + 3][r];
-                t0[a_] = m0 + m1 + m2;
-                t1[a_] = m1 - m2 - m3;
-            }
-            float y00 = t0[0] + t0[1] + t0[2], y01 = t1[0] + t1[1] + t1[2];
-            float y10 = t0[1] - t0[2] - t0[3], y11 = t1[1] - t1[2] - t1[3];
-            ssum[i][r] = 0.f;
-            ssq[i][r] = 0.f;
-            if (pix_ok && row0 + r < p.Cout) {
-                const size_t o = (size_t)(row0 + r) * out_plane + (size_t)opy * p.Wout + opx;
-                const bool two_x = opx + 1 < p.Wout, two_y = opy + 1 < p.Hout;
-                if (gres) {
-                    if (two_x) {
-                        const float2 r0 = *reinterpret_cast<const float2*>(gres + o);
-                        y00 += r0.x; y01 += r0.y;
-                        if (two_y) { const float2 r1 = *reinterpret_cast<const float2*>(gres + o + p.Wout); y10 += r1.x; y11 += r1.y; }
-                    } else {
-                        y00 += gres[o];
-                        if (two_y) y10 += gres[o + p.Wout];
-                    }
-                }
-                if (two_x) {
-                    *reinterpret_cast<float2*>(gout + o) = make_float2(y00, y01);
-                    if (two_y) *reinterpret_cast<float2*>(gout + o + p.Wout) = make_float2(y10, y11);
-                } else {
-                    gout[o] = y00;
-                    if (two_y) gout[o + p.Wout] = y10;
-                }
-                float s_ = y00, q_ = y00 * y00;
-                if (two_x) { s_ += y01; q_ += y01 * y01; }
-                if (two_y) { s_ += y10; q_ += y10 * y10; if (two_x) { s_ += y11; q_ += y11 * y11; } }
-                ssum[i][r] = s_;
-                ssq[i][r] = q_;
-            }
-        }
-    }
-    }
-    if (gstat) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s = ssum[i][r], q = ssq[i][r];
-                s = row16_sum(s);
-                q = row16_sum(q);
-                if (m == 0) {
-                    const int lr = wm * MT * 16 + i * 16 + kq * 4 + r;
-                    red[(wn * C::BM + lr) * 2] = s;
-                    red[(wn * C::BM + lr) * 2 + 1] = q;
-                }
-            }
-        __syncthreads();
-        for (int lr = tid; lr < C::BM; lr += C::THREADS) {
-            const int row = co0 + lr;
-            if (row >= p.Cout) continue;
-            double s = 0.0, q = 0.0;
-#pragma unroll
-            for (int w = 0; w < WN; ++w) {
-                s += (double)red[(w * C::BM + lr) * 2];
-                q += (double)red[(w * C::BM + lr) * 2 + 1];
-            }
-            double* dst = gstat + ((size_t)(blockIdx.x % NREP) * p.stat_C + row) * 2;
-            atomicAdd(dst, s);
-            atomicAdd(dst + 1, q);
-        }
-    }
-    } // tile loop
-#undef WN_LOAD_X
-#undef WN_LOAD_W
-#undef WN_LOAD_CHUNK
-}
-
-// ------------------------------------------------------------------------------------------
-// wino4_mfma: Winograd F(2x2,3x3) re-structured around ONE wave per SIMD with the whole 512-register file.
-// What the counters said about wino_mfma (profiles/r01_pmc_sq_waits_and_mix.txt): 3.4 VALU + 1.1 LDS instructions
-// per MFMA, two waves per SIMD waiting on each other for issue (53 % of wave time), the matrix pipe 50 % busy;
-// the non-MFMA phases (chunk opening, epilogue) of two independent workgroups overlap only by chance.  Here:
-//  * MT = 4: a wave owns 16 tiles x ALL 64 output channels of the block (256 accumulator registers = the AGPR half).
-//    Each transformed B operand now feeds 4 MFMAs instead of 2, each A fetch is one ds_read_b128 for 4 MFMAs: per MFMA
-//    the transform VALU, the LDS reads and the staging work all halve, and a 64-channel layer transforms its
-//    input ONCE instead of once per 32-row block.
-//  * a THREE-deep LDS ring (input patch + weight image per channel chunk): chunk g+2 is written while chunk g is
-//    multiplied, so chunk g+1 is complete one barrier EARLIER than it is needed and its first operands (raw patch,
-//    A fragments, column pass) are fetched during the last steps of chunk g.  The MFMA stream runs across chunk
-//    boundaries without the opening bubble (LDS round trip -> normalise -> column pass -> first MFMA) that cost
-//    wino_mfma ~1 k of every ~7 k cycles; the one barrier per chunk has nothing waiting right behind it.
-//  * the staging pipeline runs across TILE boundaries too: the load side simply walks the (item, chunk) stream two
-//    chunks ahead of the compute side, whatever tile that is.
-//  * InstanceNorm (scale, shift) of the staged chunk come through the scalar cache (wave-uniform address), not LDS.
-//  * the statistics' cross-wave reduction is deferred behind the next tile's first chunk barrier: no extra barrier.
-// One workgroup (4 waves) per CU, persistent over the (cout block, tile, frame) list like wino_mfma.
-// ------------------------------------------------------------------------------------------
-// The 256 accumulator registers of wino4_mfma are NOT C++ values: its MFMAs name a[0:255] literally.  Handing hipcc 64 live
-// accumulator quads next to ~130 asm statements per chunk ends in accumulators scattered over both register halves, AGPR
-// permutations at the loop edge and scratch spills of just-loaded operands; with the accumulators out of its sight it
-// allocates < 256 plain VGPRs and nothing else.  Every such statement clobbers the whole AGPR half, so the compiler can never
-// park a value there (audit: no v_accvgpr_* outside these statements in the ISA, tools/isa_stats.py).
-#define W4_A10(b) "a" #b "0", "a" #b "1", "a" #b "2", "a" #b "3", "a" #b "4", "a" #b "5", "a" #b "6", "a" #b "7", "a" #b "8", "a" #b "9"
-#define W4_A100(h) W4_A10(h##0), W4_A10(h##1), W4_A10(h##2), W4_A10(h##3), W4_A10(h##4), W4_A10(h##5), W4_A10(h##6), W4_A10(h##7), W4_A10(h##8), W4_A10(h##9)
-#define W4_AGPRS "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", W4_A10(1), W4_A10(2), W4_A10(3), W4_A10(4), W4_A10(5), W4_A10(6), W4_A10(7), W4_A10(8), W4_A10(9), \
-                 W4_A100(1), W4_A10(20), W4_A10(21), W4_A10(22), W4_A10(23), W4_A10(24), "a250", "a251", "a252", "a253", "a254", "a255"
-// the 16 Winograd positions of (M-tile I, accumulator row R) in ONE statement: hipcc pads every asm boundary with an s_nop
-// before a VALU may touch its outputs -- one pad per 16 reads instead of one per read
-template <int I, int R>
-__device__ __forceinline__ void w4_acc_read16(float (&v)[16])
-{
-    asm volatile("v_accvgpr_read_b32 %0, a%c16\n\tv_accvgpr_read_b32 %1, a%c17\n\tv_accvgpr_read_b32 %2, a%c18\n\tv_accvgpr_read_b32 %3, a%c19\n\t"
-                 "v_accvgpr_read_b32 %4, a%c20\n\tv_accvgpr_read_b32 %5, a%c21\n\tv_accvgpr_read_b32 %6, a%c22\n\tv_accvgpr_read_b32 %7, a%c23\n\t"
-                 "v_accvgpr_read_b32 %8, a%c24\n\tv_accvgpr_read_b32 %9, a%c25\n\tv_accvgpr_read_b32 %10, a%c26\n\tv_accvgpr_read_b32 %11, a%c27\n\t"
-                 "v_accvgpr_read_b32 %12, a%c28\n\tv_accvgpr_read_b32 %13, a%c29\n\tv_accvgpr_read_b32 %14, a%c30\n\tv_accvgpr_read_b32 %15, a%c31"
-                 : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]), "=v"(v[4]), "=v"(v[5]), "=v"(v[6]), "=v"(v[7]), "=v"(v[8]), "=v"(v[9]),
-                   "=v"(v[10]), "=v"(v[11]), "=v"(v[12]), "=v"(v[13]), "=v"(v[14]), "=v"(v[15])
-                 : "i"((0 * 4 + I) * 4 + R), "i"((1 * 4 + I) * 4 + R), "i"((2 * 4 + I) * 4 + R), "i"((3 * 4 + I) * 4 + R), "i"((4 * 4 + I) * 4 + R),
-                   "i"((5 * 4 + I) * 4 + R), "i"((6 * 4 + I) * 4 + R), "i"((7 * 4 + I) * 4 + R), "i"((8 * 4 + I) * 4 + R), "i"((9 * 4 + I) * 4 + R),
-                   "i"((10 * 4 + I) * 4 + R), "i"((11 * 4 + I) * 4 + R), "i"((12 * 4 + I) * 4 + R), "i"((13 * 4 + I) * 4 + R), "i"((14 * 4 + I) * 4 + R),
-                   "i"((15 * 4 + I) * 4 + R)
-                 : W4_AGPRS);
-}
-
-// rows R and R + 1 (R even) of M-tile I at the 16 Winograd positions, as 16 (row R, row R + 1) pairs for v_pk_* arithmetic:
-// position xi's quad starts at a[xi*16 + I*4]
-template <int I, int R>
-__device__ __forceinline__ void w4_acc_read32(float __attribute__((ext_vector_type(2))) (&v)[16])
-{
-    float l[16], u[16];
-    // operands %0..%15 = row R at position 0..15, %16..%31 = row R + 1 (operand numbers are spelled out: %1K would be ambiguous)
-    asm volatile("v_accvgpr_read_b32 %0, a[%c32+0]\n\tv_accvgpr_read_b32 %16, a[%c32+1]\n\t"
-                 "v_accvgpr_read_b32 %1, a[%c32+16]\n\tv_accvgpr_read_b32 %17, a[%c32+17]\n\t"
-                 "v_accvgpr_read_b32 %2, a[%c32+32]\n\tv_accvgpr_read_b32 %18, a[%c32+33]\n\t"
-                 "v_accvgpr_read_b32 %3, a[%c32+48]\n\tv_accvgpr_read_b32 %19, a[%c32+49]\n\t"
-                 "v_accvgpr_read_b32 %4, a[%c32+64]\n\tv_accvgpr_read_b32 %20, a[%c32+65]\n\t"
-                 "v_accvgpr_read_b32 %5, a[%c32+80]\n\tv_accvgpr_read_b32 %21, a[%c32+81]\n\t"
-                 "v_accvgpr_read_b32 %6, a[%c32+96]\n\tv_accvgpr_read_b32 %22, a[%c32+97]\n\t"
-                 "v_accvgpr_read_b32 %7, a[%c32+112]\n\tv_accvgpr_read_b32 %23, a[%c32+113]\n\t"
-                 "v_accvgpr_read_b32 %8, a[%c32+128]\n\tv_accvgpr_read_b32 %24, a[%c32+129]\n\t"
-                 "v_accvgpr_read_b32 %9, a[%c32+144]\n\tv_accvgpr_read_b32 %25, a[%c32+145]\n\t"
-                 "v_accvgpr_read_b32 %10, a[%c32+160]\n\tv_accvgpr_read_b32 %26, a[%c32+161]\n\t"
-                 "v_accvgpr_read_b32 %11, a[%c32+176]\n\tv_accvgpr_read_b32 %27, a[%c32+177]\n\t"
-                 "v_accvgpr_read_b32 %12, a[%c32+192]\n\tv_accvgpr_read_b32 %28, a[%c32+193]\n\t"
-                 "v_accvgpr_read_b32 %13, a[%c32+208]\n\tv_accvgpr_read_b32 %29, a[%c32+209]\n\t"
-                 "v_accvgpr_read_b32 %14, a[%c32+224]\n\tv_accvgpr_read_b32 %30, a[%c32+225]\n\t"
-                 "v_accvgpr_read_b32 %15, a[%c32+240]\n\tv_accvgpr_read_b32 %31, a[%c32+241]"
-                 : "=v"(l[0]), "=v"(l[1]), "=v"(l[2]), "=v"(l[3]), "=v"(l[4]), "=v"(l[5]), "=v"(l[6]), "=v"(l[7]), "=v"(l[8]), "=v"(l[9]), "=v"(l[10]),
-                   "=v"(l[11]), "=v"(l[12]), "=v"(l[13]), "=v"(l[14]), "=v"(l[15]), "=v"(u[0]), "=v"(u[1]), "=v"(u[2]), "=v"(u[3]), "=v"(u[4]), "=v"(u[5]),
-                   "=v"(u[6]), "=v"(u[7]), "=v"(u[8]), "=v"(u[9]), "=v"(u[10]), "=v"(u[11]), "=v"(u[12]), "=v"(u[13]), "=v"(u[14]), "=v"(u[15])
-                 : "i"(I * 4 + R)
-                 : W4_AGPRS);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { v[k][0] = l[k]; v[k][1] = u[k]; }
-}
-// Row pass of the Winograd input transform, middle positions: tb = (t1, t3), ta = (t0, t2) of one row of B^T d  ->  (t1 + t2, t2 - t1)
-__device__ __forceinline__ float __attribute__((ext_vector_type(2))) w4_row_mid(float __attribute__((ext_vector_type(2))) tb, float __attribute__((ext_vector_type(2))) ta)
-{
-    float __attribute__((ext_vector_type(2))) r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[1,0]" : "=v"(r) : "v"(tb), "v"(ta));
-    return r;
-}
-// Lanes 2j (tile x) and 2j+1 (tile x+1) hold the 2x2 outputs (y0 y1 / y2 y3) of neighbouring tiles.  Returns, in the even lane,
-// row y of both tiles (own y0 y1, partner's y0 y1) and in the odd lane row y+1 (partner's y2 y3, own y2 y3): v_cndmask_b32 with
-// its first source permuted over DPP (quad_perm [1,0,3,2] = lane ^ 1) -- 4 VALU instead of 2 selects + 2 DPP moves + 4 selects.
-// s_nop 1: a DPP source written by the VALU instruction before needs 2 wait states, and hipcc does not look inside asm.
-__device__ __forceinline__ f32x4 w4_pair_rows(float y0, float y1, float y2, float y3)
-{
-    float v0, v1, v2, v3;
-    asm volatile("s_mov_b32 vcc_lo, 0x55555555\n\ts_mov_b32 vcc_hi, 0x55555555\n\ts_nop 1\n\t"
-                 "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                 "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                 "s_not_b64 vcc, vcc\n\t"
-                 "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                 "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-                 : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
-                 : "v"(y0), "v"(y1), "v"(y2), "v"(y3)
-                 : "vcc", "scc");
-    return (f32x4){v0, v1, v2, v3};
-}
-
-template <int TWT, int BTX, int KC>
-struct Wino4Cfg {
-    static constexpr int WN = 4, MT = 4;
-    static constexpr int THT = 16 / TWT;
-    static constexpr int BTY = WN / BTX;
-    static constexpr int PW = BTX * TWT * 2, PH = BTY * THT * 2;
-    static constexpr int IW = PW + 2, IH = PH + 2;
-    static constexpr int HALF = (IW + 1) / 2;
-    static constexpr int iwp()
-    {
-        int v = IW;
-        if (TWT == 16) return v;
-        if (TWT == 2 && BTX == 1) return 6; // 4 x 64 strip tile: rows 12 banks apart (0,12,24,4,...) keep a wave's 8 tile rows on distinct banks
-        while ((2 * v) % 32 != TWT) ++v;
-        return v;
-    }
-    static constexpr int IWP = iwp();
-    static constexpr int cs()
-    {
-        int v = IH * IWP;
-        while (v % 32 != 16) ++v;
-        return v;
-    }
-    static constexpr int CS = cs();
-    static constexpr int BM = 64;  // rows per block = MT * 16; A image row = [m 0..15][M-tile 0..3]: one ds_read_b128 per lane, the
-                                   // 64 lanes of a step read 1 KB contiguous (kq*64 + m*4 floats) -- conflict-free without padding
-    static constexpr int THREADS = 256;
-    static constexpr int NPOS = IH * IW;
-    static constexpr int PR = (NPOS + THREADS - 1) / THREADS;
-    static constexpr int W4 = 16 * KC * BM / 4;
-    static constexpr int WR = (W4 + THREADS - 1) / THREADS;
-    static constexpr int LDS_IN = KC * CS;
-    static constexpr int LDS_W = 16 * KC * BM;
-    static constexpr int NSTAGE = 3;
-    static constexpr int LDS_FLOATS = NSTAGE * (LDS_IN + LDS_W) + 2 * WN * BM + 2 * 640;
-    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "must fit the 160 KB LDS");
-    static_assert(WN % BTX == 0, "tiles must form a rectangle");
-    static_assert(KC == 8, "the step schedule assumes two channel quads per chunk (tq parity, A ring)");
-    static_assert(W4 % THREADS == 0, "weight image is a whole number of float4 per thread");
-};
-
-template <int TWT, int BTX, int KC, int ROOFLINE = 0>
-__global__ void __launch_bounds__(256, 1) wino4_mfma(const ConvP p)
-{
-    using C = Wino4Cfg<TWT, BTX, KC>;
-    constexpr int WN = 4;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* il = smem;                               // [3][KC][CS]
-    float* wl = il + C::NSTAGE * C::LDS_IN;         // [3][16][KC][64]
-    float* red = wl + C::NSTAGE * C::LDS_W;         // [WN][BM][2]
-    float* aff = red + 2 * WN * C::BM;              // [2 frame parities][2: scale, shift][320]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wn = tid >> 6;
-    const int m = lane & 15, kq = lane >> 4;
-
-    const int nbx = p.rnbx, nby = p.rnby; // tiles of this launch's region [rx0, rx1) x [ry0, ry1)
-    const int ntile = nbx * nby, ncb = (p.Cout + C::BM - 1) / C::BM;
-    const int total = ntile * ncb * p.nb;
-    const int per = (total + 7) >> 3;
-    const int xk = blockIdx.x & 7, xj = blockIdx.x >> 3, nloc = gridDim.x >> 3;
-    const int lin_end = min(total, (xk + 1) * per);
-    const int lin0 = xk * per + xj;
-    if (lin0 >= lin_end) return;
-    const int nchunk = p.Cin / KC;
-
-    // ---------------- load side: walks the (item, chunk) stream two chunks ahead of the compute side ----------------
-    int goff[C::PR], loff[C::PR];
-    unsigned vmask = 0u;
-    __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, 0x7FFFFFFF, 0x00020000);
-    const unsigned plane_b = (unsigned)(p.Hin * p.Win) * 4u;
-    unsigned wbase_b = 0u;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 xv[C::PR][KC / 2]; // staging registers: channel pairs (2k, 2k+1), so one v_pk_fma_f32 normalises two pieces
-    f32x4 wv[C::WR];
-#pragma unroll
-    for (int r = 0; r < C::PR; ++r) {
-        const int pos = min(tid + r * C::THREADS, C::NPOS - 1); // tail threads duplicate the last position: unconditional staging
-        const int iy = pos / C::IW, ix = pos - iy * C::IW;
-        loff[r] = iy * C::IWP + (ix & 1) * C::HALF + (ix >> 1);
-    }
-    int s_lin = lin0, s_ch = 0, s_frame = 0; // chunk the NEXT load request is for, and its frame
-    int r_c0 = 0;                            // first channel of the chunk held in the registers (its table slot: r_tab)
-    unsigned r_vmask = 0u;
-    auto set_load_tile = [&](int l) {
-        const int cb_ = l % ncb, t_ = (l / ncb) % ntile, f_ = l / (ncb * ntile);
-        const int iy0_ = p.ry0 + (t_ / nbx) * C::PH - 1, ix0_ = p.rx0 + (t_ % nbx) * C::PW - 1;
-        vmask = 0u;
-#pragma unroll
-        for (int r = 0; r < C::PR; ++r) {
-            const int pos = min(tid + r * C::THREADS, C::NPOS - 1);
-            const int iy = pos / C::IW, ix = pos - iy * C::IW;
-            const int gy = iy0_ + iy, gx = ix0_ + ix;
-            const bool inb = gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
-            goff[r] = inb ? (gy * p.Win + gx) * 4 : 0;
-            vmask |= (inb ? 1u : 0u) << r;
-        }
-        rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in + (size_t)f_ * p.in_fs), 0, 0x7FFFFFFF, 0x00020000);
-        wbase_b = (unsigned)((size_t)cb_ * nchunk * C::W4 * 16);
-        s_frame = f_;
-    };
-    // The load side: advance() -- uniform branches, possibly a new tile's offsets and a new frame's (scale, shift) table --
-    // runs at the top of a chunk, outside the MFMA stream (a branch between MFMA steps makes hipcc shuffle accumulators);
-    // the requests themselves are spread over the chunk's steps, each right behind the LDS write that frees its register, so
-    // every load has a whole chunk (> 4 k cycles) to land.  Past the end of this workgroup's list the load side stays on its
-    // last chunk (harmless duplicates into ring slots nobody reads; every request stays inside the tensors).
-    // (scale, shift) of the producer's normalisation live in LDS in TWO table slots: the load side may already be in another
-    // frame while older chunks are still being normalised.  A frame change of the load side flips the slot, writes the new
-    // frame's table there, and the chunk barrier that follows publishes it (that slot's previous table belongs to a frame
-    // whose last chunk was normalised at least a whole tile ago).
-    int s_tab = 0, r_tab = 0;
-    auto load_aff = [&](int f_) {
-        float* dst = aff + s_tab * 640;
-        if (p.pre == PRE_STATS) {
-            // one-frame launches (launch_conv, B == 1): the producer's fp64 sums are finalised HERE, once per workgroup, instead of by a
-            // norm_finalize launch in front of every layer (4.7 us + a launch boundary each, 14 per frame at batch 1) -- same fp64
-            // formula, bit-identical (scale, shift)
-            const double* pa = p.pre_acc + (size_t)f_ * p.pre_fs;
-            for (int c = tid; c < p.Cin; c += C::THREADS) {
-                double s = 0.0, q = 0.0;
-#pragma unroll
-                for (int r = 0; r < NREP; ++r) { s += pa[((size_t)r * p.Cin + c) * 2]; q += pa[((size_t)r * p.Cin + c) * 2 + 1]; }
-                const double mean = s * p.pre_inv_n;
-                double var = q * p.pre_inv_n - mean * mean;
-                var = var > 0.0 ? var : 0.0;
-                const double rstd = 1.0 / sqrt(var + (double)p.eps);
-                dst[c] = (float)rstd;
-                dst[320 + c] = (float)(-mean * rstd);
-            }
-            return;
-        }
-        for (int c = tid; c < p.Cin; c += C::THREADS) {
-            dst[c] = p.pre_scale[(size_t)f_ * p.aff_fs + c];
-            dst[320 + c] = p.pre_shift[(size_t)f_ * p.aff_fs + c];
-        }
-    };
-    auto advance = [&]() {
-        if (s_ch + 1 < nchunk) ++s_ch;
-        else if (s_lin + nloc < lin_end) {
-            const int f_old = s_frame;
-            s_lin += nloc; s_ch = 0; set_load_tile(s_lin);
-            if (s_frame != f_old) { s_tab ^= 1; load_aff(s_frame); }
-        }
-    };
-// request piece E of chunk (s_lin, s_ch) into its register
-#define W4_LOAD_PIECE(E)                                                                         \
-    {                                                                                            \
-        if constexpr ((E) < C::PR * KC) {                                                        \
-            constexpr int r_ = (E) / KC, c_ = (E) % KC;                                          \
-            xv[r_][c_ / 2][c_ & 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, goff[r_], (unsigned)(s_ch * KC + c_) * plane_b, 0)); \
-        } else if constexpr ((E) < C::PR * KC + C::WR) {                                         \
-            constexpr int r_ = (E) - C::PR * KC;                                                 \
-            wv[r_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (tid + r_ * C::THREADS) * 16, wbase_b + (unsigned)s_ch * (C::W4 * 16), 0)); \
-        }                                                                                        \
-    }
-// normalise + ReLU + zero padding of input pieces E, E+1 (E even: one channel pair) in place.  SC/SH: this chunk's KC scales /
-// shifts, MASK: upper clamp per position (+inf inside the image = plain ReLU, 0 on the zero padding) -- v_pk_fma_f32 + 2 v_med3_f32
-#define W4_NORM_PAIR(E, SC, SH, MASK)                                                            \
-    {                                                                                            \
-        if constexpr ((E) < C::PR * KC && (E) % 2 == 0) {                                        \
-            constexpr int r_ = (E) / KC, c_ = (E) % KC;                                          \
-            const f32x2 t_ = __builtin_elementwise_fma(xv[r_][c_ / 2], (f32x2){SC[c_], SC[c_ + 1]}, (f32x2){SH[c_], SH[c_ + 1]}); \
-            xv[r_][c_ / 2][0] = __builtin_amdgcn_fmed3f(t_[0], 0.f, MASK[r_]);                   \
-            xv[r_][c_ / 2][1] = __builtin_amdgcn_fmed3f(t_[1], 0.f, MASK[r_]);                   \
-        }                                                                                        \
-    }
-#define W4_READ_AFF(SC, SH, TAB, C0)                                                             \
-    {                                                                                            \
-        const float* t_ = aff + (TAB) * 640 + (C0);                                              \
-        _Pragma("unroll") for (int c = 0; c < KC; c += 4) {                                      \
-            const f32x4 a_ = *reinterpret_cast<const f32x4*>(t_ + c);                            \
-            const f32x4 b_ = *reinterpret_cast<const f32x4*>(t_ + 320 + c);                      \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) { SC[c + q] = a_[q]; SH[c + q] = b_[q]; } \
-        }                                                                                        \
-    }
-#define W4_WRITE_PIECE(E, IB, WB)                                                                \
-    {                                                                                            \
-        if constexpr ((E) < C::PR * KC) {                                                        \
-            constexpr int r_ = (E) / KC, c_ = (E) % KC;                                          \
-            (IB)[c_ * C::CS + loff[r_]] = xv[r_][c_ / 2][c_ & 1];                                \
-        } else if constexpr ((E) < C::PR * KC + C::WR) {                                         \
-            constexpr int r_ = (E) - C::PR * KC;                                                 \
-            reinterpret_cast<f32x4*>(WB)[tid + r_ * C::THREADS] = wv[r_];                        \
-        }                                                                                        \
-    }
-// one row (4 values) of the raw 4x4 patch of the quad whose element index inside the ring is QB.  QB is made opaque once per
-// quad: otherwise hipcc folds the quad's offset into every row address and spends a v_add per ds_read2 on constants that no
-// longer fit the instruction's 8-bit offsets (the row offsets alone do: <= 3*IWP + HALF + 1 dwords)
-#define W4_READ_RAW_ROW(DST, QB, I)                                                              \
-    {                                                                                            \
-        DST[(I) * 2] = (f32x2){il[(QB) + (I) * C::IWP], il[(QB) + (I) * C::IWP + 1]};            \
-        DST[(I) * 2 + 1] = (f32x2){il[(QB) + (I) * C::IWP + C::HALF], il[(QB) + (I) * C::IWP + C::HALF + 1]}; \
-    }
-// Input transform V = B^T d B on column PAIRS: the patch rows sit in LDS with even and odd columns de-interleaved, so a row is
-// two ds_read2_b32 = the register pairs (d0, d2) and (d1, d3).  Packed arithmetic because a lone wave pays 4 cycles per VALU
-// instruction, MFMA shadow or not (tools/issue_probe.hip).
-// column pass, term K2 = 2*row + pair of T = B^T d (rows of pairs TA = (t0, t2), TB = (t1, t3)):
-#define W4_COLPASS2(T, D, K2)                                                                    \
-    {                                                                                            \
-        constexpr int a_ = (K2) / 2, h_ = (K2) % 2;                                              \
-        if constexpr (a_ == 0) T[0 + h_] = D[0 + h_] - D[4 + h_];                                \
-        else if constexpr (a_ == 1) T[2 + h_] = D[2 + h_] + D[4 + h_];                           \
-        else if constexpr (a_ == 2) T[4 + h_] = D[4 + h_] - D[2 + h_];                           \
-        else T[6 + h_] = D[2 + h_] - D[6 + h_];                                                  \
-    }
-// row pass of patch row A: the B operands of steps 4A .. 4A+3 = t0 - t2 | (t1 + t2, t2 - t1) in one v_pk_add_f32 | t1 - t3
-#define W4_ROW_ALL(T, A)                                                                         \
-    {                                                                                            \
-        o0[(A) & 1] = T[((A) & 3) * 2][0] - T[((A) & 3) * 2][1];                                 \
-        p12[(A) & 1] = w4_row_mid(T[((A) & 3) * 2 + 1], T[((A) & 3) * 2]);                       \
-        o3[(A) & 1] = T[((A) & 3) * 2 + 1][0] - T[((A) & 3) * 2 + 1][1];                         \
-    }
-
-    constexpr int NQ = KC / 4;                // 2
-    constexpr int NSTEP = NQ * 16;            // 32 steps of 4 MFMAs
-    constexpr int AD = 4;                     // A fragments in flight (3 steps = 384 matrix-pipe cycles ahead); NSTEP % AD == 0
-    constexpr int NPIECE = C::PR * KC + C::WR;
-    static_assert(NPIECE + 2 <= NSTEP, "staging does not fit the chunk's steps");
-
-    // this lane's tile inside the block patch (constant over items) and operand bases
-    const int btx = wn % BTX, bty = wn / BTX;
-    const int ttx = btx * TWT + (m % TWT), tty = bty * C::THT + (m / TWT);
-    const int rbase = (2 * tty) * C::IWP + ttx + kq * C::CS;
-    const int aoff = kq * C::BM + m * 4;
-
-    // ---------------- pipeline prologue: chunks 0 and 1 into ring slots 0 and 1, chunk 2 into the registers ----------------
-    set_load_tile(lin0);
-    load_aff(s_frame);
-    __syncthreads();
-    {
-        float sc_[KC], sh_[KC];
-        pp_steps<0, NPIECE>([&](auto E) { W4_LOAD_PIECE(decltype(E)::value) });
-        W4_READ_AFF(sc_, sh_, s_tab, s_ch * KC)
-        float mk_[C::PR];
-#pragma unroll
-        for (int r = 0; r < C::PR; ++r) mk_[r] = ((vmask >> r) & 1u) ? __builtin_inff() : 0.f;
-        pp_steps<0, NPIECE>([&](auto E) { W4_NORM_PAIR(decltype(E)::value, sc_, sh_, mk_) W4_WRITE_PIECE(decltype(E)::value, il, wl) });
-        advance();
-        __syncthreads(); // a new frame's table (if the second chunk is already there)
-        pp_steps<0, NPIECE>([&](auto E) { W4_LOAD_PIECE(decltype(E)::value) });
-        W4_READ_AFF(sc_, sh_, s_tab, s_ch * KC)
-#pragma unroll
-        for (int r = 0; r < C::PR; ++r) mk_[r] = ((vmask >> r) & 1u) ? __builtin_inff() : 0.f;
-        pp_steps<0, NPIECE>([&](auto E) { W4_NORM_PAIR(decltype(E)::value, sc_, sh_, mk_) W4_WRITE_PIECE(decltype(E)::value, il + C::LDS_IN, wl + C::LDS_W) });
-        advance();
-        pp_steps<0, NPIECE>([&](auto E) { W4_LOAD_PIECE(decltype(E)::value) });
-        r_tab = s_tab; r_c0 = s_ch * KC; r_vmask = vmask;
-    }
-    __syncthreads();
-
-    f32x2 draw[8], tq[2][8]; // raw 4x4 patch and its column pass, as column pairs [row][pair]
-    f32x4 a[AD];
-    float vcur;
-    float o0[2], o3[2];      // B operands of the steps 4A (o0), 4A+1 / 4A+2 (p12) and 4A+3 (o3) of patch row A: slot A & 1
-    f32x2 p12[2];
-    // first operands of the very first chunk (later chunks get theirs during their predecessor's last steps)
-    int qb = rbase;
-    pp_steps<0, 4>([&](auto I) { W4_READ_RAW_ROW(draw, qb, decltype(I)::value) });
-#pragma unroll
-    for (int s0 = 0; s0 < AD - 1; ++s0) a[s0] = *reinterpret_cast<const f32x4*>(wl + (s0 * KC) * C::BM + aoff);
-    pp_steps<0, 8>([&](auto K) { W4_COLPASS2(tq[0], draw, decltype(K)::value) });
-    o0[1] = o3[1] = 0.f;
-    p12[1] = (f32x2){0.f, 0.f};
-    W4_ROW_ALL(tq[0], 0)
-
-    int buf = 0;                 // ring slot of the chunk being multiplied
-    bool pending = false;        // statistics of the previous tile wait in `red` for their cross-wave reduction
-    double* pend_dst = nullptr;
-    const size_t out_plane = (size_t)p.Hout * p.Wout;
-
-    for (int lin = lin0; lin < lin_end; lin += nloc) {
-        const int cb = lin % ncb, tile = (lin / ncb) % ntile;
-        const size_t fz = lin / (ncb * ntile);
-        const int co0 = cb * C::BM;
-        const int ox0 = p.rx0 + (tile % nbx) * C::PW, oy0 = p.ry0 + (tile / nbx) * C::PH;
-        const int opx = ox0 + 2 * ttx, opy = oy0 + 2 * tty;
-
-        // Output / residual addressing of the epilogue (needed from the tile's LAST chunk on, which requests the first half's
-        // residual rows).  Offsets cost no VALU: the lane part (row co0 + 4 kq of the frame at this lane's pixels) is the
-        // instruction's VGPR offset, the (M-tile, accumulator row) part a wave-uniform multiple of the plane in its SGPR offset.
-        // Lanes with nothing to store start 2 GB out -- past any frame (launch_conv refuses larger ones) -- so the descriptor
-        // drops their accesses and returns zeros for their loads; a layer without a residual has a zero-record descriptor.
-        constexpr unsigned W4_FAR = 0x80000000u;
-        const bool x4_map = ((p.Wout | p.rx0 | p.rx1) & 3) == 0;
-        const int par = m & 1;
-        const bool pix_ok = (opx < p.rx1) && (opy < p.ry1); // pixels past the region's end belong to another launch (or to nobody)
-        const bool two_y = opy + 1 < p.ry1;
-        const unsigned plane_ob = (unsigned)out_plane * 4u;
-        const unsigned rowb = (unsigned)(co0 + kq * 4) * plane_ob + (unsigned)(((size_t)opy * p.Wout + opx) * 4);
-        // x4 form: even lane = row y at its own pixels, odd lane = row y+1 starting at the even partner's pixels
-        const bool ok0 = x4_map ? (pix_ok && (par == 0 || two_y)) : pix_ok;
-        const unsigned lb0 = ok0 ? ((x4_map && par) ? rowb + (unsigned)p.Wout * 4u - 8u : rowb) : W4_FAR;
-        const unsigned lb1 = (pix_ok && two_y) ? rowb + (unsigned)p.Wout * 4u : W4_FAR; // second row of the dwordx2 form
-        f32x4 rq[2][2][4]; // residual rows [half][M-tile of the half][accumulator row] (x4 form)
-        auto res_desc = [&]() {
-            const float* gres = p.res ? p.res + fz * p.res_fs : p.out;
-            return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gres), 0, p.res ? (unsigned)((size_t)p.Cout * out_plane * 4) : 0u, 0x00020000);
-        };
-        auto request_res = [&](auto HALF, auto II) { // the 4 residual rows of M-tile 2h+ii: dwordx4 requests
-            constexpr int h = decltype(HALF)::value, ii = decltype(II)::value;
-            const __amdgpu_buffer_rsrc_t rres_ = res_desc();
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                rq[h][ii][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rres_, lb0, (unsigned)((h * 2 + ii) * 16 + r) * plane_ob, 0));
-        };
-
-        // accumulator quad of (M-tile i, Winograd position xi): a[(xi*4 + i)*4 .. +3].  The tile's first 16 steps take 0 as C:
-        // no zeroing pass over 256 registers; hence the chunk body exists twice (first chunk / accumulating chunks).
-        auto chunk_body = [&](auto FIRST, int ch) {
-            constexpr bool first_ = decltype(FIRST)::value;
-            const int nbuf = buf == 2 ? 0 : buf + 1, wbuf = buf == 0 ? 2 : buf - 1; // (buf+1)%3, (buf+2)%3
-            const float* wb = wl + buf * C::LDS_W;
-            const float* wbn = wl + nbuf * C::LDS_W;
-            float* ibw = il + wbuf * C::LDS_IN;
-            float* wbw = wl + wbuf * C::LDS_W;
-            // the registers hold chunk g+2 (each piece requested a whole chunk ago): its (scale, shift) and in-image mask;
-            // then the load side moves on to chunk g+3, whose pieces are requested as the registers are freed
-            float sc_[KC], sh_[KC];
-            W4_READ_AFF(sc_, sh_, r_tab, r_c0)
-            float q_mask[C::PR]; // upper clamp of the normalised value: +inf inside the image, 0 on the zero padding (v_med3_f32 does ReLU and padding in one)
-#pragma unroll
-            for (int r = 0; r < C::PR; ++r) q_mask[r] = ((r_vmask >> r) & 1u) ? __builtin_inff() : 0.f;
-            advance();
-            r_tab = s_tab; r_c0 = s_ch * KC; r_vmask = vmask;
-            // One wave per SIMD issues IN ORDER and nothing of its own hides behind an fp32 MFMA (tools/issue_probe.hip): a VALU
-            // instruction costs its 4 issue cycles wherever it stands and every MFMA -> VALU -> MFMA turn ~12 more; SALU 0.5 cycle;
-            // the first LDS / VMEM instruction of a gap ~6.  The step = 4 MFMAs of one Winograd position and channel quad:
-            //   MFMA 0 | gap A: the A fragment of step s+3 (one ds_read_b128)
-            //   MFMA 1 | gap B (steps 0..3 of a quad): one raw patch row of the next quad (two ds_read2_b32)
-            //   MFMA 2 | gap C (first step of a patch row only): ALL the VALU work of four steps, packed (see gap_c_body)
-            //   MFMA 3 | gap D (steps 0..23): LDS write of staging piece s + the request that refills its register
-            // MFMAs with an empty gap between them share one asm statement.  A B operand is written >= 1 step before its first
-            // use and the A fragments come from LDS behind hipcc's own lgkmcnt wait, so the asm MFMAs need no s_nop pad.
-            // (All memory instructions in ONE gap behind MFMA 3 measured slower, 872 against 890 frames/s.)
-// N MFMAs of one step (M-tiles I .. I+N-1) in ONE asm statement: hipcc pads every boundary between two asm statements
-// with an s_nop, so MFMAs with nothing to put between them are issued from one statement
-#define W4_ACC(I) "i"((xi * 4 + (I)) * 4), "i"((xi * 4 + (I)) * 4 + 3)
-#define W4_MFMA_1(I)                                                                             \
-            if constexpr (first_ && s_ < 16) {                                                   \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, 0" :: "v"(a[s_ % AD][I]), "v"(vcur), W4_ACC(I) : W4_AGPRS); \
-            } else {                                                                             \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" :: "v"(a[s_ % AD][I]), "v"(vcur), W4_ACC(I) : W4_AGPRS); \
-            }                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);
-#define W4_MFMA_2(I)                                                                             \
-            if constexpr (first_ && s_ < 16) {                                                   \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c3:%c4], %0, %2, 0\n\tv_mfma_f32_16x16x4_f32 a[%c5:%c6], %1, %2, 0"                  \
-                             :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(vcur), W4_ACC(I), W4_ACC((I) + 1) : W4_AGPRS); \
-            } else {                                                                             \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c3:%c4], %0, %2, a[%c3:%c4]\n\tv_mfma_f32_16x16x4_f32 a[%c5:%c6], %1, %2, a[%c5:%c6]" \
-                             :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(vcur), W4_ACC(I), W4_ACC((I) + 1) : W4_AGPRS); \
-            }                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);
-#define W4_MFMA_3(I)                                                                             \
-            if constexpr (first_ && s_ < 16) {                                                   \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c4:%c5], %0, %3, 0\n\tv_mfma_f32_16x16x4_f32 a[%c6:%c7], %1, %3, 0\n\t"            \
-                             "v_mfma_f32_16x16x4_f32 a[%c8:%c9], %2, %3, 0"                                                                 \
-                             :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(a[s_ % AD][(I) + 2]), "v"(vcur), W4_ACC(I), W4_ACC((I) + 1), W4_ACC((I) + 2) : W4_AGPRS); \
-            } else {                                                                             \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c4:%c5], %0, %3, a[%c4:%c5]\n\tv_mfma_f32_16x16x4_f32 a[%c6:%c7], %1, %3, a[%c6:%c7]\n\t" \
-                             "v_mfma_f32_16x16x4_f32 a[%c8:%c9], %2, %3, a[%c8:%c9]"                                                        \
-                             :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(a[s_ % AD][(I) + 2]), "v"(vcur), W4_ACC(I), W4_ACC((I) + 1), W4_ACC((I) + 2) : W4_AGPRS); \
-            }                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);
-#define W4_MFMA_4(I)                                                                             \
-            if constexpr (first_ && s_ < 16) {                                                   \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c5:%c6], %0, %4, 0\n\tv_mfma_f32_16x16x4_f32 a[%c7:%c8], %1, %4, 0\n\t"            \
-                             "v_mfma_f32_16x16x4_f32 a[%c9:%c10], %2, %4, 0\n\tv_mfma_f32_16x16x4_f32 a[%c11:%c12], %3, %4, 0"             \
-                             :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(a[s_ % AD][(I) + 2]), "v"(a[s_ % AD][(I) + 3]), "v"(vcur), \
-                                W4_ACC(I), W4_ACC((I) + 1), W4_ACC((I) + 2), W4_ACC((I) + 3) : W4_AGPRS);                                    \
-            } else {                                                                             \
-                asm volatile("v_mfma_f32_16x16x4_f32 a[%c5:%c6], %0, %4, a[%c5:%c6]\n\tv_mfma_f32_16x16x4_f32 a[%c7:%c8], %1, %4, a[%c7:%c8]\n\t" \
-                             "v_mfma_f32_16x16x4_f32 a[%c9:%c10], %2, %4, a[%c9:%c10]\n\tv_mfma_f32_16x16x4_f32 a[%c11:%c12], %3, %4, a[%c11:%c12]" \
-                             :: "v"(a[s_ % AD][I]), "v"(a[s_ % AD][(I) + 1]), "v"(a[s_ % AD][(I) + 2]), "v"(a[s_ % AD][(I) + 3]), "v"(vcur), \
-                                W4_ACC(I), W4_ACC((I) + 1), W4_ACC((I) + 2), W4_ACC((I) + 3) : W4_AGPRS);                                    \
-            }                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);
-            pp_steps<0, NSTEP>([&](auto S) {
-                constexpr int s_ = decltype(S)::value;
-                constexpr int c4 = s_ / 16, xi = s_ % 16, row = s_ / 4;
-                constexpr bool gap_b = xi < 4;                      // raw patch rows of the next quad
-                constexpr bool gap_c = (xi & 3) == 0;               // the VALU work of four steps
-                vcur = (xi & 3) == 0 ? o0[row & 1] : (xi & 3) == 3 ? o3[row & 1] : p12[row & 1][(xi & 3) - 1];
-                __builtin_amdgcn_sched_barrier(0);
-                auto gap_a_body = [&]() {   // the A fragment of step s_+AD-1 (this chunk, or the next chunk's first steps from ring slot nbuf)
-                    constexpr int sa = s_ + AD - 1;
-                    if constexpr (sa < NSTEP) {
-                        constexpr int n4_ = sa / 16, nx_ = sa % 16;
-                        a[sa % AD] = *reinterpret_cast<const f32x4*>(wb + (nx_ * KC + n4_ * 4) * C::BM + aoff);
-                    } else {
-                        constexpr int sb = sa - NSTEP, n4_ = sb / 16, nx_ = sb % 16;
-                        a[sa % AD] = *reinterpret_cast<const f32x4*>(wbn + (nx_ * KC + n4_ * 4) * C::BM + aoff);
-                    }
-                };
-                // gap B (steps 0..3 of a quad): one raw patch row of the next quad (the next CHUNK's first quad from ring slot nbuf
-                // when this is the chunk's last quad)
-                auto gap_b_body = [&]() {
-                    if constexpr (xi == 0) {
-                        qb = (c4 + 1 < NQ) ? buf * C::LDS_IN + rbase + (c4 + 1) * 4 * C::CS : nbuf * C::LDS_IN + rbase;
-                        asm volatile("" : "+v"(qb));
-                    }
-                    if constexpr (xi < 4) { W4_READ_RAW_ROW(draw, qb, xi) }
-                };
-                // gap C (first step of every patch row) carries the VALU work of FOUR steps -- every MFMA -> VALU -> MFMA turn costs
-                // a lone wave ~12 cycles on top of 4 per instruction (tools/issue_probe.hip) -- all of it packed: the B operands of the
-                // next patch row's four steps (3 instructions), the normalisation of staging pieces s_ .. s_+3 (2 v_pk_fma_f32 +
-                // 4 v_med3_f32), and in rows 1 and 2 four column-pass terms of the next quad
-                auto gap_c_body = [&]() {
-                    constexpr int rn = row + 1; // next patch row; & 3 inside its quad, whose column pass sits in tq[(rn / 4) & 1]
-                    W4_ROW_ALL(tq[(rn / 4) & 1], rn)
-                    W4_NORM_PAIR(s_, sc_, sh_, q_mask) W4_NORM_PAIR(s_ + 2, sc_, sh_, q_mask)
-                    if constexpr (xi == 4 || xi == 8) {
-                        W4_COLPASS2(tq[(c4 + 1) & 1], draw, xi - 4)
-                        W4_COLPASS2(tq[(c4 + 1) & 1], draw, xi - 4 + 1)
-                        W4_COLPASS2(tq[(c4 + 1) & 1], draw, xi - 4 + 2)
-                        W4_COLPASS2(tq[(c4 + 1) & 1], draw, xi - 4 + 3)
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                W4_MFMA_1(0)
-                gap_a_body();
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (gap_b && gap_c) { W4_MFMA_1(1) gap_b_body(); __builtin_amdgcn_sched_barrier(0); W4_MFMA_1(2) gap_c_body(); W4_MFMA_1(3) }
-                else if constexpr (gap_b) { W4_MFMA_1(1) gap_b_body(); __builtin_amdgcn_sched_barrier(0); W4_MFMA_2(2) }
-                else if constexpr (gap_c) { W4_MFMA_2(1) gap_c_body(); W4_MFMA_1(3) }
-                else { W4_MFMA_3(1) }
-                // gap D: staging of chunk g+2 into ring slot wbuf, and the request that refills the register with chunk g+3's piece
-                if constexpr (s_ < NPIECE) {
-                    W4_WRITE_PIECE(s_, ibw, wbw)
-                    W4_LOAD_PIECE(s_)
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            });
-#undef W4_MFMA_1
-#undef W4_MFMA_2
-#undef W4_MFMA_3
-#undef W4_MFMA_4
-#undef W4_ACC
-            __syncthreads();
-            buf = nbuf;
-            if (ch == 0 && pending) { // previous tile's statistics: every wave's partial sums are in `red` since before this barrier
-                if (tid < C::BM) {
-                    double s = 0.0, q = 0.0;
-#pragma unroll
-                    for (int w = 0; w < WN; ++w) {
-                        s += (double)red[(w * C::BM + tid) * 2];
-                        q += (double)red[(w * C::BM + tid) * 2 + 1];
-                    }
-                    atomicAdd(pend_dst + (size_t)tid * 2, s);
-                    atomicAdd(pend_dst + (size_t)tid * 2 + 1, q);
-                }
-                pending = false;
-            }
-        };
-        chunk_body(std::true_type{}, 0);
-#pragma unroll 1
-        for (int ch = 1; ch < nchunk; ++ch) chunk_body(std::false_type{}, ch);
-
-        // ---------------- epilogue: Y = A^T M A per lane, residual, float2 row stores, statistics ----------------
-        // an 8-pass MFMA's D needs 12 wait states before anything but the next accumulating MFMA touches it (hipcc pads nothing
-        // behind an asm statement)
-        asm volatile("s_nop 11" ::: W4_AGPRS);
-        float* __restrict__ gout = p.out + fz * p.out_fs;
-        const unsigned frame_bytes = (unsigned)((size_t)p.Cout * out_plane * 4);
-        const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(gout, 0, frame_bytes, 0x00020000);
-        // Two halves (M-tiles 0-1, then 2-3), each in two phases.  Phase 1: the output transform of the half's 32 (row, tile)
-        // pairs into registers, two accumulator rows at a time on v_pk_add_f32 (a lone wave pays 4 cycles per VALU instruction,
-        // MFMA shadow or not: tools/issue_probe.hip).  Phase 2: residual add, stores, statistics.  The residual rows are
-        // requested long before they are added: the first half's at the top of the tile's last chunk, the second half's
-        // between the first half's two phases -- older than every store of the epilogue, so waiting for them never waits for
-        // a store (loads and stores share vmcnt).  The live state of the chunk pipeline (~130 VGPRs) leaves room for both
-        // halves' residual rows and one half's outputs.
-        // X4 (maps whose width is a multiple of 4): the tile's epilogue is bound by the CU's store ISSUE rate -- four waves x 32
-        // dwordx2 stores of 4 x 128-byte segments each took ~11 k cycles per tile (stamps).  Neighbouring lanes (tiles x, x+1)
-        // swap half their 2x2 outputs (w4_pair_rows: four v_cndmask_b32_dpp) so that the even lane owns row y and the odd lane
-        // row y+1 of the pair's 4 pixels: one dwordx4 store (and one dwordx4 residual load) per lane and row instead of two dwordx2.
-        f32x2 y2[2][2][4]; // [M-tile of the half][row pair][output pixel of the 2x2 tile], .x = row 2 rp, .y = row 2 rp + 1
-        auto transform_half = [&](auto HALF) {
-            constexpr int h = decltype(HALF)::value;
-            pp_steps<0, 2>([&](auto II) {
-                constexpr int ii = decltype(II)::value, i = h * 2 + ii;
-                pp_steps<0, 2>([&](auto RP) {
-                    constexpr int rp = decltype(RP)::value;
-                    f32x2 mm[16], t0[4], t1[4];
-                    w4_acc_read32<i, 2 * rp>(mm);
-#pragma unroll
-                    for (int a_ = 0; a_ < 4; ++a_) {
-                        t0[a_] = mm[a_ * 4 + 0] + mm[a_ * 4 + 1] + mm[a_ * 4 + 2];
-                        t1[a_] = mm[a_ * 4 + 1] - mm[a_ * 4 + 2] - mm[a_ * 4 + 3];
-                    }
-                    y2[ii][rp][0] = t0[0] + t0[1] + t0[2]; y2[ii][rp][1] = t1[0] + t1[1] + t1[2];
-                    y2[ii][rp][2] = t0[1] - t0[2] - t0[3]; y2[ii][rp][3] = t1[1] - t1[2] - t1[3];
-                });
-            });
-        };
-        auto finish_mt = [&](auto HALF, auto II0, auto II1, auto X4) { // M-tiles 2h+II0 .. 2h+II1-1
-            constexpr int h = decltype(HALF)::value, ii0 = decltype(II0)::value, ii1 = decltype(II1)::value;
-            constexpr bool x4 = decltype(X4)::value;
-            f32x2 r0[2][4], r1[2][4];
-            if constexpr (!x4) { // maps whose width is not a multiple of 4: two dwordx2 rows per lane, requested here
-                const __amdgpu_buffer_rsrc_t rres_ = res_desc();
-#pragma unroll
-                for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const unsigned so = (unsigned)((h * 2 + ii) * 16 + r) * plane_ob;
-                        r0[ii][r] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rres_, lb0, so, 0));
-                        r1[ii][r] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rres_, lb1, so, 0));
-                    }
-            }
-#pragma unroll
-            for (int ii = ii0; ii < ii1; ++ii) {
-                float ssum[4], ssq[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const unsigned so = (unsigned)((h * 2 + ii) * 16 + r) * plane_ob;
-                    const float y_0 = y2[ii][r >> 1][0][r & 1], y_1 = y2[ii][r >> 1][1][r & 1], y_2 = y2[ii][r >> 1][2][r & 1], y_3 = y2[ii][r >> 1][3][r & 1];
-                    if constexpr (x4) {
-                        f32x4 v = w4_pair_rows(y_0, y_1, y_2, y_3);
-                        v += rq[h][ii][r];
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b128(rout, 0u, 0, 0)), v), rout, lb0, so, 0);
-                        const f32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-                        const f32x2 s2 = lo + hi, q2 = __builtin_elementwise_fma(hi, hi, lo * lo);
-                        ssum[r] = ok0 ? s2[0] + s2[1] : 0.f;
-                        ssq[r] = ok0 ? q2[0] + q2[1] : 0.f;
-                    } else {
-                        const float y00 = y_0 + r0[ii][r][0], y01 = y_1 + r0[ii][r][1];
-                        const float y10 = y_2 + r1[ii][r][0], y11 = y_3 + r1[ii][r][1];
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b64(rout, 0u, 0, 0)), (f32x2){y00, y01}), rout, lb0, so, 0);
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b64(rout, 0u, 0, 0)), (f32x2){y10, y11}), rout, lb1, so, 0);
-                        float s_ = y00 + y01, q_ = y00 * y00 + y01 * y01; // same summation order as wino_mfma: row y, then row y+1
-                        if (lb1 != W4_FAR) { s_ += y10; q_ += y10 * y10; s_ += y11; q_ += y11 * y11; }
-                        ssum[r] = ok0 ? s_ : 0.f;
-                        ssq[r] = ok0 ? q_ : 0.f;
-                    }
-                }
-                if (p.stat_acc) {
-                    float rs[4], rqq[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { rs[r] = row16_sum(ssum[r]); rqq[r] = row16_sum(ssq[r]); }
-                    if (m == 0) { // rows (h*2+ii)*16 + kq*4 + 0..3: 8 consecutive floats of `red`
-                        float* dst = red + (wn * C::BM + (h * 2 + ii) * 16 + kq * 4) * 2;
-                        *reinterpret_cast<f32x4*>(dst) = (f32x4){rs[0], rqq[0], rs[1], rqq[1]};
-                        *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){rs[2], rqq[2], rs[3], rqq[3]};
-                    }
-                }
-            }
-        };
-        {
-            using I0 = std::integral_constant<int, 0>;
-            using I1 = std::integral_constant<int, 1>;
-            using I2 = std::integral_constant<int, 2>;
-            if (x4_map) {
-                // every residual request is >= one transform + one M-tile's finish (~3.5 k cycles) ahead of its add; 32 registers
-                // rotate through the four M-tiles' rows
-                request_res(I0{}, I0{});
-                request_res(I0{}, I1{});
-                transform_half(I0{});
-                finish_mt(I0{}, I0{}, I1{}, std::true_type{});
-                request_res(I1{}, I0{});
-                finish_mt(I0{}, I1{}, I2{}, std::true_type{});
-                request_res(I1{}, I1{});
-                transform_half(I1{});
-                finish_mt(I1{}, I0{}, I2{}, std::true_type{});
-            } else {
-                transform_half(I0{});
-                finish_mt(I0{}, I0{}, I2{}, std::false_type{});
-                transform_half(I1{});
-                finish_mt(I1{}, I0{}, I2{}, std::false_type{});
-            }
-        }
-        if (p.stat_acc) {
-            pending = true;
-            pend_dst = p.stat_acc + fz * p.stat_fs + ((size_t)(blockIdx.x % NREP) * p.stat_C + co0) * 2;
-        }
-    }
-    if (pending) {
-        __syncthreads();
-        if (tid < C::BM && blockIdx.x >= 0) {
-            double s = 0.0, q = 0.0;
-#pragma unroll
-            for (int w = 0; w < WN; ++w) {
-                s += (double)red[(w * C::BM + tid) * 2];
-                q += (double)red[(w * C::BM + tid) * 2 + 1];
-            }
-            atomicAdd(pend_dst + (size_t)tid * 2, s);
-            atomicAdd(pend_dst + (size_t)tid * 2 + 1, q);
-        }
-    }
-#undef W4_LOAD_PIECE
-#undef W4_NORM_PAIR
-#undef W4_READ_AFF
-#undef W4_READ_RAW_ROW
-#undef W4_WRITE_PIECE
-#undef W4_COLPASS2
-#undef W4_ROW_ALL
-}
-
-// ------------------------------------------------------------------------------------------
-// 1x1 contractions (the three ConvTranspose(k = s) upsamplers and the shared head) as a persistent,
-// barrier-free GEMM:  D[rows, pixel] = W[rows, K] * relu(norm(X[K, pixel]))
-// * the [K][BM] weight slab of the workgroup's row block stays in LDS for the whole launch
-//   (head: 320 x 96, deconv3: 256 x 128 -> up to 147 KB of the 160 KB)
-// * activations never touch LDS: lane (pixel m, channel c+kq) loads its B operand straight from
-//   global memory into a 4-step register ring, applies the producer's normalisation + ReLU in
-//   registers, and feeds the MFMAs -- every wave streams on its own, no workgroup barrier
-// * pixels are flattened (a 1x1 conv has no neighbourhood), N-tile = 16 consecutive pixels
-// ------------------------------------------------------------------------------------------
-// PREC (the reference's deployed path is TensorRT FP16, framework/trt_utils.py:30): 0 = fp32 MFMA (exact);
-// 1 = split-bf16 "bf16x3": x = hi + lo with hi = bf16(x), lo = bf16(x - hi), a*b ~ a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on
-// v_mfma_f32_16x16x16_bf16 with fp32 accumulation (~2^-16 relative per product: fp32-equivalent for this network, three MFMAs at
-// 8x the fp32-MFMA rate); 2 = plain bf16 operands (one MFMA, ~2^-8 per product); 3 = fp16 operands on v_mfma_f32_16x16x16_f16
-// (~2^-11 per product: the arithmetic of the reference's TensorRT FP16 engines).
-// Activations stay fp32 in HBM: normalise + ReLU in fp32, then split / round while staging.  The weight slab in LDS is
-// [K/16][hi|lo][k-group 0..3][BMP rows][4 bf16] -- the same bytes as the fp32 slab.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) // v_cvt_pk_bf16_f32 (round to nearest even)
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
-__device__ __forceinline__ unsigned pk_f16(float a, float b) // round to nearest even (v_cvt_pk_f16_f32 on gfx950)
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, f16x2_t));
-}
-// one 16-deep MFMA of the reduced-precision 1x1 path: bf16 operands (PREC 1, 2) or fp16 operands (PREC 3), fp32 accumulate
-template <int PREC>
-__device__ __forceinline__ f32x4 mfma_lp(const s16x4 a, const s16x4 b, const f32x4 c)
-{
-    if constexpr (PREC == 3) return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, a), __builtin_bit_cast(f16x4_t, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-}
-
-// IO16 (pp_set_precision 4, "fp16s": fp16 operands AND fp16 storage of the [320,H,W] concat buffer the upsamplers write and the head
-// reads -- the largest tensor of the network, 205 MB per frame in fp32): bit 0 = the input tensor is fp16, bit 1 = the output is.
-// EPI_HEAD_CLS (deferred head, MT = 1): the head's `na` cls rows alone -- the slab is gathered out of the committed full head image
-// (cls row of anchor a = tile row 4 (9 + a) + 3 of head_tile_row), so there is one weight image and the cls logits are bit-identical to
-// the full head's: same A and B values, same channel-quad order, same bias add.  One MFMA per 256 B loaded: the kernel is bound by the
-// bytes in flight per CU: it runs two workgroups per CU (a 128-register budget; at the 64 registers of four per CU the ring spills)
-// and PDX varies the ring depth.
-template <int MT, int NT, int EPI, int PREC = 0, int IO16 = 0, int PDX = 0>
-__global__ void __launch_bounds__(512, EPI == EPI_HEAD_CLS ? 4 : 2) gemm1x1(const ConvP p)
-{
-    constexpr bool IN16 = (IO16 & 1) != 0, OUT16 = (IO16 & 2) != 0;
-    static_assert(IO16 == 0 || PREC != 0, "16-bit storage comes with the 16-bit operand path");
-    static_assert(!OUT16 || EPI != EPI_HEAD, "the head's logits stay fp32");
-    constexpr int BM = MT * 16;
-    constexpr int BMP = BM + ((BM % 32 == 0) ? 16 : 0);
-    static_assert(EPI != EPI_HEAD_CLS || (MT == 1 && PREC == 0 && IO16 == 0), "the cls-only head pass is one fp32 M-tile");
-    constexpr int PD = PDX ? PDX : (MT >= 8) ? 4 : 8; // B-operand ring depth (steps in flight); even, K % (4 * PD) == 0; 128 accumulator registers leave room for 4
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* wl = smem;                         // [K][BMP]
-    const int K = p.Cin;
-    float* sc_all = wl + (size_t)K * BMP;     // [8 waves][2][K]  wave-private (scale, shift)
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // scalar: frame, item and the buffer descriptor stay in SGPRs
-    const int m = lane & 15, kq = lane >> 4;
-    float* scl = sc_all + (size_t)wave * 2 * K;
-    float* shl = scl + K;
-
-    const int ncb = (p.Cout + BM - 1) / BM;
-    // XCD-aware: workgroups are dealt round-robin over the 8 XCDs, so the ncb channel blocks that stream the
-    // SAME pixels are given ids 8 apart -- they share one L2 instead of fetching the input once per XCD
-    const bool xcd_ok = gridDim.x % (8 * ncb) == 0;
-    const int xj = blockIdx.x >> 3, xk = blockIdx.x & 7;
-    const int cb = xcd_ok ? xj % ncb : blockIdx.x % ncb;
-    const int wi = xcd_ok ? xk + 8 * (xj / ncb) : blockIdx.x / ncb, nworkers = gridDim.x / ncb;
-    if (wi >= nworkers) return;
-    const int co0 = cb * BM;
-    if constexpr (EPI == EPI_HEAD_CLS) { // column a of the slab = the cls row of anchor a in the full image [row block][K][w_bmp]; columns na .. 15 are zero
-        for (int e = tid; e < K * BMP; e += 512) {
-            const int k = e / BMP, a = e - k * BMP, t = 4 * (9 + a) + 3;
-            wl[e] = a < p.n_cls ? p.w[((size_t)(t / p.w_bm) * K + k) * p.w_bmp + t % p.w_bm] : 0.f;
-        }
-    } else {
-        const f32x4* g = reinterpret_cast<const f32x4*>(p.w) + (size_t)cb * ((size_t)K * BMP / 4);
-        f32x4* d = reinterpret_cast<f32x4*>(wl);
-        for (int e = tid; e < K * BMP / 4; e += 512) d[e] = g[e];
-    }
-    __syncthreads(); // the only workgroup barrier
-    __builtin_amdgcn_s_setprio(1); // item prologue / epilogue run at raised priority, the MFMA stream at 0
-
-    const int HW = p.Hout * p.Wout;
-    const int items_per_frame = (HW + NT * 16 - 1) / (NT * 16);
-    const int total = items_per_frame * p.nb;
-    const size_t plane = (size_t)HW;
-    const int gw = wi * 8 + wave, gstride = nworkers * 8;
-
-    // per-row partial statistics: the plain epilogue keeps one pair per tile row, the pixel-shuffle epilogues fold a
-    // lane's 4 rows (the s^2 positions of ONE output channel) into slot 0 -- 4x fewer live registers at MT = 8
-    constexpr int SR = (EPI == EPI_PLAIN) ? 4 : 1;
-    float ssum[MT][SR], ssq[MT][SR];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < SR; ++r) { ssum[i][r] = 0.f; ssq[i][r] = 0.f; }
-    int stat_frame = -1, pre_frame = -1;
-    auto flush_stats = [&](int frame) {
-        if (EPI == EPI_HEAD || EPI == EPI_HEAD_CLS || !p.stat_acc || frame < 0) return;
-        double* base = p.stat_acc + (size_t)frame * p.stat_fs + ((size_t)((blockIdx.x * 8 + wave) % NREP) * p.stat_C) * 2;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < SR; ++r) {
-                float s = ssum[i][r], q = ssq[i][r];
-                s = row16_sum(s);
-                q = row16_sum(q);
-                const int row = co0 + i * 16 + kq * 4 + r;
-                int ch = row;
-                bool lead = (m == 0);
-                if (EPI == EPI_UP2) { ch = row >> 2; lead = lead && r == 0; }
-                if (EPI == EPI_UP4) { ch = row >> 4; lead = lead && r == 0; }
-                if (lead && row < p.Cout) {
-                    atomicAdd(base + (size_t)ch * 2, (double)s);
-                    atomicAdd(base + (size_t)ch * 2 + 1, (double)q);
-                }
-                ssum[i][r] = 0.f;
-                ssq[i][r] = 0.f;
-            }
-    };
-
-    const int aoff = kq * BMP + m;
-    static_assert(NT == 4, "gemm1x1 is written for 4 interleaved N-tiles");
-    const int nsteps = K / 4;
-    const unsigned bstep = 16u * (unsigned)plane; // bytes between channel quads
-    // ---- load-side state of the item whose B quads are being requested.  At an item boundary it runs one item
-    //      AHEAD: the next item's first PD-1 quads are requested BEFORE this item's epilogue, so they are older than
-    //      its stores in the (in-order) vmcnt queue and their latency hides under the epilogue.
-    __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, 0x7FFFFFFF, 0x00020000);
-    unsigned bvoff = 0u;
-    f32x4 bq[PD];
-    auto set_load_item = [&](int it) {
-        const int f_ = __builtin_amdgcn_readfirstlane(it / items_per_frame); // the division runs on the VALU: pin the
-        const int px_ = __builtin_amdgcn_readfirstlane((it - f_ * items_per_frame) * (NT * 16)) + 4 * m; // results in SGPRs
-        // descriptor base pinned to SGPRs (a VGPR-resident descriptor costs a waterfall loop per load)
-        const uint64_t bp_ = IN16 ? (uint64_t)(reinterpret_cast<const _Float16*>(p.in) + (size_t)f_ * p.in_fs) : (uint64_t)(p.in + (size_t)f_ * p.in_fs);
-        const uint64_t bps_ = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bp_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bp_);
-        rb = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(bps_), 0, 0x7FFFFFFF, 0x00020000);
-        bvoff = ((unsigned)kq * (unsigned)plane + (unsigned)(px_ < HW ? px_ : 0)) * (IN16 ? 2u : 4u);
-    };
-#define G1_LOADB(S, SLOT) bq[SLOT] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, bvoff, (unsigned)(S) * bstep, 0));
-#define G1_PREP(S, SLOT, PAR)                                                                    \
-    {                                                                                            \
-        _Pragma("unroll") for (int i = 0; i < MT; ++i) a[PAR][i] = wl[(S) * 4 * BMP + aoff + i * 16]; \
-        if (p.pre != PRE_RAW) {                                                                  \
-            const float sc = scl[(S) * 4 + kq], sh = shl[(S) * 4 + kq];                          \
-            _Pragma("unroll") for (int j = 0; j < NT; ++j) b[PAR][j] = fmaxf(fmaf(bq[SLOT][j], sc, sh), 0.f); \
-        } else {                                                                                 \
-            _Pragma("unroll") for (int j = 0; j < NT; ++j) b[PAR][j] = bq[SLOT][j];              \
-        }                                                                                        \
-    }
-#define G1_MFMAS(PAR)                                                                            \
-    {                                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        _Pragma("unroll") for (int i = 0; i < MT; ++i)                                           \
-            _Pragma("unroll") for (int j = 0; j < NT; ++j)                                       \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[PAR][i], b[PAR][j], acc[i][j], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-    }
-    if constexpr (PREC == 0) {
-    if (gw < total) {
-        set_load_item(gw);
-#pragma unroll
-        for (int s0 = 0; s0 < PD - 1; ++s0) G1_LOADB(s0, s0)
-    }
-    }
-    for (int item = gw; item < total; item += gstride) {
-        const int fr = __builtin_amdgcn_readfirstlane(item / items_per_frame);
-        const int pix0 = __builtin_amdgcn_readfirstlane((item - fr * items_per_frame) * (NT * 16));
-        if (fr != stat_frame) { flush_stats(stat_frame); stat_frame = fr; }
-        if (p.pre != PRE_RAW && fr != pre_frame) {
-            for (int c = lane; c < K; c += 64) {
-                if (p.pre == PRE_STATS) {
-                    const double* pa = p.pre_acc + (size_t)fr * p.pre_fs;
-                    double s = 0.0, q = 0.0;
-#pragma unroll
-                    for (int r = 0; r < NREP; ++r) { s += pa[((size_t)r * K + c) * 2]; q += pa[((size_t)r * K + c) * 2 + 1]; }
-                    const double mean = s * p.pre_inv_n;
-                    double var = q * p.pre_inv_n - mean * mean;
-                    var = var > 0.0 ? var : 0.0;
-                    const double rstd = 1.0 / sqrt(var + (double)p.eps);
-                    scl[c] = (float)rstd;
-                    shl[c] = (float)(-mean * rstd);
-                } else {
-                    scl[c] = p.pre_scale[(size_t)fr * p.aff_fs + c];
-                    shl[c] = p.pre_shift[(size_t)fr * p.aff_fs + c];
-                }
-            }
-            pre_frame = fr;
-        }
-        // N-tile j of this item = pixels {pix0 + 4m + j}: one dwordx4 per lane and step feeds all four tiles
-        const int pxb = pix0 + 4 * m;       // first of this lane's 4 pixels (HW % 4 == 0: all four valid or none)
-        const bool pok = pxb < HW;
-        f32x4 acc[MT][NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-        if constexpr (PREC == 0) {
-        // K % (4 * PD) == 0 (layer_menu offers this kernel only then): no tail steps.
-        // Per step: the B quad of step st+PD-1 is requested (buffer load: lane offset in a VGPR, the channel-quad
-        // offset in an SGPR -- no address VALU), the A fragments and the normalised B values of step st+1 are
-        // prepared in the shadow of this step's MT*NT MFMAs, then the MFMAs issue.  The last ring is peeled so
-        // that no step carries a run-time condition.
-        float a[2][MT], b[2][NT];
-        G1_PREP(0, 0, 0)
-        __builtin_amdgcn_s_setprio(0); // the MFMA stream yields issue slots to the other wave's short non-MFMA segments
-        int sb = 0;
-        for (; sb < nsteps - PD; sb += PD) {
-#pragma unroll
-            for (int u = 0; u < PD; ++u) {
-                G1_LOADB(sb + u + PD - 1, (u + PD - 1) % PD)
-                G1_PREP(sb + u + 1, (u + 1) % PD, (u + 1) & 1)
-                G1_MFMAS(u & 1)
-            }
-        }
-        // last ring: only its first step still has a quad to request, the last one nothing to prepare
-        G1_LOADB(sb + PD - 1, PD - 1)
-#pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            if (u + 1 < PD) G1_PREP(sb + u + 1, (u + 1) % PD, (u + 1) & 1)
-            G1_MFMAS(u & 1)
-        }
-
-        __builtin_amdgcn_s_setprio(1);
-        if (item + gstride < total) { // next item's first quads, ahead of this item's stores
-            set_load_item(item + gstride);
-#pragma unroll
-            for (int s0 = 0; s0 < PD - 1; ++s0) G1_LOADB(s0, s0)
-        }
-
-        } else {
-            // ---- reduced-precision K loop: 16 input channels per block = one bf16 MFMA depth.  Lane (pixel group m, k-group kq)
-            //      loads channels kq*4 .. kq*4+3 of the block for its 4 pixels (4 dwordx4, block kb+1 in flight behind block kb),
-            //      normalises in fp32, packs 4 channels of one pixel into one B operand (two v_cvt_pk_bf16_f32) ----
-            set_load_item(item);
-            constexpr unsigned EB = IN16 ? 2u : 4u;                                 // bytes per input element
-            const unsigned bvq = bvoff + (unsigned)kq * 3u * (unsigned)plane * EB; // (kq*4*plane + pixel)*EB: bvoff already holds kq*plane
-            const unsigned cstep = (unsigned)plane * EB;                            // bytes between channels
-            const uint2* wl2 = reinterpret_cast<const uint2*>(wl);
-            const int nkb = K / 16;
-            f32x4 q0[4], q1[4];
-            uint2 g0[4], g1[4]; // fp16 input: a lane's 4 pixels of a channel are 8 bytes, kept as they arrive
-#define G1_LP_LOAD(Q, G, KB) _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                  \
-        if constexpr (IN16) G[t] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rb, bvq, (unsigned)((KB) * 16 + t) * cstep, 0)); \
-        else Q[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, bvq, (unsigned)((KB) * 16 + t) * cstep, 0)); \
-    }
-            // RAW (compile-time twin of the loop, chosen per launch: the upsamplers read raw block outputs, the fused head normalises):
-            // no (scale, shift) reads and no fma / max; an fp16 raw input is already the operand's arithmetic -- channel pairs of
-            // pixel j are picked out of the (pixel-pair) words with two v_perm_b32, no conversion at all
-#define G1_LP_BLOCK(Q, G, KB, RAW)                                                               \
-    {                                                                                            \
-        f32x4 sc4 = (f32x4){1.f, 1.f, 1.f, 1.f}, sh4 = (f32x4){0.f, 0.f, 0.f, 0.f};              \
-        if constexpr (!(RAW)) { sc4 = *reinterpret_cast<const f32x4*>(scl + (KB) * 16 + kq * 4); sh4 = *reinterpret_cast<const f32x4*>(shl + (KB) * 16 + kq * 4); } \
-        s16x4 bh[NT], bl[NT];                                                                    \
-        _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                         \
-            if constexpr (IN16 && (RAW)) {                                                       \
-                const unsigned sel_ = (j & 1) ? 0x07060302u : 0x05040100u;                       \
-                const unsigned h0 = __builtin_amdgcn_perm((j & 2) ? G[1].y : G[1].x, (j & 2) ? G[0].y : G[0].x, sel_); \
-                const unsigned h1 = __builtin_amdgcn_perm((j & 2) ? G[3].y : G[3].x, (j & 2) ? G[2].y : G[2].x, sel_); \
-                bh[j] = __builtin_bit_cast(s16x4, (uint2){h0, h1});                              \
-            } else {                                                                             \
-                float v_[4];                                                                     \
-                _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                  \
-                    float x_;                                                                    \
-                    if constexpr (IN16) x_ = (float)__builtin_bit_cast(f16x4_t, G[t])[j]; else x_ = Q[t][j]; \
-                    v_[t] = (RAW) ? x_ : fmaxf(fmaf(x_, sc4[t], sh4[t]), 0.f);                   \
-                }                                                                                \
-                const unsigned h0 = (PREC == 3) ? pk_f16(v_[0], v_[1]) : pk_bf16(v_[0], v_[1]);  \
-                const unsigned h1 = (PREC == 3) ? pk_f16(v_[2], v_[3]) : pk_bf16(v_[2], v_[3]);  \
-                bh[j] = __builtin_bit_cast(s16x4, (uint2){h0, h1});                              \
-                if constexpr (PREC == 1) {                                                       \
-                    const float l0 = v_[0] - __uint_as_float(h0 << 16), l1 = v_[1] - __uint_as_float(h0 & 0xFFFF0000u); \
-                    const float l2 = v_[2] - __uint_as_float(h1 << 16), l3 = v_[3] - __uint_as_float(h1 & 0xFFFF0000u); \
-                    bl[j] = __builtin_bit_cast(s16x4, (uint2){pk_bf16(l0, l1), pk_bf16(l2, l3)}); \
-                }                                                                                \
-            }                                                                                    \
-        }                                                                                        \
-        _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                         \
-            const s16x4 ah = __builtin_bit_cast(s16x4, wl2[(((KB) * 2 + 0) * 4 + kq) * BMP + i * 16 + m]); \
-            s16x4 al = ah;                                                                       \
-            if constexpr (PREC == 1) al = __builtin_bit_cast(s16x4, wl2[(((KB) * 2 + 1) * 4 + kq) * BMP + i * 16 + m]); \
-            _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                     \
-                acc[i][j] = mfma_lp<PREC>(ah, bh[j], acc[i][j]);                                 \
-                if constexpr (PREC == 1) {                                                       \
-                    acc[i][j] = mfma_lp<PREC>(ah, bl[j], acc[i][j]);                             \
-                    acc[i][j] = mfma_lp<PREC>(al, bh[j], acc[i][j]);                             \
-                }                                                                                \
-            }                                                                                    \
-        }                                                                                        \
-    }
-#define G1_LP_LOOP(RAW)                                                                          \
-    G1_LP_LOAD(q0, g0, 0)                                                                        \
-    for (int kb = 0; kb < nkb; kb += 2) { /* K % 32 == 0: whole pairs of blocks */               \
-        G1_LP_LOAD(q1, g1, kb + 1)                                                               \
-        G1_LP_BLOCK(q0, g0, kb, RAW)                                                             \
-        if (kb + 2 < nkb) G1_LP_LOAD(q0, g0, kb + 2)                                             \
-        G1_LP_BLOCK(q1, g1, kb + 1, RAW)                                                         \
-    }
-            __builtin_amdgcn_s_setprio(0);
-            if (p.pre == PRE_RAW) { G1_LP_LOOP(true) } else { G1_LP_LOOP(false) }
-            __builtin_amdgcn_s_setprio(1);
-#undef G1_LP_LOOP
-#undef G1_LP_LOAD
-#undef G1_LP_BLOCK
-        }
-
-        // ---- epilogue of this item (lane m owns pixels pxb .. pxb+3, one per N-tile) ----
-        // OUT16: `gout` counts in ELEMENTS of the output tensor either way; st4 rounds four values to fp16 and stores 8 bytes
-        float* gout = OUT16 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(p.out) + (size_t)fr * p.out_fs) : p.out + (size_t)fr * p.out_fs;
-        auto st4 = [&](size_t off, const f32x4 v) __attribute__((always_inline)) {
-            if constexpr (OUT16) {
-                const uint2 h = {pk_f16(v[0], v[1]), pk_f16(v[2], v[3])};
-                *reinterpret_cast<uint2*>(reinterpret_cast<_Float16*>(gout) + off) = h;
-            } else {
-                *reinterpret_cast<f32x4*>(gout + off) = v;
-            }
-        };
-        float* gbox = p.out_box ? p.out_box + (size_t)fr * p.box_fs : nullptr;
-        float* gdir = p.out_dir ? p.out_dir + (size_t)fr * p.dir_fs : nullptr;
-        bool up4_done = false;
-        if constexpr (EPI == EPI_UP4) {
-            if ((p.Wout & 3) == 0) {
-                // ConvTranspose k = s = 4: a lane's 4 pixels x 4 dx are 64 CONTIGUOUS output bytes (out[co][4y+dy][4x .. 4x+15]), but stored
-                // as it stands (one 16-byte piece per N-tile j) an instruction writes 16 bytes of each of 16 runs -- 64 scattered
-                // 16-byte requests.  The four lanes of a quad transpose their 4 x 4 pieces (out[k] on lane t = piece t of lane
-                // 4q + k's run: two butterfly stages of DPP quad permutes) so that instruction k writes WHOLE 64-byte runs, four
-                // lanes each.  All lanes take part (a DPP source must be live); a run beyond the map is dropped at the store.
-                up4_done = true;
-                int kq_e = kq;
-                asm volatile("" : "+v"(kq_e));
-                const int t_ = m & 3;
-                size_t ko[4];
-                bool kok[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int pk = pix0 + 4 * ((m & ~3) + k); // first pixel of lane 4q + k
-                    const int yk = pk / p.Wout, xk = pk - yk * p.Wout;
-                    kok[k] = pk < HW;
-                    ko[k] = (size_t)(4 * yk) * ((size_t)p.Wout * 4) + 4 * (size_t)xk + 4 * t_; // run of lane 4q + k starts at output x = 4 xk; this lane writes its piece t
-                }
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    const int row0 = co0 + i * 16 + kq_e * 4;
-                    if (row0 >= p.Cout) continue; // wave-uniform per kq group of 16 lanes: quads stay whole
-                    const int co = row0 >> 4, dy = (row0 >> 2) & 3;
-                    f32x4 o4[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float a0 = acc[i][0][r], a1 = acc[i][1][r], a2 = acc[i][2][r], a3 = acc[i][3][r];
-                        if (pok) {
-                            ssum[i][0] += (a0 + a1) + (a2 + a3);
-                            ssq[i][0] += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-                        }
-                        // stage 1: swap the low bit of (register j, lane t); stage 2: the high bit
-                        const float x0 = dpp_f32<0xB1>(a1), x1 = dpp_f32<0xB1>(a0), x2 = dpp_f32<0xB1>(a3), x3 = dpp_f32<0xB1>(a2); // lane ^ 1
-                        const bool odd = t_ & 1, hi = t_ & 2;
-                        const float c0 = odd ? x0 : a0, c1 = odd ? a1 : x1, c2 = odd ? x2 : a2, c3 = odd ? a3 : x3;
-                        const float z0 = dpp_f32<0x4E>(c2), z1 = dpp_f32<0x4E>(c3), z2 = dpp_f32<0x4E>(c0), z3 = dpp_f32<0x4E>(c1); // lane ^ 2
-                        o4[0][r] = hi ? z0 : c0; o4[1][r] = hi ? z1 : c1; o4[2][r] = hi ? c2 : z2; o4[3][r] = hi ? c3 : z3;
-                    }
-                    const size_t ob = (size_t)co * plane * 16 + (size_t)dy * ((size_t)p.Wout * 4);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (kok[k]) st4(ob + ko[k], o4[k]);
-                }
-            }
-        }
-        if (pok && !up4_done) {
-            // the row-dependent addresses and biases are lane constants: without this the compiler hoists all of
-            // them out of the item loop and spills them around the MFMA loop; recomputing per item is ~free
-            int kq_e = kq;
-            asm volatile("" : "+v"(kq_e));
-            // pixel-shuffle epilogues: pxb is a multiple of 4, so with Wout % 4 == 0 (workgroup-uniform test; every map of
-            // the shipped configurations) the lane's 4 pixels lie in one row and one division per item does
-            const bool row4 = (p.Wout & 3) == 0;
-            const int py_ = pxb / p.Wout, px_ = pxb - py_ * p.Wout;
-            (void)row4; (void)py_; (void)px_;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int row0 = co0 + i * 16 + kq_e * 4;
-                if (row0 >= p.Cout) continue;
-                if (EPI == EPI_PLAIN) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const f32x4 x = (f32x4){acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]};
-                        st4((size_t)(row0 + r) * plane + pxb, x);
-                        ssum[i][r] += (x[0] + x[1]) + (x[2] + x[3]);
-                        ssq[i][r] += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
-                    }
-                } else if (EPI == EPI_UP2) {
-                    const int co = row0 >> 2;
-                    const size_t W2 = (size_t)p.Wout * 2;
-                    if (row4) {
-                        // the lane's 4 pixels are 8 consecutive floats of output rows 2y and 2y+1: two dwordx4 per row,
-                        // 512 contiguous bytes per 16 lanes (the per-pixel float2 stores left 8 of every 32 bytes per instruction)
-                        const size_t o = (size_t)co * plane * 4 + (size_t)(2 * py_) * W2 + 2 * px_;
-                        st4(o, (f32x4){acc[i][0][0], acc[i][0][1], acc[i][1][0], acc[i][1][1]});
-                        st4(o + 4, (f32x4){acc[i][2][0], acc[i][2][1], acc[i][3][0], acc[i][3][1]});
-                        st4(o + W2, (f32x4){acc[i][0][2], acc[i][0][3], acc[i][1][2], acc[i][1][3]});
-                        st4(o + W2 + 4, (f32x4){acc[i][2][2], acc[i][2][3], acc[i][3][2], acc[i][3][3]});
-#pragma unroll
-                        for (int j = 0; j < NT; ++j)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) { ssum[i][0] += acc[i][j][r]; ssq[i][0] += acc[i][j][r] * acc[i][j][r]; }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            const int y = (pxb + j) / p.Wout, xx = (pxb + j) - y * p.Wout;
-                            const f32x4 v = acc[i][j];
-                            float* o = gout + (size_t)co * plane * 4 + (size_t)(2 * y) * W2 + 2 * xx;
-                            *reinterpret_cast<float2*>(o) = make_float2(v[0], v[1]);
-                            *reinterpret_cast<float2*>(o + W2) = make_float2(v[2], v[3]);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) { ssum[i][0] += v[r]; ssq[i][0] += v[r] * v[r]; }
-                        }
-                    }
-                } else if (EPI == EPI_UP4) {
-                    const int co = row0 >> 4, dy = (row0 >> 2) & 3;
-                    const size_t W4o = (size_t)p.Wout * 4;
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        const int y = row4 ? py_ : (pxb + j) / p.Wout, xx = row4 ? px_ + j : (pxb + j) - y * p.Wout;
-                        const f32x4 v = acc[i][j];
-                        float* o = gout + (size_t)co * plane * 16 + (size_t)(4 * y + dy) * W4o + 4 * xx;
-                        *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { ssum[i][0] += v[r]; ssq[i][0] += v[r] * v[r]; }
-                    }
-                } else if (EPI == EPI_HEAD_CLS) { // row = anchor: cls(a) over the lane's 4 pixels, as the full head stores it
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int a_ = row0 + r;
-                        if (a_ < p.n_cls) {
-                            const float bs = p.bias[4 * (9 + a_) + 3];
-                            *reinterpret_cast<f32x4*>(gout + (size_t)a_ * plane + pxb) =
-                                (f32x4){acc[i][0][r] + bs, acc[i][1][r] + bs, acc[i][2][r] + bs, acc[i][3][r] + bs};
-                        }
-                    }
-                } else {
-                    // head rows in head_tile_row order: this lane's 4 rows are one output run (see the host helper)
-                    const int g = row0 >> 2;
-                    const f32x4 bs = *reinterpret_cast<const f32x4*>(p.bias + row0);
-                    if (g < 9) { // box(a = g), k = 0..3
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            f32x4u* o = reinterpret_cast<f32x4u*>(gbox + ((size_t)g * plane + pxb + j) * 7);
-                            *o = (f32x4u){acc[i][j][0] + bs[0], acc[i][j][1] + bs[1], acc[i][j][2] + bs[2], acc[i][j][3] + bs[3]};
-                        }
-                    } else if (g < 18) { // box(a = g - 9), k = 4..6 ; cls(a) over the lane's 4 pixels
-                        const int a_ = g - 9;
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            float* o = gbox + ((size_t)a_ * plane + pxb + j) * 7 + 4;
-                            *reinterpret_cast<f32x2u*>(o) = (f32x2u){acc[i][j][0] + bs[0], acc[i][j][1] + bs[1]};
-                            o[2] = acc[i][j][2] + bs[2];
-                        }
-                        *reinterpret_cast<f32x4*>(gout + (size_t)a_ * plane + pxb) =
-                            (f32x4){acc[i][0][3] + bs[3], acc[i][1][3] + bs[3], acc[i][2][3] + bs[3], acc[i][3][3] + bs[3]};
-                    } else if (g < 23) { // dir(a0 = 2d), dir(a0 + 1)
-                        const int a0 = 2 * (g - 18);
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            *reinterpret_cast<float2*>(gdir + ((size_t)a0 * plane + pxb + j) * 2) = make_float2(acc[i][j][0] + bs[0], acc[i][j][1] + bs[1]);
-                            if (a0 + 1 < 9)
-                                *reinterpret_cast<float2*>(gdir + ((size_t)(a0 + 1) * plane + pxb + j) * 2) = make_float2(acc[i][j][2] + bs[2], acc[i][j][3] + bs[3]);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    flush_stats(stat_frame);
-#undef G1_MFMAS
-#undef G1_PREP
-#undef G1_LOADB
-}
 
 // y = relu(x*scale+shift) (scale/shift from the producer's statistics), plus statistics of y.
 // Used for the [conv, norm, relu] head of each block, whose output is both a residual and the
@@ -2128,81 +106,8 @@ __global__ void __launch_bounds__(256) norm_relu_stats(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------
-// host side: network description, weight packing, launch plans
+// network description, weight packing, launch plans
 // ------------------------------------------------------------------------------------------
-template <int KS, int STRIDE, int TW, int WM, int WN, int MT, int NT, int BTX, int KC, int EPI>
-Variant make_variant()
-{
-    using C = ConvCfg<KS, STRIDE, TW, WM, WN, MT, NT, BTX, KC, EPI>;
-    Variant v;
-    v.kern = conv_mfma<KS, STRIDE, TW, WM, WN, MT, NT, BTX, KC, EPI>;
-    v.bm = C::BM; v.bmp = C::BMP; v.pw = C::PW; v.ph = C::PH; v.kc = KC; v.threads = C::THREADS;
-    v.waves = WM * WN; v.pairs = MT * NT;
-    v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    snprintf(v.name, sizeof(v.name), "k%ds%d tw%d w%dx%d t%dx%d bx%d kc%d e%d", KS, STRIDE, TW, WM, WN, MT, NT, BTX, KC, EPI);
-    return v;
-}
-
-template <int TWT, int WM, int WN, int BTX, int KC>
-Variant make_wino(bool roofline_layer)
-{
-    using C = WinoCfg<TWT, WM, WN, BTX, KC>;
-    Variant v;
-    v.kern = roofline_layer ? wino_mfma<TWT, WM, WN, BTX, KC, 1> : wino_mfma<TWT, WM, WN, BTX, KC, 0>;
-    v.bm = C::BM; v.bmp = C::BMP; v.pw = C::PW; v.ph = C::PH; v.kc = KC; v.threads = C::THREADS;
-    v.waves = WM * WN; v.pairs = 2 * 16;
-    v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    v.family = Family::Wino;
-    snprintf(v.name, sizeof(v.name), "wino tw%d w%dx%d bx%d kc%d", TWT, WM, WN, BTX, KC);
-    return v;
-}
-
-template <int TWT, int BTX, int KC>
-Variant make_wino4(bool roofline_layer)
-{
-    using C = Wino4Cfg<TWT, BTX, KC>;
-    Variant v;
-    v.kern = roofline_layer ? wino4_mfma<TWT, BTX, KC, 1> : wino4_mfma<TWT, BTX, KC, 0>;
-    v.bm = C::BM; v.bmp = C::BM; v.pw = C::PW; v.ph = C::PH; v.kc = KC; v.threads = C::THREADS;
-    v.waves = 4; v.pairs = 4 * 16;
-    v.lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    v.family = Family::Wino4;
-    snprintf(v.name, sizeof(v.name), "wino4 tw%d bx%d kc%d", TWT, BTX, KC);
-    return v;
-}
-
-template <int MT, int NT, int EPI, int PREC = 0, int IO16 = 0>
-Variant make_g1()
-{
-    Variant v;
-    v.kern = gemm1x1<MT, NT, EPI, PREC, IO16>;
-    v.prec = PREC;
-    v.io16 = IO16;
-    v.bm = MT * 16; v.bmp = v.bm + ((v.bm % 32 == 0) ? 16 : 0); v.pw = NT * 16; v.ph = 1; v.kc = 4; v.threads = 512;
-    v.waves = 8; v.pairs = MT * NT;
-    v.lds = 0; // depends on K: set per layer
-    v.family = Family::Gemm1x1;
-    if (IO16) snprintf(v.name, sizeof(v.name), "g1x1 m%d n%d e%d h%d p%d", MT, NT, EPI, IO16, PREC);
-    else if (PREC) snprintf(v.name, sizeof(v.name), "g1x1 m%d n%d e%d p%d", MT, NT, EPI, PREC);
-    else snprintf(v.name, sizeof(v.name), "g1x1 m%d n%d e%d", MT, NT, EPI);
-    return v;
-}
-
-// cls-only head pass (EPI_HEAD_CLS): ring depth PD, two workgroups per CU
-template <int PD>
-Variant make_g1_cls()
-{
-    Variant v;
-    v.kern = gemm1x1<1, 4, EPI_HEAD_CLS, 0, 0, PD>;
-    v.bm = 16; v.bmp = 16; v.pw = 64; v.ph = 1; v.kc = 4; v.threads = 512;
-    v.waves = 8; v.pairs = 4;
-    v.lds = 0; // depends on K (g1_lds)
-    v.family = Family::Gemm1x1;
-    v.wpc = 2;
-    snprintf(v.name, sizeof(v.name), "g1x1 cls pd%d wg%d", PD, v.wpc);
-    return v;
-}
-
 struct Layer {
     std::string wkey;
     int kind;   // 0 conv3x3, 1 deconv(up), 2 head
@@ -2251,45 +156,8 @@ struct pp_net {
 
 const int kC[3] = {64, 128, 256};
 
-// Tiling menu.  The 16-pixel N-tile is TW x (16/TW); a workgroup covers BTX x BTY tiles.  The maps of
-// eight_20cm are 400/200/100 = 16*25 / 8*25 / 4*25, so NT=5 shapes tile them exactly; the 4x4 / 2x2 shapes
-// are the general fallback (edge tiles masked).  Which entry runs a layer is MEASURED on the device at
-// pp_commit_weights (autotune below); the cost model only breaks ties / serves PP_AUTOTUNE=0.
-template <int KS, int STRIDE, int KC, int EPI>
-void conv_menu(std::vector<Variant>& m)
-{
-    constexpr int KH = (KC >= 8) ? KC / 2 : KC;
-    //                            TW WM WN MT NT BTX
-    m.push_back(make_variant<KS, STRIDE, 16, 1, 4, 4, 5, 1, KC, EPI>()); // 16x20 px, 64 rows
-    m.push_back(make_variant<KS, STRIDE, 16, 1, 4, 4, 5, 1, KH, EPI>());
-    m.push_back(make_variant<KS, STRIDE, 16, 1, 4, 4, 4, 1, KC, EPI>()); // 16x16 px, 64 rows
-    m.push_back(make_variant<KS, STRIDE, 16, 2, 2, 2, 5, 1, KH, EPI>()); // 16x10 px, 64 rows, light waves
-    m.push_back(make_variant<KS, STRIDE, 16, 1, 4, 2, 5, 1, KC, EPI>()); // 16x20 px, 32 rows
-    m.push_back(make_variant<KS, STRIDE, 8, 2, 2, 4, 5, 5, KC, EPI>());  // 40x4 px, 128 rows
-    m.push_back(make_variant<KS, STRIDE, 8, 2, 2, 4, 5, 5, KH, EPI>());
-    m.push_back(make_variant<KS, STRIDE, 8, 4, 1, 2, 5, 5, KC, EPI>());  // 40x2 px, 128 rows, light waves
-    m.push_back(make_variant<KS, STRIDE, 8, 2, 2, 4, 2, 2, KC, EPI>());  // 16x4 px, 128 rows
-    m.push_back(make_variant<KS, STRIDE, 8, 1, 4, 4, 4, 2, KC, EPI>());  // 16x16 px, 64 rows
-    m.push_back(make_variant<KS, STRIDE, 4, 4, 1, 2, 5, 5, KC, EPI>());  // 20x4 px, 128 rows
-    m.push_back(make_variant<KS, STRIDE, 4, 4, 1, 2, 5, 5, KH, EPI>());
-    m.push_back(make_variant<KS, STRIDE, 4, 8, 1, 1, 5, 5, KC, EPI>());  // 20x4 px, 128 rows, 8 light waves
-    m.push_back(make_variant<KS, STRIDE, 4, 2, 2, 4, 5, 5, KC, EPI>());  // 20x8 px, 128 rows
-    m.push_back(make_variant<KS, STRIDE, 4, 2, 2, 4, 2, 2, KC, EPI>());  // 8x8 px, 128 rows
-    m.push_back(make_variant<KS, STRIDE, 4, 2, 2, 2, 2, 2, KC, EPI>());  // 8x8 px, 64 rows
-}
-
-// S16 (pp_set_precision 4): every activation tensor behind the first conv is stored in fp16 -- the upsamplers read fp16 block
-// outputs and write the fp16 concat buffer (io16 3), the head reads it (io16 1; its logits stay fp32)
-template <int PREC, bool S16 = false>
-void lp_menu(int kind, int up, std::vector<Variant>& menu)
-{
-    constexpr int HI = S16 ? 1 : 0, DO = S16 ? 3 : 0;
-    if (kind == 2) { menu.push_back(make_g1<6, 4, EPI_HEAD, PREC, HI>()); menu.push_back(make_g1<3, 4, EPI_HEAD, PREC, HI>()); }
-    else if (up == 1) { menu.push_back(make_g1<4, 4, EPI_PLAIN, PREC, DO>()); menu.push_back(make_g1<2, 4, EPI_PLAIN, PREC, DO>()); }
-    else if (up == 2) { menu.push_back(make_g1<4, 4, EPI_UP2, PREC, DO>()); menu.push_back(make_g1<8, 4, EPI_UP2, PREC, DO>()); }
-    else { menu.push_back(make_g1<4, 4, EPI_UP4, PREC, DO>()); menu.push_back(make_g1<8, 4, EPI_UP4, PREC, DO>()); }
-}
-
+// The tilings a layer may run, composed from what the families export (conv_common.h).  Content and order are part of the plan: the
+// order decides menu[0], the tuner's ties and what PP_AUTOTUNE=0 takes, and menu.size() is in the tune-cache key (autotune_layer).
 void layer_menu(int kind, int stride, int up, std::vector<Variant>& menu, int cin = 0, bool roofline_layer = false, bool head9 = true, int prec = 0,
                 bool first_conv = false)
 {
@@ -2299,8 +167,7 @@ void layer_menu(int kind, int stride, int up, std::vector<Variant>& menu, int ci
     // conv16.hip.  A layer whose shape none of them takes (autotune_layer checks variant_ok / shape_ok) falls back to the
     // fp32 menu below, and pp_layer_tilings shows it.
     if (prec && g1ok && (kind == 1 || (kind == 2 && head9))) {
-        if (prec == 1) lp_menu<1>(kind, up, menu); else if (prec == 2) lp_menu<2>(kind, up, menu); else if (prec == 3) lp_menu<3>(kind, up, menu);
-        else lp_menu<3, true>(kind, up, menu);
+        gemm1x1_menu(kind, up, prec, menu);
         return;
     }
     if (prec && kind == 0 && cin % 16 == 0) {
@@ -2311,39 +178,18 @@ void layer_menu(int kind, int stride, int up, std::vector<Variant>& menu, int ci
     }
     if (kind == 2) {
         // the persistent 1x1 GEMM's head epilogue (head_tile_row) is laid out for the reference's 9 anchors per location
-        if (g1ok && head9) { menu.push_back(make_g1<6, 4, EPI_HEAD>()); menu.push_back(make_g1<3, 4, EPI_HEAD>()); }
-        menu.push_back(make_variant<1, 1, 16, 1, 4, 6, 5, 1, 16, EPI_HEAD>());
-        menu.push_back(make_variant<1, 1, 16, 1, 4, 6, 2, 1, 16, EPI_HEAD>());
-        menu.push_back(make_variant<1, 1, 16, 2, 2, 3, 5, 1, 16, EPI_HEAD>());
-        menu.push_back(make_variant<1, 1, 16, 2, 4, 3, 5, 1, 32, EPI_HEAD>());
-        menu.push_back(make_variant<1, 1, 8, 1, 4, 6, 2, 1, 16, EPI_HEAD>());
-        menu.push_back(make_variant<1, 1, 8, 2, 2, 3, 4, 2, 16, EPI_HEAD>());
+        if (g1ok && head9) gemm1x1_menu(kind, up, 0, menu);
+        conv_direct_menu(kind, stride, up, menu);
     } else if (kind == 1) {
-        if (up == 1) { conv_menu<1, 1, 16, EPI_PLAIN>(menu); if (g1ok) { menu.push_back(make_g1<4, 4, EPI_PLAIN>()); menu.push_back(make_g1<2, 4, EPI_PLAIN>()); } }
-        else if (up == 2) { conv_menu<1, 1, 16, EPI_UP2>(menu); if (g1ok) { menu.push_back(make_g1<4, 4, EPI_UP2>()); menu.push_back(make_g1<8, 4, EPI_UP2>()); } }
-        else { conv_menu<1, 1, 16, EPI_UP4>(menu); if (g1ok) { menu.push_back(make_g1<4, 4, EPI_UP4>()); menu.push_back(make_g1<8, 4, EPI_UP4>()); } }
-    } else if (stride == 2) {
-        conv_menu<3, 2, 8, EPI_PLAIN>(menu);
+        conv_direct_menu(kind, stride, up, menu);
+        if (g1ok) gemm1x1_menu(kind, up, 0, menu);
     } else {
-        conv_menu<3, 1, 8, EPI_PLAIN>(menu);
-        //                     TWT WM WN BTX KC      output patch, rows
-        menu.push_back(make_wino<8, 1, 4, 1, 8>(roofline_layer));  // 16x16 px, 32 rows
-        menu.push_back(make_wino<8, 1, 4, 2, 8>(roofline_layer));  // 32x8 px, 32 rows
-        menu.push_back(make_wino<8, 2, 2, 1, 8>(roofline_layer));  // 16x8 px, 64 rows
-        menu.push_back(make_wino<8, 2, 4, 1, 8>(roofline_layer));  // 16x16 px, 64 rows, 8 waves
-        menu.push_back(make_wino<4, 1, 4, 2, 8>(roofline_layer));  // 16x16 px, 32 rows
-        menu.push_back(make_wino<4, 2, 2, 1, 8>(roofline_layer));  // 8x16 px, 64 rows
-        menu.push_back(make_wino<4, 2, 4, 2, 8>(roofline_layer));  // 16x16 px, 64 rows, 8 waves
-        menu.push_back(make_wino<4, 1, 4, 1, 8>(roofline_layer));  // 8x32 px, 32 rows
-        menu.push_back(make_wino<2, 1, 4, 2, 8>(roofline_layer));  // 8x32 px (2x8-tile N-tiles), 32 rows
-        // (8-wave 32-row tilings, WN = 8, were tried: 6-15 % slower than their 4-wave twins -- two lock-stepped waves per SIMD)
-        menu.push_back(make_wino<8, 1, 4, 1, 4>(roofline_layer));
-        menu.push_back(make_wino<4, 1, 4, 2, 4>(roofline_layer));
-        // one wave per SIMD, 64 rows, 3-deep ring (even maps, Cout a multiple of 64 only -- see variant_ok)
-        menu.push_back(make_wino4<4, 2, 8>(roofline_layer));       // 16x16 px
-        menu.push_back(make_wino4<8, 1, 8>(roofline_layer));       // 16x16 px, 8x2-tile N-tiles
-        menu.push_back(make_wino4<8, 2, 8>(roofline_layer));       // 32x8 px
-        if (cin % 32 == 0) wino6_menu(menu, roofline_layer);       // Winograd F(4x4,3x3), 16x16 px (wino6.hip)
+        conv_direct_menu(kind, stride, up, menu);
+        if (stride != 2) {
+            wino2_menu(menu, roofline_layer);
+            wino4_menu(menu, roofline_layer);
+            if (cin % 32 == 0) wino6_menu(menu, roofline_layer); // Winograd F(4x4,3x3), 16x16 px (wino6.hip)
+        }
     }
 }
 
@@ -2352,12 +198,12 @@ void layer_menu(int kind, int stride, int up, std::vector<Variant>& menu, int ci
 // 49 mostly-empty ones
 static const Variant& strip_v(Family f) // 4 px wide, 64 px tall
 {
-    static const Variant w4 = make_wino4<2, 1, 8>(false), w6 = wino6_strip_v();
+    static const Variant w4 = wino4_strip_v(), w6 = wino6_strip_v();
     return f == Family::Wino6 ? w6 : w4;
 }
 static const Variant& strip_h(Family f) // 64 px wide, 4 px tall
 {
-    static const Variant w4 = make_wino4<16, 2, 8>(false), w6 = wino6_strip_h();
+    static const Variant w4 = wino4_strip_h(), w6 = wino6_strip_h();
     return f == Family::Wino6 ? w6 : w4;
 }
 
@@ -2398,8 +244,6 @@ bool shape_ok(const Variant& v, int Hin, int Win, int Wout)
     default: return true;
     }
 }
-// LDS bytes of a persistent 1x1 GEMM for a given K
-size_t g1_lds(const Variant& v, int K) { return ((size_t)K * v.bmp + (size_t)8 * 2 * K) * sizeof(float); }
 // LDS bytes of a launch of v on a layer with cin input channels (gemm1x1 keeps the whole [K][BM] weight slab)
 size_t layer_lds(const Variant& v, int cin) { return v.family == Family::Gemm1x1 ? g1_lds(v, cin) : v.lds; }
 // One frame per launch: the families that finalise the producer's statistics in their own prologue, instead of a norm_finalize
@@ -2518,14 +362,17 @@ int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
         }
     }
     L.rows = rows;
+    auto upload = [&](const void* image, size_t bytes) -> int { // the finished image replaces the layer's device copy
+        if (L.w) (void)hipFree(L.w);
+        PP_HIP(hipMalloc((void**)&L.w, bytes));
+        L.w_bytes = bytes;
+        PP_HIP(hipMemcpy(L.w, image, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
     if (v.family == Family::Wino6) { // F(4x4,3x3): U = G g G^T in the order the four waves fetch their positions (wino6.hip)
         std::vector<float> pk6;
         wino6_pack(rowsW.data(), rows, L.cin, pk6, index_positions);
-        if (L.w) (void)hipFree(L.w);
-        PP_HIP(hipMalloc((void**)&L.w, pk6.size() * sizeof(float)));
-        L.w_bytes = pk6.size() * sizeof(float);
-        PP_HIP(hipMemcpy(L.w, pk6.data(), pk6.size() * sizeof(float), hipMemcpyHostToDevice));
-        return 0;
+        return upload(pk6.data(), pk6.size() * sizeof(float));
     }
     int taps_eff = taps;
     if (v.family == Family::Wino || v.family == Family::Wino4) { // U = G g G^T per (cout, cin), fp64 on the host; position xi = 4*a + b
@@ -2552,9 +399,10 @@ int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
         }
         rowsW.swap(perm);
     }
+    // bf16 images (conv16, gemm1x1): round to nearest even, and back
+    auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
+    auto bf16f = [](uint16_t h) -> float { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };
     if (v.family == Family::Conv16) { // conv16: [row block][cin/16][image: hi (| lo for bf16x3)][tap][k-half][BM rows][8 x 16 bit] = the LDS image of a step
-        auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
-        auto bf16f = [](uint16_t h) -> float { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };
         auto f16 = [](float f) -> uint16_t { const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }; // round to nearest even
         const int nimg = (v.prec == 1) ? 2 : 1, nblk = rows / v.bm, nch = L.cin / 16;
         std::vector<uint16_t> pk((size_t)nblk * nch * nimg * 9 * 2 * v.bm * 8, 0);
@@ -2574,15 +422,9 @@ int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
                                     if (nimg == 2) pk[img0 + (size_t)(9 * 2 * v.bm * 8) + o] = bf16(w - bf16f(hi));
                                 }
                             }
-        if (L.w) (void)hipFree(L.w);
-        PP_HIP(hipMalloc((void**)&L.w, pk.size() * sizeof(uint16_t)));
-        L.w_bytes = pk.size() * sizeof(uint16_t);
-        PP_HIP(hipMemcpy(L.w, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        return 0;
+        return upload(pk.data(), pk.size() * sizeof(uint16_t));
     }
     if (v.family == Family::Gemm1x1 && v.prec) { // [row block][K/16][hi|lo][k-group][BMP][4 bf16]: the byte count of the fp32 slab
-        auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
-        auto bf16f = [](uint16_t h) -> float { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };
         const int nb_ = pp_div_up(rows, v.bm), nkb = L.cin / 16;
         std::vector<uint16_t> pk4((size_t)nb_ * nkb * 2 * 4 * v.bmp * 4, 0);
         for (int b = 0; b < nb_; ++b)
@@ -2600,11 +442,7 @@ int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
                             pk4[(((((size_t)b * nkb + kb) * 2 + 1) * 4 + q) * v.bmp + mm) * 4 + t] = lo;
                         }
                     }
-        if (L.w) (void)hipFree(L.w);
-        PP_HIP(hipMalloc((void**)&L.w, pk4.size() * sizeof(uint16_t)));
-        L.w_bytes = pk4.size() * sizeof(uint16_t);
-        PP_HIP(hipMemcpy(L.w, pk4.data(), pk4.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        return 0;
+        return upload(pk4.data(), pk4.size() * sizeof(uint16_t));
     }
     if (v.family == Family::Gemm1x1) { // [row block][K][BMP]
         const int nb_ = pp_div_up(rows, v.bm);
@@ -2615,11 +453,7 @@ int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
                     const int row = b * v.bm + mm;
                     if (row < rows) pk3[((size_t)b * L.cin + c) * v.bmp + mm] = rowsW[(size_t)row * L.cin + c];
                 }
-        if (L.w) (void)hipFree(L.w);
-        PP_HIP(hipMalloc((void**)&L.w, pk3.size() * sizeof(float)));
-        L.w_bytes = pk3.size() * sizeof(float);
-        PP_HIP(hipMemcpy(L.w, pk3.data(), pk3.size() * sizeof(float), hipMemcpyHostToDevice));
-        return 0;
+        return upload(pk3.data(), pk3.size() * sizeof(float));
     }
     const int nblk = pp_div_up(rows, v.bm), nchunk = L.cin / v.kc;
     std::vector<float> pk((size_t)nblk * nchunk * taps_eff * v.kc * v.bmp, 0.f); // LDS image incl. row padding
@@ -2636,11 +470,7 @@ int pack_layer(pp_ctx* ctx, Layer& L, bool index_positions = false)
                         pk[((((size_t)b * nchunk + ch) * taps_eff + t) * v.kc + k) * v.bmp + col] =
                             rowsW[((size_t)row * L.cin + ch * v.kc + k) * taps_eff + t];
                     }
-    if (L.w) (void)hipFree(L.w);
-    PP_HIP(hipMalloc((void**)&L.w, pk.size() * sizeof(float)));
-    L.w_bytes = pk.size() * sizeof(float);
-    PP_HIP(hipMemcpy(L.w, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return upload(pk.data(), pk.size() * sizeof(float));
 }
 
 // InstanceNorm statistics -> (scale, shift) once per frame and layer, instead of once per workgroup of the
@@ -2700,6 +530,27 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         p.pre = PRE_AFFINE; p.pre_scale = net->aff; p.pre_shift = net->aff + 320; p.aff_fs = 640;
     }
     const Variant& v = L.var;
+    // profile bracket (pp_profile_begin) of the level-0 stride-1 layers: one event pair around the layer's launches, and its flops
+    const bool tag = ctx->prof_on && L.kind == 0 && L.level == 0 && L.stride == 1;
+    auto prof_begin = [&]() -> int {
+        if (!tag) return 0;
+        if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
+            hipEvent_t a, b;
+            PP_HIP(hipEventCreate(&a));
+            PP_HIP(hipEventCreate(&b));
+            ctx->prof_ev.push_back(a);
+            ctx->prof_ev.push_back(b);
+        }
+        ctx->prof_flops = 2.0 * Hout * Wout * (double)L.cin * L.cout * 9.0 * B;
+        PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used], stream));
+        return 0;
+    };
+    auto prof_end = [&]() -> int {
+        if (!tag) return 0;
+        PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used + 1], stream));
+        ctx->prof_used += 2;
+        return 0;
+    };
     dim3 grid(pp_div_up(Wout, v.pw) * pp_div_up(Hout, v.ph), pp_div_up(L.rows, v.bm), B);
     p.nb = B;
     const size_t lds_bytes = layer_lds(v, L.cin);
@@ -2728,7 +579,6 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         if ((size_t)L.rows * Hout * Wout * 4 >= 0x80000000ull) return PP_E_ARG; // the epilogue parks idle lanes' offsets 2 GB out (W4_FAR)
         // these two kernels always normalise (every stride-1 convolution of the network follows a norm): with PRE_RAW they would read a null table
         if (p.pre == PRE_RAW) return pp_fail(ctx, PP_E_ARG, "wino4 / wino6 tilings have no raw prologue: give the layer a (scale, shift)");
-        const bool tag4 = ctx->prof_on && L.kind == 0 && L.level == 0 && L.stride == 1;
         const int ncb = pp_div_up(L.rows, v.bm);
         // Tile skipping (tile_skip.hip): ts_k = the layer's ordinal among level 0's stride-1 layers, handed over by a pass whose first conv
         // ran sparse (or by the single-layer hook).  Listed launch + fill only for the fp32 wino6 main tile on a map of whole main tiles
@@ -2738,20 +588,12 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         const bool listed = ts_k > 0 && v.family == Family::Wino6 && v.kern2 && v.pw == 16 && v.ph == 16 && net->eff_prec == 0 && !net->up16 &&
                             L.kind == 0 && L.level == 0 && L.stride == 1 && Wout % v.pw == 0 && Hout % v.ph == 0 && Hout == ctx->H && Wout == ctx->W &&
                             pp_ts_list(ctx, ts_k, B, &ts_items, &ts_count);
-        if (tag4) {
+        if (tag) {
             const double dense = (double)(Wout / v.pw) * (Hout / v.ph) * ncb * B;
             ctx->prof_items_dense += dense;
             if (listed) ctx->prof_ts_layer.push_back(ts_k | (ncb << 8)); else ctx->prof_items += dense;
-            if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
-                hipEvent_t a, b;
-                PP_HIP(hipEventCreate(&a));
-                PP_HIP(hipEventCreate(&b));
-                ctx->prof_ev.push_back(a);
-                ctx->prof_ev.push_back(b);
-            }
-            ctx->prof_flops = 2.0 * Hout * Wout * (double)L.cin * L.cout * 9.0 * B;
-            PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used], stream));
         }
+        if (int rc = prof_begin()) return rc;
         auto launch_region = [&](const Variant& rv, int x0, int y0, int x1, int y1) {
             ConvP q = p;
             q.rx0 = x0; q.ry0 = y0; q.rx1 = x1; q.ry1 = y1;
@@ -2790,10 +632,7 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
             if (listed)
                 if (int rc = pp_ts_fill(ctx, ts_k, B, out, p.out_fs, L.rows, stream)) return rc;
         }
-        if (tag4) {
-            PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used + 1], stream));
-            ctx->prof_used += 2;
-        }
+        if (int rc = prof_end()) return rc;
         PP_HIP(hipGetLastError());
         return 0;
     }
@@ -2804,23 +643,9 @@ int launch_conv(pp_ctx* ctx, const Layer& L, const float* in, int Hin, int Win, 
         g = (g + 7) & ~7;
         grid = dim3(g, 1, 1);
     }
-    const bool tag = ctx->prof_on && L.kind == 0 && L.level == 0 && L.stride == 1;
-    if (tag) {
-        if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
-            hipEvent_t a, b;
-            PP_HIP(hipEventCreate(&a));
-            PP_HIP(hipEventCreate(&b));
-            ctx->prof_ev.push_back(a);
-            ctx->prof_ev.push_back(b);
-        }
-        ctx->prof_flops = 2.0 * Hout * Wout * (double)L.cin * L.cout * 9.0 * B;
-        PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used], stream));
-    }
+    if (int rc = prof_begin()) return rc;
     hipLaunchKernelGGL((pmap && v.kern2) ? v.kern2 : v.kern, grid, dim3(v.threads), lds_bytes, stream, p);
-    if (tag) {
-        PP_HIP(hipEventRecord(ctx->prof_ev[ctx->prof_used + 1], stream));
-        ctx->prof_used += 2;
-    }
+    if (int rc = prof_end()) return rc;
     PP_HIP(hipGetLastError());
     return 0;
 }
@@ -3033,7 +858,8 @@ int launch_head_cls(pp_ctx* ctx, const Variant& v, const float* in, const NormRe
 int autotune_head_cls(pp_ctx* ctx, float* tin, bool verbose, bool measure)
 {
     pp_net* net = (pp_net*)ctx->net;
-    const std::vector<Variant> menu = {make_g1_cls<8>(), make_g1_cls<10>(), make_g1_cls<4>()}; // every shape without scratch: a 16-deep ring spills
+    std::vector<Variant> menu;
+    gemm1x1_cls_menu(menu);
     for (const Variant& v : menu)
         PP_HIP(hipFuncSetAttribute((const void*)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g1_lds(v, 320)));
     net->cls_var = menu[0];

@@ -1,5 +1,6 @@
-// Shared by the conv kernels' translation units (conv.hip: fp32 MFMA family; conv16.hip: 16-bit operand family): kernel
-// parameter block, launch-plan entry, XCD-aware block numbering and the small device helpers.  gfx950 only.
+// Shared by the conv kernels' translation units -- one per kernel family (conv_direct.hip, wino2.hip, wino4.hip, gemm1x1.hip,
+// conv16.hip, wino6.hip) and conv.hip, the host side that composes their menus and launches them: kernel parameter block,
+// launch-plan entry, XCD-aware block numbering, the small device helpers and what each family exports.  gfx950 only.
 #pragma once
 #include <type_traits>
 #include "pp_common.h"
@@ -30,6 +31,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // dword-aligned vector stores (global memory takes multi-dword accesses at dword alignment)
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ unsigned pk_f16(float a, float b) // round to nearest even (v_cvt_pk_f16_f32 on gfx950)
+{
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, f16x2_t));
+}
 
 // Sum over the 16 lanes that share lane >> 4 (one row of the 16x16 MFMA tile = one DPP row), on the VALU: two quad
 // permutes, row_half_mirror, row_mirror.  After each step all lanes of the merged group hold the same value, so the
@@ -127,6 +135,25 @@ struct Variant { // one compiled tiling
     int wpc = 1;  // Gemm1x1: persistent workgroups per CU
 };
 
+// Every family's translation unit exports its tilings as menu functions that append to `menu` in a fixed order: the order decides
+// menu[0], ties of the tuner and the entry PP_AUTOTUNE=0 takes, and menu.size() is part of the tune-cache key (conv.hip: layer_menu).
+
+// conv_direct.hip: conv_mfma -- kind 0: conv3x3 (stride 1 / 2), kind 1: ConvTranspose(k = s = up) for up 1 / 2 / 4, kind 2: the head
+void conv_direct_menu(int kind, int stride, int up, std::vector<Variant>& menu);
+
+// wino2.hip: wino_mfma, Winograd F(2x2,3x3), two workgroups per CU
+void wino2_menu(std::vector<Variant>& menu, bool roofline_layer);
+
+// wino4.hip: wino4_mfma, Winograd F(2x2,3x3), one wave per SIMD -- menu entries and the strip tilings of its region launches
+void wino4_menu(std::vector<Variant>& menu, bool roofline_layer);
+Variant wino4_strip_v(); // 4 px wide, 64 px tall
+Variant wino4_strip_h(); // 64 px wide, 4 px tall
+
+// gemm1x1.hip: persistent 1x1 GEMM -- the upsamplers (kind 1) and the 9-anchor head (kind 2) at precision prec (0 fp32 ... 4 fp16 tensors),
+// the shapes of the cls-only head pass, and the LDS bytes of a launch with K input channels (Variant::lds is 0 for this family)
+void gemm1x1_menu(int kind, int up, int prec, std::vector<Variant>& menu);
+void gemm1x1_cls_menu(std::vector<Variant>& menu);
+size_t g1_lds(const Variant& v, int K);
 
 // conv16.hip: 16-bit operand 3x3 convolutions (fp16 / bf16 / split-bf16) -- menu entries for one layer shape and precision
 void conv16_menu(int stride, int prec, std::vector<Variant>& menu, int io16 = 0);

@@ -1,6 +1,6 @@
 // Winograd F(4x4,3x3) for the stride-1 3x3 convolutions of the backbone (networks/pointpillars8_shared.py:114-181,418-431:
 // Resnet2 = x + convs(IN -> ReLU -> conv3x3 ...)) on v_mfma_f32_16x16x4_f32 -- 36 MFMA positions per 4x4 output tile instead
-// of 16 per 2x2 tile (wino4_mfma, conv.hip): 2.25 multiplies per output pixel and channel pair against 4 (direct: 9).
+// of 16 per 2x2 tile (wino4_mfma, wino4.hip): 2.25 multiplies per output pixel and channel pair against 4 (direct: 9).
 //
 //   Y = A^T [ (G g G^T) (.) (B^T d B) ] A,   d = 6x6 input window of relu(norm(x)), g = 3x3 filter, Y = 4x4 outputs
 //

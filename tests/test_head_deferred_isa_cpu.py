@@ -42,7 +42,7 @@ def test_candidate_head_uses_no_scratch():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_cls_only_pass_uses_no_scratch():
     # gemm1x1<MT = 1, NT = 4, EPI_HEAD_CLS = 4, ...>: every ring depth / register budget on the menu
-    k = {n: u for n, u in kernel_usage("conv.hip").items() if "gemm1x1ILi1ELi4ELi4E" in n}
+    k = {n: u for n, u in kernel_usage("gemm1x1.hip").items() if "gemm1x1ILi1ELi4ELi4E" in n}
     print(k)
     assert len(k) == 3
     for n, u in k.items():

@@ -1,5 +1,5 @@
 # Fixed-tiling A/B of two builds of libpp_hip.so on the GPU box (run through gpurun): the working tree's library against a
-# baseline built by hand from another revision's conv.hip into 3d_object_detection_amd/csrc/_ab/libpp_base.so (git-ignored,
+# baseline built by hand from another revision's csrc sources into 3d_object_detection_amd/csrc/_ab/libpp_base.so (git-ignored,
 # travels with the snapshot; PP_HIP_LIB selects it).  The first run tunes and fills PP_TUNE_CACHE, the others reuse its
 # picks, so only the code differs; alternating runs give +-0.1 % repeatability.
 set -e

@@ -1,18 +1,31 @@
 #!/usr/bin/env python3
-"""ISA statistics of one kernel of conv.hip: resource usage, and per straight-line region (between labels / branches)
-the MFMA, VALU, LDS, VMEM, scratch and AGPR-move counts.  Usage: tools/isa_stats.py <mangled-name-substring> [conv.s]"""
+"""ISA statistics of one conv kernel: resource usage, and per straight-line region (between labels / branches) the MFMA, VALU,
+LDS, VMEM, scratch and AGPR-move counts.  The source file follows from the kernel family named in the pattern.
+Usage: tools/isa_stats.py <mangled-name-substring> [<file>.s [<file>.hip]]"""
 import collections
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "3d_object_detection_amd", "csrc", "conv.hip")
+CSRC = os.path.join(ROOT, "3d_object_detection_amd", "csrc")
+# kernel name (as it appears inside the mangled name) -> translation unit
+FAMILY_SRC = (("wino4_mfma", "wino4.hip"), ("wino6_mfma", "wino6.hip"), ("wino_mfma", "wino2.hip"), ("conv_mfma", "conv_direct.hip"),
+              ("gemm1x1", "gemm1x1.hip"), ("conv16", "conv16.hip"))
+
+
+def source_of(pat):
+    for kernel, src in FAMILY_SRC:
+        if kernel in pat or pat in kernel:
+            return src
+    return "conv.hip"  # the small kernels around the layers (norm_relu_stats, norm_finalize, ...)
 
 
 def main():
     pat = sys.argv[1]
-    asm = sys.argv[2] if len(sys.argv) > 2 else "/tmp/conv.s"
+    src = sys.argv[3] if len(sys.argv) > 3 else source_of(pat)
+    SRC = os.path.join(CSRC, src)
+    asm = sys.argv[2] if len(sys.argv) > 2 else "/tmp/" + os.path.splitext(os.path.basename(src))[0] + ".s"
     if not os.path.exists(asm) or os.path.getmtime(asm) < os.path.getmtime(SRC):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize",
                                "-munsafe-fp-atomics", "-S", "--cuda-device-only", SRC, "-o", asm] + os.environ.get("PP_EXTRA_FLAGS", "").split(),
