@@ -82,6 +82,9 @@ PROTOTYPES = {
     "pp_unit_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
     "pp_backbone_block_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_block_weights": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_int, c_p]),
+    "pp_down_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
+    "pp_backbone_stage_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_update_down_weight": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
     "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),

@@ -332,6 +332,11 @@ void pp_block_destroy(pp_ctx* ctx)
     ctx->blk = nullptr;
 }
 
+void pp_launch_unit_image(float* dst, const int32_t* pmap, int n, const float* w, int T, int nrc, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_unit_image, dim3(pp_div_up(n, 256)), dim3(256), 0, stream, dst, pmap, n, w, T, nrc);
+}
+
 extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip, int nb,
                                 float* dw, float* du, void* stream_)
 {
@@ -433,7 +438,7 @@ extern "C" int pp_update_block_weights(pp_ctx* ctx, int block, const float* cons
     for (int k = 0; k < 5; ++k) {
         const pp_block_image& im = ws->img[k];
         const int cnt = (int)im.pmap.size();
-        hipLaunchKernelGGL(k_unit_image, dim3(pp_div_up(cnt, 256)), dim3(256), 0, stream, im.w, ws->pmap[k], cnt, w[k], im.T, im.C * im.C);
+        pp_launch_unit_image(im.w, ws->pmap[k], cnt, w[k], im.T, im.rows * im.C, stream);
     }
     PP_HIP(hipGetLastError());
     return 0;

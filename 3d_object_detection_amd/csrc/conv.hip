@@ -150,6 +150,7 @@ struct pp_net {
     Variant cls_var;       // tiling of the cls-only head pass (chosen at pp_commit_weights when defer_ok)
     const float* tap[3] = {}; // block outputs of the last pp_run_backbone pass (what the three upsamplers read): pp_backbone_taps
     float* unit_tap = nullptr; // copy hook of pp_backbone_block_taps: caller memory f32[5][256][H/4][W/4] for block 3's unit inputs (null: inert)
+    float* z3_tap = nullptr;   // copy hook of pp_backbone_stage_taps: caller memory f32[256][H/4][W/4] for the raw output of block 3's strided conv (null: inert)
     double* dbg_stats = nullptr; // statistics accumulators of pp_debug_layer (allocated on its first call that asks for statistics)
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };
@@ -1207,6 +1208,9 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
             }
         } else if ((rc = launch_conv(ctx, net->layers[li++], x, Hin, Win, Bf[0], nullptr, raw, stat_slot(ctx, site_block(b, 0)), c, h, w, stream,
                               nullptr, nullptr, nb, 0, 0, b == 0 ? pmap : nullptr, b == 0 ? feat : nullptr))) return rc;
+        // block 3's pre-norm conv output z leaves through its own copy hook: the first unit reuses Bf[0] as a spare
+        if (b == 2 && nb == 1 && net->z3_tap)
+            PP_HIP(hipMemcpyAsync(net->z3_tap, Bf[0], (size_t)c * cnt * sizeof(float), hipMemcpyDeviceToDevice, stream));
         // y = relu(norm(Bf[0])) -> Bf[1] + stats(site 1) (the first Resnet2 unit's leading norm)
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_NORM))) return rc;
         if ((rc = launch_norm_relu(ctx, Bf[0], Bf[1], c, (int)cnt, norm_ref(ctx, site_block(b, 0), c, 0, cnt),
@@ -1430,9 +1434,29 @@ int pp_net_block_image(pp_ctx* ctx, int block, int unit, pp_block_image* img)
         if (rc) return rc;
         img->w = L.w;
         img->C = L.cin;
+        img->rows = L.cout;
         return L.cin == L.cout ? 0 : pp_fail(ctx, PP_E_ARG, "pp_net_block_image: not a C -> C unit");
     }
     return pp_fail(ctx, PP_E_ARG, "pp_net_block_image: no such unit");
+}
+
+// The strided convolution in front of block `level` of the committed plan, for pp_update_down_weight (down_train.hip)
+int pp_net_down_image(pp_ctx* ctx, int level, pp_block_image* img)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    for (Layer& L : net->layers) {
+        if (L.kind != 0 || L.level != level || L.stride != 2) continue;
+        if (net->eff_prec != 0 || L.var.prec != 0 || L.var.io16 != 0 || L.var.family == Family::Conv16)
+            return pp_fail(ctx, PP_E_ARG, "the strided convolution can be rewritten in place in the fp32 mode only (the committed plan packs it in a 16-bit format)");
+        if (L.var.family != Family::Direct) return pp_fail(ctx, PP_E_ARG, "pp_net_down_image: the strided convolution does not run a direct tiling");
+        int rc = layer_position_map(ctx, L, img->pmap, &img->T);
+        if (rc) return rc;
+        img->w = L.w;
+        img->C = L.cin;
+        img->rows = L.cout;
+        return 0;
+    }
+    return pp_fail(ctx, PP_E_ARG, "pp_net_down_image: no such layer");
 }
 
 int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
@@ -1510,6 +1534,19 @@ extern "C" int pp_backbone_block_taps(pp_ctx* ctx, const float* canvas, float* r
     net->unit_tap = units; // pp_backbone_taps checks the rest; the hook is armed for this one pass only
     int rc = pp_backbone_taps(ctx, canvas, rpn_out, x1, x2, x3, stream_);
     net->unit_tap = nullptr;
+    return rc;
+}
+
+extern "C" int pp_backbone_stage_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* units, float* z3,
+                                      void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_stage_taps: weights not committed");
+    if (!z3) return pp_fail(ctx, PP_E_ARG, "pp_backbone_stage_taps: null pointer");
+    pp_net* net = (pp_net*)ctx->net;
+    net->z3_tap = z3; // pp_backbone_block_taps checks the rest; the hook is armed for this one pass only
+    int rc = pp_backbone_block_taps(ctx, canvas, rpn_out, x1, x2, x3, units, stream_);
+    net->z3_tap = nullptr;
     return rc;
 }
 

@@ -1,0 +1,407 @@
+// Training side of the backbone (gfx950): the backward of one strided stage, Conv2d(Cin -> Cout, 3 x 3, stride 2, pad 1, no bias) ->
+// InstanceNorm2d(eps 1e-3, no affine) -> ReLU, the head of every block of RPN (pointpillars8_shared.py:143-161).  fp32 throughout,
+// InstanceNorm backbone only, generic in (Cin, Cout) = (64, 64) | (64, 128) | (128, 256) and in the map size (odd sizes included).
+//
+// With ho = (Hin + 1) / 2, wo = (Win + 1) / 2, a stride-2 tap reads input row 2 oy + ky - 1: an even row (ky = 1) or an odd one (ky = 0
+// at half-row oy - 1, ky = 2 at half-row oy), and likewise along a row.  So x is de-interleaved into its four row / column parity planes
+// (py, px), plane element (r, c) = x[2 r + py][2 c + px] (zero past the input), and every plane, like dz, takes the padded layout of
+// block_train.hip at half resolution: the (ho + 2) x wp zero-haloed image, wp = wo + 2, PP = (ho + 2) wp elements, between two guard
+// bands of G >= wp + 17 zeros, PS elements in all (G and PS multiples of 4).  Tap t = (ky, kx) is then plane (ky != 1, kx != 1) shifted
+// by the flat offset off_t = -(ky == 0) wp - (kx == 0), every shifted read stays inside the plane, and halo x anything = 0:
+//   k_down_wt      wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows
+//   k_down_xpack   per (frame, ci): the four parity planes of x (halo and guards rewritten)
+//   k_down_norm    per (frame, co): sum z, sum z^2 in fp64, mean / rstd as the forward rounds them, Gr = dy [xhat > 0], sum Gr, sum Gr xhat
+//                  in fp64, dz = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) into the padded plane
+//   k_down_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] xp[ci][plane_t][P + off_t]    M = Cout, N = 9 Cin, K = frames x PP in ranges
+//   k_down_dw_reduce  partials summed in index order (double, rounded once)
+//   k_down_dgrad   per output parity class (py, px), P the half-resolution position of x[2 r + py][2 c + px]:
+//                  dx[ci][P] = sum_{t in class, co} wT[t][co][ci] dz[co][P + (py & ky == 0) wp + (px & kx == 0)]
+//                  M = Cin, N = PP, K = Cout x {1, 2, 2, 4} taps (even: the centre tap; odd: taps 0 and 2), summed in blocks of DA_BLOCK
+// The two products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory, as in block_train.hip.
+//
+// Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
+// order; K ranges of the wgrad depend on the shapes only.  A frame's dz and dx do not depend on the batch it rides in; dw depends on
+// nb within fp32 summation error (the K ranges do), and not on whether dx is asked for.
+#include <cmath>
+#include "pp_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr size_t DOWN_WS_BUDGET = (size_t)256 << 20; // bytes of the x parity planes + dz planes: larger batches run in frame chunks
+constexpr int DW_WGS = 512;                          // workgroups a wgrad launch aims at (output tiles x K ranges)
+constexpr int DW_MAX_SPLIT = 256;
+constexpr int DA_BLOCK = 64;                         // k-terms that k_down_dgrad sums in one accumulator before adding the block to the total
+
+struct down_ws {
+    float* planes = nullptr; size_t planes_elems = 0; // xp [fc][Cin][4][PS], then dz [fc][Cout][PS]
+    float* wT = nullptr;     size_t wT_elems = 0;
+    float* part = nullptr;   size_t part_elems = 0;
+    uint64_t img_gen = 0;    // ctx->commit_gen the position map belongs to (0: none)
+    pp_block_image img;      // the strided conv of level 2 (pp_update_down_weight)
+    int32_t* pmap = nullptr;
+};
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <typename T>
+int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need)
+{
+    if (need <= *have) return 0;
+    PP_HIP(hipDeviceSynchronize()); // a kernel of an earlier call, on this stream or another, may still read the old buffer
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+    PP_HIP(hipMalloc((void**)buf, need * sizeof(T)));
+    *have = need;
+    return 0;
+}
+
+// both sums over the 256 threads' partials (segment t: elements t, t + 256, ...), added in index order 0 .. 255 by every thread: the
+// same bits in every thread
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[2])
+{
+    __syncthreads(); // red may still be read from an earlier call
+    red[threadIdx.x][0] = a; red[threadIdx.x][1] = b;
+    __syncthreads();
+    double sa = 0.0, sb = 0.0;
+    for (int t = 0; t < 256; ++t) { sa += red[t][0]; sb += red[t][1]; }
+    a = sa; b = sb;
+}
+
+__global__ void __launch_bounds__(256) k_down_wt(const float* __restrict__ w, float* __restrict__ wT, int cin, int cout)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][cout][cin]
+    if (i >= 9 * cin * cout) return;
+    const int ci = i % cin, co = (i / cin) % cout, t = i / (cin * cout);
+    wT[i] = w[((size_t)co * cin + ci) * 9 + t];
+}
+
+// ---- the four parity planes of x: grid (Cin, frames), one workgroup per input plane ----------------------------------------------
+__global__ void __launch_bounds__(256) k_down_xpack(const float* __restrict__ x, float* __restrict__ xp, int cin, int hin, int win, int ho, int wo,
+                                                    int wp, int G, int PP, int PS)
+{
+    const size_t pl = (size_t)blockIdx.y * cin + blockIdx.x;
+    const float* xi = x + pl * hin * win;
+    float* xo = xp + pl * 4 * PS;
+    for (int j = threadIdx.x; j < 4 * PS; j += 256) {
+        const int par = j / PS, P = j - par * PS - G;
+        float v = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, c = P - y * wp;
+            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
+                const int iy = 2 * (y - 1) + (par >> 1), ix = 2 * (c - 1) + (par & 1);
+                if (iy < hin && ix < win) v = xi[(size_t)iy * win + ix];
+            }
+        }
+        xo[j] = v;
+    }
+}
+
+// ---- statistics + norm backward, z, dy -> dz in the padded plane: grid (Cout, frames), one workgroup per plane.  xhat is evaluated by
+// one expression in both passes, so the xhat of the mask is the xhat of the product ------------------------------------------------
+__global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, const float* __restrict__ dy, float* __restrict__ dzp, int cout, int ho,
+                                                   int wo, int wp, int G, int PP, int PS)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x, N = ho * wo;
+    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
+    const float* zi = z + pl * N;
+    const float* dp = dy + pl * N;
+    double s = 0.0, ss = 0.0;
+    for (int i = tid; i < N; i += 256) {
+        const double v = (double)zi[i];
+        s += v; ss += v * v;
+    }
+    block_sum2(s, ss, red);
+    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
+    double var = ss * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
+    double sg = 0.0, sgx = 0.0;
+    for (int i = tid; i < N; i += 256) {
+        const float xhat = (zi[i] - meanf) * rstdf;
+        if (xhat > 0.f) {
+            const double g = (double)dp[i];
+            sg += g; sgx += g * (double)xhat;
+        }
+    }
+    block_sum2(sg, sgx, red);
+    const float c1 = (float)(sg * inv_n), c2 = (float)(sgx * inv_n);
+    float* zo = dzp + pl * PS;
+    for (int j = tid; j < PS; j += 256) {
+        const int P = j - G;
+        float v = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, c = P - y * wp;
+            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
+                const int i = (y - 1) * wo + c - 1;
+                const float xhat = (zi[i] - meanf) * rstdf;
+                const float g = xhat > 0.f ? dp[i] : 0.f;
+                v = rstdf * ((g - c1) - xhat * c2);
+            }
+        }
+        zo[j] = v;
+    }
+}
+
+// ---- wgrad: workgroup tile 64 co x 32 NB columns n = ci 9 + t, four waves 2 x 2, each 32 co x 16 NB columns.  K runs over 16-position
+// chunks of the launch's frames (chunk c: frame c / cpf, positions 16 (c % cpf) ..; positions past PP read guard zeros of dz); a lane
+// takes positions 4 q .. 4 q + 3 of the chunk as its four k-steps: one 16-byte load per dz row, four shifted loads per x column.
+// blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z, already in the state_dict layout [co][ci][3][3].
+template <int NB>
+__global__ void __launch_bounds__(256) k_down_wgrad(const float* __restrict__ dzp, const float* __restrict__ xp, float* __restrict__ part, int cin,
+                                                    int cout, int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int co0 = blockIdx.y * 64 + 32 * (wave >> 1), n0 = blockIdx.x * (32 * NB) + 16 * NB * (wave & 1);
+    const int NC = 9 * cin;
+    int boff[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int n = n0 + 16 * b + l16, ci = n / 9, t = n - 9 * ci, ky = t / 3, kx = t - 3 * ky;
+        const int par = (ky != 1 ? 2 : 0) + (kx != 1 ? 1 : 0);
+        boff[b] = (ci * 4 + par) * PS + G - (ky == 0 ? wp : 0) - (kx == 0 ? 1 : 0);
+    }
+    f32x4 acc[2][NB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
+    for (int c = c0; c < c1; ++c) {
+        const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
+        const float* zf = dzp + (size_t)f * cout * PS + G + pb;
+        const float* xf = xp + (size_t)f * cin * 4 * PS + pb;
+        float za[2][4], xb[NB][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const float4 v = *reinterpret_cast<const float4*>(zf + (size_t)(co0 + 16 * a + l16) * PS);
+            za[a][0] = v.x; za[a][1] = v.y; za[a][2] = v.z; za[a][3] = v.w;
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) xb[b][s] = xf[boff[b] + s];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a][s], xb[b][s], acc[a][b], 0, 0, 0);
+    }
+    float* pw = part + (size_t)(gbase + blockIdx.z) * cout * NC;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
+}
+
+__global__ void __launch_bounds__(256) k_down_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += (double)part[(size_t)g * n + i];
+    dw[i] = (float)s;
+}
+
+// ---- dgrad: grid (position tiles, 4 parity classes, frames).  A workgroup covers ALL Cin channels (WM = Cin / 64 waves down, 4 / WM
+// across), each wave 64 ci x 32 half-resolution positions, so dz is read once per tap.  K = (t in class, co) in steps of 4 output
+// channels (lane group q takes co + q); each DA_BLOCK terms accumulate from zero and the block sums are then added in (t, co) order.
+// Positions past PP read a clamped index and are never stored; a position is stored where its input pixel (2 r + py, 2 c + px) exists,
+// into the tight [Cin][Hin][Win] plane of dx.
+template <int WM>
+__global__ void __launch_bounds__(256) k_down_dgrad(const float* __restrict__ wT, const float* __restrict__ dzp, float* __restrict__ dx, int cin,
+                                                    int cout, int hin, int win, int wp, int G, int PP, int PS)
+{
+    constexpr int WN = 4 / WM;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int ci0 = 64 * (wave / WN), p0 = blockIdx.x * (32 * WN) + 32 * (wave % WN);
+    const int py = blockIdx.y >> 1, px = blockIdx.y & 1;
+    const float* zf = dzp + (size_t)blockIdx.z * cout * PS + G;
+    float* dxf = dx + (size_t)blockIdx.z * cin * hin * win;
+    f32x4 tot[4][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) tot[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int P0 = p0 + l16, P1 = p0 + 16 + l16;
+    const int i0 = P0 < PP ? P0 : 0, i1 = P1 < PP ? P1 : 0;
+    for (int ky = py ? 0 : 1; ky < 3; ky += 2)
+        for (int kx = px ? 0 : 1; kx < 3; kx += 2) {
+            const int t = ky * 3 + kx, off = (ky == 0 ? wp : 0) + (kx == 0 ? 1 : 0);
+            const float* wt_t = wT + (size_t)t * cout * cin + ci0 + l16;
+            for (int cb0 = 0; cb0 < cout; cb0 += DA_BLOCK) { // cout is a multiple of DA_BLOCK
+                f32x4 acc[4][2];
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+                for (int cb = cb0; cb < cb0 + DA_BLOCK; cb += 4) {
+                    const int co = cb + q;
+                    const float* wr = wt_t + (size_t)co * cin;
+                    const float* zr = zf + (size_t)co * PS + off;
+                    const float z0 = zr[i0], z1 = zr[i1];
+                    float wa[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) wa[a] = wr[16 * a];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z0, acc[a][0], 0, 0, 0);
+                        acc[a][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z1, acc[a][1], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) tot[a][b] += acc[a][b];
+            }
+        }
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int P = p0 + 16 * b + l16;
+        if (P >= PP) continue;
+        const int y = P / wp, c = P - y * wp;
+        if (y < 1 || c < 1) continue;
+        const int iy = 2 * (y - 1) + py, ix = 2 * (c - 1) + px;
+        if (iy >= hin || ix >= win) continue; // covers the lower / right halo as well: 2 ho + py >= hin, 2 wo + px >= win
+        float* o = dxf + (size_t)iy * win + ix;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[(size_t)(ci0 + 16 * a + 4 * q + i) * hin * win] = tot[a][b][i];
+    }
+}
+
+down_ws* workspace(pp_ctx* ctx)
+{
+    if (!ctx->down) ctx->down = new down_ws();
+    return (down_ws*)ctx->down;
+}
+
+// K ranges of one wgrad launch over `nchunks` 16-position chunks
+void dw_ranges(int tiles, int nchunks, int* splits, int* cps)
+{
+    int sp = DW_WGS / tiles;
+    sp = sp < 1 ? 1 : sp > DW_MAX_SPLIT ? DW_MAX_SPLIT : sp;
+    if (sp > nchunks) sp = nchunks;
+    *cps = (nchunks + sp - 1) / sp;
+    *splits = (nchunks + *cps - 1) / *cps;
+}
+
+} // namespace
+
+void pp_down_destroy(pp_ctx* ctx)
+{
+    down_ws* w = (down_ws*)ctx->down;
+    if (!w) return;
+    void* q[] = {w->planes, w->wT, w->part, w->pmap};
+    for (void* x : q)
+        if (x) (void)hipFree(x);
+    delete w;
+    ctx->down = nullptr;
+}
+
+extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z, const float* dy,
+                                int nb, float* dw, float* dx, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
+    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
+    if (!x || !wgt || !z || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: null pointer");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: nb must be 1 .. max_batch");
+    const int64_t ho64 = ((int64_t)hin + 1) / 2, wo64 = ((int64_t)win + 1) / 2;
+    if (hin < 1 || win < 1 || ho64 * wo64 < 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: hin, win >= 1 and ho wo >= 2");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: w must be 16-byte aligned");
+    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward: tensors must be 4-byte aligned");
+    // padded half-resolution plane: guards of G zeros around the (ho + 2) x wp image
+    const int64_t wp64 = wo64 + 2, PP64 = (ho64 + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
+    const uint64_t pf64 = (uint64_t)(4 * cin + cout) * (uint64_t)PS64; // one frame's planes, elements
+    if (pf64 * sizeof(float) > DOWN_WS_BUDGET)
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward: map too large (one frame's planes exceed the 256 MB workspace)");
+    const int ho = (int)ho64, wo = (int)wo64, wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    down_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: functions of the shapes alone
+    const size_t pf_elems = (size_t)pf64;
+    int fc = (int)(DOWN_WS_BUDGET / (pf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int NBt = cin >= 128 ? 4 : 2;
+    const int NC = 9 * cin, tiles = (NC / (32 * NBt)) * (cout / 64), cpf = (PP + 15) / 16;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = cout * NC;
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
+        return rc;
+    float* xp = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
+    if (dx) hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, cin, cout);
+    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
+        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS);
+        hipLaunchKernelGGL(k_down_norm, dim3(cout, fn), dim3(256), 0, stream, z + oo, dy + oo, dzp, cout, ho, wo, wp, G, PP, PS);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / (32 * NBt), cout / 64, sp);
+        if (NBt == 4)
+            hipLaunchKernelGGL(k_down_wgrad<4>, gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        else
+            hipLaunchKernelGGL(k_down_wgrad<2>, gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        gbase += sp;
+        if (dx) {
+            if (cin == 64)
+                hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
+                                   G, PP, PS);
+            else
+                hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
+                                   G, PP, PS);
+        }
+    }
+    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, Gp, nw, dw);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pp_update_down_weight(pp_ctx* ctx, int level, const float* w, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_down_weight: no committed weights to update (pp_commit_weights first)");
+    if (level != 2)
+        return pp_fail(ctx, PP_E_ARG, "pp_update_down_weight: level 2 only (the strided convolution of block 3): level 0 carries the sparse "
+                                      "first-conv packing, and nothing trains level 1 yet");
+    if (!w || ((uintptr_t)w & 3)) return pp_fail(ctx, PP_E_ARG, "pp_update_down_weight: null or misaligned weight pointer");
+    if (pp_effective_precision(ctx) != 0)
+        return pp_fail(ctx, PP_E_ARG, "pp_update_down_weight: fp32 mode only (the committed plan packs the convolutions in a 16-bit format)");
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    down_ws* ws = workspace(ctx);
+    if (ws->img_gen != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
+        ws->img_gen = 0;
+        int rc = pp_net_down_image(ctx, level, &ws->img);
+        if (rc) return rc;
+        if (ws->pmap) { (void)hipFree(ws->pmap); ws->pmap = nullptr; }
+        PP_HIP(hipMalloc((void**)&ws->pmap, ws->img.pmap.size() * sizeof(int32_t)));
+        PP_HIP(hipMemcpy(ws->pmap, ws->img.pmap.data(), ws->img.pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        ws->img_gen = ctx->commit_gen;
+    }
+    pp_launch_unit_image(ws->img.w, ws->pmap, (int)ws->img.pmap.size(), w, ws->img.T, ws->img.rows * ws->img.C, stream);
+    PP_HIP(hipGetLastError());
+    return 0;
+}

@@ -128,6 +128,7 @@ struct pp_ctx {
     void* trn = nullptr;
     void* neck = nullptr;            // neck backward (neck_train.hip): dZ workspace, dW partials, index maps of the upsampler images
     void* blk = nullptr;             // Resnet unit backward (block_train.hip): padded a / dz planes, transposed weights, dW partials
+    void* down = nullptr;            // strided stage backward (down_train.hip): parity planes of x, dz planes, transposed weights, dW partials
     // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
     //      the selected candidates only; f_box / f_dir are then stale until pp_head_materialise runs the full head over the retained
     //      concat buffer and statistics of that pass ----
@@ -248,10 +249,18 @@ void pp_neck_destroy(pp_ctx* ctx);
 // Winograd families; 9: the tap of the direct tilings), -1 for padding.  fp32 images only (PP_E_ARG otherwise).
 struct pp_block_image {
     float* w = nullptr;
-    int C = 0, T = 0;
+    int C = 0, T = 0; // C: input channels
+    int rows = 0;     // output channels (= C for a unit)
     std::vector<int32_t> pmap;
 };
 int pp_net_block_image(pp_ctx* ctx, int block, int unit, pp_block_image* img);
 void pp_block_destroy(pp_ctx* ctx);
+// The same for the strided convolution in front of block `level` (0..2), for pp_update_down_weight (down_train.hip): the layer runs a
+// direct tiling, so T = 9 and pmap[i] = (row C + c) 9 + tap.  fp32 images only (PP_E_ARG otherwise).
+int pp_net_down_image(pp_ctx* ctx, int level, pp_block_image* img);
+void pp_down_destroy(pp_ctx* ctx);
+// block_train.hip's image kernel for any position map: dst[i] = position pmap[i] % T of the transformed weight of (row, cin) =
+// pmap[i] / T (< nrc), 0 for padding; w is the state_dict tensor [rows][cin][3][3] on the device
+void pp_launch_unit_image(float* dst, const int32_t* pmap, int n, const float* w, int T, int nrc, hipStream_t stream);
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

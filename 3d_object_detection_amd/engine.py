@@ -537,6 +537,70 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_block_weights(self.ctx, 2, ptrs, 5, _stream()), self.ctx, "pp_update_block_weights")
 
+    # ------------------------------------------------------------------ strided stage backward (down_train.hip)
+    DOWN_KEYS = ("rpn.block1.0.weight", "rpn.block2.0.weight", "rpn.block3.0.weight")
+    DOWN_PAIRS = ((64, 64), (64, 128), (128, 256))
+
+    def down_backward(self, x, w, z, dy, need_dx=True):
+        """pp_down_backward: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
+        (64, 128) | (128, 256).  x [nb,Cin,Hin,Win] (the stage's raw input), w [Cout,Cin,3,3], z (the conv output) and dy (dL/d(stage
+        output)) [nb,Cout,(Hin+1)//2,(Win+1)//2] -> (dw [Cout,Cin,3,3] summed over the frames, dx [nb,Cin,Hin,Win] or None when
+        need_dx is False).  fp32, deterministic, stateless."""
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
+            raise ValueError(f"down_backward: x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb, cin, hin, win = (int(v) for v in x.shape)
+        cout = int(w.shape[0]) if isinstance(w, torch.Tensor) and w.dim() == 4 else 0
+        if (cin, cout) not in self.DOWN_PAIRS:
+            raise ValueError(f"down_backward: (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
+        ho, wo = (hin + 1) // 2, (win + 1) // 2
+        if hin < 1 or win < 1 or ho * wo < 2:
+            raise ValueError(f"down_backward: the output map needs at least two elements, got {ho} x {wo}")
+        x = _chk(x, torch.float32, (nb, cin, hin, win), "down_backward: x")
+        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), "down_backward: w")
+        z = _chk(z, torch.float32, (nb, cout, ho, wo), "down_backward: z")
+        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), "down_backward: dy")
+        for t, what in ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")):
+            if t.device != self.device:
+                raise ValueError(f"down_backward: {what} is on {t.device}, the engine on {self.device}")
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
+        dw = self._t((cout, cin, 3, 3), torch.float32)
+        dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_down_backward(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(dy), nb, _ptr(dw), _ptr(dx),
+                                                 _stream()), self.ctx, "pp_down_backward")
+        return dw, dx
+
+    def backbone_stage_taps(self, canvas):
+        """pp_backbone_stage_taps: backbone_block_taps(canvas) plus the raw output of block 3's strided convolution -> (rpn_out, x1,
+        x2, x3, units [5,256,H/4,W/4], z3 [1,256,H/4,W/4]); units[0] = relu(norm(z3)).  fp32 mode only."""
+        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
+            raise ValueError("backbone_stage_taps: expected a contiguous canvas")
+        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
+             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_stage_taps: canvas [1,64,gx,gy]")
+        out = self._t((1, 320, self.H, self.W), torch.float32)
+        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        units = self._t((5,) + self.neck_shapes(2)[0], torch.float32)
+        z3 = self._t((1,) + self.neck_shapes(2)[0], torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_backbone_stage_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]),
+                                                       _ptr(units), _ptr(z3), _stream()), self.ctx, "pp_backbone_stage_taps")
+        return (out, *taps, units, z3)
+
+    def update_down_weight(self, level, tensor):
+        """pp_update_down_weight: the device tensor DOWN_KEYS[level] -> the committed image of that level's strided convolution, in
+        place on the current stream.  level 2 (rpn.block3.0.weight) only; fp32 mode only (RuntimeError otherwise, and before the
+        first load_state_dict)."""
+        if level not in (0, 1, 2):
+            raise ValueError(f"update_down_weight: level must be 0, 1 or 2, got {level!r}")
+        cin, cout = self.DOWN_PAIRS[level]
+        t = tensor.detach() if isinstance(tensor, torch.Tensor) else tensor
+        t = _chk(t, torch.float32, (cout, cin, 3, 3), "update_down_weight: " + self.DOWN_KEYS[level])
+        if t.device != self.device:
+            raise ValueError(f"update_down_weight: {self.DOWN_KEYS[level]} is on {t.device}, the engine on {self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_down_weight(self.ctx, level, _ptr(t), _stream()), self.ctx, "pp_update_down_weight")
+
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1 + _lib.PP_MAX_CLASSES,), dtype=torch.int32, device=self.device)

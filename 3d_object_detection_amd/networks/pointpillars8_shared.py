@@ -6,8 +6,11 @@ require grad; heads(x) then records a torch.autograd.Function whose backward is 
 train(scope="neck") adds the three upsampler weights rpn.deconv{1,2,3}.0.weight: the training forward then runs the backbone through
 pp_backbone_taps and records a second Function whose backward is pp_neck_backward (csrc/neck_train.hip).  train(scope="block3") adds
 the five convolutions of the deepest Resnet block (BLOCK3_KEYS, unit order): the forward runs pp_backbone_block_taps and the
-backward continues from the third upsampler's dx through five pp_unit_backward calls (csrc/block_train.hip).  Everything in front of
-block 3's units (PFN, scatter, blocks 1 and 2, the three stride-2 convolutions) is FROZEN: it has no backward pass."""
+backward continues from the third upsampler's dx through five pp_unit_backward calls (csrc/block_train.hip).  train(scope="stage3")
+adds block 3's stride-2 convolution rpn.block3.0.weight: the forward runs pp_backbone_stage_taps, which also hands out that conv's
+pre-norm output, and the backward ends in pp_down_backward (csrc/down_train.hip).  Everything in front of it (PFN, scatter, blocks 1
+and 2 with their stride-2 convolutions) is FROZEN: the gradient with respect to block 3's input is computed by pp_down_backward on
+request but nothing consumes it yet."""
 import time
 import types
 
@@ -22,6 +25,7 @@ HEAD_KEYS = ("heads.conv_cls.weight", "heads.conv_cls.bias", "heads.conv_box.wei
 NECK_KEYS = ("rpn.deconv1.0.weight", "rpn.deconv2.0.weight", "rpn.deconv3.0.weight")
 # block 3 behind its stride-2 head, h -> r3 = h + U_b(U_a(h)), r4 = r3 + U_d(U_c(r3)), x3 = r4 + U_e(r4): the weights of units a..e
 BLOCK3_KEYS = Engine.BLOCK3_KEYS
+STAGE3_KEY = Engine.DOWN_KEYS[2]  # block 3's stride-2 convolution, in front of unit a
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -109,11 +113,57 @@ class _BlockFunction(torch.autograd.Function):
         return (None, None) + tuple(dwb) + tuple(dwn)
 
 
+class _StageFunction(torch.autograd.Function):
+    """_BlockFunction with block 3's stride-2 stage in front: the forward is pp_backbone_stage_taps per frame, the backward that of
+    _BlockFunction down to unit b, then unit a with its input gradient (plus the residual path's) and pp_down_backward for the weight
+    of the stride-2 convolution.  Block 2's output gets no gradient: nothing in front of the stage trains."""
+
+    @staticmethod
+    def forward(ctx, eng, canvases, w0, *weights):
+        ctx.eng = eng
+        outs = [eng.backbone_stage_taps(c) for c in canvases]
+        y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
+        units = [torch.stack([o[4][k] for o in outs]) for k in range(5)]
+        z3 = torch.cat([o[5] for o in outs])
+        ctx.save_for_backward(y, x1, x2, x3, *units, z3, w0, *weights)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        y, *rest = ctx.saved_tensors
+        taps, units, z3, w0, wb, wn = rest[:3], rest[3:8], rest[8], rest[9], rest[10:15], rest[15:18]
+        eng, gy = ctx.eng, gy.contiguous()
+        need_0, need_b, need_n = ctx.needs_input_grad[2], ctx.needs_input_grad[3:8], ctx.needs_input_grad[8:11]
+        deep = need_0 or any(need_b)
+        dwn = [None] * 3
+        g = None
+        for b in range(3):
+            if need_n[b] or (b == 2 and deep):
+                dwn[b], dx = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=(b == 2 and deep))
+                if b == 2:
+                    g = dx
+                if not need_n[b]:
+                    dwn[b] = None
+        dwb, dw0 = [None] * 5, None
+        if deep:
+            h, m3, r3, m4, r4 = units
+            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g)
+            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4)
+            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4)
+            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3)
+            dwb[0], g_h = eng.unit_backward(h, wb[0], g_m3, dskip=g_r3, need_du=need_0)
+            dwb = [d if n else None for d, n in zip(dwb, need_b)]
+            if need_0:
+                dw0, _ = eng.down_backward(taps[1], w0, z3, g_h, need_dx=False)
+        return (None, None, dw0) + tuple(dwb) + tuple(dwn)
+
+
 class PointPillars:
     _norm = "instance"
     # read-only defaults for an object assembled without __init__ (no engine: the key-order tests); __init__ and load_state_dict
     # give every object its own
     _block, _block_uploaded, _block_trained = types.MappingProxyType({}), None, False
+    _down, _down_uploaded, _down_trained = types.MappingProxyType({}), None, False
 
     def __init__(self, config):
         self.device = config['device']
@@ -125,7 +175,11 @@ class PointPillars:
         self._uploaded = None        # their _version numbers at the last upload into the engine
         self.training = False
         self._trained = False        # the head has been stepped since load_state_dict
-        self._scope = "head"         # train(scope=...): "head", "neck" (+ the three upsamplers) or "block3" (+ block 3's five convolutions)
+        self._scope = "head"         # train(scope=...): "head", "neck" (+ the three upsamplers), "block3" (+ block 3's five unit
+                                     # convolutions) or "stage3" (+ block 3's stride-2 convolution)
+        self._down = {}              # block 3's stride-2 weight as a device Parameter
+        self._down_uploaded = None
+        self._down_trained = False
         self._block = {}             # block 3's five weights as device Parameters
         self._block_uploaded = None
         self._block_trained = False
@@ -146,39 +200,44 @@ class PointPillars:
 
     def train(self, mode=True, scope="head"):
         """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
-        trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five convolutions of block 3 (InstanceNorm backbone, fp32
-        mode); everything in front of them stays frozen: it has no backward.  eval() / train(False) restores the inference
-        behaviour."""
-        if scope not in ("head", "neck", "block3"):
-            raise ValueError(f"train: scope must be 'head', 'neck' or 'block3', got {scope!r}")
-        if mode and scope != "head" and (self._norm != "instance" or len(self._neck) != 3 or (scope == "block3" and len(self._block) != 5)):
+        trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
+        block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
+        frozen: it has no backward.  eval() / train(False) restores the inference behaviour."""
+        if scope not in ("head", "neck", "block3", "stage3"):
+            raise ValueError(f"train: scope must be 'head', 'neck', 'block3' or 'stage3', got {scope!r}")
+        if mode and scope != "head" and (self._norm != "instance" or len(self._neck) != 3 or
+                                         (scope in ("block3", "stage3") and len(self._block) != 5) or (scope == "stage3" and len(self._down) != 1)):
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only")
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
         for p in self._params.values():
             p.requires_grad_(self.training)
         for p in self._neck.values():
-            p.requires_grad_(self.training and self._scope in ("neck", "block3"))
+            p.requires_grad_(self.training and self._scope in ("neck", "block3", "stage3"))
         for p in self._block.values():
-            p.requires_grad_(self.training and self._scope == "block3")
+            p.requires_grad_(self.training and self._scope in ("block3", "stage3"))
+        for p in self._down.values():
+            p.requires_grad_(self.training and self._scope == "stage3")
         return self
 
     def _trainable(self):
+        if self._scope == "stage3":
+            return {**self._down, **self._block, **self._neck, **self._params}
         if self._scope == "block3":
             return {**self._block, **self._neck, **self._params}
         return {**self._neck, **self._params} if self._scope == "neck" else self._params
 
     def named_parameters(self):
         """The trainable tensors on the device: heads.conv_{cls,box,dir}.{weight,bias}, behind rpn.deconv{1,2,3}.0.weight under
-        train(scope="neck"), and behind BLOCK3_KEYS (unit order) as well under train(scope="block3").  Everything before them is
-        frozen."""
+        train(scope="neck"), behind BLOCK3_KEYS (unit order) as well under train(scope="block3"), and behind rpn.block3.0.weight
+        under train(scope="stage3").  Everything before them is frozen."""
         return iter(self._trainable().items())
 
     def parameters(self):
         return iter(self._trainable().values())
 
     def zero_grad(self, set_to_none=True):
-        for p in list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
+        for p in list(self._down.values()) + list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
             if set_to_none:
                 p.grad = None
             elif p.grad is not None:
@@ -197,8 +256,11 @@ class PointPillars:
     def _block_moved(self):
         return self._block_uploaded is not None and tuple(p._version for p in self._block.values()) != self._block_uploaded
 
+    def _down_moved(self):
+        return self._down_uploaded is not None and tuple(p._version for p in self._down.values()) != self._down_uploaded
+
     def _sync_neck(self):
-        """The same for the three upsampler weights and block 3's five, ahead of whatever runs the backbone."""
+        """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone."""
         if self._neck_moved():
             self._neck_trained = True
             self._eng.update_neck_weights(self._neck)
@@ -207,6 +269,10 @@ class PointPillars:
             self._block_trained = True
             self._eng.update_block_weights(self._block)
             self._block_uploaded = tuple(p._version for p in self._block.values())
+        if self._down_moved():
+            self._down_trained = True
+            self._eng.update_down_weight(2, self._down[STAGE3_KEY])
+            self._down_uploaded = tuple(p._version for p in self._down.values())
 
     def half(self):
         """The reference deploys FP16 TensorRT engines (framework/trt_utils.py:30, networks/pointpillars8_trt.py:208-223,295-314).
@@ -227,15 +293,20 @@ class PointPillars:
             self._neck_uploaded = ()  # and the trained upsamplers at the next backbone pass
         if self._block_trained or self._block_moved():
             self._block_uploaded = ()
+        if self._down_trained or self._down_moved():
+            self._down_uploaded = ()
         return self
 
     def _head_moved(self):
         return self._uploaded is not None and tuple(p._version for p in self._params.values()) != self._uploaded
 
     def state_dict(self):
-        """The loaded tensors; the head's six, the three upsampler weights and block 3's five with their CURRENT values (after
-        optimizer steps)."""
+        """The loaded tensors; the head's six, the three upsampler weights, block 3's five and its stride-2 weight with their
+        CURRENT values (after optimizer steps)."""
         sd = dict(self._sd)
+        if self._down_moved() or self._down_trained:
+            for k, p in self._down.items():
+                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
         if self._block_moved() or self._block_trained:
             for k, p in self._block.items():
                 sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
@@ -254,8 +325,12 @@ class PointPillars:
                                               requires_grad=self.training) for k in HEAD_KEYS if k in self._sd}
         self._uploaded = tuple(p._version for p in self._params.values())
         self._trained = False
-        neck = self.training and self._scope in ("neck", "block3")
-        block = self.training and self._scope == "block3"
+        neck = self.training and self._scope in ("neck", "block3", "stage3")
+        block = self.training and self._scope in ("block3", "stage3")
+        self._down = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
+                                            requires_grad=self.training and self._scope == "stage3") for k in (STAGE3_KEY,) if k in self._sd}
+        self._down_uploaded = tuple(p._version for p in self._down.values())
+        self._down_trained = False
         self._block = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
                                              requires_grad=block) for k in BLOCK3_KEYS if k in self._sd}
         self._block_uploaded = tuple(p._version for p in self._block.values())
@@ -332,13 +407,14 @@ class PointPillars:
         return self._eng.backbone(x.contiguous())
 
     def _neck_grad(self):
-        return self.training and self._scope in ("neck", "block3") and torch.is_grad_enabled() and \
-            any(p.requires_grad for p in list(self._neck.values()) + list(self._block.values()))
+        return self.training and self._scope in ("neck", "block3", "stage3") and torch.is_grad_enabled() and \
+            any(p.requires_grad for p in list(self._neck.values()) + list(self._block.values()) + list(self._down.values()))
 
     def rpn_train(self, x):
         """RPN.forward on canvases x [B,64,gx,gy], 1 <= B <= max_batch, one backbone pass per frame; same values as rpn() bit for
         bit.  Differentiable with respect to the three upsampler weights when they require grad (train(scope="neck")) and to block
-        3's five weights (train(scope="block3")); gradients are fp32 and need the fp32 precision mode."""
+        3's five unit weights (train(scope="block3")) and its stride-2 weight (train(scope="stage3")); gradients are fp32 and need
+        the fp32 precision mode."""
         eng = self._eng
         gx, gy = int(eng.grid_size[0]), int(eng.grid_size[1])
         if not isinstance(x, torch.Tensor) or x.numel() == 0 or x.numel() % (64 * gx * gy):
@@ -348,11 +424,15 @@ class PointPillars:
             raise ValueError(f"rpn_train: {x.shape[0]} frames in the batch, max_batch is {eng.max_batch}")
         self._sync_neck()
         block = any(p.requires_grad for p in self._block.values())
-        if not (torch.is_grad_enabled() and (block or any(p.requires_grad for p in self._neck.values()))):
+        stage = any(p.requires_grad for p in self._down.values())
+        if not (torch.is_grad_enabled() and (stage or block or any(p.requires_grad for p in self._neck.values()))):
             return torch.cat([eng.backbone(c) for c in x])
         if eng.effective_precision() != "fp32":
             raise RuntimeError(f"neck training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
                                "(gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place); call float()")
+        if stage:
+            return _StageFunction.apply(eng, list(x), self._down[STAGE3_KEY], *[self._block[k] for k in BLOCK3_KEYS],
+                                        *[self._neck[k] for k in NECK_KEYS])
         if block:
             return _BlockFunction.apply(eng, list(x), *[self._block[k] for k in BLOCK3_KEYS], *[self._neck[k] for k in NECK_KEYS])
         return _NeckFunction.apply(eng, list(x), *[self._neck[k] for k in NECK_KEYS])

@@ -354,6 +354,41 @@ int pp_backbone_block_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, flo
  * fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and before the first commit. */
 int pp_update_block_weights(pp_ctx* ctx, int block, const float* const* w, int n, void* stream);
 
+/* ---- strided stage backward (down_train.hip): the head of every backbone block ----
+ * Conv2d(Cin -> Cout, 3 x 3, stride 2, pad 1, no bias) -> InstanceNorm2d(eps 1e-3, no affine) -> ReLU (pointpillars8_shared.py:143-161).
+ * The stage input x f32[nb][Cin][Hin][Win] is raw (no norm in front of this conv); with ho = (Hin + 1) / 2, wo = (Win + 1) / 2,
+ * z[co, oy, ox] = sum w[co][ci][ky][kx] x[ci, 2 oy + ky - 1, 2 ox + kx - 1] (zero padding), and per plane of z, N = ho wo: mean and
+ * rstd = 1 / sqrt(biased var + 1e-3) from fp64 sums, rounded to fp32 as the forward rounds them, xhat = (z - mean) rstd, h = max(xhat, 0).
+ *
+ * pp_down_backward: backward of one stage for nb <= max_batch frames, from the conv output z and dy = dL/dh, both f32[nb][Cout][ho][wo].
+ * Stateless, fp32 whatever pp_set_precision says, InstanceNorm backbone only.  (cin, cout) is (64, 64), (64, 128) or (128, 256);
+ * hin, win >= 1 with ho wo >= 2.  w DEVICE f32[Cout][Cin][3][3] (state_dict layout, 16-byte aligned) ->
+ * dz = rstd (Gr - sum(Gr) / N - xhat sum(Gr xhat) / N) with Gr = dy [xhat > 0] (sums in fp64),
+ * dw[co][ci][ky][kx] = sum_{frames, oy, ox} dz[co, oy, ox] x[ci, 2 oy + ky - 1, 2 ox + kx - 1], f32[Cout][Cin][3][3], fully written, and
+ * dx[ci, iy, ix] = sum_{co, ky, kx} w[co][ci][ky][kx] dz[co, (iy + 1 - ky) / 2, (ix + 1 - kx) / 2] over the taps whose quotients are whole
+ * and in range, f32[nb][Cin][Hin][Win], fully written.  dx NULL: the dgrad product is not run, and dw is the same bits.  Both products
+ * are fp32-input MFMA GEMMs over zero-haloed half-resolution copies of dz and of the four row / column parity planes of x in a workspace
+ * of its own (allocated on first use, at most 256 MB: larger batches run in frame chunks; a map whose single frame exceeds it is
+ * PP_E_ARG).  Deterministic: no atomics; dw's K range (frames x positions) is split by the shapes alone and the partials are summed in
+ * index order in double, so dw depends on nb within fp32 summation error; a frame's dx does not depend on nb at all.  The dgrad sums its
+ * K = Cout x {1, 2, 2, 4} taps per output parity class in blocks of 64 from zero and adds the block sums in a fixed order.  Calls on one
+ * context must be issued in order on one stream, as for pp_unit_backward.
+ * PP_E_ARG for a null pointer, a channel pair outside the three, sizes out of range, nb outside 1..max_batch, a misaligned w and the
+ * BatchNorm backbone. */
+int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z, const float* dy, int nb,
+                     float* dw, float* dx /* NULL: skipped */, void* stream);
+/* pp_backbone_block_taps plus z3 f32[256][H/4][W/4], the raw (pre-norm) output of block 3's strided convolution, copied out behind
+ * that launch (units[0] = relu(norm(z3)); the first unit reuses the buffer).  fp32 mode only, as pp_backbone_taps. */
+int pp_backbone_stage_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* units, float* z3,
+                           void* stream);
+/* After an optimizer step: the DEVICE tensor f32[256][128][3][3] rpn.block3.0.weight (state_dict layout) -> the packed image of the
+ * strided convolution of `level` of the committed launch plan, rewritten in place on `stream`; the image equals that of a fresh commit
+ * of the same values bit for bit (a direct tiling: a permuted copy).  level must be 2: PP_E_ARG for level 0 (it carries the sparse
+ * first-conv packing) and level 1 (nothing trains it yet).  The first call after a commit reads the image's layout back once
+ * (synchronous).  The host copies of pp_load_weights are NOT changed.  fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and
+ * before the first commit. */
+int pp_update_down_weight(pp_ctx* ctx, int level, const float* w, void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);
