@@ -85,6 +85,8 @@ PROTOTYPES = {
     "pp_down_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
     "pp_backbone_stage_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_down_weight": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
+    "pp_backbone_train_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_update_rpn_weights": (ctypes.c_int, [c_p, c_p, c_p]),
     "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),
@@ -111,6 +113,7 @@ PROTOTYPES = {
     "pp_stage_profile_begin": (ctypes.c_int, [c_p]),
     "pp_stage_profile_end": (ctypes.c_int, [c_p, ctypes.POINTER(ctypes.c_double)]),
     "pp_layer_tilings": (ctypes.c_int, [c_p, ctypes.c_char_p, ctypes.c_int]),
+    "pp_weight_image": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), c_p]),
     "pp_tune_export": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "pp_tune_import": (ctypes.c_int, [ctypes.c_char_p]),
     "pp_version": (ctypes.c_int, []),

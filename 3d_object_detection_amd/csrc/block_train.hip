@@ -8,24 +8,32 @@
 // shifted read stays inside the plane, and halo x anything = 0, so both gradient products are plain GEMMs over flat positions P with
 // no branch per tap:
 //   k_unit_wt      wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows
-//   k_unit_pack    per (frame, c): sum u, sum u^2 in fp64, mean / rstd, a and dz into the padded planes (halo and guards rewritten)
+//   k_plane_stats  per (frame, c, segment): sum u, sum u^2 in fp64 over one segment of the plane
+//   k_unit_pack    per (frame, c, slice): the segments' sums added in index order, mean / rstd, a and dz into the padded planes (halo and
+//                  guards rewritten)
 //   k_unit_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      M = C, N = 9 C, K = frames x PP, split into ranges
 //   k_unit_dw_reduce  partials summed in index order (double, rounded once)
 //   k_unit_dgrad   da[ci][P] = sum_{t, co} wT[t][co][ci] dz[co][P - off_t]           M = C, N = PP, K = 9 C, summed in blocks of DA_BLOCK
-//   k_unit_norm    per (frame, c): sum Gr, sum Gr xhat in fp64 over da, then du = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) (+ dskip)
+//   k_plane_gstats per (frame, c, segment): sum Gr, sum Gr xhat in fp64 over one segment of da
+//   k_unit_norm    per (frame, c, segment): the segments' sums added in index order, du = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) (+ dskip)
+// A plane is cut into plane_segs(elements) segments, a function of the plane size alone (one segment up to 16384 elements, so block 3's
+// 100 x 100 planes run as one workgroup each; the 400 x 400 planes of level 0 as ten), so that the streaming passes fill the device at
+// level 0's 64 channels and one frame as well.
 // The two products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory, as in neck_train.hip.
 //
 // Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
-// order; K ranges of the wgrad depend on the shapes only.  A frame's a, dz, da and du do not
+// order, a plane's segment sums likewise; segments and K ranges of the wgrad depend on the shapes only.  A frame's a, dz, da and du do not
 // depend on the batch it rides in; dw depends on nb within fp32 summation error (the K ranges do).
 #include <cmath>
 #include "pp_common.h"
+#include "train_planes.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr size_t WS_BUDGET = (size_t)256 << 20; // bytes of the a + dz planes: larger batches run in frame chunks
+constexpr size_t WS_BUDGET = (size_t)256 << 20; // bytes of one frame's a + dz planes: a larger map is refused
+constexpr size_t WS_CHUNK = (size_t)1 << 30;    // bytes of the planes of one chunk of frames: larger batches run in frame chunks
 constexpr int DW_WGS = 512;                     // workgroups a wgrad launch aims at (output tiles x K ranges)
 constexpr int DW_MAX_SPLIT = 256;
 constexpr int DA_BLOCK = 64;                    // k-terms that k_unit_dgrad sums in one accumulator before adding the block to the total
@@ -33,11 +41,15 @@ constexpr int DA_BLOCK = 64;                    // k-terms that k_unit_dgrad sum
 struct block_ws {
     float* planes = nullptr; size_t planes_elems = 0; // a [fc][C][PS], then dz [fc][C][PS]
     float* stm = nullptr;    size_t stm_elems = 0;    // [fc][C][2]: mean, rstd as the forward rounds them
+    double* pst = nullptr;   size_t pst_elems = 0;    // [fc][C][segments][2]: a plane's segment sums (statistics, then the norm backward's)
     float* wT = nullptr;     size_t wT_elems = 0;
     float* part = nullptr;   size_t part_elems = 0;
     uint64_t img_gen = 0;    // ctx->commit_gen the position maps belong to (0: none)
     pp_block_image img[5];
     int32_t* pmap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t rpn_gen = 0;    // the same for pp_update_rpn_weights: all sixteen 3 x 3 convolutions in execution order
+    pp_block_image rimg[16];
+    int32_t* rpmap[16] = {};
 };
 
 // the Winograd weight transforms' G of pack_layer (F(2x2,3x3)) and wino6_pack (F(4x4,3x3)), the same constant expressions
@@ -59,18 +71,6 @@ int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need)
     return 0;
 }
 
-// both sums over the 256 threads' partials (segment t: elements t, t + 256, ...), added in index order 0 .. 255 by every thread: the
-// same bits in every thread
-__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[2])
-{
-    __syncthreads(); // red may still be read from an earlier call
-    red[threadIdx.x][0] = a; red[threadIdx.x][1] = b;
-    __syncthreads();
-    double sa = 0.0, sb = 0.0;
-    for (int t = 0; t < 256; ++t) { sa += red[t][0]; sb += red[t][1]; }
-    a = sa; b = sb;
-}
-
 __global__ void __launch_bounds__(256) k_unit_wt(const float* __restrict__ w, float* __restrict__ wT, int C)
 {
     const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][C][C]
@@ -79,30 +79,26 @@ __global__ void __launch_bounds__(256) k_unit_wt(const float* __restrict__ w, fl
     wT[i] = w[((size_t)co * C + ci) * 9 + t];
 }
 
-// ---- statistics + a + dz: grid (C, frames), one workgroup per plane ------------------------------------------------------------
+// ---- a + dz: grid (C, frames, SP), one slice of LP elements of the padded planes per workgroup ------------------------------------
 __global__ void __launch_bounds__(256) k_unit_pack(const float* __restrict__ u, const float* __restrict__ dy, float* __restrict__ ap,
-                                                   float* __restrict__ dzp, float* __restrict__ stm, int C, int h, int w, int wp, int G, int PP,
-                                                   int PS)
+                                                   float* __restrict__ dzp, float* __restrict__ stm, const double* __restrict__ pst, int C, int h,
+                                                   int w, int wp, int G, int PP, int PS, int S, int LP)
 {
-    __shared__ double red[256][2];
     const int tid = threadIdx.x, N = h * w;
     const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
     const float* up = u + pl * N;
     const float* dp = dy + pl * N;
     double s = 0.0, ss = 0.0;
-    for (int i = tid; i < N; i += 256) {
-        const double v = (double)up[i];
-        s += v; ss += v * v;
-    }
-    block_sum2(s, ss, red);
+    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
     const double inv_n = 1.0 / (double)N, mean = s * inv_n;
     double var = ss * inv_n - mean * mean;
     var = var > 0.0 ? var : 0.0;
     const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
-    if (tid == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    if (tid == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
     float* ao = ap + pl * PS;
     float* zo = dzp + pl * PS;
-    for (int j = tid; j < PS; j += 256) {
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    for (int j = lo + tid; j < hi; j += 256) {
         const int P = j - G;
         float av = 0.f, dv = 0.f;
         if (P >= 0 && P < PP) {
@@ -118,16 +114,20 @@ __global__ void __launch_bounds__(256) k_unit_pack(const float* __restrict__ u, 
     }
 }
 
-// ---- wgrad: workgroup tile 64 co x 32 NB columns n = ci 9 + t, four waves 2 x 2, each 32 co x 16 NB columns.  K runs over 16-position
+// ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
+// 64 x 32 NB (C >= 128: 128 columns).  MA = 4: four waves side by side, every one all 64 co, tile 64 x 64 NB (C = 64: 576 = 3 x 192
+// columns; a wave loads 4 dz rows and 12 a columns for 48 MFMAs where the 2 x 2 form loads 2 and 8 for 16).  K runs over 16-position
 // chunks of the launch's frames (chunk c: frame c / cpf, positions 16 (c % cpf) ..; positions past PP read guard zeros of dz); a lane
 // takes positions 4 q .. 4 q + 3 of the chunk as its four k-steps: one 16-byte load per dz row, four shifted loads per a column.
 // blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z, already in the state_dict layout [co][ci][3][3].
-template <int NB>
+template <int NB, int MA>
 __global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dzp, const float* __restrict__ ap, float* __restrict__ part, int C,
                                                     int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase)
 {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
-    const int co0 = blockIdx.y * 64 + 32 * (wave >> 1), n0 = blockIdx.x * (32 * NB) + 16 * NB * (wave & 1);
+    static_assert(MA == 2 || MA == 4, "waves 2 x 2 or 1 x 4");
+    constexpr int WC = MA;     // waves across the tile: 2 of 2 x 2, 4 of 1 x 4
+    const int co0 = blockIdx.y * 64 + (MA == 2 ? 32 * (wave >> 1) : 0), n0 = blockIdx.x * (16 * NB * WC) + 16 * NB * (wave & (WC - 1));
     const int NC = 9 * C;
     int boff[NB];
 #pragma unroll
@@ -135,9 +135,9 @@ __global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dz
         const int n = n0 + 16 * b + l16, ci = n / 9, t = n - 9 * ci;
         boff[b] = ci * PS + G + (t / 3 - 1) * wp + (t % 3 - 1);
     }
-    f32x4 acc[2][NB];
+    f32x4 acc[MA][NB];
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < MA; ++a)
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
@@ -145,9 +145,9 @@ __global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dz
         const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
         const float* zf = dzp + (size_t)f * C * PS + G + pb;
         const float* af = ap + (size_t)f * C * PS + pb;
-        float za[2][4], ab[NB][4];
+        float za[MA][4], ab[NB][4];
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
+        for (int a = 0; a < MA; ++a) {
             const float4 v = *reinterpret_cast<const float4*>(zf + (size_t)(co0 + 16 * a + l16) * PS);
             za[a][0] = v.x; za[a][1] = v.y; za[a][2] = v.z; za[a][3] = v.w;
         }
@@ -158,25 +158,32 @@ __global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dz
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+            for (int a = 0; a < MA; ++a)
 #pragma unroll
                 for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a][s], ab[b][s], acc[a][b], 0, 0, 0);
     }
     float* pw = part + (size_t)(gbase + blockIdx.z) * C * NC;
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < MA; ++a)
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
 }
 
-__global__ void __launch_bounds__(256) k_unit_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
+// partials added in index order, four loads in flight: 64-thread workgroups, so that a 64 x 64 weight spreads over all compute units
+__global__ void __launch_bounds__(64) k_unit_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
+    const float* p = part + i;
     double s = 0.0;
-    for (int g = 0; g < G; ++g) s += (double)part[(size_t)g * n + i];
+    int g = 0;
+    for (; g + 3 < G; g += 4) {
+        const float a = p[(size_t)g * n], b = p[(size_t)(g + 1) * n], c = p[(size_t)(g + 2) * n], d = p[(size_t)(g + 3) * n];
+        s += (double)a; s += (double)b; s += (double)c; s += (double)d;
+    }
+    for (; g < G; ++g) s += (double)p[(size_t)g * n];
     dw[i] = (float)s;
 }
 
@@ -245,12 +252,34 @@ __global__ void __launch_bounds__(256) k_unit_dgrad(const float* __restrict__ wT
     }
 }
 
-// ---- norm backward, in place over da (= du): grid (C, frames).  Gr = da [a > 0] with the a of this call; xhat is re-evaluated by the
-// expression k_unit_pack used, so it is the xhat whose sign made the mask ------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, const float* __restrict__ ap, const float* __restrict__ stm,
-                                                   const float* __restrict__ dskip, float* __restrict__ du, int C, int h, int w, int wp, int G, int PS)
+// ---- norm backward, in place over da (= du).  Gr = da [a > 0] with the a of this call; xhat is re-evaluated by the expression
+// k_unit_pack used, so it is the xhat whose sign made the mask.  k_plane_gstats: grid (C, frames, S), sum Gr and sum Gr xhat of one
+// segment; k_unit_norm: grid (C, frames, S), the same segments rewritten once every sum is in ----------------------------------------
+__global__ void __launch_bounds__(256) k_plane_gstats(const float* __restrict__ ap, const float* __restrict__ du, double* __restrict__ pst, int C,
+                                                      int w, int wp, int G, int PS, int N, int L, int S)
 {
     __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* ai = ap + pl * PS + G + wp + 1; // interior origin
+    const float* dp = du + pl * N;
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sg = 0.0, sgx = 0.0;
+    strided4(lo, hi, [&](int i) { const int y = i / w, x = i - y * w; return float2{ai[y * wp + x], dp[i]}; },
+             [&](float2 v) {
+                 if (v.x > 0.f) {
+                     const double g = (double)v.y;
+                     sg += g; sgx += g * (double)v.x;
+                 }
+             });
+    block_sum2(sg, sgx, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sg; pst[(pl * S + blockIdx.z) * 2 + 1] = sgx; }
+}
+
+__global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, const float* __restrict__ ap, const float* __restrict__ stm,
+                                                   const double* __restrict__ pst, const float* __restrict__ dskip, float* __restrict__ du, int C,
+                                                   int h, int w, int wp, int G, int PS, int L, int S)
+{
     const int tid = threadIdx.x, N = h * w;
     const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
     const float* up = u + pl * N;
@@ -258,18 +287,11 @@ __global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, 
     float* dp = du + pl * N;
     const float meanf = stm[pl * 2], rstdf = stm[pl * 2 + 1];
     double sg = 0.0, sgx = 0.0;
-    for (int i = tid; i < N; i += 256) {
-        const int y = i / w, x = i - y * w;
-        const float av = ai[y * wp + x];
-        if (av > 0.f) {
-            const double g = (double)dp[i];
-            sg += g; sgx += g * (double)av;
-        }
-    }
-    block_sum2(sg, sgx, red);
+    for (int g = 0; g < S; ++g) { sg += pst[(pl * S + g) * 2]; sgx += pst[(pl * S + g) * 2 + 1]; }
     const double inv_n = 1.0 / (double)N;
     const float c1 = (float)(sg * inv_n), c2 = (float)(sgx * inv_n);
-    for (int i = tid; i < N; i += 256) {
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    for (int i = lo + tid; i < hi; i += 256) {
         const int y = i / w, x = i - y * w;
         const float g = ai[y * wp + x] > 0.f ? dp[i] : 0.f;
         const float xhat = (up[i] - meanf) * rstdf;
@@ -325,8 +347,10 @@ void pp_block_destroy(pp_ctx* ctx)
 {
     block_ws* w = (block_ws*)ctx->blk;
     if (!w) return;
-    void* q[] = {w->planes, w->stm, w->wT, w->part, w->pmap[0], w->pmap[1], w->pmap[2], w->pmap[3], w->pmap[4]};
+    void* q[] = {w->planes, w->stm, w->pst, w->wT, w->part, w->pmap[0], w->pmap[1], w->pmap[2], w->pmap[3], w->pmap[4]};
     for (void* x : q)
+        if (x) (void)hipFree(x);
+    for (int32_t* x : w->rpmap)
         if (x) (void)hipFree(x);
     delete w;
     ctx->blk = nullptr;
@@ -359,10 +383,10 @@ extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u
     block_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: functions of the shapes alone
     const size_t pf_elems = (size_t)C * PS;
-    int fc = (int)(WS_BUDGET / (2 * pf_elems * sizeof(float)));
+    int fc = (int)(WS_CHUNK / (2 * pf_elems * sizeof(float)));
     fc = fc < 1 ? 1 : fc > nb ? nb : fc;
-    const int NBt = C >= 128 ? 4 : 2;
-    const int NC = 9 * C, tiles = (NC / (32 * NBt)) * (C / 64), cpf = (PP + 15) / 16;
+    const int TN = C >= 128 ? 128 : 192; // columns of a wgrad tile: k_unit_wgrad<4, 2> or <3, 4>
+    const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
     int Gp = 0;
     for (int f0 = 0; f0 < nb; f0 += fc) {
         int sp, cps;
@@ -370,9 +394,12 @@ extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u
         Gp += sp;
     }
     const int nw = C * NC;
+    // segments of the streaming passes: over the tight plane (statistics, norm backward) and over the padded one (pack)
+    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
     int rc;
     if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
         (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)fc * C * 2)) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)fc * C * SEG_MAX * 2)) ||
         (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
         (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
         return rc;
@@ -383,14 +410,15 @@ extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u
     for (int f0 = 0; f0 < nb; f0 += fc) {
         const int fn = nb - f0 < fc ? nb - f0 : fc;
         const size_t o = (size_t)f0 * C * N;
-        hipLaunchKernelGGL(k_unit_pack, dim3(C, fn), dim3(256), 0, stream, u + o, dy + o, ap, dzp, ws->stm, C, h, w, wp, G, PP, PS);
+        hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->pst, C, N, L, S);
+        hipLaunchKernelGGL(k_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, ap, dzp, ws->stm, ws->pst, C, h, w, wp, G, PP, PS, S, LP);
         int sp, cps;
         dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / (32 * NBt), C / 64, sp);
-        if (NBt == 4)
-            hipLaunchKernelGGL(k_unit_wgrad<4>, gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        const dim3 gd(NC / TN, C / 64, sp);
+        if (C >= 128)
+            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
         else
-            hipLaunchKernelGGL(k_unit_wgrad<2>, gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
         gbase += sp;
         if (du) {
             float* duc = du + o;
@@ -400,11 +428,12 @@ extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u
                 hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
             else
                 hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            hipLaunchKernelGGL(k_unit_norm, dim3(C, fn), dim3(256), 0, stream, u + o, ap, ws->stm, dskip ? dskip + o : nullptr, duc, C, h, w, wp,
-                               G, PS);
+            hipLaunchKernelGGL(k_plane_gstats, dim3(C, fn, S), dim3(256), 0, stream, ap, duc, ws->pst, C, w, wp, G, PS, N, L, S);
+            hipLaunchKernelGGL(k_unit_norm, dim3(C, fn, S), dim3(256), 0, stream, u + o, ap, ws->stm, ws->pst, dskip ? dskip + o : nullptr, duc, C,
+                               h, w, wp, G, PS, L, S);
         }
     }
-    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, Gp, nw, dw);
+    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
     PP_HIP(hipGetLastError());
     return 0;
 }
@@ -440,6 +469,43 @@ extern "C" int pp_update_block_weights(pp_ctx* ctx, int block, const float* cons
         const int cnt = (int)im.pmap.size();
         pp_launch_unit_image(im.w, ws->pmap[k], cnt, w[k], im.T, im.rows * im.C, stream);
     }
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// All sixteen 3 x 3 convolutions of the RPN in execution order (= state_dict order): per level its strided convolution, then its 3 | 5 | 5
+// unit convolutions.  Level 0's strided weight is also the sparse first convolution's, which keeps an image of its own.
+extern "C" int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights: no committed weights to update (pp_commit_weights first)");
+    if (!w) return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights: null pointer");
+    for (int k = 0; k < 16; ++k)
+        if (!w[k] || ((uintptr_t)w[k] & 3)) return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights: null or misaligned weight pointer");
+    if (pp_effective_precision(ctx) != 0)
+        return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights: fp32 mode only (the committed plan packs the convolutions in a 16-bit format)");
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    if (ws->rpn_gen != ctx->commit_gen) { // first update after a commit: read the committed images' layout back (synchronous)
+        ws->rpn_gen = 0;
+        int k = 0;
+        for (int b = 0; b < 3; ++b)
+            for (int u = -1; u < (b == 0 ? 3 : 5); ++u, ++k) {
+                int rc = u < 0 ? pp_net_down_image(ctx, b, &ws->rimg[k]) : pp_net_block_image(ctx, b, u, &ws->rimg[k]);
+                if (rc) return rc;
+                if (ws->rpmap[k]) { (void)hipFree(ws->rpmap[k]); ws->rpmap[k] = nullptr; }
+                PP_HIP(hipMalloc((void**)&ws->rpmap[k], ws->rimg[k].pmap.size() * sizeof(int32_t)));
+                PP_HIP(hipMemcpy(ws->rpmap[k], ws->rimg[k].pmap.data(), ws->rimg[k].pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            }
+        ws->rpn_gen = ctx->commit_gen;
+    }
+    for (int k = 0; k < 16; ++k) {
+        const pp_block_image& im = ws->rimg[k];
+        pp_launch_unit_image(im.w, ws->rpmap[k], (int)im.pmap.size(), w[k], im.T, im.rows * im.C, stream);
+    }
+    int rc = pp_sc1_update(ctx, w[0], stream);
+    if (rc) return rc;
     PP_HIP(hipGetLastError());
     return 0;
 }

@@ -149,8 +149,9 @@ struct pp_net {
     bool defer_ok = false; // the committed plan can run the deferred head: fp32 mode, 9-anchor head on a gemm1x1 tiling
     Variant cls_var;       // tiling of the cls-only head pass (chosen at pp_commit_weights when defer_ok)
     const float* tap[3] = {}; // block outputs of the last pp_run_backbone pass (what the three upsamplers read): pp_backbone_taps
-    float* unit_tap = nullptr; // copy hook of pp_backbone_block_taps: caller memory f32[5][256][H/4][W/4] for block 3's unit inputs (null: inert)
-    float* z3_tap = nullptr;   // copy hook of pp_backbone_stage_taps: caller memory f32[256][H/4][W/4] for the raw output of block 3's strided conv (null: inert)
+    // copy hooks of the tap entry points, one per level b (null: inert; armed for one single-frame pass):
+    float* unit_tap[3] = {}; // caller memory f32[n_b][C_b][H>>b][W>>b] for the inputs of block b + 1's units (n_b = 3, 5, 5); pp_backbone_block_taps arms level 2
+    float* z_tap[3] = {};    // caller memory f32[C_b][H>>b][W>>b] for the raw output of level b's strided conv; pp_backbone_stage_taps arms level 2
     double* dbg_stats = nullptr; // statistics accumulators of pp_debug_layer (allocated on its first call that asks for statistics)
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };
@@ -760,9 +761,15 @@ int autotune_layer(pp_ctx* ctx, Layer& L, int Hin, int Win, int Hout, int Wout, 
     snprintf(sig, sizeof(sig), "v%d m%d k%d s%d u%d c%d r%d %dx%d n%d b%d p%d", pp_version(), (int)menu.size(), L.kind, L.stride, L.up, L.cin, L.cout, Hout, Wout,
              ctx->cfg.norm_kind, ctx->max_batch < TUNE_FRAMES ? ctx->max_batch : TUNE_FRAMES, eprec);
     const int rows = (L.kind == 2) ? head_rows(ctx->cfg.num_anchor_per_loc) : (L.kind == 1 ? L.cout * L.up * L.up : L.cout);
-    if (const char* force = getenv("PP_FORCE_VARIANT")) { // tests: pin a tiling family by name substring
-        for (const Variant& v : menu)
-            if (variant_ok(v, rows) && shape_ok(v, Hin, Win, Wout) && strstr(v.name, force)) { L.var = v; return 0; }
+    if (const char* force = getenv("PP_FORCE_VARIANT")) { // tests: pin a tiling family by name substring; "a;b": a where a layer has one, else b
+        const std::string all(force);
+        for (size_t p = 0; p <= all.size();) {
+            const size_t e = std::min(all.find(';', p), all.size());
+            const std::string one = all.substr(p, e - p);
+            for (const Variant& v : menu)
+                if (variant_ok(v, rows) && shape_ok(v, Hin, Win, Wout) && strstr(v.name, one.c_str())) { L.var = v; return 0; }
+            p = e + 1;
+        }
     }
     auto hit = tune_cache().find(sig);
     if (hit != tune_cache().end()) {
@@ -1208,9 +1215,9 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
             }
         } else if ((rc = launch_conv(ctx, net->layers[li++], x, Hin, Win, Bf[0], nullptr, raw, stat_slot(ctx, site_block(b, 0)), c, h, w, stream,
                               nullptr, nullptr, nb, 0, 0, b == 0 ? pmap : nullptr, b == 0 ? feat : nullptr))) return rc;
-        // block 3's pre-norm conv output z leaves through its own copy hook: the first unit reuses Bf[0] as a spare
-        if (b == 2 && nb == 1 && net->z3_tap)
-            PP_HIP(hipMemcpyAsync(net->z3_tap, Bf[0], (size_t)c * cnt * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        // the level's pre-norm conv output z leaves through its own copy hook: the first unit reuses Bf[0] as a spare
+        if (nb == 1 && net->z_tap[b])
+            PP_HIP(hipMemcpyAsync(net->z_tap[b], Bf[0], (size_t)c * cnt * sizeof(float), hipMemcpyDeviceToDevice, stream));
         // y = relu(norm(Bf[0])) -> Bf[1] + stats(site 1) (the first Resnet2 unit's leading norm)
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_NORM))) return rc;
         if ((rc = launch_norm_relu(ctx, Bf[0], Bf[1], c, (int)cnt, norm_ref(ctx, site_block(b, 0), c, 0, cnt),
@@ -1218,9 +1225,9 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_CONV))) return rc;
         float* cur = Bf[1];
         float* spare[3] = {Bf[0], Bf[2], Bf[3]};
-        // block 3's unit inputs h, m3, r3, m4, r4 leave through the copy hook behind the launch that produces each: the level
-        // buffers are reused before the pass ends
-        float* utap = (b == 2 && nb == 1) ? net->unit_tap : nullptr;
+        // the unit inputs (h, m, r at level 0; h, m3, r3, m4, r4 at levels 1 and 2) leave through the copy hook behind the launch that
+        // produces each: the level buffers are reused before the pass ends
+        float* utap = nb == 1 ? net->unit_tap[b] : nullptr;
         const size_t ubytes = (size_t)c * cnt * sizeof(float);
         int ucount = 0;
         if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, cur, ubytes, hipMemcpyDeviceToDevice, stream));
@@ -1531,9 +1538,9 @@ extern "C" int pp_backbone_block_taps(pp_ctx* ctx, const float* canvas, float* r
     if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_block_taps: weights not committed");
     if (!units) return pp_fail(ctx, PP_E_ARG, "pp_backbone_block_taps: null pointer");
     pp_net* net = (pp_net*)ctx->net;
-    net->unit_tap = units; // pp_backbone_taps checks the rest; the hook is armed for this one pass only
+    net->unit_tap[2] = units; // pp_backbone_taps checks the rest; the hook is armed for this one pass only
     int rc = pp_backbone_taps(ctx, canvas, rpn_out, x1, x2, x3, stream_);
-    net->unit_tap = nullptr;
+    net->unit_tap[2] = nullptr;
     return rc;
 }
 
@@ -1544,9 +1551,25 @@ extern "C" int pp_backbone_stage_taps(pp_ctx* ctx, const float* canvas, float* r
     if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_stage_taps: weights not committed");
     if (!z3) return pp_fail(ctx, PP_E_ARG, "pp_backbone_stage_taps: null pointer");
     pp_net* net = (pp_net*)ctx->net;
-    net->z3_tap = z3; // pp_backbone_block_taps checks the rest; the hook is armed for this one pass only
+    net->z_tap[2] = z3; // pp_backbone_block_taps checks the rest; the hook is armed for this one pass only
     int rc = pp_backbone_block_taps(ctx, canvas, rpn_out, x1, x2, x3, units, stream_);
-    net->z3_tap = nullptr;
+    net->z_tap[2] = nullptr;
+    return rc;
+}
+
+// every level's hooks at once: units[b] f32[3 | 5 | 5][C_b][H>>b][W>>b], z[b] f32[C_b][H>>b][W>>b]
+extern "C" int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* const* units,
+                                      float* const* z, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_train_taps: weights not committed");
+    if (!units || !z) return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps: null pointer");
+    for (int b = 0; b < 3; ++b)
+        if (!units[b] || !z[b]) return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps: null pointer");
+    pp_net* net = (pp_net*)ctx->net;
+    for (int b = 0; b < 3; ++b) { net->unit_tap[b] = units[b]; net->z_tap[b] = z[b]; } // pp_backbone_taps checks the rest; armed for this one pass only
+    int rc = pp_backbone_taps(ctx, canvas, rpn_out, x1, x2, x3, stream_);
+    for (int b = 0; b < 3; ++b) net->unit_tap[b] = net->z_tap[b] = nullptr;
     return rc;
 }
 
@@ -1734,6 +1757,24 @@ extern "C" double pp_dominant_executed_ratio(pp_ctx* ctx)
         if (L.kind == 0 && L.level == 0 && L.stride == 1) // x the share of the dense work items the profiled launches ran (tile skipping)
             return executed_ratio(L.var) * (ctx->prof_items_dense > 0.0 ? ctx->prof_items / ctx->prof_items_dense : 1.0);
     return 1.0;
+}
+
+// Test / inspection hook: the packed weight image of layer `layer` of the committed plan (0 .. 19), or of the sparse first convolution
+// (layer = -1), copied device -> device on `stream`.  Returns the image's size in bytes through `bytes`; dst may be NULL to query.
+extern "C" int pp_weight_image(pp_ctx* ctx, int layer, void* dst, size_t cap, size_t* bytes, void* stream_)
+{
+    if (!ctx || !bytes) return pp_fail(ctx, PP_E_ARG, "pp_weight_image: null pointer");
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_weight_image: weights not committed");
+    PP_HIP(hipSetDevice(ctx->device));
+    pp_net* net = (pp_net*)ctx->net;
+    const void* src = nullptr;
+    if (layer == -1) src = pp_first_conv_image(ctx, bytes);
+    else if (layer >= 0 && layer < (int)net->layers.size()) { src = net->layers[layer].w; *bytes = net->layers[layer].w_bytes; }
+    if (!src) return pp_fail(ctx, PP_E_ARG, "pp_weight_image: no such image");
+    if (!dst) return 0;
+    if (cap < *bytes) return pp_fail(ctx, PP_E_ARG, "pp_weight_image: dst too small");
+    PP_HIP(hipMemcpyAsync(dst, src, *bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream_));
+    return 0;
 }
 
 // The network's launch plan as text, one line per conv / deconv / head layer in execution order:

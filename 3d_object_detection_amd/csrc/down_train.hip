@@ -9,9 +9,14 @@
 // bands of G >= wp + 17 zeros, PS elements in all (G and PS multiples of 4).  Tap t = (ky, kx) is then plane (ky != 1, kx != 1) shifted
 // by the flat offset off_t = -(ky == 0) wp - (kx == 0), every shifted read stays inside the plane, and halo x anything = 0:
 //   k_down_wt      wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows
-//   k_down_xpack   per (frame, ci): the four parity planes of x (halo and guards rewritten)
-//   k_down_norm    per (frame, co): sum z, sum z^2 in fp64, mean / rstd as the forward rounds them, Gr = dy [xhat > 0], sum Gr, sum Gr xhat
-//                  in fp64, dz = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) into the padded plane
+//   k_down_xpack   per (frame, ci, slice): the four parity planes of x (halo and guards rewritten), x read once
+//   k_plane_stats  per (frame, co, segment): sum z, sum z^2 in fp64 over one segment of the plane (train_planes.h)
+//   k_dplane_gstats  per (frame, co, segment): mean / rstd as the forward rounds them from the segments' sums added in index order,
+//                  Gr = dy [xhat > 0], sum Gr, sum Gr xhat in fp64 over the segment
+//   k_down_norm    per (frame, co, slice): both sets of segment sums added in index order, dz = rstd (Gr - mean(Gr) - xhat mean(Gr xhat))
+//                  into the padded plane
+// A plane is cut into plane_segs(elements) segments, a function of the plane size alone (train_planes.h, shared with block_train.hip: one segment up to 16384
+// elements: block 3's 100 x 100 output planes run as one workgroup each, level 0's 400 x 400 as ten).
 //   k_down_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] xp[ci][plane_t][P + off_t]    M = Cout, N = 9 Cin, K = frames x PP in ranges
 //   k_down_dw_reduce  partials summed in index order (double, rounded once)
 //   k_down_dgrad   per output parity class (py, px), P the half-resolution position of x[2 r + py][2 c + px]:
@@ -20,22 +25,25 @@
 // The two products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory, as in block_train.hip.
 //
 // Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
-// order; K ranges of the wgrad depend on the shapes only.  A frame's dz and dx do not depend on the batch it rides in; dw depends on
+// order, a plane's segment sums likewise; segments and K ranges of the wgrad depend on the shapes only.  A frame's dz and dx do not depend on the batch it rides in; dw depends on
 // nb within fp32 summation error (the K ranges do), and not on whether dx is asked for.
 #include <cmath>
 #include "pp_common.h"
+#include "train_planes.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr size_t DOWN_WS_BUDGET = (size_t)256 << 20; // bytes of the x parity planes + dz planes: larger batches run in frame chunks
+constexpr size_t DOWN_WS_BUDGET = (size_t)256 << 20; // bytes of one frame's x parity planes + dz planes: a larger map is refused
+constexpr size_t DOWN_WS_CHUNK = (size_t)1 << 30;    // bytes of the planes of one chunk of frames: larger batches run in frame chunks
 constexpr int DW_WGS = 512;                          // workgroups a wgrad launch aims at (output tiles x K ranges)
 constexpr int DW_MAX_SPLIT = 256;
 constexpr int DA_BLOCK = 64;                         // k-terms that k_down_dgrad sums in one accumulator before adding the block to the total
 
 struct down_ws {
     float* planes = nullptr; size_t planes_elems = 0; // xp [fc][Cin][4][PS], then dz [fc][Cout][PS]
+    double* pst = nullptr;   size_t pst_elems = 0;    // [2][fc][Cout][segments][2]: a plane's segment sums of (z, z^2), then of (Gr, Gr xhat)
     float* wT = nullptr;     size_t wT_elems = 0;
     float* part = nullptr;   size_t part_elems = 0;
     uint64_t img_gen = 0;    // ctx->commit_gen the position map belongs to (0: none)
@@ -57,18 +65,6 @@ int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need)
     return 0;
 }
 
-// both sums over the 256 threads' partials (segment t: elements t, t + 256, ...), added in index order 0 .. 255 by every thread: the
-// same bits in every thread
-__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[2])
-{
-    __syncthreads(); // red may still be read from an earlier call
-    red[threadIdx.x][0] = a; red[threadIdx.x][1] = b;
-    __syncthreads();
-    double sa = 0.0, sb = 0.0;
-    for (int t = 0; t < 256; ++t) { sa += red[t][0]; sb += red[t][1]; }
-    a = sa; b = sb;
-}
-
 __global__ void __launch_bounds__(256) k_down_wt(const float* __restrict__ w, float* __restrict__ wT, int cin, int cout)
 {
     const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][cout][cin]
@@ -77,59 +73,89 @@ __global__ void __launch_bounds__(256) k_down_wt(const float* __restrict__ w, fl
     wT[i] = w[((size_t)co * cin + ci) * 9 + t];
 }
 
-// ---- the four parity planes of x: grid (Cin, frames), one workgroup per input plane ----------------------------------------------
+// ---- the four parity planes of x: grid (Cin, frames, SP), one slice of LP positions per workgroup.  A position takes its 2 x 2 input
+// pixels (x is read once, whole rows at a time) and writes one element of each plane -----------------------------------------------
 __global__ void __launch_bounds__(256) k_down_xpack(const float* __restrict__ x, float* __restrict__ xp, int cin, int hin, int win, int ho, int wo,
-                                                    int wp, int G, int PP, int PS)
+                                                    int wp, int G, int PP, int PS, int LP)
 {
     const size_t pl = (size_t)blockIdx.y * cin + blockIdx.x;
     const float* xi = x + pl * hin * win;
     float* xo = xp + pl * 4 * PS;
-    for (int j = threadIdx.x; j < 4 * PS; j += 256) {
-        const int par = j / PS, P = j - par * PS - G;
-        float v = 0.f;
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    for (int j = lo + threadIdx.x; j < hi; j += 256) {
+        const int P = j - G;
+        float v00 = 0.f, v01 = 0.f, v10 = 0.f, v11 = 0.f; // (row parity, column parity)
         if (P >= 0 && P < PP) {
             const int y = P / wp, c = P - y * wp;
             if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int iy = 2 * (y - 1) + (par >> 1), ix = 2 * (c - 1) + (par & 1);
-                if (iy < hin && ix < win) v = xi[(size_t)iy * win + ix];
+                const int iy = 2 * (y - 1), ix = 2 * (c - 1); // in the image: 2 (ho - 1) < hin, 2 (wo - 1) < win
+                const float* r = xi + (size_t)iy * win + ix;
+                const bool right = ix + 1 < win, below = iy + 1 < hin;
+                v00 = r[0];
+                if (right) v01 = r[1];
+                if (below) v10 = r[win];
+                if (right && below) v11 = r[win + 1];
             }
         }
-        xo[j] = v;
+        xo[j] = v00; xo[PS + j] = v01; xo[2 * PS + j] = v10; xo[3 * PS + j] = v11;
     }
 }
 
-// ---- statistics + norm backward, z, dy -> dz in the padded plane: grid (Cout, frames), one workgroup per plane.  xhat is evaluated by
-// one expression in both passes, so the xhat of the mask is the xhat of the product ------------------------------------------------
-__global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, const float* __restrict__ dy, float* __restrict__ dzp, int cout, int ho,
-                                                   int wo, int wp, int G, int PP, int PS)
+// mean and rstd of a plane as the forward rounds them, from its segment sums added in index order
+__device__ __forceinline__ void plane_mean_rstd(const double* __restrict__ pst, size_t pl, int S, int N, float& meanf, float& rstdf)
+{
+    double s = 0.0, ss = 0.0;
+    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
+    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
+    double var = ss * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    meanf = (float)mean; rstdf = (float)(1.0 / sqrt(var + 1e-3));
+}
+
+// ---- sums of the norm backward: grid (Cout, frames, S), sum Gr and sum Gr xhat of one segment -> pst2.  xhat is evaluated by one
+// expression here and in k_down_norm, so the xhat of the mask is the xhat of the product -------------------------------------------
+__global__ void __launch_bounds__(256) k_dplane_gstats(const float* __restrict__ z, const float* __restrict__ dy, const double* __restrict__ pst,
+                                                       double* __restrict__ pst2, int cout, int N, int L, int S)
 {
     __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
+    const float* zi = z + pl * N;
+    const float* dp = dy + pl * N;
+    float meanf, rstdf;
+    plane_mean_rstd(pst, pl, S, N, meanf, rstdf);
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sg = 0.0, sgx = 0.0;
+    strided4(lo, hi, [&](int i) { return float2{zi[i], dp[i]}; },
+             [&](float2 v) {
+                 const float xhat = (v.x - meanf) * rstdf;
+                 if (xhat > 0.f) {
+                     const double g = (double)v.y;
+                     sg += g; sgx += g * (double)xhat;
+                 }
+             });
+    block_sum2(sg, sgx, red);
+    if (tid == 0) { pst2[(pl * S + blockIdx.z) * 2] = sg; pst2[(pl * S + blockIdx.z) * 2 + 1] = sgx; }
+}
+
+// ---- norm backward, z, dy -> dz in the padded plane: grid (Cout, frames, SP), one slice of LP elements of the plane per workgroup -
+__global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, const float* __restrict__ dy, float* __restrict__ dzp,
+                                                   const double* __restrict__ pst, const double* __restrict__ pst2, int cout, int ho, int wo, int wp,
+                                                   int G, int PP, int PS, int S, int LP)
+{
     const int tid = threadIdx.x, N = ho * wo;
     const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
     const float* zi = z + pl * N;
     const float* dp = dy + pl * N;
-    double s = 0.0, ss = 0.0;
-    for (int i = tid; i < N; i += 256) {
-        const double v = (double)zi[i];
-        s += v; ss += v * v;
-    }
-    block_sum2(s, ss, red);
-    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
-    double var = ss * inv_n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
+    float meanf, rstdf;
+    plane_mean_rstd(pst, pl, S, N, meanf, rstdf);
     double sg = 0.0, sgx = 0.0;
-    for (int i = tid; i < N; i += 256) {
-        const float xhat = (zi[i] - meanf) * rstdf;
-        if (xhat > 0.f) {
-            const double g = (double)dp[i];
-            sg += g; sgx += g * (double)xhat;
-        }
-    }
-    block_sum2(sg, sgx, red);
+    for (int g = 0; g < S; ++g) { sg += pst2[(pl * S + g) * 2]; sgx += pst2[(pl * S + g) * 2 + 1]; }
+    const double inv_n = 1.0 / (double)N;
     const float c1 = (float)(sg * inv_n), c2 = (float)(sgx * inv_n);
     float* zo = dzp + pl * PS;
-    for (int j = tid; j < PS; j += 256) {
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    for (int j = lo + tid; j < hi; j += 256) {
         const int P = j - G;
         float v = 0.f;
         if (P >= 0 && P < PP) {
@@ -145,16 +171,20 @@ __global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, 
     }
 }
 
-// ---- wgrad: workgroup tile 64 co x 32 NB columns n = ci 9 + t, four waves 2 x 2, each 32 co x 16 NB columns.  K runs over 16-position
+// ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
+// 64 x 32 NB (Cin = 128: 128 columns).  MA = 4: four waves side by side, every one all 64 co, tile 64 x 64 NB (Cin = 64: 576 = 3 x 192
+// columns; a wave loads 4 dz rows and 12 x columns for 48 MFMAs where the 2 x 2 form loads 2 and 8 for 16).  K runs over 16-position
 // chunks of the launch's frames (chunk c: frame c / cpf, positions 16 (c % cpf) ..; positions past PP read guard zeros of dz); a lane
 // takes positions 4 q .. 4 q + 3 of the chunk as its four k-steps: one 16-byte load per dz row, four shifted loads per x column.
 // blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z, already in the state_dict layout [co][ci][3][3].
-template <int NB>
+template <int NB, int MA>
 __global__ void __launch_bounds__(256) k_down_wgrad(const float* __restrict__ dzp, const float* __restrict__ xp, float* __restrict__ part, int cin,
                                                     int cout, int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase)
 {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
-    const int co0 = blockIdx.y * 64 + 32 * (wave >> 1), n0 = blockIdx.x * (32 * NB) + 16 * NB * (wave & 1);
+    static_assert(MA == 2 || MA == 4, "waves 2 x 2 or 1 x 4");
+    constexpr int WC = MA;     // waves across the tile: 2 of 2 x 2, 4 of 1 x 4
+    const int co0 = blockIdx.y * 64 + (MA == 2 ? 32 * (wave >> 1) : 0), n0 = blockIdx.x * (16 * NB * WC) + 16 * NB * (wave & (WC - 1));
     const int NC = 9 * cin;
     int boff[NB];
 #pragma unroll
@@ -163,9 +193,9 @@ __global__ void __launch_bounds__(256) k_down_wgrad(const float* __restrict__ dz
         const int par = (ky != 1 ? 2 : 0) + (kx != 1 ? 1 : 0);
         boff[b] = (ci * 4 + par) * PS + G - (ky == 0 ? wp : 0) - (kx == 0 ? 1 : 0);
     }
-    f32x4 acc[2][NB];
+    f32x4 acc[MA][NB];
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < MA; ++a)
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
@@ -173,9 +203,9 @@ __global__ void __launch_bounds__(256) k_down_wgrad(const float* __restrict__ dz
         const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
         const float* zf = dzp + (size_t)f * cout * PS + G + pb;
         const float* xf = xp + (size_t)f * cin * 4 * PS + pb;
-        float za[2][4], xb[NB][4];
+        float za[MA][4], xb[NB][4];
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
+        for (int a = 0; a < MA; ++a) {
             const float4 v = *reinterpret_cast<const float4*>(zf + (size_t)(co0 + 16 * a + l16) * PS);
             za[a][0] = v.x; za[a][1] = v.y; za[a][2] = v.z; za[a][3] = v.w;
         }
@@ -186,25 +216,32 @@ __global__ void __launch_bounds__(256) k_down_wgrad(const float* __restrict__ dz
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+            for (int a = 0; a < MA; ++a)
 #pragma unroll
                 for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a][s], xb[b][s], acc[a][b], 0, 0, 0);
     }
     float* pw = part + (size_t)(gbase + blockIdx.z) * cout * NC;
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < MA; ++a)
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
 }
 
-__global__ void __launch_bounds__(256) k_down_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
+// partials added in index order, four loads in flight: 64-thread workgroups, so that a 64 x 64 weight spreads over all compute units
+__global__ void __launch_bounds__(64) k_down_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
+    const float* p = part + i;
     double s = 0.0;
-    for (int g = 0; g < G; ++g) s += (double)part[(size_t)g * n + i];
+    int g = 0;
+    for (; g + 3 < G; g += 4) {
+        const float a = p[(size_t)g * n], b = p[(size_t)(g + 1) * n], c = p[(size_t)(g + 2) * n], d = p[(size_t)(g + 3) * n];
+        s += (double)a; s += (double)b; s += (double)c; s += (double)d;
+    }
+    for (; g < G; ++g) s += (double)p[(size_t)g * n];
     dw[i] = (float)s;
 }
 
@@ -299,7 +336,7 @@ void pp_down_destroy(pp_ctx* ctx)
 {
     down_ws* w = (down_ws*)ctx->down;
     if (!w) return;
-    void* q[] = {w->planes, w->wT, w->part, w->pmap};
+    void* q[] = {w->planes, w->pst, w->wT, w->part, w->pmap};
     for (void* x : q)
         if (x) (void)hipFree(x);
     delete w;
@@ -331,10 +368,10 @@ extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win
     down_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: functions of the shapes alone
     const size_t pf_elems = (size_t)pf64;
-    int fc = (int)(DOWN_WS_BUDGET / (pf_elems * sizeof(float)));
+    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
     fc = fc < 1 ? 1 : fc > nb ? nb : fc;
-    const int NBt = cin >= 128 ? 4 : 2;
-    const int NC = 9 * cin, tiles = (NC / (32 * NBt)) * (cout / 64), cpf = (PP + 15) / 16;
+    const int TN = cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_down_wgrad<4, 2> or <3, 4>
+    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
     int Gp = 0;
     for (int f0 = 0; f0 < nb; f0 += fc) {
         int sp, cps;
@@ -342,8 +379,11 @@ extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win
         Gp += sp;
     }
     const int nw = cout * NC;
+    // segments of the streaming passes: over the tight output plane (statistics) and the padded one (dz, the parity planes of x)
+    const int No = ho * wo, S = plane_segs(No), L = seg_len(No, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
     int rc;
     if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, 2 * (size_t)fc * cout * SEG_MAX * 2)) ||
         (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
         (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
         return rc;
@@ -355,15 +395,19 @@ extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win
     for (int f0 = 0; f0 < nb; f0 += fc) {
         const int fn = nb - f0 < fc ? nb - f0 : fc;
         const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
-        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS);
-        hipLaunchKernelGGL(k_down_norm, dim3(cout, fn), dim3(256), 0, stream, z + oo, dy + oo, dzp, cout, ho, wo, wp, G, PP, PS);
+        double* pst2 = ws->pst + (size_t)fc * cout * SEG_MAX * 2;
+        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
+        hipLaunchKernelGGL(k_plane_stats, dim3(cout, fn, S), dim3(256), 0, stream, z + oo, ws->pst, cout, No, L, S);
+        hipLaunchKernelGGL(k_dplane_gstats, dim3(cout, fn, S), dim3(256), 0, stream, z + oo, dy + oo, ws->pst, pst2, cout, No, L, S);
+        hipLaunchKernelGGL(k_down_norm, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, dzp, ws->pst, pst2, cout, ho, wo, wp, G, PP, PS, S,
+                           LP);
         int sp, cps;
         dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / (32 * NBt), cout / 64, sp);
-        if (NBt == 4)
-            hipLaunchKernelGGL(k_down_wgrad<4>, gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        const dim3 gd(NC / TN, cout / 64, sp);
+        if (cin >= 128)
+            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
         else
-            hipLaunchKernelGGL(k_down_wgrad<2>, gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
         gbase += sp;
         if (dx) {
             if (cin == 64)
@@ -374,7 +418,7 @@ extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win
                                    G, PP, PS);
         }
     }
-    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, Gp, nw, dw);
+    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
     PP_HIP(hipGetLastError());
     return 0;
 }

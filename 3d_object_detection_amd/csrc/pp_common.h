@@ -200,6 +200,8 @@ int pp_net_head_gather(pp_ctx* ctx, int nb, pp_head_gather* g);
 int pp_sc1_create(pp_ctx* ctx);
 void pp_sc1_destroy(pp_ctx* ctx);
 int pp_sc1_commit(pp_ctx* ctx);
+int pp_sc1_update(pp_ctx* ctx, const float* w, hipStream_t stream); // the device tensor rpn.block1.0.weight -> the committed image, in place
+const float* pp_first_conv_image(pp_ctx* ctx, size_t* bytes); // the committed weight image (null before a commit): pp_weight_image
 bool pp_sc1_usable(pp_ctx* ctx);
 int pp_sc1_run(pp_ctx* ctx, const int32_t* pmap, const float* feat, float* out, double* stat, size_t stat_fs, int nb, hipStream_t stream);
 int pp_sc1_fetch_list(pp_ctx* ctx, int frame, void* dst, hipStream_t stream);

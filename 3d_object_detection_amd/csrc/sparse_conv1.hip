@@ -238,6 +238,18 @@ __global__ void __launch_bounds__(256) sc1_gather(const Sc1P p)
     }
 }
 
+// the (step, lane, i) map of pp_sc1_commit on the device: image element e = (q 64 + lane) 4 + i of the weight image from the state_dict
+// tensor w [64][64][3][3]
+template <int KC>
+__global__ void __launch_bounds__(256) first_conv_image(const float* __restrict__ w, float* __restrict__ img)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= SC1_W_FLOATS) return;
+    const int i = e & 3, lane = (e >> 2) & 63, q = e >> 8;
+    const int co = 16 * i + (lane & 15), ci = 4 * sc1_c4<KC>(q) + (lane >> 4);
+    img[e] = w[((size_t)co * 64 + ci) * 9 + sc1_tap<KC>(q)];
+}
+
 template <typename T>
 hipError_t sc1_alloc(T** q, size_t count) { return hipMalloc((void**)q, count * sizeof(T) + 256); }
 
@@ -297,6 +309,25 @@ int pp_sc1_commit(pp_ctx* ctx)
     PP_HIP(hipMemcpy(S->w, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
     S->weights = true;
     return 0;
+}
+
+// rpn.block1.0.weight on the device -> the committed image, in its K order, on `stream` (pp_update_rpn_weights).  No-op before the
+// first commit: there is no image to keep in step.
+int pp_sc1_update(pp_ctx* ctx, const float* w, hipStream_t stream)
+{
+    Sc1* S = (Sc1*)ctx->sc1;
+    if (!S || !S->weights) return 0;
+    hipLaunchKernelGGL(S->kc == 8 ? first_conv_image<8> : first_conv_image<4>, dim3(pp_div_up(SC1_W_FLOATS, 256)), dim3(256), 0, stream, w, S->w);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+const float* pp_first_conv_image(pp_ctx* ctx, size_t* bytes)
+{
+    const Sc1* S = (const Sc1*)ctx->sc1;
+    if (!S || !S->weights) return nullptr;
+    *bytes = (size_t)SC1_W_FLOATS * sizeof(float);
+    return S->w;
 }
 
 // The sparse path serves maps whose dense output a 32-bit buffer offset can address (the parked offset sits 2 GB out).

@@ -1,0 +1,55 @@
+// What the streaming passes of block_train.hip and down_train.hip share: how a plane is cut into segments, the fixed-order sums of a
+// workgroup, and the statistics kernel.  One copy, so that both files cut a plane the same way and a shape keeps its bits in both.
+#pragma once
+#include "pp_common.h"
+
+namespace {
+
+constexpr int SEG_ELEMS = 16384; // plane elements one workgroup of a streaming pass takes
+constexpr int SEG_MAX = 16;
+
+// ---- segments of a plane: plane_segs(n) workgroups share n elements, each a run of seg_len (a multiple of 256); one segment up to
+// SEG_ELEMS elements -------------------------------------------------------------------------------------------------------------------
+inline int plane_segs(int64_t n) { const int64_t s = (n + SEG_ELEMS - 1) / SEG_ELEMS; return s < 1 ? 1 : s > SEG_MAX ? SEG_MAX : (int)s; }
+inline int seg_len(int64_t n, int S) { return (int)((((n + S - 1) / S) + 255) & ~(int64_t)255); }
+
+// both sums over the 256 threads' partials (segment t: elements t, t + 256, ...), added in index order 0 .. 255 by every thread: the
+// same bits in every thread
+__device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[2])
+{
+    __syncthreads(); // red may still be read from an earlier call
+    red[threadIdx.x][0] = a; red[threadIdx.x][1] = b;
+    __syncthreads();
+    double sa = 0.0, sb = 0.0;
+    for (int t = 0; t < 256; ++t) { sa += red[t][0]; sb += red[t][1]; }
+    a = sa; b = sb;
+}
+
+// thread t of the workgroup visits lo + t, lo + t + 256, ... below hi in that order, four loads in flight: acc sees the same sequence
+// as the plain loop, so a sum built in it has the same bits
+template <typename LD, typename ACC>
+__device__ __forceinline__ void strided4(int lo, int hi, LD ld, ACC acc)
+{
+    int i = lo + (int)threadIdx.x;
+    for (; i + 768 < hi; i += 1024) {
+        const auto a = ld(i), b = ld(i + 256), c = ld(i + 512), d = ld(i + 768);
+        acc(a); acc(b); acc(c); acc(d);
+    }
+    for (; i < hi; i += 256) acc(ld(i));
+}
+
+// ---- statistics: grid (C, frames, S), sum u and sum u^2 of one segment of a tight [C][N] plane -> pst[plane][segment][2] ------------
+__global__ void __launch_bounds__(256) k_plane_stats(const float* __restrict__ u, double* __restrict__ pst, int C, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double s = 0.0, ss = 0.0;
+    strided4(lo, hi, [&](int i) { return up[i]; }, [&](float f) { const double v = (double)f; s += v; ss += v * v; });
+    block_sum2(s, ss, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = s; pst[(pl * S + blockIdx.z) * 2 + 1] = ss; }
+}
+
+} // namespace

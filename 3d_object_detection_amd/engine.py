@@ -601,6 +601,59 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_down_weight(self.ctx, level, _ptr(t), _stream()), self.ctx, "pp_update_down_weight")
 
+    # ------------------------------------------------------------------ the whole RPN: taps and weight update for all three levels
+    # per level b: the strided convolution, then the unit convolutions in unit order (two Resnet modules at level 0, three below)
+    RPN_UNITS = (3, 5, 5)
+    BLOCK1_KEYS = ("rpn.block1.3.conv_block.2.weight", "rpn.block1.3.conv_block.5.weight", "rpn.block1.4.conv_block.2.weight")
+    BLOCK2_KEYS = tuple(k.replace("block3", "block2") for k in BLOCK3_KEYS)
+    RPN_CONV_KEYS = (DOWN_KEYS[0],) + BLOCK1_KEYS + (DOWN_KEYS[1],) + BLOCK2_KEYS + (DOWN_KEYS[2],) + BLOCK3_KEYS  # execution = state_dict order
+
+    def rpn_conv_shapes(self):
+        """The weight shapes of RPN_CONV_KEYS."""
+        out = []
+        for b, n in enumerate(self.RPN_UNITS):
+            cin, cout = self.DOWN_PAIRS[b]
+            out += [(cout, cin, 3, 3)] + [(cout, cout, 3, 3)] * n
+        return out
+
+    def backbone_train_taps(self, canvas):
+        """pp_backbone_train_taps: backbone_taps(canvas) plus, per level b, the inputs of the block's unit convolutions and the raw
+        output of its strided convolution -> (rpn_out, (x1, x2, x3), (units0 [3,64,H,W], units1 [5,128,H/2,W/2], units2 [5,256,H/4,W/4]),
+        (z1 [1,64,H,W], z2, z3)); units_b[0] = relu(norm(z_b)).  fp32 mode only."""
+        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
+            raise ValueError("backbone_train_taps: expected a contiguous canvas")
+        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
+             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_train_taps: canvas [1,64,gx,gy]")
+        if canvas.device != self.device:
+            raise ValueError(f"backbone_train_taps: canvas is on {canvas.device}, the engine on {self.device}")
+        out = self._t((1, 320, self.H, self.W), torch.float32)
+        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        units = [self._t((n,) + self.neck_shapes(b)[0], torch.float32) for b, n in enumerate(self.RPN_UNITS)]
+        z = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        up = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in units])
+        zp = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in z])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_backbone_train_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]), up, zp,
+                                                       _stream()), self.ctx, "pp_backbone_train_taps")
+        return out, tuple(taps), tuple(units), tuple(z)
+
+    def update_rpn_weights(self, params):
+        """pp_update_rpn_weights: {state_dict name: device tensor} of RPN_CONV_KEYS -> the committed images of all sixteen 3 x 3
+        convolutions and the sparse first convolution's image, in place on the current stream.  fp32 mode only (RuntimeError otherwise,
+        and before the first load_state_dict)."""
+        args = []
+        for k, shape in zip(self.RPN_CONV_KEYS, self.rpn_conv_shapes()):
+            if k not in params:
+                raise KeyError(f"update_rpn_weights: {k} is missing")
+            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
+            t = _chk(t, torch.float32, shape, "update_rpn_weights: " + k)
+            if t.device != self.device:
+                raise ValueError(f"update_rpn_weights: {k} is on {t.device}, the engine on {self.device}")
+            args.append(t)
+        ptrs = (ctypes.c_void_p * 16)(*[t.data_ptr() for t in args])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_rpn_weights(self.ctx, ptrs, _stream()), self.ctx, "pp_update_rpn_weights")
+
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1 + _lib.PP_MAX_CLASSES,), dtype=torch.int32, device=self.device)
@@ -984,6 +1037,16 @@ class Engine:
 
     def executed_ratio(self):
         return float(self.lib.pp_dominant_executed_ratio(self.ctx))
+
+    def weight_image(self, layer):
+        """Test hook (pp_weight_image): the packed weight image of layer 0 .. 19 of the committed plan, or of the sparse first
+        convolution (layer = -1), as a uint8 tensor."""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.lib.pp_weight_image(self.ctx, int(layer), None, 0, ctypes.byref(n), None), self.ctx, "pp_weight_image")
+        out = self._t((n.value,), torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_weight_image(self.ctx, int(layer), _ptr(out), n.value, ctypes.byref(n), _stream()), self.ctx, "pp_weight_image")
+        return out
 
     def layer_tilings(self):
         """[{kind, cin, cout, stride, up, level, wino, tiling}] in execution order (pp_layer_tilings)."""

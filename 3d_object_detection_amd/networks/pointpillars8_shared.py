@@ -9,8 +9,15 @@ the five convolutions of the deepest Resnet block (BLOCK3_KEYS, unit order): the
 backward continues from the third upsampler's dx through five pp_unit_backward calls (csrc/block_train.hip).  train(scope="stage3")
 adds block 3's stride-2 convolution rpn.block3.0.weight: the forward runs pp_backbone_stage_taps, which also hands out that conv's
 pre-norm output, and the backward ends in pp_down_backward (csrc/down_train.hip).  Everything in front of it (PFN, scatter, blocks 1
-and 2 with their stride-2 convolutions) is FROZEN: the gradient with respect to block 3's input is computed by pp_down_backward on
-request but nothing consumes it yet."""
+and 2 with their stride-2 convolutions) is FROZEN under those scopes.
+
+Training the whole RPN: train(scope="rpn") trains all sixteen 3 x 3 convolutions, the three upsamplers and the head (RPN_KEYS, the
+reference's state_dict order, 25 tensors).  The forward runs pp_backbone_train_taps, which hands out every block's unit inputs and
+every strided convolution's pre-norm output; the backward (_RpnFunction) walks RPN_TABLE from block 3 to block 1: each block's
+pp_unit_backward chain, its pp_down_backward with the gradient of the stage input, to which the upsampler's dx of the level above is
+added.  The gradient of block 3's input that pp_down_backward computes is consumed by block 2 here.  optimizer.step() is followed by
+pp_update_rpn_weights, which also rewrites the sparse first convolution's image.  Only PFN and scatter stay frozen; rpn_train()
+returns the gradient with respect to the canvases when they require grad, the starting point of a PFN backward."""
 import time
 import types
 
@@ -26,6 +33,13 @@ NECK_KEYS = ("rpn.deconv1.0.weight", "rpn.deconv2.0.weight", "rpn.deconv3.0.weig
 # block 3 behind its stride-2 head, h -> r3 = h + U_b(U_a(h)), r4 = r3 + U_d(U_c(r3)), x3 = r4 + U_e(r4): the weights of units a..e
 BLOCK3_KEYS = Engine.BLOCK3_KEYS
 STAGE3_KEY = Engine.DOWN_KEYS[2]  # block 3's stride-2 convolution, in front of unit a
+RPN_CONV_KEYS = Engine.RPN_CONV_KEYS
+# the backward of the whole RPN as a table, one row per level: (level, convolutions per Resnet module in forward order).  A module of
+# two convolutions is r -> r + U_b(U_a(r)), one of a single convolution r -> r + U_a(r); the level's units count the convolutions.
+RPN_TABLE = ((0, (2, 1)), (1, (2, 2, 1)), (2, (2, 2, 1)))
+# the reference's state_dict order of everything behind the canvas: per block its convolutions, then its upsampler; then the head
+RPN_KEYS = tuple(k for b in range(3) for k in RPN_CONV_KEYS[(0, 4, 10)[b]:(4, 10, 16)[b]] + (NECK_KEYS[b],)) + HEAD_KEYS
+_RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in BLOCK3_KEYS)  # what the narrower scopes never train
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -158,12 +172,65 @@ class _StageFunction(torch.autograd.Function):
         return (None, None, dw0) + tuple(dwb) + tuple(dwn)
 
 
+def rpn_block_backward(eng, modules, units, weights, g):
+    """The backward of one block's Resnet modules (a row of RPN_TABLE): units and weights in unit order, g = dL/d(block output) ->
+    (dw per unit, dL/d(block input h))."""
+    dws = [None] * len(units)
+    i = len(units)
+    for n in reversed(modules):
+        i -= n
+        if n == 2:
+            dws[i + 1], gm = eng.unit_backward(units[i + 1], weights[i + 1], g)
+            dws[i], g = eng.unit_backward(units[i], weights[i], gm, dskip=g)
+        else:
+            dws[i], g = eng.unit_backward(units[i], weights[i], g, dskip=g)
+    return dws, g
+
+
+class _RpnFunction(torch.autograd.Function):
+    """RPN.forward as pp_backbone_train_taps per frame, stacked; its backward is pp_neck_backward for the three branches, each with dx,
+    and then, from level 2 down to level 0 along RPN_TABLE, the block's unit chain and its strided stage (pp_down_backward); the stage's
+    dx plus the upsampler's dx of the level above (in this order: upsampler + stage) is the gradient of that level's block output.
+    weights: the sixteen convolutions in RPN_CONV_KEYS order, then the three upsamplers.  The canvases get level 0's dx when they
+    require grad."""
+
+    @staticmethod
+    def forward(ctx, eng, x, *weights):
+        ctx.eng = eng
+        outs = [eng.backbone_train_taps(c) for c in x]
+        y = torch.cat([o[0] for o in outs])
+        taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
+        units = [torch.stack([o[2][b][k] for o in outs]) for b, mods in RPN_TABLE for k in range(sum(mods))]
+        zs = [torch.cat([o[3][b] for o in outs]) for b in range(3)]
+        ctx.save_for_backward(x, y, *taps, *units, *zs, *weights)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, *rest = ctx.saved_tensors
+        taps, units, zs, wc, wn = rest[:3], rest[3:16], rest[16:19], rest[19:35], rest[35:38]
+        eng, gy = ctx.eng, gy.contiguous()
+        need = ctx.needs_input_grad
+        dwn, dxn = zip(*[eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=True) for b in range(3)])
+        dwc = [None] * 16
+        g = None
+        for b, mods in reversed(RPN_TABLE):
+            n, w0 = sum(mods), (0, 4, 10)[b]  # the level's strided convolution in RPN_CONV_KEYS; its units follow
+            u0 = w0 - b
+            g = dxn[b] if g is None else dxn[b] + g
+            dwc[w0 + 1:w0 + 1 + n], gh = rpn_block_backward(eng, mods, units[u0:u0 + n], wc[w0 + 1:w0 + 1 + n], g)
+            dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=b > 0 or need[1])
+        grads = [d if need[2 + i] else None for i, d in enumerate(list(dwc) + list(dwn))]
+        return (None, g if need[1] else None) + tuple(grads)
+
+
 class PointPillars:
     _norm = "instance"
     # read-only defaults for an object assembled without __init__ (no engine: the key-order tests); __init__ and load_state_dict
     # give every object its own
     _block, _block_uploaded, _block_trained = types.MappingProxyType({}), None, False
     _down, _down_uploaded, _down_trained = types.MappingProxyType({}), None, False
+    _rpn, _rpn_uploaded, _rpn_trained = types.MappingProxyType({}), None, False
 
     def __init__(self, config):
         self.device = config['device']
@@ -176,7 +243,11 @@ class PointPillars:
         self.training = False
         self._trained = False        # the head has been stepped since load_state_dict
         self._scope = "head"         # train(scope=...): "head", "neck" (+ the three upsamplers), "block3" (+ block 3's five unit
-                                     # convolutions) or "stage3" (+ block 3's stride-2 convolution)
+                                     # convolutions), "stage3" (+ block 3's stride-2 convolution) or "rpn" (+ blocks 1 and 2 with
+                                     # their stride-2 convolutions: the whole RPN)
+        self._rpn = {}               # the ten convolutions of blocks 1 and 2 as device Parameters
+        self._rpn_uploaded = None
+        self._rpn_trained = False
         self._down = {}              # block 3's stride-2 weight as a device Parameter
         self._down_uploaded = None
         self._down_trained = False
@@ -202,25 +273,33 @@ class PointPillars:
         """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
         trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
         block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
-        frozen: it has no backward.  eval() / train(False) restores the inference behaviour."""
-        if scope not in ("head", "neck", "block3", "stage3"):
-            raise ValueError(f"train: scope must be 'head', 'neck', 'block3' or 'stage3', got {scope!r}")
+        frozen: it has no backward.  scope="rpn" trains the whole RPN (RPN_KEYS: blocks 1 and 2 with their stride-2 convolutions as
+        well); only PFN and scatter stay frozen.  eval() / train(False) restores the inference behaviour."""
+        if scope not in ("head", "neck", "block3", "stage3", "rpn"):
+            raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3' or 'rpn', got {scope!r}")
         if mode and scope != "head" and (self._norm != "instance" or len(self._neck) != 3 or
-                                         (scope in ("block3", "stage3") and len(self._block) != 5) or (scope == "stage3" and len(self._down) != 1)):
+                                         (scope in ("block3", "stage3", "rpn") and len(self._block) != 5) or
+                                         (scope in ("stage3", "rpn") and len(self._down) != 1) or
+                                         (scope == "rpn" and len(self._rpn) != len(_RPN_EXTRA_KEYS))):
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only")
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
         for p in self._params.values():
             p.requires_grad_(self.training)
         for p in self._neck.values():
-            p.requires_grad_(self.training and self._scope in ("neck", "block3", "stage3"))
+            p.requires_grad_(self.training and self._scope in ("neck", "block3", "stage3", "rpn"))
         for p in self._block.values():
-            p.requires_grad_(self.training and self._scope in ("block3", "stage3"))
+            p.requires_grad_(self.training and self._scope in ("block3", "stage3", "rpn"))
         for p in self._down.values():
-            p.requires_grad_(self.training and self._scope == "stage3")
+            p.requires_grad_(self.training and self._scope in ("stage3", "rpn"))
+        for p in self._rpn.values():
+            p.requires_grad_(self.training and self._scope == "rpn")
         return self
 
     def _trainable(self):
+        if self._scope == "rpn":
+            every = {**self._rpn, **self._down, **self._block, **self._neck, **self._params}
+            return {k: every[k] for k in RPN_KEYS if k in every}
         if self._scope == "stage3":
             return {**self._down, **self._block, **self._neck, **self._params}
         if self._scope == "block3":
@@ -230,14 +309,15 @@ class PointPillars:
     def named_parameters(self):
         """The trainable tensors on the device: heads.conv_{cls,box,dir}.{weight,bias}, behind rpn.deconv{1,2,3}.0.weight under
         train(scope="neck"), behind BLOCK3_KEYS (unit order) as well under train(scope="block3"), and behind rpn.block3.0.weight
-        under train(scope="stage3").  Everything before them is frozen."""
+        under train(scope="stage3"); under train(scope="rpn") the 25 tensors of RPN_KEYS in the reference's state_dict order.  Everything
+        before them is frozen."""
         return iter(self._trainable().items())
 
     def parameters(self):
         return iter(self._trainable().values())
 
     def zero_grad(self, set_to_none=True):
-        for p in list(self._down.values()) + list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
+        for p in list(self._rpn.values()) + list(self._down.values()) + list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
             if set_to_none:
                 p.grad = None
             elif p.grad is not None:
@@ -259,12 +339,24 @@ class PointPillars:
     def _down_moved(self):
         return self._down_uploaded is not None and tuple(p._version for p in self._down.values()) != self._down_uploaded
 
+    def _rpn_moved(self):
+        return self._rpn_uploaded is not None and tuple(p._version for p in self._rpn.values()) != self._rpn_uploaded
+
     def _sync_neck(self):
-        """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone."""
+        """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone; when
+        a convolution of blocks 1 and 2 moved, all sixteen go up in one pp_update_rpn_weights."""
         if self._neck_moved():
             self._neck_trained = True
             self._eng.update_neck_weights(self._neck)
             self._neck_uploaded = tuple(p._version for p in self._neck.values())
+        if self._rpn_moved():
+            self._rpn_trained = True
+            self._block_trained = self._block_trained or self._block_moved()
+            self._down_trained = self._down_trained or self._down_moved()
+            self._eng.update_rpn_weights({**self._rpn, **self._down, **self._block})
+            self._rpn_uploaded = tuple(p._version for p in self._rpn.values())
+            self._block_uploaded = tuple(p._version for p in self._block.values())
+            self._down_uploaded = tuple(p._version for p in self._down.values())
         if self._block_moved():
             self._block_trained = True
             self._eng.update_block_weights(self._block)
@@ -295,15 +387,20 @@ class PointPillars:
             self._block_uploaded = ()
         if self._down_trained or self._down_moved():
             self._down_uploaded = ()
+        if self._rpn_trained or self._rpn_moved():
+            self._rpn_uploaded = ()
         return self
 
     def _head_moved(self):
         return self._uploaded is not None and tuple(p._version for p in self._params.values()) != self._uploaded
 
     def state_dict(self):
-        """The loaded tensors; the head's six, the three upsampler weights, block 3's five and its stride-2 weight with their
-        CURRENT values (after optimizer steps)."""
+        """The loaded tensors; the head's six, the three upsampler weights and all sixteen 3 x 3 convolutions of the RPN (blocks 1, 2
+        and 3 with their stride-2 weights, RPN_CONV_KEYS) with their CURRENT values (after optimizer steps)."""
         sd = dict(self._sd)
+        if self._rpn_moved() or self._rpn_trained:
+            for k, p in self._rpn.items():
+                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
         if self._down_moved() or self._down_trained:
             for k, p in self._down.items():
                 sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
@@ -325,10 +422,14 @@ class PointPillars:
                                               requires_grad=self.training) for k in HEAD_KEYS if k in self._sd}
         self._uploaded = tuple(p._version for p in self._params.values())
         self._trained = False
-        neck = self.training and self._scope in ("neck", "block3", "stage3")
-        block = self.training and self._scope in ("block3", "stage3")
+        neck = self.training and self._scope in ("neck", "block3", "stage3", "rpn")
+        block = self.training and self._scope in ("block3", "stage3", "rpn")
+        self._rpn = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
+                                           requires_grad=self.training and self._scope == "rpn") for k in _RPN_EXTRA_KEYS if k in self._sd}
+        self._rpn_uploaded = tuple(p._version for p in self._rpn.values())
+        self._rpn_trained = False
         self._down = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                            requires_grad=self.training and self._scope == "stage3") for k in (STAGE3_KEY,) if k in self._sd}
+                                            requires_grad=self.training and self._scope in ("stage3", "rpn")) for k in (STAGE3_KEY,) if k in self._sd}
         self._down_uploaded = tuple(p._version for p in self._down.values())
         self._down_trained = False
         self._block = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
@@ -407,29 +508,35 @@ class PointPillars:
         return self._eng.backbone(x.contiguous())
 
     def _neck_grad(self):
-        return self.training and self._scope in ("neck", "block3", "stage3") and torch.is_grad_enabled() and \
-            any(p.requires_grad for p in list(self._neck.values()) + list(self._block.values()) + list(self._down.values()))
+        return self.training and self._scope in ("neck", "block3", "stage3", "rpn") and torch.is_grad_enabled() and \
+            any(p.requires_grad for p in list(self._neck.values()) + list(self._block.values()) + list(self._down.values()) +
+                list(self._rpn.values()))
 
     def rpn_train(self, x):
         """RPN.forward on canvases x [B,64,gx,gy], 1 <= B <= max_batch, one backbone pass per frame; same values as rpn() bit for
         bit.  Differentiable with respect to the three upsampler weights when they require grad (train(scope="neck")) and to block
-        3's five unit weights (train(scope="block3")) and its stride-2 weight (train(scope="stage3")); gradients are fp32 and need
-        the fp32 precision mode."""
+        3's five unit weights (train(scope="block3")) and its stride-2 weight (train(scope="stage3")); under train(scope="rpn") to all
+        sixteen convolutions, and then also to x itself when it requires grad (the level-0 dx: where a PFN backward would start).
+        Gradients are fp32 and need the fp32 precision mode."""
         eng = self._eng
         gx, gy = int(eng.grid_size[0]), int(eng.grid_size[1])
         if not isinstance(x, torch.Tensor) or x.numel() == 0 or x.numel() % (64 * gx * gy):
             raise ValueError(f"rpn_train: expected canvases [B,64,{gx},{gy}]")
-        x = x.contiguous().reshape(-1, 64, gx, gy)
+        x = x.contiguous().reshape(-1, 64, gx, gy)  # a view: a canvas that requires grad stays in the graph
         if not 1 <= x.shape[0] <= eng.max_batch:
             raise ValueError(f"rpn_train: {x.shape[0]} frames in the batch, max_batch is {eng.max_batch}")
         self._sync_neck()
         block = any(p.requires_grad for p in self._block.values())
         stage = any(p.requires_grad for p in self._down.values())
-        if not (torch.is_grad_enabled() and (stage or block or any(p.requires_grad for p in self._neck.values()))):
+        whole = any(p.requires_grad for p in self._rpn.values())
+        if not (torch.is_grad_enabled() and (whole or stage or block or any(p.requires_grad for p in self._neck.values()))):
             return torch.cat([eng.backbone(c) for c in x])
         if eng.effective_precision() != "fp32":
             raise RuntimeError(f"neck training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
                                "(gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place); call float()")
+        if whole:
+            every = {**self._rpn, **self._down, **self._block}
+            return _RpnFunction.apply(eng, x, *[every[k] for k in RPN_CONV_KEYS], *[self._neck[k] for k in NECK_KEYS])
         if stage:
             return _StageFunction.apply(eng, list(x), self._down[STAGE3_KEY], *[self._block[k] for k in BLOCK3_KEYS],
                                         *[self._neck[k] for k in NECK_KEYS])

@@ -328,8 +328,8 @@ int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const 
  * qx - kx + 1] and Gr = da [a > 0]; the mask is that of the a this call materialises, so dw and du see the same activation.  dskip may
  * be NULL (nothing is added; otherwise it is one fp32 add behind the rounded norm backward: the gradient of a residual connection
  * around the unit).  du NULL: the dgrad product and the norm backward are not run.  Both products are fp32-input MFMA GEMMs over
- * zero-haloed copies of a and dy in a workspace (allocated on first use, at most 256 MB: larger batches run in frame chunks; a map
- * whose single frame exceeds it is PP_E_ARG).  dw is tiled over workgroups and its K range (frames x positions) split into a fixed
+ * zero-haloed copies of a and dy in a workspace (allocated on first use, at most 1 GB: larger batches run in frame chunks; a map
+ * whose single frame takes more than 256 MB of it is PP_E_ARG).  dw is tiled over workgroups and its K range (frames x positions) split into a fixed
  * number of ranges whose partials are summed in index order in double, so dw depends on nb within fp32 summation error; a frame's du
  * does not depend on nb at all.  The dgrad sums its K = 9 C terms in blocks of 64 from zero and adds the block sums in a fixed order.
  * The workspace belongs to the context, so "stateless" is about values, not about concurrency: calls on one context must be issued in
@@ -346,7 +346,7 @@ int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const flo
 int pp_backbone_block_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* units, void* stream);
 /* After an optimizer step: the five DEVICE tensors f32[256][256][3][3] of block 3 in unit order a..e (state_dict layout) -> the packed
  * weight images of those five layers of the committed launch plan, rewritten in place on `stream` (no host copy, no re-tuning).  block
- * must be 2 (block 3) and n 5: PP_E_ARG for the other blocks (they have no backward yet, and level 0 carries the tile-skipping path).
+ * must be 2 (block 3) and n 5: PP_E_ARG for the other blocks, which pp_update_rpn_weights rewrites with all the others.
  * The Winograd tilings' images hold U = G g G^T, which a device kernel evaluates from g in fp64 in the host packer's own expression
  * order and rounds once, so the images equal those of a fresh commit of the same values bit for bit; the direct tilings' images are
  * permuted copies.  The strip tilings share the main image.  pp_backbone*, pp_infer_frame and pp_infer_batch all see the new weights.
@@ -368,8 +368,8 @@ int pp_update_block_weights(pp_ctx* ctx, int block, const float* const* w, int n
  * dx[ci, iy, ix] = sum_{co, ky, kx} w[co][ci][ky][kx] dz[co, (iy + 1 - ky) / 2, (ix + 1 - kx) / 2] over the taps whose quotients are whole
  * and in range, f32[nb][Cin][Hin][Win], fully written.  dx NULL: the dgrad product is not run, and dw is the same bits.  Both products
  * are fp32-input MFMA GEMMs over zero-haloed half-resolution copies of dz and of the four row / column parity planes of x in a workspace
- * of its own (allocated on first use, at most 256 MB: larger batches run in frame chunks; a map whose single frame exceeds it is
- * PP_E_ARG).  Deterministic: no atomics; dw's K range (frames x positions) is split by the shapes alone and the partials are summed in
+ * of its own (allocated on first use, at most 1 GB: larger batches run in frame chunks; a map whose single frame takes more than 256 MB
+ * of it is PP_E_ARG).  Deterministic: no atomics; dw's K range (frames x positions) is split by the shapes alone and the partials are summed in
  * index order in double, so dw depends on nb within fp32 summation error; a frame's dx does not depend on nb at all.  The dgrad sums its
  * K = Cout x {1, 2, 2, 4} taps per output parity class in blocks of 64 from zero and adds the block sums in a fixed order.  Calls on one
  * context must be issued in order on one stream, as for pp_unit_backward.
@@ -383,11 +383,31 @@ int pp_backbone_stage_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, flo
                            void* stream);
 /* After an optimizer step: the DEVICE tensor f32[256][128][3][3] rpn.block3.0.weight (state_dict layout) -> the packed image of the
  * strided convolution of `level` of the committed launch plan, rewritten in place on `stream`; the image equals that of a fresh commit
- * of the same values bit for bit (a direct tiling: a permuted copy).  level must be 2: PP_E_ARG for level 0 (it carries the sparse
- * first-conv packing) and level 1 (nothing trains it yet).  The first call after a commit reads the image's layout back once
+ * of the same values bit for bit (a direct tiling: a permuted copy).  level must be 2: PP_E_ARG for levels 0 and 1, which are
+ * rewritten by pp_update_rpn_weights (level 0 also carries the sparse first-conv packing).  The first call after a commit reads the image's layout back once
  * (synchronous).  The host copies of pp_load_weights are NOT changed.  fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and
  * before the first commit. */
 int pp_update_down_weight(pp_ctx* ctx, int level, const float* w, void* stream);
+
+/* ---- training the whole RPN: taps and the weight update for all three levels (conv.hip, block_train.hip, sparse_conv1.hip) ----
+ * pp_backbone_train_taps: pp_backbone_stage_taps for every level b = 0, 1, 2 (C_b = 64, 128, 256 on the (H >> b) x (W >> b) map).
+ * units[b] f32[n_b][C_b][H>>b][W>>b], n_b = 3, 5, 5: the inputs of the block's unit convolutions in unit order (level 0: h, m = U_a(h),
+ * r = h + U_b(m); x1 = r + U_c(r); levels 1 and 2 as pp_backbone_block_taps describes block 3).  z[b] f32[C_b][H>>b][W>>b]: the raw
+ * (pre-norm) output of the level's strided convolution, units[b][0] = relu(norm(z[b])).  units and z are HOST arrays of three device
+ * pointers.  Every tensor leaves through a copy hook behind the launch that produces it; the hooks are armed for this pass only, and a
+ * pass with no hook armed is bit for bit what it was.  rpn_out, x1, x2 and x3 match pp_backbone bit for bit.  One frame per call; fp32
+ * mode only, as pp_backbone_taps. */
+int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* const* units,
+                           float* const* z, void* stream);
+/* After an optimizer step: the sixteen DEVICE tensors of the RPN's 3 x 3 convolutions in execution (= state_dict) order -- per level
+ * rpn.block<b+1>.0.weight f32[C_b][C_{b-1}][3][3], then the level's 3 | 5 | 5 unit convolutions f32[C_b][C_b][3][3] -- -> the packed
+ * images of those layers of the committed launch plan, rewritten in place on `stream`, whatever tiling family each layer runs (as
+ * pp_update_block_weights does for block 3).  Level 0's strided weight also rewrites the image of the sparse first convolution, in the
+ * K order of the committed dense tiling, so the fused inference path sees the same rpn.block1.0.weight; tile skipping holds nothing
+ * derived from the weights and stays active.  Every image equals that of a fresh commit of the same values bit for bit.  The first call
+ * after a commit reads the images' layouts back once (synchronous); later calls do not synchronise.  The host copies of pp_load_weights
+ * are NOT changed.  fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and before the first commit. */
+int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w /* 16 */, void* stream);
 
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
@@ -496,6 +516,10 @@ int pp_stage_profile_end(pp_ctx* ctx, double* ms_h);
  * "<index> kind=<0 conv3x3|1 deconv|2 head> cin= cout= stride= up= level= wino=<kernel family: 0 direct|1,4,6 Winograd|3 1x1 GEMM|5 16-bit conv> tiling=<name>".
  * Returns the text length (buf may be NULL to query). */
 int pp_layer_tilings(pp_ctx* ctx, char* buf_h, int cap);
+/* Test / inspection hook: the packed weight image of layer `layer` of the committed plan (0 .. 19 in pp_layer_tilings order), or the
+ * sparse first convolution's own image of rpn.block1.0.weight (layer = -1), copied to DEVICE memory dst (cap bytes) on `stream`.  The
+ * image's size comes back through bytes_h; dst may be NULL to query it.  What the in-place weight updates are compared by. */
+int pp_weight_image(pp_ctx* ctx, int layer, void* dst, size_t cap, size_t* bytes_h, void* stream);
 /* The autotuner's table (process-wide) as text, "layer signature<TAB>tiling" per line.  Rank 0 of a multi-GPU job
  * tunes, exports and broadcasts it; the other ranks import it BEFORE pp_commit_weights so all ranks run identical
  * kernels.  pp_tune_export returns the text length (buf may be NULL to query), pp_tune_import the lines taken. */
