@@ -136,10 +136,26 @@ extern "C" pp_ctx* pp_create(int device, const pp_config* cfg)
         return nullptr;
     }
     if (cfg->max_voxels <= 0 || cfg->max_num_points <= 0 || cfg->max_points <= 0 || cfg->num_classes <= 0 ||
-        cfg->num_classes > PP_MAX_CLASSES || cfg->nms_pre_max <= 0 || cfg->nms_pre_max > 4096 ||
-        cfg->nms_post_max <= 0 || cfg->nms_post_max > cfg->nms_pre_max || cfg->nms_post_max > 1024 || cfg->max_batch < 0 ||
-        cfg->max_batch > 64) {
+        cfg->num_classes > PP_MAX_CLASSES || cfg->max_batch < 0 || cfg->max_batch > 64) {
         pp_fail(nullptr, PP_E_ARG, "pp_create: size out of range");
+        return nullptr;
+    }
+    // the post-processing's operating point: every message names its field (the short list, the NMS mask and nms_reduce's LDS
+    // keep list are sized by these limits)
+    if (cfg->nms_pre_max <= 0 || cfg->nms_pre_max > 4096) {
+        pp_fail(nullptr, PP_E_ARG, "pp_create: nms_pre_max must be in [1, 4096]");
+        return nullptr;
+    }
+    if (cfg->nms_post_max <= 0 || cfg->nms_post_max > 1024) {
+        pp_fail(nullptr, PP_E_ARG, "pp_create: nms_post_max must be in [1, 1024]");
+        return nullptr;
+    }
+    if (cfg->nms_post_max > cfg->nms_pre_max) {
+        pp_fail(nullptr, PP_E_ARG, "pp_create: nms_post_max must not exceed nms_pre_max");
+        return nullptr;
+    }
+    if (!(cfg->score_threshold > 0.f && cfg->score_threshold < 1.f)) {
+        pp_fail(nullptr, PP_E_ARG, "pp_create: score_threshold must be in (0,1)");
         return nullptr;
     }
     pp_ctx* ctx = new pp_ctx();

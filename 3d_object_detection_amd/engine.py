@@ -145,7 +145,10 @@ class Engine:
 
     PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2, "fp16": 3, "fp16s": 4}
 
-    def __init__(self, config, device_index=0, norm="instance", max_points=None, max_batch=None, precision="fp32"):
+    def __init__(self, config, device_index=0, norm="instance", max_points=None, max_batch=None, precision="fp32",
+                 nms_pre_max=1000, nms_post_max=300, nms_iou_threshold=0.1, score_threshold=0.05):
+        """nms_pre_max (<= 4096) / nms_post_max (<= 1024, <= nms_pre_max) / nms_iou_threshold / score_threshold (in (0, 1)): the
+        post-processing's operating point; the defaults are the reference's (inference.py:13-19).  pp_create rejects values out of range."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("3d_object_detection_amd needs a ROCm GPU: the HIP path has no CPU fallback")
@@ -183,8 +186,8 @@ class Engine:
         for i, v in enumerate(config["center_limit"]):
             c.center_limit[i] = float(v)
         c.norm_kind = 0 if norm == "instance" else 1
-        c.nms_pre_max, c.nms_post_max = 1000, 300          # inference.py:13-14
-        c.nms_iou_threshold, c.score_threshold = 0.1, 0.05  # inference.py:15,19
+        c.nms_pre_max, c.nms_post_max = int(nms_pre_max), int(nms_post_max)
+        c.nms_iou_threshold, c.score_threshold = float(nms_iou_threshold), float(score_threshold)
         c.max_batch = int(max_batch or config.get("max_batch", 1))
         self.max_batch = c.max_batch
         self.cfg = c

@@ -532,7 +532,7 @@ def sigmoid_f32(x):
 
 
 def postprocess(cls_preds, box_preds, dir_preds, anchors_mask, anchors, class_masks, center_limit,
-                nms_mode="aabb", detail=False, nms_fn=None):
+                nms_mode="aabb", detail=False, nms_fn=None, pre_max=None, post_max=None, iou_thr=None, score_thr=None):
     """Per class: anchor mask -> sigmoid -> score >= 0.05 -> top-1000 -> decode -> standup
     AABB -> NMS(0.1) -> first 300 -> direction flip -> range mask (quirk: dims vs upper
     limits, :107-109) -> limit_period(2*pi).  Returns (det f32[k,9] rows
@@ -541,7 +541,12 @@ def postprocess(cls_preds, box_preds, dir_preds, anchors_mask, anchors, class_ma
     anchors were candidates / kept, so a differing detection can be traced to the decision that flipped):
     dict(idx top-k anchor ids in score order, score, dets NMS input, keep positions into idx (all NMS
     survivors, before the 300 cut), final anchor id per output row).  nms_fn(dets, thr) overrides the NMS
-    implementation (the C oracle for large candidate sets)."""
+    implementation (the C oracle for large candidate sets).  pre_max / post_max / iou_thr / score_thr replace the four
+    module constants (None = the constant: the reference's operating point)."""
+    pre_max = NMS_PRE_MAX if pre_max is None else int(pre_max)
+    post_max = NMS_POST_MAX if post_max is None else int(post_max)
+    iou_thr = NMS_IOU_THR if iou_thr is None else iou_thr
+    score_thr = SCORE_THR if score_thr is None else score_thr
     info = []
     cls_preds = np.asarray(cls_preds, dtype=F32).reshape(-1)
     box_preds = np.asarray(box_preds, dtype=F32).reshape(-1, 7)
@@ -552,7 +557,7 @@ def postprocess(cls_preds, box_preds, dir_preds, anchors_mask, anchors, class_ma
     for ci, (name, (s, e)) in enumerate(class_masks.items()):
         idx = np.nonzero(anchors_mask[s:e])[0] + s
         sc = sigmoid_f32(cls_preds[idx])
-        keep = sc >= F32(SCORE_THR)
+        keep = sc >= F32(score_thr)
         idx, sc = idx[keep], sc[keep]
         if idx.size == 0:
             counts.append(0)
@@ -560,18 +565,18 @@ def postprocess(cls_preds, box_preds, dir_preds, anchors_mask, anchors, class_ma
             continue
         n_cand = int(idx.size)
         # topk: score descending, ties by lower anchor index (torch.topk leaves ties unspecified)
-        o = np.lexsort((idx, -sc.astype(np.float64)))[:NMS_PRE_MAX]
+        o = np.lexsort((idx, -sc.astype(np.float64)))[:pre_max]
         idx, sc = idx[o], sc[o]
         dirl = dir_preds[idx, 1] > dir_preds[idx, 0]  # torch.max(dim=-1)[1]: first max wins on ties
         boxes = box_decode(box_preds[idx], anchors[idx])
         if nms_mode == "aabb":
             corners = center_to_corner_box2d(boxes[:, :2], boxes[:, 3:5], boxes[:, 6])
             dets = np.concatenate([corner_to_standup_nd(corners), sc[:, None]], axis=1)
-            keep_all = (nms_fn or nms_aabb)(dets, NMS_IOU_THR)
+            keep_all = (nms_fn or nms_aabb)(dets, iou_thr)
         else:
             dets = np.concatenate([boxes[:, [0, 1, 3, 4, 6]], sc[:, None]], axis=1)
-            keep_all = (nms_fn or nms_rotated)(dets, NMS_IOU_THR)
-        sel = np.asarray(keep_all[:NMS_POST_MAX], dtype=np.int64)
+            keep_all = (nms_fn or nms_rotated)(dets, iou_thr)
+        sel = np.asarray(keep_all[:post_max], dtype=np.int64)
         b = boxes[sel].copy()
         s_sel = sc[sel]
         opp = (b[:, 6] > 0) ^ dirl[sel]
