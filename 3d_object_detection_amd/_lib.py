@@ -87,6 +87,10 @@ PROTOTYPES = {
     "pp_update_down_weight": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
     "pp_backbone_train_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_rpn_weights": (ctypes.c_int, [c_p, c_p, c_p]),
+    "pp_pfn_train_forward": (ctypes.c_int, [c_p] * 12),
+    "pp_scatter_backward": (ctypes.c_int, [c_p] * 6),
+    "pp_pfn_backward": (ctypes.c_int, [c_p] * 15),
+    "pp_update_pfn_weights": (ctypes.c_int, [c_p] * 7),
     "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),

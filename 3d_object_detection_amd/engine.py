@@ -657,6 +657,103 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_rpn_weights(self.ctx, ptrs, _stream()), self.ctx, "pp_update_rpn_weights")
 
+    # ------------------------------------------------------------------ PFN training (pfn_train.hip)
+    PFN_KEYS = ("pillar_point_net.pfn_layers.0.weight", "pillar_point_net.pfn_layers.1.weight", "pillar_point_net.pfn_layers.1.bias")
+    PFN_STAT_KEYS = ("pillar_point_net.pfn_layers.1.running_mean", "pillar_point_net.pfn_layers.1.running_var")
+    PFN_STATS = 218  # doubles: mean[64], var[64], s[9], M[9][9]
+
+    def _chk_batch_pillars(self, voxels, coors, npts, num, what):
+        """The pillars of a whole batch: up to max_batch x max_voxels rows."""
+        _chk(coors, torch.int32, (None, 3), what + ": coors")
+        _chk(num, torch.int32, (1,), what + ": num")
+        if coors.shape[0] > self.max_batch * self.max_voxels:
+            raise ValueError(f"{what}: {coors.shape[0]} pillars exceed max_batch x max_voxels = {self.max_batch * self.max_voxels}")
+        _chk(voxels, torch.float32, (coors.shape[0], self.T, self.F), what + ": voxels")
+        _chk(npts, torch.int32, (coors.shape[0],), what + ": num_points_per_voxel")
+        for t, name in ((voxels, "voxels"), (coors, "coors"), (npts, "num_points_per_voxel"), (num, "num")):
+            if t.device != self.device:
+                raise ValueError(f"{what}: {name} is on {t.device}, the engine on {self.device}")
+
+    def _chk_pfn_params(self, w, gamma, beta, what):
+        w = w.detach() if isinstance(w, torch.Tensor) else w
+        if isinstance(w, torch.Tensor) and w.dim() == 3 and w.shape[2] == 1 and w.is_contiguous():
+            w = w.reshape(64, 9)
+        out = [_chk(w, torch.float32, (64, 9), what + ": w as [64,9,1]")]
+        for t, name in ((gamma, "gamma"), (beta, "beta")):
+            if t is not None:
+                out.append(_chk(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32, (64,), f"{what}: {name}"))
+        for t in out:
+            if t.device != self.device:
+                raise ValueError(f"{what}: a parameter is on {t.device}, the engine on {self.device}")
+        return out
+
+    def pfn_train_forward(self, voxels, coors, npts, num, w, gamma, beta):
+        """pp_pfn_train_forward: PointNet in train mode on the pillars of a whole batch (rows of all frames; BatchNorm1d normalises
+        with their statistics) with the weights of the call -> (feat f32[P,64], arg u8[P,64]: the first slot that attains the maximum,
+        stats f64[218] = batch mean[64], biased var[64], s[9], M[9,9]).  Reads num back (one synchronisation); stateless."""
+        self._chk_batch_pillars(voxels, coors, npts, num, "pfn_train_forward")
+        w, gamma, beta = self._chk_pfn_params(w, gamma, beta, "pfn_train_forward")
+        rows = max(int(voxels.shape[0]), 1)
+        feat, arg, stats = self._t((rows, 64), torch.float32), self._t((rows, 64), torch.uint8), self._t((self.PFN_STATS,), torch.float64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_pfn_train_forward(self.ctx, _ptr(voxels), _ptr(coors), _ptr(npts), _ptr(num), _ptr(w), _ptr(gamma), _ptr(beta),
+                                                     _ptr(feat), _ptr(arg), _ptr(stats), _stream()), self.ctx, "pp_pfn_train_forward")
+        return feat, arg, stats
+
+    def scatter_backward(self, dcanvas, coors, num, out=None):
+        """pp_scatter_backward: dL/d(canvas) [1,64,gx,gy] of one frame -> dL/d(feat) f32[P,64] (a gather; zero rows for coordinates
+        outside the grid).  out: rows of a larger [*,64] tensor to write into."""
+        self._chk_pillars(coors, num, "scatter_backward")
+        gx, gy = int(self.grid_size[0]), int(self.grid_size[1])
+        if isinstance(dcanvas, torch.Tensor) and not dcanvas.is_contiguous():
+            raise ValueError("scatter_backward: expected a contiguous dcanvas")
+        d = _chk(dcanvas.reshape(-1) if isinstance(dcanvas, torch.Tensor) else dcanvas, torch.float32, (64 * gx * gy,),
+                 "scatter_backward: dcanvas [1,64,gx,gy]")
+        dfeat = self._t((max(int(coors.shape[0]), 1), 64), torch.float32) if out is None else \
+            _chk(out, torch.float32, (None, 64), "scatter_backward: out")
+        if dfeat.shape[0] < coors.shape[0]:
+            raise ValueError("scatter_backward: fewer output rows than pillars")
+        for t, name in ((d, "dcanvas"), (coors, "coors"), (num, "num"), (dfeat, "out")):
+            if t.device != self.device:
+                raise ValueError(f"scatter_backward: {name} is on {t.device}, the engine on {self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_scatter_backward(self.ctx, _ptr(d), _ptr(coors), _ptr(num), _ptr(dfeat), _stream()), self.ctx,
+                       "pp_scatter_backward")
+        return dfeat
+
+    def pfn_backward(self, voxels, coors, npts, num, w, gamma, stats, feat, arg, dfeat):
+        """pp_pfn_backward: dL/d(feat) f32[P,64] with feat, arg and stats of pfn_train_forward on the same pillars and weights ->
+        (dw [64,9,1], dgamma [64], dbeta [64]).  fp32 results of fp64 sums, deterministic, stateless."""
+        self._chk_batch_pillars(voxels, coors, npts, num, "pfn_backward")
+        w, gamma = self._chk_pfn_params(w, gamma, None, "pfn_backward")
+        rows = max(int(voxels.shape[0]), 1)
+        stats = _chk(stats, torch.float64, (self.PFN_STATS,), "pfn_backward: stats")
+        feat = _chk(feat, torch.float32, (rows, 64), "pfn_backward: feat")
+        arg = _chk(arg, torch.uint8, (rows, 64), "pfn_backward: arg")
+        dfeat = _chk(dfeat, torch.float32, (rows, 64), "pfn_backward: dfeat")
+        for t, name in ((stats, "stats"), (feat, "feat"), (arg, "arg"), (dfeat, "dfeat")):
+            if t.device != self.device:
+                raise ValueError(f"pfn_backward: {name} is on {t.device}, the engine on {self.device}")
+        dw, dg, db = self._t((64, 9, 1), torch.float32), self._t((64,), torch.float32), self._t((64,), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_pfn_backward(self.ctx, _ptr(voxels), _ptr(coors), _ptr(npts), _ptr(num), _ptr(w), _ptr(gamma), _ptr(stats),
+                                                _ptr(feat), _ptr(arg), _ptr(dfeat), _ptr(dw), _ptr(dg), _ptr(db), _stream()), self.ctx,
+                       "pp_pfn_backward")
+        return dw, dg, db
+
+    def update_pfn_weights(self, w, gamma, beta, running_mean, running_var):
+        """pp_update_pfn_weights: the device tensors of PFN_KEYS and PFN_STAT_KEYS -> the eval-mode PFN of the context (transposed weight,
+        scale, shift), in place on the current stream, bit for bit what load_state_dict of the same values commits."""
+        w, gamma, beta = self._chk_pfn_params(w, gamma, beta, "update_pfn_weights")
+        rm = _chk(running_mean, torch.float32, (64,), "update_pfn_weights: running_mean")
+        rv = _chk(running_var, torch.float32, (64,), "update_pfn_weights: running_var")
+        for t in (rm, rv):
+            if t.device != self.device:
+                raise ValueError(f"update_pfn_weights: a statistic is on {t.device}, the engine on {self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_pfn_weights(self.ctx, _ptr(w), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), _stream()), self.ctx,
+                       "pp_update_pfn_weights")
+
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1 + _lib.PP_MAX_CLASSES,), dtype=torch.int32, device=self.device)

@@ -16,8 +16,15 @@ reference's state_dict order, 25 tensors).  The forward runs pp_backbone_train_t
 every strided convolution's pre-norm output; the backward (_RpnFunction) walks RPN_TABLE from block 3 to block 1: each block's
 pp_unit_backward chain, its pp_down_backward with the gradient of the stage input, to which the upsampler's dx of the level above is
 added.  The gradient of block 3's input that pp_down_backward computes is consumed by block 2 here.  optimizer.step() is followed by
-pp_update_rpn_weights, which also rewrites the sparse first convolution's image.  Only PFN and scatter stay frozen; rpn_train()
-returns the gradient with respect to the canvases when they require grad, the starting point of a PFN backward."""
+pp_update_rpn_weights, which also rewrites the sparse first convolution's image.  PFN and scatter stay frozen under "rpn"; rpn_train()
+returns the gradient with respect to the canvases when they require grad.
+
+Training everything: train(scope="all") adds the pillar feature net (PFN_KEYS; ALL_KEYS = the 28 tensors net.parameters() yields in the
+reference, in its state_dict order) and follows the reference's train.py, whose net.train() makes BatchNorm1d normalise with batch
+statistics: every training-mode forward runs pp_pfn_train_forward over the pillars of all frames of the batch (_PfnFunction), moves
+running_mean / running_var (momentum 0.1, unbiased variance) and counts num_batches_tracked, whether or not grad is enabled.  The
+backward consumes the canvases' gradient: pp_scatter_backward per frame, then one pp_pfn_backward (csrc/pfn_train.hip).  The eval-mode
+PFN of the engine (running statistics folded into scale / shift) is rewritten by pp_update_pfn_weights before it is next used."""
 import time
 import types
 
@@ -38,8 +45,16 @@ RPN_CONV_KEYS = Engine.RPN_CONV_KEYS
 # two convolutions is r -> r + U_b(U_a(r)), one of a single convolution r -> r + U_a(r); the level's units count the convolutions.
 RPN_TABLE = ((0, (2, 1)), (1, (2, 2, 1)), (2, (2, 2, 1)))
 # the reference's state_dict order of everything behind the canvas: per block its convolutions, then its upsampler; then the head
+PFN_KEYS = Engine.PFN_KEYS
+PFN_STAT_KEYS = Engine.PFN_STAT_KEYS
+PFN_NBT_KEY = "pillar_point_net.pfn_layers.1.num_batches_tracked"
+BN_MOMENTUM = 0.1  # torch's BatchNorm1d default, which the reference keeps
 RPN_KEYS = tuple(k for b in range(3) for k in RPN_CONV_KEYS[(0, 4, 10)[b]:(4, 10, 16)[b]] + (NECK_KEYS[b],)) + HEAD_KEYS
 _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in BLOCK3_KEYS)  # what the narrower scopes never train
+ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
+SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
+# the scopes that train: the upsamplers; block 3's units; block 3's strided convolution; blocks 1 and 2; the pillar feature net
+_NECK_SCOPES, _BLOCK_SCOPES, _STAGE_SCOPES, _RPN_SCOPES = SCOPES[1:], SCOPES[2:], SCOPES[3:], SCOPES[4:]
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -224,6 +239,36 @@ class _RpnFunction(torch.autograd.Function):
         return (None, g if need[1] else None) + tuple(grads)
 
 
+class _PfnFunction(torch.autograd.Function):
+    """PointNet.forward in train mode and PointPillarsScatter.forward: one pp_pfn_train_forward over the pillars of all frames (rows
+    grouped by frame; frames = ((row0, row1, coors [n,3], num [1]), ...)), then pp_scatter per frame.  Returns the canvases and the
+    batch statistics f64[218] (not differentiable: the caller moves the running statistics with them).  The backward is
+    pp_scatter_backward per frame into that frame's rows of dfeat, then one pp_pfn_backward.  The three parameters are inputs so that
+    autograd routes their gradients, and the kernels read them from the call.  The points get no gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, voxels, coors, npts, frames, w, gamma, beta):
+        num = eng.num_tensor(voxels.shape[0])
+        feat, arg, stats = eng.pfn_train_forward(voxels, coors, npts, num, w, gamma, beta)
+        canvases = torch.cat([eng.scatter(feat[a:b], c, n) for a, b, c, n in frames])
+        ctx.eng, ctx.frames = eng, frames
+        ctx.save_for_backward(voxels, coors, npts, num, w, gamma, feat, arg, stats)
+        ctx.mark_non_differentiable(stats)
+        return canvases, stats
+
+    @staticmethod
+    def backward(ctx, gcanvas, _gstats):
+        voxels, coors, npts, num, w, gamma, feat, arg, stats = ctx.saved_tensors
+        eng = ctx.eng
+        gcanvas = gcanvas.contiguous()
+        dfeat = torch.empty_like(feat)
+        for f, (a, b, c, n) in enumerate(ctx.frames):
+            eng.scatter_backward(gcanvas[f], c, n, out=dfeat[a:b])
+        dw, dg, db = eng.pfn_backward(voxels, coors, npts, num, w, gamma, stats, feat, arg, dfeat)
+        need = ctx.needs_input_grad
+        return (None,) * 5 + (dw if need[5] else None, dg if need[6] else None, db if need[7] else None)
+
+
 class PointPillars:
     _norm = "instance"
     # read-only defaults for an object assembled without __init__ (no engine: the key-order tests); __init__ and load_state_dict
@@ -231,6 +276,7 @@ class PointPillars:
     _block, _block_uploaded, _block_trained = types.MappingProxyType({}), None, False
     _down, _down_uploaded, _down_trained = types.MappingProxyType({}), None, False
     _rpn, _rpn_uploaded, _rpn_trained = types.MappingProxyType({}), None, False
+    _pfn, _pfn_stats, _pfn_uploaded, _pfn_trained, _pfn_nbt = types.MappingProxyType({}), types.MappingProxyType({}), None, False, None
 
     def __init__(self, config):
         self.device = config['device']
@@ -244,7 +290,12 @@ class PointPillars:
         self._trained = False        # the head has been stepped since load_state_dict
         self._scope = "head"         # train(scope=...): "head", "neck" (+ the three upsamplers), "block3" (+ block 3's five unit
                                      # convolutions), "stage3" (+ block 3's stride-2 convolution) or "rpn" (+ blocks 1 and 2 with
-                                     # their stride-2 convolutions: the whole RPN)
+                                     # their stride-2 convolutions: the whole RPN) or "all" (+ the pillar feature net)
+        self._pfn = {}               # the PFN's Conv1d weight and BatchNorm1d weight / bias as device Parameters
+        self._pfn_stats = {}         # running_mean / running_var as device tensors (train(scope="all") moves them)
+        self._pfn_nbt = None         # num_batches_tracked when the loaded dict carried it
+        self._pfn_uploaded = None    # the _version numbers of those five at the last upload into the engine
+        self._pfn_trained = False
         self._rpn = {}               # the ten convolutions of blocks 1 and 2 as device Parameters
         self._rpn_uploaded = None
         self._rpn_trained = False
@@ -274,31 +325,42 @@ class PointPillars:
         trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
         block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
         frozen: it has no backward.  scope="rpn" trains the whole RPN (RPN_KEYS: blocks 1 and 2 with their stride-2 convolutions as
-        well); only PFN and scatter stay frozen.  eval() / train(False) restores the inference behaviour."""
-        if scope not in ("head", "neck", "block3", "stage3", "rpn"):
-            raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3' or 'rpn', got {scope!r}")
+        well); PFN and scatter stay frozen.  scope="all" trains the pillar feature net too (ALL_KEYS, what net.parameters() yields
+        in the reference): the training-mode forward then normalises the PFN with batch statistics and moves the running ones, as the
+        reference's net.train() does.  eval() / train(False) restores the inference behaviour, with the PFN's current parameters and
+        running statistics folded into the engine."""
+        if scope not in SCOPES:
+            raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
         if mode and scope != "head" and (self._norm != "instance" or len(self._neck) != 3 or
-                                         (scope in ("block3", "stage3", "rpn") and len(self._block) != 5) or
-                                         (scope in ("stage3", "rpn") and len(self._down) != 1) or
-                                         (scope == "rpn" and len(self._rpn) != len(_RPN_EXTRA_KEYS))):
+                                         (scope in _BLOCK_SCOPES and len(self._block) != 5) or
+                                         (scope in _STAGE_SCOPES and len(self._down) != 1) or
+                                         (scope in _RPN_SCOPES and len(self._rpn) != len(_RPN_EXTRA_KEYS)) or
+                                         (scope == "all" and (len(self._pfn) != 3 or len(self._pfn_stats) != 2))):
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only")
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
         for p in self._params.values():
             p.requires_grad_(self.training)
         for p in self._neck.values():
-            p.requires_grad_(self.training and self._scope in ("neck", "block3", "stage3", "rpn"))
+            p.requires_grad_(self.training and self._scope in _NECK_SCOPES)
         for p in self._block.values():
-            p.requires_grad_(self.training and self._scope in ("block3", "stage3", "rpn"))
+            p.requires_grad_(self.training and self._scope in _BLOCK_SCOPES)
         for p in self._down.values():
-            p.requires_grad_(self.training and self._scope in ("stage3", "rpn"))
+            p.requires_grad_(self.training and self._scope in _STAGE_SCOPES)
         for p in self._rpn.values():
-            p.requires_grad_(self.training and self._scope == "rpn")
+            p.requires_grad_(self.training and self._scope in _RPN_SCOPES)
+        for p in self._pfn.values():
+            p.requires_grad_(self.training and self._scope == "all")
+        if not (self.training and self._scope == "all"):
+            self._sync_pfn()  # whatever reads the engine's eval-mode PFN next (this object or framework.inference) sees the trained one
         return self
 
     def _trainable(self):
-        if self._scope == "rpn":
+        if self._scope in _RPN_SCOPES:
             every = {**self._rpn, **self._down, **self._block, **self._neck, **self._params}
+            if self._scope == "all":
+                every.update(self._pfn)
+                return {k: every[k] for k in ALL_KEYS if k in every}
             return {k: every[k] for k in RPN_KEYS if k in every}
         if self._scope == "stage3":
             return {**self._down, **self._block, **self._neck, **self._params}
@@ -309,15 +371,15 @@ class PointPillars:
     def named_parameters(self):
         """The trainable tensors on the device: heads.conv_{cls,box,dir}.{weight,bias}, behind rpn.deconv{1,2,3}.0.weight under
         train(scope="neck"), behind BLOCK3_KEYS (unit order) as well under train(scope="block3"), and behind rpn.block3.0.weight
-        under train(scope="stage3"); under train(scope="rpn") the 25 tensors of RPN_KEYS in the reference's state_dict order.  Everything
-        before them is frozen."""
+        under train(scope="stage3"); under train(scope="rpn") the 25 tensors of RPN_KEYS in the reference's state_dict order, under
+        train(scope="all") the 28 of ALL_KEYS.  Everything before them is frozen."""
         return iter(self._trainable().items())
 
     def parameters(self):
         return iter(self._trainable().values())
 
     def zero_grad(self, set_to_none=True):
-        for p in list(self._rpn.values()) + list(self._down.values()) + list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
+        for p in list(self._pfn.values()) + list(self._rpn.values()) + list(self._down.values()) + list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
             if set_to_none:
                 p.grad = None
             elif p.grad is not None:
@@ -341,6 +403,20 @@ class PointPillars:
 
     def _rpn_moved(self):
         return self._rpn_uploaded is not None and tuple(p._version for p in self._rpn.values()) != self._rpn_uploaded
+
+    def _pfn_versions(self):
+        return tuple(t._version for t in list(self._pfn.values()) + list(self._pfn_stats.values()))
+
+    def _pfn_moved(self):
+        return self._pfn_uploaded is not None and self._pfn_versions() != self._pfn_uploaded
+
+    def _sync_pfn(self):
+        """The same for the pillar feature net, ahead of whatever runs the eval-mode PFN: a stepped parameter or moved running
+        statistics are folded into the engine's transposed weight, scale and shift (pp_update_pfn_weights)."""
+        if self._pfn_moved():
+            self._pfn_trained = True
+            self._eng.update_pfn_weights(*[self._pfn[k] for k in PFN_KEYS], *[self._pfn_stats[k] for k in PFN_STAT_KEYS])
+            self._pfn_uploaded = self._pfn_versions()
 
     def _sync_neck(self):
         """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone; when
@@ -389,6 +465,10 @@ class PointPillars:
             self._down_uploaded = ()
         if self._rpn_trained or self._rpn_moved():
             self._rpn_uploaded = ()
+        if self._pfn_trained or self._pfn_moved():
+            self._pfn_uploaded = ()  # the commit folds the loaded PFN again: the trained one goes up before its next use
+            if not (self.training and self._scope == "all"):
+                self._sync_pfn()
         return self
 
     def _head_moved(self):
@@ -398,6 +478,11 @@ class PointPillars:
         """The loaded tensors; the head's six, the three upsampler weights and all sixteen 3 x 3 convolutions of the RPN (blocks 1, 2
         and 3 with their stride-2 weights, RPN_CONV_KEYS) with their CURRENT values (after optimizer steps)."""
         sd = dict(self._sd)
+        if self._pfn_moved() or self._pfn_trained:
+            for k, t in list(self._pfn.items()) + list(self._pfn_stats.items()):
+                sd[k] = t.detach().cpu().numpy().reshape(self._sd[k].shape)
+            if self._pfn_nbt is not None:
+                sd[PFN_NBT_KEY] = np.asarray(self._pfn_nbt, dtype=np.int64)
         if self._rpn_moved() or self._rpn_trained:
             for k, p in self._rpn.items():
                 sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
@@ -422,14 +507,14 @@ class PointPillars:
                                               requires_grad=self.training) for k in HEAD_KEYS if k in self._sd}
         self._uploaded = tuple(p._version for p in self._params.values())
         self._trained = False
-        neck = self.training and self._scope in ("neck", "block3", "stage3", "rpn")
-        block = self.training and self._scope in ("block3", "stage3", "rpn")
+        neck = self.training and self._scope in _NECK_SCOPES
+        block = self.training and self._scope in _BLOCK_SCOPES
         self._rpn = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                           requires_grad=self.training and self._scope == "rpn") for k in _RPN_EXTRA_KEYS if k in self._sd}
+                                           requires_grad=self.training and self._scope in _RPN_SCOPES) for k in _RPN_EXTRA_KEYS if k in self._sd}
         self._rpn_uploaded = tuple(p._version for p in self._rpn.values())
         self._rpn_trained = False
         self._down = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                            requires_grad=self.training and self._scope in ("stage3", "rpn")) for k in (STAGE3_KEY,) if k in self._sd}
+                                            requires_grad=self.training and self._scope in _STAGE_SCOPES) for k in (STAGE3_KEY,) if k in self._sd}
         self._down_uploaded = tuple(p._version for p in self._down.values())
         self._down_trained = False
         self._block = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
@@ -440,6 +525,12 @@ class PointPillars:
                                             requires_grad=neck) for k in NECK_KEYS if k in self._sd}
         self._neck_uploaded = tuple(p._version for p in self._neck.values())
         self._neck_trained = False
+        dev_of = lambda k: torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device)  # noqa: E731
+        self._pfn = {k: torch.nn.Parameter(dev_of(k), requires_grad=self.training and self._scope == "all") for k in PFN_KEYS if k in self._sd}
+        self._pfn_stats = {k: dev_of(k) for k in PFN_STAT_KEYS if k in self._sd}
+        self._pfn_nbt = int(np.asarray(self._sd[PFN_NBT_KEY])) if PFN_NBT_KEY in self._sd else None
+        self._pfn_uploaded = self._pfn_versions()
+        self._pfn_trained = False
         return self
 
     def _sync(self):
@@ -447,9 +538,43 @@ class PointPillars:
             torch.cuda.synchronize()
         return time.time()
 
+    def _pfn_training(self):
+        return self.training and self._scope == "all"
+
+    def pfn_train(self, frames):
+        """PointNet in train mode and the scatter on a batch: frames = [(voxels [n,T,4], coors [n,3], num_points_per_voxel [n]), ...],
+        at most max_batch of them -> canvases [nb,64,gx,gy].  BatchNorm1d normalises with the statistics of the pillars of all frames
+        together and the running statistics move (momentum 0.1, unbiased variance), whether or not grad is enabled.  Differentiable
+        with respect to PFN_KEYS when they require grad (train(scope="all")).  Needs the fp32 precision mode."""
+        eng = self._eng
+        if not 1 <= len(frames) <= eng.max_batch:
+            raise ValueError(f"pfn_train: {len(frames)} frames in the batch, max_batch is {eng.max_batch}")
+        if len(self._pfn) != 3 or len(self._pfn_stats) != 2:
+            raise RuntimeError("pfn_train: the state_dict holds no pillar feature net")
+        if eng.effective_precision() != "fp32":
+            raise RuntimeError(f"PFN training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
+                               "(the backward of the RPN behind it is fp32); call float()")
+        voxels = torch.cat([f[0] for f in frames]).contiguous()
+        coors = torch.cat([f[1] for f in frames]).contiguous()
+        npts = torch.cat([f[2] for f in frames]).contiguous()
+        rows, spans = 0, []
+        for _, c, _ in frames:
+            spans.append((rows, rows + int(c.shape[0]), c.contiguous(), eng.num_tensor(c.shape[0])))
+            rows += int(c.shape[0])
+        canvases, stats = _PfnFunction.apply(eng, voxels, coors, npts, tuple(spans), *[self._pfn[k] for k in PFN_KEYS])
+        n = rows * eng.T
+        with torch.no_grad():  # BatchNorm1d's update, evaluated in fp64 and rounded once
+            rm, rv = (self._pfn_stats[k] for k in PFN_STAT_KEYS)
+            rm.copy_(((1.0 - BN_MOMENTUM) * rm.double() + BN_MOMENTUM * stats[:64]).float())
+            rv.copy_(((1.0 - BN_MOMENTUM) * rv.double() + BN_MOMENTUM * (n / (n - 1.0)) * stats[64:128]).float())
+        if self._pfn_nbt is not None:
+            self._pfn_nbt += 1
+        return canvases
+
     def _forward_frames(self, example):
         """Several frames collated by merge_second_batch (coordinates carry the frame index as their last column): each frame runs
-        the frozen PFN / scatter / backbone, the rpn outputs are stacked and the head runs on the batch."""
+        the frozen PFN / scatter / backbone, the rpn outputs are stacked and the head runs on the batch.  Under train(scope="all") the
+        PFN runs in train mode over the pillars of all frames together (pfn_train)."""
         eng = self._eng
         coors = example["coordinates"]
         frame = coors[:, -1]
@@ -458,6 +583,11 @@ class PointPillars:
             raise ValueError(f"forward: {nb} frames in the batch, max_batch is {eng.max_batch}")
         neck = self._neck_grad()
         self._sync_neck()
+        if self._pfn_training():
+            sels = [frame == f for f in range(nb)]
+            canvases = self.pfn_train([(example["voxels"][s], coors[s][:, :-1].contiguous(), example["num_points_per_voxel"][s]) for s in sels])
+            return self.heads(self.rpn_train(canvases) if neck else torch.cat([eng.backbone(c) for c in canvases]))
+        self._sync_pfn()
         rpn = []
         with torch.no_grad():
             for f in range(nb):
@@ -478,9 +608,14 @@ class PointPillars:
         coors = example["coordinates"].contiguous()
         num = eng.num_tensor(voxels.shape[0])
         start = time.time()
-        feat = eng.pfn(voxels, coors, npts, num)
-        pfn_time = self._sync()
-        canvas = eng.scatter(feat, coors, num)
+        if self._pfn_training():
+            canvas = self.pfn_train([(voxels, coors, npts)])  # PFN and scatter are one Function: both are booked as pfn_time
+            pfn_time = self._sync()
+        else:
+            self._sync_pfn()
+            feat = eng.pfn(voxels, coors, npts, num)
+            pfn_time = self._sync()
+            canvas = eng.scatter(feat, coors, num)
         scatter_time = self._sync()
         rpn = self.rpn_train(canvas) if self._neck_grad() else self.rpn(canvas)
         rpn_time = self._sync()
@@ -497,6 +632,7 @@ class PointPillars:
 
     # sub-stages, named as the reference's sub-modules, for stage-wise parity tests
     def pillar_point_net(self, voxels, num_point_per_voxel, coors):
+        self._sync_pfn()
         return self._eng.pfn(voxels.contiguous(), coors.contiguous(), num_point_per_voxel.contiguous(),
                              self._eng.num_tensor(voxels.shape[0]))[:voxels.shape[0]]
 
@@ -508,7 +644,7 @@ class PointPillars:
         return self._eng.backbone(x.contiguous())
 
     def _neck_grad(self):
-        return self.training and self._scope in ("neck", "block3", "stage3", "rpn") and torch.is_grad_enabled() and \
+        return self.training and self._scope in _NECK_SCOPES and torch.is_grad_enabled() and \
             any(p.requires_grad for p in list(self._neck.values()) + list(self._block.values()) + list(self._down.values()) +
                 list(self._rpn.values()))
 
@@ -516,7 +652,7 @@ class PointPillars:
         """RPN.forward on canvases x [B,64,gx,gy], 1 <= B <= max_batch, one backbone pass per frame; same values as rpn() bit for
         bit.  Differentiable with respect to the three upsampler weights when they require grad (train(scope="neck")) and to block
         3's five unit weights (train(scope="block3")) and its stride-2 weight (train(scope="stage3")); under train(scope="rpn") to all
-        sixteen convolutions, and then also to x itself when it requires grad (the level-0 dx: where a PFN backward would start).
+        sixteen convolutions, and then also to x itself when it requires grad (the level-0 dx: where the PFN backward starts).
         Gradients are fp32 and need the fp32 precision mode."""
         eng = self._eng
         gx, gy = int(eng.grid_size[0]), int(eng.grid_size[1])

@@ -409,6 +409,51 @@ int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, flo
  * are NOT changed.  fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and before the first commit. */
 int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w /* 16 */, void* stream);
 
+/* ---- training the pillar feature net: PointNet in train mode, its backward and the scatter's (pfn_train.hip) ----
+ * PointNet.forward (pointpillars8_shared.py:30-60) with BatchNorm1d normalising by BATCH statistics.  Notation: f[p][t][0:9] the nine
+ * decorated features of slot t of pillar p (x, y, z, r, x - mx, y - my, z - mz, x - cx, y - cy; arithmetic as pp_pfn: mean over all T
+ * slots divided by n, cell centre by a separate multiply and add), all zero for padded slots t >= n_p = min(npts[p], T);
+ * P = min(*num_pillars, max_batch * max_voxels) pillars of ALL frames of a batch, T = max_num_points, N = P T (BatchNorm1d sees the
+ * padded slots as zeros).  z[p][t][c] = sum_k w[c][k] f[p][t][k].
+ *
+ * pp_pfn_train_forward: w f32[64][9] (state_dict layout of pfn_layers.0.weight), gamma / beta f32[64] are DEVICE tensors taken from the
+ * call; ctx->pfn_* is not read (stateless, as pp_unit_backward).  Pass 1: s[k] = sum f[.][.][k] and M[j][k] = sum f[.][.][j] f[.][.][k]
+ * in fp64 from the fp32 features (per-block partials in a fixed order, one finishing block in block order: no atomics, two runs agree
+ * bit for bit), then mean_c = w_c s / N, var_c = w_c M w_c^T / N - mean_c^2 (biased), scale_c = gamma_c / sqrt(var_c + 1e-5),
+ * shift_c = beta_c - mean_c scale_c, all fp64, scale / shift rounded to fp32 as pp_commit_weights rounds the eval-mode fold.
+ * Pass 2: pp_pfn's kernel with that scale / shift -> feat f32[P][64] = max_t relu(scale z + shift) over all T slots (a padded slot has
+ * z = 0) and arg u8[P][64], the FIRST slot that attains the maximum (n_p when a padded slot wins).
+ * stats f64[218] = mean[64], var[64], s[9], M[9][9].  The partials and the folded scale / shift live in a workspace of the context
+ * (allocated on first use): calls on one context must be issued in order on one stream.  The call reads *num_pillars back
+ * (synchronises `stream` once) so that it can refuse before anything is launched: PP_E_ARG for a null pointer, F != 4, T > 255 (arg is
+ * a byte) and P T < 2 (no unbiased variance: torch raises there too).
+ *
+ * pp_scatter_backward: the backward of pp_scatter for one frame is a gather, dfeat[p][c] = dcanvas[c][cx gy + cy] for
+ * p < min(*num_pillars, max_voxels), zero for a coordinate outside the grid (which the forward skips).  dcanvas f32[64][gx][gy],
+ * dfeat f32[P][64].
+ *
+ * pp_pfn_backward: from dfeat = dL/dfeat f32[P][64], with feat / arg / stats of the forward of the SAME voxels and weights.  One pass
+ * over the pillars, lane = channel: g = dfeat where feat > 0 (else 0), t* = arg, zhat* = (z[p][t*][c] - mean_c) invstd_c recomputed
+ * from the pillar's rows; S1_c = sum_p g, S2_c = sum_p g zhat*, G[c][k] = sum_p g f[p][t*][k] in fp64 (per-block partials in a fixed
+ * order, one finishing block).  dbeta = S1, dgamma = S2,
+ * dw[c][k] = gamma_c invstd_c (G[c][k] - S1_c s_k / N - S2_c invstd_c ((w M)[c][k] - mean_c s_k) / N), evaluated in fp64 and rounded.
+ * dw f32[64][9], dgamma / dbeta f32[64], fully written.  No gradient with respect to the points.  Deterministic; does not synchronise.
+ * PP_E_ARG for a null pointer, F != 4 and T > 255.
+ *
+ * pp_update_pfn_weights: after an optimizer step (or a move of the running statistics), the DEVICE tensors w f32[64][9], gamma, beta,
+ * running_mean, running_var f32[64] -> the eval-mode PFN of the context (transposed weight, scale, shift), rewritten in place on
+ * `stream` with the fp64 fold of pp_commit_weights: bit for bit what a fresh commit of the same values holds.  pp_pfn and the fused
+ * passes read those buffers.  The host copies of pp_load_weights are NOT changed.  PP_E_STATE before the first commit. */
+#define PP_PFN_STATS 218 /* doubles in stats: mean[64], var[64], s[9], M[9][9] */
+int pp_pfn_train_forward(pp_ctx* ctx, const float* voxels, const int32_t* coors, const int32_t* npts, const int32_t* num_pillars,
+                         const float* w, const float* gamma, const float* beta, float* feat, uint8_t* arg, double* stats, void* stream);
+int pp_scatter_backward(pp_ctx* ctx, const float* dcanvas, const int32_t* coors, const int32_t* num_pillars, float* dfeat, void* stream);
+int pp_pfn_backward(pp_ctx* ctx, const float* voxels, const int32_t* coors, const int32_t* npts, const int32_t* num_pillars, const float* w,
+                    const float* gamma, const double* stats, const float* feat, const uint8_t* arg, const float* dfeat, float* dw,
+                    float* dgamma, float* dbeta, void* stream);
+int pp_update_pfn_weights(pp_ctx* ctx, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                          const float* running_var, void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);
