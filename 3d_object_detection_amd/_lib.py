@@ -11,6 +11,8 @@ PP_ASSIGN_MAX_GT = 4096
 PP_AUG_MAX_BOXES = 256
 PP_AUG_MAX_TRIES = 128
 PP_AUG_PARAMS = 16
+PP_OPT_CHUNK = 2048
+PP_OPT_GROUP = 32
 
 c_f = ctypes.c_float
 c_i32 = ctypes.c_int32
@@ -91,6 +93,11 @@ PROTOTYPES = {
     "pp_scatter_backward": (ctypes.c_int, [c_p] * 6),
     "pp_pfn_backward": (ctypes.c_int, [c_p] * 15),
     "pp_update_pfn_weights": (ctypes.c_int, [c_p] * 7),
+    "pp_grad_norm": (ctypes.c_int, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_i64), ctypes.c_int, c_f, c_p, c_p]),
+    "pp_scale_grads": (ctypes.c_int, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_i64), ctypes.c_int, c_p, c_p]),
+    "pp_adam_step": (ctypes.c_int, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_i64),
+                                    ctypes.c_int, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_int, c_p, c_p]),
     "pp_augment_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_noise": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p]),

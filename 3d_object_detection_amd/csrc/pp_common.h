@@ -130,6 +130,7 @@ struct pp_ctx {
     void* blk = nullptr;             // Resnet unit backward (block_train.hip): padded a / dz planes, transposed weights, dW partials
     void* down = nullptr;            // strided stage backward (down_train.hip): parity planes of x, dz planes, transposed weights, dW partials
     void* pfnt = nullptr;            // PFN training (pfn_train.hip): fp64 partials of both reductions, the batch-statistics scale / shift
+    void* optim = nullptr;           // device optimizer (optim.hip): fp64 partials of the gradient norm, one per chunk
     // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
     //      the selected candidates only; f_box / f_dir are then stale until pp_head_materialise runs the full head over the retained
     //      concat buffer and statistics of that pass ----
@@ -263,6 +264,7 @@ void pp_block_destroy(pp_ctx* ctx);
 int pp_net_down_image(pp_ctx* ctx, int level, pp_block_image* img);
 void pp_down_destroy(pp_ctx* ctx);
 void pp_pfn_train_destroy(pp_ctx* ctx);
+void pp_optim_destroy(pp_ctx* ctx);
 // block_train.hip's image kernel for any position map: dst[i] = position pmap[i] % T of the transformed weight of (row, cin) =
 // pmap[i] / T (< nrc), 0 for padding; w is the state_dict tensor [rows][cin][3][3] on the device
 void pp_launch_unit_image(float* dst, const int32_t* pmap, int n, const float* w, int T, int nrc, hipStream_t stream);

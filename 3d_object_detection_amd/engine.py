@@ -754,6 +754,98 @@ class Engine:
             _lib.check(self.lib.pp_update_pfn_weights(self.ctx, _ptr(w), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), _stream()), self.ctx,
                        "pp_update_pfn_weights")
 
+    # ------------------------------------------------------------------ device optimizer (optim.hip)
+    OPT_CHUNK, OPT_GROUP = _lib.PP_OPT_CHUNK, _lib.PP_OPT_GROUP
+
+    def _chk_list(self, ts, what, like=None):
+        """A list of fp32 tensors for the multi-tensor kernels, of any shape or, with `like`, of the shapes of that list; None
+        entries pass (the callers that do not take them refuse them first) -> host array of device pointers.  One pass decides
+        whether every entry is in order (a step over 28 tensors checks 140 of them); the entry-by-entry _chk runs only to name
+        the offender."""
+        f32, dv = torch.float32, self.device
+        try:
+            if like is None:
+                ok = all(t is None or (t.dtype is f32 and t.is_cuda and t.device == dv and t.is_contiguous()) for t in ts)
+            else:
+                ok = len(ts) == len(like) and all(t is None or (t.dtype is f32 and t.is_cuda and t.device == dv and t.is_contiguous()
+                                                                and t.shape == q.shape) for t, q in zip(ts, like))
+        except AttributeError:  # not a tensor
+            ok = False
+        if not ok:
+            if like is not None and len(ts) != len(like):
+                raise ValueError(f"{what}: {len(ts)} tensors for {len(like)} parameters")
+            for i, t in enumerate(ts):
+                if t is None:
+                    continue
+                _chk(t, f32, tuple(like[i].shape) if like is not None else (None,) * t.dim(), f"{what}[{i}]")
+                if t.device != dv:
+                    raise ValueError(f"{what}[{i}] is on {t.device}, the engine on {dv}")
+        return (ctypes.c_void_p * max(1, len(ts)))(*[None if t is None or t.numel() == 0 else t.data_ptr() for t in ts])
+
+    @staticmethod
+    def _lens(ts):
+        return (ctypes.c_int64 * max(1, len(ts)))(*[0 if t is None else t.numel() for t in ts])
+
+    @staticmethod
+    def _no_none(ts, what):
+        ts = list(ts)
+        if any(t is None for t in ts):
+            raise TypeError(f"{what}: an entry is None")
+        return ts
+
+    def _chk_coef(self, coef, what):
+        if not isinstance(coef, torch.Tensor) or not coef.is_cuda:
+            raise TypeError(f"{what}: coef must be a CUDA tensor")
+        if coef.dtype != torch.float32 or coef.numel() < 1 or coef.device != self.device:
+            raise TypeError(f"{what}: coef must hold one float32 on {self.device}")
+        return coef
+
+    # the calls themselves, on lists that were checked (framework.optim keeps the arrays of the tensors it owns between steps)
+    def _grad_norm(self, pg, lens, n, max_norm):
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_grad_norm(self.ctx, pg, lens, n, max_norm, _ptr(out), _stream()), self.ctx, "pp_grad_norm")
+        return out
+
+    def _adam_step(self, pp, pg, pm, pv, lens, n, step, lr, beta1, beta2, eps, weight_decay, decoupled, coef):
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_adam_step(self.ctx, pp, pg, pm, pv, lens, n, step, lr, beta1, beta2, eps, weight_decay, decoupled,
+                                             _ptr(coef), _stream()), self.ctx, "pp_adam_step")
+
+    def grad_norm(self, grads, max_norm):
+        """pp_grad_norm: float32[2] = (total 2-norm of the listed tensors, clip coefficient min(1, max_norm / (norm + 1e-6))) on the
+        device; fp64 sums in a fixed order, no host synchronisation."""
+        grads = self._no_none(grads, "grad_norm: grads")
+        return self._grad_norm(self._chk_list(grads, "grad_norm: grads"), self._lens(grads), len(grads), float(max_norm))
+
+    def scale_grads(self, grads, coef):
+        """pp_scale_grads: g *= coef[0] in place for every listed tensor, coef read on the device (grad_norm(...)[1:])."""
+        grads = self._no_none(grads, "scale_grads: grads")
+        ptrs = self._chk_list(grads, "scale_grads: grads")
+        coef = self._chk_coef(coef, "scale_grads")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_scale_grads(self.ctx, ptrs, self._lens(grads), len(grads), _ptr(coef), _stream()), self.ctx, "pp_scale_grads")
+
+    def adam_step(self, params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1, beta2, eps, weight_decay=0.0, decoupled=False, coef=None):
+        """pp_adam_step: one Adam (decoupled: AdamW) step at step number `step` on the listed parameters, in place in params / exp_avgs /
+        exp_avg_sqs; a parameter whose entry of grads is None is skipped.  coef: device float32 the gradients are multiplied by on the
+        fly (the clip coefficient; the gradients themselves are not written)."""
+        params = self._no_none(params, "adam_step: params")
+        grads, exp_avgs, exp_avg_sqs = list(grads), list(exp_avgs), list(exp_avg_sqs)
+        pp = self._chk_list(params, "adam_step: params")
+        pg = self._chk_list(grads, "adam_step: grads", like=params)
+        for name, lst in (("exp_avgs", exp_avgs), ("exp_avg_sqs", exp_avg_sqs)):
+            if any(t is None and g is not None for t, g in zip(lst, grads)):
+                raise TypeError(f"adam_step: an entry of {name} is None")
+        pm = self._chk_list(exp_avgs, "adam_step: exp_avgs", like=params)
+        pv = self._chk_list(exp_avg_sqs, "adam_step: exp_avg_sqs", like=params)
+        if coef is not None:
+            coef = self._chk_coef(coef, "adam_step")
+        if int(step) != step or step < 1:
+            raise ValueError(f"adam_step: step must be a whole number >= 1, got {step}")
+        self._adam_step(pp, pg, pm, pv, self._lens(params), len(params), int(step), float(lr), float(beta1), float(beta2), float(eps),
+                        float(weight_decay), int(bool(decoupled)), coef)
+
     def postprocess(self, cls, box, dr, mask, nms_mode=0):
         det = torch.zeros((self.cfg.num_classes * self.cfg.nms_post_max, 9), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1 + _lib.PP_MAX_CLASSES,), dtype=torch.int32, device=self.device)

@@ -454,6 +454,42 @@ int pp_pfn_backward(pp_ctx* ctx, const float* voxels, const int32_t* coors, cons
 int pp_update_pfn_weights(pp_ctx* ctx, const float* w, const float* gamma, const float* beta, const float* running_mean,
                           const float* running_var, void* stream);
 
+/* ---- device optimizer: gradient-norm clipping and Adam / AdamW over a list of fp32 tensors (optim.hip) ----
+ * torch.nn.utils.clip_grad_norm_ and torch.optim.Adam / AdamW (the reference's train.py:100-108) as multi-tensor kernels.  The lists
+ * (device pointers and element counts) are HOST arrays of `count` entries; the library passes them to its kernels by value, in kernel
+ * arguments, PP_OPT_GROUP tensors per launch: no copy to the device, no allocation per call, no host synchronisation, all work on
+ * `stream`.  Every tensor is cut into chunks of PP_OPT_CHUNK elements (the last one short), one workgroup per chunk; within a chunk a
+ * lane owns fixed groups of four consecutive elements, moved with 16-byte accesses where every pointer of the tensor is 16-byte
+ * aligned and the group is whole, element by element otherwise.
+ *
+ * pp_grad_norm: out f32[2] (device) = {total_norm, coef}.  total_norm = sqrt(sum g^2) over all tensors: the squares are exact in
+ * fp64 and are added in fp64, per chunk in a fixed lane / wave order into one partial per chunk (a workspace of the context, allocated
+ * on the first call: calls on one context must be issued in order on one stream), the partials by one finishing workgroup (every lane a
+ * contiguous run in index order, the lanes' sums in lane order), then the square root, rounded once to fp32.  No atomics: two runs agree
+ * bit for bit, and neither the split into launches nor a pointer's alignment enters the order.  coef = min(1, (1 / (total_norm + 1e-6))
+ * * max_norm) in fp32 (torch evaluates max_norm / tensor as reciprocal times scalar); a NaN norm gives a NaN coef, as torch.clamp does.
+ * count == 0 or all lengths 0: {0, 1}.  PP_E_ARG for more than PP_OPT_MAX_CHUNKS chunks in all.
+ *
+ * pp_scale_grads: g *= coef[0] in place, coef on the device (out + 1 of pp_grad_norm); a coef of exactly 1 writes nothing.
+ *
+ * pp_adam_step: one step of Adam for the tensors whose g is not NULL (the others are skipped entirely), all at step number t >= 1.
+ * Per element in fp32: g' = coef[0] g (coef NULL: g; g is not written); weight_decay != 0: g' = fma(wd, p, g') (decoupled == 0, L2) or
+ * p = fma(-lr wd, p, p) (decoupled != 0, AdamW); m = fma(beta1, m, (1 - beta1) g'); v = fma(beta2, v, ((1 - beta2) g') g');
+ * p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  The bias corrections, 1 - beta and lr wd are computed on the
+ * host in double and rounded to fp32.  One pass: p, g, m, v read once, p, m, v written once.
+ *
+ * All three: PP_E_ARG for a null list, a null pointer with a non-zero length (g of pp_adam_step excepted), a negative length, a
+ * pointer that is not 4-byte aligned, t < 1, beta outside [0, 1) and negative lr / eps / weight_decay; refused before anything is
+ * launched. */
+#define PP_OPT_CHUNK 2048        /* elements per workgroup */
+#define PP_OPT_GROUP 32          /* tensors per launch */
+#define PP_OPT_MAX_CHUNKS 262144 /* partials of pp_grad_norm (2 MB): 2^29 elements in whole chunks */
+int pp_grad_norm(pp_ctx* ctx, const float* const* grads, const int64_t* lens, int count, float max_norm, float* out, void* stream);
+int pp_scale_grads(pp_ctx* ctx, float* const* grads, const int64_t* lens, int count, const float* coef, void* stream);
+int pp_adam_step(pp_ctx* ctx, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* lens, int count,
+                 int64_t t, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, const float* coef,
+                 void* stream);
+
 /* Stateless box ops (replace framework/box_torch_ops.py:18-77 and framework/nms.py:6-40,
  * eval/iou.py:438-473). */
 int pp_box_decode(const float* enc, const float* anchors, float* out, int64_t n, void* stream);
