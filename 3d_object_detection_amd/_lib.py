@@ -82,6 +82,9 @@ PROTOTYPES = {
     "pp_neck_backward": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
     "pp_update_neck_weights": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p]),
     "pp_unit_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
+    "pp_unit_backward_mp": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p,
+                                           c_p]),
+    "pp_unit_backward_path": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "pp_backbone_block_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_block_weights": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_int, c_p]),
     "pp_down_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),

@@ -24,52 +24,18 @@
 // Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
 // order, a plane's segment sums likewise; segments and K ranges of the wgrad depend on the shapes only.  A frame's a, dz, da and du do not
 // depend on the batch it rides in; dw depends on nb within fp32 summation error (the K ranges do).
+// block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp); what both share is in block_train.h.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
+#include "block_train.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr size_t WS_BUDGET = (size_t)256 << 20; // bytes of one frame's a + dz planes: a larger map is refused
-constexpr size_t WS_CHUNK = (size_t)1 << 30;    // bytes of the planes of one chunk of frames: larger batches run in frame chunks
-constexpr int DW_WGS = 512;                     // workgroups a wgrad launch aims at (output tiles x K ranges)
-constexpr int DW_MAX_SPLIT = 256;
-constexpr int DA_BLOCK = 64;                    // k-terms that k_unit_dgrad sums in one accumulator before adding the block to the total
-
-struct block_ws {
-    float* planes = nullptr; size_t planes_elems = 0; // a [fc][C][PS], then dz [fc][C][PS]
-    float* stm = nullptr;    size_t stm_elems = 0;    // [fc][C][2]: mean, rstd as the forward rounds them
-    double* pst = nullptr;   size_t pst_elems = 0;    // [fc][C][segments][2]: a plane's segment sums (statistics, then the norm backward's)
-    float* wT = nullptr;     size_t wT_elems = 0;
-    float* part = nullptr;   size_t part_elems = 0;
-    uint64_t img_gen = 0;    // ctx->commit_gen the position maps belong to (0: none)
-    pp_block_image img[5];
-    int32_t* pmap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t rpn_gen = 0;    // the same for pp_update_rpn_weights: all sixteen 3 x 3 convolutions in execution order
-    pp_block_image rimg[16];
-    int32_t* rpmap[16] = {};
-};
 
 // the Winograd weight transforms' G of pack_layer (F(2x2,3x3)) and wino6_pack (F(4x4,3x3)), the same constant expressions
 __constant__ double kG4[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
 __constant__ double kG6[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                  {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-template <typename T>
-int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need)
-{
-    if (need <= *have) return 0;
-    PP_HIP(hipDeviceSynchronize()); // a kernel of an earlier call, on this stream or another, may still read the old buffer
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *have = 0;
-    PP_HIP(hipMalloc((void**)buf, need * sizeof(T)));
-    *have = need;
-    return 0;
-}
 
 __global__ void __launch_bounds__(256) k_unit_wt(const float* __restrict__ w, float* __restrict__ wT, int C)
 {
@@ -169,22 +135,6 @@ __global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dz
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
-}
-
-// partials added in index order, four loads in flight: 64-thread workgroups, so that a 64 x 64 weight spreads over all compute units
-__global__ void __launch_bounds__(64) k_unit_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const float* p = part + i;
-    double s = 0.0;
-    int g = 0;
-    for (; g + 3 < G; g += 4) {
-        const float a = p[(size_t)g * n], b = p[(size_t)(g + 1) * n], c = p[(size_t)(g + 2) * n], d = p[(size_t)(g + 3) * n];
-        s += (double)a; s += (double)b; s += (double)c; s += (double)d;
-    }
-    for (; g < G; ++g) s += (double)p[(size_t)g * n];
-    dw[i] = (float)s;
 }
 
 // ---- dgrad: a workgroup covers ALL C channels (WM = C / 64 waves down, 4 / WM across), each wave 64 ci x 32 positions, so dz is read
@@ -325,29 +275,13 @@ __global__ void __launch_bounds__(256) k_unit_image(float* __restrict__ dst, con
     dst[i] = (float)(t0 * Gb[0] + t1 * Gb[1] + t2 * Gb[2]);
 }
 
-block_ws* workspace(pp_ctx* ctx)
-{
-    if (!ctx->blk) ctx->blk = new block_ws();
-    return (block_ws*)ctx->blk;
-}
-
-// K ranges of one wgrad launch over `nchunks` 16-position chunks
-void dw_ranges(int tiles, int nchunks, int* splits, int* cps)
-{
-    int sp = DW_WGS / tiles;
-    sp = sp < 1 ? 1 : sp > DW_MAX_SPLIT ? DW_MAX_SPLIT : sp;
-    if (sp > nchunks) sp = nchunks;
-    *cps = (nchunks + sp - 1) / sp;
-    *splits = (nchunks + *cps - 1) / *cps;
-}
-
 } // namespace
 
 void pp_block_destroy(pp_ctx* ctx)
 {
     block_ws* w = (block_ws*)ctx->blk;
     if (!w) return;
-    void* q[] = {w->planes, w->stm, w->pst, w->wT, w->part, w->pmap[0], w->pmap[1], w->pmap[2], w->pmap[3], w->pmap[4]};
+    void* q[] = {w->planes, w->stm, w->pst, w->wT, w->part, w->img16, w->wT16, w->pmap[0], w->pmap[1], w->pmap[2], w->pmap[3], w->pmap[4]};
     for (void* x : q)
         if (x) (void)hipFree(x);
     for (int32_t* x : w->rpmap)

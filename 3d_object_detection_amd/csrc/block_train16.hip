@@ -1,0 +1,477 @@
+// Mixed-precision training (gfx950): the 16-bit operand twins of block_train.hip's Resnet unit backward, pp_unit_backward_mp modes 1
+// "bf16x3" and 2 "bf16".  The two gradient products run on v_mfma_f32_16x16x32_bf16: a lane's A / B fragment is 8 consecutive k of one
+// row / column.  Only the GEMM operand streams are bf16; statistics, mask, norm backward, the dw reduction and every input and output
+// stay fp32.  bf16 (X3 = false) rounds every operand once (round to nearest even); bf16x3 (X3 = true) keeps x = hi + lo, hi = bf16(x),
+// lo = bf16(fl32(x - hi)), as two images and issues hi hi, hi lo, lo hi into the same accumulator in that order.
+//   k_unit_wt16     wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the dgrad's A operand, 8 consecutive co per lane
+//   k_plane_stats   as in block_train.hip (train_planes.h)
+//   k_unit_pack16   mean / rstd by k_unit_pack's expressions; a and dz into padded bf16 planes, 8 positions per thread
+//   k_unit_packT16  zT[P][co]: dz once more with the channel innermost, the dgrad's B operand
+//   k_unit_wgrad16  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      K = frames x PP16 in chunks of 32 positions
+//   k_unit_dgrad16  da[ci][P] = sum_{t, co} wT16[t][ci][co] zT[P - off_t][co]        K = 9 C in steps of 32, blocks of DA_BLOCK = 64
+//   k_plane_gstats_u, k_unit_norm_u  the norm backward with xhat re-evaluated from u (no fp32 image of a is kept)
+//   k_unit_dw_reduce  as in block_train.hip (block_train.h)
+// Plane layout of the 16-bit images: as the fp32 one, with the row pitch wp16 = w + 2 rounded up to a multiple of 8 (the extra
+// columns are halo zeros), G16 = wp16 + 40 and PS16 = 2 G16 + PP16 multiples of 8, so that a k-step of 8 positions starting at a
+// multiple of 8 is one aligned 16-byte load in dz and stays aligned under a row shift (ky - 1) wp16 in a.  The column shift kx - 1 is
+// an odd number of elements: the wgrad loads the aligned 16 bytes and the one dword before or behind them and funnel-shifts the five
+// dwords by 16 bits in registers (v_alignbit_b32), so a is stored once.  The dgrad's B operand is 8 consecutive co at one position: zT,
+// whose tap shift moves by whole rows of C elements.  Per frame that is 3 images of C PS16 bf16 (6 bytes per element against fp32's 8),
+// twice that for bf16x3 (12), so a chunk of frames (<= 1 GB) holds fewer frames under bf16x3 than under fp32: at level 0 (64 channels,
+// 400 x 400, 127 MB per frame) 8 where fp32 holds 12, so nb = 8 still runs as one chunk in every mode and a batch of 9 .. 12 frames
+// splits under bf16x3 only.  That moves the K ranges of dw, not the bits of du.  A frame whose images exceed the 256 MB budget runs the
+// fp32 kernels.
+//
+// Determinism as in block_train.hip: no atomics, K ranges, segments and chunks are functions of the shapes (and the mode) alone.
+#include <cmath>
+#include "pp_common.h"
+#include "train_planes.h"
+#include "block_train.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pk_bf16(float a, float b) // v_cvt_pk_bf16_f32 (round to nearest even), a in the low half
+{
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));
+}
+// the residual the lo image rounds: x - bf16(x), one fp32 subtraction (exact for finite x)
+__device__ __forceinline__ float bf16_rest(float x) { return x - __uint_as_float(pk_bf16(x, 0.f) << 16); }
+__device__ __forceinline__ u32x4 pk8(const float* v) { return u32x4{pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])}; }
+__device__ __forceinline__ u32x4 pk8_rest(const float* v)
+{
+    float r[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r[e] = bf16_rest(v[e]);
+    return pk8(r);
+}
+__device__ __forceinline__ f32x4 mfma16(const u32x4 a, const u32x4 b, const f32x4 c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]
+template <bool X3>
+__global__ void __launch_bounds__(256) k_unit_wt16(const float* __restrict__ w, uint16_t* __restrict__ wT, int C)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][C][C]
+    if (i >= 9 * C * C) return;
+    const int co = i % C, ci = (i / C) % C, t = i / (C * C);
+    const float v = w[((size_t)co * C + ci) * 9 + t];
+    wT[i] = (uint16_t)pk_bf16(v, 0.f);
+    if (X3) wT[(size_t)9 * C * C + i] = (uint16_t)pk_bf16(bf16_rest(v), 0.f);
+}
+
+// ---- a and dz: grid (C, frames, SP), a thread takes groups of 8 positions (one row: wp and G are multiples of 8).  mean and rstd by
+// k_unit_pack's expressions, so the mask is fp32's.  a16, z16: [part][frame][C][PS]; pstride = the elements of one part ----------------
+template <bool X3>
+__global__ void __launch_bounds__(256) k_unit_pack16(const float* __restrict__ u, const float* __restrict__ dy, uint16_t* __restrict__ a16,
+                                                     uint16_t* __restrict__ z16, float* __restrict__ stm, const double* __restrict__ pst, int C, int h,
+                                                     int w, int wp, int G, int PP, int PS, int S, int LG, size_t pstride)
+{
+    const int tid = threadIdx.x, N = h * w;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* dp = dy + pl * N;
+    double s = 0.0, ss = 0.0;
+    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
+    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
+    double var = ss * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
+    if (tid == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    const int ng = PS / 8, lo = blockIdx.z * LG, hi = lo + LG < ng ? lo + LG : ng;
+    for (int g = lo + tid; g < hi; g += 256) {
+        const int j = 8 * g, P = j - G;
+        float av[8], dv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) av[e] = dv[e] = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, x0 = P - y * wp;
+            if (y >= 1 && y <= h) {
+                const int r = (y - 1) * w - 1;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int x = x0 + e;
+                    if (x >= 1 && x <= w) {
+                        const float xhat = (up[r + x] - meanf) * rstdf;
+                        av[e] = xhat > 0.f ? xhat : 0.f;
+                        dv[e] = dp[r + x];
+                    }
+                }
+            }
+        }
+        const size_t o = pl * PS + j;
+        *reinterpret_cast<u32x4*>(a16 + o) = pk8(av);
+        *reinterpret_cast<u32x4*>(z16 + o) = pk8(dv);
+        if (X3) {
+            *reinterpret_cast<u32x4*>(a16 + pstride + o) = pk8_rest(av);
+            *reinterpret_cast<u32x4*>(z16 + pstride + o) = pk8_rest(dv);
+        }
+    }
+}
+
+// ---- zT[part][frame][PS][C]: grid (ceil(PS / 64), C / 64, frames), a 64 position x 64 channel tile through LDS ----------------------
+template <bool X3>
+__global__ void __launch_bounds__(256) k_unit_packT16(const float* __restrict__ dy, uint16_t* __restrict__ zT, int C, int h, int w, int wp, int G,
+                                                      int PP, int PS, size_t pstride)
+{
+    __shared__ float tile[64][65];
+    const int tid = threadIdx.x, N = h * w, c0 = blockIdx.y * 64;
+    const float* df = dy + ((size_t)blockIdx.z * C + c0) * N;
+    {
+        const int p = tid & 63, P = blockIdx.x * 64 + p - G;
+        int idx = -1;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, x = P - y * wp;
+            if (y >= 1 && y <= h && x >= 1 && x <= w) idx = (y - 1) * w + x - 1;
+        }
+#pragma unroll 4
+        for (int c = tid >> 6; c < 64; c += 4) tile[c][p] = idx >= 0 ? df[(size_t)c * N + idx] : 0.f;
+    }
+    __syncthreads();
+    const int cg = tid & 7;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int p = (tid >> 3) + 32 * i, j = blockIdx.x * 64 + p;
+        if (j >= PS) continue;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = tile[8 * cg + e][p];
+        uint16_t* o = zT + ((size_t)blockIdx.z * PS + j) * C + c0 + 8 * cg;
+        *reinterpret_cast<u32x4*>(o) = pk8(v);
+        if (X3) *reinterpret_cast<u32x4*>(o + pstride) = pk8_rest(v);
+    }
+}
+
+// ---- wgrad: workgroup tile (16 MA WR) co x (16 NB WC) columns n = ci 9 + t, four waves WR down x WC = 4 / WR across, a wave MA x NB
+// MFMA tiles.  <4, 4, 2>: 128 x 128 (C >= 128); <3, 4, 1>: 64 x 192 (C = 64: 576 = 3 x 192 columns).  K runs over 32-position chunks of
+// the launch's frames (chunk c: frame c / cpf, positions 32 (c % cpf) ..; positions past PP read guard zeros of dz); a lane takes
+// positions 8 q .. 8 q + 7 of the chunk.  Column n reads a at the row shift (t / 3 - 1) wp as one aligned 16-byte load d, plus the dword
+// e before (kx = 0) or behind (kx = 2) it; the fragment is the five dwords shifted by one element.  blockIdx.z owns chunks
+// [z cps, (z + 1) cps) and writes partial gbase + z in the state_dict layout [co][ci][3][3] -------------------------------------------
+__device__ __forceinline__ u32x4 shift_frag(const u32x4 d, const unsigned e, const int kx)
+{
+    const bool left = kx == 0; // elements P - 1 .. P + 6: e, d0 .. d3; kx = 2: P + 1 .. P + 8: d0 .. d3, e; kx = 1: d
+    const unsigned s0 = left ? e : d[0], s1 = left ? d[0] : d[1], s2 = left ? d[1] : d[2], s3 = left ? d[2] : d[3], s4 = left ? d[3] : e;
+    const unsigned sh = kx == 1 ? 0u : 16u;
+    return u32x4{__builtin_amdgcn_alignbit(s1, s0, sh), __builtin_amdgcn_alignbit(s2, s1, sh), __builtin_amdgcn_alignbit(s3, s2, sh),
+                 __builtin_amdgcn_alignbit(s4, s3, sh)};
+}
+
+template <int NB, int MA, int WR, bool X3>
+__global__ void __launch_bounds__(256) k_unit_wgrad16(const uint16_t* __restrict__ z16, const uint16_t* __restrict__ a16, float* __restrict__ part,
+                                                      int C, int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase, size_t pstride)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    static_assert(WR == 1 || WR == 2, "waves 1 x 4 or 2 x 2");
+    constexpr int WC = 4 / WR;
+    const int co0 = blockIdx.y * (16 * MA * WR) + 16 * MA * (wave / WC), n0 = blockIdx.x * (16 * NB * WC) + 16 * NB * (wave % WC);
+    const int NC = 9 * C;
+    int boff[NB], eoff[NB], kxs[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int n = n0 + 16 * b + l16, ci = n / 9, t = n - 9 * ci;
+        kxs[b] = t % 3;
+        boff[b] = ci * PS + G + (t / 3 - 1) * wp; // < C PS <= 2^27: one frame's images fit the 256 MB budget
+        eoff[b] = kxs[b] == 0 ? -2 : kxs[b] == 2 ? 8 : 0;
+    }
+    f32x4 acc[MA][NB];
+#pragma unroll
+    for (int a = 0; a < MA; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
+    for (int c = c0; c < c1; ++c) {
+        const int f = c / cpf, pb = (c - f * cpf) * 32 + 8 * q;
+        const uint16_t* zf = z16 + (size_t)f * C * PS + G + pb;
+        const uint16_t* af = a16 + (size_t)f * C * PS + pb;
+        u32x4 zh[MA], ah[NB], zl[X3 ? MA : 1], al[X3 ? NB : 1];
+#pragma unroll
+        for (int a = 0; a < MA; ++a) {
+            const uint16_t* r = zf + (size_t)(co0 + 16 * a + l16) * PS;
+            zh[a] = *reinterpret_cast<const u32x4*>(r);
+            if (X3) zl[a] = *reinterpret_cast<const u32x4*>(r + pstride);
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const uint16_t* r = af + boff[b];
+            ah[b] = shift_frag(*reinterpret_cast<const u32x4*>(r), *reinterpret_cast<const unsigned*>(r + eoff[b]), kxs[b]);
+            if (X3) al[b] = shift_frag(*reinterpret_cast<const u32x4*>(r + pstride), *reinterpret_cast<const unsigned*>(r + pstride + eoff[b]), kxs[b]);
+        }
+#pragma unroll
+        for (int a = 0; a < MA; ++a)
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                acc[a][b] = mfma16(zh[a], ah[b], acc[a][b]);
+                if (X3) {
+                    acc[a][b] = mfma16(zh[a], al[b], acc[a][b]);
+                    acc[a][b] = mfma16(zl[a], ah[b], acc[a][b]);
+                }
+            }
+    }
+    float* pw = part + (size_t)(gbase + blockIdx.z) * C * NC;
+#pragma unroll
+    for (int a = 0; a < MA; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
+}
+
+// ---- dgrad: a workgroup covers ALL C channels (WM = C / 64 waves down, 4 / WM across), each wave 64 ci x 64 positions (the weight is
+// re-read once per 64 positions; at 32 it was most of the bytes a workgroup moves).  K = (t, co) in steps of 32 output channels (lane
+// group q takes co + 8 q .. + 7); a block of DA_BLOCK = 64 k-terms is two steps, accumulated from zero, and the block sums are added in
+// (t, co) order.  A = wT16[t][ci][co .. + 7], B = zT[P - off_t][co .. + 7].  Positions past PP read a clamped index and are never stored
+template <int WM, bool X3>
+__global__ void __launch_bounds__(256) k_unit_dgrad16(const uint16_t* __restrict__ wT, const uint16_t* __restrict__ zT, float* __restrict__ da, int C,
+                                                      int h, int w, int wp, int G, int PP, int PS, size_t pstride)
+{
+    constexpr int WN = 4 / WM, NP = 4;
+    static_assert(DA_BLOCK % 32 == 0, "a block is whole k-steps");
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int ci0 = 64 * (wave / WN), p0 = blockIdx.x * (16 * NP * WN) + 16 * NP * (wave % WN);
+    const uint16_t* zf = zT + (size_t)blockIdx.z * PS * C + (size_t)G * C + 8 * q;
+    const size_t wpart = (size_t)9 * C * C;
+    float* daf = da + (size_t)blockIdx.z * C * h * w;
+    f32x4 tot[4][NP];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < NP; ++b) tot[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int ip[NP];
+#pragma unroll
+    for (int b = 0; b < NP; ++b) ip[b] = p0 + 16 * b + l16 < PP ? p0 + 16 * b + l16 : 0;
+    for (int t = 0; t < 9; ++t) {
+        const int off = (t / 3 - 1) * wp + (t % 3 - 1);
+        const uint16_t* wt_t = wT + ((size_t)t * C + ci0 + l16) * C + 8 * q;
+        const uint16_t* zp[NP];
+#pragma unroll
+        for (int b = 0; b < NP; ++b) zp[b] = zf + (ptrdiff_t)(ip[b] - off) * C;
+        for (int cb0 = 0; cb0 < C; cb0 += DA_BLOCK) { // C is a multiple of DA_BLOCK
+            f32x4 acc[4][NP];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < NP; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int cb = cb0; cb < cb0 + DA_BLOCK; cb += 32) {
+                u32x4 wh[4], zh[NP], wl[X3 ? 4 : 1], zl[X3 ? NP : 1];
+#pragma unroll
+                for (int b = 0; b < NP; ++b) {
+                    zh[b] = *reinterpret_cast<const u32x4*>(zp[b] + cb);
+                    if (X3) zl[b] = *reinterpret_cast<const u32x4*>(zp[b] + cb + pstride);
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    wh[a] = *reinterpret_cast<const u32x4*>(wt_t + (size_t)16 * a * C + cb);
+                    if (X3) wl[a] = *reinterpret_cast<const u32x4*>(wt_t + (size_t)16 * a * C + cb + wpart);
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < NP; ++b) {
+                        acc[a][b] = mfma16(wh[a], zh[b], acc[a][b]);
+                        if (X3) {
+                            acc[a][b] = mfma16(wh[a], zl[b], acc[a][b]);
+                            acc[a][b] = mfma16(wl[a], zh[b], acc[a][b]);
+                        }
+                    }
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < NP; ++b) tot[a][b] += acc[a][b];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NP; ++b) {
+        const int P = p0 + 16 * b + l16;
+        if (P >= PP) continue;
+        const int y = P / wp, x = P - y * wp;
+        if (y < 1 || y > h || x < 1 || x > w) continue;
+        float* o = daf + (size_t)(y - 1) * w + x - 1;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[(size_t)(ci0 + 16 * a + 4 * q + i) * h * w] = tot[a][b][i];
+    }
+}
+
+// ---- norm backward without an fp32 image of a: xhat by k_unit_pack's expression from u and the stored mean / rstd; xhat > 0 is the
+// mask a > 0 and, where it holds, xhat is a.  Same segments, same order of the sums as k_plane_gstats / k_unit_norm ---------------------
+__global__ void __launch_bounds__(256) k_plane_gstats_u(const float* __restrict__ u, const float* __restrict__ stm, const float* __restrict__ du,
+                                                        double* __restrict__ pst, int C, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* dp = du + pl * N;
+    const float meanf = stm[pl * 2], rstdf = stm[pl * 2 + 1];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sg = 0.0, sgx = 0.0;
+    strided4(lo, hi, [&](int i) { return float2{up[i], dp[i]}; },
+             [&](float2 v) {
+                 const float xhat = (v.x - meanf) * rstdf;
+                 if (xhat > 0.f) {
+                     const double g = (double)v.y;
+                     sg += g; sgx += g * (double)xhat;
+                 }
+             });
+    block_sum2(sg, sgx, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sg; pst[(pl * S + blockIdx.z) * 2 + 1] = sgx; }
+}
+
+__global__ void __launch_bounds__(256) k_unit_norm_u(const float* __restrict__ u, const float* __restrict__ stm, const double* __restrict__ pst,
+                                                     const float* __restrict__ dskip, float* __restrict__ du, int C, int N, int L, int S)
+{
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    float* dp = du + pl * N;
+    const float meanf = stm[pl * 2], rstdf = stm[pl * 2 + 1];
+    double sg = 0.0, sgx = 0.0;
+    for (int g = 0; g < S; ++g) { sg += pst[(pl * S + g) * 2]; sgx += pst[(pl * S + g) * 2 + 1]; }
+    const double inv_n = 1.0 / (double)N;
+    const float c1 = (float)(sg * inv_n), c2 = (float)(sgx * inv_n);
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    for (int i = lo + tid; i < hi; i += 256) {
+        const float xhat = (up[i] - meanf) * rstdf;
+        const float g = xhat > 0.f ? dp[i] : 0.f;
+        float v = rstdf * ((g - c1) - xhat * c2);
+        if (dskip) v = v + dskip[pl * N + i];
+        dp[i] = v;
+    }
+}
+
+
+// geometry of the 16-bit planes
+struct geom16 { int64_t wp, PP, G, PS; };
+inline geom16 planes16(int h, int w)
+{
+    geom16 g;
+    g.wp = ((int64_t)w + 2 + 7) & ~(int64_t)7;
+    g.PP = ((int64_t)h + 2) * g.wp;
+    g.G = g.wp + 40;
+    g.PS = 2 * g.G + g.PP;
+    return g;
+}
+// bytes of one frame's 16-bit images: a, dz and zT, each of `parts` bf16 images
+inline uint64_t frame16_bytes(int parts, int C, const geom16& g) { return (uint64_t)3 * parts * C * (uint64_t)g.PS * sizeof(uint16_t); }
+
+// the checks of pp_unit_backward that do not depend on the tensors
+int unit_shape_check(pp_ctx* ctx, int C, int h, int w)
+{
+    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
+    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: C must be 64, 128 or 256");
+    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: h, w >= 1 and h w >= 2");
+    return 0;
+}
+
+template <bool X3>
+int unit_backward16(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip, int nb, float* dw,
+                    float* du, hipStream_t stream)
+{
+    const geom16 g = planes16(h, w);
+    const int wp = (int)g.wp, PP = (int)g.PP, G = (int)g.G, PS = (int)g.PS, N = h * w, parts = X3 ? 2 : 1;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: functions of the shapes and the mode alone
+    const size_t pf_elems = (size_t)C * PS;
+    int fc = (int)(WS_CHUNK / frame16_bytes(parts, C, g));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int TN = C >= 128 ? 128 : 192, TM = C >= 128 ? 128 : 64; // a wgrad tile: k_unit_wgrad16<4, 4, 2> or <3, 4, 1>
+    const int NC = 9 * C, tiles = (NC / TN) * (C / TM), cpf = (PP + 31) / 32;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = C * NC;
+    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LG = (PS / 8 + SP - 1) / SP;
+    const size_t pstride = (size_t)fc * pf_elems; // one part of one image over the chunk's frames
+    int rc;
+    if ((rc = grow(ctx, &ws->img16, &ws->img16_elems, 3 * parts * pstride)) ||
+        (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)fc * C * 2)) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)fc * C * SEG_MAX * 2)) ||
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (du && (rc = grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)parts * nw))))
+        return rc;
+    uint16_t* a16 = ws->img16;                       // [part][fc][C][PS]
+    uint16_t* z16 = a16 + parts * pstride;           // [part][fc][C][PS]
+    uint16_t* zT = z16 + parts * pstride;            // [part][fc][PS][C]
+    if (du) hipLaunchKernelGGL(k_unit_wt16<X3>, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT16, C);
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t o = (size_t)f0 * C * N;
+        hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->pst, C, N, L, S);
+        hipLaunchKernelGGL(k_unit_pack16<X3>, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, a16, z16, ws->stm, ws->pst, C, h, w, wp, G, PP, PS, S,
+                           LG, pstride);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / TN, C / TM, sp);
+        if (C >= 128)
+            hipLaunchKernelGGL((k_unit_wgrad16<4, 4, 2, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase, pstride);
+        else
+            hipLaunchKernelGGL((k_unit_wgrad16<3, 4, 1, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase, pstride);
+        gbase += sp;
+        if (du) {
+            float* duc = du + o;
+            hipLaunchKernelGGL(k_unit_packT16<X3>, dim3(pp_div_up(PS, 64), C / 64, fn), dim3(256), 0, stream, dy + o, zT, C, h, w, wp, G, PP, PS, pstride);
+            if (C == 64)
+                hipLaunchKernelGGL((k_unit_dgrad16<1, X3>), dim3(pp_div_up(PP, 256), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
+            else if (C == 128)
+                hipLaunchKernelGGL((k_unit_dgrad16<2, X3>), dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
+            else
+                hipLaunchKernelGGL((k_unit_dgrad16<4, X3>), dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
+            hipLaunchKernelGGL(k_plane_gstats_u, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->stm, duc, ws->pst, C, N, L, S);
+            hipLaunchKernelGGL(k_unit_norm_u, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->stm, ws->pst, dskip ? dskip + o : nullptr, duc, C, N, L, S);
+        }
+    }
+    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// the mode pp_unit_backward_mp runs for a valid shape: the 16-bit tiling takes every C and map whose images fit the frame budget
+int unit_path(int mode, int C, int h, int w)
+{
+    if (mode == 0) return 0;
+    return frame16_bytes(mode == 1 ? 2 : 1, C, planes16(h, w)) <= WS_BUDGET ? mode : 0;
+}
+
+} // namespace
+
+extern "C" int pp_unit_backward_path(pp_ctx* ctx, int mode, int C, int h, int w)
+{
+    if (!ctx) return -PP_E_ARG; // the modes are 0 .. 2, so an error is the negated code
+    if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, "pp_unit_backward_path: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
+    int rc = unit_shape_check(ctx, C, h, w);
+    if (rc) return -rc;
+    return unit_path(mode, C, h, w);
+}
+
+extern "C" int pp_unit_backward_mp(pp_ctx* ctx, int mode, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip,
+                                   int nb, float* dw, float* du, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_mp: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
+    int rc = unit_shape_check(ctx, C, h, w);
+    if (rc) return rc;
+    const int path = unit_path(mode, C, h, w);
+    if (path == 0) return pp_unit_backward(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, stream_);
+    if (!u || !wgt || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: null pointer");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: nb must be 1 .. max_batch");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: w must be 16-byte aligned");
+    if (((uintptr_t)u | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw | (uintptr_t)du) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: tensors must be 4-byte aligned");
+    return path == 1 ? unit_backward16<true>(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, (hipStream_t)stream_)
+                     : unit_backward16<false>(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, (hipStream_t)stream_);
+}

@@ -479,10 +479,30 @@ class Engine:
     BLOCK3_KEYS = ("rpn.block3.3.conv_block.2.weight", "rpn.block3.3.conv_block.5.weight", "rpn.block3.4.conv_block.2.weight",
                    "rpn.block3.4.conv_block.5.weight", "rpn.block3.5.conv_block.2.weight")
 
-    def unit_backward(self, u, w, dy, dskip=None, need_du=True):
-        """pp_unit_backward: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
+    GRAD_PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2}  # pp_unit_backward_mp's modes: the numbering of pp_set_precision
+
+    @classmethod
+    def _grad_mode(cls, grad_precision, who):
+        if grad_precision not in cls.GRAD_PRECISIONS:
+            raise ValueError(f"{who}: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
+        return cls.GRAD_PRECISIONS[grad_precision]
+
+    def unit_backward_path(self, grad_precision, C, h, w):
+        """pp_unit_backward_path: the precision unit_backward(grad_precision=...) really runs at this shape: grad_precision, or "fp32"
+        where no 16-bit tiling takes the shape."""
+        mode = self._grad_mode(grad_precision, "unit_backward_path")
+        rc = self.lib.pp_unit_backward_path(self.ctx, mode, int(C), int(h), int(w))
+        if rc < 0:
+            _lib.check(-rc, self.ctx, "pp_unit_backward_path")
+        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+
+    def unit_backward(self, u, w, dy, dskip=None, need_du=True, grad_precision="fp32"):
+        """pp_unit_backward_mp: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
         dy (dL/d(conv output)) and the optional dskip (added to du: the residual path around the unit) are [nb,C,h,w], w [C,C,3,3] ->
-        (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  fp32, deterministic, stateless."""
+        (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  Deterministic, stateless.  grad_precision:
+        "fp32" (pp_unit_backward, bit for bit), "bf16x3" or "bf16": the operands of the two gradient products in split or plain bf16 on
+        the bf16 MFMA, everything else (tensors, statistics, mask, norm backward) fp32."""
+        mode = self._grad_mode(grad_precision, "unit_backward")
         if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
             raise ValueError(f"unit_backward: u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, C, h, wd = (int(v) for v in u.shape)
@@ -505,8 +525,8 @@ class Engine:
         dw = self._t((C, C, 3, 3), torch.float32)
         du = self._t((nb, C, h, wd), torch.float32) if need_du else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_unit_backward(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(dy), _ptr(dskip), nb, _ptr(dw), _ptr(du), _stream()),
-                       self.ctx, "pp_unit_backward")
+            _lib.check(self.lib.pp_unit_backward_mp(self.ctx, mode, C, h, wd, _ptr(u), _ptr(w), _ptr(dy), _ptr(dskip), nb, _ptr(dw), _ptr(du),
+                                                    _stream()), self.ctx, "pp_unit_backward_mp")
         return dw, du
 
     def backbone_block_taps(self, canvas):

@@ -24,7 +24,11 @@ reference, in its state_dict order) and follows the reference's train.py, whose 
 statistics: every training-mode forward runs pp_pfn_train_forward over the pillars of all frames of the batch (_PfnFunction), moves
 running_mean / running_var (momentum 0.1, unbiased variance) and counts num_batches_tracked, whether or not grad is enabled.  The
 backward consumes the canvases' gradient: pp_scatter_backward per frame, then one pp_pfn_backward (csrc/pfn_train.hip).  The eval-mode
-PFN of the engine (running statistics folded into scale / shift) is rewritten by pp_update_pfn_weights before it is next used."""
+PFN of the engine (running statistics folded into scale / shift) is rewritten by pp_update_pfn_weights before it is next used.
+
+Mixed precision: train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
+or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
+backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit."""
 import time
 import types
 
@@ -53,6 +57,7 @@ RPN_KEYS = tuple(k for b in range(3) for k in RPN_CONV_KEYS[(0, 4, 10)[b]:(4, 10
 _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in BLOCK3_KEYS)  # what the narrower scopes never train
 ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
 SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
+GRAD_PRECISIONS = ("fp32", "bf16x3", "bf16")  # train(grad_precision=...): the operands of the unit backwards' gradient products
 # the scopes that train: the upsamplers; block 3's units; block 3's strided convolution; blocks 1 and 2; the pillar feature net
 _NECK_SCOPES, _BLOCK_SCOPES, _STAGE_SCOPES, _RPN_SCOPES = SCOPES[1:], SCOPES[2:], SCOPES[3:], SCOPES[4:]
 
@@ -107,8 +112,8 @@ class _BlockFunction(torch.autograd.Function):
     convolution behind it stays frozen."""
 
     @staticmethod
-    def forward(ctx, eng, canvases, *weights):
-        ctx.eng = eng
+    def forward(ctx, eng, prec, canvases, *weights):
+        ctx.eng, ctx.prec = eng, prec
         outs = [eng.backbone_block_taps(c) for c in canvases]
         y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
         units = [torch.stack([o[4][k] for o in outs]) for k in range(5)]  # h, m3, r3, m4, r4, each [nb,256,H/4,W/4]
@@ -119,8 +124,8 @@ class _BlockFunction(torch.autograd.Function):
     def backward(ctx, gy):
         y, *rest = ctx.saved_tensors
         taps, units, wb, wn = rest[:3], rest[3:8], rest[8:13], rest[13:16]
-        eng, gy = ctx.eng, gy.contiguous()
-        need_b, need_n = ctx.needs_input_grad[2:7], ctx.needs_input_grad[7:10]
+        eng, prec, gy = ctx.eng, ctx.prec, gy.contiguous()
+        need_b, need_n = ctx.needs_input_grad[3:8], ctx.needs_input_grad[8:11]
         dwn = [None] * 3
         g = None
         for b in range(3):
@@ -133,13 +138,13 @@ class _BlockFunction(torch.autograd.Function):
         dwb = [None] * 5
         if any(need_b):
             h, m3, r3, m4, r4 = units
-            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g)
-            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4)
-            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4)
-            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3)
-            dwb[0], _ = eng.unit_backward(h, wb[0], g_m3, need_du=False)
+            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g, grad_precision=prec)
+            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4, grad_precision=prec)
+            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4, grad_precision=prec)
+            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3, grad_precision=prec)
+            dwb[0], _ = eng.unit_backward(h, wb[0], g_m3, need_du=False, grad_precision=prec)
             dwb = [d if n else None for d, n in zip(dwb, need_b)]
-        return (None, None) + tuple(dwb) + tuple(dwn)
+        return (None, None, None) + tuple(dwb) + tuple(dwn)
 
 
 class _StageFunction(torch.autograd.Function):
@@ -148,8 +153,8 @@ class _StageFunction(torch.autograd.Function):
     of the stride-2 convolution.  Block 2's output gets no gradient: nothing in front of the stage trains."""
 
     @staticmethod
-    def forward(ctx, eng, canvases, w0, *weights):
-        ctx.eng = eng
+    def forward(ctx, eng, prec, canvases, w0, *weights):
+        ctx.eng, ctx.prec = eng, prec
         outs = [eng.backbone_stage_taps(c) for c in canvases]
         y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
         units = [torch.stack([o[4][k] for o in outs]) for k in range(5)]
@@ -161,8 +166,8 @@ class _StageFunction(torch.autograd.Function):
     def backward(ctx, gy):
         y, *rest = ctx.saved_tensors
         taps, units, z3, w0, wb, wn = rest[:3], rest[3:8], rest[8], rest[9], rest[10:15], rest[15:18]
-        eng, gy = ctx.eng, gy.contiguous()
-        need_0, need_b, need_n = ctx.needs_input_grad[2], ctx.needs_input_grad[3:8], ctx.needs_input_grad[8:11]
+        eng, prec, gy = ctx.eng, ctx.prec, gy.contiguous()
+        need_0, need_b, need_n = ctx.needs_input_grad[3], ctx.needs_input_grad[4:9], ctx.needs_input_grad[9:12]
         deep = need_0 or any(need_b)
         dwn = [None] * 3
         g = None
@@ -176,29 +181,30 @@ class _StageFunction(torch.autograd.Function):
         dwb, dw0 = [None] * 5, None
         if deep:
             h, m3, r3, m4, r4 = units
-            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g)
-            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4)
-            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4)
-            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3)
-            dwb[0], g_h = eng.unit_backward(h, wb[0], g_m3, dskip=g_r3, need_du=need_0)
+            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g, grad_precision=prec)
+            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4, grad_precision=prec)
+            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4, grad_precision=prec)
+            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3, grad_precision=prec)
+            dwb[0], g_h = eng.unit_backward(h, wb[0], g_m3, dskip=g_r3, need_du=need_0, grad_precision=prec)
             dwb = [d if n else None for d, n in zip(dwb, need_b)]
             if need_0:
                 dw0, _ = eng.down_backward(taps[1], w0, z3, g_h, need_dx=False)
-        return (None, None, dw0) + tuple(dwb) + tuple(dwn)
+        return (None, None, None, dw0) + tuple(dwb) + tuple(dwn)
 
 
-def rpn_block_backward(eng, modules, units, weights, g):
+def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32"):
     """The backward of one block's Resnet modules (a row of RPN_TABLE): units and weights in unit order, g = dL/d(block output) ->
-    (dw per unit, dL/d(block input h))."""
+    (dw per unit, dL/d(block input h)).  grad_precision: the operand precision of every unit backward (Engine.unit_backward)."""
+    prec = grad_precision
     dws = [None] * len(units)
     i = len(units)
     for n in reversed(modules):
         i -= n
         if n == 2:
-            dws[i + 1], gm = eng.unit_backward(units[i + 1], weights[i + 1], g)
-            dws[i], g = eng.unit_backward(units[i], weights[i], gm, dskip=g)
+            dws[i + 1], gm = eng.unit_backward(units[i + 1], weights[i + 1], g, grad_precision=prec)
+            dws[i], g = eng.unit_backward(units[i], weights[i], gm, dskip=g, grad_precision=prec)
         else:
-            dws[i], g = eng.unit_backward(units[i], weights[i], g, dskip=g)
+            dws[i], g = eng.unit_backward(units[i], weights[i], g, dskip=g, grad_precision=prec)
     return dws, g
 
 
@@ -210,8 +216,8 @@ class _RpnFunction(torch.autograd.Function):
     require grad."""
 
     @staticmethod
-    def forward(ctx, eng, x, *weights):
-        ctx.eng = eng
+    def forward(ctx, eng, prec, x, *weights):
+        ctx.eng, ctx.prec = eng, prec
         outs = [eng.backbone_train_taps(c) for c in x]
         y = torch.cat([o[0] for o in outs])
         taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
@@ -225,7 +231,7 @@ class _RpnFunction(torch.autograd.Function):
         x, y, *rest = ctx.saved_tensors
         taps, units, zs, wc, wn = rest[:3], rest[3:16], rest[16:19], rest[19:35], rest[35:38]
         eng, gy = ctx.eng, gy.contiguous()
-        need = ctx.needs_input_grad
+        need = ctx.needs_input_grad[1:]  # [1] the canvases, [2 + i] weight i
         dwn, dxn = zip(*[eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=True) for b in range(3)])
         dwc = [None] * 16
         g = None
@@ -233,10 +239,10 @@ class _RpnFunction(torch.autograd.Function):
             n, w0 = sum(mods), (0, 4, 10)[b]  # the level's strided convolution in RPN_CONV_KEYS; its units follow
             u0 = w0 - b
             g = dxn[b] if g is None else dxn[b] + g
-            dwc[w0 + 1:w0 + 1 + n], gh = rpn_block_backward(eng, mods, units[u0:u0 + n], wc[w0 + 1:w0 + 1 + n], g)
+            dwc[w0 + 1:w0 + 1 + n], gh = rpn_block_backward(eng, mods, units[u0:u0 + n], wc[w0 + 1:w0 + 1 + n], g, ctx.prec)
             dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=b > 0 or need[1])
         grads = [d if need[2 + i] else None for i, d in enumerate(list(dwc) + list(dwn))]
-        return (None, g if need[1] else None) + tuple(grads)
+        return (None, None, g if need[1] else None) + tuple(grads)
 
 
 class _PfnFunction(torch.autograd.Function):
@@ -271,6 +277,7 @@ class _PfnFunction(torch.autograd.Function):
 
 class PointPillars:
     _norm = "instance"
+    grad_precision = "fp32"
     # read-only defaults for an object assembled without __init__ (no engine: the key-order tests); __init__ and load_state_dict
     # give every object its own
     _block, _block_uploaded, _block_trained = types.MappingProxyType({}), None, False
@@ -320,7 +327,7 @@ class PointPillars:
     def eval(self):
         return self.train(False)
 
-    def train(self, mode=True, scope="head"):
+    def train(self, mode=True, scope="head", grad_precision="fp32"):
         """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
         trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
         block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
@@ -328,7 +335,12 @@ class PointPillars:
         well); PFN and scatter stay frozen.  scope="all" trains the pillar feature net too (ALL_KEYS, what net.parameters() yields
         in the reference): the training-mode forward then normalises the PFN with batch statistics and moves the running ones, as the
         reference's net.train() does.  eval() / train(False) restores the inference behaviour, with the PFN's current parameters and
-        running statistics folded into the engine."""
+        running statistics folded into the engine.
+        grad_precision ("fp32" | "bf16x3" | "bf16", kept as net.grad_precision, "fp32" again after eval()): the operand precision of
+        the Resnet units' gradient products (pp_unit_backward_mp), in effect under the scopes that run them ("block3", "stage3", "rpn",
+        "all") and inert under "head" and "neck".  The forward, the strided stages, the upsamplers, the head and the PFN stay fp32."""
+        if grad_precision not in GRAD_PRECISIONS:
+            raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         if scope not in SCOPES:
             raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
         if mode and scope != "head" and (self._norm != "instance" or len(self._neck) != 3 or
@@ -339,6 +351,7 @@ class PointPillars:
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only")
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
+        self.grad_precision = grad_precision if self.training else "fp32"
         for p in self._params.values():
             p.requires_grad_(self.training)
         for p in self._neck.values():
@@ -672,12 +685,12 @@ class PointPillars:
                                "(gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place); call float()")
         if whole:
             every = {**self._rpn, **self._down, **self._block}
-            return _RpnFunction.apply(eng, x, *[every[k] for k in RPN_CONV_KEYS], *[self._neck[k] for k in NECK_KEYS])
+            return _RpnFunction.apply(eng, self.grad_precision, x, *[every[k] for k in RPN_CONV_KEYS], *[self._neck[k] for k in NECK_KEYS])
         if stage:
-            return _StageFunction.apply(eng, list(x), self._down[STAGE3_KEY], *[self._block[k] for k in BLOCK3_KEYS],
+            return _StageFunction.apply(eng, self.grad_precision, list(x), self._down[STAGE3_KEY], *[self._block[k] for k in BLOCK3_KEYS],
                                         *[self._neck[k] for k in NECK_KEYS])
         if block:
-            return _BlockFunction.apply(eng, list(x), *[self._block[k] for k in BLOCK3_KEYS], *[self._neck[k] for k in NECK_KEYS])
+            return _BlockFunction.apply(eng, self.grad_precision, list(x), *[self._block[k] for k in BLOCK3_KEYS], *[self._neck[k] for k in NECK_KEYS])
         return _NeckFunction.apply(eng, list(x), *[self._neck[k] for k in NECK_KEYS])
 
     def heads(self, x):

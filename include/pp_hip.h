@@ -339,6 +339,26 @@ int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const 
  * backbone. */
 int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip /* may be NULL */,
                      int nb, float* dw, float* du /* NULL: skipped */, void* stream);
+/* pp_unit_backward with 16-bit GEMM operands: mixed-precision training.  mode follows the numbering of pp_set_precision: 0 fp32 (exactly
+ * pp_unit_backward, bit for bit), 1 "bf16x3" (every operand of the two products split as x = hi + lo, hi = bf16(x), lo = bf16(x - hi),
+ * round to nearest even; a product is hi hi + hi lo + lo hi, issued in that order into one fp32 accumulator: relative error 3 x 2^-16
+ * per product), 2 "bf16" (every operand rounded once: 2^-7 per product).  Both run on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.
+ * Only the operand streams of the wgrad and dgrad products are 16-bit: u, w, dy, dskip, dw and du are fp32 as above, and so are the
+ * statistics (fp64 sums), the ReLU mask (that of the fp32 xhat: rounding a positive fp32 to bf16 never gives 0), the norm backward, the
+ * reduction of the dw partials in double and the dskip add.  bf16 has fp32's exponent range: no loss scaling.  Stateless as
+ * pp_unit_backward: neither pp_set_precision nor the committed plan is read.  Deterministic in the same sense: no atomics, two runs
+ * are bit-identical, a frame's du does not depend on nb, dw depends on nb through the fixed K ranges only.  The 16-bit images (a, dz,
+ * and dz once more with the channel innermost; a hi and a lo image of each under bf16x3) live in the same workspace under the same
+ * rules: a chunk of frames takes at most 1 GB, so a batch may run in more chunks than under fp32; a shape whose single frame would
+ * take more than 256 MB runs the fp32 kernels instead (pp_unit_backward_path tells).  The dgrad keeps the blocked sum: 64 k-terms from
+ * zero, block sums added in (tap, co) order.
+ * PP_E_ARG as pp_unit_backward, and for a mode outside 0..2. */
+int pp_unit_backward_mp(pp_ctx* ctx, int mode, int C, int h, int w, const float* u, const float* wgt, const float* dy,
+                        const float* dskip /* may be NULL */, int nb, float* dw, float* du /* NULL: skipped */, void* stream);
+/* The mode pp_unit_backward_mp really runs for this shape: `mode`, or 0 where no 16-bit tiling takes the shape.  Launches nothing.
+ * An error is negative: -PP_E_ARG for a null context, a mode outside 0..2, C outside the three, h or w out of range and the BatchNorm
+ * backbone. */
+int pp_unit_backward_path(pp_ctx* ctx, int mode, int C, int h, int w);
 /* pp_backbone_taps plus the inputs of the five units of block 3 (the deepest block: h -> r3 = h + U_b(U_a(h)), r4 = r3 + U_d(U_c(r3)),
  * x3 = r4 + U_e(r4), weights rpn.block3.{3,3,4,4,5}.conv_block.{2,5,2,5,2}.weight): units f32[5][256][H/4][W/4] = h, m3 = U_a(h), r3,
  * m4 = U_c(r3), r4, each copied out behind the launch that produces it (the level buffers are reused inside a block).  rpn_out, x1, x2

@@ -7,12 +7,18 @@ over_floor divided by that of the same kernel at block 3's shape in the same run
 `--windows` event windows of `--reps` calls each; the three levels take turns window by window, so a drift of the clocks reaches all of
 them, and every row carries its windows' min and max and `vs_block3_worst` = (its slowest window) / (block 3's fastest).
 
-    python tools/rpntrain_probe.py [--frames 1,8] [--reps 20] [--windows 7]
+Mixed precision: pp_unit_backward_mp is timed per `--grad-precision` mode (default all three) at the same shapes, the modes taking
+turns window by window as well.  A mode's floor is the flops its MFMAs execute over its own padded plane / its rate: fp32 157.3 TF,
+bf16 and bf16x3 2.5 PF (the bf16 MFMA roof), bf16x3 executing three MFMAs per product.  `vs_fp32` is median / fp32's median and
+`ships` whether the mode's slowest window beats fp32's fastest (the condition for pp_unit_backward_path to hand the shape to it).
+
+    python tools/rpntrain_probe.py [--frames 1,8] [--reps 20] [--windows 7] [--grad-precision fp32,bf16x3,bf16]
     rocprofv3 --kernel-trace --stats -d OUT -o rpntrain -- python tools/rpntrain_probe.py --frames 8 --no-step   (per-kernel split)
 
 Also in the same run: pp_update_rpn_weights, pp_backbone_train_taps against pp_backbone_stage_taps, whole fine-tuning steps at nb = 8
-under scope "rpn" and "stage3", alternated (per-frame forward, head, loss, backward, SGD step, weight upload), and the device memory
-the tensors saved for the backward take per frame under scope "rpn".  Prints one JSON line."""
+under scope "rpn" and "stage3", alternated (per-frame forward, head, loss, backward, SGD step, weight upload), the same step under
+scope "rpn" per grad-precision mode, alternated, and the device memory the tensors saved for the backward take per frame under scope
+"rpn".  Prints one JSON line."""
 import argparse
 import ctypes
 import importlib
@@ -25,6 +31,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 MFMA_FS = 157.3e12
+BF16_FS = 2.5e15  # the bf16 MFMA roof
+MODES = {"fp32": 0, "bf16x3": 1, "bf16": 2}
 
 
 def main():
@@ -33,7 +41,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--no-step", action="store_true", help="skip the whole-step lines")
+    ap.add_argument("--grad-precision", default="fp32,bf16x3,bf16", help="modes of pp_unit_backward_mp to time")
     a = ap.parse_args()
+    modes = [m for m in a.grad_precision.split(",") if m]
+    assert modes and all(m in MODES for m in modes), a.grad_precision
     frames = [int(v) for v in a.frames.split(",")]
     pkg = importlib.import_module("3d_object_detection_amd")
     pkg.install()
@@ -80,12 +91,17 @@ def main():
             keep = (wu, w0, x, z, dy, dwu, dw0, du, dx)
             unit = lambda C=C, h=h, w=w, z=z, wu=wu, dy=dy, dwu=dwu, du=du: lib.pp_unit_backward(  # noqa: E731
                 ctx, C, h, w, ptr(z), ptr(wu), ptr(dy), ptr(dy), nb, ptr(dwu), ptr(du), st)
+            mp = {m: (lambda C=C, h=h, w=w, z=z, wu=wu, dy=dy, dwu=dwu, du=du, m=m: lib.pp_unit_backward_mp(  # noqa: E731
+                ctx, MODES[m], C, h, w, ptr(z), ptr(wu), ptr(dy), ptr(dy), nb, ptr(dwu), ptr(du), st)) for m in modes}
+            for m in modes:
+                assert lib.pp_unit_backward_path(ctx, MODES[m], C, h, w) == MODES[m], (m, C, h, w)
             down = lambda C=C, cin=cin, h=h, w=w, x=x, w0=w0, z=z, dy=dy, dw0=dw0, dx=dx: lib.pp_down_backward(  # noqa: E731
                 ctx, cin, C, 2 * h, 2 * w, ptr(x), ptr(w0), ptr(z), ptr(dy), nb, ptr(dw0), ptr(dx), st)
-            calls[b] = dict(unit=unit, down=down, keep=keep, ms=dict(unit=[], down=[]))
+            calls[b] = dict(unit=unit, down=down, keep=keep, ms=dict(unit=[], down=[]), **{"mp_" + m: f for m, f in mp.items()})
+            calls[b]["ms"].update({"mp_" + m: [] for m in modes})
         for win in range(a.windows + 1):  # the first round warms up (workspaces grow, clocks rise) and is dropped
             for b in (2, 1, 0):
-                for k in ("unit", "down"):
+                for k in ["unit", "down"] + ["mp_" + m for m in modes]:
                     t = timed(calls[b][k])
                     if win:
                         calls[b]["ms"][k].append(t)
@@ -94,6 +110,10 @@ def main():
             PP = (h + 2) * (w + 2)  # positions a product executes per frame: the zero-haloed plane
             fl = dict(unit=2 * 2.0 * C * 9 * C * PP * nb / MFMA_FS * 1e3, down=2 * 2.0 * C * 9 * cin * PP * nb / MFMA_FS * 1e3)
             sh = dict(unit=[C, h, w], down=[cin, C, 2 * h, 2 * w])
+            PP16 = (h + 2) * ((w + 2 + 7) // 8 * 8)  # the 16-bit planes pad the row pitch to a multiple of 8
+            for m in modes:
+                fl["mp_" + m] = (fl["unit"] if m == "fp32" else (3 if m == "bf16x3" else 1) * 2 * 2.0 * C * 9 * C * PP16 * nb / BF16_FS * 1e3)
+                sh["mp_" + m] = [C, h, w]
             rows[b] = {k: dict(shape=sh[k], ms=med(v), ms_min=min(v), ms_max=max(v), floor_ms=fl[k], over_floor=med(v) / fl[k])
                        for k, v in calls[b]["ms"].items()}
         for b in (0, 1, 2):
@@ -101,6 +121,12 @@ def main():
                 r, r3 = rows[b][k], rows[2][k]
                 out["rows"].append(dict(frames=nb, call=k + "_backward", level=b, **r, vs_block3=r["over_floor"] / r3["over_floor"],
                                         vs_block3_worst=(r["ms_max"] / r["floor_ms"]) / (r3["ms_min"] / r3["floor_ms"])))
+        for b in (0, 1, 2):
+            f32 = rows[b].get("mp_fp32")
+            for m in modes:
+                r = rows[b]["mp_" + m]
+                extra = dict(vs_fp32=r["ms"] / f32["ms"], ships=r["ms_max"] < f32["ms_min"]) if f32 and m != "fp32" else {}
+                out["rows"].append(dict(frames=nb, call="unit_backward_mp", grad_precision=m, level=b, **r, **extra))
         del calls
         torch.cuda.empty_cache()
     keys = eng.RPN_CONV_KEYS
@@ -160,6 +186,12 @@ def main():
                 opt = torch.optim.SGD(net.parameters(), lr=1e-3)
                 step(opt)
                 out.setdefault("step_nb8_" + scope, []).append(step(opt))
+        for rnd in range(3):  # the whole "rpn" step per grad-precision mode, alternated
+            for m in modes:
+                net.train(scope="rpn", grad_precision=m)
+                opt = torch.optim.SGD(net.parameters(), lr=1e-3)
+                step(opt)
+                out.setdefault("step_nb8_rpn_" + m, []).append(step(opt))
         # what the forward keeps for the backward, per frame
         net.train(scope="rpn")
         torch.cuda.synchronize()
