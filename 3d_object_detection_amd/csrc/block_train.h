@@ -22,12 +22,11 @@ struct block_ws {
     float* part = nullptr;   size_t part_elems = 0;
     uint16_t* img16 = nullptr; size_t img16_elems = 0; // the 16-bit operand images of pp_unit_backward_mp (block_train16.hip)
     uint16_t* wT16 = nullptr;  size_t wT16_elems = 0;  // [part][9][ci][co] bf16
-    uint64_t img_gen = 0;    // ctx->commit_gen the position maps belong to (0: none)
-    pp_block_image img[5];
-    int32_t* pmap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t rpn_gen = 0;    // the same for pp_update_rpn_weights: all sixteen 3 x 3 convolutions in execution order
-    pp_block_image rimg[16];
-    int32_t* rpmap[16] = {};
+    // pp_update_conv_image: the committed images of the sixteen 3 x 3 convolutions in execution order and their position maps on
+    // the device, each entry read back on its first use after a commit
+    uint64_t img_gen[16] = {}; // ctx->commit_gen the entry belongs to (0: none)
+    pp_block_image img[16];
+    int32_t* pmap[16] = {};
 };
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }

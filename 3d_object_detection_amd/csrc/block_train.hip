@@ -281,18 +281,33 @@ void pp_block_destroy(pp_ctx* ctx)
 {
     block_ws* w = (block_ws*)ctx->blk;
     if (!w) return;
-    void* q[] = {w->planes, w->stm, w->pst, w->wT, w->part, w->img16, w->wT16, w->pmap[0], w->pmap[1], w->pmap[2], w->pmap[3], w->pmap[4]};
+    void* q[] = {w->planes, w->stm, w->pst, w->wT, w->part, w->img16, w->wT16};
     for (void* x : q)
         if (x) (void)hipFree(x);
-    for (int32_t* x : w->rpmap)
+    for (int32_t* x : w->pmap)
         if (x) (void)hipFree(x);
     delete w;
     ctx->blk = nullptr;
 }
 
-void pp_launch_unit_image(float* dst, const int32_t* pmap, int n, const float* w, int T, int nrc, hipStream_t stream)
+int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_unit_image, dim3(pp_div_up(n, 256)), dim3(256), 0, stream, dst, pmap, n, w, T, nrc);
+    if (k < 0 || k >= 16) return pp_fail(ctx, PP_E_ARG, "pp_update_conv_image: k must be 0 .. 15");
+    block_ws* ws = workspace(ctx);
+    pp_block_image& im = ws->img[k];
+    if (ws->img_gen[k] != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
+        ws->img_gen[k] = 0;
+        const int b = k < 4 ? 0 : k < 10 ? 1 : 2, u = k - (b == 0 ? 0 : b == 1 ? 4 : 10) - 1; // level; unit, -1: the strided convolution
+        int rc = u < 0 ? pp_net_down_image(ctx, b, &im) : pp_net_block_image(ctx, b, u, &im);
+        if (rc) return rc;
+        if (ws->pmap[k]) { (void)hipFree(ws->pmap[k]); ws->pmap[k] = nullptr; }
+        PP_HIP(hipMalloc((void**)&ws->pmap[k], im.pmap.size() * sizeof(int32_t)));
+        PP_HIP(hipMemcpy(ws->pmap[k], im.pmap.data(), im.pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        ws->img_gen[k] = ctx->commit_gen;
+    }
+    const int n = (int)im.pmap.size();
+    hipLaunchKernelGGL(k_unit_image, dim3(pp_div_up(n, 256)), dim3(256), 0, stream, im.w, ws->pmap[k], n, w, im.T, im.rows * im.C);
+    return 0;
 }
 
 extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip, int nb,
@@ -386,22 +401,9 @@ extern "C" int pp_update_block_weights(pp_ctx* ctx, int block, const float* cons
         return pp_fail(ctx, PP_E_ARG, "pp_update_block_weights: fp32 mode only (the committed plan packs the convolutions in a 16-bit format)");
     hipStream_t stream = (hipStream_t)stream_;
     PP_HIP(hipSetDevice(ctx->device));
-    block_ws* ws = workspace(ctx);
-    if (ws->img_gen != ctx->commit_gen) { // first update after a commit: read the committed images' layout back (synchronous)
-        ws->img_gen = 0;
-        for (int k = 0; k < 5; ++k) {
-            int rc = pp_net_block_image(ctx, block, k, &ws->img[k]);
-            if (rc) return rc;
-            if (ws->pmap[k]) { (void)hipFree(ws->pmap[k]); ws->pmap[k] = nullptr; }
-            PP_HIP(hipMalloc((void**)&ws->pmap[k], ws->img[k].pmap.size() * sizeof(int32_t)));
-            PP_HIP(hipMemcpy(ws->pmap[k], ws->img[k].pmap.data(), ws->img[k].pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        ws->img_gen = ctx->commit_gen;
-    }
-    for (int k = 0; k < 5; ++k) {
-        const pp_block_image& im = ws->img[k];
-        const int cnt = (int)im.pmap.size();
-        pp_launch_unit_image(im.w, ws->pmap[k], cnt, w[k], im.T, im.rows * im.C, stream);
+    for (int k = 0; k < 5; ++k) { // block 3's units: images 11 .. 15
+        int rc = pp_update_conv_image(ctx, 11 + k, w[k], stream);
+        if (rc) return rc;
     }
     PP_HIP(hipGetLastError());
     return 0;
@@ -420,25 +422,9 @@ extern "C" int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w, void* s
         return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights: fp32 mode only (the committed plan packs the convolutions in a 16-bit format)");
     hipStream_t stream = (hipStream_t)stream_;
     PP_HIP(hipSetDevice(ctx->device));
-    block_ws* ws = workspace(ctx);
-    if (ws->rpn_gen != ctx->commit_gen) { // first update after a commit: read the committed images' layout back (synchronous)
-        ws->rpn_gen = 0;
-        int k = 0;
-        for (int b = 0; b < 3; ++b)
-            for (int u = -1; u < (b == 0 ? 3 : 5); ++u, ++k) {
-                int rc = u < 0 ? pp_net_down_image(ctx, b, &ws->rimg[k]) : pp_net_block_image(ctx, b, u, &ws->rimg[k]);
-                if (rc) return rc;
-                if (ws->rpmap[k]) { (void)hipFree(ws->rpmap[k]); ws->rpmap[k] = nullptr; }
-                PP_HIP(hipMalloc((void**)&ws->rpmap[k], ws->rimg[k].pmap.size() * sizeof(int32_t)));
-                PP_HIP(hipMemcpy(ws->rpmap[k], ws->rimg[k].pmap.data(), ws->rimg[k].pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
-        ws->rpn_gen = ctx->commit_gen;
-    }
-    for (int k = 0; k < 16; ++k) {
-        const pp_block_image& im = ws->rimg[k];
-        pp_launch_unit_image(im.w, ws->rpmap[k], (int)im.pmap.size(), w[k], im.T, im.rows * im.C, stream);
-    }
-    int rc = pp_sc1_update(ctx, w[0], stream);
+    int rc = 0;
+    for (int k = 0; k < 16 && !rc; ++k) rc = pp_update_conv_image(ctx, k, w[k], stream);
+    if (!rc) rc = pp_sc1_update(ctx, w[0], stream);
     if (rc) return rc;
     PP_HIP(hipGetLastError());
     return 0;

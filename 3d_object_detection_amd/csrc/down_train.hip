@@ -46,9 +46,6 @@ struct down_ws {
     double* pst = nullptr;   size_t pst_elems = 0;    // [2][fc][Cout][segments][2]: a plane's segment sums of (z, z^2), then of (Gr, Gr xhat)
     float* wT = nullptr;     size_t wT_elems = 0;
     float* part = nullptr;   size_t part_elems = 0;
-    uint64_t img_gen = 0;    // ctx->commit_gen the position map belongs to (0: none)
-    pp_block_image img;      // the strided conv of level 2 (pp_update_down_weight)
-    int32_t* pmap = nullptr;
 };
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -336,7 +333,7 @@ void pp_down_destroy(pp_ctx* ctx)
 {
     down_ws* w = (down_ws*)ctx->down;
     if (!w) return;
-    void* q[] = {w->planes, w->pst, w->wT, w->part, w->pmap};
+    void* q[] = {w->planes, w->pst, w->wT, w->part};
     for (void* x : q)
         if (x) (void)hipFree(x);
     delete w;
@@ -435,17 +432,8 @@ extern "C" int pp_update_down_weight(pp_ctx* ctx, int level, const float* w, voi
         return pp_fail(ctx, PP_E_ARG, "pp_update_down_weight: fp32 mode only (the committed plan packs the convolutions in a 16-bit format)");
     hipStream_t stream = (hipStream_t)stream_;
     PP_HIP(hipSetDevice(ctx->device));
-    down_ws* ws = workspace(ctx);
-    if (ws->img_gen != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
-        ws->img_gen = 0;
-        int rc = pp_net_down_image(ctx, level, &ws->img);
-        if (rc) return rc;
-        if (ws->pmap) { (void)hipFree(ws->pmap); ws->pmap = nullptr; }
-        PP_HIP(hipMalloc((void**)&ws->pmap, ws->img.pmap.size() * sizeof(int32_t)));
-        PP_HIP(hipMemcpy(ws->pmap, ws->img.pmap.data(), ws->img.pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        ws->img_gen = ctx->commit_gen;
-    }
-    pp_launch_unit_image(ws->img.w, ws->pmap, (int)ws->img.pmap.size(), w, ws->img.T, ws->img.rows * ws->img.C, stream);
+    int rc = pp_update_conv_image(ctx, 10, w, stream); // block 3's strided convolution: image 10
+    if (rc) return rc;
     PP_HIP(hipGetLastError());
     return 0;
 }

@@ -265,8 +265,11 @@ int pp_net_down_image(pp_ctx* ctx, int level, pp_block_image* img);
 void pp_down_destroy(pp_ctx* ctx);
 void pp_pfn_train_destroy(pp_ctx* ctx);
 void pp_optim_destroy(pp_ctx* ctx);
-// block_train.hip's image kernel for any position map: dst[i] = position pmap[i] % T of the transformed weight of (row, cin) =
-// pmap[i] / T (< nrc), 0 for padding; w is the state_dict tensor [rows][cin][3][3] on the device
-void pp_launch_unit_image(float* dst, const int32_t* pmap, int n, const float* w, int T, int nrc, hipStream_t stream);
+// The one writer behind pp_update_{block,down,rpn}_weights (block_train.hip): the committed image of 3 x 3 convolution k of the RPN's
+// sixteen in execution = state_dict order (per level its strided convolution, then its 3 | 5 | 5 units; so 10 is block 3's strided
+// convolution and 11 .. 15 its units) <- the state_dict tensor w [rows][cin][3][3] on the device, in place on `stream`.  Image element
+// i becomes position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T, 0 for padding; the map is read back once per
+// commit, on the image's first update.  The callers check their arguments, the precision mode and set the device.
+int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream);
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -290,6 +290,36 @@ class Engine:
         """device int32[1] holding a host-known pillar count."""
         return torch.full((1,), int(p), dtype=torch.int32, device=self.device)
 
+    def _on_device(self, who, named):
+        """Every tensor of ((tensor or None, its name), ...) is on the engine's device: _chk accepts any GPU."""
+        for t, what in named:
+            if t is not None and t.device != self.device:
+                raise ValueError(f"{who}: {what} is on {t.device}, the engine on {self.device}")
+
+    def _chk_weights(self, who, params, keys, shapes):
+        """{state_dict name: device tensor} -> the fp32 tensors of `keys`, in that order, each of its shape and on the engine's device."""
+        out = []
+        for k, shape in zip(keys, shapes):
+            if k not in params:
+                raise KeyError(f"{who}: {k} is missing")
+            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
+            out.append(_chk(t, torch.float32, shape, f"{who}: {k}"))
+            self._on_device(who, [(t, k)])
+        return out
+
+    def _taps_out(self, who, canvas):
+        """The canvas check of the backbone_*taps entry points and what all of them hand out -> (rpn_out [1,320,H,W], [x1, x2, x3])."""
+        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
+            raise ValueError(f"{who}: expected a contiguous canvas")
+        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
+             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), f"{who}: canvas [1,64,gx,gy]")
+        self._on_device(who, [(canvas, "canvas")])
+        return self._t((1, 320, self.H, self.W), torch.float32), [self._level_t(1, b) for b in range(3)]
+
+    def _level_t(self, n, b):
+        """An uninitialised [n,C,h,w] at level b's block shape."""
+        return self._t((n,) + self.neck_shapes(b)[0], torch.float32)
+
     def voxelize(self, points):
         """points f32[N,F] cuda -> (voxels[max_voxels,T,F], coors[max_voxels,3], npts[max_voxels], num[1]) on device."""
         assert points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()
@@ -370,9 +400,7 @@ class Engine:
         dcls = _chk(dcls.reshape(nb, -1) if isinstance(dcls, torch.Tensor) else dcls, torch.float32, (nb, self.A), "head_backward: dcls")
         dbox = _chk(dbox.reshape(nb, -1) if isinstance(dbox, torch.Tensor) else dbox, torch.float32, (nb, self.A * 7), "head_backward: dbox")
         ddir = _chk(ddir.reshape(nb, -1) if isinstance(ddir, torch.Tensor) else ddir, torch.float32, (nb, self.A * 2), "head_backward: ddir")
-        for t, what in ((x, "rpn_out"), (dcls, "dcls"), (dbox, "dbox"), (ddir, "ddir")):
-            if t.device != self.device:
-                raise ValueError(f"head_backward: {what} is on {t.device}, the engine on {self.device}")
+        self._on_device("head_backward", ((x, "rpn_out"), (dcls, "dcls"), (dbox, "dbox"), (ddir, "ddir")))
         na = self.num_anchor_per_loc
         g = {"heads.conv_cls.weight": self._t((na, 320, 1, 1), torch.float32), "heads.conv_cls.bias": self._t((na,), torch.float32),
              "heads.conv_box.weight": self._t((7 * na, 320, 1, 1), torch.float32), "heads.conv_box.bias": self._t((7 * na,), torch.float32),
@@ -405,8 +433,7 @@ class Engine:
                 t = _chk(t, torch.float32, (rows, 320), "update_head_weights: " + k + " as [rows,320,1,1]")
             else:
                 t = _chk(t, torch.float32, (rows,), "update_head_weights: " + k)
-            if t.device != self.device:
-                raise ValueError(f"update_head_weights: {k} is on {t.device}, the engine on {self.device}")
+            self._on_device("update_head_weights", [(t, k)])
             args[k] = t
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_head_weights(self.ctx, *[_ptr(args[k]) for k in self.HEAD_KEYS], _stream()), self.ctx,
@@ -423,12 +450,7 @@ class Engine:
     def backbone_taps(self, canvas):
         """pp_backbone_taps: backbone(canvas) and the three block outputs the upsamplers read -> (rpn_out [1,320,H,W], x1 [1,64,H,W],
         x2 [1,128,H/2,W/2], x3 [1,256,H/4,W/4]).  fp32 mode only."""
-        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
-            raise ValueError("backbone_taps: expected a contiguous canvas")
-        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
-             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_taps: canvas [1,64,gx,gy]")
-        out = self._t((1, 320, self.H, self.W), torch.float32)
-        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        out, taps = self._taps_out("backbone_taps", canvas)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_backbone_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]), _stream()),
                        self.ctx, "pp_backbone_taps")
@@ -448,9 +470,7 @@ class Engine:
         w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, "neck_backward: w")
         y = _chk(y, torch.float32, (nb, 320, self.H, self.W), "neck_backward: y")
         dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), "neck_backward: dy")
-        for t, what in ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")):
-            if t.device != self.device:
-                raise ValueError(f"neck_backward: {what} is on {t.device}, the engine on {self.device}")
+        self._on_device("neck_backward", ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
         dw = self._t(wsh, torch.float32)
@@ -463,15 +483,7 @@ class Engine:
     def update_neck_weights(self, params):
         """pp_update_neck_weights: {state_dict name: device tensor} of rpn.deconv{1,2,3}.0.weight -> the committed upsampler images, in
         place on the current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
-        args = []
-        for b, k in enumerate(self.NECK_KEYS):
-            if k not in params:
-                raise KeyError(f"update_neck_weights: {k} is missing")
-            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
-            t = _chk(t, torch.float32, self.neck_shapes(b)[1], "update_neck_weights: " + k)
-            if t.device != self.device:
-                raise ValueError(f"update_neck_weights: {k} is on {t.device}, the engine on {self.device}")
-            args.append(t)
+        args = self._chk_weights("update_neck_weights", params, self.NECK_KEYS, [self.neck_shapes(b)[1] for b in range(3)])
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_neck_weights(self.ctx, *[_ptr(t) for t in args], _stream()), self.ctx, "pp_update_neck_weights")
 
@@ -513,13 +525,9 @@ class Engine:
         u = _chk(u, torch.float32, (nb, C, h, wd), "unit_backward: u")
         w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), "unit_backward: w")
         dy = _chk(dy, torch.float32, (nb, C, h, wd), "unit_backward: dy")
-        ts = [(u, "u"), (w, "w"), (dy, "dy")]
         if dskip is not None:
             dskip = _chk(dskip, torch.float32, (nb, C, h, wd), "unit_backward: dskip")
-            ts.append((dskip, "dskip"))
-        for t, what in ts:
-            if t.device != self.device:
-                raise ValueError(f"unit_backward: {what} is on {t.device}, the engine on {self.device}")
+        self._on_device("unit_backward", ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((C, C, 3, 3), torch.float32)
@@ -532,13 +540,8 @@ class Engine:
     def backbone_block_taps(self, canvas):
         """pp_backbone_block_taps: backbone_taps(canvas) plus the inputs of block 3's five units -> (rpn_out, x1, x2, x3,
         units [5,256,H/4,W/4] = h, m3, r3, m4, r4 in the order of BLOCK3_KEYS).  fp32 mode only."""
-        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
-            raise ValueError("backbone_block_taps: expected a contiguous canvas")
-        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
-             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_block_taps: canvas [1,64,gx,gy]")
-        out = self._t((1, 320, self.H, self.W), torch.float32)
-        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
-        units = self._t((5,) + self.neck_shapes(2)[0], torch.float32)
+        out, taps = self._taps_out("backbone_block_taps", canvas)
+        units = self._level_t(5, 2)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_backbone_block_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]),
                                                        _ptr(units), _stream()), self.ctx, "pp_backbone_block_taps")
@@ -547,15 +550,7 @@ class Engine:
     def update_block_weights(self, params):
         """pp_update_block_weights: {state_dict name: device tensor} of BLOCK3_KEYS -> the committed images of block 3's five
         convolutions, in place on the current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
-        args = []
-        for k in self.BLOCK3_KEYS:
-            if k not in params:
-                raise KeyError(f"update_block_weights: {k} is missing")
-            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
-            t = _chk(t, torch.float32, (256, 256, 3, 3), "update_block_weights: " + k)
-            if t.device != self.device:
-                raise ValueError(f"update_block_weights: {k} is on {t.device}, the engine on {self.device}")
-            args.append(t)
+        args = self._chk_weights("update_block_weights", params, self.BLOCK3_KEYS, [(256, 256, 3, 3)] * 5)
         ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in args])
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_block_weights(self.ctx, 2, ptrs, 5, _stream()), self.ctx, "pp_update_block_weights")
@@ -582,9 +577,7 @@ class Engine:
         w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), "down_backward: w")
         z = _chk(z, torch.float32, (nb, cout, ho, wo), "down_backward: z")
         dy = _chk(dy, torch.float32, (nb, cout, ho, wo), "down_backward: dy")
-        for t, what in ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")):
-            if t.device != self.device:
-                raise ValueError(f"down_backward: {what} is on {t.device}, the engine on {self.device}")
+        self._on_device("down_backward", ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((cout, cin, 3, 3), torch.float32)
@@ -597,14 +590,8 @@ class Engine:
     def backbone_stage_taps(self, canvas):
         """pp_backbone_stage_taps: backbone_block_taps(canvas) plus the raw output of block 3's strided convolution -> (rpn_out, x1,
         x2, x3, units [5,256,H/4,W/4], z3 [1,256,H/4,W/4]); units[0] = relu(norm(z3)).  fp32 mode only."""
-        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
-            raise ValueError("backbone_stage_taps: expected a contiguous canvas")
-        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
-             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_stage_taps: canvas [1,64,gx,gy]")
-        out = self._t((1, 320, self.H, self.W), torch.float32)
-        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
-        units = self._t((5,) + self.neck_shapes(2)[0], torch.float32)
-        z3 = self._t((1,) + self.neck_shapes(2)[0], torch.float32)
+        out, taps = self._taps_out("backbone_stage_taps", canvas)
+        units, z3 = self._level_t(5, 2), self._level_t(1, 2)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_backbone_stage_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]),
                                                        _ptr(units), _ptr(z3), _stream()), self.ctx, "pp_backbone_stage_taps")
@@ -617,10 +604,8 @@ class Engine:
         if level not in (0, 1, 2):
             raise ValueError(f"update_down_weight: level must be 0, 1 or 2, got {level!r}")
         cin, cout = self.DOWN_PAIRS[level]
-        t = tensor.detach() if isinstance(tensor, torch.Tensor) else tensor
-        t = _chk(t, torch.float32, (cout, cin, 3, 3), "update_down_weight: " + self.DOWN_KEYS[level])
-        if t.device != self.device:
-            raise ValueError(f"update_down_weight: {self.DOWN_KEYS[level]} is on {t.device}, the engine on {self.device}")
+        key = self.DOWN_KEYS[level]
+        t, = self._chk_weights("update_down_weight", {key: tensor}, (key,), [(cout, cin, 3, 3)])
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_down_weight(self.ctx, level, _ptr(t), _stream()), self.ctx, "pp_update_down_weight")
 
@@ -643,16 +628,9 @@ class Engine:
         """pp_backbone_train_taps: backbone_taps(canvas) plus, per level b, the inputs of the block's unit convolutions and the raw
         output of its strided convolution -> (rpn_out, (x1, x2, x3), (units0 [3,64,H,W], units1 [5,128,H/2,W/2], units2 [5,256,H/4,W/4]),
         (z1 [1,64,H,W], z2, z3)); units_b[0] = relu(norm(z_b)).  fp32 mode only."""
-        if isinstance(canvas, torch.Tensor) and not canvas.is_contiguous():
-            raise ValueError("backbone_train_taps: expected a contiguous canvas")
-        _chk(canvas.reshape(-1) if isinstance(canvas, torch.Tensor) else canvas, torch.float32,
-             (64 * int(self.grid_size[0]) * int(self.grid_size[1]),), "backbone_train_taps: canvas [1,64,gx,gy]")
-        if canvas.device != self.device:
-            raise ValueError(f"backbone_train_taps: canvas is on {canvas.device}, the engine on {self.device}")
-        out = self._t((1, 320, self.H, self.W), torch.float32)
-        taps = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
-        units = [self._t((n,) + self.neck_shapes(b)[0], torch.float32) for b, n in enumerate(self.RPN_UNITS)]
-        z = [self._t((1,) + self.neck_shapes(b)[0], torch.float32) for b in range(3)]
+        out, taps = self._taps_out("backbone_train_taps", canvas)
+        units = [self._level_t(n, b) for b, n in enumerate(self.RPN_UNITS)]
+        z = [self._level_t(1, b) for b in range(3)]
         up = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in units])
         zp = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in z])
         with torch.cuda.device(self.device):
@@ -664,15 +642,7 @@ class Engine:
         """pp_update_rpn_weights: {state_dict name: device tensor} of RPN_CONV_KEYS -> the committed images of all sixteen 3 x 3
         convolutions and the sparse first convolution's image, in place on the current stream.  fp32 mode only (RuntimeError otherwise,
         and before the first load_state_dict)."""
-        args = []
-        for k, shape in zip(self.RPN_CONV_KEYS, self.rpn_conv_shapes()):
-            if k not in params:
-                raise KeyError(f"update_rpn_weights: {k} is missing")
-            t = params[k].detach() if isinstance(params[k], torch.Tensor) else params[k]
-            t = _chk(t, torch.float32, shape, "update_rpn_weights: " + k)
-            if t.device != self.device:
-                raise ValueError(f"update_rpn_weights: {k} is on {t.device}, the engine on {self.device}")
-            args.append(t)
+        args = self._chk_weights("update_rpn_weights", params, self.RPN_CONV_KEYS, self.rpn_conv_shapes())
         ptrs = (ctypes.c_void_p * 16)(*[t.data_ptr() for t in args])
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_rpn_weights(self.ctx, ptrs, _stream()), self.ctx, "pp_update_rpn_weights")
@@ -690,9 +660,7 @@ class Engine:
             raise ValueError(f"{what}: {coors.shape[0]} pillars exceed max_batch x max_voxels = {self.max_batch * self.max_voxels}")
         _chk(voxels, torch.float32, (coors.shape[0], self.T, self.F), what + ": voxels")
         _chk(npts, torch.int32, (coors.shape[0],), what + ": num_points_per_voxel")
-        for t, name in ((voxels, "voxels"), (coors, "coors"), (npts, "num_points_per_voxel"), (num, "num")):
-            if t.device != self.device:
-                raise ValueError(f"{what}: {name} is on {t.device}, the engine on {self.device}")
+        self._on_device(what, ((voxels, "voxels"), (coors, "coors"), (npts, "num_points_per_voxel"), (num, "num")))
 
     def _chk_pfn_params(self, w, gamma, beta, what):
         w = w.detach() if isinstance(w, torch.Tensor) else w
@@ -702,9 +670,7 @@ class Engine:
         for t, name in ((gamma, "gamma"), (beta, "beta")):
             if t is not None:
                 out.append(_chk(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32, (64,), f"{what}: {name}"))
-        for t in out:
-            if t.device != self.device:
-                raise ValueError(f"{what}: a parameter is on {t.device}, the engine on {self.device}")
+        self._on_device(what, [(t, "a parameter") for t in out])
         return out
 
     def pfn_train_forward(self, voxels, coors, npts, num, w, gamma, beta):
@@ -733,9 +699,7 @@ class Engine:
             _chk(out, torch.float32, (None, 64), "scatter_backward: out")
         if dfeat.shape[0] < coors.shape[0]:
             raise ValueError("scatter_backward: fewer output rows than pillars")
-        for t, name in ((d, "dcanvas"), (coors, "coors"), (num, "num"), (dfeat, "out")):
-            if t.device != self.device:
-                raise ValueError(f"scatter_backward: {name} is on {t.device}, the engine on {self.device}")
+        self._on_device("scatter_backward", ((d, "dcanvas"), (coors, "coors"), (num, "num"), (dfeat, "out")))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_scatter_backward(self.ctx, _ptr(d), _ptr(coors), _ptr(num), _ptr(dfeat), _stream()), self.ctx,
                        "pp_scatter_backward")
@@ -751,9 +715,7 @@ class Engine:
         feat = _chk(feat, torch.float32, (rows, 64), "pfn_backward: feat")
         arg = _chk(arg, torch.uint8, (rows, 64), "pfn_backward: arg")
         dfeat = _chk(dfeat, torch.float32, (rows, 64), "pfn_backward: dfeat")
-        for t, name in ((stats, "stats"), (feat, "feat"), (arg, "arg"), (dfeat, "dfeat")):
-            if t.device != self.device:
-                raise ValueError(f"pfn_backward: {name} is on {t.device}, the engine on {self.device}")
+        self._on_device("pfn_backward", ((stats, "stats"), (feat, "feat"), (arg, "arg"), (dfeat, "dfeat")))
         dw, dg, db = self._t((64, 9, 1), torch.float32), self._t((64,), torch.float32), self._t((64,), torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_pfn_backward(self.ctx, _ptr(voxels), _ptr(coors), _ptr(npts), _ptr(num), _ptr(w), _ptr(gamma), _ptr(stats),
@@ -767,9 +729,7 @@ class Engine:
         w, gamma, beta = self._chk_pfn_params(w, gamma, beta, "update_pfn_weights")
         rm = _chk(running_mean, torch.float32, (64,), "update_pfn_weights: running_mean")
         rv = _chk(running_var, torch.float32, (64,), "update_pfn_weights: running_var")
-        for t in (rm, rv):
-            if t.device != self.device:
-                raise ValueError(f"update_pfn_weights: a statistic is on {t.device}, the engine on {self.device}")
+        self._on_device("update_pfn_weights", ((rm, "a statistic"), (rv, "a statistic")))
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_pfn_weights(self.ctx, _ptr(w), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), _stream()), self.ctx,
                        "pp_update_pfn_weights")
@@ -996,9 +956,7 @@ class Engine:
             raise ValueError("debug_layer: active and skip_k come together")
         if active is not None:
             active = _chk(active, torch.uint8, (nb, self.H, self.W), "debug_layer: active")
-        for tns, what in ((x, "x"), (res, "res"), (scale, "scale"), (shift, "shift"), (pmap, "pmap"), (feat, "feat"), (active, "active")):
-            if tns is not None and tns.device != self.device:
-                raise ValueError(f"debug_layer: {what} is on {tns.device}, the engine on {self.device}")
+        self._on_device("debug_layer", ((x, "x"), (res, "res"), (scale, "scale"), (shift, "shift"), (pmap, "pmap"), (feat, "feat"), (active, "active")))
         if kind == 2:
             if stats:
                 raise ValueError("debug_layer: the head accumulates no statistics")

@@ -1,36 +1,40 @@
 """networks.pointpillars8_shared.PointPillars (reference pointpillars8_shared.py:346-382): the eager
 network with the InstanceNorm backbone, running PFN / scatter / RPN / head as HIP kernels.
 
-Training surface: head fine-tuning, optionally with the neck and with block 3.  train() makes the six tensors of the anchor head
-require grad; heads(x) then records a torch.autograd.Function whose backward is pp_head_backward (csrc/train.hip).
-train(scope="neck") adds the three upsampler weights rpn.deconv{1,2,3}.0.weight: the training forward then runs the backbone through
-pp_backbone_taps and records a second Function whose backward is pp_neck_backward (csrc/neck_train.hip).  train(scope="block3") adds
-the five convolutions of the deepest Resnet block (BLOCK3_KEYS, unit order): the forward runs pp_backbone_block_taps and the
-backward continues from the third upsampler's dx through five pp_unit_backward calls (csrc/block_train.hip).  train(scope="stage3")
-adds block 3's stride-2 convolution rpn.block3.0.weight: the forward runs pp_backbone_stage_taps, which also hands out that conv's
-pre-norm output, and the backward ends in pp_down_backward (csrc/down_train.hip).  Everything in front of it (PFN, scatter, blocks 1
-and 2 with their stride-2 convolutions) is FROZEN under those scopes.
+Training is one path with a depth.  train(scope=...) names how far back from the outputs the network trains; SCOPES lists the
+depths from the head to the front, and each scope trains what the one before it trains and one group of tensors more (_GROUPS):
 
-Training the whole RPN: train(scope="rpn") trains all sixteen 3 x 3 convolutions, the three upsamplers and the head (RPN_KEYS, the
-reference's state_dict order, 25 tensors).  The forward runs pp_backbone_train_taps, which hands out every block's unit inputs and
-every strided convolution's pre-norm output; the backward (_RpnFunction) walks RPN_TABLE from block 3 to block 1: each block's
-pp_unit_backward chain, its pp_down_backward with the gradient of the stage input, to which the upsampler's dx of the level above is
-added.  The gradient of block 3's input that pp_down_backward computes is consumed by block 2 here.  optimizer.step() is followed by
-pp_update_rpn_weights, which also rewrites the sparse first convolution's image.  PFN and scatter stay frozen under "rpn"; rpn_train()
-returns the gradient with respect to the canvases when they require grad.
+    "head"    the six tensors of the anchor head (HEAD_KEYS)
+    "neck"    + the three upsampler weights (NECK_KEYS)
+    "block3"  + the five unit convolutions of the deepest Resnet block (BLOCK3_KEYS, unit order)
+    "stage3"  + that block's stride-2 convolution (STAGE3_KEY)
+    "rpn"     + the ten convolutions of blocks 1 and 2: the whole RPN (RPN_KEYS, the reference's state_dict order, 25 tensors)
+    "all"     + the pillar feature net (PFN_KEYS; ALL_KEYS = the 28 tensors net.parameters() yields in the reference)
 
-Training everything: train(scope="all") adds the pillar feature net (PFN_KEYS; ALL_KEYS = the 28 tensors net.parameters() yields in the
-reference, in its state_dict order) and follows the reference's train.py, whose net.train() makes BatchNorm1d normalise with batch
-statistics: every training-mode forward runs pp_pfn_train_forward over the pillars of all frames of the batch (_PfnFunction), moves
-running_mean / running_var (momentum 0.1, unbiased variance) and counts num_batches_tracked, whether or not grad is enabled.  The
-backward consumes the canvases' gradient: pp_scatter_backward per frame, then one pp_pfn_backward (csrc/pfn_train.hip).  The eval-mode
-PFN of the engine (running statistics folded into scale / shift) is rewritten by pp_update_pfn_weights before it is next used.
+Everything in front of the trained groups is frozen.  A training forward records up to three autograd Functions, each a thin
+wrapper of engine calls: _HeadFunction (pp_head / pp_head_backward, csrc/train.hip); _RpnFunction, whose forward runs the backbone
+with the taps its depth needs and whose backward walks RPN_TABLE from the upsamplers (pp_neck_backward, csrc/neck_train.hip)
+through each block's unit chain (pp_unit_backward, csrc/block_train.hip) and strided stage (pp_down_backward, csrc/down_train.hip),
+stopping where nothing in front needs a gradient; and, under "all", _PfnFunction in front of it (csrc/pfn_train.hip), which consumes
+the gradient of the canvases that _RpnFunction returns at full depth.  rpn_train() returns that gradient to any canvas that
+requires grad.
+
+The forward always reads the engine's packed images of the weights.  After an optimizer step each group whose tensors moved is
+written into its committed image in place before it is next used (_sync_head, _sync_neck, _sync_pfn); when a convolution of
+blocks 1 and 2 moved, all sixteen convolutions go up in one pp_update_rpn_weights, which also rewrites the sparse first
+convolution's image.  state_dict() returns the current values of the groups that were stepped.
+
+The pillar feature net under "all" follows the reference's train.py, whose net.train() makes BatchNorm1d normalise with batch
+statistics: every training-mode forward runs pp_pfn_train_forward over the pillars of all frames of the batch, moves running_mean /
+running_var (momentum 0.1, unbiased variance) and counts num_batches_tracked, whether or not grad is enabled.  The eval-mode PFN of
+the engine (running statistics folded into scale / shift) is rewritten by pp_update_pfn_weights before it is next used.
 
 Mixed precision: train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
 or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
 backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit."""
 import time
 import types
+import typing
 
 import numpy as np
 import torch
@@ -58,8 +62,30 @@ _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in
 ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
 SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
 GRAD_PRECISIONS = ("fp32", "bf16x3", "bf16")  # train(grad_precision=...): the operands of the unit backwards' gradient products
-# the scopes that train: the upsamplers; block 3's units; block 3's strided convolution; blocks 1 and 2; the pillar feature net
-_NECK_SCOPES, _BLOCK_SCOPES, _STAGE_SCOPES, _RPN_SCOPES = SCOPES[1:], SCOPES[2:], SCOPES[3:], SCOPES[4:]
+
+
+class _Group(typing.NamedTuple):
+    """One group of trainable tensors of PointPillars, kept as a dict of device Parameters."""
+    attr: str     # the dict's attribute
+    keys: tuple   # its state_dict names
+    scope: str    # the first of SCOPES that trains it; every later scope trains it too
+    upload: typing.Callable  # net -> None: the engine call that rewrites the committed image of its current values
+    covers: tuple = ()       # groups whose tensors that call carries as well
+    stats: str = None        # a dict of tensors that are no parameters but go up with the group
+
+
+# from the front of the network to the head
+_GROUPS = {g.attr: g for g in (
+    _Group("_pfn", PFN_KEYS, "all", lambda net: net._eng.update_pfn_weights(*[net._pfn[k] for k in PFN_KEYS],
+                                                                           *[net._pfn_stats[k] for k in PFN_STAT_KEYS]), stats="_pfn_stats"),
+    _Group("_rpn", _RPN_EXTRA_KEYS, "rpn", lambda net: net._eng.update_rpn_weights({**net._rpn, **net._down, **net._block}),
+           covers=("_down", "_block")),  # a convolution of blocks 1 and 2 moved: all sixteen go up in one call
+    _Group("_down", (STAGE3_KEY,), "stage3", lambda net: net._eng.update_down_weight(2, net._down[STAGE3_KEY])),
+    _Group("_block", BLOCK3_KEYS, "block3", lambda net: net._eng.update_block_weights(net._block)),
+    _Group("_neck", NECK_KEYS, "neck", lambda net: net._eng.update_neck_weights(net._neck)),
+    _Group("_params", HEAD_KEYS, "head", lambda net: net._eng.update_head_weights(net._params)),
+)}
+_BACKBONE = ("_neck", "_rpn", "_block", "_down")  # the groups _sync_neck() uploads, in its order: what _RpnFunction differentiates
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -82,167 +108,104 @@ class _HeadFunction(torch.autograd.Function):
         return (None, dx) + tuple(g[k] if ctx.needs_input_grad[2 + i] else None for i, k in enumerate(HEAD_KEYS))
 
 
-class _NeckFunction(torch.autograd.Function):
-    """RPN.forward on a list of canvases as pp_backbone_taps per frame, stacked; its backward is pp_neck_backward for the three
-    upsampling branches.  The three weights are inputs only so that autograd routes their gradients; the forward reads the engine's
-    packed copy of them (PointPillars uploads it beforehand).  The block outputs get no gradient: nothing in front of them trains."""
-
-    @staticmethod
-    def forward(ctx, eng, canvases, *weights):
-        ctx.eng = eng
-        outs = [eng.backbone_taps(c) for c in canvases]
-        y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
-        ctx.save_for_backward(y, x1, x2, x3, *weights)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        y, *rest = ctx.saved_tensors
-        taps, weights = rest[:3], rest[3:]
-        gy = gy.contiguous()
-        dws = tuple(ctx.eng.neck_backward(b, taps[b], weights[b], y, gy, need_dx=False)[0] if ctx.needs_input_grad[2 + b] else None
-                    for b in range(3))
-        return (None, None) + dws
-
-
-class _BlockFunction(torch.autograd.Function):
-    """RPN.forward as pp_backbone_block_taps per frame, stacked; its backward is pp_neck_backward for the three branches (dx for
-    branch 2 only) and then pp_unit_backward for block 3's five units, from unit e back to unit a.  The weights (five of block 3,
-    three upsamplers) are inputs only so that autograd routes their gradients.  Unit a's input gets no gradient: the stride-2
-    convolution behind it stays frozen."""
-
-    @staticmethod
-    def forward(ctx, eng, prec, canvases, *weights):
-        ctx.eng, ctx.prec = eng, prec
-        outs = [eng.backbone_block_taps(c) for c in canvases]
-        y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
-        units = [torch.stack([o[4][k] for o in outs]) for k in range(5)]  # h, m3, r3, m4, r4, each [nb,256,H/4,W/4]
-        ctx.save_for_backward(y, x1, x2, x3, *units, *weights)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        y, *rest = ctx.saved_tensors
-        taps, units, wb, wn = rest[:3], rest[3:8], rest[8:13], rest[13:16]
-        eng, prec, gy = ctx.eng, ctx.prec, gy.contiguous()
-        need_b, need_n = ctx.needs_input_grad[3:8], ctx.needs_input_grad[8:11]
-        dwn = [None] * 3
-        g = None
-        for b in range(3):
-            if need_n[b] or (b == 2 and any(need_b)):
-                dwn[b], dx = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=(b == 2 and any(need_b)))
-                if b == 2:
-                    g = dx
-                if not need_n[b]:
-                    dwn[b] = None
-        dwb = [None] * 5
-        if any(need_b):
-            h, m3, r3, m4, r4 = units
-            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g, grad_precision=prec)
-            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4, grad_precision=prec)
-            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4, grad_precision=prec)
-            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3, grad_precision=prec)
-            dwb[0], _ = eng.unit_backward(h, wb[0], g_m3, need_du=False, grad_precision=prec)
-            dwb = [d if n else None for d, n in zip(dwb, need_b)]
-        return (None, None, None) + tuple(dwb) + tuple(dwn)
-
-
-class _StageFunction(torch.autograd.Function):
-    """_BlockFunction with block 3's stride-2 stage in front: the forward is pp_backbone_stage_taps per frame, the backward that of
-    _BlockFunction down to unit b, then unit a with its input gradient (plus the residual path's) and pp_down_backward for the weight
-    of the stride-2 convolution.  Block 2's output gets no gradient: nothing in front of the stage trains."""
-
-    @staticmethod
-    def forward(ctx, eng, prec, canvases, w0, *weights):
-        ctx.eng, ctx.prec = eng, prec
-        outs = [eng.backbone_stage_taps(c) for c in canvases]
-        y, x1, x2, x3 = (torch.cat([o[i] for o in outs]) for i in range(4))
-        units = [torch.stack([o[4][k] for o in outs]) for k in range(5)]
-        z3 = torch.cat([o[5] for o in outs])
-        ctx.save_for_backward(y, x1, x2, x3, *units, z3, w0, *weights)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        y, *rest = ctx.saved_tensors
-        taps, units, z3, w0, wb, wn = rest[:3], rest[3:8], rest[8], rest[9], rest[10:15], rest[15:18]
-        eng, prec, gy = ctx.eng, ctx.prec, gy.contiguous()
-        need_0, need_b, need_n = ctx.needs_input_grad[3], ctx.needs_input_grad[4:9], ctx.needs_input_grad[9:12]
-        deep = need_0 or any(need_b)
-        dwn = [None] * 3
-        g = None
-        for b in range(3):
-            if need_n[b] or (b == 2 and deep):
-                dwn[b], dx = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=(b == 2 and deep))
-                if b == 2:
-                    g = dx
-                if not need_n[b]:
-                    dwn[b] = None
-        dwb, dw0 = [None] * 5, None
-        if deep:
-            h, m3, r3, m4, r4 = units
-            dwb[4], g_r4 = eng.unit_backward(r4, wb[4], g, dskip=g, grad_precision=prec)
-            dwb[3], g_m4 = eng.unit_backward(m4, wb[3], g_r4, grad_precision=prec)
-            dwb[2], g_r3 = eng.unit_backward(r3, wb[2], g_m4, dskip=g_r4, grad_precision=prec)
-            dwb[1], g_m3 = eng.unit_backward(m3, wb[1], g_r3, grad_precision=prec)
-            dwb[0], g_h = eng.unit_backward(h, wb[0], g_m3, dskip=g_r3, need_du=need_0, grad_precision=prec)
-            dwb = [d if n else None for d, n in zip(dwb, need_b)]
-            if need_0:
-                dw0, _ = eng.down_backward(taps[1], w0, z3, g_h, need_dx=False)
-        return (None, None, None, dw0) + tuple(dwb) + tuple(dwn)
-
-
-def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32"):
+def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32", need_dh=True):
     """The backward of one block's Resnet modules (a row of RPN_TABLE): units and weights in unit order, g = dL/d(block output) ->
-    (dw per unit, dL/d(block input h)).  grad_precision: the operand precision of every unit backward (Engine.unit_backward)."""
+    (dw per unit, dL/d(block input h)).  grad_precision: the operand precision of every unit backward (Engine.unit_backward).
+    need_dh=False: nothing in front of the block trains, so its first unit computes its weight gradient only and h gets None."""
     prec = grad_precision
     dws = [None] * len(units)
     i = len(units)
     for n in reversed(modules):
         i -= n
+        skip = g  # the gradient of the module's output is also that of its residual path
         if n == 2:
-            dws[i + 1], gm = eng.unit_backward(units[i + 1], weights[i + 1], g, grad_precision=prec)
-            dws[i], g = eng.unit_backward(units[i], weights[i], gm, dskip=g, grad_precision=prec)
+            dws[i + 1], g = eng.unit_backward(units[i + 1], weights[i + 1], g, grad_precision=prec)
+        if i or need_dh:
+            dws[i], g = eng.unit_backward(units[i], weights[i], g, dskip=skip, grad_precision=prec)
         else:
-            dws[i], g = eng.unit_backward(units[i], weights[i], g, dskip=g, grad_precision=prec)
+            dws[i], g = eng.unit_backward(units[i], weights[i], g, need_du=False, grad_precision=prec)
     return dws, g
 
 
+_W0 = (0, 4, 10)  # each level's strided convolution in RPN_CONV_KEYS; its unit convolutions follow it
+
+
+def _frame_taps(eng, first, canvas):
+    """One frame's forward with the taps a backward from convolution `first` of RPN_CONV_KEYS on needs ->
+    (y, (x1, x2, x3), {level: unit inputs}, {level: z})."""
+    if first == 0:
+        y, xs, units, zs = eng.backbone_train_taps(canvas)
+        return y, xs, dict(enumerate(units)), dict(enumerate(zs))
+    if first == len(RPN_CONV_KEYS):
+        y, *xs = eng.backbone_taps(canvas)
+        return y, xs, {}, {}
+    if first == _W0[2]:
+        y, x1, x2, x3, units, z3 = eng.backbone_stage_taps(canvas)
+        return y, (x1, x2, x3), {2: units}, {2: z3}
+    y, x1, x2, x3, units = eng.backbone_block_taps(canvas)
+    return y, (x1, x2, x3), {2: units}, {}
+
+
 class _RpnFunction(torch.autograd.Function):
-    """RPN.forward as pp_backbone_train_taps per frame, stacked; its backward is pp_neck_backward for the three branches, each with dx,
-    and then, from level 2 down to level 0 along RPN_TABLE, the block's unit chain and its strided stage (pp_down_backward); the stage's
-    dx plus the upsampler's dx of the level above (in this order: upsampler + stage) is the gradient of that level's block output.
-    weights: the sixteen convolutions in RPN_CONV_KEYS order, then the three upsamplers.  The canvases get level 0's dx when they
-    require grad."""
+    """RPN.forward on canvases x [nb,64,gx,gy], one backbone pass per frame, stacked; the backward of the RPN from its output back
+    to convolution `first` of RPN_CONV_KEYS, the first one that trains: 0 (the whole RPN, backbone_train_taps), 10 (block 3 with its
+    strided convolution, backbone_stage_taps), 11 (block 3's units, backbone_block_taps) or 16 (the upsamplers alone, backbone_taps).
+    weights: RPN_CONV_KEYS[first:], then the three upsamplers; they are inputs only so that autograd routes their gradients, the
+    forward reads the engine's packed copy of them (PointPillars uploads it beforehand).
+
+    The backward is pp_neck_backward for the three branches and then, from level 2 down along RPN_TABLE, the block's unit chain
+    (rpn_block_backward) and its strided stage (pp_down_backward); the upsampler's dx plus the dx of the stage above (in this order)
+    is the gradient of a level's block output.  It stops where nothing in front needs a gradient: a dx is computed only when a
+    weight in front of it, or the canvases, need one, and a weight that does not require grad gets None.  Kept for the backward: y,
+    x1..x3, the unit inputs and z of the levels `first` reaches, the weights, and for first = 0 the canvases, which then get level
+    0's dx when they require grad."""
 
     @staticmethod
-    def forward(ctx, eng, prec, x, *weights):
-        ctx.eng, ctx.prec = eng, prec
-        outs = [eng.backbone_train_taps(c) for c in x]
+    def forward(ctx, eng, prec, first, x, *weights):
+        ctx.eng, ctx.prec, ctx.first = eng, prec, first
+        outs = [_frame_taps(eng, first, c) for c in x]
         y = torch.cat([o[0] for o in outs])
         taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
-        units = [torch.stack([o[2][b][k] for o in outs]) for b, mods in RPN_TABLE for k in range(sum(mods))]
-        zs = [torch.cat([o[3][b] for o in outs]) for b in range(3)]
-        ctx.save_for_backward(x, y, *taps, *units, *zs, *weights)
+        units = [torch.stack([o[2][b][k] for o in outs]) for b in sorted(outs[0][2]) for k in range(sum(RPN_TABLE[b][1]))]
+        zs = [torch.cat([o[3][b] for o in outs]) for b in sorted(outs[0][3])]
+        ctx.save_for_backward(*([x] if first == 0 else []), y, *taps, *units, *zs, *weights)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, y, *rest = ctx.saved_tensors
-        taps, units, zs, wc, wn = rest[:3], rest[3:16], rest[16:19], rest[19:35], rest[35:38]
-        eng, gy = ctx.eng, gy.contiguous()
-        need = ctx.needs_input_grad[1:]  # [1] the canvases, [2 + i] weight i
-        dwn, dxn = zip(*[eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=True) for b in range(3)])
-        dwc = [None] * 16
-        g = None
-        for b, mods in reversed(RPN_TABLE):
-            n, w0 = sum(mods), (0, 4, 10)[b]  # the level's strided convolution in RPN_CONV_KEYS; its units follow
-            u0 = w0 - b
+        eng, first, saved = ctx.eng, ctx.first, list(ctx.saved_tensors)
+        x = saved.pop(0) if first == 0 else None
+        y, taps, saved = saved[0], saved[1:4], saved[4:]
+        nconv = len(RPN_CONV_KEYS)
+        levels = [(b, mods, _W0[b], sum(mods)) for b, mods in RPN_TABLE if first <= _W0[b] + 1]  # the levels with taps
+        units = {b: [saved.pop(0) for _ in range(n)] for b, _, _, n in levels}
+        zs = {b: saved.pop(0) for b, _, w0, _ in levels if first <= w0}
+        wc, wn = dict(zip(range(first, nconv), saved)), saved[nconv - first:]
+        need_x = ctx.needs_input_grad[3]
+        need_c = dict(zip(range(first, nconv), ctx.needs_input_grad[4:]))
+        need_n = ctx.needs_input_grad[4 + nconv - first:]
+        # front[b]: the canvases or a convolution in front of level b's block needs a gradient, so the block's input does;
+        # front[b + 1]: the same for the block's output
+        front = [need_x]
+        for b, mods in RPN_TABLE:
+            front.append(front[b] or any(need_c.get(k, False) for k in range(_W0[b], _W0[b] + 1 + sum(mods))))
+        gy = gy.contiguous()
+        dwn, dxn = [None] * 3, [None] * 3
+        for b in range(3):
+            if need_n[b] or front[b + 1]:
+                dwn[b], dxn[b] = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=front[b + 1])
+        dwc, g = {}, None
+        for b, mods, w0, n in reversed(levels):
+            if not front[b + 1]:
+                break
             g = dxn[b] if g is None else dxn[b] + g
-            dwc[w0 + 1:w0 + 1 + n], gh = rpn_block_backward(eng, mods, units[u0:u0 + n], wc[w0 + 1:w0 + 1 + n], g, ctx.prec)
-            dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=b > 0 or need[1])
-        grads = [d if need[2 + i] else None for i, d in enumerate(list(dwc) + list(dwn))]
-        return (None, None, g if need[1] else None) + tuple(grads)
+            need_dh = first <= w0 and (need_c[w0] or front[b])
+            dws, gh = rpn_block_backward(eng, mods, units[b], [wc[w0 + 1 + i] for i in range(n)], g, ctx.prec, need_dh=need_dh)
+            dwc.update(zip(range(w0 + 1, w0 + 1 + n), dws))
+            if need_dh:
+                dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=front[b])
+        grads = [dwc.get(k) if need_c[k] else None for k in range(first, nconv)] + [d if n else None for d, n in zip(dwn, need_n)]
+        return (None, None, None, g if need_x else None) + tuple(grads)
 
 
 class _PfnFunction(torch.autograd.Function):
@@ -278,12 +241,12 @@ class _PfnFunction(torch.autograd.Function):
 class PointPillars:
     _norm = "instance"
     grad_precision = "fp32"
-    # read-only defaults for an object assembled without __init__ (no engine: the key-order tests); __init__ and load_state_dict
-    # give every object its own
-    _block, _block_uploaded, _block_trained = types.MappingProxyType({}), None, False
-    _down, _down_uploaded, _down_trained = types.MappingProxyType({}), None, False
-    _rpn, _rpn_uploaded, _rpn_trained = types.MappingProxyType({}), None, False
-    _pfn, _pfn_stats, _pfn_uploaded, _pfn_trained, _pfn_nbt = types.MappingProxyType({}), types.MappingProxyType({}), None, False, None
+    # read-only defaults for an object assembled without __init__ (no engine: the key-order and plan tests); __init__ and
+    # load_state_dict give every object its own
+    _block = _down = _rpn = _pfn = _pfn_stats = types.MappingProxyType({})
+    _pfn_nbt = None
+    _uploaded = types.MappingProxyType({})  # per group of _GROUPS: its tensors' _version numbers at the last upload into the engine
+    _trained = frozenset()                  # the groups that have been stepped since load_state_dict
 
     def __init__(self, config):
         self.device = config['device']
@@ -291,30 +254,13 @@ class PointPillars:
         config['_pp_norm'] = self._norm
         self._eng = engine_for(config, self._norm)
         self._sd = None
-        self._params = {}            # the six head tensors as device Parameters (parameters())
-        self._uploaded = None        # their _version numbers at the last upload into the engine
         self.training = False
-        self._trained = False        # the head has been stepped since load_state_dict
-        self._scope = "head"         # train(scope=...): "head", "neck" (+ the three upsamplers), "block3" (+ block 3's five unit
-                                     # convolutions), "stage3" (+ block 3's stride-2 convolution) or "rpn" (+ blocks 1 and 2 with
-                                     # their stride-2 convolutions: the whole RPN) or "all" (+ the pillar feature net)
-        self._pfn = {}               # the PFN's Conv1d weight and BatchNorm1d weight / bias as device Parameters
+        self._scope = "head"         # train(scope=...): one of SCOPES; each trains what the one before it does and one group more
+        # the groups of _GROUPS as dicts of device Parameters: the head's six tensors, the three upsampler weights, block 3's five
+        # unit weights, its stride-2 weight, the ten convolutions of blocks 1 and 2, the PFN's Conv1d weight and BatchNorm1d weight / bias
+        self._params, self._neck, self._block, self._down, self._rpn, self._pfn = {}, {}, {}, {}, {}, {}
         self._pfn_stats = {}         # running_mean / running_var as device tensors (train(scope="all") moves them)
         self._pfn_nbt = None         # num_batches_tracked when the loaded dict carried it
-        self._pfn_uploaded = None    # the _version numbers of those five at the last upload into the engine
-        self._pfn_trained = False
-        self._rpn = {}               # the ten convolutions of blocks 1 and 2 as device Parameters
-        self._rpn_uploaded = None
-        self._rpn_trained = False
-        self._down = {}              # block 3's stride-2 weight as a device Parameter
-        self._down_uploaded = None
-        self._down_trained = False
-        self._block = {}             # block 3's five weights as device Parameters
-        self._block_uploaded = None
-        self._block_trained = False
-        self._neck = {}              # the three upsampler weights as device Parameters
-        self._neck_uploaded = None
-        self._neck_trained = False
         self.profile_stages = True  # the reference synchronises after every stage (:365-374)
         self.pfn_time, self.rpn_time, self.scatter_time, self.heads_time = 0.0, 0.0, 0.0, 0.0
         # like nn.Module construction, start from random initial weights
@@ -343,43 +289,30 @@ class PointPillars:
             raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         if scope not in SCOPES:
             raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
-        if mode and scope != "head" and (self._norm != "instance" or len(self._neck) != 3 or
-                                         (scope in _BLOCK_SCOPES and len(self._block) != 5) or
-                                         (scope in _STAGE_SCOPES and len(self._down) != 1) or
-                                         (scope in _RPN_SCOPES and len(self._rpn) != len(_RPN_EXTRA_KEYS)) or
-                                         (scope == "all" and (len(self._pfn) != 3 or len(self._pfn_stats) != 2))):
+        if mode and scope != "head" and (self._norm != "instance" or (scope == "all" and len(self._pfn_stats) != 2) or
+                                         any(len(getattr(self, g.attr)) != len(g.keys) for g in self._groups(scope) if g.scope != "head")):
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only")
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
         self.grad_precision = grad_precision if self.training else "fp32"
-        for p in self._params.values():
-            p.requires_grad_(self.training)
-        for p in self._neck.values():
-            p.requires_grad_(self.training and self._scope in _NECK_SCOPES)
-        for p in self._block.values():
-            p.requires_grad_(self.training and self._scope in _BLOCK_SCOPES)
-        for p in self._down.values():
-            p.requires_grad_(self.training and self._scope in _STAGE_SCOPES)
-        for p in self._rpn.values():
-            p.requires_grad_(self.training and self._scope in _RPN_SCOPES)
-        for p in self._pfn.values():
-            p.requires_grad_(self.training and self._scope == "all")
-        if not (self.training and self._scope == "all"):
+        trained = self._groups(self._scope) if self.training else ()
+        for g in _GROUPS.values():
+            for p in getattr(self, g.attr).values():
+                p.requires_grad_(g in trained)
+        if not self._pfn_training():
             self._sync_pfn()  # whatever reads the engine's eval-mode PFN next (this object or framework.inference) sees the trained one
         return self
 
+    @staticmethod
+    def _groups(scope):
+        """The groups train(scope=scope) trains, from the front of the network to the head."""
+        return [g for g in _GROUPS.values() if SCOPES.index(g.scope) <= SCOPES.index(scope)]
+
     def _trainable(self):
-        if self._scope in _RPN_SCOPES:
-            every = {**self._rpn, **self._down, **self._block, **self._neck, **self._params}
-            if self._scope == "all":
-                every.update(self._pfn)
-                return {k: every[k] for k in ALL_KEYS if k in every}
-            return {k: every[k] for k in RPN_KEYS if k in every}
-        if self._scope == "stage3":
-            return {**self._down, **self._block, **self._neck, **self._params}
-        if self._scope == "block3":
-            return {**self._block, **self._neck, **self._params}
-        return {**self._neck, **self._params} if self._scope == "neck" else self._params
+        every = {k: p for g in self._groups(self._scope) for k, p in getattr(self, g.attr).items()}
+        if self._scope in ("rpn", "all"):
+            return {k: every[k] for k in ALL_KEYS if k in every}  # the reference's state_dict order
+        return every
 
     def named_parameters(self):
         """The trainable tensors on the device: heads.conv_{cls,box,dir}.{weight,bias}, behind rpn.deconv{1,2,3}.0.weight under
@@ -392,68 +325,51 @@ class PointPillars:
         return iter(self._trainable().values())
 
     def zero_grad(self, set_to_none=True):
-        for p in list(self._pfn.values()) + list(self._rpn.values()) + list(self._down.values()) + list(self._block.values()) + list(self._neck.values()) + list(self._params.values()):
-            if set_to_none:
-                p.grad = None
-            elif p.grad is not None:
-                p.grad.zero_()
+        for g in _GROUPS.values():
+            for p in getattr(self, g.attr).values():
+                if set_to_none:
+                    p.grad = None
+                elif p.grad is not None:
+                    p.grad.zero_()
+
+    def _versions(self, attr):
+        g = _GROUPS[attr]
+        return tuple(t._version for d in (g.attr, g.stats) if d for t in getattr(self, d).values())
+
+    def _moved(self, attr):
+        """An optimizer stepped the group (or the running statistics moved): a _version differs from the last upload's."""
+        up = self._uploaded.get(attr)
+        return up is not None and self._versions(attr) != up
+
+    def _stepped(self):
+        """The groups whose current values differ from the loaded ones."""
+        return [a for a in _GROUPS if a in self._trained or self._moved(a)]
+
+    def _mark_uploaded(self, attrs=tuple(_GROUPS)):
+        self._uploaded = {**self._uploaded, **{a: self._versions(a) for a in attrs}}
+
+    def _sync_group(self, attr):
+        """When the group moved, rewrite the engine's committed image of it in place, with the groups the same call carries."""
+        if self._moved(attr):
+            gone_up = (attr,) + _GROUPS[attr].covers
+            self._trained = self._trained | {a for a in gone_up if self._moved(a)}
+            _GROUPS[attr].upload(self)
+            self._mark_uploaded(gone_up)
 
     def _sync_head(self):
-        """An optimizer stepped (a parameter's _version moved since the last upload): rewrite the engine's packed head in place."""
-        ver = tuple(p._version for p in self._params.values())
-        if ver != self._uploaded:
-            self._eng.update_head_weights(self._params)
-            self._uploaded = ver
-
-    def _neck_moved(self):
-        return self._neck_uploaded is not None and tuple(p._version for p in self._neck.values()) != self._neck_uploaded
-
-    def _block_moved(self):
-        return self._block_uploaded is not None and tuple(p._version for p in self._block.values()) != self._block_uploaded
-
-    def _down_moved(self):
-        return self._down_uploaded is not None and tuple(p._version for p in self._down.values()) != self._down_uploaded
-
-    def _rpn_moved(self):
-        return self._rpn_uploaded is not None and tuple(p._version for p in self._rpn.values()) != self._rpn_uploaded
-
-    def _pfn_versions(self):
-        return tuple(t._version for t in list(self._pfn.values()) + list(self._pfn_stats.values()))
-
-    def _pfn_moved(self):
-        return self._pfn_uploaded is not None and self._pfn_versions() != self._pfn_uploaded
+        """An optimizer stepped the head: rewrite the engine's packed head in place."""
+        self._sync_group("_params")
 
     def _sync_pfn(self):
         """The same for the pillar feature net, ahead of whatever runs the eval-mode PFN: a stepped parameter or moved running
         statistics are folded into the engine's transposed weight, scale and shift (pp_update_pfn_weights)."""
-        if self._pfn_moved():
-            self._pfn_trained = True
-            self._eng.update_pfn_weights(*[self._pfn[k] for k in PFN_KEYS], *[self._pfn_stats[k] for k in PFN_STAT_KEYS])
-            self._pfn_uploaded = self._pfn_versions()
+        self._sync_group("_pfn")
 
     def _sync_neck(self):
         """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone; when
         a convolution of blocks 1 and 2 moved, all sixteen go up in one pp_update_rpn_weights."""
-        if self._neck_moved():
-            self._neck_trained = True
-            self._eng.update_neck_weights(self._neck)
-            self._neck_uploaded = tuple(p._version for p in self._neck.values())
-        if self._rpn_moved():
-            self._rpn_trained = True
-            self._block_trained = self._block_trained or self._block_moved()
-            self._down_trained = self._down_trained or self._down_moved()
-            self._eng.update_rpn_weights({**self._rpn, **self._down, **self._block})
-            self._rpn_uploaded = tuple(p._version for p in self._rpn.values())
-            self._block_uploaded = tuple(p._version for p in self._block.values())
-            self._down_uploaded = tuple(p._version for p in self._down.values())
-        if self._block_moved():
-            self._block_trained = True
-            self._eng.update_block_weights(self._block)
-            self._block_uploaded = tuple(p._version for p in self._block.values())
-        if self._down_moved():
-            self._down_trained = True
-            self._eng.update_down_weight(2, self._down[STAGE3_KEY])
-            self._down_uploaded = tuple(p._version for p in self._down.values())
+        for attr in _BACKBONE:
+            self._sync_group(attr)
 
     def half(self):
         """The reference deploys FP16 TensorRT engines (framework/trt_utils.py:30, networks/pointpillars8_trt.py:208-223,295-314).
@@ -468,82 +384,36 @@ class PointPillars:
     def precision(self, mode):
         """ "fp32" | "bf16x3" (split-bf16: fp32-equivalent on the bf16 MFMAs) | "fp16" | "bf16" | "fp16s" (fp16 operands and fp16 tensors)."""
         self._eng.set_precision(mode)
-        if self._trained or self._head_moved():
-            self._uploaded = ()  # a change of mode packs the loaded weights again: the trained head is uploaded at the next heads()
-        if self._neck_trained or self._neck_moved():
-            self._neck_uploaded = ()  # and the trained upsamplers at the next backbone pass
-        if self._block_trained or self._block_moved():
-            self._block_uploaded = ()
-        if self._down_trained or self._down_moved():
-            self._down_uploaded = ()
-        if self._rpn_trained or self._rpn_moved():
-            self._rpn_uploaded = ()
-        if self._pfn_trained or self._pfn_moved():
-            self._pfn_uploaded = ()  # the commit folds the loaded PFN again: the trained one goes up before its next use
-            if not (self.training and self._scope == "all"):
-                self._sync_pfn()
+        # a change of mode packs the loaded weights again: what was stepped goes up before it is next used (heads(), a backbone pass)
+        stale = self._stepped()
+        self._uploaded = {**self._uploaded, **{a: () for a in stale}}
+        if "_pfn" in stale and not self._pfn_training():
+            self._sync_pfn()
         return self
 
-    def _head_moved(self):
-        return self._uploaded is not None and tuple(p._version for p in self._params.values()) != self._uploaded
-
     def state_dict(self):
-        """The loaded tensors; the head's six, the three upsampler weights and all sixteen 3 x 3 convolutions of the RPN (blocks 1, 2
-        and 3 with their stride-2 weights, RPN_CONV_KEYS) with their CURRENT values (after optimizer steps)."""
+        """The loaded tensors; those of every group that was stepped (the head's six, the three upsampler weights, the sixteen 3 x 3
+        convolutions of the RPN, the pillar feature net with its running statistics) with their CURRENT values."""
         sd = dict(self._sd)
-        if self._pfn_moved() or self._pfn_trained:
-            for k, t in list(self._pfn.items()) + list(self._pfn_stats.items()):
-                sd[k] = t.detach().cpu().numpy().reshape(self._sd[k].shape)
-            if self._pfn_nbt is not None:
+        for attr in self._stepped():
+            for d in (attr, _GROUPS[attr].stats):
+                for k, t in (getattr(self, d).items() if d else ()):
+                    sd[k] = t.detach().cpu().numpy().reshape(self._sd[k].shape)
+            if attr == "_pfn" and self._pfn_nbt is not None:
                 sd[PFN_NBT_KEY] = np.asarray(self._pfn_nbt, dtype=np.int64)
-        if self._rpn_moved() or self._rpn_trained:
-            for k, p in self._rpn.items():
-                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
-        if self._down_moved() or self._down_trained:
-            for k, p in self._down.items():
-                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
-        if self._block_moved() or self._block_trained:
-            for k, p in self._block.items():
-                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
-        if self._neck_moved() or self._neck_trained:
-            for k, p in self._neck.items():
-                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
-        if self._head_moved() or self._trained:
-            for k, p in self._params.items():
-                sd[k] = p.detach().cpu().numpy().reshape(self._sd[k].shape)
         return sd
 
     def load_state_dict(self, sd, strict=True):
         self._sd = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in sd.items()}
         self._eng.load_state_dict(self._sd)
-        self._params = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                              requires_grad=self.training) for k in HEAD_KEYS if k in self._sd}
-        self._uploaded = tuple(p._version for p in self._params.values())
-        self._trained = False
-        neck = self.training and self._scope in _NECK_SCOPES
-        block = self.training and self._scope in _BLOCK_SCOPES
-        self._rpn = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                           requires_grad=self.training and self._scope in _RPN_SCOPES) for k in _RPN_EXTRA_KEYS if k in self._sd}
-        self._rpn_uploaded = tuple(p._version for p in self._rpn.values())
-        self._rpn_trained = False
-        self._down = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                            requires_grad=self.training and self._scope in _STAGE_SCOPES) for k in (STAGE3_KEY,) if k in self._sd}
-        self._down_uploaded = tuple(p._version for p in self._down.values())
-        self._down_trained = False
-        self._block = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                             requires_grad=block) for k in BLOCK3_KEYS if k in self._sd}
-        self._block_uploaded = tuple(p._version for p in self._block.values())
-        self._block_trained = False
-        self._neck = {k: torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device),
-                                            requires_grad=neck) for k in NECK_KEYS if k in self._sd}
-        self._neck_uploaded = tuple(p._version for p in self._neck.values())
-        self._neck_trained = False
         dev_of = lambda k: torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device)  # noqa: E731
-        self._pfn = {k: torch.nn.Parameter(dev_of(k), requires_grad=self.training and self._scope == "all") for k in PFN_KEYS if k in self._sd}
+        trained = self._groups(self._scope) if self.training else ()
+        for g in _GROUPS.values():
+            setattr(self, g.attr, {k: torch.nn.Parameter(dev_of(k), requires_grad=g in trained) for k in g.keys if k in self._sd})
         self._pfn_stats = {k: dev_of(k) for k in PFN_STAT_KEYS if k in self._sd}
         self._pfn_nbt = int(np.asarray(self._sd[PFN_NBT_KEY])) if PFN_NBT_KEY in self._sd else None
-        self._pfn_uploaded = self._pfn_versions()
-        self._pfn_trained = False
+        self._uploaded, self._trained = {}, frozenset()
+        self._mark_uploaded()
         return self
 
     def _sync(self):
@@ -656,10 +526,11 @@ class PointPillars:
         self._sync_neck()
         return self._eng.backbone(x.contiguous())
 
+    def _backbone_requires_grad(self):
+        return any(p.requires_grad for attr in _BACKBONE for p in getattr(self, attr).values())
+
     def _neck_grad(self):
-        return self.training and self._scope in _NECK_SCOPES and torch.is_grad_enabled() and \
-            any(p.requires_grad for p in list(self._neck.values()) + list(self._block.values()) + list(self._down.values()) +
-                list(self._rpn.values()))
+        return self.training and self._scope != "head" and torch.is_grad_enabled() and self._backbone_requires_grad()
 
     def rpn_train(self, x):
         """RPN.forward on canvases x [B,64,gx,gy], 1 <= B <= max_batch, one backbone pass per frame; same values as rpn() bit for
@@ -675,32 +546,25 @@ class PointPillars:
         if not 1 <= x.shape[0] <= eng.max_batch:
             raise ValueError(f"rpn_train: {x.shape[0]} frames in the batch, max_batch is {eng.max_batch}")
         self._sync_neck()
-        block = any(p.requires_grad for p in self._block.values())
-        stage = any(p.requires_grad for p in self._down.values())
-        whole = any(p.requires_grad for p in self._rpn.values())
-        if not (torch.is_grad_enabled() and (whole or stage or block or any(p.requires_grad for p in self._neck.values()))):
+        if not (torch.is_grad_enabled() and self._backbone_requires_grad()):
             return torch.cat([eng.backbone(c) for c in x])
         if eng.effective_precision() != "fp32":
             raise RuntimeError(f"neck training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
                                "(gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place); call float()")
-        if whole:
-            every = {**self._rpn, **self._down, **self._block}
-            return _RpnFunction.apply(eng, self.grad_precision, x, *[every[k] for k in RPN_CONV_KEYS], *[self._neck[k] for k in NECK_KEYS])
-        if stage:
-            return _StageFunction.apply(eng, self.grad_precision, list(x), self._down[STAGE3_KEY], *[self._block[k] for k in BLOCK3_KEYS],
-                                        *[self._neck[k] for k in NECK_KEYS])
-        if block:
-            return _BlockFunction.apply(eng, self.grad_precision, list(x), *[self._block[k] for k in BLOCK3_KEYS], *[self._neck[k] for k in NECK_KEYS])
-        return _NeckFunction.apply(eng, list(x), *[self._neck[k] for k in NECK_KEYS])
+        # the depth of the backward: the first convolution of the frontmost group that holds a parameter requiring grad
+        req = lambda group: any(p.requires_grad for p in group.values())  # noqa: E731
+        first = 0 if req(self._rpn) else _W0[2] if req(self._down) else _W0[2] + 1 if req(self._block) else len(RPN_CONV_KEYS)
+        every = {**self._rpn, **self._down, **self._block}
+        if first:
+            x = x.detach()  # nothing in front of the stage has a backward: the graph must not reach the canvases
+        return _RpnFunction.apply(eng, self.grad_precision, first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
 
     def heads(self, x):
         """SharedHead.forward on x [B,320,H,W], 1 <= B <= max_batch.  Differentiable with respect to x and the head parameters when
         one of them requires grad (train() for the parameters); gradients are fp32 and need the fp32 precision mode."""
         x = x.contiguous()
         params = list(self._params.values())
-        if self._head_moved():
-            self._trained = True
-            self._sync_head()
+        self._sync_head()
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
             if self._eng.effective_precision() != "fp32":
                 raise RuntimeError(f"head training needs the fp32 precision mode: the network runs '{self._eng.effective_precision()}' "

@@ -162,6 +162,38 @@ def test_update_rpn_weights(force, monkeypatch):
         assert torch.equal(eng.backbone(canvas), want[which][1]), which
 
 
+def test_the_three_updaters_share_their_image_maps():
+    """pp_update_down_weight, pp_update_rpn_weights and pp_update_block_weights write through one cache of position maps, filled
+    entry by entry and dropped by a commit: narrow and whole updates in turn, a commit in between (two changes of precision mode),
+    narrow updates again -- and every packed image, with the sparse first convolution's, is the one a fresh engine packs from the
+    values that went up last."""
+    load_pkg().install()
+    sd = seeded_sd()
+    eng = ENG(small_cfg(UX, UY, 2))
+    eng.load_state_dict(sd)
+    rng = np.random.default_rng(11)
+    down, block = ENG.DOWN_KEYS[2], ENG.BLOCK3_KEYS
+    a, b, c, d = (perturbed(sd, rng) for _ in range(4))
+    eng.update_down_weight(2, dev(a[down]))  # fills entry 10 only
+    eng.update_rpn_weights({k: dev(b[k]) for k in CONV})  # the other fifteen
+    eng.update_block_weights({k: dev(c[k]) for k in block})
+    final = dict(b, **{k: c[k] for k in block})
+    fresh = ENG(small_cfg(UX, UY, 2))
+    fresh.load_state_dict(final)
+    assert fresh.layer_tilings() == eng.layer_tilings()
+    for i, (got, want) in enumerate(zip(images(eng), images(fresh))):
+        assert got.shape == want.shape and torch.equal(got, want), ("before the commit", i)
+    eng.set_precision("bf16x3")
+    eng.set_precision("fp32")  # commits sd again: every map is stale, and the images hold sd's values
+    eng.update_block_weights({k: dev(d[k]) for k in block})
+    eng.update_down_weight(2, dev(d[down]))
+    final = dict(sd, **{k: d[k] for k in block + (down,)})
+    fresh.load_state_dict(final)
+    assert fresh.layer_tilings() == eng.layer_tilings()
+    for i, (got, want) in enumerate(zip(images(eng), images(fresh))):
+        assert got.shape == want.shape and torch.equal(got, want), ("after the commit", i)
+
+
 TX, TY = 128, 160  # cells: the level-0 map is 64 x 80 = 4 x 5 tiles of 16 x 16, the geometry of test_tile_skip_gpu.py
 
 
@@ -237,7 +269,7 @@ def test_autograd_surface():
     rng = np.random.default_rng(8)
     up = {k: dev(rng.standard_normal(tuple(v.shape)).astype(np.float32) * np.float32(1e-2)) for k, v in plain.items()}
     grads = {}
-    for scope in ("stage3", "rpn"):
+    for scope in ("neck", "block3", "stage3", "rpn"):
         net.train(scope=scope)
         preds = net(example)
         for k in plain:
@@ -248,9 +280,10 @@ def test_autograd_surface():
     names = [k for k, _ in net.named_parameters()]
     assert names == list(shared.RPN_KEYS) and len(names) == 25
     assert all(p.is_cuda and p.requires_grad for p in net.parameters())
-    assert len(grads["stage3"]) == 15
-    for k, g in grads["stage3"].items():  # the tensors both scopes train get the same bits
-        assert torch.equal(g, grads["rpn"][k]), k
+    assert [len(grads[scope]) for scope in ("neck", "block3", "stage3", "rpn")] == [9, 14, 15, 25]
+    for scope in ("neck", "block3", "stage3"):  # the tensors a narrower scope trains get the same bits as under "rpn"
+        for k, g in grads[scope].items():
+            assert torch.equal(g, grads["rpn"][k]), (scope, k)
     # the same chain by hand
     frames = canvases_of(eng, example)
     canvases = torch.cat(frames)
