@@ -32,7 +32,7 @@
 
 namespace {
 
-// the Winograd weight transforms' G of pack_layer (F(2x2,3x3)) and wino6_pack (F(4x4,3x3)), the same constant expressions
+// the Winograd weight transforms' G of wino2_transform (F(2x2,3x3), wino2.hip) and wino6_pack (F(4x4,3x3)), the same constant expressions
 __constant__ double kG4[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
 __constant__ double kG6[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                  {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
@@ -297,9 +297,7 @@ int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream)
     pp_block_image& im = ws->img[k];
     if (ws->img_gen[k] != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
         ws->img_gen[k] = 0;
-        const int b = k < 4 ? 0 : k < 10 ? 1 : 2, u = k - (b == 0 ? 0 : b == 1 ? 4 : 10) - 1; // level; unit, -1: the strided convolution
-        int rc = u < 0 ? pp_net_down_image(ctx, b, &im) : pp_net_block_image(ctx, b, u, &im);
-        if (rc) return rc;
+        if (int rc = pp_net_conv_image(ctx, k, &im)) return rc;
         if (ws->pmap[k]) { (void)hipFree(ws->pmap[k]); ws->pmap[k] = nullptr; }
         PP_HIP(hipMalloc((void**)&ws->pmap[k], im.pmap.size() * sizeof(int32_t)));
         PP_HIP(hipMemcpy(ws->pmap[k], im.pmap.data(), im.pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));

@@ -568,7 +568,7 @@ void add_c16(std::vector<Variant>& m)
 
 // Tile menu.  A tile is PW x PH output pixels = whole 32-pixel N-tiles in row-major order, so PW only has to divide the map:
 // eight_20cm's 400 / 200 / 100 maps take 80 / 40 / 20, nuScenes' 240 / 120 / 60 too.  Which entry runs a layer is measured
-// on the device (autotune, conv.hip).  Shapes whose LDS image does not fit are dropped at compile time (stride 2 patches
+// on the device (autotune_layer, conv_plan.hip).  Shapes whose LDS image does not fit are dropped at compile time (stride 2 patches
 // are 4x the output tile).  OCC 2 = two workgroups per CU (<= 256 registers, single-buffered LDS): the loads, the
 // normalise-and-round staging and the store tail of one workgroup run under the MFMAs of the other -- what the layers
 // that are bound by the memory pipe need; OCC 1 = one workgroup with the whole register file and double-buffered LDS.
@@ -617,6 +617,29 @@ void conv16_menu(int stride, int prec, std::vector<Variant>& menu, int io16)
         else if (prec == P16_BF16) menu_for<2, P16_BF16>(menu);
         else if (prec == P16_FP16) menu_for<2, P16_FP16>(menu);
     }
+}
+// [row block][cin/16][image: hi (| lo for bf16x3)][tap][k-half][BM rows][8 x 16 bit] = the LDS image of a step
+void conv16_pack(const std::vector<float>& w, int rows, int cin, const Variant& v, std::vector<uint16_t>& out)
+{
+    auto f16 = [](float f) -> uint16_t { const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }; // round to nearest even
+    const int nimg = (v.prec == 1) ? 2 : 1, nblk = rows / v.bm, nch = cin / 16;
+    out.assign((size_t)nblk * nch * nimg * 9 * 2 * v.bm * 8, 0);
+    for (int b = 0; b < nblk; ++b)
+        for (int ch = 0; ch < nch; ++ch)
+            for (int t = 0; t < 9; ++t)
+                for (int h = 0; h < 2; ++h)
+                    for (int mm = 0; mm < v.bm; ++mm)
+                        for (int j = 0; j < 8; ++j) {
+                            const float x = w[((size_t)(b * v.bm + mm) * cin + ch * 16 + h * 8 + j) * 9 + t];
+                            const size_t o = (((size_t)(t * 2 + h)) * v.bm + mm) * 8 + j;
+                            const size_t img0 = (((size_t)b * nch + ch) * nimg) * (size_t)(9 * 2 * v.bm * 8);
+                            if (v.prec == 3) out[img0 + o] = f16(x);
+                            else {
+                                const uint16_t hi = to_bf16(x);
+                                out[img0 + o] = hi;
+                                if (nimg == 2) out[img0 + (size_t)(9 * 2 * v.bm * 8) + o] = to_bf16(x - from_bf16(hi));
+                            }
+                        }
 }
 
 } // namespace ppc

@@ -1,7 +1,9 @@
 // Shared by the conv kernels' translation units -- one per kernel family (conv_direct.hip, wino2.hip, wino4.hip, gemm1x1.hip,
-// conv16.hip, wino6.hip) and conv.hip, the host side that composes their menus and launches them: kernel parameter block,
-// launch-plan entry, XCD-aware block numbering, the small device helpers and what each family exports.  gfx950 only.
+// conv16.hip, wino6.hip) and the host side that composes their menus, packs their weights and launches them (conv_plan.hip, conv_run.hip,
+// conv_inspect.hip; conv_net.h): kernel parameter block, launch-plan entry, XCD-aware block numbering, the small device helpers and what
+// each family exports -- its menu and the weight image its kernel reads.  gfx950 only.
 #pragma once
+#include <cstring>
 #include <type_traits>
 #include "pp_common.h"
 
@@ -74,7 +76,7 @@ enum { PRE_RAW = 0, PRE_STATS = 1, PRE_AFFINE = 2 };
 
 struct ConvP {
     const float* in;
-    const float* w;   // packed [cout_block][chunk][tap][kc][BM]
+    const float* w;   // the layer's weight image, as the tiling's family lays it out (the *_pack functions below)
     float* out;
     const float* res; // residual, same layout as out (nullable)
     int Cin, Hin, Win;
@@ -136,27 +138,62 @@ struct Variant { // one compiled tiling
 };
 
 // Every family's translation unit exports its tilings as menu functions that append to `menu` in a fixed order: the order decides
-// menu[0], ties of the tuner and the entry PP_AUTOTUNE=0 takes, and menu.size() is part of the tune-cache key (conv.hip: layer_menu).
+// menu[0], ties of the tuner and the entry PP_AUTOTUNE=0 takes, and menu.size() is part of the tune-cache key (conv_plan.hip: layer_menu).
+// It also exports the weight image of its tilings, next to the kernel whose LDS reads define it: a plain host function from the layer's
+// weights w [rows][cin][taps] (rows = GEMM rows; pack_layer, conv_plan.hip, gathers them) to the image that is uploaded as ConvP::w.
+
+// The blocking conv_mfma, wino_mfma and wino4_mfma share: [row block of bm][cin chunk of kc][tap][k][bmp columns], a chunk of one block
+// being one LDS fill, zero in the padding; col(mm) is the column row mm of a block lands in, the family's own
+template <typename Col>
+inline void pack_blocked(const std::vector<float>& w, int rows, int cin, int taps, const Variant& v, Col col, std::vector<float>& out)
+{
+    const int nblk = pp_div_up(rows, v.bm), nchunk = cin / v.kc;
+    out.assign((size_t)nblk * nchunk * taps * v.kc * v.bmp, 0.f); // LDS image incl. row padding
+    for (int b = 0; b < nblk; ++b)
+        for (int ch = 0; ch < nchunk; ++ch)
+            for (int t = 0; t < taps; ++t)
+                for (int k = 0; k < v.kc; ++k)
+                    for (int mm = 0; mm < v.bm; ++mm) {
+                        const int row = b * v.bm + mm;
+                        if (row >= rows) continue;
+                        out[((((size_t)b * nchunk + ch) * taps + t) * v.kc + k) * v.bmp + col(mm)] = w[((size_t)row * cin + ch * v.kc + k) * taps + t];
+                    }
+}
+// bf16 images (conv16, gemm1x1): round to nearest even, and back
+inline uint16_t to_bf16(float f) { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }
+inline float from_bf16(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
 
 // conv_direct.hip: conv_mfma -- kind 0: conv3x3 (stride 1 / 2), kind 1: ConvTranspose(k = s = up) for up 1 / 2 / 4, kind 2: the head
 void conv_direct_menu(int kind, int stride, int up, std::vector<Variant>& menu);
+void conv_direct_pack(const std::vector<float>& w, int rows, int cin, int taps, const Variant& v, std::vector<float>& out);
 
-// wino2.hip: wino_mfma, Winograd F(2x2,3x3), two workgroups per CU
+// wino2.hip: wino_mfma, Winograd F(2x2,3x3), two workgroups per CU; the F(2x2,3x3) weight transform of wino_mfma and wino4_mfma:
+// w [n][3][3] -> U = G g G^T [n][4][4] in place
 void wino2_menu(std::vector<Variant>& menu, bool roofline_layer);
+void wino2_transform(std::vector<float>& w);
+void wino2_pack(const std::vector<float>& u /*[rows][cin][16]*/, int rows, int cin, const Variant& v, std::vector<float>& out);
 
 // wino4.hip: wino4_mfma, Winograd F(2x2,3x3), one wave per SIMD -- menu entries and the strip tilings of its region launches
 void wino4_menu(std::vector<Variant>& menu, bool roofline_layer);
 Variant wino4_strip_v(); // 4 px wide, 64 px tall
 Variant wino4_strip_h(); // 64 px wide, 4 px tall
+void wino4_pack(const std::vector<float>& u /*[rows][cin][16]*/, int rows, int cin, const Variant& v, std::vector<float>& out);
 
 // gemm1x1.hip: persistent 1x1 GEMM -- the upsamplers (kind 1) and the 9-anchor head (kind 2) at precision prec (0 fp32 ... 4 fp16 tensors),
-// the shapes of the cls-only head pass, and the LDS bytes of a launch with K input channels (Variant::lds is 0 for this family)
+// the shapes of the cls-only head pass, and the LDS bytes of a launch with K input channels (Variant::lds is 0 for this family).
+// head_tile_row: the natural head row (cls 0..8, box 9 + 7a + k, dir 72 + 2a + k) that tile row t of the 96-row head block holds, -1
+// for padding; gemm1x1_head_order: the head's weights [>= 90][cin] -> [96][cin] in that order.  Images: fp32 and the 16-bit operand pair
+int head_tile_row(int t);
 void gemm1x1_menu(int kind, int up, int prec, std::vector<Variant>& menu);
 void gemm1x1_cls_menu(std::vector<Variant>& menu);
 size_t g1_lds(const Variant& v, int K);
+void gemm1x1_head_order(std::vector<float>& w, int cin);
+void gemm1x1_pack(const std::vector<float>& w /*[rows][cin]*/, int rows, int cin, const Variant& v, std::vector<float>& out);
+void gemm1x1_pack16(const std::vector<float>& w /*[rows][cin]*/, int rows, int cin, const Variant& v, std::vector<uint16_t>& out);
 
 // conv16.hip: 16-bit operand 3x3 convolutions (fp16 / bf16 / split-bf16) -- menu entries for one layer shape and precision
 void conv16_menu(int stride, int prec, std::vector<Variant>& menu, int io16 = 0);
+void conv16_pack(const std::vector<float>& w /*[rows][cin][9]*/, int rows, int cin, const Variant& v, std::vector<uint16_t>& out);
 
 // wino6.hip: Winograd F(4x4,3x3) on fp32 MFMA -- menu entry, the strip tilings of its region launches, the weight image
 void wino6_menu(std::vector<Variant>& menu, bool roofline_layer);

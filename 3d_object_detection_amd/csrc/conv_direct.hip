@@ -398,7 +398,7 @@ Variant make_variant()
 // Tiling menu.  The 16-pixel N-tile is TW x (16/TW); a workgroup covers BTX x BTY tiles.  The maps of
 // eight_20cm are 400/200/100 = 16*25 / 8*25 / 4*25, so NT=5 shapes tile them exactly; the 4x4 / 2x2 shapes
 // are the general fallback (edge tiles masked).  Which entry runs a layer is MEASURED on the device at
-// pp_commit_weights (autotune_layer, conv.hip); the cost model only breaks ties / serves PP_AUTOTUNE=0.
+// pp_commit_weights (autotune_layer, conv_plan.hip); the cost model only breaks ties / serves PP_AUTOTUNE=0.
 template <int KS, int STRIDE, int KC, int EPI>
 void conv_menu(std::vector<Variant>& m)
 {
@@ -446,6 +446,11 @@ void conv_direct_menu(int kind, int stride, int up, std::vector<Variant>& menu)
     } else {
         conv_menu<3, 1, 8, EPI_PLAIN>(menu);
     }
+}
+// The image conv_mfma stages: [row block][cin chunk][tap][k][bmp], row mm of a block in column mm (taps: 9 conv3x3, 1 upsampler / head)
+void conv_direct_pack(const std::vector<float>& w, int rows, int cin, int taps, const Variant& v, std::vector<float>& out)
+{
+    pack_blocked(w, rows, cin, taps, v, [](int mm) { return mm; }, out);
 }
 
 } // namespace ppc

@@ -552,4 +552,68 @@ void gemm1x1_cls_menu(std::vector<Variant>& menu)
 // LDS bytes of a persistent 1x1 GEMM for a given K
 size_t g1_lds(const Variant& v, int K) { return ((size_t)K * v.bmp + (size_t)8 * 2 * K) * sizeof(float); }
 
+// Row order of the head inside gemm1x1.  A lane of the 16x16 MFMA tile owns 4 CONSECUTIVE tile rows (kq*4 + r), so
+// the 90 head rows are dealt to the 24 four-row groups such that a group's values are adjacent in the output:
+//   groups 0..8   box (a = g)      k = 0..3                      -> one 16-byte store per pixel
+//   groups 9..17  box (a = g - 9)  k = 4..6, then cls(a)         -> one 12-byte store per pixel + cls as a pixel quad
+//   groups 18..22 dir (a = 2d, 2d+1), both logits each           -> two 8-byte stores per pixel
+//   group 23      padding
+// (natural order: cls 0..8, box 9 + 7a + k, dir 72 + 2a + k, head rows 90..95 are zero).  With the natural order
+// the 81 box/dir rows cost 4 scalar stores each per lane -- 333 scattered store instructions per 64 pixels, whose
+// completion the next item's first loads had to wait for (vmcnt is in order): 38 % of the head's wave time.
+int head_tile_row(int t)
+{
+    const int g = t >> 2, r = t & 3;
+    if (g < 9) return 9 + 7 * g + r;
+    if (g < 18) return r < 3 ? 9 + 7 * (g - 9) + 4 + r : (g - 9);
+    if (g < 23) {
+        const int a = 2 * (g - 18) + (r >> 1);
+        return a < 9 ? 72 + 2 * a + (r & 1) : -1;
+    }
+    return -1;
+}
+// head under gemm1x1: rows in head_tile_row order
+void gemm1x1_head_order(std::vector<float>& w, int cin)
+{
+    std::vector<float> perm((size_t)96 * cin, 0.f);
+    for (int t = 0; t < 96; ++t) {
+        const int src = head_tile_row(t);
+        if (src >= 0) memcpy(&perm[(size_t)t * cin], &w[(size_t)src * cin], sizeof(float) * cin);
+    }
+    w.swap(perm);
+}
+// fp32 image: [row block][K][BMP], the weight slab a workgroup keeps resident, zero in the row padding
+void gemm1x1_pack(const std::vector<float>& w, int rows, int cin, const Variant& v, std::vector<float>& out)
+{
+    const int nb_ = pp_div_up(rows, v.bm);
+    out.assign((size_t)nb_ * cin * v.bmp, 0.f);
+    for (int b = 0; b < nb_; ++b)
+        for (int c = 0; c < cin; ++c)
+            for (int mm = 0; mm < v.bm; ++mm) {
+                const int row = b * v.bm + mm;
+                if (row < rows) out[((size_t)b * cin + c) * v.bmp + mm] = w[(size_t)row * cin + c];
+            }
+}
+// 16-bit operand image: [row block][K/16][hi|lo][k-group][BMP][4 bf16]: the byte count of the fp32 slab
+void gemm1x1_pack16(const std::vector<float>& w, int rows, int cin, const Variant& v, std::vector<uint16_t>& out)
+{
+    const int nb_ = pp_div_up(rows, v.bm), nkb = cin / 16;
+    out.assign((size_t)nb_ * nkb * 2 * 4 * v.bmp * 4, 0);
+    for (int b = 0; b < nb_; ++b)
+        for (int kb = 0; kb < nkb; ++kb)
+            for (int q = 0; q < 4; ++q)
+                for (int mm = 0; mm < v.bm; ++mm) {
+                    const int row = b * v.bm + mm;
+                    if (row >= rows) continue;
+                    for (int t = 0; t < 4; ++t) {
+                        const float x = w[(size_t)row * cin + kb * 16 + q * 4 + t];
+                        uint16_t hi = to_bf16(x);
+                        if (v.prec == 3) { const _Float16 h16 = (_Float16)x; memcpy(&hi, &h16, 2); } // fp16 operands: the hi image alone is used
+                        const uint16_t lo = to_bf16(x - from_bf16(hi));
+                        out[(((((size_t)b * nkb + kb) * 2 + 0) * 4 + q) * v.bmp + mm) * 4 + t] = hi;
+                        out[(((((size_t)b * nkb + kb) * 2 + 1) * 4 + q) * v.bmp + mm) * 4 + t] = lo;
+                    }
+                }
+}
+
 } // namespace ppc

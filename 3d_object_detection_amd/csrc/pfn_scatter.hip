@@ -11,7 +11,7 @@
 //
 // scatter_kernel (:76-111 / CUDA string of pointpillars8_trt.py:176-193): zero fill + scatter
 //   into the dense [64, gx, gy] canvas.  Only the stand-alone pp_scatter uses it; the fused
-//   frame path feeds the first conv from a pillar-index map instead (conv.hip).
+//   frame path feeds the first conv from a pillar-index map instead (conv_run.hip).
 #include "pp_common.h"
 
 namespace {

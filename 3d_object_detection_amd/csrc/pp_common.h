@@ -53,7 +53,7 @@ struct pp_tensor_h {
     std::vector<float> data;
 };
 
-// one conv-like layer after packing (see conv.hip)
+// one conv-like layer after packing (see conv_net.h)
 struct pp_layer {
     float* w = nullptr;        // packed weights on device
     int cin = 0, cout = 0;     // logical channels (cout = virtual channels for deconv)
@@ -103,7 +103,7 @@ struct pp_ctx {
     float* pfn_w = nullptr;     // [9][64] transposed
     float* pfn_scale = nullptr; // [64]
     float* pfn_shift = nullptr; // [64]
-    void* net = nullptr;        // opaque pp_net (conv.hip)
+    void* net = nullptr;        // opaque pp_net (conv_net.h)
     int precision = 0;          // pp_set_precision: 0 fp32 MFMA, 1 split-bf16 (bf16x3), 2 bf16, 3 fp16 operands -- convs, upsamplers and head
     // ---- measurement (pp_profile_begin/end) ----
     bool prof_on = false;
@@ -185,7 +185,7 @@ int pp_pfn_pmap_group(pp_ctx* ctx, int b0, int g, hipStream_t stream);
 int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream,
                          int defer_nb = 0); // defer_nb > 0: box / dir logits come from the candidate head (a deferred pass of defer_nb frames)
 int pp_run_head_fused(pp_ctx* ctx, float* cls, float* box, float* dir, int nb, hipStream_t stream); // norm+ReLU fused in the prologue
-// deferred head (conv.hip): is it what pp_infer_batch runs; the cls-only pass (marks f_box / f_dir stale); the full tensors on demand
+// deferred head (conv_run.hip): is it what pp_infer_batch runs; the cls-only pass (marks f_box / f_dir stale); the full tensors on demand
 // (no-op unless stale) -- to be called by whatever reads f_box / f_dir or overwrites the concat buffer, its statistics or the head weights
 bool pp_head_defer_on(pp_ctx* ctx);
 int pp_run_head_cls(pp_ctx* ctx, float* cls, int nb, hipStream_t stream);
@@ -230,7 +230,7 @@ int pp_ts_fetch_flags(pp_ctx* ctx, int frame, void* dst, hipStream_t stream);
 void pp_post_destroy(pp_ctx* ctx);
 void pp_assign_destroy(pp_ctx* ctx);
 void pp_train_destroy(pp_ctx* ctx);
-// The head's packed weight image and biases of the committed plan (conv.hip), described for pp_update_head_weights (train.hip):
+// The head's packed weight image and biases of the committed plan (conv_inspect.hip), described for pp_update_head_weights (train.hip):
 // wmap[i] is the element of the natural [cls | box | dir][320] weight (state_dict order, rows concatenated) that image element i
 // holds, -1 for padding; bmap / bpmap likewise for the bias in natural order and in gemm1x1's head_tile_row order (bias_perm is
 // null when the plan has no such copy).  PP_E_ARG when the committed plan packs the head in a 16-bit format.
@@ -248,20 +248,18 @@ struct pp_layer_image {
 };
 int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img);
 void pp_neck_destroy(pp_ctx* ctx);
-// Unit `unit` (0..4 = a..e) of Resnet block `block` (0..2) for pp_update_block_weights (block_train.hip): pmap[i] = (row C + c) T + pos
-// names the element of the TRANSFORMED weight [C][C][T] that image element i holds (T = 36 | 16: position of U = G g G^T of the
-// Winograd families; 9: the tap of the direct tilings), -1 for padding.  fp32 images only (PP_E_ARG otherwise).
+// 3 x 3 convolution k (0 .. 15) of the RPN in execution order, for pp_update_conv_image (block_train.hip): pmap[i] = (row C + c) T + pos
+// names the element of the TRANSFORMED weight [rows][C][T] that image element i holds (T = 36 | 16: position of U = G g G^T of the
+// Winograd families; 9: the tap of the direct tilings), -1 for padding.  fp32 images only (PP_E_ARG otherwise); a strided convolution
+// must run a direct tiling, so T = 9 there.
 struct pp_block_image {
     float* w = nullptr;
     int C = 0, T = 0; // C: input channels
     int rows = 0;     // output channels (= C for a unit)
     std::vector<int32_t> pmap;
 };
-int pp_net_block_image(pp_ctx* ctx, int block, int unit, pp_block_image* img);
+int pp_net_conv_image(pp_ctx* ctx, int k, pp_block_image* img);
 void pp_block_destroy(pp_ctx* ctx);
-// The same for the strided convolution in front of block `level` (0..2), for pp_update_down_weight (down_train.hip): the layer runs a
-// direct tiling, so T = 9 and pmap[i] = (row C + c) 9 + tap.  fp32 images only (PP_E_ARG otherwise).
-int pp_net_down_image(pp_ctx* ctx, int level, pp_block_image* img);
 void pp_down_destroy(pp_ctx* ctx);
 void pp_pfn_train_destroy(pp_ctx* ctx);
 void pp_optim_destroy(pp_ctx* ctx);

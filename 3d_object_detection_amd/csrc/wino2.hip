@@ -507,5 +507,26 @@ void wino2_menu(std::vector<Variant>& menu, bool roofline_layer)
     menu.push_back(make_wino<8, 1, 4, 1, 4>(roofline_layer));
     menu.push_back(make_wino<4, 1, 4, 2, 4>(roofline_layer));
 }
+// U = G g G^T per (cout, cin), fp64 on the host, rounded once; position xi = 4*a + b
+void wino2_transform(std::vector<float>& w)
+{
+    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    std::vector<float> u(w.size() / 9 * 16);
+    for (size_t rc = 0; rc < w.size() / 9; ++rc) {
+        const float* g = &w[rc * 9];
+        double t[4][3];
+        for (int a = 0; a < 4; ++a)
+            for (int j = 0; j < 3; ++j) t[a][j] = G[a][0] * g[0 * 3 + j] + G[a][1] * g[1 * 3 + j] + G[a][2] * g[2 * 3 + j];
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) u[rc * 16 + a * 4 + b] = (float)(t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2]);
+    }
+    w.swap(u);
+}
+// The image wino_mfma stages: [row block][cin chunk][position 0..15][k][bmp], a block's rows in the order [wm][m][M-tile] so a lane's
+// two A operands are adjacent (ds_read_b64)
+void wino2_pack(const std::vector<float>& u, int rows, int cin, const Variant& v, std::vector<float>& out)
+{
+    pack_blocked(u, rows, cin, 16, v, [](int mm) { return (mm >> 5) * 32 + (mm & 15) * 2 + ((mm >> 4) & 1); }, out);
+}
 
 } // namespace ppc

@@ -735,5 +735,12 @@ void wino4_menu(std::vector<Variant>& menu, bool roofline_layer)
 // strip tilings of the region launches (launch_conv): a map that is no multiple of 16 x 16 is covered by whole main tiles plus thin tiles
 Variant wino4_strip_v() { return make_wino4<2, 1, 8>(false); }  // 4 px wide, 64 px tall
 Variant wino4_strip_h() { return make_wino4<16, 2, 8>(false); } // 64 px wide, 4 px tall
+// The image wino4_mfma stages, from U of wino2_transform: [row block][cin chunk][position 0..15][k][bmp], a block's rows in the order
+// [m][M-tile 0..3] so a lane's four A operands are one ds_read_b128.  It depends on the 64-row block and the chunk only: the strip
+// tilings read the main tile's image
+void wino4_pack(const std::vector<float>& u, int rows, int cin, const Variant& v, std::vector<float>& out)
+{
+    pack_blocked(u, rows, cin, 16, v, [](int mm) { return (mm & 15) * 4 + (mm >> 4); }, out);
+}
 
 } // namespace ppc

@@ -1,5 +1,5 @@
 """GPU: the Resnet unit backward, block 3's unit taps and the in-place update of block 3's packed weights (csrc/block_train.hip,
-pp_backbone_block_taps in csrc/conv.hip) through the engine wrappers of the C ABI and through the autograd surface
+pp_backbone_block_taps in csrc/conv_run.hip) through the engine wrappers of the C ABI and through the autograd surface
 (PointPillars.train(scope="block3")), against the reference's float64 autograd goldens (tests/golden/make_blocktrain_goldens.py) and
 the float64 restatement pinned to them (tests/blocktrain_ref.py).
 

@@ -1,5 +1,5 @@
 """GPU: the strided stage backward, the tap of block 3's pre-norm conv output and the in-place update of its packed weight
-(csrc/down_train.hip, pp_backbone_stage_taps in csrc/conv.hip) through the engine wrappers of the C ABI and through the autograd
+(csrc/down_train.hip, pp_backbone_stage_taps in csrc/conv_run.hip) through the engine wrappers of the C ABI and through the autograd
 surface (PointPillars.train(scope="stage3")), against the reference's float64 autograd goldens
 (tests/golden/make_downtrain_goldens.py) and the float64 restatement pinned to them (tests/downtrain_ref.py).
 

@@ -18,7 +18,7 @@ def source_of(pat):
     for kernel, src in FAMILY_SRC:
         if kernel in pat or pat in kernel:
             return src
-    return "conv.hip"  # the small kernels around the layers (norm_relu_stats, norm_finalize, ...)
+    return "conv_run.hip"  # the small kernels around the layers (norm_relu_stats, norm_finalize, ...)
 
 
 def main():
