@@ -117,86 +117,61 @@ __device__ __forceinline__ void mask_lookup_full_body(const int32_t* __restrict_
     mask[a] = area > 0;
 }
 
-__global__ void __launch_bounds__(256) occ_mark(const int32_t* __restrict__ coors, const int32_t* __restrict__ num_pillars, int gy, int32_t* __restrict__ occ)
+// The kernels: a frame's buffers come from `src` (pp_common.h) -- blockIdx.z = frame of a batch, or the one frame of pp_anchor_mask.
+// The bodies above stay device functions: __restrict__ on their parameters is part of what the compiler schedules them by.
+template <class Src> __global__ void __launch_bounds__(256) occ_mark(Src src, int gy)
 {
-    occ_mark_body(coors, num_pillars, gy, occ);
-}
-__global__ void __launch_bounds__(256) scan_rows(int32_t* __restrict__ occ, int gx, int gy) { scan_rows_body(occ, gx, gy); }
-__global__ void __launch_bounds__(1024) scan_cols(int32_t* __restrict__ occ, int gx, int gy) { scan_cols_body(occ, gx, gy); }
-__global__ void __launch_bounds__(256) mask_lookup_sep(const int32_t* __restrict__ sat, int gy, int H, int W, int types,
-                                                       const int32_t* __restrict__ rect_x, const int32_t* __restrict__ rect_y, uint8_t* __restrict__ mask)
-{
-    mask_lookup_sep_body(sat, gy, H, W, types, rect_x, rect_y, mask);
-}
-__global__ void __launch_bounds__(256) mask_lookup_full(const int32_t* __restrict__ sat, int gy, int64_t A, const int4* __restrict__ rects, uint8_t* __restrict__ mask)
-{
-    mask_lookup_full_body(sat, gy, A, rects, mask);
-}
-// batched twins: blockIdx.z = frame
-__global__ void __launch_bounds__(256) occ_mark_b(const pp_pre_frame* __restrict__ tab, int gy)
-{
-    const pp_pre_frame F = tab[blockIdx.z];
+    const pp_pre_frame F = src.get();
     occ_mark_body(F.coors, F.num, gy, F.occ);
 }
-__global__ void __launch_bounds__(256) scan_rows_b(const pp_pre_frame* __restrict__ tab, int gx, int gy) { scan_rows_body(tab[blockIdx.z].occ, gx, gy); }
-__global__ void __launch_bounds__(1024) scan_cols_b(const pp_pre_frame* __restrict__ tab, int gx, int gy) { scan_cols_body(tab[blockIdx.z].occ, gx, gy); }
-__global__ void __launch_bounds__(256) mask_lookup_sep_b(const pp_pre_frame* __restrict__ tab, int gy, int H, int W, int types,
-                                                         const int32_t* __restrict__ rect_x, const int32_t* __restrict__ rect_y)
+template <class Src> __global__ void __launch_bounds__(256) scan_rows(Src src, int gx, int gy) { scan_rows_body(src.get().occ, gx, gy); }
+template <class Src> __global__ void __launch_bounds__(1024) scan_cols(Src src, int gx, int gy) { scan_cols_body(src.get().occ, gx, gy); }
+template <class Src> __global__ void __launch_bounds__(256) mask_lookup_sep(Src src, int gy, int H, int W, int types, const int32_t* __restrict__ rect_x,
+                                                                            const int32_t* __restrict__ rect_y)
 {
-    const pp_pre_frame F = tab[blockIdx.z];
+    const pp_pre_frame F = src.get();
     mask_lookup_sep_body(F.occ, gy, H, W, types, rect_x, rect_y, F.mask);
 }
-__global__ void __launch_bounds__(256) mask_lookup_full_b(const pp_pre_frame* __restrict__ tab, int gy, int64_t A, const int4* __restrict__ rects)
+template <class Src> __global__ void __launch_bounds__(256) mask_lookup_full(Src src, int gy, int64_t A, const int4* __restrict__ rects)
 {
-    const pp_pre_frame F = tab[blockIdx.z];
+    const pp_pre_frame F = src.get();
     mask_lookup_full_body(F.occ, gy, A, rects, F.mask);
 }
 
 } // namespace
 
-extern "C" int pp_anchor_mask(pp_ctx* ctx, const int32_t* coors, const int32_t* num_pillars, uint8_t* mask, void* stream_)
+// M1 .. M4 for g frames; occ is zero on entry
+template <class Src> static int anchor_mask_stages(pp_ctx* ctx, Src src, int g, hipStream_t stream)
 {
-    if (!ctx) return PP_E_ARG;
-    return pp_anchor_mask_slot(ctx, 0, coors, num_pillars, mask, (hipStream_t)stream_);
-}
-
-int pp_anchor_mask_slot(pp_ctx* ctx, int si, const int32_t* coors, const int32_t* num_pillars, uint8_t* mask, hipStream_t stream)
-{
-    pp_slot& S = ctx->slot[si];
-    if (!coors || !num_pillars || !mask) return pp_fail(ctx, PP_E_ARG, "pp_anchor_mask: null pointer");
-    if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, "pp_anchor_mask: call pp_set_anchors first");
     const int gx = ctx->gx, gy = ctx->gy;
-    PP_HIP(hipMemsetAsync(S.occ, 0, (size_t)gx * gy * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(occ_mark, dim3(pp_div_up(ctx->cfg.max_voxels, 256)), dim3(256), 0, stream, coors, num_pillars, gy, S.occ);
-    hipLaunchKernelGGL(scan_rows, dim3(pp_div_up(gx, 4)), dim3(256), 0, stream, S.occ, gx, gy);
-    hipLaunchKernelGGL(scan_cols, dim3(pp_div_up(gy, 64)), dim3(1024), 0, stream, S.occ, gx, gy);
+    hipLaunchKernelGGL(occ_mark<Src>, dim3(pp_div_up(ctx->cfg.max_voxels, 256), 1, g), dim3(256), 0, stream, src, gy);
+    hipLaunchKernelGGL(scan_rows<Src>, dim3(pp_div_up(gx, 4), 1, g), dim3(256), 0, stream, src, gx, gy);
+    hipLaunchKernelGGL(scan_cols<Src>, dim3(pp_div_up(gy, 64), 1, g), dim3(1024), 0, stream, src, gx, gy);
     if (ctx->rect_separable) {
         int types = (int)(ctx->A / ((int64_t)ctx->H * ctx->W));
-        hipLaunchKernelGGL(mask_lookup_sep, dim3(pp_div_up(ctx->A, 256)), dim3(256), 0, stream, S.occ, gy, ctx->H, ctx->W,
-                           types, ctx->rect_x, ctx->rect_y, mask);
+        hipLaunchKernelGGL(mask_lookup_sep<Src>, dim3(pp_div_up(ctx->A, 256), 1, g), dim3(256), 0, stream, src, gy, ctx->H, ctx->W, types,
+                           ctx->rect_x, ctx->rect_y);
     } else {
-        hipLaunchKernelGGL(mask_lookup_full, dim3(pp_div_up(ctx->A, 256)), dim3(256), 0, stream, S.occ, gy, ctx->A,
-                           (const int4*)ctx->rects, mask);
+        hipLaunchKernelGGL(mask_lookup_full<Src>, dim3(pp_div_up(ctx->A, 256), 1, g), dim3(256), 0, stream, src, gy, ctx->A, (const int4*)ctx->rects);
     }
     PP_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int pp_anchor_mask(pp_ctx* ctx, const int32_t* coors, const int32_t* num_pillars, uint8_t* mask, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!coors || !num_pillars || !mask) return pp_fail(ctx, PP_E_ARG, "pp_anchor_mask: null pointer");
+    if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, "pp_anchor_mask: call pp_set_anchors first");
+    hipStream_t stream = (hipStream_t)stream_;
+    pp_pre_frame f = {};
+    PP_SET(f.coors, coors); PP_SET(f.num, num_pillars); PP_SET(f.mask, mask); PP_SET(f.occ, ctx->slot[0].occ);
+    PP_HIP(hipMemsetAsync(ctx->slot[0].occ, 0, (size_t)ctx->gx * ctx->gy * sizeof(int32_t), stream));
+    return anchor_mask_stages(ctx, pp_frames_one<pp_pre_frame>{f}, 1, stream);
 }
 
 // occ tables were zeroed by pre_init_b (voxelize.hip)
 int pp_anchor_mask_group(pp_ctx* ctx, int b0, int g, hipStream_t stream)
 {
-    const pp_pre_frame* tab = ctx->d_pre + b0;
-    const int gx = ctx->gx, gy = ctx->gy;
-    hipLaunchKernelGGL(occ_mark_b, dim3(pp_div_up(ctx->cfg.max_voxels, 256), 1, g), dim3(256), 0, stream, tab, gy);
-    hipLaunchKernelGGL(scan_rows_b, dim3(pp_div_up(gx, 4), 1, g), dim3(256), 0, stream, tab, gx, gy);
-    hipLaunchKernelGGL(scan_cols_b, dim3(pp_div_up(gy, 64), 1, g), dim3(1024), 0, stream, tab, gx, gy);
-    if (ctx->rect_separable) {
-        int types = (int)(ctx->A / ((int64_t)ctx->H * ctx->W));
-        hipLaunchKernelGGL(mask_lookup_sep_b, dim3(pp_div_up(ctx->A, 256), 1, g), dim3(256), 0, stream, tab, gy, ctx->H, ctx->W, types,
-                           ctx->rect_x, ctx->rect_y);
-    } else {
-        hipLaunchKernelGGL(mask_lookup_full_b, dim3(pp_div_up(ctx->A, 256), 1, g), dim3(256), 0, stream, tab, gy, ctx->A, (const int4*)ctx->rects);
-    }
-    PP_HIP(hipGetLastError());
-    return 0;
+    return anchor_mask_stages(ctx, pp_frames_tab<pp_pre_frame>{ctx->d_pre + b0}, g, stream);
 }

@@ -10,8 +10,9 @@
 //                    (radix-select fallback when a bin is huge), box decode, NMS boxes
 //   Q4b post_cand_b  deferred head (pp_infer_batch): post_topk only selects; this kernel computes the box / dir logits of the
 //                    selected anchors from the concat buffer (the head's own MFMA arithmetic, 16 candidates per N-tile) and decodes them
-//   Q5 nms_mask      64x64 suppression bit tiles, one WAVEFRONT per tile row-block: the 64-bit
-//                    ballot of a wave64 IS a mask word (nms.py:119-150 needs a 64-iteration loop)
+//   Q5 nms_mask      64x64 suppression bit tiles, one WAVEFRONT per tile, mask stored TRANSPOSED: the lane owning a column box
+//                    builds its own 64-bit word over the tile's row boxes, which are broadcast lane to lane -- no ballot, no
+//                    loads in the loop (nms.py:119-150 is a 64-iteration loop per thread)
 //   Q6 nms_reduce    greedy sweep, tile-serial (wave-uniform bit tricks inside a tile, vector OR
 //                    across tiles), direction flip, range mask, limit_period, compaction
 //
@@ -31,7 +32,7 @@ constexpr int MAXK = 4096;      // nms_pre_max upper bound
 struct pp_post {
     uint64_t* cand = nullptr;   // [ncls][cand_cap]
     int64_t cand_cap = 0;
-    int32_t* counters = nullptr; // [ncls][8]: 0 cand count, 1 short count, 2 thr bin, 3 nsel, 4 nkeep
+    int32_t* counters = nullptr; // [ncls][8]: the CNT_* slots below
     int32_t* hist = nullptr;    // [ncls][NBINS]
     uint64_t* shortl = nullptr; // [ncls][SHORT_CAP]
     uint64_t* sel = nullptr;    // [ncls][K] sorted keys
@@ -42,6 +43,21 @@ struct pp_post {
     int K = 0, cb = 0, bin_shift = 14;
     uint32_t thr_bits = 0;
 };
+
+// slots of a class's counters[8] (the rest is padding)
+enum { CNT_CAND = 0 /* candidates appended */, CNT_SHORT = 1 /* short-list entries */, CNT_THR_BIN = 2 /* coarse bin of the K-th best */, CNT_NSEL = 3 /* selected */ };
+
+// 64-bit selection key: score bits | ~index, so that descending keys are descending scores with ties by lower index
+__device__ __forceinline__ uint64_t key_pack(uint32_t score_bits, uint32_t idx) { return ((uint64_t)score_bits << 32) | (uint64_t)(0xFFFFFFFFu - idx); }
+__device__ __forceinline__ uint32_t key_index(uint64_t k) { return 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull); }
+__device__ __forceinline__ uint32_t key_score_bits(uint64_t k) { return (uint32_t)(k >> 32); }
+
+// coarse histogram bin of a score at or above the threshold, clamped
+__device__ __forceinline__ int bin_of(uint32_t score_bits, uint32_t thr_bits, int shift)
+{
+    const int bin = (int)((score_bits - thr_bits) >> shift);
+    return bin < NBINS ? bin : NBINS - 1;
+}
 
 __device__ __forceinline__ float sigmoid_rn(float x)
 {
@@ -84,17 +100,13 @@ __device__ __forceinline__ void post_filter_body(const float* __restrict__ cls, 
         const unsigned long long bal = __ballot(pass);
         pre[it] = pass ? wcount + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
         wcount += __popcll(bal);
-        if (pass) {
-            int bin = (int)((sb[it] - thr_bits) >> bin_shift);
-            bin = bin < NBINS ? bin : NBINS - 1;
-            atomicAdd(&lh[bin], 1);
-        }
+        if (pass) atomicAdd(&lh[bin_of(sb[it], thr_bits, bin_shift)], 1);
     }
     if (lane == 0) wtot[wave] = wcount;
     __syncthreads();
     if (threadIdx.x == 0) {
         const int tot = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-        const int b0 = tot ? atomicAdd(&counters[c * 8 + 0], tot) : 0;
+        const int b0 = tot ? atomicAdd(&counters[c * 8 + CNT_CAND], tot) : 0;
         wbase[0] = b0; wbase[1] = b0 + wtot[0]; wbase[2] = wbase[1] + wtot[1]; wbase[3] = wbase[2] + wtot[2];
     }
     __syncthreads();
@@ -104,7 +116,7 @@ __device__ __forceinline__ void post_filter_body(const float* __restrict__ cls, 
         if (pre[it] < 0) continue;
         const int a = base + it * 256 + threadIdx.x;
         const int slot = wb + pre[it];
-        if (slot < cand_cap) cand[(size_t)c * cand_cap + slot] = ((uint64_t)sb[it] << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a);
+        if (slot < cand_cap) cand[(size_t)c * cand_cap + slot] = key_pack(sb[it], (uint32_t)a);
     }
     for (int i = threadIdx.x; i < NBINS; i += 256) {
         const int v = lh[i];
@@ -132,12 +144,12 @@ __device__ __forceinline__ void post_thresh_body(const int32_t* __restrict__ his
     int before = part[t] - s; // candidates in strictly higher bins than this thread's first
     const int total = part[1023];
     if (total <= K) {
-        if (t == 0) counters[c * 8 + 2] = 0; // take everything
+        if (t == 0) counters[c * 8 + CNT_THR_BIN] = 0; // take everything
         return;
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        if (before < K && before + v[k] >= K) counters[c * 8 + 2] = NBINS - 1 - (4 * t + k);
+        if (before < K && before + v[k] >= K) counters[c * 8 + CNT_THR_BIN] = NBINS - 1 - (4 * t + k);
         before += v[k];
     }
 }
@@ -153,11 +165,11 @@ __device__ __forceinline__ void post_gather_body(const uint64_t* __restrict__ ca
     __shared__ uint64_t lbuf[1024];
     __shared__ int lcnt, gbase;
     const int c = blockIdx.y, tid = threadIdx.x;
-    int n = counters[c * 8 + 0];
+    int n = counters[c * 8 + CNT_CAND];
     n = n < cand_cap ? n : (int)cand_cap;
     const int base = blockIdx.x * (256 * GATHER_ITEMS);
     if (base >= n) return; // workgroup-uniform
-    const int thr_bin = counters[c * 8 + 2];
+    const int thr_bin = counters[c * 8 + CNT_THR_BIN];
     if (tid == 0) lcnt = 0;
     __syncthreads();
 #pragma unroll 4
@@ -165,14 +177,12 @@ __device__ __forceinline__ void post_gather_body(const uint64_t* __restrict__ ca
         const int i = base + it * 256 + tid;
         if (i < n) {
             const uint64_t key = cand[(size_t)c * cand_cap + i];
-            int bin = (int)(((uint32_t)(key >> 32) - thr_bits) >> bin_shift);
-            bin = bin < NBINS ? bin : NBINS - 1;
-            if (bin >= thr_bin) {
+            if (bin_of(key_score_bits(key), thr_bits, bin_shift) >= thr_bin) {
                 const int s = atomicAdd(&lcnt, 1);
                 if (s < 1024) {
                     lbuf[s] = key;
                 } else { // more than a quarter of the block selected: append directly
-                    const int slot = atomicAdd(&counters[c * 8 + 1], 1);
+                    const int slot = atomicAdd(&counters[c * 8 + CNT_SHORT], 1);
                     if (slot < SHORT_CAP) shortl[(size_t)c * SHORT_CAP + slot] = key;
                 }
             }
@@ -180,7 +190,7 @@ __device__ __forceinline__ void post_gather_body(const uint64_t* __restrict__ ca
     }
     __syncthreads();
     const int m = lcnt < 1024 ? lcnt : 1024;
-    if (tid == 0 && m > 0) gbase = atomicAdd(&counters[c * 8 + 1], m);
+    if (tid == 0 && m > 0) gbase = atomicAdd(&counters[c * 8 + CNT_SHORT], m);
     __syncthreads();
     for (int j = tid; j < m; j += 256) {
         const int slot = gbase + j;
@@ -233,22 +243,35 @@ __device__ __forceinline__ void standup_box(float cx, float cy, float dx, float 
     o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1;
 }
 
+// decoded candidate ci = c * K + i: its box, its direction label and its NMS box in either mode
+__device__ __forceinline__ void store_candidate(const float* b, bool dir1, int rotate, size_t ci, float* __restrict__ boxes,
+                                                int32_t* __restrict__ dirl, float* __restrict__ nbox)
+{
+    float* bo = boxes + ci * 7;
+#pragma unroll
+    for (int q = 0; q < 7; ++q) bo[q] = b[q];
+    dirl[ci] = dir1 ? 1 : 0;
+    float* nb = nbox + ci * 6;
+    if (rotate) { nb[0] = b[0]; nb[1] = b[1]; nb[2] = b[3]; nb[3] = b[4]; nb[4] = b[6]; }
+    else standup_box(b[0], b[1], b[3], b[4], b[6], nb);
+}
+
 // ---------------------------------------------------------------- Q4
 __device__ __forceinline__ void post_topk_body(pp_config cfg, const uint64_t* __restrict__ cand, int64_t cand_cap,
                                                   const uint64_t* __restrict__ shortl, int32_t* __restrict__ counters, int K,
                                                   const float* __restrict__ box, const float* __restrict__ dir,
                                                   const float* __restrict__ anchors, int rotate, uint64_t* __restrict__ sel,
                                                   float* __restrict__ boxes, float* __restrict__ nbox, int32_t* __restrict__ dirl,
-                                                  bool decode = true)
+                                                  bool decode)
 {
     __shared__ uint64_t keys[SHORT_CAP];
     __shared__ int s_hist[2048];
     __shared__ uint64_t s_prefix;
     __shared__ int s_need, s_cnt;
     const int c = blockIdx.x;
-    int ncand = counters[c * 8 + 0];
+    int ncand = counters[c * 8 + CNT_CAND];
     ncand = ncand < cand_cap ? ncand : (int)cand_cap;
-    int nshort = counters[c * 8 + 1];
+    int nshort = counters[c * 8 + CNT_SHORT];
     int n = 0;
     if (nshort <= SHORT_CAP) {
         n = nshort;
@@ -298,21 +321,15 @@ __device__ __forceinline__ void post_topk_body(pp_config cfg, const uint64_t* __
     while (n2 < n) n2 <<= 1;
     bitonic_desc(keys, n2);
     const int nsel = n < K ? n : K;
-    if (threadIdx.x == 0) counters[c * 8 + 3] = nsel;
+    if (threadIdx.x == 0) counters[c * 8 + CNT_NSEL] = nsel;
     for (int i = threadIdx.x; i < nsel; i += blockDim.x) {
         const uint64_t k = keys[i];
-        const uint32_t a = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);
+        const uint32_t a = key_index(k);
         sel[(size_t)c * K + i] = k;
         if (!decode) continue; // deferred head: post_cand_b computes and decodes the candidates' logits
         float b[7];
         decode_box(box + (size_t)a * 7, anchors + (size_t)a * 7, b);
-        float* bo = boxes + ((size_t)c * K + i) * 7;
-#pragma unroll
-        for (int q = 0; q < 7; ++q) bo[q] = b[q];
-        dirl[(size_t)c * K + i] = dir[(size_t)a * 2 + 1] > dir[(size_t)a * 2] ? 1 : 0;
-        float* nb = nbox + ((size_t)c * K + i) * 6;
-        if (rotate) { nb[0] = b[0]; nb[1] = b[1]; nb[2] = b[3]; nb[3] = b[4]; nb[4] = b[6]; }
-        else standup_box(b[0], b[1], b[3], b[4], b[6], nb);
+        store_candidate(b, dir[(size_t)a * 2 + 1] > dir[(size_t)a * 2], rotate, (size_t)c * K + i, boxes, dirl, nbox);
     }
 }
 
@@ -334,7 +351,7 @@ __global__ void __launch_bounds__(64 * CAND_WAVES) post_cand_b(const pp_post_fra
     const int c = blockIdx.y, fz = blockIdx.z;
     const pp_post_frame F = tab[fz];
     const int frame = f0 + fz; // index into the pass's concat buffer / statistics
-    const int nsel = F.counters[c * 8 + 3];
+    const int nsel = F.counters[c * 8 + CNT_NSEL];
     if ((int)blockIdx.x * (16 * CAND_WAVES) >= nsel) return; // workgroup-uniform (covers nsel == 0)
     for (int ch = threadIdx.x; ch < h.K; ch += blockDim.x) { // the frame's (scale, shift): gemm1x1's own prologue
         float sc, sh; // the concat buffer is always pre-norm: statistics (InstanceNorm) or a folded affine (BatchNorm)
@@ -362,7 +379,7 @@ __global__ void __launch_bounds__(64 * CAND_WAVES) post_cand_b(const pp_post_fra
     const int i = base + m;
     const bool valid = i < nsel;
     const uint64_t key = F.sel[(size_t)c * K + (valid ? i : nsel - 1)];
-    const uint32_t a = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+    const uint32_t a = key_index(key);
     const int aloc = (int)(a / (uint32_t)HW), pix = (int)(a - (uint32_t)aloc * (uint32_t)HW);
     if (base < nsel) { // wave-uniform
         const float* bp = h.in + (size_t)frame * h.in_fs + (size_t)kq * HW + pix; // + 4 S HW per step
@@ -410,13 +427,7 @@ __global__ void __launch_bounds__(64 * CAND_WAVES) post_cand_b(const pp_post_fra
         for (int q = 0; q < 7; ++q) t7[q] = s_out[wave][m][q];
         const float d0 = s_out[wave][m][7], d1 = s_out[wave][m][8];
         decode_box(t7, anchors + (size_t)a * 7, b);
-        float* bo = F.boxes + ((size_t)c * K + i) * 7;
-#pragma unroll
-        for (int q = 0; q < 7; ++q) bo[q] = b[q];
-        F.dirl[(size_t)c * K + i] = d1 > d0 ? 1 : 0;
-        float* nb = F.nbox + ((size_t)c * K + i) * 6;
-        if (rotate) { nb[0] = b[0]; nb[1] = b[1]; nb[2] = b[3]; nb[3] = b[4]; nb[4] = b[6]; }
-        else standup_box(b[0], b[1], b[3], b[4], b[6], nb);
+        store_candidate(b, d1 > d0, rotate, (size_t)c * K + i, F.boxes, F.dirl, F.nbox);
     }
 }
 
@@ -516,15 +527,16 @@ __device__ __forceinline__ float rotated_iou_dev(const float* r1, const float* r
 }
 
 // ---------------------------------------------------------------- Q5
-// grid (col tile, row tile, class); 64 threads; lane = COLUMN box, loop over the 64 row boxes;
-// the 64-bit ballot of the wave is the mask word of that row.
+// grid (col tile, row tile, class); 64 threads; lane = COLUMN box, loop over the 64 row boxes.
 // TRANSPOSED suppression mask, row-tile major: maskT[rt][col] holds, for column box `col`, the bits r of the row boxes
 // (rt*64 + r) that suppress it (IoU > thr and row < col).  One wave per (col tile, row tile); the lane owning a
 // column accumulates its own word while the row boxes are broadcast with readlane -- no ballot, no loads in the loop.
-__device__ __forceinline__ void nms_mask_body(const int c, const float* __restrict__ nbox, int nstride, const int32_t* __restrict__ nsel_p,
-                                               int nsel_stride, int K, int cb, float thr, int rotate, uint64_t* __restrict__ maskT)
+// nbox [ncls][K][6], n = the class's CNT_NSEL.
+__device__ __forceinline__ void nms_mask_body(const int c, const float* __restrict__ nbox, const int32_t* __restrict__ counters, int K, int cb,
+                                               float thr, int rotate, uint64_t* __restrict__ maskT)
 {
-    const int n = nsel_p[c * nsel_stride];
+    constexpr int nstride = 6;
+    const int n = counters[c * 8 + CNT_NSEL];
     const int ct = blockIdx.x, rt = blockIdx.y;
     if (ct < rt || rt * 64 >= n || ct * 64 >= n) return;
     const int lane = threadIdx.x;
@@ -643,7 +655,7 @@ __device__ __forceinline__ void nms_reduce_body(pp_config cfg, const uint64_t* _
     const int ncls = cfg.num_classes;
     if (wave < ncls) {
         const int c = wave;
-        const int n = __builtin_amdgcn_readfirstlane(counters[c * 8 + 3]);
+        const int n = __builtin_amdgcn_readfirstlane(counters[c * 8 + CNT_NSEL]);
         // the kept list goes to LDS (compacted in place below): a global store per kept box inside the sweep put an unknown number of
         // stores into the vmcnt queue, so every tile's fold waited for vmcnt(0) -- the NEXT tile's words included (one memory round
         // trip per tile on the one wave that does the work)
@@ -686,7 +698,7 @@ __device__ __forceinline__ void nms_reduce_body(pp_config cfg, const uint64_t* _
             r = r - floorf(r / two_pi + 0.5f) * two_pi;
             float* d = det + (size_t)(off + k) * 9;
             d[0] = b[0]; d[1] = b[1]; d[2] = b[2]; d[3] = b[3]; d[4] = b[4]; d[5] = b[5]; d[6] = r;
-            d[7] = __uint_as_float((uint32_t)(sel[(size_t)c * K + i] >> 32));
+            d[7] = __uint_as_float(key_score_bits(sel[(size_t)c * K + i]));
             d[8] = (float)c;
         }
         if (lane == 0) det_count[1 + c] = no;
@@ -702,39 +714,42 @@ int shift_for(uint32_t thr_bits)
     return s;
 }
 
-// ---- single-frame entry kernels and their batched twins (blockIdx.z = frame; nms_mask: z = frame * ncls + class) ----
-__global__ void __launch_bounds__(256) post_filter(const float* __restrict__ cls, const uint8_t* __restrict__ mask, pp_config cfg, float thr,
-                                                   uint32_t thr_bits, int bin_shift, int64_t cand_cap, uint64_t* __restrict__ cand,
-                                                   int32_t* __restrict__ counters, int32_t* __restrict__ hist)
+// ---- the kernels: a frame's buffers come from `src` (pp_common.h) -- blockIdx.z = frame of a batch (nms_mask: z = frame * ncls +
+// class), or the one frame of a stage entry.  The bodies above stay device functions: __restrict__ on their parameters is part of
+// what the compiler schedules them by. ----
+template <class Src> __global__ void __launch_bounds__(256) post_filter(Src src, pp_config cfg, float thr, uint32_t thr_bits, int bin_shift, int64_t cand_cap)
 {
-    post_filter_body(cls, mask, cfg, thr, thr_bits, bin_shift, cand_cap, cand, counters, hist);
+    const pp_post_frame F = src.get();
+    post_filter_body(F.cls, F.mask, cfg, thr, thr_bits, bin_shift, cand_cap, F.cand, F.counters, F.hist);
 }
-__global__ void __launch_bounds__(1024) post_thresh(const int32_t* __restrict__ hist, int32_t* __restrict__ counters, int K)
+template <class Src> __global__ void __launch_bounds__(1024) post_thresh(Src src, int K)
 {
-    post_thresh_body(hist, counters, K);
+    const pp_post_frame F = src.get();
+    post_thresh_body(F.hist, F.counters, K);
 }
-__global__ void __launch_bounds__(256) post_gather(const uint64_t* __restrict__ cand, int64_t cand_cap, int32_t* __restrict__ counters,
-                                                   uint32_t thr_bits, int bin_shift, uint64_t* __restrict__ shortl)
+template <class Src> __global__ void __launch_bounds__(256) post_gather(Src src, int64_t cand_cap, uint32_t thr_bits, int bin_shift)
 {
-    post_gather_body(cand, cand_cap, counters, thr_bits, bin_shift, shortl);
+    const pp_post_frame F = src.get();
+    post_gather_body(F.cand, cand_cap, F.counters, thr_bits, bin_shift, F.shortl);
 }
-__global__ void __launch_bounds__(1024) post_topk(pp_config cfg, const uint64_t* __restrict__ cand, int64_t cand_cap, const uint64_t* __restrict__ shortl,
-                                                  int32_t* __restrict__ counters, int K, const float* __restrict__ box, const float* __restrict__ dir,
-                                                  const float* __restrict__ anchors, int nms_mode, uint64_t* __restrict__ sel,
-                                                  float* __restrict__ boxes, float* __restrict__ nbox, int32_t* __restrict__ dirl)
+template <class Src> __global__ void __launch_bounds__(1024) post_topk(Src src, pp_config cfg, int64_t cand_cap, int K, const float* __restrict__ anchors,
+                                                                       int nms_mode, int decode)
 {
-    post_topk_body(cfg, cand, cand_cap, shortl, counters, K, box, dir, anchors, nms_mode, sel, boxes, nbox, dirl);
+    const pp_post_frame F = src.get();
+    post_topk_body(cfg, F.cand, cand_cap, F.shortl, F.counters, K, F.box, F.dir, anchors, nms_mode, F.sel, F.boxes, F.nbox, F.dirl, decode != 0);
 }
-__global__ void __launch_bounds__(64) nms_mask(const float* __restrict__ nbox, int nstride, const int32_t* __restrict__ nsel_p, int nsel_stride,
-                                               int K, int cb, float thr, int rotate, uint64_t* __restrict__ maskT)
+template <class Src> __global__ void __launch_bounds__(64) nms_mask(Src src, int ncls, int K, int cb, float thr, int rotate)
 {
-    nms_mask_body(blockIdx.z, nbox, nstride, nsel_p, nsel_stride, K, cb, thr, rotate, maskT);
+    const int fr = blockIdx.z / ncls, c = blockIdx.z - fr * ncls;
+    const pp_post_frame F = src.at(fr);
+    nms_mask_body(c, F.nbox, F.counters, K, cb, thr, rotate, F.nmask);
 }
-__global__ void __launch_bounds__(64 * PP_MAX_CLASSES) nms_reduce(pp_config cfg, const uint64_t* __restrict__ mask, const uint64_t* __restrict__ sel,
-                                                  const float* __restrict__ boxes, const int32_t* __restrict__ dirl, int32_t* __restrict__ counters,
-                                                  int K, int cb, float* __restrict__ det, int32_t* __restrict__ det_count)
+template <class Src> __global__ void __launch_bounds__(64 * PP_MAX_CLASSES) nms_reduce(Src src, pp_config cfg, int K, int cb, float* __restrict__ det, size_t det_fs,
+                                                                                       int32_t* __restrict__ det_count, int cnt_fs)
 {
-    nms_reduce_body(cfg, mask, sel, boxes, dirl, counters, K, cb, det, det_count);
+    const pp_post_frame F = src.get();
+    nms_reduce_body(cfg, F.nmask, F.sel, F.boxes, F.dirl, F.counters, K, cb, det + blockIdx.z * det_fs,
+                    det_count + blockIdx.z * cnt_fs);
 }
 
 __global__ void __launch_bounds__(256) post_init_b(const pp_post_frame* __restrict__ tab, int nwords)
@@ -742,52 +757,17 @@ __global__ void __launch_bounds__(256) post_init_b(const pp_post_frame* __restri
     int32_t* h = tab[blockIdx.z].hist; // hist | counters are one allocation
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += gridDim.x * blockDim.x) h[i] = 0;
 }
-__global__ void __launch_bounds__(256) post_filter_b(const pp_post_frame* __restrict__ tab, pp_config cfg, float thr, uint32_t thr_bits,
-                                                     int bin_shift, int64_t cand_cap)
-{
-    const pp_post_frame F = tab[blockIdx.z];
-    post_filter_body(F.cls, F.mask, cfg, thr, thr_bits, bin_shift, cand_cap, F.cand, F.counters, F.hist);
-}
-__global__ void __launch_bounds__(1024) post_thresh_b(const pp_post_frame* __restrict__ tab, int K)
-{
-    const pp_post_frame F = tab[blockIdx.z];
-    post_thresh_body(F.hist, F.counters, K);
-}
-__global__ void __launch_bounds__(256) post_gather_b(const pp_post_frame* __restrict__ tab, int64_t cand_cap, uint32_t thr_bits, int bin_shift)
-{
-    const pp_post_frame F = tab[blockIdx.z];
-    post_gather_body(F.cand, cand_cap, F.counters, thr_bits, bin_shift, F.shortl);
-}
-__global__ void __launch_bounds__(1024) post_topk_b(const pp_post_frame* __restrict__ tab, pp_config cfg, int64_t cand_cap, int K,
-                                                    const float* __restrict__ anchors, int nms_mode, int decode)
-{
-    const pp_post_frame F = tab[blockIdx.z];
-    post_topk_body(cfg, F.cand, cand_cap, F.shortl, F.counters, K, F.box, F.dir, anchors, nms_mode, F.sel, F.boxes, F.nbox, F.dirl, decode != 0);
-}
-__global__ void __launch_bounds__(64) nms_mask_b(const pp_post_frame* __restrict__ tab, int ncls, int K, int cb, float thr, int rotate)
-{
-    const int fr = blockIdx.z / ncls, c = blockIdx.z - fr * ncls;
-    const pp_post_frame F = tab[fr];
-    nms_mask_body(c, F.nbox, 6, F.counters + 3, 8, K, cb, thr, rotate, F.nmask);
-}
-__global__ void __launch_bounds__(64 * PP_MAX_CLASSES) nms_reduce_b(const pp_post_frame* __restrict__ tab, pp_config cfg, int K, int cb, float* __restrict__ det,
-                                                    size_t det_fs, int32_t* __restrict__ det_count, int cnt_fs)
-{
-    const pp_post_frame F = tab[blockIdx.z];
-    nms_reduce_body(cfg, F.nmask, F.sel, F.boxes, F.dirl, F.counters, K, cb, det + blockIdx.z * det_fs,
-                    det_count + blockIdx.z * cnt_fs);
-}
 
 // stage entry pp_select_candidates: the sorted keys of post_topk as (anchor id, score) rows, -1 / 0 beyond a class's count
 __global__ void __launch_bounds__(256) post_export_sel(const uint64_t* __restrict__ sel, const int32_t* __restrict__ counters, int K,
                                                        int32_t* __restrict__ idx, float* __restrict__ score, int32_t* __restrict__ count)
 {
     const int c = blockIdx.x;
-    const int n = counters[c * 8 + 3];
+    const int n = counters[c * 8 + CNT_NSEL];
     for (int i = threadIdx.x; i < K; i += blockDim.x) {
         const uint64_t k = i < n ? sel[(size_t)c * K + i] : 0ull;
-        idx[(size_t)c * K + i] = i < n ? (int32_t)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull)) : -1;
-        score[(size_t)c * K + i] = i < n ? __uint_as_float((uint32_t)(k >> 32)) : 0.f;
+        idx[(size_t)c * K + i] = i < n ? (int32_t)key_index(k) : -1;
+        score[(size_t)c * K + i] = i < n ? __uint_as_float(key_score_bits(k)) : 0.f;
     }
     if (threadIdx.x == 0) count[c] = n;
 }
@@ -847,71 +827,6 @@ void pp_post_destroy(pp_ctx* ctx)
     }
 }
 
-extern "C" int pp_postprocess(pp_ctx* ctx, const float* cls, const float* box, const float* dir, const uint8_t* mask,
-                              float* det, int32_t* det_count, int nms_mode, void* stream_)
-{
-    if (!ctx) return PP_E_ARG;
-    return pp_postprocess_slot(ctx, 0, cls, box, dir, mask, det, det_count, nms_mode, (hipStream_t)stream_);
-}
-
-// Stage entry behind Inference.infer_torch (inference.py:140-189: per class mask gather, sigmoid, score threshold, top-k):
-// the first two stages of pp_postprocess alone.  idx i32[ncls][nms_pre_max] anchor ids by descending score (ties: lower
-// anchor id), score f32[ncls][nms_pre_max], count i32[ncls].
-extern "C" int pp_select_candidates(pp_ctx* ctx, const float* cls, const float* box, const float* dir, const uint8_t* mask,
-                                    int32_t* idx, float* score, int32_t* count, void* stream_)
-{
-    if (!ctx) return PP_E_ARG;
-    if (!cls || !box || !dir || !mask || !idx || !score || !count) return pp_fail(ctx, PP_E_ARG, "pp_select_candidates: null pointer");
-    if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, "pp_select_candidates: call pp_set_anchors first");
-    hipStream_t stream = (hipStream_t)stream_;
-    pp_post* P = (pp_post*)ctx->slot[0].post;
-    const pp_config& c = ctx->cfg;
-    const int n = c.num_classes;
-    for (int i = 0; i < n; ++i)
-        if (c.class_end[i] > ctx->A) return pp_fail(ctx, PP_E_ARG, "class range exceeds anchor count");
-    PP_HIP(hipMemsetAsync(P->hist, 0, (size_t)n * (NBINS + 8) * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(post_filter, dim3(pp_div_up(P->cand_cap, 256 * FILTER_ITEMS), n), dim3(256), 0, stream, cls, mask, c, c.score_threshold,
-                       P->thr_bits, P->bin_shift, P->cand_cap, P->cand, P->counters, P->hist);
-    hipLaunchKernelGGL(post_thresh, dim3(n), dim3(1024), 0, stream, P->hist, P->counters, P->K);
-    hipLaunchKernelGGL(post_gather, dim3(pp_div_up(P->cand_cap, 256 * GATHER_ITEMS), n), dim3(256), 0, stream, P->cand, P->cand_cap, P->counters,
-                       P->thr_bits, P->bin_shift, P->shortl);
-    hipLaunchKernelGGL(post_topk, dim3(n), dim3(1024), 0, stream, c, P->cand, P->cand_cap, P->shortl, P->counters, P->K, box, dir,
-                       ctx->anchors, 0, P->sel, P->boxes, P->nbox, P->dirl);
-    hipLaunchKernelGGL(post_export_sel, dim3(n), dim3(256), 0, stream, P->sel, P->counters, P->K, idx, score, count);
-    PP_HIP(hipGetLastError());
-    return 0;
-}
-
-int pp_postprocess_slot(pp_ctx* ctx, int si, const float* cls, const float* box, const float* dir, const uint8_t* mask, float* det,
-                        int32_t* det_count, int nms_mode, hipStream_t stream)
-{
-    if (!cls || !box || !dir || !mask || !det || !det_count) return pp_fail(ctx, PP_E_ARG, "pp_postprocess: null pointer");
-    if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, "pp_postprocess: call pp_set_anchors first");
-    pp_post* P = (pp_post*)ctx->slot[si].post;
-    const pp_config& c = ctx->cfg;
-    const int n = c.num_classes;
-    for (int i = 0; i < n; ++i)
-        if (c.class_end[i] > ctx->A) return pp_fail(ctx, PP_E_ARG, "class range exceeds anchor count");
-    { int rc0_ = pp_stage_mark(ctx, stream, PP_ST_POST); if (rc0_) return rc0_; }
-    PP_HIP(hipMemsetAsync(P->hist, 0, (size_t)n * (NBINS + 8) * sizeof(int32_t), stream)); // hist + counters
-    hipLaunchKernelGGL(post_filter, dim3(pp_div_up(P->cand_cap, 256 * FILTER_ITEMS), n), dim3(256), 0, stream, cls, mask, c, c.score_threshold,
-                       P->thr_bits, P->bin_shift, P->cand_cap, P->cand, P->counters, P->hist);
-    hipLaunchKernelGGL(post_thresh, dim3(n), dim3(1024), 0, stream, P->hist, P->counters, P->K);
-    hipLaunchKernelGGL(post_gather, dim3(pp_div_up(P->cand_cap, 256 * GATHER_ITEMS), n), dim3(256), 0, stream, P->cand, P->cand_cap, P->counters,
-                       P->thr_bits, P->bin_shift, P->shortl);
-    int rc_;
-    if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_TOPK))) return rc_;
-    hipLaunchKernelGGL(post_topk, dim3(n), dim3(1024), 0, stream, c, P->cand, P->cand_cap, P->shortl, P->counters, P->K, box, dir,
-                       ctx->anchors, nms_mode, P->sel, P->boxes, P->nbox, P->dirl);
-    if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_NMS))) return rc_;
-    hipLaunchKernelGGL(nms_mask, dim3(P->cb, P->cb, n), dim3(64), 0, stream, P->nbox, 6, P->counters + 3, 8, P->K, P->cb,
-                       c.nms_iou_threshold, nms_mode, P->nmask);
-    hipLaunchKernelGGL(nms_reduce, dim3(1), dim3(64 * PP_MAX_CLASSES), 0, stream, c, P->nmask, P->sel, P->boxes, P->dirl, P->counters, P->K, P->cb,
-                       det, det_count);
-    PP_HIP(hipGetLastError());
-    return pp_stage_mark(ctx, stream, -1);
-}
-
 void pp_post_fill_table(pp_ctx* ctx, int slot, pp_post_frame* f)
 {
     const pp_post* P = (const pp_post*)ctx->slot[slot].post;
@@ -920,43 +835,126 @@ void pp_post_fill_table(pp_ctx* ctx, int slot, pp_post_frame* f)
     PP_SET(f->boxes, P->boxes); PP_SET(f->nbox, P->nbox);
 }
 
+static int post_class_ranges(pp_ctx* ctx)
+{
+    for (int i = 0; i < ctx->cfg.num_classes; ++i)
+        if (ctx->cfg.class_end[i] > ctx->A) return pp_fail(ctx, PP_E_ARG, "class range exceeds anchor count");
+    return 0;
+}
+
+// The launch sequence, once for the batched pass and the stage entries (the sizes in slot 0's pp_post are those of every slot).
+// Selection, Q1 .. Q4, of g frames whose hist | counters are zero; marks: the stage mark in front of Q4
+template <class Src> static int post_select_stages(pp_ctx* ctx, Src src, int g, int nms_mode, int decode, bool marks, hipStream_t stream)
+{
+    const pp_post* P = (const pp_post*)ctx->slot[0].post;
+    const pp_config& c = ctx->cfg;
+    const int n = c.num_classes;
+    hipLaunchKernelGGL(post_filter<Src>, dim3(pp_div_up(P->cand_cap, 256 * FILTER_ITEMS), n, g), dim3(256), 0, stream, src, c, c.score_threshold,
+                       P->thr_bits, P->bin_shift, P->cand_cap);
+    hipLaunchKernelGGL(post_thresh<Src>, dim3(n, 1, g), dim3(1024), 0, stream, src, P->K);
+    hipLaunchKernelGGL(post_gather<Src>, dim3(pp_div_up(P->cand_cap, 256 * GATHER_ITEMS), n, g), dim3(256), 0, stream, src, P->cand_cap, P->thr_bits, P->bin_shift);
+    int rc_;
+    if (marks && (rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_TOPK))) return rc_;
+    hipLaunchKernelGGL(post_topk<Src>, dim3(n, 1, g), dim3(1024), 0, stream, src, c, P->cand_cap, P->K, ctx->anchors, nms_mode, decode);
+    return 0;
+}
+
+// NMS, Q5 + Q6, behind its stage mark: frame f of the g writes det + f * det_fs and det_count + f * PP_DET_COUNT_STRIDE
+template <class Src> static int post_nms_stages(pp_ctx* ctx, Src src, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream)
+{
+    const pp_post* P = (const pp_post*)ctx->slot[0].post;
+    const pp_config& c = ctx->cfg;
+    const int n = c.num_classes;
+    int rc_;
+    if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_NMS))) return rc_;
+    hipLaunchKernelGGL(nms_mask<Src>, dim3(P->cb, P->cb, n * g), dim3(64), 0, stream, src, n, P->K, P->cb, c.nms_iou_threshold, nms_mode);
+    hipLaunchKernelGGL(nms_reduce<Src>, dim3(1, 1, g), dim3(64 * PP_MAX_CLASSES), 0, stream, src, c, P->K, P->cb, det, (size_t)n * c.nms_post_max * 9,
+                       det_count, (int)PP_DET_COUNT_STRIDE);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// What the stage entries pp_postprocess and pp_select_candidates (`who`) share: the checks, and their frame -- slot 0's scratch
+// beside the caller's tensors, by value
+typedef pp_frames_one<pp_post_frame> post_one;
+static int post_entry_frame(pp_ctx* ctx, const char* who, bool have_ptrs, const float* cls, const float* box, const float* dir, const uint8_t* mask,
+                            post_one* src)
+{
+    if (!have_ptrs) return pp_fail(ctx, PP_E_ARG, (std::string(who) + ": null pointer").c_str());
+    if (ctx->A == 0) return pp_fail(ctx, PP_E_STATE, (std::string(who) + ": call pp_set_anchors first").c_str());
+    int rc = post_class_ranges(ctx);
+    if (rc) return rc;
+    pp_post_fill_table(ctx, 0, &src->f);
+    PP_SET(src->f.cls, cls); PP_SET(src->f.box, box); PP_SET(src->f.dir, dir); PP_SET(src->f.mask, mask);
+    return 0;
+}
+static size_t post_zero_bytes(pp_ctx* ctx) { return (size_t)ctx->cfg.num_classes * (NBINS + 8) * sizeof(int32_t); } // hist | counters
+
+extern "C" int pp_postprocess(pp_ctx* ctx, const float* cls, const float* box, const float* dir, const uint8_t* mask,
+                              float* det, int32_t* det_count, int nms_mode, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    post_one src = {};
+    int rc;
+    if ((rc = post_entry_frame(ctx, "pp_postprocess", cls && box && dir && mask && det && det_count, cls, box, dir, mask, &src))) return rc;
+    if ((rc = pp_stage_mark(ctx, stream, PP_ST_POST))) return rc;
+    PP_HIP(hipMemsetAsync(src.f.hist, 0, post_zero_bytes(ctx), stream));
+    if ((rc = post_select_stages(ctx, src, 1, nms_mode, 1, true, stream))) return rc;
+    if ((rc = post_nms_stages(ctx, src, 1, det, det_count, nms_mode, stream))) return rc;
+    return pp_stage_mark(ctx, stream, -1);
+}
+
+// Stage entry behind Inference.infer_torch (inference.py:140-189: per class mask gather, sigmoid, score threshold, top-k):
+// the selection stages of pp_postprocess alone.  idx i32[ncls][nms_pre_max] anchor ids by descending score (ties: lower
+// anchor id), score f32[ncls][nms_pre_max], count i32[ncls].
+extern "C" int pp_select_candidates(pp_ctx* ctx, const float* cls, const float* box, const float* dir, const uint8_t* mask,
+                                    int32_t* idx, float* score, int32_t* count, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    post_one src = {};
+    int rc;
+    if ((rc = post_entry_frame(ctx, "pp_select_candidates", cls && box && dir && mask && idx && score && count, cls, box, dir, mask, &src))) return rc;
+    PP_HIP(hipMemsetAsync(src.f.hist, 0, post_zero_bytes(ctx), stream));
+    if ((rc = post_select_stages(ctx, src, 1, 0, 1, false, stream))) return rc;
+    const pp_post* P = (const pp_post*)ctx->slot[0].post;
+    hipLaunchKernelGGL(post_export_sel, dim3(ctx->cfg.num_classes), dim3(256), 0, stream, P->sel, P->counters, P->K, idx, score, count);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
 // post-processing of frames b0 .. b0+g-1 as one launch per stage (blockIdx.z = frame)
 int pp_postprocess_group(pp_ctx* ctx, int b0, int g, float* det, int32_t* det_count, int nms_mode, hipStream_t stream, int defer_nb)
 {
-    const pp_post* P = (const pp_post*)ctx->slot[0].post; // sizes are the same for every slot
-    const pp_config& c = ctx->cfg;
-    const int n = c.num_classes;
-    for (int i = 0; i < n; ++i)
-        if (c.class_end[i] > ctx->A) return pp_fail(ctx, PP_E_ARG, "class range exceeds anchor count");
-    const pp_post_frame* tab = ctx->d_post + b0;
-    const size_t det_fs = (size_t)n * c.nms_post_max * 9;
-    hipLaunchKernelGGL(post_init_b, dim3(8, 1, g), dim3(256), 0, stream, tab, n * (NBINS + 8));
-    hipLaunchKernelGGL(post_filter_b, dim3(pp_div_up(P->cand_cap, 256 * FILTER_ITEMS), n, g), dim3(256), 0, stream, tab, c, c.score_threshold,
-                       P->thr_bits, P->bin_shift, P->cand_cap);
-    hipLaunchKernelGGL(post_thresh_b, dim3(n, 1, g), dim3(1024), 0, stream, tab, P->K);
-    hipLaunchKernelGGL(post_gather_b, dim3(pp_div_up(P->cand_cap, 256 * GATHER_ITEMS), n, g), dim3(256), 0, stream, tab, P->cand_cap, P->thr_bits, P->bin_shift);
+    const pp_post* P = (const pp_post*)ctx->slot[0].post;
+    const int n = ctx->cfg.num_classes;
     int rc_;
-    if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_TOPK))) return rc_;
-    hipLaunchKernelGGL(post_topk_b, dim3(n, 1, g), dim3(1024), 0, stream, tab, c, P->cand_cap, P->K, ctx->anchors, nms_mode, defer_nb > 0 ? 0 : 1);
+    if ((rc_ = post_class_ranges(ctx))) return rc_;
+    const pp_frames_tab<pp_post_frame> src = {ctx->d_post + b0};
+    hipLaunchKernelGGL(post_init_b, dim3(8, 1, g), dim3(256), 0, stream, src.tab, n * (NBINS + 8));
+    if ((rc_ = post_select_stages(ctx, src, g, nms_mode, defer_nb > 0 ? 0 : 1, true, stream))) return rc_;
     if (defer_nb > 0) { // deferred head: the selected anchors' box / dir logits, decoded (same stage mark)
         pp_head_gather hg;
         if ((rc_ = pp_net_head_gather(ctx, defer_nb, &hg))) return rc_;
         if (hg.K > CAND_MAXK || (hg.K & 31)) return pp_fail(ctx, PP_E_STATE, "candidate head: unexpected channel count");
-        hipLaunchKernelGGL(post_cand_b, dim3(pp_div_up(P->K, 16 * CAND_WAVES), n, g), dim3(64 * CAND_WAVES), 0, stream, tab, b0, P->K,
+        hipLaunchKernelGGL(post_cand_b, dim3(pp_div_up(P->K, 16 * CAND_WAVES), n, g), dim3(64 * CAND_WAVES), 0, stream, src.tab, b0, P->K,
                            ctx->H * ctx->W, ctx->anchors, nms_mode, hg);
     }
-    if ((rc_ = pp_stage_mark(ctx, stream, PP_ST_POST_NMS))) return rc_;
-    hipLaunchKernelGGL(nms_mask_b, dim3(P->cb, P->cb, n * g), dim3(64), 0, stream, tab, n, P->K, P->cb, c.nms_iou_threshold, nms_mode);
-    hipLaunchKernelGGL(nms_reduce_b, dim3(1, 1, g), dim3(64 * PP_MAX_CLASSES), 0, stream, tab, c, P->K, P->cb, det + (size_t)b0 * det_fs, det_fs,
-                       det_count + (size_t)b0 * PP_DET_COUNT_STRIDE, (int)PP_DET_COUNT_STRIDE);
-    PP_HIP(hipGetLastError());
-    return 0;
+    return post_nms_stages(ctx, src, g, det + (size_t)b0 * n * ctx->cfg.nms_post_max * 9, det_count + (size_t)b0 * PP_DET_COUNT_STRIDE, nms_mode, stream);
 }
 
 // ------------------------------------------------------------------------------------------
 // stateless box ops (framework/box_torch_ops.py:18-77, framework/nms.py:6-40, eval/iou.py:438-473)
 // ------------------------------------------------------------------------------------------
 namespace {
+
+// these entries have no context to report through: a launch error comes back as its negated HIP code
+int launch_rc()
+{
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(int)e;
+}
 
 __global__ void __launch_bounds__(256) k_box_decode(const float* __restrict__ enc, const float* __restrict__ anc, float* __restrict__ out, int64_t n)
 {
@@ -1022,9 +1020,9 @@ __global__ void __launch_bounds__(256) k_rotated_iou_eval(const float* __restric
     out[t] = v;
 }
 
-// sort dets by score (desc, ties by lower index) into nbox[n][6] (+ order[n]); one workgroup, n <= MAXK
+// sort dets by score (desc, ties by lower index) into nbox[n][6] (+ order[n]), n into the one class's counter block; one workgroup, n <= MAXK
 __global__ void __launch_bounds__(1024) k_nms_sort(const float* __restrict__ dets, int n, int stride, float* __restrict__ nbox,
-                                                   int32_t* __restrict__ order, int32_t* __restrict__ nsel)
+                                                   int32_t* __restrict__ order, int32_t* __restrict__ counters)
 {
     __shared__ uint64_t keys[MAXK];
     int n2 = 64;
@@ -1034,18 +1032,18 @@ __global__ void __launch_bounds__(1024) k_nms_sort(const float* __restrict__ det
         if (i < n) {
             uint32_t u = __float_as_uint(dets[(size_t)i * stride + stride - 1]);
             u = (u & 0x80000000u) ? ~u : (u | 0x80000000u); // total order on floats
-            k = ((uint64_t)u << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)i);
+            k = key_pack(u, (uint32_t)i);
             if (k == 0ull) k = 1ull;
         }
         keys[i] = k;
     }
     bitonic_desc(keys, n2);
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint32_t src = 0xFFFFFFFFu - (uint32_t)(keys[i] & 0xFFFFFFFFull);
+        const uint32_t src = key_index(keys[i]);
         order[i] = (int32_t)src;
         for (int q = 0; q < stride - 1; ++q) nbox[(size_t)i * 6 + q] = dets[(size_t)src * stride + q];
     }
-    if (threadIdx.x == 0) *nsel = n;
+    if (threadIdx.x == 0) counters[CNT_NSEL] = n;
 }
 
 __global__ void __launch_bounds__(64) k_nms_reduce(const uint64_t* __restrict__ mask, const int32_t* __restrict__ order, int n, int cb,
@@ -1065,8 +1063,7 @@ extern "C" int pp_box_decode(const float* enc, const float* anchors, float* out,
     if (n < 0 || (n > 0 && (!enc || !anchors || !out))) return PP_E_ARG;
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_box_decode, dim3(pp_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, enc, anchors, out, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return launch_rc();
 }
 
 extern "C" int pp_corners2d(const float* centers, const float* dims, const float* angles, float* corners, int64_t n, void* stream)
@@ -1074,8 +1071,7 @@ extern "C" int pp_corners2d(const float* centers, const float* dims, const float
     if (n < 0 || (n > 0 && (!centers || !dims || !corners))) return PP_E_ARG;
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_corners2d, dim3(pp_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, centers, dims, angles, corners, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return launch_rc();
 }
 
 extern "C" int pp_standup2d(const float* corners, float* boxes, int64_t n, void* stream)
@@ -1083,8 +1079,7 @@ extern "C" int pp_standup2d(const float* corners, float* boxes, int64_t n, void*
     if (n < 0 || (n > 0 && (!corners || !boxes))) return PP_E_ARG;
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_standup2d, dim3(pp_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, corners, boxes, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return launch_rc();
 }
 
 extern "C" int pp_rotated_iou(const float* a, const float* b, float* iou, int n, int m, void* stream)
@@ -1092,8 +1087,7 @@ extern "C" int pp_rotated_iou(const float* a, const float* b, float* iou, int n,
     if (n < 0 || m < 0 || ((int64_t)n * m > 0 && (!a || !b || !iou))) return PP_E_ARG;
     if ((int64_t)n * m == 0) return 0;
     hipLaunchKernelGGL(k_rotated_iou, dim3(pp_div_up((int64_t)n * m, 256)), dim3(256), 0, (hipStream_t)stream, a, b, iou, n, m);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return launch_rc();
 }
 
 extern "C" int pp_rotated_iou_eval(const float* boxes, const float* qboxes, float* out, int n, int k, int criterion, void* stream)
@@ -1102,8 +1096,7 @@ extern "C" int pp_rotated_iou_eval(const float* boxes, const float* qboxes, floa
     if (n == 0 || k == 0) return 0;
     if (!boxes || !qboxes || !out) return PP_E_ARG;
     hipLaunchKernelGGL(k_rotated_iou_eval, dim3(pp_div_up((int64_t)n * k, 256)), dim3(256), 0, (hipStream_t)stream, boxes, qboxes, out, n, k, criterion);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return launch_rc();
 }
 
 extern "C" int pp_nms(const float* dets, int n, int stride, float thresh, int32_t* keep, int32_t* nkeep, int rotate, void* stream_)
@@ -1116,7 +1109,7 @@ extern "C" int pp_nms(const float* dets, int n, int stride, float thresh, int32_
         return e0 == hipSuccess ? 0 : -(int)e0;
     }
     const int cb = pp_div_up(n, 64);
-    // stream-ordered scratch: sorted boxes, order, tmp keep, nsel, mask
+    // stream-ordered scratch: sorted boxes, order, tmp keep, counters[8], mask -- one class of K = n boxes to nms_mask
     size_t bytes = (size_t)n * 6 * 4 + (size_t)n * 4 * 2 + 64 + (size_t)n * cb * 8 + 256;
     char* ws = nullptr;
     hipError_t e = hipMallocAsync((void**)&ws, bytes, stream);
@@ -1125,9 +1118,10 @@ extern "C" int pp_nms(const float* dets, int n, int stride, float thresh, int32_
     float* nbox = (float*)(ws + (size_t)n * cb * 8);
     int32_t* order = (int32_t*)(nbox + (size_t)n * 6);
     int32_t* tmp = order + n;
-    int32_t* nsel = tmp + n;
-    hipLaunchKernelGGL(k_nms_sort, dim3(1), dim3(1024), 0, stream, dets, n, stride, nbox, order, nsel);
-    hipLaunchKernelGGL(nms_mask, dim3(cb, cb, 1), dim3(64), 0, stream, nbox, 6, nsel, 0, n, cb, thresh, rotate, mask);
+    post_one src = {};
+    PP_SET(src.f.nbox, nbox); PP_SET(src.f.counters, tmp + n); PP_SET(src.f.nmask, mask);
+    hipLaunchKernelGGL(k_nms_sort, dim3(1), dim3(1024), 0, stream, dets, n, stride, nbox, order, tmp + n);
+    hipLaunchKernelGGL(nms_mask<post_one>, dim3(cb, cb, 1), dim3(64), 0, stream, src, 1, n, cb, thresh, rotate);
     hipLaunchKernelGGL(k_nms_reduce, dim3(1), dim3(64), 0, stream, mask, order, n, cb, tmp, keep, nkeep);
     e = hipGetLastError();
     hipError_t e2 = hipFreeAsync(ws, stream);

@@ -15,9 +15,11 @@
         if (e_ != hipSuccess) return pp_fail_hip(ctx, e_, #call, __FILE__, __LINE__); \
     } while (0)
 
-// ---- frame tables of the batched integer stages (pp_infer_batch) ---------------------------------
-// The voxeliser / mask / PFN / post-processing kernels of a batch run as ONE launch per stage with
-// blockIdx.z = frame; each frame's buffers are looked up in a device-resident table built once.
+// ---- frames of the integer stages ------------------------------------------------------------------
+// The voxeliser / mask / PFN / post-processing kernels of a batch (pp_infer_batch) run as ONE launch per stage with
+// blockIdx.z = frame; each frame's buffers are looked up in a device-resident table built once.  A stage kernel is a template on
+// where its frame comes from (pp_frames_tab / pp_frames_one below): the table, or one entry passed by value for the single-stage
+// entry points (grid.z = 1), which put the caller's pointers beside slot 0's scratch.
 // Device side: the table entries are typed as GLOBAL pointers.  A pointer loaded from memory carries no address space, so every
 // access through these tables used to be flat_load / flat_store (both wait counters, conservative s_waitcnt 0 around each); typed,
 // the inlined stage bodies get global_load / global_store.  Same 8-byte layout on the host, which fills the tables.
@@ -41,6 +43,18 @@ struct pp_post_frame {
     uint64_t PP_GP *cand, *shortl, *sel, *nmask;
     int32_t PP_GP *counters, *hist, *dirl;
     float PP_GP *boxes, *nbox;
+};
+// frame source of a stage kernel, its first argument (the voxeliser's second, behind the clouds): `const F f = src.get();`, or
+// src.at(fr) where blockIdx.z is not the frame alone
+template <class F> struct pp_frames_tab { // pp_infer_batch: entries of ctx->d_pre / d_post
+    const F* tab;
+    __device__ F at(int fr) const { return tab[fr]; }
+    __device__ F get() const { return tab[blockIdx.z]; }
+};
+template <class F> struct pp_frames_one { // the single-stage entry points
+    F f;
+    __device__ F at(int) const { return f; }
+    __device__ F get() const { return f; }
 };
 #define PP_GROUP 32 // frames per batched launch of the integer stages (kernel-argument table size: 384 B of the 4 KB)
 struct pp_in_group {
@@ -167,12 +181,6 @@ int pp_net_create(pp_ctx* ctx);
 void pp_net_destroy(pp_ctx* ctx);
 int pp_net_commit(pp_ctx* ctx);
 int pp_post_create(pp_ctx* ctx);
-// slot-aware internals of the public single-frame entry points
-int pp_voxelize_slot(pp_ctx* ctx, int s, const float* pts, int n, int nfeat, float* voxels, int32_t* coors, int32_t* npts,
-                     int32_t* num_pillars, hipStream_t stream);
-int pp_anchor_mask_slot(pp_ctx* ctx, int s, const int32_t* coors, const int32_t* num_pillars, uint8_t* mask, hipStream_t stream);
-int pp_postprocess_slot(pp_ctx* ctx, int s, const float* cls, const float* box, const float* dir, const uint8_t* mask, float* det,
-                        int32_t* det_count, int nms_mode, hipStream_t stream);
 // nb canvases (or, when pmap != nullptr, nb sparse BEV inputs: pillar-index maps + PFN rows) -> pre-norm [nb,320,H,W] + stats
 int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream, const int32_t* pmap, const float* feat);
 int pp_pillar_map(pp_ctx* ctx, const int32_t* coors, const int32_t* num_pillars, int32_t* pmap, hipStream_t stream);

@@ -153,34 +153,33 @@ __device__ __forceinline__ void vox_gather_body(const float* __restrict__ pts, i
     }
 }
 
-// ---- single-frame entry kernels and their batched twins (blockIdx.z = frame, buffers from the frame table) ----
-__global__ void __launch_bounds__(256) vox_cell_first(const float* __restrict__ pts, int n, int nfeat, pp_config cfg,
-                                                      int32_t* __restrict__ pt_cell, int32_t* __restrict__ cell_first)
+// ---- the kernels: a frame's buffers come from `src` (pp_common.h), its cloud from `in` -- blockIdx.z = frame of a batch, or the one
+// frame of pp_voxelize.  The bodies above stay device functions: __restrict__ on their parameters is part of what the compiler
+// schedules them by. ----
+template <class Src> __global__ void __launch_bounds__(256) vox_cell_first(pp_in_group in, Src src, int nfeat, pp_config cfg)
 {
-    vox_cell_first_body(pts, n, nfeat, cfg, pt_cell, cell_first);
+    const pp_pre_frame F = src.get();
+    vox_cell_first_body(in.pts[blockIdx.z], in.n[blockIdx.z], nfeat, cfg, F.pt_cell, F.cell_first);
 }
-__global__ void __launch_bounds__(256) vox_flag_count(const int32_t* __restrict__ pt_cell, const int32_t* __restrict__ cell_first, int n,
-                                                      int32_t* __restrict__ wave_cnt)
+template <class Src> __global__ void __launch_bounds__(256) vox_flag_count(pp_in_group in, Src src)
 {
-    vox_flag_count_body(pt_cell, cell_first, n, wave_cnt);
+    const pp_pre_frame F = src.get();
+    vox_flag_count_body(F.pt_cell, F.cell_first, in.n[blockIdx.z], F.wave_cnt);
 }
-__global__ void __launch_bounds__(256) vox_rank(const float* __restrict__ pts, int n, int nfeat, pp_config cfg,
-                                                const int32_t* __restrict__ pt_cell, const int32_t* __restrict__ cell_first,
-                                                const int32_t* __restrict__ wave_cnt, int32_t* __restrict__ pt_rank,
-                                                int32_t* __restrict__ coors, int32_t* __restrict__ scalars, int32_t* __restrict__ num_pillars)
+template <class Src> __global__ void __launch_bounds__(256) vox_rank(pp_in_group in, Src src, int nfeat, pp_config cfg)
 {
-    vox_rank_body(pts, n, nfeat, cfg, pt_cell, cell_first, wave_cnt, pt_rank, coors, scalars, num_pillars);
+    const pp_pre_frame F = src.get();
+    vox_rank_body(in.pts[blockIdx.z], in.n[blockIdx.z], nfeat, cfg, F.pt_cell, F.cell_first, F.wave_cnt, F.pt_rank, F.coors, F.scalars, F.num);
 }
-__global__ void __launch_bounds__(256) vox_insert(int n, pp_config cfg, const int32_t* __restrict__ pt_cell,
-                                                  const int32_t* __restrict__ cell_first, const int32_t* __restrict__ pt_rank,
-                                                  const int32_t* __restrict__ scalars, int32_t* __restrict__ slots)
+template <class Src> __global__ void __launch_bounds__(256) vox_insert(pp_in_group in, Src src, pp_config cfg)
 {
-    vox_insert_body(n, cfg, pt_cell, cell_first, pt_rank, scalars, slots);
+    const pp_pre_frame F = src.get();
+    vox_insert_body(in.n[blockIdx.z], cfg, F.pt_cell, F.cell_first, F.pt_rank, F.scalars, F.slots);
 }
-__global__ void __launch_bounds__(256) vox_gather(const float* __restrict__ pts, int nfeat, pp_config cfg, const int32_t* __restrict__ slots,
-                                                  const int32_t* __restrict__ num_pillars, float* __restrict__ voxels, int32_t* __restrict__ npts)
+template <class Src> __global__ void __launch_bounds__(256) vox_gather(pp_in_group in, Src src, int nfeat, pp_config cfg)
 {
-    vox_gather_body(pts, nfeat, cfg, slots, num_pillars, voxels, npts);
+    const pp_pre_frame F = src.get();
+    vox_gather_body(in.pts[blockIdx.z], nfeat, cfg, F.slots, F.num, F.voxels, F.npts);
 }
 
 // one fill for everything the integer stages of a frame need initialised: cell_first | slots | scalars (0x7F..),
@@ -193,45 +192,37 @@ __global__ void __launch_bounds__(256) pre_init_b(const pp_pre_frame* __restrict
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nocc; i += stride) F.occ[i] = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npmap; i += stride) F.pmap[i] = -1;
 }
-__global__ void __launch_bounds__(256) vox_cell_first_b(pp_in_group in, const pp_pre_frame* __restrict__ tab, int nfeat, pp_config cfg)
-{
-    const pp_pre_frame F = tab[blockIdx.z];
-    vox_cell_first_body(in.pts[blockIdx.z], in.n[blockIdx.z], nfeat, cfg, F.pt_cell, F.cell_first);
-}
-__global__ void __launch_bounds__(256) vox_flag_count_b(pp_in_group in, const pp_pre_frame* __restrict__ tab)
-{
-    const pp_pre_frame F = tab[blockIdx.z];
-    vox_flag_count_body(F.pt_cell, F.cell_first, in.n[blockIdx.z], F.wave_cnt);
-}
-__global__ void __launch_bounds__(256) vox_rank_b(pp_in_group in, const pp_pre_frame* __restrict__ tab, int nfeat, pp_config cfg)
-{
-    const pp_pre_frame F = tab[blockIdx.z];
-    vox_rank_body(in.pts[blockIdx.z], in.n[blockIdx.z], nfeat, cfg, F.pt_cell, F.cell_first, F.wave_cnt, F.pt_rank, F.coors, F.scalars, F.num);
-}
-__global__ void __launch_bounds__(256) vox_insert_b(pp_in_group in, const pp_pre_frame* __restrict__ tab, pp_config cfg)
-{
-    const pp_pre_frame F = tab[blockIdx.z];
-    vox_insert_body(in.n[blockIdx.z], cfg, F.pt_cell, F.cell_first, F.pt_rank, F.scalars, F.slots);
-}
-__global__ void __launch_bounds__(256) vox_gather_b(pp_in_group in, const pp_pre_frame* __restrict__ tab, int nfeat, pp_config cfg)
-{
-    const pp_pre_frame F = tab[blockIdx.z];
-    vox_gather_body(in.pts[blockIdx.z], nfeat, cfg, F.slots, F.num, F.voxels, F.npts);
-}
 
 } // namespace
+
+// K1 .. K5 for g frames of at most nmax points; cell_first | slots | scalars hold PP_EMPTY on entry
+template <class Src> static int voxelize_stages(pp_ctx* ctx, Src src, int g, const pp_in_group& in, int nmax, hipStream_t stream)
+{
+    const pp_config& cfg = ctx->cfg;
+    const int nfeat = cfg.num_point_features;
+    const int nb = pp_div_up(nmax > 0 ? nmax : 1, 256);
+    hipLaunchKernelGGL(vox_cell_first<Src>, dim3(nb, 1, g), dim3(256), 0, stream, in, src, nfeat, cfg);
+    hipLaunchKernelGGL(vox_flag_count<Src>, dim3(nb, 1, g), dim3(256), 0, stream, in, src);
+    hipLaunchKernelGGL(vox_rank<Src>, dim3(nb, 1, g), dim3(256), 0, stream, in, src, nfeat, cfg);
+    hipLaunchKernelGGL(vox_insert<Src>, dim3(nb, 1, g), dim3(256), 0, stream, in, src, cfg);
+    const int nt = cfg.max_voxels * cfg.max_num_points;
+    hipLaunchKernelGGL(vox_gather<Src>, dim3(pp_div_up(nt, 256), 1, g), dim3(256), 0, stream, in, src, nfeat, cfg);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// cell_first | slots | vox_scalars are one allocation (pp_api.hip): a single fill of this many words
+static size_t vox_fill_words(const pp_config& cfg)
+{
+    return (size_t)cfg.grid_size[0] * cfg.grid_size[1] * cfg.grid_size[2] + (size_t)cfg.max_voxels * cfg.max_num_points + 4;
+}
 
 extern "C" int pp_voxelize(pp_ctx* ctx, const float* pts, int n, int nfeat, float* voxels, int32_t* coors,
                            int32_t* npts, int32_t* num_pillars, void* stream_)
 {
     if (!ctx) return PP_E_ARG;
-    return pp_voxelize_slot(ctx, 0, pts, n, nfeat, voxels, coors, npts, num_pillars, (hipStream_t)stream_);
-}
-
-int pp_voxelize_slot(pp_ctx* ctx, int si, const float* pts, int n, int nfeat, float* voxels, int32_t* coors, int32_t* npts,
-                     int32_t* num_pillars, hipStream_t stream)
-{
-    pp_slot& S = ctx->slot[si];
+    hipStream_t stream = (hipStream_t)stream_;
+    const pp_slot& S = ctx->slot[0];
     const pp_config& cfg = ctx->cfg;
     if (n < 0 || n > cfg.max_points) return pp_fail(ctx, PP_E_ARG, "pp_voxelize: n exceeds cfg.max_points");
     if (nfeat != cfg.num_point_features || nfeat < 3) return pp_fail(ctx, PP_E_ARG, "pp_voxelize: nfeat mismatch");
@@ -240,21 +231,15 @@ int pp_voxelize_slot(pp_ctx* ctx, int si, const float* pts, int n, int nfeat, fl
         PP_HIP(hipMemsetAsync(num_pillars, 0, sizeof(int32_t), stream));
         return 0;
     }
-    size_t cells = (size_t)cfg.grid_size[0] * cfg.grid_size[1] * cfg.grid_size[2];
-    // cell_first | slots | vox_scalars are one allocation (pp_api.hip): a single fill
-    PP_HIP(hipMemsetAsync(S.cell_first, 0x7F, (cells + (size_t)cfg.max_voxels * cfg.max_num_points + 4) * sizeof(int32_t), stream));
-    int nb = pp_div_up(n, 256);
-    hipLaunchKernelGGL(vox_cell_first, dim3(nb), dim3(256), 0, stream, pts, n, nfeat, cfg, S.pt_cell, S.cell_first);
-    hipLaunchKernelGGL(vox_flag_count, dim3(nb), dim3(256), 0, stream, S.pt_cell, S.cell_first, n, S.wave_cnt);
-    hipLaunchKernelGGL(vox_rank, dim3(nb), dim3(256), 0, stream, pts, n, nfeat, cfg, S.pt_cell, S.cell_first,
-                       S.wave_cnt, S.pt_rank, coors, S.vox_scalars, num_pillars);
-    hipLaunchKernelGGL(vox_insert, dim3(nb), dim3(256), 0, stream, n, cfg, S.pt_cell, S.cell_first, S.pt_rank,
-                       S.vox_scalars, S.slots);
-    int nt = cfg.max_voxels * cfg.max_num_points;
-    hipLaunchKernelGGL(vox_gather, dim3(pp_div_up(nt, 256)), dim3(256), 0, stream, pts, nfeat, cfg, S.slots, num_pillars,
-                       voxels, npts);
-    PP_HIP(hipGetLastError());
-    return 0;
+    pp_pre_frame f = {};
+    PP_SET(f.pt_cell, S.pt_cell); PP_SET(f.cell_first, S.cell_first); PP_SET(f.wave_cnt, S.wave_cnt); PP_SET(f.pt_rank, S.pt_rank);
+    PP_SET(f.slots, S.slots); PP_SET(f.scalars, S.vox_scalars);
+    PP_SET(f.voxels, voxels); PP_SET(f.coors, coors); PP_SET(f.npts, npts); PP_SET(f.num, num_pillars);
+    pp_in_group in = {};
+    in.pts[0] = pts;
+    in.n[0] = n;
+    PP_HIP(hipMemsetAsync(S.cell_first, 0x7F, vox_fill_words(cfg) * sizeof(int32_t), stream));
+    return voxelize_stages(ctx, pp_frames_one<pp_pre_frame>{f}, 1, in, n, stream);
 }
 
 int pp_voxelize_group(pp_ctx* ctx, int b0, int g, const pp_in_group& in, hipStream_t stream)
@@ -267,20 +252,9 @@ int pp_voxelize_group(pp_ctx* ctx, int b0, int g, const pp_in_group& in, hipStre
         nmax = in.n[i] > nmax ? in.n[i] : nmax;
     }
     const pp_pre_frame* tab = ctx->d_pre + b0;
-    const int nfeat = cfg.num_point_features;
-    const size_t cells = (size_t)cfg.grid_size[0] * cfg.grid_size[1] * cfg.grid_size[2];
-    const int n7f = (int)(cells + (size_t)cfg.max_voxels * cfg.max_num_points + 4);
     const int nbev = ctx->gx * ctx->gy;
-    hipLaunchKernelGGL(pre_init_b, dim3(256, 1, g), dim3(256), 0, stream, tab, n7f, nbev, nbev);
-    const int nb = pp_div_up(nmax > 0 ? nmax : 1, 256);
-    hipLaunchKernelGGL(vox_cell_first_b, dim3(nb, 1, g), dim3(256), 0, stream, in, tab, nfeat, cfg);
-    hipLaunchKernelGGL(vox_flag_count_b, dim3(nb, 1, g), dim3(256), 0, stream, in, tab);
-    hipLaunchKernelGGL(vox_rank_b, dim3(nb, 1, g), dim3(256), 0, stream, in, tab, nfeat, cfg);
-    hipLaunchKernelGGL(vox_insert_b, dim3(nb, 1, g), dim3(256), 0, stream, in, tab, cfg);
-    const int nt = cfg.max_voxels * cfg.max_num_points;
-    hipLaunchKernelGGL(vox_gather_b, dim3(pp_div_up(nt, 256), 1, g), dim3(256), 0, stream, in, tab, nfeat, cfg);
-    PP_HIP(hipGetLastError());
-    return 0;
+    hipLaunchKernelGGL(pre_init_b, dim3(256, 1, g), dim3(256), 0, stream, tab, (int)vox_fill_words(cfg), nbev, nbev);
+    return voxelize_stages(ctx, pp_frames_tab<pp_pre_frame>{tab}, g, in, nmax, stream);
 }
 
 // ---- sensor_msgs/PointCloud2 payload -> f32[n,4] (ros_node.py:55-59; sensor_msgs.point_cloud2.read_points) --------

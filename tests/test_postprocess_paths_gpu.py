@@ -115,8 +115,8 @@ CLOUD_SEEDS = (1000, 1001, 1002)
 
 
 def test_whole_network_batched_at_k1153(synth):
-    """pp_infer_batch with nms_pre_max 1153 / nms_post_max 1024 / IoU 0.5 (cb = 19 column tiles: post_cand_b, nms_mask_b and
-    nms_reduce_b index by a K that is no multiple of 64), three frames, AABB mode, head deferral on and off: each frame's
+    """pp_infer_batch with nms_pre_max 1153 / nms_post_max 1024 / IoU 0.5 (cb = 19 column tiles: post_cand_b, nms_mask and
+    nms_reduce index by a K that is no multiple of 64), three frames, AABB mode, head deferral on and off: each frame's
     detections are the parameterised oracle's on that frame's own logits (counts exactly, rows within 2e-5), and the two head
     modes are bit-equal.
     cls_bias None (the random-init head) was the first value tried and holds: candidates per class on an MI355X
