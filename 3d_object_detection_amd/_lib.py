@@ -66,6 +66,8 @@ PROTOTYPES = {
     "pp_fetch_frame_tensor": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p]),
     "pp_debug_layer": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_debug_layer_skip": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p]),
+    "pp_debug_head_cls": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_int, c_p, c_p, c_p, c_p]),
+    "pp_head_cls_tiling": (ctypes.c_char_p, [c_p]),
     "pp_set_head_defer": (ctypes.c_int, [c_p, ctypes.c_int]),
     "pp_head_defer_active": (ctypes.c_int, [c_p]),
     "pp_set_sparse_conv1": (ctypes.c_int, [c_p, ctypes.c_int]),
@@ -130,6 +132,7 @@ PROTOTYPES = {
     "pp_weight_image": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), c_p]),
     "pp_tune_export": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     "pp_tune_import": (ctypes.c_int, [ctypes.c_char_p]),
+    "pp_menu_names": (ctypes.c_int, [ctypes.c_int] * 12 + [ctypes.c_char_p, ctypes.c_int]),
     "pp_version": (ctypes.c_int, []),
 }
 

@@ -253,6 +253,36 @@ extern "C" int pp_debug_layer_skip(pp_ctx* ctx, int layer, int nb, const void* i
     return 0;
 }
 
+// Test hook: the cls-only head pass of the deferred head -- launch_head_cls with the committed cls tiling on the head's image -- on
+// caller tensors; see include/pp_hip.h.  Writes only cls_out.
+extern "C" int pp_debug_head_cls(pp_ctx* ctx, int nb, const void* in, int pre_mode, const float* scale, const float* shift, float* cls_out, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->net || !ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_debug_head_cls: weights not committed");
+    pp_net* net = (pp_net*)ctx->net;
+    if (!net->defer_ok) return pp_fail(ctx, PP_E_STATE, "pp_debug_head_cls: the committed plan has no deferred head (fp32 mode, 9-anchor head on a gemm1x1 tiling)");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_debug_head_cls: nb must be 1 .. cfg.max_batch");
+    if (!in) return pp_fail(ctx, PP_E_ARG, "pp_debug_head_cls: null input");
+    if (!cls_out) return pp_fail(ctx, PP_E_ARG, "pp_debug_head_cls: null output");
+    if (pre_mode < 0 || pre_mode > 2) return pp_fail(ctx, PP_E_ARG, "pp_debug_head_cls: pre_mode must be 0 (raw), 1 (shared affine) or 2 (per-frame affine)");
+    if ((pre_mode != 0) != (scale != nullptr) || (pre_mode != 0) != (shift != nullptr))
+        return pp_fail(ctx, PP_E_ARG, "pp_debug_head_cls: scale and shift go with pre_mode 1 / 2 and with nothing else");
+    const int cin = net->layers.back().cin;
+    NormRef pre;
+    if (pre_mode) { pre.mode = PRE_AFFINE; pre.scale = const_cast<float*>(scale); pre.shift = const_cast<float*>(shift); pre.C = cin; pre.aff_fs = pre_mode == 2 ? (size_t)cin : 0; }
+    const int rc = launch_head_cls(ctx, net->cls_var, (const float*)in, pre, cls_out, nb, (hipStream_t)stream_);
+    if (rc == PP_E_ARG) return pp_fail(ctx, PP_E_ARG, "pp_debug_head_cls: the cls tiling does not take the head's map");
+    return rc;
+}
+
+// The committed tiling of the cls-only head pass ("" when the plan has no deferred head)
+extern "C" const char* pp_head_cls_tiling(pp_ctx* ctx)
+{
+    if (!ctx || !ctx->net || !ctx->weights_ready) return "";
+    const pp_net* net = (const pp_net*)ctx->net;
+    return net->defer_ok ? net->cls_var.name : "";
+}
+
 extern "C" int pp_profile_begin(pp_ctx* ctx)
 {
     if (!ctx) return PP_E_ARG;

@@ -108,6 +108,7 @@ const Variant& strip_h(Family f); // 64 px wide, 4 px tall
 bool variant_ok(const Variant& v, int rows);
 bool shape_ok(const Variant& v, int Hin, int Win, int Wout);
 size_t layer_lds(const Variant& v, int cin);
+bool tiling_legal(const Variant& v, int rows, int cin, int Hin, int Win, int Wout); // variant_ok, shape_ok and the LDS budget: the tuner's rule
 bool finalises_in_prologue(Family f);
 double executed_ratio(const Variant& v);
 // L.var's image of the layer's host weights -> L.w (replaces the device copy).  index_positions: the transform (U = G g G^T of the

@@ -14,6 +14,9 @@ namespace ppc {
 
 // The tilings a layer may run, composed from what the families export (conv_common.h).  Content and order are part of the plan: the
 // order decides menu[0], the tuner's ties and what PP_AUTOTUNE=0 takes, and menu.size() is in the tune-cache key (autotune_layer).
+// Tests read the menus back through pp_menu_names and pin entry i of every menu in turn (tests/test_menu_exact_gpu.py): a new entry
+// is picked up by those slot tests automatically, as long as the menu stays within their MENU_SLOTS (32) entries -- tests/test_menu_cpu.py
+// goes red beyond that.
 static void layer_menu(int kind, int stride, int up, std::vector<Variant>& menu, int cin = 0, bool roofline_layer = false, bool head9 = true, int prec = 0,
                 bool first_conv = false)
 {
@@ -102,6 +105,12 @@ bool shape_ok(const Variant& v, int Hin, int Win, int Wout)
 }
 // LDS bytes of a launch of v on a layer with cin input channels (gemm1x1 keeps the whole [K][BM] weight slab)
 size_t layer_lds(const Variant& v, int cin) { return v.family == Family::Gemm1x1 ? g1_lds(v, cin) : v.lds; }
+// May tiling v run a layer of `rows` GEMM rows and cin input channels on these maps?  The one statement of the rule: the tuner
+// (autotune_layer) and pp_menu_names both ask here.
+bool tiling_legal(const Variant& v, int rows, int cin, int Hin, int Win, int Wout)
+{
+    return variant_ok(v, rows) && shape_ok(v, Hin, Win, Wout) && layer_lds(v, cin) <= (size_t)160 * 1024;
+}
 // One frame per launch: the families that finalise the producer's statistics in their own prologue, instead of a norm_finalize
 // launch in front of the layer -- 14 launches of 4.7 us + a boundary each per frame at batch 1.  (Batched launches keep
 // norm_finalize: a persistent workgroup would redo the fp64 finalisation at every frame change.)
@@ -359,6 +368,23 @@ static int time_layer(pp_ctx* ctx, Layer& L, const std::vector<Variant>& legal, 
     return 0;
 }
 
+// PP_FORCE_VARIANT (tests): pin a tiling by name substring; "a;b": a where `ok` has one, else b.  The first entry of `ok` that a name
+// matches goes to `out`.
+static bool forced_variant(const std::vector<Variant>& ok, Variant& out)
+{
+    const char* force = getenv("PP_FORCE_VARIANT");
+    if (!force) return false;
+    const std::string all(force);
+    for (size_t p = 0; p <= all.size();) {
+        const size_t e = std::min(all.find(';', p), all.size());
+        const std::string one = all.substr(p, e - p);
+        for (const Variant& v : ok)
+            if (strstr(v.name, one.c_str())) { out = v; return true; }
+        p = e + 1;
+    }
+    return false;
+}
+
 // The tiling of one layer: PP_FORCE_VARIANT, the tune cache, or (measure) the fastest legal entry of its menu on the device.
 // `shape` carries the layer's maps and the tuner's tensors.
 static int autotune_layer(pp_ctx* ctx, Layer& L, const ConvCall& shape, bool verbose, bool measure)
@@ -366,9 +392,7 @@ static int autotune_layer(pp_ctx* ctx, Layer& L, const ConvCall& shape, bool ver
     pp_net* net = (pp_net*)ctx->net;
     const int eprec = net->eff_prec, rows = layer_rows(ctx, L);
     const bool head9 = ctx->cfg.num_anchor_per_loc == 9, roofline = L.kind == 0 && L.stride == 1 && L.level == 0;
-    auto legal = [&](const Variant& v) {
-        return variant_ok(v, rows) && shape_ok(v, shape.Hin, shape.Win, shape.Wout) && layer_lds(v, L.cin) <= (size_t)160 * 1024;
-    };
+    auto legal = [&](const Variant& v) { return tiling_legal(v, rows, L.cin, shape.Hin, shape.Win, shape.Wout); };
     std::vector<Variant> menu, ok;
     layer_menu(L.kind, L.stride, L.up, menu, L.cin, roofline, head9, eprec, L.kind == 0 && L.stride == 2 && L.level == 0);
     std::copy_if(menu.begin(), menu.end(), std::back_inserter(ok), legal);
@@ -391,16 +415,7 @@ static int autotune_layer(pp_ctx* ctx, Layer& L, const ConvCall& shape, bool ver
     char sig[160];
     snprintf(sig, sizeof(sig), "v%d m%d k%d s%d u%d c%d r%d %dx%d n%d b%d p%d", pp_version(), (int)menu.size(), L.kind, L.stride, L.up, L.cin, L.cout,
              shape.Hout, shape.Wout, ctx->cfg.norm_kind, tune_frames(ctx), eprec);
-    if (const char* force = getenv("PP_FORCE_VARIANT")) { // tests: pin a tiling family by name substring; "a;b": a where a layer has one, else b
-        const std::string all(force);
-        for (size_t p = 0; p <= all.size();) {
-            const size_t e = std::min(all.find(';', p), all.size());
-            const std::string one = all.substr(p, e - p);
-            for (const Variant& v : ok)
-                if (strstr(v.name, one.c_str())) { L.var = v; return 0; }
-            p = e + 1;
-        }
-    }
+    if (forced_variant(ok, L.var)) return 0;
     auto hit = tune_cache().find(sig);
     if (hit != tune_cache().end())
         for (const Variant& v : menu)
@@ -418,6 +433,7 @@ static int autotune_head_cls(pp_ctx* ctx, float* tin, bool verbose, bool measure
         PP_HIP(hipFuncSetAttribute((const void*)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g1_lds(v, 320)));
     net->cls_var = menu[0];
     if (!measure) return 0;
+    if (forced_variant(menu, net->cls_var)) return 0; // like a layer's tiling: before the cache and the timing
     const int tb = tune_frames(ctx);
     char sig[160];
     snprintf(sig, sizeof(sig), "v%d m%d headcls %s %dx%d n%d b%d", pp_version(), (int)menu.size(), net->layers.back().var.name, ctx->H, ctx->W, ctx->cfg.norm_kind, tb);
@@ -441,6 +457,33 @@ static int autotune_head_cls(pp_ctx* ctx, float* tin, bool verbose, bool measure
 } // namespace ppc
 
 using namespace ppc;
+
+// The tiling names of one menu, in menu order, one per line -- stateless and without a HIP call, so tests enumerate the menus on a
+// machine without a device (include/pp_hip.h).
+extern "C" int pp_menu_names(int which, int kind, int stride, int up, int cin, int prec, int head9, int first_conv, int rows, int Hin, int Win, int Wout,
+                             char* buf, int cap)
+{
+    std::vector<Variant> menu;
+    if (which == 0) {
+        if (kind < 0 || kind > 2 || prec < 0 || prec > 4 || (kind == 0 && stride != 1 && stride != 2) || (kind == 1 && up != 1 && up != 2 && up != 4)) return -1;
+        // (the level-0 twin of a Winograd tiling -- layer_menu's roofline_layer -- has the name, the shape and the rules of the plain one)
+        layer_menu(kind, stride, up, menu, cin, false, head9 != 0, prec, first_conv != 0);
+    } else if (which == 1) {
+        gemm1x1_cls_menu(menu);
+    } else if (which == 2) {
+        for (Family f : {Family::Wino4, Family::Wino6}) { menu.push_back(strip_v(f)); menu.push_back(strip_h(f)); }
+    } else
+        return -1;
+    std::string t;
+    for (const Variant& v : menu)
+        if (rows <= 0 || tiling_legal(v, rows, cin, Hin, Win, Wout)) t += std::string(v.name) + "\n";
+    if (buf && cap > 0) {
+        const size_t n = std::min((size_t)cap - 1, t.size());
+        memcpy(buf, t.data(), n);
+        buf[n] = 0;
+    }
+    return (int)t.size();
+}
 
 int pp_net_create(pp_ctx* ctx)
 {

@@ -978,6 +978,40 @@ class Engine:
         ret = (out, box, dr) if kind == 2 else out
         return (ret, st) if stats else ret
 
+    def head_cls_tiling(self):
+        """Name of the committed tiling of the cls-only head pass (pp_head_cls_tiling); "" when the plan has no deferred head."""
+        return self.lib.pp_head_cls_tiling(self.ctx).decode()
+
+    def debug_head_cls(self, x, scale=None, shift=None):
+        """Test hook (pp_debug_head_cls): the cls-only pass of the deferred head -- the committed cls tiling on the head's weight image --
+        on caller tensors.  x f32[nb,320,H,W]; scale / shift f32[320] or f32[nb,320] as debug_layer takes them.  Returns cls f32[nb,A,1].
+        Raises RuntimeError when the committed plan has no deferred head."""
+        if not self.weights_loaded:
+            raise RuntimeError("debug_head_cls: load_state_dict first")
+        nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"debug_head_cls: the input must hold 1 .. max_batch ({self.max_batch}) frames")
+        cin = 320
+        x = _chk(x, torch.float32, (nb, cin, self.H, self.W), "debug_head_cls: x")
+        if (scale is None) != (shift is None):
+            raise ValueError("debug_head_cls: scale and shift come together")
+        pre_mode = 0
+        if scale is not None:
+            pre_mode = 2 if isinstance(scale, torch.Tensor) and scale.dim() == 2 else 1
+            shp = (nb, cin) if pre_mode == 2 else (cin,)
+            scale = _chk(scale, torch.float32, shp, "debug_head_cls: scale")
+            shift = _chk(shift, torch.float32, shp, "debug_head_cls: shift")
+        self._on_device("debug_head_cls", ((x, "x"), (scale, "scale"), (shift, "shift")))
+        front, per = 128, cin * self.H * self.W  # staged with the padding debug_layer gives its input
+        stage = torch.zeros(front + nb * per + nb * cin * (self.H + self.W + 1) + 64, dtype=torch.float32, device=self.device)
+        xin = stage[front:front + nb * per]
+        xin.copy_(x.reshape(-1))
+        out = self._t((nb, self.A, 1), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_debug_head_cls(self.ctx, nb, _ptr(xin), pre_mode, _ptr(scale), _ptr(shift), _ptr(out), _stream()), self.ctx,
+                       "pp_debug_head_cls")
+        return out
+
     def layer_io_dtypes(self, layer):
         """(input dtype, output / residual dtype) of layer `layer` of the committed plan: the `h<n>` tag of its tiling name (bit 0 of n:
         fp16 input, bit 1: fp16 output); the head's outputs are fp32 whatever the tag says."""
@@ -1258,6 +1292,25 @@ def engine_for_anchors(num_anchors, device):
     if not found:
         raise RuntimeError(f"no engine with {num_anchors} anchors on {dev}: build the network / AnchorAssigner from the config first")
     return found[-1]
+
+
+def menu_names(kind=0, stride=1, up=1, cin=0, precision=0, head9=True, first_conv=False, which="layer", shape=None):
+    """Tiling names of one of the tuner's menus, in menu order (pp_menu_names; needs no device).  which "layer": the menu of a layer --
+    kind 0 conv3x3 (stride 1 / 2), 1 upsampler (up 1 / 2 / 4), 2 head, with cin input channels at precision 0 .. 4 (or its name);
+    "cls": the cls-only head pass; "strips": the strip tilings of wino4 / wino6.  shape = (rows, hin, win, wout) keeps only the entries
+    legal for that layer (rows: GEMM rows -- cout, cout * up^2 for an upsampler, 96 for the 9-anchor head; wout: the map width at the
+    layer's level)."""
+    lib = _lib.load()
+    sel = {"layer": 0, "cls": 1, "strips": 2}[which]
+    prec = Engine.PRECISIONS[precision] if isinstance(precision, str) else int(precision)
+    rows, hin, win, wout = shape if shape is not None else (0, 0, 0, 0)
+    args = (sel, int(kind), int(stride), int(up), int(cin), prec, int(bool(head9)), int(bool(first_conv)), int(rows), int(hin), int(win), int(wout))
+    n = lib.pp_menu_names(*args, None, 0)
+    if n < 0:
+        raise ValueError(f"menu_names: no such menu {args}")
+    buf = ctypes.create_string_buffer(n + 1)
+    lib.pp_menu_names(*args, buf, n + 1)
+    return buf.value.decode().splitlines()
 
 
 def tuning_lib():

@@ -188,6 +188,15 @@ int pp_debug_layer_skip(pp_ctx* ctx, int layer, int nb, const void* in, const vo
                         const int32_t* pmap, const float* feat, void* out, float* out_box, float* out_dir, double* stats,
                         const uint8_t* active, int skip_k, void* stream);
 
+/* Test hook next to pp_debug_layer: the cls-only pass of the deferred head -- the committed cls tiling (pp_head_cls_tiling) on the
+ * head's committed weight image -- on caller tensors, nb frames in one launch.  in f32[nb][320][H][W], padded like pp_debug_layer's;
+ * pre_mode, scale and shift as there; cls_out f32[nb][A] as the head's cls output.  Every argument is checked before anything is
+ * launched (PP_E_ARG); PP_E_STATE before pp_commit_weights and when the committed plan has no deferred head (a 16-bit mode, a head of
+ * other than 9 anchors, or the head on a direct tiling).  Writes only cls_out. */
+int pp_debug_head_cls(pp_ctx* ctx, int nb, const void* in, int pre_mode, const float* scale, const float* shift, float* cls_out, void* stream);
+/* The committed tiling of that pass, "" when the plan has no deferred head.  PP_FORCE_VARIANT pins it like a layer's tiling. */
+const char* pp_head_cls_tiling(pp_ctx* ctx);
+
 /* Deferred head (default on).  Post-processing reads the box / dir logits of at most nms_pre_max anchors per class, so a pass of
  * pp_infer_batch / pp_infer_frame computes the cls rows of the head for every pixel and the box / dir logits for the selected
  * candidates only (bit-identical to the full head: same MFMA arithmetic on the same weight image).  The context's full box / dir
@@ -626,6 +635,16 @@ int pp_weight_image(pp_ctx* ctx, int layer, void* dst, size_t cap, size_t* bytes
  * kernels.  pp_tune_export returns the text length (buf may be NULL to query), pp_tune_import the lines taken. */
 int pp_tune_export(char* buf_h, int cap);
 int pp_tune_import(const char* text_h);
+/* The tilings the tuner chooses from, by name, one per line and in menu order; stateless, no device needed.  which 0: the menu of a
+ * layer, named the way the plan composes it -- kind (0 conv3x3, 1 upsampler, 2 head), stride (conv: 1 / 2), up (upsampler: 1 / 2 / 4),
+ * cin, prec (0 .. 4 as pp_set_precision), head9 (the head has the reference's 9 anchors per location), first_conv (the strided conv of
+ * level 0); which 1: the menu of the cls-only head pass; which 2: the four strip tilings of wino4 / wino6 (right, bottom of each).
+ * rows > 0 keeps only the entries legal for a layer of `rows` GEMM rows (conv: cout, upsampler: cout up^2, head: 96) and cin input
+ * channels on maps Hin x Win -> width Wout (the upsampler's Wout is its input width), by the rule the tuner itself applies; rows <= 0
+ * returns the whole menu.  Returns the text length (buf_h may be NULL to query; at most cap - 1 characters are written), -1 for a
+ * selector out of range. */
+int pp_menu_names(int which, int kind, int stride, int up, int cin, int prec, int head9, int first_conv, int rows, int Hin, int Win, int Wout,
+                  char* buf_h, int cap);
 /* name of the tiling the autotuner chose for that dominant layer (static string owned by ctx) */
 const char* pp_dominant_kernel(pp_ctx* ctx);
 int pp_version(void);

@@ -264,6 +264,10 @@ def stats_exact_margin(y):
 
 # ------------------------------------------------------------------ the plan's shapes and the shared exact cases
 GRIDS = {"64x96": (64, 96), "16x160": (16, 160)}  # BEV cells -> maps 32x48 / 16x24 / 8x12 (every tile overhangs) and 8x80 / 4x40 / 2x20
+# The strip grid (test_menu_exact_gpu.py): maps 36x44 / 18x22 / 9x11.  Level 0 is 2 x 2 main tiles of 16 x 16 px, a right strip 12 px wide and a
+# bottom strip 4 px tall -- what the strip tilings of wino4 / wino6 cover.  Not in GRIDS: the tests that iterate GRIDS assert on the full set.
+STRIP_GRID = {"72x88": (72, 88)}
+ALL_GRIDS = {**GRIDS, **STRIP_GRID}
 PROLOGUES = ("raw", "shared", "frame")
 NB = 3
 
@@ -293,8 +297,8 @@ def exact_case(sd, index, grid, pre="raw", with_res=False):
     key = (index, grid, pre, with_res)
     if key in _CASES:
         return _CASES[key]
-    L = plan_shapes(*GRIDS[grid])[index]
-    rng = np.random.default_rng([index, GRIDS[grid][0], PROLOGUES.index(pre), int(with_res)])
+    L = plan_shapes(*ALL_GRIDS[grid])[index]
+    rng = np.random.default_rng([index, ALL_GRIDS[grid][0], PROLOGUES.index(pre), int(with_res)])
     x = exact_activations(rng, (NB, L["cin"], L["hin"], L["win"])).astype(np.float32)
     scale = shift = None
     if pre != "raw":

@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import layer_ref as R
+import menu_cases as M
 from conftest import load_pkg
 from test_gpu_parity import C16_SHAPES  # the 13 tile shapes of conv16.hip, one list for both files
 
@@ -39,7 +40,7 @@ SUMSQ_REL = R.STAT_N * 2.0 ** -24
 
 
 def small_cfg(synth, grid):
-    gx, gy = R.GRIDS[grid]
+    gx, gy = R.ALL_GRIDS[grid]
     cfg = synth.load_config("eight_20cm")
     cfg["detection_range"] = [0.0, 0.0, -2.5, 0.2 * gx, 0.2 * gy, 8.5]
     cfg["max_voxels"] = 2000
@@ -50,7 +51,7 @@ def small_cfg(synth, grid):
 def make_engine(synth, grid, mode, sd):
     eng = load_pkg("engine").Engine(small_cfg(synth, grid), max_batch=R.NB, precision=mode)
     eng.load_state_dict(sd)
-    assert (eng.H, eng.W) == (R.GRIDS[grid][0] // 2, R.GRIDS[grid][1] // 2) and eng.effective_precision() == mode
+    assert (eng.H, eng.W) == (R.ALL_GRIDS[grid][0] // 2, R.ALL_GRIDS[grid][1] // 2) and eng.effective_precision() == mode
     return eng
 
 
@@ -138,23 +139,29 @@ def test_exact_default_plan(mode, synth, exact_sd, tally):
           + (f", {w6} Winograd F(4x4) layers inside their componentwise bound" if w6 else ""))
 
 
-@pytest.mark.parametrize("mode", ["bf16x3", "bf16", "fp16"])
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16", "fp16", "fp16s"])
 @pytest.mark.parametrize("shape", C16_SHAPES)
 def test_exact_conv16_forced_shape(shape, mode, synth, exact_sd, tally, monkeypatch):
-    """Every tile shape of conv16.hip pinned, in every operand type, on every conv layer that takes it, on both grids."""
+    """Every tile shape of conv16.hip pinned, in every operand type, on every conv layer that takes it, on both grids.  fp16s: the fp16
+    operand kernels on fp16 tensors (`h3`; the first conv reads fp32 and writes fp16, `h2`)."""
     monkeypatch.setenv("PP_FORCE_VARIANT", shape)
     ran = []
     for grid in sorted(R.GRIDS):
         eng = make_engine(synth, grid, mode, exact_sd)
         for index, t in enumerate(eng.layer_tilings()):
             if t["kind"] == 0 and shape in t["tiling"]:  # the shape really runs this layer (rows a multiple of its 64 / 128, its stride in the menu)
-                assert t["wino"] == 5 and f"p{eng.PRECISIONS[mode]} " in t["tiling"]
+                tag = f"p3 h{2 if index == 0 else 3} " if mode == "fp16s" else f"p{eng.PRECISIONS[mode]} "
+                assert t["wino"] == 5 and tag in t["tiling"]
                 for pre, with_res in FORCED_COMBOS:
                     check_exact(eng, exact_sd, index, grid, pre, with_res, tally, mode)
                 ran.append((grid, index))
         del eng
     assert ran, f"{shape} fits no conv layer on either grid"
     assert {g for g, _ in ran} == set(R.GRIDS)
+    # ... and those are exactly the layers on which the library calls a conv16 entry of this shape legal (menu_cases.legal_table): with
+    # test_menu_cpu's proof that the 13 shapes partition conv16's menus, every entry of every mode's menu has run wherever it can
+    legal = {gk for key, rows in M.legal_table(mode).items() if key.startswith("k3") for n, where in rows if shape in n for gk in where if gk[0] in R.GRIDS}
+    assert set(ran) == legal, (sorted(set(ran) ^ legal))
     print(f"[layer exact] conv16 {shape} {mode}: {len(ran)} layers bit-exact")
 
 

@@ -136,12 +136,12 @@ def exact_sd(synth):
     return R.exact_state_dict(synth.seeded_state_dict(0))
 
 
-@pytest.mark.parametrize("grid", sorted(R.GRIDS))
+@pytest.mark.parametrize("grid", sorted(R.ALL_GRIDS))
 def test_exact_data_meets_its_exactness_condition(grid, exact_sd):
     """Every case the GPU tests run: sum |x||w| + |res| + |bias| < 2^20 unit at every output (the largest K is 9 * 256), every value a
     multiple of the unit, the operands unchanged by bf16 / fp16 rounding with zero `lo` parts, and the statistics condition."""
     worst = 0.0
-    for index, L in enumerate(R.plan_shapes(*R.GRIDS[grid])):
+    for index, L in enumerate(R.plan_shapes(*R.ALL_GRIDS[grid])):
         for pre in R.PROLOGUES:
             for with_res in ((False, True) if L["kind"] == 0 else (False,)):
                 c = R.exact_case(exact_sd, index, grid, pre, with_res)
