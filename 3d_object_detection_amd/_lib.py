@@ -94,6 +94,14 @@ PROTOTYPES = {
     "pp_update_down_weight": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
     "pp_backbone_train_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_rpn_weights": (ctypes.c_int, [c_p, c_p, c_p]),
+    "pp_unit_backward_affine": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p,
+                                               c_p, c_p]),
+    "pp_down_backward_affine": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int,
+                                               c_p, c_p, c_p, c_p, c_p]),
+    "pp_neck_backward_affine": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
+    "pp_bn_fold": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_bn_affine_grad": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_update_bn_fold": (ctypes.c_int, [c_p, c_p, c_p]),
     "pp_pfn_train_forward": (ctypes.c_int, [c_p] * 12),
     "pp_scatter_backward": (ctypes.c_int, [c_p] * 6),
     "pp_pfn_backward": (ctypes.c_int, [c_p] * 15),

@@ -24,6 +24,8 @@
 // Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
 // order, a plane's segment sums likewise; segments and K ranges of the wgrad depend on the shapes only.  A frame's a, dz, da and du do not
 // depend on the batch it rides in; dw depends on nb within fp32 summation error (the K ranges do).
+// pp_unit_backward_affine is the same unit with a per-channel affine (a frozen BatchNorm2d) for the norm: k_affine_unit_pack, the two
+// products, k_affine_unit_du and k_affine_reduce; pp_unit_backward itself stays the InstanceNorm backbone's.
 // block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp); what both share is in block_train.h.
 #include <cmath>
 #include "pp_common.h"
@@ -251,6 +253,62 @@ __global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, 
     }
 }
 
+// ---- the unit with a per-channel affine in place of the InstanceNorm (pp_unit_backward_affine): a = max(fma(u, scale, shift), 0), the
+// forward prologue's expression, so there are no statistics passes.  k_affine_unit_pack: grid (C, frames, SP) as k_unit_pack.
+// k_affine_unit_du: grid (C, frames, S), in place over da: g = da [a > 0], du = scale g (+ dskip), and the segment's sum g u, sum g in
+// fp64 -> pst[frame][c][segment][2] -------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_affine_unit_pack(const float* __restrict__ u, const float* __restrict__ dy, float* __restrict__ ap,
+                                                          float* __restrict__ dzp, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                          int C, int h, int w, int wp, int G, int PP, int PS, int LP)
+{
+    const int tid = threadIdx.x, N = h * w;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* dp = dy + pl * N;
+    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
+    float* ao = ap + pl * PS;
+    float* zo = dzp + pl * PS;
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    for (int j = lo + tid; j < hi; j += 256) {
+        const int P = j - G;
+        float av = 0.f, dv = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, x = P - y * wp;
+            if (y >= 1 && y <= h && x >= 1 && x <= w) {
+                const int i = (y - 1) * w + x - 1;
+                av = fmaxf(fmaf(up[i], sc, sh), 0.f);
+                dv = dp[i];
+            }
+        }
+        ao[j] = av; zo[j] = dv;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_affine_unit_du(const float* __restrict__ u, const float* __restrict__ ap, const float* __restrict__ scale,
+                                                        const float* __restrict__ dskip, float* __restrict__ du, double* __restrict__ pst, int C,
+                                                        int w, int wp, int G, int PS, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* ai = ap + pl * PS + G + wp + 1; // interior origin
+    float* dp = du + pl * N;
+    const float sc = scale[blockIdx.x];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sgu = 0.0, sg = 0.0;
+    for (int i = lo + tid; i < hi; i += 256) {
+        const int y = i / w, x = i - y * w;
+        const float g = ai[y * wp + x] > 0.f ? dp[i] : 0.f;
+        sgu += (double)g * (double)up[i]; sg += (double)g;
+        float v = sc * g;
+        if (dskip) v = v + dskip[pl * N + i];
+        dp[i] = v;
+    }
+    block_sum2(sgu, sg, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
+}
+
 // ---- weight update: image element i holds position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T.  U = G g G^T is
 // evaluated in fp64 in the host packers' own expression order and rounded once; the library is built with -ffp-contract=off on both
 // sides, so the image is the one a fresh commit of the same values packs, bit for bit -------------------------------------------------
@@ -381,6 +439,84 @@ extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u
         }
     }
     hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// pp_unit_backward with a per-channel affine for the norm: the pack without statistics, the same two products over the same planes, K
+// ranges and frame chunks, and one pass behind the dgrad in place of the two of the norm backward.
+extern "C" int pp_unit_backward_affine(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* scale, const float* shift,
+                                       const float* dy, const float* dskip, int nb, float* dw, float* du, double* dscale, double* dshift,
+                                       void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: C must be 64, 128 or 256");
+    if (!u || !wgt || !scale || !shift || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: null pointer");
+    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: dscale and dshift go together");
+    if (!du && dscale) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: dscale and dshift need du (they are sums over the dgrad product)");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: nb must be 1 .. max_batch");
+    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: h, w >= 1 and h w >= 2");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: w must be 16-byte aligned");
+    if (((uintptr_t)u | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw | (uintptr_t)du) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: tensors must be 4-byte aligned");
+    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: dscale / dshift must be 8-byte aligned");
+    const int64_t wp64 = (int64_t)w + 2, PP64 = ((int64_t)h + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
+    if (2 * (uint64_t)C * (uint64_t)PS64 * sizeof(float) > WS_BUDGET)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: map too large (one frame's planes exceed the 256 MB workspace)");
+    const int wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64, N = h * w;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: as pp_unit_backward
+    const size_t pf_elems = (size_t)C * PS;
+    int fc = (int)(WS_CHUNK / (2 * pf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int TN = C >= 128 ? 128 : 192;
+    const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = C * NC;
+    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * C * SEG_MAX * 2)) || // every frame's segment sums: reduced once, behind the chunks
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
+        return rc;
+    float* ap = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * pf_elems;
+    if (du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, C);
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t o = (size_t)f0 * C * N;
+        hipLaunchKernelGGL(k_affine_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, ap, dzp, scale, shift, C, h, w, wp, G, PP, PS, LP);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / TN, C / 64, sp);
+        if (C >= 128)
+            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        else
+            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        gbase += sp;
+        if (du) {
+            float* duc = du + o;
+            if (C == 64)
+                hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            else if (C == 128)
+                hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            else
+                hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            hipLaunchKernelGGL(k_affine_unit_du, dim3(C, fn, S), dim3(256), 0, stream, u + o, ap, scale, dskip ? dskip + o : nullptr, duc,
+                               ws->pst + (size_t)f0 * C * S * 2, C, w, wp, G, PS, N, L, S);
+        }
+    }
+    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+    if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, dscale, dshift);
     PP_HIP(hipGetLastError());
     return 0;
 }

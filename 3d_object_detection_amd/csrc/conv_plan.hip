@@ -584,27 +584,117 @@ static int fold_bn(pp_ctx* ctx, const std::string& prefix, int C, int site, int 
     return 0;
 }
 
-// every BatchNorm of the RPN -> its site (the BatchNorm variant of the network)
-static int fold_all_bn(pp_ctx* ctx)
+// the nineteen BatchNorm2d layers of the RPN in state_dict order, each with its site
+struct BnSite { std::string prefix; int C, site, coff; };
+static std::vector<BnSite> bn_sites()
 {
+    std::vector<BnSite> out;
     for (int b = 0; b < 3; ++b) {
         char key[128];
         const int c = kC[b];
         snprintf(key, sizeof(key), "rpn.block%d.1", b + 1);
-        int rc = fold_bn(ctx, key, c, site_block(b, 0));
-        if (rc) return rc;
+        out.push_back({key, c, site_block(b, 0), 0});
         for (int u = 0; u < block_units(b); ++u) {
             snprintf(key, sizeof(key), "rpn.block%d.%d.conv_block.0", b + 1, 3 + u);
-            if ((rc = fold_bn(ctx, key, c, site_block(b, 1 + 2 * u)))) return rc;
+            out.push_back({key, c, site_block(b, 1 + 2 * u), 0});
             if (unit_two_convs(b, u)) {
                 snprintf(key, sizeof(key), "rpn.block%d.%d.conv_block.3", b + 1, 3 + u);
-                if ((rc = fold_bn(ctx, key, c, site_block(b, 2 + 2 * u)))) return rc;
+                out.push_back({key, c, site_block(b, 2 + 2 * u), 0});
             }
         }
         snprintf(key, sizeof(key), "rpn.deconv%d.1", b + 1);
         // deconv norms are stored contiguously at site 7 (block 0), channels [0,64),[64,192),[192,320)
-        if ((rc = fold_bn(ctx, key, (b == 0) ? 64 : 128, 7, (b == 0) ? 0 : (b == 1 ? 64 : 192)))) return rc;
+        out.push_back({key, (b == 0) ? 64 : 128, 7, (b == 0) ? 0 : (b == 1 ? 64 : 192)});
     }
+    return out;
+}
+
+// every BatchNorm of the RPN -> its site (the BatchNorm variant of the network)
+static int fold_all_bn(pp_ctx* ctx)
+{
+    for (const BnSite& s : bn_sites())
+        if (int rc = fold_bn(ctx, s.prefix, s.C, s.site, s.coff)) return rc;
+    return 0;
+}
+
+// ---- the fold on the device: fold_bn's fp64 expression, each value rounded once, so the arrays equal those of a fresh commit of the
+// same values bit for bit.  One workgroup per job (C <= 256) --------------------------------------------------------------------------
+namespace {
+constexpr int BN_LAYERS = 19;
+struct BnFoldJob { const float *gamma, *beta, *rm, *rv; float *scale, *shift; int C; };
+struct BnFoldJobs { BnFoldJob j[BN_LAYERS]; };
+
+__global__ void __launch_bounds__(256) bn_fold_kernel(const BnFoldJobs jobs)
+{
+    const BnFoldJob& j = jobs.j[blockIdx.x];
+    const int c = threadIdx.x;
+    if (c >= j.C) return;
+    const double s = (double)j.gamma[c] / sqrt((double)j.rv[c] + 1e-3);
+    j.scale[c] = (float)s;
+    j.shift[c] = (float)((double)j.beta[c] - (double)j.rm[c] * s);
+}
+
+// dgamma = r (dscale - running_mean dshift), dbeta = dshift with r = 1 / sqrt(running_var + 1e-3), in fp64, rounded once
+__global__ void __launch_bounds__(256) bn_affine_grad_kernel(const double* __restrict__ dscale, const double* __restrict__ dshift,
+                                                             const float* __restrict__ rm, const float* __restrict__ rv, float* __restrict__ dgamma,
+                                                             float* __restrict__ dbeta, int C)
+{
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    const double r = 1.0 / sqrt((double)rv[c] + 1e-3);
+    dgamma[c] = (float)(r * (dscale[c] - (double)rm[c] * dshift[c]));
+    dbeta[c] = (float)dshift[c];
+}
+} // namespace
+
+extern "C" int pp_bn_fold(pp_ctx* ctx, int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                          float* scale, float* shift, void* stream)
+{
+    if (!ctx) return PP_E_ARG;
+    if (C < 1 || C > 256) return pp_fail(ctx, PP_E_ARG, "pp_bn_fold: C must be 1 .. 256");
+    if (!gamma || !beta || !running_mean || !running_var || !scale || !shift) return pp_fail(ctx, PP_E_ARG, "pp_bn_fold: null pointer");
+    if (((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)running_mean | (uintptr_t)running_var | (uintptr_t)scale | (uintptr_t)shift) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_bn_fold: tensors must be 4-byte aligned");
+    PP_HIP(hipSetDevice(ctx->device));
+    BnFoldJobs jobs = {};
+    jobs.j[0] = BnFoldJob{gamma, beta, running_mean, running_var, scale, shift, C};
+    hipLaunchKernelGGL(bn_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, jobs);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pp_bn_affine_grad(pp_ctx* ctx, int C, const double* dscale, const double* dshift, const float* running_mean,
+                                 const float* running_var, float* dgamma, float* dbeta, void* stream)
+{
+    if (!ctx) return PP_E_ARG;
+    if (C < 1 || C > 256) return pp_fail(ctx, PP_E_ARG, "pp_bn_affine_grad: C must be 1 .. 256");
+    if (!dscale || !dshift || !running_mean || !running_var || !dgamma || !dbeta) return pp_fail(ctx, PP_E_ARG, "pp_bn_affine_grad: null pointer");
+    if ((((uintptr_t)dscale | (uintptr_t)dshift) & 7) || (((uintptr_t)running_mean | (uintptr_t)running_var | (uintptr_t)dgamma | (uintptr_t)dbeta) & 3))
+        return pp_fail(ctx, PP_E_ARG, "pp_bn_affine_grad: misaligned tensor");
+    PP_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(bn_affine_grad_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dscale, dshift, running_mean, running_var, dgamma, dbeta, C);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int pp_update_bn_fold(pp_ctx* ctx, const float* const* bn, void* stream)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_update_bn_fold: weights not committed");
+    if (ctx->cfg.norm_kind != 1) return pp_fail(ctx, PP_E_ARG, "pp_update_bn_fold: the BatchNorm backbone only (InstanceNorm has no affine to fold)");
+    if (!bn) return pp_fail(ctx, PP_E_ARG, "pp_update_bn_fold: null pointer");
+    for (int i = 0; i < 4 * BN_LAYERS; ++i)
+        if (!bn[i] || ((uintptr_t)bn[i] & 3)) return pp_fail(ctx, PP_E_ARG, "pp_update_bn_fold: null or misaligned tensor pointer");
+    pp_net* net = (pp_net*)ctx->net;
+    PP_HIP(hipSetDevice(ctx->device));
+    const std::vector<BnSite> sites = bn_sites();
+    BnFoldJobs jobs = {};
+    for (int i = 0; i < BN_LAYERS; ++i) {
+        const size_t o = (size_t)sites[i].site * 320 + sites[i].coff;
+        jobs.j[i] = BnFoldJob{bn[4 * i], bn[4 * i + 1], bn[4 * i + 2], bn[4 * i + 3], net->bn_scale + o, net->bn_shift + o, sites[i].C};
+    }
+    hipLaunchKernelGGL(bn_fold_kernel, dim3(BN_LAYERS), dim3(256), 0, (hipStream_t)stream, jobs);
+    PP_HIP(hipGetLastError());
     return 0;
 }
 

@@ -27,6 +27,8 @@
 // Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
 // order, a plane's segment sums likewise; segments and K ranges of the wgrad depend on the shapes only.  A frame's dz and dx do not depend on the batch it rides in; dw depends on
 // nb within fp32 summation error (the K ranges do), and not on whether dx is asked for.
+// pp_down_backward_affine is the same stage with a per-channel affine (a frozen BatchNorm2d) for the norm: k_affine_down_dz in place
+// of the three norm passes, then the same products and k_affine_reduce; pp_down_backward itself stays the InstanceNorm backbone's.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -166,6 +168,41 @@ __global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, 
         }
         zo[j] = v;
     }
+}
+
+// ---- the stage with a per-channel affine in place of the InstanceNorm (pp_down_backward_affine), z, dy -> dz in the padded plane: grid
+// (Cout, frames, SP) as k_down_norm.  g = dy [fma(z, scale, shift) > 0], the forward prologue's expression; dz = scale g; and the slice's
+// sum g z, sum g in fp64 -> pst[frame][co][slice][2] (every interior element lies in exactly one slice) -----------------------------------
+__global__ void __launch_bounds__(256) k_affine_down_dz(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
+                                                        const float* __restrict__ shift, float* __restrict__ dzp, double* __restrict__ pst, int cout,
+                                                        int ho, int wo, int wp, int G, int PP, int PS, int LP)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x, N = ho * wo, SP = gridDim.z;
+    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
+    const float* zi = z + pl * N;
+    const float* dp = dy + pl * N;
+    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
+    float* zo = dzp + pl * PS;
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    double sgz = 0.0, sg = 0.0;
+    for (int j = lo + tid; j < hi; j += 256) {
+        const int P = j - G;
+        float v = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, c = P - y * wp;
+            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
+                const int i = (y - 1) * wo + c - 1;
+                const float zz = zi[i];
+                const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
+                sgz += (double)g * (double)zz; sg += (double)g;
+                v = sc * g;
+            }
+        }
+        zo[j] = v;
+    }
+    block_sum2(sgz, sg, red);
+    if (tid == 0) { pst[(pl * SP + blockIdx.z) * 2] = sgz; pst[(pl * SP + blockIdx.z) * 2 + 1] = sg; }
 }
 
 // ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
@@ -416,6 +453,86 @@ extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win
         }
     }
     hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// pp_down_backward with a per-channel affine for the norm: one pass writes dz and the sums where the sibling runs three, and the two
+// products run over the same planes, K ranges and frame chunks.
+extern "C" int pp_down_backward_affine(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z,
+                                       const float* scale, const float* shift, const float* dy, int nb, float* dw, float* dx, double* dscale,
+                                       double* dshift, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
+    if (!x || !wgt || !z || !scale || !shift || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: null pointer");
+    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: dscale and dshift go together");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: nb must be 1 .. max_batch");
+    const int64_t ho64 = ((int64_t)hin + 1) / 2, wo64 = ((int64_t)win + 1) / 2;
+    if (hin < 1 || win < 1 || ho64 * wo64 < 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: hin, win >= 1 and ho wo >= 2");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: w must be 16-byte aligned");
+    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: tensors must be 4-byte aligned");
+    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: dscale / dshift must be 8-byte aligned");
+    const int64_t wp64 = wo64 + 2, PP64 = (ho64 + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
+    const uint64_t pf64 = (uint64_t)(4 * cin + cout) * (uint64_t)PS64; // one frame's planes, elements
+    if (pf64 * sizeof(float) > DOWN_WS_BUDGET)
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: map too large (one frame's planes exceed the 256 MB workspace)");
+    const int ho = (int)ho64, wo = (int)wo64, wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    down_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: as pp_down_backward
+    const size_t pf_elems = (size_t)pf64;
+    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int TN = cin >= 128 ? 128 : 192;
+    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = cout * NC;
+    const int SP = plane_segs(PS), LP = seg_len(PS, SP);
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * cout * SEG_MAX * 2)) || // every frame's slice sums: reduced once, behind the chunks
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
+        return rc;
+    float* xp = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
+    if (dx) hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, cin, cout);
+    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
+        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
+        hipLaunchKernelGGL(k_affine_down_dz, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, scale, shift, dzp,
+                           ws->pst + (size_t)f0 * cout * SP * 2, cout, ho, wo, wp, G, PP, PS, LP);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / TN, cout / 64, sp);
+        if (cin >= 128)
+            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        else
+            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        gbase += sp;
+        if (dx) {
+            if (cin == 64)
+                hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
+                                   G, PP, PS);
+            else
+                hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
+                                   G, PP, PS);
+        }
+    }
+    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+    if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(cout, 64)), dim3(64), 0, stream, ws->pst, nb, cout, SP, dscale, dshift);
     PP_HIP(hipGetLastError());
     return 0;
 }

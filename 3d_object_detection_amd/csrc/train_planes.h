@@ -1,5 +1,6 @@
 // What the streaming passes of block_train.hip and down_train.hip share: how a plane is cut into segments, the fixed-order sums of a
 // workgroup, and the statistics kernel.  One copy, so that both files cut a plane the same way and a shape keeps its bits in both.
+// k_affine_reduce, the last step of the three pp_*_backward_affine entries, is here for neck_train.hip as well.
 #pragma once
 #include "pp_common.h"
 
@@ -50,6 +51,21 @@ __global__ void __launch_bounds__(256) k_plane_stats(const float* __restrict__ u
     strided4(lo, hi, [&](int i) { return up[i]; }, [&](float f) { const double v = (double)f; s += v; ss += v * v; });
     block_sum2(s, ss, red);
     if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = s; pst[(pl * S + blockIdx.z) * 2 + 1] = ss; }
+}
+
+// ---- per-channel affine (frozen BatchNorm) backward: the two sums of a channel from pst[frame][c][segment][2], segments added in index
+// order, frames in frame order, left in fp64 (the caller's dgamma is a difference of the two that cancels) -----------------------------
+__global__ void __launch_bounds__(64) k_affine_reduce(const double* __restrict__ pst, int nb, int C, int S, double* __restrict__ dscale,
+                                                      double* __restrict__ dshift)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int f = 0; f < nb; ++f) {
+        const double* p = pst + ((size_t)f * C + c) * S * 2;
+        for (int s = 0; s < S; ++s) { a += p[2 * s]; b += p[2 * s + 1]; }
+    }
+    dscale[c] = a; dshift[c] = b;
 }
 
 } // namespace

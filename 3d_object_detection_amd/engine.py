@@ -647,6 +647,157 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_rpn_weights(self.ctx, ptrs, _stream()), self.ctx, "pp_update_rpn_weights")
 
+    # ------------------------------------------------------------------ the BatchNorm backbone with frozen statistics
+    BN_FIELDS = ("weight", "bias", "running_mean", "running_var")  # a BatchNorm2d layer's tensors in state_dict order
+
+    @staticmethod
+    def bn_prefix(conv_key):
+        """The BatchNorm2d layer that goes with a convolution or upsampler of the RPN: the norm behind a strided convolution or an
+        upsampler ('....0.weight' -> '....1'), the norm in front of a unit convolution ('...conv_block.2.weight' -> '...conv_block.0',
+        '.5.' -> '.3')."""
+        stem, idx, _ = conv_key.rsplit(".", 2)
+        return stem + "." + {"0": "1", "2": "0", "5": "3"}[idx]
+
+    @classmethod
+    def bn_layers(cls):
+        """(prefix, channels) of the nineteen BatchNorm2d layers of the RPN in state_dict order: per block the norms of its
+        convolutions, then its upsampler's."""
+        out = []
+        for b in range(3):
+            out += [(cls.bn_prefix(k), 64 << b) for k in cls.RPN_CONV_KEYS[(0, 4, 10)[b]:(4, 10, 16)[b]]]
+            out.append((cls.bn_prefix(cls.NECK_KEYS[b]), 128 if b else 64))
+        return tuple(out)
+
+    def _affine_args(self, who, scale, shift, C, need_affine):
+        scale = _chk(scale, torch.float32, (C,), f"{who}: scale")
+        shift = _chk(shift, torch.float32, (C,), f"{who}: shift")
+        self._on_device(who, ((scale, "scale"), (shift, "shift")))
+        sums = (self._t((C,), torch.float64), self._t((C,), torch.float64)) if need_affine else (None, None)
+        return scale, shift, sums
+
+    def bn_fold(self, gamma, beta, running_mean, running_var):
+        """pp_bn_fold: the eval-mode fold of one BatchNorm2d(eps 1e-3) layer, four device tensors [C] -> (scale, shift) f32[C] =
+        gamma / sqrt(running_var + 1e-3), beta - running_mean scale, in fp64 and rounded once: the bits the committed plan holds."""
+        C = int(gamma.shape[0]) if isinstance(gamma, torch.Tensor) and gamma.dim() == 1 else 0
+        if not 1 <= C <= 256:
+            raise ValueError("bn_fold: expected tensors [C] with 1 <= C <= 256")
+        ts = [_chk(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32, (C,), f"bn_fold: {n}")
+              for t, n in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var"))]
+        self._on_device("bn_fold", [(t, "a tensor") for t in ts])
+        scale, shift = self._t((C,), torch.float32), self._t((C,), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_bn_fold(self.ctx, C, *[_ptr(t) for t in ts], _ptr(scale), _ptr(shift), _stream()), self.ctx, "pp_bn_fold")
+        return scale, shift
+
+    def bn_affine_grad(self, dscale, dshift, running_mean, running_var):
+        """pp_bn_affine_grad: the sums f64[C] of an affine primitive -> (dgamma, dbeta) f32[C] of the BatchNorm2d layer,
+        dgamma = (dscale - running_mean dshift) / sqrt(running_var + 1e-3), dbeta = dshift, in fp64 and rounded once."""
+        C = int(dscale.shape[0]) if isinstance(dscale, torch.Tensor) and dscale.dim() == 1 else 0
+        if not 1 <= C <= 256:
+            raise ValueError("bn_affine_grad: expected tensors [C] with 1 <= C <= 256")
+        dscale = _chk(dscale, torch.float64, (C,), "bn_affine_grad: dscale")
+        dshift = _chk(dshift, torch.float64, (C,), "bn_affine_grad: dshift")
+        rm = _chk(running_mean, torch.float32, (C,), "bn_affine_grad: running_mean")
+        rv = _chk(running_var, torch.float32, (C,), "bn_affine_grad: running_var")
+        self._on_device("bn_affine_grad", ((dscale, "dscale"), (dshift, "dshift"), (rm, "running_mean"), (rv, "running_var")))
+        dg, db = self._t((C,), torch.float32), self._t((C,), torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_bn_affine_grad(self.ctx, C, _ptr(dscale), _ptr(dshift), _ptr(rm), _ptr(rv), _ptr(dg), _ptr(db), _stream()),
+                       self.ctx, "pp_bn_affine_grad")
+        return dg, db
+
+    def update_bn_fold(self, tensors):
+        """pp_update_bn_fold: {state_dict name: device tensor} holding weight, bias, running_mean and running_var of the nineteen
+        BatchNorm2d layers of the RPN -> the folded scale / shift arrays of the committed plan, in place on the current stream, bit for
+        bit what load_state_dict of the same values commits.  BatchNorm engines only (RuntimeError otherwise, and before the first
+        load_state_dict)."""
+        keys, shapes = zip(*[(f"{p}.{s}", (c,)) for p, c in self.bn_layers() for s in self.BN_FIELDS])
+        args = self._chk_weights("update_bn_fold", tensors, keys, shapes)
+        ptrs = (ctypes.c_void_p * len(args))(*[t.data_ptr() for t in args])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_update_bn_fold(self.ctx, ptrs, _stream()), self.ctx, "pp_update_bn_fold")
+
+    def unit_backward_affine(self, u, w, scale, shift, dy, dskip=None, need_du=True, need_affine=True):
+        """pp_unit_backward_affine: unit_backward for the unit scale/shift -> ReLU -> Conv3x3 (frozen BatchNorm): scale, shift f32[C] are
+        the folded values the forward used -> (dw, du or None, dscale, dshift); dscale = sum g u and dshift = sum g are f64[C], None
+        when need_affine is False.  need_du=False needs need_affine=False.  fp32, deterministic, stateless."""
+        if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
+            raise ValueError(f"unit_backward_affine: u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb, C, h, wd = (int(v) for v in u.shape)
+        if C not in (64, 128, 256):
+            raise ValueError(f"unit_backward_affine: C must be 64, 128 or 256, got {C}")
+        if h < 1 or wd < 1 or h * wd < 2:
+            raise ValueError(f"unit_backward_affine: the map needs at least two elements, got {h} x {wd}")
+        if need_affine and not need_du:
+            raise ValueError("unit_backward_affine: the affine sums are sums over du's product: need_affine needs need_du")
+        u = _chk(u, torch.float32, (nb, C, h, wd), "unit_backward_affine: u")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), "unit_backward_affine: w")
+        dy = _chk(dy, torch.float32, (nb, C, h, wd), "unit_backward_affine: dy")
+        if dskip is not None:
+            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), "unit_backward_affine: dskip")
+        self._on_device("unit_backward_affine", ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
+        scale, shift, (ds, dh) = self._affine_args("unit_backward_affine", scale, shift, C, need_affine)
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
+        dw = self._t((C, C, 3, 3), torch.float32)
+        du = self._t((nb, C, h, wd), torch.float32) if need_du else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_unit_backward_affine(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(scale), _ptr(shift), _ptr(dy), _ptr(dskip), nb,
+                                                        _ptr(dw), _ptr(du), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_unit_backward_affine")
+        return dw, du, ds, dh
+
+    def down_backward_affine(self, x, w, z, scale, shift, dy, need_dx=True, need_affine=True):
+        """pp_down_backward_affine: down_backward for the stage Conv3x3 stride 2 -> scale/shift -> ReLU (frozen BatchNorm) ->
+        (dw, dx or None, dscale = sum g z, dshift = sum g: f64[Cout], None when need_affine is False).  fp32, deterministic, stateless."""
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
+            raise ValueError(f"down_backward_affine: x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb, cin, hin, win = (int(v) for v in x.shape)
+        cout = int(w.shape[0]) if isinstance(w, torch.Tensor) and w.dim() == 4 else 0
+        if (cin, cout) not in self.DOWN_PAIRS:
+            raise ValueError(f"down_backward_affine: (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
+        ho, wo = (hin + 1) // 2, (win + 1) // 2
+        if hin < 1 or win < 1 or ho * wo < 2:
+            raise ValueError(f"down_backward_affine: the output map needs at least two elements, got {ho} x {wo}")
+        x = _chk(x, torch.float32, (nb, cin, hin, win), "down_backward_affine: x")
+        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), "down_backward_affine: w")
+        z = _chk(z, torch.float32, (nb, cout, ho, wo), "down_backward_affine: z")
+        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), "down_backward_affine: dy")
+        self._on_device("down_backward_affine", ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
+        scale, shift, (ds, dh) = self._affine_args("down_backward_affine", scale, shift, cout, need_affine)
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
+        dw = self._t((cout, cin, 3, 3), torch.float32)
+        dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_down_backward_affine(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(scale), _ptr(shift), _ptr(dy),
+                                                        nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_down_backward_affine")
+        return dw, dx, ds, dh
+
+    def neck_backward_affine(self, branch, x, w, scale, shift, y, dy, need_dx=True, need_affine=True):
+        """pp_neck_backward_affine: neck_backward for the branch ConvTranspose -> scale/shift -> ReLU (frozen BatchNorm); scale, shift
+        f32[Cup] are the branch's -> (dw, dx or None, dscale = sum g Z, dshift = sum g: f64[Cup], None when need_affine is False).
+        fp32, deterministic, stateless."""
+        if branch not in (0, 1, 2):
+            raise ValueError(f"neck_backward_affine: branch must be 0, 1 or 2, got {branch!r}")
+        xs, wsh = self.neck_shapes(branch)
+        nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(f"neck_backward_affine: x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
+        x = _chk(x, torch.float32, (nb,) + xs, "neck_backward_affine: x")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, "neck_backward_affine: w")
+        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), "neck_backward_affine: y")
+        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), "neck_backward_affine: dy")
+        self._on_device("neck_backward_affine", ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
+        scale, shift, (ds, dh) = self._affine_args("neck_backward_affine", scale, shift, wsh[1], need_affine)
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
+        dw = self._t(wsh, torch.float32)
+        dx = self._t((nb,) + xs, torch.float32) if need_dx else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_neck_backward_affine(self.ctx, branch, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), _ptr(dy), nb, _ptr(dw),
+                                                        _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_neck_backward_affine")
+        return dw, dx, ds, dh
+
     # ------------------------------------------------------------------ PFN training (pfn_train.hip)
     PFN_KEYS = ("pillar_point_net.pfn_layers.0.weight", "pillar_point_net.pfn_layers.1.weight", "pillar_point_net.pfn_layers.1.bias")
     PFN_STAT_KEYS = ("pillar_point_net.pfn_layers.1.running_mean", "pillar_point_net.pfn_layers.1.running_var")

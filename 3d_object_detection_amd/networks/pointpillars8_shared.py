@@ -29,6 +29,12 @@ statistics: every training-mode forward runs pp_pfn_train_forward over the pilla
 running_var (momentum 0.1, unbiased variance) and counts num_batches_tracked, whether or not grad is enabled.  The eval-mode PFN of
 the engine (running statistics folded into scale / shift) is rewritten by pp_update_pfn_weights before it is next used.
 
+The BatchNorm networks (pointpillars8_export / _trt, _norm = "batch") fine-tune with frozen statistics, train(scope=...,
+bn_stats="frozen"): every BatchNorm2d of the RPN stays the per-channel affine of its running statistics, its weight / bias sit in the
+group of the convolution whose backward primitive yields their gradient (with_bn: 63 tensors under "rpn", 66 under "all"), the
+training forward is the same tapped inference pass, _RpnBnFunction walks the same table with pp_*_backward_affine, and after a step
+_sync_neck also folds the nineteen layers again in place (pp_update_bn_fold).
+
 Mixed precision: train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
 or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
 backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit."""
@@ -62,6 +68,32 @@ _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in
 ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
 SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
 GRAD_PRECISIONS = ("fp32", "bf16x3", "bf16")  # train(grad_precision=...): the operands of the unit backwards' gradient products
+BN_STATS = ("frozen", "batch")  # train(bn_stats=...) on a BatchNorm network; "batch" is reserved for batch-statistics training
+
+
+def bn_affine_keys(conv_key):
+    """(weight, bias) of the BatchNorm2d layer whose gradient the backward primitive of this RPN convolution or upsampler yields."""
+    p = Engine.bn_prefix(conv_key)
+    return p + ".weight", p + ".bias"
+
+
+def with_bn(keys):
+    """`keys` with, for every RPN convolution and upsampler among them, the weight and bias of its BatchNorm2d layer, in the reference's
+    named_parameters() order: a unit's leading norm in front of its convolution, the norm of a strided convolution or of an upsampler
+    behind it."""
+    out = []
+    for k in keys:
+        if not k.startswith("rpn."):
+            out.append(k)
+        elif k in Engine.DOWN_KEYS or k in NECK_KEYS:
+            out += [k, *bn_affine_keys(k)]
+        else:
+            out += [*bn_affine_keys(k), k]
+    return tuple(out)
+
+
+BN_RPN_KEYS = with_bn(RPN_KEYS)        # the 63 tensors train(scope="rpn", bn_stats="frozen") trains on a BatchNorm network
+BN_ALL_KEYS = PFN_KEYS + BN_RPN_KEYS   # the 66 tensors net.parameters() yields in the reference's BatchNorm network
 
 
 class _Group(typing.NamedTuple):
@@ -208,6 +240,91 @@ class _RpnFunction(torch.autograd.Function):
         return (None, None, None, g if need_x else None) + tuple(grads)
 
 
+class _RpnBnFunction(torch.autograd.Function):
+    """_RpnFunction for the BatchNorm backbone with frozen statistics: the same forward (the tap entry points read no norm kind),
+    the same walk from the upsamplers through the levels `first` reaches, with the affine primitives (pp_neck_backward_affine,
+    pp_unit_backward_affine, pp_down_backward_affine).  A layer is a convolution or upsampler with its BatchNorm2d: tensors holds
+    (weight, gamma, beta) of RPN_CONV_KEYS[first:] and then of the three upsamplers, stats (running_mean, running_var) of the same
+    layers, which get no gradient.  The folded (scale, shift) of every layer are evaluated once in the forward by the kernel that
+    wrote the engine's own (pp_bn_fold), so the backward reads the values the forward used.  A layer's dgamma / dbeta come from the
+    two fp64 sums of its primitive (pp_bn_affine_grad).  A unit's sums are sums over its dgrad product: the first trained unit runs
+    it when its norm trains, even where nothing in front needs the gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, first, stats, x, *tensors):
+        ctx.eng, ctx.first, ctx.stats = eng, first, stats
+        n = len(tensors) // 3
+        folds = [eng.bn_fold(tensors[3 * i + 1], tensors[3 * i + 2], *stats[i]) for i in range(n)]
+        outs = [_frame_taps(eng, first, c) for c in x]
+        y = torch.cat([o[0] for o in outs])
+        taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
+        units = [torch.stack([o[2][b][k] for o in outs]) for b in sorted(outs[0][2]) for k in range(sum(RPN_TABLE[b][1]))]
+        zs = [torch.cat([o[3][b] for o in outs]) for b in sorted(outs[0][3])]
+        ctx.save_for_backward(*([x] if first == 0 else []), y, *taps, *units, *zs, *tensors[::3], *[t for f in folds for t in f])
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        eng, first, saved = ctx.eng, ctx.first, list(ctx.saved_tensors)
+        x = saved.pop(0) if first == 0 else None
+        y, taps, saved = saved[0], saved[1:4], saved[4:]
+        nconv = len(RPN_CONV_KEYS)
+        n = nconv - first + 3  # layers: convolution k is layer k - first, upsampler b layer nconv - first + b
+        levels = [(b, mods, _W0[b], sum(mods)) for b, mods in RPN_TABLE if first <= _W0[b] + 1]  # the levels with taps
+        units = {b: [saved.pop(0) for _ in range(nu)] for b, _, _, nu in levels}
+        zs = {b: saved.pop(0) for b, _, w0, _ in levels if first <= w0}
+        ws, folds = saved[:n], [saved[n + 2 * i:n + 2 * i + 2] for i in range(n)]
+        need = ctx.needs_input_grad
+        need_x = need[3]
+        need_w = [need[4 + 3 * i] for i in range(n)]
+        need_a = [need[5 + 3 * i] or need[6 + 3 * i] for i in range(n)]
+        trains = lambda k: first <= k and (need_w[k - first] or need_a[k - first])  # noqa: E731
+        front = [need_x]
+        for b, mods in RPN_TABLE:
+            front.append(front[b] or any(trains(k) for k in range(_W0[b], _W0[b] + 1 + sum(mods))))
+        grads = [None] * (3 * n)
+
+        def put(i, dw, dscale, dshift):
+            grads[3 * i] = dw if need_w[i] else None
+            if need_a[i]:
+                dg, db = eng.bn_affine_grad(dscale, dshift, *ctx.stats[i])
+                grads[3 * i + 1], grads[3 * i + 2] = dg if need[5 + 3 * i] else None, db if need[6 + 3 * i] else None
+
+        gy = gy.contiguous()
+        dxn = [None] * 3
+        for b in range(3):
+            i = nconv - first + b
+            if need_w[i] or need_a[i] or front[b + 1]:
+                dw, dxn[b], ds, dh = eng.neck_backward_affine(b, taps[b], ws[i], *folds[i], y, gy, need_dx=front[b + 1], need_affine=need_a[i])
+                put(i, dw, ds, dh)
+        g = None
+        for b, mods, w0, nu in reversed(levels):
+            if not front[b + 1]:
+                break
+            g = dxn[b] if g is None else dxn[b] + g
+            need_dh = first <= w0 and (trains(w0) or front[b])
+            u = nu
+            for m in reversed(mods):  # rpn_block_backward with the affine primitive
+                u -= m
+                skip = g
+                if m == 2:
+                    i = w0 + 2 + u - first
+                    dw, g, ds, dh = eng.unit_backward_affine(units[b][u + 1], ws[i], *folds[i], g, need_affine=need_a[i])
+                    put(i, dw, ds, dh)
+                i = w0 + 1 + u - first
+                if u or need_dh or need_a[i]:
+                    dw, g, ds, dh = eng.unit_backward_affine(units[b][u], ws[i], *folds[i], g, dskip=skip, need_affine=need_a[i])
+                else:
+                    dw, g, ds, dh = eng.unit_backward_affine(units[b][u], ws[i], *folds[i], g, need_du=False, need_affine=False)
+                put(i, dw, ds, dh)
+            if need_dh:
+                i = w0 - first
+                dw, g, ds, dh = eng.down_backward_affine(x if b == 0 else taps[b - 1], ws[i], zs[b], *folds[i], g, need_dx=front[b],
+                                                         need_affine=need_a[i])
+                put(i, dw, ds, dh)
+        return (None, None, None, g if need_x else None) + tuple(grads)
+
+
 class _PfnFunction(torch.autograd.Function):
     """PointNet.forward in train mode and PointPillarsScatter.forward: one pp_pfn_train_forward over the pillars of all frames (rows
     grouped by frame; frames = ((row0, row1, coors [n,3], num [1]), ...)), then pp_scatter per frame.  Returns the canvases and the
@@ -241,9 +358,10 @@ class _PfnFunction(torch.autograd.Function):
 class PointPillars:
     _norm = "instance"
     grad_precision = "fp32"
+    bn_stats = None  # train(bn_stats=...) while training a BatchNorm network
     # read-only defaults for an object assembled without __init__ (no engine: the key-order and plan tests); __init__ and
     # load_state_dict give every object its own
-    _block = _down = _rpn = _pfn = _pfn_stats = types.MappingProxyType({})
+    _block = _down = _rpn = _pfn = _pfn_stats = _bn_run = types.MappingProxyType({})
     _pfn_nbt = None
     _uploaded = types.MappingProxyType({})  # per group of _GROUPS: its tensors' _version numbers at the last upload into the engine
     _trained = frozenset()                  # the groups that have been stepped since load_state_dict
@@ -260,6 +378,7 @@ class PointPillars:
         # unit weights, its stride-2 weight, the ten convolutions of blocks 1 and 2, the PFN's Conv1d weight and BatchNorm1d weight / bias
         self._params, self._neck, self._block, self._down, self._rpn, self._pfn = {}, {}, {}, {}, {}, {}
         self._pfn_stats = {}         # running_mean / running_var as device tensors (train(scope="all") moves them)
+        self._bn_run = {}            # BatchNorm backbone: running_mean / running_var of the RPN's nineteen norms as device tensors (frozen)
         self._pfn_nbt = None         # num_batches_tracked when the loaded dict carried it
         self.profile_stages = True  # the reference synchronises after every stage (:365-374)
         self.pfn_time, self.rpn_time, self.scatter_time, self.heads_time = 0.0, 0.0, 0.0, 0.0
@@ -273,7 +392,7 @@ class PointPillars:
     def eval(self):
         return self.train(False)
 
-    def train(self, mode=True, scope="head", grad_precision="fp32"):
+    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None):
         """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
         trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
         block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
@@ -284,17 +403,38 @@ class PointPillars:
         running statistics folded into the engine.
         grad_precision ("fp32" | "bf16x3" | "bf16", kept as net.grad_precision, "fp32" again after eval()): the operand precision of
         the Resnet units' gradient products (pp_unit_backward_mp), in effect under the scopes that run them ("block3", "stage3", "rpn",
-        "all") and inert under "head" and "neck".  The forward, the strided stages, the upsamplers, the head and the PFN stay fp32."""
+        "all") and inert under "head" and "neck".  The forward, the strided stages, the upsamplers, the head and the PFN stay fp32.
+        bn_stats (BatchNorm networks only, kept as net.bn_stats): "frozen" enables every scope there as fine-tuning with frozen
+        statistics.  Every BatchNorm2d of the RPN stays in eval mode and normalises with its running statistics, which do not move, as
+        does num_batches_tracked; its weight / bias train with the convolution whose backward primitive yields their gradient (a
+        unit's leading norm with that unit's convolution, blockN.1 with the strided convolution, deconvN.1 with the upsampler), so
+        "rpn" trains the 63 tensors of BN_RPN_KEYS and "all" the 66 of BN_ALL_KEYS.  In torch: net.train(), then .eval() on every
+        BatchNorm2d module.  The keyword is explicit because that is not what torch's net.train() alone means; "batch" (batch
+        statistics) is reserved and raises NotImplementedError.  Gradients are fp32 (grad_precision="fp32").  bn_stats governs the RPN's
+        BatchNorm2d layers only: under "all" the PFN's BatchNorm1d normalises with batch statistics and its running statistics move,
+        exactly as on the InstanceNorm network.  None keeps a BatchNorm network to scope="head"."""
         if grad_precision not in GRAD_PRECISIONS:
             raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         if scope not in SCOPES:
             raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
-        if mode and scope != "head" and (self._norm != "instance" or (scope == "all" and len(self._pfn_stats) != 2) or
-                                         any(len(getattr(self, g.attr)) != len(g.keys) for g in self._groups(scope) if g.scope != "head")):
-            raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only")
+        if bn_stats is not None:
+            if bn_stats not in BN_STATS:
+                raise ValueError(f"train: bn_stats must be None, 'frozen' or 'batch', got {bn_stats!r}")
+            if self._norm != "batch":
+                raise ValueError("train: bn_stats is for the BatchNorm networks; the InstanceNorm backbone has no statistics to freeze")
+            if bn_stats == "batch":
+                raise NotImplementedError("train(bn_stats='batch'): the batch-statistics BatchNorm backward does not exist yet; "
+                                          "bn_stats='frozen' fine-tunes with the running statistics")
+            if grad_precision != "fp32":
+                raise ValueError("train: the frozen-statistics backward is fp32 (grad_precision='fp32')")
+        if mode and scope != "head" and ((self._norm != "instance" and bn_stats != "frozen") or (scope == "all" and len(self._pfn_stats) != 2) or
+                                         any(len(getattr(self, g.attr)) != len(self._group_keys(g)) for g in self._groups(scope) if g.scope != "head")):
+            raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only" +
+                               ("; on a BatchNorm network pass bn_stats='frozen' to fine-tune with frozen statistics" if self._norm == "batch" else ""))
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
         self.grad_precision = grad_precision if self.training else "fp32"
+        self.bn_stats = bn_stats if self.training else None
         trained = self._groups(self._scope) if self.training else ()
         for g in _GROUPS.values():
             for p in getattr(self, g.attr).values():
@@ -308,17 +448,23 @@ class PointPillars:
         """The groups train(scope=scope) trains, from the front of the network to the head."""
         return [g for g in _GROUPS.values() if SCOPES.index(g.scope) <= SCOPES.index(scope)]
 
+    def _group_keys(self, g):
+        """The state_dict names of group g in this network: on the BatchNorm backbone a group of RPN convolutions also holds the
+        weight and bias of the BatchNorm2d layers that go with them (with_bn)."""
+        return with_bn(g.keys) if self._norm == "batch" else g.keys
+
     def _trainable(self):
         every = {k: p for g in self._groups(self._scope) for k, p in getattr(self, g.attr).items()}
         if self._scope in ("rpn", "all"):
-            return {k: every[k] for k in ALL_KEYS if k in every}  # the reference's state_dict order
+            return {k: every[k] for k in (BN_ALL_KEYS if self._norm == "batch" else ALL_KEYS) if k in every}  # the reference's order
         return every
 
     def named_parameters(self):
         """The trainable tensors on the device: heads.conv_{cls,box,dir}.{weight,bias}, behind rpn.deconv{1,2,3}.0.weight under
         train(scope="neck"), behind BLOCK3_KEYS (unit order) as well under train(scope="block3"), and behind rpn.block3.0.weight
         under train(scope="stage3"); under train(scope="rpn") the 25 tensors of RPN_KEYS in the reference's state_dict order, under
-        train(scope="all") the 28 of ALL_KEYS.  Everything before them is frozen."""
+        train(scope="all") the 28 of ALL_KEYS.  Everything before them is frozen.  On a BatchNorm network under bn_stats="frozen" every
+        RPN convolution comes with its norm's weight and bias: the 63 of BN_RPN_KEYS under "rpn", the 66 of BN_ALL_KEYS under "all"."""
         return iter(self._trainable().items())
 
     def parameters(self):
@@ -367,9 +513,13 @@ class PointPillars:
 
     def _sync_neck(self):
         """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone; when
-        a convolution of blocks 1 and 2 moved, all sixteen go up in one pp_update_rpn_weights."""
+        a convolution of blocks 1 and 2 moved, all sixteen go up in one pp_update_rpn_weights.  On the BatchNorm backbone the groups
+        hold the norms' weight / bias too: when one moved, all nineteen layers are folded again in place (pp_update_bn_fold)."""
+        fold = self._norm == "batch" and any(self._moved(attr) for attr in _BACKBONE)
         for attr in _BACKBONE:
             self._sync_group(attr)
+        if fold:
+            self._eng.update_bn_fold({**self._bn_run, **{k: p for attr in _BACKBONE for k, p in getattr(self, attr).items()}})
 
     def half(self):
         """The reference deploys FP16 TensorRT engines (framework/trt_utils.py:30, networks/pointpillars8_trt.py:208-223,295-314).
@@ -409,8 +559,10 @@ class PointPillars:
         dev_of = lambda k: torch.from_numpy(np.ascontiguousarray(self._sd[k], dtype=np.float32)).to(self._eng.device)  # noqa: E731
         trained = self._groups(self._scope) if self.training else ()
         for g in _GROUPS.values():
-            setattr(self, g.attr, {k: torch.nn.Parameter(dev_of(k), requires_grad=g in trained) for k in g.keys if k in self._sd})
+            setattr(self, g.attr, {k: torch.nn.Parameter(dev_of(k), requires_grad=g in trained) for k in self._group_keys(g) if k in self._sd})
         self._pfn_stats = {k: dev_of(k) for k in PFN_STAT_KEYS if k in self._sd}
+        bn_run = [f"{p}.{s}" for p, _ in Engine.bn_layers() for s in Engine.BN_FIELDS[2:]] if self._norm == "batch" else ()
+        self._bn_run = {k: dev_of(k) for k in bn_run if k in self._sd}
         self._pfn_nbt = int(np.asarray(self._sd[PFN_NBT_KEY])) if PFN_NBT_KEY in self._sd else None
         self._uploaded, self._trained = {}, frozenset()
         self._mark_uploaded()
@@ -557,6 +709,11 @@ class PointPillars:
         every = {**self._rpn, **self._down, **self._block}
         if first:
             x = x.detach()  # nothing in front of the stage has a backward: the graph must not reach the canvases
+        if self._norm == "batch":  # frozen statistics: every layer goes in with its norm's weight and bias
+            every.update(self._neck)
+            layers = RPN_CONV_KEYS[first:] + NECK_KEYS
+            stats = [tuple(self._bn_run[f"{Engine.bn_prefix(k)}.{s}"] for s in Engine.BN_FIELDS[2:]) for k in layers]
+            return _RpnBnFunction.apply(eng, first, stats, x, *[every[n] for k in layers for n in (k, *bn_affine_keys(k))])
         return _RpnFunction.apply(eng, self.grad_precision, first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
 
     def heads(self, x):

@@ -438,6 +438,54 @@ int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, flo
  * are NOT changed.  fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and before the first commit. */
 int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w /* 16 */, void* stream);
 
+/* ---- fine-tuning the BatchNorm backbone with frozen statistics (block_train.hip, down_train.hip, neck_train.hip, conv_plan.hip) ----
+ * Every BatchNorm2d(eps 1e-3) of the RPN in eval mode is a per-channel affine, norm(v)_c = scale_c v + shift_c with
+ * scale = gamma / sqrt(running_var + 1e-3), shift = beta - running_mean scale: the fold of pp_commit_weights, which the forward applies as
+ * max(fma(v, scale_c, shift_c), 0) in the prologue of the consuming layer.  The three primitives below are the siblings of
+ * pp_unit_backward, pp_down_backward and pp_neck_backward for that norm: the same layers, arguments, workspaces, frame chunks, MFMA
+ * products, K ranges and dw reduction, without the statistics passes.  Each takes DEVICE scale, shift f32[C] -- the folded values the
+ * forward used -- and returns, beside dw and du / dx, the two per-channel sums of the norm's backward as DEVICE doubles,
+ * dscale_c = sum_{frames, positions} g v and dshift_c = sum g (g: the gradient behind the ReLU, v: the norm's input), f64[C], both
+ * NULL: not written.  They are left in fp64 because dgamma = (dscale - running_mean dshift) / sqrt(running_var + 1e-3) is a difference that
+ * cancels (pp_bn_affine_grad).  Stateless: the result depends on the arguments only, and a context of either norm kind takes them.  fp32,
+ * no atomics, two runs are bit-identical; per-segment partial sums are added in index order, frames in frame order.  A frame's du / dx
+ * does not depend on the batch it rides in nor on the frame chunks; dw depends on nb through the fixed K ranges only.
+ * PP_E_ARG as the siblings (null pointer, sizes, nb outside 1..max_batch, misaligned w), for dscale without dshift or the reverse, and
+ * for sums that are not 8-byte aligned.
+ *
+ * pp_unit_backward_affine: the unit scale/shift -> ReLU -> Conv2d(C -> C, 3 x 3, pad 1).  a = max(fma(u, scale_c, shift_c), 0),
+ * dw = sum dy (*) a, da = dgrad(dy, w) with the blocked sum, g = da [a > 0], du = scale_c g (+ dskip: one fp32 add), dscale_c = sum g u,
+ * dshift_c = sum g.  du NULL: the dgrad is not run, and dscale / dshift must be NULL too (they are sums over it).
+ * pp_down_backward_affine: the stage Conv2d(3 x 3, stride 2) -> scale/shift -> ReLU.  g = dy [fma(z, scale_c, shift_c) > 0], dz = scale_c g,
+ * then the wgrad / dgrad of pp_down_backward over dz and the parity planes of x; dscale_c = sum g z, dshift_c = sum g.
+ * pp_neck_backward_affine: the branch ConvTranspose2d(k = s) -> scale/shift -> ReLU.  Z is recomputed, the mask is the given y > 0,
+ * dZ = scale_c g, dscale_c = sum g Z, dshift_c = sum g; scale / shift are those of the branch's Cup channels; shift is not read. */
+int pp_unit_backward_affine(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* scale, const float* shift,
+                            const float* dy, const float* dskip /* may be NULL */, int nb, float* dw, float* du /* NULL: skipped */,
+                            double* dscale /* may be NULL */, double* dshift /* may be NULL */, void* stream);
+int pp_down_backward_affine(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z, const float* scale,
+                            const float* shift, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */, double* dscale /* may be NULL */,
+                            double* dshift /* may be NULL */, void* stream);
+int pp_neck_backward_affine(pp_ctx* ctx, int branch, const float* x, const float* w, const float* scale, const float* shift, const float* y,
+                            const float* dy, int nb, float* dw, float* dx /* NULL: skipped */, double* dscale /* may be NULL */,
+                            double* dshift /* may be NULL */, void* stream);
+/* The fold of one BatchNorm2d layer on the device: DEVICE gamma, beta, running_mean, running_var f32[C], C <= 256 -> scale, shift f32[C] by
+ * the fp64 expression of pp_commit_weights, each value rounded once.  Stateless. */
+int pp_bn_fold(pp_ctx* ctx, int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float* scale,
+               float* shift, void* stream);
+/* The sums of an affine primitive -> the gradients of the BatchNorm2d layer's weight and bias: dgamma = r (dscale - running_mean dshift),
+ * dbeta = dshift, r = 1 / sqrt(running_var + 1e-3), evaluated in fp64 and rounded once.  Stateless. */
+int pp_bn_affine_grad(pp_ctx* ctx, int C, const double* dscale, const double* dshift, const float* running_mean, const float* running_var,
+                      float* dgamma, float* dbeta, void* stream);
+/* After an optimizer step: the nineteen BatchNorm2d layers of the RPN in state_dict order (per block its strided convolution's norm, the
+ * norms of its units, its upsampler's norm), four DEVICE tensors each -- bn[4 i + {0, 1, 2, 3}] = weight, bias, running_mean, running_var
+ * of layer i -- -> the folded (scale, shift) arrays of the committed plan, rewritten in place on `stream` by pp_bn_fold's kernel: bit for
+ * bit what a fresh pp_commit_weights of the same values holds.  Every pass reads those arrays when it runs (pp_backbone*, pp_infer_frame,
+ * pp_infer_batch, with the sparse first convolution and tile skipping: nothing derived from them is kept between passes), so all see the
+ * new values.  The host copies of pp_load_weights are NOT changed.  PP_E_STATE before the first commit, PP_E_ARG on an InstanceNorm
+ * context and for a null or misaligned pointer. */
+int pp_update_bn_fold(pp_ctx* ctx, const float* const* bn /* 76 */, void* stream);
+
 /* ---- training the pillar feature net: PointNet in train mode, its backward and the scatter's (pfn_train.hip) ----
  * PointNet.forward (pointpillars8_shared.py:30-60) with BatchNorm1d normalising by BATCH statistics.  Notation: f[p][t][0:9] the nine
  * decorated features of slot t of pillar p (x, y, z, r, x - mx, y - my, z - mz, x - cx, y - cy; arithmetic as pp_pfn: mean over all T

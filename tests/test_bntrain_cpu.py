@@ -1,0 +1,228 @@
+"""CPU: the float64 restatement of fine-tuning the BatchNorm RPN with frozen statistics (tests/bntrain_ref.py) -- the three affine
+backward primitives against torch autograd on the CPU in float64, the whole chain against the reference's float64 autograd goldens
+(tests/golden/bntrain_small.npz, tests/golden/make_bntrain_goldens.py) -- and, on a network object assembled without an engine, the
+parameter order, the group table and the argument rules of train(bn_stats=...).  Also the C ABI's declarations and a resource audit of
+the new streaming kernels."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, ROOT, golden, load_pkg
+import bntrain_ref as R
+from test_head_deferred_isa_cpu import HIPCC, kernel_usage
+
+sys.path.insert(0, GOLDEN)
+from make_bntrain_goldens import BN_C, DW_STRIDE, DX_STRIDE, SEED, small_inputs, split, weight_shapes  # noqa: E402
+
+SYMBOLS = ("pp_unit_backward_affine", "pp_down_backward_affine", "pp_neck_backward_affine", "pp_bn_fold", "pp_bn_affine_grad",
+           "pp_update_bn_fold")
+
+
+def rel(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / np.abs(np.asarray(b)).max())
+
+
+def t64(a, grad=False):
+    return torch.from_numpy(np.asarray(a, np.float64)).requires_grad_(grad)
+
+
+def bn_eval(v, gamma, beta, rm, rv):
+    return torch.nn.functional.batch_norm(v, t64(rm), t64(rv), gamma, beta, training=False, eps=1e-3)
+
+
+def norm_params(rng, C):
+    return (rng.uniform(0.5, 1.5, C).astype(np.float32), (rng.standard_normal(C) * 0.1).astype(np.float32),
+            (rng.standard_normal(C) * 0.1).astype(np.float32), rng.uniform(0.5, 1.5, C).astype(np.float32))
+
+
+# ------------------------------------------------------------------ 1. the primitives against torch autograd
+@pytest.mark.parametrize("C,h,w,nb,skip", [(64, 7, 5, 2, True), (128, 3, 2, 1, False)])
+def test_unit_against_autograd(C, h, w, nb, skip):
+    rng = np.random.default_rng(C + h)
+    u, wt, dz = rng.standard_normal((nb, C, h, w)), rng.standard_normal((C, C, 3, 3)) * 0.05, rng.standard_normal((nb, C, h, w))
+    bn = norm_params(rng, C)
+    ut, wtt, gamma, beta = t64(u, True), t64(wt, True), t64(bn[0], True), t64(bn[1], True)
+    z = torch.nn.functional.conv2d(torch.relu(bn_eval(ut, gamma, beta, bn[2], bn[3])), wtt, padding=1)
+    (z + ut if skip else z).backward(t64(dz))
+    scale, shift = R.fold(*bn)
+    assert rel(R.unit_forward(u, wt, scale, shift), z.detach().numpy()) <= 1e-10
+    dw, du, ds, dh = R.unit_backward(u, wt, scale, shift, dz, dskip=dz if skip else None)
+    dg, db = R.affine_grad(ds, dh, bn[2], bn[3])
+    for name, got, want in (("dw", dw, wtt.grad), ("du", du, ut.grad), ("dgamma", dg, gamma.grad), ("dbeta", db, beta.grad)):
+        assert rel(got, want.numpy()) <= 1e-10, name
+
+
+@pytest.mark.parametrize("cin,cout,hin,win", [(64, 64, 6, 4), (64, 128, 5, 3)])
+def test_down_against_autograd(cin, cout, hin, win):
+    rng = np.random.default_rng(cin + cout + hin)
+    ho, wo = (hin + 1) // 2, (win + 1) // 2
+    x, wt, dy = rng.standard_normal((2, cin, hin, win)), rng.standard_normal((cout, cin, 3, 3)) * 0.05, rng.standard_normal((2, cout, ho, wo))
+    bn = norm_params(rng, cout)
+    xt, wtt, gamma, beta = t64(x, True), t64(wt, True), t64(bn[0], True), t64(bn[1], True)
+    zt = torch.nn.functional.conv2d(xt, wtt, stride=2, padding=1)
+    ht = torch.relu(bn_eval(zt, gamma, beta, bn[2], bn[3]))
+    ht.backward(t64(dy))
+    scale, shift = R.fold(*bn)
+    hr, z = R.down_forward(x, wt, scale, shift, return_z=True)
+    assert rel(hr, ht.detach().numpy()) <= 1e-10 and rel(z, zt.detach().numpy()) <= 1e-10
+    dw, dx, ds, dh = R.down_backward(x, wt, z, scale, shift, dy)
+    dg, db = R.affine_grad(ds, dh, bn[2], bn[3])
+    for name, got, want in (("dw", dw, wtt.grad), ("dx", dx, xt.grad), ("dgamma", dg, gamma.grad), ("dbeta", db, beta.grad)):
+        assert rel(got, want.numpy()) <= 1e-10, name
+
+
+@pytest.mark.parametrize("branch", [0, 1, 2])
+def test_branch_against_autograd(branch):
+    rng = np.random.default_rng(40 + branch)
+    cin, cup, s, h, w = R.N.CIN[branch], R.N.CUP[branch], 1 << branch, 3, 2
+    x, wt, dy = rng.standard_normal((2, cin, h, w)), rng.standard_normal((cin, cup, s, s)) * 0.05, rng.standard_normal((2, cup, s * h, s * w))
+    bn = norm_params(rng, cup)
+    xt, wtt, gamma, beta = t64(x, True), t64(wt, True), t64(bn[0], True), t64(bn[1], True)
+    yt = torch.relu(bn_eval(torch.nn.functional.conv_transpose2d(xt, wtt, stride=s), gamma, beta, bn[2], bn[3]))
+    yt.backward(t64(dy))
+    scale, shift = R.fold(*bn)
+    y = R.branch_forward(x, wt, scale, shift)
+    assert rel(y, yt.detach().numpy()) <= 1e-10
+    dw, dx, ds, dh = R.branch_backward(x, wt, scale, y, dy)
+    dg, db = R.affine_grad(ds, dh, bn[2], bn[3])
+    for name, got, want in (("dw", dw, wtt.grad), ("dx", dx, xt.grad), ("dgamma", dg, gamma.grad), ("dbeta", db, beta.grad)):
+        assert rel(got, want.numpy()) <= 1e-10, name
+
+
+# ------------------------------------------------------------------ 2. the chain against the reference
+@pytest.fixture(scope="module")
+def restated():
+    canvas, ws, bn, dy = small_inputs()
+    wc, wn = split(ws)
+    bnd = dict(zip(R.BN_PREFIXES, bn))
+    fwd = R.rpn_forward(canvas, wc, wn, bnd)
+    grads, dx = R.rpn_backward(canvas, wc, wn, bnd, fwd, dy)
+    return dict(fwd=fwd, grads=grads, dx=dx, ws=ws, bn=bn)
+
+
+def test_restatement_matches_the_reference(restated):
+    g = golden("bntrain_small")
+    assert int(g["seed"]) == SEED and int(g["dw_stride"]) == DW_STRIDE and int(g["dx_stride"]) == DX_STRIDE
+    assert [tuple(w.shape) for w in restated["ws"]] == weight_shapes() and [t[0].shape[0] for t in restated["bn"]] == list(BN_C)
+    names = [str(k) for k in g["param_names"]]
+    assert names == list(R.PARAM_KEYS) and len(names) == 57
+    for i, k in enumerate(names):
+        got = restated["grads"][k]
+        got = got.reshape(-1)[::DW_STRIDE] if got.ndim == 4 else got
+        assert got.shape == g[f"g_{i}"].shape and rel(got, g[f"g_{i}"]) <= 1e-10, k
+        assert abs(np.abs(restated["grads"][k]).max() - float(g[f"g_{i}_max"])) <= 1e-10 * float(g[f"g_{i}_max"]), k
+    dx = restated["dx"]
+    assert rel(dx.reshape(-1)[::DX_STRIDE], g["dcanvas"]) <= 1e-10
+    assert abs(np.abs(dx).max() - float(g["dcanvas_max"])) <= 1e-10 * np.abs(dx).max()
+
+
+def test_forward_tensors_and_masks(restated):
+    fwd = restated["fwd"]
+    assert [len(u) for u in fwd["units"]] == [3, 5, 5] and fwd["y"].shape == (2, 320, 16, 12) and len(fwd["folds"]) == 19
+    masks = R.relu_masks(fwd["y"], fwd["units"], fwd["zs"], fwd["folds"])
+    assert len(masks) == 19 and all(0 < m.mean() < 1 for m in masks.values())
+    for b in range(3):
+        assert np.array_equal(fwd["units"][b][0] > 0, masks[f"stage{b}"])
+
+
+# ------------------------------------------------------------------ 3. order, groups, argument rules
+def test_parameter_order_is_the_reference_order():
+    shared = load_pkg("networks.pointpillars8_shared")
+    eng = load_pkg("engine").Engine
+    names = [str(k) for k in golden("bntrain_small")["param_names"]]
+    assert list(shared.BN_RPN_KEYS) == names + list(shared.HEAD_KEYS) and len(shared.BN_RPN_KEYS) == 63
+    assert list(shared.BN_ALL_KEYS) == list(shared.PFN_KEYS) + list(shared.BN_RPN_KEYS) and len(shared.BN_ALL_KEYS) == 66
+    assert [p for p, _ in eng.bn_layers()] == list(R.BN_PREFIXES) and [c for _, c in eng.bn_layers()] == list(BN_C)
+    sd = load_pkg("networks.init").init_state_dict(0, norm="batch")
+    assert all(k in sd for k in shared.BN_ALL_KEYS)
+    assert all(f"{p}.{s}" in sd and sd[f"{p}.{s}"].shape == (c,) for p, c in eng.bn_layers() for s in eng.BN_FIELDS)
+    # the InstanceNorm network's lists are what they were
+    assert len(shared.RPN_KEYS) == 25 and len(shared.ALL_KEYS) == 28 and shared.with_bn(shared.HEAD_KEYS) == shared.HEAD_KEYS
+
+
+def engineless(cls, shared):
+    net = object.__new__(cls)
+    net.training, net._scope = False, "head"
+    for g in shared._GROUPS.values():
+        setattr(net, g.attr, {k: torch.nn.Parameter(torch.zeros(1), requires_grad=False) for k in net._group_keys(g)})
+    net._pfn_stats = {k: torch.zeros(1) for k in shared.PFN_STAT_KEYS}
+    return net
+
+
+def test_group_table_on_the_batchnorm_network():
+    """A norm's weight / bias sit in the group of the convolution whose primitive yields their gradient, so every scope trains
+    three tensors per layer where the InstanceNorm network trains one."""
+    shared = load_pkg("networks.pointpillars8_shared")
+    net = engineless(load_pkg("networks.pointpillars8_export").PointPillars, shared)
+    assert [len(getattr(net, a)) for a in ("_pfn", "_rpn", "_down", "_block", "_neck", "_params")] == [3, 30, 3, 15, 9, 6]
+    assert "rpn.block3.1.weight" in net._down and "rpn.block3.3.conv_block.0.bias" in net._block and "rpn.deconv2.1.weight" in net._neck
+    assert "rpn.block1.1.bias" in net._rpn and "rpn.block2.5.conv_block.0.weight" in net._rpn
+    for scope, count in (("head", 6), ("neck", 15), ("block3", 30), ("stage3", 33), ("rpn", 63), ("all", 66)):
+        net.train(scope=scope, bn_stats="frozen")
+        assert net.bn_stats == "frozen" and net.training
+        names = [k for k, _ in net.named_parameters()]
+        assert len(names) == count and all(p.requires_grad for p in net.parameters()), scope
+        every = [p for g in shared._GROUPS.values() for p in getattr(net, g.attr).values()]
+        assert sum(p.requires_grad for p in every) == count, scope
+    net.train(scope="rpn", bn_stats="frozen")
+    assert [k for k, _ in net.named_parameters()] == list(shared.BN_RPN_KEYS)
+    net.train(scope="all", bn_stats="frozen")
+    assert [k for k, _ in net.named_parameters()] == list(shared.BN_ALL_KEYS)
+    net.eval()
+    assert net.bn_stats is None and [k for k, _ in net.named_parameters()] == list(shared.HEAD_KEYS)
+
+
+def test_train_argument_rules():
+    shared = load_pkg("networks.pointpillars8_shared")
+    bn = engineless(load_pkg("networks.pointpillars8_export").PointPillars, shared)
+    trt = engineless(load_pkg("networks.pointpillars8_trt").PointPillars, shared)
+    inn = engineless(shared.PointPillars, shared)
+    for net in (bn, trt):
+        for scope in shared.SCOPES[1:]:
+            with pytest.raises(RuntimeError, match="InstanceNorm.*bn_stats='frozen'"):
+                net.train(scope=scope)  # today's refusal, with the hint
+        net.train()  # the head alone needs no keyword
+        assert net.training and net.bn_stats is None
+        with pytest.raises(NotImplementedError):
+            net.train(scope="rpn", bn_stats="batch")
+        with pytest.raises(ValueError):
+            net.train(scope="rpn", bn_stats="running")
+        for prec in ("bf16x3", "bf16"):
+            with pytest.raises(ValueError, match="fp32"):
+                net.train(scope="rpn", bn_stats="frozen", grad_precision=prec)
+        assert net.train(scope="rpn", bn_stats="frozen") is net and net.grad_precision == "fp32"
+    for value in ("frozen", "batch"):
+        with pytest.raises(ValueError, match="BatchNorm"):
+            inn.train(scope="rpn", bn_stats=value)
+    inn.train(scope="rpn")
+    assert [k for k, _ in inn.named_parameters()] == list(shared.RPN_KEYS) and inn.bn_stats is None
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@pytest.mark.parametrize("src,names", [("block_train.hip", ("k_affine_unit_pack", "k_affine_unit_du", "k_affine_reduce")),
+                                       ("down_train.hip", ("k_affine_down_dz", "k_affine_reduce")),
+                                       ("neck_train.hip", ("k_affine_neck_dz", "k_affine_reduce"))])
+def test_affine_passes_use_no_scratch(src, names):
+    k = {n: u for n, u in kernel_usage(src).items() if "k_affine_" in n}
+    print(k)
+    assert len(k) == len(names) and all(any(m in n for n in k) for m in names), sorted(k)
+    for n, u in k.items():
+        assert u["ScratchSize [bytes/lane]"] == "0" and u["VGPRs Spill"] == "0" and u["SGPRs Spill"] == "0", (n, u)
+
+
+def test_c_abi_is_declared_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "pp_hip.h")).read()
+    protos = load_pkg("_lib").PROTOTYPES
+    for name in SYMBOLS:
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
+        assert m, name + " is not declared in include/pp_hip.h"
+        nargs = len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
+        assert name in protos and len(protos[name][1]) == nargs, (name, nargs)
+    # the InstanceNorm entries keep refusing the BatchNorm backbone
+    for src, name in (("block_train.hip", "pp_unit_backward"), ("down_train.hip", "pp_down_backward"), ("neck_train.hip", "pp_neck_backward")):
+        text = open(os.path.join(ROOT, "3d_object_detection_amd", "csrc", src)).read()
+        assert f'"{name}: the InstanceNorm backbone only' in text, name
