@@ -102,6 +102,10 @@ PROTOTYPES = {
     "pp_bn_fold": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_bn_affine_grad": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_bn_fold": (ctypes.c_int, [c_p, c_p, c_p]),
+    "pp_backbone_train_taps_bn": (ctypes.c_int, [c_p, c_p, ctypes.c_int] + [c_p] * 12),
+    "pp_unit_backward_bn": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    "pp_down_backward_bn": (ctypes.c_int, [c_p] + [ctypes.c_int] * 4 + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    "pp_neck_backward_bn": (ctypes.c_int, [c_p, ctypes.c_int] + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
     "pp_pfn_train_forward": (ctypes.c_int, [c_p] * 12),
     "pp_scatter_backward": (ctypes.c_int, [c_p] * 6),
     "pp_pfn_backward": (ctypes.c_int, [c_p] * 15),

@@ -26,6 +26,8 @@
 // depend on the batch it rides in; dw depends on nb within fp32 summation error (the K ranges do).
 // pp_unit_backward_affine is the same unit with a per-channel affine (a frozen BatchNorm2d) for the norm: k_affine_unit_pack, the two
 // products, k_affine_unit_du and k_affine_reduce; pp_unit_backward itself stays the InstanceNorm backbone's.
+// pp_unit_backward_bn is that unit behind a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_unit_sums behind the
+// dgrad of every chunk, then k_bn_coef and one in-place k_bn_unit_du over all frames.
 // block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp); what both share is in block_train.h.
 #include <cmath>
 #include "pp_common.h"
@@ -309,6 +311,54 @@ __global__ void __launch_bounds__(256) k_affine_unit_du(const float* __restrict_
     if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
 }
 
+// ---- the unit behind a train-mode BatchNorm (pp_unit_backward_bn): k_affine_unit_pack and the two products as above, the raw da left in
+// du.  The norm backward needs the sums of ALL frames, so it runs behind the frame chunks, on u and du alone: the mask is re-evaluated
+// by the pack's own fma.  k_bn_unit_sums: grid (C, frames, S), g = da [fma(u, scale, shift) > 0], the segment's sum g u, sum g in fp64
+// -> pst[frame][c][segment][2].  k_bn_unit_du: same grid, in place once k_bn_coef has pooled them:
+// du = scale ((g - c1) - xhat c2) (+ dskip), xhat = (u - mean) r ------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_bn_unit_sums(const float* __restrict__ u, const float* __restrict__ du, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, double* __restrict__ pst, int C, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* dp = du + pl * N;
+    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sgu = 0.0, sg = 0.0;
+    strided4(lo, hi, [&](int i) { return float2{up[i], dp[i]}; },
+             [&](float2 v) {
+                 if (fmaf(v.x, sc, sh) > 0.f) {
+                     const double g = (double)v.y;
+                     sgu += g * (double)v.x; sg += g;
+                 }
+             });
+    block_sum2(sgu, sg, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
+}
+
+__global__ void __launch_bounds__(256) k_bn_unit_du(const float* __restrict__ u, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                    const float* __restrict__ coef, const float* __restrict__ dskip, float* __restrict__ du, int C,
+                                                    int N, int L)
+{
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + c;
+    const float* up = u + pl * N;
+    float* dp = du + pl * N;
+    const float sc = scale[c], sh = shift[c];
+    const float c1 = coef[4 * c], c2 = coef[4 * c + 1], meanf = coef[4 * c + 2], rf = coef[4 * c + 3];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    for (int i = lo + tid; i < hi; i += 256) {
+        const float uu = up[i];
+        const float g = fmaf(uu, sc, sh) > 0.f ? dp[i] : 0.f;
+        const float xhat = (uu - meanf) * rf;
+        float v = sc * ((g - c1) - xhat * c2);
+        if (dskip) v = v + dskip[pl * N + i];
+        dp[i] = v;
+    }
+}
+
 // ---- weight update: image element i holds position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T.  U = G g G^T is
 // evaluated in fp64 in the host packers' own expression order and rounded once; the library is built with -ffp-contract=off on both
 // sides, so the image is the one a fresh commit of the same values packs, bit for bit -------------------------------------------------
@@ -517,6 +567,94 @@ extern "C" int pp_unit_backward_affine(pp_ctx* ctx, int C, int h, int w, const f
     }
     hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
     if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, dscale, dshift);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// pp_unit_backward_affine behind a train-mode BatchNorm: (scale, shift) are the fold of the batch statistics (mean, var) the forward
+// used.  Two phases across the frame chunks: the chunks run pack, wgrad and dgrad (raw da -> du) and the segment sums; once every
+// frame's sums are in, k_bn_coef pools them and one in-place pass over all frames writes du.  chunk_frames > 0 caps the frames of a
+// chunk below the workspace rule (du and the sums do not depend on it; dw does within fp32 summation error, through the K ranges).
+extern "C" int pp_unit_backward_bn(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* scale, const float* shift,
+                                   const float* mean, const float* var, const float* dy, const float* dskip, int nb, float* dw, float* du,
+                                   double* dscale, double* dshift, int chunk_frames, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: C must be 64, 128 or 256");
+    if (!u || !wgt || !scale || !shift || !mean || !var || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: null pointer");
+    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: dscale and dshift go together");
+    if (!du && dscale) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: dscale and dshift need du (they are sums over the dgrad product)");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: nb must be 1 .. max_batch");
+    if (chunk_frames < 0) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: chunk_frames must be >= 0");
+    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: h, w >= 1 and h w >= 2");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: w must be 16-byte aligned");
+    if (((uintptr_t)u | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw |
+         (uintptr_t)du) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: tensors must be 4-byte aligned");
+    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: dscale / dshift must be 8-byte aligned");
+    const int64_t wp64 = (int64_t)w + 2, PP64 = ((int64_t)h + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
+    if (2 * (uint64_t)C * (uint64_t)PS64 * sizeof(float) > WS_BUDGET)
+        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: map too large (one frame's planes exceed the 256 MB workspace)");
+    const int wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64, N = h * w;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: as pp_unit_backward, the chunk capped by chunk_frames
+    const size_t pf_elems = (size_t)C * PS;
+    int fc = (int)(WS_CHUNK / (2 * pf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    if (chunk_frames > 0 && chunk_frames < fc) fc = chunk_frames;
+    const int TN = C >= 128 ? 128 : 192;
+    const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = C * NC;
+    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)C * 4)) || // k_bn_coef's coefficients
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * C * SEG_MAX * 2)) || // every frame's segment sums: pooled once, behind the chunks
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
+        return rc;
+    float* ap = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * pf_elems;
+    if (du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, C);
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t o = (size_t)f0 * C * N;
+        hipLaunchKernelGGL(k_affine_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, ap, dzp, scale, shift, C, h, w, wp, G, PP, PS, LP);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / TN, C / 64, sp);
+        if (C >= 128)
+            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        else
+            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        gbase += sp;
+        if (du) {
+            float* duc = du + o;
+            if (C == 64)
+                hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            else if (C == 128)
+                hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            else
+                hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+            hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, u + o, duc, scale, shift, ws->pst + (size_t)f0 * C * S * 2, C, N, L,
+                               S);
+        }
+    }
+    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+    if (du) {
+        hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, mean, var, (double)nb * (double)N, ws->stm, dscale,
+                           dshift);
+        hipLaunchKernelGGL(k_bn_unit_du, dim3(C, nb, S), dim3(256), 0, stream, u, scale, shift, ws->stm, dskip, du, C, N, L);
+    }
     PP_HIP(hipGetLastError());
     return 0;
 }

@@ -53,6 +53,14 @@ struct pp_net {
     // copy hooks of the tap entry points, one per level b (null: inert; armed for one single-frame pass):
     float* unit_tap[3] = {}; // caller memory f32[n_b][C_b][H>>b][W>>b] for the inputs of block b + 1's units (n_b = 3, 5, 5); pp_backbone_block_taps arms level 2
     float* z_tap[3] = {};    // caller memory f32[C_b][H>>b][W>>b] for the raw output of level b's strided conv; pp_backbone_stage_taps arms level 2
+    // the lock-step training pass of the BatchNorm backbone (pp_backbone_train_taps_bn), armed for one pass: every norm site accumulates
+    // its statistics as on the InstanceNorm backbone, bn_pass_finalize pools them over the frames behind the producer, and consumers read
+    // the pass's own fold (bnp_scale / bnp_shift, laid out as bn_scale / bn_shift, which the pass leaves alone)
+    bool bn_pass = false;
+    float* bnp_scale = nullptr;
+    float* bnp_shift = nullptr;
+    const float* const* bnp_gb = nullptr; // the 38 device pointers (gamma, beta) of the nineteen layers in bn_sites() order
+    float* bnp_out[4] = {};               // caller memory f32[19][256] each: mean, var, scale, shift
     double* dbg_stats = nullptr; // statistics accumulators of pp_debug_layer (allocated on its first call that asks for statistics)
     int w4_strips = -1; // PP_W4_STRIPS, read once at pp_create: -1 cost model, 0 never, 2 whenever whole main tiles exist (parity tests of the strip tiles)
 };

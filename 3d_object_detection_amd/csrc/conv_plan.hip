@@ -554,7 +554,7 @@ void pp_net_destroy(pp_ctx* ctx)
             if (net->buf[l][b]) (void)hipFree(net->buf[l][b] - W6_FRONT_PAD);
     for (Layer& L : net->layers)
         if (L.w) (void)hipFree(L.w);
-    void* ptrs[] = {net->dbg_stats, net->up, net->stats, net->aff, net->bn_scale, net->bn_shift, net->head_bias, net->head_bias_perm, net->ones, net->zeros};
+    void* ptrs[] = {net->dbg_stats, net->up, net->stats, net->aff, net->bn_scale, net->bn_shift, net->bnp_scale, net->bnp_shift, net->head_bias, net->head_bias_perm, net->ones, net->zeros};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     delete net;

@@ -1,6 +1,7 @@
 // 2D backbone (RPN) + shared head, host side: what runs per frame.  launch_conv (one layer of the committed plan: the kernel parameters,
 // the family's grid rule, the region launches of wino4 / wino6), the norm launches, pp_run_backbone, the head in its three forms (fused,
-// cls-only, materialised on demand) and the entry points pp_backbone, pp_head and pp_backbone_*taps.  The types are in conv_net.h; its
+// cls-only, materialised on demand) and the entry points pp_backbone, pp_head, pp_backbone_*taps and pp_backbone_train_taps_bn (the
+// lock-step training pass of the BatchNorm backbone with batch statistics).  The types are in conv_net.h; its
 // own kernels are the three small ones around the layers: norm_relu_stats, norm_finalize and f32_to_f16.
 #include <cstring>
 #include "conv_net.h"
@@ -111,6 +112,31 @@ __global__ void __launch_bounds__(320) norm_finalize(const double* __restrict__ 
     const double rstd = 1.0 / sqrt(var + (double)eps);
     aff[(size_t)blockIdx.x * aff_fs + c] = (float)rstd;
     aff[(size_t)blockIdx.x * aff_fs + 320 + c] = (float)(-mean * rstd);
+}
+
+// Train-mode BatchNorm: the per-frame accumulators of one site pooled in frame order in fp64 over n = frames x positions, mean and the
+// biased variance rounded once to fp32, and the (scale, shift) that pp_bn_fold's fp64 expression gives for (gamma, beta, mean32, var32)
+__global__ void __launch_bounds__(256) bn_batch_finalize(const double* __restrict__ acc, size_t acc_fs, int nb, int C, int stat_C, double n,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ mean,
+                                                         float* __restrict__ var, float* __restrict__ scale, float* __restrict__ shift,
+                                                         float* __restrict__ pass_scale, float* __restrict__ pass_shift)
+{
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    double s = 0.0, q = 0.0;
+    for (int f = 0; f < nb; ++f) {
+        const double* pa = acc + (size_t)f * acc_fs;
+#pragma unroll
+        for (int r = 0; r < NREP; ++r) { s += pa[((size_t)r * stat_C + c) * 2]; q += pa[((size_t)r * stat_C + c) * 2 + 1]; }
+    }
+    const double m = s / n;
+    double v = q / n - m * m;
+    v = v > 0.0 ? v : 0.0;
+    const float mf = (float)m, vf = (float)v;
+    const double sc = (double)gamma[c] / sqrt((double)vf + 1e-3);
+    const float scf = (float)sc, shf = (float)((double)beta[c] - (double)mf * sc);
+    mean[c] = mf; var[c] = vf; scale[c] = scf; shift[c] = shf;
+    pass_scale[c] = scf; pass_shift[c] = shf;
 }
 
 __global__ void __launch_bounds__(256) f32_to_f16(const float* __restrict__ x, _Float16* __restrict__ y, size_t n)
@@ -319,8 +345,8 @@ NormRef norm_ref(pp_ctx* ctx, int site, int C, int coff, size_t count)
     r.C = C;
     if (ctx->cfg.norm_kind == 1) {
         r.mode = PRE_AFFINE;
-        r.scale = net->bn_scale + (size_t)site * 320 + coff;
-        r.shift = net->bn_shift + (size_t)site * 320 + coff;
+        r.scale = (net->bn_pass ? net->bnp_scale : net->bn_scale) + (size_t)site * 320 + coff;
+        r.shift = (net->bn_pass ? net->bnp_shift : net->bn_shift) + (size_t)site * 320 + coff;
     } else {
         r.mode = PRE_STATS;
         r.acc = net->stats + (size_t)site * NREP * 320 * 2;
@@ -332,8 +358,9 @@ NormRef norm_ref(pp_ctx* ctx, int site, int C, int coff, size_t count)
 
 double* stat_slot(pp_ctx* ctx, int site)
 {
-    if (ctx->cfg.norm_kind == 1) return nullptr;
-    return ((pp_net*)ctx->net)->stats + (size_t)site * NREP * 320 * 2;
+    pp_net* net = (pp_net*)ctx->net;
+    if (ctx->cfg.norm_kind == 1 && !net->bn_pass) return nullptr;
+    return net->stats + (size_t)site * NREP * 320 * 2;
 }
 
 int launch_norm_relu(pp_ctx* ctx, const float* x, float* y, int C, int HW, const NormRef& pre, double* stat, hipStream_t stream,
@@ -362,6 +389,26 @@ bool level0_main_wino6(const pp_net* net, int h, int w)
 
 using namespace ppc;
 
+// pp_backbone_train_taps_bn: the producer of block b's norm `k` has been launched over nb frames (k = 0 .. 5: site_block(b, k); k = 7:
+// the upsampler's channel slice of site 7): pool its statistics and write the pass's fold.  Inert outside such a pass.
+static int bn_pass_finalize(pp_ctx* ctx, int b, int k, int nb, hipStream_t stream)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    if (!net->bn_pass) return 0;
+    const bool up = k == 7;
+    const int nconv = 1 + (b == 0 ? 3 : 5);                            // norms of the block's convolutions; the upsampler's follows them
+    const int idx = (b == 0 ? 0 : b == 1 ? 5 : 12) + (up ? nconv : k); // the layer in bn_sites() order
+    const int C = up ? (b == 0 ? 64 : 128) : kC[b], coff = up ? (b == 0 ? 0 : b == 1 ? 64 : 192) : 0;
+    const int site = up ? 7 : site_block(b, k), stat_C = up ? 320 : kC[b];
+    const double n = (double)nb * (up ? (double)ctx->H * ctx->W : (double)(ctx->H >> b) * (ctx->W >> b));
+    const size_t o = (size_t)site * 320 + coff;
+    hipLaunchKernelGGL(bn_batch_finalize, dim3(1), dim3(256), 0, stream, net->stats + (size_t)site * NREP * 320 * 2 + (size_t)coff * 2, STAT_FS, nb, C,
+                       stat_C, n, net->bnp_gb[2 * idx], net->bnp_gb[2 * idx + 1], net->bnp_out[0] + idx * 256, net->bnp_out[1] + idx * 256,
+                       net->bnp_out[2] + idx * 256, net->bnp_out[3] + idx * 256, net->bnp_scale + o, net->bnp_shift + o);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
 // deconv L of block b on the raw block output x -> channel slice of up[320,H,W] + stats (site 7, channel offset)
 static int run_upsampler(pp_ctx* ctx, const Layer& L, int b, const float* x, int nb, hipStream_t stream)
 {
@@ -386,7 +433,7 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
     if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "backbone: batch exceeds cfg.max_batch");
     ctx->sc1_last_nb = 0;
     pp_ts_begin_pass(ctx);
-    if (ctx->cfg.norm_kind == 0) PP_HIP(hipMemsetAsync(net->stats, 0, STAT_FS * sizeof(double) * nb, stream));
+    if (ctx->cfg.norm_kind == 0 || net->bn_pass) PP_HIP(hipMemsetAsync(net->stats, 0, STAT_FS * sizeof(double) * nb, stream));
     const float* x = canvas;
     int Hin = ctx->gx, Win = ctx->gy;
     size_t li = 0;
@@ -412,22 +459,25 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
             if (b == 0) { k.pmap = pmap; k.feat = feat; }
             if ((rc = launch_conv(ctx, net->layers[li++], k, stream))) return rc;
         }
-        // the level's pre-norm conv output z leaves through its own copy hook: the first unit reuses Bf[0] as a spare
-        if (nb == 1 && net->z_tap[b])
-            PP_HIP(hipMemcpyAsync(net->z_tap[b], Bf[0], (size_t)c * cnt * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if ((rc = bn_pass_finalize(ctx, b, 0, nb, stream))) return rc;
+        // the level's pre-norm conv output z leaves through its own copy hook: the first unit reuses Bf[0] as a spare.  The hooks copy
+        // one frame, or every frame of the lock-step training pass (z [nb][C][h][w], units [n_b][nb][C][h][w]: a unit's frames together)
+        const bool hooks = nb == 1 || net->bn_pass;
+        const size_t ubytes = (size_t)nb * c * cnt * sizeof(float);
+        if (hooks && net->z_tap[b]) PP_HIP(hipMemcpyAsync(net->z_tap[b], Bf[0], ubytes, hipMemcpyDeviceToDevice, stream));
         // y = relu(norm(Bf[0])) -> Bf[1] + stats(site 1) (the first Resnet2 unit's leading norm)
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_NORM))) return rc;
         if ((rc = launch_norm_relu(ctx, Bf[0], Bf[1], c, (int)cnt, norm_ref(ctx, site_block(b, 0), c, 0, cnt),
                                    stat_slot(ctx, site_block(b, 1)), stream, nb, net->up16 ? 1 : 0, net->up16 ? 1 : 0))) return rc;
+        if ((rc = bn_pass_finalize(ctx, b, 1, nb, stream))) return rc;
         if ((rc = pp_stage_mark(ctx, stream, PP_ST_CONV))) return rc;
         float* cur = Bf[1];
         float* spare[3] = {Bf[0], Bf[2], Bf[3]};
         // the unit inputs (h, m, r at level 0; h, m3, r3, m4, r4 at levels 1 and 2) leave through the copy hook behind the launch that
         // produces each: the level buffers are reused before the pass ends
-        float* utap = nb == 1 ? net->unit_tap[b] : nullptr;
-        const size_t ubytes = (size_t)c * cnt * sizeof(float);
+        float* utap = hooks ? net->unit_tap[b] : nullptr;
         int ucount = 0;
-        if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, cur, ubytes, hipMemcpyDeviceToDevice, stream));
+        if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * nb * c * cnt, cur, ubytes, hipMemcpyDeviceToDevice, stream));
         int ts_k = 0; // level 0: ordinal of the next stride-1 layer (launch_conv ignores it unless this pass built tile lists)
         // the level's next stride-1 layer: out = conv(relu(norm_site(in))) + res, with the statistics of out
         auto conv = [&](const float* in, float* out, const float* res, int site, double* stat) {
@@ -444,9 +494,11 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
             double* out_stat = u == block_units(b) - 1 ? nullptr : stat_slot(ctx, site_block(b, 1 + 2 * (u + 1)));
             if (unit_two_convs(b, u)) {
                 if ((rc = conv(cur, t1, nullptr, 1 + 2 * u, stat_slot(ctx, site_block(b, 2 + 2 * u))))) return rc;
-                if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, t1, ubytes, hipMemcpyDeviceToDevice, stream));
+                if ((rc = bn_pass_finalize(ctx, b, 2 + 2 * u, nb, stream))) return rc;
+                if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * nb * c * cnt, t1, ubytes, hipMemcpyDeviceToDevice, stream));
                 if ((rc = conv(t1, t2, cur, 2 + 2 * u, out_stat))) return rc;
-                if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * c * cnt, t2, ubytes, hipMemcpyDeviceToDevice, stream));
+                if (out_stat && (rc = bn_pass_finalize(ctx, b, 1 + 2 * (u + 1), nb, stream))) return rc;
+                if (utap) PP_HIP(hipMemcpyAsync(utap + (size_t)ucount++ * nb * c * cnt, t2, ubytes, hipMemcpyDeviceToDevice, stream));
                 spare[1] = cur; // t2 becomes current; old current and t1 are free
                 cur = t2;
             } else {
@@ -457,6 +509,7 @@ int pp_run_backbone(pp_ctx* ctx, const float* canvas, int nb, hipStream_t stream
         }
         net->tap[b] = cur;
         if ((rc = run_upsampler(ctx, net->layers[li++], b, cur, nb, stream))) return rc;
+        if ((rc = bn_pass_finalize(ctx, b, 7, nb, stream))) return rc;
         x = cur;
         Hin = h;
         Win = w;
@@ -622,4 +675,48 @@ extern "C" int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* r
     bool null = !units || !z;
     for (int b = 0; b < 3 && !null; ++b) null = !units[b] || !z[b];
     return backbone_taps(ctx, "pp_backbone_train_taps", null ? "pp_backbone_train_taps" : nullptr, canvas, rpn_out, x1, x2, x3, units, z, stream_);
+}
+
+// The lock-step training forward of the BatchNorm backbone: the dense backbone layer by layer over all nb frames, every BatchNorm2d
+// normalising with the statistics of the batch.  gamma_beta: the 38 device pointers (weight, bias) of the nineteen layers in
+// state_dict order.  Outputs (caller memory): rpn_out [nb][320][H][W]; x1 .. x3 [nb][C_b][H>>b][W>>b]; units[b] [3 | 5 | 5][nb][C_b][H>>b][W>>b]
+// (a unit's frames together) and z[b] [nb][C_b][H>>b][W>>b] (either array, or any entry, may be null: a tap nobody needs); mean, var (biased), scale, shift
+// f32[19][256] in the same layer order, a row filled up to its layer's channels.  The committed fold of the running statistics is not
+// touched: inference between steps sees what it saw.
+extern "C" int pp_backbone_train_taps_bn(pp_ctx* ctx, const float* canvas, int nb, const float* const* gamma_beta, float* rpn_out, float* x1,
+                                         float* x2, float* x3, float* const* units, float* const* z, float* mean, float* var, float* scale,
+                                         float* shift, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, "pp_backbone_train_taps_bn: weights not committed");
+    if (ctx->cfg.norm_kind != 1) return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps_bn: the BatchNorm backbone only");
+    if (!canvas || !gamma_beta || !rpn_out || !x1 || !x2 || !x3 || !mean || !var || !scale || !shift)
+        return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps_bn: null pointer");
+    for (int i = 0; i < 38; ++i)
+        if (!gamma_beta[i] || ((uintptr_t)gamma_beta[i] & 3))
+            return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps_bn: null or misaligned weight / bias pointer");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps_bn: nb must be 1 .. max_batch");
+    pp_net* net = (pp_net*)ctx->net;
+    if (net->eff_prec != 0 || net->up16)
+        return pp_fail(ctx, PP_E_ARG, "pp_backbone_train_taps_bn: fp32 mode only (in the 16-bit modes the level buffers may hold fp16)");
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    if (int rc0 = pp_head_materialise(ctx, stream)) return rc0; // the concat buffer is about to be overwritten
+    if (!net->bnp_scale) PP_HIP(hipMalloc((void**)&net->bnp_scale, (size_t)24 * 320 * sizeof(float)));
+    if (!net->bnp_shift) PP_HIP(hipMalloc((void**)&net->bnp_shift, (size_t)24 * 320 * sizeof(float)));
+    net->bn_pass = true;
+    net->bnp_gb = gamma_beta;
+    net->bnp_out[0] = mean; net->bnp_out[1] = var; net->bnp_out[2] = scale; net->bnp_out[3] = shift;
+    for (int b = 0; b < 3; ++b) { net->unit_tap[b] = units ? units[b] : nullptr; net->z_tap[b] = z ? z[b] : nullptr; }
+    int rc = pp_run_backbone(ctx, canvas, nb, stream, nullptr, nullptr);
+    const int HW = ctx->H * ctx->W;
+    if (!rc) rc = launch_norm_relu(ctx, net->up, rpn_out, 320, HW, norm_ref(ctx, 7, 320, 0, (size_t)HW), nullptr, stream, nb, 0);
+    net->bn_pass = false;
+    net->bnp_gb = nullptr;
+    for (int b = 0; b < 3; ++b) net->unit_tap[b] = net->z_tap[b] = nullptr;
+    if (rc) return rc;
+    float* dst[3] = {x1, x2, x3};
+    for (int b = 0; b < 3; ++b)
+        PP_HIP(hipMemcpyAsync(dst[b], net->tap[b], (size_t)nb * kC[b] * (ctx->H >> b) * (ctx->W >> b) * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    return 0;
 }

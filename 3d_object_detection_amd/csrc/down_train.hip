@@ -29,6 +29,8 @@
 // nb within fp32 summation error (the K ranges do), and not on whether dx is asked for.
 // pp_down_backward_affine is the same stage with a per-channel affine (a frozen BatchNorm2d) for the norm: k_affine_down_dz in place
 // of the three norm passes, then the same products and k_affine_reduce; pp_down_backward itself stays the InstanceNorm backbone's.
+// pp_down_backward_bn is that stage in front of a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_down_sums over
+// all frames and k_bn_coef ahead of the chunks, k_bn_down_dz in them.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -48,6 +50,7 @@ struct down_ws {
     double* pst = nullptr;   size_t pst_elems = 0;    // [2][fc][Cout][segments][2]: a plane's segment sums of (z, z^2), then of (Gr, Gr xhat)
     float* wT = nullptr;     size_t wT_elems = 0;
     float* part = nullptr;   size_t part_elems = 0;
+    float* coef = nullptr;   size_t coef_elems = 0;   // [Cout][4]: k_bn_coef's coefficients (pp_down_backward_bn)
 };
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -203,6 +206,61 @@ __global__ void __launch_bounds__(256) k_affine_down_dz(const float* __restrict_
     }
     block_sum2(sgz, sg, red);
     if (tid == 0) { pst[(pl * SP + blockIdx.z) * 2] = sgz; pst[(pl * SP + blockIdx.z) * 2 + 1] = sg; }
+}
+
+// ---- the stage in front of a train-mode BatchNorm (pp_down_backward_bn).  The norm backward needs the sums of ALL frames, and they need
+// only z and dy, so they come first, over every frame at once.  k_bn_down_sums: grid (Cout, frames, S) over the tight plane, g = dy
+// [fma(z, scale, shift) > 0], the segment's sum g z, sum g in fp64 -> pst[frame][co][segment][2].  k_bn_down_dz: grid (Cout, frames, SP) as
+// k_down_norm once k_bn_coef has pooled them: dz = scale ((g - c1) - zhat c2), zhat = (z - mean) r, into the padded plane -------------------
+__global__ void __launch_bounds__(256) k_bn_down_sums(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, double* __restrict__ pst, int cout, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
+    const float* zi = z + pl * N;
+    const float* dp = dy + pl * N;
+    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sgz = 0.0, sg = 0.0;
+    strided4(lo, hi, [&](int i) { return float2{zi[i], dp[i]}; },
+             [&](float2 v) {
+                 if (fmaf(v.x, sc, sh) > 0.f) {
+                     const double g = (double)v.y;
+                     sgz += g * (double)v.x; sg += g;
+                 }
+             });
+    block_sum2(sgz, sg, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgz; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
+}
+
+__global__ void __launch_bounds__(256) k_bn_down_dz(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
+                                                    const float* __restrict__ shift, const float* __restrict__ coef, float* __restrict__ dzp, int cout,
+                                                    int ho, int wo, int wp, int G, int PP, int PS, int LP)
+{
+    const int tid = threadIdx.x, N = ho * wo, co = blockIdx.x;
+    const size_t pl = (size_t)blockIdx.y * cout + co;
+    const float* zi = z + pl * N;
+    const float* dp = dy + pl * N;
+    const float sc = scale[co], sh = shift[co];
+    const float c1 = coef[4 * co], c2 = coef[4 * co + 1], meanf = coef[4 * co + 2], rf = coef[4 * co + 3];
+    float* zo = dzp + pl * PS;
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    for (int j = lo + tid; j < hi; j += 256) {
+        const int P = j - G;
+        float v = 0.f;
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, c = P - y * wp;
+            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
+                const int i = (y - 1) * wo + c - 1;
+                const float zz = zi[i];
+                const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
+                const float zhat = (zz - meanf) * rf;
+                v = sc * ((g - c1) - zhat * c2);
+            }
+        }
+        zo[j] = v;
+    }
 }
 
 // ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
@@ -370,7 +428,7 @@ void pp_down_destroy(pp_ctx* ctx)
 {
     down_ws* w = (down_ws*)ctx->down;
     if (!w) return;
-    void* q[] = {w->planes, w->pst, w->wT, w->part};
+    void* q[] = {w->planes, w->pst, w->wT, w->part, w->coef};
     for (void* x : q)
         if (x) (void)hipFree(x);
     delete w;
@@ -533,6 +591,92 @@ extern "C" int pp_down_backward_affine(pp_ctx* ctx, int cin, int cout, int hin, 
     }
     hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
     if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(cout, 64)), dim3(64), 0, stream, ws->pst, nb, cout, SP, dscale, dshift);
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// pp_down_backward_affine behind a train-mode BatchNorm: (scale, shift) are the fold of the batch statistics (mean, var) the forward used.
+// Two phases: the sums over every frame and k_bn_coef first, then the frame chunks with k_bn_down_dz and the two products.  chunk_frames
+// > 0 caps the frames of a chunk below the workspace rule (dx and the sums do not depend on it; dw does within fp32 summation error).
+extern "C" int pp_down_backward_bn(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z,
+                                       const float* scale, const float* shift, const float* mean, const float* var, const float* dy, int nb, float* dw, float* dx,
+                                   double* dscale, double* dshift, int chunk_frames, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
+    if (!x || !wgt || !z || !scale || !shift || !mean || !var || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: null pointer");
+    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: dscale and dshift go together");
+    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: nb must be 1 .. max_batch");
+    if (chunk_frames < 0) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: chunk_frames must be >= 0");
+    const int64_t ho64 = ((int64_t)hin + 1) / 2, wo64 = ((int64_t)win + 1) / 2;
+    if (hin < 1 || win < 1 || ho64 * wo64 < 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: hin, win >= 1 and ho wo >= 2");
+    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: w must be 16-byte aligned");
+    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: tensors must be 4-byte aligned");
+    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: dscale / dshift must be 8-byte aligned");
+    const int64_t wp64 = wo64 + 2, PP64 = (ho64 + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
+    const uint64_t pf64 = (uint64_t)(4 * cin + cout) * (uint64_t)PS64; // one frame's planes, elements
+    if (pf64 * sizeof(float) > DOWN_WS_BUDGET)
+        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: map too large (one frame's planes exceed the 256 MB workspace)");
+    const int ho = (int)ho64, wo = (int)wo64, wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    down_ws* ws = workspace(ctx);
+    // frames per chunk and K ranges: as pp_down_backward, the chunk capped by chunk_frames
+    const size_t pf_elems = (size_t)pf64;
+    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    if (chunk_frames > 0 && chunk_frames < fc) fc = chunk_frames;
+    const int TN = cin >= 128 ? 128 : 192;
+    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
+    int Gp = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        int sp, cps;
+        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
+        Gp += sp;
+    }
+    const int nw = cout * NC;
+    const int No = ho * wo, S = plane_segs(No), L = seg_len(No, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * cout * SEG_MAX * 2)) || // every frame's segment sums: pooled once, ahead of the chunks
+        (rc = grow(ctx, &ws->coef, &ws->coef_elems, (size_t)cout * 4)) ||
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
+        (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
+        return rc;
+    float* xp = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
+    if (dx) hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, cin, cout);
+    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
+    hipLaunchKernelGGL(k_bn_down_sums, dim3(cout, nb, S), dim3(256), 0, stream, z, dy, scale, shift, ws->pst, cout, No, L, S);
+    hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(cout, 64)), dim3(64), 0, stream, ws->pst, nb, cout, S, mean, var, (double)nb * (double)No, ws->coef,
+                       dscale, dshift);
+    int gbase = 0;
+    for (int f0 = 0; f0 < nb; f0 += fc) {
+        const int fn = nb - f0 < fc ? nb - f0 : fc;
+        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
+        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
+        hipLaunchKernelGGL(k_bn_down_dz, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, scale, shift, ws->coef, dzp, cout, ho, wo, wp, G, PP,
+                           PS, LP);
+        int sp, cps;
+        dw_ranges(tiles, fn * cpf, &sp, &cps);
+        const dim3 gd(NC / TN, cout / 64, sp);
+        if (cin >= 128)
+            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        else
+            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
+        gbase += sp;
+        if (dx) {
+            if (cin == 64)
+                hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
+                                   G, PP, PS);
+            else
+                hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
+                                   G, PP, PS);
+        }
+    }
+    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
     PP_HIP(hipGetLastError());
     return 0;
 }

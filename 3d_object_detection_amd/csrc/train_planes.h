@@ -1,6 +1,7 @@
 // What the streaming passes of block_train.hip and down_train.hip share: how a plane is cut into segments, the fixed-order sums of a
 // workgroup, and the statistics kernel.  One copy, so that both files cut a plane the same way and a shape keeps its bits in both.
-// k_affine_reduce, the last step of the three pp_*_backward_affine entries, is here for neck_train.hip as well.
+// k_affine_reduce, the last step of the three pp_*_backward_affine entries, is here for neck_train.hip as well, and so is k_bn_coef,
+// which pools the sums of the three pp_*_backward_bn entries.
 #pragma once
 #include "pp_common.h"
 
@@ -66,6 +67,30 @@ __global__ void __launch_bounds__(64) k_affine_reduce(const double* __restrict__
         for (int s = 0; s < S; ++s) { a += p[2 * s]; b += p[2 * s + 1]; }
     }
     dscale[c] = a; dshift[c] = b;
+}
+
+// ---- train-mode BatchNorm backward (the three pp_*_backward_bn entries): a channel's two sums pooled as k_affine_reduce pools them,
+// a = sum g v and b = sum g over all frames, and from them and the batch statistics the coefficients of the norm backward over n = frames
+// x positions elements, formed in fp64 and rounded once each: coef[c] = {c1 = b / n, c2 = r (a - mean b) / n, mean, r}, r = 1 /
+// sqrt(var + 1e-3).  dscale / dshift (nullable) take the sums themselves ----------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_bn_coef(const double* __restrict__ pst, int nb, int C, int S, const float* __restrict__ mean,
+                                                const float* __restrict__ var, double n, float* __restrict__ coef, double* __restrict__ dscale,
+                                                double* __restrict__ dshift)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int f = 0; f < nb; ++f) {
+        const double* p = pst + ((size_t)f * C + c) * S * 2;
+        for (int s = 0; s < S; ++s) { a += p[2 * s]; b += p[2 * s + 1]; }
+    }
+    const float meanf = mean[c];
+    const double r = 1.0 / sqrt((double)var[c] + 1e-3);
+    coef[4 * c] = (float)(b / n);
+    coef[4 * c + 1] = (float)(r * (a - (double)meanf * b) / n);
+    coef[4 * c + 2] = meanf;
+    coef[4 * c + 3] = (float)r;
+    if (dscale) { dscale[c] = a; dshift[c] = b; }
 }
 
 } // namespace

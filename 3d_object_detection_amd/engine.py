@@ -675,6 +675,16 @@ class Engine:
         sums = (self._t((C,), torch.float64), self._t((C,), torch.float64)) if need_affine else (None, None)
         return scale, shift, sums
 
+    def _bn_args(self, who, bn, C):
+        """(mean, var, chunk_frames) of a *_backward_bn call -> the two device tensors f32[C] and the int."""
+        mean, var, chunk = bn
+        mean = _chk(mean, torch.float32, (C,), f"{who}: mean")
+        var = _chk(var, torch.float32, (C,), f"{who}: var")
+        self._on_device(who, ((mean, "mean"), (var, "var")))
+        if not isinstance(chunk, int) or chunk < 0:
+            raise ValueError(f"{who}: chunk_frames must be an int >= 0, got {chunk!r}")
+        return mean, var, chunk
+
     def bn_fold(self, gamma, beta, running_mean, running_var):
         """pp_bn_fold: the eval-mode fold of one BatchNorm2d(eps 1e-3) layer, four device tensors [C] -> (scale, shift) f32[C] =
         gamma / sqrt(running_var + 1e-3), beta - running_mean scale, in fp64 and rounded once: the bits the committed plan holds."""
@@ -717,86 +727,155 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_bn_fold(self.ctx, ptrs, _stream()), self.ctx, "pp_update_bn_fold")
 
-    def unit_backward_affine(self, u, w, scale, shift, dy, dskip=None, need_du=True, need_affine=True):
+    def unit_backward_affine(self, u, w, scale, shift, dy, dskip=None, need_du=True, need_affine=True, _bn=None):
         """pp_unit_backward_affine: unit_backward for the unit scale/shift -> ReLU -> Conv3x3 (frozen BatchNorm): scale, shift f32[C] are
         the folded values the forward used -> (dw, du or None, dscale, dshift); dscale = sum g u and dshift = sum g are f64[C], None
         when need_affine is False.  need_du=False needs need_affine=False.  fp32, deterministic, stateless."""
+        who = "unit_backward_bn" if _bn else "unit_backward_affine"
         if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
-            raise ValueError(f"unit_backward_affine: u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
+            raise ValueError(who + f": u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, C, h, wd = (int(v) for v in u.shape)
         if C not in (64, 128, 256):
-            raise ValueError(f"unit_backward_affine: C must be 64, 128 or 256, got {C}")
+            raise ValueError(who + f": C must be 64, 128 or 256, got {C}")
         if h < 1 or wd < 1 or h * wd < 2:
-            raise ValueError(f"unit_backward_affine: the map needs at least two elements, got {h} x {wd}")
+            raise ValueError(who + f": the map needs at least two elements, got {h} x {wd}")
         if need_affine and not need_du:
-            raise ValueError("unit_backward_affine: the affine sums are sums over du's product: need_affine needs need_du")
-        u = _chk(u, torch.float32, (nb, C, h, wd), "unit_backward_affine: u")
-        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), "unit_backward_affine: w")
-        dy = _chk(dy, torch.float32, (nb, C, h, wd), "unit_backward_affine: dy")
+            raise ValueError(who + ": the affine sums are sums over du's product: need_affine needs need_du")
+        u = _chk(u, torch.float32, (nb, C, h, wd), who + ": u")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), who + ": w")
+        dy = _chk(dy, torch.float32, (nb, C, h, wd), who + ": dy")
         if dskip is not None:
-            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), "unit_backward_affine: dskip")
-        self._on_device("unit_backward_affine", ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
-        scale, shift, (ds, dh) = self._affine_args("unit_backward_affine", scale, shift, C, need_affine)
+            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), who + ": dskip")
+        self._on_device(who, ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
+        scale, shift, (ds, dh) = self._affine_args(who, scale, shift, C, need_affine)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((C, C, 3, 3), torch.float32)
         du = self._t((nb, C, h, wd), torch.float32) if need_du else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_unit_backward_affine(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(scale), _ptr(shift), _ptr(dy), _ptr(dskip), nb,
-                                                        _ptr(dw), _ptr(du), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_unit_backward_affine")
+            if _bn:
+                mean, var, chunk = self._bn_args(who, _bn, C)
+                _lib.check(self.lib.pp_unit_backward_bn(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(var), _ptr(dy),
+                                                        _ptr(dskip), nb, _ptr(dw), _ptr(du), _ptr(ds), _ptr(dh), chunk, _stream()), self.ctx,
+                           "pp_unit_backward_bn")
+            else:
+                _lib.check(self.lib.pp_unit_backward_affine(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(scale), _ptr(shift), _ptr(dy), _ptr(dskip), nb,
+                                                            _ptr(dw), _ptr(du), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_unit_backward_affine")
         return dw, du, ds, dh
 
-    def down_backward_affine(self, x, w, z, scale, shift, dy, need_dx=True, need_affine=True):
+    def down_backward_affine(self, x, w, z, scale, shift, dy, need_dx=True, need_affine=True, _bn=None):
         """pp_down_backward_affine: down_backward for the stage Conv3x3 stride 2 -> scale/shift -> ReLU (frozen BatchNorm) ->
         (dw, dx or None, dscale = sum g z, dshift = sum g: f64[Cout], None when need_affine is False).  fp32, deterministic, stateless."""
+        who = "down_backward_bn" if _bn else "down_backward_affine"
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
-            raise ValueError(f"down_backward_affine: x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
+            raise ValueError(who + f": x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, cin, hin, win = (int(v) for v in x.shape)
         cout = int(w.shape[0]) if isinstance(w, torch.Tensor) and w.dim() == 4 else 0
         if (cin, cout) not in self.DOWN_PAIRS:
-            raise ValueError(f"down_backward_affine: (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
+            raise ValueError(who + f": (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
         ho, wo = (hin + 1) // 2, (win + 1) // 2
         if hin < 1 or win < 1 or ho * wo < 2:
-            raise ValueError(f"down_backward_affine: the output map needs at least two elements, got {ho} x {wo}")
-        x = _chk(x, torch.float32, (nb, cin, hin, win), "down_backward_affine: x")
-        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), "down_backward_affine: w")
-        z = _chk(z, torch.float32, (nb, cout, ho, wo), "down_backward_affine: z")
-        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), "down_backward_affine: dy")
-        self._on_device("down_backward_affine", ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
-        scale, shift, (ds, dh) = self._affine_args("down_backward_affine", scale, shift, cout, need_affine)
+            raise ValueError(who + f": the output map needs at least two elements, got {ho} x {wo}")
+        x = _chk(x, torch.float32, (nb, cin, hin, win), who + ": x")
+        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), who + ": w")
+        z = _chk(z, torch.float32, (nb, cout, ho, wo), who + ": z")
+        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), who + ": dy")
+        self._on_device(who, ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
+        scale, shift, (ds, dh) = self._affine_args(who, scale, shift, cout, need_affine)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((cout, cin, 3, 3), torch.float32)
         dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_down_backward_affine(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(scale), _ptr(shift), _ptr(dy),
-                                                        nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_down_backward_affine")
+            if _bn:
+                mean, var, chunk = self._bn_args(who, _bn, cout)
+                _lib.check(self.lib.pp_down_backward_bn(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(scale), _ptr(shift), _ptr(mean),
+                                                        _ptr(var), _ptr(dy), nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), chunk, _stream()), self.ctx,
+                           "pp_down_backward_bn")
+            else:
+                _lib.check(self.lib.pp_down_backward_affine(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(scale), _ptr(shift), _ptr(dy),
+                                                            nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_down_backward_affine")
         return dw, dx, ds, dh
 
-    def neck_backward_affine(self, branch, x, w, scale, shift, y, dy, need_dx=True, need_affine=True):
+    def neck_backward_affine(self, branch, x, w, scale, shift, y, dy, need_dx=True, need_affine=True, _bn=None):
         """pp_neck_backward_affine: neck_backward for the branch ConvTranspose -> scale/shift -> ReLU (frozen BatchNorm); scale, shift
         f32[Cup] are the branch's -> (dw, dx or None, dscale = sum g Z, dshift = sum g: f64[Cup], None when need_affine is False).
         fp32, deterministic, stateless."""
+        who = "neck_backward_bn" if _bn else "neck_backward_affine"
         if branch not in (0, 1, 2):
-            raise ValueError(f"neck_backward_affine: branch must be 0, 1 or 2, got {branch!r}")
+            raise ValueError(who + f": branch must be 0, 1 or 2, got {branch!r}")
         xs, wsh = self.neck_shapes(branch)
         nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
         if not 1 <= nb <= self.max_batch:
-            raise ValueError(f"neck_backward_affine: x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
-        x = _chk(x, torch.float32, (nb,) + xs, "neck_backward_affine: x")
-        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, "neck_backward_affine: w")
-        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), "neck_backward_affine: y")
-        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), "neck_backward_affine: dy")
-        self._on_device("neck_backward_affine", ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
-        scale, shift, (ds, dh) = self._affine_args("neck_backward_affine", scale, shift, wsh[1], need_affine)
+            raise ValueError(who + f": x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
+        x = _chk(x, torch.float32, (nb,) + xs, who + ": x")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, who + ": w")
+        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), who + ": y")
+        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), who + ": dy")
+        self._on_device(who, ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
+        scale, shift, (ds, dh) = self._affine_args(who, scale, shift, wsh[1], need_affine)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
         dw = self._t(wsh, torch.float32)
         dx = self._t((nb,) + xs, torch.float32) if need_dx else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_neck_backward_affine(self.ctx, branch, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), _ptr(dy), nb, _ptr(dw),
-                                                        _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_neck_backward_affine")
+            if _bn:
+                mean, var, chunk = self._bn_args(who, _bn, wsh[1])
+                _lib.check(self.lib.pp_neck_backward_bn(self.ctx, branch, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(var), _ptr(y),
+                                                        _ptr(dy), nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), chunk, _stream()), self.ctx,
+                           "pp_neck_backward_bn")
+            else:
+                _lib.check(self.lib.pp_neck_backward_affine(self.ctx, branch, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), _ptr(dy), nb, _ptr(dw),
+                                                            _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_neck_backward_affine")
         return dw, dx, ds, dh
+
+    # ------------------------------------------------------------------ the BatchNorm backbone with batch statistics
+    def unit_backward_bn(self, u, w, scale, shift, mean, var, dy, dskip=None, need_du=True, need_affine=True, chunk_frames=0):
+        """pp_unit_backward_bn: unit_backward_affine behind a train-mode BatchNorm2d.  mean, var f32[C] are the batch statistics (biased
+        variance) and scale, shift their fold with the layer's weight and bias, as backbone_train_taps_bn hands them out -> (dw, du or
+        None, dscale = sum g u, dshift = sum g: f64[C] pooled over all frames, None when need_affine is False); bn_affine_grad(dscale,
+        dshift, mean, var) gives dgamma, dbeta.  chunk_frames > 0 caps the frames of a workspace chunk.  fp32, deterministic, stateless."""
+        return self.unit_backward_affine(u, w, scale, shift, dy, dskip=dskip, need_du=need_du, need_affine=need_affine, _bn=(mean, var, chunk_frames))
+
+    def down_backward_bn(self, x, w, z, scale, shift, mean, var, dy, need_dx=True, need_affine=True, chunk_frames=0):
+        """pp_down_backward_bn: down_backward_affine in front of a train-mode BatchNorm2d (arguments as unit_backward_bn) -> (dw, dx or
+        None, dscale = sum g z, dshift = sum g)."""
+        return self.down_backward_affine(x, w, z, scale, shift, dy, need_dx=need_dx, need_affine=need_affine, _bn=(mean, var, chunk_frames))
+
+    def neck_backward_bn(self, branch, x, w, scale, shift, mean, var, y, dy, need_dx=True, need_affine=True, chunk_frames=0):
+        """pp_neck_backward_bn: neck_backward_affine in front of a train-mode BatchNorm2d (arguments as unit_backward_bn) -> (dw, dx or
+        None, dscale = sum g Z, dshift = sum g)."""
+        return self.neck_backward_affine(branch, x, w, scale, shift, y, dy, need_dx=need_dx, need_affine=need_affine, _bn=(mean, var, chunk_frames))
+
+    def backbone_train_taps_bn(self, canvas, bn_params, taps=True):
+        """pp_backbone_train_taps_bn: the lock-step training forward of the BatchNorm backbone on canvases [nb,64,gx,gy], 1 <= nb <=
+        max_batch, every BatchNorm2d normalising with the statistics of the batch.  bn_params: {state_dict name: device tensor} with the
+        weight and bias of the nineteen layers of bn_layers() -> (rpn_out [nb,320,H,W], (x1, x2, x3), units, z, mean, var, scale, shift):
+        units[b] [n_b,nb,C_b,h,w] (n_b = 3, 5, 5) and z[b] [nb,C_b,h,w] per level, or None for the levels below `taps` (True: all
+        levels, False: none, an int b: levels b .. 2); mean, var (biased), scale, shift f32[19,256] in bn_layers() order, a row filled
+        up to its layer's channels.  The committed fold of the running statistics is left alone.  BatchNorm engines in fp32 mode only."""
+        who = "backbone_train_taps_bn"
+        gx, gy = int(self.grid_size[0]), int(self.grid_size[1])
+        if not (isinstance(canvas, torch.Tensor) and canvas.dim() == 4 and 1 <= int(canvas.shape[0]) <= self.max_batch):
+            raise ValueError(f"{who}: canvas must be [nb,64,{gx},{gy}] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb = int(canvas.shape[0])
+        canvas = _chk(canvas, torch.float32, (nb, 64, gx, gy), f"{who}: canvas")
+        self._on_device(who, [(canvas, "canvas")])
+        keys, shapes = zip(*[(f"{p}.{s}", (c,)) for p, c in self.bn_layers() for s in self.BN_FIELDS[:2]])
+        gb = self._chk_weights(who, bn_params, keys, shapes)
+        lo = 0 if taps is True else 3 if taps is False else int(taps)
+        out = self._t((nb, 320, self.H, self.W), torch.float32)
+        xs = [self._level_t(nb, b) for b in range(3)]
+        units = [self._t((n, nb) + self.neck_shapes(b)[0], torch.float32) if b >= lo else None for b, n in enumerate(self.RPN_UNITS)]
+        z = [self._level_t(nb, b) if b >= lo else None for b in range(3)]
+        stats = [torch.zeros((19, 256), dtype=torch.float32, device=self.device) for _ in range(4)]
+        gbp = (ctypes.c_void_p * 38)(*[t.data_ptr() for t in gb])
+        up = (ctypes.c_void_p * 3)(*[_ptr(t) for t in units])
+        zp = (ctypes.c_void_p * 3)(*[_ptr(t) for t in z])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_backbone_train_taps_bn(self.ctx, _ptr(canvas), nb, gbp, _ptr(out), _ptr(xs[0]), _ptr(xs[1]), _ptr(xs[2]), up, zp,
+                                                          *[_ptr(t) for t in stats], _stream()), self.ctx, "pp_backbone_train_taps_bn")
+        return (out, tuple(xs), tuple(units), tuple(z)) + tuple(stats)
 
     # ------------------------------------------------------------------ PFN training (pfn_train.hip)
     PFN_KEYS = ("pillar_point_net.pfn_layers.0.weight", "pillar_point_net.pfn_layers.1.weight", "pillar_point_net.pfn_layers.1.bias")

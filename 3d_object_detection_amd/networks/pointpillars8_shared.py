@@ -33,7 +33,10 @@ The BatchNorm networks (pointpillars8_export / _trt, _norm = "batch") fine-tune 
 bn_stats="frozen"): every BatchNorm2d of the RPN stays the per-channel affine of its running statistics, its weight / bias sit in the
 group of the convolution whose backward primitive yields their gradient (with_bn: 63 tensors under "rpn", 66 under "all"), the
 training forward is the same tapped inference pass, _RpnBnFunction walks the same table with pp_*_backward_affine, and after a step
-_sync_neck also folds the nineteen layers again in place (pp_update_bn_fold).
+_sync_neck also folds the nineteen layers again in place (pp_update_bn_fold).  train(scope=..., bn_stats="moving") trains them as the
+reference's net.train() does: every BatchNorm2d normalises with the statistics of the batch and moves its running statistics.  The
+training forward is then one lock-step pass over all frames (pp_backbone_train_taps_bn) and _RpnBnBatchFunction walks the table with
+pp_*_backward_bn; the moved running statistics are folded again before the next eval-mode pass.
 
 Mixed precision: train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
 or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
@@ -68,7 +71,8 @@ _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in
 ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
 SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
 GRAD_PRECISIONS = ("fp32", "bf16x3", "bf16")  # train(grad_precision=...): the operands of the unit backwards' gradient products
-BN_STATS = ("frozen", "batch")  # train(bn_stats=...) on a BatchNorm network; "batch" is reserved for batch-statistics training
+BN_STATS = ("frozen", "moving", "batch")  # train(bn_stats=...) on a BatchNorm network; "batch" is refused: "moving" is its name here
+BN2D_MOMENTUM = 0.01  # the reference's BatchNorm2d(eps=1e-3, momentum=0.01) of the RPN
 
 
 def bn_affine_keys(conv_key):
@@ -252,7 +256,7 @@ class _RpnBnFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, first, stats, x, *tensors):
-        ctx.eng, ctx.first, ctx.stats = eng, first, stats
+        ctx.eng, ctx.first, ctx.stats, ctx.batch = eng, first, stats, False
         n = len(tensors) // 3
         folds = [eng.bn_fold(tensors[3 * i + 1], tensors[3 * i + 2], *stats[i]) for i in range(n)]
         outs = [_frame_taps(eng, first, c) for c in x]
@@ -265,7 +269,12 @@ class _RpnBnFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
+        """Shared with _RpnBnBatchFunction (ctx.batch): there the primitives are the _bn siblings, which also take a layer's batch mean
+        and variance (ctx.stats), and pp_bn_affine_grad reads those in place of the running statistics."""
         eng, first, saved = ctx.eng, ctx.first, list(ctx.saved_tensors)
+        kind = "_bn" if ctx.batch else "_affine"
+        neck_backward, unit_backward, down_backward = (getattr(eng, p + kind) for p in ("neck_backward", "unit_backward", "down_backward"))
+        st = (lambda i: ctx.stats[i]) if ctx.batch else (lambda i: ())  # noqa: E731
         x = saved.pop(0) if first == 0 else None
         y, taps, saved = saved[0], saved[1:4], saved[4:]
         nconv = len(RPN_CONV_KEYS)
@@ -295,7 +304,7 @@ class _RpnBnFunction(torch.autograd.Function):
         for b in range(3):
             i = nconv - first + b
             if need_w[i] or need_a[i] or front[b + 1]:
-                dw, dxn[b], ds, dh = eng.neck_backward_affine(b, taps[b], ws[i], *folds[i], y, gy, need_dx=front[b + 1], need_affine=need_a[i])
+                dw, dxn[b], ds, dh = neck_backward(b, taps[b], ws[i], *folds[i], *st(i), y, gy, need_dx=front[b + 1], need_affine=need_a[i])
                 put(i, dw, ds, dh)
         g = None
         for b, mods, w0, nu in reversed(levels):
@@ -309,20 +318,48 @@ class _RpnBnFunction(torch.autograd.Function):
                 skip = g
                 if m == 2:
                     i = w0 + 2 + u - first
-                    dw, g, ds, dh = eng.unit_backward_affine(units[b][u + 1], ws[i], *folds[i], g, need_affine=need_a[i])
+                    dw, g, ds, dh = unit_backward(units[b][u + 1], ws[i], *folds[i], *st(i), g, need_affine=need_a[i])
                     put(i, dw, ds, dh)
                 i = w0 + 1 + u - first
                 if u or need_dh or need_a[i]:
-                    dw, g, ds, dh = eng.unit_backward_affine(units[b][u], ws[i], *folds[i], g, dskip=skip, need_affine=need_a[i])
+                    dw, g, ds, dh = unit_backward(units[b][u], ws[i], *folds[i], *st(i), g, dskip=skip, need_affine=need_a[i])
                 else:
-                    dw, g, ds, dh = eng.unit_backward_affine(units[b][u], ws[i], *folds[i], g, need_du=False, need_affine=False)
+                    dw, g, ds, dh = unit_backward(units[b][u], ws[i], *folds[i], *st(i), g, need_du=False, need_affine=False)
                 put(i, dw, ds, dh)
             if need_dh:
                 i = w0 - first
-                dw, g, ds, dh = eng.down_backward_affine(x if b == 0 else taps[b - 1], ws[i], zs[b], *folds[i], g, need_dx=front[b],
-                                                         need_affine=need_a[i])
+                dw, g, ds, dh = down_backward(x if b == 0 else taps[b - 1], ws[i], zs[b], *folds[i], *st(i), g, need_dx=front[b],
+                                              need_affine=need_a[i])
                 put(i, dw, ds, dh)
         return (None, None, None, g if need_x else None) + tuple(grads)
+
+
+class _RpnBnBatchFunction(torch.autograd.Function):
+    """_RpnBnFunction with batch statistics (train-mode BatchNorm2d): the forward is one lock-step pass over all frames,
+    pp_backbone_train_taps_bn, which hands out every layer's batch mean, biased variance and their fold with the layer's weight and
+    bias; the backward is _RpnBnFunction's walk with the pp_*_backward_bn primitives.  bn_params holds weight and bias of all nineteen
+    layers (the layers in front of `first` normalise with batch statistics too); tensors as in _RpnBnFunction.  Returns the rpn output
+    and the statistics mean, var f32[19,256] in Engine.bn_layers() order (not differentiable: the caller moves the running ones)."""
+
+    @staticmethod
+    def forward(ctx, eng, first, bn_params, x, *tensors):
+        nconv = len(RPN_CONV_KEYS)
+        taps = True if first == 0 else False if first == nconv else 2
+        y, xs, units, zs, mean, var, scale, shift = eng.backbone_train_taps_bn(x, bn_params, taps=taps)
+        order = [k for b in range(3) for k in RPN_CONV_KEYS[_W0[b]:_W0[b] + 1 + sum(RPN_TABLE[b][1])] + (NECK_KEYS[b],)]  # bn_layers() order
+        layers = RPN_CONV_KEYS[first:] + NECK_KEYS
+        rows = [(order.index(k), int(tensors[3 * i + 1].shape[0])) for i, k in enumerate(layers)]
+        ctx.eng, ctx.first, ctx.batch = eng, first, True
+        ctx.stats = [(mean[r, :c], var[r, :c]) for r, c in rows]
+        levels = [b for b, mods in RPN_TABLE if first <= _W0[b] + 1]
+        ctx.save_for_backward(*([x] if first == 0 else []), y, *xs, *[u for b in levels for u in units[b]],
+                              *[zs[b] for b in levels if first <= _W0[b]], *tensors[::3], *[t[r, :c] for r, c in rows for t in (scale, shift)])
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, gy, _gmean, _gvar):
+        return _RpnBnFunction.backward(ctx, gy)
 
 
 class _PfnFunction(torch.autograd.Function):
@@ -361,8 +398,10 @@ class PointPillars:
     bn_stats = None  # train(bn_stats=...) while training a BatchNorm network
     # read-only defaults for an object assembled without __init__ (no engine: the key-order and plan tests); __init__ and
     # load_state_dict give every object its own
-    _block = _down = _rpn = _pfn = _pfn_stats = _bn_run = types.MappingProxyType({})
+    _block = _down = _rpn = _pfn = _pfn_stats = _bn_run = _bn_nbt = types.MappingProxyType({})
     _pfn_nbt = None
+    _bn_run_up = ()          # the _version numbers of _bn_run at the last fold into the engine
+    _bn_run_trained = False  # the running statistics of the RPN moved since load_state_dict
     _uploaded = types.MappingProxyType({})  # per group of _GROUPS: its tensors' _version numbers at the last upload into the engine
     _trained = frozenset()                  # the groups that have been stepped since load_state_dict
 
@@ -378,7 +417,8 @@ class PointPillars:
         # unit weights, its stride-2 weight, the ten convolutions of blocks 1 and 2, the PFN's Conv1d weight and BatchNorm1d weight / bias
         self._params, self._neck, self._block, self._down, self._rpn, self._pfn = {}, {}, {}, {}, {}, {}
         self._pfn_stats = {}         # running_mean / running_var as device tensors (train(scope="all") moves them)
-        self._bn_run = {}            # BatchNorm backbone: running_mean / running_var of the RPN's nineteen norms as device tensors (frozen)
+        self._bn_run = {}            # BatchNorm backbone: running_mean / running_var of the RPN's nineteen norms as device tensors
+        self._bn_nbt = {}            # their num_batches_tracked, where the loaded dict carried it (bn_stats="moving" counts)
         self._pfn_nbt = None         # num_batches_tracked when the loaded dict carried it
         self.profile_stages = True  # the reference synchronises after every stage (:365-374)
         self.pfn_time, self.rpn_time, self.scatter_time, self.heads_time = 0.0, 0.0, 0.0, 0.0
@@ -412,22 +452,26 @@ class PointPillars:
         BatchNorm2d module.  The keyword is explicit because that is not what torch's net.train() alone means; "batch" (batch
         statistics) is reserved and raises NotImplementedError.  Gradients are fp32 (grad_precision="fp32").  bn_stats governs the RPN's
         BatchNorm2d layers only: under "all" the PFN's BatchNorm1d normalises with batch statistics and its running statistics move,
-        exactly as on the InstanceNorm network.  None keeps a BatchNorm network to scope="head"."""
+        exactly as on the InstanceNorm network.  None keeps a BatchNorm network to scope="head".
+        bn_stats="moving" is the reference's net.train() on a BatchNorm network: under every scope all nineteen BatchNorm2d of the RPN
+        normalise with the statistics of the batch (all frames of a forward together) and move their running statistics (momentum
+        0.01, unbiased variance) and num_batches_tracked, whether or not grad is enabled; the scope decides which tensors get
+        gradients, exactly as under "frozen".  eval() folds the moved statistics into the engine before the next pass."""
         if grad_precision not in GRAD_PRECISIONS:
             raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         if scope not in SCOPES:
             raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
         if bn_stats is not None:
             if bn_stats not in BN_STATS:
-                raise ValueError(f"train: bn_stats must be None, 'frozen' or 'batch', got {bn_stats!r}")
+                raise ValueError(f"train: bn_stats must be None, 'frozen' or 'moving', got {bn_stats!r}")
             if self._norm != "batch":
                 raise ValueError("train: bn_stats is for the BatchNorm networks; the InstanceNorm backbone has no statistics to freeze")
             if bn_stats == "batch":
-                raise NotImplementedError("train(bn_stats='batch'): the batch-statistics BatchNorm backward does not exist yet; "
-                                          "bn_stats='frozen' fine-tunes with the running statistics")
+                raise NotImplementedError("train(bn_stats='batch'): training with batch statistics is bn_stats='moving' (the running "
+                                          "statistics move, as under torch's net.train()); bn_stats='frozen' fine-tunes with them fixed")
             if grad_precision != "fp32":
-                raise ValueError("train: the frozen-statistics backward is fp32 (grad_precision='fp32')")
-        if mode and scope != "head" and ((self._norm != "instance" and bn_stats != "frozen") or (scope == "all" and len(self._pfn_stats) != 2) or
+                raise ValueError("train: the BatchNorm backward is fp32 (grad_precision='fp32')")
+        if mode and scope != "head" and ((self._norm != "instance" and bn_stats not in ("frozen", "moving")) or (scope == "all" and len(self._pfn_stats) != 2) or
                                          any(len(getattr(self, g.attr)) != len(self._group_keys(g)) for g in self._groups(scope) if g.scope != "head")):
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only" +
                                ("; on a BatchNorm network pass bn_stats='frozen' to fine-tune with frozen statistics" if self._norm == "batch" else ""))
@@ -514,11 +558,15 @@ class PointPillars:
     def _sync_neck(self):
         """The same for the three upsampler weights, block 3's five and its stride-2 weight, ahead of whatever runs the backbone; when
         a convolution of blocks 1 and 2 moved, all sixteen go up in one pp_update_rpn_weights.  On the BatchNorm backbone the groups
-        hold the norms' weight / bias too: when one moved, all nineteen layers are folded again in place (pp_update_bn_fold)."""
-        fold = self._norm == "batch" and any(self._moved(attr) for attr in _BACKBONE)
+        hold the norms' weight / bias too: when one moved, or the running statistics did (bn_stats="moving"), all nineteen layers are
+        folded again in place (pp_update_bn_fold)."""
+        run = tuple(t._version for t in self._bn_run.values())
+        fold = self._norm == "batch" and (any(self._moved(attr) for attr in _BACKBONE) or run != self._bn_run_up)
         for attr in _BACKBONE:
             self._sync_group(attr)
         if fold:
+            self._bn_run_trained = self._bn_run_trained or run != self._bn_run_up
+            self._bn_run_up = run
             self._eng.update_bn_fold({**self._bn_run, **{k: p for attr in _BACKBONE for k, p in getattr(self, attr).items()}})
 
     def half(self):
@@ -537,13 +585,16 @@ class PointPillars:
         # a change of mode packs the loaded weights again: what was stepped goes up before it is next used (heads(), a backbone pass)
         stale = self._stepped()
         self._uploaded = {**self._uploaded, **{a: () for a in stale}}
+        if self._bn_run_trained:
+            self._bn_run_up = None  # the new plan folds the loaded statistics: the moved ones go up before the next pass
         if "_pfn" in stale and not self._pfn_training():
             self._sync_pfn()
         return self
 
     def state_dict(self):
         """The loaded tensors; those of every group that was stepped (the head's six, the three upsampler weights, the sixteen 3 x 3
-        convolutions of the RPN, the pillar feature net with its running statistics) with their CURRENT values."""
+        convolutions of the RPN, the pillar feature net with its running statistics) with their CURRENT values, and so the running
+        statistics and num_batches_tracked of the RPN's BatchNorm2d layers once train(bn_stats="moving") has moved them."""
         sd = dict(self._sd)
         for attr in self._stepped():
             for d in (attr, _GROUPS[attr].stats):
@@ -551,6 +602,11 @@ class PointPillars:
                     sd[k] = t.detach().cpu().numpy().reshape(self._sd[k].shape)
             if attr == "_pfn" and self._pfn_nbt is not None:
                 sd[PFN_NBT_KEY] = np.asarray(self._pfn_nbt, dtype=np.int64)
+        if self._bn_run_trained or tuple(t._version for t in self._bn_run.values()) != self._bn_run_up:
+            for k, t in self._bn_run.items():
+                sd[k] = t.detach().cpu().numpy().reshape(self._sd[k].shape)
+            for k, v in self._bn_nbt.items():
+                sd[k] = np.asarray(v, dtype=np.int64)
         return sd
 
     def load_state_dict(self, sd, strict=True):
@@ -564,6 +620,9 @@ class PointPillars:
         bn_run = [f"{p}.{s}" for p, _ in Engine.bn_layers() for s in Engine.BN_FIELDS[2:]] if self._norm == "batch" else ()
         self._bn_run = {k: dev_of(k) for k in bn_run if k in self._sd}
         self._pfn_nbt = int(np.asarray(self._sd[PFN_NBT_KEY])) if PFN_NBT_KEY in self._sd else None
+        nbt = [f"{p}.num_batches_tracked" for p, _ in Engine.bn_layers()] if self._norm == "batch" else ()
+        self._bn_nbt = {k: int(np.asarray(self._sd[k])) for k in nbt if k in self._sd}
+        self._bn_run_up, self._bn_run_trained = tuple(t._version for t in self._bn_run.values()), False
         self._uploaded, self._trained = {}, frozenset()
         self._mark_uploaded()
         return self
@@ -682,7 +741,9 @@ class PointPillars:
         return any(p.requires_grad for attr in _BACKBONE for p in getattr(self, attr).values())
 
     def _neck_grad(self):
-        return self.training and self._scope != "head" and torch.is_grad_enabled() and self._backbone_requires_grad()
+        """The training forward goes through rpn_train(): a backbone tensor gets a gradient, or bn_stats="moving" runs the lock-step pass."""
+        return self.training and (self.bn_stats == "moving" or
+                                  (self._scope != "head" and torch.is_grad_enabled() and self._backbone_requires_grad()))
 
     def rpn_train(self, x):
         """RPN.forward on canvases x [B,64,gx,gy], 1 <= B <= max_batch, one backbone pass per frame; same values as rpn() bit for
@@ -698,7 +759,8 @@ class PointPillars:
         if not 1 <= x.shape[0] <= eng.max_batch:
             raise ValueError(f"rpn_train: {x.shape[0]} frames in the batch, max_batch is {eng.max_batch}")
         self._sync_neck()
-        if not (torch.is_grad_enabled() and self._backbone_requires_grad()):
+        moving = self.training and self.bn_stats == "moving"
+        if not (torch.is_grad_enabled() and self._backbone_requires_grad()) and not moving:
             return torch.cat([eng.backbone(c) for c in x])
         if eng.effective_precision() != "fp32":
             raise RuntimeError(f"neck training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
@@ -709,12 +771,38 @@ class PointPillars:
         every = {**self._rpn, **self._down, **self._block}
         if first:
             x = x.detach()  # nothing in front of the stage has a backward: the graph must not reach the canvases
-        if self._norm == "batch":  # frozen statistics: every layer goes in with its norm's weight and bias
+        if self._norm == "batch":  # every layer goes in with its norm's weight and bias
             every.update(self._neck)
             layers = RPN_CONV_KEYS[first:] + NECK_KEYS
+            if moving:
+                return self._rpn_train_moving(first, x, [every[n] for k in layers for n in (k, *bn_affine_keys(k))])
             stats = [tuple(self._bn_run[f"{Engine.bn_prefix(k)}.{s}"] for s in Engine.BN_FIELDS[2:]) for k in layers]
             return _RpnBnFunction.apply(eng, first, stats, x, *[every[n] for k in layers for n in (k, *bn_affine_keys(k))])
         return _RpnFunction.apply(eng, self.grad_precision, first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
+
+    def _rpn_train_moving(self, first, x, tensors):
+        """rpn_train under bn_stats="moving": one lock-step pass with batch statistics, then BatchNorm2d's update of the running
+        statistics, evaluated in fp64 and rounded once, in place (so that _sync_neck folds them again before the next eval-mode pass)."""
+        eng = self._eng
+        nb = int(x.shape[0])
+        counts = [nb * (eng.H >> b) * (eng.W >> b) for b in range(3)]
+        if min(counts) <= 1:
+            raise ValueError("rpn_train: expected more than 1 value per channel when training (BatchNorm2d with batch statistics)")
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self._backbone_requires_grad()):
+            y, mean, var = _RpnBnBatchFunction.apply(eng, first, {k: p for attr in _BACKBONE for k, p in getattr(self, attr).items()}, x, *tensors)
+        with torch.no_grad():
+            i = 0
+            for b, mods in RPN_TABLE:
+                for k in RPN_CONV_KEYS[_W0[b]:_W0[b] + 1 + sum(mods)] + (NECK_KEYS[b],):
+                    p = Engine.bn_prefix(k)
+                    n = float(nb * eng.H * eng.W if k in NECK_KEYS else counts[b])
+                    rm, rv = self._bn_run[p + ".running_mean"], self._bn_run[p + ".running_var"]
+                    c = rm.shape[0]
+                    rm.copy_(((1.0 - BN2D_MOMENTUM) * rm.double() + BN2D_MOMENTUM * mean[i, :c].double()).float())
+                    rv.copy_(((1.0 - BN2D_MOMENTUM) * rv.double() + BN2D_MOMENTUM * (n / (n - 1.0)) * var[i, :c].double()).float())
+                    i += 1
+        self._bn_nbt = {k: v + 1 for k, v in self._bn_nbt.items()}
+        return y
 
     def heads(self, x):
         """SharedHead.forward on x [B,320,H,W], 1 <= B <= max_batch.  Differentiable with respect to x and the head parameters when

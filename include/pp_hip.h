@@ -486,6 +486,49 @@ int pp_bn_affine_grad(pp_ctx* ctx, int C, const double* dscale, const double* ds
  * context and for a null or misaligned pointer. */
 int pp_update_bn_fold(pp_ctx* ctx, const float* const* bn /* 76 */, void* stream);
 
+/* ---- training the BatchNorm backbone with batch statistics (conv_run.hip, block_train.hip, down_train.hip, neck_train.hip) ----
+ * In train mode a BatchNorm2d(eps 1e-3) normalises with the statistics of the batch: per channel, over N = nb h w elements of all frames,
+ * mean = s / N and the biased var = max(q / N - mean^2, 0), each rounded once to fp32; the layer is then the affine that pp_bn_fold gives for
+ * (gamma, beta, mean, var).
+ *
+ * pp_backbone_train_taps_bn: the lock-step training forward, BatchNorm contexts in fp32 mode only.  Canvases f32[nb][64][gx][gy], 1 <= nb <=
+ * max_batch, run the dense backbone (no sparse first convolution, no tile skipping) layer by layer over all frames; behind each of the
+ * nineteen norm sites the per-frame fp64 accumulators of the producer's epilogue are pooled in frame order and folded, and the consumers
+ * read that fold.  The arrays belong to the pass: the committed fold of the running statistics (pp_commit_weights, pp_update_bn_fold) is
+ * not touched, and inference between two such passes sees the running statistics.  gamma_beta: 38 DEVICE pointers, [2 i] = weight and
+ * [2 i + 1] = bias of layer i in pp_update_bn_fold's layer order.  Outputs, all caller memory: rpn_out f32[nb][320][H][W] (normalised,
+ * ReLU); x1, x2, x3 f32[nb][C_b][H >> b][W >> b]; units[b] f32[n_b][nb][C_b][H >> b][W >> b] (n_b = 3, 5, 5: the frames of a unit
+ * input together, at nb = 1 the layout of pp_backbone_train_taps) and z[b] f32[nb][C_b][H >> b][W >> b], where either array or any entry may be NULL (a tap nobody needs); mean,
+ * var, scale, shift f32[19][256], row i filled up to layer i's channels.  PP_E_STATE before the first commit, PP_E_ARG on an InstanceNorm
+ * context, in a 16-bit mode, for nb outside 1..max_batch and for a null pointer.
+ *
+ * pp_unit_backward_bn, pp_down_backward_bn, pp_neck_backward_bn: the siblings of the _affine entries for that norm, with the same
+ * arguments plus DEVICE mean, var f32[C] (the batch statistics whose fold scale / shift are) and chunk_frames.  With r = 1 / sqrt(var +
+ * 1e-3), g and v as above and the sums pooled over all frames in fp64 (segments in index order, frames in frame order),
+ *   c1 = dshift / N, c2 = r (dscale - mean dshift) / N   (fp64, rounded once each),   vhat = (v - mean) r,
+ *   dv = scale_c ((g - c1) - vhat c2)
+ * takes the place of the affine's scale_c g: du of the unit (+ dskip, one fp32 add), dz of the stage, dZ of the branch, which feed the
+ * same products.  Every frame's dv depends on the sums of all frames, so each entry is two-phase across its frame chunks: the unit leaves
+ * the raw dgrad product in du and rewrites it in place once the sums are in (the mask re-evaluated from u by the same fma); the stage
+ * forms its sums from z and dy ahead of the chunks; the branch recomputes each chunk's Z a second time when there is more than one.
+ * dscale / dshift (may be NULL) are the sums themselves: pp_bn_affine_grad(dscale, dshift, mean, var) yields dgamma, dbeta.
+ * chunk_frames: 0 = the workspace rule, k > 0 = at most min(k, rule) frames per chunk; du / dx and the sums do not depend on it, dw does
+ * within fp32 summation error (the K ranges).  Stateless, either norm kind, fp32, no atomics, two runs are bit-identical.  PP_E_ARG as the
+ * _affine entries and for chunk_frames < 0. */
+int pp_backbone_train_taps_bn(pp_ctx* ctx, const float* canvas, int nb, const float* const* gamma_beta /* 38 */, float* rpn_out, float* x1,
+                              float* x2, float* x3, float* const* units /* 3, may be NULL */, float* const* z /* 3, may be NULL */, float* mean,
+                              float* var, float* scale, float* shift, void* stream);
+int pp_unit_backward_bn(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* scale, const float* shift,
+                        const float* mean, const float* var, const float* dy, const float* dskip /* may be NULL */, int nb, float* dw,
+                        float* du /* NULL: skipped */, double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames,
+                        void* stream);
+int pp_down_backward_bn(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z, const float* scale,
+                        const float* shift, const float* mean, const float* var, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */,
+                        double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames, void* stream);
+int pp_neck_backward_bn(pp_ctx* ctx, int branch, const float* x, const float* w, const float* scale, const float* shift, const float* mean,
+                        const float* var, const float* y, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */,
+                        double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames, void* stream);
+
 /* ---- training the pillar feature net: PointNet in train mode, its backward and the scatter's (pfn_train.hip) ----
  * PointNet.forward (pointpillars8_shared.py:30-60) with BatchNorm1d normalising by BATCH statistics.  Notation: f[p][t][0:9] the nine
  * decorated features of slot t of pillar p (x, y, z, r, x - mx, y - my, z - mz, x - cx, y - cy; arithmetic as pp_pfn: mean over all T
