@@ -90,6 +90,10 @@ PROTOTYPES = {
     "pp_backbone_block_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_block_weights": (ctypes.c_int, [c_p, ctypes.c_int, c_p, ctypes.c_int, c_p]),
     "pp_down_backward": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
+    "pp_down_backward_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 5 + [c_p] * 4 + [ctypes.c_int, c_p, c_p, c_p]),
+    "pp_down_backward_path": (ctypes.c_int, [c_p] + [ctypes.c_int] * 5),
+    "pp_neck_backward_mp": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p]),
+    "pp_neck_backward_path": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int]),
     "pp_backbone_stage_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_down_weight": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
     "pp_backbone_train_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),

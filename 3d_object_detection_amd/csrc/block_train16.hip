@@ -27,32 +27,9 @@
 #include "pp_common.h"
 #include "train_planes.h"
 #include "block_train.h"
+#include "train16.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) // v_cvt_pk_bf16_f32 (round to nearest even), a in the low half
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
-// the residual the lo image rounds: x - bf16(x), one fp32 subtraction (exact for finite x)
-__device__ __forceinline__ float bf16_rest(float x) { return x - __uint_as_float(pk_bf16(x, 0.f) << 16); }
-__device__ __forceinline__ u32x4 pk8(const float* v) { return u32x4{pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])}; }
-__device__ __forceinline__ u32x4 pk8_rest(const float* v)
-{
-    float r[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = bf16_rest(v[e]);
-    return pk8(r);
-}
-__device__ __forceinline__ f32x4 mfma16(const u32x4 a, const u32x4 b, const f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]
 template <bool X3>
@@ -154,15 +131,6 @@ __global__ void __launch_bounds__(256) k_unit_packT16(const float* __restrict__ 
 // positions 8 q .. 8 q + 7 of the chunk.  Column n reads a at the row shift (t / 3 - 1) wp as one aligned 16-byte load d, plus the dword
 // e before (kx = 0) or behind (kx = 2) it; the fragment is the five dwords shifted by one element.  blockIdx.z owns chunks
 // [z cps, (z + 1) cps) and writes partial gbase + z in the state_dict layout [co][ci][3][3] -------------------------------------------
-__device__ __forceinline__ u32x4 shift_frag(const u32x4 d, const unsigned e, const int kx)
-{
-    const bool left = kx == 0; // elements P - 1 .. P + 6: e, d0 .. d3; kx = 2: P + 1 .. P + 8: d0 .. d3, e; kx = 1: d
-    const unsigned s0 = left ? e : d[0], s1 = left ? d[0] : d[1], s2 = left ? d[1] : d[2], s3 = left ? d[2] : d[3], s4 = left ? d[3] : e;
-    const unsigned sh = kx == 1 ? 0u : 16u;
-    return u32x4{__builtin_amdgcn_alignbit(s1, s0, sh), __builtin_amdgcn_alignbit(s2, s1, sh), __builtin_amdgcn_alignbit(s3, s2, sh),
-                 __builtin_amdgcn_alignbit(s4, s3, sh)};
-}
-
 template <int NB, int MA, int WR, bool X3>
 __global__ void __launch_bounds__(256) k_unit_wgrad16(const uint16_t* __restrict__ z16, const uint16_t* __restrict__ a16, float* __restrict__ part,
                                                       int C, int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase, size_t pstride)

@@ -456,10 +456,22 @@ class Engine:
                        self.ctx, "pp_backbone_taps")
         return (out, *taps)
 
-    def neck_backward(self, branch, x, w, y, dy, need_dx=True):
-        """pp_neck_backward: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
+    def neck_backward_path(self, grad_precision, branch):
+        """pp_neck_backward_path: the precision neck_backward(grad_precision=...) really runs for this branch."""
+        mode = self._grad_mode(grad_precision, "neck_backward_path")
+        if branch not in (0, 1, 2):
+            raise ValueError(f"neck_backward_path: branch must be 0, 1 or 2, got {branch!r}")
+        rc = self.lib.pp_neck_backward_path(self.ctx, mode, int(branch))
+        if rc < 0:
+            _lib.check(-rc, self.ctx, "pp_neck_backward_path")
+        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+
+    def neck_backward(self, branch, x, w, y, dy, need_dx=True, grad_precision="fp32"):
+        """pp_neck_backward_mp: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
         dL/d(rpn_out) dy [nb,320,H,W] -> (dw [Cin,Cup,s,s] summed over the frames, dx [nb,Cin,h,w] or None when need_dx is False).
-        fp32, deterministic, stateless."""
+        Deterministic, stateless.  grad_precision: "fp32" (pp_neck_backward, bit for bit), "bf16x3" or "bf16": the operands of the dw
+        and dx products in split or plain bf16 on the bf16 MFMA, everything else (Z, statistics, mask, dZ, tensors) fp32."""
+        mode = self._grad_mode(grad_precision, "neck_backward")
         if branch not in (0, 1, 2):
             raise ValueError(f"neck_backward: branch must be 0, 1 or 2, got {branch!r}")
         xs, wsh = self.neck_shapes(branch)
@@ -476,8 +488,8 @@ class Engine:
         dw = self._t(wsh, torch.float32)
         dx = self._t((nb,) + xs, torch.float32) if need_dx else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_neck_backward(self.ctx, branch, _ptr(x), _ptr(w), _ptr(y), _ptr(dy), nb, _ptr(dw), _ptr(dx), _stream()),
-                       self.ctx, "pp_neck_backward")
+            _lib.check(self.lib.pp_neck_backward_mp(self.ctx, mode, branch, _ptr(x), _ptr(w), _ptr(y), _ptr(dy), nb, _ptr(dw), _ptr(dx), _stream()),
+                       self.ctx, "pp_neck_backward_mp")
         return dw, dx
 
     def update_neck_weights(self, params):
@@ -559,11 +571,22 @@ class Engine:
     DOWN_KEYS = ("rpn.block1.0.weight", "rpn.block2.0.weight", "rpn.block3.0.weight")
     DOWN_PAIRS = ((64, 64), (64, 128), (128, 256))
 
-    def down_backward(self, x, w, z, dy, need_dx=True):
-        """pp_down_backward: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
+    def down_backward_path(self, grad_precision, cin, cout, hin, win):
+        """pp_down_backward_path: the precision down_backward(grad_precision=...) really runs at this shape."""
+        mode = self._grad_mode(grad_precision, "down_backward_path")
+        rc = self.lib.pp_down_backward_path(self.ctx, mode, int(cin), int(cout), int(hin), int(win))
+        if rc < 0:
+            _lib.check(-rc, self.ctx, "pp_down_backward_path")
+        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+
+    def down_backward(self, x, w, z, dy, need_dx=True, grad_precision="fp32"):
+        """pp_down_backward_mp: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
         (64, 128) | (128, 256).  x [nb,Cin,Hin,Win] (the stage's raw input), w [Cout,Cin,3,3], z (the conv output) and dy (dL/d(stage
         output)) [nb,Cout,(Hin+1)//2,(Win+1)//2] -> (dw [Cout,Cin,3,3] summed over the frames, dx [nb,Cin,Hin,Win] or None when
-        need_dx is False).  fp32, deterministic, stateless."""
+        need_dx is False).  Deterministic, stateless.  grad_precision: "fp32" (pp_down_backward, bit for bit), "bf16x3" or "bf16": the
+        operands of the wgrad and dgrad products in split or plain bf16 on the bf16 MFMA, everything else (planes, statistics, mask,
+        norm backward, tensors) fp32."""
+        mode = self._grad_mode(grad_precision, "down_backward")
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
             raise ValueError(f"down_backward: x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, cin, hin, win = (int(v) for v in x.shape)
@@ -583,8 +606,8 @@ class Engine:
         dw = self._t((cout, cin, 3, 3), torch.float32)
         dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_down_backward(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(dy), nb, _ptr(dw), _ptr(dx),
-                                                 _stream()), self.ctx, "pp_down_backward")
+            _lib.check(self.lib.pp_down_backward_mp(self.ctx, mode, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(dy), nb, _ptr(dw), _ptr(dx),
+                                                    _stream()), self.ctx, "pp_down_backward_mp")
         return dw, dx
 
     def backbone_stage_taps(self, canvas):

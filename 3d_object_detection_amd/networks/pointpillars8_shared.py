@@ -38,7 +38,8 @@ reference's net.train() does: every BatchNorm2d normalises with the statistics o
 training forward is then one lock-step pass over all frames (pp_backbone_train_taps_bn) and _RpnBnBatchFunction walks the table with
 pp_*_backward_bn; the moved running statistics are folded again before the next eval-mode pass.
 
-Mixed precision: train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
+Mixed precision (grad_stages="rpn" extends it to the strided stages and the upsamplers, pp_down_backward_mp / pp_neck_backward_mp):
+train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
 or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
 backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit."""
 import time
@@ -71,6 +72,8 @@ _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in
 ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
 SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
 GRAD_PRECISIONS = ("fp32", "bf16x3", "bf16")  # train(grad_precision=...): the operands of the unit backwards' gradient products
+GRAD_STAGES = ("units", "rpn")  # train(grad_stages=...): the backwards that take grad_precision: the units alone, or the strided stages
+                                # and the upsamplers as well
 BN_STATS = ("frozen", "moving", "batch")  # train(bn_stats=...) on a BatchNorm network; "batch" is refused: "moving" is its name here
 BN2D_MOMENTUM = 0.01  # the reference's BatchNorm2d(eps=1e-3, momentum=0.01) of the RPN
 
@@ -189,6 +192,9 @@ class _RpnFunction(torch.autograd.Function):
     weights: RPN_CONV_KEYS[first:], then the three upsamplers; they are inputs only so that autograd routes their gradients, the
     forward reads the engine's packed copy of them (PointPillars uploads it beforehand).
 
+    prec is the pair (grad_precision of the unit backwards, grad_precision of the strided stages and upsamplers): the second is "fp32"
+    unless train(grad_stages="rpn") hands the network's grad_precision to pp_down_backward_mp and pp_neck_backward_mp as well.
+
     The backward is pp_neck_backward for the three branches and then, from level 2 down along RPN_TABLE, the block's unit chain
     (rpn_block_backward) and its strided stage (pp_down_backward); the upsampler's dx plus the dx of the stage above (in this order)
     is the gradient of a level's block output.  It stops where nothing in front needs a gradient: a dx is computed only when a
@@ -198,7 +204,7 @@ class _RpnFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, prec, first, x, *weights):
-        ctx.eng, ctx.prec, ctx.first = eng, prec, first
+        ctx.eng, (ctx.prec, ctx.stage_prec), ctx.first = eng, prec, first  # prec: (the units' grad_precision, the stages' and upsamplers')
         outs = [_frame_taps(eng, first, c) for c in x]
         y = torch.cat([o[0] for o in outs])
         taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
@@ -226,10 +232,12 @@ class _RpnFunction(torch.autograd.Function):
         for b, mods in RPN_TABLE:
             front.append(front[b] or any(need_c.get(k, False) for k in range(_W0[b], _W0[b] + 1 + sum(mods))))
         gy = gy.contiguous()
+        # the keyword goes to down_backward / neck_backward only when a 16-bit mode is asked for those stages (grad_stages="rpn")
+        stage_kw = {} if ctx.stage_prec == "fp32" else {"grad_precision": ctx.stage_prec}
         dwn, dxn = [None] * 3, [None] * 3
         for b in range(3):
             if need_n[b] or front[b + 1]:
-                dwn[b], dxn[b] = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=front[b + 1])
+                dwn[b], dxn[b] = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=front[b + 1], **stage_kw)
         dwc, g = {}, None
         for b, mods, w0, n in reversed(levels):
             if not front[b + 1]:
@@ -239,7 +247,7 @@ class _RpnFunction(torch.autograd.Function):
             dws, gh = rpn_block_backward(eng, mods, units[b], [wc[w0 + 1 + i] for i in range(n)], g, ctx.prec, need_dh=need_dh)
             dwc.update(zip(range(w0 + 1, w0 + 1 + n), dws))
             if need_dh:
-                dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=front[b])
+                dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=front[b], **stage_kw)
         grads = [dwc.get(k) if need_c[k] else None for k in range(first, nconv)] + [d if n else None for d, n in zip(dwn, need_n)]
         return (None, None, None, g if need_x else None) + tuple(grads)
 
@@ -395,6 +403,7 @@ class _PfnFunction(torch.autograd.Function):
 class PointPillars:
     _norm = "instance"
     grad_precision = "fp32"
+    grad_stages = "units"
     bn_stats = None  # train(bn_stats=...) while training a BatchNorm network
     # read-only defaults for an object assembled without __init__ (no engine: the key-order and plan tests); __init__ and
     # load_state_dict give every object its own
@@ -432,7 +441,7 @@ class PointPillars:
     def eval(self):
         return self.train(False)
 
-    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None):
+    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None, grad_stages="units"):
         """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
         trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
         block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
@@ -444,6 +453,9 @@ class PointPillars:
         grad_precision ("fp32" | "bf16x3" | "bf16", kept as net.grad_precision, "fp32" again after eval()): the operand precision of
         the Resnet units' gradient products (pp_unit_backward_mp), in effect under the scopes that run them ("block3", "stage3", "rpn",
         "all") and inert under "head" and "neck".  The forward, the strided stages, the upsamplers, the head and the PFN stay fp32.
+        grad_stages ("units" | "rpn", kept as net.grad_stages, "units" again after eval()): which backwards take grad_precision.  "units":
+        the Resnet units alone, as above.  "rpn": the three strided stages (pp_down_backward_mp) and the three upsamplers
+        (pp_neck_backward_mp) as well, wherever the scope runs them; the head backward, the PFN and the forward stay fp32.
         bn_stats (BatchNorm networks only, kept as net.bn_stats): "frozen" enables every scope there as fine-tuning with frozen
         statistics.  Every BatchNorm2d of the RPN stays in eval mode and normalises with its running statistics, which do not move, as
         does num_batches_tracked; its weight / bias train with the convolution whose backward primitive yields their gradient (a
@@ -459,6 +471,8 @@ class PointPillars:
         gradients, exactly as under "frozen".  eval() folds the moved statistics into the engine before the next pass."""
         if grad_precision not in GRAD_PRECISIONS:
             raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
+        if grad_stages not in GRAD_STAGES:
+            raise ValueError(f"train: grad_stages must be 'units' or 'rpn', got {grad_stages!r}")
         if scope not in SCOPES:
             raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
         if bn_stats is not None:
@@ -478,6 +492,7 @@ class PointPillars:
         self.training = bool(mode)
         self._scope = scope if self.training else "head"
         self.grad_precision = grad_precision if self.training else "fp32"
+        self.grad_stages = grad_stages if self.training else "units"
         self.bn_stats = bn_stats if self.training else None
         trained = self._groups(self._scope) if self.training else ()
         for g in _GROUPS.values():
@@ -778,7 +793,7 @@ class PointPillars:
                 return self._rpn_train_moving(first, x, [every[n] for k in layers for n in (k, *bn_affine_keys(k))])
             stats = [tuple(self._bn_run[f"{Engine.bn_prefix(k)}.{s}"] for s in Engine.BN_FIELDS[2:]) for k in layers]
             return _RpnBnFunction.apply(eng, first, stats, x, *[every[n] for k in layers for n in (k, *bn_affine_keys(k))])
-        return _RpnFunction.apply(eng, self.grad_precision, first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
+        return _RpnFunction.apply(eng, (self.grad_precision, self.grad_precision if self.grad_stages == "rpn" else "fp32"), first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
 
     def _rpn_train_moving(self, first, x, tensors):
         """rpn_train under bn_stats="moving": one lock-step pass with batch statistics, then BatchNorm2d's update of the running

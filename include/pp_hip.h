@@ -314,6 +314,20 @@ int pp_backbone_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1
  * PP_E_ARG for a null pointer, branch outside 0..2, nb outside 1..max_batch, a misaligned w and the BatchNorm backbone. */
 int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const float* w, const float* y, const float* dy, int nb, float* dw, float* dx,
                      void* stream);
+/* pp_neck_backward with 16-bit GEMM operands (neck_train16.hip): mixed-precision training, the modes of pp_unit_backward_mp with the same
+ * numbering: 0 fp32 (exactly pp_neck_backward, bit for bit), 1 "bf16x3" (operands split hi + lo, a product is hi hi + hi lo + lo hi),
+ * 2 "bf16" (operands rounded once), both on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  The recomputed forward Z, the statistics,
+ * the mask and dZ are the fp32 kernels in every mode; only the operands of dw = sum x dZ and dx = sum w dZ are 16-bit.  x and dZ are read
+ * as fp32 and rounded or split in registers (no 16-bit image is kept; w is packed once per call), so the workspace and the frame chunks are
+ * pp_neck_backward's and every branch runs in the mode asked for.  The dx product keeps the blocked sum (64 rows from zero, block sums
+ * added in row order).  Stateless and deterministic as pp_neck_backward: no atomics, two runs are bit-identical, a frame's dx does not
+ * depend on nb, dw does not depend on whether dx is asked for and depends on nb through the fixed K ranges (32-pixel chunks) only.
+ * PP_E_ARG as pp_neck_backward, and for a mode outside 0..2. */
+int pp_neck_backward_mp(pp_ctx* ctx, int mode, int branch, const float* x, const float* w, const float* y, const float* dy, int nb, float* dw,
+                        float* dx /* may be NULL */, void* stream);
+/* The mode pp_neck_backward_mp really runs for this branch: `mode`.  Launches nothing.  An error is negative: -PP_E_ARG for a null context,
+ * a mode outside 0..2, a branch outside 0..2, a BEV grid that is no multiple of 8 and the BatchNorm backbone. */
+int pp_neck_backward_path(pp_ctx* ctx, int mode, int branch);
 /* After an optimizer step: three DEVICE tensors in state_dict layout (rpn.deconv{1,2,3}.0.weight: [64][64][1][1], [128][128][2][2],
  * [256][128][4][4]) -> the packed weight images of the three upsamplers of the committed launch plan, rewritten in place on `stream` (no
  * host copy, no re-tuning).  pp_backbone, pp_backbone_taps, pp_infer_frame and pp_infer_batch read those images, so all see the new
@@ -406,6 +420,22 @@ int pp_update_block_weights(pp_ctx* ctx, int block, const float* const* w, int n
  * BatchNorm backbone. */
 int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z, const float* dy, int nb,
                      float* dw, float* dx /* NULL: skipped */, void* stream);
+/* pp_down_backward with 16-bit GEMM operands (down_train16.hip): mixed-precision training, the modes of pp_unit_backward_mp with the same
+ * numbering: 0 fp32 (exactly pp_down_backward, bit for bit), 1 "bf16x3", 2 "bf16", both on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.
+ * The parity planes of x, the plane statistics (fp64 sums), the mask xhat > 0, the norm backward that writes dz and the reduction of the
+ * dw partials in double are the fp32 kernels in every mode; only the operands of the wgrad and dgrad products are 16-bit.  The planes stay
+ * fp32 and are rounded or split in registers as they are loaded (no 16-bit image is kept; w is packed once per call), so the workspace,
+ * its budgets and the frame chunks are pp_down_backward's and every shape it takes runs in the mode asked for.  The dgrad keeps the
+ * blocked sum (64 k-terms from zero, block sums added in (tap, co) order).  Stateless and deterministic as pp_down_backward: no atomics,
+ * two runs are bit-identical, a frame's dx does not depend on nb, dw does not depend on whether dx is asked for and depends on nb through
+ * the fixed K ranges (32-position chunks) only.
+ * PP_E_ARG as pp_down_backward, and for a mode outside 0..2. */
+int pp_down_backward_mp(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z,
+                        const float* dy, int nb, float* dw, float* dx /* may be NULL */, void* stream);
+/* The mode pp_down_backward_mp really runs for this shape: `mode`.  Launches nothing.  An error is negative: -PP_E_ARG for a null context,
+ * a mode outside 0..2, a channel pair outside the three, sizes out of range (a frame past the 256 MB budget included) and the BatchNorm
+ * backbone. */
+int pp_down_backward_path(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win);
 /* pp_backbone_block_taps plus z3 f32[256][H/4][W/4], the raw (pre-norm) output of block 3's strided convolution, copied out behind
  * that launch (units[0] = relu(norm(z3)); the first unit reuses the buffer).  fp32 mode only, as pp_backbone_taps. */
 int pp_backbone_stage_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3, float* units, float* z3,

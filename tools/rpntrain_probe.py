@@ -11,6 +11,9 @@ Mixed precision: pp_unit_backward_mp is timed per `--grad-precision` mode (defau
 turns window by window as well.  A mode's floor is the flops its MFMAs execute over its own padded plane / its rate: fp32 157.3 TF,
 bf16 and bf16x3 2.5 PF (the bf16 MFMA roof), bf16x3 executing three MFMAs per product.  `vs_fp32` is median / fp32's median and
 `ships` whether the mode's slowest window beats fp32's fastest (the condition for pp_unit_backward_path to hand the shape to it).
+pp_down_backward_mp (the same shapes as pp_down_backward) and pp_neck_backward_mp (the three branches of the map) take part in the same
+windows, per mode.  Their 16-bit kernels read the fp32 planes, so a mode's floor is the fp32 call's flops x (3 for bf16x3) / 2.5 PF; the
+neck's recomputed forward Z = w^T x stays an fp32 product in every mode and is counted at 157.3 TF.  `--only-stages` skips the unit rows.
 
     python tools/rpntrain_probe.py [--frames 1,8] [--reps 20] [--windows 7] [--grad-precision fp32,bf16x3,bf16]
     rocprofv3 --kernel-trace --stats -d OUT -o rpntrain -- python tools/rpntrain_probe.py --frames 8 --no-step   (per-kernel split)
@@ -41,7 +44,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--no-step", action="store_true", help="skip the whole-step lines")
-    ap.add_argument("--grad-precision", default="fp32,bf16x3,bf16", help="modes of pp_unit_backward_mp to time")
+    ap.add_argument("--grad-precision", default="fp32,bf16x3,bf16", help="modes of the *_backward_mp entries to time")
+    ap.add_argument("--only-stages", action="store_true", help="time pp_down_backward_mp and pp_neck_backward_mp only")
     a = ap.parse_args()
     modes = [m for m in a.grad_precision.split(",") if m]
     assert modes and all(m in MODES for m in modes), a.grad_precision
@@ -80,6 +84,8 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     for nb in frames:
         calls, rows = {}, {}
+        yn = torch.randn((nb, 320, H, W), device=d, generator=gen)  # rpn_out (its sign is the ReLU mask) and dL/d(rpn_out)
+        dyn = torch.randn((nb, 320, H, W), device=d, generator=gen)
         for b in (2, 1, 0):  # block 3's shape first: the yardstick of the other two
             C, cin, h, w = 64 << b, eng.DOWN_PAIRS[b][0], H >> b, W >> b
             wu = (torch.randn((C, C, 3, 3), device=d, generator=gen) * 0.05).contiguous()
@@ -97,11 +103,26 @@ def main():
                 assert lib.pp_unit_backward_path(ctx, MODES[m], C, h, w) == MODES[m], (m, C, h, w)
             down = lambda C=C, cin=cin, h=h, w=w, x=x, w0=w0, z=z, dy=dy, dw0=dw0, dx=dx: lib.pp_down_backward(  # noqa: E731
                 ctx, cin, C, 2 * h, 2 * w, ptr(x), ptr(w0), ptr(z), ptr(dy), nb, ptr(dw0), ptr(dx), st)
-            calls[b] = dict(unit=unit, down=down, keep=keep, ms=dict(unit=[], down=[]), **{"mp_" + m: f for m, f in mp.items()})
-            calls[b]["ms"].update({"mp_" + m: [] for m in modes})
+            dmp = {m: (lambda C=C, cin=cin, h=h, w=w, x=x, w0=w0, z=z, dy=dy, dw0=dw0, dx=dx, m=m: lib.pp_down_backward_mp(  # noqa: E731
+                ctx, MODES[m], cin, C, 2 * h, 2 * w, ptr(x), ptr(w0), ptr(z), ptr(dy), nb, ptr(dw0), ptr(dx), st)) for m in modes}
+            xn = torch.randn((nb, C, h, w), device=d, generator=gen)  # the upsampler of level b reads the block output [C][h][w]
+            wn = (torch.randn((C, 128 if b else 64, 1 << b, 1 << b), device=d, generator=gen) * 0.05).contiguous()
+            dwn, dxn = torch.empty_like(wn), torch.empty_like(xn)
+            nmp = {m: (lambda b=b, xn=xn, wn=wn, dwn=dwn, dxn=dxn, m=m: lib.pp_neck_backward_mp(  # noqa: E731
+                ctx, MODES[m], b, ptr(xn), ptr(wn), ptr(yn), ptr(dyn), nb, ptr(dwn), ptr(dxn), st)) for m in modes}
+            for m in modes:
+                assert lib.pp_down_backward_path(ctx, MODES[m], cin, C, 2 * h, 2 * w) == MODES[m], (m, cin, C, h, w)
+                assert lib.pp_neck_backward_path(ctx, MODES[m], b) == MODES[m], (m, b)
+            keep += (xn, wn, dwn, dxn)
+            calls[b] = dict(unit=unit, down=down, keep=keep, ms=dict(unit=[], down=[]), **{"mp_" + m: f for m, f in mp.items()},
+                            **{"dmp_" + m: f for m, f in dmp.items()}, **{"nmp_" + m: f for m, f in nmp.items()})
+            calls[b]["ms"].update({p + m: [] for m in modes for p in ("mp_", "dmp_", "nmp_")})
+            if a.only_stages:
+                for k in ["unit", "down"] + ["mp_" + m for m in modes]:
+                    del calls[b]["ms"][k]
         for win in range(a.windows + 1):  # the first round warms up (workspaces grow, clocks rise) and is dropped
             for b in (2, 1, 0):
-                for k in ["unit", "down"] + ["mp_" + m for m in modes]:
+                for k in list(calls[b]["ms"]):
                     t = timed(calls[b][k])
                     if win:
                         calls[b]["ms"][k].append(t)
@@ -114,20 +135,29 @@ def main():
             for m in modes:
                 fl["mp_" + m] = (fl["unit"] if m == "fp32" else (3 if m == "bf16x3" else 1) * 2 * 2.0 * C * 9 * C * PP16 * nb / BF16_FS * 1e3)
                 sh["mp_" + m] = [C, h, w]
+                mult = (3 if m == "bf16x3" else 1) * MFMA_FS / BF16_FS  # the fp32 call's flops at the mode's rate
+                fl["dmp_" + m] = fl["down"] if m == "fp32" else mult * fl["down"]
+                sh["dmp_" + m] = sh["down"]
+                gemm = 2.0 * C * (128 if b else 64) * h * w * (1 << 2 * b) * nb / MFMA_FS * 1e3  # one Cin x R x p product in fp32
+                fl["nmp_" + m] = 3 * gemm if m == "fp32" else gemm + 2 * mult * gemm
+                sh["nmp_" + m] = [b, C, h, w]
             rows[b] = {k: dict(shape=sh[k], ms=med(v), ms_min=min(v), ms_max=max(v), floor_ms=fl[k], over_floor=med(v) / fl[k])
                        for k, v in calls[b]["ms"].items()}
         for b in (0, 1, 2):
-            for k in ("unit", "down"):
+            for k in () if a.only_stages else ("unit", "down"):
                 r, r3 = rows[b][k], rows[2][k]
                 out["rows"].append(dict(frames=nb, call=k + "_backward", level=b, **r, vs_block3=r["over_floor"] / r3["over_floor"],
                                         vs_block3_worst=(r["ms_max"] / r["floor_ms"]) / (r3["ms_min"] / r3["floor_ms"])))
         for b in (0, 1, 2):
-            f32 = rows[b].get("mp_fp32")
-            for m in modes:
-                r = rows[b]["mp_" + m]
-                extra = dict(vs_fp32=r["ms"] / f32["ms"], ships=r["ms_max"] < f32["ms_min"]) if f32 and m != "fp32" else {}
-                out["rows"].append(dict(frames=nb, call="unit_backward_mp", grad_precision=m, level=b, **r, **extra))
-        del calls
+            for pre, call in (("mp_", "unit_backward_mp"), ("dmp_", "down_backward_mp"), ("nmp_", "neck_backward_mp")):
+                f32 = rows[b].get(pre + "fp32")
+                for m in modes:
+                    if pre + m not in rows[b]:
+                        continue
+                    r = rows[b][pre + m]
+                    extra = dict(vs_fp32=r["ms"] / f32["ms"], ships=r["ms_max"] < f32["ms_min"]) if f32 and m != "fp32" else {}
+                    out["rows"].append(dict(frames=nb, call=call, grad_precision=m, level=b, **r, **extra))
+        del calls, yn, dyn
         torch.cuda.empty_cache()
     keys = eng.RPN_CONV_KEYS
     every = {**net._rpn, **net._down, **net._block}
@@ -192,6 +222,13 @@ def main():
                 opt = torch.optim.SGD(net.parameters(), lr=1e-3)
                 step(opt)
                 out.setdefault("step_nb8_rpn_" + m, []).append(step(opt))
+        for rnd in range(3):  # the same step with the strided stages and upsamplers in the mode as well, against the units alone
+            for m in [m for m in modes if m != "fp32"]:
+                for stages in ("units", "rpn"):
+                    net.train(scope="rpn", grad_precision=m, grad_stages=stages)
+                    opt = torch.optim.SGD(net.parameters(), lr=1e-3)
+                    step(opt)
+                    out.setdefault(f"step_nb8_rpn_{m}_stages_{stages}", []).append(step(opt))
         # what the forward keeps for the backward, per frame
         net.train(scope="rpn")
         torch.cuda.synchronize()
