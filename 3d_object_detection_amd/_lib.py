@@ -110,6 +110,7 @@ PROTOTYPES = {
     "pp_unit_backward_bn": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
     "pp_down_backward_bn": (ctypes.c_int, [c_p] + [ctypes.c_int] * 4 + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
     "pp_neck_backward_bn": (ctypes.c_int, [c_p, ctypes.c_int] + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    "pp_set_train_chunk_frames": (ctypes.c_int, [c_p, ctypes.c_int]),
     "pp_pfn_train_forward": (ctypes.c_int, [c_p] * 12),
     "pp_scatter_backward": (ctypes.c_int, [c_p] * 6),
     "pp_pfn_backward": (ctypes.c_int, [c_p] * 15),

@@ -438,8 +438,7 @@ extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u
     block_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: functions of the shapes alone
     const size_t pf_elems = (size_t)C * PS;
-    int fc = (int)(WS_CHUNK / (2 * pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, WS_CHUNK, 2 * pf_elems * sizeof(float), nb, 0);
     const int TN = C >= 128 ? 128 : 192; // columns of a wgrad tile: k_unit_wgrad<4, 2> or <3, 4>
     const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
     int Gp = 0;
@@ -519,8 +518,7 @@ extern "C" int pp_unit_backward_affine(pp_ctx* ctx, int C, int h, int w, const f
     block_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: as pp_unit_backward
     const size_t pf_elems = (size_t)C * PS;
-    int fc = (int)(WS_CHUNK / (2 * pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, WS_CHUNK, 2 * pf_elems * sizeof(float), nb, 0);
     const int TN = C >= 128 ? 128 : 192;
     const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
     int Gp = 0;
@@ -601,9 +599,7 @@ extern "C" int pp_unit_backward_bn(pp_ctx* ctx, int C, int h, int w, const float
     block_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: as pp_unit_backward, the chunk capped by chunk_frames
     const size_t pf_elems = (size_t)C * PS;
-    int fc = (int)(WS_CHUNK / (2 * pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
-    if (chunk_frames > 0 && chunk_frames < fc) fc = chunk_frames;
+    const int fc = pp_chunk_frames(ctx, WS_CHUNK, 2 * pf_elems * sizeof(float), nb, chunk_frames);
     const int TN = C >= 128 ? 128 : 192;
     const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
     int Gp = 0;

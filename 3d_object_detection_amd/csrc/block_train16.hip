@@ -351,8 +351,7 @@ int unit_backward16(pp_ctx* ctx, int C, int h, int w, const float* u, const floa
     block_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: functions of the shapes and the mode alone
     const size_t pf_elems = (size_t)C * PS;
-    int fc = (int)(WS_CHUNK / frame16_bytes(parts, C, g));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, WS_CHUNK, frame16_bytes(parts, C, g), nb, 0);
     const int TN = C >= 128 ? 128 : 192, TM = C >= 128 ? 128 : 64; // a wgrad tile: k_unit_wgrad16<4, 4, 2> or <3, 4, 1>
     const int NC = 9 * C, tiles = (NC / TN) * (C / TM), cpf = (PP + 31) / 32;
     int Gp = 0;

@@ -303,8 +303,7 @@ extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win
     down_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: functions of the shapes alone
     const size_t pf_elems = (size_t)pf64;
-    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, 0);
     const int TN = cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_down_wgrad<4, 2> or <3, 4>
     const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
     int Gp = 0;
@@ -386,8 +385,7 @@ extern "C" int pp_down_backward_affine(pp_ctx* ctx, int cin, int cout, int hin, 
     down_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: as pp_down_backward
     const size_t pf_elems = (size_t)pf64;
-    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, 0);
     const int TN = cin >= 128 ? 128 : 192;
     const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
     int Gp = 0;
@@ -468,9 +466,7 @@ extern "C" int pp_down_backward_bn(pp_ctx* ctx, int cin, int cout, int hin, int 
     down_ws* ws = workspace(ctx);
     // frames per chunk and K ranges: as pp_down_backward, the chunk capped by chunk_frames
     const size_t pf_elems = (size_t)pf64;
-    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
-    if (chunk_frames > 0 && chunk_frames < fc) fc = chunk_frames;
+    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, chunk_frames);
     const int TN = cin >= 128 ? 128 : 192;
     const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
     int Gp = 0;

@@ -240,8 +240,7 @@ int down_backward16(pp_ctx* ctx, int cin, int cout, int hin, int win, const floa
     down_ws* ws = workspace(ctx);
     // frames per chunk as pp_down_backward; K ranges over 32-position chunks: functions of the shapes alone
     const size_t pf_elems = (size_t)g.pf;
-    int fc = (int)(DOWN_WS_CHUNK / (pf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, 0);
     const int TN = cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_down_wgrad16<4, 2> or <3, 4>
     const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 31) / 32;
     int Gp = 0;

@@ -256,8 +256,7 @@ extern "C" int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const f
     neck_ws* ws = workspace(ctx);
     // frames per chunk, statistics segments, K ranges: functions of the shapes alone
     const size_t zf_elems = (size_t)g.R * g.pld;
-    int fc = (int)(Z_BUDGET / (zf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, 0);
     int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
     S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
     const int seg_len = (N + S - 1) / S;
@@ -337,8 +336,7 @@ extern "C" int pp_neck_backward_affine(pp_ctx* ctx, int branch, const float* x, 
     neck_ws* ws = workspace(ctx);
     // frames per chunk, segments, K ranges: as pp_neck_backward
     const size_t zf_elems = (size_t)g.R * g.pld;
-    int fc = (int)(Z_BUDGET / (zf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, 0);
     int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
     S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
     const int slen = (N + S - 1) / S;
@@ -419,9 +417,7 @@ extern "C" int pp_neck_backward_bn(pp_ctx* ctx, int branch, const float* x, cons
     neck_ws* ws = workspace(ctx);
     // frames per chunk, segments, K ranges: as pp_neck_backward, the chunk capped by chunk_frames
     const size_t zf_elems = (size_t)g.R * g.pld;
-    int fc = (int)(Z_BUDGET / (zf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
-    if (chunk_frames > 0 && chunk_frames < fc) fc = chunk_frames;
+    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, chunk_frames);
     int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
     S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
     const int slen = (N + S - 1) / S;

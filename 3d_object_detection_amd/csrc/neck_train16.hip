@@ -196,8 +196,7 @@ int neck_backward16(pp_ctx* ctx, int branch, const float* x, const float* wt, co
     neck_ws* ws = workspace(ctx);
     // frames per chunk and statistics segments as pp_neck_backward; K ranges over 32-pixel chunks: functions of the shapes alone
     const size_t zf_elems = (size_t)g.R * g.pld;
-    int fc = (int)(Z_BUDGET / (zf_elems * sizeof(float)));
-    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, 0);
     int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
     S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
     const int seg_len = (N + S - 1) / S;

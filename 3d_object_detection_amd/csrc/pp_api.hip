@@ -256,6 +256,15 @@ extern "C" int pp_set_precision(pp_ctx* ctx, int mode)
     return 0;
 }
 
+// the cap pp_chunk_frames (pp_common.h) applies in every training backward
+extern "C" int pp_set_train_chunk_frames(pp_ctx* ctx, int k)
+{
+    if (!ctx) return PP_E_ARG;
+    if (k < 0) return pp_fail(ctx, PP_E_ARG, "pp_set_train_chunk_frames: k must be >= 0 (0: the workspace rule alone)");
+    ctx->train_chunk_frames = k;
+    return 0;
+}
+
 extern "C" int pp_load_weights(pp_ctx* ctx, const char* name, const void* host_ptr, const int64_t* shape, int ndim)
 {
     if (!ctx || !name || !host_ptr || !shape || ndim < 0 || ndim > 4) return pp_fail(ctx, PP_E_ARG, "pp_load_weights: bad argument");

@@ -145,6 +145,7 @@ struct pp_ctx {
     void* down = nullptr;            // strided stage backward (down_train.hip): parity planes of x, dz planes, transposed weights, dW partials
     void* pfnt = nullptr;            // PFN training (pfn_train.hip): fp64 partials of both reductions, the batch-statistics scale / shift
     void* optim = nullptr;           // device optimizer (optim.hip): fp64 partials of the gradient norm, one per chunk
+    int train_chunk_frames = 0;      // pp_set_train_chunk_frames: cap on the frames of a chunk of every training backward (0: the workspace rule alone)
     // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
     //      the selected candidates only; f_box / f_dir are then stale until pp_head_materialise runs the full head over the retained
     //      concat buffer and statistics of that pass ----
@@ -277,5 +278,17 @@ void pp_optim_destroy(pp_ctx* ctx);
 // i becomes position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T, 0 for padding; the map is read back once per
 // commit, on the image's first update.  The callers check their arguments, the precision mode and set the device.
 int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream);
+
+// Frames per chunk of a training backward (the twelve pp_{unit,down,neck}_backward* chunk loops and the three _bn entries): as many
+// frames as fit `budget` bytes at frame_bytes each, at least 1 and at most nb; then at most the entry's own chunk_frames (0 where the
+// entry has none) and at most the context's cap (pp_set_train_chunk_frames), where those are non-zero.  A cap never raises the rule.
+static inline int pp_chunk_frames(const pp_ctx* ctx, size_t budget, size_t frame_bytes, int nb, int chunk_frames)
+{
+    int fc = (int)(budget / frame_bytes);
+    fc = fc < 1 ? 1 : fc > nb ? nb : fc;
+    if (chunk_frames > 0 && chunk_frames < fc) fc = chunk_frames;
+    if (ctx->train_chunk_frames > 0 && ctx->train_chunk_frames < fc) fc = ctx->train_chunk_frames;
+    return fc;
+}
 
 static inline int pp_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

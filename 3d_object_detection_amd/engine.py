@@ -254,6 +254,15 @@ class Engine:
         head on a gemm1x1 tiling."""
         return bool(self.lib.pp_head_defer_active(self.ctx))
 
+    def set_train_chunk_frames(self, k):
+        """pp_set_train_chunk_frames: cap the frames of a workspace chunk in every training backward (unit / down / neck, their
+        _affine, 16-bit and _bn forms) at min(k, the workspace rule); 0, the default, leaves the rule alone.  For tests: it lets small
+        shapes reach the chunked paths.  du / dx and the affine sums keep their bits, dw moves within fp32 summation error.  k < 0 is
+        refused (RuntimeError) and the earlier value stays."""
+        if not isinstance(k, int) or isinstance(k, bool):
+            raise ValueError(f"set_train_chunk_frames: k must be an int, got {k!r}")
+        _lib.check(self.lib.pp_set_train_chunk_frames(self.ctx, k), self.ctx, "pp_set_train_chunk_frames")
+
     def set_sparse_conv1(self, on):
         """pp_set_sparse_conv1: fp32 passes of the fused path compute the first convolution for the output pixels that see a pillar only
         (default) or with the dense tiling.  PP_SPARSE_CONV1=0 in the environment (read by pp_create) forces it off."""

@@ -544,7 +544,16 @@ int pp_update_bn_fold(pp_ctx* ctx, const float* const* bn /* 76 */, void* stream
  * dscale / dshift (may be NULL) are the sums themselves: pp_bn_affine_grad(dscale, dshift, mean, var) yields dgamma, dbeta.
  * chunk_frames: 0 = the workspace rule, k > 0 = at most min(k, rule) frames per chunk; du / dx and the sums do not depend on it, dw does
  * within fp32 summation error (the K ranges).  Stateless, either norm kind, fp32, no atomics, two runs are bit-identical.  PP_E_ARG as the
- * _affine entries and for chunk_frames < 0. */
+ * _affine entries and for chunk_frames < 0.
+ *
+ * pp_set_train_chunk_frames: a cap on the frames of a chunk for the whole context, so that small tests reach the chunked paths of EVERY
+ * training backward: pp_{unit,down,neck}_backward, their _affine and _mp forms (modes 1 and 2) and the three _bn entries.  All of them
+ * take their frames per chunk from one rule: as many frames as fit the entry's workspace budget, at least 1, at most nb.  k = 0 (the
+ * default of a fresh context) leaves that rule alone; k > 0 means at most min(k, rule) frames per chunk, in the _bn entries together with
+ * their own argument as the smaller of the non-zero values.  The cap never raises the rule and changes no result beyond what chunk_frames
+ * changes: du / dx, dscale / dshift keep their bits, dw moves within fp32 summation error (the K ranges follow the chunks).  Host side,
+ * takes effect from the next call.  PP_E_ARG for k < 0, and the earlier value stays. */
+int pp_set_train_chunk_frames(pp_ctx* ctx, int k);
 int pp_backbone_train_taps_bn(pp_ctx* ctx, const float* canvas, int nb, const float* const* gamma_beta /* 38 */, float* rpn_out, float* x1,
                               float* x2, float* x3, float* const* units /* 3, may be NULL */, float* const* z /* 3, may be NULL */, float* mean,
                               float* var, float* scale, float* shift, void* stream);
