@@ -1161,6 +1161,17 @@ class Engine:
             _lib.check(self.lib.pp_fetch_frame_tensor(self.ctx, int(frame), kind, _ptr(out), _stream()), self.ctx, "pp_fetch_frame_tensor")
         return out
 
+    def _stage_in(self, x):
+        """A copy of the hook input x inside a zeroed buffer with the slack include/pp_hip.h asks for around `in`: 256 bytes behind its
+        last element (wino6 fetches whole 16-byte pieces of a patch row, which start one float in front of a map row and end up to
+        63 floats behind it; every other family reads inside the tensor) and, in front, 128 elements -- at least the header's 256
+        bytes, and the tensor keeps the alignment of the allocation (fp32) or sits 256 bytes past it (fp16)."""
+        front, n = 128, x.numel()
+        stage = torch.zeros(front + n + 256 // x.element_size(), dtype=x.dtype, device=self.device)
+        xin = stage[front:front + n]
+        xin.copy_(x.reshape(-1))
+        return xin
+
     def debug_layer(self, layer, x=None, res=None, scale=None, shift=None, pmap=None, feat=None, stats=False, active=None, skip_k=0):
         """Test hook (pp_debug_layer): ONE layer of the committed plan -- index 0 .. 19 of layer_tilings(), with the kernel, tiling and
         weight image reported there -- on caller tensors.  x [nb,cin,hin,win] (or, layer 0 only, pmap i32[nb,gx,gy] + feat
@@ -1196,12 +1207,7 @@ class Engine:
             xin = None
         else:
             x = _chk(x, in_dt, (nb, cin, hin, win), "debug_layer: x")
-            # the Winograd tilings fetch aligned pieces that start in front of a row and end behind it: stage the input with the
-            # padding the context's own buffers have
-            front, per = 128, cin * hin * win
-            stage = torch.zeros(front + nb * per + nb * cin * (hin + win + 1) + 64, dtype=in_dt, device=self.device)
-            xin = stage[front:front + nb * per]
-            xin.copy_(x.reshape(-1))
+            xin = self._stage_in(x)
         if res is not None:
             if kind != 0:
                 raise ValueError("debug_layer: only a convolution takes a residual")
@@ -1264,10 +1270,7 @@ class Engine:
             scale = _chk(scale, torch.float32, shp, "debug_head_cls: scale")
             shift = _chk(shift, torch.float32, shp, "debug_head_cls: shift")
         self._on_device("debug_head_cls", ((x, "x"), (scale, "scale"), (shift, "shift")))
-        front, per = 128, cin * self.H * self.W  # staged with the padding debug_layer gives its input
-        stage = torch.zeros(front + nb * per + nb * cin * (self.H + self.W + 1) + 64, dtype=torch.float32, device=self.device)
-        xin = stage[front:front + nb * per]
-        xin.copy_(x.reshape(-1))
+        xin = self._stage_in(x)  # staged with the padding debug_layer gives its input
         out = self._t((nb, self.A, 1), torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_debug_head_cls(self.ctx, nb, _ptr(xin), pre_mode, _ptr(scale), _ptr(shift), _ptr(out), _stream()), self.ctx,

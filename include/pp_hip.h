@@ -171,8 +171,11 @@ int pp_fetch_frame_tensor(pp_ctx* ctx, int frame, int kind, void* dst, void* str
  *         empty) and feat f32[nb][max_voxels][64] (PFN rows), which runs the tiling's sparse twin.
  *   stats (NULL or f64[nb][cout][2]): per frame and output channel the sum and the sum of squares the epilogue accumulates for the
  *         consumer's InstanceNorm (of the fp32 values, before a 16-bit store), summed over the replicated accumulators; not the head.
- * `in` must be readable 256 bytes in front of its first and (hin + win + 1) * 4 * cin * nb bytes behind its last element (the
- * Winograd tilings fetch whole aligned pieces; the context's own buffers are padded the same way).  Every argument is checked
+ * `in` must be readable 256 bytes in front of its first and 256 bytes behind its last element, whatever its element type: the
+ * wino6 tilings fetch a patch row as whole 16-byte pieces, which start one float in front of a map row and end up to 63 floats behind
+ * it (the context's own buffers carry at least this slack).  Every other kernel family, the 16-bit ones on fp16 tensors included,
+ * keeps the fetches of its masked-out lanes inside `in`.  What lies in that slack, and anywhere else outside the tensors handed in,
+ * influences no result (tests/test_layer_arena_gpu.py).  No other argument needs slack.  Every argument is checked
  * before anything is launched (PP_E_ARG; PP_E_STATE before pp_commit_weights).  The call changes nothing a later pass reads; the
  * first call that asks for statistics allocates their scratch accumulators (synchronous), later calls only enqueue. */
 int pp_debug_layer(pp_ctx* ctx, int layer, int nb, const void* in, const void* res, int pre_mode, const float* scale, const float* shift,

@@ -93,28 +93,41 @@ def check_exact(eng, sd, index, grid, pre, with_res, tally=None, mode=None):
             eng.debug_layer(index, **args)
         return t["tiling"]
     if t["kind"] == 2:
-        got = eng.debug_layer(index, **args)
-        torch.cuda.synchronize()
-        for g, ref, name in zip(got, c["ref"], ("cls", "box", "dir")):
-            assert np.array_equal(host(g), ref.astype(np.float32)), what + (name,)
+        got, st = eng.debug_layer(index, **args), None
     else:
         got, st = eng.debug_layer(index, stats=True, **args)
-        torch.cuda.synchronize()
-        assert got.dtype == out_dt
-        want = R.round_fp16(c["ref"]).astype(np.float32) if out_dt == torch.float16 else c["ref"].astype(np.float32)
-        st = st.cpu().numpy()
-        if t["wino"] == 6:  # Winograd F(4x4,3x3): not exact on any data (module docstring)
-            bound = R.winograd4_bound(R.prologue(c["x"], c["scale"], c["shift"]), R.layer_weights(sd, index))
-            err = np.abs(host(got).astype(np.float64) - c["ref"])
-            assert (err <= bound).all(), what + (float((err / np.maximum(bound, 1e-300)).max()),)
-            assert (np.abs(st[..., 0] - c["stats"][..., 0]) <= bound.sum(axis=(2, 3)) + SUMSQ_REL * np.abs(c["ref"]).sum(axis=(2, 3))).all(), what
-            return t["tiling"]
-        assert np.array_equal(host(got), want), what + (int((host(got) != want).sum()), float(np.abs(host(got) - want).max()))
-        assert np.array_equal(st[..., 0], c["stats"][..., 0]), what + ("sum",)
-        assert (np.abs(st[..., 1] - c["stats"][..., 1]) <= SUMSQ_REL * c["stats"][..., 1]).all(), what + ("sum of squares",)
-    if tally is not None:
+    torch.cuda.synchronize()
+    if compare_exact(t, c, sd, index, out_dt, got, st, what) and tally is not None:
         tally["exact"].setdefault(mode, set()).add((grid, index, t["tiling"]))
     return t["tiling"]
+
+
+_BOUNDS = {}
+
+
+def compare_exact(t, c, sd, index, out_dt, got, st, what):
+    """The comparison half of check_exact (test_layer_arena_gpu.py calls it on what it launched itself): the output(s) `got` and the
+    statistics `st` of tiling entry `t` on exact case `c` against the case's reference.  True: bit for bit; False: a Winograd
+    F(4x4,3x3) layer, held to its componentwise bound."""
+    if t["kind"] == 2:
+        for g, ref, name in zip(got, c["ref"], ("cls", "box", "dir")):
+            assert np.array_equal(host(g), ref.astype(np.float32)), what + (name,)
+        return True
+    assert got.dtype == out_dt
+    want = R.round_fp16(c["ref"]).astype(np.float32) if out_dt == torch.float16 else c["ref"].astype(np.float32)
+    st = st.cpu().numpy()
+    if t["wino"] == 6:  # Winograd F(4x4,3x3): not exact on any data (module docstring)
+        if id(c) not in _BOUNDS:  # computed once per (shared, read-only) case; the entry keeps the case alive, so its id stays its own
+            _BOUNDS[id(c)] = (c, R.winograd4_bound(R.prologue(c["x"], c["scale"], c["shift"]), R.layer_weights(sd, index)))
+        bound = _BOUNDS[id(c)][1]
+        err =np.abs(host(got).astype(np.float64) - c["ref"])
+        assert (err <= bound).all(), what + (float((err / np.maximum(bound, 1e-300)).max()),)
+        assert (np.abs(st[..., 0] - c["stats"][..., 0]) <= bound.sum(axis=(2, 3)) + SUMSQ_REL * np.abs(c["ref"]).sum(axis=(2, 3))).all(), what
+        return False
+    assert np.array_equal(host(got), want), what + (int((host(got) != want).sum()), float(np.abs(host(got) - want).max()))
+    assert np.array_equal(st[..., 0], c["stats"][..., 0]), what + ("sum",)
+    assert (np.abs(st[..., 1] - c["stats"][..., 1]) <= SUMSQ_REL * c["stats"][..., 1]).all(), what + ("sum of squares",)
+    return True
 
 
 # ------------------------------------------------------------------ (a) exact cases
