@@ -1,17 +1,17 @@
-// What block_train.hip (the fp32 Resnet unit backward) and block_train16.hip (its 16-bit operand twins) share: the workspace of a
-// context and its budget rules, the K ranges of a wgrad launch and the reduction of the dw partials.  One copy, so that both files
-// cut K and sum the partials the same way.
+// The Resnet unit backward's own part of the training host side, shared by block_train.hip (fp32) and block_train16.hip (its 16-bit
+// operand twins): the workspace of a context and its budget rules, and the one check and plan of the family.  The fp32 driver
+// (unit_run) is block_train.hip's; the twin keeps a driver of its own (its pack, norm kernels and images differ) over the same check,
+// plan and chunk walk.  What the three families share (workspace growth, the padded-plane geometry, the frame chunks and K ranges, the
+// reduction of the dw partials) is train_host.h's.
 #pragma once
 #include "pp_common.h"
+#include "train_planes.h"
+#include "train_host.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr size_t WS_BUDGET = (size_t)256 << 20; // bytes of one frame's a + dz planes: a larger map is refused
 constexpr size_t WS_CHUNK = (size_t)1 << 30;    // bytes of the planes of one chunk of frames: larger batches run in frame chunks
-constexpr int DW_WGS = 512;                     // workgroups a wgrad launch aims at (output tiles x K ranges)
-constexpr int DW_MAX_SPLIT = 256;
 constexpr int DA_BLOCK = 64;                    // k-terms that k_unit_dgrad sums in one accumulator before adding the block to the total
 
 struct block_ws {
@@ -29,50 +29,80 @@ struct block_ws {
     int32_t* pmap[16] = {};
 };
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-template <typename T>
-int grow(pp_ctx* ctx, T** buf, size_t* have, size_t need)
-{
-    if (need <= *have) return 0;
-    PP_HIP(hipDeviceSynchronize()); // a kernel of an earlier call, on this stream or another, may still read the old buffer
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *have = 0;
-    PP_HIP(hipMalloc((void**)buf, need * sizeof(T)));
-    *have = need;
-    return 0;
-}
-
-// partials added in index order, four loads in flight: 64-thread workgroups, so that a 64 x 64 weight spreads over all compute units
-__global__ void __launch_bounds__(64) k_unit_dw_reduce(const float* __restrict__ part, int G, int n, float* __restrict__ dw)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const float* p = part + i;
-    double s = 0.0;
-    int g = 0;
-    for (; g + 3 < G; g += 4) {
-        const float a = p[(size_t)g * n], b = p[(size_t)(g + 1) * n], c = p[(size_t)(g + 2) * n], d = p[(size_t)(g + 3) * n];
-        s += (double)a; s += (double)b; s += (double)c; s += (double)d;
-    }
-    for (; g < G; ++g) s += (double)p[(size_t)g * n];
-    dw[i] = (float)s;
-}
-
 inline block_ws* workspace(pp_ctx* ctx)
 {
     if (!ctx->blk) ctx->blk = new block_ws();
     return (block_ws*)ctx->blk;
 }
 
-// K ranges of one wgrad launch over `nchunks` chunks of positions (16 per chunk in the fp32 kernels, 32 in the 16-bit ones)
-inline void dw_ranges(int tiles, int nchunks, int* splits, int* cps)
+// ---- one call: its shape, its arguments (the ones a form does not take stay null / 0) ----------------------------------------------------
+struct unit_shape { int C, h, w; };
+struct unit_args {
+    const float *u = nullptr, *wgt = nullptr, *scale = nullptr, *shift = nullptr, *mean = nullptr, *var = nullptr, *dy = nullptr, *dskip = nullptr;
+    int nb = 0;
+    float *dw = nullptr, *du = nullptr;
+    double *dscale = nullptr, *dshift = nullptr;
+    int chunk_frames = 0;
+    hipStream_t stream = nullptr;
+};
+
+// The checks of every entry of the family, reported as "<entry>: ...", in the order the fp32 entries test them.  `what` selects the ones
+// that read the shape alone (UNIT_CHK_SHAPE: pp_unit_backward_path runs just these, pp_unit_backward_mp runs them first), the ones
+// that read the tensors and nb, and the budget of the fp32 planes (the 16-bit images have a budget of their own, which decides the
+// path).  Only the InstanceNorm form refuses a BatchNorm context; the affine and batch forms add their own pointers to the null test;
+// the tests of dscale / dshift and chunk_frames pass where a form leaves those null / 0.
+enum { UNIT_CHK_SHAPE = 1, UNIT_CHK_TENSORS = 2, UNIT_CHK_BUDGET = 4, UNIT_CHK_ALL = 7 };
+inline int unit_check(pp_ctx* ctx, const char* entry, int what, norm_form form, const unit_shape& s, const unit_args& a)
 {
-    int sp = DW_WGS / tiles;
-    sp = sp < 1 ? 1 : sp > DW_MAX_SPLIT ? DW_MAX_SPLIT : sp;
-    if (sp > nchunks) sp = nchunks;
-    *cps = (nchunks + sp - 1) / sp;
-    *splits = (nchunks + *cps - 1) / *cps;
+    const bool shape = what & UNIT_CHK_SHAPE, tensors = what & UNIT_CHK_TENSORS;
+    if (shape && form == NORM_INSTANCE && ctx->cfg.norm_kind != 0)
+        return train_fail(ctx, entry, "the InstanceNorm backbone only (BatchNorm has no backward here)");
+    if (shape && s.C != 64 && s.C != 128 && s.C != 256) return train_fail(ctx, entry, "C must be 64, 128 or 256");
+    if (tensors) {
+        if (!a.u || !a.wgt || !a.dy || !a.dw || (form != NORM_INSTANCE && (!a.scale || !a.shift)) || (form == NORM_BATCH && (!a.mean || !a.var)))
+            return train_fail(ctx, entry, "null pointer");
+        if (!a.dscale != !a.dshift) return train_fail(ctx, entry, "dscale and dshift go together");
+        if (!a.du && a.dscale) return train_fail(ctx, entry, "dscale and dshift need du (they are sums over the dgrad product)");
+        if (a.nb < 1 || a.nb > ctx->max_batch) return train_fail(ctx, entry, "nb must be 1 .. max_batch");
+        if (a.chunk_frames < 0) return train_fail(ctx, entry, "chunk_frames must be >= 0");
+    }
+    if (shape && (s.h < 1 || s.w < 1 || (int64_t)s.h * s.w < 2)) return train_fail(ctx, entry, "h, w >= 1 and h w >= 2");
+    if (tensors) {
+        if (!aligned16(a.wgt)) return train_fail(ctx, entry, "w must be 16-byte aligned");
+        if (((uintptr_t)a.u | (uintptr_t)a.scale | (uintptr_t)a.shift | (uintptr_t)a.mean | (uintptr_t)a.var | (uintptr_t)a.dy | (uintptr_t)a.dskip |
+             (uintptr_t)a.dw | (uintptr_t)a.du) & 3)
+            return train_fail(ctx, entry, "tensors must be 4-byte aligned");
+        if (((uintptr_t)a.dscale | (uintptr_t)a.dshift) & 7) return train_fail(ctx, entry, "dscale / dshift must be 8-byte aligned");
+    }
+    if ((what & UNIT_CHK_BUDGET) && 2 * (uint64_t)s.C * padded_plane(s.h, s.w).elems * sizeof(float) > WS_BUDGET)
+        return train_fail(ctx, entry, "map too large (one frame's planes exceed the 256 MB workspace)");
+    return 0;
+}
+
+// ---- everything of a call that is a function of the shapes (and, for the twin, the mode) alone: the planes `g` (padded_plane for fp32,
+// planes16 for the 16-bit images), the frames of a chunk at frame_bytes each, the wgrad tiles (TN columns x tile_rows rows) and K ranges
+// over chunks of `kpos` positions (16 in the fp32 kernels, 32 in the 16-bit ones), the segments of the streaming passes over the tight
+// plane (S, L: statistics, norm backward) and the padded one (SP, LP: pack) -------------------------------------------------------------
+struct unit_plan {
+    unit_shape s;
+    pad_geom g;
+    int N, fc, TN, NC, cpf, Gp, nw, S, L, SP, LP;
+    size_t pf_elems; // one frame's plane set [C][PS], elements
+    dw_walk walk;
+};
+inline unit_plan unit_make_plan(const pp_ctx* ctx, const unit_shape& s, int nb, int chunk_frames, const pad_geom& g, size_t frame_bytes, int kpos,
+                                int tile_rows)
+{
+    unit_plan p;
+    p.s = s; p.g = g; p.N = s.h * s.w;
+    p.pf_elems = (size_t)s.C * g.PS;
+    p.fc = pp_chunk_frames(ctx, WS_CHUNK, frame_bytes, nb, chunk_frames);
+    p.TN = s.C >= 128 ? 128 : 192; // columns of a wgrad tile
+    p.NC = 9 * s.C; p.cpf = (g.PP + kpos - 1) / kpos; p.nw = s.C * p.NC;
+    p.walk = dw_walk{nb, p.fc, (p.NC / p.TN) * (s.C / tile_rows), p.cpf, DW_WGS};
+    p.Gp = count_partials(p.walk);
+    p.S = plane_segs(p.N); p.L = seg_len(p.N, p.S); p.SP = plane_segs(g.PS); p.LP = seg_len(g.PS, p.SP);
+    return p;
 }
 
 } // namespace

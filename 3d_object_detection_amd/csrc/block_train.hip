@@ -12,7 +12,7 @@
 //   k_unit_pack    per (frame, c, slice): the segments' sums added in index order, mean / rstd, a and dz into the padded planes (halo and
 //                  guards rewritten)
 //   k_unit_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      M = C, N = 9 C, K = frames x PP, split into ranges
-//   k_unit_dw_reduce  partials summed in index order (double, rounded once)
+//   k_dw_reduce    partials summed in index order (double, rounded once; train_host.h, shared by the three families)
 //   k_unit_dgrad   da[ci][P] = sum_{t, co} wT[t][co][ci] dz[co][P - off_t]           M = C, N = PP, K = 9 C, summed in blocks of DA_BLOCK
 //   k_plane_gstats per (frame, c, segment): sum Gr, sum Gr xhat in fp64 over one segment of da
 //   k_unit_norm    per (frame, c, segment): the segments' sums added in index order, du = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) (+ dskip)
@@ -28,7 +28,8 @@
 // products, k_affine_unit_du and k_affine_reduce; pp_unit_backward itself stays the InstanceNorm backbone's.
 // pp_unit_backward_bn is that unit behind a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_unit_sums behind the
 // dgrad of every chunk, then k_bn_coef and one in-place k_bn_unit_du over all frames.
-// block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp); what both share is in block_train.h.
+// block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp); what both share (the check and the plan of a call) is in block_train.h,
+// what all three training families share in train_host.h.  The three entries are thin wrappers over unit_check and unit_run.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -416,80 +417,98 @@ int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream)
     return 0;
 }
 
+namespace {
+
+// ---- the one fp32 driver of the family.  The forms differ in the passes around the two products: InstanceNorm runs the statistics and
+// k_unit_pack ahead of them and the two passes of the norm backward behind the dgrad; the affine form k_affine_unit_pack and one pass
+// behind the dgrad, with k_affine_reduce behind the chunks; the batch form the affine pack, the sums behind the dgrad of every chunk (raw
+// da -> du), and behind the chunks k_bn_coef and one in-place k_bn_unit_du over all frames --------------------------------------------------
+int unit_run(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& a)
+{
+    const int C = s.C, h = s.h, w = s.w, nb = a.nb;
+    hipStream_t stream = a.stream;
+    PP_HIP(hipSetDevice(ctx->device));
+    block_ws* ws = workspace(ctx);
+    const pad_geom g = padded_plane(h, w);
+    const unit_plan p = unit_make_plan(ctx, s, nb, a.chunk_frames, g, 2 * (size_t)C * g.PS * sizeof(float), 16, 64);
+    const int wp = g.wp, PP = g.PP, G = g.G, PS = g.PS, N = p.N, fc = p.fc, S = p.S, L = p.L, SP = p.SP, LP = p.LP;
+    // stm: a chunk's mean / rstd (InstanceNorm) or k_bn_coef's coefficients (batch); pst: a chunk's segment sums (InstanceNorm) or
+    // every frame's, reduced or pooled once behind the chunks
+    const size_t stm_elems = form == NORM_INSTANCE ? (size_t)fc * C * 2 : (size_t)C * 4;
+    const size_t pst_elems = (size_t)(form == NORM_INSTANCE ? fc : nb) * C * SEG_MAX * 2;
+    int rc;
+    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * p.pf_elems)) ||
+        (form != NORM_AFFINE && (rc = grow(ctx, &ws->stm, &ws->stm_elems, stm_elems))) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, pst_elems)) ||
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)p.Gp * p.nw)) ||
+        (a.du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)p.nw))))
+        return rc;
+    float* ap = ws->planes;
+    float* dzp = ws->planes + (size_t)fc * p.pf_elems;
+    if (a.du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, a.wgt, ws->wT, C);
+    for_chunks(p.walk, [&](const dw_chunk& c) {
+        const int fn = c.fn;
+        const size_t o = (size_t)c.f0 * C * N;
+        if (form == NORM_INSTANCE) {
+            hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->pst, C, N, L, S);
+            hipLaunchKernelGGL(k_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, a.u + o, a.dy + o, ap, dzp, ws->stm, ws->pst, C, h, w, wp, G, PP, PS, S,
+                               LP);
+        } else {
+            hipLaunchKernelGGL(k_affine_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, a.u + o, a.dy + o, ap, dzp, a.scale, a.shift, C, h, w, wp, G,
+                               PP, PS, LP);
+        }
+        const dim3 gd(p.NC / p.TN, C / 64, c.sp);
+        if (C >= 128)
+            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase);
+        else
+            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase);
+        if (!a.du) return;
+        float* duc = a.du + o;
+        if (C == 64)
+            hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+        else if (C == 128)
+            hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+        else
+            hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
+        if (form == NORM_INSTANCE) {
+            hipLaunchKernelGGL(k_plane_gstats, dim3(C, fn, S), dim3(256), 0, stream, ap, duc, ws->pst, C, w, wp, G, PS, N, L, S);
+            hipLaunchKernelGGL(k_unit_norm, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ap, ws->stm, ws->pst, a.dskip ? a.dskip + o : nullptr, duc, C,
+                               h, w, wp, G, PS, L, S);
+        } else if (form == NORM_AFFINE) {
+            hipLaunchKernelGGL(k_affine_unit_du, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ap, a.scale, a.dskip ? a.dskip + o : nullptr, duc,
+                               ws->pst + (size_t)c.f0 * C * S * 2, C, w, wp, G, PS, N, L, S);
+        } else {
+            hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
+                               C, N, L, S);
+        }
+    });
+    launch_dw_reduce(ws->part, p.Gp, p.nw, a.dw, stream);
+    if (form == NORM_AFFINE && a.dscale)
+        hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, a.dscale, a.dshift);
+    if (form == NORM_BATCH && a.du) {
+        hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, a.mean, a.var, (double)nb * (double)N, ws->stm,
+                           a.dscale, a.dshift);
+        hipLaunchKernelGGL(k_bn_unit_du, dim3(C, nb, S), dim3(256), 0, stream, a.u, a.scale, a.shift, ws->stm, a.dskip, a.du, C, N, L);
+    }
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+int unit_entry(pp_ctx* ctx, const char* entry, norm_form form, const unit_shape& s, const unit_args& a)
+{
+    if (!ctx) return PP_E_ARG;
+    if (int rc = unit_check(ctx, entry, UNIT_CHK_ALL, form, s, a)) return rc;
+    return unit_run(ctx, form, s, a);
+}
+
+} // namespace
+
 extern "C" int pp_unit_backward(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip, int nb,
                                 float* dw, float* du, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
-    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: C must be 64, 128 or 256");
-    if (!u || !wgt || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: null pointer");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: nb must be 1 .. max_batch");
-    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: h, w >= 1 and h w >= 2");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: w must be 16-byte aligned");
-    if (((uintptr_t)u | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw | (uintptr_t)du) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: tensors must be 4-byte aligned");
-    // padded plane: guards of G zeros around the (h + 2) x wp image
-    const int64_t wp64 = (int64_t)w + 2, PP64 = ((int64_t)h + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
-    if (2 * (uint64_t)C * (uint64_t)PS64 * sizeof(float) > WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: map too large (one frame's planes exceed the 256 MB workspace)");
-    const int wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64, N = h * w;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    block_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: functions of the shapes alone
-    const size_t pf_elems = (size_t)C * PS;
-    const int fc = pp_chunk_frames(ctx, WS_CHUNK, 2 * pf_elems * sizeof(float), nb, 0);
-    const int TN = C >= 128 ? 128 : 192; // columns of a wgrad tile: k_unit_wgrad<4, 2> or <3, 4>
-    const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = C * NC;
-    // segments of the streaming passes: over the tight plane (statistics, norm backward) and over the padded one (pack)
-    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)fc * C * 2)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)fc * C * SEG_MAX * 2)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
-        return rc;
-    float* ap = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * pf_elems;
-    if (du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, C);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t o = (size_t)f0 * C * N;
-        hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->pst, C, N, L, S);
-        hipLaunchKernelGGL(k_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, ap, dzp, ws->stm, ws->pst, C, h, w, wp, G, PP, PS, S, LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, C / 64, sp);
-        if (C >= 128)
-            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        else
-            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (du) {
-            float* duc = du + o;
-            if (C == 64)
-                hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            else if (C == 128)
-                hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            else
-                hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            hipLaunchKernelGGL(k_plane_gstats, dim3(C, fn, S), dim3(256), 0, stream, ap, duc, ws->pst, C, w, wp, G, PS, N, L, S);
-            hipLaunchKernelGGL(k_unit_norm, dim3(C, fn, S), dim3(256), 0, stream, u + o, ap, ws->stm, ws->pst, dskip ? dskip + o : nullptr, duc, C,
-                               h, w, wp, G, PS, L, S);
-        }
-    }
-    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
+    unit_args a;
+    a.u = u; a.wgt = wgt; a.dy = dy; a.dskip = dskip; a.nb = nb; a.dw = dw; a.du = du; a.stream = (hipStream_t)stream_;
+    return unit_entry(ctx, "pp_unit_backward", NORM_INSTANCE, unit_shape{C, h, w}, a);
 }
 
 // pp_unit_backward with a per-channel affine for the norm: the pack without statistics, the same two products over the same planes, K
@@ -498,75 +517,10 @@ extern "C" int pp_unit_backward_affine(pp_ctx* ctx, int C, int h, int w, const f
                                        const float* dy, const float* dskip, int nb, float* dw, float* du, double* dscale, double* dshift,
                                        void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: C must be 64, 128 or 256");
-    if (!u || !wgt || !scale || !shift || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: null pointer");
-    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: dscale and dshift go together");
-    if (!du && dscale) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: dscale and dshift need du (they are sums over the dgrad product)");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: nb must be 1 .. max_batch");
-    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: h, w >= 1 and h w >= 2");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: w must be 16-byte aligned");
-    if (((uintptr_t)u | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw | (uintptr_t)du) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: tensors must be 4-byte aligned");
-    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: dscale / dshift must be 8-byte aligned");
-    const int64_t wp64 = (int64_t)w + 2, PP64 = ((int64_t)h + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
-    if (2 * (uint64_t)C * (uint64_t)PS64 * sizeof(float) > WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_affine: map too large (one frame's planes exceed the 256 MB workspace)");
-    const int wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64, N = h * w;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    block_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: as pp_unit_backward
-    const size_t pf_elems = (size_t)C * PS;
-    const int fc = pp_chunk_frames(ctx, WS_CHUNK, 2 * pf_elems * sizeof(float), nb, 0);
-    const int TN = C >= 128 ? 128 : 192;
-    const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = C * NC;
-    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * C * SEG_MAX * 2)) || // every frame's segment sums: reduced once, behind the chunks
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
-        return rc;
-    float* ap = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * pf_elems;
-    if (du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, C);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t o = (size_t)f0 * C * N;
-        hipLaunchKernelGGL(k_affine_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, ap, dzp, scale, shift, C, h, w, wp, G, PP, PS, LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, C / 64, sp);
-        if (C >= 128)
-            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        else
-            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (du) {
-            float* duc = du + o;
-            if (C == 64)
-                hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            else if (C == 128)
-                hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            else
-                hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            hipLaunchKernelGGL(k_affine_unit_du, dim3(C, fn, S), dim3(256), 0, stream, u + o, ap, scale, dskip ? dskip + o : nullptr, duc,
-                               ws->pst + (size_t)f0 * C * S * 2, C, w, wp, G, PS, N, L, S);
-        }
-    }
-    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, dscale, dshift);
-    PP_HIP(hipGetLastError());
-    return 0;
+    unit_args a;
+    a.u = u; a.wgt = wgt; a.scale = scale; a.shift = shift; a.dy = dy; a.dskip = dskip; a.nb = nb; a.dw = dw; a.du = du;
+    a.dscale = dscale; a.dshift = dshift; a.stream = (hipStream_t)stream_;
+    return unit_entry(ctx, "pp_unit_backward_affine", NORM_AFFINE, unit_shape{C, h, w}, a);
 }
 
 // pp_unit_backward_affine behind a train-mode BatchNorm: (scale, shift) are the fold of the batch statistics (mean, var) the forward
@@ -577,82 +531,10 @@ extern "C" int pp_unit_backward_bn(pp_ctx* ctx, int C, int h, int w, const float
                                    const float* mean, const float* var, const float* dy, const float* dskip, int nb, float* dw, float* du,
                                    double* dscale, double* dshift, int chunk_frames, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: C must be 64, 128 or 256");
-    if (!u || !wgt || !scale || !shift || !mean || !var || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: null pointer");
-    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: dscale and dshift go together");
-    if (!du && dscale) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: dscale and dshift need du (they are sums over the dgrad product)");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: nb must be 1 .. max_batch");
-    if (chunk_frames < 0) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: chunk_frames must be >= 0");
-    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: h, w >= 1 and h w >= 2");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: w must be 16-byte aligned");
-    if (((uintptr_t)u | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw |
-         (uintptr_t)du) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: tensors must be 4-byte aligned");
-    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: dscale / dshift must be 8-byte aligned");
-    const int64_t wp64 = (int64_t)w + 2, PP64 = ((int64_t)h + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
-    if (2 * (uint64_t)C * (uint64_t)PS64 * sizeof(float) > WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_bn: map too large (one frame's planes exceed the 256 MB workspace)");
-    const int wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64, N = h * w;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    block_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: as pp_unit_backward, the chunk capped by chunk_frames
-    const size_t pf_elems = (size_t)C * PS;
-    const int fc = pp_chunk_frames(ctx, WS_CHUNK, 2 * pf_elems * sizeof(float), nb, chunk_frames);
-    const int TN = C >= 128 ? 128 : 192;
-    const int NC = 9 * C, tiles = (NC / TN) * (C / 64), cpf = (PP + 15) / 16;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = C * NC;
-    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, 2 * (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)C * 4)) || // k_bn_coef's coefficients
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * C * SEG_MAX * 2)) || // every frame's segment sums: pooled once, behind the chunks
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (du && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
-        return rc;
-    float* ap = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * pf_elems;
-    if (du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, C);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t o = (size_t)f0 * C * N;
-        hipLaunchKernelGGL(k_affine_unit_pack, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, ap, dzp, scale, shift, C, h, w, wp, G, PP, PS, LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, C / 64, sp);
-        if (C >= 128)
-            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        else
-            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (du) {
-            float* duc = du + o;
-            if (C == 64)
-                hipLaunchKernelGGL(k_unit_dgrad<1>, dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            else if (C == 128)
-                hipLaunchKernelGGL(k_unit_dgrad<2>, dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            else
-                hipLaunchKernelGGL(k_unit_dgrad<4>, dim3(pp_div_up(PP, 32), 1, fn), dim3(256), 0, stream, ws->wT, dzp, duc, C, h, w, wp, G, PP, PS);
-            hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, u + o, duc, scale, shift, ws->pst + (size_t)f0 * C * S * 2, C, N, L,
-                               S);
-        }
-    }
-    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    if (du) {
-        hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, mean, var, (double)nb * (double)N, ws->stm, dscale,
-                           dshift);
-        hipLaunchKernelGGL(k_bn_unit_du, dim3(C, nb, S), dim3(256), 0, stream, u, scale, shift, ws->stm, dskip, du, C, N, L);
-    }
-    PP_HIP(hipGetLastError());
-    return 0;
+    unit_args a;
+    a.u = u; a.wgt = wgt; a.scale = scale; a.shift = shift; a.mean = mean; a.var = var; a.dy = dy; a.dskip = dskip; a.nb = nb; a.dw = dw;
+    a.du = du; a.dscale = dscale; a.dshift = dshift; a.chunk_frames = chunk_frames; a.stream = (hipStream_t)stream_;
+    return unit_entry(ctx, "pp_unit_backward_bn", NORM_BATCH, unit_shape{C, h, w}, a);
 }
 
 extern "C" int pp_update_block_weights(pp_ctx* ctx, int block, const float* const* w, int n, void* stream_)

@@ -10,7 +10,7 @@
 //   k_unit_wgrad16  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      K = frames x PP16 in chunks of 32 positions
 //   k_unit_dgrad16  da[ci][P] = sum_{t, co} wT16[t][ci][co] zT[P - off_t][co]        K = 9 C in steps of 32, blocks of DA_BLOCK = 64
 //   k_plane_gstats_u, k_unit_norm_u  the norm backward with xhat re-evaluated from u (no fp32 image of a is kept)
-//   k_unit_dw_reduce  as in block_train.hip (block_train.h)
+//   k_dw_reduce     as in block_train.hip (train_host.h)
 // Plane layout of the 16-bit images: as the fp32 one, with the row pitch wp16 = w + 2 rounded up to a multiple of 8 (the extra
 // columns are halo zeros), G16 = wp16 + 40 and PS16 = 2 G16 + PP16 multiples of 8, so that a k-step of 8 positions starting at a
 // multiple of 8 is one aligned 16-byte load in dz and stays aligned under a row shift (ky - 1) wp16 in a.  The column shift kx - 1 is
@@ -318,91 +318,67 @@ __global__ void __launch_bounds__(256) k_unit_norm_u(const float* __restrict__ u
 }
 
 
-// geometry of the 16-bit planes
-struct geom16 { int64_t wp, PP, G, PS; };
-inline geom16 planes16(int h, int w)
+// geometry of the 16-bit planes: rows of wp (a multiple of 8) elements, guards of wp + 40
+inline pad_geom planes16(int h, int w)
 {
-    geom16 g;
-    g.wp = ((int64_t)w + 2 + 7) & ~(int64_t)7;
-    g.PP = ((int64_t)h + 2) * g.wp;
-    g.G = g.wp + 40;
-    g.PS = 2 * g.G + g.PP;
-    return g;
+    const int64_t wp = ((int64_t)w + 2 + 7) & ~(int64_t)7, PP = ((int64_t)h + 2) * wp, G = wp + 40, PS = 2 * G + PP;
+    return pad_geom{(int)wp, (int)PP, (int)G, (int)PS, (uint64_t)PS};
 }
 // bytes of one frame's 16-bit images: a, dz and zT, each of `parts` bf16 images
-inline uint64_t frame16_bytes(int parts, int C, const geom16& g) { return (uint64_t)3 * parts * C * (uint64_t)g.PS * sizeof(uint16_t); }
+inline uint64_t frame16_bytes(int parts, int C, const pad_geom& g) { return (uint64_t)3 * parts * C * g.elems * sizeof(uint16_t); }
 
-// the checks of pp_unit_backward that do not depend on the tensors
-int unit_shape_check(pp_ctx* ctx, int C, int h, int w)
-{
-    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
-    if (C != 64 && C != 128 && C != 256) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: C must be 64, 128 or 256");
-    if (h < 1 || w < 1 || (int64_t)h * w < 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: h, w >= 1 and h w >= 2");
-    return 0;
-}
-
+// The twin's driver: the check, the plan, the chunk walk and the reduce are the family's; the pack, the norm kernels and the images are
+// its own.
 template <bool X3>
-int unit_backward16(pp_ctx* ctx, int C, int h, int w, const float* u, const float* wgt, const float* dy, const float* dskip, int nb, float* dw,
-                    float* du, hipStream_t stream)
+int unit_backward16(pp_ctx* ctx, const unit_shape& s, const unit_args& a)
 {
-    const geom16 g = planes16(h, w);
-    const int wp = (int)g.wp, PP = (int)g.PP, G = (int)g.G, PS = (int)g.PS, N = h * w, parts = X3 ? 2 : 1;
+    const int C = s.C, h = s.h, w = s.w, nb = a.nb, parts = X3 ? 2 : 1;
+    hipStream_t stream = a.stream;
+    const pad_geom g = planes16(h, w);
+    const int wp = g.wp, PP = g.PP, G = g.G, PS = g.PS;
     PP_HIP(hipSetDevice(ctx->device));
     block_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: functions of the shapes and the mode alone
-    const size_t pf_elems = (size_t)C * PS;
-    const int fc = pp_chunk_frames(ctx, WS_CHUNK, frame16_bytes(parts, C, g), nb, 0);
-    const int TN = C >= 128 ? 128 : 192, TM = C >= 128 ? 128 : 64; // a wgrad tile: k_unit_wgrad16<4, 4, 2> or <3, 4, 1>
-    const int NC = 9 * C, tiles = (NC / TN) * (C / TM), cpf = (PP + 31) / 32;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = C * NC;
-    const int S = plane_segs(N), L = seg_len(N, S), SP = plane_segs(PS), LG = (PS / 8 + SP - 1) / SP;
-    const size_t pstride = (size_t)fc * pf_elems; // one part of one image over the chunk's frames
+    // a wgrad tile: k_unit_wgrad16<4, 4, 2> (128 x 128) or <3, 4, 1> (64 x 192)
+    const unit_plan p = unit_make_plan(ctx, s, nb, 0, g, frame16_bytes(parts, C, g), 32, C >= 128 ? 128 : 64);
+    const int N = p.N, fc = p.fc, S = p.S, L = p.L, SP = p.SP, LG = (PS / 8 + SP - 1) / SP;
+    const size_t pstride = (size_t)fc * p.pf_elems; // one part of one image over the chunk's frames
     int rc;
     if ((rc = grow(ctx, &ws->img16, &ws->img16_elems, 3 * parts * pstride)) ||
         (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)fc * C * 2)) ||
         (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)fc * C * SEG_MAX * 2)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (du && (rc = grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)parts * nw))))
+        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)p.Gp * p.nw)) ||
+        (a.du && (rc = grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)parts * p.nw))))
         return rc;
     uint16_t* a16 = ws->img16;                       // [part][fc][C][PS]
     uint16_t* z16 = a16 + parts * pstride;           // [part][fc][C][PS]
     uint16_t* zT = z16 + parts * pstride;            // [part][fc][PS][C]
-    if (du) hipLaunchKernelGGL(k_unit_wt16<X3>, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT16, C);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t o = (size_t)f0 * C * N;
-        hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->pst, C, N, L, S);
-        hipLaunchKernelGGL(k_unit_pack16<X3>, dim3(C, fn, SP), dim3(256), 0, stream, u + o, dy + o, a16, z16, ws->stm, ws->pst, C, h, w, wp, G, PP, PS, S,
-                           LG, pstride);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, C / TM, sp);
+    if (a.du) hipLaunchKernelGGL(k_unit_wt16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, a.wgt, ws->wT16, C);
+    for_chunks(p.walk, [&](const dw_chunk& c) {
+        const int fn = c.fn;
+        const size_t o = (size_t)c.f0 * C * N;
+        hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->pst, C, N, L, S);
+        hipLaunchKernelGGL(k_unit_pack16<X3>, dim3(C, fn, SP), dim3(256), 0, stream, a.u + o, a.dy + o, a16, z16, ws->stm, ws->pst, C, h, w, wp, G, PP,
+                           PS, S, LG, pstride);
+        const dim3 gd(p.NC / p.TN, C / (C >= 128 ? 128 : 64), c.sp);
         if (C >= 128)
-            hipLaunchKernelGGL((k_unit_wgrad16<4, 4, 2, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase, pstride);
+            hipLaunchKernelGGL((k_unit_wgrad16<4, 4, 2, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase,
+                               pstride);
         else
-            hipLaunchKernelGGL((k_unit_wgrad16<3, 4, 1, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, cpf, fn * cpf, cps, gbase, pstride);
-        gbase += sp;
-        if (du) {
-            float* duc = du + o;
-            hipLaunchKernelGGL(k_unit_packT16<X3>, dim3(pp_div_up(PS, 64), C / 64, fn), dim3(256), 0, stream, dy + o, zT, C, h, w, wp, G, PP, PS, pstride);
-            if (C == 64)
-                hipLaunchKernelGGL((k_unit_dgrad16<1, X3>), dim3(pp_div_up(PP, 256), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
-            else if (C == 128)
-                hipLaunchKernelGGL((k_unit_dgrad16<2, X3>), dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
-            else
-                hipLaunchKernelGGL((k_unit_dgrad16<4, X3>), dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
-            hipLaunchKernelGGL(k_plane_gstats_u, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->stm, duc, ws->pst, C, N, L, S);
-            hipLaunchKernelGGL(k_unit_norm_u, dim3(C, fn, S), dim3(256), 0, stream, u + o, ws->stm, ws->pst, dskip ? dskip + o : nullptr, duc, C, N, L, S);
-        }
-    }
-    hipLaunchKernelGGL(k_unit_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
+            hipLaunchKernelGGL((k_unit_wgrad16<3, 4, 1, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase,
+                               pstride);
+        if (!a.du) return;
+        float* duc = a.du + o;
+        hipLaunchKernelGGL(k_unit_packT16<X3>, dim3(pp_div_up(PS, 64), C / 64, fn), dim3(256), 0, stream, a.dy + o, zT, C, h, w, wp, G, PP, PS, pstride);
+        if (C == 64)
+            hipLaunchKernelGGL((k_unit_dgrad16<1, X3>), dim3(pp_div_up(PP, 256), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
+        else if (C == 128)
+            hipLaunchKernelGGL((k_unit_dgrad16<2, X3>), dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
+        else
+            hipLaunchKernelGGL((k_unit_dgrad16<4, X3>), dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
+        hipLaunchKernelGGL(k_plane_gstats_u, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->stm, duc, ws->pst, C, N, L, S);
+        hipLaunchKernelGGL(k_unit_norm_u, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->stm, ws->pst, a.dskip ? a.dskip + o : nullptr, duc, C, N, L, S);
+    });
+    launch_dw_reduce(ws->part, p.Gp, p.nw, a.dw, stream);
     PP_HIP(hipGetLastError());
     return 0;
 }
@@ -420,8 +396,7 @@ extern "C" int pp_unit_backward_path(pp_ctx* ctx, int mode, int C, int h, int w)
 {
     if (!ctx) return -PP_E_ARG; // the modes are 0 .. 2, so an error is the negated code
     if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, "pp_unit_backward_path: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
-    int rc = unit_shape_check(ctx, C, h, w);
-    if (rc) return -rc;
+    if (int rc = unit_check(ctx, "pp_unit_backward", UNIT_CHK_SHAPE, NORM_INSTANCE, unit_shape{C, h, w}, unit_args())) return -rc;
     return unit_path(mode, C, h, w);
 }
 
@@ -430,15 +405,13 @@ extern "C" int pp_unit_backward_mp(pp_ctx* ctx, int mode, int C, int h, int w, c
 {
     if (!ctx) return PP_E_ARG;
     if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward_mp: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
-    int rc = unit_shape_check(ctx, C, h, w);
-    if (rc) return rc;
+    const unit_shape s{C, h, w};
+    unit_args a;
+    a.u = u; a.wgt = wgt; a.dy = dy; a.dskip = dskip; a.nb = nb; a.dw = dw; a.du = du; a.stream = (hipStream_t)stream_;
+    // the shape first, under pp_unit_backward's name: it decides the path, and the fp32 path is that entry
+    if (int rc = unit_check(ctx, "pp_unit_backward", UNIT_CHK_SHAPE, NORM_INSTANCE, s, a)) return rc;
     const int path = unit_path(mode, C, h, w);
     if (path == 0) return pp_unit_backward(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, stream_);
-    if (!u || !wgt || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: null pointer");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: nb must be 1 .. max_batch");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: w must be 16-byte aligned");
-    if (((uintptr_t)u | (uintptr_t)dy | (uintptr_t)dskip | (uintptr_t)dw | (uintptr_t)du) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_unit_backward: tensors must be 4-byte aligned");
-    return path == 1 ? unit_backward16<true>(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, (hipStream_t)stream_)
-                     : unit_backward16<false>(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, (hipStream_t)stream_);
+    if (int rc = unit_check(ctx, "pp_unit_backward", UNIT_CHK_TENSORS, NORM_INSTANCE, s, a)) return rc;
+    return path == 1 ? unit_backward16<true>(ctx, s, a) : unit_backward16<false>(ctx, s, a);
 }

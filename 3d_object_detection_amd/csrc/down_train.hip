@@ -18,7 +18,7 @@
 // A plane is cut into plane_segs(elements) segments, a function of the plane size alone (train_planes.h, shared with block_train.hip: one segment up to 16384
 // elements: block 3's 100 x 100 output planes run as one workgroup each, level 0's 400 x 400 as ten).
 //   k_down_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] xp[ci][plane_t][P + off_t]    M = Cout, N = 9 Cin, K = frames x PP in ranges
-//   k_down_dw_reduce  partials summed in index order (double, rounded once)
+//   k_dw_reduce    partials summed in index order (double, rounded once; train_host.h, shared by the three families)
 //   k_down_dgrad   per output parity class (py, px), P the half-resolution position of x[2 r + py][2 c + px]:
 //                  dx[ci][P] = sum_{t in class, co} wT[t][co][ci] dz[co][P + (py & ky == 0) wp + (px & kx == 0)]
 //                  M = Cin, N = PP, K = Cout x {1, 2, 2, 4} taps (even: the centre tap; odd: taps 0 and 2), summed in blocks of DA_BLOCK
@@ -31,6 +31,8 @@
 // of the three norm passes, then the same products and k_affine_reduce; pp_down_backward itself stays the InstanceNorm backbone's.
 // pp_down_backward_bn is that stage in front of a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_down_sums over
 // all frames and k_bn_coef ahead of the chunks, k_bn_down_dz in them.
+// The plane and norm kernels of every form and the family's one check, plan and driver (down_check, down_make_plan, down_run) are
+// down_train.h's, shared with the 16-bit twin; this file holds the fp32 products and the entries, thin wrappers over them.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -45,96 +47,6 @@ __global__ void __launch_bounds__(256) k_down_wt(const float* __restrict__ w, fl
     if (i >= 9 * cin * cout) return;
     const int ci = i % cin, co = (i / cin) % cout, t = i / (cin * cout);
     wT[i] = w[((size_t)co * cin + ci) * 9 + t];
-}
-
-// ---- the stage with a per-channel affine in place of the InstanceNorm (pp_down_backward_affine), z, dy -> dz in the padded plane: grid
-// (Cout, frames, SP) as k_down_norm.  g = dy [fma(z, scale, shift) > 0], the forward prologue's expression; dz = scale g; and the slice's
-// sum g z, sum g in fp64 -> pst[frame][co][slice][2] (every interior element lies in exactly one slice) -----------------------------------
-__global__ void __launch_bounds__(256) k_affine_down_dz(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
-                                                        const float* __restrict__ shift, float* __restrict__ dzp, double* __restrict__ pst, int cout,
-                                                        int ho, int wo, int wp, int G, int PP, int PS, int LP)
-{
-    __shared__ double red[256][2];
-    const int tid = threadIdx.x, N = ho * wo, SP = gridDim.z;
-    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
-    const float* zi = z + pl * N;
-    const float* dp = dy + pl * N;
-    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
-    float* zo = dzp + pl * PS;
-    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    double sgz = 0.0, sg = 0.0;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
-        float v = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, c = P - y * wp;
-            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int i = (y - 1) * wo + c - 1;
-                const float zz = zi[i];
-                const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
-                sgz += (double)g * (double)zz; sg += (double)g;
-                v = sc * g;
-            }
-        }
-        zo[j] = v;
-    }
-    block_sum2(sgz, sg, red);
-    if (tid == 0) { pst[(pl * SP + blockIdx.z) * 2] = sgz; pst[(pl * SP + blockIdx.z) * 2 + 1] = sg; }
-}
-
-// ---- the stage in front of a train-mode BatchNorm (pp_down_backward_bn).  The norm backward needs the sums of ALL frames, and they need
-// only z and dy, so they come first, over every frame at once.  k_bn_down_sums: grid (Cout, frames, S) over the tight plane, g = dy
-// [fma(z, scale, shift) > 0], the segment's sum g z, sum g in fp64 -> pst[frame][co][segment][2].  k_bn_down_dz: grid (Cout, frames, SP) as
-// k_down_norm once k_bn_coef has pooled them: dz = scale ((g - c1) - zhat c2), zhat = (z - mean) r, into the padded plane -------------------
-__global__ void __launch_bounds__(256) k_bn_down_sums(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, double* __restrict__ pst, int cout, int N, int L, int S)
-{
-    __shared__ double red[256][2];
-    const int tid = threadIdx.x;
-    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
-    const float* zi = z + pl * N;
-    const float* dp = dy + pl * N;
-    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
-    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
-    double sgz = 0.0, sg = 0.0;
-    strided4(lo, hi, [&](int i) { return float2{zi[i], dp[i]}; },
-             [&](float2 v) {
-                 if (fmaf(v.x, sc, sh) > 0.f) {
-                     const double g = (double)v.y;
-                     sgz += g * (double)v.x; sg += g;
-                 }
-             });
-    block_sum2(sgz, sg, red);
-    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgz; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
-}
-
-__global__ void __launch_bounds__(256) k_bn_down_dz(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
-                                                    const float* __restrict__ shift, const float* __restrict__ coef, float* __restrict__ dzp, int cout,
-                                                    int ho, int wo, int wp, int G, int PP, int PS, int LP)
-{
-    const int tid = threadIdx.x, N = ho * wo, co = blockIdx.x;
-    const size_t pl = (size_t)blockIdx.y * cout + co;
-    const float* zi = z + pl * N;
-    const float* dp = dy + pl * N;
-    const float sc = scale[co], sh = shift[co];
-    const float c1 = coef[4 * co], c2 = coef[4 * co + 1], meanf = coef[4 * co + 2], rf = coef[4 * co + 3];
-    float* zo = dzp + pl * PS;
-    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
-        float v = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, c = P - y * wp;
-            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int i = (y - 1) * wo + c - 1;
-                const float zz = zi[i];
-                const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
-                const float zhat = (zz - meanf) * rf;
-                v = sc * ((g - c1) - zhat * c2);
-            }
-        }
-        zo[j] = v;
-    }
 }
 
 // ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
@@ -264,6 +176,43 @@ __global__ void __launch_bounds__(256) k_down_dgrad(const float* __restrict__ wT
     }
 }
 
+// the fp32 products of down_run (down_train.h)
+struct down_fp32 {
+    static constexpr int KPOS = 16, WGS = DW_WGS;
+    static int grow_wt(pp_ctx* ctx, down_ws* ws, int nw) { return grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw); }
+    static void pack_wt(const down_plan& p, down_ws* ws, const float* wgt, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wgt, ws->wT, p.s.cin, p.s.cout);
+    }
+    static void wgrad(const down_plan& p, const dw_chunk& c, const float* dzp, const float* xp, float* part, hipStream_t stream)
+    {
+        const int cin = p.s.cin, cout = p.s.cout;
+        const dim3 gd(p.NC / p.TN, cout / 64, c.sp);
+        if (cin >= 128)
+            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PS, p.cpf, c.nchunks, c.cps,
+                               c.gbase);
+        else
+            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PS, p.cpf, c.nchunks, c.cps,
+                               c.gbase);
+    }
+    static void dgrad(const down_plan& p, const down_ws* ws, const float* dzp, float* dx, int fn, hipStream_t stream)
+    {
+        const int cin = p.s.cin, cout = p.s.cout, PP = p.g.PP;
+        if (cin == 64)
+            hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx, cin, cout, p.s.hin, p.s.win,
+                               p.g.wp, p.g.G, PP, p.g.PS);
+        else
+            hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx, cin, cout, p.s.hin, p.s.win,
+                               p.g.wp, p.g.G, PP, p.g.PS);
+    }
+};
+
+int down_entry(pp_ctx* ctx, const char* entry, norm_form form, const down_shape& s, const down_args& a)
+{
+    if (!ctx) return PP_E_ARG;
+    if (int rc = down_check(ctx, entry, DOWN_CHK_ALL, form, s, a)) return rc;
+    return down_run<down_fp32>(ctx, form, s, a);
+}
 
 } // namespace
 
@@ -281,80 +230,9 @@ void pp_down_destroy(pp_ctx* ctx)
 extern "C" int pp_down_backward(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z, const float* dy,
                                 int nb, float* dw, float* dx, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
-    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
-    if (!x || !wgt || !z || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: null pointer");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: nb must be 1 .. max_batch");
-    const int64_t ho64 = ((int64_t)hin + 1) / 2, wo64 = ((int64_t)win + 1) / 2;
-    if (hin < 1 || win < 1 || ho64 * wo64 < 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: hin, win >= 1 and ho wo >= 2");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward: tensors must be 4-byte aligned");
-    // padded half-resolution plane: guards of G zeros around the (ho + 2) x wp image
-    const int64_t wp64 = wo64 + 2, PP64 = (ho64 + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
-    const uint64_t pf64 = (uint64_t)(4 * cin + cout) * (uint64_t)PS64; // one frame's planes, elements
-    if (pf64 * sizeof(float) > DOWN_WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward: map too large (one frame's planes exceed the 256 MB workspace)");
-    const int ho = (int)ho64, wo = (int)wo64, wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    down_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: functions of the shapes alone
-    const size_t pf_elems = (size_t)pf64;
-    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, 0);
-    const int TN = cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_down_wgrad<4, 2> or <3, 4>
-    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = cout * NC;
-    // segments of the streaming passes: over the tight output plane (statistics) and the padded one (dz, the parity planes of x)
-    const int No = ho * wo, S = plane_segs(No), L = seg_len(No, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, 2 * (size_t)fc * cout * SEG_MAX * 2)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
-        return rc;
-    float* xp = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
-    if (dx) hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, cin, cout);
-    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
-        double* pst2 = ws->pst + (size_t)fc * cout * SEG_MAX * 2;
-        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
-        hipLaunchKernelGGL(k_plane_stats, dim3(cout, fn, S), dim3(256), 0, stream, z + oo, ws->pst, cout, No, L, S);
-        hipLaunchKernelGGL(k_dplane_gstats, dim3(cout, fn, S), dim3(256), 0, stream, z + oo, dy + oo, ws->pst, pst2, cout, No, L, S);
-        hipLaunchKernelGGL(k_down_norm, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, dzp, ws->pst, pst2, cout, ho, wo, wp, G, PP, PS, S,
-                           LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, cout / 64, sp);
-        if (cin >= 128)
-            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        else
-            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (dx) {
-            if (cin == 64)
-                hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
-                                   G, PP, PS);
-            else
-                hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
-                                   G, PP, PS);
-        }
-    }
-    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
+    down_args a;
+    a.x = x; a.wgt = wgt; a.z = z; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx; a.stream = (hipStream_t)stream_;
+    return down_entry(ctx, "pp_down_backward", NORM_INSTANCE, down_shape{cin, cout, hin, win}, a);
 }
 
 // pp_down_backward with a per-channel affine for the norm: one pass writes dz and the sums where the sibling runs three, and the two
@@ -363,161 +241,23 @@ extern "C" int pp_down_backward_affine(pp_ctx* ctx, int cin, int cout, int hin, 
                                        const float* scale, const float* shift, const float* dy, int nb, float* dw, float* dx, double* dscale,
                                        double* dshift, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
-    if (!x || !wgt || !z || !scale || !shift || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: null pointer");
-    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: dscale and dshift go together");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: nb must be 1 .. max_batch");
-    const int64_t ho64 = ((int64_t)hin + 1) / 2, wo64 = ((int64_t)win + 1) / 2;
-    if (hin < 1 || win < 1 || ho64 * wo64 < 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: hin, win >= 1 and ho wo >= 2");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: tensors must be 4-byte aligned");
-    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: dscale / dshift must be 8-byte aligned");
-    const int64_t wp64 = wo64 + 2, PP64 = (ho64 + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
-    const uint64_t pf64 = (uint64_t)(4 * cin + cout) * (uint64_t)PS64; // one frame's planes, elements
-    if (pf64 * sizeof(float) > DOWN_WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_affine: map too large (one frame's planes exceed the 256 MB workspace)");
-    const int ho = (int)ho64, wo = (int)wo64, wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    down_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: as pp_down_backward
-    const size_t pf_elems = (size_t)pf64;
-    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, 0);
-    const int TN = cin >= 128 ? 128 : 192;
-    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = cout * NC;
-    const int SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * cout * SEG_MAX * 2)) || // every frame's slice sums: reduced once, behind the chunks
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
-        return rc;
-    float* xp = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
-    if (dx) hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, cin, cout);
-    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
-        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
-        hipLaunchKernelGGL(k_affine_down_dz, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, scale, shift, dzp,
-                           ws->pst + (size_t)f0 * cout * SP * 2, cout, ho, wo, wp, G, PP, PS, LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, cout / 64, sp);
-        if (cin >= 128)
-            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        else
-            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (dx) {
-            if (cin == 64)
-                hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
-                                   G, PP, PS);
-            else
-                hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
-                                   G, PP, PS);
-        }
-    }
-    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(cout, 64)), dim3(64), 0, stream, ws->pst, nb, cout, SP, dscale, dshift);
-    PP_HIP(hipGetLastError());
-    return 0;
+    down_args a;
+    a.x = x; a.wgt = wgt; a.z = z; a.scale = scale; a.shift = shift; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.stream = (hipStream_t)stream_;
+    return down_entry(ctx, "pp_down_backward_affine", NORM_AFFINE, down_shape{cin, cout, hin, win}, a);
 }
 
 // pp_down_backward_affine behind a train-mode BatchNorm: (scale, shift) are the fold of the batch statistics (mean, var) the forward used.
 // Two phases: the sums over every frame and k_bn_coef first, then the frame chunks with k_bn_down_dz and the two products.  chunk_frames
 // > 0 caps the frames of a chunk below the workspace rule (dx and the sums do not depend on it; dw does within fp32 summation error).
 extern "C" int pp_down_backward_bn(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z,
-                                       const float* scale, const float* shift, const float* mean, const float* var, const float* dy, int nb, float* dw, float* dx,
-                                   double* dscale, double* dshift, int chunk_frames, void* stream_)
+                                   const float* scale, const float* shift, const float* mean, const float* var, const float* dy, int nb, float* dw,
+                                   float* dx, double* dscale, double* dshift, int chunk_frames, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
-    if (!x || !wgt || !z || !scale || !shift || !mean || !var || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: null pointer");
-    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: dscale and dshift go together");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: nb must be 1 .. max_batch");
-    if (chunk_frames < 0) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: chunk_frames must be >= 0");
-    const int64_t ho64 = ((int64_t)hin + 1) / 2, wo64 = ((int64_t)win + 1) / 2;
-    if (hin < 1 || win < 1 || ho64 * wo64 < 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: hin, win >= 1 and ho wo >= 2");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: tensors must be 4-byte aligned");
-    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: dscale / dshift must be 8-byte aligned");
-    const int64_t wp64 = wo64 + 2, PP64 = (ho64 + 2) * wp64, G64 = ((wp64 + 1 + 3) & ~(int64_t)3) + 16, PS64 = (2 * G64 + PP64 + 3) & ~(int64_t)3;
-    const uint64_t pf64 = (uint64_t)(4 * cin + cout) * (uint64_t)PS64; // one frame's planes, elements
-    if (pf64 * sizeof(float) > DOWN_WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_bn: map too large (one frame's planes exceed the 256 MB workspace)");
-    const int ho = (int)ho64, wo = (int)wo64, wp = (int)wp64, PP = (int)PP64, G = (int)G64, PS = (int)PS64;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    down_ws* ws = workspace(ctx);
-    // frames per chunk and K ranges: as pp_down_backward, the chunk capped by chunk_frames
-    const size_t pf_elems = (size_t)pf64;
-    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, chunk_frames);
-    const int TN = cin >= 128 ? 128 : 192;
-    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 15) / 16;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        Gp += sp;
-    }
-    const int nw = cout * NC;
-    const int No = ho * wo, S = plane_segs(No), L = seg_len(No, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)nb * cout * SEG_MAX * 2)) || // every frame's segment sums: pooled once, ahead of the chunks
-        (rc = grow(ctx, &ws->coef, &ws->coef_elems, (size_t)cout * 4)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (dx && (rc = grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw))))
-        return rc;
-    float* xp = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
-    if (dx) hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT, cin, cout);
-    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
-    hipLaunchKernelGGL(k_bn_down_sums, dim3(cout, nb, S), dim3(256), 0, stream, z, dy, scale, shift, ws->pst, cout, No, L, S);
-    hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(cout, 64)), dim3(64), 0, stream, ws->pst, nb, cout, S, mean, var, (double)nb * (double)No, ws->coef,
-                       dscale, dshift);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
-        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
-        hipLaunchKernelGGL(k_bn_down_dz, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, scale, shift, ws->coef, dzp, cout, ho, wo, wp, G, PP,
-                           PS, LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(NC / TN, cout / 64, sp);
-        if (cin >= 128)
-            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        else
-            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (dx) {
-            if (cin == 64)
-                hipLaunchKernelGGL(k_down_dgrad<1>, dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
-                                   G, PP, PS);
-            else
-                hipLaunchKernelGGL(k_down_dgrad<2>, dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT, dzp, dx + oi, cin, cout, hin, win, wp,
-                                   G, PP, PS);
-        }
-    }
-    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
+    down_args a;
+    a.x = x; a.wgt = wgt; a.z = z; a.scale = scale; a.shift = shift; a.mean = mean; a.var = var; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.chunk_frames = chunk_frames; a.stream = (hipStream_t)stream_;
+    return down_entry(ctx, "pp_down_backward_bn", NORM_BATCH, down_shape{cin, cout, hin, win}, a);
 }
 
 extern "C" int pp_update_down_weight(pp_ctx* ctx, int level, const float* w, void* stream_)

@@ -206,92 +206,37 @@ __global__ void __launch_bounds__(256) k_down_dgrad16(const uint16_t* __restrict
     }
 }
 
-// geometry of the padded half-resolution planes: pp_down_backward's
-struct dgeom { int64_t ho, wo, wp, PP, G, PS; uint64_t pf; };
-inline dgeom down_planes(int cin, int cout, int hin, int win)
-{
-    dgeom g;
-    g.ho = ((int64_t)hin + 1) / 2; g.wo = ((int64_t)win + 1) / 2;
-    g.wp = g.wo + 2; g.PP = (g.ho + 2) * g.wp; g.G = ((g.wp + 1 + 3) & ~(int64_t)3) + 16; g.PS = (2 * g.G + g.PP + 3) & ~(int64_t)3;
-    g.pf = (uint64_t)(4 * cin + cout) * (uint64_t)g.PS; // one frame's planes, elements
-    return g;
-}
-
-// the checks of pp_down_backward that do not depend on the tensors
-int down_shape_check(pp_ctx* ctx, int cin, int cout, int hin, int win)
-{
-    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: the InstanceNorm backbone only (BatchNorm has no backward here)");
-    if (!((cin == 64 && cout == 64) || (cin == 64 && cout == 128) || (cin == 128 && cout == 256)))
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: (cin, cout) must be (64, 64), (64, 128) or (128, 256)");
-    if (hin < 1 || win < 1 || (((int64_t)hin + 1) / 2) * (((int64_t)win + 1) / 2) < 2)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: hin, win >= 1 and ho wo >= 2");
-    if (down_planes(cin, cout, hin, win).pf * sizeof(float) > DOWN_WS_BUDGET)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: map too large (one frame's planes exceed the 256 MB workspace)");
-    return 0;
-}
-
+// the 16-bit products of down_run (down_train.h): K over 32-position chunks, the bf16 weight image of the dgrad
 template <bool X3>
-int down_backward16(pp_ctx* ctx, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z, const float* dy, int nb,
-                    float* dw, float* dx, hipStream_t stream)
-{
-    const dgeom g = down_planes(cin, cout, hin, win);
-    const int ho = (int)g.ho, wo = (int)g.wo, wp = (int)g.wp, PP = (int)g.PP, G = (int)g.G, PS = (int)g.PS, parts = X3 ? 2 : 1;
-    PP_HIP(hipSetDevice(ctx->device));
-    down_ws* ws = workspace(ctx);
-    // frames per chunk as pp_down_backward; K ranges over 32-position chunks: functions of the shapes alone
-    const size_t pf_elems = (size_t)g.pf;
-    const int fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, pf_elems * sizeof(float), nb, 0);
-    const int TN = cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_down_wgrad16<4, 2> or <3, 4>
-    const int NC = 9 * cin, tiles = (NC / TN) * (cout / 64), cpf = (PP + 31) / 32;
-    int Gp = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps, DW16_WGS);
-        Gp += sp;
+struct down_bf16 {
+    static constexpr int KPOS = 32, WGS = DW16_WGS;
+    static int grow_wt(pp_ctx* ctx, down_ws* ws, int nw) { return grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)(X3 ? 2 : 1) * nw); }
+    static void pack_wt(const down_plan& p, down_ws* ws, const float* wgt, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(k_down_wt16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wgt, ws->wT16, p.s.cin, p.s.cout);
     }
-    const int nw = cout * NC;
-    const int No = ho * wo, S = plane_segs(No), L = seg_len(No, S), SP = plane_segs(PS), LP = seg_len(PS, SP);
-    int rc;
-    if ((rc = grow(ctx, &ws->planes, &ws->planes_elems, (size_t)fc * pf_elems)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, 2 * (size_t)fc * cout * SEG_MAX * 2)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)Gp * nw)) ||
-        (dx && (rc = grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)parts * nw))))
-        return rc;
-    float* xp = ws->planes;
-    float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
-    if (dx) hipLaunchKernelGGL(k_down_wt16<X3>, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wgt, ws->wT16, cin, cout);
-    const size_t nin = (size_t)hin * win, nout = (size_t)ho * wo;
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const size_t oi = (size_t)f0 * cin * nin, oo = (size_t)f0 * cout * nout;
-        double* pst2 = ws->pst + (size_t)fc * cout * SEG_MAX * 2;
-        hipLaunchKernelGGL(k_down_xpack, dim3(cin, fn, SP), dim3(256), 0, stream, x + oi, xp, cin, hin, win, ho, wo, wp, G, PP, PS, LP);
-        hipLaunchKernelGGL(k_plane_stats, dim3(cout, fn, S), dim3(256), 0, stream, z + oo, ws->pst, cout, No, L, S);
-        hipLaunchKernelGGL(k_dplane_gstats, dim3(cout, fn, S), dim3(256), 0, stream, z + oo, dy + oo, ws->pst, pst2, cout, No, L, S);
-        hipLaunchKernelGGL(k_down_norm, dim3(cout, fn, SP), dim3(256), 0, stream, z + oo, dy + oo, dzp, ws->pst, pst2, cout, ho, wo, wp, G, PP, PS, S,
-                           LP);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps, DW16_WGS);
-        const dim3 gd(NC / TN, cout / 64, sp);
+    static void wgrad(const down_plan& p, const dw_chunk& c, const float* dzp, const float* xp, float* part, hipStream_t stream)
+    {
+        const int cin = p.s.cin, cout = p.s.cout;
+        const dim3 gd(p.NC / p.TN, cout / 64, c.sp);
         if (cin >= 128)
-            hipLaunchKernelGGL((k_down_wgrad16<4, 2, X3>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PP, PS, cpf, fn * cpf, cps, gbase);
+            hipLaunchKernelGGL((k_down_wgrad16<4, 2, X3>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PP, p.g.PS, p.cpf,
+                               c.nchunks, c.cps, c.gbase);
         else
-            hipLaunchKernelGGL((k_down_wgrad16<3, 4, X3>), gd, dim3(256), 0, stream, dzp, xp, ws->part, cin, cout, wp, G, PP, PS, cpf, fn * cpf, cps, gbase);
-        gbase += sp;
-        if (dx) {
-            if (cin == 64)
-                hipLaunchKernelGGL((k_down_dgrad16<1, X3>), dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT16, dzp, dx + oi, cin, cout, hin,
-                                   win, wp, G, PP, PS);
-            else
-                hipLaunchKernelGGL((k_down_dgrad16<2, X3>), dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT16, dzp, dx + oi, cin, cout, hin,
-                                   win, wp, G, PP, PS);
-        }
+            hipLaunchKernelGGL((k_down_wgrad16<3, 4, X3>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PP, p.g.PS, p.cpf,
+                               c.nchunks, c.cps, c.gbase);
     }
-    hipLaunchKernelGGL(k_down_dw_reduce, dim3(pp_div_up(nw, 64)), dim3(64), 0, stream, ws->part, Gp, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
-}
+    static void dgrad(const down_plan& p, const down_ws* ws, const float* dzp, float* dx, int fn, hipStream_t stream)
+    {
+        const int cin = p.s.cin, cout = p.s.cout, PP = p.g.PP;
+        if (cin == 64)
+            hipLaunchKernelGGL((k_down_dgrad16<1, X3>), dim3(pp_div_up(PP, 128), 4, fn), dim3(256), 0, stream, ws->wT16, dzp, dx, cin, cout, p.s.hin,
+                               p.s.win, p.g.wp, p.g.G, PP, p.g.PS);
+        else
+            hipLaunchKernelGGL((k_down_dgrad16<2, X3>), dim3(pp_div_up(PP, 64), 4, fn), dim3(256), 0, stream, ws->wT16, dzp, dx, cin, cout, p.s.hin,
+                               p.s.win, p.g.wp, p.g.G, PP, p.g.PS);
+    }
+};
 
 } // namespace
 
@@ -299,8 +244,7 @@ extern "C" int pp_down_backward_path(pp_ctx* ctx, int mode, int cin, int cout, i
 {
     if (!ctx) return -PP_E_ARG; // the modes are 0 .. 2, so an error is the negated code
     if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, "pp_down_backward_path: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
-    int rc = down_shape_check(ctx, cin, cout, hin, win);
-    if (rc) return -rc;
+    if (int rc = down_check(ctx, "pp_down_backward_mp", DOWN_CHK_SHAPE, NORM_INSTANCE, down_shape{cin, cout, hin, win}, down_args())) return -rc;
     return mode; // the 16-bit kernels read the fp32 planes: every shape the fp32 entry takes runs in the mode asked for
 }
 
@@ -310,13 +254,13 @@ extern "C" int pp_down_backward_mp(pp_ctx* ctx, int mode, int cin, int cout, int
     if (!ctx) return PP_E_ARG;
     if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
     if (mode == 0) return pp_down_backward(ctx, cin, cout, hin, win, x, wgt, z, dy, nb, dw, dx, stream_);
-    int rc = down_shape_check(ctx, cin, cout, hin, win);
-    if (rc) return rc;
-    if (!x || !wgt || !z || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: null pointer");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: nb must be 1 .. max_batch");
-    if (!aligned16(wgt)) return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)z | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_down_backward_mp: tensors must be 4-byte aligned");
-    return mode == 1 ? down_backward16<true>(ctx, cin, cout, hin, win, x, wgt, z, dy, nb, dw, dx, (hipStream_t)stream_)
-                     : down_backward16<false>(ctx, cin, cout, hin, win, x, wgt, z, dy, nb, dw, dx, (hipStream_t)stream_);
+    const down_shape s{cin, cout, hin, win};
+    down_args a;
+    a.x = x; a.wgt = wgt; a.z = z; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx; a.stream = (hipStream_t)stream_;
+    int rc; // the shape first, then the tensors
+    if ((rc = down_check(ctx, "pp_down_backward_mp", DOWN_CHK_SHAPE, NORM_INSTANCE, s, a)) ||
+        (rc = down_check(ctx, "pp_down_backward_mp", DOWN_CHK_TENSORS, NORM_INSTANCE, s, a)))
+        return rc;
+    return mode == 1 ? down_run<down_bf16<true>>(ctx, NORM_INSTANCE, s, a) : down_run<down_bf16<false>>(ctx, NORM_INSTANCE, s, a);
 }
+

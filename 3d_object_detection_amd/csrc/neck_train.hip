@@ -10,7 +10,7 @@
 //   k_neck_stats  per (frame, co): sum z, sum z^2, sum Gr, sum Gr z in fp64 over S segments of the channel's N = H W elements
 //   k_neck_dz     mean / rstd / the two backward means from the S partials, dZ = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) over Z
 //   k_neck_dw     dw[ci][r] = sum_{frame, q} x[ci][q] dZ[r][q]  M = Cin, N = R, K = frames x p, split into pixel / frame ranges
-//   k_neck_dw_reduce  partials summed in index order (double, rounded once)
+//   k_dw_reduce   partials summed in index order (double, rounded once; train_host.h, shared by the three families)
 //   k_neck_dx     dx[ci][q] = sum_r w[ci][r] dZ[r][q]           M = Cin, N = p, K = R, summed in blocks of DX_BLOCK rows
 // The three products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory (every operand row is contiguous along
 // the lane's load direction; the sum over K is order-free, so where K is the contiguous direction a lane's four k-steps are one
@@ -22,79 +22,13 @@
 // of k_neck_stats and k_neck_dz, then the same products and k_affine_reduce; pp_neck_backward itself stays the InstanceNorm backbone's.
 // pp_neck_backward_bn is that branch in front of a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_neck_sums
 // per chunk, k_bn_coef, then k_bn_neck_dz and the products per chunk (Z recomputed when there are several).
+// The Z, statistics and dZ kernels of every form and the family's one check, plan and driver (neck_check, neck_make_plan, neck_run) are
+// neck_train.h's, shared with the 16-bit twin; this file holds the fp32 products and the entries, thin wrappers over them.
 #include <cmath>
 #include "pp_common.h"
-#include "train_planes.h" // k_affine_reduce
-
 #include "neck_train.h"
 
 namespace {
-
-// ---- the branch with a per-channel affine in place of the InstanceNorm (pp_neck_backward_affine), grid (S, Cup, frames) as k_neck_dz:
-// g = dy [y > 0], the segment's sum g Z, sum g in fp64 -> st[frame][co][segment][2], and dZ = scale g over Z ------------------------------
-__global__ void __launch_bounds__(256) k_affine_neck_dz(float* __restrict__ Z, const float* __restrict__ y, const float* __restrict__ dy,
-                                                        const float* __restrict__ scale, double* __restrict__ st, int Cup, int coff, int H, int W,
-                                                        int ls, int w, int pld, int R, int seg_len)
-{
-    __shared__ double red[4][2];
-    const int tid = threadIdx.x, co = blockIdx.y, f = blockIdx.z, N = H * W;
-    float* Zf = Z + (size_t)f * R * pld;
-    const size_t plane = ((size_t)f * 320 + coff + co) * N;
-    const float sc = scale[co];
-    const int i0 = blockIdx.x * seg_len, i1 = i0 + seg_len < N ? i0 + seg_len : N;
-    double sgz = 0.0, sg = 0.0;
-    for (int i = i0 + tid; i < i1; i += 256) {
-        const size_t zi = z_index(i, co, W, ls, w, pld);
-        const float g = y[plane + i] > 0.f ? dy[plane + i] : 0.f; // the mask is the caller's y, never a recomputed sign
-        sgz += (double)g * (double)Zf[zi]; sg += (double)g;
-        Zf[zi] = sc * g;
-    }
-    sgz = wave_sum(sgz); sg = wave_sum(sg);
-    if ((tid & 63) == 0) { red[tid >> 6][0] = sgz; red[tid >> 6][1] = sg; }
-    __syncthreads();
-    if (tid < 2) st[(((size_t)f * Cup + co) * gridDim.x + blockIdx.x) * 2 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-}
-
-// ---- the branch in front of a train-mode BatchNorm (pp_neck_backward_bn), grid (S, Cup, frames) as k_neck_dz.  k_bn_neck_sums: g = dy
-// [y > 0], the segment's sum g Z, sum g in fp64 -> st[frame][co][segment][2], Z left as it is.  k_bn_neck_dz, once k_bn_coef has pooled
-// the sums of all frames: dZ = scale ((g - c1) - zhat c2) over Z, zhat = (Z - mean) r ----------------------------------------------------
-__global__ void __launch_bounds__(256) k_bn_neck_sums(const float* __restrict__ Z, const float* __restrict__ y, const float* __restrict__ dy,
-                                                      double* __restrict__ st, int Cup, int coff, int H, int W, int ls, int w, int pld, int R,
-                                                      int seg_len)
-{
-    __shared__ double red[4][2];
-    const int tid = threadIdx.x, co = blockIdx.y, f = blockIdx.z, N = H * W;
-    const float* Zf = Z + (size_t)f * R * pld;
-    const size_t plane = ((size_t)f * 320 + coff + co) * N;
-    const int i0 = blockIdx.x * seg_len, i1 = i0 + seg_len < N ? i0 + seg_len : N;
-    double sgz = 0.0, sg = 0.0;
-    for (int i = i0 + tid; i < i1; i += 256) {
-        const float g = y[plane + i] > 0.f ? dy[plane + i] : 0.f; // the mask is the caller's y, never a recomputed sign
-        sgz += (double)g * (double)Zf[z_index(i, co, W, ls, w, pld)]; sg += (double)g;
-    }
-    sgz = wave_sum(sgz); sg = wave_sum(sg);
-    if ((tid & 63) == 0) { red[tid >> 6][0] = sgz; red[tid >> 6][1] = sg; }
-    __syncthreads();
-    if (tid < 2) st[(((size_t)f * Cup + co) * gridDim.x + blockIdx.x) * 2 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-}
-
-__global__ void __launch_bounds__(256) k_bn_neck_dz(float* __restrict__ Z, const float* __restrict__ y, const float* __restrict__ dy,
-                                                    const float* __restrict__ scale, const float* __restrict__ coef, int Cup, int coff, int H, int W,
-                                                    int ls, int w, int pld, int R, int seg_len)
-{
-    const int tid = threadIdx.x, co = blockIdx.y, f = blockIdx.z, N = H * W;
-    float* Zf = Z + (size_t)f * R * pld;
-    const size_t plane = ((size_t)f * 320 + coff + co) * N;
-    const float sc = scale[co];
-    const float c1 = coef[4 * co], c2 = coef[4 * co + 1], meanf = coef[4 * co + 2], rf = coef[4 * co + 3];
-    const int i0 = blockIdx.x * seg_len, i1 = i0 + seg_len < N ? i0 + seg_len : N;
-    for (int i = i0 + tid; i < i1; i += 256) {
-        const size_t zi = z_index(i, co, W, ls, w, pld);
-        const float zhat = (Zf[zi] - meanf) * rf;
-        const float g = y[plane + i] > 0.f ? dy[plane + i] : 0.f;
-        Zf[zi] = sc * ((g - c1) - zhat * c2);
-    }
-}
 
 // ---- dw: workgroup tile 64 ci x 32 NB rows, four waves 2 x 2, each 32 ci x 16 NB rows.  K runs over 16-pixel chunks of the launch's
 // frames (chunk c: frame c / cpf, pixels 16 (c % cpf) ..); a lane takes pixels 4 q .. 4 q + 3 of the chunk as its four k-steps, one
@@ -220,6 +154,38 @@ __global__ void __launch_bounds__(256) k_gather1(float* __restrict__ dst, const 
     dst[i] = m < 0 || m >= nsrc ? 0.f : src[m];
 }
 
+// the fp32 products of neck_run (neck_train.h): the dx product reads w itself, so there is no weight image
+struct neck_fp32 {
+    static constexpr int KPIX = 16;
+    static int grow_wt(pp_ctx*, neck_ws*, int) { return 0; }
+    static void pack_wt(const neck_plan&, neck_ws*, const float*, hipStream_t) {}
+    static void dw(const neck_plan& p, const dw_chunk& c, const float* xc, const float* dZ, float* part, int xvec, hipStream_t stream)
+    {
+        const geom& g = p.g;
+        const dim3 gd(g.R / (32 * p.NBt), g.Cin / 64, c.sp);
+        if (p.NBt == 4)
+            hipLaunchKernelGGL(k_neck_dw<4>, gd, dim3(256), 0, stream, xc, dZ, part, g.Cin, g.R, g.p, g.pld, p.cpf, c.nchunks, c.cps, c.gbase, xvec);
+        else
+            hipLaunchKernelGGL(k_neck_dw<2>, gd, dim3(256), 0, stream, xc, dZ, part, g.Cin, g.R, g.p, g.pld, p.cpf, c.nchunks, c.cps, c.gbase, xvec);
+    }
+    static void dx(const neck_plan& p, const neck_ws*, const float* wt, const float* dZ, float* dxc, int fn, hipStream_t stream)
+    {
+        const geom& g = p.g;
+        if (g.Cin == 64)
+            hipLaunchKernelGGL(k_neck_dx<1>, dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, wt, dZ, dxc, g.Cin, g.R, g.p, g.pld);
+        else if (g.Cin == 128)
+            hipLaunchKernelGGL(k_neck_dx<2>, dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, wt, dZ, dxc, g.Cin, g.R, g.p, g.pld);
+        else
+            hipLaunchKernelGGL(k_neck_dx<4>, dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, wt, dZ, dxc, g.Cin, g.R, g.p, g.pld);
+    }
+};
+
+int neck_entry(pp_ctx* ctx, const char* entry, norm_form form, int branch, const neck_args& a)
+{
+    if (!ctx) return PP_E_ARG;
+    if (int rc = neck_check(ctx, entry, NECK_CHK_ALL, form, branch, a)) return rc;
+    return neck_run<neck_fp32>(ctx, form, branch, a);
+}
 
 } // namespace
 
@@ -237,77 +203,9 @@ void pp_neck_destroy(pp_ctx* ctx)
 extern "C" int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const float* wt, const float* y, const float* dy, int nb, float* dw,
                                 float* dx, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: the InstanceNorm backbone only (BatchNorm has no backward here)");
-    if (branch < 0 || branch > 2) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: branch must be 0, 1 or 2");
-    if (!x || !wt || !y || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: null pointer");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: nb must be 1 .. max_batch");
-    if ((ctx->H % 4) || (ctx->W % 4)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: BEV grid must be a multiple of 8 in x and y");
-    if (!aligned16(wt)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_neck_backward: tensors must be 4-byte aligned");
-    geom g;
-    g.H = ctx->H; g.W = ctx->W; g.ls = branch; g.s = 1 << branch;
-    g.Cin = 64 << branch; g.Cup = branch ? 128 : 64; g.coff = branch == 0 ? 0 : branch == 1 ? 64 : 192;
-    g.h = g.H >> branch; g.w = g.W >> branch; g.p = g.h * g.w; g.pld = (g.p + 3) & ~3; g.R = g.Cup * g.s * g.s;
-    const int N = g.H * g.W;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    neck_ws* ws = workspace(ctx);
-    // frames per chunk, statistics segments, K ranges: functions of the shapes alone
-    const size_t zf_elems = (size_t)g.R * g.pld;
-    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, 0);
-    int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
-    S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
-    const int seg_len = (N + S - 1) / S;
-    S = (N + seg_len - 1) / seg_len;
-    const int NBt = g.R >= 128 ? 4 : 2;
-    const int tiles = (g.R / (32 * NBt)) * (g.Cin / 64), cpf = (g.p + 15) / 16;
-    int G = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        G += sp;
-    }
-    const int nw = g.Cin * g.R;
-    int rc;
-    if ((rc = grow(ctx, &ws->z, &ws->z_elems, (size_t)fc * zf_elems, stream)) ||
-        (rc = grow(ctx, &ws->st, &ws->st_elems, (size_t)fc * g.Cup * S * 4, stream)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)G * nw, stream)))
-        return rc;
-    const int xvec = g.p % 4 == 0 && aligned16(x);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const float* xc = x + (size_t)f0 * g.Cin * g.p;
-        const float* yc = y + (size_t)f0 * 320 * N;
-        const float* dyc = dy + (size_t)f0 * 320 * N;
-        hipLaunchKernelGGL(k_neck_fwd, dim3(pp_div_up(g.pld, 64), g.R / 64, fn), dim3(256), 0, stream, xc, wt, ws->z, g.Cin, g.R, g.p, g.pld);
-        hipLaunchKernelGGL(k_neck_stats, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, ws->st, g.Cup, g.coff, g.H, g.W, g.ls, g.w,
-                           g.pld, g.R, seg_len);
-        hipLaunchKernelGGL(k_neck_dz, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, ws->st, g.Cup, g.coff, g.H, g.W, g.ls, g.w, g.pld,
-                           g.R, seg_len);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(g.R / (32 * NBt), g.Cin / 64, sp);
-        if (NBt == 4)
-            hipLaunchKernelGGL(k_neck_dw<4>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        else
-            hipLaunchKernelGGL(k_neck_dw<2>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        gbase += sp;
-        if (dx) {
-            float* dxc = dx + (size_t)f0 * g.Cin * g.p;
-            if (g.Cin == 64)
-                hipLaunchKernelGGL(k_neck_dx<1>, dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else if (g.Cin == 128)
-                hipLaunchKernelGGL(k_neck_dx<2>, dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else
-                hipLaunchKernelGGL(k_neck_dx<4>, dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-        }
-    }
-    hipLaunchKernelGGL(k_neck_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, G, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
+    neck_args a;
+    a.x = x; a.wt = wt; a.y = y; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx; a.stream = (hipStream_t)stream_;
+    return neck_entry(ctx, "pp_neck_backward", NORM_INSTANCE, branch, a);
 }
 
 // pp_neck_backward with a per-channel affine for the norm: Z recomputed as there, one pass for the sums and dZ where the sibling runs
@@ -316,77 +214,10 @@ extern "C" int pp_neck_backward(pp_ctx* ctx, int branch, const float* x, const f
 extern "C" int pp_neck_backward_affine(pp_ctx* ctx, int branch, const float* x, const float* wt, const float* scale, const float* shift,
                                        const float* y, const float* dy, int nb, float* dw, float* dx, double* dscale, double* dshift, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (branch < 0 || branch > 2) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: branch must be 0, 1 or 2");
-    if (!x || !wt || !scale || !shift || !y || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: null pointer");
-    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: dscale and dshift go together");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: nb must be 1 .. max_batch");
-    if ((ctx->H % 4) || (ctx->W % 4)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: BEV grid must be a multiple of 8 in x and y");
-    if (!aligned16(wt)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: tensors must be 4-byte aligned");
-    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_affine: dscale / dshift must be 8-byte aligned");
-    geom g;
-    g.H = ctx->H; g.W = ctx->W; g.ls = branch; g.s = 1 << branch;
-    g.Cin = 64 << branch; g.Cup = branch ? 128 : 64; g.coff = branch == 0 ? 0 : branch == 1 ? 64 : 192;
-    g.h = g.H >> branch; g.w = g.W >> branch; g.p = g.h * g.w; g.pld = (g.p + 3) & ~3; g.R = g.Cup * g.s * g.s;
-    const int N = g.H * g.W;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    neck_ws* ws = workspace(ctx);
-    // frames per chunk, segments, K ranges: as pp_neck_backward
-    const size_t zf_elems = (size_t)g.R * g.pld;
-    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, 0);
-    int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
-    S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
-    const int slen = (N + S - 1) / S;
-    S = (N + slen - 1) / slen;
-    const int NBt = g.R >= 128 ? 4 : 2;
-    const int tiles = (g.R / (32 * NBt)) * (g.Cin / 64), cpf = (g.p + 15) / 16;
-    int G = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        G += sp;
-    }
-    const int nw = g.Cin * g.R;
-    int rc;
-    if ((rc = grow(ctx, &ws->z, &ws->z_elems, (size_t)fc * zf_elems, stream)) ||
-        (rc = grow(ctx, &ws->st, &ws->st_elems, (size_t)nb * g.Cup * S * 2, stream)) || // every frame's segment sums: reduced once, behind the chunks
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)G * nw, stream)))
-        return rc;
-    const int xvec = g.p % 4 == 0 && aligned16(x);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const float* xc = x + (size_t)f0 * g.Cin * g.p;
-        const float* yc = y + (size_t)f0 * 320 * N;
-        const float* dyc = dy + (size_t)f0 * 320 * N;
-        hipLaunchKernelGGL(k_neck_fwd, dim3(pp_div_up(g.pld, 64), g.R / 64, fn), dim3(256), 0, stream, xc, wt, ws->z, g.Cin, g.R, g.p, g.pld);
-        hipLaunchKernelGGL(k_affine_neck_dz, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, scale, ws->st + (size_t)f0 * g.Cup * S * 2,
-                           g.Cup, g.coff, g.H, g.W, g.ls, g.w, g.pld, g.R, slen);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(g.R / (32 * NBt), g.Cin / 64, sp);
-        if (NBt == 4)
-            hipLaunchKernelGGL(k_neck_dw<4>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        else
-            hipLaunchKernelGGL(k_neck_dw<2>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        gbase += sp;
-        if (dx) {
-            float* dxc = dx + (size_t)f0 * g.Cin * g.p;
-            if (g.Cin == 64)
-                hipLaunchKernelGGL(k_neck_dx<1>, dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else if (g.Cin == 128)
-                hipLaunchKernelGGL(k_neck_dx<2>, dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else
-                hipLaunchKernelGGL(k_neck_dx<4>, dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-        }
-    }
-    hipLaunchKernelGGL(k_neck_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, G, nw, dw);
-    if (dscale) hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(g.Cup, 64)), dim3(64), 0, stream, ws->st, nb, g.Cup, S, dscale, dshift);
-    PP_HIP(hipGetLastError());
-    return 0;
+    neck_args a;
+    a.x = x; a.wt = wt; a.scale = scale; a.shift = shift; a.y = y; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.stream = (hipStream_t)stream_;
+    return neck_entry(ctx, "pp_neck_backward_affine", NORM_AFFINE, branch, a);
 }
 
 // pp_neck_backward_affine behind a train-mode BatchNorm: (scale, shift) are the fold of the batch statistics (mean, var) the forward used;
@@ -396,90 +227,10 @@ extern "C" int pp_neck_backward_bn(pp_ctx* ctx, int branch, const float* x, cons
                                    const float* mean, const float* var, const float* y, const float* dy, int nb, float* dw, float* dx,
                                    double* dscale, double* dshift, int chunk_frames, void* stream_)
 {
-    if (!ctx) return PP_E_ARG;
-    if (branch < 0 || branch > 2) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: branch must be 0, 1 or 2");
-    if (!x || !wt || !scale || !shift || !mean || !var || !y || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: null pointer");
-    if (!dscale != !dshift) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: dscale and dshift go together");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: nb must be 1 .. max_batch");
-    if (chunk_frames < 0) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: chunk_frames must be >= 0");
-    if ((ctx->H % 4) || (ctx->W % 4)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: BEV grid must be a multiple of 8 in x and y");
-    if (!aligned16(wt)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: tensors must be 4-byte aligned");
-    if (((uintptr_t)dscale | (uintptr_t)dshift) & 7) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_bn: dscale / dshift must be 8-byte aligned");
-    geom g;
-    g.H = ctx->H; g.W = ctx->W; g.ls = branch; g.s = 1 << branch;
-    g.Cin = 64 << branch; g.Cup = branch ? 128 : 64; g.coff = branch == 0 ? 0 : branch == 1 ? 64 : 192;
-    g.h = g.H >> branch; g.w = g.W >> branch; g.p = g.h * g.w; g.pld = (g.p + 3) & ~3; g.R = g.Cup * g.s * g.s;
-    const int N = g.H * g.W;
-    hipStream_t stream = (hipStream_t)stream_;
-    PP_HIP(hipSetDevice(ctx->device));
-    neck_ws* ws = workspace(ctx);
-    // frames per chunk, segments, K ranges: as pp_neck_backward, the chunk capped by chunk_frames
-    const size_t zf_elems = (size_t)g.R * g.pld;
-    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, chunk_frames);
-    int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
-    S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
-    const int slen = (N + S - 1) / S;
-    S = (N + slen - 1) / slen;
-    const int NBt = g.R >= 128 ? 4 : 2;
-    const int tiles = (g.R / (32 * NBt)) * (g.Cin / 64), cpf = (g.p + 15) / 16;
-    int G = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        G += sp;
-    }
-    const int nw = g.Cin * g.R;
-    int rc;
-    if ((rc = grow(ctx, &ws->z, &ws->z_elems, (size_t)fc * zf_elems, stream)) ||
-        (rc = grow(ctx, &ws->st, &ws->st_elems, (size_t)nb * g.Cup * S * 2, stream)) || // every frame's segment sums: pooled once, between the two rounds
-        (rc = grow(ctx, &ws->coef, &ws->coef_elems, (size_t)g.Cup * 4, stream)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)G * nw, stream)))
-        return rc;
-    const int xvec = g.p % 4 == 0 && aligned16(x);
-    // Z is recomputed per chunk into the workspace.  One chunk: Z stays in place between the sums and dZ.  Several: a first round over the
-    // chunks for the sums, a second that recomputes each chunk's Z (the same bits) for dZ and the products.
-    const bool one = fc >= nb;
-    auto fwd_sums = [&](int f0, int fn) {
-        hipLaunchKernelGGL(k_neck_fwd, dim3(pp_div_up(g.pld, 64), g.R / 64, fn), dim3(256), 0, stream, x + (size_t)f0 * g.Cin * g.p, wt, ws->z, g.Cin,
-                           g.R, g.p, g.pld);
-        hipLaunchKernelGGL(k_bn_neck_sums, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, y + (size_t)f0 * 320 * N, dy + (size_t)f0 * 320 * N,
-                           ws->st + (size_t)f0 * g.Cup * S * 2, g.Cup, g.coff, g.H, g.W, g.ls, g.w, g.pld, g.R, slen);
-    };
-    for (int f0 = 0; f0 < nb; f0 += fc) fwd_sums(f0, nb - f0 < fc ? nb - f0 : fc);
-    hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(g.Cup, 64)), dim3(64), 0, stream, ws->st, nb, g.Cup, S, mean, var, (double)nb * (double)N, ws->coef,
-                       dscale, dshift);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const float* xc = x + (size_t)f0 * g.Cin * g.p;
-        const float* yc = y + (size_t)f0 * 320 * N;
-        const float* dyc = dy + (size_t)f0 * 320 * N;
-        if (!one) hipLaunchKernelGGL(k_neck_fwd, dim3(pp_div_up(g.pld, 64), g.R / 64, fn), dim3(256), 0, stream, xc, wt, ws->z, g.Cin, g.R, g.p, g.pld);
-        hipLaunchKernelGGL(k_bn_neck_dz, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, scale, ws->coef, g.Cup, g.coff, g.H, g.W, g.ls, g.w,
-                           g.pld, g.R, slen);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(g.R / (32 * NBt), g.Cin / 64, sp);
-        if (NBt == 4)
-            hipLaunchKernelGGL(k_neck_dw<4>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        else
-            hipLaunchKernelGGL(k_neck_dw<2>, gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        gbase += sp;
-        if (dx) {
-            float* dxc = dx + (size_t)f0 * g.Cin * g.p;
-            if (g.Cin == 64)
-                hipLaunchKernelGGL(k_neck_dx<1>, dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else if (g.Cin == 128)
-                hipLaunchKernelGGL(k_neck_dx<2>, dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else
-                hipLaunchKernelGGL(k_neck_dx<4>, dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, wt, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-        }
-    }
-    hipLaunchKernelGGL(k_neck_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, G, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
+    neck_args a;
+    a.x = x; a.wt = wt; a.scale = scale; a.shift = shift; a.mean = mean; a.var = var; a.y = y; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.chunk_frames = chunk_frames; a.stream = (hipStream_t)stream_;
+    return neck_entry(ctx, "pp_neck_backward_bn", NORM_BATCH, branch, a);
 }
 
 extern "C" int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const float* w3, void* stream_)

@@ -174,83 +174,35 @@ __global__ void __launch_bounds__(256) k_neck_dx16(const uint16_t* __restrict__ 
         }
 }
 
-// the checks of pp_neck_backward that do not depend on the tensors
-int neck_shape_check(pp_ctx* ctx, int branch)
-{
-    if (ctx->cfg.norm_kind != 0) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: the InstanceNorm backbone only (BatchNorm has no backward here)");
-    if (branch < 0 || branch > 2) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: branch must be 0, 1 or 2");
-    if ((ctx->H % 4) || (ctx->W % 4)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: BEV grid must be a multiple of 8 in x and y");
-    return 0;
-}
-
+// the 16-bit products of neck_run (neck_train.h): K over 32-pixel chunks, the bf16 image of w for the dx product
 template <bool X3>
-int neck_backward16(pp_ctx* ctx, int branch, const float* x, const float* wt, const float* y, const float* dy, int nb, float* dw, float* dx,
-                    hipStream_t stream)
-{
-    geom g;
-    g.H = ctx->H; g.W = ctx->W; g.ls = branch; g.s = 1 << branch;
-    g.Cin = 64 << branch; g.Cup = branch ? 128 : 64; g.coff = branch == 0 ? 0 : branch == 1 ? 64 : 192;
-    g.h = g.H >> branch; g.w = g.W >> branch; g.p = g.h * g.w; g.pld = (g.p + 3) & ~3; g.R = g.Cup * g.s * g.s;
-    const int N = g.H * g.W, parts = X3 ? 2 : 1;
-    PP_HIP(hipSetDevice(ctx->device));
-    neck_ws* ws = workspace(ctx);
-    // frames per chunk and statistics segments as pp_neck_backward; K ranges over 32-pixel chunks: functions of the shapes alone
-    const size_t zf_elems = (size_t)g.R * g.pld;
-    const int fc = pp_chunk_frames(ctx, Z_BUDGET, zf_elems * sizeof(float), nb, 0);
-    int S = N / 256 < 2048 / g.Cup ? N / 256 : 2048 / g.Cup;
-    S = S < 1 ? 1 : S > ST_MAX_SEG ? ST_MAX_SEG : S;
-    const int seg_len = (N + S - 1) / S;
-    S = (N + seg_len - 1) / seg_len;
-    const int NBt = g.R >= 128 ? 4 : 2;
-    const int tiles = (g.R / (32 * NBt)) * (g.Cin / 64), cpf = (g.p + 31) / 32;
-    int G = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        int sp, cps;
-        dw_ranges(tiles, (nb - f0 < fc ? nb - f0 : fc) * cpf, &sp, &cps);
-        G += sp;
+struct neck_bf16 {
+    static constexpr int KPIX = 32;
+    static int grow_wt(pp_ctx* ctx, neck_ws* ws, int nw) { return grow(ctx, &ws->w16, &ws->w16_elems, (size_t)(X3 ? 2 : 1) * nw); }
+    static void pack_wt(const neck_plan& p, neck_ws* ws, const float* wt, hipStream_t stream)
+    {
+        hipLaunchKernelGGL(k_neck_w16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wt, ws->w16, p.nw);
     }
-    const int nw = g.Cin * g.R;
-    int rc;
-    if ((rc = grow(ctx, &ws->z, &ws->z_elems, (size_t)fc * zf_elems, stream)) ||
-        (rc = grow(ctx, &ws->st, &ws->st_elems, (size_t)fc * g.Cup * S * 4, stream)) ||
-        (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)G * nw, stream)) ||
-        (dx && (rc = grow(ctx, &ws->w16, &ws->w16_elems, (size_t)parts * nw, stream))))
-        return rc;
-    const int xvec = g.p % 4 == 0 && aligned16(x);
-    if (dx) hipLaunchKernelGGL(k_neck_w16<X3>, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, wt, ws->w16, nw);
-    int gbase = 0;
-    for (int f0 = 0; f0 < nb; f0 += fc) {
-        const int fn = nb - f0 < fc ? nb - f0 : fc;
-        const float* xc = x + (size_t)f0 * g.Cin * g.p;
-        const float* yc = y + (size_t)f0 * 320 * N;
-        const float* dyc = dy + (size_t)f0 * 320 * N;
-        hipLaunchKernelGGL(k_neck_fwd, dim3(pp_div_up(g.pld, 64), g.R / 64, fn), dim3(256), 0, stream, xc, wt, ws->z, g.Cin, g.R, g.p, g.pld);
-        hipLaunchKernelGGL(k_neck_stats, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, ws->st, g.Cup, g.coff, g.H, g.W, g.ls, g.w,
-                           g.pld, g.R, seg_len);
-        hipLaunchKernelGGL(k_neck_dz, dim3(S, g.Cup, fn), dim3(256), 0, stream, ws->z, yc, dyc, ws->st, g.Cup, g.coff, g.H, g.W, g.ls, g.w, g.pld,
-                           g.R, seg_len);
-        int sp, cps;
-        dw_ranges(tiles, fn * cpf, &sp, &cps);
-        const dim3 gd(g.R / (32 * NBt), g.Cin / 64, sp);
-        if (NBt == 4)
-            hipLaunchKernelGGL((k_neck_dw16<4, X3>), gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
+    static void dw(const neck_plan& p, const dw_chunk& c, const float* xc, const float* dZ, float* part, int xvec, hipStream_t stream)
+    {
+        const geom& g = p.g;
+        const dim3 gd(g.R / (32 * p.NBt), g.Cin / 64, c.sp);
+        if (p.NBt == 4)
+            hipLaunchKernelGGL((k_neck_dw16<4, X3>), gd, dim3(256), 0, stream, xc, dZ, part, g.Cin, g.R, g.p, g.pld, p.cpf, c.nchunks, c.cps, c.gbase, xvec);
         else
-            hipLaunchKernelGGL((k_neck_dw16<2, X3>), gd, dim3(256), 0, stream, xc, ws->z, ws->part, g.Cin, g.R, g.p, g.pld, cpf, fn * cpf, cps, gbase, xvec);
-        gbase += sp;
-        if (dx) {
-            float* dxc = dx + (size_t)f0 * g.Cin * g.p;
-            if (g.Cin == 64)
-                hipLaunchKernelGGL((k_neck_dx16<1, X3>), dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, ws->w16, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else if (g.Cin == 128)
-                hipLaunchKernelGGL((k_neck_dx16<2, X3>), dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, ws->w16, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-            else
-                hipLaunchKernelGGL((k_neck_dx16<4, X3>), dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, ws->w16, ws->z, dxc, g.Cin, g.R, g.p, g.pld);
-        }
+            hipLaunchKernelGGL((k_neck_dw16<2, X3>), gd, dim3(256), 0, stream, xc, dZ, part, g.Cin, g.R, g.p, g.pld, p.cpf, c.nchunks, c.cps, c.gbase, xvec);
     }
-    hipLaunchKernelGGL(k_neck_dw_reduce, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, ws->part, G, nw, dw);
-    PP_HIP(hipGetLastError());
-    return 0;
-}
+    static void dx(const neck_plan& p, const neck_ws* ws, const float*, const float* dZ, float* dxc, int fn, hipStream_t stream)
+    {
+        const geom& g = p.g;
+        if (g.Cin == 64)
+            hipLaunchKernelGGL((k_neck_dx16<1, X3>), dim3(pp_div_up(g.p, 128), 1, fn), dim3(256), 0, stream, ws->w16, dZ, dxc, g.Cin, g.R, g.p, g.pld);
+        else if (g.Cin == 128)
+            hipLaunchKernelGGL((k_neck_dx16<2, X3>), dim3(pp_div_up(g.p, 64), 1, fn), dim3(256), 0, stream, ws->w16, dZ, dxc, g.Cin, g.R, g.p, g.pld);
+        else
+            hipLaunchKernelGGL((k_neck_dx16<4, X3>), dim3(pp_div_up(g.p, 32), 1, fn), dim3(256), 0, stream, ws->w16, dZ, dxc, g.Cin, g.R, g.p, g.pld);
+    }
+};
 
 } // namespace
 
@@ -258,8 +210,7 @@ extern "C" int pp_neck_backward_path(pp_ctx* ctx, int mode, int branch)
 {
     if (!ctx) return -PP_E_ARG; // the modes are 0 .. 2, so an error is the negated code
     if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, "pp_neck_backward_path: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
-    int rc = neck_shape_check(ctx, branch);
-    if (rc) return -rc;
+    if (int rc = neck_check(ctx, "pp_neck_backward_mp", NECK_CHK_SHAPE, NORM_INSTANCE, branch, neck_args())) return -rc;
     return mode; // the 16-bit kernels keep no image of their own: every branch the fp32 entry takes runs in the mode asked for
 }
 
@@ -269,13 +220,11 @@ extern "C" int pp_neck_backward_mp(pp_ctx* ctx, int mode, int branch, const floa
     if (!ctx) return PP_E_ARG;
     if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
     if (mode == 0) return pp_neck_backward(ctx, branch, x, wt, y, dy, nb, dw, dx, stream_);
-    int rc = neck_shape_check(ctx, branch);
-    if (rc) return rc;
-    if (!x || !wt || !y || !dy || !dw) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: null pointer");
-    if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: nb must be 1 .. max_batch");
-    if (!aligned16(wt)) return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: w must be 16-byte aligned");
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)dx) & 3)
-        return pp_fail(ctx, PP_E_ARG, "pp_neck_backward_mp: tensors must be 4-byte aligned");
-    return mode == 1 ? neck_backward16<true>(ctx, branch, x, wt, y, dy, nb, dw, dx, (hipStream_t)stream_)
-                     : neck_backward16<false>(ctx, branch, x, wt, y, dy, nb, dw, dx, (hipStream_t)stream_);
+    neck_args a;
+    a.x = x; a.wt = wt; a.y = y; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx; a.stream = (hipStream_t)stream_;
+    int rc; // the branch and the context first, then the tensors
+    if ((rc = neck_check(ctx, "pp_neck_backward_mp", NECK_CHK_SHAPE, NORM_INSTANCE, branch, a)) ||
+        (rc = neck_check(ctx, "pp_neck_backward_mp", NECK_CHK_TENSORS, NORM_INSTANCE, branch, a)))
+        return rc;
+    return mode == 1 ? neck_run<neck_bf16<true>>(ctx, NORM_INSTANCE, branch, a) : neck_run<neck_bf16<false>>(ctx, NORM_INSTANCE, branch, a);
 }

@@ -140,9 +140,9 @@ struct pp_ctx {
     //      the natural-order copy of the head weights and the index map of the head's packed image are rebuilt after a commit ----
     uint64_t commit_gen = 0;
     void* trn = nullptr;
-    void* neck = nullptr;            // neck backward (neck_train.hip): dZ workspace, dW partials, index maps of the upsampler images
-    void* blk = nullptr;             // Resnet unit backward (block_train.hip): padded a / dz planes, transposed weights, dW partials
-    void* down = nullptr;            // strided stage backward (down_train.hip): parity planes of x, dz planes, transposed weights, dW partials
+    void* neck = nullptr;            // neck backward (neck_ws, neck_train.h): dZ workspace, dW partials, index maps of the upsampler images
+    void* blk = nullptr;             // Resnet unit backward (block_ws, block_train.h): padded a / dz planes, transposed weights, dW partials
+    void* down = nullptr;            // strided stage backward (down_ws, down_train.h): parity planes of x, dz planes, transposed weights, dW partials
     void* pfnt = nullptr;            // PFN training (pfn_train.hip): fp64 partials of both reductions, the batch-statistics scale / shift
     void* optim = nullptr;           // device optimizer (optim.hip): fp64 partials of the gradient norm, one per chunk
     int train_chunk_frames = 0;      // pp_set_train_chunk_frames: cap on the frames of a chunk of every training backward (0: the workspace rule alone)

@@ -2,6 +2,7 @@
 // splitting fp32 values into bf16 fragments, the bf16 MFMA, and the funnel shift of a fragment by one element.
 #pragma once
 #include "pp_common.h"
+#include "train_host.h" // f32x4
 
 namespace {
 
@@ -9,7 +10,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) // v_cvt_pk_bf16_f32 (round to nearest even), a in the low half
 {

@@ -1,4 +1,5 @@
-// What the streaming passes of block_train.hip and down_train.hip share: how a plane is cut into segments, the fixed-order sums of a
+// The device side that the streaming passes of block_train.hip and down_train.hip share (the host side of the training backwards is
+// train_host.h's): how a plane is cut into segments, the fixed-order sums of a
 // workgroup, and the statistics kernel.  One copy, so that both files cut a plane the same way and a shape keeps its bits in both.
 // k_affine_reduce, the last step of the three pp_*_backward_affine entries, is here for neck_train.hip as well, and so is k_bn_coef,
 // which pools the sums of the three pp_*_backward_bn entries.

@@ -465,41 +465,67 @@ class Engine:
                        self.ctx, "pp_backbone_taps")
         return (out, *taps)
 
+    # The three families' backwards come in three norm forms behind one helper per family (_neck_backward, _unit_backward,
+    # _down_backward): InstanceNorm (affine=None; grad_precision picks the mode of pp_*_backward_mp), a frozen BatchNorm
+    # (affine=(scale, shift, need_affine): pp_*_backward_affine) and a train-mode BatchNorm (bn=(mean, var, chunk_frames) as well:
+    # pp_*_backward_bn).  `who` is the public method, for messages.
+    def _backward_path(self, entry, grad_precision, *ints):
+        """One pp_*_backward_path entry: the precision that family's backward really runs at these shapes."""
+        mode = self._grad_mode(grad_precision, entry[3:])
+        rc = getattr(self.lib, entry)(self.ctx, mode, *ints)
+        if rc < 0:
+            _lib.check(-rc, self.ctx, entry)
+        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+
+    def _norm_args(self, who, C, affine, bn):
+        """The norm form of a backward over C normalised channels -> (the entry's suffix, the norm's tensors, the arguments behind the
+        outputs, the affine sums the caller gets back: () for InstanceNorm)."""
+        if affine is None:
+            return "_mp", [], [], ()
+        scale, shift, sums = self._affine_args(who, *affine[:2], C, affine[2])
+        if bn is None:
+            return "_affine", [scale, shift], list(sums), sums
+        mean, var, chunk = self._bn_args(who, bn, C)
+        return "_bn", [scale, shift, mean, var], [*sums, chunk], sums
+
+    def _call_backward(self, entry, *args):
+        """One training backward of the library on the current stream; tensors (or None) go as pointers, ints as they are."""
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, entry)(self.ctx, *[_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args], _stream()), self.ctx, entry)
+
+    def _neck_backward(self, who, branch, x, w, y, dy, need_dx, affine=None, bn=None, grad_precision=None):
+        mode = [self._grad_mode(grad_precision, who)] if affine is None else []
+        if branch not in (0, 1, 2):
+            raise ValueError(who + f": branch must be 0, 1 or 2, got {branch!r}")
+        xs, wsh = self.neck_shapes(branch)
+        nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        if not 1 <= nb <= self.max_batch:
+            raise ValueError(who + f": x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
+        x = _chk(x, torch.float32, (nb,) + xs, who + ": x")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, who + ": w")
+        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), who + ": y")
+        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), who + ": dy")
+        self._on_device(who, ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
+        suffix, norm, tail, sums = self._norm_args(who, wsh[1], affine, bn)
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
+        dw = self._t(wsh, torch.float32)
+        dx = self._t((nb,) + xs, torch.float32) if need_dx else None
+        self._call_backward("pp_neck_backward" + suffix, *mode, branch, x, w, *norm, y, dy, nb, dw, dx, *tail)
+        return (dw, dx, *sums)
+
     def neck_backward_path(self, grad_precision, branch):
         """pp_neck_backward_path: the precision neck_backward(grad_precision=...) really runs for this branch."""
-        mode = self._grad_mode(grad_precision, "neck_backward_path")
-        if branch not in (0, 1, 2):
+        if grad_precision in self.GRAD_PRECISIONS and branch not in (0, 1, 2):  # a grad_precision that is not one is reported first
             raise ValueError(f"neck_backward_path: branch must be 0, 1 or 2, got {branch!r}")
-        rc = self.lib.pp_neck_backward_path(self.ctx, mode, int(branch))
-        if rc < 0:
-            _lib.check(-rc, self.ctx, "pp_neck_backward_path")
-        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+        return self._backward_path("pp_neck_backward_path", grad_precision, int(branch))
 
     def neck_backward(self, branch, x, w, y, dy, need_dx=True, grad_precision="fp32"):
         """pp_neck_backward_mp: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
         dL/d(rpn_out) dy [nb,320,H,W] -> (dw [Cin,Cup,s,s] summed over the frames, dx [nb,Cin,h,w] or None when need_dx is False).
         Deterministic, stateless.  grad_precision: "fp32" (pp_neck_backward, bit for bit), "bf16x3" or "bf16": the operands of the dw
         and dx products in split or plain bf16 on the bf16 MFMA, everything else (Z, statistics, mask, dZ, tensors) fp32."""
-        mode = self._grad_mode(grad_precision, "neck_backward")
-        if branch not in (0, 1, 2):
-            raise ValueError(f"neck_backward: branch must be 0, 1 or 2, got {branch!r}")
-        xs, wsh = self.neck_shapes(branch)
-        nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
-        if not 1 <= nb <= self.max_batch:
-            raise ValueError(f"neck_backward: x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
-        x = _chk(x, torch.float32, (nb,) + xs, "neck_backward: x")
-        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, "neck_backward: w")
-        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), "neck_backward: y")
-        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), "neck_backward: dy")
-        self._on_device("neck_backward", ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
-        if w.data_ptr() % 16:
-            w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
-        dw = self._t(wsh, torch.float32)
-        dx = self._t((nb,) + xs, torch.float32) if need_dx else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_neck_backward_mp(self.ctx, mode, branch, _ptr(x), _ptr(w), _ptr(y), _ptr(dy), nb, _ptr(dw), _ptr(dx), _stream()),
-                       self.ctx, "pp_neck_backward_mp")
-        return dw, dx
+        return self._neck_backward("neck_backward", branch, x, w, y, dy, need_dx, grad_precision=grad_precision)
 
     def update_neck_weights(self, params):
         """pp_update_neck_weights: {state_dict name: device tensor} of rpn.deconv{1,2,3}.0.weight -> the committed upsampler images, in
@@ -523,11 +549,32 @@ class Engine:
     def unit_backward_path(self, grad_precision, C, h, w):
         """pp_unit_backward_path: the precision unit_backward(grad_precision=...) really runs at this shape: grad_precision, or "fp32"
         where no 16-bit tiling takes the shape."""
-        mode = self._grad_mode(grad_precision, "unit_backward_path")
-        rc = self.lib.pp_unit_backward_path(self.ctx, mode, int(C), int(h), int(w))
-        if rc < 0:
-            _lib.check(-rc, self.ctx, "pp_unit_backward_path")
-        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+        return self._backward_path("pp_unit_backward_path", grad_precision, int(C), int(h), int(w))
+
+    def _unit_backward(self, who, u, w, dy, dskip, need_du, affine=None, bn=None, grad_precision=None):
+        mode = [self._grad_mode(grad_precision, who)] if affine is None else []
+        if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
+            raise ValueError(who + f": u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb, C, h, wd = (int(v) for v in u.shape)
+        if C not in (64, 128, 256):
+            raise ValueError(who + f": C must be 64, 128 or 256, got {C}")
+        if h < 1 or wd < 1 or h * wd < 2:
+            raise ValueError(who + f": the map needs at least two elements, got {h} x {wd}")
+        if affine is not None and affine[2] and not need_du:
+            raise ValueError(who + ": the affine sums are sums over du's product: need_affine needs need_du")
+        u = _chk(u, torch.float32, (nb, C, h, wd), who + ": u")
+        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), who + ": w")
+        dy = _chk(dy, torch.float32, (nb, C, h, wd), who + ": dy")
+        if dskip is not None:
+            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), who + ": dskip")
+        self._on_device(who, ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
+        suffix, norm, tail, sums = self._norm_args(who, C, affine, bn)
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
+        dw = self._t((C, C, 3, 3), torch.float32)
+        du = self._t((nb, C, h, wd), torch.float32) if need_du else None
+        self._call_backward("pp_unit_backward" + suffix, *mode, C, h, wd, u, w, *norm, dy, dskip, nb, dw, du, *tail)
+        return (dw, du, *sums)
 
     def unit_backward(self, u, w, dy, dskip=None, need_du=True, grad_precision="fp32"):
         """pp_unit_backward_mp: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
@@ -535,28 +582,7 @@ class Engine:
         (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  Deterministic, stateless.  grad_precision:
         "fp32" (pp_unit_backward, bit for bit), "bf16x3" or "bf16": the operands of the two gradient products in split or plain bf16 on
         the bf16 MFMA, everything else (tensors, statistics, mask, norm backward) fp32."""
-        mode = self._grad_mode(grad_precision, "unit_backward")
-        if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
-            raise ValueError(f"unit_backward: u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
-        nb, C, h, wd = (int(v) for v in u.shape)
-        if C not in (64, 128, 256):
-            raise ValueError(f"unit_backward: C must be 64, 128 or 256, got {C}")
-        if h < 1 or wd < 1 or h * wd < 2:
-            raise ValueError(f"unit_backward: the map needs at least two elements, got {h} x {wd}")
-        u = _chk(u, torch.float32, (nb, C, h, wd), "unit_backward: u")
-        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), "unit_backward: w")
-        dy = _chk(dy, torch.float32, (nb, C, h, wd), "unit_backward: dy")
-        if dskip is not None:
-            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), "unit_backward: dskip")
-        self._on_device("unit_backward", ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
-        if w.data_ptr() % 16:
-            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
-        dw = self._t((C, C, 3, 3), torch.float32)
-        du = self._t((nb, C, h, wd), torch.float32) if need_du else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_unit_backward_mp(self.ctx, mode, C, h, wd, _ptr(u), _ptr(w), _ptr(dy), _ptr(dskip), nb, _ptr(dw), _ptr(du),
-                                                    _stream()), self.ctx, "pp_unit_backward_mp")
-        return dw, du
+        return self._unit_backward("unit_backward", u, w, dy, dskip, need_du, grad_precision=grad_precision)
 
     def backbone_block_taps(self, canvas):
         """pp_backbone_block_taps: backbone_taps(canvas) plus the inputs of block 3's five units -> (rpn_out, x1, x2, x3,
@@ -582,11 +608,31 @@ class Engine:
 
     def down_backward_path(self, grad_precision, cin, cout, hin, win):
         """pp_down_backward_path: the precision down_backward(grad_precision=...) really runs at this shape."""
-        mode = self._grad_mode(grad_precision, "down_backward_path")
-        rc = self.lib.pp_down_backward_path(self.ctx, mode, int(cin), int(cout), int(hin), int(win))
-        if rc < 0:
-            _lib.check(-rc, self.ctx, "pp_down_backward_path")
-        return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
+        return self._backward_path("pp_down_backward_path", grad_precision, int(cin), int(cout), int(hin), int(win))
+
+    def _down_backward(self, who, x, w, z, dy, need_dx, affine=None, bn=None, grad_precision=None):
+        mode = [self._grad_mode(grad_precision, who)] if affine is None else []
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
+            raise ValueError(who + f": x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
+        nb, cin, hin, win = (int(v) for v in x.shape)
+        cout = int(w.shape[0]) if isinstance(w, torch.Tensor) and w.dim() == 4 else 0
+        if (cin, cout) not in self.DOWN_PAIRS:
+            raise ValueError(who + f": (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
+        ho, wo = (hin + 1) // 2, (win + 1) // 2
+        if hin < 1 or win < 1 or ho * wo < 2:
+            raise ValueError(who + f": the output map needs at least two elements, got {ho} x {wo}")
+        x = _chk(x, torch.float32, (nb, cin, hin, win), who + ": x")
+        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), who + ": w")
+        z = _chk(z, torch.float32, (nb, cout, ho, wo), who + ": z")
+        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), who + ": dy")
+        self._on_device(who, ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
+        suffix, norm, tail, sums = self._norm_args(who, cout, affine, bn)
+        if w.data_ptr() % 16:
+            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
+        dw = self._t((cout, cin, 3, 3), torch.float32)
+        dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
+        self._call_backward("pp_down_backward" + suffix, *mode, cin, cout, hin, win, x, w, z, *norm, dy, nb, dw, dx, *tail)
+        return (dw, dx, *sums)
 
     def down_backward(self, x, w, z, dy, need_dx=True, grad_precision="fp32"):
         """pp_down_backward_mp: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
@@ -595,29 +641,7 @@ class Engine:
         need_dx is False).  Deterministic, stateless.  grad_precision: "fp32" (pp_down_backward, bit for bit), "bf16x3" or "bf16": the
         operands of the wgrad and dgrad products in split or plain bf16 on the bf16 MFMA, everything else (planes, statistics, mask,
         norm backward, tensors) fp32."""
-        mode = self._grad_mode(grad_precision, "down_backward")
-        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
-            raise ValueError(f"down_backward: x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
-        nb, cin, hin, win = (int(v) for v in x.shape)
-        cout = int(w.shape[0]) if isinstance(w, torch.Tensor) and w.dim() == 4 else 0
-        if (cin, cout) not in self.DOWN_PAIRS:
-            raise ValueError(f"down_backward: (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
-        ho, wo = (hin + 1) // 2, (win + 1) // 2
-        if hin < 1 or win < 1 or ho * wo < 2:
-            raise ValueError(f"down_backward: the output map needs at least two elements, got {ho} x {wo}")
-        x = _chk(x, torch.float32, (nb, cin, hin, win), "down_backward: x")
-        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), "down_backward: w")
-        z = _chk(z, torch.float32, (nb, cout, ho, wo), "down_backward: z")
-        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), "down_backward: dy")
-        self._on_device("down_backward", ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
-        if w.data_ptr() % 16:
-            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
-        dw = self._t((cout, cin, 3, 3), torch.float32)
-        dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.pp_down_backward_mp(self.ctx, mode, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(dy), nb, _ptr(dw), _ptr(dx),
-                                                    _stream()), self.ctx, "pp_down_backward_mp")
-        return dw, dx
+        return self._down_backward("down_backward", x, w, z, dy, need_dx, grad_precision=grad_precision)
 
     def backbone_stage_taps(self, canvas):
         """pp_backbone_stage_taps: backbone_block_taps(canvas) plus the raw output of block 3's strided convolution -> (rpn_out, x1,
@@ -759,107 +783,22 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_update_bn_fold(self.ctx, ptrs, _stream()), self.ctx, "pp_update_bn_fold")
 
-    def unit_backward_affine(self, u, w, scale, shift, dy, dskip=None, need_du=True, need_affine=True, _bn=None):
+    def unit_backward_affine(self, u, w, scale, shift, dy, dskip=None, need_du=True, need_affine=True):
         """pp_unit_backward_affine: unit_backward for the unit scale/shift -> ReLU -> Conv3x3 (frozen BatchNorm): scale, shift f32[C] are
         the folded values the forward used -> (dw, du or None, dscale, dshift); dscale = sum g u and dshift = sum g are f64[C], None
         when need_affine is False.  need_du=False needs need_affine=False.  fp32, deterministic, stateless."""
-        who = "unit_backward_bn" if _bn else "unit_backward_affine"
-        if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
-            raise ValueError(who + f": u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
-        nb, C, h, wd = (int(v) for v in u.shape)
-        if C not in (64, 128, 256):
-            raise ValueError(who + f": C must be 64, 128 or 256, got {C}")
-        if h < 1 or wd < 1 or h * wd < 2:
-            raise ValueError(who + f": the map needs at least two elements, got {h} x {wd}")
-        if need_affine and not need_du:
-            raise ValueError(who + ": the affine sums are sums over du's product: need_affine needs need_du")
-        u = _chk(u, torch.float32, (nb, C, h, wd), who + ": u")
-        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), who + ": w")
-        dy = _chk(dy, torch.float32, (nb, C, h, wd), who + ": dy")
-        if dskip is not None:
-            dskip = _chk(dskip, torch.float32, (nb, C, h, wd), who + ": dskip")
-        self._on_device(who, ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
-        scale, shift, (ds, dh) = self._affine_args(who, scale, shift, C, need_affine)
-        if w.data_ptr() % 16:
-            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
-        dw = self._t((C, C, 3, 3), torch.float32)
-        du = self._t((nb, C, h, wd), torch.float32) if need_du else None
-        with torch.cuda.device(self.device):
-            if _bn:
-                mean, var, chunk = self._bn_args(who, _bn, C)
-                _lib.check(self.lib.pp_unit_backward_bn(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(var), _ptr(dy),
-                                                        _ptr(dskip), nb, _ptr(dw), _ptr(du), _ptr(ds), _ptr(dh), chunk, _stream()), self.ctx,
-                           "pp_unit_backward_bn")
-            else:
-                _lib.check(self.lib.pp_unit_backward_affine(self.ctx, C, h, wd, _ptr(u), _ptr(w), _ptr(scale), _ptr(shift), _ptr(dy), _ptr(dskip), nb,
-                                                            _ptr(dw), _ptr(du), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_unit_backward_affine")
-        return dw, du, ds, dh
+        return self._unit_backward("unit_backward_affine", u, w, dy, dskip, need_du, affine=(scale, shift, need_affine))
 
-    def down_backward_affine(self, x, w, z, scale, shift, dy, need_dx=True, need_affine=True, _bn=None):
+    def down_backward_affine(self, x, w, z, scale, shift, dy, need_dx=True, need_affine=True):
         """pp_down_backward_affine: down_backward for the stage Conv3x3 stride 2 -> scale/shift -> ReLU (frozen BatchNorm) ->
         (dw, dx or None, dscale = sum g z, dshift = sum g: f64[Cout], None when need_affine is False).  fp32, deterministic, stateless."""
-        who = "down_backward_bn" if _bn else "down_backward_affine"
-        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
-            raise ValueError(who + f": x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
-        nb, cin, hin, win = (int(v) for v in x.shape)
-        cout = int(w.shape[0]) if isinstance(w, torch.Tensor) and w.dim() == 4 else 0
-        if (cin, cout) not in self.DOWN_PAIRS:
-            raise ValueError(who + f": (Cin, Cout) must be one of {self.DOWN_PAIRS}, got ({cin}, {cout})")
-        ho, wo = (hin + 1) // 2, (win + 1) // 2
-        if hin < 1 or win < 1 or ho * wo < 2:
-            raise ValueError(who + f": the output map needs at least two elements, got {ho} x {wo}")
-        x = _chk(x, torch.float32, (nb, cin, hin, win), who + ": x")
-        w = _chk(w.detach(), torch.float32, (cout, cin, 3, 3), who + ": w")
-        z = _chk(z, torch.float32, (nb, cout, ho, wo), who + ": z")
-        dy = _chk(dy, torch.float32, (nb, cout, ho, wo), who + ": dy")
-        self._on_device(who, ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
-        scale, shift, (ds, dh) = self._affine_args(who, scale, shift, cout, need_affine)
-        if w.data_ptr() % 16:
-            w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
-        dw = self._t((cout, cin, 3, 3), torch.float32)
-        dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
-        with torch.cuda.device(self.device):
-            if _bn:
-                mean, var, chunk = self._bn_args(who, _bn, cout)
-                _lib.check(self.lib.pp_down_backward_bn(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(scale), _ptr(shift), _ptr(mean),
-                                                        _ptr(var), _ptr(dy), nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), chunk, _stream()), self.ctx,
-                           "pp_down_backward_bn")
-            else:
-                _lib.check(self.lib.pp_down_backward_affine(self.ctx, cin, cout, hin, win, _ptr(x), _ptr(w), _ptr(z), _ptr(scale), _ptr(shift), _ptr(dy),
-                                                            nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_down_backward_affine")
-        return dw, dx, ds, dh
+        return self._down_backward("down_backward_affine", x, w, z, dy, need_dx, affine=(scale, shift, need_affine))
 
-    def neck_backward_affine(self, branch, x, w, scale, shift, y, dy, need_dx=True, need_affine=True, _bn=None):
+    def neck_backward_affine(self, branch, x, w, scale, shift, y, dy, need_dx=True, need_affine=True):
         """pp_neck_backward_affine: neck_backward for the branch ConvTranspose -> scale/shift -> ReLU (frozen BatchNorm); scale, shift
         f32[Cup] are the branch's -> (dw, dx or None, dscale = sum g Z, dshift = sum g: f64[Cup], None when need_affine is False).
         fp32, deterministic, stateless."""
-        who = "neck_backward_bn" if _bn else "neck_backward_affine"
-        if branch not in (0, 1, 2):
-            raise ValueError(who + f": branch must be 0, 1 or 2, got {branch!r}")
-        xs, wsh = self.neck_shapes(branch)
-        nb = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
-        if not 1 <= nb <= self.max_batch:
-            raise ValueError(who + f": x must be [nb,{xs[0]},{xs[1]},{xs[2]}] with 1 <= nb <= max_batch ({self.max_batch})")
-        x = _chk(x, torch.float32, (nb,) + xs, who + ": x")
-        w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, wsh, who + ": w")
-        y = _chk(y, torch.float32, (nb, 320, self.H, self.W), who + ": y")
-        dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), who + ": dy")
-        self._on_device(who, ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
-        scale, shift, (ds, dh) = self._affine_args(who, scale, shift, wsh[1], need_affine)
-        if w.data_ptr() % 16:
-            w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
-        dw = self._t(wsh, torch.float32)
-        dx = self._t((nb,) + xs, torch.float32) if need_dx else None
-        with torch.cuda.device(self.device):
-            if _bn:
-                mean, var, chunk = self._bn_args(who, _bn, wsh[1])
-                _lib.check(self.lib.pp_neck_backward_bn(self.ctx, branch, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(var), _ptr(y),
-                                                        _ptr(dy), nb, _ptr(dw), _ptr(dx), _ptr(ds), _ptr(dh), chunk, _stream()), self.ctx,
-                           "pp_neck_backward_bn")
-            else:
-                _lib.check(self.lib.pp_neck_backward_affine(self.ctx, branch, _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), _ptr(dy), nb, _ptr(dw),
-                                                            _ptr(dx), _ptr(ds), _ptr(dh), _stream()), self.ctx, "pp_neck_backward_affine")
-        return dw, dx, ds, dh
+        return self._neck_backward("neck_backward_affine", branch, x, w, y, dy, need_dx, affine=(scale, shift, need_affine))
 
     # ------------------------------------------------------------------ the BatchNorm backbone with batch statistics
     def unit_backward_bn(self, u, w, scale, shift, mean, var, dy, dskip=None, need_du=True, need_affine=True, chunk_frames=0):
@@ -867,17 +806,17 @@ class Engine:
         variance) and scale, shift their fold with the layer's weight and bias, as backbone_train_taps_bn hands them out -> (dw, du or
         None, dscale = sum g u, dshift = sum g: f64[C] pooled over all frames, None when need_affine is False); bn_affine_grad(dscale,
         dshift, mean, var) gives dgamma, dbeta.  chunk_frames > 0 caps the frames of a workspace chunk.  fp32, deterministic, stateless."""
-        return self.unit_backward_affine(u, w, scale, shift, dy, dskip=dskip, need_du=need_du, need_affine=need_affine, _bn=(mean, var, chunk_frames))
+        return self._unit_backward("unit_backward_bn", u, w, dy, dskip, need_du, affine=(scale, shift, need_affine), bn=(mean, var, chunk_frames))
 
     def down_backward_bn(self, x, w, z, scale, shift, mean, var, dy, need_dx=True, need_affine=True, chunk_frames=0):
         """pp_down_backward_bn: down_backward_affine in front of a train-mode BatchNorm2d (arguments as unit_backward_bn) -> (dw, dx or
         None, dscale = sum g z, dshift = sum g)."""
-        return self.down_backward_affine(x, w, z, scale, shift, dy, need_dx=need_dx, need_affine=need_affine, _bn=(mean, var, chunk_frames))
+        return self._down_backward("down_backward_bn", x, w, z, dy, need_dx, affine=(scale, shift, need_affine), bn=(mean, var, chunk_frames))
 
     def neck_backward_bn(self, branch, x, w, scale, shift, mean, var, y, dy, need_dx=True, need_affine=True, chunk_frames=0):
         """pp_neck_backward_bn: neck_backward_affine in front of a train-mode BatchNorm2d (arguments as unit_backward_bn) -> (dw, dx or
         None, dscale = sum g Z, dshift = sum g)."""
-        return self.neck_backward_affine(branch, x, w, scale, shift, y, dy, need_dx=need_dx, need_affine=need_affine, _bn=(mean, var, chunk_frames))
+        return self._neck_backward("neck_backward_bn", branch, x, w, y, dy, need_dx, affine=(scale, shift, need_affine), bn=(mean, var, chunk_frames))
 
     def backbone_train_taps_bn(self, canvas, bn_params, taps=True):
         """pp_backbone_train_taps_bn: the lock-step training forward of the BatchNorm backbone on canvases [nb,64,gx,gy], 1 <= nb <=

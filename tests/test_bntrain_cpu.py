@@ -222,7 +222,10 @@ def test_c_abi_is_declared_and_bound():
         assert m, name + " is not declared in include/pp_hip.h"
         nargs = len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
         assert name in protos and len(protos[name][1]) == nargs, (name, nargs)
-    # the InstanceNorm entries keep refusing the BatchNorm backbone
-    for src, name in (("block_train.hip", "pp_unit_backward"), ("down_train.hip", "pp_down_backward"), ("neck_train.hip", "pp_neck_backward")):
-        text = open(os.path.join(ROOT, "3d_object_detection_amd", "csrc", src)).read()
-        assert f'"{name}: the InstanceNorm backbone only' in text, name
+    # the InstanceNorm entries keep refusing the BatchNorm backbone: the entry runs its family's check (the family header) in the
+    # InstanceNorm form under its own name, and that form, and no other, refuses a context whose norm is not InstanceNorm
+    for stem, name in (("block_train", "pp_unit_backward"), ("down_train", "pp_down_backward"), ("neck_train", "pp_neck_backward")):
+        src, check = (open(os.path.join(ROOT, "3d_object_detection_amd", "csrc", stem + ext)).read() for ext in (".hip", ".h"))
+        assert re.search(r'_entry\(ctx, "' + name + r'", NORM_INSTANCE,', src), name
+        refusal = re.findall(r'if \(([^\n]*)\)\s*return train_fail\(ctx, entry, "the InstanceNorm backbone only', check)
+        assert refusal == ["shape && form == NORM_INSTANCE && ctx->cfg.norm_kind != 0"], (name, refusal)

@@ -5,7 +5,7 @@ flops / 157.3 TF (the constants bench.py uses).
 
     python tools/necktrain_probe.py [--frames 1,8] [--reps 10]
     rocprofv3 --kernel-trace --stats -d OUT -o necktrain -- python tools/necktrain_probe.py --frames 8 --no-torch   (per-kernel split:
-                                       k_neck_fwd, k_neck_stats, k_neck_dz, k_neck_dw, k_neck_dw_reduce, k_neck_dx, k_gather1)
+                                       k_neck_fwd, k_neck_stats, k_neck_dz, k_neck_dw, k_dw_reduce, k_neck_dx, k_gather1)
 Also timed in the same run: the same branch in stock PyTorch (conv_transpose2d -> instance_norm -> relu, .backward()), pp_backbone_taps
 against pp_backbone, and one whole fine-tuning step at nb = 8 with the neck trained (per-frame forward through pp_backbone_taps, head,
 loss, backward of head and neck, SGD step, weight upload).  Prints one JSON line."""
