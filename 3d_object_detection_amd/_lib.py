@@ -11,6 +11,7 @@ PP_ASSIGN_MAX_GT = 4096
 PP_AUG_MAX_BOXES = 256
 PP_AUG_MAX_TRIES = 128
 PP_AUG_PARAMS = 16
+PP_GT_CHUNK = 1024
 PP_OPT_CHUNK = 2048
 PP_OPT_GROUP = 32
 
@@ -126,6 +127,15 @@ PROTOTYPES = {
     "pp_augment_boxes": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
     "pp_augment_points": (ctypes.c_int, [c_p, c_p, c_p, ctypes.POINTER(c_i32), c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int,
                                          c_p, c_p]),
+    "pp_gt_count": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_i32), c_p, ctypes.POINTER(c_i32), ctypes.c_int, ctypes.POINTER(c_f), c_p, c_p]),
+    "pp_gt_extract": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_i32), c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_i64, c_p, c_p]),
+    "pp_gt_select": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_i32), c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p]),
+    "pp_gt_paste_count": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_i32), c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_i64, c_i64,
+                                         ctypes.c_int, c_p, c_p, c_p]),
+    "pp_gt_paste": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_i32), c_p, c_p, c_p, ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p, c_i64, c_i64,
+                                   ctypes.c_int, c_p, ctypes.POINTER(c_i32), c_p, c_p]),
+    "pp_gt_draw": (ctypes.c_int, [c_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i32), ctypes.c_int,
+                                  ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.c_int, c_p, c_p]),
     "pp_box_decode": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p]),
     "pp_corners2d": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_p]),
     "pp_standup2d": (ctypes.c_int, [c_p, c_p, c_i64, c_p]),

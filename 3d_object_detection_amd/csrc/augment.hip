@@ -17,6 +17,7 @@
 // A Python float meeting a float32 array is cast to float32 first (NEP 50, weak scalars): written as (float)x.
 #include <cstring>
 #include "pp_common.h"
+#include "aug_geom.h"
 
 namespace {
 
@@ -27,10 +28,6 @@ constexpr int BOX_THREADS = MAXB;
 constexpr int PTS_THREADS = 256;
 constexpr int PTS_PER_THREAD = 4;
 constexpr float TWO_PI_F = 6.28318530717958647692f; // 2 * np.pi as a weak Python float against a float32 array
-// P1 prefilter slack: 8 mm at 80 m.  The face-plane sign of a point at distance d outside a face is ~|n| d, its float32 rounding a
-// few ulp of |n| |p|: below 1e-4 (1 + |p|) for every box that fits the capacity, so the prefilter never rejects a point the
-// plane test would keep
-constexpr float AABB_PAD = 1e-4f;
 static_assert(NOISE_THREADS >= PP_AUG_MAX_TRIES && NOISE_THREADS % 64 == 0, "k_noise: one lane per try");
 static_assert(BOX_THREADS == MAXB && BOX_THREADS % 64 == 0, "k_boxes: one thread per box");
 static_assert(MAXB <= PTS_THREADS && PTS_THREADS == 256 && MAXB <= 32767, "k_points: one thread per box for the LDS setup, 4 waves, int16 list");
@@ -42,69 +39,6 @@ struct aug_args {
     int32_t T;                   // tries per box
     float range[4];              // x0, y0, x1, y1 of the range filter (float32, as detection_range[[0, 1, 3, 4]])
 };
-
-// corners_norm of box2d_to_corner_jit / center_to_corner_box2d: (-.5,-.5) (-.5,.5) (.5,.5) (.5,-.5)
-__device__ __constant__ float NX[4] = {-0.5f, -0.5f, 0.5f, 0.5f};
-__device__ __constant__ float NY[4] = {-0.5f, 0.5f, 0.5f, -0.5f};
-
-// box2d_to_corner_jit (box_np_ops.py:659-679) of one (x, y, l, w, r): (dims * norm) @ [[c, s], [-s, c]] + xy, float32
-__device__ __forceinline__ void bev_corners(float x, float y, float l, float w, float r, float* c)
-{
-    const float s = sinf(r), co = cosf(r);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float cx = l * NX[k], cy = w * NY[k];
-        c[2 * k] = (cx * co + cy * (-s)) + x;
-        c[2 * k + 1] = (cx * s + cy * co) + y;
-    }
-}
-
-// corner_to_standup_nd_jit: xmin, ymin, xmax, ymax
-__device__ __forceinline__ void standup(const float* c, float* s)
-{
-    s[0] = fminf(fminf(c[0], c[2]), fminf(c[4], c[6]));
-    s[1] = fminf(fminf(c[1], c[3]), fminf(c[5], c[7]));
-    s[2] = fmaxf(fmaxf(c[0], c[2]), fmaxf(c[4], c[6]));
-    s[3] = fmaxf(fmaxf(c[1], c[3]), fmaxf(c[5], c[7]));
-}
-
-// every corner of q strictly inside the clockwise box b (:661-676; vec = -(b[k] - b[k+1]))
-__device__ __forceinline__ bool inside_all(const float* b, const float* q)
-{
-    for (int l = 0; l < 4; ++l)
-        for (int k = 0; k < 4; ++k) {
-            const int k1 = (k + 1) & 3;
-            const float v0 = -(b[2 * k] - b[2 * k1]), v1 = -(b[2 * k + 1] - b[2 * k1 + 1]);
-            float cross = v1 * (b[2 * k] - q[2 * l]);
-            cross -= v0 * (b[2 * k + 1] - q[2 * l + 1]);
-            if (cross >= 0.f) return false;
-        }
-    return true;
-}
-
-// box_collision_test (:617-697) of one pair.  `ret[i, j] is True / is False` are value tests under numba (the deployed reference):
-// without an edge crossing, containment either way is a collision.
-__device__ bool collide(const float* b, const float* bs, const float* q, const float* qs)
-{
-    const float iw = fminf(bs[2], qs[2]) - fmaxf(bs[0], qs[0]);
-    if (!(iw > 0.f)) return false;
-    const float ih = fminf(bs[3], qs[3]) - fmaxf(bs[1], qs[1]);
-    if (!(ih > 0.f)) return false;
-    for (int k = 0; k < 4; ++k) {
-        const float A0 = b[2 * k], A1 = b[2 * k + 1], B0 = b[2 * ((k + 1) & 3)], B1 = b[2 * ((k + 1) & 3) + 1];
-        for (int l = 0; l < 4; ++l) {
-            const float C0 = q[2 * l], C1 = q[2 * l + 1], D0 = q[2 * ((l + 1) & 3)], D1 = q[2 * ((l + 1) & 3) + 1];
-            const bool acd = (D1 - A1) * (C0 - A0) > (C1 - A1) * (D0 - A0);
-            const bool bcd = (D1 - B1) * (C0 - B0) > (C1 - B1) * (D0 - B0);
-            if (acd != bcd) {
-                const bool abc = (C1 - A1) * (B0 - A0) > (B1 - A1) * (C0 - A0);
-                const bool abd = (D1 - A1) * (B0 - A0) > (B1 - A1) * (D0 - A0);
-                if (abc != abd) return true;
-            }
-        }
-    }
-    return inside_all(b, q) || inside_all(q, b);
-}
 
 __global__ void __launch_bounds__(NOISE_THREADS) k_noise(aug_args p, const float* __restrict__ boxes, const uint8_t* __restrict__ valid,
                                                          const double* __restrict__ loc, const double* __restrict__ rot,
@@ -320,22 +254,7 @@ __global__ void __launch_bounds__(BOX_THREADS) k_boxes(aug_args p, const float* 
 }
 
 // ---- device random mode ------------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11), key = the 64-bit seed, counter = (element, stream | epoch << 8, sample index lo, hi):
-// a frame's draws depend only on (seed, epoch, sample index), never on the batch it runs in.
-struct u32x4 {
-    uint32_t x, y, z, w;
-};
-__device__ __forceinline__ u32x4 philox(u32x4 c, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        c = u32x4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
+// Philox4x32-10 and the keyed Feistel bijection: aug_geom.h
 // 53-bit uniforms in [0, 1) from two words (numpy's random_standard_uniform construction)
 __device__ __forceinline__ double u53(uint32_t a, uint32_t b) { return (double)(((uint64_t)(a >> 5) << 26) | (b >> 6)) * 0x1.0p-53; }
 // Box-Muller in float64: (1 - u1) in (0, 1]
@@ -346,33 +265,10 @@ __device__ __forceinline__ void box_muller(double u1, double u2, double& z0, dou
     z1 = r * sin(t);
 }
 
-// keyed bijection of [0, n): a balanced Feistel network of FEISTEL_ROUNDS rounds on 2h >= ceil(log2 n) bits, cycle-walked back
-// into [0, n) (at most 4 steps expected).  The 64-bit key sits in prm[PP_AUG_KEY_LO / _HI] as exact doubles.
-constexpr int FEISTEL_ROUNDS = 8;
-__device__ __forceinline__ uint32_t mix32(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
+// the permutation's 64-bit key sits in prm[PP_AUG_KEY_LO / _HI] as exact doubles
 __device__ __forceinline__ uint32_t feistel(uint32_t k, uint32_t n, const double* P)
 {
-    if (n <= 1) return k;
-    const uint32_t k0 = (uint32_t)P[PP_AUG_KEY_LO], k1 = (uint32_t)P[PP_AUG_KEY_HI];
-    int bits = 32 - __clz(n - 1);
-    const int h = (bits + 1) >> 1;
-    const uint32_t mask = (1u << h) - 1u;
-    uint32_t x = k;
-    do {
-        uint32_t L = x >> h, R = x & mask;
-        for (int r = 0; r < FEISTEL_ROUNDS; ++r) {
-            const uint32_t F = mix32(R ^ (r & 1 ? k1 : k0) ^ (uint32_t)r * 0x9E3779B9u) & mask;
-            const uint32_t nl = R;
-            R = L ^ F;
-            L = nl;
-        }
-        x = (L << h) | R;
-    } while (x >= n);
-    return x;
+    return feistel_keyed(k, n, (uint32_t)P[PP_AUG_KEY_LO], (uint32_t)P[PP_AUG_KEY_HI]);
 }
 
 struct draw_args {
@@ -467,34 +363,7 @@ __global__ void __launch_bounds__(PTS_THREADS) k_points(aug_args p, const float4
         const int g = b0 + t;
         v = valid[g] != 0;
         const float* b = boxes + (size_t)g * 7;
-        // center_to_corner_box3d(origin (0.5, 0.5, 0.5), axis 2): corners_nd order, rotation_3d_in_axis's einsum, + centre
-        const float s = sinf(b[6]), co = cosf(b[6]);
-        float cx[8], cy[8], cz[8];
-        const int ux[8] = {0, 0, 0, 0, 1, 1, 1, 1}, uy[8] = {0, 0, 1, 1, 0, 0, 1, 1}, uz[8] = {0, 1, 1, 0, 0, 1, 1, 0};
-        float lo[3] = {3.4e38f, 3.4e38f, 3.4e38f}, hi[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-        for (int q = 0; q < 8; ++q) {
-            const float dx = b[3] * ((float)ux[q] - 0.5f), dy = b[4] * ((float)uy[q] - 0.5f), dz = b[5] * ((float)uz[q] - 0.5f);
-            cx[q] = (dx * co + dy * (-s)) + b[0];
-            cy[q] = (dx * s + dy * co) + b[1];
-            cz[q] = dz + b[2];
-            lo[0] = fminf(lo[0], cx[q]); hi[0] = fmaxf(hi[0], cx[q]);
-            lo[1] = fminf(lo[1], cy[q]); hi[1] = fmaxf(hi[1], cy[q]);
-            lo[2] = fminf(lo[2], cz[q]); hi[2] = fmaxf(hi[2], cz[q]);
-        }
-        // corner_to_surfaces_3d_jit + surface_equ_3d_jit: n = (P0 - P1) x (P1 - P2), d = n . P0
-        const int sf[6][3] = {{0, 1, 2}, {7, 6, 5}, {0, 3, 7}, {1, 5, 6}, {0, 4, 5}, {3, 2, 6}};
-        for (int q = 0; q < 6; ++q) {
-            const int i0 = sf[q][0], i1 = sf[q][1], i2 = sf[q][2];
-            const float ax = cx[i0] - cx[i1], ay = cy[i0] - cy[i1], az = cz[i0] - cz[i1];
-            const float bx = cx[i1] - cx[i2], by = cy[i1] - cy[i2], bz = cz[i1] - cz[i2];
-            const float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-            const float d = (nx * cx[i0] + ny * cy[i0]) + nz * cz[i0];
-            pl[t][q] = make_float4(nx, ny, nz, -d);
-        }
-        for (int q = 0; q < 3; ++q) {
-            bb[t][q] = lo[q] - AABB_PAD * (1.f + fabsf(lo[q]));
-            bb[t][3 + q] = hi[q] + AABB_PAD * (1.f + fabsf(hi[q]));
-        }
+        box_face_planes(b, pl[t], bb[t]);
         ctr[t][0] = b[0]; ctr[t][1] = b[1]; ctr[t][2] = b[2];
         const rot3 r = mk_rot(sel_rot[g]); // _rotation_matrix_3d_: float64 sin / cos into the float32 matrix
         mv[t][0] = r.c; mv[t][1] = r.s;
@@ -527,14 +396,7 @@ __global__ void __launch_bounds__(PTS_THREADS) k_points(aug_args p, const float4
             float x = q.x, y = q.y, zz = q.z;
             for (int e = 0; e < nv; ++e) {
                 const int j = list[e];
-                if (x < bb[j][0] || x > bb[j][3] || y < bb[j][1] || y > bb[j][4] || zz < bb[j][2] || zz > bb[j][5]) continue;
-                bool in = true;
-                for (int h = 0; h < 6 && in; ++h) {
-                    const float4 a = pl[j][h];
-                    const float sgn = ((x * a.x + y * a.y) + zz * a.z) + a.w;
-                    in = sgn < 0.f; // outside at sign >= 0
-                }
-                if (!in) continue;
+                if (!inside_box(x, y, zz, pl[j], bb[j])) continue;
                 // points_transform_: -= centre, @ yaw matrix, += centre, += loc (float64)
                 const float c = mv[j][0], s = mv[j][1];
                 const float px = x - ctr[j][0], py = y - ctr[j][1], pz = zz - ctr[j][2];

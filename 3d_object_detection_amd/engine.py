@@ -1440,6 +1440,142 @@ class Engine:
                                                   _ptr(prm), boff, nb, _ptr(out), _stream()), self.ctx, "pp_augment_points")
         return out
 
+    # ------------------------------------------------------------------ ground-truth database sampling (gt_sample.hip)
+    def _gt_cloud(self, points, pt_off, what):
+        P = int(points.shape[0]) if points.dim() == 2 else -1
+        points = _chk(points, torch.float32, (P, 4), what + ": points")
+        off, nb = self._csr(pt_off, P, what + ": point offsets")
+        return points, off, nb
+
+    def _gt_rows(self, boxes, off, what, per_frame=None):
+        G = int(boxes.shape[0]) if boxes.dim() == 2 else -1
+        boxes = _chk(boxes, torch.float32, (G, 7), what)
+        if G > _lib.PP_ASSIGN_MAX_GT:
+            raise ValueError(f"{what}: {G} rows exceed the capacity {_lib.PP_ASSIGN_MAX_GT}")
+        off, nb = self._csr(off, G, what + " offsets", per_frame)
+        return boxes, off, nb, G
+
+    def gt_count(self, points, pt_off, boxes, box_off, extra=(0.0, 0.0, 0.0)):
+        """pp_gt_count: points f32[P,4] and boxes f32[G,7] of nb frames (host CSR offsets) -> i32[G], the points of its frame inside each
+        box after `extra` is added to (l, w, h): (0, 0, 0) create_info's num_points, (1.2, 0.5, 8) its difficulty."""
+        points, poff, nb = self._gt_cloud(points, pt_off, "gt_count")
+        boxes, boff, nbb, G = self._gt_rows(boxes, box_off, "gt_count: boxes")
+        if nbb != nb:
+            raise ValueError("gt_count: point and box offsets describe different frame counts")
+        ex = (ctypes.c_float * 3)(*[float(v) for v in extra])
+        counts = self._t((G,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_gt_count(self.ctx, _ptr(points), poff, _ptr(boxes), boff, nb, ex, _ptr(counts), _stream()), self.ctx,
+                       "pp_gt_count")
+        return counts
+
+    def gt_extract(self, points, pt_off, boxes, box_off, obj_off, total, out=None):
+        """pp_gt_extract: obj_off i64[G+1] on the device (the counts' exclusive scan, the total last), total = its last value on the
+        host -> f32[total,4]: per box its member points in the cloud's order, xyz minus the box centre."""
+        points, poff, nb = self._gt_cloud(points, pt_off, "gt_extract")
+        boxes, boff, nbb, G = self._gt_rows(boxes, box_off, "gt_extract: boxes")
+        if nbb != nb:
+            raise ValueError("gt_extract: point and box offsets describe different frame counts")
+        obj_off = _chk(obj_off, torch.int64, (G + 1,), "gt_extract: obj_off")
+        T = int(total)
+        if T < 0:
+            raise ValueError("gt_extract: negative total")
+        out = self._t((T, 4), torch.float32) if out is None else _chk(out, torch.float32, (T, 4), "gt_extract: out")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_gt_extract(self.ctx, _ptr(points), poff, _ptr(boxes), boff, nb, _ptr(obj_off), T, _ptr(out), _stream()),
+                       self.ctx, "pp_gt_extract")
+        return out
+
+    def gt_select(self, boxes, box_off, cand, cand_off):
+        """pp_gt_select: existing boxes f32[G,7] and candidates f32[Gc,7] (in decision order) of nb frames -> accept u8[Gc]: a candidate
+        is accepted iff it collides with no existing box and no earlier accepted candidate of its frame."""
+        boxes, boff, nb, _ = self._gt_rows(boxes, box_off, "gt_select: boxes")
+        cand, coff, nbc, Gc = self._gt_rows(cand, cand_off, "gt_select: candidates")
+        if nbc != nb:
+            raise ValueError("gt_select: box and candidate offsets describe different frame counts")
+        if any((boff[f + 1] - boff[f]) + (coff[f + 1] - coff[f]) > _lib.PP_AUG_MAX_BOXES for f in range(nb)):
+            raise ValueError(f"gt_select: more than {_lib.PP_AUG_MAX_BOXES} existing + candidate boxes in one frame (PP_AUG_MAX_BOXES)")
+        accept = self._t((Gc,), torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_gt_select(self.ctx, _ptr(boxes), boff, _ptr(cand), coff, nb, _ptr(accept), _stream()), self.ctx, "pp_gt_select")
+        return accept
+
+    def _gt_paste_args(self, points, pt_off, cand, cand_idx, accept, cand_off, db_points, db_off, what):
+        points, poff, nb = self._gt_cloud(points, pt_off, what)
+        cand, coff, nbc, Gc = self._gt_rows(cand, cand_off, what + ": candidates", _lib.PP_AUG_MAX_BOXES)
+        if nbc != nb:
+            raise ValueError(f"{what}: point and candidate offsets describe different frame counts")
+        n_db = int(db_off.shape[0]) - 1
+        T = int(db_points.shape[0]) if db_points.dim() == 2 else -1
+        db_points = _chk(db_points, torch.float32, (T, 4), what + ": db_points")
+        db_off = _chk(db_off, torch.int64, (n_db + 1,), what + ": db_off")
+        if not isinstance(cand_idx, torch.Tensor):  # host indices are refused here; device ones are checked by the kernels
+            ci = np.asarray(cand_idx, dtype=np.int64).reshape(-1)
+            if ci.size and (ci.min() < 0 or ci.max() >= n_db):
+                raise ValueError(f"{what}: a candidate index outside the database of {n_db} objects")
+            cand_idx = torch.from_numpy(ci.astype(np.int32)).to(self.device)
+        cand_idx = _chk(cand_idx, torch.int32, (Gc,), what + ": cand_idx")
+        accept = _chk(accept.view(torch.uint8) if accept.dtype == torch.bool else accept, torch.uint8, (Gc,), what + ": accept")
+        n = [poff[f + 1] - poff[f] for f in range(nb)]
+        chunks = sum(-(-v // _lib.PP_GT_CHUNK) for v in n)
+        return points, poff, nb, cand, coff, cand_idx, accept, db_points, db_off, n_db, T, chunks
+
+    def gt_paste_count(self, points, pt_off, cand, cand_idx, accept, cand_off, db_points, db_off, remove=True):
+        """pp_gt_paste_count -> (out_n i32[nb], blk): per frame the points of the accepted objects + the scene points that survive
+        (remove: a scene point inside an accepted candidate box is dropped); blk is the per-chunk workspace gt_paste reads."""
+        a = self._gt_paste_args(points, pt_off, cand, cand_idx, accept, cand_off, db_points, db_off, "gt_paste_count")
+        points, poff, nb, cand, coff, cand_idx, accept, db_points, db_off, n_db, T, chunks = a
+        blk = self._t((chunks,), torch.int32)
+        out_n = self._t((nb,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_gt_paste_count(self.ctx, _ptr(points), poff, _ptr(cand), _ptr(cand_idx), _ptr(accept), coff, nb, _ptr(db_off),
+                                                  n_db, T, int(bool(remove)), _ptr(blk), _ptr(out_n), _stream()), self.ctx, "pp_gt_paste_count")
+        return out_n, blk
+
+    def gt_paste(self, points, pt_off, cand, cand_idx, accept, cand_off, db_points, db_off, blk, out_off, remove=True, out=None):
+        """pp_gt_paste: out_off host ints [nb+1] (the CSR of gt_paste_count's out_n), blk from gt_paste_count with the same arguments ->
+        f32[out_off[-1],4]: per frame the accepted objects in candidate order (local + box centre), then the surviving scene points."""
+        a = self._gt_paste_args(points, pt_off, cand, cand_idx, accept, cand_off, db_points, db_off, "gt_paste")
+        points, poff, nb, cand, coff, cand_idx, accept, db_points, db_off, n_db, T, chunks = a
+        blk = _chk(blk, torch.int32, (chunks,), "gt_paste: blk")
+        N = int(out_off[-1]) if len(out_off) else 0
+        ooff, nbo = self._csr(out_off, N, "gt_paste: output offsets")
+        if nbo != nb:
+            raise ValueError("gt_paste: output offsets describe another frame count")
+        out = self._t((N, 4), torch.float32) if out is None else _chk(out, torch.float32, (N, 4), "gt_paste: out")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_gt_paste(self.ctx, _ptr(points), poff, _ptr(cand), _ptr(cand_idx), _ptr(accept), coff, nb, _ptr(db_points),
+                                            _ptr(db_off), n_db, T, int(bool(remove)), _ptr(blk), ooff, _ptr(out), _stream()), self.ctx,
+                       "pp_gt_paste")
+        return out
+
+    def gt_draw(self, seed, epoch, samples, class_off, counts):
+        """pp_gt_draw (device random mode): counts host ints [nb][C], class_off host ints [C+1] (the database's class offsets) ->
+        (cand_idx i32[Gc], cand_off list [nb+1]): per frame and class the first counts[f][c] values of the keyed bijection on the class's
+        objects, a function of (seed, epoch, samples[f], class) only."""
+        samples = [int(s) for s in samples]
+        nb = len(samples)
+        k = np.ascontiguousarray(counts, dtype=np.int32).reshape(nb, -1)
+        C = k.shape[1]
+        co = [int(v) for v in class_off]
+        if len(co) != C + 1 or not 1 <= C <= _lib.PP_MAX_CLASSES or co[0] != 0 or any(b < a for a, b in zip(co, co[1:])):
+            raise ValueError("gt_draw: class_off must be C + 1 non-decreasing values from 0, C = 1 .. PP_MAX_CLASSES")
+        if nb < 1 or (k < 0).any() or (k > np.diff(co)[None, :]).any():
+            raise ValueError("gt_draw: a count outside 0 .. the class's objects")
+        if not 0 <= int(epoch) < (1 << 24) or not 0 <= int(seed) < (1 << 64) or any(s < 0 for s in samples):
+            raise ValueError("gt_draw: seed must fit 64 bits, epoch 24 bits, sample indices must be >= 0")
+        cand_off = [0] + np.cumsum(k.sum(axis=1)).tolist()
+        Gc = cand_off[-1]
+        if Gc > _lib.PP_ASSIGN_MAX_GT:
+            raise ValueError(f"gt_draw: {Gc} candidates exceed the capacity {_lib.PP_ASSIGN_MAX_GT}")
+        coff, _ = self._csr(cand_off, Gc, "gt_draw: candidate offsets", _lib.PP_AUG_MAX_BOXES)
+        cand_idx = self._t((Gc,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_gt_draw(self.ctx, int(seed), int(epoch), (ctypes.c_int64 * nb)(*samples), (ctypes.c_int32 * (C + 1))(*co), C,
+                                           k.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), coff, nb, _ptr(cand_idx), _stream()), self.ctx,
+                       "pp_gt_draw")
+        return cand_idx, cand_off
+
     def dominant_kernel(self):
         return self.lib.pp_dominant_kernel(self.ctx).decode()
 

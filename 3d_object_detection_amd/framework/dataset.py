@@ -2,7 +2,15 @@
 voxelise + anchor mask -> example dict.  The augmentation, voxeliser, anchor mask and target assignment run on the device; the host
 keeps the random draws (framework.augmentation.draw_frame) and the file reads.  CUDA does not survive fork: use num_workers=0 with a
 torch DataLoader, or get_batch, which runs the augmentation of B frames as one set of launches (voxeliser and anchor mask per
-frame, target assignment once)."""
+frame, target assignment once).
+
+config["gt_sampler"] (framework.gt_sampler) switches ground-truth database sampling on for training with augm=True: after the class
+filter and in front of the chain, recorded objects are selected (greedy collision rejection) and pasted into the cloud on the device;
+the accepted boxes, classes, names and difficulty are appended behind the frame's own (valid True; the frame's own boxes keep the
+dataset.py:126-127 quirk) and the unchanged chain runs on the new cloud and boxes, so noise_per_object moves pasted objects too and the
+permutation covers the new point count.  Cost: one extra small D2H per batch (accept flags, candidate rows, output sizes) in device
+mode; numpy mode runs select / paste frame by frame, because a frame's draw_frame draws need its new point and box counts and must
+follow its own sampling draws in the stream.  Without the key nothing of this is entered."""
 import time
 from pathlib import Path
 
@@ -12,6 +20,7 @@ import torch
 from .. import kitti_io
 from ..engine import engine_for
 from . import augmentation as agm
+from . import gt_sampler as gts
 
 
 class InferData:
@@ -79,6 +88,9 @@ class GenericDataset:
         self.seed = 0 if seed is None else int(seed)
         if seed is not None and rng == "numpy":
             np.random.seed(seed)
+        self.sampler = None
+        if training and augm and 'gt_sampler' in config:
+            self.sampler = gts.GtSampler(config, gts.GtDatabase.load(self.data_root / config['gt_sampler']['database']))
 
     def __len__(self):
         return len(self.infos)
@@ -113,8 +125,33 @@ class GenericDataset:
                       valid=augm_class_mask[:gt_boxes.shape[0]])
         draws = None
         if self.rng == "numpy":
+            if self.sampler is not None:  # the sampling draws first, then select / paste: draw_frame needs the new counts
+                rows = self.sampler.draw_numpy(gt['classes'])
+                points, gt, gt['sample'] = gts.paste_frames(self._engine(), self.sampler, [points], [gt], cand_rows=[rows])[0]
             draws = agm.draw_frame(points.shape[0], 0 if gt is None else gt['boxes'].shape[0], self.training, self.augm)
         return ex, points, gt, draws, idx
+
+    def _sample_device(self, frames):
+        """Device mode: select -> paste for the frames of one batch as one set of launches, keyed by (seed, epoch, index)."""
+        if self.sampler is None or self.rng != "device":
+            return frames
+        res = gts.paste_frames(self._engine(), self.sampler, [f[1] for f in frames], [f[2] for f in frames],
+                               draw=(self.seed, self.epoch, [f[4] for f in frames]))
+        out = []
+        for f, (points, gt, record) in zip(frames, res):
+            gt['sample'] = record
+            out.append((f[0], points, gt, f[3], f[4]))
+        return out
+
+    def export_samples(self, indices):
+        """Test hook: per frame the sampling record of paste_frames -- the frame's own boxes, the candidates' database rows in
+        decision order, the accept flags -- plus the cloud and boxes as they enter the chain.  numpy mode consumes the stream as
+        __getitem__ does."""
+        if self.sampler is None:
+            raise ValueError("export_samples: the dataset has no gt_sampler")
+        frames = self._sample_device([self._read(i) for i in indices])
+        return [dict(f[2]['sample'], points=f[1].cpu().numpy(), gt_boxes=f[2]['boxes'].copy(), gt_classes=f[2]['classes'].copy(),
+                     valid=f[2]['valid'].copy()) for f in frames]
 
     def _run(self, frames):
         """Device part for the frames of one batch: one set of augmentation launches, then per frame the voxeliser and the anchor
@@ -122,8 +159,12 @@ class GenericDataset:
         eng = self._engine()
         dev = eng.device
         nb = len(frames)
+        frames = self._sample_device(frames)
         pt_off = np.concatenate([[0], np.cumsum([f[1].shape[0] for f in frames])]).astype(np.int64).tolist()
-        pts = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[1] for f in frames]), dtype=np.float32)).to(dev)
+        if isinstance(frames[0][1], torch.Tensor):  # pasted clouds are on the device already
+            pts = torch.cat([f[1] for f in frames])
+        else:
+            pts = torch.from_numpy(np.ascontiguousarray(np.concatenate([f[1] for f in frames]), dtype=np.float32)).to(dev)
         if self.training:
             gts = [f[2] for f in frames]
             box_off = np.concatenate([[0], np.cumsum([g['boxes'].shape[0] for g in gts])]).astype(np.int64).tolist()
@@ -168,7 +209,7 @@ class GenericDataset:
         """Test hook (device mode): the drawn records of these frames as host draw_frame dicts, the permutation included."""
         if self.rng != "device" or not self.training:
             raise ValueError("export_params: only a training dataset in device mode draws on the device")
-        frames = [self._read(i) for i in indices]
+        frames = self._sample_device([self._read(i) for i in indices])
         eng = self._engine()
         box_off = np.concatenate([[0], np.cumsum([f[2]['boxes'].shape[0] for f in frames])]).astype(np.int64).tolist()
         pt_off = np.concatenate([[0], np.cumsum([f[1].shape[0] for f in frames])]).astype(np.int64).tolist()

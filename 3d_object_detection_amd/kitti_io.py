@@ -9,6 +9,7 @@
   run_sequence(...)              clouds -> annos through pp_infer_batch, B frames per pass, one D2H per pass
   save_detections / load_detections   the `dt_info` pickle                        (train.py:264-265)
   gt_from_annos(annos, ...)      annos -> (gt_classes, gt_boxes) as GenericDataset builds them (dataset.py:108-140, no augmentation)
+  point_counts(points, boxes)    (num_points, difficulty) of an info's annotations   (create_info.py:159-183)
   sequence_loss(...)             validation loss and Metric over a labelled sequence: pp_infer_batch + pp_batch_loss per pass
   pointcloud2_to_points(msg)     sensor_msgs/PointCloud2 payload -> f32[N,4] on the device   (ros_node.py:55-59)
 
@@ -208,6 +209,27 @@ def gt_from_annos(annos, detect_class, detection_range):
     boxes, cls = boxes[m], cls[m]
     boxes[:, 6] = boxes[:, 6] - np.floor(boxes[:, 6] / (2 * np.pi) + 0.5) * (2 * np.pi)
     return cls, boxes
+
+
+# create_info.py:180: the box grows by this (l, w, h) before the second count
+DIFFICULTY_EXTRA = (1.2, 0.5, 8.0)
+
+
+def point_counts(points, boxes, config=None):
+    """add_difficulty_to_annos_v2 (create_info.py:159-183): per lidar box (x, y, z, l, w, h, r) the points inside it
+    (annos["num_points"]) and inside the box grown by (1.2, 0.5, 8) (annos["difficulty"]), counted on the device (pp_gt_count) in
+    float32.  points f32[N,4], boxes [M,7], numpy or device tensors -> two i32[M] numpy arrays.  config: the engine's, default the
+    augmentation's (a live engine, else the shipped eight_20cm one)."""
+    from .framework.augmentation import _engine
+    eng = engine_for(config) if config is not None else _engine()
+    as_dev = lambda a: (a.to(eng.device, torch.float32).contiguous() if isinstance(a, torch.Tensor)
+                        else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(eng.device))
+    pts, bx = as_dev(points).reshape(-1, 4), as_dev(boxes).reshape(-1, 7)
+    off_p, off_b = [0, int(pts.shape[0])], [0, int(bx.shape[0])]
+    num = eng.gt_count(pts, off_p, bx, off_b)
+    diff = eng.gt_count(pts, off_p, bx, off_b, DIFFICULTY_EXTRA)
+    host = torch.stack([num, diff]).cpu().numpy()
+    return host[0], host[1]
 
 
 def sequence_loss(config, clouds, gts, batch=16, nms_mode=0):

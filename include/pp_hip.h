@@ -712,6 +712,53 @@ int pp_augment_points(pp_ctx* ctx, const float* pts, const int32_t* perm, const 
                       const uint8_t* valid, const double* sel_loc, const double* sel_rot, const double* prm, const int32_t* box_off_h,
                       int nb, float* out, void* stream);
 
+/* ---- ground-truth database sampling (the `# sample` slot of framework/dataset.py:123; a build-side extension: the reference has the
+ * slot and the helpers -- points_in_rbbox, box_collision_test, remove_points_in_boxes -- but no sampler) ----
+ * All entries run nb frames on `stream` with no host synchronisation; *_off_h are HOST i32[nb+1] CSR offsets, box rows are
+ * (x, y, z, l, w, h, r), points f32[.][4] (16-byte aligned).  Membership is points_in_rbbox with origin (0.5, 0.5, 0.5): inside at
+ * sign < 0 on all six faces, the planes pp_augment_points builds.  Collision is box_collision_test on the BEV corners as
+ * pp_augment_noise evaluates it (containment collides), the candidate as `boxes`, the other box as `qboxes`.  At most
+ * PP_ASSIGN_MAX_GT box / candidate rows per call.  PP_E_ARG for null or misaligned pointers, offsets that do not start at 0 or
+ * decrease, and counts above the capacities; nothing is launched then.  Two runs are bit-identical: every order comes from ballots
+ * and prefix counts, never from atomics. */
+#define PP_GT_CHUNK 1024 /* scene points per entry of `blk` (pp_gt_paste_count / pp_gt_paste) */
+/* counts i32[G]: per box the points of its frame inside it after extra_h (HOST f32[3]) is added to (l, w, h) in float32; a point
+ * inside two boxes counts in both.  extra (0, 0, 0): annos["num_points"] of create_info.py:175-177; (1.2, 0.5, 8): its "difficulty". */
+int pp_gt_count(pp_ctx* ctx, const float* pts, const int32_t* pt_off_h, const float* boxes, const int32_t* box_off_h, int nb,
+                const float* extra_h, int32_t* counts, void* stream);
+/* out f32[T][4]: box g's member points (extra 0) in the cloud's order at rows obj_off[g] .. obj_off[g+1]-1 (DEVICE i64[G+1], the
+ * counts' exclusive scan with the total behind), xyz minus the box centre (one float32 subtraction each), feature 3 copied.  No row
+ * outside an object's range or outside [0, T) is written, whatever obj_off holds. */
+int pp_gt_extract(pp_ctx* ctx, const float* pts, const int32_t* pt_off_h, const float* boxes, const int32_t* box_off_h, int nb,
+                  const int64_t* obj_off, int64_t T, float* out, void* stream);
+/* accept u8[Gc]: per frame the candidates (cand f32[Gc][7], cand_off_h, already in decision order) taken in order: candidate j is
+ * accepted iff it collides with no existing box of the frame (boxes f32[G][7], box_off_h; valid or not) and with no earlier ACCEPTED
+ * candidate.  existing + candidates of a frame <= PP_AUG_MAX_BOXES. */
+int pp_gt_select(pp_ctx* ctx, const float* boxes, const int32_t* box_off_h, const float* cand, const int32_t* cand_off_h, int nb,
+                 uint8_t* accept, void* stream);
+/* The database is device-resident: db_points f32[db_T][4] (object-local xyz), db_off i64[n_db+1]; candidate g is object
+ * cand_idx[g] (i32[Gc]).  A candidate whose index lies outside [0, n_db) or whose rows lie outside [0, db_T) counts as NOT accepted
+ * in both entries, and nothing of it is read.  At most PP_AUG_MAX_BOXES candidates per frame.
+ * pp_gt_paste_count: out_n i32[nb] = the points of the frame's accepted objects + its surviving scene points; remove != 0 drops a
+ * scene point inside any accepted candidate box (remove_points_in_boxes).  blk i32[sum_f ceil(n_f / PP_GT_CHUNK)] receives the
+ * survivors per chunk of scene points and is read back by pp_gt_paste (same arguments, same stream).
+ * pp_gt_paste: out f32[out_off_h[nb]][4], per frame (out_off_h: HOST CSR of out_n) the accepted objects in candidate order, each
+ * point local + the candidate box's centre (one float32 addition each), then the surviving scene points in their order, bits
+ * unchanged.  No row outside the frame's slot is written. */
+int pp_gt_paste_count(pp_ctx* ctx, const float* pts, const int32_t* pt_off_h, const float* cand, const int32_t* cand_idx,
+                      const uint8_t* accept, const int32_t* cand_off_h, int nb, const int64_t* db_off, int64_t n_db, int64_t db_T,
+                      int remove, int32_t* blk, int32_t* out_n, void* stream);
+int pp_gt_paste(pp_ctx* ctx, const float* pts, const int32_t* pt_off_h, const float* cand, const int32_t* cand_idx, const uint8_t* accept,
+                const int32_t* cand_off_h, int nb, const float* db_points, const int64_t* db_off, int64_t n_db, int64_t db_T, int remove,
+                const int32_t* blk, const int32_t* out_off_h, float* out, void* stream);
+/* device random mode: cand_idx i32[Gc], for frame f the classes in order, class c contributing k_h[f][c] (HOST i32[nb][num_classes],
+ * 0 .. n_c) rows: class_off_h[c] + the first k values of the keyed Feistel bijection on [0, n_c) (the one pp_augment_points uses),
+ * n_c = class_off_h[c+1] - class_off_h[c] (HOST i32[num_classes+1]), so no object is drawn twice.  The key is Philox4x32-10 of
+ * (seed, counter (class, stream 16 | epoch << 8, sample_h[f])): a stream pp_augment_draw does not use; the draw depends on (seed,
+ * epoch, sample index, class) only.  cand_off_h must equal the row sums of k_h. */
+int pp_gt_draw(pp_ctx* ctx, uint64_t seed, uint32_t epoch, const int64_t* sample_h, const int32_t* class_off_h, int num_classes,
+               const int32_t* k_h, const int32_t* cand_off_h, int nb, int32_t* cand_idx, void* stream);
+
 /* ---- evaluation ----
  * pp_rotated_iou_eval replaces rotate_iou_gpu_eval (eval/iou.py:540-638): out[i,j] for box i and query j with
  * criterion -1: IoU, 0: inter / area(query), 1: inter / area(box), 2: intersection area -- the reference's kernel
