@@ -8,6 +8,7 @@ also builds in __init__ (voxel_generator.py:6-26, anchor_assigner.py:221-298).
 import ctypes
 import os
 import re
+import typing
 import weakref
 
 import numpy as np
@@ -138,6 +139,18 @@ def _chk(t, dtype, shape, what):
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class BackwardNorm(typing.NamedTuple):
+    """The BatchNorm2d of a layer, as Engine.unit_backward / down_backward / neck_backward take it (norm=...): scale, shift f32[C]
+    are the folded values the forward used.  Without mean / var the statistics are frozen (pp_*_backward_affine); with them, f32[C],
+    they are the batch's (biased variance) and the norm is differentiated through them (pp_*_backward_bn)."""
+    scale: torch.Tensor
+    shift: torch.Tensor
+    mean: torch.Tensor = None
+    var: torch.Tensor = None
+    need_affine: bool = True  # also return dscale, dshift f64[C], the sums from which bn_affine_grad makes dgamma, dbeta
+    chunk_frames: int = 0     # > 0 caps the frames of a workspace chunk (batch statistics only)
 
 
 class Engine:
@@ -465,10 +478,11 @@ class Engine:
                        self.ctx, "pp_backbone_taps")
         return (out, *taps)
 
-    # The three families' backwards come in three norm forms behind one helper per family (_neck_backward, _unit_backward,
-    # _down_backward): InstanceNorm (affine=None; grad_precision picks the mode of pp_*_backward_mp), a frozen BatchNorm
-    # (affine=(scale, shift, need_affine): pp_*_backward_affine) and a train-mode BatchNorm (bn=(mean, var, chunk_frames) as well:
-    # pp_*_backward_bn).  `who` is the public method, for messages.
+    # The three families' backwards (neck_backward, unit_backward, down_backward) come in three norm forms, chosen by norm=:
+    # InstanceNorm (None; grad_precision picks the mode of pp_*_backward_mp and the method returns (dw, dx)), a frozen BatchNorm (a
+    # BackwardNorm without statistics: pp_*_backward_affine) and a train-mode BatchNorm (one with mean and var: pp_*_backward_bn);
+    # the BatchNorm forms are fp32 and return (dw, dx, dscale, dshift).  The *_affine / *_bn methods are the same calls with the
+    # record's fields as arguments.  `who` is the method the form goes by, for messages.
     def _backward_path(self, entry, grad_precision, *ints):
         """One pp_*_backward_path entry: the precision that family's backward really runs at these shapes."""
         mode = self._grad_mode(grad_precision, entry[3:])
@@ -477,24 +491,45 @@ class Engine:
             _lib.check(-rc, self.ctx, entry)
         return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
 
-    def _norm_args(self, who, C, affine, bn):
+    def _backward_form(self, name, norm, grad_precision):
+        """-> (who, the mode argument that leads an InstanceNorm entry's list: none for the BatchNorm forms, which are fp32)."""
+        if norm is None:
+            return name, [self._grad_mode(grad_precision, name)]
+        who = name + ("_affine" if norm.mean is None else "_bn")
+        if grad_precision != "fp32":
+            raise ValueError(f"{who}: the BatchNorm backward is fp32 (grad_precision='fp32'), got {grad_precision!r}")
+        return who, []
+
+    def _norm_args(self, who, C, norm):
         """The norm form of a backward over C normalised channels -> (the entry's suffix, the norm's tensors, the arguments behind the
         outputs, the affine sums the caller gets back: () for InstanceNorm)."""
-        if affine is None:
+        if norm is None:
             return "_mp", [], [], ()
-        scale, shift, sums = self._affine_args(who, *affine[:2], C, affine[2])
-        if bn is None:
+        scale = _chk(norm.scale, torch.float32, (C,), f"{who}: scale")
+        shift = _chk(norm.shift, torch.float32, (C,), f"{who}: shift")
+        self._on_device(who, ((scale, "scale"), (shift, "shift")))
+        sums = (self._t((C,), torch.float64), self._t((C,), torch.float64)) if norm.need_affine else (None, None)
+        if norm.mean is None:
             return "_affine", [scale, shift], list(sums), sums
-        mean, var, chunk = self._bn_args(who, bn, C)
-        return "_bn", [scale, shift, mean, var], [*sums, chunk], sums
+        mean = _chk(norm.mean, torch.float32, (C,), f"{who}: mean")
+        var = _chk(norm.var, torch.float32, (C,), f"{who}: var")
+        self._on_device(who, ((mean, "mean"), (var, "var")))
+        if not isinstance(norm.chunk_frames, int) or norm.chunk_frames < 0:
+            raise ValueError(f"{who}: chunk_frames must be an int >= 0, got {norm.chunk_frames!r}")
+        return "_bn", [scale, shift, mean, var], [*sums, norm.chunk_frames], sums
 
     def _call_backward(self, entry, *args):
         """One training backward of the library on the current stream; tensors (or None) go as pointers, ints as they are."""
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, entry)(self.ctx, *[_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args], _stream()), self.ctx, entry)
 
-    def _neck_backward(self, who, branch, x, w, y, dy, need_dx, affine=None, bn=None, grad_precision=None):
-        mode = [self._grad_mode(grad_precision, who)] if affine is None else []
+    def neck_backward(self, branch, x, w, y, dy, need_dx=True, grad_precision="fp32", norm=None):
+        """pp_neck_backward_mp: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
+        dL/d(rpn_out) dy [nb,320,H,W] -> (dw [Cin,Cup,s,s] summed over the frames, dx [nb,Cin,h,w] or None when need_dx is False).
+        Deterministic, stateless.  grad_precision: "fp32" (pp_neck_backward, bit for bit), "bf16x3" or "bf16": the operands of the dw
+        and dx products in split or plain bf16 on the bf16 MFMA, everything else (Z, statistics, mask, dZ, tensors) fp32.
+        norm: a BackwardNorm for the branch behind a BatchNorm2d (neck_backward_affine / neck_backward_bn) -> (dw, dx, dscale, dshift)."""
+        who, mode = self._backward_form("neck_backward", norm, grad_precision)
         if branch not in (0, 1, 2):
             raise ValueError(who + f": branch must be 0, 1 or 2, got {branch!r}")
         xs, wsh = self.neck_shapes(branch)
@@ -506,7 +541,7 @@ class Engine:
         y = _chk(y, torch.float32, (nb, 320, self.H, self.W), who + ": y")
         dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), who + ": dy")
         self._on_device(who, ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
-        suffix, norm, tail, sums = self._norm_args(who, wsh[1], affine, bn)
+        suffix, norm, tail, sums = self._norm_args(who, wsh[1], norm)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
         dw = self._t(wsh, torch.float32)
@@ -519,13 +554,6 @@ class Engine:
         if grad_precision in self.GRAD_PRECISIONS and branch not in (0, 1, 2):  # a grad_precision that is not one is reported first
             raise ValueError(f"neck_backward_path: branch must be 0, 1 or 2, got {branch!r}")
         return self._backward_path("pp_neck_backward_path", grad_precision, int(branch))
-
-    def neck_backward(self, branch, x, w, y, dy, need_dx=True, grad_precision="fp32"):
-        """pp_neck_backward_mp: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
-        dL/d(rpn_out) dy [nb,320,H,W] -> (dw [Cin,Cup,s,s] summed over the frames, dx [nb,Cin,h,w] or None when need_dx is False).
-        Deterministic, stateless.  grad_precision: "fp32" (pp_neck_backward, bit for bit), "bf16x3" or "bf16": the operands of the dw
-        and dx products in split or plain bf16 on the bf16 MFMA, everything else (Z, statistics, mask, dZ, tensors) fp32."""
-        return self._neck_backward("neck_backward", branch, x, w, y, dy, need_dx, grad_precision=grad_precision)
 
     def update_neck_weights(self, params):
         """pp_update_neck_weights: {state_dict name: device tensor} of rpn.deconv{1,2,3}.0.weight -> the committed upsampler images, in
@@ -551,8 +579,14 @@ class Engine:
         where no 16-bit tiling takes the shape."""
         return self._backward_path("pp_unit_backward_path", grad_precision, int(C), int(h), int(w))
 
-    def _unit_backward(self, who, u, w, dy, dskip, need_du, affine=None, bn=None, grad_precision=None):
-        mode = [self._grad_mode(grad_precision, who)] if affine is None else []
+    def unit_backward(self, u, w, dy, dskip=None, need_du=True, grad_precision="fp32", norm=None):
+        """pp_unit_backward_mp: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
+        dy (dL/d(conv output)) and the optional dskip (added to du: the residual path around the unit) are [nb,C,h,w], w [C,C,3,3] ->
+        (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  Deterministic, stateless.  grad_precision:
+        "fp32" (pp_unit_backward, bit for bit), "bf16x3" or "bf16": the operands of the two gradient products in split or plain bf16 on
+        the bf16 MFMA, everything else (tensors, statistics, mask, norm backward) fp32.
+        norm: a BackwardNorm for the unit behind a BatchNorm2d (unit_backward_affine / unit_backward_bn) -> (dw, du, dscale, dshift)."""
+        who, mode = self._backward_form("unit_backward", norm, grad_precision)
         if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
             raise ValueError(who + f": u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, C, h, wd = (int(v) for v in u.shape)
@@ -560,7 +594,7 @@ class Engine:
             raise ValueError(who + f": C must be 64, 128 or 256, got {C}")
         if h < 1 or wd < 1 or h * wd < 2:
             raise ValueError(who + f": the map needs at least two elements, got {h} x {wd}")
-        if affine is not None and affine[2] and not need_du:
+        if norm is not None and norm.need_affine and not need_du:
             raise ValueError(who + ": the affine sums are sums over du's product: need_affine needs need_du")
         u = _chk(u, torch.float32, (nb, C, h, wd), who + ": u")
         w = _chk(w.detach() if isinstance(w, torch.Tensor) else w, torch.float32, (C, C, 3, 3), who + ": w")
@@ -568,21 +602,13 @@ class Engine:
         if dskip is not None:
             dskip = _chk(dskip, torch.float32, (nb, C, h, wd), who + ": dskip")
         self._on_device(who, ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
-        suffix, norm, tail, sums = self._norm_args(who, C, affine, bn)
+        suffix, norm, tail, sums = self._norm_args(who, C, norm)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((C, C, 3, 3), torch.float32)
         du = self._t((nb, C, h, wd), torch.float32) if need_du else None
         self._call_backward("pp_unit_backward" + suffix, *mode, C, h, wd, u, w, *norm, dy, dskip, nb, dw, du, *tail)
         return (dw, du, *sums)
-
-    def unit_backward(self, u, w, dy, dskip=None, need_du=True, grad_precision="fp32"):
-        """pp_unit_backward_mp: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
-        dy (dL/d(conv output)) and the optional dskip (added to du: the residual path around the unit) are [nb,C,h,w], w [C,C,3,3] ->
-        (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  Deterministic, stateless.  grad_precision:
-        "fp32" (pp_unit_backward, bit for bit), "bf16x3" or "bf16": the operands of the two gradient products in split or plain bf16 on
-        the bf16 MFMA, everything else (tensors, statistics, mask, norm backward) fp32."""
-        return self._unit_backward("unit_backward", u, w, dy, dskip, need_du, grad_precision=grad_precision)
 
     def backbone_block_taps(self, canvas):
         """pp_backbone_block_taps: backbone_taps(canvas) plus the inputs of block 3's five units -> (rpn_out, x1, x2, x3,
@@ -610,8 +636,15 @@ class Engine:
         """pp_down_backward_path: the precision down_backward(grad_precision=...) really runs at this shape."""
         return self._backward_path("pp_down_backward_path", grad_precision, int(cin), int(cout), int(hin), int(win))
 
-    def _down_backward(self, who, x, w, z, dy, need_dx, affine=None, bn=None, grad_precision=None):
-        mode = [self._grad_mode(grad_precision, who)] if affine is None else []
+    def down_backward(self, x, w, z, dy, need_dx=True, grad_precision="fp32", norm=None):
+        """pp_down_backward_mp: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
+        (64, 128) | (128, 256).  x [nb,Cin,Hin,Win] (the stage's raw input), w [Cout,Cin,3,3], z (the conv output) and dy (dL/d(stage
+        output)) [nb,Cout,(Hin+1)//2,(Win+1)//2] -> (dw [Cout,Cin,3,3] summed over the frames, dx [nb,Cin,Hin,Win] or None when
+        need_dx is False).  Deterministic, stateless.  grad_precision: "fp32" (pp_down_backward, bit for bit), "bf16x3" or "bf16": the
+        operands of the wgrad and dgrad products in split or plain bf16 on the bf16 MFMA, everything else (planes, statistics, mask,
+        norm backward, tensors) fp32.
+        norm: a BackwardNorm for the stage with a BatchNorm2d (down_backward_affine / down_backward_bn) -> (dw, dx, dscale, dshift)."""
+        who, mode = self._backward_form("down_backward", norm, grad_precision)
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
             raise ValueError(who + f": x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, cin, hin, win = (int(v) for v in x.shape)
@@ -626,22 +659,13 @@ class Engine:
         z = _chk(z, torch.float32, (nb, cout, ho, wo), who + ": z")
         dy = _chk(dy, torch.float32, (nb, cout, ho, wo), who + ": dy")
         self._on_device(who, ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
-        suffix, norm, tail, sums = self._norm_args(who, cout, affine, bn)
+        suffix, norm, tail, sums = self._norm_args(who, cout, norm)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((cout, cin, 3, 3), torch.float32)
         dx = self._t((nb, cin, hin, win), torch.float32) if need_dx else None
         self._call_backward("pp_down_backward" + suffix, *mode, cin, cout, hin, win, x, w, z, *norm, dy, nb, dw, dx, *tail)
         return (dw, dx, *sums)
-
-    def down_backward(self, x, w, z, dy, need_dx=True, grad_precision="fp32"):
-        """pp_down_backward_mp: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
-        (64, 128) | (128, 256).  x [nb,Cin,Hin,Win] (the stage's raw input), w [Cout,Cin,3,3], z (the conv output) and dy (dL/d(stage
-        output)) [nb,Cout,(Hin+1)//2,(Win+1)//2] -> (dw [Cout,Cin,3,3] summed over the frames, dx [nb,Cin,Hin,Win] or None when
-        need_dx is False).  Deterministic, stateless.  grad_precision: "fp32" (pp_down_backward, bit for bit), "bf16x3" or "bf16": the
-        operands of the wgrad and dgrad products in split or plain bf16 on the bf16 MFMA, everything else (planes, statistics, mask,
-        norm backward, tensors) fp32."""
-        return self._down_backward("down_backward", x, w, z, dy, need_dx, grad_precision=grad_precision)
 
     def backbone_stage_taps(self, canvas):
         """pp_backbone_stage_taps: backbone_block_taps(canvas) plus the raw output of block 3's strided convolution -> (rpn_out, x1,
@@ -724,23 +748,6 @@ class Engine:
             out.append((cls.bn_prefix(cls.NECK_KEYS[b]), 128 if b else 64))
         return tuple(out)
 
-    def _affine_args(self, who, scale, shift, C, need_affine):
-        scale = _chk(scale, torch.float32, (C,), f"{who}: scale")
-        shift = _chk(shift, torch.float32, (C,), f"{who}: shift")
-        self._on_device(who, ((scale, "scale"), (shift, "shift")))
-        sums = (self._t((C,), torch.float64), self._t((C,), torch.float64)) if need_affine else (None, None)
-        return scale, shift, sums
-
-    def _bn_args(self, who, bn, C):
-        """(mean, var, chunk_frames) of a *_backward_bn call -> the two device tensors f32[C] and the int."""
-        mean, var, chunk = bn
-        mean = _chk(mean, torch.float32, (C,), f"{who}: mean")
-        var = _chk(var, torch.float32, (C,), f"{who}: var")
-        self._on_device(who, ((mean, "mean"), (var, "var")))
-        if not isinstance(chunk, int) or chunk < 0:
-            raise ValueError(f"{who}: chunk_frames must be an int >= 0, got {chunk!r}")
-        return mean, var, chunk
-
     def bn_fold(self, gamma, beta, running_mean, running_var):
         """pp_bn_fold: the eval-mode fold of one BatchNorm2d(eps 1e-3) layer, four device tensors [C] -> (scale, shift) f32[C] =
         gamma / sqrt(running_var + 1e-3), beta - running_mean scale, in fp64 and rounded once: the bits the committed plan holds."""
@@ -787,18 +794,18 @@ class Engine:
         """pp_unit_backward_affine: unit_backward for the unit scale/shift -> ReLU -> Conv3x3 (frozen BatchNorm): scale, shift f32[C] are
         the folded values the forward used -> (dw, du or None, dscale, dshift); dscale = sum g u and dshift = sum g are f64[C], None
         when need_affine is False.  need_du=False needs need_affine=False.  fp32, deterministic, stateless."""
-        return self._unit_backward("unit_backward_affine", u, w, dy, dskip, need_du, affine=(scale, shift, need_affine))
+        return self.unit_backward(u, w, dy, dskip, need_du, norm=BackwardNorm(scale, shift, need_affine=need_affine))
 
     def down_backward_affine(self, x, w, z, scale, shift, dy, need_dx=True, need_affine=True):
         """pp_down_backward_affine: down_backward for the stage Conv3x3 stride 2 -> scale/shift -> ReLU (frozen BatchNorm) ->
         (dw, dx or None, dscale = sum g z, dshift = sum g: f64[Cout], None when need_affine is False).  fp32, deterministic, stateless."""
-        return self._down_backward("down_backward_affine", x, w, z, dy, need_dx, affine=(scale, shift, need_affine))
+        return self.down_backward(x, w, z, dy, need_dx, norm=BackwardNorm(scale, shift, need_affine=need_affine))
 
     def neck_backward_affine(self, branch, x, w, scale, shift, y, dy, need_dx=True, need_affine=True):
         """pp_neck_backward_affine: neck_backward for the branch ConvTranspose -> scale/shift -> ReLU (frozen BatchNorm); scale, shift
         f32[Cup] are the branch's -> (dw, dx or None, dscale = sum g Z, dshift = sum g: f64[Cup], None when need_affine is False).
         fp32, deterministic, stateless."""
-        return self._neck_backward("neck_backward_affine", branch, x, w, y, dy, need_dx, affine=(scale, shift, need_affine))
+        return self.neck_backward(branch, x, w, y, dy, need_dx, norm=BackwardNorm(scale, shift, need_affine=need_affine))
 
     # ------------------------------------------------------------------ the BatchNorm backbone with batch statistics
     def unit_backward_bn(self, u, w, scale, shift, mean, var, dy, dskip=None, need_du=True, need_affine=True, chunk_frames=0):
@@ -806,17 +813,17 @@ class Engine:
         variance) and scale, shift their fold with the layer's weight and bias, as backbone_train_taps_bn hands them out -> (dw, du or
         None, dscale = sum g u, dshift = sum g: f64[C] pooled over all frames, None when need_affine is False); bn_affine_grad(dscale,
         dshift, mean, var) gives dgamma, dbeta.  chunk_frames > 0 caps the frames of a workspace chunk.  fp32, deterministic, stateless."""
-        return self._unit_backward("unit_backward_bn", u, w, dy, dskip, need_du, affine=(scale, shift, need_affine), bn=(mean, var, chunk_frames))
+        return self.unit_backward(u, w, dy, dskip, need_du, norm=BackwardNorm(scale, shift, mean, var, need_affine, chunk_frames))
 
     def down_backward_bn(self, x, w, z, scale, shift, mean, var, dy, need_dx=True, need_affine=True, chunk_frames=0):
         """pp_down_backward_bn: down_backward_affine in front of a train-mode BatchNorm2d (arguments as unit_backward_bn) -> (dw, dx or
         None, dscale = sum g z, dshift = sum g)."""
-        return self._down_backward("down_backward_bn", x, w, z, dy, need_dx, affine=(scale, shift, need_affine), bn=(mean, var, chunk_frames))
+        return self.down_backward(x, w, z, dy, need_dx, norm=BackwardNorm(scale, shift, mean, var, need_affine, chunk_frames))
 
     def neck_backward_bn(self, branch, x, w, scale, shift, mean, var, y, dy, need_dx=True, need_affine=True, chunk_frames=0):
         """pp_neck_backward_bn: neck_backward_affine in front of a train-mode BatchNorm2d (arguments as unit_backward_bn) -> (dw, dx or
         None, dscale = sum g Z, dshift = sum g)."""
-        return self._neck_backward("neck_backward_bn", branch, x, w, y, dy, need_dx, affine=(scale, shift, need_affine), bn=(mean, var, chunk_frames))
+        return self.neck_backward(branch, x, w, y, dy, need_dx, norm=BackwardNorm(scale, shift, mean, var, need_affine, chunk_frames))
 
     def backbone_train_taps_bn(self, canvas, bn_params, taps=True):
         """pp_backbone_train_taps_bn: the lock-step training forward of the BatchNorm backbone on canvases [nb,64,gx,gy], 1 <= nb <=

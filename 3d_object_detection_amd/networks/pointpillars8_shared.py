@@ -13,7 +13,7 @@ depths from the head to the front, and each scope trains what the one before it 
 
 Everything in front of the trained groups is frozen.  A training forward records up to three autograd Functions, each a thin
 wrapper of engine calls: _HeadFunction (pp_head / pp_head_backward, csrc/train.hip); _RpnFunction, whose forward runs the backbone
-with the taps its depth needs and whose backward walks RPN_TABLE from the upsamplers (pp_neck_backward, csrc/neck_train.hip)
+with the taps its depth needs and whose backward (_rpn_backward) walks RPN_TABLE from the upsamplers (pp_neck_backward, csrc/neck_train.hip)
 through each block's unit chain (pp_unit_backward, csrc/block_train.hip) and strided stage (pp_down_backward, csrc/down_train.hip),
 stopping where nothing in front needs a gradient; and, under "all", _PfnFunction in front of it (csrc/pfn_train.hip), which consumes
 the gradient of the canvases that _RpnFunction returns at full depth.  rpn_train() returns that gradient to any canvas that
@@ -32,10 +32,10 @@ the engine (running statistics folded into scale / shift) is rewritten by pp_upd
 The BatchNorm networks (pointpillars8_export / _trt, _norm = "batch") fine-tune with frozen statistics, train(scope=...,
 bn_stats="frozen"): every BatchNorm2d of the RPN stays the per-channel affine of its running statistics, its weight / bias sit in the
 group of the convolution whose backward primitive yields their gradient (with_bn: 63 tensors under "rpn", 66 under "all"), the
-training forward is the same tapped inference pass, _RpnBnFunction walks the same table with pp_*_backward_affine, and after a step
+training forward is the same tapped inference pass, _RpnBnFunction runs the same walk with pp_*_backward_affine, and after a step
 _sync_neck also folds the nineteen layers again in place (pp_update_bn_fold).  train(scope=..., bn_stats="moving") trains them as the
 reference's net.train() does: every BatchNorm2d normalises with the statistics of the batch and moves its running statistics.  The
-training forward is then one lock-step pass over all frames (pp_backbone_train_taps_bn) and _RpnBnBatchFunction walks the table with
+training forward is then one lock-step pass over all frames (pp_backbone_train_taps_bn) and _RpnBnBatchFunction runs the walk with
 pp_*_backward_bn; the moved running statistics are folded again before the next eval-mode pass.
 
 Mixed precision (grad_stages="rpn" extends it to the strided stages and the upsamplers, pp_down_backward_mp / pp_neck_backward_mp):
@@ -49,7 +49,7 @@ import typing
 import numpy as np
 import torch
 
-from ..engine import Engine, engine_for
+from ..engine import BackwardNorm, Engine, engine_for
 from .init import init_state_dict
 
 HEAD_KEYS = ("heads.conv_cls.weight", "heads.conv_cls.bias", "heads.conv_box.weight", "heads.conv_box.bias",
@@ -147,23 +147,51 @@ class _HeadFunction(torch.autograd.Function):
         return (None, dx) + tuple(g[k] if ctx.needs_input_grad[2 + i] else None for i, k in enumerate(HEAD_KEYS))
 
 
-def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32", need_dh=True):
+class _Layer(typing.NamedTuple):
+    """One trained convolution or upsampler of the RPN as its backward sees it, with its BatchNorm2d on a BatchNorm backbone."""
+    w: torch.Tensor
+    need_w: bool
+    norm: BackwardNorm = None        # BatchNorm: the fold the forward used (and the batch statistics), need_affine = the norm trains
+    stats: tuple = ()                # what bn_affine_grad reads: the running statistics when frozen, the batch's when they move
+    need_gb: tuple = (False, False)  # the norm's weight / bias require grad
+
+    def trains(self):
+        return self.need_w or any(self.need_gb)
+
+
+def _layer_backward(eng, primitive, layer, *args, prec=None, **kw):
+    """One backward primitive of the engine (neck_backward, unit_backward, down_backward) for `layer` -> ((dw, dgamma, dbeta), dx),
+    each gradient None unless its tensor requires grad.  InstanceNorm: prec, when given, goes in as grad_precision.  BatchNorm: the
+    layer's norm goes in, and its dgamma / dbeta come from the primitive's two fp64 sums (pp_bn_affine_grad)."""
+    if layer.norm is None:
+        dw, dx = primitive(*args, **kw, **({} if prec is None else {"grad_precision": prec}))
+        return (dw if layer.need_w else None, None, None), dx
+    dw, dx, dscale, dshift = primitive(*args, **kw, norm=layer.norm)
+    dg, db = eng.bn_affine_grad(dscale, dshift, *layer.stats) if layer.norm.need_affine else (None, None)
+    return (dw if layer.need_w else None, dg if layer.need_gb[0] else None, db if layer.need_gb[1] else None), dx
+
+
+def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32", need_dh=True, layers=None):
     """The backward of one block's Resnet modules (a row of RPN_TABLE): units and weights in unit order, g = dL/d(block output) ->
     (dw per unit, dL/d(block input h)).  grad_precision: the operand precision of every unit backward (Engine.unit_backward).
-    need_dh=False: nothing in front of the block trains, so its first unit computes its weight gradient only and h gets None."""
-    prec = grad_precision
-    dws = [None] * len(units)
+    need_dh=False: nothing in front of the block trains, so its first unit computes its weight gradient only and h gets None.
+    layers: the units' _Layer entries in place of weights=None (any norm form); a unit's result is then its (dw, dgamma, dbeta).
+    The first unit runs its dgrad when something in front needs the gradient or its own norm trains: a unit's affine sums are sums
+    over its dgrad product."""
+    layers = layers or [_Layer(w, True) for w in weights]
+    unit = lambda i, g, **kw: _layer_backward(eng, eng.unit_backward, layers[i], units[i], layers[i].w, g, prec=grad_precision, **kw)  # noqa: E731
+    grads = [None] * len(units)
     i = len(units)
     for n in reversed(modules):
         i -= n
         skip = g  # the gradient of the module's output is also that of its residual path
         if n == 2:
-            dws[i + 1], g = eng.unit_backward(units[i + 1], weights[i + 1], g, grad_precision=prec)
-        if i or need_dh:
-            dws[i], g = eng.unit_backward(units[i], weights[i], g, dskip=skip, grad_precision=prec)
+            grads[i + 1], g = unit(i + 1, g)
+        if i or need_dh or any(layers[i].need_gb):
+            grads[i], g = unit(i, g, dskip=skip)
         else:
-            dws[i], g = eng.unit_backward(units[i], weights[i], g, need_du=False, grad_precision=prec)
-    return dws, g
+            grads[i], g = unit(i, g, need_du=False)
+    return (grads if weights is None else [dw for dw, _, _ in grads]), g
 
 
 _W0 = (0, 4, 10)  # each level's strided convolution in RPN_CONV_KEYS; its unit convolutions follow it
@@ -185,6 +213,62 @@ def _frame_taps(eng, first, canvas):
     return y, (x1, x2, x3), {2: units}, {}
 
 
+def _stacked_taps(eng, first, x):
+    """_frame_taps of every canvas of x, stacked over the frames -> [y, x1, x2, x3, the unit inputs of the levels `first` reaches, their
+    z]: what a backward from `first` keeps, in the order _rpn_backward reads."""
+    outs = [_frame_taps(eng, first, c) for c in x]
+    y = torch.cat([o[0] for o in outs])
+    taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
+    units = [torch.stack([o[2][b][k] for o in outs]) for b in sorted(outs[0][2]) for k in range(sum(RPN_TABLE[b][1]))]
+    zs = [torch.cat([o[3][b] for o in outs]) for b in sorted(outs[0][3])]
+    return [y, *taps, *units, *zs]
+
+
+def _rpn_backward(eng, first, saved, layers, gy, need_x, prec=("fp32", "fp32")):
+    """The backward of the RPN from its output back to convolution `first` of RPN_CONV_KEYS, for every norm form: pp_neck_backward
+    for the three branches and then, from level 2 down along RPN_TABLE, the block's unit chain (rpn_block_backward) and its strided
+    stage (pp_down_backward); the upsampler's dx plus the dx of the stage above (in this order) is the gradient of a level's block
+    output.  saved: what the forward kept, the canvases when first = 0 and then the list of _stacked_taps; layers: the _Layer of
+    RPN_CONV_KEYS[first:], then of the three upsamplers; prec as in _RpnFunction.  It stops where nothing in front needs a gradient:
+    a dx is computed only when a layer in front of it trains or the canvases need one (need_x), and a layer whose tensors need no
+    gradient runs only for the dx it hands on.
+    -> (dL/d(canvases) or None, per layer its (dw, dgamma, dbeta), None for a tensor that does not require grad)."""
+    saved = list(saved)
+    x = saved.pop(0) if first == 0 else None
+    y, taps, saved = saved[0], saved[1:4], saved[4:]
+    levels = [(b, sum(mods)) for b, mods in RPN_TABLE if first <= _W0[b] + 1]  # the levels with taps
+    units = {b: [saved.pop(0) for _ in range(n)] for b, n in levels}
+    zs = {b: saved.pop(0) for b, _ in levels if first <= _W0[b]}
+    nconv = len(RPN_CONV_KEYS)
+    conv = lambda k: layers[k - first]  # noqa: E731
+    # front[b]: the canvases or a convolution in front of level b's block needs a gradient, so the block's input does;
+    # front[b + 1]: the same for the block's output
+    front = [need_x]
+    for b, mods in RPN_TABLE:
+        front.append(front[b] or any(conv(k).trains() for k in range(max(first, _W0[b]), _W0[b] + 1 + sum(mods))))
+    gy = gy.contiguous()
+    stage_prec = None if prec[1] == "fp32" else prec[1]  # the keyword goes to the stages and upsamplers only in a 16-bit mode
+    grads = [(None, None, None)] * len(layers)
+    dxn = [None] * 3
+    for b in range(3):
+        i = nconv - first + b
+        if layers[i].trains() or front[b + 1]:
+            grads[i], dxn[b] = _layer_backward(eng, eng.neck_backward, layers[i], b, taps[b], layers[i].w, y, gy, prec=stage_prec, need_dx=front[b + 1])
+    g = None
+    for b, n in reversed(levels):
+        w0, mods = _W0[b], RPN_TABLE[b][1]
+        if not front[b + 1]:
+            break
+        g = dxn[b] if g is None else dxn[b] + g
+        need_dh = first <= w0 and (conv(w0).trains() or front[b])
+        grads[w0 + 1 - first:w0 + 1 + n - first], g = rpn_block_backward(eng, mods, units[b], None, g, prec[0], need_dh=need_dh,
+                                                                           layers=layers[w0 + 1 - first:w0 + 1 + n - first])
+        if need_dh:
+            grads[w0 - first], g = _layer_backward(eng, eng.down_backward, conv(w0), x if b == 0 else taps[b - 1], conv(w0).w, zs[b], g,
+                                                   prec=stage_prec, need_dx=front[b])
+    return (g if need_x else None), grads
+
+
 class _RpnFunction(torch.autograd.Function):
     """RPN.forward on canvases x [nb,64,gx,gy], one backbone pass per frame, stacked; the backward of the RPN from its output back
     to convolution `first` of RPN_CONV_KEYS, the first one that trains: 0 (the whole RPN, backbone_train_taps), 10 (block 3 with its
@@ -195,151 +279,57 @@ class _RpnFunction(torch.autograd.Function):
     prec is the pair (grad_precision of the unit backwards, grad_precision of the strided stages and upsamplers): the second is "fp32"
     unless train(grad_stages="rpn") hands the network's grad_precision to pp_down_backward_mp and pp_neck_backward_mp as well.
 
-    The backward is pp_neck_backward for the three branches and then, from level 2 down along RPN_TABLE, the block's unit chain
-    (rpn_block_backward) and its strided stage (pp_down_backward); the upsampler's dx plus the dx of the stage above (in this order)
-    is the gradient of a level's block output.  It stops where nothing in front needs a gradient: a dx is computed only when a
-    weight in front of it, or the canvases, need one, and a weight that does not require grad gets None.  Kept for the backward: y,
+    The backward is _rpn_backward with InstanceNorm layers; a weight that does not require grad gets None.  Kept for the backward: y,
     x1..x3, the unit inputs and z of the levels `first` reaches, the weights, and for first = 0 the canvases, which then get level
     0's dx when they require grad."""
 
     @staticmethod
     def forward(ctx, eng, prec, first, x, *weights):
-        ctx.eng, (ctx.prec, ctx.stage_prec), ctx.first = eng, prec, first  # prec: (the units' grad_precision, the stages' and upsamplers')
-        outs = [_frame_taps(eng, first, c) for c in x]
-        y = torch.cat([o[0] for o in outs])
-        taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
-        units = [torch.stack([o[2][b][k] for o in outs]) for b in sorted(outs[0][2]) for k in range(sum(RPN_TABLE[b][1]))]
-        zs = [torch.cat([o[3][b] for o in outs]) for b in sorted(outs[0][3])]
-        ctx.save_for_backward(*([x] if first == 0 else []), y, *taps, *units, *zs, *weights)
-        return y
+        ctx.eng, ctx.prec, ctx.first = eng, prec, first
+        kept = _stacked_taps(eng, first, x)
+        ctx.save_for_backward(*([x] if first == 0 else []), *kept, *weights)
+        return kept[0]
 
     @staticmethod
     def backward(ctx, gy):
-        eng, first, saved = ctx.eng, ctx.first, list(ctx.saved_tensors)
-        x = saved.pop(0) if first == 0 else None
-        y, taps, saved = saved[0], saved[1:4], saved[4:]
-        nconv = len(RPN_CONV_KEYS)
-        levels = [(b, mods, _W0[b], sum(mods)) for b, mods in RPN_TABLE if first <= _W0[b] + 1]  # the levels with taps
-        units = {b: [saved.pop(0) for _ in range(n)] for b, _, _, n in levels}
-        zs = {b: saved.pop(0) for b, _, w0, _ in levels if first <= w0}
-        wc, wn = dict(zip(range(first, nconv), saved)), saved[nconv - first:]
-        need_x = ctx.needs_input_grad[3]
-        need_c = dict(zip(range(first, nconv), ctx.needs_input_grad[4:]))
-        need_n = ctx.needs_input_grad[4 + nconv - first:]
-        # front[b]: the canvases or a convolution in front of level b's block needs a gradient, so the block's input does;
-        # front[b + 1]: the same for the block's output
-        front = [need_x]
-        for b, mods in RPN_TABLE:
-            front.append(front[b] or any(need_c.get(k, False) for k in range(_W0[b], _W0[b] + 1 + sum(mods))))
-        gy = gy.contiguous()
-        # the keyword goes to down_backward / neck_backward only when a 16-bit mode is asked for those stages (grad_stages="rpn")
-        stage_kw = {} if ctx.stage_prec == "fp32" else {"grad_precision": ctx.stage_prec}
-        dwn, dxn = [None] * 3, [None] * 3
-        for b in range(3):
-            if need_n[b] or front[b + 1]:
-                dwn[b], dxn[b] = eng.neck_backward(b, taps[b], wn[b], y, gy, need_dx=front[b + 1], **stage_kw)
-        dwc, g = {}, None
-        for b, mods, w0, n in reversed(levels):
-            if not front[b + 1]:
-                break
-            g = dxn[b] if g is None else dxn[b] + g
-            need_dh = first <= w0 and (need_c[w0] or front[b])
-            dws, gh = rpn_block_backward(eng, mods, units[b], [wc[w0 + 1 + i] for i in range(n)], g, ctx.prec, need_dh=need_dh)
-            dwc.update(zip(range(w0 + 1, w0 + 1 + n), dws))
-            if need_dh:
-                dwc[w0], g = eng.down_backward(x if b == 0 else taps[b - 1], wc[w0], zs[b], gh, need_dx=front[b], **stage_kw)
-        grads = [dwc.get(k) if need_c[k] else None for k in range(first, nconv)] + [d if n else None for d, n in zip(dwn, need_n)]
-        return (None, None, None, g if need_x else None) + tuple(grads)
+        need, saved = ctx.needs_input_grad, ctx.saved_tensors
+        layers = [_Layer(w, n) for w, n in zip(saved[len(saved) + 4 - len(need):], need[4:])]  # the weights are the last tensors kept
+        g, grads = _rpn_backward(ctx.eng, ctx.first, saved, layers, gy, need[3], ctx.prec)
+        return (None, None, None, g) + tuple(dw for dw, _, _ in grads)
 
 
 class _RpnBnFunction(torch.autograd.Function):
-    """_RpnFunction for the BatchNorm backbone with frozen statistics: the same forward (the tap entry points read no norm kind),
-    the same walk from the upsamplers through the levels `first` reaches, with the affine primitives (pp_neck_backward_affine,
+    """_RpnFunction for the BatchNorm backbone with frozen statistics: the same forward (the tap entry points read no norm kind) and
+    the same walk (_rpn_backward), whose layers carry a BackwardNorm without statistics (pp_neck_backward_affine,
     pp_unit_backward_affine, pp_down_backward_affine).  A layer is a convolution or upsampler with its BatchNorm2d: tensors holds
     (weight, gamma, beta) of RPN_CONV_KEYS[first:] and then of the three upsamplers, stats (running_mean, running_var) of the same
     layers, which get no gradient.  The folded (scale, shift) of every layer are evaluated once in the forward by the kernel that
     wrote the engine's own (pp_bn_fold), so the backward reads the values the forward used.  A layer's dgamma / dbeta come from the
-    two fp64 sums of its primitive (pp_bn_affine_grad).  A unit's sums are sums over its dgrad product: the first trained unit runs
-    it when its norm trains, even where nothing in front needs the gradient."""
+    two fp64 sums of its primitive (pp_bn_affine_grad)."""
 
     @staticmethod
     def forward(ctx, eng, first, stats, x, *tensors):
         ctx.eng, ctx.first, ctx.stats, ctx.batch = eng, first, stats, False
         n = len(tensors) // 3
         folds = [eng.bn_fold(tensors[3 * i + 1], tensors[3 * i + 2], *stats[i]) for i in range(n)]
-        outs = [_frame_taps(eng, first, c) for c in x]
-        y = torch.cat([o[0] for o in outs])
-        taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
-        units = [torch.stack([o[2][b][k] for o in outs]) for b in sorted(outs[0][2]) for k in range(sum(RPN_TABLE[b][1]))]
-        zs = [torch.cat([o[3][b] for o in outs]) for b in sorted(outs[0][3])]
-        ctx.save_for_backward(*([x] if first == 0 else []), y, *taps, *units, *zs, *tensors[::3], *[t for f in folds for t in f])
-        return y
+        kept = _stacked_taps(eng, first, x)
+        ctx.save_for_backward(*([x] if first == 0 else []), *kept, *tensors[::3], *[t for f in folds for t in f])
+        return kept[0]
 
     @staticmethod
     def backward(ctx, gy):
-        """Shared with _RpnBnBatchFunction (ctx.batch): there the primitives are the _bn siblings, which also take a layer's batch mean
-        and variance (ctx.stats), and pp_bn_affine_grad reads those in place of the running statistics."""
-        eng, first, saved = ctx.eng, ctx.first, list(ctx.saved_tensors)
-        kind = "_bn" if ctx.batch else "_affine"
-        neck_backward, unit_backward, down_backward = (getattr(eng, p + kind) for p in ("neck_backward", "unit_backward", "down_backward"))
-        st = (lambda i: ctx.stats[i]) if ctx.batch else (lambda i: ())  # noqa: E731
-        x = saved.pop(0) if first == 0 else None
-        y, taps, saved = saved[0], saved[1:4], saved[4:]
-        nconv = len(RPN_CONV_KEYS)
-        n = nconv - first + 3  # layers: convolution k is layer k - first, upsampler b layer nconv - first + b
-        levels = [(b, mods, _W0[b], sum(mods)) for b, mods in RPN_TABLE if first <= _W0[b] + 1]  # the levels with taps
-        units = {b: [saved.pop(0) for _ in range(nu)] for b, _, _, nu in levels}
-        zs = {b: saved.pop(0) for b, _, w0, _ in levels if first <= w0}
-        ws, folds = saved[:n], [saved[n + 2 * i:n + 2 * i + 2] for i in range(n)]
-        need = ctx.needs_input_grad
-        need_x = need[3]
-        need_w = [need[4 + 3 * i] for i in range(n)]
-        need_a = [need[5 + 3 * i] or need[6 + 3 * i] for i in range(n)]
-        trains = lambda k: first <= k and (need_w[k - first] or need_a[k - first])  # noqa: E731
-        front = [need_x]
-        for b, mods in RPN_TABLE:
-            front.append(front[b] or any(trains(k) for k in range(_W0[b], _W0[b] + 1 + sum(mods))))
-        grads = [None] * (3 * n)
-
-        def put(i, dw, dscale, dshift):
-            grads[3 * i] = dw if need_w[i] else None
-            if need_a[i]:
-                dg, db = eng.bn_affine_grad(dscale, dshift, *ctx.stats[i])
-                grads[3 * i + 1], grads[3 * i + 2] = dg if need[5 + 3 * i] else None, db if need[6 + 3 * i] else None
-
-        gy = gy.contiguous()
-        dxn = [None] * 3
-        for b in range(3):
-            i = nconv - first + b
-            if need_w[i] or need_a[i] or front[b + 1]:
-                dw, dxn[b], ds, dh = neck_backward(b, taps[b], ws[i], *folds[i], *st(i), y, gy, need_dx=front[b + 1], need_affine=need_a[i])
-                put(i, dw, ds, dh)
-        g = None
-        for b, mods, w0, nu in reversed(levels):
-            if not front[b + 1]:
-                break
-            g = dxn[b] if g is None else dxn[b] + g
-            need_dh = first <= w0 and (trains(w0) or front[b])
-            u = nu
-            for m in reversed(mods):  # rpn_block_backward with the affine primitive
-                u -= m
-                skip = g
-                if m == 2:
-                    i = w0 + 2 + u - first
-                    dw, g, ds, dh = unit_backward(units[b][u + 1], ws[i], *folds[i], *st(i), g, need_affine=need_a[i])
-                    put(i, dw, ds, dh)
-                i = w0 + 1 + u - first
-                if u or need_dh or need_a[i]:
-                    dw, g, ds, dh = unit_backward(units[b][u], ws[i], *folds[i], *st(i), g, dskip=skip, need_affine=need_a[i])
-                else:
-                    dw, g, ds, dh = unit_backward(units[b][u], ws[i], *folds[i], *st(i), g, need_du=False, need_affine=False)
-                put(i, dw, ds, dh)
-            if need_dh:
-                i = w0 - first
-                dw, g, ds, dh = down_backward(x if b == 0 else taps[b - 1], ws[i], zs[b], *folds[i], *st(i), g, need_dx=front[b],
-                                              need_affine=need_a[i])
-                put(i, dw, ds, dh)
-        return (None, None, None, g if need_x else None) + tuple(grads)
+        """Shared with _RpnBnBatchFunction (ctx.batch): there a layer's norm also holds its batch mean and variance (ctx.stats: the
+        pp_*_backward_bn primitives), and pp_bn_affine_grad reads those in place of the running statistics."""
+        need, saved = ctx.needs_input_grad, ctx.saved_tensors
+        n = (len(need) - 4) // 3
+        own = saved[len(saved) - 3 * n:]  # the last tensors kept: the n weights, then every layer's (scale, shift)
+        layers = []
+        for i in range(n):
+            need_gb = tuple(need[5 + 3 * i:7 + 3 * i])
+            norm = BackwardNorm(own[n + 2 * i], own[n + 2 * i + 1], *(ctx.stats[i] if ctx.batch else ()), need_affine=any(need_gb))
+            layers.append(_Layer(own[i], need[4 + 3 * i], norm, ctx.stats[i], need_gb))
+        g, grads = _rpn_backward(ctx.eng, ctx.first, saved, layers, gy, need[3])
+        return (None, None, None, g) + tuple(t for layer in grads for t in layer)
 
 
 class _RpnBnBatchFunction(torch.autograd.Function):
@@ -442,33 +432,27 @@ class PointPillars:
         return self.train(False)
 
     def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None, grad_stages="units"):
-        """Training mode: the six head parameters require grad and forward() accepts a batch of several frames.  scope="neck" also
-        trains rpn.deconv{1,2,3}.0.weight, scope="block3" those and the five unit convolutions of block 3, scope="stage3" those and
-        block 3's stride-2 convolution rpn.block3.0.weight (InstanceNorm backbone, fp32 mode); everything in front of them stays
-        frozen: it has no backward.  scope="rpn" trains the whole RPN (RPN_KEYS: blocks 1 and 2 with their stride-2 convolutions as
-        well); PFN and scatter stay frozen.  scope="all" trains the pillar feature net too (ALL_KEYS, what net.parameters() yields
-        in the reference): the training-mode forward then normalises the PFN with batch statistics and moves the running ones, as the
-        reference's net.train() does.  eval() / train(False) restores the inference behaviour, with the PFN's current parameters and
-        running statistics folded into the engine.
+        """Training mode: forward() accepts a batch of several frames and the tensors of `scope` require grad (SCOPES, from "head",
+        the six head parameters, to "all", everything net.parameters() yields in the reference: the module docstring lists them);
+        everything in front of the scope stays frozen.  Under "all" the PFN normalises with batch statistics and moves its running
+        ones, as the reference's net.train() does.  eval() / train(False) restores the inference behaviour, with the current parameters
+        and running statistics folded into the engine.
         grad_precision ("fp32" | "bf16x3" | "bf16", kept as net.grad_precision, "fp32" again after eval()): the operand precision of
-        the Resnet units' gradient products (pp_unit_backward_mp), in effect under the scopes that run them ("block3", "stage3", "rpn",
-        "all") and inert under "head" and "neck".  The forward, the strided stages, the upsamplers, the head and the PFN stay fp32.
-        grad_stages ("units" | "rpn", kept as net.grad_stages, "units" again after eval()): which backwards take grad_precision.  "units":
-        the Resnet units alone, as above.  "rpn": the three strided stages (pp_down_backward_mp) and the three upsamplers
-        (pp_neck_backward_mp) as well, wherever the scope runs them; the head backward, the PFN and the forward stay fp32.
-        bn_stats (BatchNorm networks only, kept as net.bn_stats): "frozen" enables every scope there as fine-tuning with frozen
-        statistics.  Every BatchNorm2d of the RPN stays in eval mode and normalises with its running statistics, which do not move, as
-        does num_batches_tracked; its weight / bias train with the convolution whose backward primitive yields their gradient (a
-        unit's leading norm with that unit's convolution, blockN.1 with the strided convolution, deconvN.1 with the upsampler), so
-        "rpn" trains the 63 tensors of BN_RPN_KEYS and "all" the 66 of BN_ALL_KEYS.  In torch: net.train(), then .eval() on every
-        BatchNorm2d module.  The keyword is explicit because that is not what torch's net.train() alone means; "batch" (batch
-        statistics) is reserved and raises NotImplementedError.  Gradients are fp32 (grad_precision="fp32").  bn_stats governs the RPN's
-        BatchNorm2d layers only: under "all" the PFN's BatchNorm1d normalises with batch statistics and its running statistics move,
-        exactly as on the InstanceNorm network.  None keeps a BatchNorm network to scope="head".
-        bn_stats="moving" is the reference's net.train() on a BatchNorm network: under every scope all nineteen BatchNorm2d of the RPN
-        normalise with the statistics of the batch (all frames of a forward together) and move their running statistics (momentum
-        0.01, unbiased variance) and num_batches_tracked, whether or not grad is enabled; the scope decides which tensors get
-        gradients, exactly as under "frozen".  eval() folds the moved statistics into the engine before the next pass."""
+        the gradient products of the backwards that grad_stages names (kept as net.grad_stages, "units" again after eval()): "units",
+        the Resnet units alone (pp_unit_backward_mp), or "rpn", the three strided stages (pp_down_backward_mp) and the three
+        upsamplers (pp_neck_backward_mp) as well, wherever the scope runs them.  The forward, the head backward, the PFN and every
+        tensor handed around stay fp32.  InstanceNorm backbone only: the BatchNorm backward is fp32.
+        bn_stats (BatchNorm networks only, kept as net.bn_stats; None keeps such a network to scope="head") governs the nineteen
+        BatchNorm2d layers of the RPN; a layer's weight / bias train with the convolution whose backward primitive yields their
+        gradient (a unit's leading norm with that unit's convolution, blockN.1 with the strided convolution, deconvN.1 with the
+        upsampler), so "rpn" trains the 63 tensors of BN_RPN_KEYS and "all" the 66 of BN_ALL_KEYS.  "frozen" fine-tunes: every layer
+        stays in eval mode and normalises with its running statistics, which do not move, as does num_batches_tracked (in torch:
+        net.train(), then .eval() on every BatchNorm2d module).  "moving" is the reference's net.train(): under every scope all
+        nineteen normalise with the statistics of the batch (all frames of a forward together) and move their running statistics
+        (momentum 0.01, unbiased variance) and num_batches_tracked, whether or not grad is enabled; the scope decides which tensors
+        get gradients, exactly as under "frozen", and eval() folds the moved statistics into the engine before the next pass.  The
+        keyword is explicit because "frozen" is not what torch's net.train() alone means; "batch" is refused: "moving" is its name
+        here.  Under "all" the PFN's BatchNorm1d behaves as on the InstanceNorm network whatever bn_stats says."""
         if grad_precision not in GRAD_PRECISIONS:
             raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         if grad_stages not in GRAD_STAGES:
@@ -789,10 +773,11 @@ class PointPillars:
         if self._norm == "batch":  # every layer goes in with its norm's weight and bias
             every.update(self._neck)
             layers = RPN_CONV_KEYS[first:] + NECK_KEYS
+            tensors = [every[n] for k in layers for n in (k, *bn_affine_keys(k))]
             if moving:
-                return self._rpn_train_moving(first, x, [every[n] for k in layers for n in (k, *bn_affine_keys(k))])
+                return self._rpn_train_moving(first, x, tensors)
             stats = [tuple(self._bn_run[f"{Engine.bn_prefix(k)}.{s}"] for s in Engine.BN_FIELDS[2:]) for k in layers]
-            return _RpnBnFunction.apply(eng, first, stats, x, *[every[n] for k in layers for n in (k, *bn_affine_keys(k))])
+            return _RpnBnFunction.apply(eng, first, stats, x, *tensors)
         return _RpnFunction.apply(eng, (self.grad_precision, self.grad_precision if self.grad_stages == "rpn" else "fp32"), first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
 
     def _rpn_train_moving(self, first, x, tensors):

@@ -18,73 +18,14 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import blocktrain_ref as R
+from train_common import (GX, GY, canvases_of, check_bound, check_grad, dev, engine, loaded, random_case, small_cfg, small_net,  # noqa: F401
+                          two_frames)
 
 sys.path.insert(0, GOLDEN)
 from make_blocktrain_goldens import DW_STRIDE, MODULES, small_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 KEYS = load_pkg("engine").Engine.BLOCK3_KEYS  # unit order a .. e
-_ENGINES = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def small_cfg(gx, gy, max_batch):
-    cfg = load_pkg("synth").load_config("eight_20cm")
-    cfg["detection_range"] = [0.0, 0.0, -2.5, 0.2 * gx, 0.2 * gy, 8.5]
-    cfg["max_voxels"] = 2000
-    cfg["device"] = torch.device("cuda:0")
-    cfg["max_batch"] = max_batch
-    return cfg
-
-
-def engine(max_batch=3):
-    """An engine without weights (pp_unit_backward is stateless and takes its map size from the call)."""
-    if max_batch not in _ENGINES:
-        load_pkg().install()
-        _ENGINES[max_batch] = load_pkg("engine").Engine(small_cfg(24, 16, max_batch))
-    return _ENGINES[max_batch]
-
-
-@pytest.fixture(scope="module")
-def loaded():
-    """48 x 32 cells (level-2 map 6 x 4) with the seeded weights committed and a canvas with a few pillars."""
-    load_pkg().install()
-    synth = load_pkg("synth")
-    eng = load_pkg("engine").Engine(small_cfg(48, 32, 2))
-    sd = {k: np.asarray(v, np.float32) for k, v in synth.seeded_state_dict(0).items()}
-    eng.load_state_dict(sd)
-    rng = np.random.default_rng(3)
-    canvas = np.zeros((1, 64, 48, 32), np.float32)
-    cells = rng.choice(48 * 32, 300, replace=False)
-    canvas[0, :, cells // 32, cells % 32] = np.maximum(rng.standard_normal((300, 64)), 0).astype(np.float32)
-    return dict(eng=eng, sd=sd, canvas=dev(canvas))
-
-
-def random_case(C, h, w, nb, seed):
-    rng = np.random.default_rng(seed)
-    u = R.tie_free(rng.standard_normal((nb, C, h, w)))
-    assert not R.near_ties(u, 1e-4).any()
-    wt = (rng.standard_normal((C, C, 3, 3)) * 0.05).astype(np.float32)
-    dz = rng.standard_normal((nb, C, h, w)).astype(np.float32)
-    dskip = rng.standard_normal((nb, C, h, w)).astype(np.float32)
-    return u, wt, dz, dskip
-
-
-def check_grad(got, want64, ref32_dev, scale, what):
-    got = got.cpu().numpy().astype(np.float64).reshape(-1)
-    bar = 4.0 * ref32_dev * scale
-    err = np.abs(got - want64.reshape(-1)).max()
-    print(f"{what}: max err {err:.3e}, bar {bar:.3e} ({err / bar:.2f} of it)")
-    assert err <= bar, what
-
-
-def check_bound(got, want, bound, what):
-    frac = float((np.abs(got.cpu().numpy().astype(np.float64) - want) / bound).max())
-    print(f"{what}: largest fraction of the a-priori bound {frac:.3f}")
-    assert frac <= 1.0, (what, frac)
 
 
 # ------------------------------------------------------------------ 1. fixture gradients
@@ -155,7 +96,7 @@ def test_frames():
 
 
 # ------------------------------------------------------------------ 4. unit taps of block 3
-def test_backbone_block_taps(loaded):
+def test_backbone_block_taps(loaded):  # noqa: F811
     eng, sd, canvas = loaded["eng"], loaded["sd"], loaded["canvas"]
     want = eng.backbone_taps(canvas)
     got = eng.backbone_block_taps(canvas)
@@ -225,42 +166,6 @@ def test_update_block_weights(force, monkeypatch):
 
 
 # ------------------------------------------------------------------ 6 / 7. autograd surface and trajectory
-GX, GY = 48, 32
-
-
-def small_net(seed=0):
-    cfg = small_cfg(GX, GY, 4)
-    load_pkg("framework.voxel_generator").VoxelGenerator(cfg)
-    net = load_pkg("networks.pointpillars8_shared").PointPillars(cfg)
-    net.load_state_dict(load_pkg("synth").seeded_state_dict(seed))
-    return net, cfg
-
-
-def two_frames(eng):
-    rng = np.random.default_rng(4)
-    frames = []
-    for f in range(2):
-        n = 200 + 60 * f
-        cells = rng.choice(GX * GY, n, replace=False)
-        coors = np.stack([cells // GY, cells % GY, np.zeros(n, np.int64)], 1).astype(np.int32)
-        vox = rng.standard_normal((n, eng.T, eng.F)).astype(np.float32)
-        frames.append(dict(voxels=vox, coordinates=coors, num_points_per_voxel=rng.integers(1, eng.T + 1, n).astype(np.int32)))
-    utils = load_pkg("framework.utils")
-    return utils.example_convert_to_torch(utils.merge_second_batch(frames))
-
-
-def canvases_of(eng, example):
-    coors = example["coordinates"]
-    out = []
-    for f in range(2):
-        sel = coors[:, -1] == f
-        c = coors[sel][:, :-1].contiguous()
-        num = eng.num_tensor(c.shape[0])
-        feat = eng.pfn(example["voxels"][sel].contiguous(), c, example["num_points_per_voxel"][sel].contiguous(), num)
-        out.append(eng.scatter(feat, c, num))
-    return out
-
-
 def test_autograd_surface():
     load_pkg().install()
     net, _ = small_net()
@@ -365,7 +270,7 @@ def test_trajectory():
 
 
 # ------------------------------------------------------------------ 8. errors
-def test_bad_arguments_raise_and_the_next_call_works(loaded):
+def test_bad_arguments_raise_and_the_next_call_works(loaded):  # noqa: F811
     eng = engine(2)
     u, wt, dz, dskip = random_case(64, 5, 4, 2, 1)
     args = [dev(u), dev(wt), dev(dz)]

@@ -16,7 +16,7 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import bnbatch_ref as R
-from test_blocktrain_gpu import GX, GY, canvases_of, check_bound, check_grad, dev, engine, small_cfg, two_frames
+from train_common import GX, GY, canvases_of, check_bound, check_grad, dev, engine, small_cfg, two_frames
 from test_bntrain_gpu import ENG, bn_net, bn_sd, check_all, norm_params, same
 
 sys.path.insert(0, GOLDEN)

@@ -17,7 +17,7 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import bntrain_ref as R
-from test_blocktrain_gpu import GX, GY, canvases_of, check_bound, check_grad, dev, engine, small_cfg, two_frames
+from train_common import GX, GY, canvases_of, check_bound, check_grad, dev, engine, small_cfg, two_frames
 
 sys.path.insert(0, GOLDEN)
 from make_bntrain_goldens import DW_STRIDE, DX_STRIDE, small_inputs, split  # noqa: E402
@@ -347,15 +347,15 @@ def test_scopes():
     net.train(scope="neck", bn_stats="frozen")
     frames = canvases_of(eng, example)
     calls = []
-    real = eng.neck_backward_affine
-    eng.neck_backward_affine = lambda *a, **kw: calls.append(kw) or real(*a, **kw)
+    real = eng.neck_backward  # the walk hands the frozen norm over as a record: norm=BackwardNorm(scale, shift, need_affine=...)
+    eng.neck_backward = lambda *a, **kw: calls.append({**kw, "need_affine": kw["norm"].mean is None and kw["norm"].need_affine}) or real(*a, **kw)
     try:
         y = net.rpn_train(torch.cat(frames))
         gh, dxh = eng.head_backward(y.detach(), up["cls_preds"], up["box_preds"], up["dir_preds"])
         net.zero_grad()
         y.backward(dxh)
     finally:
-        del eng.neck_backward_affine
+        del eng.neck_backward
     assert len(calls) == 3 and not any(kw["need_dx"] for kw in calls) and all(kw["need_affine"] for kw in calls)
     taps = [eng.backbone_taps(c) for c in frames]
     p = {k: v.detach() for d in (net._neck, net._bn_run) for k, v in d.items()}

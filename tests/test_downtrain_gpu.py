@@ -18,7 +18,7 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import downtrain_ref as R
-from test_blocktrain_gpu import GX, GY, canvases_of, check_bound, check_grad, dev, small_cfg, small_net, two_frames
+from train_common import GX, GY, canvases_of, check_bound, check_grad, dev, small_cfg, small_net, two_frames
 
 sys.path.insert(0, GOLDEN)
 from make_downtrain_goldens import DW_STRIDE, MODULES, small_inputs  # noqa: E402

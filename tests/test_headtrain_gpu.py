@@ -16,15 +16,12 @@ import torch
 from conftest import GOLDEN, golden, load_pkg
 import headtrain_ref as R
 from test_headtrain_cpu import full_inputs
+from train_common import dev
 
 sys.path.insert(0, GOLDEN)
 from make_headtrain_goldens import KEYS, small_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def small_cfg(max_batch=4, gx=16, gy=12):

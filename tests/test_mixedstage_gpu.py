@@ -17,7 +17,7 @@ import torch
 
 from conftest import load_pkg
 import mixedstage_ref as M
-from test_mixedtrain_gpu import dev, small_cfg, small_net, two_frames
+from train_common import dev, small_cfg, small_net, two_frames
 
 pytestmark = pytest.mark.gpu
 MODES = ("bf16x3", "bf16")

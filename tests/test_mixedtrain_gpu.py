@@ -21,27 +21,14 @@ import torch
 from conftest import load_pkg
 import blocktrain_ref as R
 import mixedtrain_ref as M
+from train_common import check_bound, dev, small_cfg, small_net, two_frames
 
 pytestmark = pytest.mark.gpu
 MODES = ("bf16x3", "bf16")
 SHAPES = [(64, 33, 17, 1), (128, 20, 18, 2), (256, 25, 9, 3), (256, 1, 7, 2), (256, 2, 20, 1), (256, 3, 2, 2), (64, 130, 127, 1)]
 NETWORK_SHAPES = [(64, 400, 400), (128, 200, 200), (256, 100, 100)]
-GX, GY = 48, 32
 _ENGINES = {}
 _CASES = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def small_cfg(gx, gy, max_batch):
-    cfg = load_pkg("synth").load_config("eight_20cm")
-    cfg["detection_range"] = [0.0, 0.0, -2.5, 0.2 * gx, 0.2 * gy, 8.5]
-    cfg["max_voxels"] = 2000
-    cfg["device"] = torch.device("cuda:0")
-    cfg["max_batch"] = max_batch
-    return cfg
 
 
 def engine(max_batch=3):
@@ -64,12 +51,6 @@ def random_case(C, h, w, nb, seed):
         dskip = rng.standard_normal((nb, C, h, w)).astype(np.float32)
         _CASES[key] = (u, wt, dz, dskip)
     return _CASES[key]
-
-
-def check_bound(got, want, bound, what):
-    frac = float((np.abs(got.cpu().numpy().astype(np.float64) - want) / bound).max())
-    print(f"{what}: largest fraction of the a-priori bound {frac:.3f}")
-    assert frac <= 1.0, (what, frac)
 
 
 # ------------------------------------------------------------------ 1. mode 0 is the old call
@@ -165,27 +146,6 @@ def test_frames(mode):
 
 
 # ------------------------------------------------------------------ 5. autograd surface
-def small_net(seed=0):
-    cfg = small_cfg(GX, GY, 4)
-    load_pkg("framework.voxel_generator").VoxelGenerator(cfg)
-    net = load_pkg("networks.pointpillars8_shared").PointPillars(cfg)
-    net.load_state_dict(load_pkg("synth").seeded_state_dict(seed))
-    return net, cfg
-
-
-def two_frames(eng):
-    rng = np.random.default_rng(4)
-    frames = []
-    for f in range(2):
-        n = 200 + 60 * f
-        cells = rng.choice(GX * GY, n, replace=False)
-        coors = np.stack([cells // GY, cells % GY, np.zeros(n, np.int64)], 1).astype(np.int32)
-        vox = rng.standard_normal((n, eng.T, eng.F)).astype(np.float32)
-        frames.append(dict(voxels=vox, coordinates=coors, num_points_per_voxel=rng.integers(1, eng.T + 1, n).astype(np.int32)))
-    utils = load_pkg("framework.utils")
-    return utils.example_convert_to_torch(utils.merge_second_batch(frames))
-
-
 def test_autograd_surface(monkeypatch):
     load_pkg().install()
     net, _ = small_net()

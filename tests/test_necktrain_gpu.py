@@ -15,6 +15,7 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import necktrain_ref as R
+from train_common import canvases_of, check_bound, check_grad, dev, small_cfg
 
 sys.path.insert(0, GOLDEN)
 from make_necktrain_goldens import COFF, CUP, DW_STRIDE, small_inputs  # noqa: E402
@@ -22,19 +23,6 @@ from make_necktrain_goldens import COFF, CUP, DW_STRIDE, small_inputs  # noqa: E
 pytestmark = pytest.mark.gpu
 KEYS = R.KEYS
 _ENGINES = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def small_cfg(gx, gy, max_batch):
-    cfg = load_pkg("synth").load_config("eight_20cm")
-    cfg["detection_range"] = [0.0, 0.0, -2.5, 0.2 * gx, 0.2 * gy, 8.5]
-    cfg["max_voxels"] = 2000
-    cfg["device"] = torch.device("cuda:0")
-    cfg["max_batch"] = max_batch
-    return cfg
 
 
 def engine(gx, gy, max_batch=3):
@@ -70,20 +58,6 @@ def random_case(H, W, nb, seed):
     y = np.concatenate([R.branch_forward(xs[b], ws[b]) for b in range(3)], 1).astype(np.float32)
     dy = rng.standard_normal((nb, 320, H, W)).astype(np.float32)
     return xs, ws, y, dy
-
-
-def check_grad(got, want64, ref32_dev, scale, what):
-    got = got.cpu().numpy().astype(np.float64).reshape(-1)
-    bar = 4.0 * ref32_dev * scale
-    err = np.abs(got - want64.reshape(-1)).max()
-    print(f"{what}: max err {err:.3e}, bar {bar:.3e} ({err / bar:.2f} of it)")
-    assert err <= bar, what
-
-
-def check_bound(got, want, bound, what):
-    frac = float((np.abs(got.cpu().numpy().astype(np.float64) - want) / bound).max())
-    print(f"{what}: largest fraction of the a-priori bound {frac:.3f}")
-    assert frac <= 1.0, (what, frac)
 
 
 # ------------------------------------------------------------------ 1. fixture gradients
@@ -205,18 +179,6 @@ def two_frames(eng):
         frames.append(dict(voxels=vox, coordinates=coors, num_points_per_voxel=rng.integers(1, eng.T + 1, n).astype(np.int32)))
     utils = load_pkg("framework.utils")
     return utils.example_convert_to_torch(utils.merge_second_batch(frames))
-
-
-def canvases_of(eng, example):
-    coors = example["coordinates"]
-    out = []
-    for f in range(2):
-        sel = coors[:, -1] == f
-        c = coors[sel][:, :-1].contiguous()
-        num = eng.num_tensor(c.shape[0])
-        feat = eng.pfn(example["voxels"][sel].contiguous(), c, example["num_points_per_voxel"][sel].contiguous(), num)
-        out.append(eng.scatter(feat, c, num))
-    return out
 
 
 def test_autograd_surface():

@@ -4,7 +4,7 @@ and the autograd surface PointPillars.train(scope="all") -- against the referenc
 (tests/golden/make_pfntrain_goldens.py) and the float64 restatement pinned to them (tests/pfntrain_ref.py).
 
 Bars.  Fixture values and gradients: 4 x ref32_dev x max |x64| per tensor, ref32_dev being the reference's own float32-against-float64
-deviation stored in the fixture (the project's margin, test_blocktrain_gpu.check_grad).  The fixture's seed keeps every argmax and ReLU
+deviation stored in the fixture (the project's margin, train_common.check_grad).  The fixture's seed keeps every argmax and ReLU
 decision 2^-15 away from a tie, so arg is compared exactly.  At 5000 pillars near-ties cannot be excluded: there the GPU's selection
 must maximise the float64 activations to within 1e-5, and the gradients are compared, at case a's bars (same pillar geometry), with the
 restatement evaluated at the GPU's own selection and ReLU branches.  Equality is asserted between two runs, between the autograd
@@ -18,8 +18,7 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import pfntrain_ref as R
-from test_blocktrain_gpu import GX, GY, canvases_of, dev, small_cfg, small_net, two_frames  # noqa: F401
-from test_rpntrain_gpu import by_hand, seeded_sd, stacked_taps
+from train_common import GX, GY, by_hand, canvases_of, dev, seeded_sd, small_cfg, small_net, stacked_taps, two_frames  # noqa: F401
 
 sys.path.insert(0, GOLDEN)
 import make_pfntrain_goldens as G  # noqa: E402
@@ -337,7 +336,7 @@ def test_trajectory():
 
 def test_rpn_scope_is_unchanged():
     """Scope "rpn" on a freshly loaded network: the forward is the inference forward and the gradients are those of the chain made by
-    hand from the frozen eval-mode PFN's canvases (test_rpntrain_gpu.by_hand): the code path of the scopes that existed before."""
+    hand from the frozen eval-mode PFN's canvases (train_common.by_hand): the code path of the scopes that existed before."""
     load_pkg().install()
     shared = load_pkg("networks.pointpillars8_shared")
     net, _ = small_net()

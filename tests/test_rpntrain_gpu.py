@@ -4,7 +4,7 @@ PointPillars.train(scope="rpn") -- against the reference's float64 autograd gold
 float64 restatement pinned to them (tests/rpntrain_ref.py).
 
 Bars.  Fixture gradients: 4 x ref32_dev x max |g64| per tensor, ref32_dev being the reference's own float32-against-float64 deviation
-stored in the fixture (test_blocktrain_gpu.check_grad).  Per-convolution gradients of the autograd surface: the element-wise a-priori
+stored in the fixture (train_common.check_grad).  Per-convolution gradients of the autograd surface: the element-wise a-priori
 bounds of blocktrain_ref.grad_bounds / downtrain_ref.grad_bounds, evaluated from the GPU's own taps.  Taps: the backbone's bar of 2e-4
 against the float64 restatement of the forward (the CPU oracle of the intermediate tensors; oracle/pp_oracle.py hands out rpn_out
 only, which is compared as well).  Equality is asserted between the tap entry points, between the autograd surface and the same chain
@@ -19,7 +19,8 @@ import torch
 
 from conftest import GOLDEN, golden, load_pkg
 import rpntrain_ref as R
-from test_blocktrain_gpu import GX, GY, canvases_of, check_bound, check_grad, dev, loaded, small_cfg, small_net, two_frames  # noqa: F401
+from train_common import (GX, GY, by_hand, canvases_of, check_bound, check_grad, dev, loaded, seeded_sd, small_cfg, small_net,  # noqa: F401
+                          stacked_taps, two_frames)
 
 sys.path.insert(0, GOLDEN)
 from make_rpntrain_goldens import DW_STRIDE, DX_STRIDE, small_inputs, split  # noqa: E402
@@ -28,58 +29,6 @@ pytestmark = pytest.mark.gpu
 ENG = load_pkg("engine").Engine
 CONV, NECK = ENG.RPN_CONV_KEYS, ENG.NECK_KEYS
 BAR = 2e-4  # the project's backbone bar
-
-
-def seeded_sd(seed=0):
-    return {k: np.asarray(v, np.float32) for k, v in load_pkg("synth").seeded_state_dict(seed).items()}
-
-
-def stacked_taps(eng, canvases):
-    """backbone_train_taps per frame, stacked: y, (x1, x2, x3), per level the list of unit inputs [nb,C,h,w], (z1, z2, z3)."""
-    outs = [eng.backbone_train_taps(c) for c in canvases]
-    y = torch.cat([o[0] for o in outs])
-    xs = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
-    units = [[torch.stack([o[2][b][k] for o in outs]) for k in range(ENG.RPN_UNITS[b])] for b in range(3)]
-    zs = [torch.cat([o[3][b] for o in outs]) for b in range(3)]
-    return y, xs, units, zs
-
-
-def by_hand(eng, canvas, taps, p, gy, need_dx):
-    """The backward of the whole RPN with the engine primitives, written out: -> ({key: dw}, dcanvas, {conv key: the (input, dy) the
-    call saw})."""
-    y, xs, units, zs = taps
-    dw, seen = {}, {}
-    dxn = []
-    for b in range(3):
-        dw[NECK[b]], dx = eng.neck_backward(b, xs[b], p[NECK[b]], y, gy, need_dx=True)
-        dxn.append(dx)
-
-    def unit(key, u, g, dskip=None):
-        dw[key], du = eng.unit_backward(u, p[key], g, dskip=dskip)
-        seen[key] = (u, g)
-        return du
-
-    def down(key, x, z, g, need=True):
-        dw[key], dx = eng.down_backward(x, p[key], z, g, need_dx=need)
-        seen[key] = (x, z, g)
-        return dx
-
-    g = dxn[2]
-    for b in (2, 1):  # h -> r3 = h + U_b(U_a(h)), r4 = r3 + U_d(U_c(r3)), x = r4 + U_e(r4)
-        k0, ka, kb, kc, kd, ke = CONV[4 + 6 * (b - 1):10 + 6 * (b - 1)]
-        h, m3, r3, m4, r4 = units[b]
-        g_r4 = unit(ke, r4, g, dskip=g)
-        g_m4 = unit(kd, m4, g_r4)
-        g_r3 = unit(kc, r3, g_m4, dskip=g_r4)
-        g_m3 = unit(kb, m3, g_r3)
-        g_h = unit(ka, h, g_m3, dskip=g_r3)
-        g = dxn[b - 1] + down(k0, xs[b - 1], zs[b], g_h)  # the upsampler's dx, then the stage's
-    k0, ka, kb, kc = CONV[:4]  # h -> r = h + U_b(U_a(h)), x1 = r + U_c(r)
-    h, m, r = units[0]
-    g_r = unit(kc, r, g, dskip=g)
-    g_m = unit(kb, m, g_r)
-    g_h = unit(ka, h, g_m, dskip=g_r)
-    return dw, down(k0, canvas, zs[0], g_h, need=need_dx), seen
 
 
 # ------------------------------------------------------------------ 1. taps

@@ -17,8 +17,8 @@ import torch
 
 import blocktrain_ref as RB
 import downtrain_ref as RD
-from test_blocktrain_gpu import check_bound, dev, engine
-from test_blocktrain_gpu import random_case as unit_case
+from train_common import check_bound, dev, engine
+from train_common import random_case as unit_case
 from test_downtrain_gpu import random_case as down_case
 
 pytestmark = pytest.mark.gpu

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from conftest import load_pkg
-from test_blocktrain_gpu import small_cfg
+from train_common import small_cfg
 
 pytestmark = pytest.mark.gpu
 PP_E_ARG = 1

@@ -33,7 +33,7 @@ import bntrain_ref as A
 import mixedstage_ref as S
 import mixedtrain_ref as M
 import rpntrain_ref as RR
-from test_blocktrain_gpu import check_bound, check_grad, dev, small_cfg
+from train_common import check_bound, check_grad, dev, small_cfg
 from test_bnbatch_gpu import chunks_agree, folded32
 from test_bntrain_gpu import bn_net, bn_sd, down_case as affine_down_case, norm_params, same, unit_case as affine_unit_case
 from test_mixedtrain_gpu import random_case as unit_case
