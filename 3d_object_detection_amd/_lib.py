@@ -111,6 +111,16 @@ PROTOTYPES = {
     "pp_unit_backward_bn": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
     "pp_down_backward_bn": (ctypes.c_int, [c_p] + [ctypes.c_int] * 4 + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
     "pp_neck_backward_bn": (ctypes.c_int, [c_p, ctypes.c_int] + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    # the six BatchNorm backwards with `int mode` behind the context (their fp32 siblings' lists otherwise), and their path queries
+    "pp_unit_backward_affine_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 4 + [c_p] * 6 + [ctypes.c_int] + [c_p] * 5),
+    "pp_down_backward_affine_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 5 + [c_p] * 6 + [ctypes.c_int] + [c_p] * 5),
+    "pp_neck_backward_affine_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 2 + [c_p] * 6 + [ctypes.c_int] + [c_p] * 5),
+    "pp_unit_backward_bn_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 4 + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    "pp_down_backward_bn_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 5 + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    "pp_neck_backward_bn_mp": (ctypes.c_int, [c_p] + [ctypes.c_int] * 2 + [c_p] * 8 + [ctypes.c_int] + [c_p] * 4 + [ctypes.c_int, c_p]),
+    "pp_unit_backward_bn_path": (ctypes.c_int, [c_p] + [ctypes.c_int] * 4),
+    "pp_down_backward_bn_path": (ctypes.c_int, [c_p] + [ctypes.c_int] * 5),
+    "pp_neck_backward_bn_path": (ctypes.c_int, [c_p] + [ctypes.c_int] * 2),
     "pp_set_train_chunk_frames": (ctypes.c_int, [c_p, ctypes.c_int]),
     "pp_pfn_train_forward": (ctypes.c_int, [c_p] * 12),
     "pp_scatter_backward": (ctypes.c_int, [c_p] * 6),

@@ -1,7 +1,8 @@
 // The Resnet unit backward's own part of the training host side, shared by block_train.hip (fp32) and block_train16.hip (its 16-bit
-// operand twins): the workspace of a context and its budget rules, and the one check and plan of the family.  The fp32 driver
-// (unit_run) is block_train.hip's; the twin keeps a driver of its own (its pack, norm kernels and images differ) over the same check,
-// plan and chunk walk.  What the three families share (workspace growth, the padded-plane geometry, the frame chunks and K ranges, the
+// operand twins): the workspace of a context and its budget rules, the one check and plan of the family, and the passes behind the
+// dgrad of the two BatchNorm forms (k_affine_unit_du, k_bn_unit_sums, k_bn_unit_du), which read u and du only.  The fp32 driver
+// (unit_run) is block_train.hip's; the twin keeps a driver of its own (its pack, its InstanceNorm kernels and images differ) over the
+// same check, plan and chunk walk.  What the three families share (workspace growth, the padded-plane geometry, the frame chunks and K ranges, the
 // reduction of the dw partials) is train_host.h's.
 #pragma once
 #include "pp_common.h"
@@ -77,6 +78,95 @@ inline int unit_check(pp_ctx* ctx, const char* entry, int what, norm_form form, 
     if ((what & UNIT_CHK_BUDGET) && 2 * (uint64_t)s.C * padded_plane(s.h, s.w).elems * sizeof(float) > WS_BUDGET)
         return train_fail(ctx, entry, "map too large (one frame's planes exceed the 256 MB workspace)");
     return 0;
+}
+
+// ---- the passes behind the dgrad of the two BatchNorm forms, run by the fp32 driver and by the 16-bit twin.  a = max(fma(u, scale,
+// shift), 0) is the forward prologue's expression (affine_relu); fma rounds once and keeps the sign, so fma(u, scale, shift) > 0,
+// re-evaluated from u, is the mask a > 0 bit for bit.
+// k_affine_unit_du: grid (C, frames, S), in place over da: g = da [a > 0], du = scale g (+ dskip), and the segment's sum g u, sum g in
+// fp64 -> pst[frame][c][segment][2].  FROM_U = false reads the mask from the fp32 plane of a (ap); FROM_U = true re-evaluates it from u:
+// the twin keeps no fp32 image of a (ap is null there) --------------------------------------------------------------------------------------
+__device__ __forceinline__ float affine_relu(float u, float sc, float sh) { return fmaxf(fmaf(u, sc, sh), 0.f); }
+
+template <bool FROM_U>
+__global__ void __launch_bounds__(256) k_affine_unit_du(const float* __restrict__ u, const float* __restrict__ ap, const float* __restrict__ scale,
+                                                        const float* __restrict__ shift, const float* __restrict__ dskip, float* __restrict__ du,
+                                                        double* __restrict__ pst, int C, int w, int wp, int G, int PS, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* ai = FROM_U ? nullptr : ap + pl * PS + G + wp + 1; // interior origin
+    float* dp = du + pl * N;
+    const float sc = scale[blockIdx.x], sh = FROM_U ? shift[blockIdx.x] : 0.f;
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sgu = 0.0, sg = 0.0;
+    for (int i = lo + tid; i < hi; i += 256) {
+        const float uu = up[i];
+        bool on;
+        if (FROM_U) {
+            on = fmaf(uu, sc, sh) > 0.f;
+        } else {
+            const int y = i / w, x = i - y * w;
+            on = ai[y * wp + x] > 0.f;
+        }
+        const float g = on ? dp[i] : 0.f;
+        sgu += (double)g * (double)uu; sg += (double)g;
+        float v = sc * g;
+        if (dskip) v = v + dskip[pl * N + i];
+        dp[i] = v;
+    }
+    block_sum2(sgu, sg, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
+}
+
+// ---- the unit behind a train-mode BatchNorm (pp_unit_backward_bn): k_affine_unit_pack and the two products as above, the raw da left in
+// du.  The norm backward needs the sums of ALL frames, so it runs behind the frame chunks, on u and du alone: the mask is re-evaluated
+// by the pack's own fma.  k_bn_unit_sums: grid (C, frames, S), g = da [fma(u, scale, shift) > 0], the segment's sum g u, sum g in fp64
+// -> pst[frame][c][segment][2].  k_bn_unit_du: same grid, in place once k_bn_coef has pooled them:
+// du = scale ((g - c1) - xhat c2) (+ dskip), xhat = (u - mean) r ------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_bn_unit_sums(const float* __restrict__ u, const float* __restrict__ du, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, double* __restrict__ pst, int C, int N, int L, int S)
+{
+    __shared__ double red[256][2];
+    const int tid = threadIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float* up = u + pl * N;
+    const float* dp = du + pl * N;
+    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    double sgu = 0.0, sg = 0.0;
+    strided4(lo, hi, [&](int i) { return float2{up[i], dp[i]}; },
+             [&](float2 v) {
+                 if (fmaf(v.x, sc, sh) > 0.f) {
+                     const double g = (double)v.y;
+                     sgu += g * (double)v.x; sg += g;
+                 }
+             });
+    block_sum2(sgu, sg, red);
+    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
+}
+
+__global__ void __launch_bounds__(256) k_bn_unit_du(const float* __restrict__ u, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                    const float* __restrict__ coef, const float* __restrict__ dskip, float* __restrict__ du, int C,
+                                                    int N, int L)
+{
+    const int tid = threadIdx.x, c = blockIdx.x;
+    const size_t pl = (size_t)blockIdx.y * C + c;
+    const float* up = u + pl * N;
+    float* dp = du + pl * N;
+    const float sc = scale[c], sh = shift[c];
+    const float c1 = coef[4 * c], c2 = coef[4 * c + 1], meanf = coef[4 * c + 2], rf = coef[4 * c + 3];
+    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
+    for (int i = lo + tid; i < hi; i += 256) {
+        const float uu = up[i];
+        const float g = fmaf(uu, sc, sh) > 0.f ? dp[i] : 0.f;
+        const float xhat = (uu - meanf) * rf;
+        float v = sc * ((g - c1) - xhat * c2);
+        if (dskip) v = v + dskip[pl * N + i];
+        dp[i] = v;
+    }
 }
 
 // ---- everything of a call that is a function of the shapes (and, for the twin, the mode) alone: the planes `g` (padded_plane for fp32,

@@ -28,8 +28,9 @@
 // products, k_affine_unit_du and k_affine_reduce; pp_unit_backward itself stays the InstanceNorm backbone's.
 // pp_unit_backward_bn is that unit behind a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_unit_sums behind the
 // dgrad of every chunk, then k_bn_coef and one in-place k_bn_unit_du over all frames.
-// block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp); what both share (the check and the plan of a call) is in block_train.h,
-// what all three training families share in train_host.h.  The three entries are thin wrappers over unit_check and unit_run.
+// block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp and the _affine_mp / _bn_mp entries); what both
+// share (the check and the plan of a call, the passes behind the dgrad of the two BatchNorm forms) is in block_train.h, what all three
+// training families share in train_host.h.  The three entries are thin wrappers over unit_check and unit_run.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -258,8 +259,8 @@ __global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, 
 
 // ---- the unit with a per-channel affine in place of the InstanceNorm (pp_unit_backward_affine): a = max(fma(u, scale, shift), 0), the
 // forward prologue's expression, so there are no statistics passes.  k_affine_unit_pack: grid (C, frames, SP) as k_unit_pack.
-// k_affine_unit_du: grid (C, frames, S), in place over da: g = da [a > 0], du = scale g (+ dskip), and the segment's sum g u, sum g in
-// fp64 -> pst[frame][c][segment][2] -------------------------------------------------------------------------------------------------------
+// The passes behind the dgrad (k_affine_unit_du; k_bn_unit_sums, k_bn_unit_du for the batch form) are block_train.h's: the 16-bit twin
+// runs them too ----------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_affine_unit_pack(const float* __restrict__ u, const float* __restrict__ dy, float* __restrict__ ap,
                                                           float* __restrict__ dzp, const float* __restrict__ scale, const float* __restrict__ shift,
                                                           int C, int h, int w, int wp, int G, int PP, int PS, int LP)
@@ -279,84 +280,11 @@ __global__ void __launch_bounds__(256) k_affine_unit_pack(const float* __restric
             const int y = P / wp, x = P - y * wp;
             if (y >= 1 && y <= h && x >= 1 && x <= w) {
                 const int i = (y - 1) * w + x - 1;
-                av = fmaxf(fmaf(up[i], sc, sh), 0.f);
+                av = affine_relu(up[i], sc, sh);
                 dv = dp[i];
             }
         }
         ao[j] = av; zo[j] = dv;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_affine_unit_du(const float* __restrict__ u, const float* __restrict__ ap, const float* __restrict__ scale,
-                                                        const float* __restrict__ dskip, float* __restrict__ du, double* __restrict__ pst, int C,
-                                                        int w, int wp, int G, int PS, int N, int L, int S)
-{
-    __shared__ double red[256][2];
-    const int tid = threadIdx.x;
-    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    const float* up = u + pl * N;
-    const float* ai = ap + pl * PS + G + wp + 1; // interior origin
-    float* dp = du + pl * N;
-    const float sc = scale[blockIdx.x];
-    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
-    double sgu = 0.0, sg = 0.0;
-    for (int i = lo + tid; i < hi; i += 256) {
-        const int y = i / w, x = i - y * w;
-        const float g = ai[y * wp + x] > 0.f ? dp[i] : 0.f;
-        sgu += (double)g * (double)up[i]; sg += (double)g;
-        float v = sc * g;
-        if (dskip) v = v + dskip[pl * N + i];
-        dp[i] = v;
-    }
-    block_sum2(sgu, sg, red);
-    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
-}
-
-// ---- the unit behind a train-mode BatchNorm (pp_unit_backward_bn): k_affine_unit_pack and the two products as above, the raw da left in
-// du.  The norm backward needs the sums of ALL frames, so it runs behind the frame chunks, on u and du alone: the mask is re-evaluated
-// by the pack's own fma.  k_bn_unit_sums: grid (C, frames, S), g = da [fma(u, scale, shift) > 0], the segment's sum g u, sum g in fp64
-// -> pst[frame][c][segment][2].  k_bn_unit_du: same grid, in place once k_bn_coef has pooled them:
-// du = scale ((g - c1) - xhat c2) (+ dskip), xhat = (u - mean) r ------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_bn_unit_sums(const float* __restrict__ u, const float* __restrict__ du, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, double* __restrict__ pst, int C, int N, int L, int S)
-{
-    __shared__ double red[256][2];
-    const int tid = threadIdx.x;
-    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    const float* up = u + pl * N;
-    const float* dp = du + pl * N;
-    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
-    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
-    double sgu = 0.0, sg = 0.0;
-    strided4(lo, hi, [&](int i) { return float2{up[i], dp[i]}; },
-             [&](float2 v) {
-                 if (fmaf(v.x, sc, sh) > 0.f) {
-                     const double g = (double)v.y;
-                     sgu += g * (double)v.x; sg += g;
-                 }
-             });
-    block_sum2(sgu, sg, red);
-    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
-}
-
-__global__ void __launch_bounds__(256) k_bn_unit_du(const float* __restrict__ u, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                    const float* __restrict__ coef, const float* __restrict__ dskip, float* __restrict__ du, int C,
-                                                    int N, int L)
-{
-    const int tid = threadIdx.x, c = blockIdx.x;
-    const size_t pl = (size_t)blockIdx.y * C + c;
-    const float* up = u + pl * N;
-    float* dp = du + pl * N;
-    const float sc = scale[c], sh = shift[c];
-    const float c1 = coef[4 * c], c2 = coef[4 * c + 1], meanf = coef[4 * c + 2], rf = coef[4 * c + 3];
-    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
-    for (int i = lo + tid; i < hi; i += 256) {
-        const float uu = up[i];
-        const float g = fmaf(uu, sc, sh) > 0.f ? dp[i] : 0.f;
-        const float xhat = (uu - meanf) * rf;
-        float v = sc * ((g - c1) - xhat * c2);
-        if (dskip) v = v + dskip[pl * N + i];
-        dp[i] = v;
     }
 }
 
@@ -475,8 +403,8 @@ int unit_run(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& 
             hipLaunchKernelGGL(k_unit_norm, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ap, ws->stm, ws->pst, a.dskip ? a.dskip + o : nullptr, duc, C,
                                h, w, wp, G, PS, L, S);
         } else if (form == NORM_AFFINE) {
-            hipLaunchKernelGGL(k_affine_unit_du, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ap, a.scale, a.dskip ? a.dskip + o : nullptr, duc,
-                               ws->pst + (size_t)c.f0 * C * S * 2, C, w, wp, G, PS, N, L, S);
+            hipLaunchKernelGGL(k_affine_unit_du<false>, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ap, a.scale, a.shift,
+                               a.dskip ? a.dskip + o : nullptr, duc, ws->pst + (size_t)c.f0 * C * S * 2, C, w, wp, G, PS, N, L, S);
         } else {
             hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
                                C, N, L, S);

@@ -6,6 +6,7 @@
 //   k_unit_wt16     wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the dgrad's A operand, 8 consecutive co per lane
 //   k_plane_stats   as in block_train.hip (train_planes.h)
 //   k_unit_pack16   mean / rstd by k_unit_pack's expressions; a and dz into padded bf16 planes, 8 positions per thread
+//   k_affine_unit_pack16  the same planes for the BatchNorm forms: a by the affine, no statistics
 //   k_unit_packT16  zT[P][co]: dz once more with the channel innermost, the dgrad's B operand
 //   k_unit_wgrad16  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      K = frames x PP16 in chunks of 32 positions
 //   k_unit_dgrad16  da[ci][P] = sum_{t, co} wT16[t][ci][co] zT[P - off_t][co]        K = 9 C in steps of 32, blocks of DA_BLOCK = 64
@@ -21,6 +22,12 @@
 // 400 x 400, 127 MB per frame) 8 where fp32 holds 12, so nb = 8 still runs as one chunk in every mode and a batch of 9 .. 12 frames
 // splits under bf16x3 only.  That moves the K ranges of dw, not the bits of du.  A frame whose images exceed the 256 MB budget runs the
 // fp32 kernels.
+//
+// The two BatchNorm forms (pp_unit_backward_affine_mp, pp_unit_backward_bn_mp) run the same products behind k_affine_unit_pack16, which has
+// k_unit_pack16's grid and layout and no statistics: a = max(fma(u, scale, shift), 0) in fp32 by k_affine_unit_pack's expression, then
+// rounded or split.  Behind the dgrad they run block_train.h's passes, which read u and du only: k_affine_unit_du<true> (the mask
+// fma(u, scale, shift) > 0 re-evaluated from u: the fp32 path's mask bit for bit) and k_affine_reduce for the affine form; k_bn_unit_sums
+// per chunk, then k_bn_coef and one in-place k_bn_unit_du over all frames for the batch form, whatever frames the 16-bit chunks held.
 //
 // Determinism as in block_train.hip: no atomics, K ranges, segments and chunks are functions of the shapes (and the mode) alone.
 #include <cmath>
@@ -43,24 +50,15 @@ __global__ void __launch_bounds__(256) k_unit_wt16(const float* __restrict__ w, 
     if (X3) wT[(size_t)9 * C * C + i] = (uint16_t)pk_bf16(bf16_rest(v), 0.f);
 }
 
-// ---- a and dz: grid (C, frames, SP), a thread takes groups of 8 positions (one row: wp and G are multiples of 8).  mean and rstd by
-// k_unit_pack's expressions, so the mask is fp32's.  a16, z16: [part][frame][C][PS]; pstride = the elements of one part ----------------
-template <bool X3>
-__global__ void __launch_bounds__(256) k_unit_pack16(const float* __restrict__ u, const float* __restrict__ dy, uint16_t* __restrict__ a16,
-                                                     uint16_t* __restrict__ z16, float* __restrict__ stm, const double* __restrict__ pst, int C, int h,
-                                                     int w, int wp, int G, int PP, int PS, int S, int LG, size_t pstride)
+// ---- a and dz: grid (C, frames, SP), a thread takes groups of 8 positions (one row: wp and G are multiples of 8).  pack16_plane is the
+// body of both pack kernels: act(u) is the form's a in fp32, rounded (bf16) or split (bf16x3) behind it, dz likewise; halo and guards are
+// rewritten with zeros.  a16, z16: [part][frame][C][PS]; pstride = the elements of one part ------------------------------------------------
+template <bool X3, typename ACT>
+__device__ __forceinline__ void pack16_plane(const float* __restrict__ up, const float* __restrict__ dp, uint16_t* __restrict__ a16,
+                                             uint16_t* __restrict__ z16, size_t pl, int h, int w, int wp, int G, int PP, int PS, int LG, size_t pstride,
+                                             ACT act)
 {
-    const int tid = threadIdx.x, N = h * w;
-    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    const float* up = u + pl * N;
-    const float* dp = dy + pl * N;
-    double s = 0.0, ss = 0.0;
-    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
-    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
-    double var = ss * inv_n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
-    if (tid == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    const int tid = threadIdx.x;
     const int ng = PS / 8, lo = blockIdx.z * LG, hi = lo + LG < ng ? lo + LG : ng;
     for (int g = lo + tid; g < hi; g += 256) {
         const int j = 8 * g, P = j - G;
@@ -75,8 +73,7 @@ __global__ void __launch_bounds__(256) k_unit_pack16(const float* __restrict__ u
                 for (int e = 0; e < 8; ++e) {
                     const int x = x0 + e;
                     if (x >= 1 && x <= w) {
-                        const float xhat = (up[r + x] - meanf) * rstdf;
-                        av[e] = xhat > 0.f ? xhat : 0.f;
+                        av[e] = act(up[r + x]);
                         dv[e] = dp[r + x];
                     }
                 }
@@ -90,6 +87,40 @@ __global__ void __launch_bounds__(256) k_unit_pack16(const float* __restrict__ u
             *reinterpret_cast<u32x4*>(z16 + pstride + o) = pk8_rest(dv);
         }
     }
+}
+
+// InstanceNorm: mean and rstd by k_unit_pack's expressions, so the mask is fp32's
+template <bool X3>
+__global__ void __launch_bounds__(256) k_unit_pack16(const float* __restrict__ u, const float* __restrict__ dy, uint16_t* __restrict__ a16,
+                                                     uint16_t* __restrict__ z16, float* __restrict__ stm, const double* __restrict__ pst, int C, int h,
+                                                     int w, int wp, int G, int PP, int PS, int S, int LG, size_t pstride)
+{
+    const int tid = threadIdx.x, N = h * w;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    double s = 0.0, ss = 0.0;
+    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
+    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
+    double var = ss * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
+    if (tid == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    pack16_plane<X3>(u + pl * N, dy + pl * N, a16, z16, pl, h, w, wp, G, PP, PS, LG, pstride, [&](float v) {
+        const float xhat = (v - meanf) * rstdf;
+        return xhat > 0.f ? xhat : 0.f;
+    });
+}
+
+// the two BatchNorm forms: a = max(fma(u, scale_c, shift_c), 0) by k_affine_unit_pack's expression, no statistics
+template <bool X3>
+__global__ void __launch_bounds__(256) k_affine_unit_pack16(const float* __restrict__ u, const float* __restrict__ dy, uint16_t* __restrict__ a16,
+                                                            uint16_t* __restrict__ z16, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, int C, int h, int w, int wp, int G, int PP, int PS,
+                                                            int LG, size_t pstride)
+{
+    const int N = h * w;
+    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
+    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
+    pack16_plane<X3>(u + pl * N, dy + pl * N, a16, z16, pl, h, w, wp, G, PP, PS, LG, pstride, [&](float v) { return affine_relu(v, sc, sh); });
 }
 
 // ---- zT[part][frame][PS][C]: grid (ceil(PS / 64), C / 64, frames), a 64 position x 64 channel tile through LDS ----------------------
@@ -327,10 +358,14 @@ inline pad_geom planes16(int h, int w)
 // bytes of one frame's 16-bit images: a, dz and zT, each of `parts` bf16 images
 inline uint64_t frame16_bytes(int parts, int C, const pad_geom& g) { return (uint64_t)3 * parts * C * g.elems * sizeof(uint16_t); }
 
-// The twin's driver: the check, the plan, the chunk walk and the reduce are the family's; the pack, the norm kernels and the images are
-// its own.
+// The twin's driver for the three norm forms: the check, the plan, the chunk walk, the reduce and the passes behind the dgrad of the two
+// BatchNorm forms are the family's; the packs, the InstanceNorm kernels and the images are its own.  The forms differ as in unit_run:
+// InstanceNorm runs the statistics and k_unit_pack16 ahead of the products and its two norm passes behind the dgrad; the affine form
+// k_affine_unit_pack16 and k_affine_unit_du<true> per chunk, k_affine_reduce behind the chunks; the batch form the affine pack and
+// k_bn_unit_sums per chunk (raw da -> du), and behind the chunks k_bn_coef and one in-place k_bn_unit_du over all frames.  Those passes
+// read u and du alone, so the batch form does not care that a 16-bit chunk holds other frames than an fp32 one.
 template <bool X3>
-int unit_backward16(pp_ctx* ctx, const unit_shape& s, const unit_args& a)
+int unit_backward16(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& a)
 {
     const int C = s.C, h = s.h, w = s.w, nb = a.nb, parts = X3 ? 2 : 1;
     hipStream_t stream = a.stream;
@@ -339,13 +374,16 @@ int unit_backward16(pp_ctx* ctx, const unit_shape& s, const unit_args& a)
     PP_HIP(hipSetDevice(ctx->device));
     block_ws* ws = workspace(ctx);
     // a wgrad tile: k_unit_wgrad16<4, 4, 2> (128 x 128) or <3, 4, 1> (64 x 192)
-    const unit_plan p = unit_make_plan(ctx, s, nb, 0, g, frame16_bytes(parts, C, g), 32, C >= 128 ? 128 : 64);
+    const unit_plan p = unit_make_plan(ctx, s, nb, a.chunk_frames, g, frame16_bytes(parts, C, g), 32, C >= 128 ? 128 : 64);
     const int N = p.N, fc = p.fc, S = p.S, L = p.L, SP = p.SP, LG = (PS / 8 + SP - 1) / SP;
     const size_t pstride = (size_t)fc * p.pf_elems; // one part of one image over the chunk's frames
+    // stm, pst: unit_run's rules for the forms
+    const size_t stm_elems = form == NORM_INSTANCE ? (size_t)fc * C * 2 : (size_t)C * 4;
+    const size_t pst_elems = (size_t)(form == NORM_INSTANCE ? fc : nb) * C * SEG_MAX * 2;
     int rc;
     if ((rc = grow(ctx, &ws->img16, &ws->img16_elems, 3 * parts * pstride)) ||
-        (rc = grow(ctx, &ws->stm, &ws->stm_elems, (size_t)fc * C * 2)) ||
-        (rc = grow(ctx, &ws->pst, &ws->pst_elems, (size_t)fc * C * SEG_MAX * 2)) ||
+        (form != NORM_AFFINE && (rc = grow(ctx, &ws->stm, &ws->stm_elems, stm_elems))) ||
+        (rc = grow(ctx, &ws->pst, &ws->pst_elems, pst_elems)) ||
         (rc = grow(ctx, &ws->part, &ws->part_elems, (size_t)p.Gp * p.nw)) ||
         (a.du && (rc = grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)parts * p.nw))))
         return rc;
@@ -356,9 +394,14 @@ int unit_backward16(pp_ctx* ctx, const unit_shape& s, const unit_args& a)
     for_chunks(p.walk, [&](const dw_chunk& c) {
         const int fn = c.fn;
         const size_t o = (size_t)c.f0 * C * N;
-        hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->pst, C, N, L, S);
-        hipLaunchKernelGGL(k_unit_pack16<X3>, dim3(C, fn, SP), dim3(256), 0, stream, a.u + o, a.dy + o, a16, z16, ws->stm, ws->pst, C, h, w, wp, G, PP,
-                           PS, S, LG, pstride);
+        if (form == NORM_INSTANCE) {
+            hipLaunchKernelGGL(k_plane_stats, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->pst, C, N, L, S);
+            hipLaunchKernelGGL(k_unit_pack16<X3>, dim3(C, fn, SP), dim3(256), 0, stream, a.u + o, a.dy + o, a16, z16, ws->stm, ws->pst, C, h, w, wp, G,
+                               PP, PS, S, LG, pstride);
+        } else {
+            hipLaunchKernelGGL(k_affine_unit_pack16<X3>, dim3(C, fn, SP), dim3(256), 0, stream, a.u + o, a.dy + o, a16, z16, a.scale, a.shift, C, h, w,
+                               wp, G, PP, PS, LG, pstride);
+        }
         const dim3 gd(p.NC / p.TN, C / (C >= 128 ? 128 : 64), c.sp);
         if (C >= 128)
             hipLaunchKernelGGL((k_unit_wgrad16<4, 4, 2, X3>), gd, dim3(256), 0, stream, z16, a16, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase,
@@ -375,10 +418,26 @@ int unit_backward16(pp_ctx* ctx, const unit_shape& s, const unit_args& a)
             hipLaunchKernelGGL((k_unit_dgrad16<2, X3>), dim3(pp_div_up(PP, 128), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
         else
             hipLaunchKernelGGL((k_unit_dgrad16<4, X3>), dim3(pp_div_up(PP, 64), 1, fn), dim3(256), 0, stream, ws->wT16, zT, duc, C, h, w, wp, G, PP, PS, pstride);
-        hipLaunchKernelGGL(k_plane_gstats_u, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->stm, duc, ws->pst, C, N, L, S);
-        hipLaunchKernelGGL(k_unit_norm_u, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->stm, ws->pst, a.dskip ? a.dskip + o : nullptr, duc, C, N, L, S);
+        if (form == NORM_INSTANCE) {
+            hipLaunchKernelGGL(k_plane_gstats_u, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->stm, duc, ws->pst, C, N, L, S);
+            hipLaunchKernelGGL(k_unit_norm_u, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ws->stm, ws->pst, a.dskip ? a.dskip + o : nullptr, duc, C, N, L,
+                               S);
+        } else if (form == NORM_AFFINE) {
+            hipLaunchKernelGGL(k_affine_unit_du<true>, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, (const float*)nullptr, a.scale, a.shift,
+                               a.dskip ? a.dskip + o : nullptr, duc, ws->pst + (size_t)c.f0 * C * S * 2, C, w, 0, 0, 0, N, L, S);
+        } else {
+            hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
+                               C, N, L, S);
+        }
     });
     launch_dw_reduce(ws->part, p.Gp, p.nw, a.dw, stream);
+    if (form == NORM_AFFINE && a.dscale)
+        hipLaunchKernelGGL(k_affine_reduce, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, a.dscale, a.dshift);
+    if (form == NORM_BATCH && a.du) {
+        hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(C, 64)), dim3(64), 0, stream, ws->pst, nb, C, S, a.mean, a.var, (double)nb * (double)N, ws->stm,
+                           a.dscale, a.dshift);
+        hipLaunchKernelGGL(k_bn_unit_du, dim3(C, nb, S), dim3(256), 0, stream, a.u, a.scale, a.shift, ws->stm, a.dskip, a.du, C, N, L);
+    }
     PP_HIP(hipGetLastError());
     return 0;
 }
@@ -390,6 +449,19 @@ int unit_path(int mode, int C, int h, int w)
     return frame16_bytes(mode == 1 ? 2 : 1, C, planes16(h, w)) <= WS_BUDGET ? mode : 0;
 }
 
+const char* const MODE_MSG = ": mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)";
+
+// One _affine_mp / _bn_mp call in mode 1 or 2: the shape first (it decides the path); a shape no 16-bit tiling takes returns -1 and the
+// caller runs its fp32 sibling; then the tensors, then the twin
+int unit_entry16(pp_ctx* ctx, const char* entry, norm_form form, int mode, const unit_shape& s, const unit_args& a)
+{
+    if (int rc = unit_check(ctx, entry, UNIT_CHK_SHAPE, form, s, a)) return rc;
+    const int path = unit_path(mode, s.C, s.h, s.w);
+    if (path == 0) return -1;
+    if (int rc = unit_check(ctx, entry, UNIT_CHK_TENSORS, form, s, a)) return rc;
+    return path == 1 ? unit_backward16<true>(ctx, form, s, a) : unit_backward16<false>(ctx, form, s, a);
+}
+
 } // namespace
 
 extern "C" int pp_unit_backward_path(pp_ctx* ctx, int mode, int C, int h, int w)
@@ -397,6 +469,16 @@ extern "C" int pp_unit_backward_path(pp_ctx* ctx, int mode, int C, int h, int w)
     if (!ctx) return -PP_E_ARG; // the modes are 0 .. 2, so an error is the negated code
     if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, "pp_unit_backward_path: mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
     if (int rc = unit_check(ctx, "pp_unit_backward", UNIT_CHK_SHAPE, NORM_INSTANCE, unit_shape{C, h, w}, unit_args())) return -rc;
+    return unit_path(mode, C, h, w);
+}
+
+// the same answer for pp_unit_backward_affine_mp and pp_unit_backward_bn_mp (the path depends on shape and mode, not on the form), on a
+// context of either norm kind
+extern "C" int pp_unit_backward_bn_path(pp_ctx* ctx, int mode, int C, int h, int w)
+{
+    if (!ctx) return -PP_E_ARG;
+    if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, (std::string("pp_unit_backward_bn_path") + MODE_MSG).c_str());
+    if (int rc = unit_check(ctx, "pp_unit_backward_bn_path", UNIT_CHK_SHAPE, NORM_AFFINE, unit_shape{C, h, w}, unit_args())) return -rc;
     return unit_path(mode, C, h, w);
 }
 
@@ -413,5 +495,39 @@ extern "C" int pp_unit_backward_mp(pp_ctx* ctx, int mode, int C, int h, int w, c
     const int path = unit_path(mode, C, h, w);
     if (path == 0) return pp_unit_backward(ctx, C, h, w, u, wgt, dy, dskip, nb, dw, du, stream_);
     if (int rc = unit_check(ctx, "pp_unit_backward", UNIT_CHK_TENSORS, NORM_INSTANCE, s, a)) return rc;
-    return path == 1 ? unit_backward16<true>(ctx, s, a) : unit_backward16<false>(ctx, s, a);
+    return path == 1 ? unit_backward16<true>(ctx, NORM_INSTANCE, s, a) : unit_backward16<false>(ctx, NORM_INSTANCE, s, a);
+}
+
+// pp_unit_backward_affine with the two products in 16-bit operands: mode 0, and a shape whose images exceed the budget, is that entry
+extern "C" int pp_unit_backward_affine_mp(pp_ctx* ctx, int mode, int C, int h, int w, const float* u, const float* wgt, const float* scale,
+                                          const float* shift, const float* dy, const float* dskip, int nb, float* dw, float* du, double* dscale,
+                                          double* dshift, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, (std::string("pp_unit_backward_affine_mp") + MODE_MSG).c_str());
+    if (mode) {
+        unit_args a;
+        a.u = u; a.wgt = wgt; a.scale = scale; a.shift = shift; a.dy = dy; a.dskip = dskip; a.nb = nb; a.dw = dw; a.du = du;
+        a.dscale = dscale; a.dshift = dshift; a.stream = (hipStream_t)stream_;
+        const int rc = unit_entry16(ctx, "pp_unit_backward_affine_mp", NORM_AFFINE, mode, unit_shape{C, h, w}, a);
+        if (rc >= 0) return rc;
+    }
+    return pp_unit_backward_affine(ctx, C, h, w, u, wgt, scale, shift, dy, dskip, nb, dw, du, dscale, dshift, stream_);
+}
+
+// pp_unit_backward_bn likewise.  The two phases are that entry's; chunk_frames caps the frames of a chunk of 16-bit images
+extern "C" int pp_unit_backward_bn_mp(pp_ctx* ctx, int mode, int C, int h, int w, const float* u, const float* wgt, const float* scale,
+                                      const float* shift, const float* mean, const float* var, const float* dy, const float* dskip, int nb,
+                                      float* dw, float* du, double* dscale, double* dshift, int chunk_frames, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, (std::string("pp_unit_backward_bn_mp") + MODE_MSG).c_str());
+    if (mode) {
+        unit_args a;
+        a.u = u; a.wgt = wgt; a.scale = scale; a.shift = shift; a.mean = mean; a.var = var; a.dy = dy; a.dskip = dskip; a.nb = nb; a.dw = dw;
+        a.du = du; a.dscale = dscale; a.dshift = dshift; a.chunk_frames = chunk_frames; a.stream = (hipStream_t)stream_;
+        const int rc = unit_entry16(ctx, "pp_unit_backward_bn_mp", NORM_BATCH, mode, unit_shape{C, h, w}, a);
+        if (rc >= 0) return rc;
+    }
+    return pp_unit_backward_bn(ctx, C, h, w, u, wgt, scale, shift, mean, var, dy, dskip, nb, dw, du, dscale, dshift, chunk_frames, stream_);
 }

@@ -14,6 +14,9 @@
 // So the workspace is pp_down_backward's plus the small wT16, the budgets and frame chunks are its own, and every shape the fp32 entry
 // takes runs in the mode asked for (a frame past the 256 MB budget is refused by both).
 //
+// pp_down_backward_affine_mp / pp_down_backward_bn_mp are the same products behind the dz plane of the BatchNorm forms (k_affine_down_dz,
+// k_bn_down_dz): mask, dz and the two fp64 sums are the fp32 path's bits in every mode.
+//
 // Determinism as in down_train.hip: no atomics, K ranges, segments and chunks are functions of the shapes alone.
 #include <cmath>
 #include "pp_common.h"
@@ -264,3 +267,55 @@ extern "C" int pp_down_backward_mp(pp_ctx* ctx, int mode, int cin, int cout, int
     return mode == 1 ? down_run<down_bf16<true>>(ctx, NORM_INSTANCE, s, a) : down_run<down_bf16<false>>(ctx, NORM_INSTANCE, s, a);
 }
 
+namespace {
+
+// One _affine_mp / _bn_mp call in mode 1 or 2: the shape first, then the tensors, under `form`'s rules; down_run<down_bf16<X3>> is the whole
+// driver: the policies read the plan, the fp32 dz plane and the parity planes of x, whichever pass of the form wrote dz
+int down_entry16(pp_ctx* ctx, const char* entry, norm_form form, int mode, const down_shape& s, const down_args& a)
+{
+    int rc;
+    if ((rc = down_check(ctx, entry, DOWN_CHK_SHAPE, form, s, a)) || (rc = down_check(ctx, entry, DOWN_CHK_TENSORS, form, s, a))) return rc;
+    return mode == 1 ? down_run<down_bf16<true>>(ctx, form, s, a) : down_run<down_bf16<false>>(ctx, form, s, a);
+}
+
+const char* const DOWN_MODE_MSG = ": mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)";
+
+} // namespace
+
+// The mode pp_down_backward_affine_mp and pp_down_backward_bn_mp run for this shape: `mode`, on a context of either norm kind
+extern "C" int pp_down_backward_bn_path(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win)
+{
+    if (!ctx) return -PP_E_ARG;
+    if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, (std::string("pp_down_backward_bn_path") + DOWN_MODE_MSG).c_str());
+    if (int rc = down_check(ctx, "pp_down_backward_bn_path", DOWN_CHK_SHAPE, NORM_AFFINE, down_shape{cin, cout, hin, win}, down_args())) return -rc;
+    return mode;
+}
+
+// pp_down_backward_affine / pp_down_backward_bn with the two products in 16-bit operands.  k_affine_down_dz, k_bn_down_sums, k_bn_coef and
+// k_bn_down_dz are the fp32 path's own passes, so the mask, dz, dscale and dshift are its bits in every mode; mode 0 is the fp32 entry.
+extern "C" int pp_down_backward_affine_mp(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win, const float* x, const float* wgt,
+                                          const float* z, const float* scale, const float* shift, const float* dy, int nb, float* dw, float* dx,
+                                          double* dscale, double* dshift, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, (std::string("pp_down_backward_affine_mp") + DOWN_MODE_MSG).c_str());
+    if (mode == 0) return pp_down_backward_affine(ctx, cin, cout, hin, win, x, wgt, z, scale, shift, dy, nb, dw, dx, dscale, dshift, stream_);
+    down_args a;
+    a.x = x; a.wgt = wgt; a.z = z; a.scale = scale; a.shift = shift; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.stream = (hipStream_t)stream_;
+    return down_entry16(ctx, "pp_down_backward_affine_mp", NORM_AFFINE, mode, down_shape{cin, cout, hin, win}, a);
+}
+
+extern "C" int pp_down_backward_bn_mp(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win, const float* x, const float* wgt, const float* z,
+                                      const float* scale, const float* shift, const float* mean, const float* var, const float* dy, int nb,
+                                      float* dw, float* dx, double* dscale, double* dshift, int chunk_frames, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, (std::string("pp_down_backward_bn_mp") + DOWN_MODE_MSG).c_str());
+    if (mode == 0)
+        return pp_down_backward_bn(ctx, cin, cout, hin, win, x, wgt, z, scale, shift, mean, var, dy, nb, dw, dx, dscale, dshift, chunk_frames, stream_);
+    down_args a;
+    a.x = x; a.wgt = wgt; a.z = z; a.scale = scale; a.shift = shift; a.mean = mean; a.var = var; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.chunk_frames = chunk_frames; a.stream = (hipStream_t)stream_;
+    return down_entry16(ctx, "pp_down_backward_bn_mp", NORM_BATCH, mode, down_shape{cin, cout, hin, win}, a);
+}

@@ -13,6 +13,8 @@
 // entry takes runs in the mode asked for.
 //
 // Determinism as in neck_train.hip: no atomics, K ranges and chunks are functions of the shapes alone.
+// pp_neck_backward_affine_mp / pp_neck_backward_bn_mp are the same products behind the dZ of the BatchNorm forms (k_affine_neck_dz,
+// k_bn_neck_dz): mask, dZ and the two fp64 sums are the fp32 path's bits in every mode.
 #include <cmath>
 #include "pp_common.h"
 #include "neck_train.h"
@@ -227,4 +229,57 @@ extern "C" int pp_neck_backward_mp(pp_ctx* ctx, int mode, int branch, const floa
         (rc = neck_check(ctx, "pp_neck_backward_mp", NECK_CHK_TENSORS, NORM_INSTANCE, branch, a)))
         return rc;
     return mode == 1 ? neck_run<neck_bf16<true>>(ctx, NORM_INSTANCE, branch, a) : neck_run<neck_bf16<false>>(ctx, NORM_INSTANCE, branch, a);
+}
+
+namespace {
+
+// One _affine_mp / _bn_mp call in mode 1 or 2: the branch and the context first, then the tensors, under `form`'s rules;
+// neck_run<neck_bf16<X3>> is the whole driver: the policies read the plan, x, w and the fp32 dZ, whichever pass of the form wrote it
+int neck_entry16(pp_ctx* ctx, const char* entry, norm_form form, int mode, int branch, const neck_args& a)
+{
+    int rc;
+    if ((rc = neck_check(ctx, entry, NECK_CHK_SHAPE, form, branch, a)) || (rc = neck_check(ctx, entry, NECK_CHK_TENSORS, form, branch, a))) return rc;
+    return mode == 1 ? neck_run<neck_bf16<true>>(ctx, form, branch, a) : neck_run<neck_bf16<false>>(ctx, form, branch, a);
+}
+
+const char* const NECK_MODE_MSG = ": mode must be 0 (fp32), 1 (bf16x3) or 2 (bf16)";
+
+} // namespace
+
+// The mode pp_neck_backward_affine_mp and pp_neck_backward_bn_mp run for this branch: `mode`, on a context of either norm kind
+extern "C" int pp_neck_backward_bn_path(pp_ctx* ctx, int mode, int branch)
+{
+    if (!ctx) return -PP_E_ARG;
+    if (mode < 0 || mode > 2) return -pp_fail(ctx, PP_E_ARG, (std::string("pp_neck_backward_bn_path") + NECK_MODE_MSG).c_str());
+    if (int rc = neck_check(ctx, "pp_neck_backward_bn_path", NECK_CHK_SHAPE, NORM_AFFINE, branch, neck_args())) return -rc;
+    return mode;
+}
+
+// pp_neck_backward_affine / pp_neck_backward_bn with the dw and dx products in 16-bit operands.  Z, k_affine_neck_dz, k_bn_neck_sums,
+// k_bn_coef and k_bn_neck_dz are the fp32 path's own passes, so the mask, dZ, dscale and dshift are its bits in every mode; mode 0 is the
+// fp32 entry.
+extern "C" int pp_neck_backward_affine_mp(pp_ctx* ctx, int mode, int branch, const float* x, const float* wt, const float* scale, const float* shift,
+                                          const float* y, const float* dy, int nb, float* dw, float* dx, double* dscale, double* dshift,
+                                          void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, (std::string("pp_neck_backward_affine_mp") + NECK_MODE_MSG).c_str());
+    if (mode == 0) return pp_neck_backward_affine(ctx, branch, x, wt, scale, shift, y, dy, nb, dw, dx, dscale, dshift, stream_);
+    neck_args a;
+    a.x = x; a.wt = wt; a.scale = scale; a.shift = shift; a.y = y; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.stream = (hipStream_t)stream_;
+    return neck_entry16(ctx, "pp_neck_backward_affine_mp", NORM_AFFINE, mode, branch, a);
+}
+
+extern "C" int pp_neck_backward_bn_mp(pp_ctx* ctx, int mode, int branch, const float* x, const float* wt, const float* scale, const float* shift,
+                                      const float* mean, const float* var, const float* y, const float* dy, int nb, float* dw, float* dx,
+                                      double* dscale, double* dshift, int chunk_frames, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (mode < 0 || mode > 2) return pp_fail(ctx, PP_E_ARG, (std::string("pp_neck_backward_bn_mp") + NECK_MODE_MSG).c_str());
+    if (mode == 0) return pp_neck_backward_bn(ctx, branch, x, wt, scale, shift, mean, var, y, dy, nb, dw, dx, dscale, dshift, chunk_frames, stream_);
+    neck_args a;
+    a.x = x; a.wt = wt; a.scale = scale; a.shift = shift; a.mean = mean; a.var = var; a.y = y; a.dy = dy; a.nb = nb; a.dw = dw; a.dx = dx;
+    a.dscale = dscale; a.dshift = dshift; a.chunk_frames = chunk_frames; a.stream = (hipStream_t)stream_;
+    return neck_entry16(ctx, "pp_neck_backward_bn_mp", NORM_BATCH, mode, branch, a);
 }

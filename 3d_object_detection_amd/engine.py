@@ -481,55 +481,68 @@ class Engine:
     # The three families' backwards (neck_backward, unit_backward, down_backward) come in three norm forms, chosen by norm=:
     # InstanceNorm (None; grad_precision picks the mode of pp_*_backward_mp and the method returns (dw, dx)), a frozen BatchNorm (a
     # BackwardNorm without statistics: pp_*_backward_affine) and a train-mode BatchNorm (one with mean and var: pp_*_backward_bn);
-    # the BatchNorm forms are fp32 and return (dw, dx, dscale, dshift).  The *_affine / *_bn methods are the same calls with the
-    # record's fields as arguments.  `who` is the method the form goes by, for messages.
-    def _backward_path(self, entry, grad_precision, *ints):
-        """One pp_*_backward_path entry: the precision that family's backward really runs at these shapes."""
+    # the BatchNorm forms return (dw, dx, dscale, dshift) and take bn_grad_precision in its place: "fp32" calls the fp32 entries, "bf16x3" /
+    # "bf16" their _mp forms (pp_*_backward_affine_mp / _bn_mp).  The *_affine / *_bn methods are the same calls with the record's fields as
+    # arguments.  `who` is the method the form goes by, for messages.
+    def _backward_path(self, entry, grad_precision, *ints, bn=False):
+        """One pp_*_backward_path entry: the precision that family's backward really runs at these shapes.  bn=True: the query of the
+        BatchNorm forms (pp_*_backward_bn_path: the _affine_mp and _bn_mp entries, a context of either norm kind)."""
+        entry = entry.replace("_path", "_bn_path") if bn else entry
         mode = self._grad_mode(grad_precision, entry[3:])
         rc = getattr(self.lib, entry)(self.ctx, mode, *ints)
         if rc < 0:
             _lib.check(-rc, self.ctx, entry)
         return {v: k for k, v in self.GRAD_PRECISIONS.items()}[rc]
 
-    def _backward_form(self, name, norm, grad_precision):
-        """-> (who, the mode argument that leads an InstanceNorm entry's list: none for the BatchNorm forms, which are fp32)."""
+    def _backward_form(self, name, norm, grad_precision, bn_grad_precision):
+        """-> (who, the mode argument that leads the entry's list).  InstanceNorm: always a mode, grad_precision's (pp_*_backward_mp).
+        BatchNorm: grad_precision stays "fp32" and bn_grad_precision picks: no mode under "fp32" (the fp32 entries pp_*_backward_affine /
+        _bn themselves), the mode of their _mp forms under "bf16x3" / "bf16"."""
         if norm is None:
+            if bn_grad_precision != "fp32":
+                raise ValueError(f"{name}: bn_grad_precision goes with norm=; without a norm the keyword is grad_precision")
             return name, [self._grad_mode(grad_precision, name)]
         who = name + ("_affine" if norm.mean is None else "_bn")
         if grad_precision != "fp32":
-            raise ValueError(f"{who}: the BatchNorm backward is fp32 (grad_precision='fp32'), got {grad_precision!r}")
-        return who, []
+            raise ValueError(f"{who}: with a norm grad_precision stays 'fp32' and bn_grad_precision picks the operand precision, got "
+                             f"grad_precision={grad_precision!r}")
+        if bn_grad_precision not in self.GRAD_PRECISIONS:
+            raise ValueError(f"{who}: bn_grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {bn_grad_precision!r}")
+        mode = self.GRAD_PRECISIONS[bn_grad_precision]
+        return who, [mode] if mode else []
 
-    def _norm_args(self, who, C, norm):
-        """The norm form of a backward over C normalised channels -> (the entry's suffix, the norm's tensors, the arguments behind the
-        outputs, the affine sums the caller gets back: () for InstanceNorm)."""
+    def _norm_args(self, who, C, norm, mode):
+        """The norm form of a backward over C normalised channels, mode as _backward_form gives it -> (the entry's suffix, the norm's
+        tensors, the arguments behind the outputs, the affine sums the caller gets back: () for InstanceNorm)."""
         if norm is None:
             return "_mp", [], [], ()
+        mp = "_mp" if mode else ""
         scale = _chk(norm.scale, torch.float32, (C,), f"{who}: scale")
         shift = _chk(norm.shift, torch.float32, (C,), f"{who}: shift")
         self._on_device(who, ((scale, "scale"), (shift, "shift")))
         sums = (self._t((C,), torch.float64), self._t((C,), torch.float64)) if norm.need_affine else (None, None)
         if norm.mean is None:
-            return "_affine", [scale, shift], list(sums), sums
+            return "_affine" + mp, [scale, shift], list(sums), sums
         mean = _chk(norm.mean, torch.float32, (C,), f"{who}: mean")
         var = _chk(norm.var, torch.float32, (C,), f"{who}: var")
         self._on_device(who, ((mean, "mean"), (var, "var")))
         if not isinstance(norm.chunk_frames, int) or norm.chunk_frames < 0:
             raise ValueError(f"{who}: chunk_frames must be an int >= 0, got {norm.chunk_frames!r}")
-        return "_bn", [scale, shift, mean, var], [*sums, norm.chunk_frames], sums
+        return "_bn" + mp, [scale, shift, mean, var], [*sums, norm.chunk_frames], sums
 
     def _call_backward(self, entry, *args):
         """One training backward of the library on the current stream; tensors (or None) go as pointers, ints as they are."""
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, entry)(self.ctx, *[_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args], _stream()), self.ctx, entry)
 
-    def neck_backward(self, branch, x, w, y, dy, need_dx=True, grad_precision="fp32", norm=None):
+    def neck_backward(self, branch, x, w, y, dy, need_dx=True, grad_precision="fp32", norm=None, bn_grad_precision="fp32"):
         """pp_neck_backward_mp: branch 0..2, the block output x [nb,Cin,h,w], the upsampler weight w [Cin,Cup,s,s], rpn_out y and
         dL/d(rpn_out) dy [nb,320,H,W] -> (dw [Cin,Cup,s,s] summed over the frames, dx [nb,Cin,h,w] or None when need_dx is False).
         Deterministic, stateless.  grad_precision: "fp32" (pp_neck_backward, bit for bit), "bf16x3" or "bf16": the operands of the dw
         and dx products in split or plain bf16 on the bf16 MFMA, everything else (Z, statistics, mask, dZ, tensors) fp32.
-        norm: a BackwardNorm for the branch behind a BatchNorm2d (neck_backward_affine / neck_backward_bn) -> (dw, dx, dscale, dshift)."""
-        who, mode = self._backward_form("neck_backward", norm, grad_precision)
+        norm: a BackwardNorm for the branch behind a BatchNorm2d (neck_backward_affine / neck_backward_bn) -> (dw, dx, dscale, dshift);
+        with it bn_grad_precision picks the mode (pp_neck_backward_affine_mp / _bn_mp) and grad_precision stays "fp32"."""
+        who, mode = self._backward_form("neck_backward", norm, grad_precision, bn_grad_precision)
         if branch not in (0, 1, 2):
             raise ValueError(who + f": branch must be 0, 1 or 2, got {branch!r}")
         xs, wsh = self.neck_shapes(branch)
@@ -541,7 +554,7 @@ class Engine:
         y = _chk(y, torch.float32, (nb, 320, self.H, self.W), who + ": y")
         dy = _chk(dy, torch.float32, (nb, 320, self.H, self.W), who + ": dy")
         self._on_device(who, ((x, "x"), (w, "w"), (y, "y"), (dy, "dy")))
-        suffix, norm, tail, sums = self._norm_args(who, wsh[1], norm)
+        suffix, norm, tail, sums = self._norm_args(who, wsh[1], norm, mode)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the kernels read w with 16-byte loads
         dw = self._t(wsh, torch.float32)
@@ -549,11 +562,12 @@ class Engine:
         self._call_backward("pp_neck_backward" + suffix, *mode, branch, x, w, *norm, y, dy, nb, dw, dx, *tail)
         return (dw, dx, *sums)
 
-    def neck_backward_path(self, grad_precision, branch):
-        """pp_neck_backward_path: the precision neck_backward(grad_precision=...) really runs for this branch."""
+    def neck_backward_path(self, grad_precision, branch, bn=False):
+        """pp_neck_backward_path: the precision neck_backward(grad_precision=...) really runs for this branch (bn=True: with a norm,
+        pp_neck_backward_bn_path)."""
         if grad_precision in self.GRAD_PRECISIONS and branch not in (0, 1, 2):  # a grad_precision that is not one is reported first
             raise ValueError(f"neck_backward_path: branch must be 0, 1 or 2, got {branch!r}")
-        return self._backward_path("pp_neck_backward_path", grad_precision, int(branch))
+        return self._backward_path("pp_neck_backward_path", grad_precision, int(branch), bn=bn)
 
     def update_neck_weights(self, params):
         """pp_update_neck_weights: {state_dict name: device tensor} of rpn.deconv{1,2,3}.0.weight -> the committed upsampler images, in
@@ -574,19 +588,20 @@ class Engine:
             raise ValueError(f"{who}: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         return cls.GRAD_PRECISIONS[grad_precision]
 
-    def unit_backward_path(self, grad_precision, C, h, w):
+    def unit_backward_path(self, grad_precision, C, h, w, bn=False):
         """pp_unit_backward_path: the precision unit_backward(grad_precision=...) really runs at this shape: grad_precision, or "fp32"
-        where no 16-bit tiling takes the shape."""
-        return self._backward_path("pp_unit_backward_path", grad_precision, int(C), int(h), int(w))
+        where no 16-bit tiling takes the shape (bn=True: with a norm, pp_unit_backward_bn_path)."""
+        return self._backward_path("pp_unit_backward_path", grad_precision, int(C), int(h), int(w), bn=bn)
 
-    def unit_backward(self, u, w, dy, dskip=None, need_du=True, grad_precision="fp32", norm=None):
+    def unit_backward(self, u, w, dy, dskip=None, need_du=True, grad_precision="fp32", norm=None, bn_grad_precision="fp32"):
         """pp_unit_backward_mp: backward of InstanceNorm -> ReLU -> Conv3x3(C -> C, pad 1) for C = 64 | 128 | 256.  u (the unit's input),
         dy (dL/d(conv output)) and the optional dskip (added to du: the residual path around the unit) are [nb,C,h,w], w [C,C,3,3] ->
         (dw [C,C,3,3] summed over the frames, du [nb,C,h,w] or None when need_du is False).  Deterministic, stateless.  grad_precision:
         "fp32" (pp_unit_backward, bit for bit), "bf16x3" or "bf16": the operands of the two gradient products in split or plain bf16 on
         the bf16 MFMA, everything else (tensors, statistics, mask, norm backward) fp32.
-        norm: a BackwardNorm for the unit behind a BatchNorm2d (unit_backward_affine / unit_backward_bn) -> (dw, du, dscale, dshift)."""
-        who, mode = self._backward_form("unit_backward", norm, grad_precision)
+        norm: a BackwardNorm for the unit behind a BatchNorm2d (unit_backward_affine / unit_backward_bn) -> (dw, du, dscale, dshift);
+        with it bn_grad_precision picks the mode (pp_unit_backward_affine_mp / _bn_mp) and grad_precision stays "fp32"."""
+        who, mode = self._backward_form("unit_backward", norm, grad_precision, bn_grad_precision)
         if not (isinstance(u, torch.Tensor) and u.dim() == 4 and 1 <= int(u.shape[0]) <= self.max_batch):
             raise ValueError(who + f": u must be [nb,C,h,w] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, C, h, wd = (int(v) for v in u.shape)
@@ -602,7 +617,7 @@ class Engine:
         if dskip is not None:
             dskip = _chk(dskip, torch.float32, (nb, C, h, wd), who + ": dskip")
         self._on_device(who, ((u, "u"), (w, "w"), (dy, "dy"), (dskip, "dskip")))
-        suffix, norm, tail, sums = self._norm_args(who, C, norm)
+        suffix, norm, tail, sums = self._norm_args(who, C, norm, mode)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((C, C, 3, 3), torch.float32)
@@ -632,19 +647,21 @@ class Engine:
     DOWN_KEYS = ("rpn.block1.0.weight", "rpn.block2.0.weight", "rpn.block3.0.weight")
     DOWN_PAIRS = ((64, 64), (64, 128), (128, 256))
 
-    def down_backward_path(self, grad_precision, cin, cout, hin, win):
-        """pp_down_backward_path: the precision down_backward(grad_precision=...) really runs at this shape."""
-        return self._backward_path("pp_down_backward_path", grad_precision, int(cin), int(cout), int(hin), int(win))
+    def down_backward_path(self, grad_precision, cin, cout, hin, win, bn=False):
+        """pp_down_backward_path: the precision down_backward(grad_precision=...) really runs at this shape (bn=True: with a norm,
+        pp_down_backward_bn_path)."""
+        return self._backward_path("pp_down_backward_path", grad_precision, int(cin), int(cout), int(hin), int(win), bn=bn)
 
-    def down_backward(self, x, w, z, dy, need_dx=True, grad_precision="fp32", norm=None):
+    def down_backward(self, x, w, z, dy, need_dx=True, grad_precision="fp32", norm=None, bn_grad_precision="fp32"):
         """pp_down_backward_mp: backward of Conv3x3(Cin -> Cout, stride 2, pad 1) -> InstanceNorm -> ReLU for (Cin, Cout) = (64, 64) |
         (64, 128) | (128, 256).  x [nb,Cin,Hin,Win] (the stage's raw input), w [Cout,Cin,3,3], z (the conv output) and dy (dL/d(stage
         output)) [nb,Cout,(Hin+1)//2,(Win+1)//2] -> (dw [Cout,Cin,3,3] summed over the frames, dx [nb,Cin,Hin,Win] or None when
         need_dx is False).  Deterministic, stateless.  grad_precision: "fp32" (pp_down_backward, bit for bit), "bf16x3" or "bf16": the
         operands of the wgrad and dgrad products in split or plain bf16 on the bf16 MFMA, everything else (planes, statistics, mask,
         norm backward, tensors) fp32.
-        norm: a BackwardNorm for the stage with a BatchNorm2d (down_backward_affine / down_backward_bn) -> (dw, dx, dscale, dshift)."""
-        who, mode = self._backward_form("down_backward", norm, grad_precision)
+        norm: a BackwardNorm for the stage with a BatchNorm2d (down_backward_affine / down_backward_bn) -> (dw, dx, dscale, dshift);
+        with it bn_grad_precision picks the mode (pp_down_backward_affine_mp / _bn_mp) and grad_precision stays "fp32"."""
+        who, mode = self._backward_form("down_backward", norm, grad_precision, bn_grad_precision)
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and 1 <= int(x.shape[0]) <= self.max_batch):
             raise ValueError(who + f": x must be [nb,Cin,Hin,Win] with 1 <= nb <= max_batch ({self.max_batch})")
         nb, cin, hin, win = (int(v) for v in x.shape)
@@ -659,7 +676,7 @@ class Engine:
         z = _chk(z, torch.float32, (nb, cout, ho, wo), who + ": z")
         dy = _chk(dy, torch.float32, (nb, cout, ho, wo), who + ": dy")
         self._on_device(who, ((x, "x"), (w, "w"), (z, "z"), (dy, "dy")))
-        suffix, norm, tail, sums = self._norm_args(who, cout, norm)
+        suffix, norm, tail, sums = self._norm_args(who, cout, norm, mode)
         if w.data_ptr() % 16:
             w = w.clone()  # a view into a larger tensor: the library wants w 16-byte aligned
         dw = self._t((cout, cin, 3, 3), torch.float32)

@@ -41,7 +41,9 @@ pp_*_backward_bn; the moved running statistics are folded again before the next 
 Mixed precision (grad_stages="rpn" extends it to the strided stages and the upsamplers, pp_down_backward_mp / pp_neck_backward_mp):
 train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of every Resnet unit backward with split
 or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
-backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit."""
+backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit.  On a BatchNorm network train(..., bn_stats=...,
+bn_grad_precision="bf16x3" | "bf16") does the same for the BatchNorm backwards (pp_*_backward_affine_mp / pp_*_backward_bn_mp), again
+for the units alone or, under grad_stages="rpn", the stages and upsamplers too."""
 import time
 import types
 import typing
@@ -161,12 +163,13 @@ class _Layer(typing.NamedTuple):
 
 def _layer_backward(eng, primitive, layer, *args, prec=None, **kw):
     """One backward primitive of the engine (neck_backward, unit_backward, down_backward) for `layer` -> ((dw, dgamma, dbeta), dx),
-    each gradient None unless its tensor requires grad.  InstanceNorm: prec, when given, goes in as grad_precision.  BatchNorm: the
-    layer's norm goes in, and its dgamma / dbeta come from the primitive's two fp64 sums (pp_bn_affine_grad)."""
+    each gradient None unless its tensor requires grad.  prec, when given, goes in as grad_precision (InstanceNorm) or as
+    bn_grad_precision (BatchNorm).  BatchNorm: the layer's norm goes in, and its dgamma / dbeta come from the primitive's two fp64 sums
+    (pp_bn_affine_grad)."""
     if layer.norm is None:
         dw, dx = primitive(*args, **kw, **({} if prec is None else {"grad_precision": prec}))
         return (dw if layer.need_w else None, None, None), dx
-    dw, dx, dscale, dshift = primitive(*args, **kw, norm=layer.norm)
+    dw, dx, dscale, dshift = primitive(*args, **kw, norm=layer.norm, **({} if prec is None else {"bn_grad_precision": prec}))
     dg, db = eng.bn_affine_grad(dscale, dshift, *layer.stats) if layer.norm.need_affine else (None, None)
     return (dw if layer.need_w else None, dg if layer.need_gb[0] else None, db if layer.need_gb[1] else None), dx
 
@@ -179,7 +182,9 @@ def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32", n
     The first unit runs its dgrad when something in front needs the gradient or its own norm trains: a unit's affine sums are sums
     over its dgrad product."""
     layers = layers or [_Layer(w, True) for w in weights]
-    unit = lambda i, g, **kw: _layer_backward(eng, eng.unit_backward, layers[i], units[i], layers[i].w, g, prec=grad_precision, **kw)  # noqa: E731
+    # a unit with a norm gets the keyword only in a 16-bit mode: fp32 runs make the calls they always made
+    prec = lambda layer: None if layer.norm is not None and grad_precision == "fp32" else grad_precision  # noqa: E731
+    unit = lambda i, g, **kw: _layer_backward(eng, eng.unit_backward, layers[i], units[i], layers[i].w, g, prec=prec(layers[i]), **kw)  # noqa: E731
     grads = [None] * len(units)
     i = len(units)
     for n in reversed(modules):
@@ -305,10 +310,17 @@ class _RpnBnFunction(torch.autograd.Function):
     (weight, gamma, beta) of RPN_CONV_KEYS[first:] and then of the three upsamplers, stats (running_mean, running_var) of the same
     layers, which get no gradient.  The folded (scale, shift) of every layer are evaluated once in the forward by the kernel that
     wrote the engine's own (pp_bn_fold), so the backward reads the values the forward used.  A layer's dgamma / dbeta come from the
-    two fp64 sums of its primitive (pp_bn_affine_grad)."""
+    two fp64 sums of its primitive (pp_bn_affine_grad).  prec, _RpnFunction's pair (units, stages), may follow the tensors as the last
+    argument (train(bn_grad_precision=...)); without it the walk is fp32 and makes the calls it always made."""
+
+    @staticmethod
+    def _split_prec(tensors):
+        """tensors, possibly followed by the pair prec -> (tensors, prec or None)."""
+        return (tensors[:-1], tensors[-1]) if tensors and isinstance(tensors[-1], tuple) else (tensors, None)
 
     @staticmethod
     def forward(ctx, eng, first, stats, x, *tensors):
+        tensors, ctx.prec = _RpnBnFunction._split_prec(tensors)
         ctx.eng, ctx.first, ctx.stats, ctx.batch = eng, first, stats, False
         n = len(tensors) // 3
         folds = [eng.bn_fold(tensors[3 * i + 1], tensors[3 * i + 2], *stats[i]) for i in range(n)]
@@ -328,19 +340,21 @@ class _RpnBnFunction(torch.autograd.Function):
             need_gb = tuple(need[5 + 3 * i:7 + 3 * i])
             norm = BackwardNorm(own[n + 2 * i], own[n + 2 * i + 1], *(ctx.stats[i] if ctx.batch else ()), need_affine=any(need_gb))
             layers.append(_Layer(own[i], need[4 + 3 * i], norm, ctx.stats[i], need_gb))
-        g, grads = _rpn_backward(ctx.eng, ctx.first, saved, layers, gy, need[3])
-        return (None, None, None, g) + tuple(t for layer in grads for t in layer)
+        g, grads = _rpn_backward(ctx.eng, ctx.first, saved, layers, gy, need[3], ctx.prec or ("fp32", "fp32"))
+        return (None, None, None, g) + tuple(t for layer in grads for t in layer) + ((None,) if ctx.prec else ())
 
 
 class _RpnBnBatchFunction(torch.autograd.Function):
     """_RpnBnFunction with batch statistics (train-mode BatchNorm2d): the forward is one lock-step pass over all frames,
     pp_backbone_train_taps_bn, which hands out every layer's batch mean, biased variance and their fold with the layer's weight and
     bias; the backward is _RpnBnFunction's walk with the pp_*_backward_bn primitives.  bn_params holds weight and bias of all nineteen
-    layers (the layers in front of `first` normalise with batch statistics too); tensors as in _RpnBnFunction.  Returns the rpn output
+    layers (the layers in front of `first` normalise with batch statistics too); tensors (and the optional prec behind them) as in
+    _RpnBnFunction.  Returns the rpn output
     and the statistics mean, var f32[19,256] in Engine.bn_layers() order (not differentiable: the caller moves the running ones)."""
 
     @staticmethod
     def forward(ctx, eng, first, bn_params, x, *tensors):
+        tensors, ctx.prec = _RpnBnFunction._split_prec(tensors)
         nconv = len(RPN_CONV_KEYS)
         taps = True if first == 0 else False if first == nconv else 2
         y, xs, units, zs, mean, var, scale, shift = eng.backbone_train_taps_bn(x, bn_params, taps=taps)
@@ -394,6 +408,7 @@ class PointPillars:
     _norm = "instance"
     grad_precision = "fp32"
     grad_stages = "units"
+    bn_grad_precision = "fp32"  # train(bn_grad_precision=...) while training a BatchNorm network
     bn_stats = None  # train(bn_stats=...) while training a BatchNorm network
     # read-only defaults for an object assembled without __init__ (no engine: the key-order and plan tests); __init__ and
     # load_state_dict give every object its own
@@ -431,7 +446,7 @@ class PointPillars:
     def eval(self):
         return self.train(False)
 
-    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None, grad_stages="units"):
+    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None, grad_stages="units", bn_grad_precision="fp32"):
         """Training mode: forward() accepts a batch of several frames and the tensors of `scope` require grad (SCOPES, from "head",
         the six head parameters, to "all", everything net.parameters() yields in the reference: the module docstring lists them);
         everything in front of the scope stays frozen.  Under "all" the PFN normalises with batch statistics and moves its running
@@ -441,7 +456,11 @@ class PointPillars:
         the gradient products of the backwards that grad_stages names (kept as net.grad_stages, "units" again after eval()): "units",
         the Resnet units alone (pp_unit_backward_mp), or "rpn", the three strided stages (pp_down_backward_mp) and the three
         upsamplers (pp_neck_backward_mp) as well, wherever the scope runs them.  The forward, the head backward, the PFN and every
-        tensor handed around stay fp32.  InstanceNorm backbone only: the BatchNorm backward is fp32.
+        tensor handed around stay fp32.  InstanceNorm backbone only: on a BatchNorm network the keyword is bn_grad_precision.
+        bn_grad_precision ("fp32" | "bf16x3" | "bf16", BatchNorm networks under bn_stats only, kept as net.bn_grad_precision, "fp32"
+        again after eval()): the same for the BatchNorm backwards (pp_*_backward_affine_mp under "frozen", pp_*_backward_bn_mp under
+        "moving"), for the backwards grad_stages names; net.grad_precision stays "fp32" on these networks, and "fp32", the default, is
+        the fp32 walk bit for bit.
         bn_stats (BatchNorm networks only, kept as net.bn_stats; None keeps such a network to scope="head") governs the nineteen
         BatchNorm2d layers of the RPN; a layer's weight / bias train with the convolution whose backward primitive yields their
         gradient (a unit's leading norm with that unit's convolution, blockN.1 with the strided convolution, deconvN.1 with the
@@ -459,6 +478,12 @@ class PointPillars:
             raise ValueError(f"train: grad_stages must be 'units' or 'rpn', got {grad_stages!r}")
         if scope not in SCOPES:
             raise ValueError(f"train: scope must be 'head', 'neck', 'block3', 'stage3', 'rpn' or 'all', got {scope!r}")
+        if bn_grad_precision not in GRAD_PRECISIONS:
+            raise ValueError(f"train: bn_grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {bn_grad_precision!r}")
+        if bn_grad_precision != "fp32" and self._norm != "batch":
+            raise ValueError("train: bn_grad_precision is for the BatchNorm networks; on the InstanceNorm backbone the keyword is grad_precision")
+        if bn_grad_precision != "fp32" and bn_stats is None:
+            raise ValueError("train: bn_grad_precision needs bn_stats ('frozen' or 'moving'): without it a BatchNorm network trains its head alone")
         if bn_stats is not None:
             if bn_stats not in BN_STATS:
                 raise ValueError(f"train: bn_stats must be None, 'frozen' or 'moving', got {bn_stats!r}")
@@ -468,7 +493,8 @@ class PointPillars:
                 raise NotImplementedError("train(bn_stats='batch'): training with batch statistics is bn_stats='moving' (the running "
                                           "statistics move, as under torch's net.train()); bn_stats='frozen' fine-tunes with them fixed")
             if grad_precision != "fp32":
-                raise ValueError("train: the BatchNorm backward is fp32 (grad_precision='fp32')")
+                raise ValueError("train: on a BatchNorm network grad_precision stays 'fp32'; bn_grad_precision picks the operand precision "
+                                 "of the BatchNorm backwards")
         if mode and scope != "head" and ((self._norm != "instance" and bn_stats not in ("frozen", "moving")) or (scope == "all" and len(self._pfn_stats) != 2) or
                                          any(len(getattr(self, g.attr)) != len(self._group_keys(g)) for g in self._groups(scope) if g.scope != "head")):
             raise RuntimeError(f"train(scope='{scope}'): the neck and block backward exist for the InstanceNorm backbone only" +
@@ -477,6 +503,7 @@ class PointPillars:
         self._scope = scope if self.training else "head"
         self.grad_precision = grad_precision if self.training else "fp32"
         self.grad_stages = grad_stages if self.training else "units"
+        self.bn_grad_precision = bn_grad_precision if self.training else "fp32"
         self.bn_stats = bn_stats if self.training else None
         trained = self._groups(self._scope) if self.training else ()
         for g in _GROUPS.values():
@@ -774,6 +801,8 @@ class PointPillars:
             every.update(self._neck)
             layers = RPN_CONV_KEYS[first:] + NECK_KEYS
             tensors = [every[n] for k in layers for n in (k, *bn_affine_keys(k))]
+            if self.bn_grad_precision != "fp32":  # the pair (units, stages) rides behind the tensors; an fp32 run makes the calls it made
+                tensors.append((self.bn_grad_precision, self.bn_grad_precision if self.grad_stages == "rpn" else "fp32"))
             if moving:
                 return self._rpn_train_moving(first, x, tensors)
             stats = [tuple(self._bn_run[f"{Engine.bn_prefix(k)}.{s}"] for s in Engine.BN_FIELDS[2:]) for k in layers]

@@ -571,6 +571,50 @@ int pp_neck_backward_bn(pp_ctx* ctx, int branch, const float* x, const float* w,
                         const float* var, const float* y, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */,
                         double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames, void* stream);
 
+/* ---- mixed-precision training of the BatchNorm networks (block_train16.hip, down_train16.hip, neck_train16.hip) ----
+ * The six _affine / _bn entries above with `int mode` behind the context, numbered as pp_unit_backward_mp numbers it: 0 fp32 (a call of
+ * the fp32 sibling, bit for bit), 1 bf16x3, 2 bf16; any other mode is PP_E_ARG under the entry's name.  Modes 1 and 2 run only the two
+ * gradient products of the call on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, with the operand images, tiles and K ranges of the
+ * InstanceNorm _mp entries; every tensor in and out, the ReLU mask, the dw partial reduction in double, the fp64 per-channel sums,
+ * their reduction (affine) or pooling into c1, c2 (batch) and chunk_frames stay as they are.
+ *   Stage and branch: the products read the fp32 dz / dZ that the form's own fp32 pass writes, so the mask, dz and the two sums (dscale,
+ *   dshift) are the fp32 entry's bits in every mode; only dw and dx move, within the bounds of pp_down_backward_mp / pp_neck_backward_mp.
+ *   Unit: a = max(fma(u, scale_c, shift_c), 0) is evaluated in fp32 and rounded (bf16) or split (bf16x3) into the 16-bit image, dy
+ *   likewise; no fp32 image of a is kept, and the pass behind the dgrad takes its mask from fma(u, scale_c, shift_c) > 0 re-evaluated
+ *   from u, which is the fp32 path's mask bit for bit (fma rounds once and keeps the sign).  dscale / dshift are sums over the dgrad
+ *   product, so they move with du, within the bound of the form's own expressions.  A shape whose 16-bit images of one frame exceed
+ *   256 MB runs the fp32 kernels (pp_unit_backward_bn_path tells).  A chunk of frames holds fewer frames than under fp32 (bf16x3: 8 against
+ *   12 at level 0); the batch form's second phase reads u and du alone, so du and the sums do not depend on the chunks.
+ * Stateless, either norm kind, no atomics; K ranges, segments and chunks are functions of shape, mode and chunk_frames alone, two runs are
+ * bit-identical; under the affine form a frame's du / dx depends on neither nb nor the chunks; under the batch form du / dx and the sums
+ * do not depend on the chunking, dw does within its bound.  PP_E_ARG as the fp32 siblings.
+ * pp_{unit,down,neck}_backward_bn_path: the mode the _affine_mp and the _bn_mp entry really run at this shape (the path depends on shape
+ * and mode, not on the form), on a context of either norm kind; launches nothing; an error is the negated code, as pp_unit_backward_path.
+ * The stage and branch queries return `mode`; the unit query returns 0 where the images exceed the budget. */
+int pp_unit_backward_affine_mp(pp_ctx* ctx, int mode, int C, int h, int w, const float* u, const float* wgt, const float* scale,
+                               const float* shift, const float* dy, const float* dskip /* may be NULL */, int nb, float* dw,
+                               float* du /* NULL: skipped */, double* dscale /* may be NULL */, double* dshift /* may be NULL */, void* stream);
+int pp_unit_backward_bn_mp(pp_ctx* ctx, int mode, int C, int h, int w, const float* u, const float* wgt, const float* scale, const float* shift,
+                           const float* mean, const float* var, const float* dy, const float* dskip /* may be NULL */, int nb, float* dw,
+                           float* du /* NULL: skipped */, double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames,
+                           void* stream);
+int pp_down_backward_affine_mp(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z,
+                               const float* scale, const float* shift, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */,
+                               double* dscale /* may be NULL */, double* dshift /* may be NULL */, void* stream);
+int pp_down_backward_bn_mp(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win, const float* x, const float* w, const float* z,
+                           const float* scale, const float* shift, const float* mean, const float* var, const float* dy, int nb, float* dw,
+                           float* dx /* NULL: skipped */, double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames,
+                           void* stream);
+int pp_neck_backward_affine_mp(pp_ctx* ctx, int mode, int branch, const float* x, const float* w, const float* scale, const float* shift,
+                               const float* y, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */,
+                               double* dscale /* may be NULL */, double* dshift /* may be NULL */, void* stream);
+int pp_neck_backward_bn_mp(pp_ctx* ctx, int mode, int branch, const float* x, const float* w, const float* scale, const float* shift,
+                           const float* mean, const float* var, const float* y, const float* dy, int nb, float* dw, float* dx /* NULL: skipped */,
+                           double* dscale /* may be NULL */, double* dshift /* may be NULL */, int chunk_frames, void* stream);
+int pp_unit_backward_bn_path(pp_ctx* ctx, int mode, int C, int h, int w);
+int pp_down_backward_bn_path(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win);
+int pp_neck_backward_bn_path(pp_ctx* ctx, int mode, int branch);
+
 /* ---- training the pillar feature net: PointNet in train mode, its backward and the scatter's (pfn_train.hip) ----
  * PointNet.forward (pointpillars8_shared.py:30-60) with BatchNorm1d normalising by BATCH statistics.  Notation: f[p][t][0:9] the nine
  * decorated features of slot t of pillar p (x, y, z, r, x - mx, y - my, z - mz, x - cx, y - cy; arithmetic as pp_pfn: mean over all T
