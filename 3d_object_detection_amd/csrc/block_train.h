@@ -1,6 +1,7 @@
 // The Resnet unit backward's own part of the training host side, shared by block_train.hip (fp32) and block_train16.hip (its 16-bit
 // operand twins): the workspace of a context and its budget rules, the one check and plan of the family, and the passes behind the
-// dgrad of the two BatchNorm forms (k_affine_unit_du, k_bn_unit_sums, k_bn_unit_du), which read u and du only.  The fp32 driver
+// dgrad of the two BatchNorm forms (k_affine_unit_du, k_bn_unit_du; the batch form's sums are train_conv3.h's k_bn_plane_sums), which
+// read u and du only.  The fp32 driver
 // (unit_run) is block_train.hip's; the twin keeps a driver of its own (its pack, its InstanceNorm kernels and images differ) over the
 // same check, plan and chunk walk.  What the three families share (workspace growth, the padded-plane geometry, the frame chunks and K ranges, the
 // reduction of the dw partials) is train_host.h's.
@@ -8,12 +9,12 @@
 #include "pp_common.h"
 #include "train_planes.h"
 #include "train_host.h"
+#include "train_conv3.h"
 
 namespace {
 
 constexpr size_t WS_BUDGET = (size_t)256 << 20; // bytes of one frame's a + dz planes: a larger map is refused
 constexpr size_t WS_CHUNK = (size_t)1 << 30;    // bytes of the planes of one chunk of frames: larger batches run in frame chunks
-constexpr int DA_BLOCK = 64;                    // k-terms that k_unit_dgrad sums in one accumulator before adding the block to the total
 
 struct block_ws {
     float* planes = nullptr; size_t planes_elems = 0; // a [fc][C][PS], then dz [fc][C][PS]
@@ -123,31 +124,9 @@ __global__ void __launch_bounds__(256) k_affine_unit_du(const float* __restrict_
 
 // ---- the unit behind a train-mode BatchNorm (pp_unit_backward_bn): k_affine_unit_pack and the two products as above, the raw da left in
 // du.  The norm backward needs the sums of ALL frames, so it runs behind the frame chunks, on u and du alone: the mask is re-evaluated
-// by the pack's own fma.  k_bn_unit_sums: grid (C, frames, S), g = da [fma(u, scale, shift) > 0], the segment's sum g u, sum g in fp64
-// -> pst[frame][c][segment][2].  k_bn_unit_du: same grid, in place once k_bn_coef has pooled them:
-// du = scale ((g - c1) - xhat c2) (+ dskip), xhat = (u - mean) r ------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_bn_unit_sums(const float* __restrict__ u, const float* __restrict__ du, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, double* __restrict__ pst, int C, int N, int L, int S)
-{
-    __shared__ double red[256][2];
-    const int tid = threadIdx.x;
-    const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    const float* up = u + pl * N;
-    const float* dp = du + pl * N;
-    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
-    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
-    double sgu = 0.0, sg = 0.0;
-    strided4(lo, hi, [&](int i) { return float2{up[i], dp[i]}; },
-             [&](float2 v) {
-                 if (fmaf(v.x, sc, sh) > 0.f) {
-                     const double g = (double)v.y;
-                     sgu += g * (double)v.x; sg += g;
-                 }
-             });
-    block_sum2(sgu, sg, red);
-    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgu; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
-}
-
+// by the pack's own fma.  k_bn_plane_sums (train_conv3.h) takes each chunk's segment sums of g = da [fma(u, scale, shift) > 0].
+// k_bn_unit_du: grid (C, frames, S), in place once k_bn_coef has pooled them: du = scale ((g - c1) - xhat c2) (+ dskip),
+// xhat = (u - mean) r --------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_bn_unit_du(const float* __restrict__ u, const float* __restrict__ scale, const float* __restrict__ shift,
                                                     const float* __restrict__ coef, const float* __restrict__ dskip, float* __restrict__ du, int C,
                                                     int N, int L)

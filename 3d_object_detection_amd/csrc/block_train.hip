@@ -7,13 +7,15 @@
 // in all (G and PS multiples of 4).  In that layout a 3 x 3 tap is a shift of the flat index by off_t = (ky - 1) wp + (kx - 1), every
 // shifted read stays inside the plane, and halo x anything = 0, so both gradient products are plain GEMMs over flat positions P with
 // no branch per tap:
-//   k_unit_wt      wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows
+//   k_conv3_wt     wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows (train_conv3.h)
 //   k_plane_stats  per (frame, c, segment): sum u, sum u^2 in fp64 over one segment of the plane
 //   k_unit_pack    per (frame, c, slice): the segments' sums added in index order, mean / rstd, a and dz into the padded planes (halo and
 //                  guards rewritten)
-//   k_unit_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      M = C, N = 9 C, K = frames x PP, split into ranges
+//   k_conv3_wgrad  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      M = C, N = 9 C, K = frames x PP, split into ranges
+//                  (train_conv3.h's kernel with the stride-1 taps, taps_s1)
 //   k_dw_reduce    partials summed in index order (double, rounded once; train_host.h, shared by the three families)
 //   k_unit_dgrad   da[ci][P] = sum_{t, co} wT[t][co][ci] dz[co][P - off_t]           M = C, N = PP, K = 9 C, summed in blocks of DA_BLOCK
+//                  (each tap by train_conv3.h's conv3_dgrad_tap)
 //   k_plane_gstats per (frame, c, segment): sum Gr, sum Gr xhat in fp64 over one segment of da
 //   k_unit_norm    per (frame, c, segment): the segments' sums added in index order, du = rstd (Gr - mean(Gr) - xhat mean(Gr xhat)) (+ dskip)
 // A plane is cut into plane_segs(elements) segments, a function of the plane size alone (one segment up to 16384 elements, so block 3's
@@ -26,11 +28,12 @@
 // depend on the batch it rides in; dw depends on nb within fp32 summation error (the K ranges do).
 // pp_unit_backward_affine is the same unit with a per-channel affine (a frozen BatchNorm2d) for the norm: k_affine_unit_pack, the two
 // products, k_affine_unit_du and k_affine_reduce; pp_unit_backward itself stays the InstanceNorm backbone's.
-// pp_unit_backward_bn is that unit behind a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_unit_sums behind the
+// pp_unit_backward_bn is that unit behind a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_plane_sums behind the
 // dgrad of every chunk, then k_bn_coef and one in-place k_bn_unit_du over all frames.
 // block_train16.hip holds the 16-bit operand twins of these kernels (pp_unit_backward_mp and the _affine_mp / _bn_mp entries); what both
-// share (the check and the plan of a call, the passes behind the dgrad of the two BatchNorm forms) is in block_train.h, what all three
-// training families share in train_host.h.  The three entries are thin wrappers over unit_check and unit_run.
+// share (the check and the plan of a call, the passes behind the dgrad of the two BatchNorm forms) is in block_train.h, what the unit
+// shares with the strided stage in train_planes.h (the streaming passes) and train_conv3.h (the two products), what all three training
+// families share in train_host.h.  The three entries are thin wrappers over unit_check and unit_run.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -43,111 +46,39 @@ __constant__ double kG4[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {
 __constant__ double kG6[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                  {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
 
-__global__ void __launch_bounds__(256) k_unit_wt(const float* __restrict__ w, float* __restrict__ wT, int C)
+// ---- a + dz: grid (C, frames, SP), one slice of LP elements of the padded planes per workgroup (halo and guards rewritten).
+// unit_pack_plane is the body of both pack kernels: act(u) is the form's a ---------------------------------------------------------------
+template <typename ACT>
+__device__ __forceinline__ void unit_pack_plane(const float* __restrict__ up, const float* __restrict__ dp, float* __restrict__ ao,
+                                                float* __restrict__ zo, int h, int w, int wp, int G, int PP, int PS, int LP, ACT act)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][C][C]
-    if (i >= 9 * C * C) return;
-    const int ci = i % C, co = (i / C) % C, t = i / (C * C);
-    wT[i] = w[((size_t)co * C + ci) * 9 + t];
+    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
+    padded_walk(lo, hi, h, w, wp, G, PP, [&](int j, const plane_pos& p) {
+        float av = 0.f, dv = 0.f;
+        if (p.inside) { av = act(up[p.i]); dv = dp[p.i]; }
+        ao[j] = av; zo[j] = dv;
+    });
 }
 
-// ---- a + dz: grid (C, frames, SP), one slice of LP elements of the padded planes per workgroup ------------------------------------
 __global__ void __launch_bounds__(256) k_unit_pack(const float* __restrict__ u, const float* __restrict__ dy, float* __restrict__ ap,
                                                    float* __restrict__ dzp, float* __restrict__ stm, const double* __restrict__ pst, int C, int h,
                                                    int w, int wp, int G, int PP, int PS, int S, int LP)
 {
-    const int tid = threadIdx.x, N = h * w;
+    const int N = h * w;
     const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    const float* up = u + pl * N;
-    const float* dp = dy + pl * N;
-    double s = 0.0, ss = 0.0;
-    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
-    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
-    double var = ss * inv_n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
-    if (tid == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
-    float* ao = ap + pl * PS;
-    float* zo = dzp + pl * PS;
-    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
-        float av = 0.f, dv = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, x = P - y * wp;
-            if (y >= 1 && y <= h && x >= 1 && x <= w) {
-                const int i = (y - 1) * w + x - 1;
-                const float xhat = (up[i] - meanf) * rstdf;
-                av = xhat > 0.f ? xhat : 0.f;
-                dv = dp[i];
-            }
-        }
-        ao[j] = av; zo[j] = dv;
-    }
-}
-
-// ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
-// 64 x 32 NB (C >= 128: 128 columns).  MA = 4: four waves side by side, every one all 64 co, tile 64 x 64 NB (C = 64: 576 = 3 x 192
-// columns; a wave loads 4 dz rows and 12 a columns for 48 MFMAs where the 2 x 2 form loads 2 and 8 for 16).  K runs over 16-position
-// chunks of the launch's frames (chunk c: frame c / cpf, positions 16 (c % cpf) ..; positions past PP read guard zeros of dz); a lane
-// takes positions 4 q .. 4 q + 3 of the chunk as its four k-steps: one 16-byte load per dz row, four shifted loads per a column.
-// blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z, already in the state_dict layout [co][ci][3][3].
-template <int NB, int MA>
-__global__ void __launch_bounds__(256) k_unit_wgrad(const float* __restrict__ dzp, const float* __restrict__ ap, float* __restrict__ part, int C,
-                                                    int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase)
-{
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
-    static_assert(MA == 2 || MA == 4, "waves 2 x 2 or 1 x 4");
-    constexpr int WC = MA;     // waves across the tile: 2 of 2 x 2, 4 of 1 x 4
-    const int co0 = blockIdx.y * 64 + (MA == 2 ? 32 * (wave >> 1) : 0), n0 = blockIdx.x * (16 * NB * WC) + 16 * NB * (wave & (WC - 1));
-    const int NC = 9 * C;
-    int boff[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int n = n0 + 16 * b + l16, ci = n / 9, t = n - 9 * ci;
-        boff[b] = ci * PS + G + (t / 3 - 1) * wp + (t % 3 - 1);
-    }
-    f32x4 acc[MA][NB];
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
-    for (int c = c0; c < c1; ++c) {
-        const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
-        const float* zf = dzp + (size_t)f * C * PS + G + pb;
-        const float* af = ap + (size_t)f * C * PS + pb;
-        float za[MA][4], ab[NB][4];
-#pragma unroll
-        for (int a = 0; a < MA; ++a) {
-            const float4 v = *reinterpret_cast<const float4*>(zf + (size_t)(co0 + 16 * a + l16) * PS);
-            za[a][0] = v.x; za[a][1] = v.y; za[a][2] = v.z; za[a][3] = v.w;
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) ab[b][s] = af[boff[b] + s];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int a = 0; a < MA; ++a)
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a][s], ab[b][s], acc[a][b], 0, 0, 0);
-    }
-    float* pw = part + (size_t)(gbase + blockIdx.z) * C * NC;
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
+    float meanf, rstdf;
+    plane_mean_rstd(pst, pl, S, N, meanf, rstdf);
+    if (threadIdx.x == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    unit_pack_plane(u + pl * N, dy + pl * N, ap + pl * PS, dzp + pl * PS, h, w, wp, G, PP, PS, LP, [&](float v) {
+        const float xhat = (v - meanf) * rstdf;
+        return xhat > 0.f ? xhat : 0.f;
+    });
 }
 
 // ---- dgrad: a workgroup covers ALL C channels (WM = C / 64 waves down, 4 / WM across), each wave 64 ci x 32 positions, so dz is read
-// once per tap.  K = (t, co) in steps of 4 output channels (lane group q takes co + q).  The sum over K (2304 terms at C = 256) is
-// blocked: each DA_BLOCK terms accumulate from zero and the block sums are then added in (t, co) order, so the rounding error grows
-// with the block length and the block count, not with K.  Positions past PP read a clamped index and are never stored; only interior
-// positions are stored, into the tight [C][h][w] plane of du.
+// once per tap.  K = (t, co): the nine taps in order, each tap's blocked sum over co by conv3_dgrad_tap (2304 terms at C = 256).
+// Positions past PP read a clamped index and are never stored; only interior positions are stored, into the tight [C][h][w] plane of
+// du.
 template <int WM>
 __global__ void __launch_bounds__(256) k_unit_dgrad(const float* __restrict__ wT, const float* __restrict__ dzp, float* __restrict__ da, int C, int h,
                                                     int w, int wp, int G, int PP, int PS)
@@ -166,33 +97,7 @@ __global__ void __launch_bounds__(256) k_unit_dgrad(const float* __restrict__ wT
     const int i0 = P0 < PP ? P0 : 0, i1 = P1 < PP ? P1 : 0;
     for (int t = 0; t < 9; ++t) {
         const int off = (t / 3 - 1) * wp + (t % 3 - 1);
-        const float* wt_t = wT + (size_t)t * C * C + ci0 + l16;
-        for (int cb0 = 0; cb0 < C; cb0 += DA_BLOCK) { // C is a multiple of DA_BLOCK
-            f32x4 acc[4][2];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-            for (int cb = cb0; cb < cb0 + DA_BLOCK; cb += 4) {
-                const int co = cb + q;
-                const float* wr = wt_t + (size_t)co * C;
-                const float* zr = zf + (size_t)co * PS - off;
-                const float z0 = zr[i0], z1 = zr[i1];
-                float wa[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) wa[a] = wr[16 * a];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z0, acc[a][0], 0, 0, 0);
-                    acc[a][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z1, acc[a][1], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) tot[a][b] += acc[a][b];
-        }
+        conv3_dgrad_tap(tot, wT + (size_t)t * C * C + ci0 + l16, zf, -off, i0, i1, q, C, C, PS);
     }
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -259,33 +164,16 @@ __global__ void __launch_bounds__(256) k_unit_norm(const float* __restrict__ u, 
 
 // ---- the unit with a per-channel affine in place of the InstanceNorm (pp_unit_backward_affine): a = max(fma(u, scale, shift), 0), the
 // forward prologue's expression, so there are no statistics passes.  k_affine_unit_pack: grid (C, frames, SP) as k_unit_pack.
-// The passes behind the dgrad (k_affine_unit_du; k_bn_unit_sums, k_bn_unit_du for the batch form) are block_train.h's: the 16-bit twin
-// runs them too ----------------------------------------------------------------------------------------------------------------------------
+// The passes behind the dgrad (k_affine_unit_du; k_bn_plane_sums, k_bn_unit_du for the batch form) are block_train.h's and
+// train_conv3.h's: the 16-bit twin runs them too -------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_affine_unit_pack(const float* __restrict__ u, const float* __restrict__ dy, float* __restrict__ ap,
                                                           float* __restrict__ dzp, const float* __restrict__ scale, const float* __restrict__ shift,
                                                           int C, int h, int w, int wp, int G, int PP, int PS, int LP)
 {
-    const int tid = threadIdx.x, N = h * w;
+    const int N = h * w;
     const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    const float* up = u + pl * N;
-    const float* dp = dy + pl * N;
     const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
-    float* ao = ap + pl * PS;
-    float* zo = dzp + pl * PS;
-    const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
-        float av = 0.f, dv = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, x = P - y * wp;
-            if (y >= 1 && y <= h && x >= 1 && x <= w) {
-                const int i = (y - 1) * w + x - 1;
-                av = affine_relu(up[i], sc, sh);
-                dv = dp[i];
-            }
-        }
-        ao[j] = av; zo[j] = dv;
-    }
+    unit_pack_plane(u + pl * N, dy + pl * N, ap + pl * PS, dzp + pl * PS, h, w, wp, G, PP, PS, LP, [&](float v) { return affine_relu(v, sc, sh); });
 }
 
 // ---- weight update: image element i holds position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T.  U = G g G^T is
@@ -373,7 +261,7 @@ int unit_run(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& 
         return rc;
     float* ap = ws->planes;
     float* dzp = ws->planes + (size_t)fc * p.pf_elems;
-    if (a.du) hipLaunchKernelGGL(k_unit_wt, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, a.wgt, ws->wT, C);
+    if (a.du) hipLaunchKernelGGL(k_conv3_wt, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, a.wgt, ws->wT, C, C);
     for_chunks(p.walk, [&](const dw_chunk& c) {
         const int fn = c.fn;
         const size_t o = (size_t)c.f0 * C * N;
@@ -387,9 +275,11 @@ int unit_run(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& 
         }
         const dim3 gd(p.NC / p.TN, C / 64, c.sp);
         if (C >= 128)
-            hipLaunchKernelGGL((k_unit_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase);
+            hipLaunchKernelGGL((k_conv3_wgrad<4, 2, taps_s1>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, C, wp, G, PS, p.cpf, c.nchunks, c.cps,
+                               c.gbase);
         else
-            hipLaunchKernelGGL((k_unit_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, wp, G, PS, p.cpf, c.nchunks, c.cps, c.gbase);
+            hipLaunchKernelGGL((k_conv3_wgrad<3, 4, taps_s1>), gd, dim3(256), 0, stream, dzp, ap, ws->part, C, C, wp, G, PS, p.cpf, c.nchunks, c.cps,
+                               c.gbase);
         if (!a.du) return;
         float* duc = a.du + o;
         if (C == 64)
@@ -406,7 +296,7 @@ int unit_run(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& 
             hipLaunchKernelGGL(k_affine_unit_du<false>, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, ap, a.scale, a.shift,
                                a.dskip ? a.dskip + o : nullptr, duc, ws->pst + (size_t)c.f0 * C * S * 2, C, w, wp, G, PS, N, L, S);
         } else {
-            hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
+            hipLaunchKernelGGL(k_bn_plane_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
                                C, N, L, S);
         }
     });

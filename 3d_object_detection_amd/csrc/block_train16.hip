@@ -3,9 +3,10 @@
 // row / column.  Only the GEMM operand streams are bf16; statistics, mask, norm backward, the dw reduction and every input and output
 // stay fp32.  bf16 (X3 = false) rounds every operand once (round to nearest even); bf16x3 (X3 = true) keeps x = hi + lo, hi = bf16(x),
 // lo = bf16(fl32(x - hi)), as two images and issues hi hi, hi lo, lo hi into the same accumulator in that order.
-//   k_unit_wt16     wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the dgrad's A operand, 8 consecutive co per lane
+//   k_conv3_wt16    wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the dgrad's A operand, 8 consecutive co per lane (train16.h)
 //   k_plane_stats   as in block_train.hip (train_planes.h)
-//   k_unit_pack16   mean / rstd by k_unit_pack's expressions; a and dz into padded bf16 planes, 8 positions per thread
+//   k_unit_pack16   mean / rstd by plane_mean_rstd (train_planes.h) as in k_unit_pack; a and dz into padded bf16 planes, 8 positions per
+//                   thread
 //   k_affine_unit_pack16  the same planes for the BatchNorm forms: a by the affine, no statistics
 //   k_unit_packT16  zT[P][co]: dz once more with the channel innermost, the dgrad's B operand
 //   k_unit_wgrad16  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] a[ci][P + off_t]      K = frames x PP16 in chunks of 32 positions
@@ -26,7 +27,7 @@
 // The two BatchNorm forms (pp_unit_backward_affine_mp, pp_unit_backward_bn_mp) run the same products behind k_affine_unit_pack16, which has
 // k_unit_pack16's grid and layout and no statistics: a = max(fma(u, scale, shift), 0) in fp32 by k_affine_unit_pack's expression, then
 // rounded or split.  Behind the dgrad they run block_train.h's passes, which read u and du only: k_affine_unit_du<true> (the mask
-// fma(u, scale, shift) > 0 re-evaluated from u: the fp32 path's mask bit for bit) and k_affine_reduce for the affine form; k_bn_unit_sums
+// fma(u, scale, shift) > 0 re-evaluated from u: the fp32 path's mask bit for bit) and k_affine_reduce for the affine form; k_bn_plane_sums
 // per chunk, then k_bn_coef and one in-place k_bn_unit_du over all frames for the batch form, whatever frames the 16-bit chunks held.
 //
 // Determinism as in block_train.hip: no atomics, K ranges, segments and chunks are functions of the shapes (and the mode) alone.
@@ -38,21 +39,11 @@
 
 namespace {
 
-// wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]
-template <bool X3>
-__global__ void __launch_bounds__(256) k_unit_wt16(const float* __restrict__ w, uint16_t* __restrict__ wT, int C)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][C][C]
-    if (i >= 9 * C * C) return;
-    const int co = i % C, ci = (i / C) % C, t = i / (C * C);
-    const float v = w[((size_t)co * C + ci) * 9 + t];
-    wT[i] = (uint16_t)pk_bf16(v, 0.f);
-    if (X3) wT[(size_t)9 * C * C + i] = (uint16_t)pk_bf16(bf16_rest(v), 0.f);
-}
-
 // ---- a and dz: grid (C, frames, SP), a thread takes groups of 8 positions (one row: wp and G are multiples of 8).  pack16_plane is the
 // body of both pack kernels: act(u) is the form's a in fp32, rounded (bf16) or split (bf16x3) behind it, dz likewise; halo and guards are
-// rewritten with zeros.  a16, z16: [part][frame][C][PS]; pstride = the elements of one part ------------------------------------------------
+// rewritten with zeros.  It keeps a walk of its own: a group of 8 tests its row once and its columns one by one, which padded_walk
+// (train_planes.h, one element at a time) does not give without a second path.  a16, z16: [part][frame][C][PS]; pstride = the elements of
+// one part ----------------------------------------------------------------------------------------------------------------------------------
 template <bool X3, typename ACT>
 __device__ __forceinline__ void pack16_plane(const float* __restrict__ up, const float* __restrict__ dp, uint16_t* __restrict__ a16,
                                              uint16_t* __restrict__ z16, size_t pl, int h, int w, int wp, int G, int PP, int PS, int LG, size_t pstride,
@@ -89,21 +80,17 @@ __device__ __forceinline__ void pack16_plane(const float* __restrict__ up, const
     }
 }
 
-// InstanceNorm: mean and rstd by k_unit_pack's expressions, so the mask is fp32's
+// InstanceNorm: mean and rstd by plane_mean_rstd as in k_unit_pack, so the mask is fp32's
 template <bool X3>
 __global__ void __launch_bounds__(256) k_unit_pack16(const float* __restrict__ u, const float* __restrict__ dy, uint16_t* __restrict__ a16,
                                                      uint16_t* __restrict__ z16, float* __restrict__ stm, const double* __restrict__ pst, int C, int h,
                                                      int w, int wp, int G, int PP, int PS, int S, int LG, size_t pstride)
 {
-    const int tid = threadIdx.x, N = h * w;
+    const int N = h * w;
     const size_t pl = (size_t)blockIdx.y * C + blockIdx.x;
-    double s = 0.0, ss = 0.0;
-    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
-    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
-    double var = ss * inv_n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const float meanf = (float)mean, rstdf = (float)(1.0 / sqrt(var + 1e-3));
-    if (tid == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
+    float meanf, rstdf;
+    plane_mean_rstd(pst, pl, S, N, meanf, rstdf);
+    if (threadIdx.x == 0 && blockIdx.z == 0) { stm[pl * 2] = meanf; stm[pl * 2 + 1] = rstdf; }
     pack16_plane<X3>(u + pl * N, dy + pl * N, a16, z16, pl, h, w, wp, G, PP, PS, LG, pstride, [&](float v) {
         const float xhat = (v - meanf) * rstdf;
         return xhat > 0.f ? xhat : 0.f;
@@ -362,7 +349,7 @@ inline uint64_t frame16_bytes(int parts, int C, const pad_geom& g) { return (uin
 // BatchNorm forms are the family's; the packs, the InstanceNorm kernels and the images are its own.  The forms differ as in unit_run:
 // InstanceNorm runs the statistics and k_unit_pack16 ahead of the products and its two norm passes behind the dgrad; the affine form
 // k_affine_unit_pack16 and k_affine_unit_du<true> per chunk, k_affine_reduce behind the chunks; the batch form the affine pack and
-// k_bn_unit_sums per chunk (raw da -> du), and behind the chunks k_bn_coef and one in-place k_bn_unit_du over all frames.  Those passes
+// k_bn_plane_sums per chunk (raw da -> du), and behind the chunks k_bn_coef and one in-place k_bn_unit_du over all frames.  Those passes
 // read u and du alone, so the batch form does not care that a 16-bit chunk holds other frames than an fp32 one.
 template <bool X3>
 int unit_backward16(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit_args& a)
@@ -390,7 +377,7 @@ int unit_backward16(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit
     uint16_t* a16 = ws->img16;                       // [part][fc][C][PS]
     uint16_t* z16 = a16 + parts * pstride;           // [part][fc][C][PS]
     uint16_t* zT = z16 + parts * pstride;            // [part][fc][PS][C]
-    if (a.du) hipLaunchKernelGGL(k_unit_wt16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, a.wgt, ws->wT16, C);
+    if (a.du) hipLaunchKernelGGL(k_conv3_wt16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, a.wgt, ws->wT16, C, C);
     for_chunks(p.walk, [&](const dw_chunk& c) {
         const int fn = c.fn;
         const size_t o = (size_t)c.f0 * C * N;
@@ -426,7 +413,7 @@ int unit_backward16(pp_ctx* ctx, norm_form form, const unit_shape& s, const unit
             hipLaunchKernelGGL(k_affine_unit_du<true>, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, (const float*)nullptr, a.scale, a.shift,
                                a.dskip ? a.dskip + o : nullptr, duc, ws->pst + (size_t)c.f0 * C * S * 2, C, w, 0, 0, 0, N, L, S);
         } else {
-            hipLaunchKernelGGL(k_bn_unit_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
+            hipLaunchKernelGGL(k_bn_plane_sums, dim3(C, fn, S), dim3(256), 0, stream, a.u + o, duc, a.scale, a.shift, ws->pst + (size_t)c.f0 * C * S * 2,
                                C, N, L, S);
         }
     });

@@ -1,19 +1,20 @@
 // The strided-stage backward's own part of the training host side, shared by down_train.hip (fp32) and down_train16.hip (its 16-bit
 // operand twin): the workspace of a context and its budget rules, the parity planes of x, the norm backward of every form (InstanceNorm,
 // a frozen BatchNorm's affine, a train-mode BatchNorm) that writes dz into its padded plane, fp32 / fp64 in every mode, and the one
-// check, plan and driver of the family.  What the three families share (workspace growth, the padded-plane geometry, the frame chunks
-// and K ranges, the reduction of the dw partials) is train_host.h's.
+// check, plan and driver of the family.  What the stage shares with the Resnet unit is train_planes.h's (the walk over the padded plane,
+// mean / rstd) and train_conv3.h's (the fp32 products, DA_BLOCK, k_bn_plane_sums); what the three families share (workspace growth, the
+// padded-plane geometry, the frame chunks and K ranges, the reduction of the dw partials) is train_host.h's.
 #pragma once
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
 #include "train_host.h"
+#include "train_conv3.h"
 
 namespace {
 
 constexpr size_t DOWN_WS_BUDGET = (size_t)256 << 20; // bytes of one frame's x parity planes + dz planes: a larger map is refused
 constexpr size_t DOWN_WS_CHUNK = (size_t)1 << 30;    // bytes of the planes of one chunk of frames: larger batches run in frame chunks
-constexpr int DA_BLOCK = 64;                         // k-terms that k_down_dgrad sums in one accumulator before adding the block to the total
 
 struct down_ws {
     float* planes = nullptr; size_t planes_elems = 0; // xp [fc][Cin][4][PS], then dz [fc][Cout][PS]
@@ -33,34 +34,19 @@ __global__ void __launch_bounds__(256) k_down_xpack(const float* __restrict__ x,
     const float* xi = x + pl * hin * win;
     float* xo = xp + pl * 4 * PS;
     const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    for (int j = lo + threadIdx.x; j < hi; j += 256) {
-        const int P = j - G;
+    padded_walk(lo, hi, ho, wo, wp, G, PP, [&](int j, const plane_pos& p) {
         float v00 = 0.f, v01 = 0.f, v10 = 0.f, v11 = 0.f; // (row parity, column parity)
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, c = P - y * wp;
-            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int iy = 2 * (y - 1), ix = 2 * (c - 1); // in the image: 2 (ho - 1) < hin, 2 (wo - 1) < win
-                const float* r = xi + (size_t)iy * win + ix;
-                const bool right = ix + 1 < win, below = iy + 1 < hin;
-                v00 = r[0];
-                if (right) v01 = r[1];
-                if (below) v10 = r[win];
-                if (right && below) v11 = r[win + 1];
-            }
+        if (p.inside) {
+            const int iy = 2 * p.r, ix = 2 * p.c; // in the image: 2 (ho - 1) < hin, 2 (wo - 1) < win
+            const float* r = xi + (size_t)iy * win + ix;
+            const bool right = ix + 1 < win, below = iy + 1 < hin;
+            v00 = r[0];
+            if (right) v01 = r[1];
+            if (below) v10 = r[win];
+            if (right && below) v11 = r[win + 1];
         }
         xo[j] = v00; xo[PS + j] = v01; xo[2 * PS + j] = v10; xo[3 * PS + j] = v11;
-    }
-}
-
-// mean and rstd of a plane as the forward rounds them, from its segment sums added in index order
-__device__ __forceinline__ void plane_mean_rstd(const double* __restrict__ pst, size_t pl, int S, int N, float& meanf, float& rstdf)
-{
-    double s = 0.0, ss = 0.0;
-    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
-    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
-    double var = ss * inv_n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    meanf = (float)mean; rstdf = (float)(1.0 / sqrt(var + 1e-3));
+    });
 }
 
 // ---- sums of the norm backward: grid (Cout, frames, S), sum Gr and sum Gr xhat of one segment -> pst2.  xhat is evaluated by one
@@ -94,7 +80,7 @@ __global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, 
                                                    const double* __restrict__ pst, const double* __restrict__ pst2, int cout, int ho, int wo, int wp,
                                                    int G, int PP, int PS, int S, int LP)
 {
-    const int tid = threadIdx.x, N = ho * wo;
+    const int N = ho * wo;
     const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
     const float* zi = z + pl * N;
     const float* dp = dy + pl * N;
@@ -106,20 +92,16 @@ __global__ void __launch_bounds__(256) k_down_norm(const float* __restrict__ z, 
     const float c1 = (float)(sg * inv_n), c2 = (float)(sgx * inv_n);
     float* zo = dzp + pl * PS;
     const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
+    padded_walk(lo, hi, ho, wo, wp, G, PP, [&](int j, const plane_pos& p) {
         float v = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, c = P - y * wp;
-            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int i = (y - 1) * wo + c - 1;
-                const float xhat = (zi[i] - meanf) * rstdf;
-                const float g = xhat > 0.f ? dp[i] : 0.f;
-                v = rstdf * ((g - c1) - xhat * c2);
-            }
+        if (p.inside) {
+            const int i = p.i;
+            const float xhat = (zi[i] - meanf) * rstdf;
+            const float g = xhat > 0.f ? dp[i] : 0.f;
+            v = rstdf * ((g - c1) - xhat * c2);
         }
         zo[j] = v;
-    }
+    });
 }
 
 // ---- the stage with a per-channel affine in place of the InstanceNorm (pp_down_backward_affine), z, dy -> dz in the padded plane: grid
@@ -138,56 +120,30 @@ __global__ void __launch_bounds__(256) k_affine_down_dz(const float* __restrict_
     float* zo = dzp + pl * PS;
     const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
     double sgz = 0.0, sg = 0.0;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
+    padded_walk(lo, hi, ho, wo, wp, G, PP, [&](int j, const plane_pos& p) {
         float v = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, c = P - y * wp;
-            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int i = (y - 1) * wo + c - 1;
-                const float zz = zi[i];
-                const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
-                sgz += (double)g * (double)zz; sg += (double)g;
-                v = sc * g;
-            }
+        if (p.inside) {
+            const int i = p.i;
+            const float zz = zi[i];
+            const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
+            sgz += (double)g * (double)zz; sg += (double)g;
+            v = sc * g;
         }
         zo[j] = v;
-    }
+    });
     block_sum2(sgz, sg, red);
     if (tid == 0) { pst[(pl * SP + blockIdx.z) * 2] = sgz; pst[(pl * SP + blockIdx.z) * 2 + 1] = sg; }
 }
 
 // ---- the stage in front of a train-mode BatchNorm (pp_down_backward_bn).  The norm backward needs the sums of ALL frames, and they need
-// only z and dy, so they come first, over every frame at once.  k_bn_down_sums: grid (Cout, frames, S) over the tight plane, g = dy
-// [fma(z, scale, shift) > 0], the segment's sum g z, sum g in fp64 -> pst[frame][co][segment][2].  k_bn_down_dz: grid (Cout, frames, SP) as
-// k_down_norm once k_bn_coef has pooled them: dz = scale ((g - c1) - zhat c2), zhat = (z - mean) r, into the padded plane -------------------
-__global__ void __launch_bounds__(256) k_bn_down_sums(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, double* __restrict__ pst, int cout, int N, int L, int S)
-{
-    __shared__ double red[256][2];
-    const int tid = threadIdx.x;
-    const size_t pl = (size_t)blockIdx.y * cout + blockIdx.x;
-    const float* zi = z + pl * N;
-    const float* dp = dy + pl * N;
-    const float sc = scale[blockIdx.x], sh = shift[blockIdx.x];
-    const int lo = blockIdx.z * L, hi = lo + L < N ? lo + L : N;
-    double sgz = 0.0, sg = 0.0;
-    strided4(lo, hi, [&](int i) { return float2{zi[i], dp[i]}; },
-             [&](float2 v) {
-                 if (fmaf(v.x, sc, sh) > 0.f) {
-                     const double g = (double)v.y;
-                     sgz += g * (double)v.x; sg += g;
-                 }
-             });
-    block_sum2(sgz, sg, red);
-    if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = sgz; pst[(pl * S + blockIdx.z) * 2 + 1] = sg; }
-}
-
+// only z and dy, so they come first, over every frame at once: k_bn_plane_sums (train_conv3.h), the segment sums of g = dy
+// [fma(z, scale, shift) > 0].  k_bn_down_dz: grid (Cout, frames, SP) as k_down_norm once k_bn_coef has pooled them:
+// dz = scale ((g - c1) - zhat c2), zhat = (z - mean) r, into the padded plane -----------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_bn_down_dz(const float* __restrict__ z, const float* __restrict__ dy, const float* __restrict__ scale,
                                                     const float* __restrict__ shift, const float* __restrict__ coef, float* __restrict__ dzp, int cout,
                                                     int ho, int wo, int wp, int G, int PP, int PS, int LP)
 {
-    const int tid = threadIdx.x, N = ho * wo, co = blockIdx.x;
+    const int N = ho * wo, co = blockIdx.x;
     const size_t pl = (size_t)blockIdx.y * cout + co;
     const float* zi = z + pl * N;
     const float* dp = dy + pl * N;
@@ -195,21 +151,17 @@ __global__ void __launch_bounds__(256) k_bn_down_dz(const float* __restrict__ z,
     const float c1 = coef[4 * co], c2 = coef[4 * co + 1], meanf = coef[4 * co + 2], rf = coef[4 * co + 3];
     float* zo = dzp + pl * PS;
     const int lo = blockIdx.z * LP, hi = lo + LP < PS ? lo + LP : PS;
-    for (int j = lo + tid; j < hi; j += 256) {
-        const int P = j - G;
+    padded_walk(lo, hi, ho, wo, wp, G, PP, [&](int j, const plane_pos& p) {
         float v = 0.f;
-        if (P >= 0 && P < PP) {
-            const int y = P / wp, c = P - y * wp;
-            if (y >= 1 && y <= ho && c >= 1 && c <= wo) {
-                const int i = (y - 1) * wo + c - 1;
-                const float zz = zi[i];
-                const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
-                const float zhat = (zz - meanf) * rf;
-                v = sc * ((g - c1) - zhat * c2);
-            }
+        if (p.inside) {
+            const int i = p.i;
+            const float zz = zi[i];
+            const float g = fmaf(zz, sc, sh) > 0.f ? dp[i] : 0.f;
+            const float zhat = (zz - meanf) * rf;
+            v = sc * ((g - c1) - zhat * c2);
         }
         zo[j] = v;
-    }
+    });
 }
 
 inline down_ws* workspace(pp_ctx* ctx)
@@ -287,7 +239,7 @@ inline down_plan down_make_plan(const pp_ctx* ctx, const down_shape& s, int nb, 
     p.g = padded_plane(p.ho, p.wo);
     p.pf_elems = (size_t)(4 * s.cin + s.cout) * p.g.PS;
     p.fc = pp_chunk_frames(ctx, DOWN_WS_CHUNK, p.pf_elems * sizeof(float), nb, chunk_frames);
-    p.TN = s.cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_down_wgrad{,16}<4, 2> or <3, 4>
+    p.TN = s.cin >= 128 ? 128 : 192; // columns of a wgrad tile: k_conv3_wgrad / k_down_wgrad16 <4, 2> or <3, 4>
     p.NC = 9 * s.cin; p.cpf = (p.g.PP + kpos - 1) / kpos; p.nw = s.cout * p.NC;
     p.walk = dw_walk{nb, p.fc, (p.NC / p.TN) * (s.cout / 64), p.cpf, wgs};
     p.Gp = count_partials(p.walk);
@@ -322,7 +274,7 @@ int down_run(pp_ctx* ctx, norm_form form, const down_shape& s, const down_args& 
     float* dzp = ws->planes + (size_t)fc * cin * 4 * PS;
     if (a.dx) P::pack_wt(p, ws, a.wgt, stream);
     if (form == NORM_BATCH) {
-        hipLaunchKernelGGL(k_bn_down_sums, dim3(cout, nb, S), dim3(256), 0, stream, a.z, a.dy, a.scale, a.shift, ws->pst, cout, No, L, S);
+        hipLaunchKernelGGL(k_bn_plane_sums, dim3(cout, nb, S), dim3(256), 0, stream, a.z, a.dy, a.scale, a.shift, ws->pst, cout, No, L, S);
         hipLaunchKernelGGL(k_bn_coef, dim3(pp_div_up(cout, 64)), dim3(64), 0, stream, ws->pst, nb, cout, S, a.mean, a.var, (double)nb * (double)No,
                            ws->coef, a.dscale, a.dshift);
     }

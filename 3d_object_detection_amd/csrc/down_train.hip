@@ -8,7 +8,7 @@
 // block_train.hip at half resolution: the (ho + 2) x wp zero-haloed image, wp = wo + 2, PP = (ho + 2) wp elements, between two guard
 // bands of G >= wp + 17 zeros, PS elements in all (G and PS multiples of 4).  Tap t = (ky, kx) is then plane (ky != 1, kx != 1) shifted
 // by the flat offset off_t = -(ky == 0) wp - (kx == 0), every shifted read stays inside the plane, and halo x anything = 0:
-//   k_down_wt      wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows
+//   k_conv3_wt     wT[t][co][ci] = w[co][ci][t]: the dgrad's A operand, contiguous along its rows (train_conv3.h)
 //   k_down_xpack   per (frame, ci, slice): the four parity planes of x (halo and guards rewritten), x read once
 //   k_plane_stats  per (frame, co, segment): sum z, sum z^2 in fp64 over one segment of the plane (train_planes.h)
 //   k_dplane_gstats  per (frame, co, segment): mean / rstd as the forward rounds them from the segments' sums added in index order,
@@ -17,11 +17,13 @@
 //                  into the padded plane
 // A plane is cut into plane_segs(elements) segments, a function of the plane size alone (train_planes.h, shared with block_train.hip: one segment up to 16384
 // elements: block 3's 100 x 100 output planes run as one workgroup each, level 0's 400 x 400 as ten).
-//   k_down_wgrad   dw[co][(ci, t)] = sum_{frame, P} dz[co][P] xp[ci][plane_t][P + off_t]    M = Cout, N = 9 Cin, K = frames x PP in ranges
+//   k_conv3_wgrad  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] xp[ci][plane_t][P + off_t]    M = Cout, N = 9 Cin, K = frames x PP in ranges
+//                  (train_conv3.h's kernel with the stride-2 taps, taps_s2)
 //   k_dw_reduce    partials summed in index order (double, rounded once; train_host.h, shared by the three families)
 //   k_down_dgrad   per output parity class (py, px), P the half-resolution position of x[2 r + py][2 c + px]:
 //                  dx[ci][P] = sum_{t in class, co} wT[t][co][ci] dz[co][P + (py & ky == 0) wp + (px & kx == 0)]
 //                  M = Cin, N = PP, K = Cout x {1, 2, 2, 4} taps (even: the centre tap; odd: taps 0 and 2), summed in blocks of DA_BLOCK
+//                  (each tap by train_conv3.h's conv3_dgrad_tap)
 // The two products run on v_mfma_f32_16x16x4_f32 with operands straight from global memory, as in block_train.hip.
 //
 // Determinism: no atomics at all.  Every reduction has a fixed shape: a workgroup's 256 strided fp64 partials are added in index
@@ -29,10 +31,11 @@
 // nb within fp32 summation error (the K ranges do), and not on whether dx is asked for.
 // pp_down_backward_affine is the same stage with a per-channel affine (a frozen BatchNorm2d) for the norm: k_affine_down_dz in place
 // of the three norm passes, then the same products and k_affine_reduce; pp_down_backward itself stays the InstanceNorm backbone's.
-// pp_down_backward_bn is that stage in front of a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_down_sums over
+// pp_down_backward_bn is that stage in front of a train-mode BatchNorm2d (batch statistics pooled over the frames): k_bn_plane_sums over
 // all frames and k_bn_coef ahead of the chunks, k_bn_down_dz in them.
 // The plane and norm kernels of every form and the family's one check, plan and driver (down_check, down_make_plan, down_run) are
-// down_train.h's, shared with the 16-bit twin; this file holds the fp32 products and the entries, thin wrappers over them.
+// down_train.h's, shared with the 16-bit twin; the fp32 products are train_conv3.h's, shared with block_train.hip; this file holds the
+// stage's dgrad (its taps and its store), the launches of the products and the entries, thin wrappers over them.
 #include <cmath>
 #include "pp_common.h"
 #include "train_planes.h"
@@ -41,75 +44,9 @@
 
 namespace {
 
-__global__ void __launch_bounds__(256) k_down_wt(const float* __restrict__ w, float* __restrict__ wT, int cin, int cout)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][cout][cin]
-    if (i >= 9 * cin * cout) return;
-    const int ci = i % cin, co = (i / cin) % cout, t = i / (cin * cout);
-    wT[i] = w[((size_t)co * cin + ci) * 9 + t];
-}
-
-// ---- wgrad: workgroup tile 64 co x columns n = ci 9 + t, a wave MA 16-row blocks of co x 16 NB columns.  MA = 2: four waves 2 x 2, tile
-// 64 x 32 NB (Cin = 128: 128 columns).  MA = 4: four waves side by side, every one all 64 co, tile 64 x 64 NB (Cin = 64: 576 = 3 x 192
-// columns; a wave loads 4 dz rows and 12 x columns for 48 MFMAs where the 2 x 2 form loads 2 and 8 for 16).  K runs over 16-position
-// chunks of the launch's frames (chunk c: frame c / cpf, positions 16 (c % cpf) ..; positions past PP read guard zeros of dz); a lane
-// takes positions 4 q .. 4 q + 3 of the chunk as its four k-steps: one 16-byte load per dz row, four shifted loads per x column.
-// blockIdx.z owns chunks [z cps, (z + 1) cps) and writes partial gbase + z, already in the state_dict layout [co][ci][3][3].
-template <int NB, int MA>
-__global__ void __launch_bounds__(256) k_down_wgrad(const float* __restrict__ dzp, const float* __restrict__ xp, float* __restrict__ part, int cin,
-                                                    int cout, int wp, int G, int PS, int cpf, int nchunks, int cps, int gbase)
-{
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
-    static_assert(MA == 2 || MA == 4, "waves 2 x 2 or 1 x 4");
-    constexpr int WC = MA;     // waves across the tile: 2 of 2 x 2, 4 of 1 x 4
-    const int co0 = blockIdx.y * 64 + (MA == 2 ? 32 * (wave >> 1) : 0), n0 = blockIdx.x * (16 * NB * WC) + 16 * NB * (wave & (WC - 1));
-    const int NC = 9 * cin;
-    int boff[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int n = n0 + 16 * b + l16, ci = n / 9, t = n - 9 * ci, ky = t / 3, kx = t - 3 * ky;
-        const int par = (ky != 1 ? 2 : 0) + (kx != 1 ? 1 : 0);
-        boff[b] = (ci * 4 + par) * PS + G - (ky == 0 ? wp : 0) - (kx == 0 ? 1 : 0);
-    }
-    f32x4 acc[MA][NB];
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int c0 = blockIdx.z * cps, c1 = c0 + cps < nchunks ? c0 + cps : nchunks;
-    for (int c = c0; c < c1; ++c) {
-        const int f = c / cpf, pb = (c - f * cpf) * 16 + 4 * q;
-        const float* zf = dzp + (size_t)f * cout * PS + G + pb;
-        const float* xf = xp + (size_t)f * cin * 4 * PS + pb;
-        float za[MA][4], xb[NB][4];
-#pragma unroll
-        for (int a = 0; a < MA; ++a) {
-            const float4 v = *reinterpret_cast<const float4*>(zf + (size_t)(co0 + 16 * a + l16) * PS);
-            za[a][0] = v.x; za[a][1] = v.y; za[a][2] = v.z; za[a][3] = v.w;
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) xb[b][s] = xf[boff[b] + s];
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int a = 0; a < MA; ++a)
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(za[a][s], xb[b][s], acc[a][b], 0, 0, 0);
-    }
-    float* pw = part + (size_t)(gbase + blockIdx.z) * cout * NC;
-#pragma unroll
-    for (int a = 0; a < MA; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pw[(size_t)(co0 + 16 * a + 4 * q + i) * NC + n0 + 16 * b + l16] = acc[a][b][i];
-}
-
 // ---- dgrad: grid (position tiles, 4 parity classes, frames).  A workgroup covers ALL Cin channels (WM = Cin / 64 waves down, 4 / WM
-// across), each wave 64 ci x 32 half-resolution positions, so dz is read once per tap.  K = (t in class, co) in steps of 4 output
-// channels (lane group q takes co + q); each DA_BLOCK terms accumulate from zero and the block sums are then added in (t, co) order.
+// across), each wave 64 ci x 32 half-resolution positions, so dz is read once per tap.  K = (t in class, co): the class's taps in order,
+// each tap's blocked sum over co by conv3_dgrad_tap.
 // Positions past PP read a clamped index and are never stored; a position is stored where its input pixel (2 r + py, 2 c + px) exists,
 // into the tight [Cin][Hin][Win] plane of dx.
 template <int WM>
@@ -132,33 +69,7 @@ __global__ void __launch_bounds__(256) k_down_dgrad(const float* __restrict__ wT
     for (int ky = py ? 0 : 1; ky < 3; ky += 2)
         for (int kx = px ? 0 : 1; kx < 3; kx += 2) {
             const int t = ky * 3 + kx, off = (ky == 0 ? wp : 0) + (kx == 0 ? 1 : 0);
-            const float* wt_t = wT + (size_t)t * cout * cin + ci0 + l16;
-            for (int cb0 = 0; cb0 < cout; cb0 += DA_BLOCK) { // cout is a multiple of DA_BLOCK
-                f32x4 acc[4][2];
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-                for (int cb = cb0; cb < cb0 + DA_BLOCK; cb += 4) {
-                    const int co = cb + q;
-                    const float* wr = wt_t + (size_t)co * cin;
-                    const float* zr = zf + (size_t)co * PS + off;
-                    const float z0 = zr[i0], z1 = zr[i1];
-                    float wa[4];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) wa[a] = wr[16 * a];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z0, acc[a][0], 0, 0, 0);
-                        acc[a][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[a], z1, acc[a][1], 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) tot[a][b] += acc[a][b];
-            }
+            conv3_dgrad_tap(tot, wT + (size_t)t * cout * cin + ci0 + l16, zf, off, i0, i1, q, cin, cout, PS);
         }
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -182,17 +93,17 @@ struct down_fp32 {
     static int grow_wt(pp_ctx* ctx, down_ws* ws, int nw) { return grow(ctx, &ws->wT, &ws->wT_elems, (size_t)nw); }
     static void pack_wt(const down_plan& p, down_ws* ws, const float* wgt, hipStream_t stream)
     {
-        hipLaunchKernelGGL(k_down_wt, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wgt, ws->wT, p.s.cin, p.s.cout);
+        hipLaunchKernelGGL(k_conv3_wt, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wgt, ws->wT, p.s.cin, p.s.cout);
     }
     static void wgrad(const down_plan& p, const dw_chunk& c, const float* dzp, const float* xp, float* part, hipStream_t stream)
     {
         const int cin = p.s.cin, cout = p.s.cout;
         const dim3 gd(p.NC / p.TN, cout / 64, c.sp);
         if (cin >= 128)
-            hipLaunchKernelGGL((k_down_wgrad<4, 2>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PS, p.cpf, c.nchunks, c.cps,
+            hipLaunchKernelGGL((k_conv3_wgrad<4, 2, taps_s2>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PS, p.cpf, c.nchunks, c.cps,
                                c.gbase);
         else
-            hipLaunchKernelGGL((k_down_wgrad<3, 4>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PS, p.cpf, c.nchunks, c.cps,
+            hipLaunchKernelGGL((k_conv3_wgrad<3, 4, taps_s2>), gd, dim3(256), 0, stream, dzp, xp, part, cin, cout, p.g.wp, p.g.G, p.g.PS, p.cpf, c.nchunks, c.cps,
                                c.gbase);
     }
     static void dgrad(const down_plan& p, const down_ws* ws, const float* dzp, float* dx, int fn, hipStream_t stream)

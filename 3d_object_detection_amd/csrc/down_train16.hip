@@ -2,7 +2,7 @@
 // "bf16x3" and 2 "bf16".  The parity planes of x, the plane statistics, the norm backward and the padded dz plane are down_train.h's
 // fp32 / fp64 kernels, so mean, rstd, the mask xhat > 0 and dz itself are the fp32 path's bits.  Only the two gradient products run on
 // v_mfma_f32_16x16x32_bf16 (a lane's A / B fragment is 8 consecutive k of one row / column), with fp32 accumulation:
-//   k_down_wt16     wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the dgrad's A operand, 8 consecutive co per lane
+//   k_conv3_wt16    wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the dgrad's A operand, 8 consecutive co per lane (train16.h)
 //   k_down_wgrad16  dw[co][(ci, t)] = sum_{frame, P} dz[co][P] xp[ci][plane_t][P + off_t]   K = frames x PP in chunks of 32 positions
 //   k_down_dgrad16  per output parity class: dx[ci][P] = sum_{t in class, co} wT16[t][ci][co] dz[co][P + off]   K in steps of 32 co,
 //                   blocks of DA_BLOCK = 64 from zero
@@ -30,18 +30,7 @@ struct __attribute__((packed, aligned(4))) f32x4u { float v[4]; }; // four float
 
 constexpr int DW16_WGS = 2048; // workgroups a 16-bit wgrad launch aims at: its short K steps need more waves per SIMD than fp32's DW_WGS
 
-template <bool X3>
-__global__ void __launch_bounds__(256) k_down_wt16(const float* __restrict__ w, uint16_t* __restrict__ wT, int cin, int cout)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][cin][cout]
-    if (i >= 9 * cin * cout) return;
-    const int co = i % cout, ci = (i / cout) % cin, t = i / (cin * cout);
-    const float v = w[((size_t)co * cin + ci) * 9 + t];
-    wT[i] = (uint16_t)pk_bf16(v, 0.f);
-    if (X3) wT[(size_t)9 * cin * cout + i] = (uint16_t)pk_bf16(bf16_rest(v), 0.f);
-}
-
-// ---- wgrad: k_down_wgrad's tiles (MA = 2: waves 2 x 2, 64 co x 32 NB columns; MA = 4: waves 1 x 4, 64 co x 64 NB columns).  K runs over
+// ---- wgrad: k_conv3_wgrad's tiles (MA = 2: waves 2 x 2, 64 co x 32 NB columns; MA = 4: waves 1 x 4, 64 co x 64 NB columns).  K runs over
 // 32-position chunks of the launch's frames (chunk c: frame c / cpf, positions 32 (c % cpf) ..); a lane's 8 k are positions 4 q .. 4 q + 3
 // and 16 + 4 q .. 16 + 4 q + 3 of the chunk (the sum over K is order-free: with this assignment the four lane groups of a row read 64
 // contiguous bytes per load where 8 q .. 8 q + 7 reads 16 of every 32, twice the cache lines per instruction).  dz: two aligned 16-byte
@@ -216,7 +205,7 @@ struct down_bf16 {
     static int grow_wt(pp_ctx* ctx, down_ws* ws, int nw) { return grow(ctx, &ws->wT16, &ws->wT16_elems, (size_t)(X3 ? 2 : 1) * nw); }
     static void pack_wt(const down_plan& p, down_ws* ws, const float* wgt, hipStream_t stream)
     {
-        hipLaunchKernelGGL(k_down_wt16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wgt, ws->wT16, p.s.cin, p.s.cout);
+        hipLaunchKernelGGL(k_conv3_wt16<X3>, dim3(pp_div_up(p.nw, 256)), dim3(256), 0, stream, wgt, ws->wT16, p.s.cin, p.s.cout);
     }
     static void wgrad(const down_plan& p, const dw_chunk& c, const float* dzp, const float* xp, float* part, hipStream_t stream)
     {
@@ -291,7 +280,7 @@ extern "C" int pp_down_backward_bn_path(pp_ctx* ctx, int mode, int cin, int cout
     return mode;
 }
 
-// pp_down_backward_affine / pp_down_backward_bn with the two products in 16-bit operands.  k_affine_down_dz, k_bn_down_sums, k_bn_coef and
+// pp_down_backward_affine / pp_down_backward_bn with the two products in 16-bit operands.  k_affine_down_dz, k_bn_plane_sums, k_bn_coef and
 // k_bn_down_dz are the fp32 path's own passes, so the mask, dz, dscale and dshift are its bits in every mode; mode 0 is the fp32 entry.
 extern "C" int pp_down_backward_affine_mp(pp_ctx* ctx, int mode, int cin, int cout, int hin, int win, const float* x, const float* wgt,
                                           const float* z, const float* scale, const float* shift, const float* dy, int nb, float* dw, float* dx,

@@ -1,5 +1,6 @@
 // The bf16 operand helpers of the mixed-precision backwards (block_train16.hip, down_train16.hip, neck_train16.hip): packing and
-// splitting fp32 values into bf16 fragments, the bf16 MFMA, and the funnel shift of a fragment by one element.
+// splitting fp32 values into bf16 fragments, the bf16 MFMA, the funnel shift of a fragment by one element, and the weight image of the
+// 3 x 3 dgrads (k_conv3_wt16: the unit's with cin = cout = C, and the strided stage's).
 #pragma once
 #include "pp_common.h"
 #include "train_host.h" // f32x4
@@ -28,6 +29,18 @@ __device__ __forceinline__ u32x4 pk8_rest(const float* v)
 __device__ __forceinline__ f32x4 mfma16(const u32x4 a, const u32x4 b, const f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// wT16[part][t][ci][co] = bf16 parts of w[co][ci][t]: the A operand of k_unit_dgrad16 and k_down_dgrad16, 8 consecutive co per lane
+template <bool X3>
+__global__ void __launch_bounds__(256) k_conv3_wt16(const float* __restrict__ w, uint16_t* __restrict__ wT, int cin, int cout)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x; // index into wT [9][cin][cout]
+    if (i >= 9 * cin * cout) return;
+    const int co = i % cout, ci = (i / cout) % cin, t = i / (cin * cout);
+    const float v = w[((size_t)co * cin + ci) * 9 + t];
+    wT[i] = (uint16_t)pk_bf16(v, 0.f);
+    if (X3) wT[(size_t)9 * cin * cout + i] = (uint16_t)pk_bf16(bf16_rest(v), 0.f);
 }
 
 // eight consecutive bf16 elements starting one element before (kx = 0) or behind (kx = 2) an aligned 16-byte group d: e is the dword

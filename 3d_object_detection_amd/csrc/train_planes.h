@@ -1,6 +1,7 @@
 // The device side that the streaming passes of block_train.hip and down_train.hip share (the host side of the training backwards is
-// train_host.h's): how a plane is cut into segments, the fixed-order sums of a
-// workgroup, and the statistics kernel.  One copy, so that both files cut a plane the same way and a shape keeps its bits in both.
+// train_host.h's, the two MFMA products train_conv3.h's): how a plane is cut into segments, the fixed-order sums of a workgroup, the
+// walk over a slice of the padded plane, the statistics kernel and the mean / rstd of a plane from its sums.  One copy, so that both
+// files cut a plane the same way and a shape keeps its bits in both.
 // k_affine_reduce, the last step of the three pp_*_backward_affine entries, is here for neck_train.hip as well, and so is k_bn_coef,
 // which pools the sums of the three pp_*_backward_bn entries.
 #pragma once
@@ -41,6 +42,25 @@ __device__ __forceinline__ void strided4(int lo, int hi, LD ld, ACC acc)
     for (; i < hi; i += 256) acc(ld(i));
 }
 
+// thread t of the workgroup visits elements j = lo + t, lo + t + 256, ... below hi of the padded plane of an h x w map (padded_plane,
+// train_host.h) in that order: body(j, pos), where pos tells whether element j is interior and, if so, its row r, column c and index
+// i = r w + c in the tight [h][w] plane.  The one statement of which elements of a padded plane are interior: both products rely on
+// the others, halo and guard bands, being zeros, which the callers store themselves
+struct plane_pos { bool inside; int i, r, c; };
+template <typename F>
+__device__ __forceinline__ void padded_walk(int lo, int hi, int h, int w, int wp, int G, int PP, F body)
+{
+    for (int j = lo + (int)threadIdx.x; j < hi; j += 256) {
+        const int P = j - G;
+        plane_pos pos{false, 0, 0, 0};
+        if (P >= 0 && P < PP) {
+            const int y = P / wp, x = P - y * wp;
+            if (y >= 1 && y <= h && x >= 1 && x <= w) pos = plane_pos{true, (y - 1) * w + x - 1, y - 1, x - 1};
+        }
+        body(j, pos);
+    }
+}
+
 // ---- statistics: grid (C, frames, S), sum u and sum u^2 of one segment of a tight [C][N] plane -> pst[plane][segment][2] ------------
 __global__ void __launch_bounds__(256) k_plane_stats(const float* __restrict__ u, double* __restrict__ pst, int C, int N, int L, int S)
 {
@@ -53,6 +73,17 @@ __global__ void __launch_bounds__(256) k_plane_stats(const float* __restrict__ u
     strided4(lo, hi, [&](int i) { return up[i]; }, [&](float f) { const double v = (double)f; s += v; ss += v * v; });
     block_sum2(s, ss, red);
     if (tid == 0) { pst[(pl * S + blockIdx.z) * 2] = s; pst[(pl * S + blockIdx.z) * 2 + 1] = ss; }
+}
+
+// mean and rstd of a plane as the forward rounds them, from its segment sums added in index order
+__device__ __forceinline__ void plane_mean_rstd(const double* __restrict__ pst, size_t pl, int S, int N, float& meanf, float& rstdf)
+{
+    double s = 0.0, ss = 0.0;
+    for (int g = 0; g < S; ++g) { s += pst[(pl * S + g) * 2]; ss += pst[(pl * S + g) * 2 + 1]; }
+    const double inv_n = 1.0 / (double)N, mean = s * inv_n;
+    double var = ss * inv_n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    meanf = (float)mean; rstdf = (float)(1.0 / sqrt(var + 1e-3));
 }
 
 // ---- per-channel affine (frozen BatchNorm) backward: the two sums of a channel from pst[frame][c][segment][2], segments added in index

@@ -209,8 +209,8 @@ def test_c_abi_is_declared_and_bound():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-@pytest.mark.parametrize("src,names", [("block_train.hip", ("k_bn_unit_sums", "k_bn_unit_du", "k_bn_coef")),
-                                       ("down_train.hip", ("k_bn_down_sums", "k_bn_down_dz", "k_bn_coef")),
+@pytest.mark.parametrize("src,names", [("block_train.hip", ("k_bn_plane_sums", "k_bn_unit_du", "k_bn_coef")),
+                                       ("down_train.hip", ("k_bn_plane_sums", "k_bn_down_dz", "k_bn_coef")),
                                        ("neck_train.hip", ("k_bn_neck_sums", "k_bn_neck_dz", "k_bn_coef"))])
 def test_bn_passes_use_no_scratch(src, names):
     k = {n: u for n, u in kernel_usage(src).items() if "k_bn_" in n}

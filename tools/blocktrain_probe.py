@@ -5,7 +5,7 @@ and its executed MFMA flops / 157.3 TF (the constants bench.py uses).
 
     python tools/blocktrain_probe.py [--frames 1,8] [--reps 10]
     rocprofv3 --kernel-trace --stats -d OUT -o blocktrain -- python tools/blocktrain_probe.py --frames 8 --no-torch   (per-kernel split:
-                                       k_unit_wt, k_unit_pack, k_unit_wgrad, k_dw_reduce, k_unit_dgrad, k_unit_norm, k_unit_image)
+                                       k_conv3_wt, k_unit_pack, k_conv3_wgrad, k_dw_reduce, k_unit_dgrad, k_unit_norm, k_unit_image)
 Also timed in the same run: the same unit in stock PyTorch (instance_norm -> relu -> conv2d, .backward()), pp_update_block_weights,
 pp_backbone_block_taps against pp_backbone_taps, and one whole fine-tuning step at nb = 8 per scope (per-frame forward, head, loss,
 backward, SGD step, weight upload).  Prints one JSON line."""

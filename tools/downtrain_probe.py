@@ -5,7 +5,7 @@ next to each call's floors -- its algorithmic HBM bytes / 8 TB/s and its execute
 
     python tools/downtrain_probe.py [--frames 1,8] [--reps 10]
     rocprofv3 --kernel-trace --stats -d OUT -o downtrain -- python tools/downtrain_probe.py --frames 8 --no-step   (per-kernel split:
-                                       k_down_wt, k_down_xpack, k_down_norm, k_down_wgrad, k_dw_reduce, k_down_dgrad)
+                                       k_conv3_wt, k_down_xpack, k_down_norm, k_conv3_wgrad, k_dw_reduce, k_down_dgrad)
 Also timed in the same run: pp_unit_backward at C = 256 on the 100 x 100 map (the yardstick beside it), pp_update_down_weight,
 pp_backbone_stage_taps against pp_backbone_block_taps, and whole fine-tuning steps at nb = 8 under scope "block3" and "stage3",
 alternated (per-frame forward, head, loss, backward, SGD step, weight upload).  Prints one JSON line."""
