@@ -16,13 +16,21 @@ counted from the start of the allocation (t starts at an even word):
   "poison" +-2^40 (fp16 +-2^14), word i positive when i is even: finite, so no max / med3 drops it the way it drops a NaN, and of
            both signs, so one of two neighbouring words survives relu(x * scale + shift) whatever the sign of scale
   "a5"     the byte 0xA5, for outputs: the tensor region holds it too (place_out), so an element the kernel never stored shows.
-untouched(arena): every byte outside t still holds the fill (integer comparison of the bytes, no float semantics)."""
+  "5a"     the byte 0x5A, a second pre-fill for outputs: two runs whose outputs start as 0xA5 and as 0x5A can only end with equal bits
+           in the elements the kernel stored, so comparing them finds an element it never stored without naming a pattern.
+untouched(arena): every byte outside t still holds the fill (integer comparison of the bytes, no float semantics).
+
+`offset` (default OFFSET) moves the tensor's start within its 512-byte block: 260 gives a 4-byte element type an address that is
+4-byte aligned only (% 16 == 4), 264 an 8-byte one that is 8-byte aligned only, 272 one that is 16-byte aligned and no more.  An input
+whose tensor the kernel updates in place is place(..., inplace=True): it keeps its contents, and untouched() then compares the
+surroundings alone, as for an output."""
 import numpy as np
 import torch
 
 BAND = 64 * 1024
 ALIGN, OFFSET = 512, 256
 FILLS = ("zeros", "nan", "poison")
+OUT_FILLS = {"a5": 0xA5, "5a": 0x5A}  # pre-fill bytes of an output arena
 _WORDS = {("nan", 4): (0x7FC00BAD, 0x7FC00BAD), ("nan", 2): (0x7E01, 0x7E01),
           ("poison", 4): (0x53800000, 0xD3800000), ("poison", 2): (0x7400, 0xF400),  # +-2^40, +-2^14
           ("zeros", 4): (0, 0), ("zeros", 2): (0, 0), ("a5", 4): (0xA5A5A5A5, 0xA5A5A5A5), ("a5", 2): (0xA5A5, 0xA5A5)}
@@ -45,24 +53,25 @@ class Arena:
     """buf: the whole allocation (uint8); t: the tensor view inside it; lo, hi: t's byte range in buf; snap: a copy of buf taken by
     seal() once t holds its contents; out: an output arena (the kernel is expected to write t)"""
 
-    def __init__(self, shape, dtype, device, front_bytes, behind_bytes, fill):
+    def __init__(self, shape, dtype, device, front_bytes, behind_bytes, fill, offset=OFFSET):
         esize = torch.empty((), dtype=dtype).element_size()
+        assert 0 <= offset < ALIGN and offset % esize == 0, (offset, esize)
         nbytes = int(np.prod(shape)) * esize
         band = max(BAND, -(-nbytes // max(1, int(shape[0]))))
         raw = torch.empty(2 * band + front_bytes + nbytes + behind_bytes + 3 * ALIGN, dtype=torch.uint8, device=device)
         skip = (-raw.data_ptr()) % ALIGN                   # the allocator aligns to 512 already; not relied on
         lo = band + front_bytes
-        lo += (OFFSET - (raw.data_ptr() + skip + lo)) % ALIGN
+        lo += (offset - (raw.data_ptr() + skip + lo)) % ALIGN
         total = (lo + nbytes + behind_bytes + band + 7) & ~7
         self.buf = raw[skip:skip + total]
         assert total <= raw.numel() - skip and lo >= band + front_bytes and total - (lo + nbytes) >= behind_bytes + band
-        if fill == "a5":
-            self.buf.fill_(0xA5)
+        if fill in OUT_FILLS:
+            self.buf.fill_(OUT_FILLS[fill])
         else:
             self.buf.copy_(fill_words(fill, esize, total, device))
-        self.lo, self.hi, self.fill, self.esize, self.out, self.snap = lo, lo + nbytes, fill, esize, fill == "a5", None
+        self.lo, self.hi, self.fill, self.esize, self.out, self.snap = lo, lo + nbytes, fill, esize, fill in OUT_FILLS, None
         self.t = self.buf[lo:lo + nbytes].view(dtype).view(shape)
-        assert self.t.data_ptr() % ALIGN == OFFSET and self.t.data_ptr() == self.buf.data_ptr() + lo
+        assert self.t.data_ptr() % ALIGN == offset and self.t.data_ptr() == self.buf.data_ptr() + lo
 
     def seal(self):
         self.snap = self.buf.clone()
@@ -82,16 +91,19 @@ class Arena:
         return int((self.words() == pattern).sum())
 
 
-def place(t, front_bytes=0, behind_bytes=0, fill="zeros"):
-    """Arena whose .t has t's shape, type and contents; `front_bytes` / `behind_bytes` of contractual slack, then the bands, all `fill`."""
-    a = Arena(tuple(t.shape), t.dtype, t.device, front_bytes, behind_bytes, fill)
+def place(t, front_bytes=0, behind_bytes=0, fill="zeros", offset=OFFSET, inplace=False):
+    """Arena whose .t has t's shape, type and contents; `front_bytes` / `behind_bytes` of contractual slack, then the bands, all `fill`.
+    inplace: the kernel may rewrite the tensor, so untouched() judges the surroundings alone."""
+    a = Arena(tuple(t.shape), t.dtype, t.device, front_bytes, behind_bytes, fill, offset)
     a.t.copy_(t)
+    a.out = bool(inplace)
     return a.seal()
 
 
-def place_out(shape, dtype, device="cuda"):
-    """Arena for an output: tensor region and surroundings pre-filled with the byte 0xA5"""
-    return Arena(tuple(shape), dtype, torch.device(device), 0, 0, "a5").seal()
+def place_out(shape, dtype, device="cuda", fill="a5", offset=OFFSET):
+    """Arena for an output: tensor region and surroundings pre-filled with the byte 0xA5 (fill "5a": 0x5A)"""
+    assert fill in OUT_FILLS
+    return Arena(tuple(shape), dtype, torch.device(device), 0, 0, fill, offset).seal()
 
 
 def untouched(arena):
