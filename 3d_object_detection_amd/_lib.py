@@ -99,6 +99,11 @@ PROTOTYPES = {
     "pp_update_down_weight": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
     "pp_backbone_train_taps": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pp_update_rpn_weights": (ctypes.c_int, [c_p, c_p, c_p]),
+    "pp_backbone_train_taps_mp": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_update_rpn_weights_mp": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p]),
+    "pp_update_neck_weights_mp": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p]),
+    "pp_update_head_weights_mp": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pp_debug_image16": (ctypes.c_int, [c_p, ctypes.c_int, c_p, c_p, c_p, c_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), c_p]),
     "pp_unit_backward_affine": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_p, c_p,
                                                c_p, c_p]),
     "pp_down_backward_affine": (ctypes.c_int, [c_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int,

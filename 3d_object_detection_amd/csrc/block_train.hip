@@ -215,14 +215,14 @@ void pp_block_destroy(pp_ctx* ctx)
     ctx->blk = nullptr;
 }
 
-int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream)
+int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream, bool any_plan)
 {
     if (k < 0 || k >= 16) return pp_fail(ctx, PP_E_ARG, "pp_update_conv_image: k must be 0 .. 15");
     block_ws* ws = workspace(ctx);
     pp_block_image& im = ws->img[k];
     if (ws->img_gen[k] != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
         ws->img_gen[k] = 0;
-        if (int rc = pp_net_conv_image(ctx, k, &im)) return rc;
+        if (int rc = pp_net_conv_image(ctx, k, &im, any_plan)) return rc;
         if (ws->pmap[k]) { (void)hipFree(ws->pmap[k]); ws->pmap[k] = nullptr; }
         PP_HIP(hipMalloc((void**)&ws->pmap[k], im.pmap.size() * sizeof(int32_t)));
         PP_HIP(hipMemcpy(ws->pmap[k], im.pmap.data(), im.pmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -394,6 +394,31 @@ extern "C" int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w, void* s
     for (int k = 0; k < 16 && !rc; ++k) rc = pp_update_conv_image(ctx, k, w[k], stream);
     if (!rc) rc = pp_sc1_update(ctx, w[0], stream);
     if (rc) return rc;
+    PP_HIP(hipGetLastError());
+    return 0;
+}
+
+// pp_update_rpn_weights for a plan committed in a 16-bit mode (1 bf16x3, 2 bf16, 3 fp16): every convolution on a 16-bit tiling is
+// rewritten by k_image16 (image16.hip), one that keeps an fp32 tiling by the fp32 writer above.  The sparse first convolution is fp32
+// only and keeps no image a 16-bit pass reads: a return to fp32 commits again.
+extern "C" int pp_update_rpn_weights_mp(pp_ctx* ctx, int mode, const float* const* w, void* stream_)
+{
+    if (!ctx) return PP_E_ARG;
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights_mp: no committed weights to update (pp_commit_weights first)");
+    if (!w) return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights_mp: null pointer");
+    for (int k = 0; k < 16; ++k)
+        if (!w[k] || ((uintptr_t)w[k] & 3)) return pp_fail(ctx, PP_E_ARG, "pp_update_rpn_weights_mp: null or misaligned weight pointer");
+    if (int rc = pp_mp_mode_check(ctx, "pp_update_rpn_weights_mp", mode)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    PP_HIP(hipSetDevice(ctx->device));
+    for (int k = 0; k < 16; ++k) {
+        const int layer = pp_net_layer_index(ctx, 0, k);
+        const int cout = k < 4 ? 64 : k < 10 ? 128 : 256, cin = k == 0 || k == 4 ? 64 : k == 10 ? 128 : cout;
+        bool is16 = false;
+        int rc = pp_update_image16(ctx, layer, w[k], nullptr, nullptr, cout * cin * 9, 0, 0, stream, &is16);
+        if (!rc && !is16) rc = pp_update_conv_image(ctx, k, w[k], stream, true);
+        if (rc) return rc;
+    }
     PP_HIP(hipGetLastError());
     return 0;
 }

@@ -28,7 +28,8 @@ static int packed_indices(pp_ctx* ctx, const Layer& L, bool index_positions, std
 // A packed weight image as an index map (pp_common.h): pack_layer itself packs an index-valued weight (element i of the
 // concatenation of the named host tensors holds the float i + 1; exact below 2^24) into a scratch image with the layer's committed
 // tiling, so whatever row order (head_tile_row), row padding and K blocking that tiling uses is read back, not restated.  fp32 images
-// only: the 16-bit images round their elements, the indices would not survive.  Synchronous; called once per commit by train.hip.
+// only: the 16-bit images round their elements, the indices would not survive (pp_net_image16 below reads those back digit by digit).
+// Synchronous; called once per commit by train.hip.
 static int layer_index_map(pp_ctx* ctx, const Layer& L, const std::vector<std::string>& names, std::vector<int32_t>& wmap)
 {
     std::vector<std::vector<float>> saved(names.size());
@@ -60,13 +61,13 @@ static int layer_position_map(pp_ctx* ctx, const Layer& L, std::vector<int32_t>&
 
 // The k-th 3 x 3 convolution of the committed plan in execution order (0 .. 15: per level its strided convolution, then its units'),
 // for pp_update_conv_image (block_train.hip)
-int pp_net_conv_image(pp_ctx* ctx, int k, pp_block_image* img)
+int pp_net_conv_image(pp_ctx* ctx, int k, pp_block_image* img, bool any_plan)
 {
     pp_net* net = (pp_net*)ctx->net;
     int seen = 0;
     for (Layer& L : net->layers) {
         if (L.kind != 0 || seen++ != k) continue;
-        if (net->eff_prec != 0 || L.var.prec != 0 || L.var.io16 != 0 || L.var.family == Family::Conv16)
+        if ((!any_plan && net->eff_prec != 0) || L.var.prec != 0 || L.var.io16 != 0 || L.var.family == Family::Conv16)
             return pp_fail(ctx, PP_E_ARG, L.stride == 2 ? "the strided convolution can be rewritten in place in the fp32 mode only (the committed plan packs it in a 16-bit format)"
                                                         : "block weights can be rewritten in place in the fp32 mode only (the committed plan packs them in a 16-bit format)");
         if (L.stride == 2 && L.var.family != Family::Direct)
@@ -81,11 +82,11 @@ int pp_net_conv_image(pp_ctx* ctx, int k, pp_block_image* img)
     return pp_fail(ctx, PP_E_ARG, "pp_net_conv_image: no such convolution");
 }
 
-int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
+int pp_net_head_image(pp_ctx* ctx, pp_head_image* img, bool any_plan)
 {
     pp_net* net = (pp_net*)ctx->net;
     Layer& head = net->layers.back();
-    if (net->eff_prec != 0 || head.var.prec != 0 || head.var.io16 != 0)
+    if ((!any_plan && net->eff_prec != 0) || head.var.prec != 0 || head.var.io16 != 0)
         return pp_fail(ctx, PP_E_ARG, "head weights can be rewritten in place in the fp32 mode only (the committed plan packs the head in a 16-bit format)");
     const int na = ctx->cfg.num_anchor_per_loc;
     std::vector<std::string> names;
@@ -98,6 +99,14 @@ int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
     int rc = layer_index_map(ctx, head, names, img->wmap);
     if (rc) return rc;
     img->w = head.w;
+    return pp_net_head_bias(ctx, img);
+}
+
+// the bias part of pp_net_head_image: it does not depend on the head's tiling or on the precision mode
+int pp_net_head_bias(pp_ctx* ctx, pp_head_image* img)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    const int na = ctx->cfg.num_anchor_per_loc;
     img->bias = net->head_bias;
     img->bmap.assign((size_t)head_rows(na), -1);
     for (int r = 0; r < 10 * na; ++r) img->bmap[r] = r;
@@ -113,13 +122,13 @@ int pp_net_head_image(pp_ctx* ctx, pp_head_image* img)
 
 // The packed image of upsampler `branch` (0..2) of the committed plan, described the same way: wmap[i] is the element of the
 // state_dict tensor rpn.deconv<branch+1>.0.weight [Cin][Cup][s][s] that image element i holds, -1 for padding.
-int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img)
+int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img, bool any_plan)
 {
     pp_net* net = (pp_net*)ctx->net;
     int seen = 0;
     for (Layer& L : net->layers) {
         if (L.kind != 1 || seen++ != branch) continue;
-        if (net->eff_prec != 0 || L.var.prec != 0 || L.var.io16 != 0)
+        if ((!any_plan && net->eff_prec != 0) || L.var.prec != 0 || L.var.io16 != 0)
             return pp_fail(ctx, PP_E_ARG, "upsampler weights can be rewritten in place in the fp32 mode only (the committed plan packs them in a 16-bit format)");
         int rc = layer_index_map(ctx, L, {L.wkey}, img->wmap);
         if (rc) return rc;
@@ -128,6 +137,98 @@ int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img)
         return 0;
     }
     return pp_fail(ctx, PP_E_ARG, "pp_net_deconv_image: no such upsampler");
+}
+
+int pp_net_layer_index(pp_ctx* ctx, int kind, int ordinal)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    int seen = 0;
+    for (size_t i = 0; i < net->layers.size(); ++i)
+        if (net->layers[i].kind == kind && seen++ == ordinal) return (int)i;
+    return -1;
+}
+
+// A 16-bit image as an element map (pp_common.h).  An index does not survive one 16-bit rounding, so it goes through the packer digit
+// by digit: in pass p element e of the concatenated host tensors holds digit_value((e / 128^p) % 128), a value whose rounded part and
+// whose bf16 residual are both exact, non-zero and different for every digit, and an image element is recognised by its bits.  The
+// two tables come from the packers' own conversions (conv_common.h), so the part of an element -- rounded value or residual -- is
+// read back with its index; zero bits in every pass are padding.
+static const int kDigits = 128;
+static inline float digit_value(int d) { return (float)(d + 1) * (1.f / 256.f) * (1.f + 1.f / 512.f); }
+
+int pp_net_image16(pp_ctx* ctx, int layer, pp_image16* img)
+{
+    pp_net* net = (pp_net*)ctx->net;
+    if (layer < 0 || layer >= (int)net->layers.size()) return pp_fail(ctx, PP_E_ARG, "pp_net_image16: no such layer");
+    const Layer& L = net->layers[layer];
+    img->w = L.w;
+    img->bytes = L.w_bytes;
+    img->map.clear();
+    img->fp16 = L.var.prec == 3;
+    img->is16 = L.var.family == Family::Conv16 || (L.var.family == Family::Gemm1x1 && L.var.prec != 0); // pack_layer's own rule
+    if (!img->is16) return 0;
+    if (L.var.io16 != 0) return pp_fail(ctx, PP_E_ARG, "pp_net_image16: the committed plan runs fp16 tensors (fp16s)");
+    std::vector<std::string> names;
+    if (L.kind == 2)
+        for (const HeadPart& part : kHead) names.push_back(part.weight);
+    else
+        names.push_back(L.wkey);
+    // the two parts of every digit, by the packers' conversions
+    std::map<uint16_t, int> hi_of, lo_of;
+    for (int d = 0; d < kDigits; ++d) {
+        const float x = digit_value(d);
+        uint16_t hi = to_bf16(x);
+        if (img->fp16) { const _Float16 h16 = (_Float16)x; memcpy(&hi, &h16, 2); }
+        const uint16_t lo = to_bf16(x - from_bf16(hi));
+        hi_of[hi] = d; lo_of[lo] = d;
+    }
+    bool distinct = (int)hi_of.size() == kDigits && (int)lo_of.size() == kDigits && !hi_of.count(0) && !lo_of.count(0);
+    for (auto& kv : hi_of) distinct = distinct && !lo_of.count(kv.first);
+    if (!distinct) return pp_fail(ctx, PP_E_STATE, "pp_net_image16: the digit values do not round to distinct parts");
+    std::vector<std::vector<float>> saved(names.size());
+    size_t total = 0;
+    for (size_t h = 0; h < names.size(); ++h) {
+        auto w = ctx->host_w.find(names[h]);
+        if (w == ctx->host_w.end()) return pp_fail(ctx, PP_E_NAME, ("missing weight " + names[h]).c_str());
+        total += w->second.data.size();
+    }
+    if (total > (size_t)kDigits * kDigits * kDigits) return pp_fail(ctx, PP_E_ARG, "pp_net_image16: weight too large for three base-128 digits");
+    for (size_t h = 0; h < names.size(); ++h) saved[h] = ctx->host_w[names[h]].data;
+    const size_t n = L.w_bytes / sizeof(uint16_t);
+    std::vector<uint16_t> image(n);
+    std::vector<int32_t> idx(n, 0), part(n, -1); // part: -1 padding so far
+    int rc = 0;
+    size_t div = 1;
+    for (int p = 0; p < 3 && !rc; ++p, div *= kDigits) {
+        size_t e = 0;
+        for (size_t h = 0; h < names.size(); ++h)
+            for (float& v : ctx->host_w[names[h]].data) v = digit_value((int)((e++ / div) % kDigits));
+        Layer scratch = L;
+        scratch.w = nullptr;
+        rc = pack_layer(ctx, scratch);
+        if (!rc && scratch.w_bytes != L.w_bytes) rc = pp_fail(ctx, PP_E_STATE, "pp_net_image16: the scratch image has another size");
+        if (!rc) {
+            const hipError_t e = hipMemcpy(image.data(), scratch.w, scratch.w_bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = pp_fail_hip(ctx, e, "hipMemcpy (pp_net_image16)", __FILE__, __LINE__);
+        }
+        if (scratch.w) (void)hipFree(scratch.w);
+        for (size_t i = 0; i < n && !rc; ++i) {
+            const uint16_t b = image[i];
+            const auto hi = hi_of.find(b), lo = lo_of.find(b);
+            const int pt = b == 0 ? -1 : hi != hi_of.end() ? 0 : lo != lo_of.end() ? 1 : -2;
+            if (pt == -2 || (p > 0 && pt != part[i])) { rc = pp_fail(ctx, PP_E_STATE, "pp_net_image16: an image element is no part of a digit"); break; }
+            part[i] = pt;
+            if (pt >= 0) idx[i] += (int32_t)((pt ? lo->second : hi->second) * div);
+        }
+    }
+    for (size_t h = 0; h < names.size(); ++h) ctx->host_w[names[h]].data.swap(saved[h]);
+    if (rc) return rc;
+    img->map.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (part[i] >= 0 && (size_t)idx[i] >= total) return pp_fail(ctx, PP_E_STATE, "pp_net_image16: an image element names no weight");
+        img->map[i] = part[i] < 0 ? -1 : 2 * idx[i] + part[i];
+    }
+    return 0;
 }
 
 // Test / inspection hook: copy one tensor of frame `frame` of the LAST pp_infer_batch / pp_infer_frame pass out of the

@@ -625,16 +625,20 @@ extern "C" int pp_head(pp_ctx* ctx, const float* rpn_out, float* cls, float* box
 // pp_backbone plus the block outputs x1..x3 and, where given, the copy hooks of pp_run_backbone: units[b] f32[3 | 5 | 5][C_b][H>>b][W>>b]
 // and z[b] f32[C_b][H>>b][W>>b] per level b (either array, or any entry, may be null).  The hooks are armed for this one pass only.
 // who: the entry point; null_in: the entry point one of whose own pointer arguments is null (or nullptr)
+// mode: 0 an fp32 plan (the four fp32 entries), 1 | 2 | 3 a plan committed in that 16-bit mode (pp_backbone_train_taps_mp): the level buffers
+// are fp32 there too and the copy hooks sit behind the launches whatever tiling runs, so the pass is the same with the other guard
 static int backbone_taps(pp_ctx* ctx, const char* who, const char* null_in, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3,
-                         float* const* units, float* const* z, void* stream_)
+                         float* const* units, float* const* z, void* stream_, int mode = 0)
 {
     if (!ctx) return PP_E_ARG;
     if (!ctx->weights_ready) return pp_fail(ctx, PP_E_STATE, (std::string(who) + ": weights not committed").c_str());
     if (null_in) return pp_fail(ctx, PP_E_ARG, (std::string(null_in) + ": null pointer").c_str());
     if (!canvas || !rpn_out || !x1 || !x2 || !x3) return pp_fail(ctx, PP_E_ARG, "pp_backbone_taps: null pointer");
     pp_net* net = (pp_net*)ctx->net;
-    if (net->eff_prec != 0 || net->up16)
+    if (mode == 0 && (net->eff_prec != 0 || net->up16))
         return pp_fail(ctx, PP_E_ARG, "pp_backbone_taps: fp32 mode only (in the 16-bit modes the level buffers may hold fp16)");
+    if (mode != 0)
+        if (int rc0 = pp_mp_mode_check(ctx, who, mode)) return rc0;
     for (int b = 0; b < 3; ++b) { net->unit_tap[b] = units ? units[b] : nullptr; net->z_tap[b] = z ? z[b] : nullptr; }
     int rc = pp_backbone(ctx, canvas, rpn_out, stream_);
     for (int b = 0; b < 3; ++b) net->unit_tap[b] = net->z_tap[b] = nullptr;
@@ -675,6 +679,16 @@ extern "C" int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* r
     bool null = !units || !z;
     for (int b = 0; b < 3 && !null; ++b) null = !units[b] || !z[b];
     return backbone_taps(ctx, "pp_backbone_train_taps", null ? "pp_backbone_train_taps" : nullptr, canvas, rpn_out, x1, x2, x3, units, z, stream_);
+}
+
+// pp_backbone_train_taps on a plan committed in 16-bit mode `mode`: the taps are the fp32 activations of that 16-bit forward
+extern "C" int pp_backbone_train_taps_mp(pp_ctx* ctx, int mode, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3,
+                                         float* const* units, float* const* z, void* stream_)
+{
+    bool null = !units || !z;
+    for (int b = 0; b < 3 && !null; ++b) null = !units[b] || !z[b];
+    return backbone_taps(ctx, "pp_backbone_train_taps_mp", null ? "pp_backbone_train_taps_mp" : nullptr, canvas, rpn_out, x1, x2, x3, units, z, stream_,
+                         mode);
 }
 
 // The lock-step training forward of the BatchNorm backbone: the dense backbone layer by layer over all nb frames, every BatchNorm2d

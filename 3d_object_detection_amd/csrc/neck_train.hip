@@ -233,31 +233,56 @@ extern "C" int pp_neck_backward_bn(pp_ctx* ctx, int branch, const float* x, cons
     return neck_entry(ctx, "pp_neck_backward_bn", NORM_BATCH, branch, a);
 }
 
-extern "C" int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const float* w3, void* stream_)
+namespace {
+// mode 0: pp_update_neck_weights (an fp32 plan); 1 | 2 | 3: the _mp entry for a plan committed in that 16-bit mode, where an upsampler on
+// a 16-bit tiling goes through k_image16 (image16.hip) and one that keeps an fp32 tiling through k_gather1
+int neck_update(pp_ctx* ctx, const char* who, int mode, const float* w1, const float* w2, const float* w3, void* stream_)
 {
     if (!ctx) return PP_E_ARG;
-    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_neck_weights: no committed weights to update (pp_commit_weights first)");
-    if (!w1 || !w2 || !w3) return pp_fail(ctx, PP_E_ARG, "pp_update_neck_weights: null pointer");
-    if (pp_effective_precision(ctx) != 0)
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, (std::string(who) + ": no committed weights to update (pp_commit_weights first)").c_str());
+    if (!w1 || !w2 || !w3) return pp_fail(ctx, PP_E_ARG, (std::string(who) + ": null pointer").c_str());
+    if (mode == 0 && pp_effective_precision(ctx) != 0)
         return pp_fail(ctx, PP_E_ARG, "pp_update_neck_weights: fp32 mode only (the committed plan packs the upsamplers in a 16-bit format)");
+    if (mode != 0)
+        if (int rc = pp_mp_mode_check(ctx, who, mode)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     PP_HIP(hipSetDevice(ctx->device));
     neck_ws* ws = workspace(ctx);
+    const float* src[3] = {w1, w2, w3};
+    bool is16[3] = {false, false, false};
+    if (mode != 0)
+        for (int b = 0; b < 3; ++b) {
+            const size_t elems = (size_t)(64 << b) * (b ? 128 : 64) * (1 << b) * (1 << b);
+            if (int rc = pp_update_image16(ctx, pp_net_layer_index(ctx, 1, b), src[b], nullptr, nullptr, (int)elems, 0, 0, stream, &is16[b])) return rc;
+        }
     if (ws->img_gen != ctx->commit_gen) { // first update after a commit: read the committed images' layout back (synchronous)
         for (int b = 0; b < 3; ++b) {
-            int rc = pp_net_deconv_image(ctx, b, &ws->img[b]);
-            if (rc) return rc;
             if (ws->wmap[b]) { (void)hipFree(ws->wmap[b]); ws->wmap[b] = nullptr; }
+            ws->img[b].wmap.clear();
+            if (is16[b]) continue;
+            int rc = pp_net_deconv_image(ctx, b, &ws->img[b], mode != 0);
+            if (rc) return rc;
             PP_HIP(hipMalloc((void**)&ws->wmap[b], ws->img[b].wmap.size() * sizeof(int32_t)));
             PP_HIP(hipMemcpy(ws->wmap[b], ws->img[b].wmap.data(), ws->img[b].wmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
         ws->img_gen = ctx->commit_gen;
     }
-    const float* src[3] = {w1, w2, w3};
     for (int b = 0; b < 3; ++b) {
+        if (is16[b]) continue;
         const int n = (int)ws->img[b].wmap.size();
         hipLaunchKernelGGL(k_gather1, dim3(pp_div_up(n, 256)), dim3(256), 0, stream, ws->img[b].w, ws->wmap[b], n, src[b], (int)ws->img[b].elems);
     }
     PP_HIP(hipGetLastError());
     return 0;
+}
+} // namespace
+
+extern "C" int pp_update_neck_weights(pp_ctx* ctx, const float* w1, const float* w2, const float* w3, void* stream_)
+{
+    return neck_update(ctx, "pp_update_neck_weights", 0, w1, w2, w3, stream_);
+}
+
+extern "C" int pp_update_neck_weights_mp(pp_ctx* ctx, int mode, const float* w1, const float* w2, const float* w3, void* stream_)
+{
+    return neck_update(ctx, "pp_update_neck_weights_mp", mode, w1, w2, w3, stream_);
 }

@@ -231,6 +231,7 @@ extern "C" void pp_destroy(pp_ctx* ctx)
     pp_down_destroy(ctx);
     pp_pfn_train_destroy(ctx);
     pp_optim_destroy(ctx);
+    pp_image16_destroy(ctx);
     for (pp_slot& S : ctx->slot) {
         void* sp[] = {S.cell_first, S.pt_cell, S.pt_rank, S.wave_cnt, S.occ};
         for (void* q : sp)

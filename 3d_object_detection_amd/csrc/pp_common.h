@@ -144,6 +144,7 @@ struct pp_ctx {
     void* blk = nullptr;             // Resnet unit backward (block_ws, block_train.h): padded a / dz planes, transposed weights, dW partials
     void* down = nullptr;            // strided stage backward (down_ws, down_train.h): parity planes of x, dz planes, transposed weights, dW partials
     void* pfnt = nullptr;            // PFN training (pfn_train.hip): fp64 partials of both reductions, the batch-statistics scale / shift
+    void* img16 = nullptr;           // in-place writer of the 16-bit weight images (image16.hip): the element maps of the twenty layers
     void* optim = nullptr;           // device optimizer (optim.hip): fp64 partials of the gradient norm, one per chunk
     int train_chunk_frames = 0;      // pp_set_train_chunk_frames: cap on the frames of a chunk of every training backward (0: the workspace rule alone)
     // ---- deferred head (pp_set_head_defer): the passes of pp_infer_batch run the cls rows for every pixel and the box / dir logits for
@@ -247,7 +248,8 @@ struct pp_head_image {
     float *w = nullptr, *bias = nullptr, *bias_perm = nullptr;
     std::vector<int32_t> wmap, bmap, bpmap;
 };
-int pp_net_head_image(pp_ctx* ctx, pp_head_image* img);
+int pp_net_head_image(pp_ctx* ctx, pp_head_image* img, bool any_plan = false);
+int pp_net_head_bias(pp_ctx* ctx, pp_head_image* img); // bias, bmap, bias_perm and bpmap alone (any plan)
 // The same for upsampler `branch` (0..2), for pp_update_neck_weights (neck_train.hip): wmap[i] is the element of the state_dict tensor
 // rpn.deconv<branch+1>.0.weight [Cin][Cup][s][s] (elems in all) that image element i holds, -1 for padding.
 struct pp_layer_image {
@@ -255,7 +257,7 @@ struct pp_layer_image {
     size_t elems = 0;
     std::vector<int32_t> wmap;
 };
-int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img);
+int pp_net_deconv_image(pp_ctx* ctx, int branch, pp_layer_image* img, bool any_plan = false);
 void pp_neck_destroy(pp_ctx* ctx);
 // 3 x 3 convolution k (0 .. 15) of the RPN in execution order, for pp_update_conv_image (block_train.hip): pmap[i] = (row C + c) T + pos
 // names the element of the TRANSFORMED weight [rows][C][T] that image element i holds (T = 36 | 16: position of U = G g G^T of the
@@ -267,7 +269,7 @@ struct pp_block_image {
     int rows = 0;     // output channels (= C for a unit)
     std::vector<int32_t> pmap;
 };
-int pp_net_conv_image(pp_ctx* ctx, int k, pp_block_image* img);
+int pp_net_conv_image(pp_ctx* ctx, int k, pp_block_image* img, bool any_plan = false);
 void pp_block_destroy(pp_ctx* ctx);
 void pp_down_destroy(pp_ctx* ctx);
 void pp_pfn_train_destroy(pp_ctx* ctx);
@@ -277,7 +279,32 @@ void pp_optim_destroy(pp_ctx* ctx);
 // convolution and 11 .. 15 its units) <- the state_dict tensor w [rows][cin][3][3] on the device, in place on `stream`.  Image element
 // i becomes position pmap[i] % T of the transformed weight of (row, cin) = pmap[i] / T, 0 for padding; the map is read back once per
 // commit, on the image's first update.  The callers check their arguments, the precision mode and set the device.
-int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream);
+// any_plan: the committed plan may run a 16-bit mode, in which convolution k keeps an fp32 tiling (the _mp updates: a shape no 16-bit
+// tiling takes); the default refuses every plan but an fp32 one, as pp_net_conv_image / _deconv_image / _head_image do.
+int pp_update_conv_image(pp_ctx* ctx, int k, const float* w, hipStream_t stream, bool any_plan = false);
+
+// ---- the 16-bit weight images (image16.hip; the maps by conv_inspect.hip) ----
+// Layer `layer` (0 .. 19) of the committed plan as the in-place writer sees it.  is16: the image holds 16-bit elements (conv16_pack,
+// gemm1x1_pack16); otherwise it is an fp32 image and map stays empty (the fp32 writers own it).  map[i] = 2 e + part for image element i:
+// e the element of the concatenation of the layer's state_dict tensors (a convolution's or an upsampler's weight; cls | box | dir of the
+// head), part 0 the rounded value (bf16, or fp16 when fp16 is set), 1 the bf16 residual lo = bf16(x - hi); -1 for padding.  Read back
+// from the packers themselves: three passes of base-128 digits, each digit a value whose two parts are both exact and non-zero.
+struct pp_image16 {
+    void* w = nullptr;
+    size_t bytes = 0;
+    bool is16 = false, fp16 = false;
+    std::vector<int32_t> map;
+};
+int pp_net_layer_index(pp_ctx* ctx, int kind, int ordinal); // conv3x3 k | upsampler branch | the head -> 0 .. 19, -1: no such layer
+int pp_net_image16(pp_ctx* ctx, int layer, pp_image16* img);
+// Rewrite layer `layer`'s 16-bit image in place on `stream` from the device tensors s0 | s1 | s2 (n0, n1, n2 elements; one tensor for a
+// convolution or an upsampler).  *is16 = false and nothing written when the layer keeps an fp32 image.  The map is read back on the
+// first call after a commit (synchronous) and cached per commit_gen.
+int pp_update_image16(pp_ctx* ctx, int layer, const float* s0, const float* s1, const float* s2, int n0, int n1, int n2, hipStream_t stream,
+                      bool* is16);
+void pp_image16_destroy(pp_ctx* ctx);
+// The guard of the four _mp entries: mode 1 | 2 | 3 and the committed plan's effective precision equals it (so fp16 tensors are off)
+int pp_mp_mode_check(pp_ctx* ctx, const char* who, int mode);
 
 // Frames per chunk of a training backward (the twelve pp_{unit,down,neck}_backward* chunk loops and the three _bn entries): as many
 // frames as fit `budget` bytes at frame_bytes each, at least 1 and at most nb; then at most the entry's own chunk_frames (0 where the

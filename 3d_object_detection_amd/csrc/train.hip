@@ -474,29 +474,50 @@ extern "C" int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* 
     return 0;
 }
 
-extern "C" int pp_update_head_weights(pp_ctx* ctx, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
-                                      const float* w_dir, const float* b_dir, void* stream_)
+namespace {
+// mode 0: pp_update_head_weights (an fp32 plan); 1 | 2 | 3: the _mp entry for a plan committed in that 16-bit mode.  There the weight
+// image goes through k_image16 (image16.hip) when the head runs a 16-bit tiling and through k_gather3 when it keeps an fp32 one; the
+// bias stays fp32 in every mode, in natural order and, where the plan has that copy, in head_tile_row order.
+int head_update(pp_ctx* ctx, const char* who_, int mode, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
+                const float* w_dir, const float* b_dir, void* stream_)
 {
     if (!ctx) return PP_E_ARG;
-    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, "pp_update_head_weights: no committed weights to update (pp_commit_weights first)");
-    if (!w_cls || !b_cls || !w_box || !b_box || !w_dir || !b_dir) return pp_fail(ctx, PP_E_ARG, "pp_update_head_weights: null pointer");
+    const std::string who(who_);
+    if (!ctx->weights_ready) return pp_fail(ctx, PP_E_ARG, (who + ": no committed weights to update (pp_commit_weights first)").c_str());
+    if (!w_cls || !b_cls || !w_box || !b_box || !w_dir || !b_dir) return pp_fail(ctx, PP_E_ARG, (who + ": null pointer").c_str());
+    if (mode == 0 && pp_effective_precision(ctx) != 0) // (the map below may be the _mp entry's: its own refusal would not be reached)
+        return pp_fail(ctx, PP_E_ARG, "head weights can be rewritten in place in the fp32 mode only (the committed plan packs the head in a 16-bit format)");
+    if (mode != 0)
+        if (int rc = pp_mp_mode_check(ctx, who_, mode)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     PP_HIP(hipSetDevice(ctx->device));
     trn_ws* w = workspace(ctx);
-    if (!w) return pp_fail(ctx, PP_E_STATE, "pp_update_head_weights: workspace allocation failed");
+    if (!w) return pp_fail(ctx, PP_E_STATE, (who + ": workspace allocation failed").c_str());
     if (int rc0 = pp_head_materialise(ctx, stream)) return rc0; // the last deferred pass gets its full tensors from the weights it ran with
+    const int na = ctx->cfg.num_anchor_per_loc;
+    bool is16 = false;
+    if (mode != 0)
+        if (int rc = pp_update_image16(ctx, pp_net_layer_index(ctx, 2, 0), w_cls, w_box, w_dir, na * HB_C, 7 * na * HB_C, 2 * na * HB_C, stream, &is16))
+            return rc;
     if (w->img_gen != ctx->commit_gen) { // first update after a commit: read the committed image's layout back (synchronous)
-        int rc = pp_net_head_image(ctx, &w->img);
+        int rc = 0;
+        if (is16) { // the biases alone: their maps do not depend on the tiling
+            w->img.wmap.clear();
+            w->img.w = nullptr;
+            rc = pp_net_head_bias(ctx, &w->img);
+        } else {
+            rc = pp_net_head_image(ctx, &w->img, mode != 0);
+        }
         if (rc) return rc;
         if ((rc = upload_map(ctx, w->img.wmap, &w->wmap)) || (rc = upload_map(ctx, w->img.bmap, &w->bmap)) ||
             (rc = upload_map(ctx, w->img.bpmap, &w->bpmap)))
             return rc;
         w->img_gen = ctx->commit_gen;
     }
-    const int na = ctx->cfg.num_anchor_per_loc;
     const int nw = (int)w->img.wmap.size(), nbm = (int)w->img.bmap.size(), nbp = (int)w->img.bpmap.size();
-    hipLaunchKernelGGL(k_gather3, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, w->img.w, w->wmap, nw, w_cls, w_box, w_dir, na * HB_C,
-                       7 * na * HB_C, 2 * na * HB_C);
+    if (nw)
+        hipLaunchKernelGGL(k_gather3, dim3(pp_div_up(nw, 256)), dim3(256), 0, stream, w->img.w, w->wmap, nw, w_cls, w_box, w_dir, na * HB_C,
+                           7 * na * HB_C, 2 * na * HB_C);
     hipLaunchKernelGGL(k_gather3, dim3(pp_div_up(nbm, 256)), dim3(256), 0, stream, w->img.bias, w->bmap, nbm, b_cls, b_box, b_dir, na, 7 * na,
                        2 * na);
     if (nbp)
@@ -514,4 +535,17 @@ extern "C" int pp_update_head_weights(pp_ctx* ctx, const float* w_cls, const flo
     }
     PP_HIP(hipGetLastError());
     return 0;
+}
+} // namespace
+
+extern "C" int pp_update_head_weights(pp_ctx* ctx, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
+                                      const float* w_dir, const float* b_dir, void* stream_)
+{
+    return head_update(ctx, "pp_update_head_weights", 0, w_cls, b_cls, w_box, b_box, w_dir, b_dir, stream_);
+}
+
+extern "C" int pp_update_head_weights_mp(pp_ctx* ctx, int mode, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
+                                         const float* w_dir, const float* b_dir, void* stream_)
+{
+    return head_update(ctx, "pp_update_head_weights_mp", mode, w_cls, b_cls, w_box, b_box, w_dir, b_dir, stream_);
 }

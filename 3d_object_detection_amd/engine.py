@@ -304,6 +304,19 @@ class Engine:
             _lib.check(self.lib.pp_commit_weights(self.ctx), self.ctx, "pp_commit_weights")
         self.weights_loaded = True
 
+    FORWARD_PRECISIONS = ("fp32", "bf16x3", "bf16", "fp16")  # forward_precision=...: "fp16s" keeps fp16 tensors, the taps are fp32
+
+    def _forward_mode(self, forward_precision, who):
+        """forward_precision of the taps and weight updates -> 0 (today's fp32 entry) or the mode of the _mp entry, which must be the
+        one the committed plan runs."""
+        if forward_precision not in self.FORWARD_PRECISIONS:
+            raise ValueError(f"{who}: forward_precision must be 'fp32', 'bf16x3', 'bf16' or 'fp16', got {forward_precision!r}")
+        mode = self.PRECISIONS[forward_precision]
+        if mode and self.effective_precision() != forward_precision:
+            raise RuntimeError(f"{who}: called with forward_precision='{forward_precision}', the committed plan runs "
+                               f"'{self.effective_precision()}'")
+        return mode
+
     # ------------------------------------------------------------------ stages (device tensors in/out)
     def _t(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
@@ -438,9 +451,11 @@ class Engine:
     HEAD_KEYS = ("heads.conv_cls.weight", "heads.conv_cls.bias", "heads.conv_box.weight", "heads.conv_box.bias",
                  "heads.conv_dir.weight", "heads.conv_dir.bias")
 
-    def update_head_weights(self, sd):
+    def update_head_weights(self, sd, forward_precision="fp32"):
         """pp_update_head_weights: {state_dict name: device tensor} of the six head tensors -> the committed head image, in place on the
-        current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
+        current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict).  forward_precision "bf16x3" |
+        "bf16" | "fp16": pp_update_head_weights_mp, for a plan committed in that mode (RuntimeError when it runs another)."""
+        mode = self._forward_mode(forward_precision, "update_head_weights")
         na = self.num_anchor_per_loc
         rows_of = {"cls": na, "box": 7 * na, "dir": 2 * na}
         args = {}
@@ -458,6 +473,10 @@ class Engine:
             self._on_device("update_head_weights", [(t, k)])
             args[k] = t
         with torch.cuda.device(self.device):
+            if mode:
+                _lib.check(self.lib.pp_update_head_weights_mp(self.ctx, mode, *[_ptr(args[k]) for k in self.HEAD_KEYS], _stream()), self.ctx,
+                           "pp_update_head_weights_mp")
+                return
             _lib.check(self.lib.pp_update_head_weights(self.ctx, *[_ptr(args[k]) for k in self.HEAD_KEYS], _stream()), self.ctx,
                        "pp_update_head_weights")
 
@@ -569,11 +588,17 @@ class Engine:
             raise ValueError(f"neck_backward_path: branch must be 0, 1 or 2, got {branch!r}")
         return self._backward_path("pp_neck_backward_path", grad_precision, int(branch), bn=bn)
 
-    def update_neck_weights(self, params):
+    def update_neck_weights(self, params, forward_precision="fp32"):
         """pp_update_neck_weights: {state_dict name: device tensor} of rpn.deconv{1,2,3}.0.weight -> the committed upsampler images, in
-        place on the current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict)."""
+        place on the current stream.  fp32 mode only (RuntimeError otherwise, and before the first load_state_dict).  forward_precision
+        "bf16x3" | "bf16" | "fp16": pp_update_neck_weights_mp, for a plan committed in that mode (RuntimeError when it runs another)."""
+        mode = self._forward_mode(forward_precision, "update_neck_weights")
         args = self._chk_weights("update_neck_weights", params, self.NECK_KEYS, [self.neck_shapes(b)[1] for b in range(3)])
         with torch.cuda.device(self.device):
+            if mode:
+                _lib.check(self.lib.pp_update_neck_weights_mp(self.ctx, mode, *[_ptr(t) for t in args], _stream()), self.ctx,
+                           "pp_update_neck_weights_mp")
+                return
             _lib.check(self.lib.pp_update_neck_weights(self.ctx, *[_ptr(t) for t in args], _stream()), self.ctx, "pp_update_neck_weights")
 
     # ------------------------------------------------------------------ Resnet unit backward (block_train.hip)
@@ -721,27 +746,39 @@ class Engine:
             out += [(cout, cin, 3, 3)] + [(cout, cout, 3, 3)] * n
         return out
 
-    def backbone_train_taps(self, canvas):
+    def backbone_train_taps(self, canvas, forward_precision="fp32"):
         """pp_backbone_train_taps: backbone_taps(canvas) plus, per level b, the inputs of the block's unit convolutions and the raw
         output of its strided convolution -> (rpn_out, (x1, x2, x3), (units0 [3,64,H,W], units1 [5,128,H/2,W/2], units2 [5,256,H/4,W/4]),
-        (z1 [1,64,H,W], z2, z3)); units_b[0] = relu(norm(z_b)).  fp32 mode only."""
+        (z1 [1,64,H,W], z2, z3)); units_b[0] = relu(norm(z_b)).  fp32 mode only.  forward_precision "bf16x3" | "bf16" | "fp16":
+        pp_backbone_train_taps_mp, the same pass on a plan committed in that mode (RuntimeError when it runs another); the taps are
+        the fp32 activations of that 16-bit forward."""
+        mode = self._forward_mode(forward_precision, "backbone_train_taps")
         out, taps = self._taps_out("backbone_train_taps", canvas)
         units = [self._level_t(n, b) for b, n in enumerate(self.RPN_UNITS)]
         z = [self._level_t(1, b) for b in range(3)]
         up = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in units])
         zp = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in z])
         with torch.cuda.device(self.device):
+            if mode:
+                _lib.check(self.lib.pp_backbone_train_taps_mp(self.ctx, mode, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]),
+                                                              up, zp, _stream()), self.ctx, "pp_backbone_train_taps_mp")
+                return out, tuple(taps), tuple(units), tuple(z)
             _lib.check(self.lib.pp_backbone_train_taps(self.ctx, _ptr(canvas), _ptr(out), _ptr(taps[0]), _ptr(taps[1]), _ptr(taps[2]), up, zp,
                                                        _stream()), self.ctx, "pp_backbone_train_taps")
         return out, tuple(taps), tuple(units), tuple(z)
 
-    def update_rpn_weights(self, params):
+    def update_rpn_weights(self, params, forward_precision="fp32"):
         """pp_update_rpn_weights: {state_dict name: device tensor} of RPN_CONV_KEYS -> the committed images of all sixteen 3 x 3
         convolutions and the sparse first convolution's image, in place on the current stream.  fp32 mode only (RuntimeError otherwise,
-        and before the first load_state_dict)."""
+        and before the first load_state_dict).  forward_precision "bf16x3" | "bf16" | "fp16": pp_update_rpn_weights_mp, the sixteen
+        images of a plan committed in that mode (RuntimeError when it runs another)."""
+        mode = self._forward_mode(forward_precision, "update_rpn_weights")
         args = self._chk_weights("update_rpn_weights", params, self.RPN_CONV_KEYS, self.rpn_conv_shapes())
         ptrs = (ctypes.c_void_p * 16)(*[t.data_ptr() for t in args])
         with torch.cuda.device(self.device):
+            if mode:
+                _lib.check(self.lib.pp_update_rpn_weights_mp(self.ctx, mode, ptrs, _stream()), self.ctx, "pp_update_rpn_weights_mp")
+                return
             _lib.check(self.lib.pp_update_rpn_weights(self.ctx, ptrs, _stream()), self.ctx, "pp_update_rpn_weights")
 
     # ------------------------------------------------------------------ the BatchNorm backbone with frozen statistics
@@ -1614,6 +1651,21 @@ class Engine:
         out = self._t((n.value,), torch.uint8)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.pp_weight_image(self.ctx, int(layer), _ptr(out), n.value, ctypes.byref(n), _stream()), self.ctx, "pp_weight_image")
+        return out
+
+    def debug_image16(self, layer, weights, out=None):
+        """Test hook (pp_debug_image16): the in-place writer of the 16-bit weight images on caller memory.  weights: the fp32 device
+        tensor of the layer's state_dict weight, or the head's (cls, box, dir) weights; out: a uint8 device tensor to write the image
+        into (allocated when None) -> out, of which the image's bytes are written.  RuntimeError when the layer keeps an fp32 image."""
+        ws = list(weights) if isinstance(weights, (tuple, list)) else [weights]
+        ws = [_chk(t.reshape(-1), torch.float32, (t.numel(),), "debug_image16: weight") for t in ws] + [None] * (3 - len(ws))
+        n = ctypes.c_size_t(0)
+        _lib.check(self.lib.pp_debug_image16(self.ctx, int(layer), None, None, None, None, 0, ctypes.byref(n), None), self.ctx, "pp_debug_image16")
+        if out is None:
+            out = self._t((n.value,), torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.pp_debug_image16(self.ctx, int(layer), *[_ptr(t) for t in ws], _ptr(out), out.numel(), ctypes.byref(n), _stream()),
+                       self.ctx, "pp_debug_image16")
         return out
 
     def layer_tilings(self):

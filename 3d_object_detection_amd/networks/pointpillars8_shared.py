@@ -43,7 +43,15 @@ train(..., grad_precision="bf16x3" | "bf16") runs the two gradient products of e
 or plain bf16 operands on the bf16 MFMA (pp_unit_backward_mp); the forward, the weights, every tensor handed around and the other
 backwards stay fp32, and "fp32", the default, is the fp32 path bit for bit.  On a BatchNorm network train(..., bn_stats=...,
 bn_grad_precision="bf16x3" | "bf16") does the same for the BatchNorm backwards (pp_*_backward_affine_mp / pp_*_backward_bn_mp), again
-for the units alone or, under grad_stages="rpn", the stages and upsamplers too."""
+for the units alone or, under grad_stages="rpn", the stages and upsamplers too.
+
+train(..., forward_precision="bf16x3" | "bf16" | "fp16") (InstanceNorm network) runs the training forward in that precision mode of
+the engine: the plan committed for inference in that mode, tapped by pp_backbone_train_taps_mp, so a network is fine-tuned in the
+arithmetic it is deployed in.  The taps are the fp32 activations of that forward, the backward is untouched (fp32 master weights,
+straight through the operand rounding) and combines freely with grad_precision, and after a step the 16-bit images are rewritten in
+place (pp_update_*_weights_mp).  The uploads pick their entry by the engine's effective precision in eval mode too, so weights stepped
+in fp32 reach a network switched with half() / precision() without a reload; only "fp16s" cannot take them.  The PFN is fp32 in
+every mode."""
 import time
 import types
 import typing
@@ -74,6 +82,7 @@ _RPN_EXTRA_KEYS = tuple(k for k in RPN_CONV_KEYS if k != STAGE3_KEY and k not in
 ALL_KEYS = PFN_KEYS + RPN_KEYS  # everything net.parameters() yields in the reference, in its state_dict order
 SCOPES = ("head", "neck", "block3", "stage3", "rpn", "all")
 GRAD_PRECISIONS = ("fp32", "bf16x3", "bf16")  # train(grad_precision=...): the operands of the unit backwards' gradient products
+FORWARD_PRECISIONS = Engine.FORWARD_PRECISIONS  # train(forward_precision=...): the precision mode the training forward runs in
 GRAD_STAGES = ("units", "rpn")  # train(grad_stages=...): the backwards that take grad_precision: the units alone, or the strided stages
                                 # and the upsamplers as well
 BN_STATS = ("frozen", "moving", "batch")  # train(bn_stats=...) on a BatchNorm network; "batch" is refused: "moving" is its name here
@@ -202,9 +211,14 @@ def rpn_block_backward(eng, modules, units, weights, g, grad_precision="fp32", n
 _W0 = (0, 4, 10)  # each level's strided convolution in RPN_CONV_KEYS; its unit convolutions follow it
 
 
-def _frame_taps(eng, first, canvas):
+def _frame_taps(eng, first, canvas, forward_precision="fp32"):
     """One frame's forward with the taps a backward from convolution `first` of RPN_CONV_KEYS on needs ->
-    (y, (x1, x2, x3), {level: unit inputs}, {level: z})."""
+    (y, (x1, x2, x3), {level: unit inputs}, {level: z}).  A 16-bit forward_precision has the one tapped pass of every level
+    (backbone_train_taps with the keyword) and keeps what `first` needs of it."""
+    if forward_precision != "fp32":
+        y, xs, units, zs = eng.backbone_train_taps(canvas, forward_precision=forward_precision)
+        levels = [b for b, _ in RPN_TABLE if first <= _W0[b] + 1]
+        return y, xs, {b: units[b] for b in levels}, {b: zs[b] for b in levels if first <= _W0[b]}
     if first == 0:
         y, xs, units, zs = eng.backbone_train_taps(canvas)
         return y, xs, dict(enumerate(units)), dict(enumerate(zs))
@@ -218,10 +232,10 @@ def _frame_taps(eng, first, canvas):
     return y, (x1, x2, x3), {2: units}, {}
 
 
-def _stacked_taps(eng, first, x):
+def _stacked_taps(eng, first, x, forward_precision="fp32"):
     """_frame_taps of every canvas of x, stacked over the frames -> [y, x1, x2, x3, the unit inputs of the levels `first` reaches, their
     z]: what a backward from `first` keeps, in the order _rpn_backward reads."""
-    outs = [_frame_taps(eng, first, c) for c in x]
+    outs = [_frame_taps(eng, first, c, forward_precision) for c in x]
     y = torch.cat([o[0] for o in outs])
     taps = [torch.cat([o[1][b] for o in outs]) for b in range(3)]
     units = [torch.stack([o[2][b][k] for o in outs]) for b in sorted(outs[0][2]) for k in range(sum(RPN_TABLE[b][1]))]
@@ -286,21 +300,29 @@ class _RpnFunction(torch.autograd.Function):
 
     The backward is _rpn_backward with InstanceNorm layers; a weight that does not require grad gets None.  Kept for the backward: y,
     x1..x3, the unit inputs and z of the levels `first` reaches, the weights, and for first = 0 the canvases, which then get level
-    0's dx when they require grad."""
+    0's dx when they require grad.
+
+    A 16-bit forward_precision (train(forward_precision=...)) may follow the weights as the last argument, a str: the forward then
+    taps the engine's 16-bit plan; without it the forward is fp32 and makes the calls it always made.  The backward is the same
+    either way."""
 
     @staticmethod
     def forward(ctx, eng, prec, first, x, *weights):
+        ctx.fwd = weights[-1] if weights and isinstance(weights[-1], str) else None
+        weights = weights[:-1] if ctx.fwd else weights
         ctx.eng, ctx.prec, ctx.first = eng, prec, first
-        kept = _stacked_taps(eng, first, x)
+        kept = _stacked_taps(eng, first, x, ctx.fwd or "fp32")
         ctx.save_for_backward(*([x] if first == 0 else []), *kept, *weights)
         return kept[0]
 
     @staticmethod
     def backward(ctx, gy):
         need, saved = ctx.needs_input_grad, ctx.saved_tensors
+        if ctx.fwd:
+            need = need[:-1]
         layers = [_Layer(w, n) for w, n in zip(saved[len(saved) + 4 - len(need):], need[4:])]  # the weights are the last tensors kept
         g, grads = _rpn_backward(ctx.eng, ctx.first, saved, layers, gy, need[3], ctx.prec)
-        return (None, None, None, g) + tuple(dw for dw, _, _ in grads)
+        return (None, None, None, g) + tuple(dw for dw, _, _ in grads) + ((None,) if ctx.fwd else ())
 
 
 class _RpnBnFunction(torch.autograd.Function):
@@ -408,6 +430,7 @@ class PointPillars:
     _norm = "instance"
     grad_precision = "fp32"
     grad_stages = "units"
+    forward_precision = "fp32"  # train(forward_precision=...): the precision mode the training forward runs in
     bn_grad_precision = "fp32"  # train(bn_grad_precision=...) while training a BatchNorm network
     bn_stats = None  # train(bn_stats=...) while training a BatchNorm network
     # read-only defaults for an object assembled without __init__ (no engine: the key-order and plan tests); __init__ and
@@ -446,7 +469,8 @@ class PointPillars:
     def eval(self):
         return self.train(False)
 
-    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None, grad_stages="units", bn_grad_precision="fp32"):
+    def train(self, mode=True, scope="head", grad_precision="fp32", bn_stats=None, grad_stages="units", bn_grad_precision="fp32",
+              forward_precision="fp32"):
         """Training mode: forward() accepts a batch of several frames and the tensors of `scope` require grad (SCOPES, from "head",
         the six head parameters, to "all", everything net.parameters() yields in the reference: the module docstring lists them);
         everything in front of the scope stays frozen.  Under "all" the PFN normalises with batch statistics and moves its running
@@ -471,7 +495,16 @@ class PointPillars:
         (momentum 0.01, unbiased variance) and num_batches_tracked, whether or not grad is enabled; the scope decides which tensors
         get gradients, exactly as under "frozen", and eval() folds the moved statistics into the engine before the next pass.  The
         keyword is explicit because "frozen" is not what torch's net.train() alone means; "batch" is refused: "moving" is its name
-        here.  Under "all" the PFN's BatchNorm1d behaves as on the InstanceNorm network whatever bn_stats says."""
+        here.  Under "all" the PFN's BatchNorm1d behaves as on the InstanceNorm network whatever bn_stats says.
+        forward_precision ("fp32" | "bf16x3" | "bf16" | "fp16", InstanceNorm network only, kept as net.forward_precision, "fp32" again
+        after eval()): the precision mode the training forward runs in.  A 16-bit value switches the engine to that mode
+        (precision(mode)) if it is not there; the training forward then runs while the engine's effective precision equals it and
+        raises RuntimeError otherwise (after float(), say).  The taps are fp32, the backward and the master weights are untouched, and
+        grad_precision / grad_stages combine freely with it; the PFN is fp32 in every mode."""
+        if forward_precision not in FORWARD_PRECISIONS:
+            raise ValueError(f"train: forward_precision must be 'fp32', 'bf16x3', 'bf16' or 'fp16', got {forward_precision!r}")
+        if forward_precision != "fp32" and self._norm != "instance":
+            raise ValueError("train: forward_precision is for the InstanceNorm network; a BatchNorm network trains with an fp32 forward")
         if grad_precision not in GRAD_PRECISIONS:
             raise ValueError(f"train: grad_precision must be 'fp32', 'bf16x3' or 'bf16', got {grad_precision!r}")
         if grad_stages not in GRAD_STAGES:
@@ -503,6 +536,9 @@ class PointPillars:
         self._scope = scope if self.training else "head"
         self.grad_precision = grad_precision if self.training else "fp32"
         self.grad_stages = grad_stages if self.training else "units"
+        self.forward_precision = forward_precision if self.training else "fp32"
+        if self.forward_precision != "fp32" and self._eng.effective_precision() != self.forward_precision:
+            self.precision(self.forward_precision)
         self.bn_grad_precision = bn_grad_precision if self.training else "fp32"
         self.bn_stats = bn_stats if self.training else None
         trained = self._groups(self._scope) if self.training else ()
@@ -567,10 +603,27 @@ class PointPillars:
     def _sync_group(self, attr):
         """When the group moved, rewrite the engine's committed image of it in place, with the groups the same call carries."""
         if self._moved(attr):
-            gone_up = (attr,) + _GROUPS[attr].covers
+            convs = ("_rpn", "_down", "_block")  # in a 16-bit mode the sixteen convolutions always go up together (_upload)
+            gone_up = convs if attr in convs and self._eng.effective_precision() not in (None, "fp32") else (attr,) + _GROUPS[attr].covers
             self._trained = self._trained | {a for a in gone_up if self._moved(a)}
-            _GROUPS[attr].upload(self)
+            self._upload(attr)
             self._mark_uploaded(gone_up)
+
+    def _upload(self, attr):
+        """The engine call that writes group attr's current values into the committed plan, chosen by the engine's effective
+        precision: the group's own fp32 entry, or in a 16-bit mode the _mp entry of its family (there the sixteen convolutions always
+        go up together).  The PFN is fp32 in every mode.  "fp16s" has no in-place writer."""
+        mode = self._eng.effective_precision()
+        if attr == "_pfn" or mode in (None, "fp32"):
+            return _GROUPS[attr].upload(self)
+        if mode not in FORWARD_PRECISIONS:
+            raise RuntimeError(f"the network runs '{mode}', whose packed weights cannot be rewritten in place: load_state_dict(net.state_dict()) "
+                               "again to commit the trained weights in this mode")
+        if attr == "_params":
+            return self._eng.update_head_weights(self._params, forward_precision=mode)
+        if attr == "_neck":
+            return self._eng.update_neck_weights(self._neck, forward_precision=mode)
+        return self._eng.update_rpn_weights({**self._rpn, **self._down, **self._block}, forward_precision=mode)
 
     def _sync_head(self):
         """An optimizer stepped the head: rewrite the engine's packed head in place."""
@@ -658,6 +711,14 @@ class PointPillars:
             torch.cuda.synchronize()
         return time.time()
 
+    def _mode_error(self, what, why):
+        """The message of a training forward whose engine does not run net.forward_precision."""
+        runs = self._eng.effective_precision()
+        if self.forward_precision == "fp32":
+            return f"{what} needs the fp32 precision mode: the network runs '{runs}' ({why}); call float()"
+        return (f"{what} under train(forward_precision='{self.forward_precision}') needs the engine in that mode: the network runs '{runs}'; "
+                f"call precision('{self.forward_precision}'), or train() again")
+
     def _pfn_training(self):
         return self.training and self._scope == "all"
 
@@ -665,15 +726,15 @@ class PointPillars:
         """PointNet in train mode and the scatter on a batch: frames = [(voxels [n,T,4], coors [n,3], num_points_per_voxel [n]), ...],
         at most max_batch of them -> canvases [nb,64,gx,gy].  BatchNorm1d normalises with the statistics of the pillars of all frames
         together and the running statistics move (momentum 0.1, unbiased variance), whether or not grad is enabled.  Differentiable
-        with respect to PFN_KEYS when they require grad (train(scope="all")).  Needs the fp32 precision mode."""
+        with respect to PFN_KEYS when they require grad (train(scope="all")).  The PFN itself is fp32 in every mode; the engine must run
+        net.forward_precision (the fp32 mode unless train(forward_precision=...) said otherwise)."""
         eng = self._eng
         if not 1 <= len(frames) <= eng.max_batch:
             raise ValueError(f"pfn_train: {len(frames)} frames in the batch, max_batch is {eng.max_batch}")
         if len(self._pfn) != 3 or len(self._pfn_stats) != 2:
             raise RuntimeError("pfn_train: the state_dict holds no pillar feature net")
-        if eng.effective_precision() != "fp32":
-            raise RuntimeError(f"PFN training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
-                               "(the backward of the RPN behind it is fp32); call float()")
+        if eng.effective_precision() != self.forward_precision:
+            raise RuntimeError(self._mode_error("PFN training", "the backward of the RPN behind it is fp32"))
         voxels = torch.cat([f[0] for f in frames]).contiguous()
         coors = torch.cat([f[1] for f in frames]).contiguous()
         npts = torch.cat([f[2] for f in frames]).contiguous()
@@ -776,7 +837,7 @@ class PointPillars:
         bit.  Differentiable with respect to the three upsampler weights when they require grad (train(scope="neck")) and to block
         3's five unit weights (train(scope="block3")) and its stride-2 weight (train(scope="stage3")); under train(scope="rpn") to all
         sixteen convolutions, and then also to x itself when it requires grad (the level-0 dx: where the PFN backward starts).
-        Gradients are fp32 and need the fp32 precision mode."""
+        Gradients are fp32; the engine must run net.forward_precision (the fp32 mode unless train(forward_precision=...) said otherwise)."""
         eng = self._eng
         gx, gy = int(eng.grid_size[0]), int(eng.grid_size[1])
         if not isinstance(x, torch.Tensor) or x.numel() == 0 or x.numel() % (64 * gx * gy):
@@ -788,9 +849,8 @@ class PointPillars:
         moving = self.training and self.bn_stats == "moving"
         if not (torch.is_grad_enabled() and self._backbone_requires_grad()) and not moving:
             return torch.cat([eng.backbone(c) for c in x])
-        if eng.effective_precision() != "fp32":
-            raise RuntimeError(f"neck training needs the fp32 precision mode: the network runs '{eng.effective_precision()}' "
-                               "(gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place); call float()")
+        if eng.effective_precision() != self.forward_precision:
+            raise RuntimeError(self._mode_error("neck training", "gradients are fp32 and the packed 16-bit upsampler weights cannot be updated in place"))
         # the depth of the backward: the first convolution of the frontmost group that holds a parameter requiring grad
         req = lambda group: any(p.requires_grad for p in group.values())  # noqa: E731
         first = 0 if req(self._rpn) else _W0[2] if req(self._down) else _W0[2] + 1 if req(self._block) else len(RPN_CONV_KEYS)
@@ -807,7 +867,9 @@ class PointPillars:
                 return self._rpn_train_moving(first, x, tensors)
             stats = [tuple(self._bn_run[f"{Engine.bn_prefix(k)}.{s}"] for s in Engine.BN_FIELDS[2:]) for k in layers]
             return _RpnBnFunction.apply(eng, first, stats, x, *tensors)
-        return _RpnFunction.apply(eng, (self.grad_precision, self.grad_precision if self.grad_stages == "rpn" else "fp32"), first, x, *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS])
+        fwd = () if self.forward_precision == "fp32" else (self.forward_precision,)  # rides behind the weights; an fp32 run makes the calls it made
+        return _RpnFunction.apply(eng, (self.grad_precision, self.grad_precision if self.grad_stages == "rpn" else "fp32"), first, x,
+                                  *[every[k] for k in RPN_CONV_KEYS[first:]], *[self._neck[k] for k in NECK_KEYS], *fwd)
 
     def _rpn_train_moving(self, first, x, tensors):
         """rpn_train under bn_stats="moving": one lock-step pass with batch statistics, then BatchNorm2d's update of the running
@@ -835,14 +897,13 @@ class PointPillars:
 
     def heads(self, x):
         """SharedHead.forward on x [B,320,H,W], 1 <= B <= max_batch.  Differentiable with respect to x and the head parameters when
-        one of them requires grad (train() for the parameters); gradients are fp32 and need the fp32 precision mode."""
+        one of them requires grad (train() for the parameters); gradients are fp32, and the engine must run net.forward_precision."""
         x = x.contiguous()
         params = list(self._params.values())
         self._sync_head()
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            if self._eng.effective_precision() != "fp32":
-                raise RuntimeError(f"head training needs the fp32 precision mode: the network runs '{self._eng.effective_precision()}' "
-                                   "(gradients are fp32 and the packed 16-bit head weights cannot be updated in place); call float()")
+            if self._eng.effective_precision() != self.forward_precision:
+                raise RuntimeError(self._mode_error("head training", "gradients are fp32 and the packed 16-bit head weights cannot be updated in place"))
             if x.dim() != 4:
                 x = x.reshape(-1, 320, self._eng.H, self._eng.W)
             cls, box, dr = _HeadFunction.apply(self._eng, x, *params)

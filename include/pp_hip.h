@@ -471,6 +471,38 @@ int pp_backbone_train_taps(pp_ctx* ctx, const float* canvas, float* rpn_out, flo
  * are NOT changed.  fp32 mode only: PP_E_ARG when pp_effective_precision != 0, and before the first commit. */
 int pp_update_rpn_weights(pp_ctx* ctx, const float* const* w /* 16 */, void* stream);
 
+/* ---- the training forward on 16-bit MFMA operands: the _mp forms of the taps and of the three weight updates (conv_run.hip,
+ *      image16.hip, block_train.hip, neck_train.hip, train.hip) ----
+ * mode is 1 (bf16x3), 2 (bf16) or 3 (fp16), the numbering of pp_set_precision.  Each entry returns PP_E_ARG unless
+ * pp_effective_precision(ctx) == mode, so a plan that keeps fp16 tensors (4, fp16s) is refused throughout: the taps are fp32 tensors.
+ * The fp32 entries above keep refusing every plan but an fp32 one.
+ * pp_backbone_train_taps_mp: pp_backbone_train_taps on that plan.  In modes 1 - 3 the level buffers are fp32 and the copy hooks sit
+ * behind the launches whatever tiling runs, so the taps are the fp32 activations of the 16-bit forward (the norms and ReLUs are fp32
+ * in every mode); rpn_out, x1, x2, x3 match pp_backbone bit for bit, and a pass with no hook armed is bit for bit what it was.
+ * The three updates rewrite the committed images in place on `stream` from fp32 DEVICE tensors, as their fp32 forms do.  A 16-bit image
+ * holds no transform: it is a permutation of the weight elements, each rounded to nearest even to bf16 (modes 1, 2) or fp16 (mode 3),
+ * with a second image of the residuals bf16(x - hi) where the packer writes one; the element map -- which element, which part, or
+ * padding -- is read back from the packers once per commit (three passes of base-128 digits; synchronous, on the first update after a
+ * commit), and every image equals that of a fresh commit of the same values in that mode bit for bit.  A layer whose shape no 16-bit
+ * tiling takes keeps its fp32 tiling in a 16-bit plan (pp_layer_tilings says so) and its fp32 writer.
+ * pp_update_rpn_weights_mp: the sixteen convolutions; the sparse first convolution is fp32 only and keeps no image these modes read
+ * (a return to fp32 commits again).  pp_update_neck_weights_mp: the three upsamplers.  pp_update_head_weights_mp: the head; the bias
+ * stays fp32, in natural order and, where the plan keeps that copy, in head_tile_row order; the natural-order copy of the weights that
+ * pp_head_backward's dX product reads is refreshed too.  The host copies of pp_load_weights are NOT changed. */
+int pp_backbone_train_taps_mp(pp_ctx* ctx, int mode, const float* canvas, float* rpn_out, float* x1, float* x2, float* x3,
+                              float* const* units, float* const* z, void* stream);
+int pp_update_rpn_weights_mp(pp_ctx* ctx, int mode, const float* const* w /* 16 */, void* stream);
+int pp_update_neck_weights_mp(pp_ctx* ctx, int mode, const float* w1, const float* w2, const float* w3, void* stream);
+int pp_update_head_weights_mp(pp_ctx* ctx, int mode, const float* w_cls, const float* b_cls, const float* w_box, const float* b_box,
+                              const float* w_dir, const float* b_dir, void* stream);
+/* Test hook: the in-place writer of the 16-bit images on caller memory.  The image of layer `layer` (0 .. 19 of pp_layer_tilings) of the
+ * committed plan is written into dst (cap bytes) from the fp32 DEVICE tensor w0 (a convolution's or an upsampler's state_dict weight;
+ * the head: w0 | w1 | w2 = cls | box | dir, NULL otherwise) on `stream`; *bytes gets the image's size, and dst = NULL only queries it.
+ * Writes exactly *bytes bytes of dst and nothing else; reads the plan and its cached element map.  PP_E_ARG when the layer keeps an fp32
+ * image in the committed plan; PP_E_STATE before pp_commit_weights. */
+int pp_debug_image16(pp_ctx* ctx, int layer, const float* w0, const float* w1, const float* w2, void* dst, size_t cap, size_t* bytes,
+                     void* stream);
+
 /* ---- fine-tuning the BatchNorm backbone with frozen statistics (block_train.hip, down_train.hip, neck_train.hip, conv_plan.hip) ----
  * Every BatchNorm2d(eps 1e-3) of the RPN in eval mode is a per-channel affine, norm(v)_c = scale_c v + shift_c with
  * scale = gamma / sqrt(running_var + 1e-3), shift = beta - running_mean scale: the fold of pp_commit_weights, which the forward applies as
