@@ -20,9 +20,10 @@ constexpr double SL1_SIGMA2 = 9.0;            // smooth-L1 sigma^2
 
 struct trn_ws {
     int32_t* npos = nullptr;   // [max_batch] positives per frame of the running pp_target_loss_grad
-    float* w_nat = nullptr;    // [96][320] head weights in natural row order (cls | box | dir), rows >= 10 na zero
+    float* w_nat = nullptr;    // [rows_padded(na)][320] head weights in natural row order (cls | box | dir), rows >= 10 na zero
     float* part = nullptr;     // dW / db partials of pp_head_backward
     size_t part_elems = 0;
+    bool dx_wide_lds = false;  // k_head_dx_wide has been given its dynamic LDS size on this device
     uint64_t w_gen = 0;        // ctx->commit_gen w_nat belongs to (0: none)
     // pp_update_head_weights: index maps of the committed head image (pp_net_head_image)
     uint64_t img_gen = 0;
@@ -30,13 +31,18 @@ struct trn_ws {
     int32_t *wmap = nullptr, *bmap = nullptr, *bpmap = nullptr;
 };
 
+// Rows of the head backward's GEMMs: 96 up to 9 anchors per location (the kernels written for that count), above that 10 na rounded
+// up to the 16 rows of an MFMA tile (k_head_dw_wide / k_head_dx_wide).
+constexpr int HB_MAX_NA = 24; // 12 classes (PP_MAX_CLASSES) x 1 size x 2 rotations
+inline int rows_padded(int na) { return 10 * na <= 96 ? 96 : (10 * na + 15) / 16 * 16; }
+
 trn_ws* workspace(pp_ctx* ctx)
 {
     if (ctx->trn) return (trn_ws*)ctx->trn;
     trn_ws* w = new trn_ws();
     ctx->trn = w;
     if (hipMalloc((void**)&w->npos, (size_t)ctx->max_batch * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&w->w_nat, (size_t)96 * 320 * sizeof(float)) != hipSuccess) {
+        hipMalloc((void**)&w->w_nat, (size_t)rows_padded(ctx->cfg.num_anchor_per_loc) * 320 * sizeof(float)) != hipSuccess) {
         pp_train_destroy(ctx);
         return nullptr;
     }
@@ -277,7 +283,8 @@ __global__ void __launch_bounds__(256, 2) k_head_dw(const float* __restrict__ X,
 
 // partials -> dW / db in state_dict order (the natural row order IS state_dict order: cls rows, then box a * 7 + k, then dir a * 2 + k),
 // summed over workgroups in index order: frame-major, pixel ranges ascending
-__global__ void __launch_bounds__(256) k_head_dw_reduce(const float* __restrict__ part, int G, int na, float* __restrict__ dw_cls,
+// (rows: the padded row count the partials were written with, 96 or rows_padded(na))
+__global__ void __launch_bounds__(256) k_head_dw_reduce(const float* __restrict__ part, int G, int na, int rows, float* __restrict__ dw_cls,
                                                         float* __restrict__ dw_box, float* __restrict__ dw_dir, float* __restrict__ db_cls,
                                                         float* __restrict__ db_box, float* __restrict__ db_dir)
 {
@@ -286,9 +293,10 @@ __global__ void __launch_bounds__(256) k_head_dw_reduce(const float* __restrict_
     if (i >= R * HB_C + R) return;
     const bool bias = i >= R * HB_C;
     const int r = bias ? i - R * HB_C : i / HB_C, c = bias ? 0 : i - r * HB_C;
-    const float* p = part + (bias ? (size_t)HB_ROWS * HB_C + r : (size_t)i);
+    const float* p = part + (bias ? (size_t)rows * HB_C + r : (size_t)i);
+    const size_t stride = (size_t)rows * (HB_C + 1);
     double s = 0.0; // up to ~512 partials, for db mostly of one sign: summed in double, rounded once
-    for (int g = 0; g < G; ++g) s += (double)p[(size_t)g * PART_STRIDE];
+    for (int g = 0; g < G; ++g) s += (double)p[(size_t)g * stride];
     const int w = bias ? 1 : HB_C;
     float* dst = r < na ? (bias ? db_cls : dw_cls) + (size_t)r * w : r < 8 * na ? (bias ? db_box : dw_box) + (size_t)(r - na) * w
                                                                              : (bias ? db_dir : dw_dir) + (size_t)(r - 8 * na) * w;
@@ -343,6 +351,203 @@ __global__ void __launch_bounds__(256, 2) k_head_dx(const float* __restrict__ Wn
 }
 
 // ------------------------------------------------------------------------------------------
+// head backward, more than 96 rows (10 .. 24 anchors per location)
+// ------------------------------------------------------------------------------------------
+// The GEMM rows are 10 na rounded up to 16 (rows_padded).  Neither 96-row kernel's register plan stretches to them at two waves per
+// SIMD (13 x 5 accumulator tiles, or 5 x 52 W^T fragments, are 260 registers), so each splits ONE dimension over the grid and keeps
+// the plan of its 96-row form: k_head_dw_wide the rows, k_head_dx_wide the channels.  The split is the fastest-varying part of
+// blockIdx.x, so the workgroups that read the same pixels are dispatched together and the re-read comes from the caches.
+
+// load_dy_tile for a window of rows: rows [r0, r1) of the natural order go to dYs[(row - r0) * LD + pixel]; r1 <= 10 na.  The
+// same two paths: 16-byte loads of an anchor's contiguous box / dir span for a full, aligned tile, single floats otherwise.  A span
+// is read whole where only some of its rows fall in the window (at most two anchors of box and of dir per window).
+template <int LD>
+__device__ __forceinline__ void load_dy_rows(float* __restrict__ dYs, const float* __restrict__ dcls, const float* __restrict__ dbox,
+                                             const float* __restrict__ ddir, int na, int P, int p0, int np, bool full, int r0, int r1)
+{
+    const int tid = threadIdx.x;
+    const unsigned nr = (unsigned)(r1 - r0);
+    // anchors whose cls / box / dir rows meet the window
+    const int c0 = r0 < na ? r0 : na, c1 = r1 < na ? r1 : na;
+    const int b0 = r0 > na ? ((r0 - na) / 7 < na ? (r0 - na) / 7 : na) : 0, b1 = r1 > na ? ((r1 - na + 6) / 7 < na ? (r1 - na + 6) / 7 : na) : 0;
+    const int d0 = r0 > 8 * na ? (r0 - 8 * na) / 2 : 0, d1 = r1 > 8 * na ? (r1 - 8 * na + 1) / 2 : 0;
+    for (int i = tid; i < (c1 - c0) * HB_PX; i += 256) {
+        const int a = c0 + (i >> 6), px = i & 63;
+        dYs[(a - r0) * LD + px] = px < np ? dcls[(size_t)a * P + p0 + px] : 0.f;
+    }
+    if (full) {
+        for (int i = tid; i < (b1 - b0) * (HB_PX * 7 / 4); i += 256) {
+            const int a = b0 + i / (HB_PX * 7 / 4), q = i - (a - b0) * (HB_PX * 7 / 4);
+            const float4 v = reinterpret_cast<const float4*>(dbox + ((size_t)a * P + p0) * 7)[q];
+            const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int e = 4 * q + j, px = e / 7, k = e - 7 * px;
+                const unsigned row = (unsigned)(na + 7 * a + k - r0);
+                if (row < nr) dYs[row * LD + px] = e4[j];
+            }
+        }
+        for (int i = tid; i < (d1 - d0) * (HB_PX * 2 / 4); i += 256) {
+            const int a = d0 + i / (HB_PX * 2 / 4), q = i - (a - d0) * (HB_PX * 2 / 4);
+            const float4 v = reinterpret_cast<const float4*>(ddir + ((size_t)a * P + p0) * 2)[q];
+            const unsigned row = (unsigned)(8 * na + 2 * a - r0);
+            if (row < nr) { dYs[row * LD + 2 * q] = v.x; dYs[row * LD + 2 * q + 1] = v.z; }
+            if (row + 1 < nr) { dYs[(row + 1) * LD + 2 * q] = v.y; dYs[(row + 1) * LD + 2 * q + 1] = v.w; }
+        }
+    } else {
+        for (int i = tid; i < (b1 - b0) * HB_PX * 7; i += 256) {
+            const int a = b0 + i / (HB_PX * 7), e = i - (a - b0) * (HB_PX * 7), px = e / 7, k = e - 7 * px;
+            const unsigned row = (unsigned)(na + 7 * a + k - r0);
+            if (row < nr) dYs[row * LD + px] = px < np ? dbox[((size_t)a * P + p0) * 7 + e] : 0.f;
+        }
+        for (int i = tid; i < (d1 - d0) * HB_PX * 2; i += 256) {
+            const int a = d0 + i / (HB_PX * 2), e = i - (a - d0) * (HB_PX * 2), px = e >> 1, k = e & 1;
+            const unsigned row = (unsigned)(8 * na + 2 * a + k - r0);
+            if (row < nr) dYs[row * LD + px] = px < np ? ddir[((size_t)a * P + p0) * 2 + e] : 0.f;
+        }
+    }
+}
+
+// k_head_dw with the rows split into nrb = ceil(tiles / 6) blocks of row tiles, as evenly as they go (13 tiles: 5 | 4 | 4): a
+// workgroup owns one block of one pixel range, brings only that block's rows of dY into LDS and reads the range's X again.  The
+// accumulators are the 6 x 5 tiles of k_head_dw; a block with fewer row tiles skips the others (wave-uniform), so the MFMAs executed
+// are those of the padded row count.  Partials: part[frame][pixel range][rows * 320 + rows], every block writing its own rows; rows
+// 10 na .. rows - 1 are zero in LDS and k_head_dw_reduce never reads what they give.
+__global__ void __launch_bounds__(256, 2) k_head_dw_wide(const float* __restrict__ X, const float* __restrict__ dcls, const float* __restrict__ dbox,
+                                                         const float* __restrict__ ddir, int na, int P, int tiles_per_wg, int ntiles, int nrb,
+                                                         int rows, float* __restrict__ part, int vec)
+{
+    __shared__ __attribute__((aligned(16))) float dYs[HB_ROWS * DW_LD];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int f = blockIdx.y, rbk = blockIdx.x % nrb, range = blockIdx.x / nrb, nranges = gridDim.x / nrb;
+    const int base = (rows / 16) / nrb, rem = (rows / 16) % nrb;
+    const int nrt = base + (rbk < rem), r0 = 16 * (rbk * base + (rbk < rem ? rbk : rem)); // nrt <= 6 row tiles from row r0
+    const int r1 = r0 + 16 * nrt < 10 * na ? r0 + 16 * nrt : 10 * na;
+    const size_t A = (size_t)na * P;
+    const float* Xf = X + (size_t)f * HB_C * P;
+    dcls += f * A; dbox += f * A * 7; ddir += f * A * 2;
+    f32x4 acc[6][5];
+#pragma unroll
+    for (int rb = 0; rb < 6; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 5; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    double dbacc = 0.0;
+    for (int i = tid; i < HB_ROWS * DW_LD; i += 256) dYs[i] = 0.f;
+    const int t0 = range * tiles_per_wg, t1 = t0 + tiles_per_wg < ntiles ? t0 + tiles_per_wg : ntiles;
+    for (int t = t0; t < t1; ++t) {
+        const int p0 = t * HB_PX, np = P - p0 < HB_PX ? P - p0 : HB_PX;
+        const bool full = vec && np == HB_PX;
+        __syncthreads();
+        load_dy_rows<DW_LD>(dYs, dcls, dbox, ddir, na, P, p0, np, full, r0, r1);
+        __syncthreads();
+        if (tid < 16 * nrt) {
+            double s = 0.0;
+            for (int px = 0; px < HB_PX; ++px) s += dYs[tid * DW_LD + px];
+            dbacc += s;
+        }
+#pragma unroll 1
+        for (int g = 0; g < 4; ++g) {
+            const int pg = 16 * g + 4 * q;
+            float xb[5][4];
+#pragma unroll
+            for (int cb = 0; cb < 5; ++cb) {
+                const float* px_ = Xf + (size_t)(80 * wave + 16 * cb + l16) * P + p0 + pg;
+                if (full) {
+                    const float4 v = *reinterpret_cast<const float4*>(px_);
+                    xb[cb][0] = v.x; xb[cb][1] = v.y; xb[cb][2] = v.z; xb[cb][3] = v.w;
+                } else {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) xb[cb][s] = pg + s < np ? px_[s] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int rb = 0; rb < 6; ++rb) {
+                if (rb < nrt) {
+                    const float4 v = *reinterpret_cast<const float4*>(&dYs[(16 * rb + l16) * DW_LD + pg]);
+                    const float ya[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int cb = 0; cb < 5; ++cb)
+                            acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[s], xb[cb][s], acc[rb][cb], 0, 0, 0);
+                }
+            }
+        }
+    }
+    float* pw = part + ((size_t)f * nranges + range) * ((size_t)rows * (HB_C + 1));
+#pragma unroll
+    for (int rb = 0; rb < 6; ++rb)
+        if (rb < nrt)
+#pragma unroll
+            for (int cb = 0; cb < 5; ++cb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pw[(size_t)(r0 + 16 * rb + 4 * q + i) * HB_C + 80 * wave + 16 * cb + l16] = acc[rb][cb][i];
+    if (tid < 16 * nrt) pw[(size_t)rows * HB_C + r0 + tid] = (float)dbacc;
+}
+
+// k_head_dx with the 320 channels split over DXW_GROUPS workgroups per pixel range: a wave keeps the W^T fragments of two 16-channel
+// blocks for every row (2 x rows / 4 <= 120 registers, loaded once per workgroup), the whole dY tile [rows][64] sits in LDS (dynamic,
+// rows * DX_LD floats: 77 KB at 24 anchors) and is brought in once per group.  Twenty channel blocks over 3 x 4 x 2 slots: the last
+// group's waves 2 and 3 have none and only help to load the tile.
+constexpr int DXW_CB = 2;                                          // 16-channel blocks per wave
+constexpr int DXW_GROUPS = (HB_C / 16 + 4 * DXW_CB - 1) / (4 * DXW_CB);
+constexpr int DXW_KB = (10 * HB_MAX_NA + 15) / 16;                 // blocks of 16 rows (four k-steps) at the cap
+
+__global__ void __launch_bounds__(256, 2) k_head_dx_wide(const float* __restrict__ Wn, const float* __restrict__ dcls, const float* __restrict__ dbox,
+                                                         const float* __restrict__ ddir, int na, int P, int tiles_per_wg, int ntiles, int rows,
+                                                         float* __restrict__ dX, int vec)
+{
+    extern __shared__ __attribute__((aligned(16))) float dYw[]; // [rows][DX_LD]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, q = lane >> 4;
+    const int f = blockIdx.y, grp = blockIdx.x % DXW_GROUPS, range = blockIdx.x / DXW_GROUPS;
+    const int nkb = rows / 16, cb0 = 4 * DXW_CB * grp + DXW_CB * wave; // this wave's channel blocks: cb0 + j where that is < 20
+    const size_t A = (size_t)na * P;
+    float* dXf = dX + (size_t)f * HB_C * P;
+    dcls += f * A; dbox += f * A * 7; ddir += f * A * 2;
+    float wa[DXW_CB][DXW_KB][4];
+#pragma unroll
+    for (int j = 0; j < DXW_CB; ++j)
+#pragma unroll
+        for (int kb = 0; kb < DXW_KB; ++kb)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                wa[j][kb][s] = kb < nkb && cb0 + j < HB_C / 16 ? Wn[(size_t)(16 * kb + 4 * s + q) * HB_C + 16 * (cb0 + j) + l16] : 0.f;
+    for (int i = tid; i < rows * DX_LD; i += 256) dYw[i] = 0.f;
+    const int t0 = range * tiles_per_wg, t1 = t0 + tiles_per_wg < ntiles ? t0 + tiles_per_wg : ntiles;
+    for (int t = t0; t < t1; ++t) {
+        const int p0 = t * HB_PX, np = P - p0 < HB_PX ? P - p0 : HB_PX;
+        __syncthreads();
+        load_dy_rows<DX_LD>(dYw, dcls, dbox, ddir, na, P, p0, np, vec && np == HB_PX, 0, 10 * na);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < DXW_CB; ++j) {
+            if (cb0 + j >= HB_C / 16) continue;
+            f32x4 acc[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < DXW_KB; ++kb) {
+                if (kb < nkb) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt)
+                            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[j][kb][s], dYw[(16 * kb + 4 * s + q) * DX_LD + 16 * nt + l16], acc[nt], 0,
+                                                                           0, 0);
+                }
+            }
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int px = 16 * nt + l16;
+                    if (px < np) dXf[(size_t)(16 * (cb0 + j) + 4 * q + i) * P + p0 + px] = acc[nt][i];
+                }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // in-place rewrite of the head's packed image
 // ------------------------------------------------------------------------------------------
 // dst[i] = element map[i] of the concatenation src0 | src1 | src2 (n0, n1 elements in the first two), 0 where map[i] < 0
@@ -371,7 +576,7 @@ int refresh_w_nat(pp_ctx* ctx, trn_ws* w)
     const int na = ctx->cfg.num_anchor_per_loc;
     const char* names[3] = {"heads.conv_cls.weight", "heads.conv_box.weight", "heads.conv_dir.weight"};
     const int cnt[3] = {na, 7 * na, 2 * na};
-    std::vector<float> h((size_t)HB_ROWS * HB_C, 0.f);
+    std::vector<float> h((size_t)rows_padded(na) * HB_C, 0.f);
     size_t r0 = 0;
     for (int k = 0; k < 3; ++k) {
         auto it = ctx->host_w.find(names[k]);
@@ -445,7 +650,9 @@ extern "C" int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* 
         return pp_fail(ctx, PP_E_ARG, "pp_head_backward: null pointer");
     if (nb < 1 || nb > ctx->max_batch) return pp_fail(ctx, PP_E_ARG, "pp_head_backward: nb must be 1 .. max_batch");
     const int na = ctx->cfg.num_anchor_per_loc, P = ctx->H * ctx->W;
-    if (10 * na > HB_ROWS) return pp_fail(ctx, PP_E_ARG, "pp_head_backward: more than 9 anchors per location");
+    if (na > HB_MAX_NA) return pp_fail(ctx, PP_E_ARG, "pp_head_backward: more than 24 anchors per location");
+    const bool wide = 10 * na > HB_ROWS;
+    const int rows = rows_padded(na);
     hipStream_t stream = (hipStream_t)stream_;
     PP_HIP(hipSetDevice(ctx->device));
     trn_ws* w = workspace(ctx);
@@ -453,7 +660,7 @@ extern "C" int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* 
     const int ntiles = pp_div_up(P, HB_PX);
     int wgs = 0, tpw = 0;
     pixel_ranges(nb, ntiles, &wgs, &tpw);
-    const size_t need = (size_t)nb * wgs * PART_STRIDE;
+    const size_t need = (size_t)nb * wgs * rows * (HB_C + 1); // PART_STRIDE of either dW kernel
     if (need > w->part_elems) {
         PP_HIP(hipStreamSynchronize(stream)); // a running reduce may still read the old buffer
         if (w->part) (void)hipFree(w->part);
@@ -462,13 +669,30 @@ extern "C" int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* 
         w->part_elems = need;
     }
     const int vec = P % 4 == 0 && aligned16(rpn_out) && aligned16(dbox) && aligned16(ddir);
-    hipLaunchKernelGGL(k_head_dw, dim3(wgs, nb), dim3(256), 0, stream, rpn_out, dcls, dbox, ddir, na, P, tpw, ntiles, w->part, vec);
-    hipLaunchKernelGGL(k_head_dw_reduce, dim3(pp_div_up(10 * na * (HB_C + 1), 256)), dim3(256), 0, stream, w->part, nb * wgs, na, dw_cls, dw_box,
-                       dw_dir, db_cls, db_box, db_dir);
+    if (wide) {
+        const int nrb = pp_div_up(rows / 16, 6); // row blocks of at most six 16-row tiles
+        hipLaunchKernelGGL(k_head_dw_wide, dim3(wgs * nrb, nb), dim3(256), 0, stream, rpn_out, dcls, dbox, ddir, na, P, tpw, ntiles, nrb, rows,
+                           w->part, vec);
+    } else {
+        hipLaunchKernelGGL(k_head_dw, dim3(wgs, nb), dim3(256), 0, stream, rpn_out, dcls, dbox, ddir, na, P, tpw, ntiles, w->part, vec);
+    }
+    hipLaunchKernelGGL(k_head_dw_reduce, dim3(pp_div_up(10 * na * (HB_C + 1), 256)), dim3(256), 0, stream, w->part, nb * wgs, na, rows, dw_cls,
+                       dw_box, dw_dir, db_cls, db_box, db_dir);
     if (dx) {
         int rc = refresh_w_nat(ctx, w);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_head_dx, dim3(wgs, nb), dim3(256), 0, stream, w->w_nat, dcls, dbox, ddir, na, P, tpw, ntiles, dx, vec);
+        if (wide) {
+            const size_t lds = (size_t)rows * DX_LD * sizeof(float);
+            if (!w->dx_wide_lds) { // the attribute belongs to the device, not to this context: the size at the cap serves every context
+                PP_HIP(hipFuncSetAttribute((const void*)k_head_dx_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)(16 * DXW_KB * DX_LD * sizeof(float))));
+                w->dx_wide_lds = true;
+            }
+            hipLaunchKernelGGL(k_head_dx_wide, dim3(wgs * DXW_GROUPS, nb), dim3(256), lds, stream, w->w_nat, dcls, dbox, ddir, na, P, tpw, ntiles,
+                               rows, dx, vec);
+        } else {
+            hipLaunchKernelGGL(k_head_dx, dim3(wgs, nb), dim3(256), 0, stream, w->w_nat, dcls, dbox, ddir, na, P, tpw, ntiles, dx, vec);
+        }
     }
     PP_HIP(hipGetLastError());
     return 0;
@@ -524,15 +748,13 @@ int head_update(pp_ctx* ctx, const char* who_, int mode, const float* w_cls, con
         hipLaunchKernelGGL(k_gather3, dim3(pp_div_up(nbp, 256)), dim3(256), 0, stream, w->img.bias_perm, w->bpmap, nbp, b_cls, b_box, b_dir, na,
                            7 * na, 2 * na);
     // the natural-order copy pp_head_backward's dX product reads
-    if (10 * na <= HB_ROWS) {
-        if (w->w_gen != ctx->commit_gen) {
-            PP_HIP(hipMemsetAsync(w->w_nat, 0, (size_t)HB_ROWS * HB_C * sizeof(float), stream));
-            w->w_gen = ctx->commit_gen;
-        }
-        PP_HIP(hipMemcpyAsync(w->w_nat, w_cls, (size_t)na * HB_C * 4, hipMemcpyDeviceToDevice, stream));
-        PP_HIP(hipMemcpyAsync(w->w_nat + (size_t)na * HB_C, w_box, (size_t)7 * na * HB_C * 4, hipMemcpyDeviceToDevice, stream));
-        PP_HIP(hipMemcpyAsync(w->w_nat + (size_t)8 * na * HB_C, w_dir, (size_t)2 * na * HB_C * 4, hipMemcpyDeviceToDevice, stream));
+    if (w->w_gen != ctx->commit_gen) {
+        PP_HIP(hipMemsetAsync(w->w_nat, 0, (size_t)rows_padded(na) * HB_C * sizeof(float), stream));
+        w->w_gen = ctx->commit_gen;
     }
+    PP_HIP(hipMemcpyAsync(w->w_nat, w_cls, (size_t)na * HB_C * 4, hipMemcpyDeviceToDevice, stream));
+    PP_HIP(hipMemcpyAsync(w->w_nat + (size_t)na * HB_C, w_box, (size_t)7 * na * HB_C * 4, hipMemcpyDeviceToDevice, stream));
+    PP_HIP(hipMemcpyAsync(w->w_nat + (size_t)8 * na * HB_C, w_dir, (size_t)2 * na * HB_C * 4, hipMemcpyDeviceToDevice, stream));
     PP_HIP(hipGetLastError());
     return 0;
 }

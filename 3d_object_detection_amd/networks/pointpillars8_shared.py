@@ -11,6 +11,10 @@ depths from the head to the front, and each scope trains what the one before it 
     "rpn"     + the ten convolutions of blocks 1 and 2: the whole RPN (RPN_KEYS, the reference's state_dict order, 25 tensors)
     "all"     + the pillar feature net (PFN_KEYS; ALL_KEYS = the 28 tensors net.parameters() yields in the reference)
 
+Every shipped configuration trains (eight_20cm, ntusl_10cm, nuscene and nuscene_10class), and so does any class_table with at
+most 24 anchors per location: the head backward takes 1 .. 24 (pp_head_backward raises above that), everything behind
+dL/d(rpn_out) does not depend on the count.
+
 Everything in front of the trained groups is frozen.  A training forward records up to three autograd Functions, each a thin
 wrapper of engine calls: _HeadFunction (pp_head / pp_head_backward, csrc/train.hip); _RpnFunction, whose forward runs the backbone
 with the taps its depth needs and whose backward (_rpn_backward) walks RPN_TABLE from the upsamplers (pp_neck_backward, csrc/neck_train.hip)
@@ -459,8 +463,8 @@ class PointPillars:
         self._pfn_nbt = None         # num_batches_tracked when the loaded dict carried it
         self.profile_stages = True  # the reference synchronises after every stage (:365-374)
         self.pfn_time, self.rpn_time, self.scatter_time, self.heads_time = 0.0, 0.0, 0.0, 0.0
-        # like nn.Module construction, start from random initial weights
-        self.load_state_dict(init_state_dict(0, norm=self._norm))
+        # like nn.Module construction, start from random initial weights (the head as wide as the config's anchors per location)
+        self.load_state_dict(init_state_dict(0, norm=self._norm, num_anchor_per_loc=self._eng.num_anchor_per_loc))
 
     # nn.Module-style surface used by train.py:196-205
     def to(self, device):

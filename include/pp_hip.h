@@ -283,7 +283,9 @@ int pp_target_loss_grad(pp_ctx* ctx, const float* cls, const float* box, const f
  * a * 2 + k of conv_dir), summed over the nb frames, and dx f32[nb][320][H][W] = dL/d(rpn_out) (NULL: skipped).  fp32-input MFMA, fp32
  * accumulation.  Each workgroup owns a pixel range of one frame; its [10 na][320] partial is summed with the others in a fixed order,
  * so the result depends on nb (the ranges do) only within fp32 summation error.  dx uses the committed head weights, or those of the
- * last pp_update_head_weights.  At most 9 anchors per location.  PP_E_STATE before pp_commit_weights. */
+ * last pp_update_head_weights.  1 .. 24 anchors per location (24 = PP_MAX_CLASSES x 1 size x 2 rotations; PP_E_ARG above): up to 9 the
+ * 96-row kernels, from 10 on the row-blocked dW and channel-blocked dX kernels over 10 na rows rounded up to 16, same contract.
+ * PP_E_STATE before pp_commit_weights. */
 int pp_head_backward(pp_ctx* ctx, const float* rpn_out, const float* dcls, const float* dbox, const float* ddir, int nb, float* dw_cls,
                      float* dw_box, float* dw_dir, float* db_cls, float* db_box, float* db_dir, float* dx, void* stream);
 /* After an optimizer step: six DEVICE tensors in state_dict layout (heads.conv_{cls,box,dir}.{weight,bias}: [na][320], [na], [7 na][320],

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Kernel time of head-only training (csrc/train.hip) on eight_20cm at nb = 1, 8, 32: HIP events around back-to-back C calls whose
-arguments are built beforehand, next to each call's floor -- the larger of its algorithmic HBM bytes / 8 TB/s and, for the head
+"""Kernel time of head-only training (csrc/train.hip) on eight_20cm (or --config NAME) at nb = 1, 8, 32: HIP events around
+back-to-back C calls whose arguments are built beforehand, next to each call's floor -- the larger of its algorithmic HBM bytes / 8 TB/s and, for the head
 backward, its executed MFMA flops / 157.3 TF (the constants bench.py uses).
 
-    python tools/headtrain_probe.py [--frames 1,8,32] [--reps 10]
+    python tools/headtrain_probe.py [--frames 1,8,32] [--reps 10] [--config nuscene_10class]
     rocprofv3 --kernel-trace --stats -d OUT -o headtrain -- python tools/headtrain_probe.py --frames 8     (per-kernel split: k_count_pos,
-                                                             k_loss_grad, k_head_dw, k_head_dw_reduce, k_head_dx, k_gather3)
-Also timed in the same run: the same head backward in stock PyTorch (conv2d with 90 output channels on [nb,320,H,W], .backward()),
+                                                             k_loss_grad, k_head_dw, k_head_dw_reduce, k_head_dx, k_gather3; above 9
+                                                             anchors per location k_head_dw_wide and k_head_dx_wide)
+Also timed in the same run: the same head backward in stock PyTorch (conv2d with 10 na output channels on [nb,320,H,W], .backward()),
 and one whole fine-tuning step at nb = 8 (frozen forward, loss, backward, SGD step, weight upload).  Prints one JSON line."""
 import argparse
 import ctypes
@@ -28,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", default="1,8,32")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--config", default="eight_20cm", help="a shipped configuration, e.g. nuscene_10class (20 anchors per location)")
     ap.add_argument("--no-torch", action="store_true", help="skip the stock PyTorch yardstick and the whole-step line")
     a = ap.parse_args()
     frames = [int(v) for v in a.frames.split(",")]
@@ -37,13 +39,13 @@ def main():
     shared = importlib.import_module("3d_object_detection_amd.networks.pointpillars8_shared")
     vgm = importlib.import_module("3d_object_detection_amd.framework.voxel_generator")
     lgm = importlib.import_module("3d_object_detection_amd.framework.loss_generator")
-    cfg = synth.load_config("eight_20cm")
+    cfg = synth.load_config(a.config)
     cfg["device"] = torch.device("cuda:0")
     cfg["max_batch"] = max(frames + [8])
     vgm.VoxelGenerator(cfg)
     net = shared.PointPillars(cfg)
-    net.load_state_dict(synth.seeded_state_dict(0, cls_bias=-3.0))
     eng = net._eng
+    net.load_state_dict(synth.seeded_state_dict(0, cls_bias=-3.0, num_anchor_per_loc=eng.num_anchor_per_loc))
     d, A, H, W, na = eng.device, eng.A, eng.H, eng.W, eng.num_anchor_per_loc
     P = H * W
     lib, ctx, st = eng.lib, eng.ctx, torch.cuda.current_stream().cuda_stream
@@ -63,6 +65,11 @@ def main():
         return s.elapsed_time(e) / reps
 
     out = {"anchors": A, "map": [H, W], "rows": []}
+    if a.config != "eight_20cm":
+        out["config"] = a.config
+    # GEMM rows the kernels execute, how often the dW kernel reads X (once per row block) and the dX kernel dY (once per channel group)
+    rows = 96 if na <= 9 else (10 * na + 15) // 16 * 16
+    x_reads, dy_reads = (1, 1) if na <= 9 else (-(-(rows // 16) // 6), 3)
     for nb in frames:
         x = torch.relu(torch.randn((nb, 320, H, W), device=d, generator=gen))
         cls = torch.randn((nb, A), device=d, generator=gen) * 2 - 3
@@ -86,8 +93,8 @@ def main():
         # floors: 29 floats in and out + the label re-read of the count pass per anchor; X read once per product, dY twice, dX written
         n = nb * A
         row["loss_grad_floor_ms"] = (29 * 4 + 4) * n / HBM_BS * 1e3
-        by = nb * P * 4 * (320 * 2 + 10 * na * 2 + 320)
-        fl = 2 * 2.0 * 96 * 320 * nb * P  # executed: 96 padded rows, two products
+        by = nb * P * 4 * (320 * (1 + x_reads) + 10 * na * (1 + dy_reads) + 320)
+        fl = 2 * 2.0 * rows * 320 * nb * P  # executed: the padded rows, two products
         row["head_backward_floor_ms"] = max(by / HBM_BS, fl / MFMA_FS) * 1e3
         row["head_backward_floor_bound"] = "bytes" if by / HBM_BS > fl / MFMA_FS else "flops"
         if not a.no_torch:
@@ -111,7 +118,7 @@ def main():
         # one whole fine-tuning step at nb = 8: frozen forward of 8 clouds (pp_infer_batch keeps the rpn outputs), head, loss, backward,
         # SGD step, weight upload at the next forward
         nb = 8
-        pts = [torch.from_numpy(synth.lidar_cloud("eight_20cm", seed=300 + i)).to(d) for i in range(nb)]
+        pts = [torch.from_numpy(synth.lidar_cloud(a.config, seed=300 + i)).to(d) for i in range(nb)]
         u = torch.rand((nb, A), device=d, generator=gen)
         ex = {"labels": torch.where(u < 0.002, 1, torch.where(u < 0.3, 0, -1)).to(torch.int32),
               "bbox_targets": torch.randn((nb, A, 7), device=d, generator=gen) * 0.3,
